@@ -3,21 +3,29 @@
 
     python bench.py --gpus N --steps K --warmup W                  (N > 1 without a launcher: starts the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py ... --full                                     (the records beside the headline as well)
+    python bench.py ... --dump-outputs DIR                         (the timed call's predictions as DIR/*.npy)
 
 Headline (BASELINE.json configs[1], "c2"): reactions/sec of greedy-speculative decoding at bs=32, draft_len=10, n_drafts=3,
 max_len=200 on USPTO-MIT-shaped synthetic SMILES.  A "step" is one given batch of 32 reactions through the generator (encoder
 + the whole verify loop); the K given batches go through ``generate_many(reorder=True)`` (slot pools, the reference's loop
 replayed per given batch: outputs and counters of per-batch ``generate``).  Inputs are resident in HBM before the timed region;
 every rank decodes its own shard of the synthetic test set (weak scaling, no data-path collective); weights are broadcast once
-from rank 0 and predictions gathered once at the end over RCCL.  The timed region is repeated (default 5 times, each bracketed
-by barrier + synchronize, MAX over ranks) and the MEDIAN is the value (SURVEY.md §8(d): "5 timed repeats, median + min/max";
-the reference's scripts repeat every setting, scripts/product_prediction.sh:160-193).  Rank 0 prints ONE JSON line, which at
-N = 1 also carries the sub-records "c3" / "c4" (BASELINE configs[2] / configs[3]: beam-search speculative, batch pools), the
-strings-in -> CSV-out pipeline, the roofline of the dominant kernel family and the CPU baseline.
+from rank 0 and predictions gathered once at the end over RCCL.  Each run of the timed region is bracketed by barrier +
+synchronize, MAX over ranks.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, warm-up (the W batches one at a time, then two untimed runs of the
+timed call over the K batches: see measure_c2), ONE run of the timed region (K steps; `ms_per_step` = its wall clock / K),
+the outputs (--dump-outputs) and the line.  --full adds everything else: the timed region repeated (default 5 times) with
+the MEDIAN as the value ("5 timed repeats, median + min/max"; the reference's scripts repeat every
+setting, scripts/product_prediction.sh:160-193), the legs beside the headline (N = 1 drafts, one batch at a time, the
+Lightning surface), the strings-in -> CSV-out pipeline, the roofline of the dominant kernel family, the CPU baseline with
+its parity check and, at N = 1, the sub-records "c3" / "c4" (BASELINE configs[2] / configs[3]: beam-search speculative,
+batch pools).
 
 Weights: there is no checkpoint offline, so full-size (d=256, 8 heads, FFN 2048; 4+4 and 6+6 layers) models are trained on the
-synthetic task by tools/train_synth.py for a fixed step budget (cached under /tmp, or shipped as .weights_cache/).  That is
-set-up, outside every timed region.
+synthetic task by tools/train_synth.py for a fixed step budget and cached (under /tmp and in the git-ignored .weights_cache/;
+__graft_entry__.build() makes the 4+4 cache when a GPU is visible).  That is set-up, outside every timed region.
 """
 from __future__ import annotations
 
@@ -38,6 +46,8 @@ import torch  # noqa: E402
 
 PEAK_F32_MATRIX_TFLOPS = 157.3   # /opt/skills/guides/MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dense peak
 PEAK_HBM_GBS = 8000.0            # same guide: HBM3E 8 TB/s spec
+TRAIN_STEPS = int(os.environ.get("TTX_TRAIN_STEPS", "1500"))   # training budget of the synthetic-task weights
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: at most this much in all; above it a fixed, seeded sample of rows
 BASELINE_REACTIONS_PER_S = 47.97  # BASELINE.md §1, bs=32 D=10 N=3 (reference's own run, unstated GPU)
 
 # BASELINE.json configs[2] / configs[3]: generator settings of the reference's own grid optimum for that batch size
@@ -58,26 +68,34 @@ def parse():
     ap.add_argument("--config", choices=("c2", "c3", "c4"), default="c2",
                     help="headline: BASELINE.json configs[1] (greedy speculative bs=32; default — c3 and c4 are then sub-records), "
                          "configs[2] (MIT beam speculative n_best=5 bs=4 N=7) or configs[3] (50K 6+6 beam speculative n_best=10 bs=8 N=2)")
-    ap.add_argument("--steps", type=int, default=None, help="timed batches (default 256 for c2, 64 / 32 for c3 / c4)")
+    ap.add_argument("--steps", type=int, default=None, help="timed batches = steps (default 256 for c2, 64 / 32 for c3 / c4)")
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=None, help="repetitions of the timed region; the median is reported (default 5)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="repetitions of the timed region; the median is reported (default 1, with --full 5)")
     ap.add_argument("--batch-size", type=int, default=None)
     ap.add_argument("--draft-len", type=int, default=10)
     ap.add_argument("--n-drafts", type=int, default=None)
     ap.add_argument("--smart", type=int, default=0, help="c3/c4: smart_drafts_mode of the timed run (the other mode is reported beside it)")
     ap.add_argument("--max-len", type=int, default=200)
-    ap.add_argument("--train-steps", type=int, default=int(os.environ.get("TTX_TRAIN_STEPS", "1500")))
+    ap.add_argument("--train-steps", type=int, default=TRAIN_STEPS)
     ap.add_argument("--cpu-batches", type=int, default=None, help="batches of the workload timed on the host cores (default 3 / 1)")
     ap.add_argument("--schedule", choices=("rows", "batches"), default=os.environ.get("TTX_SCHEDULE", "rows"),
                     help="rows: slot pools over the rows / sources of all given batches (exact replay per batch); batches: as given")
     ap.add_argument("--inflight", type=int, default=int(os.environ.get("TTX_INFLIGHT", "8")),
                     help="batches decoded concurrently per GPU (1 = the reference's one-batch-at-a-time loop)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-sub-records", action="store_true", help="c2 headline without the c3 / c4 / string-pipeline sub-records")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline: 5 repeats, the other legs, c3 / c4 sub-records, string pipeline, "
+                         "roofline pass, CPU baseline and parity (a plain run times the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and parity")
+    ap.add_argument("--no-profile", action="store_true", help="--full without the roofline pass")
+    ap.add_argument("--no-sub-records", action="store_true", help="--full: c2 headline without the c3 / c4 / string-pipeline sub-records")
     ap.add_argument("--timed-only", action="store_true",
-                    help="only the timed region of the headline (one repeat unless --repeats is given): for rocprofv3 runs")
+                    help="only the timed region of the headline, even with --full (what a plain run does; kept for rocprofv3 runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the predictions of the timed call's last run as DIR/predictions.npy "
+                         "(float32 token ids [rows, hypotheses, max_len]) and their row indices as DIR/rows.npy (float64)")
     a = ap.parse_args()
+    a.timed_only = a.timed_only or not a.full
     if a.timed_only:
         a.no_profile = a.no_cpu_baseline = a.no_sub_records = True
     if a.repeats is None:
@@ -106,11 +124,13 @@ def log(*a):
 
 
 def get_weights(train_steps: int, device: str, kind: str = "mit", layers: int = 4, info: dict | None = None) -> dict:
-    """Weights for the synthetic task: a cache written by an earlier run on this box (/tmp) or shipped with the snapshot
-    (.weights_cache/, git-ignored), else trained here (set-up, untimed; `info` records which and how long it took)."""
+    """Weights for the synthetic task: a cache written by an earlier run on this machine (/tmp) or by build() / an earlier run of
+    this checkout (.weights_cache/, git-ignored), else trained here and cached in both places (set-up, untimed; `info` records
+    which and how long it took)."""
     path = os.environ.get("TTX_WEIGHTS" if kind == "mit" else "TTX_WEIGHTS_50K") or f"/tmp/ttx_synth_{kind}_{train_steps}.pt"
-    for cand in (path, str(ROOT / ".weights_cache" / f"synth_{kind}_{train_steps}.pt")):   # caches written by earlier runs
-        if os.path.exists(cand) and os.environ.get("TTX_NO_WEIGHTS_CACHE") != "1":             # =1: what a clean clone does
+    local = ROOT / ".weights_cache" / f"synth_{kind}_{train_steps}.pt"
+    for cand in (path, str(local)):                                                            # caches written by earlier runs
+        if os.path.exists(cand) and os.environ.get("TTX_NO_WEIGHTS_CACHE") != "1":             # =1: train here, ignore caches
             if info is not None:
                 info[kind] = {"weights": "cache", "path": cand}
             return torch.load(cand, weights_only=True, map_location="cpu")
@@ -119,14 +139,28 @@ def get_weights(train_steps: int, device: str, kind: str = "mit", layers: int = 
     sd = train(kind, steps=train_steps, n_enc=layers, n_dec=layers, device=device, verbose=os.environ.get("TTX_BENCH_VERBOSE") == "1")
     if info is not None:
         info[kind] = {"weights": "trained in this run", "train_steps": train_steps, "train_seconds": round(time.perf_counter() - t0, 1)}
-    try:
-        torch.save(sd, path)
-        extra = os.environ.get("TTX_SAVE_WEIGHTS")
-        if extra:
-            torch.save(sd, extra)
-    except OSError:
-        pass
+    for out in (path, local, os.environ.get("TTX_SAVE_WEIGHTS")):
+        if out:
+            try:
+                Path(out).parent.mkdir(parents=True, exist_ok=True)
+                torch.save(sd, out)
+            except OSError:
+                pass
     return sd
+
+
+def dump_outputs(out_dir: str, preds: torch.Tensor) -> None:
+    """--dump-outputs: what the timed call returned in its last run, gathered over the ranks — token ids [rows, hypotheses,
+    max_len] in the timed region's row order (a batch on which the reference raises as all-PAD rows, as the line counts it) —
+    as DIR/predictions.npy (float32: the ids are exact) and the index of every written row as DIR/rows.npy (float64).  Above
+    DUMP_LIMIT_BYTES in all a fixed, seeded sample of rows (in order) is written instead of every row."""
+    arr = preds.cpu().numpy()
+    n = arr.shape[0]
+    cap = (DUMP_LIMIT_BYTES - 4096) // (4 * max(1, arr[0].size) + 8)          # 4096: the two .npy headers
+    rows = np.arange(n) if n <= cap else np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "predictions.npy"), arr[rows].astype(np.float32))
+    np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
 
 
 def work(cfg: dict, positions: int, src_tokens: int, steps: int, batches: int, kv_read_positions: int, kv_written_tokens: int) -> dict:
@@ -202,7 +236,7 @@ class Ctx:
 
     def timed(self, fn, repeats: int, local: bool = False):
         """`repeats` runs of fn() -> result, each bracketed by barrier + synchronize on both sides, elapsed = MAX over ranks.
-        Returns (sorted list of seconds, result of the median run, all seconds in run order).  `local`: a measurement only
+        Returns (sorted list of seconds, result of the last run, all seconds in run order).  `local`: a measurement only
         rank 0 makes (the records beside the headline): synchronize only, no collective — the other ranks are not there."""
         runs = []
         for _ in range(max(1, repeats)):
@@ -219,8 +253,7 @@ class Ctx:
             self.barrier()
             runs.append((self.max_over_ranks(time.perf_counter() - t0), res))
         order = sorted(range(len(runs)), key=lambda i: runs[i][0])
-        med = order[(len(order) - 1) // 2]
-        return [runs[i][0] for i in order], runs[med][1], [r[0] for r in runs]
+        return [runs[i][0] for i in order], runs[-1][1], [r[0] for r in runs]
 
 
 def spread(sorted_s: list, units: float) -> dict:
@@ -449,7 +482,11 @@ def measure_c2(ctx: Ctx, a, tta) -> dict:
     g0 = make_gen(model)
     for b in warm:
         g0.generate(b)
-    decode(make_gen(model), timed)          # sessions, workspaces and graphs at the timed region's own layout
+    # two untimed runs of the timed call at the timed region's own layout: the first creates its sessions, workspaces and
+    # graphs; the run after it is still ~3 ms slower than every later one (measured at 20 and at 256 steps), so the second
+    # takes that and a single timed run measures the steady state
+    for _ in range(2):
+        decode(make_gen(model), timed)
     log("warmup done")
     sorted_s, (outs, raised, gen), run_s = ctx.timed(lambda: decode(make_gen(model), timed), a.repeats)
     elapsed = median_seconds(sorted_s)
@@ -464,6 +501,8 @@ def measure_c2(ctx: Ctx, a, tta) -> dict:
         assert gathered.shape[0] == world * preds.shape[0]
         if os.environ.get("TTX_DUMP_PREDICTIONS"):        # tests/test_gpu_dist.py compares them with a single-process decode
             np.save(os.environ["TTX_DUMP_PREDICTIONS"], gathered.cpu().numpy())
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, gathered)
     counted = tta.dist.sum_counters({"reactions": sum(int(timed[i].shape[0]) for i in range(len(timed)) if i not in raised),
                                      "raised": len(raised)}, dev, dist)
     n_reactions = int(counted["reactions"])
@@ -642,7 +681,8 @@ def measure_beam(ctx: Ctx, a, tta, name: str, steps: int, warmup: int, full: boo
     g0 = make_gen(model, smart)
     for b in warm:
         g0.generate(b)
-    run(make_gen(model, smart), timed, a.inflight, pooled)              # pools, workspaces and graphs at the timed layout
+    for _ in range(2):                                                  # pools, workspaces and graphs at the timed layout
+        run(make_gen(model, smart), timed, a.inflight, pooled)          # (twice: see measure_c2)
     log(name, "warmup done")
     sorted_s, (outs, gen), run_s = ctx.timed(lambda: run(make_gen(model, smart), timed, a.inflight, pooled), a.repeats)
     elapsed = median_seconds(sorted_s)
@@ -651,6 +691,8 @@ def measure_beam(ctx: Ctx, a, tta, name: str, steps: int, warmup: int, full: boo
     gathered = tta.dist.gather_predictions(flat, world * flat.shape[0], dist)
     if rank == 0:
         assert gathered.shape[0] == world * flat.shape[0]
+        if a.dump_outputs and a.config == name:          # the headline's outputs only, not a sub-record's
+            dump_outputs(a.dump_outputs, gathered)
     counted = tta.dist.sum_counters({"reactions": sum(int(b.shape[0]) for b in timed)}, dev, dist)
     n_reactions = int(counted["reactions"])
     value = n_reactions / elapsed

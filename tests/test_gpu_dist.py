@@ -97,10 +97,11 @@ def test_two_rank_bench_data_path_equals_single_process(tmp_path):
                MASTER_PORT=str(_free_port()))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    # the driver's form of the command (no --timed-only): after the headline rank 0 goes on alone with the records beside it
-    # (N = 1 drafts, one batch at a time, the surface, the roofline pass) while rank 1 waits at the final barrier — none of those
-    # may use a collective (round 3 shipped one for a while: "connection closed by peer" at N > 1)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline"]
+    # --full: after the headline rank 0 goes on alone with the records beside it (N = 1 drafts, one batch at a time, the
+    # surface, the roofline pass) while rank 1 waits at the final barrier — none of those may use a collective (round 3 shipped
+    # one for a while: "connection closed by peer" at N > 1)
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--steps", str(steps), "--warmup", str(warmup), "--full",
+           "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.strip().split("\n") if l.startswith("{")][-1])

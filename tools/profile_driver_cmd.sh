@@ -2,8 +2,8 @@
 # rocprofv3 evidence for one bench.py configuration: kernel trace of the timed-only run, kernel trace of the run WITH bench.py's
 # roofline pass, and the two PMC passes (FETCH_SIZE, WRITE_SIZE) of the latter.  The profiled command is the driver's, minus the
 # legs that would follow the roofline pass (tools/roofline_from_trace.py finds the pass as the last GEMM launches of the process):
-#   c2:  python3 bench.py --gpus 1 --steps STEPS --warmup WARMUP --no-cpu-baseline --no-sub-records
-#   c3:  python3 bench.py --gpus 1 --config c3 --no-cpu-baseline          (c4 likewise)
+#   c2:  python3 bench.py --gpus 1 --steps STEPS --warmup WARMUP --full --no-cpu-baseline --no-sub-records
+#   c3:  python3 bench.py --gpus 1 --config c3 --full --no-cpu-baseline   (c4 likewise)
 # Run on the GPU box from the repo root:  bash tools/profile_driver_cmd.sh CONFIG [STEPS] [WARMUP] [TAG]
 # Raw output goes to gpurun_out/<TAG>_*; the summaries land in gpurun_out/<TAG>_summary/ (copy them to profiles/).
 set -o pipefail
@@ -14,15 +14,15 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 if [ "$CFG" = "c2" ]; then
   ARGS="--gpus 1 --steps $STEPS --warmup $WARM"
-  FULL="$ARGS --no-cpu-baseline --no-sub-records"
+  FULL="$ARGS --full --no-cpu-baseline --no-sub-records"
   KEY="{\"schedule\": \"rows\", \"inflight\": 8, \"batch_size\": 32, \"n_drafts\": 3, \"draft_len\": 10, \"max_len\": 200}"
 elif [ "$CFG" = "c3" ]; then
   ARGS="--gpus 1 --config c3"
-  FULL="$ARGS --no-cpu-baseline"
+  FULL="$ARGS --full --no-cpu-baseline"
   KEY="{\"schedule\": \"rows\", \"inflight\": 8, \"batch_size\": 4, \"n_drafts\": 7, \"draft_len\": 10, \"max_len\": 200, \"smart\": 0}"
 else
   ARGS="--gpus 1 --config c4"
-  FULL="$ARGS --no-cpu-baseline"
+  FULL="$ARGS --full --no-cpu-baseline"
   KEY="{\"schedule\": \"rows\", \"inflight\": 8, \"batch_size\": 8, \"n_drafts\": 2, \"draft_len\": 10, \"max_len\": 200, \"smart\": 0}"
 fi
 echo "[1/4] kernel trace, timed-only"
