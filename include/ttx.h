@@ -100,6 +100,26 @@ int ttx_decode_tgt(ttx_session* s, const int64_t* d_tgt, int R, int Lt, const fl
 int ttx_forward(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_tgt, int Lt,
                 float* d_logits, void* stream);
 
+/* Teacher-forced evaluation: VanillaEncoderDecoderTransformerLightning.validation_step / test_step
+ * (src/model/lightning_model.py:174-207) with the metrics of src/utils/metrics.py, quirks included:
+ *   loss      nn.CrossEntropyLoss(reduction="mean") over ALL B*(Lt-1) positions (PAD targets count: no ignore_index);
+ *   token_acc mean of argmax == target over all positions;
+ *   seq_acc   calc_sequence_acc: per row, the positions p with target[(p+1) mod T] == eos in ascending order are paired with
+ *             the EOS positions q in ascending order; a pair is a hit when cumsum(argmax == target)[p] == q; hits / pairs
+ *             over the batch, NaN when no target holds an EOS.
+ * Targets are read off d_tgt int64 [B,Lt] at column 1 (tgt[:, 1:]); the argmax keeps the first maximum (torch.argmax).
+ * d_pred int64 [B,Lt-1] and d_nll fp32 [B,Lt-1] (per-position cross-entropy) are optional outputs (NULL: session scratch);
+ * d_out3 fp32 [3] = {loss, token_acc, seq_acc}, written on the device (nothing is synchronised).  Vocabulary <= 1024,
+ * B*(Lt-1) < 2^24.  Target ids outside [0, V) are the caller's to reject (the kernels read them as id 0).  Two calls on the
+ * same inputs give bit-identical results.
+ * ttx_token_metrics: the metric stage alone over caller-provided logits fp32 [B,Lt-1,V].
+ * ttx_teacher_forced_eval: ttx_forward(src, tgt[:, :-1]) followed by the metric stage; d_logits [B,Lt-1,V] or NULL (the logits
+ * then stay in session scratch). */
+int ttx_token_metrics(ttx_session* s, const float* d_logits, const int64_t* d_tgt, int B, int Lt, int V, int eos, int64_t* d_pred,
+                      float* d_nll, float* d_out3, void* stream);
+int ttx_teacher_forced_eval(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_tgt, int Lt, int eos,
+                            float* d_logits, int64_t* d_pred, float* d_nll, float* d_out3, void* stream);
+
 /* Draft maker: make_drafts (src/utils/drafting.py:5-67) on the device.  d_src int64 [B,L];
  * d_drafts int64 [B,n_drafts,D] out with D = clamp(draft_len, min_draft_len, max_draft_len). */
 int ttx_make_drafts(ttx_session* s, const int64_t* d_src, int B, int L, int draft_len, int n_drafts,

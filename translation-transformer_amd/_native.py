@@ -16,8 +16,8 @@ INCLUDE = PKG_DIR.parent / "include"
 LIB_PATH = PKG_DIR / "libttx_hip.so"
 # translation units (compiled in parallel, linked into one shared library) and the headers every one of them depends on
 UNITS = [CSRC / "ttx_api.hip", CSRC / "ttx_gemm.hip", CSRC / "ttx_attn.hip"]
-HEADERS = [CSRC / "ttx_internal.h", CSRC / "ttx_common.hip.h", CSRC / "ttx_loop_kernels.hip.h", CSRC / "ttx_select.h",
-           CSRC / "ttx_tokenizer.h", INCLUDE / "ttx.h"]
+HEADERS = [CSRC / "ttx_internal.h", CSRC / "ttx_common.hip.h", CSRC / "ttx_loop_kernels.hip.h", CSRC / "ttx_metrics.hip.h",
+           CSRC / "ttx_select.h", CSRC / "ttx_tokenizer.h", INCLUDE / "ttx.h"]
 SOURCES = UNITS + HEADERS
 OBJ_DIR = CSRC / "build"
 
@@ -98,6 +98,8 @@ SYMBOLS = {
     "ttx_encode_src": (C.c_int, [_VP, _VP, _I, _I, _VP, _VP]),
     "ttx_decode_tgt": (C.c_int, [_VP, _VP, _I, _I, _VP, _VP, _VP, _I, _I, _VP, _VP]),
     "ttx_forward": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _VP, _VP]),
+    "ttx_token_metrics": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
+    "ttx_teacher_forced_eval": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "ttx_make_drafts": (C.c_int, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP]),
     "ttx_greedy_speculative_generate": (C.c_int, [_VP, _VP, _I, _I, C.POINTER(GenParams), _VP, C.POINTER(GenStats), _VP]),
     "ttx_greedy_generate": (C.c_int, [_VP, _VP, _I, _I, C.POINTER(GenParams), _VP, C.POINTER(GenStats), _VP]),

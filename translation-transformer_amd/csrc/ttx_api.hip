@@ -4,6 +4,7 @@
 // No CPU fallback exists anywhere in this library: without a gfx950 device every entry point fails.
 #include "ttx_internal.h"
 #include "ttx_loop_kernels.hip.h"
+#include "ttx_metrics.hip.h"
 #include "ttx_tokenizer.h"
 
 #include <algorithm>
@@ -523,6 +524,85 @@ extern "C" int ttx_forward(ttx_session* s, const int64_t* d_src, int B, int Ls, 
                      s->mem_pad_tmp.as<uint8_t>(), B * Ls);
   HIP_TRY(hipGetLastError());
   return ttx_decode_tgt(s, d_tgt, B, Lt, s->memory.as<float>(), s->mem_pad_tmp.as<uint8_t>(), nullptr, B, Ls, d_logits, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Teacher-forced evaluation (lightning_model.py:174-207, metrics.py): csrc/ttx_metrics.hip.h.
+static int session_required(const char* fn) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
+    return fail(TTX_ERR_NO_DEVICE, "no HIP device visible; libttx_hip has no CPU fallback");
+  return fail(TTX_ERR_INVALID, std::string("bad argument to ") + fn + ": null session");
+}
+
+static int check_metric_shapes(const ttx_session* s, int B, int Lt, int V, const char* fn) {
+  if (B <= 0 || Lt < 2 || V <= 0) return fail(TTX_ERR_INVALID, std::string("bad argument to ") + fn + ": B > 0, Lt >= 2, V > 0");
+  if (V > MET_MAX_V) return fail(TTX_ERR_INVALID, std::string(fn) + ": vocabulary larger than 1024");
+  if ((long long)B * (Lt - 1) >= (1LL << 24))      // token / sequence hit counts stay exact in fp32, as torch's float mean has them
+    return fail(TTX_ERR_INVALID, std::string(fn) + ": more than 2^24 positions in one call");
+  if (Lt - 1 > s->m->cfg.max_positions) return fail(TTX_ERR_INVALID, std::string(fn) + ": target longer than the positional table");
+  return TTX_OK;
+}
+
+static int launch_metrics(ttx_session* s, hipStream_t st, const float* logits, const int64_t* tgt, int B, int Lt, int V, int eos,
+                          int64_t* pred, float* nll, float* out3) {
+  const int M = B * (Lt - 1);
+  if (!pred) {
+    TTX_TRY(ensure(s->ev_pred, (size_t)M * sizeof(int64_t), st));
+    pred = s->ev_pred.as<int64_t>();
+  }
+  if (!nll) {
+    TTX_TRY(ensure(s->ev_nll, (size_t)M * sizeof(float), st));
+    nll = s->ev_nll.as<float>();
+  }
+  if (V % 4 == 0 && reinterpret_cast<uintptr_t>(logits) % 16 == 0)
+    hipLaunchKernelGGL(k_token_metrics<true>, dim3(cdiv(M, 4)), dim3(256), 0, st, logits, tgt, Lt, M, V, pred, nll);
+  else
+    hipLaunchKernelGGL(k_token_metrics<false>, dim3(cdiv(M, 4)), dim3(256), 0, st, logits, tgt, Lt, M, V, pred, nll);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_batch_metrics, dim3(1), dim3(MET_BATCH_THREADS), 0, st, pred, nll, tgt, B, Lt, eos, out3);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+extern "C" int ttx_token_metrics(ttx_session* s, const float* d_logits, const int64_t* d_tgt, int B, int Lt, int V, int eos,
+                                 int64_t* d_pred, float* d_nll, float* d_out3, void* stream) {
+  if (!s) return session_required("ttx_token_metrics");
+  if (!d_logits || !d_tgt || !d_out3) return fail(TTX_ERR_INVALID, "bad argument to ttx_token_metrics");
+  TTX_TRY(check_metric_shapes(s, B, Lt, V, "ttx_token_metrics"));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->m->device));
+  return launch_metrics(s, st, d_logits, d_tgt, B, Lt, V, eos, d_pred, d_nll, d_out3);
+}
+
+extern "C" int ttx_teacher_forced_eval(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_tgt, int Lt, int eos,
+                                       float* d_logits, int64_t* d_pred, float* d_nll, float* d_out3, void* stream) {
+  if (!s) return session_required("ttx_teacher_forced_eval");
+  if (!d_src || !d_tgt || !d_out3 || Ls <= 0) return fail(TTX_ERR_INVALID, "bad argument to ttx_teacher_forced_eval");
+  const ttx_config& c = s->m->cfg;
+  TTX_TRY(check_metric_shapes(s, B, Lt, c.vocab_size, "ttx_teacher_forced_eval"));
+  if (Ls > c.max_positions) return fail(TTX_ERR_INVALID, "source longer than the positional table");
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->m->device));
+  const int T = Lt - 1, V = c.vocab_size, d = c.embedding_dim;
+  if (!d_logits) {
+    TTX_TRY(ensure(s->ev_logits, (size_t)B * T * V * sizeof(float), st));
+    d_logits = s->ev_logits.as<float>();
+  }
+  // ttx_forward(src, tgt[:, :-1]) without a sliced copy: the decoder's int32 tokens are read off the [B, Lt] rows directly
+  TTX_TRY(ensure(s->memory, (size_t)B * Ls * d * 4, st));
+  TTX_TRY(ensure(s->mem_pad_tmp, (size_t)B * Ls, st));
+  TTX_TRY(ttx_encode_src(s, d_src, B, Ls, s->memory.as<float>(), stream));
+  hipLaunchKernelGGL(k_invert_mask, dim3(cdiv(B * Ls, 256)), dim3(256), 0, st, s->src_valid.as<uint8_t>(),
+                     s->mem_pad_tmp.as<uint8_t>(), B * Ls);
+  HIP_TRY(hipGetLastError());
+  TTX_TRY(ensure(s->tok_tgt, (size_t)B * T * 4, st));
+  hipLaunchKernelGGL(k_prepare_tokens_2d, dim3(cdiv(B * T, 256)), dim3(256), 0, st, d_tgt, Lt, s->tok_tgt.as<int>(),
+                     (uint8_t*)nullptr, B, T, c.pad_token);
+  HIP_TRY(hipGetLastError());
+  TTX_TRY(run_decoder_full(s, st, s->tok_tgt.as<int>(), B, T, s->memory.as<float>(), s->mem_pad_tmp.as<uint8_t>(), nullptr, B, Ls,
+                           d_logits));
+  return launch_metrics(s, st, d_logits, d_tgt, B, Lt, V, eos, d_pred, d_nll, d_out3);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -411,7 +411,7 @@ __global__ void k_prepare_tokens_2d(const int64_t* in, int ld_in, int* out, uint
     const int r = i / cols, c = i - r * cols;
     const int tk = (int)in[(size_t)r * ld_in + c];
     out[i] = tk;
-    valid[i] = (tk != pad) ? 1 : 0;
+    if (valid) valid[i] = (tk != pad) ? 1 : 0;
   }
 }
 

@@ -3,16 +3,17 @@
     VanillaEncoderDecoderTransformerLightning   <- src/model/lightning_model.py:22-243
 
 Same ``init_args`` (lightning_model.py:24-51), same ``predict_step`` / ``on_predict_start`` /
-``on_predict_end`` hooks and JSON report keys, same attributes the PredictionWriter callback reads
-(``tgt_tokenizer``; src/callbacks.py:49-64), same checkpoint key layout (``model.`` + the names of
-SURVEY §8(b) B6) — so ``main.py predict -c cfg.yaml --ckpt_path ...`` runs unchanged once the YAML's
-``model.class_path`` points here.  Training hooks are out of scope and raise.
+``on_predict_end`` hooks and JSON report keys, same ``validation_step`` / ``test_step`` (teacher-forced loss, token and
+sequence accuracy logged under the reference's names and flags; the outputs DecodingCallback reads), same attributes the
+PredictionWriter callback reads (``tgt_tokenizer``; src/callbacks.py:49-64), same checkpoint key layout (``model.`` + the
+names of SURVEY §8(b) B6) — so ``main.py predict|validate|test -c cfg.yaml --ckpt_path ...`` runs unchanged once the YAML's
+``model.class_path`` points here.  Training is out of scope: ``training_step`` raises.
 
 ``self.model`` is a parameter container with the reference's module names (so Lightning's checkpoint loading
 fills it); its torch ``forward`` is never called — all arithmetic runs in libttx_hip.so through the
-NativeTransformer built from those parameters when prediction starts.  The module imports without
-pytorch_lightning (absent in the build container); then a minimal stand-in base class is used and
-``run_predict`` below drives the hooks.
+NativeTransformer built from those parameters when prediction starts (or at the first validation / test step).  The
+module imports without pytorch_lightning (absent in the build container); then a minimal stand-in base class is used and
+``run_predict`` / ``run_evaluate`` below drive the hooks.
 """
 from __future__ import annotations
 
@@ -44,6 +45,13 @@ except Exception:  # pragma: no cover
             frame = inspect.currentframe().f_back
             args = {k: v for k, v in frame.f_locals.items() if k not in ("self", "__class__") and k not in ignore}
             self.hparams = SimpleNamespace(**args)
+
+        def log(self, name, value, batch_size=None, **flags):
+            """Records what Lightning's ``self.log`` would reduce: the value (kept on the device), the batch size and the
+            flags.  ``batch_size`` defaults to the one run_evaluate set for the current batch, as Lightning infers it."""
+            if batch_size is None:
+                batch_size = getattr(self, "_current_batch_size", None)
+            self.__dict__.setdefault("logged", []).append((name, value, batch_size, flags))
 
 from .model import NativeTransformer
 from . import decoding as D
@@ -305,11 +313,32 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             with open(h.report_prediction_file, "a") as f:
                 print(text, file=f)
 
+    # -- teacher-forced evaluation (lightning_model.py:174-207) ---------------------------------------
+    def _teacher_forced(self, batch: Any, return_logits: bool):
+        if self.native is None:
+            self.build_native()
+        return self.native.teacher_forced(batch["src_tokens"], batch["tgt_tokens"], return_logits=return_logits,
+                                          eos_token_idx=self.tgt_eos_token_i)
+
+    def _log_metrics(self, stage: str, r, batch_size: int) -> None:
+        # the reference's names and flags; batch_size is what Lightning infers from the batch (its first tensor, src_tokens)
+        self.log(f"{stage}/loss", r.loss, on_step=False, on_epoch=True, prog_bar=True, batch_size=batch_size)
+        self.log(f"{stage}/acc_single_tok", r.token_acc, on_step=False, on_epoch=True, prog_bar=False, batch_size=batch_size)
+        self.log(f"{stage}/acc_sequence", r.seq_acc, on_step=False, on_epoch=True, prog_bar=False, batch_size=batch_size)
+
+    def validation_step(self, batch: Any, batch_idx: int) -> Any:
+        r = self._teacher_forced(batch, return_logits=False)
+        self._log_metrics("val", r, batch["src_tokens"].shape[0])
+        return {"pred_tokens": r.pred_tokens, "target_ahead": batch["tgt_tokens"][:, 1:]}
+
+    def test_step(self, batch: Any, batch_idx: int) -> Any:
+        r = self._teacher_forced(batch, return_logits=True)
+        self._log_metrics("test", r, batch["src_tokens"].shape[0])
+        return {"source_token_ids": batch["src_tokens"], "pred_logits": r.logits, "target_token_ids": batch["tgt_tokens"]}
+
     # -- out of scope ------------------------------------------------------------
     def training_step(self, *a, **k):
         raise NotImplementedError("training is outside the MI355X inference path; train with the reference")
-
-    validation_step = test_step = training_step
 
 
 def run_predict(module: VanillaEncoderDecoderTransformerLightning, batches, writer=None, datamodule=None,
@@ -341,3 +370,48 @@ def run_predict(module: VanillaEncoderDecoderTransformerLightning, batches, writ
         else:
             os.environ["TTX_INFLIGHT"] = old_inflight
     return outs
+
+
+def run_evaluate(module: VanillaEncoderDecoderTransformerLightning, batches, stage: str = "validate", callbacks=()) -> dict:
+    """Stand-in for ``Trainer.validate`` / ``Trainer.test`` when pytorch_lightning is absent: Lightning's hook order
+    (on_{stage}_start, on_{stage}_epoch_start, then per batch on_{stage}_batch_start -> {stage}_step -> the callbacks'
+    on_{stage}_batch_end, then the callbacks' on_{stage}_epoch_end, on_{stage}_epoch_end, on_{stage}_end; hooks the module does
+    not define are skipped) and Lightning's reduction of ``on_epoch=True`` logs: the mean over the batches weighted by each
+    batch's size (``src_tokens.shape[0]``).  Returns {name: epoch value} as floats; metrics the callbacks send to
+    ``trainer.logger.log_metrics`` are kept in ``module.trainer.logger.metrics``."""
+    if stage not in ("validate", "test"):
+        raise ValueError("stage must be 'validate' or 'test'")
+    hook = "validation" if stage == "validate" else "test"
+    step = getattr(module, f"{hook}_step")
+    logger = SimpleNamespace(metrics={})
+    logger.log_metrics = lambda metrics, step=None: logger.metrics.update(metrics)
+    module.trainer = SimpleNamespace(logger=logger, datamodule=None)
+
+    def call(obj, name, *args):
+        fn = getattr(obj, name, None)
+        if fn is not None:
+            fn(*args)
+
+    module.logged = []
+    with torch.inference_mode():
+        call(module, f"on_{hook}_start")
+        call(module, f"on_{hook}_epoch_start")
+        for i, batch in enumerate(batches):
+            module._current_batch_size = int(batch["src_tokens"].shape[0])
+            call(module, f"on_{hook}_batch_start", batch, i)
+            out = step(batch, i)
+            for cb in callbacks:
+                call(cb, f"on_{hook}_batch_end", module.trainer, module, out, batch, i)
+        for cb in callbacks:
+            call(cb, f"on_{hook}_epoch_end", module.trainer, module)
+        call(module, f"on_{hook}_epoch_end")
+        call(module, f"on_{hook}_end")
+    module._current_batch_size = None
+    sums, sizes = {}, {}
+    for name, value, bs, flags in module.logged:
+        if not flags.get("on_epoch", False):
+            continue
+        v = torch.as_tensor(value).detach().double().cpu().item()
+        sums[name] = sums.get(name, 0.0) + v * bs
+        sizes[name] = sizes.get(name, 0) + bs
+    return {name: sums[name] / sizes[name] for name in sums}

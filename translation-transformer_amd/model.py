@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -52,6 +53,16 @@ class _DeviceSpan:
 
     def __init__(self, ptr: int, nbytes: int):
         self.__cuda_array_interface__ = {"shape": (nbytes // 4,), "typestr": "<f4", "data": (ptr, False), "version": 2}
+
+
+class TeacherForced(NamedTuple):
+    """Result of ``NativeTransformer.teacher_forced``: device tensors, nothing copied to the host."""
+    loss: torch.Tensor            # 0-d fp32: nn.CrossEntropyLoss (mean over all B*(Lt-1) positions, PAD targets included)
+    token_acc: torch.Tensor       # 0-d fp32: calc_token_acc
+    seq_acc: torch.Tensor         # 0-d fp32: calc_sequence_acc (NaN when no target holds an EOS)
+    pred_tokens: torch.Tensor     # int64 [B, Lt-1]: argmax of the logits (first maximum)
+    token_nll: torch.Tensor       # fp32 [B, Lt-1]: per-position cross-entropy
+    logits: torch.Tensor | None   # fp32 [B, Lt-1, V] when asked for
 
 
 class NativeTransformer:
@@ -220,6 +231,44 @@ class NativeTransformer:
         return logits
 
     forward = __call__
+
+    # -- teacher-forced evaluation -------------------------------------------------------------
+    def teacher_forced(self, src: torch.Tensor, tgt: torch.Tensor, return_logits: bool = False,
+                       eos_token_idx: int = 2) -> TeacherForced:
+        """What validation_step / test_step compute (src/model/lightning_model.py:174-207, src/utils/metrics.py): the forward
+        pass on ``tgt[:, :-1]`` followed by the loss and accuracy stage against ``tgt[:, 1:]``, all on the device
+        (ttx_teacher_forced_eval).  The logits are materialised only with ``return_logits=True``."""
+        src, tgt = self._tokens(src), self._tokens(tgt)
+        self.check_tokens(src)
+        self.check_tokens(tgt, self.tgt_vocab_size)       # the reference's embedding / cross-entropy raise on these
+        B, Ls = src.shape
+        Lt = tgt.shape[1]
+        if tgt.shape[0] != B or Lt < 2:
+            raise ValueError(f"teacher_forced needs tgt [B, Lt >= 2] for src [B, Ls]; got {tuple(tgt.shape)} for {tuple(src.shape)}")
+        T = Lt - 1
+        logits = (torch.empty((B, T, self.tgt_vocab_size), dtype=torch.float32, device=self.device) if return_logits else None)
+        pred = torch.empty((B, T), dtype=torch.int64, device=self.device)
+        nll = torch.empty((B, T), dtype=torch.float32, device=self.device)
+        out = torch.empty(3, dtype=torch.float32, device=self.device)
+        N.check(self._lib.ttx_teacher_forced_eval(self._session, src.data_ptr(), B, Ls, tgt.data_ptr(), Lt, int(eos_token_idx),
+                                                  logits.data_ptr() if logits is not None else None, pred.data_ptr(),
+                                                  nll.data_ptr(), out.data_ptr(), self._stream()))
+        return TeacherForced(out[0], out[1], out[2], pred, nll, logits)
+
+    def token_metrics(self, logits: torch.Tensor, tgt: torch.Tensor, eos_token_idx: int = 2) -> TeacherForced:
+        """The metric stage alone over given logits [B, Lt-1, V] (ttx_token_metrics)."""
+        x = logits.to(self.device, torch.float32).contiguous()
+        tgt = self._tokens(tgt)
+        B, T, V = x.shape
+        if tgt.shape != (B, T + 1):
+            raise ValueError(f"token_metrics needs tgt [B, T+1] for logits [B, T, V]; got {tuple(tgt.shape)} for {tuple(x.shape)}")
+        self.check_tokens(tgt, V)
+        pred = torch.empty((B, T), dtype=torch.int64, device=self.device)
+        nll = torch.empty((B, T), dtype=torch.float32, device=self.device)
+        out = torch.empty(3, dtype=torch.float32, device=self.device)
+        N.check(self._lib.ttx_token_metrics(self._session, x.data_ptr(), tgt.data_ptr(), B, T + 1, V, int(eos_token_idx),
+                                            pred.data_ptr(), nll.data_ptr(), out.data_ptr(), self._stream()))
+        return TeacherForced(out[0], out[1], out[2], pred, nll, x)
 
     # -- beam-speculative bookkeeping kernels --------------------------------------------------
     def nucleus_mask(self, logits: torch.Tensor, nucleus: float, max_kept: int, fill: float) -> torch.Tensor:
