@@ -352,6 +352,28 @@ int ttx_last_kernel_profile(ttx_session* s, double* gemm_ms, int64_t* gemm_launc
 int ttx_debug_gemm_bench(ttx_session* s, int M, int N, int K, int splits, int variant, int reps, double* us_per_launch,
                          double* max_abs_diff);
 
+/* Test entry points (tests/test_gpu_gemm_kernels.py): ONE launch of the GEMM family / the LayerNorm finisher on DEVICE operands
+ * of the caller.  Y = act(X W^T + bias) with X [m_max, ldx], W [N, ldw], Y [m_max, ldy] (splits == 0), or `splits` raw slabs
+ * Y[s] = X[:, s K/splits ...] W[:, ...]^T at d_y + s * slab_stride (no bias, no activation).  d_m: live row count on the
+ * device (a verify-step launch; rows >= *d_m are neither read into a result nor written) or NULL (all m_max rows).
+ * variant: 0 big tiles, 1 short chains, 2 big tiles with FFN2 slabs, 3 mid; tiling: 0 the production choice between the
+ * 64x64 and the 128x64 body, 1 64x64 only, 2 128x64 whenever the kernel has both.  kernel_id (optional) receives what was
+ * dispatched: 1 k_gemm3, 2 k_gemm_tn, 3 k_gemm24<4>, 4 k_gemm24<0>, 5..8 k_gemm2<1|2|4|0>, plus 16 when k_gemm24 takes the
+ * 128x64 body for this row count.  Nothing is launched and TTX_ERR_INVALID is returned for arguments a kernel cannot take:
+ * null pointers, K not a multiple of 32, ldx / ldw not multiples of 4, X / W / bias (and Y when ldy % 4 == 0) not 16-byte
+ * aligned, slabs that are not whole canonical slices (K / splits of 64, 128 or a multiple of 256; a multiple of 32 for K
+ * without slices), a live row count outside [0, m_max]. */
+int ttx_debug_gemm(ttx_session* s, const float* d_x, int ldx, const float* d_w, int ldw, const float* d_bias, float* d_y, int ldy,
+                   const int32_t* d_m, int m_max, int N, int K, int relu, int splits, int64_t slab_stride, int variant, int tiling,
+                   int32_t* kernel_id, void* stream);
+
+/* y = LN2?( LN( (resid + bias) + (slab[0] + slab[1] + ...) ) ) over rows of width d in {64, 128, 256, 512, 1024}; rows with
+ * row_valid == 0 become 0, rows >= *d_m are left alone.  d_g2 / d_b2 / d_row_valid / d_m may be NULL.  Float operands must be
+ * 16-byte aligned and slab_stride a multiple of 4 covering m_max * d; otherwise TTX_ERR_INVALID, nothing launched. */
+int ttx_debug_finish_ln(ttx_session* s, const float* d_slabs, int n_slabs, int64_t slab_stride, const float* d_bias,
+                        const float* d_resid, const float* d_g1, const float* d_b1, const float* d_g2, const float* d_b2,
+                        const uint8_t* d_row_valid, float* d_y, const int32_t* d_m, int m_max, int d, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

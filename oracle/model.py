@@ -63,14 +63,17 @@ class OracleTransformer:
     """Functional fp32 model over a reference-layout state dict.  Exposes the L3->L2 protocol of
     SURVEY.md §8(b) B5: ``src_pad_token_i``, ``encode_src``, ``decode_tgt``, ``__call__(src, tgt)``."""
 
-    def __init__(self, cfg: OracleConfig, state: dict, device: str | torch.device = "cpu"):
+    def __init__(self, cfg: OracleConfig, state: dict, device: str | torch.device = "cpu", dtype: torch.dtype = torch.float32):
+        """``dtype=torch.float64``: the same fp32 weights and the same (fp32-built) sinusoid table, cast once, with every
+        operation in float64 — the yardstick that shows how far fp32 itself is from the exact result."""
         self.cfg = cfg
         self.device = torch.device(device)
+        self.dtype = dtype
         st = strip_prefix(state)
-        self.w = {k: torch.as_tensor(v, dtype=torch.float32).to(self.device) for k, v in st.items()}
+        self.w = {k: torch.as_tensor(v, dtype=torch.float32).to(self.device, dtype) for k, v in st.items()}
         self.src_pad_token_i = cfg.pad_token_idx
         self.tgt_pad_token_i = cfg.pad_token_idx
-        self.pe = positional_table(cfg.embedding_dim, cfg.max_positions).to(self.device)
+        self.pe = positional_table(cfg.embedding_dim, cfg.max_positions).to(self.device, dtype)
         self.trace: dict | None = None  # set to {} to record intermediates
 
     # -- helpers ------------------------------------------------------------------------
@@ -121,7 +124,7 @@ class OracleTransformer:
         set to zero: in eval/inference mode the reference's TransformerEncoder takes the nested-tensor
         fast path, which zero-fills them; they are masked by every consumer anyway."""
         x = self._embed(src, "src")
-        key_mask = torch.zeros(src_pad_mask.shape, dtype=torch.float32, device=x.device)
+        key_mask = torch.zeros(src_pad_mask.shape, dtype=self.dtype, device=x.device)
         key_mask = key_mask.masked_fill(src_pad_mask, NEG_INF)[:, None, None, :]
         self._rec("enc.embed", x)
         for i in range(self.cfg.num_encoder_layers):
@@ -136,10 +139,10 @@ class OracleTransformer:
     def decode_hidden(self, tgt: torch.Tensor, memory: torch.Tensor, memory_pad_mask: torch.Tensor) -> torch.Tensor:
         x = self._embed(tgt, "tgt")
         Lt = tgt.size(1)
-        causal = torch.full((Lt, Lt), NEG_INF, device=x.device).triu(1)  # modules.py:128
-        self_mask = causal[None, None] + torch.zeros(tgt.shape, dtype=torch.float32, device=x.device) \
+        causal = torch.full((Lt, Lt), NEG_INF, dtype=self.dtype, device=x.device).triu(1)  # modules.py:128
+        self_mask = causal[None, None] + torch.zeros(tgt.shape, dtype=self.dtype, device=x.device) \
             .masked_fill(tgt == self.tgt_pad_token_i, NEG_INF)[:, None, None, :]  # modules.py:127
-        mem_mask = torch.zeros(memory_pad_mask.shape, dtype=torch.float32, device=x.device) \
+        mem_mask = torch.zeros(memory_pad_mask.shape, dtype=self.dtype, device=x.device) \
             .masked_fill(memory_pad_mask, NEG_INF)[:, None, None, :]
         self._rec("dec.embed", x)
         for i in range(self.cfg.num_decoder_layers):

@@ -2651,6 +2651,22 @@ extern "C" int ttx_debug_gemm_bench(ttx_session* s, int M, int N, int K, int spl
   return gemm_bench(s, M, N, K, splits, variant, reps, us_per_launch, max_abs_diff);
 }
 
+// Test entry points: one GEMM / finisher launch on the caller's device operands (ttx_gemm.hip: gemm_debug, finish_debug).
+extern "C" int ttx_debug_gemm(ttx_session* s, const float* d_x, int ldx, const float* d_w, int ldw, const float* d_bias, float* d_y,
+                              int ldy, const int32_t* d_m, int m_max, int N, int K, int relu, int splits, int64_t slab_stride,
+                              int variant, int tiling, int32_t* kernel_id, void* stream) {
+  return gemm_debug(s, d_x, ldx, d_w, ldw, d_bias, d_y, ldy, d_m, m_max, N, K, relu, splits, (long long)slab_stride, variant, tiling,
+                    kernel_id, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int ttx_debug_finish_ln(ttx_session* s, const float* d_slabs, int n_slabs, int64_t slab_stride, const float* d_bias,
+                                   const float* d_resid, const float* d_g1, const float* d_b1, const float* d_g2, const float* d_b2,
+                                   const uint8_t* d_row_valid, float* d_y, const int32_t* d_m, int m_max, int d, float eps,
+                                   void* stream) {
+  return finish_debug(s, d_slabs, n_slabs, (long long)slab_stride, d_bias, d_resid, d_g1, d_b1, d_g2, d_b2, d_row_valid, d_y, d_m,
+                      m_max, d, eps, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int ttx_last_kernel_profile(ttx_session* s, double* gemm_ms, int64_t* gemm_launches, double* empty_pair_ms) {
   if (!s) return fail(TTX_ERR_INVALID, "null session");
   if (gemm_ms) *gemm_ms = s->prof_ms;

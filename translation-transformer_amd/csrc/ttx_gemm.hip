@@ -779,7 +779,14 @@ int launch_gemm(ttx_session* s, hipStream_t st, const float* X, int ldx, const f
   a.k_per_split = K / S;
   a.slab_stride = slab_stride;
   a.slice_k = gemm_slice_k(K);
+  if (K % S) return fail(TTX_ERR_INVALID, "GEMM K must be a multiple of the slab count");
+  // raw slabs are partial sums: an activation belongs after their sum (the kernels' epilogue would clamp every slab on its own)
+  if (a.raw && relu) return fail(TTX_ERR_INVALID, "raw split-K slabs take no activation");
   if (a.slice_k && a.k_per_split % a.slice_k) return fail(TTX_ERR_INVALID, "split-K slabs must be whole canonical slices");
+  // the 64x64 ring walks four 64-deep tiles per pass (a slab of 192 or 320 k's would be computed over a range that is not its own)
+  if (a.slice_k && a.k_per_split != 64 && a.k_per_split != 128 && a.k_per_split % 256)
+    return fail(TTX_ERR_INVALID, "split-K slabs must be 64, 128 or a multiple of 256 deep");
+  if (!a.slice_k && a.k_per_split % 32) return fail(TTX_ERR_INVALID, "split-K slabs must be a multiple of 32 deep");
   a.big_min_tiles = 0;
   hipEvent_t e1 = nullptr;
   if (s->profile) {
@@ -794,9 +801,12 @@ int launch_gemm(ttx_session* s, hipStream_t st, const float* X, int ldx, const f
     s->ev_used++;
   }
   const bool step = (m_ptr != nullptr);
+  s->last_gemm_big_min_tiles = 0;
   if (use_gemm3(step, variant, N, K) && S == 1) {
+    s->last_gemm_kernel = GK_GEMM3;
     hipLaunchKernelGGL(k_gemm3, dim3(cdiv(N, 32), cdiv(Mmax, 32), 1), dim3(256), 0, st, a);
   } else if (a.slice_k == 0) {
+    s->last_gemm_kernel = GK_GEMM_TN;
     hipLaunchKernelGGL((k_gemm_tn<2, 2>), dim3(cdiv(N, 64), cdiv(Mmax, 64), S), dim3(256), 0, st, a);
   } else if (a.k_per_split % 256 == 0 && !(step && variant == GV_SMALL)) {
     // one launch that picks the tiling (128x64 / 64x64) from the live row count.  Where the 128-row tiling starts to pay
@@ -805,10 +815,13 @@ int launch_gemm(ttx_session* s, hipStream_t st, const float* X, int ldx, const f
     a.big_min_tiles = K >= 2048 ? std::max(1, s->big_min_tiles / 3) : (N >= 2048 ? 2 * s->big_min_tiles : s->big_min_tiles);
     if (s->big_min_tiles == 0) a.big_min_tiles = 0;
     dim3 grid(cdiv(N, 64), cdiv(Mmax, 64), S);
+    s->last_gemm_kernel = a.k_per_split == 256 ? GK_GEMM24_4 : GK_GEMM24_0;
+    s->last_gemm_big_min_tiles = a.big_min_tiles;
     if (a.k_per_split == 256) hipLaunchKernelGGL((k_gemm24<4>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((k_gemm24<0>), grid, dim3(256), 0, st, a);
   } else {
     dim3 grid(cdiv(N, 64), cdiv(Mmax, 64), S);
+    s->last_gemm_kernel = a.k_per_split == 64 ? GK_GEMM2_1 : a.k_per_split == 128 ? GK_GEMM2_2 : a.k_per_split == 256 ? GK_GEMM2_4 : GK_GEMM2_0;
     switch (a.k_per_split) {
       case 64: hipLaunchKernelGGL((k_gemm2<1>), grid, dim3(256), 0, st, a); break;
       case 128: hipLaunchKernelGGL((k_gemm2<2>), grid, dim3(256), 0, st, a); break;
@@ -824,14 +837,21 @@ int launch_gemm(ttx_session* s, hipStream_t st, const float* X, int ldx, const f
 int launch_finish(ttx_session* s, hipStream_t st, const float* slabs, int n_slabs, long long slab_stride, const float* bias,
                   const float* resid, const float* g1, const float* b1, const float* g2, const float* b2,
                   const uint8_t* row_valid, float* Y, const int* m_ptr, int Mmax) {
-  if (Mmax <= 0) return TTX_OK;
   const ttx_config& c = s->m->cfg;
+  return launch_finish_d(st, slabs, n_slabs, slab_stride, bias, resid, g1, b1, g2, b2, row_valid, Y, m_ptr, Mmax, c.embedding_dim,
+                         c.layer_norm_eps);
+}
+
+int launch_finish_d(hipStream_t st, const float* slabs, int n_slabs, long long slab_stride, const float* bias, const float* resid,
+                    const float* g1, const float* b1, const float* g2, const float* b2, const uint8_t* row_valid, float* Y,
+                    const int* m_ptr, int Mmax, int d, float eps) {
+  if (Mmax <= 0) return TTX_OK;
   FinishArgs a;
   a.slabs = slabs; a.n_slabs = n_slabs; a.slab_stride = slab_stride; a.bias = bias; a.resid = resid;
   a.g1 = g1; a.b1 = b1; a.g2 = g2; a.b2 = b2; a.row_valid = row_valid; a.Y = Y; a.m_ptr = m_ptr; a.M = Mmax;
-  a.d = c.embedding_dim; a.eps = c.layer_norm_eps;
+  a.d = d; a.eps = eps;
   dim3 grid(cdiv(Mmax, 4));
-  switch (c.embedding_dim / 64) {
+  switch (d / 64) {
     case 1: hipLaunchKernelGGL((k_finish_ln<1>), grid, dim3(256), 0, st, a); break;
     case 2: hipLaunchKernelGGL((k_finish_ln<2>), grid, dim3(256), 0, st, a); break;
     case 4: hipLaunchKernelGGL((k_finish_ln<4>), grid, dim3(256), 0, st, a); break;
@@ -920,6 +940,86 @@ int gemm_bench(ttx_session* s, int M, int N, int K, int splits, int variant, int
   (void)hipStreamDestroy(st);
   (void)hipFree(dx); (void)hipFree(dw); (void)hipFree(db); (void)hipFree(dy); (void)hipFree(dref); (void)hipFree(dm);
   return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Test entry points (ttx_debug_gemm / ttx_debug_finish_ln): ONE launch of launch_gemm / launch_finish_d on the caller's device
+// operands.  Everything the kernels take on trust from the production call sites is checked here on the host, so that a test
+// can never launch a kernel on arguments it cannot handle.
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// live row count of a step launch (read back: these are test calls), checked against the capacity
+static int debug_live_rows(const int32_t* d_m, int m_max, hipStream_t st, int* M) {
+  *M = m_max;
+  if (!d_m) return TTX_OK;
+  int32_t m = -1;
+  HIP_TRY(hipStreamSynchronize(st));               // the caller's write of the count is ordered on its stream
+  HIP_TRY(hipMemcpy(&m, d_m, 4, hipMemcpyDeviceToHost));
+  if (m < 0 || m > m_max) return fail(TTX_ERR_INVALID, "live row count on the device is outside [0, m_max]");
+  *M = m;
+  return TTX_OK;
+}
+
+int gemm_debug(ttx_session* s, const float* d_x, int ldx, const float* d_w, int ldw, const float* d_bias, float* d_y, int ldy,
+               const int32_t* d_m, int m_max, int N, int K, int relu, int splits, long long slab_stride, int variant, int tiling,
+               int32_t* kernel_id, hipStream_t st) {
+  if (!s || !d_x || !d_w || !d_y) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_gemm");
+  if (m_max <= 0 || N <= 0 || K <= 0 || splits < 0) return fail(TTX_ERR_INVALID, "ttx_debug_gemm: m_max, N, K must be positive and splits >= 0");
+  if (K % 32) return fail(TTX_ERR_INVALID, "ttx_debug_gemm: K must be a multiple of 32");
+  if (variant < GV_BIG || variant > GV_MID || tiling < 0 || tiling > 2) return fail(TTX_ERR_INVALID, "ttx_debug_gemm: variant is 0..3, tiling 0..2");
+  if (ldx < K || ldw < K || ldy < N) return fail(TTX_ERR_INVALID, "ttx_debug_gemm: leading dimensions must cover K (X, W) and N (Y)");
+  if ((ldx & 3) || (ldw & 3) || !aligned16(d_x) || !aligned16(d_w))
+    return fail(TTX_ERR_INVALID, "ttx_debug_gemm: X and W are read as float4 (16-byte aligned pointers, ldx and ldw multiples of 4)");
+  // the 32x32 kernel moves bias and whole-row outputs as float4 whenever ldy is a multiple of 4
+  if ((d_bias && !aligned16(d_bias)) || ((ldy & 3) == 0 && !aligned16(d_y)))
+    return fail(TTX_ERR_INVALID, "ttx_debug_gemm: bias, and Y when ldy is a multiple of 4, must be 16-byte aligned");
+  const int S = splits > 0 ? splits : 1;
+  const int slice = gemm_slice_k(K);
+  if (K % S) return fail(TTX_ERR_INVALID, "ttx_debug_gemm: K must be a multiple of splits");
+  const int kps = K / S;
+  if (slice ? (kps % slice != 0 || (kps != 64 && kps != 128 && kps % 256 != 0)) : (kps % 32 != 0))
+    return fail(TTX_ERR_INVALID, "ttx_debug_gemm: slabs must be whole canonical slices (64, 128 or a multiple of 256 k's; 32 without slices)");
+  if (S > 1 && (slab_stride < (long long)(m_max - 1) * ldy + N || ((slab_stride & 3) && (ldy & 3) == 0)))
+    return fail(TTX_ERR_INVALID, "ttx_debug_gemm: slab_stride must cover one [m_max, ldy] slab");
+  HIP_TRY(hipSetDevice(s->m->device));
+  int M = 0;
+  TTX_TRY(debug_live_rows(d_m, m_max, st, &M));
+  const bool was_profile = s->profile;
+  const int keep_min = s->big_min_tiles;
+  s->profile = false;
+  if (tiling == 1) s->big_min_tiles = 0;
+  else if (tiling == 2) s->big_min_tiles = 1;
+  const int rc = launch_gemm(s, st, d_x, ldx, d_w, ldw, d_bias, d_y, ldy, d_m, m_max, N, K, relu != 0, splits, slab_stride, variant);
+  s->big_min_tiles = keep_min; s->profile = was_profile;
+  if (rc != TTX_OK) return rc;
+  if (kernel_id) {
+    int id = s->last_gemm_kernel;
+    if (id == GK_GEMM24_4 || id == GK_GEMM24_0) {
+      // k_gemm24's own condition for the 128x64 body
+      const int mid_tiles = ((M + 127) >> 7) * ((N + 63) >> 6) * S;
+      if (s->last_gemm_big_min_tiles > 0 && mid_tiles >= s->last_gemm_big_min_tiles) id |= GK_BODY_128x64;
+    }
+    *kernel_id = id;
+  }
+  return TTX_OK;
+}
+
+int finish_debug(ttx_session* s, const float* d_slabs, int n_slabs, long long slab_stride, const float* d_bias, const float* d_resid,
+                 const float* d_g1, const float* d_b1, const float* d_g2, const float* d_b2, const uint8_t* d_row_valid, float* d_y,
+                 const int32_t* d_m, int m_max, int d, float eps, hipStream_t st) {
+  if (!s || !d_slabs || !d_bias || !d_resid || !d_g1 || !d_b1 || !d_y) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_finish_ln");
+  if ((d_g2 == nullptr) != (d_b2 == nullptr)) return fail(TTX_ERR_INVALID, "ttx_debug_finish_ln: the second norm needs both gamma and beta");
+  if (d != 64 && d != 128 && d != 256 && d != 512 && d != 1024) return fail(TTX_ERR_INVALID, "ttx_debug_finish_ln: d must be 64, 128, 256, 512 or 1024");
+  if (m_max <= 0 || n_slabs < 1 || !(eps >= 0.f)) return fail(TTX_ERR_INVALID, "ttx_debug_finish_ln: m_max and n_slabs must be positive, eps >= 0");
+  if (n_slabs > 1 && (slab_stride < (long long)m_max * d || (slab_stride & 3)))
+    return fail(TTX_ERR_INVALID, "ttx_debug_finish_ln: slab_stride must cover one [m_max, d] slab and be a multiple of 4");
+  for (const void* p : {(const void*)d_slabs, (const void*)d_bias, (const void*)d_resid, (const void*)d_g1, (const void*)d_b1,
+                        (const void*)d_g2, (const void*)d_b2, (const void*)d_y})
+    if (!aligned16(p)) return fail(TTX_ERR_INVALID, "ttx_debug_finish_ln: float operands must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(s->m->device));
+  int M = 0;
+  TTX_TRY(debug_live_rows(d_m, m_max, st, &M));
+  return launch_finish_d(st, d_slabs, n_slabs, slab_stride, d_bias, d_resid, d_g1, d_b1, d_g2, d_b2, d_row_valid, d_y, d_m, m_max, d, eps);
 }
 
 }  // namespace ttx

@@ -57,6 +57,11 @@ struct Buf {
 //             the tiles for QKV and FFN1 (a 32x32 launch over 768 columns loses to 64x64 tiles from about 800 rows on)
 enum GemmVariant { GV_BIG = 0, GV_SMALL = 1, GV_BIG_FFN2_SLABS = 2, GV_MID = 3 };
 
+// Kernel of a GEMM launch as ttx_debug_gemm reports it (include/ttx.h); GK_BODY_128x64 is or-ed in when k_gemm24 takes its
+// 128x64 body for the launch's live row count.
+enum GemmKernelId { GK_GEMM3 = 1, GK_GEMM_TN = 2, GK_GEMM24_4 = 3, GK_GEMM24_0 = 4, GK_GEMM2_1 = 5, GK_GEMM2_2 = 6, GK_GEMM2_4 = 7,
+                    GK_GEMM2_0 = 8, GK_BODY_128x64 = 16 };
+
 struct GraphKey {
   int B, Ls, N, D, max_len, mode, kcap, variant;   // mode: 0 speculative, 1 plain greedy, 2 per-row rule, 3 slot pool
   bool operator<(const GraphKey& o) const {
@@ -127,6 +132,9 @@ struct ttx_session {
   // k_gemm24 picks the tiling per launch from the live row count: 128x64 tiles once there are big_min_tiles of them,
   // else 64x64 (TTX_BIG_MIN_TILES)
   int big_min_tiles = TTX_BIG_MIN_TILES;
+  // what the most recent launch_gemm dispatched (GemmKernelId) and the tile threshold it handed k_gemm24: ttx_debug_gemm reports
+  // them so that a test can prove which kernel it reached
+  int last_gemm_kernel = 0, last_gemm_big_min_tiles = 0;
   int attn_split = -1;             // -1 by launch size, 0 never, 1 always (key tiles of a head over 4 waves)
   bool attn_fallback = false;      // TTX_ATTN_FALLBACK=1 (test hook): every attention launch on the streaming kernel k_attn
   // profiling of the GEMM launches (bench.py roofline): a HIP event pair around every GEMM launch
@@ -188,6 +196,17 @@ int launch_gemm(ttx_session* s, hipStream_t st, const float* X, int ldx, const f
 int launch_finish(ttx_session* s, hipStream_t st, const float* slabs, int n_slabs, long long slab_stride, const float* bias,
                   const float* resid, const float* g1, const float* b1, const float* g2, const float* b2,
                   const uint8_t* row_valid, float* Y, const int* m_ptr, int Mmax);
+// launch_finish with the row width and epsilon given by the caller instead of the model
+int launch_finish_d(hipStream_t st, const float* slabs, int n_slabs, long long slab_stride, const float* bias, const float* resid,
+                    const float* g1, const float* b1, const float* g2, const float* b2, const uint8_t* row_valid, float* Y,
+                    const int* m_ptr, int Mmax, int d, float eps);
+// ttx_debug_gemm / ttx_debug_finish_ln (include/ttx.h): host-side validation, then one launch
+int gemm_debug(ttx_session* s, const float* d_x, int ldx, const float* d_w, int ldw, const float* d_bias, float* d_y, int ldy,
+               const int32_t* d_m, int m_max, int N, int K, int relu, int splits, long long slab_stride, int variant, int tiling,
+               int32_t* kernel_id, hipStream_t st);
+int finish_debug(ttx_session* s, const float* d_slabs, int n_slabs, long long slab_stride, const float* d_bias, const float* d_resid,
+                 const float* d_g1, const float* d_b1, const float* d_g2, const float* d_b2, const uint8_t* d_row_valid, float* d_y,
+                 const int32_t* d_m, int m_max, int d, float eps, hipStream_t st);
 int gemm_bench(ttx_session* s, int M, int N, int K, int splits, int variant, int reps, double* us_per_launch, double* max_abs_diff);
 
 // ---- ttx_attn.hip ------------------------------------------------------------------------------------------------

@@ -162,6 +162,33 @@ class NativeTransformer:
                 over.append(e.value)
         return {"gemm_ms": tot_ms, "launches": tot_n, "pair_overhead_ms": float(np.median(over)) if over else 0.0}
 
+    # -- kernel-level test entry points --------------------------------------------------------
+    @staticmethod
+    def _ptr(t: torch.Tensor | None):
+        return None if t is None else t.data_ptr()
+
+    def debug_gemm(self, x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None, y: torch.Tensor, n: int, k: int,
+                   m_max: int, m_live: torch.Tensor | None = None, relu: bool = False, splits: int = 0, slab_stride: int = 0,
+                   variant: int = 0, tiling: int = 0) -> int:
+        """One GEMM launch on the caller's device tensors (ttx_debug_gemm): ``x`` / ``w`` / ``y`` are 2-D fp32 views whose
+        row strides are the leading dimensions (``y``: the first slab), ``m_live`` an int32 device scalar or None.  Returns
+        the kernel id the launch dispatched; arguments a kernel cannot take raise TtxError (TTX_ERR_INVALID)."""
+        kid = C.c_int32(0)
+        N.check(self._lib.ttx_debug_gemm(self._session, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), self._ptr(bias),
+                                         y.data_ptr(), y.stride(0), self._ptr(m_live), int(m_max), int(n), int(k), int(relu),
+                                         int(splits), int(slab_stride), int(variant), int(tiling), C.byref(kid), self._stream()))
+        return int(kid.value)
+
+    def debug_finish_ln(self, slabs: torch.Tensor, n_slabs: int, slab_stride: int, bias: torch.Tensor, resid: torch.Tensor,
+                        g1: torch.Tensor, b1: torch.Tensor, g2: torch.Tensor | None, b2: torch.Tensor | None,
+                        row_valid: torch.Tensor | None, y: torch.Tensor, m_max: int, d: int, eps: float = 1e-5,
+                        m_live: torch.Tensor | None = None) -> None:
+        """One finisher launch on the caller's device tensors (ttx_debug_finish_ln): rows are contiguous, ``d`` wide."""
+        N.check(self._lib.ttx_debug_finish_ln(self._session, slabs.data_ptr(), int(n_slabs), int(slab_stride), bias.data_ptr(),
+                                              resid.data_ptr(), g1.data_ptr(), b1.data_ptr(), self._ptr(g2), self._ptr(b2),
+                                              self._ptr(row_valid), y.data_ptr(), self._ptr(m_live), int(m_max), int(d),
+                                              float(eps), self._stream()))
+
     def close(self) -> None:
         for extra in getattr(self, "_pool", [])[1:]:
             self._lib.ttx_session_destroy(extra)
