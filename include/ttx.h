@@ -120,6 +120,28 @@ int ttx_token_metrics(ttx_session* s, const float* d_logits, const int64_t* d_tg
 int ttx_teacher_forced_eval(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_tgt, int Lt, int eos,
                             float* d_logits, int64_t* d_pred, float* d_nll, float* d_out3, void* stream);
 
+/* Log-likelihood scores of hypotheses, one scale for every generator.  For a hypothesis row h[0..W-1] (column 0 holds the BOS and
+ * is never scored) and logits = decode_tgt(h[:W-1], memory(src)), the model's own teacher-forced forward on the hypothesis:
+ *   n         the column of the first EOS at a column >= 1 (finished = 1); else the last column >= 1 holding a non-PAD token
+ *             (finished = 0); else 0 (an all-PAD row);
+ *   tok_logp  [t-1] = log_softmax(logits[t-1])[h[t]] for t = 1..n and exactly 0 for t > n; a PAD before the EOS is a target like
+ *             any other;
+ *   score     the sum of tok_logp[0..n-1] in position order, accumulated in double and rounded once; length = n.  A row with
+ *             n = 0 has score 0 and finished = 0.
+ * Nothing is synchronised and every output is written on the device; every argument is checked before any launch (W >= 2,
+ * vocabulary <= 1024, W - 1 and Ls within the positional table, rows * (W-1) < 2^24).  Token ids outside [0, V) are the caller's
+ * to reject (the kernels read them as id 0).  Two calls on the same inputs give bit-identical results.  d_tok_logp and d_finished
+ * are optional outputs (NULL: not handed out).
+ * ttx_hypothesis_logprobs: the scoring stage alone over caller-provided logits fp32 [R,W-1,V]; d_hyp int64 [R,W].
+ * ttx_score_hypotheses: the encoder once per source, the full-prefix decoder over the B*N rows (row r reads memory row r / N) and
+ * the stage above.  d_hyp int64 [B*N] rows with row stride ld_hyp >= W, so the first W columns of a wider tensor are scored in
+ * place; d_logits [B*N,W-1,V] or NULL (session scratch): what ttx_decode_tgt returns for the same rows, bit for bit. */
+int ttx_hypothesis_logprobs(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad, int eos,
+                            float* d_tok_logp, float* d_score, int32_t* d_length, uint8_t* d_finished, void* stream);
+int ttx_score_hypotheses(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N, int W,
+                         int eos, float* d_logits, float* d_tok_logp, float* d_score, int32_t* d_length, uint8_t* d_finished,
+                         void* stream);
+
 /* Draft maker: make_drafts (src/utils/drafting.py:5-67) on the device.  d_src int64 [B,L];
  * d_drafts int64 [B,n_drafts,D] out with D = clamp(draft_len, min_draft_len, max_draft_len). */
 int ttx_make_drafts(ttx_session* s, const int64_t* d_src, int B, int L, int draft_len, int n_drafts,

@@ -17,7 +17,7 @@ LIB_PATH = PKG_DIR / "libttx_hip.so"
 # translation units (compiled in parallel, linked into one shared library) and the headers every one of them depends on
 UNITS = [CSRC / "ttx_api.hip", CSRC / "ttx_gemm.hip", CSRC / "ttx_attn.hip"]
 HEADERS = [CSRC / "ttx_internal.h", CSRC / "ttx_common.hip.h", CSRC / "ttx_loop_kernels.hip.h", CSRC / "ttx_metrics.hip.h",
-           CSRC / "ttx_select.h", CSRC / "ttx_tokenizer.h", INCLUDE / "ttx.h"]
+           CSRC / "ttx_score.hip.h", CSRC / "ttx_select.h", CSRC / "ttx_tokenizer.h", INCLUDE / "ttx.h"]
 SOURCES = UNITS + HEADERS
 OBJ_DIR = CSRC / "build"
 
@@ -100,6 +100,8 @@ SYMBOLS = {
     "ttx_forward": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _VP, _VP]),
     "ttx_token_metrics": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
     "ttx_teacher_forced_eval": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
+    "ttx_hypothesis_logprobs": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
+    "ttx_score_hypotheses": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ttx_make_drafts": (C.c_int, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP]),
     "ttx_greedy_speculative_generate": (C.c_int, [_VP, _VP, _I, _I, C.POINTER(GenParams), _VP, C.POINTER(GenStats), _VP]),
     "ttx_greedy_generate": (C.c_int, [_VP, _VP, _I, _I, C.POINTER(GenParams), _VP, C.POINTER(GenStats), _VP]),

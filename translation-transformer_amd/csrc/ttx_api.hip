@@ -5,6 +5,7 @@
 #include "ttx_internal.h"
 #include "ttx_loop_kernels.hip.h"
 #include "ttx_metrics.hip.h"
+#include "ttx_score.hip.h"
 #include "ttx_tokenizer.h"
 
 #include <algorithm>
@@ -603,6 +604,80 @@ extern "C" int ttx_teacher_forced_eval(ttx_session* s, const int64_t* d_src, int
   TTX_TRY(run_decoder_full(s, st, s->tok_tgt.as<int>(), B, T, s->memory.as<float>(), s->mem_pad_tmp.as<uint8_t>(), nullptr, B, Ls,
                            d_logits));
   return launch_metrics(s, st, d_logits, d_tgt, B, Lt, V, eos, d_pred, d_nll, d_out3);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Log-likelihood scores of hypotheses: csrc/ttx_score.hip.h.
+static int check_score_shapes(const ttx_session* s, long long R, int W, int V, const char* fn) {
+  if (R <= 0 || W < 2 || V <= 0) return fail(TTX_ERR_INVALID, std::string("bad argument to ") + fn + ": rows > 0, W >= 2, V > 0");
+  if (V > MET_MAX_V) return fail(TTX_ERR_INVALID, std::string(fn) + ": vocabulary larger than 1024");
+  if (R * (W - 1) >= (1LL << 24)) return fail(TTX_ERR_INVALID, std::string(fn) + ": more than 2^24 positions in one call");
+  if (W - 1 > s->m->cfg.max_positions) return fail(TTX_ERR_INVALID, std::string(fn) + ": hypothesis longer than the positional table");
+  return TTX_OK;
+}
+
+static int launch_score(ttx_session* s, hipStream_t st, const float* logits, const int64_t* hyp, int ld_hyp, int R, int W, int V,
+                        int pad, int eos, float* tok_logp, float* score, int32_t* length, uint8_t* finished) {
+  if (!tok_logp) {                        // the sum reads the per-token values back: session scratch when the caller wants none
+    TTX_TRY(ensure(s->ev_nll, (size_t)R * (W - 1) * sizeof(float), st));
+    tok_logp = s->ev_nll.as<float>();
+  }
+  if (V % 4 == 0 && reinterpret_cast<uintptr_t>(logits) % 16 == 0)
+    hipLaunchKernelGGL(k_hyp_score<true>, dim3(R), dim3(SCORE_THREADS), 0, st, logits, hyp, ld_hyp, W, V, pad, eos, tok_logp, score,
+                       length, finished);
+  else
+    hipLaunchKernelGGL(k_hyp_score<false>, dim3(R), dim3(SCORE_THREADS), 0, st, logits, hyp, ld_hyp, W, V, pad, eos, tok_logp, score,
+                       length, finished);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+extern "C" int ttx_hypothesis_logprobs(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad,
+                                       int eos, float* d_tok_logp, float* d_score, int32_t* d_length, uint8_t* d_finished,
+                                       void* stream) {
+  if (!s) return session_required("ttx_hypothesis_logprobs");
+  if (!d_logits || !d_hyp || !d_score || !d_length) return fail(TTX_ERR_INVALID, "bad argument to ttx_hypothesis_logprobs");
+  TTX_TRY(check_score_shapes(s, R, W, V, "ttx_hypothesis_logprobs"));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->m->device));
+  return launch_score(s, st, d_logits, d_hyp, W, R, W, V, pad, eos, d_tok_logp, d_score, d_length, d_finished);
+}
+
+extern "C" int ttx_score_hypotheses(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N,
+                                    int W, int eos, float* d_logits, float* d_tok_logp, float* d_score, int32_t* d_length,
+                                    uint8_t* d_finished, void* stream) {
+  if (!s) return session_required("ttx_score_hypotheses");
+  if (!d_src || !d_hyp || !d_score || !d_length || B <= 0 || N <= 0 || Ls <= 0)
+    return fail(TTX_ERR_INVALID, "bad argument to ttx_score_hypotheses");
+  if (ld_hyp < W) return fail(TTX_ERR_INVALID, "ttx_score_hypotheses: row stride ld_hyp smaller than W");
+  const ttx_config& c = s->m->cfg;
+  TTX_TRY(check_score_shapes(s, (long long)B * N, W, c.vocab_size, "ttx_score_hypotheses"));
+  if (Ls > c.max_positions) return fail(TTX_ERR_INVALID, "source longer than the positional table");
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->m->device));
+  const int R = B * N, T = W - 1, V = c.vocab_size, d = c.embedding_dim;
+  if (!d_logits) {
+    TTX_TRY(ensure(s->ev_logits, (size_t)R * T * V * sizeof(float), st));
+    d_logits = s->ev_logits.as<float>();
+  }
+  // the encoder once per source; decoder row r attends to memory row r / N
+  TTX_TRY(ensure(s->memory, (size_t)B * Ls * d * 4, st));
+  TTX_TRY(ensure(s->mem_pad_tmp, (size_t)B * Ls, st));
+  TTX_TRY(ensure(s->sc_src_of, (size_t)R * 4, st));
+  TTX_TRY(ttx_encode_src(s, d_src, B, Ls, s->memory.as<float>(), stream));
+  hipLaunchKernelGGL(k_invert_mask, dim3(cdiv(B * Ls, 256)), dim3(256), 0, st, s->src_valid.as<uint8_t>(),
+                     s->mem_pad_tmp.as<uint8_t>(), B * Ls);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_score_src_of, dim3(cdiv(R, 256)), dim3(256), 0, st, s->sc_src_of.as<int>(), R, N);
+  HIP_TRY(hipGetLastError());
+  // decode_tgt(hyp[:, :W-1]) without a sliced copy: the decoder's int32 tokens are read off the strided rows directly
+  TTX_TRY(ensure(s->tok_tgt, (size_t)R * T * 4, st));
+  hipLaunchKernelGGL(k_prepare_tokens_2d, dim3(cdiv(R * T, 256)), dim3(256), 0, st, d_hyp, ld_hyp, s->tok_tgt.as<int>(),
+                     (uint8_t*)nullptr, R, T, c.pad_token);
+  HIP_TRY(hipGetLastError());
+  TTX_TRY(run_decoder_full(s, st, s->tok_tgt.as<int>(), R, T, s->memory.as<float>(), s->mem_pad_tmp.as<uint8_t>(),
+                           s->sc_src_of.as<int>(), B, Ls, d_logits));
+  return launch_score(s, st, d_logits, d_hyp, ld_hyp, R, W, V, c.pad_token, eos, d_tok_logp, d_score, d_length, d_finished);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -83,6 +83,9 @@ struct ttx_session {
   Buf tok_tgt, mem_pad_tmp;
   // teacher-forced evaluation (ttx_teacher_forced_eval / ttx_token_metrics): logits / argmax / nll the caller did not ask for
   Buf ev_logits, ev_pred, ev_nll;
+  // hypothesis scoring (ttx_score_hypotheses): decoder row -> memory row; logits / per-token values it does not hand out live in
+  // ev_logits / ev_nll
+  Buf sc_src_of;
   // loop
   Buf drafts, gen, front, act_idx, rec, pred, state, kcache, vcache, src32, outbuf, haspad, traj, fin_step;
   // slot pool (continuous batching)
@@ -151,7 +154,7 @@ struct ttx_session {
   long long host_launches = 0;
   hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;
   ttx_session() { for (Buf* b : {&x, &x1, &x2, &xf, &ao, &q2, &hbuf, &slab, &qkv, &logits, &ckv, &tok_src, &src_valid, &memory,
-                                 &memkv, &tok_tgt, &mem_pad_tmp, &ev_logits, &ev_pred, &ev_nll, &drafts, &gen, &front, &act_idx, &rec, &pred, &state,
+                                 &memkv, &tok_tgt, &mem_pad_tmp, &ev_logits, &ev_pred, &ev_nll, &sc_src_of, &drafts, &gen, &front, &act_idx, &rec, &pred, &state,
                                  &kcache, &vcache, &src32, &outbuf, &haspad, &traj, &fin_step, &rstep, &row_of, &src_len, &new_slot,
                                  &pool_io, &memkv_new, &valid_new, &drafts_new, &tk[0], &tk[1], &tv[0], &tv[1],
                                  &t_prev_len, &t_slot_of, &t_src_of,

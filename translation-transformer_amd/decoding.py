@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .model import NativeTransformer
+from .model import HypothesisScores, NativeTransformer
 
 
 def _need_native(model) -> NativeTransformer:
@@ -20,7 +20,29 @@ def _need_native(model) -> NativeTransformer:
     return model
 
 
-class TranslationInferenceGreedySpeculative:
+class _ScoresHypotheses:
+    """``score`` for every generator: the model's log-likelihood of each returned hypothesis, by one teacher-forced pass over the
+    finished rows (NativeTransformer.score_hypotheses) — the same scale for all four classes.  Scoring is no part of the
+    reference's loops and leaves the counters (``model_calls_num`` and the rest) alone."""
+
+    def _pad_eos(self) -> tuple:
+        return self.pad_token, self.eos_token
+
+    def score(self, src: torch.Tensor, pred: torch.Tensor, **kw) -> HypothesisScores:
+        """``pred``: Long[B, N, L] as ``generate(src)`` returned it.  Keywords go to ``score_hypotheses``."""
+        pad, eos = self._pad_eos()
+        if pad != self.model.tgt_pad_token_i:
+            raise ValueError("the generator's pad token differs from the model's")
+        return self.model.score_hypotheses(src, pred, eos_token_idx=eos, **kw)
+
+    def _scored(self, src: torch.Tensor, pred: torch.Tensor, return_scores: bool):
+        return (pred, self.score(src, pred)) if return_scores else pred
+
+    def _scored_many(self, batches: list, preds: list) -> list:
+        return [(p, None if p is None else self.score(b, p)) for b, p in zip(batches, preds)]
+
+
+class TranslationInferenceGreedySpeculative(_ScoresHypotheses):
     """Drop-in for src/decoding/speculative_decoding.py:8-174: copy-drafts, one parallel verify pass per
     step, longest accepted prefix + 1 bonus token — the whole loop runs in ttx_greedy_speculative_generate."""
 
@@ -62,7 +84,8 @@ class TranslationInferenceGreedySpeculative:
         return (f"Greedy speculative decoding (draft_len={self.draft_len}, n_drafts={self.n_drafts}, "
                 f"max_len={self.max_len})")
 
-    def generate(self, src: torch.Tensor) -> torch.Tensor:
+    def generate(self, src: torch.Tensor, return_scores: bool = False):
+        """``return_scores=True``: ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``)."""
         m = self.model
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
@@ -81,10 +104,10 @@ class TranslationInferenceGreedySpeculative:
         t["src_tokens_padded"] += B * Ls
         t["batches"] += 1
         self.last_stats = st
-        return out
+        return self._scored(src, out, return_scores)
 
     def generate_many(self, batches: list, in_flight: int = 4, reorder: bool = False, group_size: int | None = None,
-                      on_error: str = "raise", pool: bool | None = None) -> list:
+                      on_error: str = "raise", pool: bool | None = None, return_scores: bool = False) -> list:
         """Decode several batches with up to `in_flight` of them on the GPU at once (one session + stream each;
         ttx_greedy_speculative_generate_many).  Returns one [B,1,max_len] tensor per batch, each identical to what
         ``generate`` returns for that batch; counters accumulate as if ``generate`` had been called per batch.
@@ -96,7 +119,12 @@ class TranslationInferenceGreedySpeculative:
 
         ``on_error="skip"``: a batch on which the reference raises (a row finishing at a width beyond max_len,
         speculative_decoding.py:158) yields ``None`` in the returned list instead of ending the call; the indices are
-        kept in ``self.last_failed_batches``."""
+        kept in ``self.last_failed_batches``.
+
+        ``return_scores=True``: a list of ``(pred, HypothesisScores)`` pairs; a batch that came back ``None`` has ``None``
+        scores."""
+        if return_scores:
+            return self._scored_many(batches, self.generate_many(batches, in_flight, reorder, group_size, on_error, pool))
         m = self.model
         if on_error not in ("raise", "skip"):
             raise ValueError("on_error must be 'raise' or 'skip'")
@@ -265,7 +293,7 @@ class TranslationInferenceGreedySpeculative:
         return outs
 
 
-class TranslationInferenceGreedy:
+class TranslationInferenceGreedy(_ScoresHypotheses):
     """Drop-in for src/decoding/standard_decoding.py:4-55; the loop runs in ttx_greedy_generate (KV cache)."""
 
     def __init__(self, model, max_len: int, pad_token: int, bos_token: int, eos_token: int) -> None:
@@ -278,7 +306,8 @@ class TranslationInferenceGreedy:
     def __str__(self):
         return f"Greedy decoding (max_len={self.max_len})"
 
-    def generate(self, src: torch.Tensor) -> torch.Tensor:
+    def generate(self, src: torch.Tensor, return_scores: bool = False):
+        """``return_scores=True``: ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``)."""
         m = self.model
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
@@ -290,10 +319,10 @@ class TranslationInferenceGreedy:
                                            m._stream()))
         self.model_calls_num += int(st.model_calls)
         self.given_tokens += int((src != m.src_pad_token_i).sum())
-        return out
+        return self._scored(src, out, return_scores)
 
 
-class TranslationInferenceBeamSearch:
+class TranslationInferenceBeamSearch(_ScoresHypotheses):
     """Drop-in for src/decoding/standard_decoding.py:58-174: the whole loop runs in ttx_beam_generate (per-hypothesis KV
     cache, encoder and cross K/V once per source, log-softmax + top-beam + row assembly in one kernel per step)."""
 
@@ -310,7 +339,8 @@ class TranslationInferenceBeamSearch:
     def __str__(self):
         return f"Beam search decoding (beam_size={self.beam_size}, max_len={self.max_len})"
 
-    def generate(self, src: torch.Tensor) -> torch.Tensor:
+    def generate(self, src: torch.Tensor, return_scores: bool = False):
+        """``return_scores=True``: ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``)."""
         m, K = self.model, self.beam_size
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
@@ -322,10 +352,10 @@ class TranslationInferenceBeamSearch:
         self.model_calls_num += int(st.model_calls)
         self.b_sz += int(st.running_rows)
         self.given_tokens += int((src != m.src_pad_token_i).sum())
-        return out[:, :, :int(st.out_width)].contiguous()
+        return self._scored(src, out[:, :, :int(st.out_width)].contiguous(), return_scores)
 
 
-class TranslationInferenceBeamSearchSpeculative:
+class TranslationInferenceBeamSearchSpeculative(_ScoresHypotheses):
     """Drop-in for src/decoding/speculative_decoding.py:241-869 (both draft modes): the whole loop — candidate rows, draft
     slots, KV-cached verify step, accepted lengths, best draft, leaf enumeration and scoring, per-source selection,
     termination — runs in ttx_beam_speculative_generate; Python allocates the output tensor and keeps the counters."""
@@ -370,6 +400,9 @@ class TranslationInferenceBeamSearchSpeculative:
         return N.BeamParams(self.max_len, self.n_best, self.draft_len, self.requested_drafts_num, int(bool(self.smart_drafts_mode)),
                             self.pad_token_idx, self.bos_token_idx, self.eos_token_idx, self.C_token_idx, int(self.max_steps or 0))
 
+    def _pad_eos(self) -> tuple:
+        return self.pad_token_idx, self.eos_token_idx
+
     _COUNTERS = ("model_calls_num", "accepted_tokens_num", "produced_non_pad_tokens", "model_input_lines_num", "b_sz", "n_drafts")
 
     def _counter_values(self) -> dict:
@@ -391,7 +424,8 @@ class TranslationInferenceBeamSearchSpeculative:
         if not self.smart_drafts_mode:
             self.n_drafts += B * self.requested_drafts_num                       # :434
 
-    def generate(self, src: torch.Tensor) -> torch.Tensor:
+    def generate(self, src: torch.Tensor, return_scores: bool = False):
+        """``return_scores=True``: ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``)."""
         m = self.model
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
@@ -401,10 +435,10 @@ class TranslationInferenceBeamSearchSpeculative:
         N.check(m._lib.ttx_beam_speculative_generate(m.session, src.data_ptr(), B, Ls, C.byref(p), out.data_ptr(), C.byref(st),
                                                      m._stream()))
         self._account(st, B)
-        return out[:, :, :int(st.out_width)].contiguous()
+        return self._scored(src, out[:, :, :int(st.out_width)].contiguous(), return_scores)
 
     def generate_many(self, batches: list, in_flight: int = 4, pool: bool | None = None, on_error: str = "raise",
-                      capacity: int | None = None) -> list:
+                      capacity: int | None = None, return_scores: bool = False) -> list:
         """Several batches on the GPU at once; every returned tensor and the counters are those of per-batch ``generate`` calls.
 
         ``pool`` (default: on for two or more batches, ``TTX_BEAM_POOL=0`` turns it off): the given batches are decoded in slot
@@ -415,7 +449,12 @@ class TranslationInferenceBeamSearchSpeculative:
         given, ``in_flight`` of them at once, one session + stream each (ttx_beam_speculative_generate_many).
 
         ``on_error="skip"``: a batch on which the reference raises (or the ``max_steps`` guard trips) yields ``None`` instead of
-        ending the call; the indices are kept in ``self.last_failed_batches`` — ``generate`` on that batch raises the error."""
+        ending the call; the indices are kept in ``self.last_failed_batches`` — ``generate`` on that batch raises the error.
+
+        ``return_scores=True``: a list of ``(pred, HypothesisScores)`` pairs; a batch that came back ``None`` has ``None``
+        scores."""
+        if return_scores:
+            return self._scored_many(batches, self.generate_many(batches, in_flight, pool, on_error, capacity))
         m = self.model
         if on_error not in ("raise", "skip"):
             raise ValueError("on_error must be 'raise' or 'skip'")

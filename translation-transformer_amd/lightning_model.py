@@ -190,9 +190,14 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         self.native: NativeTransformer | None = None
         self.generator = None
         self._ahead = None
+        self._scores_on = False
         # batches decoded ahead of predict_step (0: decode every batch inside its own predict_step like the reference);
         # not an init_arg, so the reference's YAML files load unchanged — set the attribute or TTX_PREDICT_WINDOW
         self.predict_window = 256
+        # predict_step also scores its hypotheses (NativeTransformer.score_hypotheses) into self.predict_scores[batch_idx];
+        # like predict_window no init_arg — set the attribute or TTX_PREDICT_SCORES=1
+        self.predict_with_scores = False
+        self.predict_scores: dict = {}
         self.report_prediction_time = report_prediction_time
         self.prediction_start_time = None
 
@@ -248,11 +253,27 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         if self.generator is None:
             self.build_native()
         ahead = self._ahead
+        pred = None
         if ahead is not None and dataloader_idx == 0:
             pred = ahead.take(batch["src_tokens"], batch_idx)
-            if pred is not None:
-                return pred
-        return self.generator.generate(batch["src_tokens"])
+        if pred is None:
+            pred = self.generator.generate(batch["src_tokens"])
+        if self._scores_on:
+            self._score_batch(batch["src_tokens"], pred, batch_idx)
+        return pred
+
+    def _score_batch(self, src: torch.Tensor, pred: torch.Tensor, batch_idx: int) -> None:
+        """The batch's HypothesisScores, whether it was decoded ahead or on the spot; the token tensor predict_step returns
+        stays what it was.  Timed with a synchronisation on both sides, so scoring_seconds is the pass's own time."""
+        torch.cuda.synchronize()
+        t0 = timer()
+        sc = self.generator.score(src, pred)
+        torch.cuda.synchronize()
+        self._scoring_seconds += timer() - t0
+        self.predict_scores[batch_idx] = sc
+        self._top1_sum = self._top1_sum + sc.score[:, 0].double().sum()      # kept on the device until the report
+        self._top1_n += int(sc.score.shape[0])
+        self._unfinished = self._unfinished + (~sc.finished).sum()
 
     def _predict_loader(self):
         """The (first) predict dataloader Trainer.predict iterates, or None."""
@@ -274,6 +295,9 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
     def on_predict_start(self) -> None:
         self.build_native()                      # weights are final here (Trainer.predict has loaded --ckpt_path)
         self._ahead = None
+        self._scores_on = bool(self.predict_with_scores) or os.environ.get("TTX_PREDICT_SCORES") == "1"
+        self.predict_scores = {}
+        self._scoring_seconds, self._top1_n, self._top1_sum, self._unfinished = 0.0, 0, 0.0, 0
         window = int(os.environ.get("TTX_PREDICT_WINDOW", str(self.predict_window)))
         if window > 0 and hasattr(self.generator, "generate_many"):
             loader = self._predict_loader()
@@ -306,6 +330,10 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
                 report["accepted_tokens"] = self.generator.accepted_tokens_num
                 report["acceptance_rate"] = round(self.generator.accepted_tokens_num /
                                                   max(1, self.generator.produced_non_pad_tokens), 4)
+        if self._scores_on:
+            report["scoring_seconds"] = round(self._scoring_seconds, 6)
+            report["mean_top1_logprob"] = round(float(self._top1_sum) / max(1, self._top1_n), 6)
+            report["unfinished_hypotheses"] = int(self._unfinished)
         text = json.dumps(report)
         print(text)
         if h.report_prediction_file is not None:

@@ -65,7 +65,22 @@ class TeacherForced(NamedTuple):
     logits: torch.Tensor | None   # fp32 [B, Lt-1, V] when asked for
 
 
+class HypothesisScores(NamedTuple):
+    """Result of ``NativeTransformer.score_hypotheses`` / ``hypothesis_logprobs``: device tensors, nothing copied to the host.
+    For hypothesis ``h = hyp[b, k]`` (column 0, the BOS, is never scored): ``length`` n is the column of the first EOS at a
+    column >= 1 (``finished``), else the last column >= 1 holding a non-PAD token, else 0; ``token_logp[t-1]`` is
+    ``log_softmax(decode_tgt(h[:-1])[t-1])[h[t]]`` for t = 1..n and exactly 0 beyond; ``score`` is their sum."""
+    score: torch.Tensor              # fp32 [B, N]: log-likelihood of the hypothesis under the model (0.0 for an all-PAD row)
+    length: torch.Tensor             # int32 [B, N]: scored tokens, the EOS included
+    finished: torch.Tensor           # bool [B, N]: the hypothesis holds an EOS
+    token_logp: torch.Tensor | None  # fp32 [B, N, W-1] when asked for
+
+
 class NativeTransformer:
+    # score_hypotheses: decoder positions (rows x columns) of one call; the widest activation buffer takes ff_dim floats per
+    # position (256 MiB at ff_dim 2048), and a bench batch of 32 rows x 199 columns still fits one call
+    SCORE_MAX_ROWS = 32768
+
     def __init__(self, state_dict: dict | None, num_heads: int, pad_token_idx: int = 0, device: int | str | torch.device = 0,
                  max_positions: int = 5000, layer_norm_eps: float = 1e-5, shape: dict | None = None):
         """``state_dict``: the reference's state dict (weights are packed into one HBM blob).  ``state_dict=None`` with
@@ -190,6 +205,9 @@ class NativeTransformer:
                                               float(eps), self._stream()))
 
     def close(self) -> None:
+        if getattr(self, "_score_session", None):
+            self._lib.ttx_session_destroy(self._score_session)
+            self._score_session = None
         for extra in getattr(self, "_pool", [])[1:]:
             self._lib.ttx_session_destroy(extra)
         self._pool = None
@@ -296,6 +314,89 @@ class NativeTransformer:
         N.check(self._lib.ttx_token_metrics(self._session, x.data_ptr(), tgt.data_ptr(), B, T + 1, V, int(eos_token_idx),
                                             pred.data_ptr(), nll.data_ptr(), out.data_ptr(), self._stream()))
         return TeacherForced(out[0], out[1], out[2], pred, nll, x)
+
+    # -- log-likelihood scores of hypotheses ----------------------------------------------------
+    def _scoring_session(self) -> C.c_void_p:
+        """Scoring runs on a session of its own: its activation buffers are sized by whole hypotheses, and growing a buffer of
+        a decoding session would drop that session's captured graphs."""
+        if getattr(self, "_score_session", None) is None:
+            self._score_session = self.new_session()
+        return self._score_session
+
+    def hypothesis_logprobs(self, logits: torch.Tensor, hyp: torch.Tensor, pad: int, eos: int) -> HypothesisScores:
+        """The scoring stage alone (ttx_hypothesis_logprobs): ``logits`` fp32 [..., W-1, V] as ``decode_tgt(hyp[..., :-1])``
+        gives them, ``hyp`` Long[..., W] with the same leading shape.  Nothing is synchronised."""
+        x = logits.to(self.device, torch.float32).contiguous()
+        hyp = self._tokens(hyp)
+        lead, W = tuple(hyp.shape[:-1]), int(hyp.shape[-1])
+        if hyp.dim() < 2 or W < 2 or tuple(x.shape[:-1]) != lead + (W - 1,):
+            raise ValueError(f"hypothesis_logprobs needs hyp [..., W >= 2] for logits [..., W-1, V]; got {tuple(hyp.shape)} for "
+                             f"{tuple(x.shape)}")
+        V = int(x.shape[-1])
+        self.check_tokens(hyp, V)
+        R = hyp.numel() // W
+        tok = torch.empty(lead + (W - 1,), dtype=torch.float32, device=self.device)
+        score = torch.empty(lead, dtype=torch.float32, device=self.device)
+        length = torch.empty(lead, dtype=torch.int32, device=self.device)
+        fin = torch.empty(lead, dtype=torch.bool, device=self.device)
+        N.check(self._lib.ttx_hypothesis_logprobs(self._scoring_session(), x.data_ptr(), hyp.data_ptr(), R, W, V, int(pad), int(eos),
+                                                  tok.data_ptr(), score.data_ptr(), length.data_ptr(), fin.data_ptr(),
+                                                  self._stream()))
+        return HypothesisScores(score, length, fin, tok)
+
+    def score_hypotheses(self, src: torch.Tensor, hyp: torch.Tensor, eos_token_idx: int = 2, return_token_logp: bool = False,
+                         max_rows: int | None = None, trim: bool = True, logits_out: torch.Tensor | None = None) -> HypothesisScores:
+        """Log-likelihood of every hypothesis ``hyp[b, k]`` (Long[B, N, W], as the generators return them) of source ``src[b]``
+        under the model: the encoder once per source, ONE teacher-forced decoder pass over the B*N rows and the scoring stage
+        (ttx_score_hypotheses).  The same scale for the output of every generator.
+
+        ``trim=True`` (default) reads the longest non-PAD extent of the batch and scores only that many columns: generator
+        outputs are PAD-filled to ``max_len`` and the decoder pass would pay for every PAD column.  This is ONE scalar
+        device-to-host read, i.e. one synchronisation; ``trim=False`` never synchronises.  ``token_logp`` keeps the full
+        [B, N, W-1] shape either way, zeros beyond a hypothesis' length.
+
+        ``max_rows`` (default ``SCORE_MAX_ROWS`` = 32768) bounds the decoder positions ``B_chunk * N * (W-1)`` of one library
+        call: whole sources are scored in chunks, so that a look-ahead window of many batches does not size the activation
+        buffers by the whole window.  A single source is never split.
+
+        ``logits_out`` (fp32 [B*N, W-1, V], needs ``trim=False`` and one chunk) receives the decoder's logits."""
+        src, hyp = self._tokens(src), self._tokens(hyp)
+        if src.dim() != 2 or hyp.dim() != 3 or hyp.shape[0] != src.shape[0] or hyp.shape[1] < 1 or hyp.shape[2] < 2:
+            raise ValueError(f"score_hypotheses needs hyp [B, N >= 1, W >= 2] for src [B, Ls]; got {tuple(hyp.shape)} for "
+                             f"{tuple(src.shape)}")
+        self.check_tokens(src)
+        self.check_tokens(hyp, self.tgt_vocab_size)
+        (B, Ls), (_, K, W) = src.shape, hyp.shape
+        pad, eos = self.tgt_pad_token_i, int(eos_token_idx)
+        Wt = W
+        if trim:
+            cols = torch.arange(1, W + 1, device=self.device)
+            Wt = min(W, max(2, int((((hyp != pad) | (hyp == eos)) * cols).amax())))
+        per_src = K * (Wt - 1)
+        limit = min(int(max_rows or self.SCORE_MAX_ROWS), (1 << 24) - 1)
+        chunk = max(1, limit // per_src)
+        if logits_out is not None:
+            if Wt != W or chunk < B or tuple(logits_out.shape) != (B * K, W - 1, self.tgt_vocab_size) \
+                    or logits_out.dtype != torch.float32 or not logits_out.is_contiguous() or logits_out.device != self.device:
+                raise ValueError("logits_out needs trim=False, one chunk and a contiguous fp32 [B*N, W-1, V] device tensor")
+        score = torch.empty((B, K), dtype=torch.float32, device=self.device)
+        length = torch.empty((B, K), dtype=torch.int32, device=self.device)
+        fin = torch.empty((B, K), dtype=torch.bool, device=self.device)
+        tok = None
+        if return_token_logp:
+            tok = (torch.empty if Wt == W else torch.zeros)((B, K, W - 1), dtype=torch.float32, device=self.device)
+        sess, stream = self._scoring_session(), self._stream()
+        for b0 in range(0, B, chunk):
+            b1 = min(B, b0 + chunk)
+            part = None
+            if tok is not None:
+                part = tok[b0:b1] if Wt == W else torch.empty((b1 - b0, K, Wt - 1), dtype=torch.float32, device=self.device)
+            N.check(self._lib.ttx_score_hypotheses(sess, src[b0:b1].data_ptr(), b1 - b0, Ls, hyp[b0:b1].data_ptr(), W, K, Wt, eos,
+                                                   self._ptr(logits_out), self._ptr(part), score[b0:b1].data_ptr(),
+                                                   length[b0:b1].data_ptr(), fin[b0:b1].data_ptr(), stream))
+            if part is not None and Wt != W:
+                tok[b0:b1, :, :Wt - 1] = part
+        return HypothesisScores(score, length, fin, tok)
 
     # -- beam-speculative bookkeeping kernels --------------------------------------------------
     def nucleus_mask(self, logits: torch.Tensor, nucleus: float, max_kept: int, fill: float) -> torch.Tensor:

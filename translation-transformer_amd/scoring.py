@@ -110,6 +110,41 @@ def score_tokens(pred, tgt, pad: int, bos: int, eos: int) -> dict:
     return {"n_queries": B, "n_preds": N, "accuracy": {f"top {k}": 100.0 * float(top[:, k - 1].float().mean()) for k in ks}}
 
 
+def rank_by_score(pred, scores):
+    """The hypotheses of every source reordered by descending score, unfinished ones last, equal scores in their given order.
+    ``pred`` Long[B,N,L]; ``scores``: a HypothesisScores (or anything with ``score`` / ``length`` / ``finished`` [B,N] and an
+    optional ``token_logp`` [B,N,L-1]).  Returns ``(pred, scores, perm)`` reordered, with ``perm`` Long[B,N]: rank -> index of the
+    hypothesis in the input.  Runs on whatever device the tensors are on."""
+    import torch
+    order = torch.argsort(scores.score, dim=1, descending=True, stable=True)         # by score ...
+    fin = scores.finished.bool().gather(1, order)
+    perm = order.gather(1, torch.argsort((~fin).to(torch.int8), dim=1, stable=True))  # ... then finished first, order kept
+    tok = getattr(scores, "token_logp", None)
+    out = type(scores)(scores.score.gather(1, perm), scores.length.gather(1, perm), scores.finished.gather(1, perm),
+                       None if tok is None else tok.gather(1, perm[:, :, None].expand(-1, -1, tok.shape[2])))
+    return pred.gather(1, perm[:, :, None].expand(-1, -1, pred.shape[2])), out, perm
+
+
+def write_scores(filename: str, scores, append: bool = True) -> None:
+    """The side file of the prediction CSV: one line per source, ``score_1,length_1,finished_1,...,score_N,length_N,finished_N``
+    in the order of the CSV's ``prediction_1..N`` columns (scores with 9 significant digits: fp32 round-trips).  The prediction
+    CSV itself, which ``score_csv`` reads, is left as it is."""
+    sc, ln, fin = (t.detach().cpu().tolist() for t in (scores.score, scores.length, scores.finished))
+    with open(filename, "a" if append else "w") as f:
+        for s_row, l_row, f_row in zip(sc, ln, fin):
+            print(",".join(f"{s:.9g},{int(n)},{int(bool(d))}" for s, n, d in zip(s_row, l_row, f_row)), file=f)
+
+
+def read_scores(filename: str) -> list:
+    """What ``write_scores`` wrote: per source a list of ``(score, length, finished)``."""
+    rows = []
+    with open(filename) as f:
+        for line in f:
+            v = line.strip().split(",")
+            rows.append([(float(v[i]), int(v[i + 1]), bool(int(v[i + 2]))) for i in range(0, len(v) - 2, 3)])
+    return rows
+
+
 def _fmt(d: dict) -> str:
     w = max(len(k) for k in d)
     return "\n".join(f"{k.ljust(w)}    {'n/a' if v is None else round(v, 6)}" for k, v in d.items())
