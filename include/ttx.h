@@ -396,6 +396,28 @@ int ttx_debug_finish_ln(ttx_session* s, const float* d_slabs, int n_slabs, int64
                         const float* d_resid, const float* d_g1, const float* d_b1, const float* d_g2, const float* d_b2,
                         const uint8_t* d_row_valid, float* d_y, const int32_t* d_m, int m_max, int d, float eps, void* stream);
 
+/* Test entry point (tests/test_gpu_attn_kernels.py): ONE launch of the attention family on DEVICE operands of the caller.  The
+ * arguments are those of the kernels' argument block (csrc/ttx_common.hip.h: AttnArgs): per head, out = softmax(scale q k^T + mask) v
+ * with d = 32 H, query rows at d_q + row * ldq, key / value rows at d_k / d_v + row * ldkv, output rows d wide.  mode: 0 encoder
+ * (keys masked where tok == pad), 1 full-prefix decoder self-attention (the same, causal), 2 full-prefix cross-attention (memory
+ * row mem_row[g] or g, key_pad 1 = PAD), 3 verify-step self-attention (slot g < n_active is sequence act_idx[g] with front
+ * front[b], token row tok + b * gen_ld, cache row cache_slot[b] or b of kcache / vcache [.., cache_seq_stride] with rows d wide,
+ * and the 1 + N*D step rows g * (1 + N*D) ..), 4 verify-step cross-attention (source row src_of[b] or b, its first src_len[b] or
+ * Lk keys, key_pad 1 = real token).  groups: decoder rows / sources / slots; n_active (step modes) is put into a DecState on the
+ * device, ordered on `stream`, before the launch; max_keys is what production passes to the launcher: the cache capacity (every
+ * front <= max_keys; the caller's promise, like the indices in the device arrays) or the key count Ls.  kernel: 0 the production
+ * choice, 1 k_attn, 2 k_attn2, 3 k_attn3, 4 k_attn3s; kernel_id (optional) receives what was dispatched (1..4).  Nothing is
+ * launched and TTX_ERR_INVALID is returned for arguments a kernel cannot take: a null pointer the mode requires, H <= 0, ldq /
+ * ldkv that are not multiples of 4 or below d, float operands that are not 16-byte aligned, n_active outside [0, groups], max_keys
+ * below L / Lk, and a forced kernel that cannot serve the request (never rerouted): k_attn3 / k_attn3s outside the step modes or
+ * with H % 4 != 0, k_attn3 whose parked partials exceed 64 KB of LDS, k_attn2 beyond 384 staged keys or its LDS limit, k_attn
+ * beyond its LDS limit. */
+int ttx_debug_attn(ttx_session* s, const float* d_q, int ldq, const float* d_k, const float* d_v, int ldkv, float* d_out, int H,
+                   float scale, int L, int Lk, const int32_t* d_tok, int pad, const uint8_t* d_key_pad, const int32_t* d_mem_row,
+                   const int32_t* d_act_idx, const int32_t* d_front, const int32_t* d_src_of, const int32_t* d_src_len,
+                   const float* d_kcache, const float* d_vcache, int64_t cache_seq_stride, const int32_t* d_cache_slot, int gen_ld,
+                   int N, int D, int mode, int groups, int n_active, int max_keys, int kernel, int32_t* kernel_id, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

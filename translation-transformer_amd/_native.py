@@ -134,6 +134,8 @@ SYMBOLS = {
     "ttx_debug_gemm": (C.c_int, [_VP, _VP, _I, _VP, _I, _VP, _VP, _I, _VP, _I, _I, _I, _I, _I, C.c_int64, _I, _I,
                                  C.POINTER(C.c_int32), _VP]),
     "ttx_debug_finish_ln": (C.c_int, [_VP, _VP, _I, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, C.c_float, _VP]),
+    "ttx_debug_attn": (C.c_int, [_VP, _VP, _I, _VP, _VP, _I, _VP, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                 C.c_int64, _VP, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), _VP]),
     "ttx_last_kernel_profile": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
 }
 

@@ -2742,6 +2742,21 @@ extern "C" int ttx_debug_finish_ln(ttx_session* s, const float* d_slabs, int n_s
                       m_max, d, eps, reinterpret_cast<hipStream_t>(stream));
 }
 
+// Test entry point: one attention launch on the caller's device operands (ttx_attn.hip: attn_debug).
+extern "C" int ttx_debug_attn(ttx_session* s, const float* d_q, int ldq, const float* d_k, const float* d_v, int ldkv, float* d_out,
+                              int H, float scale, int L, int Lk, const int32_t* d_tok, int pad, const uint8_t* d_key_pad,
+                              const int32_t* d_mem_row, const int32_t* d_act_idx, const int32_t* d_front, const int32_t* d_src_of,
+                              const int32_t* d_src_len, const float* d_kcache, const float* d_vcache, int64_t cache_seq_stride,
+                              const int32_t* d_cache_slot, int gen_ld, int N, int D, int mode, int groups, int n_active, int max_keys,
+                              int kernel, int32_t* kernel_id, void* stream) {
+  AttnArgs a{};
+  a.q = d_q; a.ldq = ldq; a.k = d_k; a.v = d_v; a.ldkv = ldkv; a.out = d_out; a.scale = scale; a.L = L; a.Lk = Lk;
+  a.tok = d_tok; a.pad = pad; a.key_pad = d_key_pad; a.mem_row = d_mem_row; a.act_idx = d_act_idx; a.front = d_front;
+  a.src_of = d_src_of; a.src_len = d_src_len; a.kcache = d_kcache; a.vcache = d_vcache; a.cache_seq_stride = (long long)cache_seq_stride;
+  a.cache_slot = d_cache_slot; a.gen_ld = gen_ld; a.N = N; a.D = D;
+  return attn_debug(s, a, H, mode, groups, n_active, max_keys, kernel, kernel_id, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int ttx_last_kernel_profile(ttx_session* s, double* gemm_ms, int64_t* gemm_launches, double* empty_pair_ms) {
   if (!s) return fail(TTX_ERR_INVALID, "null session");
   if (gemm_ms) *gemm_ms = s->prof_ms;

@@ -915,16 +915,26 @@ static int launch_attn_mode(ttx_session* s, hipStream_t st, const AttnArgs& a, i
   // step modes: q_per_group = RPS = 1 + N*D rows per running sequence.  Self-attention keys of one workgroup:
   // prefix (< max_keys) + front row + the rows of every draft with a query among its 64 rows.
   const int D = D1 - 1;
+  // test hook (ttx_debug_attn): a forced kernel replaces the choice below and is refused where it cannot serve the launch;
+  // unset (0), want3 and want2 are the production conditions
+  const int force = s->attn_force;
+  const bool want3 = force ? (force == AK_ATTN3 || force == AK_ATTN3S) : !s->attn_fallback;
+  const bool want2 = force ? force == AK_ATTN2 : !s->attn_fallback;
+  if ((force == AK_ATTN3 || force == AK_ATTN3S) && !(step && H % 4 == 0))
+    return fail(TTX_ERR_INVALID, "k_attn3 / k_attn3s serve the step modes with a head count that is a multiple of 4");
   if constexpr (step) {
     // the verify step: one wave per (sequence, head, 32 step rows), registers only — no key-count limit
-    if (H % 4 == 0 && !s->attn_fallback) {
+    if (H % 4 == 0 && want3) {
       // few sequences (a 32-row batch): the key tiles of one (sequence, head) are shared out over the four waves of
       // a workgroup (k_attn3); many (row groups, slot pools): one wave per (sequence, head), streamed (k_attn3s).
       // Bit-identical either way.
       const int qtiles = cdiv(q_per_group, A3_QT);
       const int keys3 = (MODE == ATT_STEP_SELF) ? max_keys + 1 + N * std::max(D, 0) : max_keys;
       const size_t lds3 = sizeof(float) * (size_t)A3_PART * cdiv(keys3, 32);
-      const bool split = s->attn_split != 0 && (s->attn_split > 0 || (long long)groups * H * qtiles < TTX_A3_SPLIT_BELOW) && lds3 <= 64 * 1024;
+      bool split = s->attn_split != 0 && (s->attn_split > 0 || (long long)groups * H * qtiles < TTX_A3_SPLIT_BELOW) && lds3 <= 64 * 1024;
+      if (force == AK_ATTN3 && lds3 > 64 * 1024) return fail(TTX_ERR_INVALID, "k_attn3: the parked tile partials exceed 64 KB of LDS");
+      if (force) split = (force == AK_ATTN3);
+      s->last_attn_kernel = split ? AK_ATTN3 : AK_ATTN3S;
       if (split) {
         hipLaunchKernelGGL((k_attn3<MODE>), dim3(groups, H, qtiles), dim3(256), lds3, st, a);
       } else {
@@ -940,7 +950,10 @@ static int launch_attn_mode(ttx_session* s, hipStream_t st, const AttnArgs& a, i
   const int draft_keys = (D > 0) ? (std::min(N, (A2_QT + D - 2) / D + 1)) * D : 0;
   const int keys2 = (MODE == ATT_STEP_SELF) ? max_keys + 1 + draft_keys : max_keys;
   const size_t lds2 = attn2_lds_bytes(keys2, a2_qcap(q_per_group));
-  if (lds2 <= kAttn2LdsLimit && attn2_fits(keys2) && !s->attn_fallback) {
+  if (force == AK_ATTN2 && !(lds2 <= kAttn2LdsLimit && attn2_fits(keys2)))
+    return fail(TTX_ERR_INVALID, "k_attn2: more keys than its register and LDS images hold");
+  if (lds2 <= kAttn2LdsLimit && attn2_fits(keys2) && want2) {
+    s->last_attn_kernel = AK_ATTN2;
     const int tiles = cdiv(q_per_group, A2_QT);
     if (lds2 > 64 * 1024 && !s->attr_attn2[MODE]) {             // per device: kept per session, set outside graph capture
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn2<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -956,6 +969,7 @@ static int launch_attn_mode(ttx_session* s, hipStream_t st, const AttnArgs& a, i
   if (lds > kAttn2LdsLimit) return fail(TTX_ERR_INVALID, "sequence too long for the attention kernels' LDS score buffer");
   if (lds > 64 * 1024)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  s->last_attn_kernel = AK_ATTN;
   hipLaunchKernelGGL((k_attn<MODE>), dim3(groups, H, cdiv(q_per_group, ATT_MAXQ)), dim3(64), lds, st, a);
   HIP_TRY(hipGetLastError());
   return TTX_OK;
@@ -971,6 +985,66 @@ int launch_attn(int mode, ttx_session* s, hipStream_t st, const AttnArgs& a, int
     case ATT_STEP_CROSS: return launch_attn_mode<ATT_STEP_CROSS>(s, st, a, groups, H, q_per_group, max_keys, N, D1);
   }
   return fail(TTX_ERR_INVALID, "unknown attention mode");
+}
+
+// ------------------------------------------------------------------------------------------------
+// Test entry point (ttx_debug_attn): ONE launch of launch_attn on the caller's device operands.  What the kernels take on trust
+// from the production call sites and the host can see is checked here, so that a test cannot launch a kernel on arguments it
+// cannot handle; the device-side index arrays and the front positions (<= max_keys, as under production's kcap) are the caller's.
+static bool attn_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+int attn_debug(ttx_session* s, const AttnArgs& in, int H, int mode, int groups, int n_active, int max_keys, int kernel,
+               int32_t* kernel_id, hipStream_t st) {
+  if (!s) return fail(TTX_ERR_INVALID, "null session");
+  if (mode < ATT_ENC || mode > ATT_STEP_CROSS || kernel < 0 || kernel > AK_ATTN3S)
+    return fail(TTX_ERR_INVALID, "ttx_debug_attn: mode is 0..4, kernel 0..4");
+  if (H <= 0 || groups <= 0 || max_keys <= 0) return fail(TTX_ERR_INVALID, "ttx_debug_attn: H, groups and max_keys must be positive");
+  const bool step = (mode == ATT_STEP_SELF || mode == ATT_STEP_CROSS);
+  const bool cross = (mode == ATT_FULL_CROSS || mode == ATT_STEP_CROSS);
+  AttnArgs a = in;
+  a.d = H * ATT_DH;
+  if (!a.q || !a.k || !a.v || !a.out) return fail(TTX_ERR_INVALID, "ttx_debug_attn: q, k, v and out are required");
+  if (cross ? !a.key_pad : !a.tok) return fail(TTX_ERR_INVALID, "ttx_debug_attn: self modes need tok, cross modes key_pad");
+  if (step && !a.act_idx) return fail(TTX_ERR_INVALID, "ttx_debug_attn: the step modes need act_idx");
+  if (mode == ATT_STEP_SELF && (!a.front || !a.kcache || !a.vcache))
+    return fail(TTX_ERR_INVALID, "ttx_debug_attn: STEP_SELF needs front, kcache and vcache");
+  if ((a.ldq & 3) || (a.ldkv & 3) || a.ldq < a.d || a.ldkv < a.d)
+    return fail(TTX_ERR_INVALID, "ttx_debug_attn: ldq and ldkv must be multiples of 4 that cover d = 32 H");
+  for (const void* p : {(const void*)a.q, (const void*)a.k, (const void*)a.v, (const void*)a.out, (const void*)a.kcache, (const void*)a.vcache})
+    if (!attn_aligned16(p)) return fail(TTX_ERR_INVALID, "ttx_debug_attn: float operands must be 16-byte aligned");
+  int q_per_group = a.L;
+  if (step) {
+    if (a.N < 1 || a.D < 0) return fail(TTX_ERR_INVALID, "ttx_debug_attn: step modes need N >= 1 and D >= 0");
+    if (n_active < 0 || n_active > groups) return fail(TTX_ERR_INVALID, "ttx_debug_attn: n_active must lie in [0, groups]");
+    if (mode == ATT_STEP_SELF && (a.gen_ld <= 0 || a.cache_seq_stride <= 0 || (a.cache_seq_stride & 3)))
+      return fail(TTX_ERR_INVALID, "ttx_debug_attn: STEP_SELF needs gen_ld > 0 and a cache_seq_stride that is a positive multiple of 4");
+    q_per_group = step_rps(a.N, a.D);
+  } else if (a.L <= 0 || (mode != ATT_FULL_CROSS && max_keys < a.L)) {
+    return fail(TTX_ERR_INVALID, "ttx_debug_attn: L must be positive and max_keys cover it");
+  }
+  if (cross && (a.Lk <= 0 || max_keys < a.Lk)) return fail(TTX_ERR_INVALID, "ttx_debug_attn: Lk must be positive and max_keys cover it");
+  HIP_TRY(hipSetDevice(s->m->device));
+  DecState* dst = nullptr;
+  if (step) {
+    // n_active reaches the kernels as production hands it over: in a DecState on the device, written on the launch's stream
+    HIP_TRY(hipMalloc((void**)&dst, sizeof(DecState)));
+    hipError_t e = hipMemsetAsync(dst, 0, sizeof(DecState), st);
+    if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&dst->n_active), n_active, 1, st);
+    if (e != hipSuccess) { (void)hipFree(dst); HIP_TRY(e); }
+    a.st = dst;
+  }
+  const int keep = s->attn_force;
+  s->attn_force = kernel;
+  s->last_attn_kernel = 0;
+  int rc = launch_attn(mode, s, st, a, groups, H, q_per_group, max_keys, step ? a.N : 1, step ? a.D + 1 : 1);
+  s->attn_force = keep;
+  if (dst) {
+    const hipError_t e = hipStreamSynchronize(st);     // the launch reads the state: keep it until the launch is through
+    (void)hipFree(dst);
+    if (rc == TTX_OK) HIP_TRY(e);
+  }
+  if (rc == TTX_OK && kernel_id) *kernel_id = s->last_attn_kernel;
+  return rc;
 }
 
 }  // namespace ttx

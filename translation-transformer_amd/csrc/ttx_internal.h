@@ -62,6 +62,9 @@ enum GemmVariant { GV_BIG = 0, GV_SMALL = 1, GV_BIG_FFN2_SLABS = 2, GV_MID = 3 }
 enum GemmKernelId { GK_GEMM3 = 1, GK_GEMM_TN = 2, GK_GEMM24_4 = 3, GK_GEMM24_0 = 4, GK_GEMM2_1 = 5, GK_GEMM2_2 = 6, GK_GEMM2_4 = 7,
                     GK_GEMM2_0 = 8, GK_BODY_128x64 = 16 };
 
+// Kernel of an attention launch as ttx_debug_attn selects and reports it (include/ttx.h).
+enum AttnKernelId { AK_ATTN = 1, AK_ATTN2 = 2, AK_ATTN3 = 3, AK_ATTN3S = 4 };
+
 struct GraphKey {
   int B, Ls, N, D, max_len, mode, kcap, variant;   // mode: 0 speculative, 1 plain greedy, 2 per-row rule, 3 slot pool
   bool operator<(const GraphKey& o) const {
@@ -140,6 +143,8 @@ struct ttx_session {
   int last_gemm_kernel = 0, last_gemm_big_min_tiles = 0;
   int attn_split = -1;             // -1 by launch size, 0 never, 1 always (key tiles of a head over 4 waves)
   bool attn_fallback = false;      // TTX_ATTN_FALLBACK=1 (test hook): every attention launch on the streaming kernel k_attn
+  int attn_force = 0;              // ttx_debug_attn (test hook): an AttnKernelId that replaces launch_attn's choice; 0 (always, outside that call): unset
+  int last_attn_kernel = 0;        // what the most recent launch_attn dispatched (AttnKernelId): ttx_debug_attn reports it
   // profiling of the GEMM launches (bench.py roofline): a HIP event pair around every GEMM launch
   bool profile = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
@@ -217,5 +222,9 @@ int gemm_bench(ttx_session* s, int M, int N, int K, int splits, int variant, int
 // 1 + N*D step rows of a sequence); for the step modes `D1`/`N` shape the draft tiles.
 int launch_attn(int mode, ttx_session* s, hipStream_t st, const AttnArgs& a, int groups, int H, int q_per_group, int max_keys,
                 int N = 1, int D1 = 1);
+// ttx_debug_attn (include/ttx.h): host-side validation, n_active into a DecState on the device, then one launch_attn with
+// `kernel` (0 or an AttnKernelId) in ttx_session::attn_force; `in.d` and `in.st` are filled in here
+int attn_debug(ttx_session* s, const AttnArgs& in, int H, int mode, int groups, int n_active, int max_keys, int kernel,
+               int32_t* kernel_id, hipStream_t st);
 
 }  // namespace ttx

@@ -204,6 +204,27 @@ class NativeTransformer:
                                               self._ptr(row_valid), y.data_ptr(), self._ptr(m_live), int(m_max), int(d),
                                               float(eps), self._stream()))
 
+    def debug_attn(self, mode: int, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, heads: int, scale: float,
+                   groups: int, max_keys: int, L: int = 0, Lk: int = 0, tok: torch.Tensor | None = None, pad: int = 0,
+                   key_pad: torch.Tensor | None = None, mem_row: torch.Tensor | None = None, act_idx: torch.Tensor | None = None,
+                   front: torch.Tensor | None = None, src_of: torch.Tensor | None = None, src_len: torch.Tensor | None = None,
+                   kcache: torch.Tensor | None = None, vcache: torch.Tensor | None = None, cache_seq_stride: int = 0,
+                   cache_slot: torch.Tensor | None = None, gen_ld: int = 0, n: int = 1, d: int = 0, n_active: int = 0,
+                   kernel: int = 0) -> int:
+        """One attention launch on the caller's device tensors (ttx_debug_attn): ``q`` / ``k`` / ``v`` are 2-D fp32 views whose row
+        strides are the leading dimensions (``k`` and ``v`` share theirs), ``out`` has rows of 32 * ``heads`` floats; index and
+        token tensors are int32, ``key_pad`` uint8.  ``kernel``: 0 the production choice, 1 k_attn, 2 k_attn2, 3 k_attn3,
+        4 k_attn3s.  Returns the kernel that ran; arguments a kernel cannot take raise TtxError (TTX_ERR_INVALID)."""
+        kid = C.c_int32(0)
+        assert k.stride(0) == v.stride(0)
+        N.check(self._lib.ttx_debug_attn(self._session, q.data_ptr(), q.stride(0), k.data_ptr(), v.data_ptr(), k.stride(0),
+                                         out.data_ptr(), int(heads), float(scale), int(L), int(Lk), self._ptr(tok), int(pad),
+                                         self._ptr(key_pad), self._ptr(mem_row), self._ptr(act_idx), self._ptr(front),
+                                         self._ptr(src_of), self._ptr(src_len), self._ptr(kcache), self._ptr(vcache),
+                                         int(cache_seq_stride), self._ptr(cache_slot), int(gen_ld), int(n), int(d), int(mode),
+                                         int(groups), int(n_active), int(max_keys), int(kernel), C.byref(kid), self._stream()))
+        return int(kid.value)
+
     def close(self) -> None:
         if getattr(self, "_score_session", None):
             self._lib.ttx_session_destroy(self._score_session)
