@@ -41,7 +41,7 @@ typedef struct ttx_config {
   int32_t vocab_size;           /* tgt (= src when shared) vocabulary                          */
   int32_t src_vocab_size;
   int32_t embedding_dim;        /* d: multiple of 64, <= 1024                                  */
-  int32_t num_heads;            /* d / num_heads must be 32                                    */
+  int32_t num_heads;            /* divides d; d / num_heads (head dimension) must be 32 or 64  */
   int32_t feedforward_dim;      /* multiple of 64                                              */
   int32_t num_encoder_layers;
   int32_t num_decoder_layers;
@@ -411,12 +411,29 @@ int ttx_debug_finish_ln(ttx_session* s, const float* d_slabs, int n_slabs, int64
  * ldkv that are not multiples of 4 or below d, float operands that are not 16-byte aligned, n_active outside [0, groups], max_keys
  * below L / Lk, and a forced kernel that cannot serve the request (never rerouted): k_attn3 / k_attn3s outside the step modes or
  * with H % 4 != 0, k_attn3 whose parked partials exceed 64 KB of LDS, k_attn2 beyond 384 staged keys or its LDS limit, k_attn
- * beyond its LDS limit. */
+ * beyond its LDS limit.  This entry point launches at head dimension 32; ttx_debug_attn_hd below takes the head dimension. */
 int ttx_debug_attn(ttx_session* s, const float* d_q, int ldq, const float* d_k, const float* d_v, int ldkv, float* d_out, int H,
                    float scale, int L, int Lk, const int32_t* d_tok, int pad, const uint8_t* d_key_pad, const int32_t* d_mem_row,
                    const int32_t* d_act_idx, const int32_t* d_front, const int32_t* d_src_of, const int32_t* d_src_len,
                    const float* d_kcache, const float* d_vcache, int64_t cache_seq_stride, const int32_t* d_cache_slot, int gen_ld,
                    int N, int D, int mode, int groups, int n_active, int max_keys, int kernel, int32_t* kernel_id, void* stream);
+
+/* ttx_debug_attn at head dimension head_dim (32 or 64; anything else is TTX_ERR_INVALID): d = head_dim * H, every other argument
+ * as above (tests/test_gpu_attn_hd64.py).  k_attn3 / k_attn3s exist at head dimension 32 only: forced at 64 they are refused,
+ * and the production choice for a step mode is then k_attn2 (k_attn beyond its capacity) whatever H is.  k_attn2 stages at most
+ * ttx_attn_staged_key_limit keys. */
+int ttx_debug_attn_hd(ttx_session* s, const float* d_q, int ldq, const float* d_k, const float* d_v, int ldkv, float* d_out, int H,
+                      int head_dim, float scale, int L, int Lk, const int32_t* d_tok, int pad, const uint8_t* d_key_pad,
+                      const int32_t* d_mem_row, const int32_t* d_act_idx, const int32_t* d_front, const int32_t* d_src_of,
+                      const int32_t* d_src_len, const float* d_kcache, const float* d_vcache, int64_t cache_seq_stride,
+                      const int32_t* d_cache_slot, int gen_ld, int N, int D, int mode, int groups, int n_active, int max_keys,
+                      int kernel, int32_t* kernel_id, void* stream);
+
+/* Host query, no device needed: the number of keys one k_attn2 workgroup can stage at head dimension head_dim when a group has
+ * q_per_group query rows (up to 32 rows share one query image, more take the 64-row one): 384 at head dimension 32, 320 at 64;
+ * 0 for a head dimension without kernels.  A launch whose key count (step self-attention: cache capacity + 1 + the draft rows
+ * of a 64-row tile) exceeds it runs on k_attn. */
+int ttx_attn_staged_key_limit(int head_dim, int q_per_group);
 
 #ifdef __cplusplus
 }

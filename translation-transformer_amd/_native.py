@@ -136,6 +136,9 @@ SYMBOLS = {
     "ttx_debug_finish_ln": (C.c_int, [_VP, _VP, _I, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, C.c_float, _VP]),
     "ttx_debug_attn": (C.c_int, [_VP, _VP, _I, _VP, _VP, _I, _VP, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                  C.c_int64, _VP, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), _VP]),
+    "ttx_debug_attn_hd": (C.c_int, [_VP, _VP, _I, _VP, _VP, _I, _VP, _I, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                    _VP, C.c_int64, _VP, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), _VP]),
+    "ttx_attn_staged_key_limit": (C.c_int, [_I, _I]),
     "ttx_last_kernel_profile": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
 }
 

@@ -38,8 +38,8 @@ static int build_layout(ttx_model* m) {
   const size_t d = c.embedding_dim, F = c.feedforward_dim, V = c.vocab_size, Vs = c.src_vocab_size;
   if (c.embedding_dim <= 0 || c.embedding_dim % 64 || c.embedding_dim > 1024)
     return fail(TTX_ERR_INVALID, "embedding_dim must be a multiple of 64 in [64,1024]");
-  if (c.num_heads <= 0 || c.embedding_dim / c.num_heads != ATT_DH || c.embedding_dim % c.num_heads)
-    return fail(TTX_ERR_INVALID, "embedding_dim / num_heads must be 32");
+  if (c.num_heads <= 0 || c.embedding_dim % c.num_heads || (c.embedding_dim / c.num_heads != 32 && c.embedding_dim / c.num_heads != 64))
+    return fail(TTX_ERR_INVALID, "embedding_dim / num_heads must be 32 or 64");
   const int vpl = c.embedding_dim / 64;
   if (vpl != 1 && vpl != 2 && vpl != 4 && vpl != 8 && vpl != 16)
     return fail(TTX_ERR_INVALID, "embedding_dim must be 64, 128, 256, 512 or 1024");
@@ -412,7 +412,7 @@ static int run_encoder(ttx_session* s, hipStream_t st, const int* tok, const uin
     TTX_TRY(launch_gemm(s, st, x, d, m->p(w.sa_in_w), d, m->p(w.sa_in_b), qkv, 3 * d, nullptr, M, 3 * d, d, false, 0, 0, gv));
     AttnArgs a{};
     a.q = qkv; a.ldq = 3 * d; a.k = qkv + d; a.v = qkv + 2 * d; a.ldkv = 3 * d; a.out = ao; a.d = d;
-    a.scale = 1.0f / sqrtf((float)ATT_DH); a.L = Ls; a.tok = tok; a.pad = c.pad_token;
+    a.scale = 1.0f / sqrtf((float)(d / H)); a.L = Ls; a.tok = tok; a.pad = c.pad_token;
     TTX_TRY(launch_attn(ATT_ENC, s, st, a, B, H, Ls, Ls));
     TTX_TRY(gemm_ln(s, st, ao, d, d, m->p(w.sa_out_w), m->p(w.sa_out_b), x, m->p(w.n1_w), m->p(w.n1_b), nullptr, nullptr,
                     nullptr, x1, nullptr, M, gv));
@@ -461,7 +461,7 @@ static int run_decoder_full(ttx_session* s, hipStream_t st, const int* tok, int 
   float* q2 = s->q2.as<float>();
   float* hb = s->hbuf.as<float>();
   float* ckv = s->ckv.as<float>();
-  const float scale = 1.0f / sqrtf((float)ATT_DH);
+  const float scale = 1.0f / sqrtf((float)(d / H));
   EmbedArgs e{};
   e.table = m->p(m->tgt_emb); e.pe = m->p(m->pe); e.X = x; e.d = d; e.V = c.vocab_size; e.tok = tok; e.rows = M; e.L = Lt;
   hipLaunchKernelGGL((k_embed<false>), dim3(cdiv(M, 4)), dim3(256), 0, st, e);
@@ -747,7 +747,7 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
   float* q2 = s->q2.as<float>();
   float* hb = s->hbuf.as<float>();
   float* logits = s->logits.as<float>();
-  const float scale = 1.0f / sqrtf((float)ATT_DH);
+  const float scale = 1.0f / sqrtf((float)(d / H));
   const long long qkv_layer = (long long)Mmax * 3 * d;
   const long long cache_seq = (long long)k.Lc * d;
   const long long cache_layer = (long long)k.B * cache_seq;
@@ -2743,19 +2743,32 @@ extern "C" int ttx_debug_finish_ln(ttx_session* s, const float* d_slabs, int n_s
 }
 
 // Test entry point: one attention launch on the caller's device operands (ttx_attn.hip: attn_debug).
+extern "C" int ttx_debug_attn_hd(ttx_session* s, const float* d_q, int ldq, const float* d_k, const float* d_v, int ldkv, float* d_out,
+                                 int H, int head_dim, float scale, int L, int Lk, const int32_t* d_tok, int pad, const uint8_t* d_key_pad,
+                                 const int32_t* d_mem_row, const int32_t* d_act_idx, const int32_t* d_front, const int32_t* d_src_of,
+                                 const int32_t* d_src_len, const float* d_kcache, const float* d_vcache, int64_t cache_seq_stride,
+                                 const int32_t* d_cache_slot, int gen_ld, int N, int D, int mode, int groups, int n_active, int max_keys,
+                                 int kernel, int32_t* kernel_id, void* stream) {
+  AttnArgs a{};
+  a.q = d_q; a.ldq = ldq; a.k = d_k; a.v = d_v; a.ldkv = ldkv; a.out = d_out; a.scale = scale; a.L = L; a.Lk = Lk;
+  a.tok = d_tok; a.pad = pad; a.key_pad = d_key_pad; a.mem_row = d_mem_row; a.act_idx = d_act_idx; a.front = d_front;
+  a.src_of = d_src_of; a.src_len = d_src_len; a.kcache = d_kcache; a.vcache = d_vcache; a.cache_seq_stride = (long long)cache_seq_stride;
+  a.cache_slot = d_cache_slot; a.gen_ld = gen_ld; a.N = N; a.D = D;
+  return attn_debug(s, a, H, head_dim, mode, groups, n_active, max_keys, kernel, kernel_id, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int ttx_debug_attn(ttx_session* s, const float* d_q, int ldq, const float* d_k, const float* d_v, int ldkv, float* d_out,
                               int H, float scale, int L, int Lk, const int32_t* d_tok, int pad, const uint8_t* d_key_pad,
                               const int32_t* d_mem_row, const int32_t* d_act_idx, const int32_t* d_front, const int32_t* d_src_of,
                               const int32_t* d_src_len, const float* d_kcache, const float* d_vcache, int64_t cache_seq_stride,
                               const int32_t* d_cache_slot, int gen_ld, int N, int D, int mode, int groups, int n_active, int max_keys,
                               int kernel, int32_t* kernel_id, void* stream) {
-  AttnArgs a{};
-  a.q = d_q; a.ldq = ldq; a.k = d_k; a.v = d_v; a.ldkv = ldkv; a.out = d_out; a.scale = scale; a.L = L; a.Lk = Lk;
-  a.tok = d_tok; a.pad = pad; a.key_pad = d_key_pad; a.mem_row = d_mem_row; a.act_idx = d_act_idx; a.front = d_front;
-  a.src_of = d_src_of; a.src_len = d_src_len; a.kcache = d_kcache; a.vcache = d_vcache; a.cache_seq_stride = (long long)cache_seq_stride;
-  a.cache_slot = d_cache_slot; a.gen_ld = gen_ld; a.N = N; a.D = D;
-  return attn_debug(s, a, H, mode, groups, n_active, max_keys, kernel, kernel_id, reinterpret_cast<hipStream_t>(stream));
+  return ttx_debug_attn_hd(s, d_q, ldq, d_k, d_v, ldkv, d_out, H, 32, scale, L, Lk, d_tok, pad, d_key_pad, d_mem_row, d_act_idx, d_front,
+                           d_src_of, d_src_len, d_kcache, d_vcache, cache_seq_stride, d_cache_slot, gen_ld, N, D, mode, groups, n_active,
+                           max_keys, kernel, kernel_id, stream);
 }
+
+extern "C" int ttx_attn_staged_key_limit(int head_dim, int q_per_group) { return attn_staged_key_limit(head_dim, q_per_group); }
 
 extern "C" int ttx_last_kernel_profile(ttx_session* s, double* gemm_ms, int64_t* gemm_launches, double* empty_pair_ms) {
   if (!s) return fail(TTX_ERR_INVALID, "null session");

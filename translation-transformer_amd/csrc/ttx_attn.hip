@@ -15,22 +15,22 @@ namespace ttx {
 constexpr int ATT_MAXQ = 16;
 constexpr int ATT_SQ = ATT_MAXQ + 1;
 
-__host__ __device__ inline size_t attn_lds_bytes(int max_keys) {
-  return sizeof(float) * ((size_t)ATT_MAXQ * ATT_DH + (size_t)max_keys * ATT_SQ + ATT_MAXQ);
+__host__ __device__ inline size_t attn_lds_bytes(int max_keys, int dh) {
+  return sizeof(float) * ((size_t)ATT_MAXQ * dh + (size_t)max_keys * ATT_SQ + ATT_MAXQ);
 }
 
 // keyptr(key, kp, vp): K/V row pointers of key; vis(i, key): may query i (0..nq) see key?
-template <class KeyPtr, class Vis>
+template <int DH, class KeyPtr, class Vis>
 __device__ __forceinline__ void attn_core(const float* __restrict__ q, int ldq, int nq, int nk, KeyPtr keyptr, Vis vis,
                                           float* __restrict__ out, int ldo, float scale, float* lds) {
   const int lane = threadIdx.x & 63;
   float* Qs = lds;                               // [MAXQ][DH]
-  float* S = lds + ATT_MAXQ * ATT_DH;            // [nk][SQ]
+  float* S = lds + ATT_MAXQ * DH;                // [nk][SQ]
   float* inv = S + (size_t)nk * ATT_SQ;          // [MAXQ]
 
-  for (int e = lane * 4; e < nq * ATT_DH; e += 256) {
-    const int i = e / ATT_DH, c = e % ATT_DH;
-    *reinterpret_cast<float4*>(&Qs[i * ATT_DH + c]) = *reinterpret_cast<const float4*>(q + (size_t)i * ldq + c);
+  for (int e = lane * 4; e < nq * DH; e += 256) {
+    const int i = e / DH, c = e % DH;
+    *reinterpret_cast<float4*>(&Qs[i * DH + c]) = *reinterpret_cast<const float4*>(q + (size_t)i * ldq + c);
   }
   __syncthreads();
 
@@ -41,14 +41,14 @@ __device__ __forceinline__ void attn_core(const float* __restrict__ q, int ldq, 
       const float* kp;
       const float* vp;
       keyptr(key, kp, vp);
-      float4 kr[ATT_DH / 4];
+      float4 kr[DH / 4];
 #pragma unroll
-      for (int c = 0; c < ATT_DH / 4; ++c) kr[c] = *reinterpret_cast<const float4*>(kp + 4 * c);
+      for (int c = 0; c < DH / 4; ++c) kr[c] = *reinterpret_cast<const float4*>(kp + 4 * c);
       for (int i = 0; i < nq; ++i) {
-        const float4* qv = reinterpret_cast<const float4*>(&Qs[i * ATT_DH]);
+        const float4* qv = reinterpret_cast<const float4*>(&Qs[i * DH]);
         float dot = 0.f;
 #pragma unroll
-        for (int c = 0; c < ATT_DH / 4; ++c) {
+        for (int c = 0; c < DH / 4; ++c) {
           const float4 qq = qv[c];
           dot = fmaf(kr[c].x, qq.x, dot); dot = fmaf(kr[c].y, qq.y, dot);
           dot = fmaf(kr[c].z, qq.z, dot); dot = fmaf(kr[c].w, qq.w, dot);
@@ -76,13 +76,15 @@ __device__ __forceinline__ void attn_core(const float* __restrict__ q, int ldq, 
   }
   __syncthreads();
 
-  // phase 3: out[i][d] = sum_key P[i][key] V[key][d]; lane = d + 32 * (key parity)
-  const int d = lane & 31, half = lane >> 5;
+  // phase 3: out[i][d] = sum_key P[i][key] V[key][d]; DH = 32: lane = d + 32 * (key parity), the two parities meet in one
+  // exchange; DH = 64: lane = d, every lane walks all keys in order
+  constexpr int KPAR = 64 / DH;
+  const int d = lane & (DH - 1), half = lane / DH;
   float acc[ATT_MAXQ];
 #pragma unroll
   for (int i = 0; i < ATT_MAXQ; ++i) acc[i] = 0.f;
 #pragma unroll 4
-  for (int key = half; key < nk; key += 2) {
+  for (int key = half; key < nk; key += KPAR) {
     const float* kp;
     const float* vp;
     keyptr(key, kp, vp);
@@ -92,8 +94,10 @@ __device__ __forceinline__ void attn_core(const float* __restrict__ q, int ldq, 
     for (int i = 0; i < ATT_MAXQ; ++i)
       if (i < nq) acc[i] = fmaf(pr[i], v, acc[i]);
   }
+  if constexpr (KPAR == 2) {
 #pragma unroll
-  for (int i = 0; i < ATT_MAXQ; ++i) acc[i] += __shfl_xor(acc[i], 32, 64);
+    for (int i = 0; i < ATT_MAXQ; ++i) acc[i] += __shfl_xor(acc[i], 32, 64);
+  }
   if (half == 0) {
 #pragma unroll
     for (int i = 0; i < ATT_MAXQ; ++i)
@@ -105,10 +109,11 @@ __device__ __forceinline__ void attn_core(const float* __restrict__ q, int ldq, 
 
 
 // Streaming fallback for key counts beyond the LDS images of k_attn2: one wave per (group, head, <=16 queries).
-template <int MODE>
+template <int MODE, int DH>
 __global__ __launch_bounds__(64) void k_attn(AttnArgs a) {
+  static_assert(DH == 32 || DH == 64, "k_attn is written for head dimensions 32 and 64");
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int hd = blockIdx.y * ATT_DH;
+  const int hd = blockIdx.y * DH;
   const int q0 = blockIdx.z * ATT_MAXQ;
   const int g = blockIdx.x;
 
@@ -123,7 +128,7 @@ __global__ __launch_bounds__(64) void k_attn(AttnArgs a) {
       const float* kb = a.k + mrow0 * a.ldkv + hd;
       const float* vb = a.v + mrow0 * a.ldkv + hd;
       const int ld = a.ldkv;
-      attn_core(a.q + (row0 + q0) * a.ldq + hd, a.ldq, nq, a.Lk,
+      attn_core<DH>(a.q + (row0 + q0) * a.ldq + hd, a.ldq, nq, a.Lk,
                 [=](int key, const float*& kp, const float*& vp) { kp = kb + (size_t)key * ld; vp = vb + (size_t)key * ld; },
                 [=](int, int key) { return kpad[key] == 0; },
                 a.out + (row0 + q0) * a.d + hd, a.d, a.scale, lds);
@@ -134,7 +139,7 @@ __global__ __launch_bounds__(64) void k_attn(AttnArgs a) {
       const float* vb = a.v + row0 * a.ldkv + hd;
       const int ld = a.ldkv;
       const bool causal = (MODE == ATT_FULL_SELF);
-      attn_core(a.q + (row0 + q0) * a.ldq + hd, a.ldq, nq, causal ? min(a.L, q0 + nq) : a.L,
+      attn_core<DH>(a.q + (row0 + q0) * a.ldq + hd, a.ldq, nq, causal ? min(a.L, q0 + nq) : a.L,
                 [=](int key, const float*& kp, const float*& vp) { kp = kb + (size_t)key * ld; vp = vb + (size_t)key * ld; },
                 [=](int i, int key) { return tk[key] != pad && (!causal || key <= q0 + i); },
                 a.out + (row0 + q0) * a.d + hd, a.d, a.scale, lds);
@@ -158,7 +163,7 @@ __global__ __launch_bounds__(64) void k_attn(AttnArgs a) {
       const int ld = a.ldkv, dd = a.d;
       const bool front_ok = tk[f] != pad;
       // keys: cached prefix [0,f), then every step row of the slot (row 0 = position f, draft rows after it)
-      attn_core(a.q + (srow0 + q0) * a.ldq + hd, a.ldq, nq, f + RPS,
+      attn_core<DH>(a.q + (srow0 + q0) * a.ldq + hd, a.ldq, nq, f + RPS,
                 [=](int key, const float*& kp, const float*& vp) {
                   if (key < f) { kp = kc + (size_t)key * dd; vp = vc + (size_t)key * dd; }
                   else { kp = kb + (size_t)(key - f) * ld; vp = vb + (size_t)(key - f) * ld; }
@@ -180,7 +185,7 @@ __global__ __launch_bounds__(64) void k_attn(AttnArgs a) {
       const int ld = a.ldkv;
       // slot pool: only the slot's own source positions hold data (the rest of its row is stale or uninitialised,
       // and a masked key's V still enters 0 * V)
-      attn_core(a.q + (srow0 + q0) * a.ldq + hd, a.ldq, nq, a.src_len ? a.src_len[b] : a.Lk,
+      attn_core<DH>(a.q + (srow0 + q0) * a.ldq + hd, a.ldq, nq, a.src_len ? a.src_len[b] : a.Lk,
                 [=](int key, const float*& kp, const float*& vp) { kp = kb + (size_t)key * ld; vp = vb + (size_t)key * ld; },
                 [=](int, int key) { return kv[key] != 0; },
                 a.out + (srow0 + q0) * a.d + hd, a.d, a.scale, lds);
@@ -197,22 +202,26 @@ __global__ __launch_bounds__(64) void k_attn(AttnArgs a) {
 // MFMA (32x32x2), key tiles / key ranges split over the 4 waves; softmax by wavefront shuffles.
 constexpr int A2_MT = 32;                  // rows of one MFMA tile
 constexpr int A2_QT = 64;                  // queries per workgroup (two MFMA row tiles share the staged K/V)
-constexpr int A2_LDQ = ATT_DH + 4;         // LDS row stride of Q and K rows (conflict-free ds_read_b128)
+// per head dimension dh (32 or 64):
+__host__ __device__ constexpr int a2_ldq(int dh) { return dh + 4; }                 // LDS row stride of Q and K rows (conflict-free ds_read_b128)
+__host__ __device__ constexpr int a2_op(int dh) { return 4 * A2_MT * (dh + 1); }    // floats of the four waves' partial output tiles (aliased onto the score image)
+// V rows held in registers: 8 keys per step per wave.  dh = 32: 12 steps of one value -> up to 384 keys.  dh = 64: a step holds
+// two values per key (dims r and r + 32); 10 steps = 80 registers -> up to 320 keys, the most whose LDS images (a 64-query
+// launch: 147 584 B; 352 keys would need 160 000 B) stay under the 150 KB limit of the launcher.
+__host__ __device__ constexpr int a2_vsteps(int dh) { return dh == 32 ? 12 : 10; }
 
 __host__ __device__ inline int a2_nkp(int nk) { return (nk + 31) & ~31; }
-constexpr int A2_OP = 4 * A2_MT * 33;      // floats of the four waves' partial output tiles (aliased onto the score image)
-constexpr int A2_VSTEPS = 12;              // V rows held in registers: 8 keys per step per wave -> up to 384 keys
 __host__ __device__ inline int a2_qcap(int q_per_group) { return q_per_group <= A2_MT ? A2_MT : A2_QT; }
-__host__ __device__ inline size_t a2_score_floats(int nkp) {
+__host__ __device__ inline size_t a2_score_floats(int nkp, int dh) {
   const size_t sf = (size_t)A2_MT * (nkp + 4);
-  return sf > (size_t)A2_OP ? sf : (size_t)A2_OP;
+  return sf > (size_t)a2_op(dh) ? sf : (size_t)a2_op(dh);
 }
-__host__ __device__ inline size_t attn2_lds_bytes(int max_keys, int qcap) {
+__host__ __device__ inline size_t attn2_lds_bytes(int max_keys, int qcap, int dh) {
   const size_t nkp = a2_nkp(max_keys);
-  return sizeof(float) * ((size_t)qcap * A2_LDQ + nkp * A2_LDQ + a2_score_floats((int)nkp) + A2_MT) +
+  return sizeof(float) * ((size_t)qcap * a2_ldq(dh) + nkp * a2_ldq(dh) + a2_score_floats((int)nkp, dh) + A2_MT) +
          sizeof(int) * (nkp + A2_QT);
 }
-__host__ __device__ inline bool attn2_fits(int max_keys) { return a2_nkp(max_keys) <= 32 * A2_VSTEPS; }
+__host__ __device__ inline bool attn2_fits(int max_keys, int dh) { return a2_nkp(max_keys) <= 32 * a2_vsteps(dh); }
 
 // Visibility is decided from one int per key and one per query, computed once while staging:
 //   key flag A2_MASKED   masked (PAD key / padding row)
@@ -228,42 +237,56 @@ __device__ __forceinline__ bool a2_visible(int qf, int kf) {
 }
 
 // keyptr(key, kp, vp): branch-free K/V row pointers of key (0 <= key < nk); keyflag(key), qflag(qi): see above.
-template <class KeyPtr, class KeyFlag, class QFlag>
+template <int DH, class KeyPtr, class KeyFlag, class QFlag>
 __device__ __forceinline__ void attn2_core(const float* __restrict__ q, int ldq, int nq, int nk, KeyPtr keyptr, KeyFlag keyflag,
                                            QFlag qflag, float* __restrict__ out, int ldo, float scale, float* lds, int qcap) {
+  constexpr int A2_LDQ = a2_ldq(DH), A2_VSTEPS = a2_vsteps(DH);
+  constexpr int A2_OS = DH + 1;                      // row stride of a partial output tile
+  constexpr int A2_NV = DH / 32;                     // values per key and lane in O = P·V: dims r, r + 32, ...
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
   const int r = lane & 31, h = lane >> 5;
   const int nkp = a2_nkp(nk);
   const int lds_s = nkp + 4;
-  float* Qs = lds;                                   // [qcap][36]
-  float* Ks = Qs + qcap * A2_LDQ;                    // [nkp][36]
+  float* Qs = lds;                                   // [qcap][DH+4]
+  float* Ks = Qs + qcap * A2_LDQ;                    // [nkp][DH+4]
   float* S = Ks + (size_t)nkp * A2_LDQ;              // [32][nkp+4]   scores of the current row tile
-  float* Op = S;                                     // [4 waves][32][33] partial outputs reuse the score image
-  float* inv = S + a2_score_floats(nkp);             // [32]
+  float* Op = S;                                     // [4 waves][32][DH+1] partial outputs reuse the score image
+  float* inv = S + a2_score_floats(nkp, DH);         // [32]
   int* kfl = reinterpret_cast<int*>(inv + A2_MT);    // [nkp]
   int* qfl = kfl + nkp;                              // [64]
 
-  // ---- stage Q, K, V: a row is 32 floats = 8 lanes x float4.  Loads are unconditional (indices are clamped;
-  // rows past nq / nk are masked through the flags) and all of them are requested before the first LDS write.
-  const int lr = t >> 3, lc = (t & 7) * 4;
+  // ---- stage Q, K, V: a row is DH floats = DH/4 lanes x float4, so the 256 threads take A2_RP = 32 (DH = 32) or 16
+  // (DH = 64) rows per pass.  Loads are unconditional (indices are clamped; rows past nq / nk are masked through the
+  // flags) and all of them are requested before the first LDS write.
+  constexpr int A2_LPR = DH / 4, A2_RP = 256 / A2_LPR;
+  constexpr int A2_QP = A2_MT / A2_RP;               // passes over one 32-query row tile
+  const int lr = (unsigned)t / A2_LPR, lc = ((unsigned)t % A2_LPR) * 4;
   typedef float f32x4 __attribute__((ext_vector_type(4)));
-  f32x4 qv0 = *reinterpret_cast<const f32x4*>(q + (size_t)min(lr, nq - 1) * ldq + lc);
-  f32x4 qv1 = qv0;
-  if (qcap > A2_MT) qv1 = *reinterpret_cast<const f32x4*>(q + (size_t)min(lr + 32, nq - 1) * ldq + lc);
-  constexpr int A2_U = 8;                            // passes of 32 keys in flight
+  f32x4 qv0[A2_QP], qv1[A2_QP];
+#pragma unroll
+  for (int p = 0; p < A2_QP; ++p) {
+    qv0[p] = *reinterpret_cast<const f32x4*>(q + (size_t)min(lr + p * A2_RP, nq - 1) * ldq + lc);
+    qv1[p] = qv0[p];
+  }
+  if (qcap > A2_MT) {
+#pragma unroll
+    for (int p = 0; p < A2_QP; ++p)
+      qv1[p] = *reinterpret_cast<const f32x4*>(q + (size_t)min(lr + p * A2_RP + 32, nq - 1) * ldq + lc);
+  }
+  constexpr int A2_U = 8;                            // passes of A2_RP keys in flight
   // V never touches LDS: in O = P·V lane (dh, h) needs V[key][dh] for its wave's keys only, so each wave keeps its
   // nkp/4 value rows in registers (requested here, consumed after the softmax).  Wave w owns the 8-key groups
   // w, w+4, w+8, ...: a fixed interleave, so the order in which a row's keys are summed does not depend on how far
   // the batch's padding extends (masked keys add exact zeros) — results are the same in any batch.
   const int kq = nkp / 4;
-  float vr[A2_VSTEPS][4];
-  for (int k0 = 0; k0 < nkp; k0 += 32 * A2_U) {
+  float vr[A2_NV][A2_VSTEPS][4];
+  for (int k0 = 0; k0 < nkp; k0 += A2_RP * A2_U) {
     f32x4 kv[A2_U];
 #pragma unroll
     for (int u = 0; u < A2_U; ++u) {
       const float* kp;
       const float* vp;
-      keyptr(min(k0 + u * 32 + lr, nk - 1), kp, vp);
+      keyptr(min(k0 + u * A2_RP + lr, nk - 1), kp, vp);
       kv[u] = *reinterpret_cast<const f32x4*>(kp + lc);
     }
     if (k0 == 0) {
@@ -275,7 +298,8 @@ __device__ __forceinline__ void attn2_core(const float* __restrict__ q, int ldq,
             const float* kp;
             const float* vp;
             keyptr(min((wave + 4 * si) * 8 + 4 * h + jj, nk - 1), kp, vp);
-            vr[si][jj] = vp[r];
+#pragma unroll
+            for (int n = 0; n < A2_NV; ++n) vr[n][si][jj] = vp[r + 32 * n];
           }
         }
       }
@@ -288,12 +312,16 @@ __device__ __forceinline__ void attn2_core(const float* __restrict__ q, int ldq,
     asm volatile("" : "+v"(kv[0]), "+v"(kv[1]), "+v"(kv[2]), "+v"(kv[3]), "+v"(kv[4]), "+v"(kv[5]), "+v"(kv[6]), "+v"(kv[7]));
 #pragma unroll
     for (int u = 0; u < A2_U; ++u) {
-      const int key = k0 + u * 32 + lr;
-      if (k0 + u * 32 < nkp) *reinterpret_cast<f32x4*>(&Ks[(size_t)key * A2_LDQ + lc]) = kv[u];
+      const int key = k0 + u * A2_RP + lr;
+      if (k0 + u * A2_RP < nkp) *reinterpret_cast<f32x4*>(&Ks[(size_t)key * A2_LDQ + lc]) = kv[u];
     }
   }
-  *reinterpret_cast<f32x4*>(&Qs[lr * A2_LDQ + lc]) = qv0;
-  if (qcap > A2_MT) *reinterpret_cast<f32x4*>(&Qs[(lr + 32) * A2_LDQ + lc]) = qv1;
+#pragma unroll
+  for (int p = 0; p < A2_QP; ++p) *reinterpret_cast<f32x4*>(&Qs[(lr + p * A2_RP) * A2_LDQ + lc]) = qv0[p];
+  if (qcap > A2_MT) {
+#pragma unroll
+    for (int p = 0; p < A2_QP; ++p) *reinterpret_cast<f32x4*>(&Qs[(lr + p * A2_RP + 32) * A2_LDQ + lc]) = qv1[p];
+  }
   __syncthreads();
 
   const int n_mt = (nq + A2_MT - 1) / A2_MT;         // 1 or 2 row tiles
@@ -311,7 +339,7 @@ __device__ __forceinline__ void attn2_core(const float* __restrict__ q, int ldq,
       const float* ap = &Qs[(q0 + r) * A2_LDQ + 4 * h];
       const float* bp = &Ks[(size_t)(kt * 32 + r) * A2_LDQ + 4 * h];
 #pragma unroll
-      for (int kk = 0; kk < ATT_DH; kk += 8) {
+      for (int kk = 0; kk < DH; kk += 8) {
         const float4 av = *reinterpret_cast<const float4*>(ap + kk);
         const float4 bv = *reinterpret_cast<const float4*>(bp + kk);
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);
@@ -355,31 +383,39 @@ __device__ __forceinline__ void attn2_core(const float* __restrict__ q, int ldq,
     __syncthreads();
 
     // ---- O = P V: wave w takes keys [w*nkp/4, (w+1)*nkp/4) with its V rows from registers; partial sums meet in LDS
+    // (DH = 64: one accumulator per 32 output dims, both fed by the same P values)
     {
-      f32x16 acc;
+      f32x16 acc[A2_NV];
 #pragma unroll
-      for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+      for (int n = 0; n < A2_NV; ++n)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[n][i] = 0.f;
       const float* prow = S + (size_t)r * lds_s + 4 * h + wave * 8;
 #pragma unroll
       for (int si = 0; si < A2_VSTEPS; ++si) {
         if (si * 8 < kq) {
           const float4 pv = *reinterpret_cast<const float4*>(prow + si * 32);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pv.x, vr[si][0], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pv.y, vr[si][1], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pv.z, vr[si][2], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pv.w, vr[si][3], acc, 0, 0, 0);
+#pragma unroll
+          for (int n = 0; n < A2_NV; ++n) {
+            acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(pv.x, vr[n][si][0], acc[n], 0, 0, 0);
+            acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(pv.y, vr[n][si][1], acc[n], 0, 0, 0);
+            acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(pv.z, vr[n][si][2], acc[n], 0, 0, 0);
+            acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(pv.w, vr[n][si][3], acc[n], 0, 0, 0);
+          }
         }
       }
       __syncthreads();                                // every wave has read its P columns: the image becomes Op
-      float* part = Op + (size_t)wave * (A2_MT * 33);
+      float* part = Op + (size_t)wave * (A2_MT * A2_OS);
 #pragma unroll
-      for (int v = 0; v < 16; ++v) part[((v & 3) + 8 * (v >> 2) + 4 * h) * 33 + r] = acc[v];
+      for (int n = 0; n < A2_NV; ++n)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) part[((v & 3) + 8 * (v >> 2) + 4 * h) * A2_OS + r + 32 * n] = acc[n][v];
     }
     __syncthreads();
-    for (int e = t; e < A2_MT * ATT_DH; e += 256) {
-      const int ql = e >> 5, c = e & 31;
-      const float o = Op[ql * 33 + c] + Op[A2_MT * 33 + ql * 33 + c] + Op[2 * A2_MT * 33 + ql * 33 + c] +
-                      Op[3 * A2_MT * 33 + ql * 33 + c];
+    for (int e = t; e < A2_MT * DH; e += 256) {
+      const int ql = (unsigned)e / DH, c = (unsigned)e % DH;
+      const float o = Op[ql * A2_OS + c] + Op[A2_MT * A2_OS + ql * A2_OS + c] + Op[2 * A2_MT * A2_OS + ql * A2_OS + c] +
+                      Op[3 * A2_MT * A2_OS + ql * A2_OS + c];
       if (q0 + ql < nq) out[(size_t)(q0 + ql) * ldo + c] = o * inv[ql];
     }
     if (mt + 1 < n_mt) __syncthreads();               // S, inv and Op are rewritten by the next row tile
@@ -388,10 +424,13 @@ __device__ __forceinline__ void attn2_core(const float* __restrict__ q, int ldq,
 
 // amdgpu_waves_per_eu(1, 2): the LDS images allow at most two workgroups per CU, so let the compiler keep the
 // staging loads in registers (with the default occupancy target it spills them to scratch to stay under 64 VGPRs)
-template <int MODE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_attn2(AttnArgs a) {
+// DH = 64 asks for exactly two: left at (1, 2) the compiler takes 232 VGPRs + 64 AGPRs and one workgroup per CU; held to 256
+// registers it needs 231 - 236 VGPRs, no AGPRs and no scratch
+template <int MODE, int DH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DH == 32 ? 1 : 2, 2))) void k_attn2(AttnArgs a) {
+  static_assert(DH == 32 || DH == 64, "k_attn2 is written for head dimensions 32 and 64");
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int hd = blockIdx.y * ATT_DH;
+  const int hd = blockIdx.y * DH;
   const int tile = blockIdx.z;
   auto q_any = [](int) { return 0; };
 
@@ -407,7 +446,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
       const float* kb = a.k + row0 * a.ldkv + hd;
       const float* vb = a.v + row0 * a.ldkv + hd;
       const int ld = a.ldkv;
-      attn2_core(a.q + (row0 + q0) * a.ldq + hd, a.ldq, nq, a.L,
+      attn2_core<DH>(a.q + (row0 + q0) * a.ldq + hd, a.ldq, nq, a.L,
                  [=](int key, const float*& kp, const float*& vp) { kp = kb + (size_t)key * ld; vp = vb + (size_t)key * ld; },
                  [=](int key) { return tk[key] != pad ? A2_ALL : A2_MASKED; }, q_any,
                  a.out + (row0 + q0) * a.d + hd, a.d, a.scale, lds, a2_qcap(a.L));
@@ -418,7 +457,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
       const float* kb = a.k + mrow0 * a.ldkv + hd;
       const float* vb = a.v + mrow0 * a.ldkv + hd;
       const int ld = a.ldkv;
-      attn2_core(a.q + (row0 + q0) * a.ldq + hd, a.ldq, nq, a.Lk,
+      attn2_core<DH>(a.q + (row0 + q0) * a.ldq + hd, a.ldq, nq, a.Lk,
                  [=](int key, const float*& kp, const float*& vp) { kp = kb + (size_t)key * ld; vp = vb + (size_t)key * ld; },
                  [=](int key) { return kpad[key] == 0 ? A2_ALL : A2_MASKED; }, q_any,
                  a.out + (row0 + q0) * a.d + hd, a.d, a.scale, lds, a2_qcap(a.L));
@@ -434,7 +473,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     const float* kb = a.k + row0 * a.ldkv + hd;
     const float* vb = a.v + row0 * a.ldkv + hd;
     const int ld = a.ldkv;
-    attn2_core(a.q + (row0 + q0) * a.ldq + hd, a.ldq, nq, min(a.L, q0 + nq),
+    attn2_core<DH>(a.q + (row0 + q0) * a.ldq + hd, a.ldq, nq, min(a.L, q0 + nq),
                [=](int key, const float*& kp, const float*& vp) { kp = kb + (size_t)key * ld; vp = vb + (size_t)key * ld; },
                [=](int key) { return tk[key] != pad ? a2_flag(0, key) : A2_MASKED; },
                [=](int qi) { return a2_flag(0, q0 + qi); },
@@ -465,7 +504,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
       const int n_hi = (rlast == 0) ? -1 : (rlast - 1) / D;
       const int kr0 = 1 + n_lo * D;                    // first draft row staged
       const int n_draft_keys = (n_hi >= n_lo && D > 0) ? (n_hi - n_lo + 1) * D : 0;
-      attn2_core(a.q + (srow0 + r0) * a.ldq + hd, a.ldq, nq, f + 1 + n_draft_keys,
+      attn2_core<DH>(a.q + (srow0 + r0) * a.ldq + hd, a.ldq, nq, f + 1 + n_draft_keys,
                  [=](int key, const float*& kp, const float*& vp) {
                    const bool cached = key < f;
                    const int srow = (key == f) ? 0 : kr0 + (key - f - 1);
@@ -492,7 +531,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
       const float* kb = a.k + mrow0 * a.ldkv + hd;
       const float* vb = a.v + mrow0 * a.ldkv + hd;
       const int ld = a.ldkv;
-      attn2_core(a.q + (srow0 + r0) * a.ldq + hd, a.ldq, nq, a.src_len ? a.src_len[b] : a.Lk,   // see k_attn: slot pool
+      attn2_core<DH>(a.q + (srow0 + r0) * a.ldq + hd, a.ldq, nq, a.src_len ? a.src_len[b] : a.Lk,   // see k_attn: slot pool
                  [=](int key, const float*& kp, const float*& vp) { kp = kb + (size_t)key * ld; vp = vb + (size_t)key * ld; },
                  [=](int key) { return kv[key] != 0 ? A2_ALL : A2_MASKED; }, q_any,
                  a.out + (srow0 + r0) * a.d + hd, a.d, a.scale, lds, a2_qcap(RPS));
@@ -908,7 +947,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // ------------------------------------------------------------------------------------------------
 static constexpr size_t kAttn2LdsLimit = 150 * 1024;
 
-template <int MODE>
+template <int MODE, int DH>
 static int launch_attn_mode(ttx_session* s, hipStream_t st, const AttnArgs& a, int groups, int H, int q_per_group, int max_keys, int N, int D1) {
   if (groups <= 0 || q_per_group <= 0) return TTX_OK;
   constexpr bool step = (MODE == ATT_STEP_SELF || MODE == ATT_STEP_CROSS);
@@ -920,10 +959,11 @@ static int launch_attn_mode(ttx_session* s, hipStream_t st, const AttnArgs& a, i
   const int force = s->attn_force;
   const bool want3 = force ? (force == AK_ATTN3 || force == AK_ATTN3S) : !s->attn_fallback;
   const bool want2 = force ? force == AK_ATTN2 : !s->attn_fallback;
-  if ((force == AK_ATTN3 || force == AK_ATTN3S) && !(step && H % 4 == 0))
-    return fail(TTX_ERR_INVALID, "k_attn3 / k_attn3s serve the step modes with a head count that is a multiple of 4");
-  if constexpr (step) {
-    // the verify step: one wave per (sequence, head, 32 step rows), registers only — no key-count limit
+  if ((force == AK_ATTN3 || force == AK_ATTN3S) && !(step && H % 4 == 0 && DH == ATT_DH))
+    return fail(TTX_ERR_INVALID, "k_attn3 / k_attn3s serve the step modes at head dimension 32 with a head count that is a multiple of 4");
+  if constexpr (step && DH == ATT_DH) {
+    // the verify step: one wave per (sequence, head, 32 step rows), registers only — no key-count limit.  Head dimension 32
+    // only: at 64 a step launch takes the route below (k_attn2, k_attn beyond its capacity) whatever H is.
     if (H % 4 == 0 && want3) {
       // few sequences (a 32-row batch): the key tiles of one (sequence, head) are shared out over the four waves of
       // a workgroup (k_attn3); many (row groups, slot pools): one wave per (sequence, head), streamed (k_attn3s).
@@ -949,42 +989,61 @@ static int launch_attn_mode(ttx_session* s, hipStream_t st, const AttnArgs& a, i
   }
   const int draft_keys = (D > 0) ? (std::min(N, (A2_QT + D - 2) / D + 1)) * D : 0;
   const int keys2 = (MODE == ATT_STEP_SELF) ? max_keys + 1 + draft_keys : max_keys;
-  const size_t lds2 = attn2_lds_bytes(keys2, a2_qcap(q_per_group));
-  if (force == AK_ATTN2 && !(lds2 <= kAttn2LdsLimit && attn2_fits(keys2)))
+  const size_t lds2 = attn2_lds_bytes(keys2, a2_qcap(q_per_group), DH);
+  if (force == AK_ATTN2 && !(lds2 <= kAttn2LdsLimit && attn2_fits(keys2, DH)))
     return fail(TTX_ERR_INVALID, "k_attn2: more keys than its register and LDS images hold");
-  if (lds2 <= kAttn2LdsLimit && attn2_fits(keys2) && want2) {
+  if (lds2 <= kAttn2LdsLimit && attn2_fits(keys2, DH) && want2) {
     s->last_attn_kernel = AK_ATTN2;
     const int tiles = cdiv(q_per_group, A2_QT);
-    if (lds2 > 64 * 1024 && !s->attr_attn2[MODE]) {             // per device: kept per session, set outside graph capture
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn2<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    bool& attr_set = s->attr_attn2[DH == ATT_DH ? 0 : 1][MODE];
+    if (lds2 > 64 * 1024 && !attr_set) {                        // per device: kept per session, set outside graph capture
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn2<MODE, DH>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)kAttn2LdsLimit));
-      s->attr_attn2[MODE] = true;
+      attr_set = true;
     }
-    hipLaunchKernelGGL((k_attn2<MODE>), dim3(groups, H, tiles), dim3(256), lds2, st, a);
+    hipLaunchKernelGGL((k_attn2<MODE, DH>), dim3(groups, H, tiles), dim3(256), lds2, st, a);
     HIP_TRY(hipGetLastError());
     return TTX_OK;
   }
   const int keys1 = (MODE == ATT_STEP_SELF) ? max_keys + q_per_group : max_keys;
-  const size_t lds = attn_lds_bytes(keys1);
+  const size_t lds = attn_lds_bytes(keys1, DH);
   if (lds > kAttn2LdsLimit) return fail(TTX_ERR_INVALID, "sequence too long for the attention kernels' LDS score buffer");
   if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn<MODE, DH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   s->last_attn_kernel = AK_ATTN;
-  hipLaunchKernelGGL((k_attn<MODE>), dim3(groups, H, cdiv(q_per_group, ATT_MAXQ)), dim3(64), lds, st, a);
+  hipLaunchKernelGGL((k_attn<MODE, DH>), dim3(groups, H, cdiv(q_per_group, ATT_MAXQ)), dim3(64), lds, st, a);
   HIP_TRY(hipGetLastError());
   return TTX_OK;
 }
 
-int launch_attn(int mode, ttx_session* s, hipStream_t st, const AttnArgs& a, int groups, int H, int q_per_group, int max_keys,
-                int N, int D1) {
+template <int DH>
+static int launch_attn_dh(int mode, ttx_session* s, hipStream_t st, const AttnArgs& a, int groups, int H, int q_per_group, int max_keys,
+                          int N, int D1) {
   switch (mode) {
-    case ATT_ENC: return launch_attn_mode<ATT_ENC>(s, st, a, groups, H, q_per_group, max_keys, N, D1);
-    case ATT_FULL_SELF: return launch_attn_mode<ATT_FULL_SELF>(s, st, a, groups, H, q_per_group, max_keys, N, D1);
-    case ATT_FULL_CROSS: return launch_attn_mode<ATT_FULL_CROSS>(s, st, a, groups, H, q_per_group, max_keys, N, D1);
-    case ATT_STEP_SELF: return launch_attn_mode<ATT_STEP_SELF>(s, st, a, groups, H, q_per_group, max_keys, N, D1);
-    case ATT_STEP_CROSS: return launch_attn_mode<ATT_STEP_CROSS>(s, st, a, groups, H, q_per_group, max_keys, N, D1);
+    case ATT_ENC: return launch_attn_mode<ATT_ENC, DH>(s, st, a, groups, H, q_per_group, max_keys, N, D1);
+    case ATT_FULL_SELF: return launch_attn_mode<ATT_FULL_SELF, DH>(s, st, a, groups, H, q_per_group, max_keys, N, D1);
+    case ATT_FULL_CROSS: return launch_attn_mode<ATT_FULL_CROSS, DH>(s, st, a, groups, H, q_per_group, max_keys, N, D1);
+    case ATT_STEP_SELF: return launch_attn_mode<ATT_STEP_SELF, DH>(s, st, a, groups, H, q_per_group, max_keys, N, D1);
+    case ATT_STEP_CROSS: return launch_attn_mode<ATT_STEP_CROSS, DH>(s, st, a, groups, H, q_per_group, max_keys, N, D1);
   }
   return fail(TTX_ERR_INVALID, "unknown attention mode");
+}
+
+// the head dimension of a launch is a.d / H
+int launch_attn(int mode, ttx_session* s, hipStream_t st, const AttnArgs& a, int groups, int H, int q_per_group, int max_keys,
+                int N, int D1) {
+  if (H > 0 && a.d == H * 32) return launch_attn_dh<32>(mode, s, st, a, groups, H, q_per_group, max_keys, N, D1);
+  if (H > 0 && a.d == H * 64) return launch_attn_dh<64>(mode, s, st, a, groups, H, q_per_group, max_keys, N, D1);
+  return fail(TTX_ERR_INVALID, "attention kernels exist for head dimensions 32 and 64");
+}
+
+// Keys k_attn2 can stage for one workgroup at head dimension `head_dim` when a group has `q_per_group` query rows: the register
+// image of V and the LDS limit, whichever is reached first (ttx_attn_staged_key_limit).
+int attn_staged_key_limit(int head_dim, int q_per_group) {
+  if ((head_dim != 32 && head_dim != 64) || q_per_group <= 0) return 0;
+  int keys = 32 * a2_vsteps(head_dim);
+  while (keys > 0 && attn2_lds_bytes(keys, a2_qcap(q_per_group), head_dim) > kAttn2LdsLimit) keys -= 32;
+  return keys;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -993,23 +1052,24 @@ int launch_attn(int mode, ttx_session* s, hipStream_t st, const AttnArgs& a, int
 // cannot handle; the device-side index arrays and the front positions (<= max_keys, as under production's kcap) are the caller's.
 static bool attn_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-int attn_debug(ttx_session* s, const AttnArgs& in, int H, int mode, int groups, int n_active, int max_keys, int kernel,
+int attn_debug(ttx_session* s, const AttnArgs& in, int H, int head_dim, int mode, int groups, int n_active, int max_keys, int kernel,
                int32_t* kernel_id, hipStream_t st) {
   if (!s) return fail(TTX_ERR_INVALID, "null session");
+  if (head_dim != 32 && head_dim != 64) return fail(TTX_ERR_INVALID, "ttx_debug_attn_hd: head_dim is 32 or 64");
   if (mode < ATT_ENC || mode > ATT_STEP_CROSS || kernel < 0 || kernel > AK_ATTN3S)
     return fail(TTX_ERR_INVALID, "ttx_debug_attn: mode is 0..4, kernel 0..4");
   if (H <= 0 || groups <= 0 || max_keys <= 0) return fail(TTX_ERR_INVALID, "ttx_debug_attn: H, groups and max_keys must be positive");
   const bool step = (mode == ATT_STEP_SELF || mode == ATT_STEP_CROSS);
   const bool cross = (mode == ATT_FULL_CROSS || mode == ATT_STEP_CROSS);
   AttnArgs a = in;
-  a.d = H * ATT_DH;
+  a.d = H * head_dim;
   if (!a.q || !a.k || !a.v || !a.out) return fail(TTX_ERR_INVALID, "ttx_debug_attn: q, k, v and out are required");
   if (cross ? !a.key_pad : !a.tok) return fail(TTX_ERR_INVALID, "ttx_debug_attn: self modes need tok, cross modes key_pad");
   if (step && !a.act_idx) return fail(TTX_ERR_INVALID, "ttx_debug_attn: the step modes need act_idx");
   if (mode == ATT_STEP_SELF && (!a.front || !a.kcache || !a.vcache))
     return fail(TTX_ERR_INVALID, "ttx_debug_attn: STEP_SELF needs front, kcache and vcache");
   if ((a.ldq & 3) || (a.ldkv & 3) || a.ldq < a.d || a.ldkv < a.d)
-    return fail(TTX_ERR_INVALID, "ttx_debug_attn: ldq and ldkv must be multiples of 4 that cover d = 32 H");
+    return fail(TTX_ERR_INVALID, "ttx_debug_attn: ldq and ldkv must be multiples of 4 that cover d = head_dim * H");
   for (const void* p : {(const void*)a.q, (const void*)a.k, (const void*)a.v, (const void*)a.out, (const void*)a.kcache, (const void*)a.vcache})
     if (!attn_aligned16(p)) return fail(TTX_ERR_INVALID, "ttx_debug_attn: float operands must be 16-byte aligned");
   int q_per_group = a.L;

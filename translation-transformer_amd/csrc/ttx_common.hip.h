@@ -76,7 +76,8 @@ struct FinishArgs {
 };
 
 // ------------------------------------------------------------------------------------------------
-constexpr int ATT_DH = 32;                  // head dimension every attention kernel is written for
+// Head dimensions: k_attn and k_attn2 are templates over DH in {32, 64}; k_attn3 / k_attn3s are written for ATT_DH only.
+constexpr int ATT_DH = 32;
 enum AttnMode { ATT_ENC = 0, ATT_FULL_SELF = 1, ATT_FULL_CROSS = 2, ATT_STEP_SELF = 3, ATT_STEP_CROSS = 4 };
 
 // Step-mode row layout (one verify step): a running sequence ("slot") owns RPS = 1 + N*D consecutive rows:

@@ -129,7 +129,7 @@ struct ttx_session {
   void graphs_current() { if (graphs_generation != alloc_generation) { drop_graphs(); graphs_generation = alloc_generation; } }
   ttx::DecState* host_state = nullptr;  // pinned copy target
   // function attributes (dynamic LDS limits) are per device: set once per session, outside graph capture
-  bool attr_attn2[8] = {false, false, false, false, false, false, false, false};
+  bool attr_attn2[2][8] = {};      // [head dimension 32 / 64][mode]
   bool attr_select = false, attr_step = false, attr_topk = false, attr_pool_select = false;
   // GEMM policy (all choices are between bit-identical evaluations, see GemmVariant)
   int qkv_small_rows = 800;        // a verify step with fewer live rows than this runs under GV_SMALL (TTX_QKV_SMALL_ROWS)
@@ -222,9 +222,11 @@ int gemm_bench(ttx_session* s, int M, int N, int K, int splits, int variant, int
 // 1 + N*D step rows of a sequence); for the step modes `D1`/`N` shape the draft tiles.
 int launch_attn(int mode, ttx_session* s, hipStream_t st, const AttnArgs& a, int groups, int H, int q_per_group, int max_keys,
                 int N = 1, int D1 = 1);
-// ttx_debug_attn (include/ttx.h): host-side validation, n_active into a DecState on the device, then one launch_attn with
+// ttx_debug_attn / ttx_debug_attn_hd (include/ttx.h): host-side validation, n_active into a DecState on the device, then one launch_attn with
 // `kernel` (0 or an AttnKernelId) in ttx_session::attn_force; `in.d` and `in.st` are filled in here
-int attn_debug(ttx_session* s, const AttnArgs& in, int H, int mode, int groups, int n_active, int max_keys, int kernel,
+int attn_debug(ttx_session* s, const AttnArgs& in, int H, int head_dim, int mode, int groups, int n_active, int max_keys, int kernel,
                int32_t* kernel_id, hipStream_t st);
+// ttx_attn_staged_key_limit (include/ttx.h); 0 for a head dimension without kernels
+int attn_staged_key_limit(int head_dim, int q_per_group);
 
 }  // namespace ttx

@@ -210,20 +210,27 @@ class NativeTransformer:
                    front: torch.Tensor | None = None, src_of: torch.Tensor | None = None, src_len: torch.Tensor | None = None,
                    kcache: torch.Tensor | None = None, vcache: torch.Tensor | None = None, cache_seq_stride: int = 0,
                    cache_slot: torch.Tensor | None = None, gen_ld: int = 0, n: int = 1, d: int = 0, n_active: int = 0,
-                   kernel: int = 0) -> int:
-        """One attention launch on the caller's device tensors (ttx_debug_attn): ``q`` / ``k`` / ``v`` are 2-D fp32 views whose row
-        strides are the leading dimensions (``k`` and ``v`` share theirs), ``out`` has rows of 32 * ``heads`` floats; index and
-        token tensors are int32, ``key_pad`` uint8.  ``kernel``: 0 the production choice, 1 k_attn, 2 k_attn2, 3 k_attn3,
-        4 k_attn3s.  Returns the kernel that ran; arguments a kernel cannot take raise TtxError (TTX_ERR_INVALID)."""
+                   kernel: int = 0, head_dim: int = 32) -> int:
+        """One attention launch on the caller's device tensors (ttx_debug_attn_hd): ``q`` / ``k`` / ``v`` are 2-D fp32 views whose
+        row strides are the leading dimensions (``k`` and ``v`` share theirs), ``out`` has rows of ``head_dim`` * ``heads`` floats
+        (``head_dim`` 32 or 64); index and token tensors are int32, ``key_pad`` uint8.  ``kernel``: 0 the production choice,
+        1 k_attn, 2 k_attn2, 3 k_attn3, 4 k_attn3s.  Returns the kernel that ran; arguments a kernel cannot take raise TtxError
+        (TTX_ERR_INVALID)."""
         kid = C.c_int32(0)
         assert k.stride(0) == v.stride(0)
-        N.check(self._lib.ttx_debug_attn(self._session, q.data_ptr(), q.stride(0), k.data_ptr(), v.data_ptr(), k.stride(0),
-                                         out.data_ptr(), int(heads), float(scale), int(L), int(Lk), self._ptr(tok), int(pad),
-                                         self._ptr(key_pad), self._ptr(mem_row), self._ptr(act_idx), self._ptr(front),
-                                         self._ptr(src_of), self._ptr(src_len), self._ptr(kcache), self._ptr(vcache),
-                                         int(cache_seq_stride), self._ptr(cache_slot), int(gen_ld), int(n), int(d), int(mode),
-                                         int(groups), int(n_active), int(max_keys), int(kernel), C.byref(kid), self._stream()))
+        N.check(self._lib.ttx_debug_attn_hd(self._session, q.data_ptr(), q.stride(0), k.data_ptr(), v.data_ptr(), k.stride(0),
+                                            out.data_ptr(), int(heads), int(head_dim), float(scale), int(L), int(Lk), self._ptr(tok),
+                                            int(pad), self._ptr(key_pad), self._ptr(mem_row), self._ptr(act_idx), self._ptr(front),
+                                            self._ptr(src_of), self._ptr(src_len), self._ptr(kcache), self._ptr(vcache),
+                                            int(cache_seq_stride), self._ptr(cache_slot), int(gen_ld), int(n), int(d), int(mode),
+                                            int(groups), int(n_active), int(max_keys), int(kernel), C.byref(kid), self._stream()))
         return int(kid.value)
+
+    @staticmethod
+    def attn_staged_key_limit(head_dim: int, q_per_group: int) -> int:
+        """Keys one k_attn2 workgroup can stage at ``head_dim`` for groups of ``q_per_group`` query rows
+        (ttx_attn_staged_key_limit; a host query)."""
+        return int(N.lib().ttx_attn_staged_key_limit(int(head_dim), int(q_per_group)))
 
     def close(self) -> None:
         if getattr(self, "_score_session", None):
