@@ -50,6 +50,11 @@ typedef struct ttx_config {
   float   layer_norm_eps;       /* modules.py:52: 1e-5                                         */
 } ttx_config;
 
+/* The feed-forward non-linearity of a model (the reference's `activation` init_arg: "relu" or "gelu").  TTX_ACT_GELU is the exact
+ * GELU, 0.5 x (1 + erf(x / sqrt 2)) — torch's approximate="none" — not the tanh form.  TTX_ACT_NONE is only meaningful for
+ * ttx_debug_gemm_act. */
+typedef enum ttx_activation { TTX_ACT_NONE = 0, TTX_ACT_RELU = 1, TTX_ACT_GELU = 2 } ttx_activation;
+
 typedef struct ttx_model ttx_model;      /* weights resident in HBM                          */
 typedef struct ttx_session ttx_session;  /* workspaces, KV caches, captured graphs, one stream at a time */
 
@@ -78,6 +83,13 @@ void ttx_model_destroy(ttx_model* m);
  * ttx_model_create_empty and receives the blob with one ncclBroadcast on [ptr, ptr+bytes). */
 int  ttx_model_create_empty(const ttx_config* cfg, int device, ttx_model** out);
 int  ttx_model_blob(ttx_model* m, void** d_ptr, int64_t* bytes);
+
+/* The state dict does not carry the activation, so a model is ReLU until told otherwise.  ttx_model_set_activation accepts
+ * TTX_ACT_RELU or TTX_ACT_GELU (anything else: TTX_ERR_INVALID) and is legal only while no session of the model has ever been
+ * created: captured graphs and step argument blocks bake the FFN1 epilogue in.  Once ttx_session_create has succeeded on the
+ * model it returns TTX_ERR_INVALID and leaves the model as it is.  ttx_model_activation returns the current value. */
+int  ttx_model_set_activation(ttx_model* m, int activation);
+int  ttx_model_activation(const ttx_model* m);
 
 int  ttx_session_create(ttx_model* m, ttx_session** out);
 void ttx_session_destroy(ttx_session* s);
@@ -388,6 +400,12 @@ int ttx_debug_gemm_bench(ttx_session* s, int M, int N, int K, int splits, int va
 int ttx_debug_gemm(ttx_session* s, const float* d_x, int ldx, const float* d_w, int ldw, const float* d_bias, float* d_y, int ldy,
                    const int32_t* d_m, int m_max, int N, int K, int relu, int splits, int64_t slab_stride, int variant, int tiling,
                    int32_t* kernel_id, void* stream);
+/* ttx_debug_gemm with a ttx_activation (0 none, 1 ReLU, 2 exact GELU) in place of `relu`; any other value, or an activation on raw
+ * slabs (splits > 0), is TTX_ERR_INVALID and nothing is launched.  ttx_debug_gemm forwards here with relu ? 1 : 0.  The kernel ids
+ * are the same: GELU is another instantiation of the kernel the shape dispatches to (tests/test_gpu_gemm_gelu.py). */
+int ttx_debug_gemm_act(ttx_session* s, const float* d_x, int ldx, const float* d_w, int ldw, const float* d_bias, float* d_y, int ldy,
+                       const int32_t* d_m, int m_max, int N, int K, int activation, int splits, int64_t slab_stride, int variant,
+                       int tiling, int32_t* kernel_id, void* stream);
 
 /* y = LN2?( LN( (resid + bias) + (slab[0] + slab[1] + ...) ) ) over rows of width d in {64, 128, 256, 512, 1024}; rows with
  * row_valid == 0 become 0, rows >= *d_m are left alone.  d_g2 / d_b2 / d_row_valid / d_m may be NULL.  Float operands must be

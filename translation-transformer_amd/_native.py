@@ -24,6 +24,16 @@ OBJ_DIR = CSRC / "build"
 TTX_OK, TTX_ERR_INVALID, TTX_ERR_HIP, TTX_ERR_NO_DEVICE, TTX_ERR_REFERENCE, TTX_ERR_NOMEM = 0, -1, -2, -3, -4, -5
 TTX_ERR_ROW_REPLAY = -6
 TTX_ERR_MAX_STEPS = -7
+# enum ttx_activation; the strings are the reference's `activation` init_arg
+TTX_ACT_NONE, TTX_ACT_RELU, TTX_ACT_GELU = 0, 1, 2
+ACTIVATIONS = {"relu": TTX_ACT_RELU, "gelu": TTX_ACT_GELU}
+
+
+def activation_code(activation: str) -> int:
+    """The ttx_activation of the reference's `activation` string; ValueError for anything but the two it can be here."""
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"activation must be 'relu' or 'gelu' (the exact erf GELU), got {activation!r}")
+    return ACTIVATIONS[activation]
 
 
 class TtxError(RuntimeError):
@@ -93,6 +103,8 @@ SYMBOLS = {
     "ttx_model_destroy": (None, [_VP]),
     "ttx_model_create_empty": (C.c_int, [C.POINTER(Config), _I, C.POINTER(_VP)]),
     "ttx_model_blob": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int64)]),
+    "ttx_model_set_activation": (C.c_int, [_VP, _I]),
+    "ttx_model_activation": (C.c_int, [_VP]),
     "ttx_session_create": (C.c_int, [_VP, C.POINTER(_VP)]),
     "ttx_session_destroy": (None, [_VP]),
     "ttx_encode_src": (C.c_int, [_VP, _VP, _I, _I, _VP, _VP]),
@@ -133,6 +145,8 @@ SYMBOLS = {
     "ttx_debug_gemm_bench": (C.c_int, [_VP, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "ttx_debug_gemm": (C.c_int, [_VP, _VP, _I, _VP, _I, _VP, _VP, _I, _VP, _I, _I, _I, _I, _I, C.c_int64, _I, _I,
                                  C.POINTER(C.c_int32), _VP]),
+    "ttx_debug_gemm_act": (C.c_int, [_VP, _VP, _I, _VP, _I, _VP, _VP, _I, _VP, _I, _I, _I, _I, _I, C.c_int64, _I, _I,
+                                     C.POINTER(C.c_int32), _VP]),
     "ttx_debug_finish_ln": (C.c_int, [_VP, _VP, _I, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, C.c_float, _VP]),
     "ttx_debug_attn": (C.c_int, [_VP, _VP, _I, _VP, _VP, _I, _VP, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                  C.c_int64, _VP, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), _VP]),

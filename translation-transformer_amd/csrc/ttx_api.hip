@@ -143,6 +143,18 @@ extern "C" int ttx_model_create_empty(const ttx_config* cfg, int device, ttx_mod
   return model_alloc(cfg, device, out);
 }
 
+extern "C" int ttx_model_set_activation(ttx_model* m, int activation) {
+  if (!m) return fail(TTX_ERR_INVALID, "null argument");
+  if (activation != TTX_ACT_RELU && activation != TTX_ACT_GELU)
+    return fail(TTX_ERR_INVALID, "the feed-forward activation is TTX_ACT_RELU or TTX_ACT_GELU");
+  // captured graphs and step argument blocks of a session bake the FFN1 epilogue in
+  if (m->n_sessions > 0) return fail(TTX_ERR_INVALID, "ttx_model_set_activation: the model already has had a session");
+  m->activation = activation;
+  return TTX_OK;
+}
+
+extern "C" int ttx_model_activation(const ttx_model* m) { return m ? m->activation : TTX_ACT_NONE; }
+
 extern "C" int ttx_model_blob(ttx_model* m, void** d_ptr, int64_t* bytes) {
   if (!m || !d_ptr || !bytes) return fail(TTX_ERR_INVALID, "null argument");
   *d_ptr = m->blob;
@@ -310,6 +322,7 @@ extern "C" int ttx_session_create(ttx_model* m, ttx_session** out) {
   // test hook: every attention launch on the streaming fallback kernel
   if (const char* e = getenv("TTX_ATTN_FALLBACK")) s->attn_fallback = atoi(e) != 0;
   s->host_timing = getenv("TTX_HOST_TIMING") != nullptr;
+  m->n_sessions++;                                   // from here on the model's activation is fixed (ttx_model_set_activation)
   *out = s;
   return TTX_OK;
 }
@@ -416,7 +429,7 @@ static int run_encoder(ttx_session* s, hipStream_t st, const int* tok, const uin
     TTX_TRY(launch_attn(ATT_ENC, s, st, a, B, H, Ls, Ls));
     TTX_TRY(gemm_ln(s, st, ao, d, d, m->p(w.sa_out_w), m->p(w.sa_out_b), x, m->p(w.n1_w), m->p(w.n1_b), nullptr, nullptr,
                     nullptr, x1, nullptr, M, gv));
-    TTX_TRY(launch_gemm(s, st, x1, d, m->p(w.l1_w), d, m->p(w.l1_b), hb, F, nullptr, M, F, d, true, 0, 0, gv));
+    TTX_TRY(launch_gemm(s, st, x1, d, m->p(w.l1_w), d, m->p(w.l1_b), hb, F, nullptr, M, F, d, m->activation, 0, 0, gv));
     TTX_TRY(gemm_ln(s, st, hb, F, F, m->p(w.l2_w), m->p(w.l2_b), x1, m->p(w.n2_w), m->p(w.n2_b),
                     last ? m->p(m->enc_norm_w) : nullptr, last ? m->p(m->enc_norm_b) : nullptr, last ? valid : nullptr,
                     last ? memory : x, nullptr, M, gv));
@@ -486,7 +499,7 @@ static int run_decoder_full(ttx_session* s, hipStream_t st, const int* tok, int 
     TTX_TRY(launch_attn(ATT_FULL_CROSS, s, st, ca, R, H, Lt, Ls));
     TTX_TRY(gemm_ln(s, st, ao, d, d, m->p(w.ca_out_w), m->p(w.ca_out_b), x1, m->p(w.n2_w), m->p(w.n2_b), nullptr, nullptr,
                     nullptr, x2, nullptr, M, gv));
-    TTX_TRY(launch_gemm(s, st, x2, d, m->p(w.l1_w), d, m->p(w.l1_b), hb, F, nullptr, M, F, d, true, 0, 0, gv));
+    TTX_TRY(launch_gemm(s, st, x2, d, m->p(w.l1_w), d, m->p(w.l1_b), hb, F, nullptr, M, F, d, m->activation, 0, 0, gv));
     TTX_TRY(gemm_ln(s, st, hb, F, F, m->p(w.l2_w), m->p(w.l2_b), x2, m->p(w.n3_w), m->p(w.n3_b),
                     last ? m->p(m->dec_norm_w) : nullptr, last ? m->p(m->dec_norm_b) : nullptr, nullptr, last ? xf : x, nullptr, M, gv));
   }
@@ -782,7 +795,7 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
     TTX_TRY(launch_attn(ATT_STEP_CROSS, s, st, ca, k.B, H, RPS, k.Ls, k.N, D1));
     TTX_TRY(gemm_ln(s, st, ao, d, d, m->p(w.ca_out_w), m->p(w.ca_out_b), x1, m->p(w.n2_w), m->p(w.n2_b), nullptr, nullptr,
                     nullptr, x2, m_ptr, Mmax, vd));
-    TTX_TRY(launch_gemm(s, st, x2, d, m->p(w.l1_w), d, m->p(w.l1_b), hb, F, m_ptr, Mmax, F, d, true, 0, 0, v1));
+    TTX_TRY(launch_gemm(s, st, x2, d, m->p(w.l1_w), d, m->p(w.l1_b), hb, F, m_ptr, Mmax, F, d, m->activation, 0, 0, v1));
     TTX_TRY(gemm_ln(s, st, hb, F, F, m->p(w.l2_w), m->p(w.l2_b), x2, m->p(w.n3_w), m->p(w.n3_b),
                     last ? m->p(m->dec_norm_w) : nullptr, last ? m->p(m->dec_norm_b) : nullptr, nullptr, last ? xf : x, m_ptr, Mmax, vf));
   }
@@ -2727,11 +2740,18 @@ extern "C" int ttx_debug_gemm_bench(ttx_session* s, int M, int N, int K, int spl
 }
 
 // Test entry points: one GEMM / finisher launch on the caller's device operands (ttx_gemm.hip: gemm_debug, finish_debug).
+extern "C" int ttx_debug_gemm_act(ttx_session* s, const float* d_x, int ldx, const float* d_w, int ldw, const float* d_bias, float* d_y,
+                                  int ldy, const int32_t* d_m, int m_max, int N, int K, int activation, int splits, int64_t slab_stride,
+                                  int variant, int tiling, int32_t* kernel_id, void* stream) {
+  return gemm_debug(s, d_x, ldx, d_w, ldw, d_bias, d_y, ldy, d_m, m_max, N, K, activation, splits, (long long)slab_stride, variant,
+                    tiling, kernel_id, reinterpret_cast<hipStream_t>(stream));
+}
+
 extern "C" int ttx_debug_gemm(ttx_session* s, const float* d_x, int ldx, const float* d_w, int ldw, const float* d_bias, float* d_y,
                               int ldy, const int32_t* d_m, int m_max, int N, int K, int relu, int splits, int64_t slab_stride,
                               int variant, int tiling, int32_t* kernel_id, void* stream) {
-  return gemm_debug(s, d_x, ldx, d_w, ldw, d_bias, d_y, ldy, d_m, m_max, N, K, relu, splits, (long long)slab_stride, variant, tiling,
-                    kernel_id, reinterpret_cast<hipStream_t>(stream));
+  return ttx_debug_gemm_act(s, d_x, ldx, d_w, ldw, d_bias, d_y, ldy, d_m, m_max, N, K, relu ? TTX_ACT_RELU : TTX_ACT_NONE, splits,
+                            slab_stride, variant, tiling, kernel_id, stream);
 }
 
 extern "C" int ttx_debug_finish_ln(ttx_session* s, const float* d_slabs, int n_slabs, int64_t slab_stride, const float* d_bias,

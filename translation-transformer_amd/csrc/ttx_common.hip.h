@@ -40,7 +40,8 @@ struct GemmArgs {
   const int* m_ptr;          // device-resident row count (null: use M)
   int M, N, K;
   int k_per_split;           // K range handled by one blockIdx.z
-  int relu;                  // epilogue
+  int relu;                  // epilogue: 1 clamps at zero (TTX_ACT_RELU).  GELU is not a run-time flag but a template parameter of
+                             // the kernels (gemm_act below): the ReLU / no-activation code objects stay what they were without it
   int raw;                   // 1: write un-biased partial sums to slab blockIdx.z
   long long slab_stride;     // floats between slabs
   int slice_k;               // canonical slice length (see ttx_gemm.hip): the result is the ordered sum over the K range's
@@ -48,6 +49,28 @@ struct GemmArgs {
   int big_min_tiles;         // k_gemm24: smallest 128x64-tile count (x slabs) at which that tiling is used instead of 64x64 (0: never)
 };
 
+
+// ------------------------------------------------------------------------------------------------
+// Exact GELU (torch's approximate="none"): gelu(x) = 0.5 x (1 + erf(x / sqrt 2)), evaluated in ONE pinned order,
+//     t = x * fl(1 / sqrt 2);   e = erff(t);   h = 0.5 * x;   y = fma(h, e, h),
+// every product and the fma spelled out, so that no instantiation of a GEMM kernel can contract the expression differently from
+// another: equal pre-activation bits (canonical slice order, ttx_gemm.hip) give equal GELU bits in every kernel, tiling and live
+// row count.  erff is the device library's, inlined as the same instruction sequence everywhere.  The closing fma rounds
+// h (1 + e) once: in the negative tail, where e -> -1, nothing is lost beyond erff's own error (DESIGN.md "GELU").
+__device__ __forceinline__ float gelu_erf(float x) {
+  const float t = __fmul_rn(x, 0.70710678118654752440f);
+  const float e = erff(t);
+  const float h = __fmul_rn(0.5f, x);
+  return __fmaf_rn(h, e, h);
+}
+
+// The activation of a GEMM epilogue.  GELU = false is the epilogue the kernels always had: a clamp at `lo` (0 for ReLU, -inf for
+// none), untouched by the GELU instantiations beside it.
+template <bool GELU>
+__device__ __forceinline__ float gemm_act(float v, float lo) {
+  if constexpr (GELU) return gelu_erf(v);
+  else return fmaxf(v, lo);
+}
 
 // ------------------------------------------------------------------------------------------------
 // Wave reductions (64 lanes).

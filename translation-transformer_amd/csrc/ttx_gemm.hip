@@ -24,7 +24,7 @@ namespace ttx {
 // ------------------------------------------------------------------------------------------------
 // Generic fallback (K a multiple of 32 that is neither 64, 128 nor a multiple of 256): 32-deep LDS-staged tiles, one chain per output element.  Such K have
 // no canonical slices (gemm_slice_k = 0) and every variant sends them here, so they too have one arithmetic.
-template <int WGM, int WGN>
+template <int WGM, int WGN, bool GELU = false>
 __global__ __launch_bounds__(64 * WGM * WGN) void k_gemm_tn(GemmArgs a) {
   constexpr int NT = 64 * WGM * WGN;
   constexpr int BM = 32 * WGM, BN = 32 * WGN, BK = 32, LDT = BK + 4;
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_gemm_tn(GemmArgs a) {
   const float lo = a.relu ? 0.f : -INFINITY;
   float val[16];
 #pragma unroll
-  for (int v = 0; v < 16; ++v) val[v] = fmaxf(acc[v] + bv, lo);
+  for (int v = 0; v < 16; ++v) val[v] = gemm_act<GELU>(acc[v] + bv, lo);
   if (col < a.N) {
     float* yp = Y + (size_t)(m0 + wm * 32 + 4 * h) * a.ldy + col;
     const int rows_left = M - (m0 + wm * 32 + 4 * h);
@@ -203,7 +203,7 @@ constexpr int G24_SMEM_FLOATS = 2 * 2 * 64 * 68;       // 69 632 B: the larger o
 
 // NT = number of 64-deep K tiles per workgroup when it is 1, 2 or 4 (straight-line code, every tile
 // requested up front); NT = 0: any multiple of 4 tiles, ring slots refilled as they drain.
-template <int NT>
+template <int NT, bool GELU>
 __device__ __forceinline__ void g2_body(const GemmArgs& a, const int M, const int bx, const int by, const int bz, float* smem) {
   constexpr int BM = 64, BN = 64, BK = 64, LDT = BK + 4, RING = 4;
   typedef float (*TileBufs)[BM * LDT];
@@ -338,7 +338,7 @@ __device__ __forceinline__ void g2_body(const GemmArgs& a, const int M, const in
   const float lo = a.relu ? 0.f : -INFINITY;
   float val[16];
 #pragma unroll
-  for (int v = 0; v < 16; ++v) val[v] = fmaxf(acc[v] + bv, lo);
+  for (int v = 0; v < 16; ++v) val[v] = gemm_act<GELU>(acc[v] + bv, lo);
   if (m0 + BM <= M && n0 + BN <= a.N) {             // interior workgroup (uniform): straight-line stores
     float* yp = Y + (size_t)(m0 + wm * 32 + 4 * h) * a.ldy + col;
 #pragma unroll
@@ -354,11 +354,11 @@ __device__ __forceinline__ void g2_body(const GemmArgs& a, const int M, const in
   }
 }
 
-template <int NT>
+template <int NT, bool GELU = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_gemm2(GemmArgs a) {
   __shared__ __attribute__((aligned(16))) float smem[2 * 2 * 64 * 68];
   const int M = a.m_ptr ? *a.m_ptr : a.M;
-  g2_body<NT>(a, M, blockIdx.x, blockIdx.y, blockIdx.z, smem);
+  g2_body<NT, GELU>(a, M, blockIdx.x, blockIdx.y, blockIdx.z, smem);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -375,7 +375,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // slice_k / 64 pairs.
 struct G4Frag { float4 a0, a1, a2, a3, b0, b1; };
 
-template <bool ALT>
+template <bool ALT, bool GELU>
 __device__ __forceinline__ void g4_body(const GemmArgs& a, const int M, const int bx, const int by, const int bz, float* smem) {
   constexpr int BM = 128, BN = 64, BK = 32, LDT = BK + 4;
   constexpr int WN = BN / 2;                      // columns per wave
@@ -480,7 +480,10 @@ __device__ __forceinline__ void g4_body(const GemmArgs& a, const int M, const in
   const int bcol = n0 + wn * WN + r;
   // the bias value is requested before the K loop (a load still pending in the epilogue would make every predicated store
   // wait for vmcnt(0), i.e. for the previous store: 32 serialised round trips)
-  const float bias0 = (!a.raw && a.bias) ? a.bias[min(bcol, a.N - 1)] : 0.f;
+  // (The GELU instantiation asks for it after the K loop instead, still ahead of every store: the register it would hold across
+  // the loop is what makes k_gemm24<4> spill two values, and a GELU code object is to have no scratch — DESIGN.md "GELU".)
+  float bias0 = 0.f;
+  if constexpr (!GELU) bias0 = (!a.raw && a.bias) ? a.bias[min(bcol, a.N - 1)] : 0.f;
   const int pairs_per_slice = (a.slice_k > 0 && a.slice_k < kend - kbeg) ? a.slice_k / (2 * BK) : ntiles / 2;   // not sliced: one slice
   const int n_slices = (ntiles / 2) / pairs_per_slice;
   asm volatile("" ::: "memory");
@@ -540,13 +543,14 @@ __device__ __forceinline__ void g4_body(const GemmArgs& a, const int M, const in
     c00 = t00; c10 = t10;
   }
 
+  if constexpr (GELU) bias0 = (!a.raw && a.bias) ? a.bias[min(bcol, a.N - 1)] : 0.f;
   float* Y = a.Y + (a.raw ? (size_t)bz * a.slab_stride : 0);
   const float lo = a.relu ? 0.f : -INFINITY;
   auto store_tile = [&](const f32x16& c, int tm) {
     const int col = n0 + wn * WN + r;
     float val[16];
 #pragma unroll
-    for (int v = 0; v < 16; ++v) val[v] = fmaxf(c[v] + bias0, lo);
+    for (int v = 0; v < 16; ++v) val[v] = gemm_act<GELU>(c[v] + bias0, lo);
     const int row0 = m0 + wm * 64 + tm * 32 + 4 * h;
     float* yp = Y + (size_t)row0 * a.ldy + col;
     if (m0 + BM <= M && n0 + BN <= a.N) {            // interior workgroup (uniform): straight-line stores
@@ -584,7 +588,7 @@ __device__ __forceinline__ bool tile_of_workgroup(int n_tiles, int nbx, int nby,
 // One launch, two tilings: the grid is laid out for 64x64 tiles; when the row count read from the device gives the 128x64
 // tiling at least `big_min_tiles` workgroups, the first workgroups in dispatch order each compute such a tile and the others
 // leave at once, otherwise all compute their 64x64 tile.  Both evaluate the canonical slice sum: bit-identical results.
-template <int NT>
+template <int NT, bool GELU = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_gemm24(GemmArgs a) {
   __shared__ __attribute__((aligned(16))) float smem[G24_SMEM_FLOATS];
   const int M = a.m_ptr ? *a.m_ptr : a.M;
@@ -593,9 +597,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   if (a.big_min_tiles > 0 && mid_tiles >= a.big_min_tiles) {
     int bx, by, slab;
     if (!tile_of_workgroup(mid_tiles, nbx, nby, bx, by, slab)) return;
-    g4_body<NT == 4>(a, M, bx, by, slab, smem);
+    g4_body<NT == 4, GELU>(a, M, bx, by, slab, smem);
   } else {
-    g2_body<NT>(a, M, blockIdx.x, blockIdx.y, blockIdx.z, smem);
+    g2_body<NT, GELU>(a, M, blockIdx.x, blockIdx.y, blockIdx.z, smem);
   }
 }
 
@@ -605,6 +609,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // memory into the registers the MFMA reads (lane (r,h) owns row r / column r and the k's 8g+4h..8g+4h+3, which is exactly
 // one float4 per 8 k's) — no LDS staging, no barrier before the math; the four slices meet in LDS (16.5 KB), are added in
 // slice order and leave as whole 128-B rows.  4x the workgroups of the 64x64 kernel and many of them resident per CU.
+template <bool GELU = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_gemm3(GemmArgs a) {
   constexpr int KW = 64;                                   // k's per wave = the canonical slice of the K = 256 contractions
   __shared__ __attribute__((aligned(16))) float part[4][32 * 33];
@@ -656,12 +661,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 4))) voi
     if (gcol + 3 < a.N && (a.ldy & 3) == 0) {
       float4 bb = make_float4(0.f, 0.f, 0.f, 0.f);
       if (!a.raw && a.bias) bb = *reinterpret_cast<const float4*>(a.bias + gcol);
-      o.x = fmaxf(o.x + bb.x, lo); o.y = fmaxf(o.y + bb.y, lo); o.z = fmaxf(o.z + bb.z, lo); o.w = fmaxf(o.w + bb.w, lo);
+      o.x = gemm_act<GELU>(o.x + bb.x, lo); o.y = gemm_act<GELU>(o.y + bb.y, lo); o.z = gemm_act<GELU>(o.z + bb.z, lo); o.w = gemm_act<GELU>(o.w + bb.w, lo);
       *reinterpret_cast<float4*>(Y) = o;
     } else {
       for (int i = 0; i < 4 && gcol + i < a.N; ++i) {
         const float bb = (!a.raw && a.bias) ? a.bias[gcol + i] : 0.f;
-        Y[i] = fmaxf(op[i] + bb, lo);
+        Y[i] = gemm_act<GELU>(op[i] + bb, lo);
       }
     }
   }
@@ -767,21 +772,22 @@ int gemm_splits(int N, int K, bool step, int variant) {
 }
 
 int launch_gemm(ttx_session* s, hipStream_t st, const float* X, int ldx, const float* W, int ldw, const float* bias,
-                float* Y, int ldy, const int* m_ptr, int Mmax, int N, int K, bool relu, int splits, long long slab_stride,
+                float* Y, int ldy, const int* m_ptr, int Mmax, int N, int K, int act, int splits, long long slab_stride,
                 int variant) {
+  if (act != TTX_ACT_NONE && act != TTX_ACT_RELU && act != TTX_ACT_GELU) return fail(TTX_ERR_INVALID, "GEMM activation must be a ttx_activation");
   if (Mmax <= 0) return TTX_OK;
   if (K % 32) return fail(TTX_ERR_INVALID, "GEMM K must be a multiple of 32");
   GemmArgs a;
   a.X = X; a.ldx = ldx; a.W = W; a.ldw = ldw; a.bias = bias; a.Y = Y; a.ldy = ldy; a.m_ptr = m_ptr;
-  a.M = Mmax; a.N = N; a.K = K; a.relu = relu ? 1 : 0;
+  a.M = Mmax; a.N = N; a.K = K; a.relu = act == TTX_ACT_RELU ? 1 : 0;
   a.raw = splits > 0 ? 1 : 0;
   const int S = splits > 0 ? splits : 1;
   a.k_per_split = K / S;
   a.slab_stride = slab_stride;
   a.slice_k = gemm_slice_k(K);
   if (K % S) return fail(TTX_ERR_INVALID, "GEMM K must be a multiple of the slab count");
-  // raw slabs are partial sums: an activation belongs after their sum (the kernels' epilogue would clamp every slab on its own)
-  if (a.raw && relu) return fail(TTX_ERR_INVALID, "raw split-K slabs take no activation");
+  // raw slabs are partial sums: an activation belongs after their sum (the kernels' epilogue would apply it to every slab on its own)
+  if (a.raw && act != TTX_ACT_NONE) return fail(TTX_ERR_INVALID, "raw split-K slabs take no activation");
   if (a.slice_k && a.k_per_split % a.slice_k) return fail(TTX_ERR_INVALID, "split-K slabs must be whole canonical slices");
   // the 64x64 ring walks four 64-deep tiles per pass (a slab of 192 or 320 k's would be computed over a range that is not its own)
   if (a.slice_k && a.k_per_split != 64 && a.k_per_split != 128 && a.k_per_split % 256)
@@ -801,13 +807,16 @@ int launch_gemm(ttx_session* s, hipStream_t st, const float* X, int ldx, const f
     s->ev_used++;
   }
   const bool step = (m_ptr != nullptr);
+  const bool gelu = act == TTX_ACT_GELU;           // the same dispatch, the GELU instantiation of the kernel it picks
   s->last_gemm_big_min_tiles = 0;
   if (use_gemm3(step, variant, N, K) && S == 1) {
     s->last_gemm_kernel = GK_GEMM3;
-    hipLaunchKernelGGL(k_gemm3, dim3(cdiv(N, 32), cdiv(Mmax, 32), 1), dim3(256), 0, st, a);
+    if (gelu) hipLaunchKernelGGL((k_gemm3<true>), dim3(cdiv(N, 32), cdiv(Mmax, 32), 1), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_gemm3<false>), dim3(cdiv(N, 32), cdiv(Mmax, 32), 1), dim3(256), 0, st, a);
   } else if (a.slice_k == 0) {
     s->last_gemm_kernel = GK_GEMM_TN;
-    hipLaunchKernelGGL((k_gemm_tn<2, 2>), dim3(cdiv(N, 64), cdiv(Mmax, 64), S), dim3(256), 0, st, a);
+    if (gelu) hipLaunchKernelGGL((k_gemm_tn<2, 2, true>), dim3(cdiv(N, 64), cdiv(Mmax, 64), S), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_gemm_tn<2, 2>), dim3(cdiv(N, 64), cdiv(Mmax, 64), S), dim3(256), 0, st, a);
   } else if (a.k_per_split % 256 == 0 && !(step && variant == GV_SMALL)) {
     // one launch that picks the tiling (128x64 / 64x64) from the live row count.  Where the 128-row tiling starts to pay
     // depends on how long a tile runs (profiles/r03_gemm_bench_canonical_slices.txt): deep contractions (FFN2, K = 2048) from
@@ -817,12 +826,21 @@ int launch_gemm(ttx_session* s, hipStream_t st, const float* X, int ldx, const f
     dim3 grid(cdiv(N, 64), cdiv(Mmax, 64), S);
     s->last_gemm_kernel = a.k_per_split == 256 ? GK_GEMM24_4 : GK_GEMM24_0;
     s->last_gemm_big_min_tiles = a.big_min_tiles;
-    if (a.k_per_split == 256) hipLaunchKernelGGL((k_gemm24<4>), grid, dim3(256), 0, st, a);
+    if (gelu) {
+      if (a.k_per_split == 256) hipLaunchKernelGGL((k_gemm24<4, true>), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((k_gemm24<0, true>), grid, dim3(256), 0, st, a);
+    } else if (a.k_per_split == 256) hipLaunchKernelGGL((k_gemm24<4>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((k_gemm24<0>), grid, dim3(256), 0, st, a);
   } else {
     dim3 grid(cdiv(N, 64), cdiv(Mmax, 64), S);
     s->last_gemm_kernel = a.k_per_split == 64 ? GK_GEMM2_1 : a.k_per_split == 128 ? GK_GEMM2_2 : a.k_per_split == 256 ? GK_GEMM2_4 : GK_GEMM2_0;
-    switch (a.k_per_split) {
+    if (gelu) switch (a.k_per_split) {
+      case 64: hipLaunchKernelGGL((k_gemm2<1, true>), grid, dim3(256), 0, st, a); break;
+      case 128: hipLaunchKernelGGL((k_gemm2<2, true>), grid, dim3(256), 0, st, a); break;
+      case 256: hipLaunchKernelGGL((k_gemm2<4, true>), grid, dim3(256), 0, st, a); break;
+      default: hipLaunchKernelGGL((k_gemm2<0, true>), grid, dim3(256), 0, st, a); break;
+    }
+    else switch (a.k_per_split) {
       case 64: hipLaunchKernelGGL((k_gemm2<1>), grid, dim3(256), 0, st, a); break;
       case 128: hipLaunchKernelGGL((k_gemm2<2>), grid, dim3(256), 0, st, a); break;
       case 256: hipLaunchKernelGGL((k_gemm2<4>), grid, dim3(256), 0, st, a); break;
@@ -902,7 +920,7 @@ int gemm_bench(ttx_session* s, int M, int N, int K, int splits, int variant, int
     if (var == 2) s->big_min_tiles = 0;
     else if (var == 46) s->big_min_tiles = 1;
     else if (var == 3 || var == 8) gv = GV_SMALL;
-    return launch_gemm(s, st, dx, K, dw, K, n_slabs > 0 ? nullptr : db, y, N, dm, M, N, K, false, n_slabs, (long long)M * N, gv);
+    return launch_gemm(s, st, dx, K, dw, K, n_slabs > 0 ? nullptr : db, y, N, dm, M, N, K, TTX_ACT_NONE, n_slabs, (long long)M * N, gv);
   };
   int rc = launch(2, dref, 0);                                     // reference: 64x64 tiles, one workgroup walks all slices
   const int slabs = (variant == 8) ? gemm_splits(N, K, true, GV_SMALL) : splits;
@@ -961,9 +979,10 @@ static int debug_live_rows(const int32_t* d_m, int m_max, hipStream_t st, int* M
 }
 
 int gemm_debug(ttx_session* s, const float* d_x, int ldx, const float* d_w, int ldw, const float* d_bias, float* d_y, int ldy,
-               const int32_t* d_m, int m_max, int N, int K, int relu, int splits, long long slab_stride, int variant, int tiling,
+               const int32_t* d_m, int m_max, int N, int K, int act, int splits, long long slab_stride, int variant, int tiling,
                int32_t* kernel_id, hipStream_t st) {
   if (!s || !d_x || !d_w || !d_y) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_gemm");
+  if (act != TTX_ACT_NONE && act != TTX_ACT_RELU && act != TTX_ACT_GELU) return fail(TTX_ERR_INVALID, "ttx_debug_gemm_act: activation is 0 (none), 1 (ReLU) or 2 (GELU)");
   if (m_max <= 0 || N <= 0 || K <= 0 || splits < 0) return fail(TTX_ERR_INVALID, "ttx_debug_gemm: m_max, N, K must be positive and splits >= 0");
   if (K % 32) return fail(TTX_ERR_INVALID, "ttx_debug_gemm: K must be a multiple of 32");
   if (variant < GV_BIG || variant > GV_MID || tiling < 0 || tiling > 2) return fail(TTX_ERR_INVALID, "ttx_debug_gemm: variant is 0..3, tiling 0..2");
@@ -989,7 +1008,7 @@ int gemm_debug(ttx_session* s, const float* d_x, int ldx, const float* d_w, int 
   s->profile = false;
   if (tiling == 1) s->big_min_tiles = 0;
   else if (tiling == 2) s->big_min_tiles = 1;
-  const int rc = launch_gemm(s, st, d_x, ldx, d_w, ldw, d_bias, d_y, ldy, d_m, m_max, N, K, relu != 0, splits, slab_stride, variant);
+  const int rc = launch_gemm(s, st, d_x, ldx, d_w, ldw, d_bias, d_y, ldy, d_m, m_max, N, K, act, splits, slab_stride, variant);
   s->big_min_tiles = keep_min; s->profile = was_profile;
   if (rc != TTX_OK) return rc;
   if (kernel_id) {

@@ -28,6 +28,9 @@ struct LayerW {
 struct ttx_model {
   ttx_config cfg;
   int device;
+  int activation = TTX_ACT_RELU;   // FFN non-linearity (ttx_model_set_activation): fixed once a session exists
+  int n_sessions = 0;              // sessions ever created on this model
+
   int n_cu = 256;                  // compute units of the device (grids sized to the machine: k_attn3s)
   float* blob = nullptr;
   size_t blob_floats = 0;
@@ -196,10 +199,10 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 int gemm_slice_k(int K);
 // Split-K slabs of a d-wide step GEMM under `variant` (1 for everything but FFN2 under GV_SMALL).
 int gemm_splits(int N, int K, bool step, int variant);
-// Y = act(X W^T + b) (splits == 0) or `splits` raw slabs [splits][Mmax][ldy] (k_finish_ln sums them in slab order).
+// Y = act(X W^T + b) (splits == 0; `act` is a ttx_activation) or `splits` raw slabs [splits][Mmax][ldy] (k_finish_ln sums them in slab order).
 // m_ptr != null marks a verify-step launch (live row count on the device, capacity Mmax); `variant` is a GemmVariant.
 int launch_gemm(ttx_session* s, hipStream_t st, const float* X, int ldx, const float* W, int ldw, const float* bias,
-                float* Y, int ldy, const int* m_ptr, int Mmax, int N, int K, bool relu, int splits, long long slab_stride,
+                float* Y, int ldy, const int* m_ptr, int Mmax, int N, int K, int act, int splits, long long slab_stride,
                 int variant);
 int launch_finish(ttx_session* s, hipStream_t st, const float* slabs, int n_slabs, long long slab_stride, const float* bias,
                   const float* resid, const float* g1, const float* b1, const float* g2, const float* b2,
@@ -210,7 +213,7 @@ int launch_finish_d(hipStream_t st, const float* slabs, int n_slabs, long long s
                     const int* m_ptr, int Mmax, int d, float eps);
 // ttx_debug_gemm / ttx_debug_finish_ln (include/ttx.h): host-side validation, then one launch
 int gemm_debug(ttx_session* s, const float* d_x, int ldx, const float* d_w, int ldw, const float* d_bias, float* d_y, int ldy,
-               const int32_t* d_m, int m_max, int N, int K, int relu, int splits, long long slab_stride, int variant, int tiling,
+               const int32_t* d_m, int m_max, int N, int K, int act, int splits, long long slab_stride, int variant, int tiling,
                int32_t* kernel_id, hipStream_t st);
 int finish_debug(ttx_session* s, const float* d_slabs, int n_slabs, long long slab_stride, const float* d_bias, const float* d_resid,
                  const float* d_g1, const float* d_b1, const float* d_g2, const float* d_b2, const uint8_t* d_row_valid, float* d_y,

@@ -49,27 +49,41 @@ def broadcast_state_dict(state: dict | None, device: torch.device | str, dist=No
     return out
 
 
-def broadcast_model(state: dict | None, num_heads: int, pad_token_idx: int, device, dist=None, src: int = 0):
+def broadcast_model(state: dict | None, num_heads: int, pad_token_idx: int, device, dist=None, src: int = 0,
+                    activation: str = "relu"):
     """C1 as SURVEY.md §8(e) words it: rank `src` builds the model from its state dict (weights packed into one HBM blob),
     every other rank creates an EMPTY model of the same shape (ttx_model_create_empty) and receives the blob with ONE
     RCCL broadcast straight into HBM (ttx_model_blob) — no host staging, no per-tensor messages.  Returns the
     NativeTransformer of this rank.  Under gloo (CPU tests, several ranks sharing one GPU) the weights travel as a host
-    state dict instead (broadcast_state_dict) and every rank uploads them."""
-    from .model import NativeTransformer, shape_of_state
+    state dict instead (broadcast_state_dict) and every rank uploads them.  ``activation`` ("relu" / "gelu") is rank `src`'s:
+    neither the state dict nor the blob holds it, so it travels in the broadcast metadata next to the shape."""
+    from . import _native
+    from .model import NativeTransformer
+    _native.activation_code(activation)              # ValueError on every rank before any collective
     if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
-        return NativeTransformer(state, num_heads, pad_token_idx, device=device)
-    if dist.get_backend() == "gloo":
-        sd = broadcast_state_dict(state, device, dist, src)
-        return NativeTransformer(sd, num_heads, pad_token_idx, device=device)
+        return NativeTransformer(state, num_heads, pad_token_idx, device=device, activation=activation)
     rank = dist.get_rank()
-    meta = [shape_of_state(state) if rank == src else None]
+    if dist.get_backend() == "gloo":
+        act = [activation if rank == src else None]
+        dist.broadcast_object_list(act, src=src)
+        sd = broadcast_state_dict(state, device, dist, src)
+        return NativeTransformer(sd, num_heads, pad_token_idx, device=device, activation=act[0])
+    meta = [model_metadata(state, activation) if rank == src else None]
     dist.broadcast_object_list(meta, src=src)
-    model = NativeTransformer(state if rank == src else None, num_heads, pad_token_idx, device=device, shape=meta[0])
+    model = NativeTransformer(state if rank == src else None, num_heads, pad_token_idx, device=device, shape=meta[0]["shape"],
+                              activation=meta[0]["activation"])
     blob = model.blob_tensor()
     torch.cuda.synchronize(blob.device)           # rank src: the upload of the blob has completed
     dist.broadcast(blob, src=src)
     torch.cuda.synchronize(blob.device)
     return model
+
+
+def model_metadata(state: dict, activation: str = "relu") -> dict:
+    """What a rank needs besides the blob to build the EMPTY model the blob is broadcast into: the dimensions
+    (shape_of_state) and the feed-forward activation."""
+    from .model import shape_of_state
+    return {"shape": shape_of_state(state), "activation": activation}
 
 
 def gather_predictions(local: torch.Tensor, n_items: int, dist=None, dst: int = 0, pad_value: int = 0):

@@ -53,6 +53,7 @@ except Exception:  # pragma: no cover
                 batch_size = getattr(self, "_current_batch_size", None)
             self.__dict__.setdefault("logged", []).append((name, value, batch_size, flags))
 
+from ._native import activation_code
 from .model import NativeTransformer
 from . import decoding as D
 
@@ -66,15 +67,15 @@ class _Emb(nn.Module):
 class WeightContainer(nn.Module):
     """Parameters only, named exactly like the reference's VanillaTransformer (src/model/modules.py:40-84)."""
 
-    def __init__(self, src_vocab, tgt_vocab, n_enc, n_dec, d, heads, ff, share, src_pad, tgt_pad):
+    def __init__(self, src_vocab, tgt_vocab, n_enc, n_dec, d, heads, ff, share, src_pad, tgt_pad, activation="relu"):
         super().__init__()
         self.src_pad_token_i, self.tgt_pad_token_i = src_pad, tgt_pad
         self.emb_dim, self.num_heads = d, heads
         self.src_token_featurizer = _Emb(src_vocab, d, src_pad)
         self.tgt_token_featurizer = self.src_token_featurizer if share else _Emb(tgt_vocab, d, tgt_pad)
-        enc = nn.TransformerEncoder(nn.TransformerEncoderLayer(d, heads, ff, 0.0, "relu", 1e-5, True, False), n_enc,
+        enc = nn.TransformerEncoder(nn.TransformerEncoderLayer(d, heads, ff, 0.0, activation, 1e-5, True, False), n_enc,
                                     nn.LayerNorm(d, eps=1e-5), enable_nested_tensor=False)
-        dec = nn.TransformerDecoder(nn.TransformerDecoderLayer(d, heads, ff, 0.0, "relu", 1e-5, True, False), n_dec,
+        dec = nn.TransformerDecoder(nn.TransformerDecoderLayer(d, heads, ff, 0.0, activation, 1e-5, True, False), n_dec,
                                     nn.LayerNorm(d, eps=1e-5))
         self.transformer = nn.Transformer(d_model=d, nhead=heads, batch_first=True, custom_encoder=enc, custom_decoder=dec)
         self.next_token_classifier = nn.Linear(d, tgt_vocab)
@@ -172,7 +173,7 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         self.save_hyperparameters(ignore=["src_tokenizer", "tgt_tokenizer"])
         assert src_tokenizer is not None, "source tokenizer not provided"
         assert tgt_tokenizer is not None, "target tokenizer not provided"
-        assert activation == "relu", "the HIP path implements the reference configs' ReLU feed-forward"
+        activation_code(activation)                  # ValueError for anything but "relu" / "gelu" (the reference passes a string)
         self.src_tokenizer, self.tgt_tokenizer = src_tokenizer, tgt_tokenizer
         self.src_vocab_size, self.tgt_vocab_size = src_tokenizer.n_tokens, tgt_tokenizer.n_tokens
         self.src_pad_token_i, self.src_bos_token_i, self.src_eos_token_i = (
@@ -181,7 +182,7 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             tgt_tokenizer.pad_token_idx, tgt_tokenizer.bos_token_idx, tgt_tokenizer.eos_token_idx)
         self.model = WeightContainer(self.src_vocab_size, self.tgt_vocab_size, num_encoder_layers, num_decoder_layers,
                                      embedding_dim, num_heads, feedforward_dim, share_embeddings,
-                                     self.src_pad_token_i, self.tgt_pad_token_i)
+                                     self.src_pad_token_i, self.tgt_pad_token_i, activation)
         if generation not in ("greedy", "beam_search", "greedy_speculative", "beam_search_speculative"):
             options = ", ".join(["beam_search", "greedy", "greedy_speculative", "beam_search_speculative"])
             raise ValueError(f'Unknown generation option {generation}. Options are {options}.')
@@ -229,7 +230,8 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             # AND target keys, so a source tokenizer with another pad index would be masked wrongly: refuse it loudly
             raise ValueError(f"source pad id {self.src_pad_token_i} != target pad id {self.tgt_pad_token_i}: the HIP path "
                              "supports one shared pad index (the reference's tokenizers fix PAD=0, tokenizer_base.py:27)")
-        self.native = NativeTransformer(self.model.state_dict(), self.hparams.num_heads, self.tgt_pad_token_i, device=device)
+        self.native = NativeTransformer(self.model.state_dict(), self.hparams.num_heads, self.tgt_pad_token_i, device=device,
+                                        activation=self.hparams.activation)
         self._native_fp = fp
         self.generator = self._create_generator()
         print(self.generator)

@@ -82,10 +82,13 @@ class NativeTransformer:
     SCORE_MAX_ROWS = 32768
 
     def __init__(self, state_dict: dict | None, num_heads: int, pad_token_idx: int = 0, device: int | str | torch.device = 0,
-                 max_positions: int = 5000, layer_norm_eps: float = 1e-5, shape: dict | None = None):
+                 max_positions: int = 5000, layer_norm_eps: float = 1e-5, shape: dict | None = None, activation: str = "relu"):
         """``state_dict``: the reference's state dict (weights are packed into one HBM blob).  ``state_dict=None`` with
         ``shape`` (see shape_of_state): an EMPTY model of those dimensions whose blob is filled afterwards — the receiving side
-        of the one-off weight broadcast (dist.broadcast_model)."""
+        of the one-off weight broadcast (dist.broadcast_model).  ``activation``: the reference's init_arg,
+        "relu" or "gelu" (the exact erf GELU); the state dict does not carry it, so it has to be given with the weights."""
+        act = N.activation_code(activation)         # ValueError before any GPU call
+        self.activation = activation
         if not torch.cuda.is_available():
             raise RuntimeError("NativeTransformer needs an MI355X: the HIP path has no CPU fallback")
         dev = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
@@ -108,6 +111,7 @@ class NativeTransformer:
         self._profile_sessions = os.environ.get("TTX_PROFILE_GEMM") == "1"
         if st is None:
             N.check(self._lib.ttx_model_create_empty(C.byref(self.cfg), dev.index or 0, C.byref(self._model)))
+            N.check(self._lib.ttx_model_set_activation(self._model, act))      # before the first session: sessions bake it in
             N.check(self._lib.ttx_session_create(self._model, C.byref(self._session)))
             return
         host = {k: torch.as_tensor(v).detach().to("cpu", torch.float32).contiguous() for k, v in st.items()}
@@ -119,6 +123,7 @@ class NativeTransformer:
             keep.append((name, v))
             arr[i] = N.Tensor(name, C.cast(v.data_ptr(), C.POINTER(C.c_float)), v.numel())
         N.check(self._lib.ttx_model_create(C.byref(self.cfg), arr, len(host), dev.index or 0, C.byref(self._model)))
+        N.check(self._lib.ttx_model_set_activation(self._model, act))
         N.check(self._lib.ttx_session_create(self._model, C.byref(self._session)))
 
     def blob_tensor(self) -> torch.Tensor:
@@ -184,11 +189,18 @@ class NativeTransformer:
 
     def debug_gemm(self, x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None, y: torch.Tensor, n: int, k: int,
                    m_max: int, m_live: torch.Tensor | None = None, relu: bool = False, splits: int = 0, slab_stride: int = 0,
-                   variant: int = 0, tiling: int = 0) -> int:
+                   variant: int = 0, tiling: int = 0, activation: int | None = None) -> int:
         """One GEMM launch on the caller's device tensors (ttx_debug_gemm): ``x`` / ``w`` / ``y`` are 2-D fp32 views whose
         row strides are the leading dimensions (``y``: the first slab), ``m_live`` an int32 device scalar or None.  Returns
-        the kernel id the launch dispatched; arguments a kernel cannot take raise TtxError (TTX_ERR_INVALID)."""
+        the kernel id the launch dispatched; arguments a kernel cannot take raise TtxError (TTX_ERR_INVALID).  ``activation``
+        (0 none, 1 ReLU, 2 exact GELU) goes through ttx_debug_gemm_act and then replaces ``relu``."""
         kid = C.c_int32(0)
+        if activation is not None:
+            N.check(self._lib.ttx_debug_gemm_act(self._session, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), self._ptr(bias),
+                                                 y.data_ptr(), y.stride(0), self._ptr(m_live), int(m_max), int(n), int(k),
+                                                 int(activation), int(splits), int(slab_stride), int(variant), int(tiling),
+                                                 C.byref(kid), self._stream()))
+            return int(kid.value)
         N.check(self._lib.ttx_debug_gemm(self._session, x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), self._ptr(bias),
                                          y.data_ptr(), y.stride(0), self._ptr(m_live), int(m_max), int(n), int(k), int(relu),
                                          int(splits), int(slab_stride), int(variant), int(tiling), C.byref(kid), self._stream()))
