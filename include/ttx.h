@@ -447,6 +447,68 @@ int ttx_debug_attn_hd(ttx_session* s, const float* d_q, int ldq, const float* d_
                       const int32_t* d_cache_slot, int gen_ld, int N, int D, int mode, int groups, int n_active, int max_keys,
                       int kernel, int32_t* kernel_id, void* stream);
 
+/* Test entry points (tests/test_gpu_loop_kernels.py): ONE launch of a loop kernel of csrc/ttx_loop_kernels.hip.h on DEVICE operands
+ * of the caller, with production's grid and block rules.  All of them are integer or bit-copy work: the tests ask for exact
+ * equality with tests/util_loop_checks.py.  Nothing is launched and TTX_ERR_INVALID is returned for arguments a kernel cannot
+ * take; the device-side index arrays are read back and checked too (these are test calls).
+ *
+ * ttx_debug_argmax: k_argmax, one wave per row of d_logits [m_max, V] (any V >= 1): d_pred[row] = the first index of the row's
+ * maximum (-0.0 == 0.0; an all -inf row and an all-NaN row give 0); rows that mix NaN with other values are outside the
+ * contract and only give some id in [0, V).  d_m: live row count on the device
+ * or NULL (all m_max rows); rows >= *d_m are not written.  Refused: null pointers, V < 1, m_max < 1, *d_m outside [0, m_max]. */
+int ttx_debug_argmax(ttx_session* s, const float* d_logits, int V, int32_t* d_pred, const int32_t* d_m, int m_max, void* stream);
+
+/* ttx_debug_embed: k_embed on the caller's embedding table d_table [V, d] and positional table d_pe [pe_rows, d]:
+ * X[row] = table[tok] + pe[pos + 1] in fp32, ids outside [0, V) looked up as id 0.  step == 0 (full mode): tok = d_tok[row],
+ * pos = row % L, rows [0, rows).  step != 0 (one verify step): slot g < n_active is sequence b = d_act_idx[g] with front f =
+ * d_front[b] and owns the 1 + N*D rows g * (1 + N*D) ..: row 0 is d_gen[b * gen_ld + f] at position f, row 1 + n*D + (j-1) is
+ * d_drafts[b, n, j-1] at position f + j; the grid covers B slots and the live row count n_active * (1 + N*D) is put into a
+ * DecState on the device, ordered on `stream`; rows beyond it are not written.  Refused: null pointers the mode needs, d not in
+ * {64, 128, 256, 512, 1024}, table / pe / X not 16-byte aligned, n_active outside [0, B], act_idx that are not distinct rows of
+ * [0, B), a gen_ld too small for front + D + 2, a positional table with fewer than L + 1 (full) or front + D + 2 (step) rows. */
+int ttx_debug_embed(ttx_session* s, const float* d_table, int V, const float* d_pe, int pe_rows, int d, float* d_x,
+                    const int32_t* d_tok, int rows, int L, const int32_t* d_act_idx, const int32_t* d_front, const int32_t* d_gen,
+                    int gen_ld, const int32_t* d_drafts, int B, int N, int D, int n_active, int step, void* stream);
+
+/* Operands of ttx_debug_accept: the argument block of k_accept / k_greedy_accept (csrc/ttx_loop_kernels.hip.h: LoopArgs), every
+ * array a DEVICE array of the caller.  act_idx int32 [B] (running rows in slot order), front int32 [B], gen int32 [B, gen_ld],
+ * drafts int32 [B, N, D], pred int32 [n_active * (1 + N*D)] in the step-row layout above, rec int32 [B, 5] (b, best, n_acc,
+ * front_old, flags per slot), out int64 [B, max_len], haspad int32 [B].  row_rule: traj int16 [B, traj_ld], fin_step int32 [B].
+ * pool (implies row_rule): rstep, row_of int32 [B] and the caller-side rows pool_out int64 [pool_rows, max_len], pool_traj int16
+ * [pool_rows, traj_ld], pool_fin_step int32 [pool_rows] take the place of out, traj and fin_step. */
+typedef struct ttx_debug_accept_args {
+  int32_t* d_act_idx; int32_t* d_front; int32_t* d_gen; const int32_t* d_drafts; const int32_t* d_pred; int32_t* d_rec;
+  int64_t* d_out; int32_t* d_haspad;
+  int16_t* d_traj; int32_t* d_fin_step;
+  int32_t* d_rstep; int32_t* d_row_of; int64_t* d_pool_out; int16_t* d_pool_traj; int32_t* d_pool_fin_step;
+  int32_t gen_ld, traj_ld, pool_rows, row_rule, pool;
+  int32_t B, N, D, Ls, max_len, pad, bos, eos;
+  int32_t greedy;          /* 1: k_greedy_accept (N = 1, D = 0, no row_rule; rows [0, n_active) all at the front of row 0) */
+  int32_t threads;         /* k_accept's block size: 0 the production choice (256 for B <= 256, 1024 above), or 256 / 1024 */
+} ttx_debug_accept_args;
+
+/* ttx_debug_accept: ONE launch of k_accept (greedy: k_greedy_accept).  `state` is a HOST array of 17 int64: on entry [0..7] =
+ * n_active, r_rows, m_rows, stop, width, steps, error, n_copy and [8..12] = accepted, produced, verified_positions,
+ * kv_prefix_positions, src_positions, put into a DecState on the device, ordered on `stream`; on return the same 13 words as the
+ * kernel left them, copied back after the launch completed, and [13..16] = the words it published for the host (stop,
+ * steps_done, width, n_active; -1 each when the kernel published nothing, as at n_active == 0).
+ * threads: production never launches 256 threads for B > 256, so that is refused; 1024 threads are a launch the kernel is
+ * written for at any B and are accepted everywhere, so both sizes can be compared wherever B <= 256.  k_greedy_accept always
+ * runs with 256 threads.  Also refused: null required pointers, n_active outside [0, B], act_idx that are not distinct rows of
+ * [0, B), a gen_ld below max_len or too small for front + D + 2 of a running row, row_of outside [0, pool_rows). */
+int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, int64_t* state, void* stream);
+
+/* ttx_debug_kvcopy: ONE launch of k_kvcopy on a grid of (B, Ld) workgroups: for slot < n_copy with record (b, best, n_acc,
+ * front_old, .) of d_rec int32 [B, 5] and j = 0 .. n_acc, the K and V thirds of step row (j == 0 ? 0 : 1 + best*D + (j-1)) of the
+ * slot, in d_qkv [Ld][B * (1 + N*D)][3d] with qkv_layer_stride floats between layers, are copied bit for bit to position
+ * front_old + j of cache row b (d_kcache / d_vcache + l * cache_layer_stride + b * cache_seq_stride, positions d wide).  Nothing
+ * else is written.  n_copy is put into a DecState on the device, ordered on `stream`.  Refused: null pointers, d not in {64, 128,
+ * 256, 512, 1024}, n_copy outside [0, B], operands that are not 16-byte aligned, strides that are not multiples of 4 or do not
+ * cover their rows, a record with b, best or n_acc out of range or front_old + n_acc + 1 positions beyond the cache row. */
+int ttx_debug_kvcopy(ttx_session* s, const int32_t* d_rec, int n_copy, const float* d_qkv, int64_t qkv_layer_stride, float* d_kcache,
+                     float* d_vcache, int64_t cache_layer_stride, int64_t cache_seq_stride, int N, int D, int d, int B, int Ld,
+                     void* stream);
+
 /* Host query, no device needed: the number of keys one k_attn2 workgroup can stage at head dimension head_dim when a group has
  * q_per_group query rows (up to 32 rows share one query image, more take the 64-row one): 384 at head dimension 32, 320 at 64;
  * 0 for a head dimension without kernels.  A launch whose key count (step self-attention: cache capacity + 1 + the draft rows

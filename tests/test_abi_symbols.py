@@ -35,6 +35,7 @@ def test_struct_sizes_match_header_layout():
     assert C.sizeof(N.GenParams) == 8 * 4
     assert C.sizeof(N.GenStats) == 6 * 8 + 2 * 8 + 2 * 8
     assert C.sizeof(N.Tensor) == 24
+    assert C.sizeof(N.DebugAcceptArgs) == 15 * 8 + 15 * 4 + 4            # ttx_debug_accept_args: 15 pointers, 15 int32, tail padding
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="only meaningful on a machine without a GPU")

@@ -306,3 +306,22 @@ def test_profiling_model_brackets_every_pool_session_and_changes_no_output(tta, 
     assert prof["launches"] >= steps * (6 * pm.num_dec_layers + 1), (prof, steps)
     assert prof["gemm_ms"] > 0 and prof["pair_overhead_ms"] >= 0
     pm.close()
+
+
+def test_one_batch_of_1200_rows_equals_its_three_sources(tta, tiny):
+    """Three fixture sources, each 400 times, shuffled, decoded as ONE batch of 1 200 rows: k_accept runs with 1 024 threads in two
+    rounds of its slot loop and of its ordered compaction, and 400 rows finish in the same step (more than its list of finished
+    rows holds, so the output copy scans all slots).  The set of fronts is the same at every step as in the batch of the three
+    sources alone, so the width rule is too: every row equals its source's row there, and so does model_calls_num."""
+    src, _, c, _ = fixture_tokens()
+    three = src[[0, 4, 8]]
+    three = three[:, :int((three != PAD).sum(1).max())]
+    g3 = tta.TranslationInferenceGreedySpeculative(tiny, 150, 10, 3, PAD, BOS, EOS, c)
+    want = g3.generate(three.cuda()).cpu()
+    assert bool((want == EOS).any(-1).all()), "every source finishes"
+    which = torch.from_numpy(np.random.default_rng(5).permutation(np.repeat(np.arange(3), 400)))
+    g = tta.TranslationInferenceGreedySpeculative(tiny, 150, 10, 3, PAD, BOS, EOS, c)
+    got = g.generate(three[which].cuda()).cpu()
+    assert got.shape == (1200,) + tuple(want.shape[1:])
+    assert torch.equal(got, want[which])
+    assert g.model_calls_num == g3.model_calls_num

@@ -93,6 +93,18 @@ class GenStats(C.Structure):
                 ("status", C.c_int64)]
 
 
+class DebugAcceptArgs(C.Structure):
+    """ttx_debug_accept_args: the device arrays and scalars of one k_accept / k_greedy_accept launch."""
+    _fields_ = [(n, C.c_void_p) for n in ("d_act_idx", "d_front", "d_gen", "d_drafts", "d_pred", "d_rec", "d_out", "d_haspad",
+                                          "d_traj", "d_fin_step", "d_rstep", "d_row_of", "d_pool_out", "d_pool_traj",
+                                          "d_pool_fin_step")] + \
+               [(n, C.c_int32) for n in ("gen_ld", "traj_ld", "pool_rows", "row_rule", "pool", "B", "N", "D", "Ls", "max_len",
+                                         "pad", "bos", "eos", "greedy", "threads")]
+
+
+DEBUG_ACCEPT_STATE_WORDS = 17     # int64 words of ttx_debug_accept's host `state` array (include/ttx.h)
+
+
 # every symbol include/ttx.h declares: (name, restype, argtypes)
 _VP, _I, _I64P = C.c_void_p, C.c_int, C.c_void_p
 SYMBOLS = {
@@ -152,6 +164,10 @@ SYMBOLS = {
                                  C.c_int64, _VP, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), _VP]),
     "ttx_debug_attn_hd": (C.c_int, [_VP, _VP, _I, _VP, _VP, _I, _VP, _I, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                     _VP, C.c_int64, _VP, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), _VP]),
+    "ttx_debug_argmax": (C.c_int, [_VP, _VP, _I, _VP, _VP, _I, _VP]),
+    "ttx_debug_embed": (C.c_int, [_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _I, _I, _I, _I, _I, _VP]),
+    "ttx_debug_accept": (C.c_int, [_VP, C.POINTER(DebugAcceptArgs), C.POINTER(C.c_int64), _VP]),
+    "ttx_debug_kvcopy": (C.c_int, [_VP, _VP, _I, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int64, _I, _I, _I, _I, _I, _VP]),
     "ttx_attn_staged_key_limit": (C.c_int, [_I, _I]),
     "ttx_last_kernel_profile": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
 }

@@ -2788,6 +2788,240 @@ extern "C" int ttx_debug_attn(ttx_session* s, const float* d_q, int ldq, const f
                            max_keys, kernel, kernel_id, stream);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Test entry points of the loop kernels (tests/test_gpu_loop_kernels.py): ONE launch of k_argmax, k_embed, k_accept /
+// k_greedy_accept or k_kvcopy with production's grid and block rules on the caller's device operands.  What the kernels take on
+// trust from the production call sites is checked here first, the device-side index arrays included (they are read back: these are
+// test calls), so that a test cannot launch a kernel on arguments that would take it out of its operands.
+static bool dbg_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static bool dbg_model_d(int d) { return d == 64 || d == 128 || d == 256 || d == 512 || d == 1024; }
+
+// The running list and the fronts of a step launch: act_idx[0, n_active) are distinct rows of [0, B) and every running row leaves
+// front + D + 2 <= gen_ld columns (what a verify step reads and writes).  Hands back the largest running front.
+static int dbg_check_slots(const char* who, const int32_t* d_act_idx, const int32_t* d_front, int B, int n_active, int gen_ld, int D,
+                           hipStream_t st, int* max_front) {
+  *max_front = 0;
+  if (n_active == 0) return TTX_OK;
+  std::vector<int32_t> act((size_t)n_active), front((size_t)B);
+  HIP_TRY(hipStreamSynchronize(st));               // the caller's writes are ordered on its stream
+  HIP_TRY(hipMemcpy(act.data(), d_act_idx, (size_t)n_active * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(front.data(), d_front, (size_t)B * 4, hipMemcpyDeviceToHost));
+  std::vector<char> seen((size_t)B, 0);
+  for (int i = 0; i < n_active; ++i) {
+    const int b = act[i];
+    if (b < 0 || b >= B || seen[b]) return fail(TTX_ERR_INVALID, std::string(who) + ": act_idx must hold distinct rows of [0, B)");
+    seen[b] = 1;
+    if (front[b] < 0 || (long long)front[b] + D + 2 > gen_ld)
+      return fail(TTX_ERR_INVALID, std::string(who) + ": gen_ld is too small for front + D + 2 (or a front is negative)");
+    *max_front = std::max(*max_front, (int)front[b]);
+  }
+  return TTX_OK;
+}
+
+extern "C" int ttx_debug_argmax(ttx_session* s, const float* d_logits, int V, int32_t* d_pred, const int32_t* d_m, int m_max,
+                                void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !d_logits || !d_pred) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_argmax");
+  if (V < 1 || m_max < 1) return fail(TTX_ERR_INVALID, "ttx_debug_argmax: V and m_max must be positive");
+  HIP_TRY(hipSetDevice(s->m->device));
+  if (d_m) {
+    int32_t m = -1;
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(&m, d_m, 4, hipMemcpyDeviceToHost));
+    if (m < 0 || m > m_max) return fail(TTX_ERR_INVALID, "ttx_debug_argmax: the live row count on the device is outside [0, m_max]");
+  }
+  hipLaunchKernelGGL(k_argmax, dim3(cdiv(m_max, 4)), dim3(256), 0, st, d_logits, V, d_pred, d_m, m_max);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+extern "C" int ttx_debug_embed(ttx_session* s, const float* d_table, int V, const float* d_pe, int pe_rows, int d, float* d_x,
+                               const int32_t* d_tok, int rows, int L, const int32_t* d_act_idx, const int32_t* d_front,
+                               const int32_t* d_gen, int gen_ld, const int32_t* d_drafts, int B, int N, int D, int n_active, int step,
+                               void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !d_table || !d_pe || !d_x) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_embed");
+  if (!dbg_model_d(d)) return fail(TTX_ERR_INVALID, "ttx_debug_embed: d must be 64, 128, 256, 512 or 1024");
+  if (V < 1 || pe_rows < 1) return fail(TTX_ERR_INVALID, "ttx_debug_embed: V and pe_rows must be positive");
+  if (!dbg_aligned16(d_table) || !dbg_aligned16(d_pe) || !dbg_aligned16(d_x))
+    return fail(TTX_ERR_INVALID, "ttx_debug_embed: float operands must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(s->m->device));
+  EmbedArgs e{};
+  e.table = d_table; e.pe = d_pe; e.X = d_x; e.d = d; e.V = V;
+  if (!step) {
+    if (!d_tok || rows < 1 || L < 1) return fail(TTX_ERR_INVALID, "ttx_debug_embed: full mode needs tokens, rows >= 1 and L >= 1");
+    if (pe_rows < L + 1) return fail(TTX_ERR_INVALID, "ttx_debug_embed: the positional table must have L + 1 rows");
+    e.tok = d_tok; e.rows = rows; e.L = L;
+    hipLaunchKernelGGL((k_embed<false>), dim3(cdiv(rows, 4)), dim3(256), 0, st, e);
+    HIP_TRY(hipGetLastError());
+    return TTX_OK;
+  }
+  if (!d_act_idx || !d_front || !d_gen || !d_drafts) return fail(TTX_ERR_INVALID, "ttx_debug_embed: step mode needs act_idx, front, gen and drafts");
+  if (B < 1 || N < 1 || D < 1 || gen_ld < 1) return fail(TTX_ERR_INVALID, "ttx_debug_embed: step mode needs B, N, D and gen_ld >= 1");
+  if (n_active < 0 || n_active > B) return fail(TTX_ERR_INVALID, "ttx_debug_embed: n_active must lie in [0, B]");
+  int max_front = 0;
+  TTX_TRY(dbg_check_slots("ttx_debug_embed", d_act_idx, d_front, B, n_active, gen_ld, D, st, &max_front));
+  if (n_active > 0 && pe_rows < max_front + D + 2) return fail(TTX_ERR_INVALID, "ttx_debug_embed: the positional table must have front + D + 2 rows");
+  const int RPS = step_rps(N, D);
+  // the live row count reaches the kernel as production hands it over: in a DecState on the device, written on the launch's stream
+  DecState* dst = nullptr;
+  HIP_TRY(hipMalloc((void**)&dst, sizeof(DecState)));
+  DecState* hs = reinterpret_cast<DecState*>(s->host_state);
+  *hs = DecState{};
+  hs->n_active = n_active; hs->r_rows = n_active * N; hs->m_rows = n_active * RPS;
+  hipError_t err = hipMemcpyAsync(dst, hs, sizeof(DecState), hipMemcpyHostToDevice, st);
+  if (err == hipSuccess) {
+    e.st = dst; e.act_idx = d_act_idx; e.front = d_front; e.gen = d_gen; e.gen_ld = gen_ld; e.drafts = d_drafts; e.N = N; e.D = D;
+    hipLaunchKernelGGL((k_embed<true>), dim3(cdiv(B * RPS, 4)), dim3(256), 0, st, e);
+    err = hipGetLastError();
+  }
+  const hipError_t esync = hipStreamSynchronize(st);   // the launch reads the state: keep it until the launch is through
+  (void)hipFree(dst);
+  HIP_TRY(err);
+  HIP_TRY(esync);
+  return TTX_OK;
+}
+
+extern "C" int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, int64_t* state, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !a || !state) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_accept");
+  if (!a->d_act_idx || !a->d_front || !a->d_gen || !a->d_pred || !a->d_rec)
+    return fail(TTX_ERR_INVALID, "ttx_debug_accept: act_idx, front, gen, pred and rec are required");
+  const bool greedy = a->greedy != 0;
+  if (greedy && (a->row_rule || a->pool || a->N != 1 || a->D != 0))
+    return fail(TTX_ERR_INVALID, "ttx_debug_accept: plain greedy runs with N = 1, D = 0 and neither row_rule nor pool");
+  if (!greedy && (!a->d_drafts || !a->d_haspad || a->N < 1 || a->D < 1))
+    return fail(TTX_ERR_INVALID, "ttx_debug_accept: the speculative step needs drafts, haspad, N >= 1 and D >= 1");
+  if (a->pool && !a->row_rule) return fail(TTX_ERR_INVALID, "ttx_debug_accept: pool implies row_rule");
+  if (!greedy && !a->pool && !a->d_out) return fail(TTX_ERR_INVALID, "ttx_debug_accept: out is required outside pool mode");
+  if (a->row_rule && !a->pool && (!a->d_traj || !a->d_fin_step)) return fail(TTX_ERR_INVALID, "ttx_debug_accept: row_rule needs traj and fin_step");
+  if (a->pool && (!a->d_rstep || !a->d_row_of || !a->d_pool_out || !a->d_pool_traj || !a->d_pool_fin_step || a->pool_rows < 1))
+    return fail(TTX_ERR_INVALID, "ttx_debug_accept: pool mode needs rstep, row_of and the caller-side out, traj and fin_step rows");
+  if (a->row_rule && a->traj_ld < 1) return fail(TTX_ERR_INVALID, "ttx_debug_accept: traj_ld must be positive");
+  if (a->B < 1 || a->max_len < 1 || a->gen_ld < 1 || a->Ls < 0) return fail(TTX_ERR_INVALID, "ttx_debug_accept: B, max_len and gen_ld must be positive");
+  // production launches 256 threads for B <= 256 and ACCEPT_THREADS above; 256 threads at B > 256 is a launch it never makes
+  if (a->threads != 0 && a->threads != 256 && a->threads != ACCEPT_THREADS) return fail(TTX_ERR_INVALID, "ttx_debug_accept: threads is 0, 256 or 1024");
+  if (a->threads == 256 && a->B > 256) return fail(TTX_ERR_INVALID, "ttx_debug_accept: 256 threads are never launched for B > 256");
+  if (greedy && a->threads == ACCEPT_THREADS) return fail(TTX_ERR_INVALID, "ttx_debug_accept: plain greedy always runs with 256 threads");
+  const int n_active = (int)state[0];
+  if (state[0] < 0 || state[0] > a->B) return fail(TTX_ERR_INVALID, "ttx_debug_accept: n_active must lie in [0, B]");
+  if (a->gen_ld < a->max_len) return fail(TTX_ERR_INVALID, "ttx_debug_accept: gen_ld must cover max_len (finished rows are copied from gen)");
+  HIP_TRY(hipSetDevice(s->m->device));
+  int max_front = 0;
+  if (greedy) {
+    // every row shares the front of row 0 and the running rows are rows [0, n_active)
+    if (n_active > 0) {
+      int32_t f0 = -1;
+      HIP_TRY(hipStreamSynchronize(st));
+      HIP_TRY(hipMemcpy(&f0, a->d_front, 4, hipMemcpyDeviceToHost));
+      if (f0 < 0 || (long long)f0 + 2 > a->gen_ld) return fail(TTX_ERR_INVALID, "ttx_debug_accept: gen_ld is too small for front + D + 2");
+    }
+  } else {
+    TTX_TRY(dbg_check_slots("ttx_debug_accept", a->d_act_idx, a->d_front, a->B, n_active, a->gen_ld, a->D, st, &max_front));
+    if (a->pool && n_active > 0) {
+      std::vector<int32_t> row_of((size_t)a->B);
+      HIP_TRY(hipMemcpy(row_of.data(), a->d_row_of, (size_t)a->B * 4, hipMemcpyDeviceToHost));
+      std::vector<int32_t> act((size_t)n_active);
+      HIP_TRY(hipMemcpy(act.data(), a->d_act_idx, (size_t)n_active * 4, hipMemcpyDeviceToHost));
+      for (int i = 0; i < n_active; ++i)
+        if (row_of[act[i]] < 0 || row_of[act[i]] >= a->pool_rows) return fail(TTX_ERR_INVALID, "ttx_debug_accept: row_of must lie in [0, pool_rows)");
+    }
+  }
+  HostInfo* hinfo = nullptr;
+  HostInfo* dev_info = nullptr;
+  DecState* dst = nullptr;
+  PoolIo* dio = nullptr;
+  hipError_t err = hipHostMalloc((void**)&hinfo, sizeof(HostInfo), hipHostMallocMapped);
+  if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&dev_info, (void*)hinfo, 0);
+  if (err == hipSuccess) err = hipMalloc((void**)&dst, sizeof(DecState));
+  if (err == hipSuccess && a->pool) err = hipMalloc((void**)&dio, sizeof(PoolIo));
+  DecState* hs = reinterpret_cast<DecState*>(s->host_state);
+  PoolIo hio{a->d_pool_out, a->d_pool_traj, a->d_pool_fin_step, a->traj_ld, 0};
+  if (err == hipSuccess) {
+    *hinfo = HostInfo{-1, -1, -1, -1};
+    hs->n_active = n_active; hs->r_rows = (int)state[1]; hs->m_rows = (int)state[2]; hs->stop = (int)state[3];
+    hs->width = (int)state[4]; hs->steps = (int)state[5]; hs->error = (int)state[6]; hs->n_copy = (int)state[7];
+    hs->accepted = state[8]; hs->produced = state[9]; hs->verified_positions = state[10]; hs->kv_prefix_positions = state[11];
+    hs->src_positions = state[12];
+    // the entry state reaches the kernel as production hands it over: in a DecState on the device, written on the launch's stream
+    err = hipMemcpyAsync(dst, hs, sizeof(DecState), hipMemcpyHostToDevice, st);
+  }
+  if (err == hipSuccess && a->pool) err = hipMemcpyAsync(dio, &hio, sizeof(PoolIo), hipMemcpyHostToDevice, st);
+  if (err == hipSuccess) {
+    LoopArgs la{};
+    la.st = dst; la.act_idx = a->d_act_idx; la.front = a->d_front; la.gen = a->d_gen; la.gen_ld = a->gen_ld;
+    la.drafts = a->d_drafts; la.pred = a->d_pred; la.rec = reinterpret_cast<CopyRec*>(a->d_rec); la.out = a->d_out;
+    la.host = dev_info; la.haspad = a->d_haspad;
+    la.row_rule = a->row_rule ? 1 : 0; la.traj = a->d_traj; la.traj_ld = a->traj_ld; la.fin_step = a->d_fin_step;
+    la.pool = a->pool ? 1 : 0; la.rstep = a->d_rstep; la.row_of = a->d_row_of; la.io = dio;
+    la.B = a->B; la.N = a->N; la.D = a->D; la.Ls = a->Ls; la.max_len = a->max_len; la.pad = a->pad; la.bos = a->bos; la.eos = a->eos;
+    if (greedy) hipLaunchKernelGGL(k_greedy_accept, dim3(1), dim3(256), 0, st, la);
+    else hipLaunchKernelGGL(k_accept, dim3(1), dim3(a->threads ? a->threads : (a->B > 256 ? ACCEPT_THREADS : 256)), 0, st, la);
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess) err = hipMemcpyAsync(hs, dst, sizeof(DecState), hipMemcpyDeviceToHost, st);
+  const hipError_t esync = hipStreamSynchronize(st);
+  if (err == hipSuccess && esync == hipSuccess) {
+    state[0] = hs->n_active; state[1] = hs->r_rows; state[2] = hs->m_rows; state[3] = hs->stop; state[4] = hs->width;
+    state[5] = hs->steps; state[6] = hs->error; state[7] = hs->n_copy;
+    state[8] = hs->accepted; state[9] = hs->produced; state[10] = hs->verified_positions; state[11] = hs->kv_prefix_positions;
+    state[12] = hs->src_positions;
+    state[13] = hinfo->stop; state[14] = hinfo->steps_done; state[15] = hinfo->width; state[16] = hinfo->n_active;
+  }
+  if (dio) (void)hipFree(dio);
+  if (dst) (void)hipFree(dst);
+  if (hinfo) (void)hipHostFree(hinfo);
+  HIP_TRY(err);
+  HIP_TRY(esync);
+  return TTX_OK;
+}
+
+extern "C" int ttx_debug_kvcopy(ttx_session* s, const int32_t* d_rec, int n_copy, const float* d_qkv, int64_t qkv_layer_stride,
+                                float* d_kcache, float* d_vcache, int64_t cache_layer_stride, int64_t cache_seq_stride, int N, int D,
+                                int d, int B, int Ld, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !d_rec || !d_qkv || !d_kcache || !d_vcache) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_kvcopy");
+  if (!dbg_model_d(d)) return fail(TTX_ERR_INVALID, "ttx_debug_kvcopy: d must be 64, 128, 256, 512 or 1024");
+  if (B < 1 || Ld < 1 || N < 1 || D < 0) return fail(TTX_ERR_INVALID, "ttx_debug_kvcopy: B, Ld and N must be positive, D >= 0");
+  if (n_copy < 0 || n_copy > B) return fail(TTX_ERR_INVALID, "ttx_debug_kvcopy: n_copy must lie in [0, B]");
+  if (!dbg_aligned16(d_qkv) || !dbg_aligned16(d_kcache) || !dbg_aligned16(d_vcache))
+    return fail(TTX_ERR_INVALID, "ttx_debug_kvcopy: float operands must be 16-byte aligned");
+  const int RPS = step_rps(N, D);
+  if ((qkv_layer_stride & 3) || qkv_layer_stride < (int64_t)B * RPS * 3 * d)
+    return fail(TTX_ERR_INVALID, "ttx_debug_kvcopy: qkv_layer_stride must be a multiple of 4 covering B * (1 + N*D) rows of 3d");
+  if ((cache_seq_stride & 3) || cache_seq_stride < d || (cache_layer_stride & 3) || cache_layer_stride < (int64_t)B * cache_seq_stride)
+    return fail(TTX_ERR_INVALID, "ttx_debug_kvcopy: the cache strides must be multiples of 4, a row's covering d and a layer's B rows");
+  HIP_TRY(hipSetDevice(s->m->device));
+  if (n_copy > 0) {
+    std::vector<CopyRec> rec((size_t)n_copy);
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(rec.data(), d_rec, (size_t)n_copy * sizeof(CopyRec), hipMemcpyDeviceToHost));
+    for (const CopyRec& r : rec)
+      if (r.b < 0 || r.b >= B || r.best < 0 || r.best >= N || r.nacc < 0 || r.nacc > D || r.front_old < 0 ||
+          ((int64_t)r.front_old + r.nacc + 1) * d > cache_seq_stride)
+        return fail(TTX_ERR_INVALID, "ttx_debug_kvcopy: a record is outside the operands (b, best, nacc or front_old + nacc + 1 positions)");
+  }
+  DecState* dst = nullptr;
+  HIP_TRY(hipMalloc((void**)&dst, sizeof(DecState)));
+  DecState* hs = reinterpret_cast<DecState*>(s->host_state);
+  *hs = DecState{};
+  hs->n_copy = n_copy;
+  hipError_t err = hipMemcpyAsync(dst, hs, sizeof(DecState), hipMemcpyHostToDevice, st);
+  if (err == hipSuccess) {
+    KvCopyArgs kc{};
+    kc.st = dst; kc.rec = reinterpret_cast<const CopyRec*>(d_rec); kc.qkv = d_qkv; kc.qkv_layer_stride = (long long)qkv_layer_stride;
+    kc.kcache = d_kcache; kc.vcache = d_vcache; kc.cache_layer_stride = (long long)cache_layer_stride;
+    kc.cache_seq_stride = (long long)cache_seq_stride; kc.N = N; kc.D = D; kc.d = d;
+    hipLaunchKernelGGL(k_kvcopy, dim3(B, Ld), dim3(256), 0, st, kc);
+    err = hipGetLastError();
+  }
+  const hipError_t esync = hipStreamSynchronize(st);
+  (void)hipFree(dst);
+  HIP_TRY(err);
+  HIP_TRY(esync);
+  return TTX_OK;
+}
+
 extern "C" int ttx_attn_staged_key_limit(int head_dim, int q_per_group) { return attn_staged_key_limit(head_dim, q_per_group); }
 
 extern "C" int ttx_last_kernel_profile(ttx_session* s, double* gemm_ms, int64_t* gemm_launches, double* empty_pair_ms) {

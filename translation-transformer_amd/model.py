@@ -238,6 +238,50 @@ class NativeTransformer:
                                             int(groups), int(n_active), int(max_keys), int(kernel), C.byref(kid), self._stream()))
         return int(kid.value)
 
+    def debug_argmax(self, logits: torch.Tensor, pred: torch.Tensor, m_max: int, m_live: torch.Tensor | None = None) -> None:
+        """One k_argmax launch (ttx_debug_argmax): ``logits`` fp32 [m_max, V] contiguous, ``pred`` int32 [m_max], ``m_live`` an
+        int32 device scalar or None."""
+        N.check(self._lib.ttx_debug_argmax(self._session, logits.data_ptr(), int(logits.shape[1]), pred.data_ptr(),
+                                           self._ptr(m_live), int(m_max), self._stream()))
+
+    def debug_embed(self, table: torch.Tensor, pe: torch.Tensor, x: torch.Tensor, tok: torch.Tensor | None = None, rows: int = 0,
+                    L: int = 0, act_idx: torch.Tensor | None = None, front: torch.Tensor | None = None,
+                    gen: torch.Tensor | None = None, drafts: torch.Tensor | None = None, B: int = 0, n: int = 1, d: int = 0,
+                    n_active: int = 0, step: bool = False) -> None:
+        """One k_embed launch (ttx_debug_embed) on the caller's tables: full mode takes ``tok`` int32 [rows] and ``L``, step mode
+        ``act_idx`` / ``front`` int32 [B], ``gen`` int32 [B, gen_ld], ``drafts`` int32 [B, n, d] and ``n_active``."""
+        N.check(self._lib.ttx_debug_embed(self._session, table.data_ptr(), int(table.shape[0]), pe.data_ptr(), int(pe.shape[0]),
+                                          int(table.shape[1]), x.data_ptr(), self._ptr(tok), int(rows), int(L), self._ptr(act_idx),
+                                          self._ptr(front), self._ptr(gen), 0 if gen is None else int(gen.stride(0)),
+                                          self._ptr(drafts), int(B), int(n), int(d), int(n_active), int(bool(step)), self._stream()))
+
+    def debug_accept(self, state, *, B: int, n: int, d: int, Ls: int, max_len: int, pad: int, bos: int, eos: int, gen_ld: int,
+                     greedy: bool = False, threads: int = 0, row_rule: bool = False, pool: bool = False, traj_ld: int = 0,
+                     pool_rows: int = 0, **arrays) -> list:
+        """One k_accept (``greedy``: k_greedy_accept) launch (ttx_debug_accept).  ``state``: the 13 entry words of the DecState
+        (include/ttx.h); ``arrays``: device tensors named as the fields of ttx_debug_accept_args without the ``d_`` prefix.
+        Returns the 17 exit words: the DecState the kernel left and the four words it published for the host."""
+        a = N.DebugAcceptArgs()
+        for name, _ in N.DebugAcceptArgs._fields_[:15]:
+            t = arrays.pop(name[2:], None)
+            setattr(a, name, None if t is None else t.data_ptr())
+        assert not arrays, f"unknown operands {sorted(arrays)}"
+        a.gen_ld, a.traj_ld, a.pool_rows, a.row_rule, a.pool = int(gen_ld), int(traj_ld), int(pool_rows), int(row_rule), int(pool)
+        a.B, a.N, a.D, a.Ls, a.max_len, a.pad, a.bos, a.eos = int(B), int(n), int(d), int(Ls), int(max_len), int(pad), int(bos), int(eos)
+        a.greedy, a.threads = int(greedy), int(threads)
+        words = (C.c_int64 * N.DEBUG_ACCEPT_STATE_WORDS)(*[int(v) for v in state], *([0] * (N.DEBUG_ACCEPT_STATE_WORDS - len(state))))
+        N.check(self._lib.ttx_debug_accept(self._session, C.byref(a), words, self._stream()))
+        return [int(v) for v in words]
+
+    def debug_kvcopy(self, rec: torch.Tensor, n_copy: int, qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
+                     n: int, d: int, width: int, B: int) -> None:
+        """One k_kvcopy launch (ttx_debug_kvcopy): ``rec`` int32 [B, 5], ``qkv`` fp32 [Ld, B * (1 + n*d), 3 * width], the caches
+        fp32 [Ld, B, Lc, width]; all contiguous in their last dimensions."""
+        assert kcache.stride() == vcache.stride()
+        N.check(self._lib.ttx_debug_kvcopy(self._session, rec.data_ptr(), int(n_copy), qkv.data_ptr(), int(qkv.stride(0)),
+                                           kcache.data_ptr(), vcache.data_ptr(), int(kcache.stride(0)), int(kcache.stride(1)),
+                                           int(n), int(d), int(width), int(B), int(qkv.shape[0]), self._stream()))
+
     @staticmethod
     def attn_staged_key_limit(head_dim: int, q_per_group: int) -> int:
         """Keys one k_attn2 workgroup can stage at ``head_dim`` for groups of ``q_per_group`` query rows
