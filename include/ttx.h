@@ -447,6 +447,16 @@ int ttx_debug_attn_hd(ttx_session* s, const float* d_q, int ldq, const float* d_
                       const int32_t* d_cache_slot, int gen_ld, int N, int D, int mode, int groups, int n_active, int max_keys,
                       int kernel, int32_t* kernel_id, void* stream);
 
+/* ttx_debug_attn_hd for a step-mode launch that chooses between k_attn2 and k_attn as a launch in the layout (sel_N, sel_D) on the
+ * same cache does: what the probe of the two-phase verify step does with the draft pass's layout (DESIGN.md "Two-phase verify
+ * step"), because the two kernels do not give the same bits.  kernel = 0 is the case it exists for.  Refused: sel_N < 1, sel_D < 0. */
+int ttx_debug_attn_as(ttx_session* s, const float* d_q, int ldq, const float* d_k, const float* d_v, int ldkv, float* d_out, int H,
+                      int head_dim, float scale, int L, int Lk, const int32_t* d_tok, int pad, const uint8_t* d_key_pad,
+                      const int32_t* d_mem_row, const int32_t* d_act_idx, const int32_t* d_front, const int32_t* d_src_of,
+                      const int32_t* d_src_len, const float* d_kcache, const float* d_vcache, int64_t cache_seq_stride,
+                      const int32_t* d_cache_slot, int gen_ld, int N, int D, int mode, int groups, int n_active, int max_keys,
+                      int kernel, int32_t* kernel_id, int sel_N, int sel_D, void* stream);
+
 /* Test entry points (tests/test_gpu_loop_kernels.py): ONE launch of a loop kernel of csrc/ttx_loop_kernels.hip.h on DEVICE operands
  * of the caller, with production's grid and block rules.  All of them are integer or bit-copy work: the tests ask for exact
  * equality with tests/util_loop_checks.py.  Nothing is launched and TTX_ERR_INVALID is returned for arguments a kernel cannot
@@ -508,6 +518,33 @@ int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, int64_t* st
 int ttx_debug_kvcopy(ttx_session* s, const int32_t* d_rec, int n_copy, const float* d_qkv, int64_t qkv_layer_stride, float* d_kcache,
                      float* d_vcache, int64_t cache_layer_stride, int64_t cache_seq_stride, int N, int D, int d, int B, int Ld,
                      void* stream);
+
+/* ttx_debug_kvcopy_split: ttx_debug_kvcopy with the indirection of the two-phase verify step (DESIGN.md "Two-phase verify step").
+ * d_pos2 int32 [n_copy]: a slot with pos2 >= 0 takes its step rows from position pos2 of d_qkv instead of its own; a slot with
+ * pos2 == -1 takes the K and V thirds of its single row of d_qkv_probe [Ld][B][3d] (probe_layer_stride floats between layers) and
+ * commits that row alone, at front_old.  With d_pos2 and d_qkv_probe both NULL it is ttx_debug_kvcopy.  Also refused: one of the
+ * two without the other, a probe buffer that is not 16-byte aligned or whose stride does not cover B rows, pos2 outside [-1, B),
+ * a record with n_acc != 0 at pos2 == -1. */
+int ttx_debug_kvcopy_split(ttx_session* s, const int32_t* d_rec, int n_copy, const float* d_qkv, int64_t qkv_layer_stride,
+                           float* d_kcache, float* d_vcache, int64_t cache_layer_stride, int64_t cache_seq_stride, int N, int D, int d,
+                           int B, int Ld, const int32_t* d_pos2, const float* d_qkv_probe, int64_t probe_layer_stride, void* stream);
+
+/* ttx_debug_probe_split: ONE launch of k_probe_split (one workgroup: 256 threads for B <= 256, 1024 above).  Slot g < n_active is
+ * sequence b = d_act_idx[g]; it matches when d_pred_probe[g] equals d_drafts[b, n, 0] for some n (drafts int32 [B, N, D]).  The
+ * matching sequences are written to d_act2 in the order of d_act_idx (entries past the match count are not written) and
+ * d_pos2[g] = the slot's position in d_act2, or -1.  `result` is a HOST array of 7 int32: on entry [4] = probes counted so far;
+ * on return [0..2] = n_active, r_rows, m_rows of the draft pass's DecState (matches, matches * N, matches * (1 + N*D)), [3] = the
+ * executed rows n_active + matches * (1 + N*D), [4] = the probe count, [5..6] = the words published for the host (matches,
+ * probes_done).  Refused: null pointers, B, N or D < 1, n_active outside [0, B], act_idx that are not distinct rows of [0, B). */
+int ttx_debug_probe_split(ttx_session* s, const int32_t* d_act_idx, const int32_t* d_pred_probe, const int32_t* d_drafts, int B, int N,
+                          int D, int n_active, int32_t* d_act2, int32_t* d_pos2, int32_t* result, void* stream);
+
+/* ttx_debug_merge_pred: ONE launch of k_merge_pred: d_pred [n_active * (1 + N*D)] in k_accept's layout; a slot with pos2 >= 0
+ * takes the 1 + N*D predictions at position pos2 of d_pred2, any other slot d_pred_probe[g] in row 0 and -1 in its draft rows.
+ * Rows past n_active * (1 + N*D) are not written.  Refused: null pointers, B, N or D < 1, n_active outside [0, B], pos2 outside
+ * [-1, B). */
+int ttx_debug_merge_pred(ttx_session* s, const int32_t* d_pos2, const int32_t* d_pred_probe, const int32_t* d_pred2, int32_t* d_pred,
+                         int B, int N, int D, int n_active, void* stream);
 
 /* Host query, no device needed: the number of keys one k_attn2 workgroup can stage at head dimension head_dim when a group has
  * q_per_group query rows (up to 32 rows share one query image, more take the 64-row one): 384 at head dimension 32, 320 at 64;

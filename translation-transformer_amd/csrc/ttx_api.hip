@@ -303,11 +303,16 @@ extern "C" int ttx_session_create(ttx_model* m, ttx_session** out) {
   ttx_session* s = new ttx_session();
   s->m = m;
   if (hipHostMalloc((void**)&s->host_info, sizeof(HostInfo), hipHostMallocMapped) != hipSuccess ||
+      hipHostMalloc((void**)&s->probe_info, sizeof(ProbeInfo), hipHostMallocMapped) != hipSuccess ||
       hipHostMalloc((void**)&s->host_state, sizeof(DecState), hipHostMallocDefault) != hipSuccess) {
+    if (s->host_info) (void)hipHostFree(s->host_info);
+    if (s->probe_info) (void)hipHostFree(s->probe_info);
+    if (s->host_state) (void)hipHostFree(s->host_state);
     delete s;
     return fail(TTX_ERR_NOMEM, "hipHostMalloc failed");
   }
   std::memset(s->host_info, 0, sizeof(HostInfo));
+  std::memset(s->probe_info, 0, sizeof(ProbeInfo));
   HIP_TRY(hipEventCreate(&s->ev_a));
   HIP_TRY(hipEventCreate(&s->ev_b));
   HIP_TRY(hipEventCreate(&s->ev_c));
@@ -344,6 +349,7 @@ extern "C" void ttx_session_destroy(ttx_session* s) {
   for (Buf* b : s->all)
     if (b->p) (void)hipFree(b->p);
   if (s->host_info) (void)hipHostFree(s->host_info);
+  if (s->probe_info) (void)hipHostFree(s->probe_info);
   if (s->beam_host) (void)hipHostFree(s->beam_host);
   if (s->bp_host) (void)hipHostFree(s->bp_host);
   s->drop_graphs();
@@ -740,6 +746,12 @@ struct StepCtx {
   const int* cache_slot = nullptr; // batch pool: running row (candidate) -> slot of its KV cache
   bool want_argmax = true;
   int variant = GV_BIG;            // GemmVariant of this step's launches (bit-identical results; chosen from the live row count)
+  // two-phase verify step of the slot pool; unset (null): the session's state, active list, step QKV buffer and argmax buffer
+  DecState* st_ov = nullptr;       // live rows of this pass
+  const int* act_ov = nullptr;     // sequences of this pass
+  float* qkv_ov = nullptr;         // [Ld][B * RPS][3d]
+  int* pred_ov = nullptr;          // [B * RPS]
+  int sel_N = 0, sel_D = 0;        // probe: the layout of the draft pass, whose choice between k_attn2 and k_attn it takes
 };
 
 static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) {
@@ -750,7 +762,9 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
   const int RPS = step_rps(k.N, k.D);
   const int Mmax = k.B * RPS;
   const int vq = variant_qkv(k.variant), vd = variant_dd(k.variant), v1 = variant_ffn1(k.variant), vf = variant_ffn2(k.variant);
-  DecState* dst = s->state.as<DecState>();
+  DecState* dst = k.st_ov ? k.st_ov : s->state.as<DecState>();
+  const int* act = k.act_ov ? k.act_ov : s->act_idx.as<int>();
+  float* qkv_base = k.qkv_ov ? k.qkv_ov : s->qkv.as<float>();
   const int* m_ptr = &dst->m_rows;
   float* x = s->x.as<float>();
   float* x1 = s->x1.as<float>();
@@ -765,9 +779,14 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
   const long long cache_seq = (long long)k.Lc * d;
   const long long cache_layer = (long long)k.B * cache_seq;
 
+  struct AttnSel {                 // the attention launches of this step choose their kernel as the layout (sel_N, sel_D) does
+    ttx_session* s;
+    AttnSel(ttx_session* s_, int N, int D) : s(s_) { s->attn_sel_N = N; s->attn_sel_D = D; }
+    ~AttnSel() { s->attn_sel_N = 0; s->attn_sel_D = 0; }
+  } attn_sel(s, k.sel_N, k.sel_D);
   EmbedArgs e{};
   e.table = m->p(m->tgt_emb); e.pe = m->p(m->pe); e.X = x; e.d = d; e.V = c.vocab_size;
-  e.st = dst; e.act_idx = s->act_idx.as<int>(); e.front = s->front.as<int>(); e.gen = s->gen.as<int>(); e.gen_ld = k.gen_ld;
+  e.st = dst; e.act_idx = act; e.front = s->front.as<int>(); e.gen = s->gen.as<int>(); e.gen_ld = k.gen_ld;
   e.drafts = s->drafts.as<int>(); e.N = k.N; e.D = k.D;
   hipLaunchKernelGGL((k_embed<true>), dim3(cdiv(Mmax, 4)), dim3(256), 0, st, e);
   HIP_TRY(hipGetLastError());
@@ -775,11 +794,11 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
   for (int l = 0; l < Ld; ++l) {
     const LayerW& w = m->dec[l];
     const bool last = (l == Ld - 1);
-    float* qkv = s->qkv.as<float>() + (size_t)l * qkv_layer;
+    float* qkv = qkv_base + (size_t)l * qkv_layer;
     TTX_TRY(launch_gemm(s, st, x, d, m->p(w.sa_in_w), d, m->p(w.sa_in_b), qkv, 3 * d, m_ptr, Mmax, 3 * d, d, false, 0, 0, vq));
     AttnArgs a{};
     a.q = qkv; a.ldq = 3 * d; a.k = qkv + d; a.v = qkv + 2 * d; a.ldkv = 3 * d; a.out = ao; a.d = d; a.scale = scale;
-    a.tok = s->gen.as<int>(); a.pad = c.pad_token; a.st = dst; a.act_idx = s->act_idx.as<int>(); a.front = s->front.as<int>();
+    a.tok = s->gen.as<int>(); a.pad = c.pad_token; a.st = dst; a.act_idx = act; a.front = s->front.as<int>();
     a.kcache = (k.kcache ? k.kcache : s->kcache.as<float>()) + (size_t)l * cache_layer;
     a.vcache = (k.vcache ? k.vcache : s->vcache.as<float>()) + (size_t)l * cache_layer;
     a.cache_seq_stride = cache_seq; a.gen_ld = k.gen_ld; a.N = k.N; a.D = k.D; a.cache_slot = k.cache_slot;
@@ -790,7 +809,7 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
     AttnArgs ca{};
     ca.q = q2; ca.ldq = d; ca.k = s->memkv.as<float>() + (size_t)l * 2 * d; ca.v = ca.k + d; ca.ldkv = Ld * 2 * d;
     ca.out = ao; ca.d = d; ca.scale = scale; ca.Lk = k.Ls; ca.key_pad = s->src_valid.as<uint8_t>();
-    ca.st = dst; ca.act_idx = s->act_idx.as<int>(); ca.front = s->front.as<int>(); ca.N = k.N; ca.D = k.D;
+    ca.st = dst; ca.act_idx = act; ca.front = s->front.as<int>(); ca.N = k.N; ca.D = k.D;
     ca.src_of = k.src_of; ca.src_len = k.src_len;
     TTX_TRY(launch_attn(ATT_STEP_CROSS, s, st, ca, k.B, H, RPS, k.Ls, k.N, D1));
     TTX_TRY(gemm_ln(s, st, ao, d, d, m->p(w.ca_out_w), m->p(w.ca_out_b), x1, m->p(w.n2_w), m->p(w.n2_b), nullptr, nullptr,
@@ -801,7 +820,7 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
   }
   TTX_TRY(launch_gemm(s, st, xf, d, m->p(m->cls_w), d, m->p(m->cls_b), logits, V, m_ptr, Mmax, V, d, false, 0, 0, vd));
   if (k.want_argmax) {
-    hipLaunchKernelGGL(k_argmax, dim3(cdiv(Mmax, 4)), dim3(256), 0, st, logits, V, s->pred.as<int>(), m_ptr, Mmax);
+    hipLaunchKernelGGL(k_argmax, dim3(cdiv(Mmax, 4)), dim3(256), 0, st, logits, V, k.pred_ov ? k.pred_ov : s->pred.as<int>(), m_ptr, Mmax);
     HIP_TRY(hipGetLastError());
   }
   return TTX_OK;
@@ -1200,6 +1219,14 @@ struct PoolJob {
   unsigned idle_spins = 0;
   std::chrono::steady_clock::time_point last_progress = std::chrono::steady_clock::now();
   long long admitted_rows = 0, src_tokens_padded = 0;
+  // two-phase verify step (DESIGN.md "Two-phase verify step"): a free choice per step, both forms give the same bits
+  bool two_phase = true;    // TTX_TWO_PHASE=0: every step in one pass
+  long long min_rows = 800; // TTX_TWO_PHASE_MIN_ROWS: steps with fewer live rows (slots * RPS) run in one pass; 0: always split
+  GenCtx g2{};              // accept and commit behind a split step: executed-row count, indirection of the K/V commit
+  ProbeInfo* dev_probe = nullptr;   // device address of the session's pinned probe words
+  int probes = 0;           // probes launched
+  bool probe_pending = false;   // a probe is in flight; the step's second graph follows once it has published
+  long long slot_steps = 0, matched_slot_steps = 0, split_steps = 0, skipped_draft_passes = 0;   // TTX_TWO_PHASE_STATS=1
 };
 
 static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_cap, const ttx_gen_params* p, int64_t* d_out,
@@ -1238,10 +1265,26 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
   TTX_TRY(ensure_acts(s, st, Macts, 1));
   TTX_TRY(ensure(s->qkv, std::max((size_t)Ld * Mmax, (size_t)C * Ls_cap) * 3 * d * 4, st));
   TTX_TRY(ensure(s->slab, sizeof(float) * 16 * Macts * d, st));
+  // read at the start of every pool call
+  j.two_phase = true; j.min_rows = 800; j.probes = 0; j.probe_pending = false;
+  j.slot_steps = j.matched_slot_steps = j.split_steps = j.skipped_draft_passes = 0;
+  if (const char* e = getenv("TTX_TWO_PHASE")) j.two_phase = atoi(e) != 0;
+  if (const char* e = getenv("TTX_TWO_PHASE_MIN_ROWS")) j.min_rows = std::max(0, atoi(e));
+  if (j.two_phase) {                                              // nothing may allocate inside a capture
+    TTX_TRY(ensure(s->qkv_probe, (size_t)Ld * C * 3 * d * 4, st));
+    for (Buf* b : {&s->pred_probe, &s->act2, &s->pos2}) TTX_TRY(ensure(*b, (size_t)C * 4, st));
+    TTX_TRY(ensure(s->pred_draft, Mmax * 4, st));
+    TTX_TRY(ensure(s->state2, 3 * sizeof(DecState), st));
+  }
   s->graphs_current();
 
   s->ev_used = 0;
   HIP_TRY(hipEventRecord(s->ev_a, st));
+  if (j.two_phase) {
+    HIP_TRY(hipMemsetAsync(s->state2.p, 0, 3 * sizeof(DecState), st));
+    s->probe_info->matches = 0; s->probe_info->probes_done = 0;
+    HIP_TRY(hipHostGetDevicePointer((void**)&j.dev_probe, (void*)s->probe_info, 0));
+  }
   j.io = PoolIo{d_out, d_traj, d_fin, max_len + 1, 0};        // lives in the job until every stream has drained
   HIP_TRY(hipMemcpyAsync(s->pool_io.p, &j.io, sizeof(j.io), hipMemcpyHostToDevice, st));
   g.la.st = s->state.as<DecState>(); g.la.act_idx = s->act_idx.as<int>(); g.la.front = s->front.as<int>();
@@ -1260,6 +1303,11 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
   g.kc.kcache = s->kcache.as<float>(); g.kc.vcache = s->vcache.as<float>();
   g.kc.cache_seq_stride = (long long)g.k.Lc * d; g.kc.cache_layer_stride = (long long)C * g.k.Lc * d;
   g.kc.N = N; g.kc.D = D; g.kc.d = d;
+  j.g2 = g;
+  if (j.two_phase) {
+    j.g2.la.exec_rows = reinterpret_cast<const int*>(s->state2.as<DecState>() + 2);
+    j.g2.kc.pos2 = s->pos2.as<int>(); j.g2.kc.qkv_probe = s->qkv_probe.as<float>(); j.g2.kc.probe_layer_stride = (long long)C * 3 * d;
+  }
   s->host_info->stop = 0; s->host_info->steps_done = 0; s->host_info->width = 1; s->host_info->n_active = 0;
   hipLaunchKernelGGL(k_pool_init, dim3(4), dim3(256), 0, st, g.la);
   HIP_TRY(hipGetLastError());
@@ -1307,28 +1355,23 @@ static int pool_admit(PoolJob& j, const int64_t* d_src_rows, int ld_src, int R, 
   return TTX_OK;
 }
 
-static int pool_launch_step(PoolJob& j, int n_live) {
+// Enqueue one graph's worth of a pool step: replayed from the captured graph of `key`, captured on second use (the first use of
+// a shape runs eagerly: function attributes are set outside capture), or eagerly (TTX_NO_GRAPH, profiling sessions).
+template <class Enqueue>
+static int pool_replay(PoolJob& j, const GraphKey& key, Enqueue&& enqueue) {
   ttx_session* s = j.s;
-  StepCtx k = j.g.k;
-  k.variant = variant_for_rows(s, (long long)n_live * step_rps(k.N, k.D), true);     // free choice: identical bits
-  const int kcap = k.max_len;
   const bool use_graph = s->use_graphs && !s->profile;
-  GraphKey key{k.B, k.Ls, k.N, k.D, k.max_len, 3, kcap, k.variant};
   s->graphs_current();
   auto it = s->graphs.find(key);
   if (!use_graph || (it == s->graphs.end() && !s->warmed.count(key))) {
-    s->warmed.insert(key);          // first use of a shape runs eagerly once (function attributes are set outside capture)
-    TTX_TRY(run_step(s, j.st, k, kcap));
-    TTX_TRY(launch_accept_and_commit(s, j.st, j.g, false));
-    ++j.launched;
-    return TTX_OK;
+    s->warmed.insert(key);
+    return enqueue();
   }
   if (it == s->graphs.end()) {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     HIP_TRY(hipStreamBeginCapture(j.st, hipStreamCaptureModeThreadLocal));
-    int rc = run_step(s, j.st, k, kcap);
-    if (rc == TTX_OK) rc = launch_accept_and_commit(s, j.st, j.g, false);
+    int rc = enqueue();
     hipError_t e = hipStreamEndCapture(j.st, &graph);
     if (rc != TTX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
     if (e != hipSuccess) return fail(TTX_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -1339,6 +1382,75 @@ static int pool_launch_step(PoolJob& j, int n_live) {
     it = s->graphs.emplace(key, exec).first;
   }
   HIP_TRY(hipGraphLaunch(it->second, j.st));
+  return TTX_OK;
+}
+
+// One verify step of the pool.  With enough live rows it is split: this call enqueues the probe (the front rows of all live
+// slots, then k_probe_split) and pool_launch_drafts follows once the probe has published its match count.
+static int pool_launch_step(PoolJob& j, int n_live) {
+  ttx_session* s = j.s;
+  StepCtx k = j.g.k;
+  const int kcap = k.max_len;
+  const long long rows = (long long)n_live * step_rps(k.N, k.D);
+  if (!j.two_phase || rows < j.min_rows) {
+    k.variant = variant_for_rows(s, rows, true);     // free choice: identical bits
+    GraphKey key{k.B, k.Ls, k.N, k.D, k.max_len, 3, kcap, k.variant, 0};
+    TTX_TRY(pool_replay(j, key, [&]() -> int {
+      TTX_TRY(run_step(s, j.st, k, kcap));
+      return launch_accept_and_commit(s, j.st, j.g, false);
+    }));
+    ++j.launched;
+    return TTX_OK;
+  }
+  DecState* st2 = s->state2.as<DecState>();          // [0] probe, [1] draft pass, then the executed-row count
+  StepCtx kp = k;
+  kp.N = 1; kp.D = 0; kp.sel_N = k.N; kp.sel_D = k.D;
+  kp.st_ov = st2; kp.qkv_ov = s->qkv_probe.as<float>(); kp.pred_ov = s->pred_probe.as<int>();
+  kp.variant = variant_for_rows(s, n_live, true);
+  GraphKey key{k.B, k.Ls, k.N, k.D, k.max_len, 3, kcap, kp.variant, 1};
+  TTX_TRY(pool_replay(j, key, [&]() -> int {
+    hipLaunchKernelGGL(k_probe_begin, dim3(1), dim3(64), 0, j.st, s->state.as<DecState>(), st2);
+    HIP_TRY(hipGetLastError());
+    TTX_TRY(run_step(s, j.st, kp, kcap));
+    ProbeSplitArgs ps{};
+    ps.st = s->state.as<DecState>(); ps.act_idx = s->act_idx.as<int>(); ps.pred_probe = s->pred_probe.as<int>();
+    ps.drafts = s->drafts.as<int>(); ps.N = k.N; ps.D = k.D; ps.act2 = s->act2.as<int>(); ps.pos2 = s->pos2.as<int>();
+    ps.st2 = st2 + 1; ps.exec_rows = reinterpret_cast<int*>(st2 + 2);
+    ps.host = j.dev_probe;
+    hipLaunchKernelGGL(k_probe_split, dim3(1), dim3(k.B > 256 ? ACCEPT_THREADS : 256), 0, j.st, ps);
+    HIP_TRY(hipGetLastError());
+    return TTX_OK;
+  }));
+  ++j.probes;
+  j.probe_pending = true;
+  j.split_steps += 1; j.slot_steps += n_live;
+  return TTX_OK;
+}
+
+// Second half of a split step, once the probe has published: the full step on the matching slots (skipped when there are none),
+// then merge, accept and commit.
+static int pool_launch_drafts(PoolJob& j) {
+  ttx_session* s = j.s;
+  StepCtx k = j.g.k;
+  const int kcap = k.max_len;
+  const int matches = ((volatile ProbeInfo*)s->probe_info)->matches;
+  if (matches < 0 || matches > k.B) return fail(TTX_ERR_HIP, "slot pool: the probe published a match count outside the pool");
+  const int RPS = step_rps(k.N, k.D);
+  DecState* st2 = s->state2.as<DecState>();
+  k.st_ov = st2 + 1; k.act_ov = s->act2.as<int>(); k.pred_ov = s->pred_draft.as<int>();
+  k.variant = matches ? variant_for_rows(s, (long long)matches * RPS, true) : 0;
+  j.matched_slot_steps += matches; j.skipped_draft_passes += matches ? 0 : 1;
+  GraphKey key{k.B, k.Ls, k.N, k.D, k.max_len, 3, kcap, k.variant, matches ? 2 : 3};
+  TTX_TRY(pool_replay(j, key, [&]() -> int {
+    if (matches) TTX_TRY(run_step(s, j.st, k, kcap));
+    MergePredArgs mp{};
+    mp.st = s->state.as<DecState>(); mp.pos2 = s->pos2.as<int>(); mp.pred_probe = s->pred_probe.as<int>();
+    mp.pred2 = s->pred_draft.as<int>(); mp.pred = s->pred.as<int>(); mp.RPS = RPS;
+    hipLaunchKernelGGL(k_merge_pred, dim3(cdiv(k.B * RPS, 256)), dim3(256), 0, j.st, mp);
+    HIP_TRY(hipGetLastError());
+    return launch_accept_and_commit(s, j.st, j.g2, false);
+  }));
+  j.probe_pending = false;
   ++j.launched;
   return TTX_OK;
 }
@@ -1398,6 +1510,21 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
       ttx_session* s = j.s;
       volatile HostInfo* hi = s->host_info;
       if (j.phase == 1) {
+        if (j.probe_pending) {                                                // the same rules as for steps_done below
+          if (((volatile ProbeInfo*)s->probe_info)->probes_done < j.probes) {
+            if ((++j.idle_spins & 0xffff) == 0 && watchdog_expired(j.last_progress)) {
+              rc_final = session_hung(s);
+              hung = true;
+              break;
+            }
+            continue;
+          }
+          j.idle_spins = 0;
+          j.last_progress = std::chrono::steady_clock::now();
+          rc_final = pool_launch_drafts(j);
+          progressed = true;
+          continue;
+        }
         if (j.launched > 0 && hi->steps_done < j.launched) {                  // the step in flight has not published yet
           // never spin forever (no HIP call in the polling loop: only the clock)
           if ((++j.idle_spins & 0xffff) == 0 && watchdog_expired(j.last_progress)) {
@@ -1461,6 +1588,9 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, s->ev_a, s->ev_c) == hipSuccess) stats->decode_ms += ms;
           }
+          if (getenv("TTX_TWO_PHASE_STATS"))
+            fprintf(stderr, "[ttx two-phase] pool %d: %d steps, %lld split (%lld without a draft pass), %lld slot-steps probed, %lld matched\n",
+                    i, j.launched, j.split_steps, j.skipped_draft_passes, j.slot_steps, j.matched_slot_steps);
           if (hs.error == 3 && rc_final == TTX_OK)
             rc_final = fail(TTX_ERR_ROW_REPLAY, "a row emitted PAD inside its sequence: decode the batches as given");
           else if (hs.error && rc_final == TTX_OK)
@@ -2777,6 +2907,22 @@ extern "C" int ttx_debug_attn_hd(ttx_session* s, const float* d_q, int ldq, cons
   return attn_debug(s, a, H, head_dim, mode, groups, n_active, max_keys, kernel, kernel_id, reinterpret_cast<hipStream_t>(stream));
 }
 
+extern "C" int ttx_debug_attn_as(ttx_session* s, const float* d_q, int ldq, const float* d_k, const float* d_v, int ldkv, float* d_out,
+                                 int H, int head_dim, float scale, int L, int Lk, const int32_t* d_tok, int pad, const uint8_t* d_key_pad,
+                                 const int32_t* d_mem_row, const int32_t* d_act_idx, const int32_t* d_front, const int32_t* d_src_of,
+                                 const int32_t* d_src_len, const float* d_kcache, const float* d_vcache, int64_t cache_seq_stride,
+                                 const int32_t* d_cache_slot, int gen_ld, int N, int D, int mode, int groups, int n_active, int max_keys,
+                                 int kernel, int32_t* kernel_id, int sel_N, int sel_D, void* stream) {
+  if (!s) return fail(TTX_ERR_INVALID, "null session");
+  if (sel_N < 1 || sel_D < 0) return fail(TTX_ERR_INVALID, "ttx_debug_attn_as: the layout to choose as needs N >= 1 and D >= 0");
+  s->attn_sel_N = sel_N; s->attn_sel_D = sel_D;
+  const int rc = ttx_debug_attn_hd(s, d_q, ldq, d_k, d_v, ldkv, d_out, H, head_dim, scale, L, Lk, d_tok, pad, d_key_pad, d_mem_row, d_act_idx,
+                                   d_front, d_src_of, d_src_len, d_kcache, d_vcache, cache_seq_stride, d_cache_slot, gen_ld, N, D, mode,
+                                   groups, n_active, max_keys, kernel, kernel_id, stream);
+  s->attn_sel_N = 0; s->attn_sel_D = 0;
+  return rc;
+}
+
 extern "C" int ttx_debug_attn(ttx_session* s, const float* d_q, int ldq, const float* d_k, const float* d_v, int ldkv, float* d_out,
                               int H, float scale, int L, int Lk, const int32_t* d_tok, int pad, const uint8_t* d_key_pad,
                               const int32_t* d_mem_row, const int32_t* d_act_idx, const int32_t* d_front, const int32_t* d_src_of,
@@ -2976,30 +3122,39 @@ extern "C" int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, 
   return TTX_OK;
 }
 
-extern "C" int ttx_debug_kvcopy(ttx_session* s, const int32_t* d_rec, int n_copy, const float* d_qkv, int64_t qkv_layer_stride,
-                                float* d_kcache, float* d_vcache, int64_t cache_layer_stride, int64_t cache_seq_stride, int N, int D,
-                                int d, int B, int Ld, void* stream) {
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (!s || !d_rec || !d_qkv || !d_kcache || !d_vcache) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_kvcopy");
-  if (!dbg_model_d(d)) return fail(TTX_ERR_INVALID, "ttx_debug_kvcopy: d must be 64, 128, 256, 512 or 1024");
-  if (B < 1 || Ld < 1 || N < 1 || D < 0) return fail(TTX_ERR_INVALID, "ttx_debug_kvcopy: B, Ld and N must be positive, D >= 0");
-  if (n_copy < 0 || n_copy > B) return fail(TTX_ERR_INVALID, "ttx_debug_kvcopy: n_copy must lie in [0, B]");
+static int kvcopy_debug(const char* who, ttx_session* s, const int32_t* d_rec, int n_copy, const float* d_qkv, int64_t qkv_layer_stride,
+                        float* d_kcache, float* d_vcache, int64_t cache_layer_stride, int64_t cache_seq_stride, int N, int D, int d, int B,
+                        int Ld, const int32_t* d_pos2, const float* d_qkv_probe, int64_t probe_layer_stride, hipStream_t st) {
+  const std::string w(who);
+  if (!s || !d_rec || !d_qkv || !d_kcache || !d_vcache) return fail(TTX_ERR_INVALID, "null argument to " + w);
+  if (!dbg_model_d(d)) return fail(TTX_ERR_INVALID, w + ": d must be 64, 128, 256, 512 or 1024");
+  if (B < 1 || Ld < 1 || N < 1 || D < 0) return fail(TTX_ERR_INVALID, w + ": B, Ld and N must be positive, D >= 0");
+  if (n_copy < 0 || n_copy > B) return fail(TTX_ERR_INVALID, w + ": n_copy must lie in [0, B]");
   if (!dbg_aligned16(d_qkv) || !dbg_aligned16(d_kcache) || !dbg_aligned16(d_vcache))
-    return fail(TTX_ERR_INVALID, "ttx_debug_kvcopy: float operands must be 16-byte aligned");
+    return fail(TTX_ERR_INVALID, w + ": float operands must be 16-byte aligned");
   const int RPS = step_rps(N, D);
   if ((qkv_layer_stride & 3) || qkv_layer_stride < (int64_t)B * RPS * 3 * d)
-    return fail(TTX_ERR_INVALID, "ttx_debug_kvcopy: qkv_layer_stride must be a multiple of 4 covering B * (1 + N*D) rows of 3d");
+    return fail(TTX_ERR_INVALID, w + ": qkv_layer_stride must be a multiple of 4 covering B * (1 + N*D) rows of 3d");
   if ((cache_seq_stride & 3) || cache_seq_stride < d || (cache_layer_stride & 3) || cache_layer_stride < (int64_t)B * cache_seq_stride)
-    return fail(TTX_ERR_INVALID, "ttx_debug_kvcopy: the cache strides must be multiples of 4, a row's covering d and a layer's B rows");
+    return fail(TTX_ERR_INVALID, w + ": the cache strides must be multiples of 4, a row's covering d and a layer's B rows");
+  if ((d_pos2 != nullptr) != (d_qkv_probe != nullptr)) return fail(TTX_ERR_INVALID, w + ": pos2 and qkv_probe come together");
+  if (d_pos2 && (!dbg_aligned16(d_qkv_probe) || (probe_layer_stride & 3) || probe_layer_stride < (int64_t)B * 3 * d))
+    return fail(TTX_ERR_INVALID, w + ": qkv_probe must be 16-byte aligned and its layer stride a multiple of 4 covering B rows of 3d");
   HIP_TRY(hipSetDevice(s->m->device));
   if (n_copy > 0) {
     std::vector<CopyRec> rec((size_t)n_copy);
+    std::vector<int> pos((size_t)n_copy, 0);
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipMemcpy(rec.data(), d_rec, (size_t)n_copy * sizeof(CopyRec), hipMemcpyDeviceToHost));
-    for (const CopyRec& r : rec)
+    if (d_pos2) HIP_TRY(hipMemcpy(pos.data(), d_pos2, (size_t)n_copy * sizeof(int), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n_copy; ++i) {
+      const CopyRec& r = rec[i];
       if (r.b < 0 || r.b >= B || r.best < 0 || r.best >= N || r.nacc < 0 || r.nacc > D || r.front_old < 0 ||
           ((int64_t)r.front_old + r.nacc + 1) * d > cache_seq_stride)
-        return fail(TTX_ERR_INVALID, "ttx_debug_kvcopy: a record is outside the operands (b, best, nacc or front_old + nacc + 1 positions)");
+        return fail(TTX_ERR_INVALID, w + ": a record is outside the operands (b, best, nacc or front_old + nacc + 1 positions)");
+      if (d_pos2 && (pos[i] < -1 || pos[i] >= B || (pos[i] < 0 && r.nacc != 0)))
+        return fail(TTX_ERR_INVALID, w + ": pos2 must lie in [-1, B), and a slot without a draft pass (-1) accepts nothing");
+    }
   }
   DecState* dst = nullptr;
   HIP_TRY(hipMalloc((void**)&dst, sizeof(DecState)));
@@ -3012,9 +3167,121 @@ extern "C" int ttx_debug_kvcopy(ttx_session* s, const int32_t* d_rec, int n_copy
     kc.st = dst; kc.rec = reinterpret_cast<const CopyRec*>(d_rec); kc.qkv = d_qkv; kc.qkv_layer_stride = (long long)qkv_layer_stride;
     kc.kcache = d_kcache; kc.vcache = d_vcache; kc.cache_layer_stride = (long long)cache_layer_stride;
     kc.cache_seq_stride = (long long)cache_seq_stride; kc.N = N; kc.D = D; kc.d = d;
+    kc.pos2 = d_pos2; kc.qkv_probe = d_qkv_probe; kc.probe_layer_stride = (long long)probe_layer_stride;
     hipLaunchKernelGGL(k_kvcopy, dim3(B, Ld), dim3(256), 0, st, kc);
     err = hipGetLastError();
   }
+  const hipError_t esync = hipStreamSynchronize(st);
+  (void)hipFree(dst);
+  HIP_TRY(err);
+  HIP_TRY(esync);
+  return TTX_OK;
+}
+
+extern "C" int ttx_debug_kvcopy(ttx_session* s, const int32_t* d_rec, int n_copy, const float* d_qkv, int64_t qkv_layer_stride,
+                                float* d_kcache, float* d_vcache, int64_t cache_layer_stride, int64_t cache_seq_stride, int N, int D,
+                                int d, int B, int Ld, void* stream) {
+  return kvcopy_debug("ttx_debug_kvcopy", s, d_rec, n_copy, d_qkv, qkv_layer_stride, d_kcache, d_vcache, cache_layer_stride,
+                      cache_seq_stride, N, D, d, B, Ld, nullptr, nullptr, 0, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int ttx_debug_kvcopy_split(ttx_session* s, const int32_t* d_rec, int n_copy, const float* d_qkv, int64_t qkv_layer_stride,
+                                      float* d_kcache, float* d_vcache, int64_t cache_layer_stride, int64_t cache_seq_stride, int N,
+                                      int D, int d, int B, int Ld, const int32_t* d_pos2, const float* d_qkv_probe,
+                                      int64_t probe_layer_stride, void* stream) {
+  return kvcopy_debug("ttx_debug_kvcopy_split", s, d_rec, n_copy, d_qkv, qkv_layer_stride, d_kcache, d_vcache, cache_layer_stride,
+                      cache_seq_stride, N, D, d, B, Ld, d_pos2, d_qkv_probe, probe_layer_stride, reinterpret_cast<hipStream_t>(stream));
+}
+
+// k_probe_split / k_merge_pred of the two-phase verify step (tests/test_gpu_two_phase.py).  The live count reaches the kernels as
+// in production: in a DecState on the device.
+static int dbg_state_with(hipStream_t st, int n_active, int steps, DecState** out) {
+  DecState* dst = nullptr;
+  HIP_TRY(hipMalloc((void**)&dst, 2 * sizeof(DecState)));
+  DecState h[2] = {};
+  h[0].n_active = n_active;
+  h[1].steps = steps;
+  const hipError_t e = hipMemcpy(dst, h, sizeof(h), hipMemcpyHostToDevice);
+  (void)st;
+  if (e != hipSuccess) { (void)hipFree(dst); HIP_TRY(e); }
+  *out = dst;
+  return TTX_OK;
+}
+
+extern "C" int ttx_debug_probe_split(ttx_session* s, const int32_t* d_act_idx, const int32_t* d_pred_probe, const int32_t* d_drafts,
+                                     int B, int N, int D, int n_active, int32_t* d_act2, int32_t* d_pos2, int32_t* result,
+                                     void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !d_act_idx || !d_pred_probe || !d_drafts || !d_act2 || !d_pos2 || !result)
+    return fail(TTX_ERR_INVALID, "null argument to ttx_debug_probe_split");
+  if (B < 1 || N < 1 || D < 1) return fail(TTX_ERR_INVALID, "ttx_debug_probe_split: B, N and D must be positive");
+  if (n_active < 0 || n_active > B) return fail(TTX_ERR_INVALID, "ttx_debug_probe_split: n_active must lie in [0, B]");
+  HIP_TRY(hipSetDevice(s->m->device));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (n_active > 0) {
+    std::vector<int> act((size_t)n_active);
+    HIP_TRY(hipMemcpy(act.data(), d_act_idx, (size_t)n_active * 4, hipMemcpyDeviceToHost));
+    std::vector<char> seen((size_t)B, 0);
+    for (int b : act) {
+      if (b < 0 || b >= B || seen[b]) return fail(TTX_ERR_INVALID, "ttx_debug_probe_split: act_idx must be distinct rows of [0, B)");
+      seen[b] = 1;
+    }
+  }
+  ProbeInfo* hinfo = nullptr;
+  if (hipHostMalloc((void**)&hinfo, sizeof(ProbeInfo), hipHostMallocMapped) != hipSuccess) return fail(TTX_ERR_NOMEM, "hipHostMalloc failed");
+  hinfo->matches = -1; hinfo->probes_done = -1;
+  DecState* dst = nullptr;
+  int rc = dbg_state_with(st, n_active, result[4], &dst);           // result[4] on entry: probes counted so far
+  int* d_exec = nullptr;
+  hipError_t err = hipSuccess;
+  if (rc == TTX_OK) err = hipMalloc((void**)&d_exec, 4);
+  if (rc == TTX_OK && err == hipSuccess) {
+    ProbeSplitArgs ps{};
+    ps.st = dst; ps.act_idx = d_act_idx; ps.pred_probe = d_pred_probe; ps.drafts = d_drafts; ps.N = N; ps.D = D;
+    ps.act2 = d_act2; ps.pos2 = d_pos2; ps.st2 = dst + 1; ps.exec_rows = d_exec;
+    err = hipHostGetDevicePointer((void**)&ps.host, (void*)hinfo, 0);
+    if (err == hipSuccess) {
+      hipLaunchKernelGGL(k_probe_split, dim3(1), dim3(B > 256 ? ACCEPT_THREADS : 256), 0, st, ps);
+      err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    DecState h2{};
+    int exec = 0;
+    if (err == hipSuccess) err = hipMemcpy(&h2, dst + 1, sizeof(DecState), hipMemcpyDeviceToHost);
+    if (err == hipSuccess) err = hipMemcpy(&exec, d_exec, 4, hipMemcpyDeviceToHost);
+    if (err == hipSuccess) {
+      result[0] = h2.n_active; result[1] = h2.r_rows; result[2] = h2.m_rows; result[3] = exec; result[4] = h2.steps;
+      result[5] = hinfo->matches; result[6] = hinfo->probes_done;
+    }
+  }
+  if (d_exec) (void)hipFree(d_exec);
+  if (dst) (void)hipFree(dst);
+  (void)hipHostFree(hinfo);
+  TTX_TRY(rc);
+  HIP_TRY(err);
+  return TTX_OK;
+}
+
+extern "C" int ttx_debug_merge_pred(ttx_session* s, const int32_t* d_pos2, const int32_t* d_pred_probe, const int32_t* d_pred2,
+                                    int32_t* d_pred, int B, int N, int D, int n_active, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !d_pos2 || !d_pred_probe || !d_pred2 || !d_pred) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_merge_pred");
+  if (B < 1 || N < 1 || D < 1) return fail(TTX_ERR_INVALID, "ttx_debug_merge_pred: B, N and D must be positive");
+  if (n_active < 0 || n_active > B) return fail(TTX_ERR_INVALID, "ttx_debug_merge_pred: n_active must lie in [0, B]");
+  HIP_TRY(hipSetDevice(s->m->device));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (n_active > 0) {
+    std::vector<int> pos((size_t)n_active);
+    HIP_TRY(hipMemcpy(pos.data(), d_pos2, (size_t)n_active * 4, hipMemcpyDeviceToHost));
+    for (int p : pos)
+      if (p < -1 || p >= B) return fail(TTX_ERR_INVALID, "ttx_debug_merge_pred: pos2 must lie in [-1, B)");
+  }
+  DecState* dst = nullptr;
+  TTX_TRY(dbg_state_with(st, n_active, 0, &dst));
+  MergePredArgs mp{};
+  mp.st = dst; mp.pos2 = d_pos2; mp.pred_probe = d_pred_probe; mp.pred2 = d_pred2; mp.pred = d_pred; mp.RPS = step_rps(N, D);
+  hipLaunchKernelGGL(k_merge_pred, dim3(cdiv(B * mp.RPS, 256)), dim3(256), 0, st, mp);
+  hipError_t err = hipGetLastError();
   const hipError_t esync = hipStreamSynchronize(st);
   (void)hipFree(dst);
   HIP_TRY(err);

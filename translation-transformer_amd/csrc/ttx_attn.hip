@@ -992,7 +992,16 @@ static int launch_attn_mode(ttx_session* s, hipStream_t st, const AttnArgs& a, i
   const size_t lds2 = attn2_lds_bytes(keys2, a2_qcap(q_per_group), DH);
   if (force == AK_ATTN2 && !(lds2 <= kAttn2LdsLimit && attn2_fits(keys2, DH)))
     return fail(TTX_ERR_INVALID, "k_attn2: more keys than its register and LDS images hold");
-  if (lds2 <= kAttn2LdsLimit && attn2_fits(keys2, DH) && want2) {
+  // k_attn2 or k_attn: the two do not give the same bits, and the probe of a two-phase verify step recomputes row 0 of a launch in
+  // the layout (attn_sel_N, attn_sel_D).  It takes the kernel THAT launch takes (whose images hold the probe's fewer keys and rows).
+  bool fits2 = lds2 <= kAttn2LdsLimit && attn2_fits(keys2, DH);
+  if (step && s->attn_sel_N > 0) {
+    const int cN = s->attn_sel_N, cD = s->attn_sel_D;
+    const int c_draft = (cD > 0) ? (std::min(cN, (A2_QT + cD - 2) / cD + 1)) * cD : 0;
+    const int c_keys2 = (MODE == ATT_STEP_SELF) ? max_keys + 1 + c_draft : max_keys;
+    fits2 = fits2 && attn2_lds_bytes(c_keys2, a2_qcap(step_rps(cN, cD)), DH) <= kAttn2LdsLimit && attn2_fits(c_keys2, DH);
+  }
+  if (fits2 && want2) {
     s->last_attn_kernel = AK_ATTN2;
     const int tiles = cdiv(q_per_group, A2_QT);
     bool& attr_set = s->attr_attn2[DH == ATT_DH ? 0 : 1][MODE];

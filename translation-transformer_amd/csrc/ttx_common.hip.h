@@ -30,6 +30,10 @@ struct CopyRec { int b, best, nacc, front_old, flags; };   // flags: 1 finished 
 // synchronising the stream.
 struct HostInfo { int stop; int steps_done; int width; int n_active; };
 
+// Two-phase verify step of the slot pool (DESIGN.md "Two-phase verify step"): k_probe_split publishes how many live slots matched
+// a draft's first token and how many probes have run.  A word pair of its own: HostInfo stays what the accept kernels write.
+struct ProbeInfo { int matches; int probes_done; };
+
 // ------------------------------------------------------------------------------------------------
 // GEMM:  Y[m, n] = sum_k X[m, k] * W[n, k]   (torch.nn.Linear layout: both operands K-contiguous)
 struct GemmArgs {

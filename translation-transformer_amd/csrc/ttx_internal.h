@@ -70,8 +70,10 @@ enum AttnKernelId { AK_ATTN = 1, AK_ATTN2 = 2, AK_ATTN3 = 3, AK_ATTN3S = 4 };
 
 struct GraphKey {
   int B, Ls, N, D, max_len, mode, kcap, variant;   // mode: 0 speculative, 1 plain greedy, 2 per-row rule, 3 slot pool
+  int phase = 0;                                   // slot pool: 0 the whole step in one pass, 1 probe, 2 draft pass + accept, 3 accept alone
   bool operator<(const GraphKey& o) const {
-    return std::tie(B, Ls, N, D, max_len, mode, kcap, variant) < std::tie(o.B, o.Ls, o.N, o.D, o.max_len, o.mode, o.kcap, o.variant);
+    return std::tie(B, Ls, N, D, max_len, mode, kcap, variant, phase) <
+           std::tie(o.B, o.Ls, o.N, o.D, o.max_len, o.mode, o.kcap, o.variant, o.phase);
   }
 };
 
@@ -96,6 +98,10 @@ struct ttx_session {
   Buf drafts, gen, front, act_idx, rec, pred, state, kcache, vcache, src32, outbuf, haspad, traj, fin_step;
   // slot pool (continuous batching)
   Buf rstep, row_of, src_len, new_slot, pool_io, memkv_new, valid_new, drafts_new;
+  // two-phase verify step of the slot pool: the probe's QKV rows [Ld][C][3d] and argmax [C], the draft pass's argmax, the list of
+  // matching sequences, slot -> position in it, and {DecState probe, DecState draft pass, int executed rows}
+  Buf qkv_probe, pred_probe, pred_draft, act2, pos2, state2;
+  ttx::ProbeInfo* probe_info = nullptr; // pinned + device-mapped, written by k_probe_split
   // snapshot of one verify step for the logits parity test (ttx_gen_params.want_logits)
   Buf snap_logits, snap_act, snap_front, snap_gen, snap_state;
   int snap_B = 0, snap_rps = 0, snap_gen_ld = 0, snap_step = 0;
@@ -147,6 +153,7 @@ struct ttx_session {
   int attn_split = -1;             // -1 by launch size, 0 never, 1 always (key tiles of a head over 4 waves)
   bool attn_fallback = false;      // TTX_ATTN_FALLBACK=1 (test hook): every attention launch on the streaming kernel k_attn
   int attn_force = 0;              // ttx_debug_attn (test hook): an AttnKernelId that replaces launch_attn's choice; 0 (always, outside that call): unset
+  int attn_sel_N = 0, attn_sel_D = 0;   // > 0 around the launches of a probe (run_step, ttx_debug_attn_as): choose between k_attn2 and k_attn as a step launch in the layout (N, D) does
   int last_attn_kernel = 0;        // what the most recent launch_attn dispatched (AttnKernelId): ttx_debug_attn reports it
   // profiling of the GEMM launches (bench.py roofline): a HIP event pair around every GEMM launch
   bool profile = false;
@@ -164,7 +171,7 @@ struct ttx_session {
   ttx_session() { for (Buf* b : {&x, &x1, &x2, &xf, &ao, &q2, &hbuf, &slab, &qkv, &logits, &ckv, &tok_src, &src_valid, &memory,
                                  &memkv, &tok_tgt, &mem_pad_tmp, &ev_logits, &ev_pred, &ev_nll, &sc_src_of, &drafts, &gen, &front, &act_idx, &rec, &pred, &state,
                                  &kcache, &vcache, &src32, &outbuf, &haspad, &traj, &fin_step, &rstep, &row_of, &src_len, &new_slot,
-                                 &pool_io, &memkv_new, &valid_new, &drafts_new, &tk[0], &tk[1], &tv[0], &tv[1],
+                                 &pool_io, &memkv_new, &valid_new, &drafts_new, &qkv_probe, &pred_probe, &pred_draft, &act2, &pos2, &state2, &tk[0], &tk[1], &tv[0], &tv[1],
                                  &t_prev_len, &t_slot_of, &t_src_of,
                                  &snap_logits, &snap_act, &snap_front, &snap_gen, &snap_state, &leaf_score, &leaf_tok, &leaf_cnt,
                                  &beam_summary, &bs_cand_next, &bs_len_next, &bs_fin_next, &bs_logp_next, &bs_len, &bs_fin, &bs_active,

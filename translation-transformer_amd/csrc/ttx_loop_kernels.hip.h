@@ -142,6 +142,8 @@ struct LoopArgs {
   // a row's step count, its position in the caller's arrays and the output pointers live beside the slot state
   int pool; int* rstep; int* row_of; const struct PoolIo* io;
   int B, N, D, Ls, max_len, pad, bos, eos;
+  // two-phase verify step: rows the step really sent through the decoder (live slots + matching slots * RPS); null: Bc * RPS
+  const int* exec_rows;
 };
 struct PoolIo { int64_t* out; short* traj; int* fin_step; int traj_ld; int pad_; };
 
@@ -285,7 +287,7 @@ __global__ __launch_bounds__(ACCEPT_THREADS) void k_accept(LoopArgs a) {
     st->steps += 1;
     st->accepted += s_acc;
     st->produced += s_acc + Bc;
-    st->verified_positions += (long long)Bc * RPS;
+    st->verified_positions += a.exec_rows ? (long long)*a.exec_rows : (long long)Bc * RPS;
     st->kv_prefix_positions += s_prefix;
     st->src_positions += (long long)Bc * a.Ls;
     st->width = width;
@@ -464,6 +466,10 @@ struct KvCopyArgs {
   const float* qkv; long long qkv_layer_stride;      // [Ld][Mmax][3d]
   float* kcache; float* vcache; long long cache_layer_stride; long long cache_seq_stride;
   int N, D, d;
+  // two-phase verify step (both null: every slot's rows lie at its own position in `qkv`): slot -> position of its rows in
+  // `qkv` (the draft pass ran the matching slots only), or -1: the slot ran in the probe alone, whose single row per slot
+  // lies in `qkv_probe` [Ld][C][3d] and is all that is committed
+  const int* pos2; const float* qkv_probe; long long probe_layer_stride;
 };
 
 __global__ __launch_bounds__(256) void k_kvcopy(KvCopyArgs a) {
@@ -472,10 +478,16 @@ __global__ __launch_bounds__(256) void k_kvcopy(KvCopyArgs a) {
   const CopyRec r = a.rec[slot];
   const int RPS = step_rps(a.N, a.D);
   const float* src = a.qkv + (size_t)l * a.qkv_layer_stride + ((size_t)slot * RPS) * 3 * a.d;   // the slot's step rows
+  int nrows = r.nacc + 1;
+  if (a.pos2) {
+    const int p = a.pos2[slot];
+    if (p >= 0) src = a.qkv + (size_t)l * a.qkv_layer_stride + ((size_t)p * RPS) * 3 * a.d;
+    else { src = a.qkv_probe + (size_t)l * a.probe_layer_stride + (size_t)slot * 3 * a.d; nrows = 1; }   // nacc is 0 here
+  }
   float* kc = a.kcache + (size_t)l * a.cache_layer_stride + (size_t)r.b * a.cache_seq_stride + (size_t)r.front_old * a.d;
   float* vc = a.vcache + (size_t)l * a.cache_layer_stride + (size_t)r.b * a.cache_seq_stride + (size_t)r.front_old * a.d;
   const int per_row = a.d / 4;                    // float4 per K (or V) row
-  const int total = (r.nacc + 1) * per_row;
+  const int total = nrows * per_row;
   for (int e = threadIdx.x; e < total; e += blockDim.x) {
     const int j = e / per_row, c = (e % per_row) * 4;
     const int srow = (j == 0) ? 0 : 1 + r.best * a.D + (j - 1);   // position front_old + j of the chosen draft
@@ -483,6 +495,95 @@ __global__ __launch_bounds__(256) void k_kvcopy(KvCopyArgs a) {
     *reinterpret_cast<float4*>(kc + (size_t)j * a.d + c) = *reinterpret_cast<const float4*>(p + a.d + c);
     *reinterpret_cast<float4*>(vc + (size_t)j * a.d + c) = *reinterpret_cast<const float4*>(p + 2 * a.d + c);
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Two-phase verify step of the slot pool.  A slot's N*D draft rows can change the step's result only if the prediction made by
+// its front row equals the first token of one of its drafts; otherwise k_accept takes n_acc = 0 and commits row 0 alone.  So the
+// step first runs the front rows of all live slots (the probe: layout N = 1, D = 0), k_probe_split lists the slots that match,
+// the full step runs on those alone (the draft pass), and k_merge_pred lays the predictions out as k_accept reads them.
+//
+// The probe runs on a DecState of its own: n_active live slots, one row each.
+__global__ void k_probe_begin(const DecState* st, DecState* stp) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    const int n = st->n_active;
+    stp->n_active = n; stp->r_rows = n; stp->m_rows = n;
+  }
+}
+
+struct ProbeSplitArgs {
+  const DecState* st;              // the pool's state: n_active live slots
+  const int* act_idx;              // [n_active] live sequences
+  const int* pred_probe;           // [n_active] the probe's argmax per slot
+  const int* drafts; int N, D;     // [B, N, D]
+  int* act2;                       // out: the matching sequences in the order of act_idx (entries past the count stay untouched)
+  int* pos2;                       // out [n_active]: slot -> position in act2, -1 without a match
+  DecState* st2;                   // out: n_active = matches, r_rows, m_rows = matches * RPS; steps counts the probes
+  int* exec_rows;                  // out: n_active + matches * RPS
+  ProbeInfo* host;                 // out (may be null): matches, then the probe counter
+};
+
+// One block; ordered compaction as in k_accept, in rounds of blockDim.x slots.
+__global__ __launch_bounds__(ACCEPT_THREADS) void k_probe_split(ProbeSplitArgs a) {
+  __shared__ int s_scan[ACCEPT_THREADS / 64];
+  const int Bc = a.st->n_active;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int n_before = 0;
+  for (int base = 0; base < Bc; base += blockDim.x) {
+    const int slot = base + threadIdx.x;
+    int b = 0, hit = 0;
+    if (slot < Bc) {
+      b = a.act_idx[slot];
+      const int t = a.pred_probe[slot];
+      for (int n = 0; n < a.N; ++n) hit |= (a.drafts[((size_t)b * a.N + n) * a.D] == t) ? 1 : 0;
+    }
+    const unsigned long long mask = __ballot(hit);
+    if (lane == 0) s_scan[wave] = __popcll(mask);
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) {
+      const int c = s_scan[w];
+      before += (w < wave) ? c : 0;
+      total += c;
+    }
+    if (slot < Bc) {
+      const int p = n_before + before + __popcll(mask & ((1ull << lane) - 1ull));
+      if (hit) a.act2[p] = b;
+      a.pos2[slot] = hit ? p : -1;
+    }
+    n_before += total;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const int RPS = step_rps(a.N, a.D);
+    a.st2->n_active = n_before; a.st2->r_rows = n_before * a.N; a.st2->m_rows = n_before * RPS;
+    a.st2->steps += 1;
+    *a.exec_rows = Bc + n_before * RPS;
+    if (a.host) {
+      a.host->matches = n_before;
+      __threadfence_system();
+      a.host->probes_done = a.st2->steps;            // last: the host reads `matches` once it sees this one move
+    }
+  }
+}
+
+struct MergePredArgs {
+  const DecState* st;              // n_active live slots
+  const int* pos2;                 // [n_active] slot -> position in the draft pass, -1: probe only
+  const int* pred_probe;           // [n_active]
+  const int* pred2;                // [matches * RPS] the draft pass's argmax
+  int* pred;                       // out [n_active * RPS]: what k_accept reads
+  int RPS;
+};
+
+// A slot without a match gets the probe's prediction in row 0 and -1 in its draft rows: k_accept's first comparison of every
+// draft is against row 0, which matches none, so n_acc = 0 and best = 0 whatever the filler is.
+__global__ __launch_bounds__(256) void k_merge_pred(MergePredArgs a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.st->n_active * a.RPS) return;
+  const int slot = i / a.RPS, r = i - slot * a.RPS;
+  const int p = a.pos2[slot];
+  a.pred[i] = p >= 0 ? a.pred2[(size_t)p * a.RPS + r] : (r == 0 ? a.pred_probe[slot] : -1);
 }
 
 // ------------------------------------------------------------------------------------------------

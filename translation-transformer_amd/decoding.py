@@ -184,8 +184,9 @@ class TranslationInferenceGreedySpeculative(_ScoresHypotheses):
         R = sum(sizes)
         # device group size: the given batch size is not binding any more; larger groups run the GEMMs at better MFMA
         # occupancy, but at least `in_flight` groups should exist so that tails overlap
-        if pool:      # slot pool: 512 slots x 5 pools for long lists (measured); short lists are split evenly
-            gsz = int(group_size or os.environ.get("TTX_POOL_CAPACITY") or 512)
+        if pool:      # slot pool: 1 024 slots x 3 pools for lists that fill them, else 512 slots x 5 pools (measured, DESIGN.md
+            # §6); lists that fit the pools at once are split evenly
+            gsz = int(group_size or os.environ.get("TTX_POOL_CAPACITY") or (1024 if R >= 3 * 1024 else 512))
         else:
             gsz = int(group_size or min(256, max(max(sizes), -(-R // max(1, in_flight)))))
         self.last_group_size = gsz
@@ -210,7 +211,12 @@ class TranslationInferenceGreedySpeculative(_ScoresHypotheses):
         if pool:
             # continuous batching: every session keeps `gsz` slots filled from the sorted work list
             # (ttx_greedy_speculative_generate_pool)
-            n_sess = max(1, min(in_flight, max(1, 2560 // gsz), -(-R // 32)))     # five pools (sweeps: profiles/r03_sweep_c2_pools.txt)
+            # the default of a list that fills them is three pools of 1 024 slots since the verify step runs in two phases
+            # (profiles/r08_sweep_c2_pools.txt); every other case keeps the rule it had (five pools of 512:
+            # profiles/r03_sweep_c2_pools.txt)
+            by_default = not (group_size or os.environ.get("TTX_POOL_CAPACITY"))
+            n_pools = 3 if (by_default and gsz == 1024) else max(1, 2560 // gsz)
+            n_sess = max(1, min(in_flight, n_pools, -(-R // 32)))
             if os.environ.get("TTX_POOL_SESSIONS"):                               # experiments
                 n_sess = max(1, int(os.environ["TTX_POOL_SESSIONS"]))
             sessions = m.session_pool(n_sess)

@@ -222,14 +222,24 @@ class NativeTransformer:
                    front: torch.Tensor | None = None, src_of: torch.Tensor | None = None, src_len: torch.Tensor | None = None,
                    kcache: torch.Tensor | None = None, vcache: torch.Tensor | None = None, cache_seq_stride: int = 0,
                    cache_slot: torch.Tensor | None = None, gen_ld: int = 0, n: int = 1, d: int = 0, n_active: int = 0,
-                   kernel: int = 0, head_dim: int = 32) -> int:
+                   kernel: int = 0, head_dim: int = 32, choose_as: tuple | None = None) -> int:
         """One attention launch on the caller's device tensors (ttx_debug_attn_hd): ``q`` / ``k`` / ``v`` are 2-D fp32 views whose
         row strides are the leading dimensions (``k`` and ``v`` share theirs), ``out`` has rows of ``head_dim`` * ``heads`` floats
         (``head_dim`` 32 or 64); index and token tensors are int32, ``key_pad`` uint8.  ``kernel``: 0 the production choice,
         1 k_attn, 2 k_attn2, 3 k_attn3, 4 k_attn3s.  Returns the kernel that ran; arguments a kernel cannot take raise TtxError
-        (TTX_ERR_INVALID)."""
+        (TTX_ERR_INVALID).  ``choose_as`` = (n, d): a step launch that chooses between k_attn2 and k_attn as a launch in that
+        layout does (ttx_debug_attn_as: the probe of the two-phase verify step)."""
         kid = C.c_int32(0)
         assert k.stride(0) == v.stride(0)
+        if choose_as is not None:
+            N.check(self._lib.ttx_debug_attn_as(self._session, q.data_ptr(), q.stride(0), k.data_ptr(), v.data_ptr(), k.stride(0),
+                                                out.data_ptr(), int(heads), int(head_dim), float(scale), int(L), int(Lk), self._ptr(tok),
+                                                int(pad), self._ptr(key_pad), self._ptr(mem_row), self._ptr(act_idx), self._ptr(front),
+                                                self._ptr(src_of), self._ptr(src_len), self._ptr(kcache), self._ptr(vcache),
+                                                int(cache_seq_stride), self._ptr(cache_slot), int(gen_ld), int(n), int(d), int(mode),
+                                                int(groups), int(n_active), int(max_keys), int(kernel), C.byref(kid),
+                                                int(choose_as[0]), int(choose_as[1]), self._stream()))
+            return int(kid.value)
         N.check(self._lib.ttx_debug_attn_hd(self._session, q.data_ptr(), q.stride(0), k.data_ptr(), v.data_ptr(), k.stride(0),
                                             out.data_ptr(), int(heads), int(head_dim), float(scale), int(L), int(Lk), self._ptr(tok),
                                             int(pad), self._ptr(key_pad), self._ptr(mem_row), self._ptr(act_idx), self._ptr(front),
@@ -281,6 +291,35 @@ class NativeTransformer:
         N.check(self._lib.ttx_debug_kvcopy(self._session, rec.data_ptr(), int(n_copy), qkv.data_ptr(), int(qkv.stride(0)),
                                            kcache.data_ptr(), vcache.data_ptr(), int(kcache.stride(0)), int(kcache.stride(1)),
                                            int(n), int(d), int(width), int(B), int(qkv.shape[0]), self._stream()))
+
+    def debug_kvcopy_split(self, rec: torch.Tensor, n_copy: int, qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
+                           n: int, d: int, width: int, B: int, pos2: torch.Tensor | None = None,
+                           qkv_probe: torch.Tensor | None = None) -> None:
+        """debug_kvcopy with the two-phase indirection (ttx_debug_kvcopy_split): ``pos2`` int32 [n_copy] (slot -> position of its
+        rows in ``qkv``, -1: the slot's single row of ``qkv_probe`` fp32 [Ld, B, 3 * width]); both None: debug_kvcopy."""
+        assert kcache.stride() == vcache.stride()
+        N.check(self._lib.ttx_debug_kvcopy_split(self._session, rec.data_ptr(), int(n_copy), qkv.data_ptr(), int(qkv.stride(0)),
+                                                 kcache.data_ptr(), vcache.data_ptr(), int(kcache.stride(0)), int(kcache.stride(1)),
+                                                 int(n), int(d), int(width), int(B), int(qkv.shape[0]), self._ptr(pos2),
+                                                 self._ptr(qkv_probe), 0 if qkv_probe is None else int(qkv_probe.stride(0)),
+                                                 self._stream()))
+
+    def debug_probe_split(self, act_idx: torch.Tensor, pred_probe: torch.Tensor, drafts: torch.Tensor, n_active: int,
+                          act2: torch.Tensor, pos2: torch.Tensor, probes_before: int = 0) -> list:
+        """One k_probe_split launch (ttx_debug_probe_split): ``act_idx`` / ``pred_probe`` / ``act2`` / ``pos2`` int32 [B],
+        ``drafts`` int32 [B, n, d].  Returns the 7 result words of include/ttx.h."""
+        B, n, d = drafts.shape
+        words = (C.c_int32 * 7)(0, 0, 0, 0, int(probes_before), 0, 0)
+        N.check(self._lib.ttx_debug_probe_split(self._session, act_idx.data_ptr(), pred_probe.data_ptr(), drafts.data_ptr(), int(B),
+                                                int(n), int(d), int(n_active), act2.data_ptr(), pos2.data_ptr(), words,
+                                                self._stream()))
+        return [int(v) for v in words]
+
+    def debug_merge_pred(self, pos2: torch.Tensor, pred_probe: torch.Tensor, pred2: torch.Tensor, pred: torch.Tensor, B: int,
+                         n: int, d: int, n_active: int) -> None:
+        """One k_merge_pred launch (ttx_debug_merge_pred): ``pred`` int32 [B * (1 + n*d)] in k_accept's layout."""
+        N.check(self._lib.ttx_debug_merge_pred(self._session, pos2.data_ptr(), pred_probe.data_ptr(), pred2.data_ptr(),
+                                               pred.data_ptr(), int(B), int(n), int(d), int(n_active), self._stream()))
 
     @staticmethod
     def attn_staged_key_limit(head_dim: int, q_per_group: int) -> int:
