@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 
 using namespace ttx;
 
@@ -338,7 +339,7 @@ extern "C" void ttx_session_destroy(ttx_session* s) {
     fprintf(stderr, "[ttx host timing] hipGraphLaunch: %lld launches, %.1f us each\n", s->host_launches,
             s->host_launch_us / (double)s->host_launches);
   if (s->host_timing && s->host_captures)
-    fprintf(stderr, "[ttx host timing] beam iteration graphs captured: %lld, %.1f us each\n", s->host_captures,
+    fprintf(stderr, "[ttx host timing] graphs captured: %lld, %.1f us each\n", s->host_captures,
             s->host_capture_us / (double)s->host_captures);
   if (s->dead) {        // hipFree / hipDeviceSynchronize would wait for the stuck stream, and a late kernel may still write
     delete s;           // the mapped host words: leak workspaces, pinned memory, graphs and events of a hung session
@@ -390,6 +391,17 @@ static int gemm_ln(ttx_session* s, hipStream_t st, const float* X, int ldx, int 
   return launch_finish(s, st, s->slab.as<float>(), S, stride, bias, resid, g1, b1, g2, b2, row_valid, Y, m_ptr, Mmax);
 }
 
+// The feed-forward half of a layer on the rows in `x`: Y = LN2?(LN(x + b2 + act(x W1^T + b1) W2^T)), LN from the layer's norm at
+// (n_w, n_b), LN2 (g2, b2: the stack's final norm, null except behind its last layer); rows with row_valid[row] == 0 come out zero.
+static int ffn_half(ttx_session* s, hipStream_t st, const LayerW& w, const float* x, size_t n_w, size_t n_b, const float* g2,
+                    const float* b2, const uint8_t* row_valid, float* Y, const int* m_ptr, int Mmax, int v_ffn1, int v_ffn2) {
+  const ttx_model* m = s->m;
+  const int d = m->cfg.embedding_dim, F = m->cfg.feedforward_dim;
+  float* hb = s->hbuf.as<float>();
+  TTX_TRY(launch_gemm(s, st, x, d, m->p(w.l1_w), d, m->p(w.l1_b), hb, F, m_ptr, Mmax, F, d, m->activation, 0, 0, v_ffn1));
+  return gemm_ln(s, st, hb, F, F, m->p(w.l2_w), m->p(w.l2_b), x, m->p(n_w), m->p(n_b), g2, b2, row_valid, Y, m_ptr, Mmax, v_ffn2);
+}
+
 static int ensure_acts(ttx_session* s, hipStream_t st, size_t M, int qkv_layers) {
   const ttx_config& c = s->m->cfg;
   const size_t d = c.embedding_dim, F = c.feedforward_dim;
@@ -412,7 +424,7 @@ static int run_encoder(ttx_session* s, hipStream_t st, const int* tok, const uin
                        float* qkv_buf = nullptr) {
   const ttx_model* m = s->m;
   const ttx_config& c = m->cfg;
-  const int d = c.embedding_dim, F = c.feedforward_dim, H = c.num_heads;
+  const int d = c.embedding_dim, H = c.num_heads;
   const int M = B * Ls;
   const int gv = variant_for_rows(s, M, false);
   TTX_TRY(ensure_acts(s, st, (size_t)M, 1));
@@ -420,7 +432,6 @@ static int run_encoder(ttx_session* s, hipStream_t st, const int* tok, const uin
   float* x1 = s->x1.as<float>();
   float* qkv = qkv_buf ? qkv_buf : s->qkv.as<float>();
   float* ao = s->ao.as<float>();
-  float* hb = s->hbuf.as<float>();
   EmbedArgs e{};
   e.table = m->p(m->src_emb); e.pe = m->p(m->pe); e.X = x; e.d = d; e.V = c.src_vocab_size; e.tok = tok; e.rows = M; e.L = Ls;
   hipLaunchKernelGGL((k_embed<false>), dim3(cdiv(M, 4)), dim3(256), 0, st, e);
@@ -435,10 +446,8 @@ static int run_encoder(ttx_session* s, hipStream_t st, const int* tok, const uin
     TTX_TRY(launch_attn(ATT_ENC, s, st, a, B, H, Ls, Ls));
     TTX_TRY(gemm_ln(s, st, ao, d, d, m->p(w.sa_out_w), m->p(w.sa_out_b), x, m->p(w.n1_w), m->p(w.n1_b), nullptr, nullptr,
                     nullptr, x1, nullptr, M, gv));
-    TTX_TRY(launch_gemm(s, st, x1, d, m->p(w.l1_w), d, m->p(w.l1_b), hb, F, nullptr, M, F, d, m->activation, 0, 0, gv));
-    TTX_TRY(gemm_ln(s, st, hb, F, F, m->p(w.l2_w), m->p(w.l2_b), x1, m->p(w.n2_w), m->p(w.n2_b),
-                    last ? m->p(m->enc_norm_w) : nullptr, last ? m->p(m->enc_norm_b) : nullptr, last ? valid : nullptr,
-                    last ? memory : x, nullptr, M, gv));
+    TTX_TRY(ffn_half(s, st, w, x1, w.n2_w, w.n2_b, last ? m->p(m->enc_norm_w) : nullptr, last ? m->p(m->enc_norm_b) : nullptr,
+                     last ? valid : nullptr, last ? memory : x, nullptr, M, gv, gv));
   }
   return TTX_OK;
 }
@@ -461,55 +470,85 @@ extern "C" int ttx_encode_src(ttx_session* s, const int64_t* d_src, int B, int L
 }
 
 // ------------------------------------------------------------------------------------------------
+// The rows one pass of the decoder stack runs on: a bulk pass over M rows (m_ptr null, Mmax = M, every variant GV_BIG, one
+// Q/K/V buffer for all layers) or a verify step (live row count on the device, per-shape variants, Q/K/V rows kept per layer).
+struct StackRows {
+  const int* m_ptr;
+  int Mmax;
+  int v_qkv, v_dd, v_ffn1, v_ffn2;   // GemmVariant per GEMM shape: QKV | the d-wide K = d GEMMs and the classifier | FFN1 | FFN2
+  float* qkv;                        // layer l's packed Q/K/V rows start at qkv + l * qkv_layer
+  long long qkv_layer;
+};
+
+// Decoder layers and classifier over the embedded rows in s->x: per layer QKV GEMM, self attention, out-projection + LN, Q GEMM,
+// cross attention, out-projection + LN, feed-forward (+ the final norm behind the last layer); then logits = classifier(xf).
+// self_attn(l, qkv) and cross_attn(l) launch layer l's attention from the layer's Q/K/V rows / from s->q2 into s->ao.
+template <class SelfAttn, class CrossAttn>
+static int run_decoder_stack(ttx_session* s, hipStream_t st, const StackRows& r, SelfAttn&& self_attn, CrossAttn&& cross_attn,
+                             float* logits) {
+  const ttx_model* m = s->m;
+  const ttx_config& c = m->cfg;
+  const int d = c.embedding_dim, V = c.vocab_size, Ld = c.num_decoder_layers;
+  float* x = s->x.as<float>();
+  float* x1 = s->x1.as<float>();
+  float* x2 = s->x2.as<float>();
+  float* xf = s->xf.as<float>();
+  float* ao = s->ao.as<float>();
+  float* q2 = s->q2.as<float>();
+  for (int l = 0; l < Ld; ++l) {
+    const LayerW& w = m->dec[l];
+    const bool last = (l == Ld - 1);
+    float* qkv = r.qkv + (size_t)l * r.qkv_layer;
+    TTX_TRY(launch_gemm(s, st, x, d, m->p(w.sa_in_w), d, m->p(w.sa_in_b), qkv, 3 * d, r.m_ptr, r.Mmax, 3 * d, d, false, 0, 0, r.v_qkv));
+    TTX_TRY(self_attn(l, qkv));
+    TTX_TRY(gemm_ln(s, st, ao, d, d, m->p(w.sa_out_w), m->p(w.sa_out_b), x, m->p(w.n1_w), m->p(w.n1_b), nullptr, nullptr,
+                    nullptr, x1, r.m_ptr, r.Mmax, r.v_dd));
+    TTX_TRY(launch_gemm(s, st, x1, d, m->p(w.ca_in_w), d, m->p(w.ca_in_b), q2, d, r.m_ptr, r.Mmax, d, d, false, 0, 0, r.v_dd));
+    TTX_TRY(cross_attn(l));
+    TTX_TRY(gemm_ln(s, st, ao, d, d, m->p(w.ca_out_w), m->p(w.ca_out_b), x1, m->p(w.n2_w), m->p(w.n2_b), nullptr, nullptr,
+                    nullptr, x2, r.m_ptr, r.Mmax, r.v_dd));
+    TTX_TRY(ffn_half(s, st, w, x2, w.n3_w, w.n3_b, last ? m->p(m->dec_norm_w) : nullptr, last ? m->p(m->dec_norm_b) : nullptr,
+                     nullptr, last ? xf : x, r.m_ptr, r.Mmax, r.v_ffn1, r.v_ffn2));
+  }
+  return launch_gemm(s, st, xf, d, m->p(m->cls_w), d, m->p(m->cls_b), logits, V, r.m_ptr, r.Mmax, V, d, false, 0, 0, r.v_dd);
+}
+
 // Full-prefix decoder (modules.py:118-138).  tok int32 [R*Lt]; memory fp32 [Rm*Ls, d]; mem_pad u8 [Rm*Ls].
 static int run_decoder_full(ttx_session* s, hipStream_t st, const int* tok, int R, int Lt, const float* memory,
                             const uint8_t* mem_pad, const int* mem_row, int Rm, int Ls, float* logits) {
   const ttx_model* m = s->m;
   const ttx_config& c = m->cfg;
-  const int d = c.embedding_dim, F = c.feedforward_dim, H = c.num_heads, V = c.vocab_size;
+  const int d = c.embedding_dim, H = c.num_heads;
   const int M = R * Lt, Mk = Rm * Ls;
   const int gv = variant_for_rows(s, M, false);
   TTX_TRY(ensure_acts(s, st, (size_t)M, 1));
   TTX_TRY(ensure(s->ckv, (size_t)Mk * 2 * d * 4, st));
-  float* x = s->x.as<float>();
-  float* x1 = s->x1.as<float>();
-  float* x2 = s->x2.as<float>();
-  float* xf = s->xf.as<float>();
-  float* qkv = s->qkv.as<float>();
   float* ao = s->ao.as<float>();
-  float* q2 = s->q2.as<float>();
-  float* hb = s->hbuf.as<float>();
   float* ckv = s->ckv.as<float>();
   const float scale = 1.0f / sqrtf((float)(d / H));
   EmbedArgs e{};
-  e.table = m->p(m->tgt_emb); e.pe = m->p(m->pe); e.X = x; e.d = d; e.V = c.vocab_size; e.tok = tok; e.rows = M; e.L = Lt;
+  e.table = m->p(m->tgt_emb); e.pe = m->p(m->pe); e.X = s->x.as<float>(); e.d = d; e.V = c.vocab_size; e.tok = tok; e.rows = M; e.L = Lt;
   hipLaunchKernelGGL((k_embed<false>), dim3(cdiv(M, 4)), dim3(256), 0, st, e);
   HIP_TRY(hipGetLastError());
-  for (int l = 0; l < c.num_decoder_layers; ++l) {
-    const LayerW& w = m->dec[l];
-    const bool last = (l == c.num_decoder_layers - 1);
-    TTX_TRY(launch_gemm(s, st, x, d, m->p(w.sa_in_w), d, m->p(w.sa_in_b), qkv, 3 * d, nullptr, M, 3 * d, d, false, 0, 0, gv));
-    AttnArgs a{};
-    a.q = qkv; a.ldq = 3 * d; a.k = qkv + d; a.v = qkv + 2 * d; a.ldkv = 3 * d; a.out = ao; a.d = d; a.scale = scale;
-    a.L = Lt; a.tok = tok; a.pad = c.pad_token;
-    TTX_TRY(launch_attn(ATT_FULL_SELF, s, st, a, R, H, Lt, Lt));
-    TTX_TRY(gemm_ln(s, st, ao, d, d, m->p(w.sa_out_w), m->p(w.sa_out_b), x, m->p(w.n1_w), m->p(w.n1_b), nullptr, nullptr,
-                    nullptr, x1, nullptr, M, gv));
-    // cross attention: Q from the decoder stream, K/V re-projected from `memory` (as the reference does per call)
-    TTX_TRY(launch_gemm(s, st, x1, d, m->p(w.ca_in_w), d, m->p(w.ca_in_b), q2, d, nullptr, M, d, d, false, 0, 0, gv));
-    TTX_TRY(launch_gemm(s, st, memory, d, m->p(w.ca_in_w) + (size_t)d * d, d, m->p(w.ca_in_b) + d, ckv, 2 * d, nullptr, Mk,
-                        2 * d, d, false, 0, 0, gv));
-    AttnArgs ca{};
-    ca.q = q2; ca.ldq = d; ca.k = ckv; ca.v = ckv + d; ca.ldkv = 2 * d; ca.out = ao; ca.d = d; ca.scale = scale;
-    ca.L = Lt; ca.Lk = Ls; ca.key_pad = mem_pad; ca.mem_row = mem_row;
-    TTX_TRY(launch_attn(ATT_FULL_CROSS, s, st, ca, R, H, Lt, Ls));
-    TTX_TRY(gemm_ln(s, st, ao, d, d, m->p(w.ca_out_w), m->p(w.ca_out_b), x1, m->p(w.n2_w), m->p(w.n2_b), nullptr, nullptr,
-                    nullptr, x2, nullptr, M, gv));
-    TTX_TRY(launch_gemm(s, st, x2, d, m->p(w.l1_w), d, m->p(w.l1_b), hb, F, nullptr, M, F, d, m->activation, 0, 0, gv));
-    TTX_TRY(gemm_ln(s, st, hb, F, F, m->p(w.l2_w), m->p(w.l2_b), x2, m->p(w.n3_w), m->p(w.n3_b),
-                    last ? m->p(m->dec_norm_w) : nullptr, last ? m->p(m->dec_norm_b) : nullptr, nullptr, last ? xf : x, nullptr, M, gv));
-  }
-  return launch_gemm(s, st, xf, d, m->p(m->cls_w), d, m->p(m->cls_b), logits, V, nullptr, M, V, d, false, 0, 0, gv);
+  const StackRows rows{nullptr, M, gv, gv, gv, gv, s->qkv.as<float>(), 0};
+  return run_decoder_stack(s, st, rows,
+      [&](int, float* qkv) -> int {
+        AttnArgs a{};
+        a.q = qkv; a.ldq = 3 * d; a.k = qkv + d; a.v = qkv + 2 * d; a.ldkv = 3 * d; a.out = ao; a.d = d; a.scale = scale;
+        a.L = Lt; a.tok = tok; a.pad = c.pad_token;
+        return launch_attn(ATT_FULL_SELF, s, st, a, R, H, Lt, Lt);
+      },
+      [&](int l) -> int {
+        // cross attention: Q from the decoder stream, K/V re-projected from `memory` (as the reference does per call)
+        const LayerW& w = m->dec[l];
+        TTX_TRY(launch_gemm(s, st, memory, d, m->p(w.ca_in_w) + (size_t)d * d, d, m->p(w.ca_in_b) + d, ckv, 2 * d, nullptr, Mk,
+                            2 * d, d, false, 0, 0, gv));
+        AttnArgs ca{};
+        ca.q = s->q2.as<float>(); ca.ldq = d; ca.k = ckv; ca.v = ckv + d; ca.ldkv = 2 * d; ca.out = ao; ca.d = d; ca.scale = scale;
+        ca.L = Lt; ca.Lk = Ls; ca.key_pad = mem_pad; ca.mem_row = mem_row;
+        return launch_attn(ATT_FULL_CROSS, s, st, ca, R, H, Lt, Ls);
+      },
+      logits);
 }
 
 extern "C" int ttx_decode_tgt(ttx_session* s, const int64_t* d_tgt, int R, int Lt, const float* d_memory,
@@ -700,6 +739,15 @@ extern "C" int ttx_score_hypotheses(ttx_session* s, const int64_t* d_src, int B,
 }
 
 // ------------------------------------------------------------------------------------------------
+// A kernel whose dynamic LDS exceeds the default limit has the limit raised once per session (`done`), outside graph capture.
+static int raise_lds_limit(const void* kernel, size_t lds, bool& done) {
+  if (lds > 64 * 1024 && !done) {
+    HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    done = true;
+  }
+  return TTX_OK;
+}
+
 static int clamp_draft_len(int draft_len, int lo, int hi) { return std::min(std::max(lo, draft_len), hi); }
 
 template <typename OutT>
@@ -757,25 +805,16 @@ struct StepCtx {
 static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) {
   const ttx_model* m = s->m;
   const ttx_config& c = m->cfg;
-  const int d = c.embedding_dim, F = c.feedforward_dim, H = c.num_heads, V = c.vocab_size, Ld = c.num_decoder_layers;
+  const int d = c.embedding_dim, H = c.num_heads, V = c.vocab_size, Ld = c.num_decoder_layers;
   const int D1 = k.D + 1;
   const int RPS = step_rps(k.N, k.D);
   const int Mmax = k.B * RPS;
-  const int vq = variant_qkv(k.variant), vd = variant_dd(k.variant), v1 = variant_ffn1(k.variant), vf = variant_ffn2(k.variant);
   DecState* dst = k.st_ov ? k.st_ov : s->state.as<DecState>();
   const int* act = k.act_ov ? k.act_ov : s->act_idx.as<int>();
-  float* qkv_base = k.qkv_ov ? k.qkv_ov : s->qkv.as<float>();
   const int* m_ptr = &dst->m_rows;
-  float* x = s->x.as<float>();
-  float* x1 = s->x1.as<float>();
-  float* x2 = s->x2.as<float>();
-  float* xf = s->xf.as<float>();
   float* ao = s->ao.as<float>();
-  float* q2 = s->q2.as<float>();
-  float* hb = s->hbuf.as<float>();
   float* logits = s->logits.as<float>();
   const float scale = 1.0f / sqrtf((float)(d / H));
-  const long long qkv_layer = (long long)Mmax * 3 * d;
   const long long cache_seq = (long long)k.Lc * d;
   const long long cache_layer = (long long)k.B * cache_seq;
 
@@ -785,40 +824,33 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
     ~AttnSel() { s->attn_sel_N = 0; s->attn_sel_D = 0; }
   } attn_sel(s, k.sel_N, k.sel_D);
   EmbedArgs e{};
-  e.table = m->p(m->tgt_emb); e.pe = m->p(m->pe); e.X = x; e.d = d; e.V = c.vocab_size;
+  e.table = m->p(m->tgt_emb); e.pe = m->p(m->pe); e.X = s->x.as<float>(); e.d = d; e.V = c.vocab_size;
   e.st = dst; e.act_idx = act; e.front = s->front.as<int>(); e.gen = s->gen.as<int>(); e.gen_ld = k.gen_ld;
   e.drafts = s->drafts.as<int>(); e.N = k.N; e.D = k.D;
   hipLaunchKernelGGL((k_embed<true>), dim3(cdiv(Mmax, 4)), dim3(256), 0, st, e);
   HIP_TRY(hipGetLastError());
 
-  for (int l = 0; l < Ld; ++l) {
-    const LayerW& w = m->dec[l];
-    const bool last = (l == Ld - 1);
-    float* qkv = qkv_base + (size_t)l * qkv_layer;
-    TTX_TRY(launch_gemm(s, st, x, d, m->p(w.sa_in_w), d, m->p(w.sa_in_b), qkv, 3 * d, m_ptr, Mmax, 3 * d, d, false, 0, 0, vq));
-    AttnArgs a{};
-    a.q = qkv; a.ldq = 3 * d; a.k = qkv + d; a.v = qkv + 2 * d; a.ldkv = 3 * d; a.out = ao; a.d = d; a.scale = scale;
-    a.tok = s->gen.as<int>(); a.pad = c.pad_token; a.st = dst; a.act_idx = act; a.front = s->front.as<int>();
-    a.kcache = (k.kcache ? k.kcache : s->kcache.as<float>()) + (size_t)l * cache_layer;
-    a.vcache = (k.vcache ? k.vcache : s->vcache.as<float>()) + (size_t)l * cache_layer;
-    a.cache_seq_stride = cache_seq; a.gen_ld = k.gen_ld; a.N = k.N; a.D = k.D; a.cache_slot = k.cache_slot;
-    TTX_TRY(launch_attn(ATT_STEP_SELF, s, st, a, k.B, H, RPS, kcap, k.N, D1));
-    TTX_TRY(gemm_ln(s, st, ao, d, d, m->p(w.sa_out_w), m->p(w.sa_out_b), x, m->p(w.n1_w), m->p(w.n1_b), nullptr, nullptr,
-                    nullptr, x1, m_ptr, Mmax, vd));
-    TTX_TRY(launch_gemm(s, st, x1, d, m->p(w.ca_in_w), d, m->p(w.ca_in_b), q2, d, m_ptr, Mmax, d, d, false, 0, 0, vd));
-    AttnArgs ca{};
-    ca.q = q2; ca.ldq = d; ca.k = s->memkv.as<float>() + (size_t)l * 2 * d; ca.v = ca.k + d; ca.ldkv = Ld * 2 * d;
-    ca.out = ao; ca.d = d; ca.scale = scale; ca.Lk = k.Ls; ca.key_pad = s->src_valid.as<uint8_t>();
-    ca.st = dst; ca.act_idx = act; ca.front = s->front.as<int>(); ca.N = k.N; ca.D = k.D;
-    ca.src_of = k.src_of; ca.src_len = k.src_len;
-    TTX_TRY(launch_attn(ATT_STEP_CROSS, s, st, ca, k.B, H, RPS, k.Ls, k.N, D1));
-    TTX_TRY(gemm_ln(s, st, ao, d, d, m->p(w.ca_out_w), m->p(w.ca_out_b), x1, m->p(w.n2_w), m->p(w.n2_b), nullptr, nullptr,
-                    nullptr, x2, m_ptr, Mmax, vd));
-    TTX_TRY(launch_gemm(s, st, x2, d, m->p(w.l1_w), d, m->p(w.l1_b), hb, F, m_ptr, Mmax, F, d, m->activation, 0, 0, v1));
-    TTX_TRY(gemm_ln(s, st, hb, F, F, m->p(w.l2_w), m->p(w.l2_b), x2, m->p(w.n3_w), m->p(w.n3_b),
-                    last ? m->p(m->dec_norm_w) : nullptr, last ? m->p(m->dec_norm_b) : nullptr, nullptr, last ? xf : x, m_ptr, Mmax, vf));
-  }
-  TTX_TRY(launch_gemm(s, st, xf, d, m->p(m->cls_w), d, m->p(m->cls_b), logits, V, m_ptr, Mmax, V, d, false, 0, 0, vd));
+  const StackRows rows{m_ptr, Mmax, variant_qkv(k.variant), variant_dd(k.variant), variant_ffn1(k.variant), variant_ffn2(k.variant),
+                       k.qkv_ov ? k.qkv_ov : s->qkv.as<float>(), (long long)Mmax * 3 * d};
+  TTX_TRY(run_decoder_stack(s, st, rows,
+      [&](int l, float* qkv) -> int {
+        AttnArgs a{};
+        a.q = qkv; a.ldq = 3 * d; a.k = qkv + d; a.v = qkv + 2 * d; a.ldkv = 3 * d; a.out = ao; a.d = d; a.scale = scale;
+        a.tok = s->gen.as<int>(); a.pad = c.pad_token; a.st = dst; a.act_idx = act; a.front = s->front.as<int>();
+        a.kcache = (k.kcache ? k.kcache : s->kcache.as<float>()) + (size_t)l * cache_layer;
+        a.vcache = (k.vcache ? k.vcache : s->vcache.as<float>()) + (size_t)l * cache_layer;
+        a.cache_seq_stride = cache_seq; a.gen_ld = k.gen_ld; a.N = k.N; a.D = k.D; a.cache_slot = k.cache_slot;
+        return launch_attn(ATT_STEP_SELF, s, st, a, k.B, H, RPS, kcap, k.N, D1);
+      },
+      [&](int l) -> int {
+        AttnArgs ca{};
+        ca.q = s->q2.as<float>(); ca.ldq = d; ca.k = s->memkv.as<float>() + (size_t)l * 2 * d; ca.v = ca.k + d; ca.ldkv = Ld * 2 * d;
+        ca.out = ao; ca.d = d; ca.scale = scale; ca.Lk = k.Ls; ca.key_pad = s->src_valid.as<uint8_t>();
+        ca.st = dst; ca.act_idx = act; ca.front = s->front.as<int>(); ca.N = k.N; ca.D = k.D;
+        ca.src_of = k.src_of; ca.src_len = k.src_len;
+        return launch_attn(ATT_STEP_CROSS, s, st, ca, k.B, H, RPS, k.Ls, k.N, D1);
+      },
+      logits));
   if (k.want_argmax) {
     hipLaunchKernelGGL(k_argmax, dim3(cdiv(Mmax, 4)), dim3(256), 0, st, logits, V, k.pred_ov ? k.pred_ov : s->pred.as<int>(), m_ptr, Mmax);
     HIP_TRY(hipGetLastError());
@@ -862,6 +894,52 @@ static int session_alive(const ttx_session* s) {
   return TTX_OK;
 }
 
+// A polling loop's wait for the step in flight: stalled() counts one fruitless look and asks the watchdog on every 65 536th,
+// advanced() restarts both when the step has published.  No HIP call while polling: only the clock.
+struct Progress {
+  unsigned idle_spins = 0;
+  std::chrono::steady_clock::time_point last_progress = std::chrono::steady_clock::now();
+  bool stalled() { return (++idle_spins & 0xffff) == 0 && watchdog_expired(last_progress); }
+  void advanced() { idle_spins = 0; last_progress = std::chrono::steady_clock::now(); }
+};
+
+// Key capacity of a step whose rows see fewer than `width` prefix keys: the LDS images of the self-attention come in buckets of
+// 64 keys, so that a graph serves 64 widths.
+static int key_capacity(int width, int max_len) { return std::min(max_len, ((width + 63) / 64) * 64); }
+
+// Enqueue the launch sequence `enqueue()` puts on `st`: eagerly when graphs are off (TTX_NO_GRAPH, profiling sessions) and the
+// first time `key` is seen (function attributes, i.e. dynamic LDS limits, are set outside capture); captured into `cache` the
+// second time; replayed from the captured graph from then on.
+template <class Enqueue>
+static int graph_replay(ttx_session* s, hipStream_t st, GraphCache& cache, const GraphKey& key, Enqueue&& enqueue) {
+  if (!s->use_graphs || s->profile) return enqueue();
+  const auto now = [s] { return s->host_timing ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point(); };
+  const auto us_since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::micro>(now() - t0).count(); };
+  s->graphs_current();                             // captured pointers may be stale
+  auto it = cache.map.find(key);
+  if (it == cache.map.end()) {
+    if (cache.warmed.insert(key).second) return enqueue();
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    const auto t0 = now();
+    HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue();
+    hipError_t e = hipStreamEndCapture(st, &graph);
+    if (rc != TTX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+    if (e != hipSuccess) return fail(TTX_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (e != hipSuccess) return fail(TTX_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+    if (cache.map.size() > cache.limit) s->drop_graphs();
+    it = cache.map.emplace(key, exec).first;
+    if (s->host_timing) { s->host_captures += 1; s->host_capture_us += us_since(t0); }
+  }
+  const auto t0 = now();
+  HIP_TRY(hipGraphLaunch(it->second, st));
+  if (s->host_timing) { s->host_launches += 1; s->host_launch_us += us_since(t0); }
+  return TTX_OK;
+}
+
 struct EventGuard {              // destroys the event on every exit path
   hipEvent_t e = nullptr;
   ~EventGuard() { if (e) (void)hipEventDestroy(e); }
@@ -880,8 +958,7 @@ struct GenJob {
   int launched = 0;
   int phase = 0;          // 0 idle, 1 running, 2 finishing
   int batch = -1;
-  unsigned idle_spins = 0;
-  std::chrono::steady_clock::time_point last_progress = std::chrono::steady_clock::now();
+  Progress progress;
 };
 
 static int gen_validate(const ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_gen_params* p, const int64_t* d_out,
@@ -989,8 +1066,8 @@ static int gen_start(GenJob& j, ttx_session* s, hipStream_t st, const int64_t* d
   return TTX_OK;
 }
 
-// Enqueue one verify step: replay the captured graph for this (shape, key-capacity bucket), capturing it on
-// first use.  `width_bound` bounds the reference's generated width when the step runs.
+// Enqueue one verify step through graph_replay, one graph per (shape, key-capacity bucket); the step whose logits the caller
+// asked for (want_logits) runs eagerly.  `width_bound` bounds the reference's generated width when the step runs.
 static int gen_launch_step(GenJob& j, int width_bound) {
   ttx_session* s = j.s;
   StepCtx k = j.g.k;
@@ -998,65 +1075,31 @@ static int gen_launch_step(GenJob& j, int width_bound) {
   // keeps all B rows): a free choice, every variant returns the same bits
   const int live = j.greedy ? k.B : std::max(1, (int)((volatile HostInfo*)s->host_info)->n_active);
   k.variant = variant_for_rows(s, (long long)live * step_rps(k.N, k.D), true);
-  // prefix keys this step can see: < width_bound; bucket the LDS images of the self-attention in steps of 64 keys
-  int kcap = std::min(k.max_len, ((std::max(width_bound, 1) + 63) / 64) * 64);
-  const bool snapshot = (k.p.want_logits > 0 && k.p.want_logits == j.launched + 1);
-  const bool use_graph = s->use_graphs && !s->profile && !snapshot;
-  if (!use_graph) {
+  const int kcap = key_capacity(std::max(width_bound, 1), k.max_len);        // prefix keys this step can see: < width_bound
+  const auto enqueue = [&]() -> int {
     TTX_TRY(run_step(s, j.st, k, kcap));
-    if (snapshot) {
-      // keep this step's pre-argmax logits and the loop state they belong to (before accept changes it)
-      const ttx_config& c = s->m->cfg;
-      const size_t Mmax = (size_t)k.B * step_rps(k.N, k.D);
-      TTX_TRY(ensure(s->snap_logits, Mmax * c.vocab_size * 4, j.st));
-      TTX_TRY(ensure(s->snap_act, (size_t)k.B * 4, j.st));
-      TTX_TRY(ensure(s->snap_front, (size_t)k.B * 4, j.st));
-      TTX_TRY(ensure(s->snap_gen, (size_t)k.B * k.gen_ld * 4, j.st));
-      TTX_TRY(ensure(s->snap_state, sizeof(DecState), j.st));
-      HIP_TRY(hipMemcpyAsync(s->snap_logits.p, s->logits.p, Mmax * c.vocab_size * 4, hipMemcpyDeviceToDevice, j.st));
-      HIP_TRY(hipMemcpyAsync(s->snap_act.p, s->act_idx.p, (size_t)k.B * 4, hipMemcpyDeviceToDevice, j.st));
-      HIP_TRY(hipMemcpyAsync(s->snap_front.p, s->front.p, (size_t)k.B * 4, hipMemcpyDeviceToDevice, j.st));
-      HIP_TRY(hipMemcpyAsync(s->snap_gen.p, s->gen.p, (size_t)k.B * k.gen_ld * 4, hipMemcpyDeviceToDevice, j.st));
-      HIP_TRY(hipMemcpyAsync(s->snap_state.p, s->state.p, sizeof(DecState), hipMemcpyDeviceToDevice, j.st));
-      s->snap_B = k.B; s->snap_rps = step_rps(k.N, k.D); s->snap_gen_ld = k.gen_ld; s->snap_step = j.launched + 1;
-    }
+    return launch_accept_and_commit(s, j.st, j.g, j.greedy);
+  };
+  if (k.p.want_logits > 0 && k.p.want_logits == j.launched + 1) {
+    // the snapshot step runs eagerly: keep its pre-argmax logits and the loop state they belong to (before accept changes it)
+    TTX_TRY(run_step(s, j.st, k, kcap));
+    const ttx_config& c = s->m->cfg;
+    const size_t Mmax = (size_t)k.B * step_rps(k.N, k.D);
+    TTX_TRY(ensure(s->snap_logits, Mmax * c.vocab_size * 4, j.st));
+    TTX_TRY(ensure(s->snap_act, (size_t)k.B * 4, j.st));
+    TTX_TRY(ensure(s->snap_front, (size_t)k.B * 4, j.st));
+    TTX_TRY(ensure(s->snap_gen, (size_t)k.B * k.gen_ld * 4, j.st));
+    TTX_TRY(ensure(s->snap_state, sizeof(DecState), j.st));
+    HIP_TRY(hipMemcpyAsync(s->snap_logits.p, s->logits.p, Mmax * c.vocab_size * 4, hipMemcpyDeviceToDevice, j.st));
+    HIP_TRY(hipMemcpyAsync(s->snap_act.p, s->act_idx.p, (size_t)k.B * 4, hipMemcpyDeviceToDevice, j.st));
+    HIP_TRY(hipMemcpyAsync(s->snap_front.p, s->front.p, (size_t)k.B * 4, hipMemcpyDeviceToDevice, j.st));
+    HIP_TRY(hipMemcpyAsync(s->snap_gen.p, s->gen.p, (size_t)k.B * k.gen_ld * 4, hipMemcpyDeviceToDevice, j.st));
+    HIP_TRY(hipMemcpyAsync(s->snap_state.p, s->state.p, sizeof(DecState), hipMemcpyDeviceToDevice, j.st));
+    s->snap_B = k.B; s->snap_rps = step_rps(k.N, k.D); s->snap_gen_ld = k.gen_ld; s->snap_step = j.launched + 1;
     TTX_TRY(launch_accept_and_commit(s, j.st, j.g, j.greedy));
-    ++j.launched;
-    return TTX_OK;
-  }
-  GraphKey key{k.B, k.Ls, k.N, k.D, k.max_len, j.greedy ? 1 : (j.g.la.row_rule ? 2 : 0), kcap, k.variant};
-  s->graphs_current();
-  auto it = s->graphs.find(key);
-  if (it == s->graphs.end()) {
-    if (!s->warmed.count(key)) {
-      // first use of a shape runs eagerly once: function attributes (dynamic LDS limits) are set outside capture
-      s->warmed.insert(key);
-      TTX_TRY(run_step(s, j.st, k, kcap));
-      TTX_TRY(launch_accept_and_commit(s, j.st, j.g, j.greedy));
-      ++j.launched;
-      return TTX_OK;
-    }
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    HIP_TRY(hipStreamBeginCapture(j.st, hipStreamCaptureModeThreadLocal));
-    int rc = run_step(s, j.st, k, kcap);
-    if (rc == TTX_OK) rc = launch_accept_and_commit(s, j.st, j.g, j.greedy);
-    hipError_t e = hipStreamEndCapture(j.st, &graph);
-    if (rc != TTX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    if (e != hipSuccess) return fail(TTX_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) return fail(TTX_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-    if (s->graphs.size() > 512) s->drop_graphs();
-    it = s->graphs.emplace(key, exec).first;
-  }
-  if (s->host_timing) {
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(hipGraphLaunch(it->second, j.st));
-    s->host_launch_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    s->host_launches += 1;
   } else {
-    HIP_TRY(hipGraphLaunch(it->second, j.st));
+    const int site = j.greedy ? GS_STEP_GREEDY : (j.g.la.row_rule ? GS_STEP_ROW_RULE : GS_STEP_SPECULATIVE);
+    TTX_TRY(graph_replay(s, j.st, s->step_graphs, GraphKey{site, k.B, k.Ls, k.N, k.D, k.max_len, kcap, k.variant, 0}, enqueue));
   }
   ++j.launched;
   return TTX_OK;
@@ -1175,10 +1218,9 @@ static int generate_common(ttx_session* s, const int64_t* d_src, int B, int Ls, 
     if (j.launched > p->max_len + 2) return fail(TTX_ERR_HIP, "decode loop failed to terminate");
     TTX_TRY(gen_launch_step(j, hi->width + D1));
     const int want = j.launched;
-    unsigned spins = 0;
-    const auto since = std::chrono::steady_clock::now();
-    while (hi->steps_done < want && !hi->stop) {            // no HIP call while polling: only the clock
-      if ((++spins & 0xffff) == 0 && watchdog_expired(since)) return session_hung(s);
+    Progress wait;
+    while (hi->steps_done < want && !hi->stop) {
+      if (wait.stalled()) return session_hung(s);
       __builtin_ia32_pause();
     }
   }
@@ -1216,8 +1258,7 @@ struct PoolJob {
   int admits = 0;
   int quota_end = -1;       // serial (profiling) pass: end of this pool's share of the work list
   PoolIo io{};
-  unsigned idle_spins = 0;
-  std::chrono::steady_clock::time_point last_progress = std::chrono::steady_clock::now();
+  Progress progress;
   long long admitted_rows = 0, src_tokens_padded = 0;
   // two-phase verify step (DESIGN.md "Two-phase verify step"): a free choice per step, both forms give the same bits
   bool two_phase = true;    // TTX_TWO_PHASE=0: every step in one pass
@@ -1355,34 +1396,9 @@ static int pool_admit(PoolJob& j, const int64_t* d_src_rows, int ld_src, int R, 
   return TTX_OK;
 }
 
-// Enqueue one graph's worth of a pool step: replayed from the captured graph of `key`, captured on second use (the first use of
-// a shape runs eagerly: function attributes are set outside capture), or eagerly (TTX_NO_GRAPH, profiling sessions).
-template <class Enqueue>
-static int pool_replay(PoolJob& j, const GraphKey& key, Enqueue&& enqueue) {
-  ttx_session* s = j.s;
-  const bool use_graph = s->use_graphs && !s->profile;
-  s->graphs_current();
-  auto it = s->graphs.find(key);
-  if (!use_graph || (it == s->graphs.end() && !s->warmed.count(key))) {
-    s->warmed.insert(key);
-    return enqueue();
-  }
-  if (it == s->graphs.end()) {
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    HIP_TRY(hipStreamBeginCapture(j.st, hipStreamCaptureModeThreadLocal));
-    int rc = enqueue();
-    hipError_t e = hipStreamEndCapture(j.st, &graph);
-    if (rc != TTX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    if (e != hipSuccess) return fail(TTX_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) return fail(TTX_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-    if (s->graphs.size() > 512) s->drop_graphs();
-    it = s->graphs.emplace(key, exec).first;
-  }
-  HIP_TRY(hipGraphLaunch(it->second, j.st));
-  return TTX_OK;
+// Key of one graph's worth of a pool step (`phase`: GraphKey in ttx_internal.h); the pool's steps see every key of a slot.
+static GraphKey pool_key(const StepCtx& k, int variant, int phase) {
+  return GraphKey{GS_STEP_POOL, k.B, k.Ls, k.N, k.D, k.max_len, k.max_len, variant, phase};
 }
 
 // One verify step of the pool.  With enough live rows it is split: this call enqueues the probe (the front rows of all live
@@ -1394,8 +1410,7 @@ static int pool_launch_step(PoolJob& j, int n_live) {
   const long long rows = (long long)n_live * step_rps(k.N, k.D);
   if (!j.two_phase || rows < j.min_rows) {
     k.variant = variant_for_rows(s, rows, true);     // free choice: identical bits
-    GraphKey key{k.B, k.Ls, k.N, k.D, k.max_len, 3, kcap, k.variant, 0};
-    TTX_TRY(pool_replay(j, key, [&]() -> int {
+    TTX_TRY(graph_replay(s, j.st, s->step_graphs, pool_key(k, k.variant, 0), [&]() -> int {
       TTX_TRY(run_step(s, j.st, k, kcap));
       return launch_accept_and_commit(s, j.st, j.g, false);
     }));
@@ -1407,8 +1422,7 @@ static int pool_launch_step(PoolJob& j, int n_live) {
   kp.N = 1; kp.D = 0; kp.sel_N = k.N; kp.sel_D = k.D;
   kp.st_ov = st2; kp.qkv_ov = s->qkv_probe.as<float>(); kp.pred_ov = s->pred_probe.as<int>();
   kp.variant = variant_for_rows(s, n_live, true);
-  GraphKey key{k.B, k.Ls, k.N, k.D, k.max_len, 3, kcap, kp.variant, 1};
-  TTX_TRY(pool_replay(j, key, [&]() -> int {
+  TTX_TRY(graph_replay(s, j.st, s->step_graphs, pool_key(k, kp.variant, 1), [&]() -> int {
     hipLaunchKernelGGL(k_probe_begin, dim3(1), dim3(64), 0, j.st, s->state.as<DecState>(), st2);
     HIP_TRY(hipGetLastError());
     TTX_TRY(run_step(s, j.st, kp, kcap));
@@ -1440,8 +1454,7 @@ static int pool_launch_drafts(PoolJob& j) {
   k.st_ov = st2 + 1; k.act_ov = s->act2.as<int>(); k.pred_ov = s->pred_draft.as<int>();
   k.variant = matches ? variant_for_rows(s, (long long)matches * RPS, true) : 0;
   j.matched_slot_steps += matches; j.skipped_draft_passes += matches ? 0 : 1;
-  GraphKey key{k.B, k.Ls, k.N, k.D, k.max_len, 3, kcap, k.variant, matches ? 2 : 3};
-  TTX_TRY(pool_replay(j, key, [&]() -> int {
+  TTX_TRY(graph_replay(s, j.st, s->step_graphs, pool_key(k, k.variant, matches ? 2 : 3), [&]() -> int {
     if (matches) TTX_TRY(run_step(s, j.st, k, kcap));
     MergePredArgs mp{};
     mp.st = s->state.as<DecState>(); mp.pos2 = s->pos2.as<int>(); mp.pred_probe = s->pred_probe.as<int>();
@@ -1512,30 +1525,27 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
       if (j.phase == 1) {
         if (j.probe_pending) {                                                // the same rules as for steps_done below
           if (((volatile ProbeInfo*)s->probe_info)->probes_done < j.probes) {
-            if ((++j.idle_spins & 0xffff) == 0 && watchdog_expired(j.last_progress)) {
+            if (j.progress.stalled()) {
               rc_final = session_hung(s);
               hung = true;
               break;
             }
             continue;
           }
-          j.idle_spins = 0;
-          j.last_progress = std::chrono::steady_clock::now();
+          j.progress.advanced();
           rc_final = pool_launch_drafts(j);
           progressed = true;
           continue;
         }
         if (j.launched > 0 && hi->steps_done < j.launched) {                  // the step in flight has not published yet
-          // never spin forever (no HIP call in the polling loop: only the clock)
-          if ((++j.idle_spins & 0xffff) == 0 && watchdog_expired(j.last_progress)) {
+          if (j.progress.stalled()) {                                         // never spin forever
             rc_final = session_hung(s);
             hung = true;
             break;
           }
           continue;
         }
-        j.idle_spins = 0;
-        j.last_progress = std::chrono::steady_clock::now();
+        j.progress.advanced();
         int n_act = (j.launched == 0) ? 0 : hi->n_active;
         const int free_slots = C - n_act;
         // serial pass: every pool decodes an equal contiguous share of the rest of the list (what it takes at once when the list
@@ -1671,10 +1681,9 @@ static int generate_many_impl(ttx_session** sessions, int n_sessions, int n_batc
           int rc = gen_launch_step(j, hi->width + D1);
           if (rc != TTX_OK) { rc_final = rc; done = n_batches; break; }
           progressed = true;
-          j.idle_spins = 0;
-          j.last_progress = std::chrono::steady_clock::now();
-        } else if (j.launched > 0 && (++j.idle_spins & 0xffff) == 0 && watchdog_expired(j.last_progress)) {
-          rc_final = session_hung(s);                                                       // no HIP call while polling
+          j.progress.advanced();
+        } else if (j.launched > 0 && j.progress.stalled()) {
+          rc_final = session_hung(s);
           hung = true;
           done = n_batches;
           break;
@@ -1753,10 +1762,7 @@ extern "C" int ttx_ragged_topk(ttx_session* s, const float* d_score, const int32
   if (G == 0) return TTX_OK;
   HIP_TRY(hipSetDevice(s->m->device));
   const size_t lds = (size_t)max_group * 4;
-  if (lds > 64 * 1024 && !s->attr_topk) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ragged_topk), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    s->attr_topk = true;
-  }
+  TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_ragged_topk), lds, s->attr_topk));
   RaggedTopkArgs a{d_score, d_offsets, k, d_top, d_idx};
   hipLaunchKernelGGL(k_ragged_topk, dim3(G), dim3(256), lds, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
@@ -1786,8 +1792,7 @@ struct BeamJob {
   int64_t* d_out = nullptr;
   ttx_beam_stats* stats = nullptr;
   int rc = TTX_OK;
-  std::chrono::steady_clock::time_point last_progress = std::chrono::steady_clock::now();
-  unsigned idle_spins = 0;
+  Progress progress;
 };
 
 static int beam_validate(const ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_beam_params* p, const int64_t* d_out) {
@@ -1892,92 +1897,126 @@ __global__ void k_bs_src_of(int* src_of, int n, int beam) {
   if (i < n) src_of[i] = i / beam;
 }
 
+// ---- the pieces of one beam iteration, shared by the beam-speculative loop, its batch pool and standard beam search ----------
+// k_bs_prep (the rows of the last selection -> this iteration's candidates and draft slots) and the candidate -> source map.
+// `pa` arrives with the shape (ld, n_cand, beam, dl, N, pad) and, for the speculative loop, the draft-source fields set.
+static int enqueue_bs_prep(ttx_session* s, hipStream_t st, int MC, BeamPrepArgs pa) {
+  pa.cand_next = s->bs_cand_next.as<int64_t>(); pa.len_next = s->bs_len_next.as<int>();
+  pa.fin_next = s->bs_fin_next.as<uint8_t>(); pa.logp_next = s->bs_logp_next.as<float>();
+  pa.gen = s->gen.as<int>(); pa.front = s->front.as<int>(); pa.len = s->bs_len.as<int>(); pa.active = s->bs_active.as<uint8_t>();
+  pa.finished = s->bs_fin.as<uint8_t>(); pa.logp = s->bs_logp.as<float>(); pa.per_cand = s->bs_per_cand.as<int>();
+  pa.drafts32 = s->drafts.as<int>();
+  hipLaunchKernelGGL(k_bs_prep, dim3(MC), dim3(256), 0, st, pa);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_bs_src_of, dim3(cdiv(MC, 256)), dim3(256), 0, st, s->t_src_of.as<int>(), MC, pa.beam);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+// k_tree_cache: every candidate's KV cache in buffer `to` from its parent's in buffer `from` plus the rows the parent's accepted
+// draft left in the previous step's Q/K/V buffer (layout (prev_N, prev_D)).  With slot maps (the batch pool: from == to) a
+// candidate's cache lives in the slot the map names.
+static int enqueue_tree_cache(ttx_session* s, hipStream_t st, int MC, int Lc, int from, int to, const int* slot_parent,
+                              const int* slot_self, int prev_N, int prev_D) {
+  const int d = s->m->cfg.embedding_dim;
+  TreeCacheArgs ca{};
+  ca.len = s->bs_len.as<int>(); ca.parent = s->bs_parent.as<int>(); ca.parent_draft = s->bs_parent_draft.as<int>();
+  ca.prev_len = s->t_prev_len.as<int>(); ca.active = s->bs_active.as<uint8_t>();
+  ca.k_old = s->tk[from].as<float>(); ca.v_old = s->tv[from].as<float>();
+  ca.k_new = s->tk[to].as<float>(); ca.v_new = s->tv[to].as<float>();
+  ca.slot_parent = slot_parent; ca.slot_self = slot_self;
+  ca.cache_seq_stride = (long long)Lc * d; ca.cache_layer_stride = (long long)MC * ca.cache_seq_stride;
+  ca.qkv_prev = s->qkv.as<float>();
+  ca.qkv_layer_stride = (long long)MC * step_rps(prev_N, prev_D) * 3 * d;
+  ca.prev_slot_of = s->t_slot_of.as<int>(); ca.prev_N = prev_N; ca.prev_D = prev_D; ca.d = d;
+  hipLaunchKernelGGL(k_tree_cache, dim3(MC, s->m->cfg.num_decoder_layers), dim3(256), 0, st, ca);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+// k_bs_list: the running candidates -> the verify step's active list, slot map and DecState.
+static int enqueue_bs_list(ttx_session* s, hipStream_t st, int n_cand, int N, int dl) {
+  BeamListArgs la{};
+  la.active = s->bs_active.as<uint8_t>(); la.per_cand = s->bs_per_cand.as<int>(); la.len = s->bs_len.as<int>();
+  la.n_cand = n_cand; la.N = N; la.dl = dl;
+  la.act_idx = s->act_idx.as<int>(); la.slot_of = s->t_slot_of.as<int>(); la.prev_len = s->t_prev_len.as<int>();
+  la.st = s->state.as<DecState>(); la.cnt = s->bs_cnt.as<BeamCounters>(); la.summary = s->beam_summary.as<int>();
+  hipLaunchKernelGGL(k_bs_list, dim3(1), dim3(256), 0, st, la);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+// The verify step of tree decoding: D + 1 new positions per (running candidate, draft slot) on the candidate's KV cache in
+// buffer `cache`, logits only (the selection kernels read them).
+static StepCtx tree_step_ctx(ttx_session* s, int MC, int Ls, int N, int D, int Lc, int gen_ld, int max_len, int cache, int variant) {
+  StepCtx k{};
+  k.B = MC; k.Ls = Ls; k.N = N; k.D = D; k.Lc = Lc; k.gen_ld = gen_ld; k.max_len = max_len;
+  k.kcache = s->tk[cache].as<float>(); k.vcache = s->tv[cache].as<float>(); k.src_of = s->t_src_of.as<int>(); k.want_argmax = false;
+  k.variant = variant;
+  return k;
+}
+
+// k_bs_hits (which draft tokens the step's logits accept) and k_bs_leaves (the best draft per candidate and its leaves).
+// `pool`: the batch pool's per-candidate draft lengths, live flags and batch maps (null: one batch, one draft length).
+// `skip_hits_without_drafts`: the single-batch loop launches no k_bs_hits at dl == 0; the pool always launches it.
+static int enqueue_hits_leaves(ttx_session* s, hipStream_t st, int MC, int n_cand, int N, int dl, int K, const ttx_beam_params& p,
+                               bool smart, const BeamPoolArgs* pool, bool skip_hits_without_drafts) {
+  const int V = s->m->cfg.vocab_size;
+  BeamHitsArgs ha{};
+  ha.logits = s->logits.as<float>(); ha.V = V; ha.finished = s->bs_fin.as<uint8_t>(); ha.slot_of = s->t_slot_of.as<int>();
+  ha.per_cand = s->bs_per_cand.as<int>(); ha.drafts32 = s->drafts.as<int>();
+  ha.n_cand = n_cand; ha.N = N; ha.dl = dl; ha.K = K; ha.nucleus = 0.9975f; ha.hit = s->bs_hit.as<uint8_t>();
+  BeamLeaves2Args le{};
+  le.logits = s->logits.as<float>(); le.V = V; le.finished = s->bs_fin.as<uint8_t>(); le.slot_of = s->t_slot_of.as<int>();
+  le.per_cand = s->bs_per_cand.as<int>(); le.drafts32 = s->drafts.as<int>(); le.logp = s->bs_logp.as<float>();
+  le.hit = s->bs_hit.as<uint8_t>(); le.cnt = s->bs_cnt.as<BeamCounters>();
+  le.n_cand = n_cand; le.N = N; le.dl = dl; le.K = K; le.bos = p.bos_token; le.pad = p.pad_token; le.smart = smart ? 1 : 0;
+  le.best_n = s->bs_best_n.as<int>(); le.best_slot = s->bs_best_slot.as<int>(); le.chosen = s->bs_chosen.as<int64_t>();
+  le.leaf_score = s->leaf_score.as<float>(); le.leaf_tok = s->leaf_tok.as<int>(); le.leaf_cnt = s->leaf_cnt.as<int>();
+  if (pool) {
+    ha.dl_of = pool->cand_dl;
+    le.live = pool->live; le.dl_of = pool->cand_dl; le.grp_of = pool->bat_grp; le.cand_batch = pool->cand_batch;
+  }
+  const dim3 hits_grid(MC, cdiv(std::max(N * dl, 1), BS_HITS_WAVES));
+  const size_t leaves_lds = (size_t)2 * (dl + 1) * 4;
+  const bool hits = dl > 0 || !skip_hits_without_drafts;
+  const auto launch = [&](auto vpl) {
+    constexpr int VPL = decltype(vpl)::value;
+    if (hits) hipLaunchKernelGGL(k_bs_hits<VPL>, hits_grid, dim3(BS_HITS_WAVES * 64), 0, st, ha);
+    hipLaunchKernelGGL(k_bs_leaves<VPL>, dim3(MC), dim3(BS_LEAVES_THREADS), leaves_lds, st, le);
+  };
+  // logits per lane the selection keeps in registers: the smallest of 4 / 8 / 16 that covers the vocabulary (same results)
+  if (V <= 256) launch(std::integral_constant<int, 4>{});
+  else if (V <= 512) launch(std::integral_constant<int, 8>{});
+  else launch(std::integral_constant<int, NUC_VPL>{});
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
 // The kernels of one iteration, in order, as a function of the job's scalars alone (so that the sequence can be captured
 // once per shape and replayed).  `first`: no cache to derive (every candidate is a fresh <BOS> row); `cur`: which of the
 // two cache buffers holds the parents' caches.
 static int beam_enqueue_iter(const BeamJob& j, bool first, int cur) {
   ttx_session* s = j.s;
   hipStream_t st = j.st;
-  const ttx_model* m = s->m;
-  const ttx_config& c = m->cfg;
-  const int d = c.embedding_dim, Ld = c.num_decoder_layers, V = c.vocab_size;
   const int dl = j.dl, MC = j.max_cand;
-  const long long cache_seq = (long long)j.Lc * d, cache_layer = (long long)MC * cache_seq;
   BeamPrepArgs pa{};
-  pa.cand_next = s->bs_cand_next.as<int64_t>(); pa.ld = j.gen_ld; pa.len_next = s->bs_len_next.as<int>();
-  pa.fin_next = s->bs_fin_next.as<uint8_t>(); pa.logp_next = s->bs_logp_next.as<float>();
-  pa.n_cand = j.n_cand; pa.beam = j.beam; pa.dl = dl; pa.N = j.N; pa.pad = j.p.pad_token;
+  pa.ld = j.gen_ld; pa.n_cand = j.n_cand; pa.beam = j.beam; pa.dl = dl; pa.N = j.N; pa.pad = j.p.pad_token;
   pa.smart = j.smart ? 1 : 0; pa.n_lib = j.n_lib; pa.lib_ld = j.lib_ld;
   pa.drafts_all = s->bs_drafts_src.as<int>(); pa.D0 = j.D0; pa.lib = s->bs_drafts_src.as<int>();
-  pa.gen = s->gen.as<int>(); pa.front = s->front.as<int>(); pa.len = s->bs_len.as<int>(); pa.active = s->bs_active.as<uint8_t>();
-  pa.finished = s->bs_fin.as<uint8_t>(); pa.logp = s->bs_logp.as<float>(); pa.per_cand = s->bs_per_cand.as<int>();
-  pa.drafts32 = s->drafts.as<int>();
-  hipLaunchKernelGGL(k_bs_prep, dim3(MC), dim3(256), 0, st, pa);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_bs_src_of, dim3(cdiv(MC, 256)), dim3(256), 0, st, s->t_src_of.as<int>(), MC, j.beam);
-  HIP_TRY(hipGetLastError());
-  const int nxt = cur ^ 1;
-  if (!first) {
-    TreeCacheArgs ca{};
-    ca.len = s->bs_len.as<int>(); ca.parent = s->bs_parent.as<int>(); ca.parent_draft = s->bs_parent_draft.as<int>();
-    ca.prev_len = s->t_prev_len.as<int>(); ca.active = s->bs_active.as<uint8_t>();
-    ca.k_old = s->tk[cur].as<float>(); ca.v_old = s->tv[cur].as<float>();
-    ca.k_new = s->tk[nxt].as<float>(); ca.v_new = s->tv[nxt].as<float>();
-    ca.cache_layer_stride = cache_layer; ca.cache_seq_stride = cache_seq;
-    ca.qkv_prev = s->qkv.as<float>();
-    ca.qkv_layer_stride = (long long)MC * step_rps(j.N, j.prev_dl) * 3 * d;
-    ca.prev_slot_of = s->t_slot_of.as<int>(); ca.prev_N = j.N; ca.prev_D = j.prev_dl; ca.d = d;
-    hipLaunchKernelGGL(k_tree_cache, dim3(MC, Ld), dim3(256), 0, st, ca);
-    HIP_TRY(hipGetLastError());
-  }
-  BeamListArgs la{};
-  la.active = s->bs_active.as<uint8_t>(); la.per_cand = s->bs_per_cand.as<int>(); la.len = s->bs_len.as<int>();
-  la.n_cand = j.n_cand; la.N = j.N; la.dl = dl;
-  la.act_idx = s->act_idx.as<int>(); la.slot_of = s->t_slot_of.as<int>(); la.prev_len = s->t_prev_len.as<int>();
-  la.st = s->state.as<DecState>(); la.cnt = s->bs_cnt.as<BeamCounters>(); la.summary = s->beam_summary.as<int>();
-  hipLaunchKernelGGL(k_bs_list, dim3(1), dim3(256), 0, st, la);
-  HIP_TRY(hipGetLastError());
-  // the verify step: D+1 new positions per (running candidate, draft slot) on the candidate's KV cache
-  StepCtx k{};
-  k.B = MC; k.Ls = j.Ls; k.N = j.N; k.D = dl; k.Lc = j.Lc; k.gen_ld = j.gen_ld; k.max_len = j.p.max_len;
-  k.kcache = s->tk[nxt].as<float>(); k.vcache = s->tv[nxt].as<float>(); k.src_of = s->t_src_of.as<int>(); k.want_argmax = false;
-  k.variant = j.variant;
-  TTX_TRY(run_step(s, st, k, std::min(j.p.max_len, ((j.width + 63) / 64) * 64)));
-  BeamHitsArgs ha{};
-  ha.logits = s->logits.as<float>(); ha.V = V; ha.finished = s->bs_fin.as<uint8_t>(); ha.slot_of = s->t_slot_of.as<int>();
-  ha.per_cand = s->bs_per_cand.as<int>(); ha.drafts32 = s->drafts.as<int>();
-  ha.n_cand = j.n_cand; ha.N = j.N; ha.dl = dl; ha.K = j.K; ha.nucleus = 0.9975f; ha.hit = s->bs_hit.as<uint8_t>();
-  BeamLeaves2Args le{};
-  le.logits = s->logits.as<float>(); le.V = V; le.finished = s->bs_fin.as<uint8_t>(); le.slot_of = s->t_slot_of.as<int>();
-  le.per_cand = s->bs_per_cand.as<int>(); le.drafts32 = s->drafts.as<int>(); le.logp = s->bs_logp.as<float>();
-  le.hit = s->bs_hit.as<uint8_t>(); le.cnt = s->bs_cnt.as<BeamCounters>();
-  le.n_cand = j.n_cand; le.N = j.N; le.dl = dl; le.K = j.K; le.bos = j.p.bos_token; le.pad = j.p.pad_token; le.smart = j.smart ? 1 : 0;
-  le.best_n = s->bs_best_n.as<int>(); le.best_slot = s->bs_best_slot.as<int>(); le.chosen = s->bs_chosen.as<int64_t>();
-  le.leaf_score = s->leaf_score.as<float>(); le.leaf_tok = s->leaf_tok.as<int>(); le.leaf_cnt = s->leaf_cnt.as<int>();
-  const dim3 hits_grid(MC, cdiv(std::max(j.N * dl, 1), BS_HITS_WAVES));
-  const size_t leaves_lds = (size_t)2 * (dl + 1) * 4;
-  // logits per lane the selection keeps in registers: the smallest of 4 / 8 / 16 that covers the vocabulary (same results)
-  if (V <= 256) {
-    if (dl > 0) hipLaunchKernelGGL(k_bs_hits<4>, hits_grid, dim3(BS_HITS_WAVES * 64), 0, st, ha);
-    hipLaunchKernelGGL(k_bs_leaves<4>, dim3(MC), dim3(BS_LEAVES_THREADS), leaves_lds, st, le);
-  } else if (V <= 512) {
-    if (dl > 0) hipLaunchKernelGGL(k_bs_hits<8>, hits_grid, dim3(BS_HITS_WAVES * 64), 0, st, ha);
-    hipLaunchKernelGGL(k_bs_leaves<8>, dim3(MC), dim3(BS_LEAVES_THREADS), leaves_lds, st, le);
-  } else {
-    if (dl > 0) hipLaunchKernelGGL(k_bs_hits<NUC_VPL>, hits_grid, dim3(BS_HITS_WAVES * 64), 0, st, ha);
-    hipLaunchKernelGGL(k_bs_leaves<NUC_VPL>, dim3(MC), dim3(BS_LEAVES_THREADS), leaves_lds, st, le);
-  }
-  HIP_TRY(hipGetLastError());
+  TTX_TRY(enqueue_bs_prep(s, st, MC, pa));
+  if (!first) TTX_TRY(enqueue_tree_cache(s, st, MC, j.Lc, cur, cur ^ 1, nullptr, nullptr, j.N, j.prev_dl));
+  TTX_TRY(enqueue_bs_list(s, st, j.n_cand, j.N, dl));
+  TTX_TRY(run_step(s, st, tree_step_ctx(s, MC, j.Ls, j.N, dl, j.Lc, j.gen_ld, j.p.max_len, cur ^ 1, j.variant),
+                   key_capacity(j.width, j.p.max_len)));
+  TTX_TRY(enqueue_hits_leaves(s, st, MC, j.n_cand, j.N, dl, j.K, j.p, j.smart, nullptr, true));
   BeamSelectArgs<int> sa{s->leaf_score.as<float>(), s->leaf_tok.as<int>(), s->leaf_cnt.as<int>(), s->gen.as<int>(), j.gen_ld, j.gen_ld,
                          j.gen_ld, s->bs_len.as<int>(), s->bs_chosen.as<int64_t>(), s->bs_best_slot.as<int>(), s->bs_fin.as<uint8_t>(),
                          j.B, j.beam, dl, j.K, j.p.pad_token, j.p.eos_token, s->bs_cand_next.as<int64_t>(), s->bs_logp_next.as<float>(),
                          s->bs_parent.as<int>(), s->bs_parent_draft.as<int>(), s->bs_mark.as<int>(), s->beam_summary.as<int>(),
                          s->bs_len_next.as<int>(), s->bs_fin_next.as<uint8_t>()};
   const size_t lds = 2 * (size_t)j.beam * (dl + 1) * j.K * 4;
-  if (lds > 64 * 1024 && !s->attr_select) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_beam_select<int>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    s->attr_select = true;
-  }
+  TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_beam_select<int>), lds, s->attr_select));
   hipLaunchKernelGGL(k_beam_select<int>, dim3(j.B), dim3(256), lds, st, sa);
   HIP_TRY(hipGetLastError());
   BeamHost* dev_host = nullptr;
@@ -1987,8 +2026,7 @@ static int beam_enqueue_iter(const BeamJob& j, bool first, int cur) {
   return TTX_OK;
 }
 
-// Enqueue one iteration (the loop condition of :464 / :652 was checked by the caller): replay the captured graph of this
-// shape, capturing it on its second use (the first use runs eagerly: function attributes are set outside capture).
+// Enqueue one iteration (the loop condition of :464 / :652 was checked by the caller) through graph_replay, one graph per shape.
 static int beam_launch_iter(BeamJob& j) {
   ttx_session* s = j.s;
   j.dl = std::min(j.room, j.dl);                                   // :476
@@ -1996,47 +2034,15 @@ static int beam_launch_iter(BeamJob& j) {
   if (grow > 0) j.width += grow;
   const bool first = j.launched == 0;
   const int cur = j.cur;
-  const int kcap = std::min(j.p.max_len, ((j.width + 63) / 64) * 64);
   j.variant = variant_for_rows(s, (long long)std::max(1, j.n_cand - j.n_eos) * step_rps(j.N, j.dl), true);
-  int rc = TTX_OK;
-  if (!s->use_graphs || s->profile) {
-    rc = beam_enqueue_iter(j, first, cur);
-  } else {
-    s->graphs_current();
-    const std::vector<int> key{j.B, j.Ls, j.K, j.N, j.D0, j.smart ? 1 : 0, j.p.max_len, j.n_cand, j.beam, j.dl, j.prev_dl, cur, kcap,
-                               first ? 1 : 0, j.p.pad_token, j.p.bos_token, j.p.eos_token, j.variant};
-    auto it = s->beam_graphs.find(key);
-    if (it == s->beam_graphs.end() && !s->beam_warmed.count(key)) {
-      s->beam_warmed.insert(key);
-      rc = beam_enqueue_iter(j, first, cur);
-    } else {
-      if (it == s->beam_graphs.end()) {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        const auto cap0 = std::chrono::steady_clock::now();
-        HIP_TRY(hipStreamBeginCapture(j.st, hipStreamCaptureModeThreadLocal));
-        rc = beam_enqueue_iter(j, first, cur);
-        hipError_t e = hipStreamEndCapture(j.st, &graph);
-        if (rc != TTX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (e != hipSuccess) return fail(TTX_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (e != hipSuccess) return fail(TTX_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-        if (s->beam_graphs.size() > 256) s->drop_graphs();
-        it = s->beam_graphs.emplace(key, exec).first;
-        s->host_captures += 1;
-        s->host_capture_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - cap0).count();
-      }
-      HIP_TRY(hipGraphLaunch(it->second, j.st));
-    }
-  }
-  TTX_TRY(rc);
+  const GraphKey key{GS_BEAM_ITER, j.B, j.Ls, j.K, j.N, j.D0, j.smart ? 1 : 0, j.p.max_len, j.n_cand, j.beam, j.dl, j.prev_dl, cur,
+                     key_capacity(j.width, j.p.max_len), first ? 1 : 0, j.p.pad_token, j.p.bos_token, j.p.eos_token, j.variant};
+  TTX_TRY(graph_replay(s, j.st, s->iter_graphs, key, [&]() -> int { return beam_enqueue_iter(j, first, cur); }));
   ++j.launched;
   j.cur = cur ^ 1;
   j.prev_dl = j.dl;
   j.any_iteration = true;
-  j.last_progress = std::chrono::steady_clock::now();
-  j.idle_spins = 0;
+  j.progress.advanced();
   return TTX_OK;
 }
 
@@ -2141,7 +2147,7 @@ extern "C" int ttx_beam_speculative_generate_many(ttx_session** sessions, int n_
         progressed = true;
       } else if (j.phase == 1) {
         if (s->beam_host->steps_done < j.launched) {               // the iteration in flight has not published yet
-          if ((++j.idle_spins & 0xffff) == 0 && watchdog_expired(j.last_progress)) { hung = true; fail_all(session_hung(s)); break; }
+          if (j.progress.stalled()) { hung = true; fail_all(session_hung(s)); break; }
           continue;
         }
         int rc = TTX_OK;
@@ -2197,8 +2203,7 @@ struct BeamPoolJob {
   int admitted_since = 0;           // sources admitted since the last published iteration
   int quota_b = -1;                 // serial (profiling) pass: end (batch index) of this pool's share of the work list
   long long src_tokens_padded = 0, admitted_rows = 0;
-  unsigned idle_spins = 0;
-  std::chrono::steady_clock::time_point last_progress = std::chrono::steady_clock::now();
+  Progress progress;
 };
 
 static int bpool_start(BeamPoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_cap, const ttx_beam_params* p, const BeamPoolIo& io_host,
@@ -2336,71 +2341,22 @@ static int bpool_admit(BeamPoolJob& j, const int64_t* d_src_rows, int ld_src, in
   return TTX_OK;
 }
 
-static int bpool_enqueue_iter(const BeamPoolJob& j, int cur, int variant) {
+static int bpool_enqueue_iter(const BeamPoolJob& j, int variant) {
   ttx_session* s = j.s;
   hipStream_t st = j.st;
-  const ttx_config& c = s->m->cfg;
-  const int d = c.embedding_dim, Ld = c.num_decoder_layers, V = c.vocab_size;
   const int dl = j.D0, MC = j.MC;
-  const long long cache_seq = (long long)j.Lc * d, cache_layer = (long long)MC * cache_seq;
   hipLaunchKernelGGL(k_bsp_prep, dim3(MC), dim3(256), 0, st, j.a);
   HIP_TRY(hipGetLastError());
-  const int nxt = cur ^ 1;
-  (void)nxt;
-  TreeCacheArgs ca{};
-  ca.len = s->bs_len.as<int>(); ca.parent = s->bs_parent.as<int>(); ca.parent_draft = s->bs_parent_draft.as<int>();
-  ca.prev_len = s->t_prev_len.as<int>(); ca.active = s->bs_active.as<uint8_t>();
-  // ONE cache buffer and a candidate -> slot map (k_bsp_select): most children append in their parent's slot, few copy
-  ca.k_old = s->tk[0].as<float>(); ca.v_old = s->tv[0].as<float>(); ca.k_new = s->tk[0].as<float>(); ca.v_new = s->tv[0].as<float>();
-  ca.slot_parent = j.a.cache_slot_parent; ca.slot_self = j.a.cache_slot;
-  ca.cache_layer_stride = cache_layer; ca.cache_seq_stride = cache_seq;
-  ca.qkv_prev = s->qkv.as<float>(); ca.qkv_layer_stride = (long long)MC * step_rps(j.N, dl) * 3 * d;
-  ca.prev_slot_of = s->t_slot_of.as<int>(); ca.prev_N = j.N; ca.prev_D = dl; ca.d = d;
-  hipLaunchKernelGGL(k_tree_cache, dim3(MC, Ld), dim3(256), 0, st, ca);      // fresh candidates (parent -1) have nothing to inherit
-  HIP_TRY(hipGetLastError());
-  BeamListArgs la{};
-  la.active = s->bs_active.as<uint8_t>(); la.per_cand = s->bs_per_cand.as<int>(); la.len = s->bs_len.as<int>();
-  la.n_cand = MC; la.N = j.N; la.dl = dl;
-  la.act_idx = s->act_idx.as<int>(); la.slot_of = s->t_slot_of.as<int>(); la.prev_len = s->t_prev_len.as<int>();
-  la.st = s->state.as<DecState>(); la.cnt = s->bs_cnt.as<BeamCounters>(); la.summary = s->beam_summary.as<int>();
-  hipLaunchKernelGGL(k_bs_list, dim3(1), dim3(256), 0, st, la);
-  HIP_TRY(hipGetLastError());
-  StepCtx k{};
-  k.B = MC; k.Ls = j.Ls_cap; k.N = j.N; k.D = dl; k.Lc = j.Lc; k.gen_ld = j.gen_ld; k.max_len = j.p.max_len;
-  k.kcache = s->tk[0].as<float>(); k.vcache = s->tv[0].as<float>(); k.cache_slot = j.a.cache_slot;
-  k.src_of = s->t_src_of.as<int>(); k.src_len = s->bp_cand_len.as<int>();
-  k.want_argmax = false; k.variant = variant;
-  TTX_TRY(run_step(s, st, k, std::min(j.p.max_len, ((j.p.max_len + 63) / 64) * 64)));
-  BeamHitsArgs ha{};
-  ha.logits = s->logits.as<float>(); ha.V = V; ha.finished = s->bs_fin.as<uint8_t>(); ha.slot_of = s->t_slot_of.as<int>();
-  ha.per_cand = s->bs_per_cand.as<int>(); ha.drafts32 = s->drafts.as<int>();
-  ha.n_cand = MC; ha.N = j.N; ha.dl = dl; ha.K = j.K; ha.nucleus = 0.9975f; ha.hit = s->bs_hit.as<uint8_t>(); ha.dl_of = j.a.cand_dl;
-  BeamLeaves2Args le{};
-  le.logits = s->logits.as<float>(); le.V = V; le.finished = s->bs_fin.as<uint8_t>(); le.slot_of = s->t_slot_of.as<int>();
-  le.per_cand = s->bs_per_cand.as<int>(); le.drafts32 = s->drafts.as<int>(); le.logp = s->bs_logp.as<float>();
-  le.hit = s->bs_hit.as<uint8_t>(); le.cnt = s->bs_cnt.as<BeamCounters>();
-  le.n_cand = MC; le.N = j.N; le.dl = dl; le.K = j.K; le.bos = j.p.bos_token; le.pad = j.p.pad_token; le.smart = j.smart ? 1 : 0;
-  le.best_n = s->bs_best_n.as<int>(); le.best_slot = s->bs_best_slot.as<int>(); le.chosen = s->bs_chosen.as<int64_t>();
-  le.leaf_score = s->leaf_score.as<float>(); le.leaf_tok = s->leaf_tok.as<int>(); le.leaf_cnt = s->leaf_cnt.as<int>();
-  le.live = s->bs_mark.as<uint8_t>(); le.dl_of = j.a.cand_dl; le.grp_of = j.a.bat_grp; le.cand_batch = j.a.cand_batch;
-  const dim3 hits_grid(MC, cdiv(std::max(j.N * dl, 1), BS_HITS_WAVES));
-  const size_t leaves_lds = (size_t)2 * (dl + 1) * 4;
-  if (V <= 256) {
-    hipLaunchKernelGGL(k_bs_hits<4>, hits_grid, dim3(BS_HITS_WAVES * 64), 0, st, ha);
-    hipLaunchKernelGGL(k_bs_leaves<4>, dim3(MC), dim3(BS_LEAVES_THREADS), leaves_lds, st, le);
-  } else if (V <= 512) {
-    hipLaunchKernelGGL(k_bs_hits<8>, hits_grid, dim3(BS_HITS_WAVES * 64), 0, st, ha);
-    hipLaunchKernelGGL(k_bs_leaves<8>, dim3(MC), dim3(BS_LEAVES_THREADS), leaves_lds, st, le);
-  } else {
-    hipLaunchKernelGGL(k_bs_hits<NUC_VPL>, hits_grid, dim3(BS_HITS_WAVES * 64), 0, st, ha);
-    hipLaunchKernelGGL(k_bs_leaves<NUC_VPL>, dim3(MC), dim3(BS_LEAVES_THREADS), leaves_lds, st, le);
-  }
-  HIP_TRY(hipGetLastError());
+  // ONE cache buffer and a candidate -> slot map (k_bsp_select): most children append in their parent's slot, few copy; fresh
+  // candidates (parent -1) have nothing to inherit
+  TTX_TRY(enqueue_tree_cache(s, st, MC, j.Lc, 0, 0, j.a.cache_slot_parent, j.a.cache_slot, j.N, dl));
+  TTX_TRY(enqueue_bs_list(s, st, MC, j.N, dl));
+  StepCtx k = tree_step_ctx(s, MC, j.Ls_cap, j.N, dl, j.Lc, j.gen_ld, j.p.max_len, 0, variant);
+  k.cache_slot = j.a.cache_slot; k.src_len = s->bp_cand_len.as<int>();
+  TTX_TRY(run_step(s, st, k, key_capacity(j.p.max_len, j.p.max_len)));
+  TTX_TRY(enqueue_hits_leaves(s, st, MC, MC, j.N, dl, j.K, j.p, j.smart, &j.a, false));
   const size_t lds = 2 * (size_t)j.K * (dl + 1) * j.K * 4;
-  if (lds > 64 * 1024 && !s->attr_pool_select) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bsp_select), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    s->attr_pool_select = true;
-  }
+  TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_bsp_select), lds, s->attr_pool_select));
   hipLaunchKernelGGL(k_bsp_select, dim3(j.C), dim3(256), lds, st, j.a);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_bsp_batches, dim3(cdiv(j.C, 256)), dim3(256), 0, st, j.a);
@@ -2412,43 +2368,14 @@ static int bpool_enqueue_iter(const BeamPoolJob& j, int cur, int variant) {
 
 static int bpool_launch_iter(BeamPoolJob& j, int n_running) {
   ttx_session* s = j.s;
-  const int cur = j.cur;
   const int variant = variant_for_rows(s, (long long)std::max(1, n_running) * step_rps(j.N, j.D0), true);
-  int rc = TTX_OK;
-  if (!s->use_graphs || s->profile) {
-    rc = bpool_enqueue_iter(j, cur, variant);
-  } else {
-    s->graphs_current();
-    const std::vector<int> key{-7, j.C, j.Ls_cap, j.K, j.N, j.D0, j.smart ? 1 : 0, j.p.max_len, cur, variant, j.p.pad_token, j.p.bos_token,
-                               j.p.eos_token, j.p.replace_token, j.p.max_steps};
-    auto it = s->beam_graphs.find(key);
-    if (it == s->beam_graphs.end() && !s->beam_warmed.count(key)) {
-      s->beam_warmed.insert(key);                  // first use runs eagerly: function attributes are set outside capture
-      rc = bpool_enqueue_iter(j, cur, variant);
-    } else {
-      if (it == s->beam_graphs.end()) {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        HIP_TRY(hipStreamBeginCapture(j.st, hipStreamCaptureModeThreadLocal));
-        rc = bpool_enqueue_iter(j, cur, variant);
-        hipError_t e = hipStreamEndCapture(j.st, &graph);
-        if (rc != TTX_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (e != hipSuccess) return fail(TTX_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (e != hipSuccess) return fail(TTX_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-        if (s->beam_graphs.size() > 256) s->drop_graphs();
-        it = s->beam_graphs.emplace(key, exec).first;
-      }
-      HIP_TRY(hipGraphLaunch(it->second, j.st));
-    }
-  }
-  TTX_TRY(rc);
+  const GraphKey key{GS_BEAM_POOL_ITER, j.C, j.Ls_cap, j.K, j.N, j.D0, j.smart ? 1 : 0, j.p.max_len, j.cur, variant, j.p.pad_token,
+                     j.p.bos_token, j.p.eos_token, j.p.replace_token, j.p.max_steps};
+  TTX_TRY(graph_replay(s, j.st, s->iter_graphs, key, [&]() -> int { return bpool_enqueue_iter(j, variant); }));
   ++j.launched;
-  j.cur = cur ^ 1;
+  j.cur ^= 1;
   j.admitted_since = 0;
-  j.last_progress = std::chrono::steady_clock::now();
-  j.idle_spins = 0;
+  j.progress.advanced();
   return TTX_OK;
 }
 
@@ -2520,7 +2447,7 @@ extern "C" int ttx_beam_speculative_generate_pool(ttx_session** sessions, int n_
       volatile BeamPoolHost* bh = s->bp_host;
       if (j.phase == 1) {
         if (j.launched > 0 && bh->steps_done < j.launched) {                  // the iteration in flight has not published yet
-          if ((++j.idle_spins & 0xffff) == 0 && watchdog_expired(j.last_progress)) { rc_final = session_hung(s); hung = true; break; }
+          if (j.progress.stalled()) { rc_final = session_hung(s); hung = true; break; }
           continue;
         }
         if (bh->error) { rc_final = fail(TTX_ERR_HIP, "batch pool bookkeeping failed (admitted more sources than free slots)"); break; }
@@ -2682,45 +2609,16 @@ static int beam_generate_impl(ttx_session* s, const int64_t* d_src, int B, int L
                      MC, B, p->bos_token, p->pad_token, s->bs_cnt.as<BeamCounters>());
   HIP_TRY(hipGetLastError());
 
-  const long long cache_seq = (long long)Lc * d, cache_layer = (long long)MC * cache_seq;
   int n_cand = B, beam = 1, width = 1, cur = 0, launched = 0, n_eos = 0;
   const int max_iters = max_len - 1;                 // the <BOS> step plus `predictions - 1` loop iterations (:127-131)
   auto enqueue = [&](bool first) -> int {
     BeamPrepArgs pa{};
-    pa.cand_next = s->bs_cand_next.as<int64_t>(); pa.ld = ld; pa.len_next = s->bs_len_next.as<int>();
-    pa.fin_next = s->bs_fin_next.as<uint8_t>(); pa.logp_next = s->bs_logp_next.as<float>();
-    pa.n_cand = n_cand; pa.beam = beam; pa.dl = 0; pa.N = 1; pa.pad = p->pad_token; pa.smart = 0;
-    pa.gen = s->gen.as<int>(); pa.front = s->front.as<int>(); pa.len = s->bs_len.as<int>(); pa.active = s->bs_active.as<uint8_t>();
-    pa.finished = s->bs_fin.as<uint8_t>(); pa.logp = s->bs_logp.as<float>(); pa.per_cand = s->bs_per_cand.as<int>();
-    pa.drafts32 = s->drafts.as<int>();
-    hipLaunchKernelGGL(k_bs_prep, dim3(MC), dim3(256), 0, st, pa);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_bs_src_of, dim3(cdiv(MC, 256)), dim3(256), 0, st, s->t_src_of.as<int>(), MC, beam);
-    HIP_TRY(hipGetLastError());
-    const int nxt = cur ^ 1;
-    if (!first) {
-      TreeCacheArgs ca{};
-      ca.len = s->bs_len.as<int>(); ca.parent = s->bs_parent.as<int>(); ca.parent_draft = s->bs_parent_draft.as<int>();
-      ca.prev_len = s->t_prev_len.as<int>(); ca.active = s->bs_active.as<uint8_t>();
-      ca.k_old = s->tk[cur].as<float>(); ca.v_old = s->tv[cur].as<float>(); ca.k_new = s->tk[nxt].as<float>(); ca.v_new = s->tv[nxt].as<float>();
-      ca.cache_layer_stride = cache_layer; ca.cache_seq_stride = cache_seq;
-      ca.qkv_prev = s->qkv.as<float>(); ca.qkv_layer_stride = (long long)MC * 3 * d;
-      ca.prev_slot_of = s->t_slot_of.as<int>(); ca.prev_N = 1; ca.prev_D = 0; ca.d = d;
-      hipLaunchKernelGGL(k_tree_cache, dim3(MC, Ld), dim3(256), 0, st, ca);
-      HIP_TRY(hipGetLastError());
-    }
-    BeamListArgs la{};
-    la.active = s->bs_active.as<uint8_t>(); la.per_cand = s->bs_per_cand.as<int>(); la.len = s->bs_len.as<int>();
-    la.n_cand = n_cand; la.N = 1; la.dl = 0;
-    la.act_idx = s->act_idx.as<int>(); la.slot_of = s->t_slot_of.as<int>(); la.prev_len = s->t_prev_len.as<int>();
-    la.st = s->state.as<DecState>(); la.cnt = s->bs_cnt.as<BeamCounters>(); la.summary = s->beam_summary.as<int>();
-    hipLaunchKernelGGL(k_bs_list, dim3(1), dim3(256), 0, st, la);
-    HIP_TRY(hipGetLastError());
-    StepCtx k{};
-    k.B = MC; k.Ls = Ls; k.N = 1; k.D = 0; k.Lc = Lc; k.gen_ld = ld; k.max_len = max_len;
-    k.kcache = s->tk[nxt].as<float>(); k.vcache = s->tv[nxt].as<float>(); k.src_of = s->t_src_of.as<int>(); k.want_argmax = false;
-    k.variant = variant_for_rows(s, (long long)std::max(1, n_cand - n_eos), true);
-    TTX_TRY(run_step(s, st, k, std::min(max_len, ((width + 63) / 64) * 64)));
+    pa.ld = ld; pa.n_cand = n_cand; pa.beam = beam; pa.dl = 0; pa.N = 1; pa.pad = p->pad_token; pa.smart = 0;
+    TTX_TRY(enqueue_bs_prep(s, st, MC, pa));
+    if (!first) TTX_TRY(enqueue_tree_cache(s, st, MC, Lc, cur, cur ^ 1, nullptr, nullptr, 1, 0));
+    TTX_TRY(enqueue_bs_list(s, st, n_cand, 1, 0));
+    const int variant = variant_for_rows(s, (long long)std::max(1, n_cand - n_eos), true);
+    TTX_TRY(run_step(s, st, tree_step_ctx(s, MC, Ls, 1, 0, Lc, ld, max_len, cur ^ 1, variant), key_capacity(width, max_len)));
     BeamStepArgs sa{};
     sa.logits = s->logits.as<float>(); sa.V = V; sa.slot_of = s->t_slot_of.as<int>(); sa.finished = s->bs_fin.as<uint8_t>();
     sa.score = s->bs_logp.as<float>(); sa.gen = s->gen.as<int>(); sa.ld = ld; sa.width = width;
@@ -2729,10 +2627,7 @@ static int beam_generate_impl(ttx_session* s, const int64_t* d_src, int B, int L
     sa.new_len = s->bs_len_next.as<int>(); sa.new_finished = s->bs_fin_next.as<uint8_t>(); sa.parent_draft = s->bs_parent_draft.as<int>();
     sa.summary = s->beam_summary.as<int>();
     const size_t lds = (size_t)beam * V * 4;
-    if (lds > 64 * 1024 && !s->attr_step) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_beam_step), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      s->attr_step = true;
-    }
+    TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_beam_step), lds, s->attr_step));
     hipLaunchKernelGGL(k_beam_step, dim3(B), dim3(256), lds, st, sa);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_bs_publish, dim3(1), dim3(64), 0, st, s->beam_summary.as<int>(), dev_host, s->bs_cnt.as<BeamCounters>());
@@ -2747,10 +2642,9 @@ static int beam_generate_impl(ttx_session* s, const int64_t* d_src, int B, int L
     TTX_TRY(enqueue(first));
     ++launched;
     cur ^= 1;
-    unsigned spins = 0;
-    const auto since = std::chrono::steady_clock::now();
+    Progress wait;
     while (bh->steps_done < launched) {
-      if ((++spins & 0xffff) == 0 && watchdog_expired(since)) return session_hung(s);
+      if (wait.stalled()) return session_hung(s);
       __builtin_ia32_pause();
     }
     width += 1;

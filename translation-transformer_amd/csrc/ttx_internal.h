@@ -1,6 +1,8 @@
 // Host-side types shared by the translation units of libttx_hip.so (ttx_api.hip: C ABI, runtime, loop kernels;
-// ttx_gemm.hip: GEMM family; ttx_attn.hip: attention family).  Kernels are launched from the unit that defines them;
-// the other units reach them through the launchers declared at the bottom.
+// ttx_gemm.hip: GEMM family; ttx_attn.hip: attention family): the model and its weight layout, the session with its
+// workspaces (declared once, in TTX_SESSION_BUFS) and its two caches of captured graphs (GraphCache, keyed by GraphKey).
+// Kernels are launched from the unit that defines them; the other units reach them through the launchers declared at the
+// bottom.
 #pragma once
 #include "ttx.h"
 #include "ttx_common.hip.h"
@@ -8,7 +10,6 @@
 #include <map>
 #include <set>
 #include <string>
-#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -68,52 +69,75 @@ enum GemmKernelId { GK_GEMM3 = 1, GK_GEMM_TN = 2, GK_GEMM24_4 = 3, GK_GEMM24_0 =
 // Kernel of an attention launch as ttx_debug_attn selects and reports it (include/ttx.h).
 enum AttnKernelId { AK_ATTN = 1, AK_ATTN2 = 2, AK_ATTN3 = 3, AK_ATTN3S = 4 };
 
-struct GraphKey {
-  int B, Ls, N, D, max_len, mode, kcap, variant;   // mode: 0 speculative, 1 plain greedy, 2 per-row rule, 3 slot pool
-  int phase = 0;                                   // slot pool: 0 the whole step in one pass, 1 probe, 2 draft pass + accept, 3 accept alone
-  bool operator<(const GraphKey& o) const {
-    return std::tie(B, Ls, N, D, max_len, mode, kcap, variant, phase) <
-           std::tie(o.B, o.Ls, o.N, o.D, o.max_len, o.mode, o.kcap, o.variant, o.phase);
+// Key of a captured launch sequence: the GraphSite that enqueues it, then every scalar the sequence depends on, in the order
+// the site lists them (the device pointers it bakes in are covered by ttx_session::alloc_generation).
+//   verify step (GS_STEP_*)       B, Ls, N, D, max_len, key capacity, GemmVariant, phase (slot pool: 0 the whole step in one pass,
+//                                 1 probe, 2 draft pass + accept, 3 accept alone; else 0)
+//   GS_BEAM_ITER, GS_BEAM_POOL_ITER   see beam_launch_iter / bpool_launch_iter
+enum GraphSite { GS_STEP_SPECULATIVE = 0, GS_STEP_GREEDY = 1, GS_STEP_ROW_RULE = 2, GS_STEP_POOL = 3, GS_BEAM_ITER = 4, GS_BEAM_POOL_ITER = 5 };
+typedef std::vector<int> GraphKey;
+
+// Captured graphs of one family of keys.  A key runs eagerly the first time it is seen (`warmed`: function attributes are set
+// outside capture), is captured the second time and replayed from then on; once `map` holds more than `limit` graphs the
+// session drops all it has (ttx_session::drop_graphs).
+struct GraphCache {
+  std::map<GraphKey, hipGraphExec_t> map;
+  std::set<GraphKey> warmed;
+  size_t limit;
+  explicit GraphCache(size_t limit_) : limit(limit_) {}
+  void clear() {
+    for (auto& kv : map) (void)hipGraphExecDestroy(kv.second);
+    map.clear(); warmed.clear();
   }
 };
+
+// Every workspace of a session, each name once: ttx_session expands the list to its Buf members and to the loop that registers
+// them (a buffer that is not registered would never bump alloc_generation when it grows, and a captured graph would keep its old
+// address).
+#define TTX_SESSION_BUFS(X)                                                                                                      \
+  /* activations (shared by encoder / full decoder / step) */                                                                    \
+  X(x) X(x1) X(x2) X(xf) X(ao) X(q2) X(hbuf) X(slab) X(qkv) X(logits) X(ckv)                                                      \
+  /* sources */                                                                                                                  \
+  X(tok_src) X(src_valid) X(memory) X(memkv)                                                                                     \
+  /* full decoder */                                                                                                             \
+  X(tok_tgt) X(mem_pad_tmp)                                                                                                      \
+  /* teacher-forced evaluation (ttx_teacher_forced_eval / ttx_token_metrics): logits / argmax / nll the caller did not ask for */ \
+  X(ev_logits) X(ev_pred) X(ev_nll)                                                                                              \
+  /* hypothesis scoring (ttx_score_hypotheses): decoder row -> memory row; logits / per-token values it does not hand out live */ \
+  /* in ev_logits / ev_nll */                                                                                                    \
+  X(sc_src_of)                                                                                                                   \
+  /* loop */                                                                                                                     \
+  X(drafts) X(gen) X(front) X(act_idx) X(rec) X(pred) X(state) X(kcache) X(vcache) X(src32) X(outbuf) X(haspad) X(traj)           \
+  X(fin_step)                                                                                                                    \
+  /* slot pool (continuous batching) */                                                                                          \
+  X(rstep) X(row_of) X(src_len) X(new_slot) X(pool_io) X(memkv_new) X(valid_new) X(drafts_new)                                    \
+  /* two-phase verify step of the slot pool: the probe's QKV rows [Ld][C][3d] and argmax [C], the draft pass's argmax, the */     \
+  /* list of matching sequences, slot -> position in it, and {DecState probe, DecState draft pass, int executed rows} */          \
+  X(qkv_probe) X(pred_probe) X(pred_draft) X(act2) X(pos2) X(state2)                                                             \
+  /* snapshot of one verify step for the logits parity test (ttx_gen_params.want_logits) */                                      \
+  X(snap_logits) X(snap_act) X(snap_front) X(snap_gen) X(snap_state)                                                             \
+  X(leaf_score) X(leaf_tok) X(leaf_cnt) X(beam_summary)                                                                          \
+  /* native beam-speculative loop */                                                                                             \
+  X(bs_cand_next) X(bs_len_next) X(bs_fin_next) X(bs_logp_next) X(bs_len) X(bs_fin) X(bs_active) X(bs_logp) X(bs_per_cand)        \
+  X(bs_best_n) X(bs_best_slot) X(bs_chosen) X(bs_parent) X(bs_parent_draft) X(bs_mark) X(bs_drafts_src) X(bs_cnt) X(bs_hit)       \
+  /* tree (beam) decoding, beside tk[2] / tv[2] */                                                                               \
+  X(t_prev_len) X(t_slot_of) X(t_src_of)                                                                                         \
+  /* beam-speculative source pool (continuous batching over sources of many batches) */                                          \
+  X(bp_row_of) X(bp_batch) X(bp_cand) X(bp_cand_len) X(bp_tok) X(bp_new_slot) X(bp_io) X(bp_grp) X(bp_src_acc) X(bp_enc_qkv)
+#define TTX_DECLARE_BUF(name) Buf name;
+#define TTX_REGISTER_BUF(name) all.push_back(&name);
 
 #ifndef TTX_BIG_MIN_TILES
 #define TTX_BIG_MIN_TILES 400
 #endif
 struct ttx_session {
   ttx_model* m;
-  std::vector<Buf*> all;
-  // activations (shared by encoder / full decoder / step)
-  Buf x, x1, x2, xf, ao, q2, hbuf, slab, qkv, logits, ckv;
-  // sources
-  Buf tok_src, src_valid, memory, memkv;
-  // full decoder
-  Buf tok_tgt, mem_pad_tmp;
-  // teacher-forced evaluation (ttx_teacher_forced_eval / ttx_token_metrics): logits / argmax / nll the caller did not ask for
-  Buf ev_logits, ev_pred, ev_nll;
-  // hypothesis scoring (ttx_score_hypotheses): decoder row -> memory row; logits / per-token values it does not hand out live in
-  // ev_logits / ev_nll
-  Buf sc_src_of;
-  // loop
-  Buf drafts, gen, front, act_idx, rec, pred, state, kcache, vcache, src32, outbuf, haspad, traj, fin_step;
-  // slot pool (continuous batching)
-  Buf rstep, row_of, src_len, new_slot, pool_io, memkv_new, valid_new, drafts_new;
-  // two-phase verify step of the slot pool: the probe's QKV rows [Ld][C][3d] and argmax [C], the draft pass's argmax, the list of
-  // matching sequences, slot -> position in it, and {DecState probe, DecState draft pass, int executed rows}
-  Buf qkv_probe, pred_probe, pred_draft, act2, pos2, state2;
+  std::vector<Buf*> all;           // every workspace below: the constructor registers them from the same list that declares them
+  TTX_SESSION_BUFS(TTX_DECLARE_BUF)
+  Buf tk[2], tv[2];                // tree (beam) decoding: the two cache buffers an iteration derives one from the other
+  int snap_B = 0, snap_rps = 0, snap_gen_ld = 0, snap_step = 0;        // what snap_* hold
   ttx::ProbeInfo* probe_info = nullptr; // pinned + device-mapped, written by k_probe_split
-  // snapshot of one verify step for the logits parity test (ttx_gen_params.want_logits)
-  Buf snap_logits, snap_act, snap_front, snap_gen, snap_state;
-  int snap_B = 0, snap_rps = 0, snap_gen_ld = 0, snap_step = 0;
-  Buf leaf_score, leaf_tok, leaf_cnt, beam_summary;
-  // native beam-speculative loop
-  Buf bs_cand_next, bs_len_next, bs_fin_next, bs_logp_next, bs_len, bs_fin, bs_active, bs_logp, bs_per_cand, bs_best_n, bs_best_slot,
-      bs_chosen, bs_parent, bs_parent_draft, bs_mark, bs_drafts_src, bs_cnt, bs_hit;
   ttx::BeamHost* beam_host = nullptr;   // pinned + device-mapped, written by k_bs_publish
-  // tree (beam) decoding
-  Buf tk[2], tv[2], t_prev_len, t_slot_of, t_src_of;
-  // beam-speculative source pool (continuous batching over sources of many batches)
-  Buf bp_row_of, bp_batch, bp_cand, bp_cand_len, bp_tok, bp_new_slot, bp_io, bp_grp, bp_src_acc, bp_enc_qkv;
   ttx::BeamPoolHost* bp_host = nullptr; // pinned + device-mapped, written by k_bsp_publish
   ttx::HostInfo* host_info = nullptr;   // pinned + device-mapped, written by the accept kernels
   hipStream_t own_stream = nullptr;     // the loops run on a session-owned stream (the caller's may be the null stream)
@@ -124,17 +148,10 @@ struct ttx_session {
   uint64_t graphs_generation = 0;
   bool dead = false;               // a verify step never published its result (watchdog): the stream may still be stuck
   bool use_graphs = true;
-  std::map<GraphKey, hipGraphExec_t> graphs;
-  std::set<GraphKey> warmed;
+  GraphCache step_graphs{512};     // one verify step (or one phase of a split pool step) per shape
+  GraphCache iter_graphs{256};     // one iteration of the beam-speculative loop / of the beam pool per shape
   hipEvent_t ev_done = nullptr;
-  std::map<std::vector<int>, hipGraphExec_t> beam_graphs;   // one iteration of the beam-speculative loop per shape
-  std::set<std::vector<int>> beam_warmed;
-  void drop_graphs() {
-    for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
-    graphs.clear(); warmed.clear();
-    for (auto& kv : beam_graphs) (void)hipGraphExecDestroy(kv.second);
-    beam_graphs.clear(); beam_warmed.clear();
-  }
+  void drop_graphs() { step_graphs.clear(); iter_graphs.clear(); }
   void graphs_current() { if (graphs_generation != alloc_generation) { drop_graphs(); graphs_generation = alloc_generation; } }
   ttx::DecState* host_state = nullptr;  // pinned copy target
   // function attributes (dynamic LDS limits) are per device: set once per session, outside graph capture
@@ -164,20 +181,15 @@ struct ttx_session {
   long long prof_launches = 0;
   bool host_timing = false;
   double host_launch_us = 0;
-  long long host_captures = 0;      // TTX_HOST_TIMING: iteration graphs captured on this session and the host time they took
+  long long host_captures = 0;      // TTX_HOST_TIMING: graphs captured on this session and the host time they took
   double host_capture_us = 0;
   long long host_launches = 0;
   hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;
-  ttx_session() { for (Buf* b : {&x, &x1, &x2, &xf, &ao, &q2, &hbuf, &slab, &qkv, &logits, &ckv, &tok_src, &src_valid, &memory,
-                                 &memkv, &tok_tgt, &mem_pad_tmp, &ev_logits, &ev_pred, &ev_nll, &sc_src_of, &drafts, &gen, &front, &act_idx, &rec, &pred, &state,
-                                 &kcache, &vcache, &src32, &outbuf, &haspad, &traj, &fin_step, &rstep, &row_of, &src_len, &new_slot,
-                                 &pool_io, &memkv_new, &valid_new, &drafts_new, &qkv_probe, &pred_probe, &pred_draft, &act2, &pos2, &state2, &tk[0], &tk[1], &tv[0], &tv[1],
-                                 &t_prev_len, &t_slot_of, &t_src_of,
-                                 &snap_logits, &snap_act, &snap_front, &snap_gen, &snap_state, &leaf_score, &leaf_tok, &leaf_cnt,
-                                 &beam_summary, &bs_cand_next, &bs_len_next, &bs_fin_next, &bs_logp_next, &bs_len, &bs_fin, &bs_active,
-                                 &bs_logp, &bs_per_cand, &bs_best_n, &bs_best_slot, &bs_chosen, &bs_parent, &bs_parent_draft, &bs_mark,
-                                 &bs_drafts_src, &bs_cnt, &bs_hit, &bp_row_of, &bp_batch, &bp_cand, &bp_cand_len, &bp_tok, &bp_new_slot,
-                                 &bp_io, &bp_grp, &bp_src_acc, &bp_enc_qkv}) { b->owner_gen = &alloc_generation; all.push_back(b); } }
+  ttx_session() {
+    TTX_SESSION_BUFS(TTX_REGISTER_BUF)
+    for (Buf* b : {&tk[0], &tk[1], &tv[0], &tv[1]}) all.push_back(b);
+    for (Buf* b : all) b->owner_gen = &alloc_generation;
+  }
 };
 
 namespace ttx {
