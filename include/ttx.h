@@ -546,6 +546,53 @@ int ttx_debug_probe_split(ttx_session* s, const int32_t* d_act_idx, const int32_
 int ttx_debug_merge_pred(ttx_session* s, const int32_t* d_pos2, const int32_t* d_pred_probe, const int32_t* d_pred2, int32_t* d_pred,
                          int B, int N, int D, int n_active, void* stream);
 
+/* Draft select (DESIGN.md "Two-phase verify step"): the draft pass of a split pool step runs, for every matching slot, row 0 and the D
+ * rows of each draft whose first token is the probe's prediction, stored compacted.  Per position p of the draft pass:
+ * draft_mask[p] (bit n: draft n is present, never 0) and row_base[p], the exclusive prefix sum of 1 + D * popcount(mask): the
+ * slot's row 0 lies at row_base[p], row 1 + n*D + (j-1) of a present draft at row_base[p] + 1 + rank(n)*D + (j-1) with rank(n) =
+ * popcount(mask & ((1 << n) - 1)).  The test entry points below (tests/test_gpu_draft_select.py) are those above with these
+ * operands; each reads them back and refuses (TTX_ERR_INVALID, nothing launched) a mask that is 0 or has bits at or beyond N, a
+ * row_base that is not that prefix sum, N > 32 or D < 1, one of the operands without the others, besides what its counterpart
+ * refuses.  With the draft-select operands all NULL each is its counterpart.
+ *
+ * ttx_debug_probe_split_select: ttx_debug_probe_split that also writes d_draft_mask, d_row_base [matches] and d_row_map [compacted
+ * rows]: compacted row -> layout row p * (1 + N*D) + rs.  result has 8 words: [2] = m_rows is the compacted total and [7] the row
+ * count published for the host; [3] stays n_active + matches * (1 + N*D).  Entries past the counts are not written. */
+int ttx_debug_probe_split_select(ttx_session* s, const int32_t* d_act_idx, const int32_t* d_pred_probe, const int32_t* d_drafts, int B,
+                                 int N, int D, int n_active, int32_t* d_act2, int32_t* d_pos2, int32_t* d_draft_mask, int32_t* d_row_base,
+                                 int32_t* d_row_map, int32_t* result, void* stream);
+/* ttx_debug_merge_pred_select: d_pred2 is compacted; an absent draft's rows of a matching slot read -1. */
+int ttx_debug_merge_pred_select(ttx_session* s, const int32_t* d_pos2, const int32_t* d_pred_probe, const int32_t* d_pred2,
+                                int32_t* d_pred, int B, int N, int D, int n_active, const int32_t* d_row_base,
+                                const int32_t* d_draft_mask, void* stream);
+/* ttx_debug_kvcopy_select: ttx_debug_kvcopy_split on a compacted d_qkv (its layer stride still covers B * (1 + N*D) rows).  Also
+ * refused: a record with n_acc > 0 whose best draft is absent from its slot's mask. */
+int ttx_debug_kvcopy_select(ttx_session* s, const int32_t* d_rec, int n_copy, const float* d_qkv, int64_t qkv_layer_stride,
+                            float* d_kcache, float* d_vcache, int64_t cache_layer_stride, int64_t cache_seq_stride, int N, int D, int d,
+                            int B, int Ld, const int32_t* d_pos2, const float* d_qkv_probe, int64_t probe_layer_stride,
+                            const int32_t* d_row_base, const int32_t* d_draft_mask, void* stream);
+/* ttx_debug_embed_select: the step mode of ttx_debug_embed writing m_rows rows, row i holding the token and position of layout row
+ * d_row_map[i].  Refused: m_rows outside [0, n_active * (1 + N*D)], a map entry outside the live slots' layout rows. */
+int ttx_debug_embed_select(ttx_session* s, const float* d_table, int V, const float* d_pe, int pe_rows, int d, float* d_x,
+                           const int32_t* d_act_idx, const int32_t* d_front, const int32_t* d_gen, int gen_ld, const int32_t* d_drafts,
+                           int B, int N, int D, int n_active, const int32_t* d_row_map, int m_rows, void* stream);
+/* ttx_debug_attn_select: a step-mode launch (mode 3 or 4) of ttx_debug_attn at head dimension 32 on compacted q / k / v / out rows;
+ * kernel is 0, 3 (k_attn3) or 4 (k_attn3s).  Stored rows equal, bit for bit, the same rows of the full-layout launch. */
+int ttx_debug_attn_select(ttx_session* s, const float* d_q, int ldq, const float* d_k, const float* d_v, int ldkv, float* d_out, int H,
+                          float scale, int Lk, const int32_t* d_tok, int pad, const uint8_t* d_key_pad, const int32_t* d_act_idx,
+                          const int32_t* d_front, const int32_t* d_src_of, const int32_t* d_src_len, const float* d_kcache,
+                          const float* d_vcache, int64_t cache_seq_stride, const int32_t* d_cache_slot, int gen_ld, int N, int D, int mode,
+                          int groups, int n_active, int max_keys, int kernel, int32_t* kernel_id, const int32_t* d_row_base,
+                          const int32_t* d_draft_mask, void* stream);
+
+/* Counters of the last ttx_greedy_speculative_generate_pool call whose FIRST session was `s`, summed over its pools, into a HOST
+ * array of 7 int64: [0] steps, [1] split steps, [2] slot-steps probed, [3] slots matched, [4] drafts run by the draft passes (under
+ * draft select the matching ones, else N per matching slot), [5] rows sent through the decoder by all steps (probes and one-pass
+ * steps included), [6] 1 when the call ran under draft select, 0 when its draft passes ran every draft (TTX_DRAFT_SELECT=0, or a
+ * model whose step attention runs on k_attn2 / k_attn).  ttx_gen_stats.verified_positions keeps counting the positions of matching
+ * slots whether their rows ran or not. */
+int ttx_pool_last_counters(ttx_session* s, int64_t* counters);
+
 /* Host query, no device needed: the number of keys one k_attn2 workgroup can stage at head dimension head_dim when a group has
  * q_per_group query rows (up to 32 rows share one query image, more take the 64-row one): 384 at head dimension 32, 320 at 64;
  * 0 for a head dimension without kernels.  A launch whose key count (step self-attention: cache capacity + 1 + the draft rows

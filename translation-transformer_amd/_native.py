@@ -174,6 +174,14 @@ SYMBOLS = {
                                          C.c_int64, _VP]),
     "ttx_debug_probe_split": (C.c_int, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, C.POINTER(C.c_int32), _VP]),
     "ttx_debug_merge_pred": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP]),
+    "ttx_debug_probe_split_select": (C.c_int, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_int32), _VP]),
+    "ttx_debug_merge_pred_select": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP]),
+    "ttx_debug_kvcopy_select": (C.c_int, [_VP, _VP, _I, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int64, _I, _I, _I, _I, _I, _VP, _VP,
+                                          C.c_int64, _VP, _VP, _VP]),
+    "ttx_debug_embed_select": (C.c_int, [_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _I, _VP, _I, _I, _I, _I, _VP, _I, _VP]),
+    "ttx_debug_attn_select": (C.c_int, [_VP, _VP, _I, _VP, _VP, _I, _VP, _I, C.c_float, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                        C.c_int64, _VP, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), _VP, _VP, _VP]),
+    "ttx_pool_last_counters": (C.c_int, [_VP, C.POINTER(C.c_int64)]),
     "ttx_attn_staged_key_limit": (C.c_int, [_I, _I]),
     "ttx_last_kernel_profile": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
 }

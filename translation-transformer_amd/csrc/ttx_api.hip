@@ -800,6 +800,8 @@ struct StepCtx {
   float* qkv_ov = nullptr;         // [Ld][B * RPS][3d]
   int* pred_ov = nullptr;          // [B * RPS]
   int sel_N = 0, sel_D = 0;        // probe: the layout of the draft pass, whose choice between k_attn2 and k_attn it takes
+  // draft select (draft pass of a split step; all null otherwise): the pass's rows are stored compacted (k_probe_split)
+  const int* row_base = nullptr; const int* draft_mask = nullptr; const int* row_map = nullptr;
 };
 
 static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) {
@@ -826,7 +828,7 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
   EmbedArgs e{};
   e.table = m->p(m->tgt_emb); e.pe = m->p(m->pe); e.X = s->x.as<float>(); e.d = d; e.V = c.vocab_size;
   e.st = dst; e.act_idx = act; e.front = s->front.as<int>(); e.gen = s->gen.as<int>(); e.gen_ld = k.gen_ld;
-  e.drafts = s->drafts.as<int>(); e.N = k.N; e.D = k.D;
+  e.drafts = s->drafts.as<int>(); e.N = k.N; e.D = k.D; e.row_map = k.row_map;
   hipLaunchKernelGGL((k_embed<true>), dim3(cdiv(Mmax, 4)), dim3(256), 0, st, e);
   HIP_TRY(hipGetLastError());
 
@@ -840,6 +842,7 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
         a.kcache = (k.kcache ? k.kcache : s->kcache.as<float>()) + (size_t)l * cache_layer;
         a.vcache = (k.vcache ? k.vcache : s->vcache.as<float>()) + (size_t)l * cache_layer;
         a.cache_seq_stride = cache_seq; a.gen_ld = k.gen_ld; a.N = k.N; a.D = k.D; a.cache_slot = k.cache_slot;
+        a.row_base = k.row_base; a.draft_mask = k.draft_mask;
         return launch_attn(ATT_STEP_SELF, s, st, a, k.B, H, RPS, kcap, k.N, D1);
       },
       [&](int l) -> int {
@@ -847,7 +850,7 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
         ca.q = s->q2.as<float>(); ca.ldq = d; ca.k = s->memkv.as<float>() + (size_t)l * 2 * d; ca.v = ca.k + d; ca.ldkv = Ld * 2 * d;
         ca.out = ao; ca.d = d; ca.scale = scale; ca.Lk = k.Ls; ca.key_pad = s->src_valid.as<uint8_t>();
         ca.st = dst; ca.act_idx = act; ca.front = s->front.as<int>(); ca.N = k.N; ca.D = k.D;
-        ca.src_of = k.src_of; ca.src_len = k.src_len;
+        ca.src_of = k.src_of; ca.src_len = k.src_len; ca.row_base = k.row_base; ca.draft_mask = k.draft_mask;
         return launch_attn(ATT_STEP_CROSS, s, st, ca, k.B, H, RPS, k.Ls, k.N, D1);
       },
       logits));
@@ -1268,6 +1271,11 @@ struct PoolJob {
   int probes = 0;           // probes launched
   bool probe_pending = false;   // a probe is in flight; the step's second graph follows once it has published
   long long slot_steps = 0, matched_slot_steps = 0, split_steps = 0, skipped_draft_passes = 0;   // TTX_TWO_PHASE_STATS=1
+  // draft select: the draft pass runs row 0 and the drafts whose first token matched, stored compacted
+  bool draft_select = false;
+  long long drafts_matched = 0;     // drafts run by the draft passes (draft select: the matching ones; else N per matching slot)
+  long long rows_executed = 0;      // rows every step of this pool sent through the decoder, probes included
+  long long unsplit_rows = 0;       // ... of which in steps that ran in one pass
 };
 
 static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_cap, const ttx_gen_params* p, int64_t* d_out,
@@ -1309,8 +1317,17 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
   // read at the start of every pool call
   j.two_phase = true; j.min_rows = 800; j.probes = 0; j.probe_pending = false;
   j.slot_steps = j.matched_slot_steps = j.split_steps = j.skipped_draft_passes = 0;
+  j.drafts_matched = j.rows_executed = j.unsplit_rows = 0;
   if (const char* e = getenv("TTX_TWO_PHASE")) j.two_phase = atoi(e) != 0;
   if (const char* e = getenv("TTX_TWO_PHASE_MIN_ROWS")) j.min_rows = std::max(0, atoi(e));
+  // draft select needs the compacted-row mapping, which k_attn3 / k_attn3s have: head dimension 32, H % 4 == 0.  Models whose step
+  // attention runs on k_attn2 / k_attn keep the all-drafts pass.
+  j.draft_select = j.two_phase && d == c.num_heads * ATT_DH && c.num_heads % 4 == 0 && !s->attn_fallback && N <= 32 && D >= 1;
+  if (const char* e = getenv("TTX_DRAFT_SELECT")) j.draft_select = j.draft_select && atoi(e) != 0;
+  if (j.draft_select) {
+    for (Buf* b : {&s->draft_mask, &s->row_base}) TTX_TRY(ensure(*b, (size_t)C * 4, st));
+    TTX_TRY(ensure(s->row_map, Mmax * 4, st));
+  }
   if (j.two_phase) {                                              // nothing may allocate inside a capture
     TTX_TRY(ensure(s->qkv_probe, (size_t)Ld * C * 3 * d * 4, st));
     for (Buf* b : {&s->pred_probe, &s->act2, &s->pos2}) TTX_TRY(ensure(*b, (size_t)C * 4, st));
@@ -1323,7 +1340,7 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
   HIP_TRY(hipEventRecord(s->ev_a, st));
   if (j.two_phase) {
     HIP_TRY(hipMemsetAsync(s->state2.p, 0, 3 * sizeof(DecState), st));
-    s->probe_info->matches = 0; s->probe_info->probes_done = 0;
+    s->probe_info->matches = 0; s->probe_info->probes_done = 0; s->probe_info->rows = 0;
     HIP_TRY(hipHostGetDevicePointer((void**)&j.dev_probe, (void*)s->probe_info, 0));
   }
   j.io = PoolIo{d_out, d_traj, d_fin, max_len + 1, 0};        // lives in the job until every stream has drained
@@ -1348,6 +1365,7 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
   if (j.two_phase) {
     j.g2.la.exec_rows = reinterpret_cast<const int*>(s->state2.as<DecState>() + 2);
     j.g2.kc.pos2 = s->pos2.as<int>(); j.g2.kc.qkv_probe = s->qkv_probe.as<float>(); j.g2.kc.probe_layer_stride = (long long)C * 3 * d;
+    if (j.draft_select) { j.g2.kc.row_base = s->row_base.as<int>(); j.g2.kc.draft_mask = s->draft_mask.as<int>(); }
   }
   s->host_info->stop = 0; s->host_info->steps_done = 0; s->host_info->width = 1; s->host_info->n_active = 0;
   hipLaunchKernelGGL(k_pool_init, dim3(4), dim3(256), 0, st, g.la);
@@ -1415,6 +1433,7 @@ static int pool_launch_step(PoolJob& j, int n_live) {
       return launch_accept_and_commit(s, j.st, j.g, false);
     }));
     ++j.launched;
+    j.rows_executed += rows; j.unsplit_rows += rows;
     return TTX_OK;
   }
   DecState* st2 = s->state2.as<DecState>();          // [0] probe, [1] draft pass, then the executed-row count
@@ -1422,7 +1441,7 @@ static int pool_launch_step(PoolJob& j, int n_live) {
   kp.N = 1; kp.D = 0; kp.sel_N = k.N; kp.sel_D = k.D;
   kp.st_ov = st2; kp.qkv_ov = s->qkv_probe.as<float>(); kp.pred_ov = s->pred_probe.as<int>();
   kp.variant = variant_for_rows(s, n_live, true);
-  TTX_TRY(graph_replay(s, j.st, s->step_graphs, pool_key(k, kp.variant, 1), [&]() -> int {
+  TTX_TRY(graph_replay(s, j.st, s->step_graphs, pool_key(k, kp.variant, j.draft_select ? 4 : 1), [&]() -> int {
     hipLaunchKernelGGL(k_probe_begin, dim3(1), dim3(64), 0, j.st, s->state.as<DecState>(), st2);
     HIP_TRY(hipGetLastError());
     TTX_TRY(run_step(s, j.st, kp, kcap));
@@ -1431,13 +1450,14 @@ static int pool_launch_step(PoolJob& j, int n_live) {
     ps.drafts = s->drafts.as<int>(); ps.N = k.N; ps.D = k.D; ps.act2 = s->act2.as<int>(); ps.pos2 = s->pos2.as<int>();
     ps.st2 = st2 + 1; ps.exec_rows = reinterpret_cast<int*>(st2 + 2);
     ps.host = j.dev_probe;
+    if (j.draft_select) { ps.draft_mask = s->draft_mask.as<int>(); ps.row_base = s->row_base.as<int>(); ps.row_map = s->row_map.as<int>(); }
     hipLaunchKernelGGL(k_probe_split, dim3(1), dim3(k.B > 256 ? ACCEPT_THREADS : 256), 0, j.st, ps);
     HIP_TRY(hipGetLastError());
     return TTX_OK;
   }));
   ++j.probes;
   j.probe_pending = true;
-  j.split_steps += 1; j.slot_steps += n_live;
+  j.split_steps += 1; j.slot_steps += n_live; j.rows_executed += n_live;
   return TTX_OK;
 }
 
@@ -1450,15 +1470,23 @@ static int pool_launch_drafts(PoolJob& j) {
   const int matches = ((volatile ProbeInfo*)s->probe_info)->matches;
   if (matches < 0 || matches > k.B) return fail(TTX_ERR_HIP, "slot pool: the probe published a match count outside the pool");
   const int RPS = step_rps(k.N, k.D);
+  // rows of the draft pass: under draft select the compacted count the probe published, else every row of the matching slots
+  const long long rows = j.draft_select ? ((volatile ProbeInfo*)s->probe_info)->rows : (long long)matches * RPS;
+  if (rows < (long long)matches * (matches ? 1 + k.D : 0) || rows > (long long)matches * RPS)
+    return fail(TTX_ERR_HIP, "slot pool: the probe published a row count outside its matches' rows");
   DecState* st2 = s->state2.as<DecState>();
   k.st_ov = st2 + 1; k.act_ov = s->act2.as<int>(); k.pred_ov = s->pred_draft.as<int>();
-  k.variant = matches ? variant_for_rows(s, (long long)matches * RPS, true) : 0;
+  if (j.draft_select) { k.row_base = s->row_base.as<int>(); k.draft_mask = s->draft_mask.as<int>(); k.row_map = s->row_map.as<int>(); }
+  k.variant = matches ? variant_for_rows(s, rows, true) : 0;
   j.matched_slot_steps += matches; j.skipped_draft_passes += matches ? 0 : 1;
-  TTX_TRY(graph_replay(s, j.st, s->step_graphs, pool_key(k, k.variant, matches ? 2 : 3), [&]() -> int {
+  j.rows_executed += rows; j.drafts_matched += (rows - matches) / k.D;
+  const int phase = j.draft_select ? (matches ? 5 : 6) : (matches ? 2 : 3);
+  TTX_TRY(graph_replay(s, j.st, s->step_graphs, pool_key(k, k.variant, phase), [&]() -> int {
     if (matches) TTX_TRY(run_step(s, j.st, k, kcap));
     MergePredArgs mp{};
     mp.st = s->state.as<DecState>(); mp.pos2 = s->pos2.as<int>(); mp.pred_probe = s->pred_probe.as<int>();
     mp.pred2 = s->pred_draft.as<int>(); mp.pred = s->pred.as<int>(); mp.RPS = RPS;
+    mp.row_base = k.row_base; mp.draft_mask = k.draft_mask; mp.D = k.D;
     hipLaunchKernelGGL(k_merge_pred, dim3(cdiv(k.B * RPS, 256)), dim3(256), 0, j.st, mp);
     HIP_TRY(hipGetLastError());
     return launch_accept_and_commit(s, j.st, j.g2, false);
@@ -1500,12 +1528,15 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
   const int C = std::min(capacity, std::max(1, cdiv(R_total, n_jobs)));      // never more slots than a fair share of the rows
   std::vector<PoolJob> jobs(n_jobs);
   int rc_final = TTX_OK;
+  std::fill(std::begin(sessions[0]->pool_counters), std::end(sessions[0]->pool_counters), 0LL);
   for (int i = 0; i < n_jobs && rc_final == TTX_OK; ++i) {
     ttx_session* s = sessions[i];
     TTX_TRY(ensure_own_stream(s));
     HIP_TRY(hipStreamWaitEvent(s->own_stream, ready, 0));
     rc_final = pool_start(jobs[i], s, s->own_stream, C, Ls_cap, p, d_out, d_traj, d_fin_step);
   }
+  // every pool of a call has the same model and reads the same environment: the mode is the call's
+  sessions[0]->pool_counters[6] = jobs[0].draft_select ? 1 : 0;
   const int min_admit = std::max(1, C / 4);                    // admissions of at least a quarter pool (or into an empty one)
   const bool serial = sessions[0]->profile;
   int cursor = 0, done = 0;
@@ -1599,8 +1630,15 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
             if (hipEventElapsedTime(&ms, s->ev_a, s->ev_c) == hipSuccess) stats->decode_ms += ms;
           }
           if (getenv("TTX_TWO_PHASE_STATS"))
-            fprintf(stderr, "[ttx two-phase] pool %d: %d steps, %lld split (%lld without a draft pass), %lld slot-steps probed, %lld matched\n",
-                    i, j.launched, j.split_steps, j.skipped_draft_passes, j.slot_steps, j.matched_slot_steps);
+            fprintf(stderr, "[ttx two-phase] pool %d: %d steps, %lld split (%lld without a draft pass), %lld slot-steps probed, %lld matched, "
+                            "%lld draft rows executed, %lld drafts matched\n",      // draft select off: N drafts per matching slot
+                    i, j.launched, j.split_steps, j.skipped_draft_passes, j.slot_steps, j.matched_slot_steps,
+                    j.rows_executed - j.slot_steps - j.unsplit_rows, j.drafts_matched);
+          {
+            long long* pc = sessions[0]->pool_counters;
+            pc[0] += j.launched; pc[1] += j.split_steps; pc[2] += j.slot_steps; pc[3] += j.matched_slot_steps;
+            pc[4] += j.drafts_matched; pc[5] += j.rows_executed;
+          }
           if (hs.error == 3 && rc_final == TTX_OK)
             rc_final = fail(TTX_ERR_ROW_REPLAY, "a row emitted PAD inside its sequence: decode the batches as given");
           else if (hs.error && rc_final == TTX_OK)
@@ -2828,6 +2866,58 @@ extern "C" int ttx_debug_attn(ttx_session* s, const float* d_q, int ldq, const f
                            max_keys, kernel, kernel_id, stream);
 }
 
+// Draft select (tests/test_gpu_draft_select.py): the per-position operands of a compacted draft pass, read back and checked as the
+// other index arrays of the test entry points are.  mask[p] is a non-zero subset of the N drafts and row_base the exclusive prefix
+// sum of 1 + D * popcount(mask); hands back the compacted row count.
+static int dbg_check_select(const std::string& who, const int32_t* d_row_base, const int32_t* d_draft_mask, int n, int N, int D,
+                            hipStream_t st, std::vector<int32_t>* mask_out, int* total) {
+  *total = 0;
+  if (!d_row_base || !d_draft_mask) return fail(TTX_ERR_INVALID, who + ": row_base and draft_mask are required");
+  if (N < 1 || N > 32 || D < 1) return fail(TTX_ERR_INVALID, who + ": draft select needs 1 <= N <= 32 and D >= 1");
+  std::vector<int32_t> base((size_t)std::max(n, 1)), mask((size_t)std::max(n, 1));
+  if (n > 0) {
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(base.data(), d_row_base, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mask.data(), d_draft_mask, (size_t)n * 4, hipMemcpyDeviceToHost));
+  }
+  int sum = 0;
+  for (int p = 0; p < n; ++p) {
+    const unsigned m = (unsigned)mask[p];
+    if (m == 0u || (N < 32 && (m >> N))) return fail(TTX_ERR_INVALID, who + ": a listed slot's draft mask must be a non-zero subset of the N drafts");
+    if (base[p] != sum) return fail(TTX_ERR_INVALID, who + ": row_base must be the exclusive prefix sum of 1 + D * popcount(mask)");
+    sum += step_sel_rows(m, D);
+  }
+  mask.resize((size_t)n);
+  if (mask_out) *mask_out = mask;
+  *total = sum;
+  return TTX_OK;
+}
+
+extern "C" int ttx_debug_attn_select(ttx_session* s, const float* d_q, int ldq, const float* d_k, const float* d_v, int ldkv, float* d_out,
+                                     int H, float scale, int Lk, const int32_t* d_tok, int pad, const uint8_t* d_key_pad,
+                                     const int32_t* d_act_idx, const int32_t* d_front, const int32_t* d_src_of, const int32_t* d_src_len,
+                                     const float* d_kcache, const float* d_vcache, int64_t cache_seq_stride, const int32_t* d_cache_slot,
+                                     int gen_ld, int N, int D, int mode, int groups, int n_active, int max_keys, int kernel,
+                                     int32_t* kernel_id, const int32_t* d_row_base, const int32_t* d_draft_mask, void* stream) {
+  if (!s) return fail(TTX_ERR_INVALID, "null session");
+  if (mode != ATT_STEP_SELF && mode != ATT_STEP_CROSS) return fail(TTX_ERR_INVALID, "ttx_debug_attn_select: a step mode (3 or 4) is required");
+  if (kernel != 0 && kernel != AK_ATTN3 && kernel != AK_ATTN3S)
+    return fail(TTX_ERR_INVALID, "ttx_debug_attn_select: draft select runs on k_attn3 (3) or k_attn3s (4); 0 chooses between them");
+  if (n_active < 0 || n_active > groups) return fail(TTX_ERR_INVALID, "ttx_debug_attn_select: n_active must lie in [0, groups]");
+  HIP_TRY(hipSetDevice(s->m->device));
+  if ((d_row_base != nullptr) != (d_draft_mask != nullptr))
+    return fail(TTX_ERR_INVALID, "ttx_debug_attn_select: row_base and draft_mask come together");
+  int total = 0;
+  if (d_row_base)
+    TTX_TRY(dbg_check_select("ttx_debug_attn_select", d_row_base, d_draft_mask, n_active, N, D, reinterpret_cast<hipStream_t>(stream), nullptr, &total));
+  AttnArgs a{};
+  a.q = d_q; a.ldq = ldq; a.k = d_k; a.v = d_v; a.ldkv = ldkv; a.out = d_out; a.scale = scale; a.Lk = Lk;
+  a.tok = d_tok; a.pad = pad; a.key_pad = d_key_pad; a.act_idx = d_act_idx; a.front = d_front;
+  a.src_of = d_src_of; a.src_len = d_src_len; a.kcache = d_kcache; a.vcache = d_vcache; a.cache_seq_stride = (long long)cache_seq_stride;
+  a.cache_slot = d_cache_slot; a.gen_ld = gen_ld; a.N = N; a.D = D; a.row_base = d_row_base; a.draft_mask = d_draft_mask;
+  return attn_debug(s, a, H, 32, mode, groups, n_active, max_keys, kernel, kernel_id, reinterpret_cast<hipStream_t>(stream));
+}
+
 // ------------------------------------------------------------------------------------------------
 // Test entry points of the loop kernels (tests/test_gpu_loop_kernels.py): ONE launch of k_argmax, k_embed, k_accept /
 // k_greedy_accept or k_kvcopy with production's grid and block rules on the caller's device operands.  What the kernels take on
@@ -2875,10 +2965,11 @@ extern "C" int ttx_debug_argmax(ttx_session* s, const float* d_logits, int V, in
   return TTX_OK;
 }
 
-extern "C" int ttx_debug_embed(ttx_session* s, const float* d_table, int V, const float* d_pe, int pe_rows, int d, float* d_x,
-                               const int32_t* d_tok, int rows, int L, const int32_t* d_act_idx, const int32_t* d_front,
-                               const int32_t* d_gen, int gen_ld, const int32_t* d_drafts, int B, int N, int D, int n_active, int step,
-                               void* stream) {
+// d_row_map (ttx_debug_embed_select; null: ttx_debug_embed): the launch writes m_rows rows, row i holding layout row d_row_map[i]
+static int embed_debug(ttx_session* s, const float* d_table, int V, const float* d_pe, int pe_rows, int d, float* d_x,
+                       const int32_t* d_tok, int rows, int L, const int32_t* d_act_idx, const int32_t* d_front,
+                       const int32_t* d_gen, int gen_ld, const int32_t* d_drafts, int B, int N, int D, int n_active, int step,
+                       const int32_t* d_row_map, int m_rows, void* stream) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (!s || !d_table || !d_pe || !d_x) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_embed");
   if (!dbg_model_d(d)) return fail(TTX_ERR_INVALID, "ttx_debug_embed: d must be 64, 128, 256, 512 or 1024");
@@ -2903,15 +2994,24 @@ extern "C" int ttx_debug_embed(ttx_session* s, const float* d_table, int V, cons
   TTX_TRY(dbg_check_slots("ttx_debug_embed", d_act_idx, d_front, B, n_active, gen_ld, D, st, &max_front));
   if (n_active > 0 && pe_rows < max_front + D + 2) return fail(TTX_ERR_INVALID, "ttx_debug_embed: the positional table must have front + D + 2 rows");
   const int RPS = step_rps(N, D);
+  if (d_row_map) {
+    if (m_rows < 0 || m_rows > n_active * RPS) return fail(TTX_ERR_INVALID, "ttx_debug_embed_select: m_rows must lie in [0, n_active * (1 + N*D)]");
+    std::vector<int32_t> map((size_t)std::max(m_rows, 1));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (m_rows > 0) HIP_TRY(hipMemcpy(map.data(), d_row_map, (size_t)m_rows * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < m_rows; ++i)
+      if (map[i] < 0 || map[i] >= n_active * RPS) return fail(TTX_ERR_INVALID, "ttx_debug_embed_select: row_map must hold layout rows of the live slots");
+  }
   // the live row count reaches the kernel as production hands it over: in a DecState on the device, written on the launch's stream
   DecState* dst = nullptr;
   HIP_TRY(hipMalloc((void**)&dst, sizeof(DecState)));
   DecState* hs = reinterpret_cast<DecState*>(s->host_state);
   *hs = DecState{};
-  hs->n_active = n_active; hs->r_rows = n_active * N; hs->m_rows = n_active * RPS;
+  hs->n_active = n_active; hs->r_rows = n_active * N; hs->m_rows = d_row_map ? m_rows : n_active * RPS;
   hipError_t err = hipMemcpyAsync(dst, hs, sizeof(DecState), hipMemcpyHostToDevice, st);
   if (err == hipSuccess) {
     e.st = dst; e.act_idx = d_act_idx; e.front = d_front; e.gen = d_gen; e.gen_ld = gen_ld; e.drafts = d_drafts; e.N = N; e.D = D;
+    e.row_map = d_row_map;
     hipLaunchKernelGGL((k_embed<true>), dim3(cdiv(B * RPS, 4)), dim3(256), 0, st, e);
     err = hipGetLastError();
   }
@@ -2920,6 +3020,22 @@ extern "C" int ttx_debug_embed(ttx_session* s, const float* d_table, int V, cons
   HIP_TRY(err);
   HIP_TRY(esync);
   return TTX_OK;
+}
+
+extern "C" int ttx_debug_embed(ttx_session* s, const float* d_table, int V, const float* d_pe, int pe_rows, int d, float* d_x,
+                               const int32_t* d_tok, int rows, int L, const int32_t* d_act_idx, const int32_t* d_front,
+                               const int32_t* d_gen, int gen_ld, const int32_t* d_drafts, int B, int N, int D, int n_active, int step,
+                               void* stream) {
+  return embed_debug(s, d_table, V, d_pe, pe_rows, d, d_x, d_tok, rows, L, d_act_idx, d_front, d_gen, gen_ld, d_drafts, B, N, D, n_active,
+                     step, nullptr, 0, stream);
+}
+
+extern "C" int ttx_debug_embed_select(ttx_session* s, const float* d_table, int V, const float* d_pe, int pe_rows, int d, float* d_x,
+                                      const int32_t* d_act_idx, const int32_t* d_front, const int32_t* d_gen, int gen_ld,
+                                      const int32_t* d_drafts, int B, int N, int D, int n_active, const int32_t* d_row_map, int m_rows,
+                                      void* stream) {
+  return embed_debug(s, d_table, V, d_pe, pe_rows, d, d_x, nullptr, 0, 0, d_act_idx, d_front, d_gen, gen_ld, d_drafts, B, N, D, n_active, 1,
+                     d_row_map, m_rows, stream);
 }
 
 extern "C" int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, int64_t* state, void* stream) {
@@ -3018,8 +3134,10 @@ extern "C" int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, 
 
 static int kvcopy_debug(const char* who, ttx_session* s, const int32_t* d_rec, int n_copy, const float* d_qkv, int64_t qkv_layer_stride,
                         float* d_kcache, float* d_vcache, int64_t cache_layer_stride, int64_t cache_seq_stride, int N, int D, int d, int B,
-                        int Ld, const int32_t* d_pos2, const float* d_qkv_probe, int64_t probe_layer_stride, hipStream_t st) {
+                        int Ld, const int32_t* d_pos2, const float* d_qkv_probe, int64_t probe_layer_stride, hipStream_t st,
+                        const int32_t* d_row_base = nullptr, const int32_t* d_draft_mask = nullptr) {
   const std::string w(who);
+  if ((d_row_base || d_draft_mask) && !d_pos2) return fail(TTX_ERR_INVALID, w + ": row_base and draft_mask need pos2");
   if (!s || !d_rec || !d_qkv || !d_kcache || !d_vcache) return fail(TTX_ERR_INVALID, "null argument to " + w);
   if (!dbg_model_d(d)) return fail(TTX_ERR_INVALID, w + ": d must be 64, 128, 256, 512 or 1024");
   if (B < 1 || Ld < 1 || N < 1 || D < 0) return fail(TTX_ERR_INVALID, w + ": B, Ld and N must be positive, D >= 0");
@@ -3049,6 +3167,15 @@ static int kvcopy_debug(const char* who, ttx_session* s, const int32_t* d_rec, i
       if (d_pos2 && (pos[i] < -1 || pos[i] >= B || (pos[i] < 0 && r.nacc != 0)))
         return fail(TTX_ERR_INVALID, w + ": pos2 must lie in [-1, B), and a slot without a draft pass (-1) accepts nothing");
     }
+    if (d_row_base || d_draft_mask) {
+      int n_pos = 0, total = 0;
+      for (int i = 0; i < n_copy; ++i) n_pos = std::max(n_pos, pos[i] + 1);
+      std::vector<int32_t> mask;
+      TTX_TRY(dbg_check_select(w, d_row_base, d_draft_mask, n_pos, N, D, st, &mask, &total));
+      for (int i = 0; i < n_copy; ++i)
+        if (pos[i] >= 0 && rec[i].nacc > 0 && !(((unsigned)mask[pos[i]] >> rec[i].best) & 1u))
+          return fail(TTX_ERR_INVALID, w + ": the best draft of a slot that accepted tokens must be a present one");
+    }
   }
   DecState* dst = nullptr;
   HIP_TRY(hipMalloc((void**)&dst, sizeof(DecState)));
@@ -3062,6 +3189,7 @@ static int kvcopy_debug(const char* who, ttx_session* s, const int32_t* d_rec, i
     kc.kcache = d_kcache; kc.vcache = d_vcache; kc.cache_layer_stride = (long long)cache_layer_stride;
     kc.cache_seq_stride = (long long)cache_seq_stride; kc.N = N; kc.D = D; kc.d = d;
     kc.pos2 = d_pos2; kc.qkv_probe = d_qkv_probe; kc.probe_layer_stride = (long long)probe_layer_stride;
+    kc.row_base = d_row_base; kc.draft_mask = d_draft_mask;
     hipLaunchKernelGGL(k_kvcopy, dim3(B, Ld), dim3(256), 0, st, kc);
     err = hipGetLastError();
   }
@@ -3087,6 +3215,17 @@ extern "C" int ttx_debug_kvcopy_split(ttx_session* s, const int32_t* d_rec, int 
                       cache_seq_stride, N, D, d, B, Ld, d_pos2, d_qkv_probe, probe_layer_stride, reinterpret_cast<hipStream_t>(stream));
 }
 
+extern "C" int ttx_debug_kvcopy_select(ttx_session* s, const int32_t* d_rec, int n_copy, const float* d_qkv, int64_t qkv_layer_stride,
+                                       float* d_kcache, float* d_vcache, int64_t cache_layer_stride, int64_t cache_seq_stride, int N,
+                                       int D, int d, int B, int Ld, const int32_t* d_pos2, const float* d_qkv_probe,
+                                       int64_t probe_layer_stride, const int32_t* d_row_base, const int32_t* d_draft_mask, void* stream) {
+  if ((d_row_base != nullptr) != (d_draft_mask != nullptr))
+    return fail(TTX_ERR_INVALID, "ttx_debug_kvcopy_select: row_base and draft_mask come together");
+  return kvcopy_debug("ttx_debug_kvcopy_select", s, d_rec, n_copy, d_qkv, qkv_layer_stride, d_kcache, d_vcache, cache_layer_stride,
+                      cache_seq_stride, N, D, d, B, Ld, d_pos2, d_qkv_probe, probe_layer_stride, reinterpret_cast<hipStream_t>(stream),
+                      d_row_base, d_draft_mask);
+}
+
 // k_probe_split / k_merge_pred of the two-phase verify step (tests/test_gpu_two_phase.py).  The live count reaches the kernels as
 // in production: in a DecState on the device.
 static int dbg_state_with(hipStream_t st, int n_active, int steps, DecState** out) {
@@ -3102,9 +3241,10 @@ static int dbg_state_with(hipStream_t st, int n_active, int steps, DecState** ou
   return TTX_OK;
 }
 
-extern "C" int ttx_debug_probe_split(ttx_session* s, const int32_t* d_act_idx, const int32_t* d_pred_probe, const int32_t* d_drafts,
-                                     int B, int N, int D, int n_active, int32_t* d_act2, int32_t* d_pos2, int32_t* result,
-                                     void* stream) {
+// d_draft_mask / d_row_base / d_row_map (ttx_debug_probe_split_select; all null: ttx_debug_probe_split): result has 8 words then
+static int probe_split_debug(ttx_session* s, const int32_t* d_act_idx, const int32_t* d_pred_probe, const int32_t* d_drafts,
+                             int B, int N, int D, int n_active, int32_t* d_act2, int32_t* d_pos2, int32_t* result,
+                             int32_t* d_draft_mask, int32_t* d_row_base, int32_t* d_row_map, void* stream) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (!s || !d_act_idx || !d_pred_probe || !d_drafts || !d_act2 || !d_pos2 || !result)
     return fail(TTX_ERR_INVALID, "null argument to ttx_debug_probe_split");
@@ -3123,7 +3263,7 @@ extern "C" int ttx_debug_probe_split(ttx_session* s, const int32_t* d_act_idx, c
   }
   ProbeInfo* hinfo = nullptr;
   if (hipHostMalloc((void**)&hinfo, sizeof(ProbeInfo), hipHostMallocMapped) != hipSuccess) return fail(TTX_ERR_NOMEM, "hipHostMalloc failed");
-  hinfo->matches = -1; hinfo->probes_done = -1;
+  hinfo->matches = -1; hinfo->probes_done = -1; hinfo->rows = -1;
   DecState* dst = nullptr;
   int rc = dbg_state_with(st, n_active, result[4], &dst);           // result[4] on entry: probes counted so far
   int* d_exec = nullptr;
@@ -3133,6 +3273,7 @@ extern "C" int ttx_debug_probe_split(ttx_session* s, const int32_t* d_act_idx, c
     ProbeSplitArgs ps{};
     ps.st = dst; ps.act_idx = d_act_idx; ps.pred_probe = d_pred_probe; ps.drafts = d_drafts; ps.N = N; ps.D = D;
     ps.act2 = d_act2; ps.pos2 = d_pos2; ps.st2 = dst + 1; ps.exec_rows = d_exec;
+    ps.draft_mask = d_draft_mask; ps.row_base = d_row_base; ps.row_map = d_row_map;
     err = hipHostGetDevicePointer((void**)&ps.host, (void*)hinfo, 0);
     if (err == hipSuccess) {
       hipLaunchKernelGGL(k_probe_split, dim3(1), dim3(B > 256 ? ACCEPT_THREADS : 256), 0, st, ps);
@@ -3146,6 +3287,7 @@ extern "C" int ttx_debug_probe_split(ttx_session* s, const int32_t* d_act_idx, c
     if (err == hipSuccess) {
       result[0] = h2.n_active; result[1] = h2.r_rows; result[2] = h2.m_rows; result[3] = exec; result[4] = h2.steps;
       result[5] = hinfo->matches; result[6] = hinfo->probes_done;
+      if (d_row_base) result[7] = hinfo->rows;
     }
   }
   if (d_exec) (void)hipFree(d_exec);
@@ -3156,8 +3298,26 @@ extern "C" int ttx_debug_probe_split(ttx_session* s, const int32_t* d_act_idx, c
   return TTX_OK;
 }
 
-extern "C" int ttx_debug_merge_pred(ttx_session* s, const int32_t* d_pos2, const int32_t* d_pred_probe, const int32_t* d_pred2,
-                                    int32_t* d_pred, int B, int N, int D, int n_active, void* stream) {
+extern "C" int ttx_debug_probe_split(ttx_session* s, const int32_t* d_act_idx, const int32_t* d_pred_probe, const int32_t* d_drafts,
+                                     int B, int N, int D, int n_active, int32_t* d_act2, int32_t* d_pos2, int32_t* result,
+                                     void* stream) {
+  return probe_split_debug(s, d_act_idx, d_pred_probe, d_drafts, B, N, D, n_active, d_act2, d_pos2, result, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int ttx_debug_probe_split_select(ttx_session* s, const int32_t* d_act_idx, const int32_t* d_pred_probe, const int32_t* d_drafts,
+                                            int B, int N, int D, int n_active, int32_t* d_act2, int32_t* d_pos2, int32_t* d_draft_mask,
+                                            int32_t* d_row_base, int32_t* d_row_map, int32_t* result, void* stream) {
+  if ((d_draft_mask != nullptr) != (d_row_base != nullptr) || (d_row_base != nullptr) != (d_row_map != nullptr))
+    return fail(TTX_ERR_INVALID, "ttx_debug_probe_split_select: draft_mask, row_base and row_map come together");
+  if (d_row_base && N > 32) return fail(TTX_ERR_INVALID, "ttx_debug_probe_split_select: draft select needs N <= 32");
+  return probe_split_debug(s, d_act_idx, d_pred_probe, d_drafts, B, N, D, n_active, d_act2, d_pos2, result, d_draft_mask, d_row_base,
+                           d_row_map, stream);
+}
+
+// d_row_base / d_draft_mask (ttx_debug_merge_pred_select; both null: ttx_debug_merge_pred): d_pred2 is compacted
+static int merge_pred_debug(ttx_session* s, const int32_t* d_pos2, const int32_t* d_pred_probe, const int32_t* d_pred2,
+                            int32_t* d_pred, int B, int N, int D, int n_active, const int32_t* d_row_base, const int32_t* d_draft_mask,
+                            void* stream) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (!s || !d_pos2 || !d_pred_probe || !d_pred2 || !d_pred) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_merge_pred");
   if (B < 1 || N < 1 || D < 1) return fail(TTX_ERR_INVALID, "ttx_debug_merge_pred: B, N and D must be positive");
@@ -3169,17 +3329,42 @@ extern "C" int ttx_debug_merge_pred(ttx_session* s, const int32_t* d_pos2, const
     HIP_TRY(hipMemcpy(pos.data(), d_pos2, (size_t)n_active * 4, hipMemcpyDeviceToHost));
     for (int p : pos)
       if (p < -1 || p >= B) return fail(TTX_ERR_INVALID, "ttx_debug_merge_pred: pos2 must lie in [-1, B)");
+    if (d_row_base || d_draft_mask) {
+      int n_pos = 0, total = 0;
+      for (int p : pos) n_pos = std::max(n_pos, p + 1);
+      TTX_TRY(dbg_check_select("ttx_debug_merge_pred_select", d_row_base, d_draft_mask, n_pos, N, D, st, nullptr, &total));
+    }
   }
   DecState* dst = nullptr;
   TTX_TRY(dbg_state_with(st, n_active, 0, &dst));
   MergePredArgs mp{};
   mp.st = dst; mp.pos2 = d_pos2; mp.pred_probe = d_pred_probe; mp.pred2 = d_pred2; mp.pred = d_pred; mp.RPS = step_rps(N, D);
+  mp.row_base = d_row_base; mp.draft_mask = d_draft_mask; mp.D = D;
   hipLaunchKernelGGL(k_merge_pred, dim3(cdiv(B * mp.RPS, 256)), dim3(256), 0, st, mp);
   hipError_t err = hipGetLastError();
   const hipError_t esync = hipStreamSynchronize(st);
   (void)hipFree(dst);
   HIP_TRY(err);
   HIP_TRY(esync);
+  return TTX_OK;
+}
+
+extern "C" int ttx_debug_merge_pred(ttx_session* s, const int32_t* d_pos2, const int32_t* d_pred_probe, const int32_t* d_pred2,
+                                    int32_t* d_pred, int B, int N, int D, int n_active, void* stream) {
+  return merge_pred_debug(s, d_pos2, d_pred_probe, d_pred2, d_pred, B, N, D, n_active, nullptr, nullptr, stream);
+}
+
+extern "C" int ttx_debug_merge_pred_select(ttx_session* s, const int32_t* d_pos2, const int32_t* d_pred_probe, const int32_t* d_pred2,
+                                           int32_t* d_pred, int B, int N, int D, int n_active, const int32_t* d_row_base,
+                                           const int32_t* d_draft_mask, void* stream) {
+  if ((d_row_base != nullptr) != (d_draft_mask != nullptr))
+    return fail(TTX_ERR_INVALID, "ttx_debug_merge_pred_select: row_base and draft_mask come together");
+  return merge_pred_debug(s, d_pos2, d_pred_probe, d_pred2, d_pred, B, N, D, n_active, d_row_base, d_draft_mask, stream);
+}
+
+extern "C" int ttx_pool_last_counters(ttx_session* s, int64_t* counters) {
+  if (!s || !counters) return fail(TTX_ERR_INVALID, "null argument to ttx_pool_last_counters");
+  for (int i = 0; i < 7; ++i) counters[i] = s->pool_counters[i];
   return TTX_OK;
 }
 

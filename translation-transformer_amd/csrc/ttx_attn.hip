@@ -596,6 +596,7 @@ struct A3Unit {
   const uint8_t* kvalid;                       // STEP_CROSS: source-valid bytes
   int nq, nk, n_plain, lin_limit, ntiles;
   int f, kr0, n_lo, r0;
+  unsigned mask;                               // SEL: the slot's present drafts
 };
 
 __device__ __forceinline__ int a3_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -604,17 +605,29 @@ __device__ __forceinline__ int a3_uniform(int v) { return __builtin_amdgcn_readf
 __device__ __forceinline__ unsigned a3_magic(int D) { return D >= 2 ? (unsigned)(0x100000000ull / (unsigned)D) + 1u : 0u; }
 __device__ __forceinline__ int a3_div(int x, int D, unsigned magic) { return D >= 2 ? (int)__umulhi((unsigned)x, magic) : x; }
 
-template <int MODE>
+// SEL (draft select): the slot's rows are stored compacted from row_base[slot] on: row 0, then the D rows of every
+// draft in draft_mask[slot].  Queries and keys KEEP their layout positions (r0 + r, f + rs), so every sum runs in the order it has
+// without SEL; only the memory row a position maps to changes (step_sel_row), a row of an absent draft aliasing the slot's row 0:
+// a valid address with finite data, visible to that draft's own queries alone, and those are never stored.
+template <int MODE, bool SEL>
 __device__ __forceinline__ A3Unit a3_unit(const AttnArgs& a, int slot, int head, int qt, int RPS, unsigned magic) {
   A3Unit c;
   const int hd = head * ATT_DH;
   const int r0 = qt * A3_QT;
   const int b = a3_uniform(a.act_idx[slot]);
-  const size_t srow0 = (size_t)slot * RPS;
+  size_t srow0 = (size_t)slot * RPS;
   c.r0 = r0;
   c.nq = min(A3_QT, RPS - r0);
-  c.q = a.q + (srow0 + r0) * a.ldq + hd;
-  c.out = a.out + (srow0 + r0) * a.d + hd;
+  c.mask = 0u;
+  if constexpr (SEL) {
+    srow0 = (size_t)a3_uniform(a.row_base[slot]);
+    c.mask = (unsigned)a3_uniform(a.draft_mask[slot]);
+    c.q = a.q + srow0 * a.ldq + hd;                  // the slot's row 0: a3_sel_row gives the row from there
+    c.out = a.out + srow0 * a.d + hd;
+  } else {
+    c.q = a.q + (srow0 + r0) * a.ldq + hd;
+    c.out = a.out + (srow0 + r0) * a.d + hd;
+  }
   if constexpr (MODE == ATT_STEP_SELF) {
     const int D = a.D;
     const int f = a3_uniform(a.front[b]);
@@ -649,17 +662,35 @@ __device__ __forceinline__ A3Unit a3_unit(const AttnArgs& a, int slot, int head,
     c.n_plain = (nkeys + 31) & ~31;
     c.lin_limit = nkeys;
   }
+  if constexpr (SEL) {
+    // a unit none of whose rows is stored (row 0 is not among them and all its drafts are absent) folds one key and leaves
+    // (the first and last draft of the unit are worked out here again, for both modes, and not shared with STEP_SELF's lines above:
+    // hoisting them changes the register allocation of the existing k_attn3s<STEP_SELF> instantiation, which is to stay as it was)
+    if (r0 > 0) {
+      const int n_lo = a3_div(r0 - 1, a.D, magic), n_hi = a3_div(r0 + c.nq - 2, a.D, magic);
+      const unsigned span = ((2u << n_hi) - 1u) & ~((1u << n_lo) - 1u);
+      if (!(c.mask & span)) c.nk = 1;
+    }
+  }
   c.ntiles = (c.nk + 31) >> 5;
   return c;
 }
 
+// SEL: layout row `rs` of the unit's slot -> row inside the slot's compacted rows; -1: a row of an absent draft
+__device__ __forceinline__ int a3_sel_row(const AttnArgs& a, const A3Unit& c, int rs, unsigned magic) {
+  if (rs == 0) return 0;
+  const int n = a3_div(rs - 1, a.D, magic);
+  return step_sel_row(c.mask, n, rs - 1 - n * a.D, a.D);
+}
+
 // K / V row of key `key` (0 <= key < nk) as an offset in floats from the unit's bases: 32-bit arithmetic (a sequence's cache, its
 // step rows and a source's memory rows each span far less than 2^31 floats)
-template <int MODE>
-__device__ __forceinline__ void a3_keyrow(const AttnArgs& a, const A3Unit& c, int key, const float*& kp, const float*& vp) {
+template <int MODE, bool SEL>
+__device__ __forceinline__ void a3_keyrow(const AttnArgs& a, const A3Unit& c, int key, unsigned magic, const float*& kp, const float*& vp) {
   if constexpr (MODE == ATT_STEP_SELF) {
     const bool cached = key < c.f;
-    const int srow = (key == c.f) ? 0 : c.kr0 + (key - c.f - 1);
+    int srow = (key == c.f) ? 0 : c.kr0 + (key - c.f - 1);
+    if constexpr (SEL) srow = max(a3_sel_row(a, c, max(srow, 0), magic), 0);
     const int off = cached ? key * a.d : srow * a.ldkv;
     kp = (cached ? c.klin : c.kb) + off;
     vp = (cached ? c.vlin : c.vb) + off;
@@ -704,13 +735,22 @@ __device__ __forceinline__ int a3_qflag(const AttnArgs& a, const A3Unit& c, int 
 struct A3Query {
   float qx[16];              // B operand of S^T: query r, dims 8g + 4h .. +3, already times the scale
   int qf;                    // (rows past nq repeat the last query; they are never stored)
+  int orow;                  // SEL: row the lane's query is stored at, from the slot's row 0 on; -1: not stored
 };
 
-template <int MODE>
+template <int MODE, bool SEL>
 __device__ __forceinline__ A3Query a3_load_query(const AttnArgs& a, const A3Unit& c, int r, int h, unsigned magic) {
   typedef float f32x4 __attribute__((ext_vector_type(4)));
   A3Query qq;
-  const float* qp = c.q + (size_t)min(r, c.nq - 1) * a.ldq + 4 * h;
+  const float* qp;
+  if constexpr (SEL) {
+    const int m = a3_sel_row(a, c, c.r0 + min(r, c.nq - 1), magic);
+    qq.orow = r < c.nq ? m : -1;
+    qp = c.q + (size_t)max(m, 0) * a.ldq + 4 * h;
+  } else {
+    qq.orow = 0;
+    qp = c.q + (size_t)min(r, c.nq - 1) * a.ldq + 4 * h;
+  }
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
     f32x4 v = *reinterpret_cast<const f32x4*>(qp + 8 * g);
@@ -723,8 +763,8 @@ __device__ __forceinline__ A3Query a3_load_query(const AttnArgs& a, const A3Unit
 
 // every load of a tile is unconditional (key indices clamped to nk - 1; such keys are masked): a conditional load
 // costs a branch and a full vmcnt(0) round trip each
-template <int MODE>
-__device__ __forceinline__ A3Tile a3_load_tile(const AttnArgs& a, const A3Unit& c, int key0, int r, int h) {
+template <int MODE, bool SEL>
+__device__ __forceinline__ A3Tile a3_load_tile(const AttnArgs& a, const A3Unit& c, int key0, int r, int h, unsigned magic) {
   A3Tile tl;
   const int lin_ld = (MODE == ATT_STEP_SELF) ? a.d : a.ldkv;
   if (key0 + 32 <= c.lin_limit) {                   // uniform: all 32 keys exist and are laid out linearly
@@ -741,16 +781,29 @@ __device__ __forceinline__ A3Tile a3_load_tile(const AttnArgs& a, const A3Unit& 
   }
   const float *kp, *vp;
   const int kown = min(key0 + r, c.nk - 1);
-  a3_keyrow<MODE>(a, c, kown, kp, vp);
+  a3_keyrow<MODE, SEL>(a, c, kown, magic, kp, vp);
   tl.k0 = *reinterpret_cast<const float4*>(kp + 4 * h);
   tl.k1 = *reinterpret_cast<const float4*>(kp + 4 * h + 8);
   tl.k2 = *reinterpret_cast<const float4*>(kp + 4 * h + 16);
   tl.k3 = *reinterpret_cast<const float4*>(kp + 4 * h + 24);
   tl.own = a3_keyown<MODE>(a, c, kown);
+  if constexpr (SEL && MODE == ATT_STEP_SELF) {
+    // the row of key key0 + r is mapped ONCE, by the lane that loads its K, and handed to the lanes that load its V (as the
+    // visibility flags are in a3_tile_partial): an offset from the cache base (>= 0) or, complemented, from the step rows
+    const int code = kown < c.f ? (int)(vp - c.vlin) : ~(int)(vp - c.vb);
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      const int j0 = (t & 3) + 8 * (t >> 2);
+      const int c0 = __builtin_amdgcn_readlane(code, j0), c1 = __builtin_amdgcn_readlane(code, j0 + 4);
+      const int cc = h ? c1 : c0;
+      tl.v[t] = (cc >= 0 ? c.vlin + cc : c.vb + ~cc)[r];
+    }
+    return tl;
+  }
 #pragma unroll
   for (int t = 0; t < 16; ++t) {
     const float *kq, *vq;
-    a3_keyrow<MODE>(a, c, min(key0 + (t & 3) + 8 * (t >> 2) + 4 * h, c.nk - 1), kq, vq);
+    a3_keyrow<MODE, SEL>(a, c, min(key0 + (t & 3) + 8 * (t >> 2) + 4 * h, c.nk - 1), magic, kq, vq);
     tl.v[t] = vq[r];
   }
   return tl;
@@ -819,7 +872,7 @@ __device__ __forceinline__ void a3_tile_partial(const AttnArgs& a, const A3Unit&
 }
 
 // Few sequences: one workgroup per unit, its key tiles shared out over the four waves.
-template <int MODE>
+template <int MODE, bool SEL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_attn3(AttnArgs a) {
   static_assert(MODE == ATT_STEP_SELF || MODE == ATT_STEP_CROSS, "k_attn3 serves the verify step");
   typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -830,13 +883,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   if ((int)blockIdx.z * A3_QT >= RPS) return;
   const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5, wave = threadIdx.x >> 6;
   const unsigned magic = a3_magic(a.D);
-  const A3Unit c = a3_unit<MODE>(a, slot, blockIdx.y, blockIdx.z, RPS, magic);
-  const A3Query q = a3_load_query<MODE>(a, c, r, h, magic);
-  A3Tile cur = a3_load_tile<MODE>(a, c, min(wave, c.ntiles - 1) * 32, r, h);
+  const A3Unit c = a3_unit<MODE, SEL>(a, slot, blockIdx.y, blockIdx.z, RPS, magic);
+  const A3Query q = a3_load_query<MODE, SEL>(a, c, r, h, magic);
+  A3Tile cur = a3_load_tile<MODE, SEL>(a, c, min(wave, c.ntiles - 1) * 32, r, h, magic);
   for (int it = wave; it < c.ntiles; it += 4) {
     // the next tile's loads go out before this tile's arithmetic (the empty asm keeps them above it); the copy at the
     // bottom of the loop is where they are waited for
-    A3Tile nxt = a3_load_tile<MODE>(a, c, min(it + 4, c.ntiles - 1) * 32, r, h);
+    A3Tile nxt = a3_load_tile<MODE, SEL>(a, c, min(it + 4, c.ntiles - 1) * 32, r, h, magic);
     asm volatile("" ::: "memory");
     float mx, rs;
     f32x16 oi;
@@ -857,10 +910,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
     for (int v = 0; v < 4; ++v) o4[v] = __fmaf_rn(o4[v], fa, __fmul_rn(part[(4 * wave + v) * 64 + lane], fb));
   }
-  if (r < c.nq) {
+  if (SEL ? q.orow >= 0 : r < c.nq) {
     const float inv = l > 0.f ? 1.0f / l : 0.f;
     f32x4 w = {o4[0] * inv, o4[1] * inv, o4[2] * inv, o4[3] * inv};
-    *reinterpret_cast<f32x4*>(c.out + (size_t)r * a.d + 4 * h + 8 * wave) = w;
+    *reinterpret_cast<f32x4*>(c.out + (size_t)(SEL ? q.orow : r) * a.d + 4 * h + 8 * wave) = w;
   }
 }
 
@@ -870,7 +923,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // machine's size (two waves per SIMD) and every wave walks units u = wave, wave + W, ...: while the last tile of a unit is in the
 // matrix pipe, the first tile and the queries of the NEXT unit are already in flight, and that unit's scalars were fetched one
 // unit earlier.
-template <int MODE>
+template <int MODE, bool SEL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_attn3s(AttnArgs a, int H, int qtiles) {
   static_assert(MODE == ATT_STEP_SELF || MODE == ATT_STEP_CROSS, "k_attn3s serves the verify step");
   typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -884,11 +937,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // unit u = ((slot * qtiles) + q tile) * H + head
   auto unit = [&](int uu) {
     const int head = uu % H, t = uu / H;
-    return a3_unit<MODE>(a, t / qtiles, head, t % qtiles, RPS, magic);
+    return a3_unit<MODE, SEL>(a, t / qtiles, head, t % qtiles, RPS, magic);
   };
   A3Unit cu = unit(u);
-  A3Query cq = a3_load_query<MODE>(a, cu, r, h, magic);
-  A3Tile cur = a3_load_tile<MODE>(a, cu, 0, r, h);
+  A3Query cq = a3_load_query<MODE, SEL>(a, cu, r, h, magic);
+  A3Tile cur = a3_load_tile<MODE, SEL>(a, cu, 0, r, h, magic);
   int un = u + W;
   A3Unit nu = unit(min(un, n_units - 1));               // the next unit's scalars, one unit ahead
   float m = -INFINITY, l = 0.f;
@@ -904,10 +957,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     A3Tile nxt = cur;
     A3Query nq = cq;
     if (!last) {
-      nxt = a3_load_tile<MODE>(a, cu, it * 32 + 32, r, h);
+      nxt = a3_load_tile<MODE, SEL>(a, cu, it * 32 + 32, r, h, magic);
     } else if (more) {
-      nxt = a3_load_tile<MODE>(a, nu, 0, r, h);
-      nq = a3_load_query<MODE>(a, nu, r, h, magic);
+      nxt = a3_load_tile<MODE, SEL>(a, nu, 0, r, h, magic);
+      nq = a3_load_query<MODE, SEL>(a, nu, r, h, magic);
     }
     asm volatile("" ::: "memory");
     float mx, rs, fa, fb;
@@ -922,9 +975,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       continue;
     }
     // o[v] = O[query r][dim (v&3) + 8(v>>2) + 4h]: four float4 per lane
-    if (r < cu.nq) {
+    if (SEL ? cq.orow >= 0 : r < cu.nq) {
       const float inv = l > 0.f ? 1.0f / l : 0.f;
-      float* op = cu.out + (size_t)r * a.d + 4 * h;
+      float* op = cu.out + (size_t)(SEL ? cq.orow : r) * a.d + 4 * h;
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
         f32x4 w = {o[4 * v] * inv, o[4 * v + 1] * inv, o[4 * v + 2] * inv, o[4 * v + 3] * inv};
@@ -961,6 +1014,11 @@ static int launch_attn_mode(ttx_session* s, hipStream_t st, const AttnArgs& a, i
   const bool want2 = force ? force == AK_ATTN2 : !s->attn_fallback;
   if ((force == AK_ATTN3 || force == AK_ATTN3S) && !(step && H % 4 == 0 && DH == ATT_DH))
     return fail(TTX_ERR_INVALID, "k_attn3 / k_attn3s serve the step modes at head dimension 32 with a head count that is a multiple of 4");
+  // draft select (a.row_base / a.draft_mask): compacted step rows, which only the SEL instantiations of k_attn3 / k_attn3s read
+  const bool sel = a.row_base != nullptr;
+  if (sel && !(step && DH == ATT_DH && H % 4 == 0 && want3 && a.draft_mask && N <= 32 && D >= 1))
+    return fail(TTX_ERR_INVALID, "draft select runs on k_attn3 / k_attn3s only: a step launch at head dimension 32, a head count that is a "
+                                 "multiple of 4, 1 <= N <= 32 and D >= 1");
   if constexpr (step && DH == ATT_DH) {
     // the verify step: one wave per (sequence, head, 32 step rows), registers only — no key-count limit.  Head dimension 32
     // only: at 64 a step launch takes the route below (k_attn2, k_attn beyond its capacity) whatever H is.
@@ -976,12 +1034,14 @@ static int launch_attn_mode(ttx_session* s, hipStream_t st, const AttnArgs& a, i
       if (force) split = (force == AK_ATTN3);
       s->last_attn_kernel = split ? AK_ATTN3 : AK_ATTN3S;
       if (split) {
-        hipLaunchKernelGGL((k_attn3<MODE>), dim3(groups, H, qtiles), dim3(256), lds3, st, a);
+        if (sel) hipLaunchKernelGGL((k_attn3<MODE, true>), dim3(groups, H, qtiles), dim3(256), lds3, st, a);
+        else hipLaunchKernelGGL((k_attn3<MODE, false>), dim3(groups, H, qtiles), dim3(256), lds3, st, a);
       } else {
         // a grid of the machine's size (two workgroups = eight waves per CU), every wave walking its share of the units
         const long long units = (long long)groups * H * qtiles;
         const int wgs = (int)std::min<long long>((units + 3) / 4, (long long)TTX_A3S_WGS_PER_CU * s->m->n_cu);
-        hipLaunchKernelGGL((k_attn3s<MODE>), dim3(wgs), dim3(256), 0, st, a, H, qtiles);
+        if (sel) hipLaunchKernelGGL((k_attn3s<MODE, true>), dim3(wgs), dim3(256), 0, st, a, H, qtiles);
+        else hipLaunchKernelGGL((k_attn3s<MODE, false>), dim3(wgs), dim3(256), 0, st, a, H, qtiles);
       }
       HIP_TRY(hipGetLastError());
       return TTX_OK;

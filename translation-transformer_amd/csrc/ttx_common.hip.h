@@ -32,7 +32,8 @@ struct HostInfo { int stop; int steps_done; int width; int n_active; };
 
 // Two-phase verify step of the slot pool (DESIGN.md "Two-phase verify step"): k_probe_split publishes how many live slots matched
 // a draft's first token and how many probes have run.  A word pair of its own: HostInfo stays what the accept kernels write.
-struct ProbeInfo { int matches; int probes_done; };
+// `rows` (draft select): the compacted row count of the draft pass, written before probes_done like `matches`.
+struct ProbeInfo { int matches; int probes_done; int rows; };
 
 // ------------------------------------------------------------------------------------------------
 // GEMM:  Y[m, n] = sum_k X[m, k] * W[n, k]   (torch.nn.Linear layout: both operands K-contiguous)
@@ -129,6 +130,16 @@ struct AttnArgs {
   const float* kcache; const float* vcache; long long cache_seq_stride;  // floats per sequence in the cache
   const int* cache_slot;           // STEP_SELF: running row -> its sequence's slot in the cache (null: the row index itself)
   int gen_ld; int N; int D;
+  // draft select (the SEL instantiations of k_attn3 / k_attn3s; both null otherwise): slot -> first row of its compacted rows in
+  // q / k / v / out, and slot -> bit n set when draft n's rows are stored (see step_sel_row)
+  const int* row_base; const int* draft_mask;
 };
+
+// Draft select: a slot of the draft pass stores row 0 and the D rows of every draft in `mask`, the present drafts in the order of n.
+// Layout row rs (see step_rps) -> row inside the slot's compacted rows, or -1 for a row of an absent draft.
+__host__ __device__ inline int step_sel_rows(unsigned mask, int D) { return 1 + D * __builtin_popcount(mask); }
+__device__ __forceinline__ int step_sel_row(unsigned mask, int n, int j0, int D) {     // rs = 1 + n * D + j0
+  return ((mask >> n) & 1u) ? 1 + __popc(mask & ((1u << n) - 1u)) * D + j0 : -1;
+}
 
 }  // namespace ttx

@@ -72,7 +72,7 @@ enum AttnKernelId { AK_ATTN = 1, AK_ATTN2 = 2, AK_ATTN3 = 3, AK_ATTN3S = 4 };
 // Key of a captured launch sequence: the GraphSite that enqueues it, then every scalar the sequence depends on, in the order
 // the site lists them (the device pointers it bakes in are covered by ttx_session::alloc_generation).
 //   verify step (GS_STEP_*)       B, Ls, N, D, max_len, key capacity, GemmVariant, phase (slot pool: 0 the whole step in one pass,
-//                                 1 probe, 2 draft pass + accept, 3 accept alone; else 0)
+//                                 1 probe, 2 draft pass + accept, 3 accept alone; 4, 5, 6: the same three under draft select; else 0)
 //   GS_BEAM_ITER, GS_BEAM_POOL_ITER   see beam_launch_iter / bpool_launch_iter
 enum GraphSite { GS_STEP_SPECULATIVE = 0, GS_STEP_GREEDY = 1, GS_STEP_ROW_RULE = 2, GS_STEP_POOL = 3, GS_BEAM_ITER = 4, GS_BEAM_POOL_ITER = 5 };
 typedef std::vector<int> GraphKey;
@@ -114,6 +114,8 @@ struct GraphCache {
   /* two-phase verify step of the slot pool: the probe's QKV rows [Ld][C][3d] and argmax [C], the draft pass's argmax, the */     \
   /* list of matching sequences, slot -> position in it, and {DecState probe, DecState draft pass, int executed rows} */          \
   X(qkv_probe) X(pred_probe) X(pred_draft) X(act2) X(pos2) X(state2)                                                             \
+  /* draft select: per matching slot its present drafts and the first of its compacted rows; compacted row -> layout row */       \
+  X(draft_mask) X(row_base) X(row_map)                                                                                           \
   /* snapshot of one verify step for the logits parity test (ttx_gen_params.want_logits) */                                      \
   X(snap_logits) X(snap_act) X(snap_front) X(snap_gen) X(snap_state)                                                             \
   X(leaf_score) X(leaf_tok) X(leaf_cnt) X(beam_summary)                                                                          \
@@ -137,6 +139,8 @@ struct ttx_session {
   Buf tk[2], tv[2];                // tree (beam) decoding: the two cache buffers an iteration derives one from the other
   int snap_B = 0, snap_rps = 0, snap_gen_ld = 0, snap_step = 0;        // what snap_* hold
   ttx::ProbeInfo* probe_info = nullptr; // pinned + device-mapped, written by k_probe_split
+  // ttx_pool_last_counters: summed over the pools of the last ttx_greedy_speculative_generate_pool call whose first session this was
+  long long pool_counters[7] = {};
   ttx::BeamHost* beam_host = nullptr;   // pinned + device-mapped, written by k_bs_publish
   ttx::BeamPoolHost* bp_host = nullptr; // pinned + device-mapped, written by k_bsp_publish
   ttx::HostInfo* host_info = nullptr;   // pinned + device-mapped, written by the accept kernels

@@ -18,6 +18,8 @@ struct EmbedArgs {
   // step mode
   const DecState* st; const int* act_idx; const int* front; const int* gen; int gen_ld;
   const int* drafts; int N; int D;   // drafts int32 [B, N, D]
+  // step mode, draft select (null: output row = layout row): output row -> layout row slot * RPS + rs of the token it holds
+  const int* row_map;
 };
 
 template <bool STEP>
@@ -28,8 +30,9 @@ __global__ __launch_bounds__(256) void k_embed(EmbedArgs a) {
   if constexpr (STEP) {
     if (row >= a.st->m_rows) return;
     const int RPS = step_rps(a.N, a.D);
-    const int rs = row % RPS;                      // row inside the slot (layout: see step_rps)
-    const int b = a.act_idx[row / RPS];
+    const int lrow = a.row_map ? a.row_map[row] : row;
+    const int rs = lrow % RPS;                     // row inside the slot (layout: see step_rps)
+    const int b = a.act_idx[lrow / RPS];
     const int f = a.front[b];
     if (rs == 0) {
       tok = a.gen[(size_t)b * a.gen_ld + f];
@@ -470,6 +473,9 @@ struct KvCopyArgs {
   // `qkv` (the draft pass ran the matching slots only), or -1: the slot ran in the probe alone, whose single row per slot
   // lies in `qkv_probe` [Ld][C][3d] and is all that is committed
   const int* pos2; const float* qkv_probe; long long probe_layer_stride;
+  // draft select (both null: a slot of the draft pass owns RPS rows): position in the draft pass -> first of its compacted rows in
+  // `qkv`, and its present drafts.  The best draft of a slot that accepted anything is a present one (an absent one accepts 0).
+  const int* row_base; const int* draft_mask;
 };
 
 __global__ __launch_bounds__(256) void k_kvcopy(KvCopyArgs a) {
@@ -479,9 +485,13 @@ __global__ __launch_bounds__(256) void k_kvcopy(KvCopyArgs a) {
   const int RPS = step_rps(a.N, a.D);
   const float* src = a.qkv + (size_t)l * a.qkv_layer_stride + ((size_t)slot * RPS) * 3 * a.d;   // the slot's step rows
   int nrows = r.nacc + 1;
+  int best_row = 1 + r.best * a.D;                  // the slot's row of token 1 of the chosen draft
   if (a.pos2) {
     const int p = a.pos2[slot];
-    if (p >= 0) src = a.qkv + (size_t)l * a.qkv_layer_stride + ((size_t)p * RPS) * 3 * a.d;
+    if (p >= 0 && a.row_base) {
+      src = a.qkv + (size_t)l * a.qkv_layer_stride + (size_t)a.row_base[p] * 3 * a.d;
+      best_row = max(step_sel_row((unsigned)a.draft_mask[p], r.best, 0, a.D), 0);     // read only when nacc > 0: present then
+    } else if (p >= 0) src = a.qkv + (size_t)l * a.qkv_layer_stride + ((size_t)p * RPS) * 3 * a.d;
     else { src = a.qkv_probe + (size_t)l * a.probe_layer_stride + (size_t)slot * 3 * a.d; nrows = 1; }   // nacc is 0 here
   }
   float* kc = a.kcache + (size_t)l * a.cache_layer_stride + (size_t)r.b * a.cache_seq_stride + (size_t)r.front_old * a.d;
@@ -490,7 +500,7 @@ __global__ __launch_bounds__(256) void k_kvcopy(KvCopyArgs a) {
   const int total = nrows * per_row;
   for (int e = threadIdx.x; e < total; e += blockDim.x) {
     const int j = e / per_row, c = (e % per_row) * 4;
-    const int srow = (j == 0) ? 0 : 1 + r.best * a.D + (j - 1);   // position front_old + j of the chosen draft
+    const int srow = (j == 0) ? 0 : best_row + (j - 1);           // position front_old + j of the chosen draft
     const float* p = src + (size_t)srow * 3 * a.d;
     *reinterpret_cast<float4*>(kc + (size_t)j * a.d + c) = *reinterpret_cast<const float4*>(p + a.d + c);
     *reinterpret_cast<float4*>(vc + (size_t)j * a.d + c) = *reinterpret_cast<const float4*>(p + 2 * a.d + c);
@@ -520,47 +530,89 @@ struct ProbeSplitArgs {
   int* pos2;                       // out [n_active]: slot -> position in act2, -1 without a match
   DecState* st2;                   // out: n_active = matches, r_rows, m_rows = matches * RPS; steps counts the probes
   int* exec_rows;                  // out: n_active + matches * RPS
-  ProbeInfo* host;                 // out (may be null): matches, then the probe counter
+  ProbeInfo* host;                 // out (may be null): matches (and the draft pass's rows), then the probe counter
+  // draft select (all three null: the draft pass runs every draft of a matching slot, RPS rows each).  Per matching slot, in the
+  // order of act2: bit n of draft_mask = draft n's first token is the probe's prediction; row_base = exclusive prefix sum of
+  // 1 + D * popcount(mask), the first of the slot's compacted rows; row_map [st2->m_rows]: compacted row -> layout row
+  // position * RPS + rs.  st2->m_rows is then the compacted total.  Entries past the counts stay untouched.
+  int* draft_mask; int* row_base; int* row_map;
 };
 
 // One block; ordered compaction as in k_accept, in rounds of blockDim.x slots.
 __global__ __launch_bounds__(ACCEPT_THREADS) void k_probe_split(ProbeSplitArgs a) {
-  __shared__ int s_scan[ACCEPT_THREADS / 64];
+  __shared__ int s_scan[ACCEPT_THREADS / 64], s_rows[ACCEPT_THREADS / 64];
   const int Bc = a.st->n_active;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int n_before = 0;
+  const int RPS = step_rps(a.N, a.D);
+  const bool sel = a.row_base != nullptr;
+  int n_before = 0, rows_before = 0;
   for (int base = 0; base < Bc; base += blockDim.x) {
     const int slot = base + threadIdx.x;
     int b = 0, hit = 0;
+    unsigned dm = 0u;
     if (slot < Bc) {
       b = a.act_idx[slot];
       const int t = a.pred_probe[slot];
-      for (int n = 0; n < a.N; ++n) hit |= (a.drafts[((size_t)b * a.N + n) * a.D] == t) ? 1 : 0;
+      for (int n = 0; n < a.N; ++n) {
+        const int eq = (a.drafts[((size_t)b * a.N + n) * a.D] == t) ? 1 : 0;
+        hit |= eq;
+        dm |= (unsigned)eq << (n & 31);
+      }
     }
     const unsigned long long mask = __ballot(hit);
     if (lane == 0) s_scan[wave] = __popcll(mask);
+    // draft select: the same ordered scan carrying a slot's rows instead of a count (inclusive over the wave, then the waves before)
+    const int wrows = (sel && hit) ? step_sel_rows(dm, a.D) : 0;
+    int incl = wrows;
+    if (sel) {
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o, 64);
+        incl += (lane >= o) ? v : 0;
+      }
+      if (lane == 63) s_rows[wave] = incl;
+    }
     __syncthreads();
-    int before = 0, total = 0;
+    int before = 0, total = 0, rbefore = 0, rtotal = 0;
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) {
       const int c = s_scan[w];
       before += (w < wave) ? c : 0;
       total += c;
+      if (sel) {
+        const int rw = s_rows[w];
+        rbefore += (w < wave) ? rw : 0;
+        rtotal += rw;
+      }
     }
     if (slot < Bc) {
       const int p = n_before + before + __popcll(mask & ((1ull << lane) - 1ull));
       if (hit) a.act2[p] = b;
       a.pos2[slot] = hit ? p : -1;
+      if (sel && hit) {
+        a.draft_mask[p] = (int)dm;
+        a.row_base[p] = rows_before + rbefore + incl - wrows;
+      }
     }
     n_before += total;
+    rows_before += rtotal;
     __syncthreads();
   }
+  if (sel) {
+    // the row map, shared out over the block (the barrier above ordered the masks and bases written by the other threads)
+    for (int i = threadIdx.x; i < n_before * RPS; i += blockDim.x) {
+      const int p = i / RPS, rs = i - p * RPS;
+      const int m = rs == 0 ? 0 : step_sel_row((unsigned)a.draft_mask[p], (rs - 1) / a.D, (rs - 1) % a.D, a.D);
+      if (m >= 0) a.row_map[a.row_base[p] + m] = i;
+    }
+  }
   if (threadIdx.x == 0) {
-    const int RPS = step_rps(a.N, a.D);
-    a.st2->n_active = n_before; a.st2->r_rows = n_before * a.N; a.st2->m_rows = n_before * RPS;
+    const int m_rows = sel ? rows_before : n_before * RPS;
+    a.st2->n_active = n_before; a.st2->r_rows = n_before * a.N; a.st2->m_rows = m_rows;
     a.st2->steps += 1;
-    *a.exec_rows = Bc + n_before * RPS;
+    *a.exec_rows = Bc + n_before * RPS;              // what verified_positions adds: the positions of matching slots, run or not
     if (a.host) {
       a.host->matches = n_before;
+      a.host->rows = m_rows;
       __threadfence_system();
       a.host->probes_done = a.st2->steps;            // last: the host reads `matches` once it sees this one move
     }
@@ -574,15 +626,23 @@ struct MergePredArgs {
   const int* pred2;                // [matches * RPS] the draft pass's argmax
   int* pred;                       // out [n_active * RPS]: what k_accept reads
   int RPS;
+  // draft select (both null: pred2 holds RPS rows per position): pred2 is compacted as the draft pass stored it
+  const int* row_base; const int* draft_mask; int D;
 };
 
 // A slot without a match gets the probe's prediction in row 0 and -1 in its draft rows: k_accept's first comparison of every
-// draft is against row 0, which matches none, so n_acc = 0 and best = 0 whatever the filler is.
+// draft is against row 0, which matches none, so n_acc = 0 and best = 0 whatever the filler is.  Under draft select the same holds for
+// the absent drafts of a matching slot: their first token is not row 0's prediction, their rows were not run and read -1.
 __global__ __launch_bounds__(256) void k_merge_pred(MergePredArgs a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.st->n_active * a.RPS) return;
   const int slot = i / a.RPS, r = i - slot * a.RPS;
   const int p = a.pos2[slot];
+  if (p >= 0 && a.row_base) {
+    const int m = r == 0 ? 0 : step_sel_row((unsigned)a.draft_mask[p], (r - 1) / a.D, (r - 1) % a.D, a.D);
+    a.pred[i] = m >= 0 ? a.pred2[a.row_base[p] + m] : -1;
+    return;
+  }
   a.pred[i] = p >= 0 ? a.pred2[(size_t)p * a.RPS + r] : (r == 0 ? a.pred_probe[slot] : -1);
 }
 

@@ -321,6 +321,75 @@ class NativeTransformer:
         N.check(self._lib.ttx_debug_merge_pred(self._session, pos2.data_ptr(), pred_probe.data_ptr(), pred2.data_ptr(),
                                                pred.data_ptr(), int(B), int(n), int(d), int(n_active), self._stream()))
 
+    # draft select (DESIGN.md "Two-phase verify step"): the same launches on the compacted rows of a draft pass
+    def debug_probe_split_select(self, act_idx: torch.Tensor, pred_probe: torch.Tensor, drafts: torch.Tensor, n_active: int,
+                                 act2: torch.Tensor, pos2: torch.Tensor, draft_mask: torch.Tensor, row_base: torch.Tensor,
+                                 row_map: torch.Tensor, probes_before: int = 0) -> list:
+        """debug_probe_split that also writes ``draft_mask`` / ``row_base`` int32 [B] and ``row_map`` int32 [B * (1 + n*d)]
+        (ttx_debug_probe_split_select).  Returns the 8 result words of include/ttx.h."""
+        B, n, d = drafts.shape
+        words = (C.c_int32 * 8)(0, 0, 0, 0, int(probes_before), 0, 0, 0)
+        N.check(self._lib.ttx_debug_probe_split_select(self._session, act_idx.data_ptr(), pred_probe.data_ptr(), drafts.data_ptr(),
+                                                       int(B), int(n), int(d), int(n_active), act2.data_ptr(), pos2.data_ptr(),
+                                                       self._ptr(draft_mask), self._ptr(row_base), self._ptr(row_map), words,
+                                                       self._stream()))
+        return [int(v) for v in words]
+
+    def debug_merge_pred_select(self, pos2: torch.Tensor, pred_probe: torch.Tensor, pred2: torch.Tensor, pred: torch.Tensor, B: int,
+                                n: int, d: int, n_active: int, row_base: torch.Tensor | None, draft_mask: torch.Tensor | None) -> None:
+        """debug_merge_pred on compacted draft-pass predictions (ttx_debug_merge_pred_select)."""
+        N.check(self._lib.ttx_debug_merge_pred_select(self._session, pos2.data_ptr(), pred_probe.data_ptr(), pred2.data_ptr(),
+                                                      pred.data_ptr(), int(B), int(n), int(d), int(n_active), self._ptr(row_base),
+                                                      self._ptr(draft_mask), self._stream()))
+
+    def debug_kvcopy_select(self, rec: torch.Tensor, n_copy: int, qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
+                            n: int, d: int, width: int, B: int, pos2: torch.Tensor | None, qkv_probe: torch.Tensor | None,
+                            row_base: torch.Tensor | None, draft_mask: torch.Tensor | None) -> None:
+        """debug_kvcopy_split on a compacted ``qkv`` (ttx_debug_kvcopy_select)."""
+        assert kcache.stride() == vcache.stride()
+        N.check(self._lib.ttx_debug_kvcopy_select(self._session, rec.data_ptr(), int(n_copy), qkv.data_ptr(), int(qkv.stride(0)),
+                                                  kcache.data_ptr(), vcache.data_ptr(), int(kcache.stride(0)), int(kcache.stride(1)),
+                                                  int(n), int(d), int(width), int(B), int(qkv.shape[0]), self._ptr(pos2),
+                                                  self._ptr(qkv_probe), 0 if qkv_probe is None else int(qkv_probe.stride(0)),
+                                                  self._ptr(row_base), self._ptr(draft_mask), self._stream()))
+
+    def debug_embed_select(self, table: torch.Tensor, pe: torch.Tensor, x: torch.Tensor, act_idx: torch.Tensor, front: torch.Tensor,
+                           gen: torch.Tensor, drafts: torch.Tensor, B: int, n: int, d: int, n_active: int,
+                           row_map: torch.Tensor | None, m_rows: int) -> None:
+        """The step mode of debug_embed writing ``m_rows`` rows, row i that of layout row ``row_map[i]`` (ttx_debug_embed_select)."""
+        N.check(self._lib.ttx_debug_embed_select(self._session, table.data_ptr(), int(table.shape[0]), pe.data_ptr(), int(pe.shape[0]),
+                                                 int(table.shape[1]), x.data_ptr(), act_idx.data_ptr(), front.data_ptr(),
+                                                 gen.data_ptr(), int(gen.stride(0)), drafts.data_ptr(), int(B), int(n), int(d),
+                                                 int(n_active), self._ptr(row_map), int(m_rows), self._stream()))
+
+    def debug_attn_select(self, mode: int, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, heads: int,
+                          scale: float, groups: int, max_keys: int, row_base: torch.Tensor | None, draft_mask: torch.Tensor | None,
+                          Lk: int = 0, tok: torch.Tensor | None = None, pad: int = 0, key_pad: torch.Tensor | None = None,
+                          act_idx: torch.Tensor | None = None, front: torch.Tensor | None = None, src_of: torch.Tensor | None = None,
+                          src_len: torch.Tensor | None = None, kcache: torch.Tensor | None = None, vcache: torch.Tensor | None = None,
+                          cache_seq_stride: int = 0, cache_slot: torch.Tensor | None = None, gen_ld: int = 0, n: int = 1, d: int = 0,
+                          n_active: int = 0, kernel: int = 0, **unused) -> int:
+        """A step-mode debug_attn at head dimension 32 on compacted rows (ttx_debug_attn_select); takes debug_attn's keywords."""
+        kid = C.c_int32(0)
+        assert k.stride(0) == v.stride(0)
+        N.check(self._lib.ttx_debug_attn_select(self._session, q.data_ptr(), q.stride(0), k.data_ptr(), v.data_ptr(), k.stride(0),
+                                                out.data_ptr(), int(heads), float(scale), int(Lk), self._ptr(tok), int(pad),
+                                                self._ptr(key_pad), self._ptr(act_idx), self._ptr(front), self._ptr(src_of),
+                                                self._ptr(src_len), self._ptr(kcache), self._ptr(vcache), int(cache_seq_stride),
+                                                self._ptr(cache_slot), int(gen_ld), int(n), int(d), int(mode), int(groups),
+                                                int(n_active), int(max_keys), int(kernel), C.byref(kid), self._ptr(row_base),
+                                                self._ptr(draft_mask), self._stream()))
+        return int(kid.value)
+
+    POOL_COUNTERS = ("steps", "split_steps", "slot_steps_probed", "slots_matched", "drafts_matched", "rows_executed", "draft_select")
+
+    def pool_last_counters(self, session=None) -> dict:
+        """Counters of the last slot-pool call whose first session was ``session`` (default: this model's own), summed over its
+        pools (ttx_pool_last_counters)."""
+        words = (C.c_int64 * 7)()
+        N.check(self._lib.ttx_pool_last_counters(self._session if session is None else session, words))
+        return dict(zip(self.POOL_COUNTERS, (int(v) for v in words)))
+
     @staticmethod
     def attn_staged_key_limit(head_dim: int, q_per_group: int) -> int:
         """Keys one k_attn2 workgroup can stage at ``head_dim`` for groups of ``q_per_group`` query rows
