@@ -424,12 +424,13 @@ int ttx_debug_finish_ln(ttx_session* s, const float* d_slabs, int n_slabs, int64
  * Lk keys, key_pad 1 = real token).  groups: decoder rows / sources / slots; n_active (step modes) is put into a DecState on the
  * device, ordered on `stream`, before the launch; max_keys is what production passes to the launcher: the cache capacity (every
  * front <= max_keys; the caller's promise, like the indices in the device arrays) or the key count Ls.  kernel: 0 the production
- * choice, 1 k_attn, 2 k_attn2, 3 k_attn3, 4 k_attn3s; kernel_id (optional) receives what was dispatched (1..4).  Nothing is
+ * choice, 1 k_attn, 2 k_attn2, 3 k_attn3, 4 k_attn3s, 5 k_attn1; kernel_id (optional) receives what was dispatched (1..5).  Nothing is
  * launched and TTX_ERR_INVALID is returned for arguments a kernel cannot take: a null pointer the mode requires, H <= 0, ldq /
  * ldkv that are not multiples of 4 or below d, float operands that are not 16-byte aligned, n_active outside [0, groups], max_keys
  * below L / Lk, and a forced kernel that cannot serve the request (never rerouted): k_attn3 / k_attn3s outside the step modes or
  * with H % 4 != 0, k_attn3 whose parked partials exceed 64 KB of LDS, k_attn2 beyond 384 staged keys or its LDS limit, k_attn
- * beyond its LDS limit.  This entry point launches at head dimension 32; ttx_debug_attn_hd below takes the head dimension. */
+ * beyond its LDS limit, k_attn1 outside the step modes, with H % 4 != 0, at head dimension 64 or with N * D > 0 (it serves step
+ * launches of one row per slot).  This entry point launches at head dimension 32; ttx_debug_attn_hd below takes the head dimension. */
 int ttx_debug_attn(ttx_session* s, const float* d_q, int ldq, const float* d_k, const float* d_v, int ldkv, float* d_out, int H,
                    float scale, int L, int Lk, const int32_t* d_tok, int pad, const uint8_t* d_key_pad, const int32_t* d_mem_row,
                    const int32_t* d_act_idx, const int32_t* d_front, const int32_t* d_src_of, const int32_t* d_src_len,
@@ -598,6 +599,11 @@ int ttx_pool_last_counters(ttx_session* s, int64_t* counters);
  * 0 for a head dimension without kernels.  A launch whose key count (step self-attention: cache capacity + 1 + the draft rows
  * of a 64-row tile) exceeds it runs on k_attn. */
 int ttx_attn_staged_key_limit(int head_dim, int q_per_group);
+
+/* Test query: which attention kernels this session has dispatched since it was created, as a bit mask (bit k: kernel id k of
+ * ttx_debug_attn, 1 k_attn .. 5 k_attn1), counted where a launch is issued (under graphs: when a step is captured).  A negative
+ * error code for a null session. */
+int ttx_debug_attn_kernels_seen(ttx_session* s);
 
 #ifdef __cplusplus
 }

@@ -183,6 +183,7 @@ SYMBOLS = {
                                         C.c_int64, _VP, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), _VP, _VP, _VP]),
     "ttx_pool_last_counters": (C.c_int, [_VP, C.POINTER(C.c_int64)]),
     "ttx_attn_staged_key_limit": (C.c_int, [_I, _I]),
+    "ttx_debug_attn_kernels_seen": (C.c_int, [_VP]),
     "ttx_last_kernel_profile": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
 }
 

@@ -327,6 +327,8 @@ extern "C" int ttx_session_create(ttx_model* m, ttx_session** out) {
   if (const char* e = getenv("TTX_QKV_SMALL_ROWS")) s->qkv_small_rows = std::max(0, atoi(e));
   // test hook: every attention launch on the streaming fallback kernel
   if (const char* e = getenv("TTX_ATTN_FALLBACK")) s->attn_fallback = atoi(e) != 0;
+  // A/B and test switch: 0 keeps one-row step launches off k_attn1, 1 puts every eligible one on it
+  if (const char* e = getenv("TTX_ATTN_ROW")) s->attn_row = atoi(e) != 0 ? 1 : 0;
   s->host_timing = getenv("TTX_HOST_TIMING") != nullptr;
   m->n_sessions++;                                   // from here on the model's activation is fixed (ttx_model_set_activation)
   *out = s;
@@ -3369,6 +3371,11 @@ extern "C" int ttx_pool_last_counters(ttx_session* s, int64_t* counters) {
 }
 
 extern "C" int ttx_attn_staged_key_limit(int head_dim, int q_per_group) { return attn_staged_key_limit(head_dim, q_per_group); }
+
+extern "C" int ttx_debug_attn_kernels_seen(ttx_session* s) {
+  if (!s) return fail(TTX_ERR_INVALID, "null session");
+  return (int)s->attn_kernels_seen;
+}
 
 extern "C" int ttx_last_kernel_profile(ttx_session* s, double* gemm_ms, int64_t* gemm_launches, double* empty_pair_ms) {
   if (!s) return fail(TTX_ERR_INVALID, "null session");

@@ -997,6 +997,114 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
+// One step row per sequence (q_per_group == 1: the probe of a two-phase verify step, any (1, 0) step launch).  k_attn3s would give
+// such a unit a 32-column MFMA tile with 31 copies of the one query; here the same fmaf chains run on the VALU, in the order the
+// MFMAs of a3_tile_partial contract them (dims 8g + c + 4h, keys (t&3) + 8(t>>2) + 4h), so the bits are those of k_attn3 /
+// k_attn3s.  A wave takes two heads of one slot, one per 32-lane half.  Scores: lane = key, its 128-B K row in registers, the
+// scaled query of the half's head in 32 registers.  Output: lane = dim, the tile's 32 probabilities handed over through LDS (every
+// lane of a half reads the same addresses: a broadcast), V rows read 256 B at a time across the wave.  No unit is walked: one
+// wave, one (slot, head pair); the launch leaves latency hiding to the waves resident beside it.
+template <int MODE>
+__global__ __launch_bounds__(64) void k_attn1(AttnArgs a) {
+  static_assert(MODE == ATT_STEP_SELF || MODE == ATT_STEP_CROSS, "k_attn1 serves the verify step");
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  __shared__ __attribute__((aligned(16))) float a1_p[2][64];          // the probabilities of a tile, two tiles in turn
+  constexpr int A1_KROW = 36;                                            // floats between the LDS rows of two keys
+  __shared__ __attribute__((aligned(16))) float a1_k[64 * A1_KROW + 32];    // the K rows of a tile: [head of the pair][key][32 dims]
+  const int slot = blockIdx.x;
+  if (slot >= a.st->n_active) return;
+  const int lane = threadIdx.x, r = lane & 31, ho = (lane >> 5) * ATT_DH;
+  const A3Unit c = a3_unit<MODE, false>(a, slot, 2 * (int)blockIdx.y, 0, 1, 0u);
+  float q[32];
+#pragma unroll
+  for (int g = 0; g < 8; ++g) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(c.q + ho + 4 * g);
+    q[4 * g] = __fmul_rn(v.x, a.scale); q[4 * g + 1] = __fmul_rn(v.y, a.scale);
+    q[4 * g + 2] = __fmul_rn(v.z, a.scale); q[4 * g + 3] = __fmul_rn(v.w, a.scale);
+  }
+  // K / V row of key `key` < nk (a3_keyrow with one step row: the cached prefix, then the slot's row of this step), as a select
+  auto a1_row = [&](int key, const float* lin, const float* stp) -> const float* {
+    if constexpr (MODE == ATT_STEP_SELF) return key < c.f ? lin + key * a.d : stp;
+    else return lin + key * a.ldkv;
+  };
+  // every load is unconditional, key indices clamped to nk - 1 (such keys are masked), as in a3_load_tile.  K rows are fetched
+  // whole: the 256 B a key holds for the two heads go to 16 consecutive lanes (load j: keys 4j .. 4j + 3), so that every 128-B line
+  // is touched by one instruction, and reach the lane that owns the key through LDS (row of (head, key): 144 B apart, the second
+  // head's rows 128 B further, which keeps both the 16-byte writes and the row reads off each other's banks).
+  const int kc4 = (lane & 15) * 4, ksub = lane >> 4;
+  float* const kst = a1_k + (lane & 8) * (A1_KROW * 4 + 4) + (lane & 7) * 4;      // + key * A1_KROW: where this lane's pieces go
+  const float* const krd = a1_k + (lane >> 5) * (A1_KROW * 32 + 32) + r * A1_KROW;
+  f32x4 kg[8];
+  int own;
+  auto load_k = [&](int key0) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      kg[j] = *reinterpret_cast<const f32x4*>(a1_row(min(key0 + 4 * j + ksub, c.nk - 1), c.klin, c.kb) + kc4);
+    own = a3_keyown<MODE>(a, c, min(key0 + r, c.nk - 1));
+  };
+  float m = -INFINITY, l = 0.f, o = 0.f;
+  if (c.ntiles > 0) load_k(0);
+  for (int it = 0; it < c.ntiles; ++it) {
+    const int key0 = it * 32;
+    // the tile's V rows go out before its scores are worked out, and the next tile's K rows right after them, into the registers
+    // the scores have just freed (the empty asm statements keep the loads where they stand).  The tile index of that prefetch is
+    // clamped, as in k_attn3: a unit's last iteration fetches its last tile's K rows again (from L1 / L2) and never uses them,
+    // which keeps the loop body free of a branch around loads and of the full vmcnt(0) wait such a branch costs
+    float vv[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+      vv[j] = a1_row(min(key0 + j, c.nk - 1), c.vlin, c.vb)[ho + r];
+    }
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int j = 0; j < 8; ++j) *reinterpret_cast<f32x4*>(kst + (4 * j + ksub) * A1_KROW) = kg[j];
+    __syncthreads();
+    f32x4 kk[8];
+#pragma unroll
+    for (int g = 0; g < 8; ++g) kk[g] = *reinterpret_cast<const f32x4*>(krd + 4 * g);
+    float s = 0.f;
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        s = __fmaf_rn(kk[2 * g][e], q[8 * g + e], s);
+        s = __fmaf_rn(kk[2 * g + 1][e], q[8 * g + 4 + e], s);
+      }
+    s = (key0 + r < c.nk && own != 0) ? s : -INFINITY;
+    asm volatile("" ::: "memory");
+    __syncthreads();                                                    // every row of the tile has been read
+    load_k(min(it + 1, c.ntiles - 1) * 32);
+    asm volatile("" ::: "memory");
+    float mx = s;                                                       // m_i: over the 32 keys of the half
+#pragma unroll
+    for (int off = 16; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    const float base = (mx == -INFINITY) ? 0.f : mx;                  // nothing visible in this tile: every exp below is 0
+    float* pl = a1_p[it & 1];
+    pl[lane] = __expf(s - base);
+    __syncthreads();
+    float p[32];
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(pl + ho + 4 * g);
+      p[4 * g] = v.x; p[4 * g + 1] = v.y; p[4 * g + 2] = v.z; p[4 * g + 3] = v.w;
+    }
+    float rs0 = 0.f, rs1 = 0.f, oi = 0.f;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      const int j = (t & 3) + 8 * (t >> 2);
+      rs0 = __fadd_rn(rs0, p[j]);
+      rs1 = __fadd_rn(rs1, p[j + 4]);
+      oi = __fmaf_rn(vv[j], p[j], oi);
+      oi = __fmaf_rn(vv[j + 4], p[j + 4], oi);
+    }
+    float fa, fb;
+    a3_fold(m, l, mx, __fadd_rn(rs0, rs1), fa, fb);                     // l_i
+    o = __fmaf_rn(o, fa, __fmul_rn(oi, fb));
+  }
+  const float inv = l > 0.f ? 1.0f / l : 0.f;
+  c.out[ho + r] = o * inv;
+}
+
 // ------------------------------------------------------------------------------------------------
 static constexpr size_t kAttn2LdsLimit = 150 * 1024;
 
@@ -1010,8 +1118,10 @@ static int launch_attn_mode(ttx_session* s, hipStream_t st, const AttnArgs& a, i
   // test hook (ttx_debug_attn): a forced kernel replaces the choice below and is refused where it cannot serve the launch;
   // unset (0), want3 and want2 are the production conditions
   const int force = s->attn_force;
-  const bool want3 = force ? (force == AK_ATTN3 || force == AK_ATTN3S) : !s->attn_fallback;
+  const bool want3 = force ? (force == AK_ATTN3 || force == AK_ATTN3S || force == AK_ATTN1) : !s->attn_fallback;
   const bool want2 = force ? force == AK_ATTN2 : !s->attn_fallback;
+  if (force == AK_ATTN1 && !(step && H % 4 == 0 && DH == ATT_DH && q_per_group == 1))
+    return fail(TTX_ERR_INVALID, "k_attn1 serves one-row step launches (N * D = 0) at head dimension 32 with a head count that is a multiple of 4");
   if ((force == AK_ATTN3 || force == AK_ATTN3S) && !(step && H % 4 == 0 && DH == ATT_DH))
     return fail(TTX_ERR_INVALID, "k_attn3 / k_attn3s serve the step modes at head dimension 32 with a head count that is a multiple of 4");
   // draft select (a.row_base / a.draft_mask): compacted step rows, which only the SEL instantiations of k_attn3 / k_attn3s read
@@ -1032,8 +1142,13 @@ static int launch_attn_mode(ttx_session* s, hipStream_t st, const AttnArgs& a, i
       bool split = s->attn_split != 0 && (s->attn_split > 0 || (long long)groups * H * qtiles < TTX_A3_SPLIT_BELOW) && lds3 <= 64 * 1024;
       if (force == AK_ATTN3 && lds3 > 64 * 1024) return fail(TTX_ERR_INVALID, "k_attn3: the parked tile partials exceed 64 KB of LDS");
       if (force) split = (force == AK_ATTN3);
-      s->last_attn_kernel = split ? AK_ATTN3 : AK_ATTN3S;
-      if (split) {
+      // one row per sequence (the probe of a two-phase step): the launches k_attn3s would get run on k_attn1, bit-identical too.
+      // Like `split`, decided by what a step's graph key holds (groups, layout) and the session's switches.
+      const bool row = force ? force == AK_ATTN1 : (q_per_group == 1 && !sel && s->attn_row != 0 && (s->attn_row > 0 || !split));
+      s->last_attn_kernel = row ? AK_ATTN1 : split ? AK_ATTN3 : AK_ATTN3S;
+      if (row) {
+        hipLaunchKernelGGL((k_attn1<MODE>), dim3(groups, H / 2), dim3(64), 0, st, a);
+      } else if (split) {
         if (sel) hipLaunchKernelGGL((k_attn3<MODE, true>), dim3(groups, H, qtiles), dim3(256), lds3, st, a);
         else hipLaunchKernelGGL((k_attn3<MODE, false>), dim3(groups, H, qtiles), dim3(256), lds3, st, a);
       } else {
@@ -1101,9 +1216,12 @@ static int launch_attn_dh(int mode, ttx_session* s, hipStream_t st, const AttnAr
 // the head dimension of a launch is a.d / H
 int launch_attn(int mode, ttx_session* s, hipStream_t st, const AttnArgs& a, int groups, int H, int q_per_group, int max_keys,
                 int N, int D1) {
-  if (H > 0 && a.d == H * 32) return launch_attn_dh<32>(mode, s, st, a, groups, H, q_per_group, max_keys, N, D1);
-  if (H > 0 && a.d == H * 64) return launch_attn_dh<64>(mode, s, st, a, groups, H, q_per_group, max_keys, N, D1);
-  return fail(TTX_ERR_INVALID, "attention kernels exist for head dimensions 32 and 64");
+  if (!(H > 0 && (a.d == H * 32 || a.d == H * 64))) return fail(TTX_ERR_INVALID, "attention kernels exist for head dimensions 32 and 64");
+  s->last_attn_kernel = 0;
+  const int rc = a.d == H * 32 ? launch_attn_dh<32>(mode, s, st, a, groups, H, q_per_group, max_keys, N, D1)
+                               : launch_attn_dh<64>(mode, s, st, a, groups, H, q_per_group, max_keys, N, D1);
+  if (rc == TTX_OK && s->last_attn_kernel) s->attn_kernels_seen |= 1u << s->last_attn_kernel;      // what a test reads back
+  return rc;
 }
 
 // Keys k_attn2 can stage for one workgroup at head dimension `head_dim` when a group has `q_per_group` query rows: the register
@@ -1125,8 +1243,8 @@ int attn_debug(ttx_session* s, const AttnArgs& in, int H, int head_dim, int mode
                int32_t* kernel_id, hipStream_t st) {
   if (!s) return fail(TTX_ERR_INVALID, "null session");
   if (head_dim != 32 && head_dim != 64) return fail(TTX_ERR_INVALID, "ttx_debug_attn_hd: head_dim is 32 or 64");
-  if (mode < ATT_ENC || mode > ATT_STEP_CROSS || kernel < 0 || kernel > AK_ATTN3S)
-    return fail(TTX_ERR_INVALID, "ttx_debug_attn: mode is 0..4, kernel 0..4");
+  if (mode < ATT_ENC || mode > ATT_STEP_CROSS || kernel < 0 || kernel > AK_ATTN1)
+    return fail(TTX_ERR_INVALID, "ttx_debug_attn: mode is 0..4, kernel 0..5");
   if (H <= 0 || groups <= 0 || max_keys <= 0) return fail(TTX_ERR_INVALID, "ttx_debug_attn: H, groups and max_keys must be positive");
   const bool step = (mode == ATT_STEP_SELF || mode == ATT_STEP_CROSS);
   const bool cross = (mode == ATT_FULL_CROSS || mode == ATT_STEP_CROSS);

@@ -67,7 +67,7 @@ enum GemmKernelId { GK_GEMM3 = 1, GK_GEMM_TN = 2, GK_GEMM24_4 = 3, GK_GEMM24_0 =
                     GK_GEMM2_0 = 8, GK_BODY_128x64 = 16 };
 
 // Kernel of an attention launch as ttx_debug_attn selects and reports it (include/ttx.h).
-enum AttnKernelId { AK_ATTN = 1, AK_ATTN2 = 2, AK_ATTN3 = 3, AK_ATTN3S = 4 };
+enum AttnKernelId { AK_ATTN = 1, AK_ATTN2 = 2, AK_ATTN3 = 3, AK_ATTN3S = 4, AK_ATTN1 = 5 };
 
 // Key of a captured launch sequence: the GraphSite that enqueues it, then every scalar the sequence depends on, in the order
 // the site lists them (the device pointers it bakes in are covered by ttx_session::alloc_generation).
@@ -172,10 +172,12 @@ struct ttx_session {
   // them so that a test can prove which kernel it reached
   int last_gemm_kernel = 0, last_gemm_big_min_tiles = 0;
   int attn_split = -1;             // -1 by launch size, 0 never, 1 always (key tiles of a head over 4 waves)
+  int attn_row = -1;               // TTX_ATTN_ROW: one-row step launches on k_attn1: -1 those k_attn3s would get, 0 never, 1 every eligible one
   bool attn_fallback = false;      // TTX_ATTN_FALLBACK=1 (test hook): every attention launch on the streaming kernel k_attn
   int attn_force = 0;              // ttx_debug_attn (test hook): an AttnKernelId that replaces launch_attn's choice; 0 (always, outside that call): unset
   int attn_sel_N = 0, attn_sel_D = 0;   // > 0 around the launches of a probe (run_step, ttx_debug_attn_as): choose between k_attn2 and k_attn as a step launch in the layout (N, D) does
   int last_attn_kernel = 0;        // what the most recent launch_attn dispatched (AttnKernelId): ttx_debug_attn reports it
+  unsigned attn_kernels_seen = 0;  // bit k: launch_attn has dispatched AttnKernelId k on this session (ttx_debug_attn_kernels_seen)
   // profiling of the GEMM launches (bench.py roofline): a HIP event pair around every GEMM launch
   bool profile = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;

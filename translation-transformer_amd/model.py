@@ -226,7 +226,7 @@ class NativeTransformer:
         """One attention launch on the caller's device tensors (ttx_debug_attn_hd): ``q`` / ``k`` / ``v`` are 2-D fp32 views whose
         row strides are the leading dimensions (``k`` and ``v`` share theirs), ``out`` has rows of ``head_dim`` * ``heads`` floats
         (``head_dim`` 32 or 64); index and token tensors are int32, ``key_pad`` uint8.  ``kernel``: 0 the production choice,
-        1 k_attn, 2 k_attn2, 3 k_attn3, 4 k_attn3s.  Returns the kernel that ran; arguments a kernel cannot take raise TtxError
+        1 k_attn, 2 k_attn2, 3 k_attn3, 4 k_attn3s, 5 k_attn1.  Returns the kernel that ran; arguments a kernel cannot take raise TtxError
         (TTX_ERR_INVALID).  ``choose_as`` = (n, d): a step launch that chooses between k_attn2 and k_attn as a launch in that
         layout does (ttx_debug_attn_as: the probe of the two-phase verify step)."""
         kid = C.c_int32(0)
@@ -380,6 +380,13 @@ class NativeTransformer:
                                                 int(n_active), int(max_keys), int(kernel), C.byref(kid), self._ptr(row_base),
                                                 self._ptr(draft_mask), self._stream()))
         return int(kid.value)
+
+    def attn_kernels_seen(self, session=None) -> set:
+        """Ids of the attention kernels ``session`` (default: this model's own) has dispatched so far (ttx_debug_attn_kernels_seen)."""
+        mask = int(self._lib.ttx_debug_attn_kernels_seen(self._session if session is None else session))
+        if mask < 0:
+            N.check(mask)
+        return {k for k in range(1, 32) if mask >> k & 1}
 
     POOL_COUNTERS = ("steps", "split_steps", "slot_steps_probed", "slots_matched", "drafts_matched", "rows_executed", "draft_select")
 
