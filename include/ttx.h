@@ -154,6 +154,33 @@ int ttx_score_hypotheses(ttx_session* s, const int64_t* d_src, int B, int Ls, co
                          int eos, float* d_logits, float* d_tok_logp, float* d_score, int32_t* d_length, uint8_t* d_finished,
                          void* stream);
 
+/* Cross-attention maps of hypotheses: which source position each output token attended to.  d_src int64 [B,Ls] and d_hyp int64
+ * [B*N] rows of stride ld_hyp >= W as for ttx_score_hypotheses; T = W - 1; decoder row r = b*N + k reads hyp[b,k,:T] and attends
+ * to memory row b.
+ *   length    [r] = n of the scoring rule on the tokens alone: the column of the first EOS at a column >= 1, else the last column
+ *             >= 1 holding a non-PAD token, else 0.  Query position t (0-based, the one that predicts hyp[t+1]) is live iff
+ *             t + 1 <= n: the convention of tok_logp[t-1].
+ *   heads     P[r,h,t,j] = softmax_j(scale * q[r,t,h,:] . k[b,j,h,:]) over the keys j with src[b,j] != PAD, scale =
+ *             1/sqrt(head_dim); q is the cross-attention Q projection of decoder layer `layer` (of the stream behind the
+ *             self-attention LayerNorm), k the K half of that layer's projection of the encoder memory.  fp32 [B*N,H,T,Ls].
+ *   mean      M[r,t,j] = (P[r,0,t,j] + P[r,1,t,j] + ... in ascending h, fp32) / (float)H: what nn.MultiheadAttention returns
+ *             with average_attn_weights=True.  fp32 [B*N,T,Ls].
+ *   align     A[r,t] = the smallest j with M[r,t,j] == max_j M[r,t,:] (the first maximum), -1 where t is not live.  int32 [B*N,T].
+ * PAD keys are exactly 0.0, positions that are not live are exactly 0.0 in every element, and a source row that is all PAD gives
+ * zeros, never NaN.  layer is in [0, num_decoder_layers), or -1 for the last.  d_heads, d_mean, d_align and d_length are optional
+ * outputs (NULL: not computed / not handed out), at least one of the first three is required; all of them are written in full by
+ * the kernels, so no caller sees uninitialised memory.  The pass ends at the tapped layer's cross attention: no logits are formed
+ * and the vocabulary limit of scoring does not apply.  Nothing is synchronised.  TTX_ERR_INVALID with nothing launched: no output
+ * requested, layer out of range, Ls above ttx_attn_probs_key_limit(head_dim) or the positional table, W < 2, W - 1 above the
+ * positional table, rows * (W-1) >= 2^24.  A map depends only on its own (source, hypothesis): it is bit-identical from call to
+ * call and across B, N and the padded widths, within the key range scoring documents (ttx_attn_staged_key_limit). */
+int ttx_attention_maps(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N, int W, int eos,
+                       int layer, float* d_heads, float* d_mean, int32_t* d_align, int32_t* d_length, void* stream);
+
+/* Host query, no device needed: the largest Ls k_attn_probs takes at head dimension head_dim (1024 at 32 and 64; 0 for a head
+ * dimension without kernels). */
+int ttx_attn_probs_key_limit(int head_dim);
+
 /* Draft maker: make_drafts (src/utils/drafting.py:5-67) on the device.  d_src int64 [B,L];
  * d_drafts int64 [B,n_drafts,D] out with D = clamp(draft_len, min_draft_len, max_draft_len). */
 int ttx_make_drafts(ttx_session* s, const int64_t* d_src, int B, int L, int draft_len, int n_drafts,
@@ -604,6 +631,17 @@ int ttx_attn_staged_key_limit(int head_dim, int q_per_group);
  * ttx_debug_attn, 1 k_attn .. 5 k_attn1), counted where a launch is issued (under graphs: when a step is captured).  A negative
  * error code for a null session. */
 int ttx_debug_attn_kernels_seen(ttx_session* s);
+
+/* Test entry: ONE launch of k_attn_probs (csrc/ttx_attn_probs.hip.h) on operands of the test.  d_q fp32 [R*T, ldq] and d_k fp32
+ * [Rm*Ls, ldkv] with head h at columns h*head_dim .. (H * head_dim need not be a model width; head_dim 32 or 64); d_key_pad u8
+ * [Rm*Ls], non-zero = PAD; d_mem_row int32 [R] (NULL: row r reads memory row r, Rm == R; a value outside [0, Rm) reads as a
+ * memory row of PAD keys); d_length int32 [R]: position t of row r is live iff t < length[r].  Outputs as ttx_attention_maps has
+ * them, each optional, at least one required: d_heads [R,H,T,Ls], d_mean [R,T,Ls], d_align [R,T].  Rows go out as 16-byte stores
+ * when Ls % 4 == 0 and the bases are 16-byte aligned, else 4 bytes at a time, with the same bits.  Keys appended as PAD change no
+ * bit of the other columns.  TTX_ERR_INVALID with nothing launched for Ls above ttx_attn_probs_key_limit(head_dim). */
+int ttx_debug_attn_probs(ttx_session* s, const float* d_q, int ldq, const float* d_k, int ldkv, const uint8_t* d_key_pad,
+                         const int32_t* d_mem_row, const int32_t* d_length, int R, int Rm, int H, int head_dim, int T, int Ls,
+                         float scale, float* d_heads, float* d_mean, int32_t* d_align, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@
 #include "ttx_loop_kernels.hip.h"
 #include "ttx_metrics.hip.h"
 #include "ttx_score.hip.h"
+#include "ttx_attn_probs.hip.h"
 #include "ttx_tokenizer.h"
 
 #include <algorithm>
@@ -485,9 +486,10 @@ struct StackRows {
 // Decoder layers and classifier over the embedded rows in s->x: per layer QKV GEMM, self attention, out-projection + LN, Q GEMM,
 // cross attention, out-projection + LN, feed-forward (+ the final norm behind the last layer); then logits = classifier(xf).
 // self_attn(l, qkv) and cross_attn(l) launch layer l's attention from the layer's Q/K/V rows / from s->q2 into s->ao.
+// stop_layer >= 0: the pass ends behind cross_attn(stop_layer) (the cross-attention tap: nothing downstream of s->q2 is wanted).
 template <class SelfAttn, class CrossAttn>
 static int run_decoder_stack(ttx_session* s, hipStream_t st, const StackRows& r, SelfAttn&& self_attn, CrossAttn&& cross_attn,
-                             float* logits) {
+                             float* logits, int stop_layer = -1) {
   const ttx_model* m = s->m;
   const ttx_config& c = m->cfg;
   const int d = c.embedding_dim, V = c.vocab_size, Ld = c.num_decoder_layers;
@@ -507,6 +509,7 @@ static int run_decoder_stack(ttx_session* s, hipStream_t st, const StackRows& r,
                     nullptr, x1, r.m_ptr, r.Mmax, r.v_dd));
     TTX_TRY(launch_gemm(s, st, x1, d, m->p(w.ca_in_w), d, m->p(w.ca_in_b), q2, d, r.m_ptr, r.Mmax, d, d, false, 0, 0, r.v_dd));
     TTX_TRY(cross_attn(l));
+    if (l == stop_layer) return TTX_OK;
     TTX_TRY(gemm_ln(s, st, ao, d, d, m->p(w.ca_out_w), m->p(w.ca_out_b), x1, m->p(w.n2_w), m->p(w.n2_b), nullptr, nullptr,
                     nullptr, x2, r.m_ptr, r.Mmax, r.v_dd));
     TTX_TRY(ffn_half(s, st, w, x2, w.n3_w, w.n3_b, last ? m->p(m->dec_norm_w) : nullptr, last ? m->p(m->dec_norm_b) : nullptr,
@@ -515,9 +518,23 @@ static int run_decoder_stack(ttx_session* s, hipStream_t st, const StackRows& r,
   return launch_gemm(s, st, xf, d, m->p(m->cls_w), d, m->p(m->cls_b), logits, V, r.m_ptr, r.Mmax, V, d, false, 0, 0, r.v_dd);
 }
 
-// Full-prefix decoder (modules.py:118-138).  tok int32 [R*Lt]; memory fp32 [Rm*Ls, d]; mem_pad u8 [Rm*Ls].
+// The cross-attention tap of run_decoder_full: the probabilities of decoder layer `layer` (csrc/ttx_attn_probs.hip.h).
+struct AttnTap {
+  int layer;
+  const int* length;                 // [R]: query position t of row r is live iff t < length[r]
+  float* heads;                      // [R, H, Lt, Ls] or null
+  float* mean;                       // [R, Lt, Ls] or null
+  int* align;                        // [R, Lt] or null
+};
+
+static int launch_attn_probs(ttx_session* s, hipStream_t st, const AttnProbsArgs& a, int head_dim);
+
+// Full-prefix decoder (modules.py:118-138).  tok int32 [R*Lt]; memory fp32 [Rm*Ls, d]; mem_pad u8 [Rm*Ls].  With a tap the pass
+// ends at the tapped layer's cross attention: its K projection of the memory, its Q projection, k_attn_probs, and nothing after
+// (logits are not formed); without one the launches are the same as ever.
 static int run_decoder_full(ttx_session* s, hipStream_t st, const int* tok, int R, int Lt, const float* memory,
-                            const uint8_t* mem_pad, const int* mem_row, int Rm, int Ls, float* logits) {
+                            const uint8_t* mem_pad, const int* mem_row, int Rm, int Ls, float* logits,
+                            const AttnTap* tap = nullptr) {
   const ttx_model* m = s->m;
   const ttx_config& c = m->cfg;
   const int d = c.embedding_dim, H = c.num_heads;
@@ -545,12 +562,19 @@ static int run_decoder_full(ttx_session* s, hipStream_t st, const int* tok, int 
         const LayerW& w = m->dec[l];
         TTX_TRY(launch_gemm(s, st, memory, d, m->p(w.ca_in_w) + (size_t)d * d, d, m->p(w.ca_in_b) + d, ckv, 2 * d, nullptr, Mk,
                             2 * d, d, false, 0, 0, gv));
+        if (tap && l == tap->layer) {
+          AttnProbsArgs pa{};
+          pa.q = s->q2.as<float>(); pa.ldq = d; pa.k = ckv; pa.ldkv = 2 * d; pa.key_pad = mem_pad; pa.mem_row = mem_row;
+          pa.length = tap->length; pa.heads = tap->heads; pa.mean = tap->mean; pa.align = tap->align;
+          pa.R = R; pa.Rm = Rm; pa.H = H; pa.T = Lt; pa.Ls = Ls; pa.scale = scale;
+          return launch_attn_probs(s, st, pa, d / H);
+        }
         AttnArgs ca{};
         ca.q = s->q2.as<float>(); ca.ldq = d; ca.k = ckv; ca.v = ckv + d; ca.ldkv = 2 * d; ca.out = ao; ca.d = d; ca.scale = scale;
         ca.L = Lt; ca.Lk = Ls; ca.key_pad = mem_pad; ca.mem_row = mem_row;
         return launch_attn(ATT_FULL_CROSS, s, st, ca, R, H, Lt, Ls);
       },
-      logits);
+      logits, tap ? tap->layer : -1);
 }
 
 extern "C" int ttx_decode_tgt(ttx_session* s, const int64_t* d_tgt, int R, int Lt, const float* d_memory,
@@ -748,6 +772,105 @@ static int raise_lds_limit(const void* kernel, size_t lds, bool& done) {
     done = true;
   }
   return TTX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Cross-attention maps of hypotheses: csrc/ttx_attn_probs.hip.h.
+static int attn_probs_key_limit(int head_dim) { return (head_dim == 32 || head_dim == 64) ? AP_MAX_KEYS : 0; }
+
+template <int DH>
+static int launch_attn_probs_dh(ttx_session* s, hipStream_t st, const AttnProbsArgs& a, bool vec_out, bool vec_k, size_t lds) {
+  const int grid = a.R * cdiv(a.T, AP_TQ);
+  bool* done = &s->attr_attn_probs[(DH == 64 ? 4 : 0) + (vec_out ? 2 : 0) + (vec_k ? 1 : 0)];
+#define TTX_AP_LAUNCH(VO, VK)                                                                                        \
+  do {                                                                                                               \
+    TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_attn_probs<DH, VO, VK>), lds, *done));                  \
+    hipLaunchKernelGGL((k_attn_probs<DH, VO, VK>), dim3(grid), dim3(AP_THREADS), lds, st, a);                        \
+  } while (0)
+  if (vec_out && vec_k) TTX_AP_LAUNCH(true, true);
+  else if (vec_out) TTX_AP_LAUNCH(true, false);
+  else if (vec_k) TTX_AP_LAUNCH(false, true);
+  else TTX_AP_LAUNCH(false, false);
+#undef TTX_AP_LAUNCH
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+// ONE launch of k_attn_probs.  The 16-byte forms are chosen from the arguments alone and give the same bits as the 4-byte ones.
+static int launch_attn_probs(ttx_session* s, hipStream_t st, const AttnProbsArgs& a, int head_dim) {
+  const int limit = attn_probs_key_limit(head_dim);
+  if (limit == 0) return fail(TTX_ERR_INVALID, "attention maps: head dimension must be 32 or 64");
+  if (a.R <= 0 || a.Rm <= 0 || a.H <= 0 || a.T <= 0 || a.Ls <= 0 || a.ldq < a.H * head_dim || a.ldkv < a.H * head_dim)
+    return fail(TTX_ERR_INVALID, "attention maps: R, Rm, H, T, Ls > 0 and ldq, ldkv >= H * head_dim");
+  if (a.Ls > limit)
+    return fail(TTX_ERR_INVALID, "attention maps: source longer than " + std::to_string(limit) + " keys (ttx_attn_probs_key_limit)");
+  if ((long long)a.R * a.T >= (1LL << 24)) return fail(TTX_ERR_INVALID, "attention maps: more than 2^24 positions in one call");
+  auto al16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+  const bool vec_out = a.Ls % 4 == 0 && al16(a.heads) && al16(a.mean);
+  const bool vec_k = a.ldkv % 4 == 0 && al16(a.k);
+  const size_t lds = ap_lds_bytes(a.Ls, head_dim, a.mean || a.align);
+  return head_dim == 64 ? launch_attn_probs_dh<64>(s, st, a, vec_out, vec_k, lds) : launch_attn_probs_dh<32>(s, st, a, vec_out, vec_k, lds);
+}
+
+extern "C" int ttx_attn_probs_key_limit(int head_dim) { return attn_probs_key_limit(head_dim); }
+
+extern "C" int ttx_debug_attn_probs(ttx_session* s, const float* d_q, int ldq, const float* d_k, int ldkv, const uint8_t* d_key_pad,
+                                    const int32_t* d_mem_row, const int32_t* d_length, int R, int Rm, int H, int head_dim, int T,
+                                    int Ls, float scale, float* d_heads, float* d_mean, int32_t* d_align, void* stream) {
+  if (!s) return session_required("ttx_debug_attn_probs");
+  if (!d_q || !d_k || !d_key_pad || !d_length || (!d_heads && !d_mean && !d_align))
+    return fail(TTX_ERR_INVALID, "bad argument to ttx_debug_attn_probs");
+  if (!d_mem_row && Rm != R) return fail(TTX_ERR_INVALID, "ttx_debug_attn_probs: without a row map the memory must have one row per query row");
+  HIP_TRY(hipSetDevice(s->m->device));
+  AttnProbsArgs a{};
+  a.q = d_q; a.ldq = ldq; a.k = d_k; a.ldkv = ldkv; a.key_pad = d_key_pad; a.mem_row = d_mem_row; a.length = d_length;
+  a.heads = d_heads; a.mean = d_mean; a.align = d_align; a.R = R; a.Rm = Rm; a.H = H; a.T = T; a.Ls = Ls; a.scale = scale;
+  return launch_attn_probs(s, reinterpret_cast<hipStream_t>(stream), a, head_dim);
+}
+
+extern "C" int ttx_attention_maps(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N, int W,
+                                  int eos, int layer, float* d_heads, float* d_mean, int32_t* d_align, int32_t* d_length,
+                                  void* stream) {
+  if (!s) return session_required("ttx_attention_maps");
+  if (!d_src || !d_hyp || B <= 0 || N <= 0 || Ls <= 0) return fail(TTX_ERR_INVALID, "bad argument to ttx_attention_maps");
+  if (!d_heads && !d_mean && !d_align) return fail(TTX_ERR_INVALID, "ttx_attention_maps: no output requested (heads, mean and alignment are all null)");
+  if (ld_hyp < W) return fail(TTX_ERR_INVALID, "ttx_attention_maps: row stride ld_hyp smaller than W");
+  const ttx_config& c = s->m->cfg;
+  if (layer == -1) layer = c.num_decoder_layers - 1;
+  if (layer < 0 || layer >= c.num_decoder_layers)
+    return fail(TTX_ERR_INVALID, "ttx_attention_maps: layer must be -1 or in [0, " + std::to_string(c.num_decoder_layers) + ")");
+  // the position limits of scoring; its vocabulary limit does not apply (no logits are formed)
+  TTX_TRY(check_score_shapes(s, (long long)B * N, W, 1, "ttx_attention_maps"));
+  if (Ls > c.max_positions) return fail(TTX_ERR_INVALID, "source longer than the positional table");
+  const int limit = attn_probs_key_limit(c.embedding_dim / c.num_heads);
+  if (Ls > limit)
+    return fail(TTX_ERR_INVALID, "ttx_attention_maps: source longer than " + std::to_string(limit) + " keys (ttx_attn_probs_key_limit)");
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->m->device));
+  const int R = B * N, T = W - 1, d = c.embedding_dim;
+  if (!d_length) {
+    TTX_TRY(ensure(s->am_length, (size_t)R * 4, st));
+    d_length = s->am_length.as<int32_t>();
+  }
+  // as ttx_score_hypotheses: the encoder once per source; decoder row r attends to memory row r / N
+  TTX_TRY(ensure(s->memory, (size_t)B * Ls * d * 4, st));
+  TTX_TRY(ensure(s->mem_pad_tmp, (size_t)B * Ls, st));
+  TTX_TRY(ensure(s->sc_src_of, (size_t)R * 4, st));
+  TTX_TRY(ttx_encode_src(s, d_src, B, Ls, s->memory.as<float>(), stream));
+  hipLaunchKernelGGL(k_invert_mask, dim3(cdiv(B * Ls, 256)), dim3(256), 0, st, s->src_valid.as<uint8_t>(),
+                     s->mem_pad_tmp.as<uint8_t>(), B * Ls);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_score_src_of, dim3(cdiv(R, 256)), dim3(256), 0, st, s->sc_src_of.as<int>(), R, N);
+  HIP_TRY(hipGetLastError());
+  TTX_TRY(ensure(s->tok_tgt, (size_t)R * T * 4, st));
+  hipLaunchKernelGGL(k_prepare_tokens_2d, dim3(cdiv(R * T, 256)), dim3(256), 0, st, d_hyp, ld_hyp, s->tok_tgt.as<int>(),
+                     (uint8_t*)nullptr, R, T, c.pad_token);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_hyp_length, dim3(cdiv(R, 4)), dim3(256), 0, st, d_hyp, ld_hyp, R, W, c.pad_token, eos, d_length);
+  HIP_TRY(hipGetLastError());
+  const AttnTap tap{layer, d_length, d_heads, d_mean, d_align};
+  return run_decoder_full(s, st, s->tok_tgt.as<int>(), R, T, s->memory.as<float>(), s->mem_pad_tmp.as<uint8_t>(),
+                          s->sc_src_of.as<int>(), B, Ls, nullptr, &tap);
 }
 
 static int clamp_draft_len(int draft_len, int lo, int hi) { return std::min(std::max(lo, draft_len), hi); }

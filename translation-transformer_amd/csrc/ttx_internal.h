@@ -105,7 +105,7 @@ struct GraphCache {
   X(ev_logits) X(ev_pred) X(ev_nll)                                                                                              \
   /* hypothesis scoring (ttx_score_hypotheses): decoder row -> memory row; logits / per-token values it does not hand out live */ \
   /* in ev_logits / ev_nll */                                                                                                    \
-  X(sc_src_of)                                                                                                                   \
+  X(sc_src_of) X(am_length)                                                                                                                   \
   /* loop */                                                                                                                     \
   X(drafts) X(gen) X(front) X(act_idx) X(rec) X(pred) X(state) X(kcache) X(vcache) X(src32) X(outbuf) X(haspad) X(traj)           \
   X(fin_step)                                                                                                                    \
@@ -161,6 +161,7 @@ struct ttx_session {
   // function attributes (dynamic LDS limits) are per device: set once per session, outside graph capture
   bool attr_attn2[2][8] = {};      // [head dimension 32 / 64][mode]
   bool attr_select = false, attr_step = false, attr_topk = false, attr_pool_select = false;
+  bool attr_attn_probs[8] = {};    // k_attn_probs: [head dimension 32 / 64][16-byte output stores][16-byte key loads]
   // GEMM policy (all choices are between bit-identical evaluations, see GemmVariant)
   int qkv_small_rows = 800;        // a verify step with fewer live rows than this runs under GV_SMALL (TTX_QKV_SMALL_ROWS)
   int small_rows = 2000;           // ... with fewer than this under GV_MID (TTX_SMALL_ROWS)

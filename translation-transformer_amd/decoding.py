@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .model import HypothesisScores, NativeTransformer
+from .model import AttentionMaps, HypothesisScores, NativeTransformer
 
 
 def _need_native(model) -> NativeTransformer:
@@ -34,6 +34,14 @@ class _ScoresHypotheses:
         if pad != self.model.tgt_pad_token_i:
             raise ValueError("the generator's pad token differs from the model's")
         return self.model.score_hypotheses(src, pred, eos_token_idx=eos, **kw)
+
+    def attention(self, src: torch.Tensor, pred: torch.Tensor, **kw) -> AttentionMaps:
+        """Cross-attention maps and source alignments of the hypotheses ``pred`` (Long[B, N, L] as ``generate(src)`` returned
+        it), from the same teacher-forced pass as ``score``.  Keywords go to ``attention_maps``."""
+        pad, eos = self._pad_eos()
+        if pad != self.model.tgt_pad_token_i:
+            raise ValueError("the generator's pad token differs from the model's")
+        return self.model.attention_maps(src, pred, eos_token_idx=eos, **kw)
 
     def _scored(self, src: torch.Tensor, pred: torch.Tensor, return_scores: bool):
         return (pred, self.score(src, pred)) if return_scores else pred

@@ -199,6 +199,12 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         # like predict_window no init_arg — set the attribute or TTX_PREDICT_SCORES=1
         self.predict_with_scores = False
         self.predict_scores: dict = {}
+        # predict_step also keeps the source alignment of its hypotheses (NativeTransformer.attention_maps, last layer) as
+        # self.predict_alignments[batch_idx] = (alignment, length) — the alignment, not the maps: a window of 256 batches of
+        # maps does not belong in memory.  No init_arg either — set the attribute or TTX_PREDICT_ATTENTION=1
+        self.predict_with_attention = False
+        self.predict_alignments: dict = {}
+        self._attention_on = False
         self.report_prediction_time = report_prediction_time
         self.prediction_start_time = None
 
@@ -262,6 +268,8 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             pred = self.generator.generate(batch["src_tokens"])
         if self._scores_on:
             self._score_batch(batch["src_tokens"], pred, batch_idx)
+        if self._attention_on:
+            self._align_batch(batch["src_tokens"], pred, batch_idx)
         return pred
 
     def _score_batch(self, src: torch.Tensor, pred: torch.Tensor, batch_idx: int) -> None:
@@ -276,6 +284,16 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         self._top1_sum = self._top1_sum + sc.score[:, 0].double().sum()      # kept on the device until the report
         self._top1_n += int(sc.score.shape[0])
         self._unfinished = self._unfinished + (~sc.finished).sum()
+
+    def _align_batch(self, src: torch.Tensor, pred: torch.Tensor, batch_idx: int) -> None:
+        """The batch's source alignments, whether it was decoded ahead or on the spot; the token tensor predict_step returns
+        stays what it was.  Timed like _score_batch."""
+        torch.cuda.synchronize()
+        t0 = timer()
+        maps = self.generator.attention(src, pred)
+        torch.cuda.synchronize()
+        self._attention_seconds += timer() - t0
+        self.predict_alignments[batch_idx] = (maps.alignment, maps.length)
 
     def _predict_loader(self):
         """The (first) predict dataloader Trainer.predict iterates, or None."""
@@ -299,6 +317,9 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         self._ahead = None
         self._scores_on = bool(self.predict_with_scores) or os.environ.get("TTX_PREDICT_SCORES") == "1"
         self.predict_scores = {}
+        self._attention_on = bool(self.predict_with_attention) or os.environ.get("TTX_PREDICT_ATTENTION") == "1"
+        self.predict_alignments = {}
+        self._attention_seconds = 0.0
         self._scoring_seconds, self._top1_n, self._top1_sum, self._unfinished = 0.0, 0, 0.0, 0
         window = int(os.environ.get("TTX_PREDICT_WINDOW", str(self.predict_window)))
         if window > 0 and hasattr(self.generator, "generate_many"):
@@ -336,6 +357,8 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             report["scoring_seconds"] = round(self._scoring_seconds, 6)
             report["mean_top1_logprob"] = round(float(self._top1_sum) / max(1, self._top1_n), 6)
             report["unfinished_hypotheses"] = int(self._unfinished)
+        if self._attention_on:
+            report["attention_seconds"] = round(self._attention_seconds, 6)
         text = json.dumps(report)
         print(text)
         if h.report_prediction_file is not None:

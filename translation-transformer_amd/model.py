@@ -76,6 +76,16 @@ class HypothesisScores(NamedTuple):
     token_logp: torch.Tensor | None  # fp32 [B, N, W-1] when asked for
 
 
+class AttentionMaps(NamedTuple):
+    """Result of ``NativeTransformer.attention_maps``: device tensors, nothing copied to the host.  Query position ``t`` of
+    hypothesis ``hyp[b, k]`` (the one that predicts ``hyp[b, k, t+1]``) is live iff ``t + 1 <= length[b, k]``; ``attn`` is the
+    cross-attention of one decoder layer over the source positions, exactly 0.0 at PAD keys and at positions that are not
+    live; ``alignment[b, k, t]`` is the source position of the first maximum of the head-mean map, -1 where not live."""
+    attn: torch.Tensor               # fp32 [B, N, W-1, Ls] (heads="mean") or [B, N, H, W-1, Ls] (heads="all")
+    alignment: torch.Tensor | None   # int32 [B, N, W-1] when asked for
+    length: torch.Tensor             # int32 [B, N]: as HypothesisScores.length
+
+
 class NativeTransformer:
     # score_hypotheses: decoder positions (rows x columns) of one call; the widest activation buffer takes ff_dim floats per
     # position (256 MiB at ff_dim 2048), and a bench batch of 32 rows x 199 columns still fits one call
@@ -247,6 +257,25 @@ class NativeTransformer:
                                             int(cache_seq_stride), self._ptr(cache_slot), int(gen_ld), int(n), int(d), int(mode),
                                             int(groups), int(n_active), int(max_keys), int(kernel), C.byref(kid), self._stream()))
         return int(kid.value)
+
+    def debug_attn_probs(self, q: torch.Tensor, k: torch.Tensor, key_pad: torch.Tensor, length: torch.Tensor, heads: int,
+                         head_dim: int, T: int, Ls: int, scale: float, mem_row: torch.Tensor | None = None,
+                         out_heads: torch.Tensor | None = None, out_mean: torch.Tensor | None = None,
+                         out_align: torch.Tensor | None = None) -> None:
+        """One k_attn_probs launch on the caller's device tensors (ttx_debug_attn_probs): ``q`` [R*T, >= heads*head_dim] and
+        ``k`` [Rm*Ls, >= heads*head_dim] are 2-D fp32 views whose row strides are the leading dimensions, ``key_pad`` uint8
+        [Rm*Ls], ``length`` int32 [R], ``mem_row`` int32 [R] or None; the outputs are written in place: ``out_heads``
+        fp32 [R, heads, T, Ls], ``out_mean`` fp32 [R, T, Ls], ``out_align`` int32 [R, T], each optional."""
+        R, Rm = int(length.numel()), int(key_pad.numel()) // int(Ls)
+        N.check(self._lib.ttx_debug_attn_probs(self._session, q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), key_pad.data_ptr(),
+                                               self._ptr(mem_row), length.data_ptr(), R, Rm, int(heads), int(head_dim), int(T), int(Ls),
+                                               float(scale), self._ptr(out_heads), self._ptr(out_mean), self._ptr(out_align),
+                                               self._stream()))
+
+    @staticmethod
+    def attn_probs_key_limit(head_dim: int) -> int:
+        """The longest source ``attention_maps`` takes at ``head_dim`` (ttx_attn_probs_key_limit; a host query)."""
+        return int(N.lib().ttx_attn_probs_key_limit(int(head_dim)))
 
     def debug_argmax(self, logits: torch.Tensor, pred: torch.Tensor, m_max: int, m_live: torch.Tensor | None = None) -> None:
         """One k_argmax launch (ttx_debug_argmax): ``logits`` fp32 [m_max, V] contiguous, ``pred`` int32 [m_max], ``m_live`` an
@@ -522,6 +551,18 @@ class NativeTransformer:
             self._score_session = self.new_session()
         return self._score_session
 
+    def _trim_and_chunk(self, hyp: torch.Tensor, eos: int, trim: bool, max_rows: int | None) -> tuple:
+        """(Wt, chunk) of one teacher-forced pass over ``hyp`` Long[B, N, W]: the columns that are run (``trim``: the longest
+        non-PAD extent of the batch, one scalar device-to-host read) and the sources per library call, so that one call runs at
+        most ``max_rows`` decoder positions (a single source is never split)."""
+        _, K, W = hyp.shape
+        Wt = W
+        if trim:
+            cols = torch.arange(1, W + 1, device=self.device)
+            Wt = min(W, max(2, int((((hyp != self.tgt_pad_token_i) | (hyp == eos)) * cols).amax())))
+        limit = min(int(max_rows or self.SCORE_MAX_ROWS), (1 << 24) - 1)
+        return Wt, max(1, limit // (K * (Wt - 1)))
+
     def hypothesis_logprobs(self, logits: torch.Tensor, hyp: torch.Tensor, pad: int, eos: int) -> HypothesisScores:
         """The scoring stage alone (ttx_hypothesis_logprobs): ``logits`` fp32 [..., W-1, V] as ``decode_tgt(hyp[..., :-1])``
         gives them, ``hyp`` Long[..., W] with the same leading shape.  Nothing is synchronised."""
@@ -566,14 +607,8 @@ class NativeTransformer:
         self.check_tokens(src)
         self.check_tokens(hyp, self.tgt_vocab_size)
         (B, Ls), (_, K, W) = src.shape, hyp.shape
-        pad, eos = self.tgt_pad_token_i, int(eos_token_idx)
-        Wt = W
-        if trim:
-            cols = torch.arange(1, W + 1, device=self.device)
-            Wt = min(W, max(2, int((((hyp != pad) | (hyp == eos)) * cols).amax())))
-        per_src = K * (Wt - 1)
-        limit = min(int(max_rows or self.SCORE_MAX_ROWS), (1 << 24) - 1)
-        chunk = max(1, limit // per_src)
+        eos = int(eos_token_idx)
+        Wt, chunk = self._trim_and_chunk(hyp, eos, trim, max_rows)
         if logits_out is not None:
             if Wt != W or chunk < B or tuple(logits_out.shape) != (B * K, W - 1, self.tgt_vocab_size) \
                     or logits_out.dtype != torch.float32 or not logits_out.is_contiguous() or logits_out.device != self.device:
@@ -596,6 +631,52 @@ class NativeTransformer:
             if part is not None and Wt != W:
                 tok[b0:b1, :, :Wt - 1] = part
         return HypothesisScores(score, length, fin, tok)
+
+    # -- cross-attention maps of hypotheses -----------------------------------------------------
+    def attention_maps(self, src: torch.Tensor, hyp: torch.Tensor, eos_token_idx: int = 2, layer: int = -1, heads: str = "mean",
+                       return_alignment: bool = True, max_rows: int | None = None, trim: bool = True) -> AttentionMaps:
+        """Which source positions every token of hypothesis ``hyp[b, k]`` (Long[B, N, W]) attended to: the cross-attention
+        probabilities of decoder layer ``layer`` (-1: the last) in the model's own teacher-forced pass on the hypothesis
+        (ttx_attention_maps).  ``heads="mean"`` gives the head average fp32 [B, N, W-1, Ls] (what ``nn.MultiheadAttention``
+        returns with ``average_attn_weights=True``), ``heads="all"`` every head, fp32 [B, N, H, W-1, Ls].  The pass ends at the
+        tapped layer: no later layer, no logits.
+
+        ``trim`` and ``max_rows`` behave as in ``score_hypotheses``: one scalar device-to-host read or none, whole sources per
+        chunk of at most ``max_rows`` decoder positions, which also bounds the map bytes one library call writes
+        (``positions * Ls * 4``, times H for ``"all"``).  Results keep the full ``W-1``: zeros / -1 past the trimmed width."""
+        if heads not in ("mean", "all"):
+            raise ValueError(f"heads must be 'mean' or 'all', got {heads!r}")
+        src, hyp = self._tokens(src), self._tokens(hyp)
+        if src.dim() != 2 or hyp.dim() != 3 or hyp.shape[0] != src.shape[0] or hyp.shape[1] < 1 or hyp.shape[2] < 2:
+            raise ValueError(f"attention_maps needs hyp [B, N >= 1, W >= 2] for src [B, Ls]; got {tuple(hyp.shape)} for "
+                             f"{tuple(src.shape)}")
+        self.check_tokens(src)
+        self.check_tokens(hyp, self.tgt_vocab_size)
+        (B, Ls), (_, K, W) = src.shape, hyp.shape
+        eos, H = int(eos_token_idx), self.num_heads
+        Wt, chunk = self._trim_and_chunk(hyp, eos, trim, max_rows)
+        T, Tt = W - 1, Wt - 1
+        shape = (B, K, H, T, Ls) if heads == "all" else (B, K, T, Ls)
+        attn = (torch.empty if Wt == W else torch.zeros)(shape, dtype=torch.float32, device=self.device)
+        align = torch.full((B, K, T), -1, dtype=torch.int32, device=self.device) if return_alignment else None
+        length = torch.empty((B, K), dtype=torch.int32, device=self.device)
+        sess, stream = self._scoring_session(), self._stream()
+        for b0 in range(0, B, chunk):
+            b1 = min(B, b0 + chunk)
+            if Wt == W:
+                a_part, al_part = attn[b0:b1], (align[b0:b1] if align is not None else None)
+            else:
+                a_part = torch.empty((b1 - b0,) + shape[1:-2] + (Tt, Ls), dtype=torch.float32, device=self.device)
+                al_part = torch.empty((b1 - b0, K, Tt), dtype=torch.int32, device=self.device) if align is not None else None
+            N.check(self._lib.ttx_attention_maps(sess, src[b0:b1].data_ptr(), b1 - b0, Ls, hyp[b0:b1].data_ptr(), W, K, Wt, eos,
+                                                 int(layer), a_part.data_ptr() if heads == "all" else None,
+                                                 a_part.data_ptr() if heads == "mean" else None, self._ptr(al_part),
+                                                 length[b0:b1].data_ptr(), stream))
+            if Wt != W:
+                attn[b0:b1, ..., :Tt, :] = a_part
+                if align is not None:
+                    align[b0:b1, :, :Tt] = al_part
+        return AttentionMaps(attn, align, length)
 
     # -- beam-speculative bookkeeping kernels --------------------------------------------------
     def nucleus_mask(self, logits: torch.Tensor, nucleus: float, max_kept: int, fill: float) -> torch.Tensor:

@@ -145,6 +145,23 @@ def read_scores(filename: str) -> list:
     return rows
 
 
+def write_alignments(filename: str, maps, append: bool = True) -> None:
+    """The alignment side file of the prediction CSV: one line per source, the hypotheses separated by commas in the order of
+    the CSV's ``prediction_1..N`` columns, each the source positions of its live query positions separated by spaces (position
+    ``t`` aligns the token ``t + 1`` of the hypothesis; a hypothesis of length 0 gives an empty field).  ``maps``: an
+    AttentionMaps (or anything with ``alignment`` [B,N,T] and ``length`` [B,N]).  The prediction CSV itself is left as it is."""
+    al, ln = (t.detach().cpu().tolist() for t in (maps.alignment, maps.length))
+    with open(filename, "a" if append else "w") as f:
+        for a_row, l_row in zip(al, ln):
+            print(",".join(" ".join(str(int(j)) for j in a[:int(n)]) for a, n in zip(a_row, l_row)), file=f)
+
+
+def read_alignments(filename: str) -> list:
+    """What ``write_alignments`` wrote: per source a list of per-hypothesis lists of source positions."""
+    with open(filename) as f:
+        return [[[int(j) for j in field.split()] for field in line.rstrip("\n").split(",")] for line in f]
+
+
 def _fmt(d: dict) -> str:
     w = max(len(k) for k in d)
     return "\n".join(f"{k.ljust(w)}    {'n/a' if v is None else round(v, 6)}" for k, v in d.items())
