@@ -154,6 +154,37 @@ int ttx_score_hypotheses(ttx_session* s, const int64_t* d_src, int B, int Ls, co
                          int eos, float* d_logits, float* d_tok_logp, float* d_score, int32_t* d_length, uint8_t* d_finished,
                          void* stream);
 
+/* Per-position alternatives of hypotheses: what else the model considered where it emitted a token.  Hypothesis rows, logits, n
+ * and the limits as for the scoring pair above; T = W - 1; x = logits[r,p,:]; position p of row r is live iff p < n, and for a live
+ * position, t = h[p+1] and 1 <= k <= min(32, V):
+ *   top_id       [p,j], j = 0..k-1: the ids of the k largest logits, largest first; equal logits: the lower id first (-0.0 equals
+ *                0.0, a -inf logit is an ordinary value that sorts last).  int32 [R,T,k].
+ *   top_logp     [p,j] = log_softmax(x)[top_id[p,j]], evaluated as -(log1pf(rs) + (m - x[id])) with the (m, rs) of the scoring
+ *                stage, so that top_logp[p,0] == -log1pf(rs).  fp32 [R,T,k].
+ *   chosen_logp  [p] = that value for t: tok_logp[p] of the scoring pair on the same logits, bit for bit (for V % 4 == 0 on a
+ *                16-byte aligned d_logits, which is what the decoder writes).  fp32 [R,T].
+ *   rank         [p] = the number of ids v with x[v] > x[t], or x[v] == x[t] and v < t: 0 when the emitted token was the first
+ *                maximum, and top_id[p, rank[p]] == t whenever rank[p] < k.  int32 [R,T].
+ *   entropy      [p] = -sum_v q_v log q_v in nats, q = softmax(x), fp32 in one fixed order; a -inf logit contributes exactly 0.
+ *                fp32 [R,T].
+ *   length       [r] = n.  int32 [R].
+ * Positions that are not live hold top_id = -1, top_logp = 0, chosen_logp = 0, rank = -1, entropy = 0 in every element; all
+ * outputs are written in full by the kernels.  Every output is optional (NULL: not handed out); at least one of the five
+ * per-position outputs is required.  A row whose maximum logit is not finite is outside the contract and still gives ids and
+ * ranks in [0, V).  Nothing is synchronised.  TTX_ERR_INVALID with nothing launched: the limits of the scoring pair, k < 1,
+ * k > 32, k > V, no output requested, ld_hyp < W, Ls above the positional table.  A position's outputs depend only on its own
+ * logits row and hypothesis: bit-identical from call to call, across batching and padded widths, and for a d_logits base that is
+ * or is not 16-byte aligned.
+ * ttx_hypothesis_alternatives: the stage alone over caller-provided logits fp32 [R,W-1,V]; d_hyp int64 [R,W].
+ * ttx_score_alternatives: exactly the pass of ttx_score_hypotheses (d_hyp rows of stride ld_hyp >= W, d_logits [B*N,W-1,V] or
+ * NULL for session scratch), then the stage. */
+int ttx_hypothesis_alternatives(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad, int eos,
+                                int k, int32_t* d_top_id, float* d_top_logp, float* d_chosen_logp, int32_t* d_rank,
+                                float* d_entropy, int32_t* d_length, void* stream);
+int ttx_score_alternatives(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N, int W,
+                           int eos, int k, float* d_logits, int32_t* d_top_id, float* d_top_logp, float* d_chosen_logp,
+                           int32_t* d_rank, float* d_entropy, int32_t* d_length, void* stream);
+
 /* Cross-attention maps of hypotheses: which source position each output token attended to.  d_src int64 [B,Ls] and d_hyp int64
  * [B*N] rows of stride ld_hyp >= W as for ttx_score_hypotheses; T = W - 1; decoder row r = b*N + k reads hyp[b,k,:T] and attends
  * to memory row b.

@@ -17,7 +17,8 @@ LIB_PATH = PKG_DIR / "libttx_hip.so"
 # translation units (compiled in parallel, linked into one shared library) and the headers every one of them depends on
 UNITS = [CSRC / "ttx_api.hip", CSRC / "ttx_gemm.hip", CSRC / "ttx_attn.hip"]
 HEADERS = [CSRC / "ttx_internal.h", CSRC / "ttx_common.hip.h", CSRC / "ttx_loop_kernels.hip.h", CSRC / "ttx_metrics.hip.h",
-           CSRC / "ttx_score.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_select.h", CSRC / "ttx_tokenizer.h", INCLUDE / "ttx.h"]
+           CSRC / "ttx_score.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_select.h",
+           CSRC / "ttx_tokenizer.h", INCLUDE / "ttx.h"]
 SOURCES = UNITS + HEADERS
 OBJ_DIR = CSRC / "build"
 
@@ -126,6 +127,8 @@ SYMBOLS = {
     "ttx_teacher_forced_eval": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "ttx_hypothesis_logprobs": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "ttx_score_hypotheses": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ttx_hypothesis_alternatives": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ttx_score_alternatives": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ttx_attention_maps": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "ttx_attn_probs_key_limit": (C.c_int, [_I]),
     "ttx_debug_attn_probs": (C.c_int, [_VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, C.c_float, _VP, _VP, _VP, _VP]),

@@ -6,6 +6,7 @@
 #include "ttx_loop_kernels.hip.h"
 #include "ttx_metrics.hip.h"
 #include "ttx_score.hip.h"
+#include "ttx_alternatives.hip.h"
 #include "ttx_attn_probs.hip.h"
 #include "ttx_tokenizer.h"
 
@@ -727,6 +728,30 @@ extern "C" int ttx_hypothesis_logprobs(ttx_session* s, const float* d_logits, co
   return launch_score(s, st, d_logits, d_hyp, W, R, W, V, pad, eos, d_tok_logp, d_score, d_length, d_finished);
 }
 
+// The teacher-forced pass of ttx_score_hypotheses / ttx_score_alternatives: the encoder once per source, the full-prefix decoder
+// over the B*N rows (row r attends to memory row r / N); logits [B*N, W-1, V] into d_logits.
+static int score_forward(ttx_session* s, hipStream_t st, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N,
+                         int W, float* d_logits) {
+  const ttx_config& c = s->m->cfg;
+  const int R = B * N, T = W - 1, d = c.embedding_dim;
+  TTX_TRY(ensure(s->memory, (size_t)B * Ls * d * 4, st));
+  TTX_TRY(ensure(s->mem_pad_tmp, (size_t)B * Ls, st));
+  TTX_TRY(ensure(s->sc_src_of, (size_t)R * 4, st));
+  TTX_TRY(ttx_encode_src(s, d_src, B, Ls, s->memory.as<float>(), (void*)st));
+  hipLaunchKernelGGL(k_invert_mask, dim3(cdiv(B * Ls, 256)), dim3(256), 0, st, s->src_valid.as<uint8_t>(),
+                     s->mem_pad_tmp.as<uint8_t>(), B * Ls);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_score_src_of, dim3(cdiv(R, 256)), dim3(256), 0, st, s->sc_src_of.as<int>(), R, N);
+  HIP_TRY(hipGetLastError());
+  // decode_tgt(hyp[:, :W-1]) without a sliced copy: the decoder's int32 tokens are read off the strided rows directly
+  TTX_TRY(ensure(s->tok_tgt, (size_t)R * T * 4, st));
+  hipLaunchKernelGGL(k_prepare_tokens_2d, dim3(cdiv(R * T, 256)), dim3(256), 0, st, d_hyp, ld_hyp, s->tok_tgt.as<int>(),
+                     (uint8_t*)nullptr, R, T, c.pad_token);
+  HIP_TRY(hipGetLastError());
+  return run_decoder_full(s, st, s->tok_tgt.as<int>(), R, T, s->memory.as<float>(), s->mem_pad_tmp.as<uint8_t>(),
+                          s->sc_src_of.as<int>(), B, Ls, d_logits);
+}
+
 extern "C" int ttx_score_hypotheses(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N,
                                     int W, int eos, float* d_logits, float* d_tok_logp, float* d_score, int32_t* d_length,
                                     uint8_t* d_finished, void* stream) {
@@ -739,29 +764,82 @@ extern "C" int ttx_score_hypotheses(ttx_session* s, const int64_t* d_src, int B,
   if (Ls > c.max_positions) return fail(TTX_ERR_INVALID, "source longer than the positional table");
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(s->m->device));
-  const int R = B * N, T = W - 1, V = c.vocab_size, d = c.embedding_dim;
+  const int R = B * N, T = W - 1, V = c.vocab_size;
   if (!d_logits) {
     TTX_TRY(ensure(s->ev_logits, (size_t)R * T * V * sizeof(float), st));
     d_logits = s->ev_logits.as<float>();
   }
-  // the encoder once per source; decoder row r attends to memory row r / N
-  TTX_TRY(ensure(s->memory, (size_t)B * Ls * d * 4, st));
-  TTX_TRY(ensure(s->mem_pad_tmp, (size_t)B * Ls, st));
-  TTX_TRY(ensure(s->sc_src_of, (size_t)R * 4, st));
-  TTX_TRY(ttx_encode_src(s, d_src, B, Ls, s->memory.as<float>(), stream));
-  hipLaunchKernelGGL(k_invert_mask, dim3(cdiv(B * Ls, 256)), dim3(256), 0, st, s->src_valid.as<uint8_t>(),
-                     s->mem_pad_tmp.as<uint8_t>(), B * Ls);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_score_src_of, dim3(cdiv(R, 256)), dim3(256), 0, st, s->sc_src_of.as<int>(), R, N);
-  HIP_TRY(hipGetLastError());
-  // decode_tgt(hyp[:, :W-1]) without a sliced copy: the decoder's int32 tokens are read off the strided rows directly
-  TTX_TRY(ensure(s->tok_tgt, (size_t)R * T * 4, st));
-  hipLaunchKernelGGL(k_prepare_tokens_2d, dim3(cdiv(R * T, 256)), dim3(256), 0, st, d_hyp, ld_hyp, s->tok_tgt.as<int>(),
-                     (uint8_t*)nullptr, R, T, c.pad_token);
-  HIP_TRY(hipGetLastError());
-  TTX_TRY(run_decoder_full(s, st, s->tok_tgt.as<int>(), R, T, s->memory.as<float>(), s->mem_pad_tmp.as<uint8_t>(),
-                           s->sc_src_of.as<int>(), B, Ls, d_logits));
+  TTX_TRY(score_forward(s, st, d_src, B, Ls, d_hyp, ld_hyp, N, W, d_logits));
   return launch_score(s, st, d_logits, d_hyp, ld_hyp, R, W, V, c.pad_token, eos, d_tok_logp, d_score, d_length, d_finished);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Per-position alternatives of hypotheses: csrc/ttx_alternatives.hip.h.
+static int check_alt_args(int V, int k, const void* top_id, const void* top_logp, const void* chosen, const void* rank,
+                          const void* entropy, const char* fn) {
+  if (k < 1) return fail(TTX_ERR_INVALID, std::string(fn) + ": k must be at least 1");
+  if (k > ALT_MAX_K) return fail(TTX_ERR_INVALID, std::string(fn) + ": k larger than 32");
+  if (k > V) return fail(TTX_ERR_INVALID, std::string(fn) + ": k larger than the vocabulary");
+  if (!top_id && !top_logp && !chosen && !rank && !entropy)
+    return fail(TTX_ERR_INVALID, std::string(fn) + ": no output requested (top_id, top_logp, chosen_logp, rank and entropy are all null)");
+  return TTX_OK;
+}
+
+// k_hyp_length, then ONE launch of k_alternatives over all R*T positions.  The column order follows V alone; the 16-byte loads
+// are chosen from the base address and give the same bits as the 4-byte ones.
+static int launch_alternatives(ttx_session* s, hipStream_t st, const float* logits, const int64_t* hyp, int ld_hyp, int R, int W, int V,
+                               int pad, int eos, int k, int32_t* top_id, float* top_logp, float* chosen, int32_t* rank, float* entropy,
+                               int32_t* length) {
+  if (!length) {
+    TTX_TRY(ensure(s->am_length, (size_t)R * 4, st));
+    length = s->am_length.as<int32_t>();
+  }
+  hipLaunchKernelGGL(k_hyp_length, dim3(cdiv(R, 4)), dim3(256), 0, st, hyp, ld_hyp, R, W, pad, eos, length);
+  HIP_TRY(hipGetLastError());
+  AltArgs a{};
+  a.logits = logits; a.hyp = hyp; a.length = length; a.top_id = top_id; a.top_logp = top_logp; a.chosen_logp = chosen;
+  a.rank = rank; a.entropy = entropy; a.ld_hyp = ld_hyp; a.M = R * (W - 1); a.T = W - 1; a.V = V; a.k = k;
+  const dim3 grid(cdiv(a.M, 4)), block(256);
+  if (V % 4 != 0) hipLaunchKernelGGL((k_alternatives<false, false>), grid, block, 0, st, a);
+  else if (reinterpret_cast<uintptr_t>(logits) % 16 == 0) hipLaunchKernelGGL((k_alternatives<true, true>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((k_alternatives<true, false>), grid, block, 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+extern "C" int ttx_hypothesis_alternatives(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad,
+                                           int eos, int k, int32_t* d_top_id, float* d_top_logp, float* d_chosen_logp,
+                                           int32_t* d_rank, float* d_entropy, int32_t* d_length, void* stream) {
+  if (!s) return session_required("ttx_hypothesis_alternatives");
+  if (!d_logits || !d_hyp) return fail(TTX_ERR_INVALID, "bad argument to ttx_hypothesis_alternatives");
+  TTX_TRY(check_score_shapes(s, R, W, V, "ttx_hypothesis_alternatives"));
+  TTX_TRY(check_alt_args(V, k, d_top_id, d_top_logp, d_chosen_logp, d_rank, d_entropy, "ttx_hypothesis_alternatives"));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->m->device));
+  return launch_alternatives(s, st, d_logits, d_hyp, W, R, W, V, pad, eos, k, d_top_id, d_top_logp, d_chosen_logp, d_rank, d_entropy,
+                             d_length);
+}
+
+extern "C" int ttx_score_alternatives(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N,
+                                      int W, int eos, int k, float* d_logits, int32_t* d_top_id, float* d_top_logp,
+                                      float* d_chosen_logp, int32_t* d_rank, float* d_entropy, int32_t* d_length, void* stream) {
+  if (!s) return session_required("ttx_score_alternatives");
+  if (!d_src || !d_hyp || B <= 0 || N <= 0 || Ls <= 0) return fail(TTX_ERR_INVALID, "bad argument to ttx_score_alternatives");
+  if (ld_hyp < W) return fail(TTX_ERR_INVALID, "ttx_score_alternatives: row stride ld_hyp smaller than W");
+  const ttx_config& c = s->m->cfg;
+  TTX_TRY(check_score_shapes(s, (long long)B * N, W, c.vocab_size, "ttx_score_alternatives"));
+  TTX_TRY(check_alt_args(c.vocab_size, k, d_top_id, d_top_logp, d_chosen_logp, d_rank, d_entropy, "ttx_score_alternatives"));
+  if (Ls > c.max_positions) return fail(TTX_ERR_INVALID, "source longer than the positional table");
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->m->device));
+  const int R = B * N, T = W - 1, V = c.vocab_size;
+  if (!d_logits) {
+    TTX_TRY(ensure(s->ev_logits, (size_t)R * T * V * sizeof(float), st));
+    d_logits = s->ev_logits.as<float>();
+  }
+  TTX_TRY(score_forward(s, st, d_src, B, Ls, d_hyp, ld_hyp, N, W, d_logits));
+  return launch_alternatives(s, st, d_logits, d_hyp, ld_hyp, R, W, V, c.pad_token, eos, k, d_top_id, d_top_logp, d_chosen_logp, d_rank,
+                             d_entropy, d_length);
 }
 
 // ------------------------------------------------------------------------------------------------

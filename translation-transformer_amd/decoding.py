@@ -43,6 +43,15 @@ class _ScoresHypotheses:
             raise ValueError("the generator's pad token differs from the model's")
         return self.model.attention_maps(src, pred, eos_token_idx=eos, **kw)
 
+    def alternatives(self, src: torch.Tensor, pred: torch.Tensor, k: int = 5, **kw):
+        """What the model considered at every position of the hypotheses ``pred`` (Long[B, N, L] as ``generate(src)`` returned
+        it): an ``Alternatives`` (with ``with_scores=True`` also the ``HypothesisScores``), from the same teacher-forced pass
+        as ``score``.  Keywords go to ``NativeTransformer.alternatives``."""
+        pad, eos = self._pad_eos()
+        if pad != self.model.tgt_pad_token_i:
+            raise ValueError("the generator's pad token differs from the model's")
+        return self.model.alternatives(src, pred, k=k, eos_token_idx=eos, **kw)
+
     def _scored(self, src: torch.Tensor, pred: torch.Tensor, return_scores: bool):
         return (pred, self.score(src, pred)) if return_scores else pred
 

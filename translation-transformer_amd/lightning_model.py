@@ -205,6 +205,13 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         self.predict_with_attention = False
         self.predict_alignments: dict = {}
         self._attention_on = False
+        # predict_step also keeps what the model considered at every position of its hypotheses (NativeTransformer.alternatives)
+        # as self.predict_alternatives[batch_idx]: k > 0 switches it on and is the number of alternatives per position.  With
+        # predict_with_scores on too, both come from one decoder pass.  No init_arg either — set the attribute or
+        # TTX_PREDICT_ALTERNATIVES=k
+        self.predict_with_alternatives = 0
+        self.predict_alternatives: dict = {}
+        self._alternatives_k = 0
         self.report_prediction_time = report_prediction_time
         self.prediction_start_time = None
 
@@ -266,7 +273,9 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             pred = ahead.take(batch["src_tokens"], batch_idx)
         if pred is None:
             pred = self.generator.generate(batch["src_tokens"])
-        if self._scores_on:
+        if self._alternatives_k > 0:
+            self._alternatives_batch(batch["src_tokens"], pred, batch_idx)
+        elif self._scores_on:
             self._score_batch(batch["src_tokens"], pred, batch_idx)
         if self._attention_on:
             self._align_batch(batch["src_tokens"], pred, batch_idx)
@@ -280,10 +289,30 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         sc = self.generator.score(src, pred)
         torch.cuda.synchronize()
         self._scoring_seconds += timer() - t0
+        self._keep_scores(sc, batch_idx)
+
+    def _keep_scores(self, sc, batch_idx: int) -> None:
         self.predict_scores[batch_idx] = sc
         self._top1_sum = self._top1_sum + sc.score[:, 0].double().sum()      # kept on the device until the report
         self._top1_n += int(sc.score.shape[0])
         self._unfinished = self._unfinished + (~sc.finished).sum()
+
+    def _alternatives_batch(self, src: torch.Tensor, pred: torch.Tensor, batch_idx: int) -> None:
+        """The batch's Alternatives and, with scores on, its HypothesisScores from the same decoder pass (its time then counts
+        as scoring_seconds too); the token tensor predict_step returns stays what it was.  Timed like _score_batch."""
+        torch.cuda.synchronize()
+        t0 = timer()
+        out = self.generator.alternatives(src, pred, k=self._alternatives_k, with_scores=self._scores_on)
+        torch.cuda.synchronize()
+        dt = timer() - t0
+        self._alternatives_seconds += dt
+        if not self._scores_on:
+            self.predict_alternatives[batch_idx] = out
+            return
+        alts, sc = out
+        self._scoring_seconds += dt
+        self.predict_alternatives[batch_idx] = alts
+        self._keep_scores(type(sc)(sc.score, sc.length, sc.finished, None), batch_idx)
 
     def _align_batch(self, src: torch.Tensor, pred: torch.Tensor, batch_idx: int) -> None:
         """The batch's source alignments, whether it was decoded ahead or on the spot; the token tensor predict_step returns
@@ -319,6 +348,13 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         self.predict_scores = {}
         self._attention_on = bool(self.predict_with_attention) or os.environ.get("TTX_PREDICT_ATTENTION") == "1"
         self.predict_alignments = {}
+        try:
+            self._alternatives_k = int(self.predict_with_alternatives) or int(os.environ.get("TTX_PREDICT_ALTERNATIVES", "0"))
+        except ValueError:
+            raise ValueError("predict_with_alternatives / TTX_PREDICT_ALTERNATIVES must be an integer k (0: off), got "
+                             f"{self.predict_with_alternatives!r} / {os.environ.get('TTX_PREDICT_ALTERNATIVES')!r}") from None
+        self.predict_alternatives = {}
+        self._alternatives_seconds = 0.0
         self._attention_seconds = 0.0
         self._scoring_seconds, self._top1_n, self._top1_sum, self._unfinished = 0.0, 0, 0.0, 0
         window = int(os.environ.get("TTX_PREDICT_WINDOW", str(self.predict_window)))
@@ -357,6 +393,8 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             report["scoring_seconds"] = round(self._scoring_seconds, 6)
             report["mean_top1_logprob"] = round(float(self._top1_sum) / max(1, self._top1_n), 6)
             report["unfinished_hypotheses"] = int(self._unfinished)
+        if self._alternatives_k > 0:
+            report["alternatives_seconds"] = round(self._alternatives_seconds, 6)
         if self._attention_on:
             report["attention_seconds"] = round(self._attention_seconds, 6)
         text = json.dumps(report)

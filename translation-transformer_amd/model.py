@@ -86,6 +86,25 @@ class AttentionMaps(NamedTuple):
     length: torch.Tensor             # int32 [B, N]: as HypothesisScores.length
 
 
+class Alternatives(NamedTuple):
+    """Result of ``NativeTransformer.alternatives`` / ``hypothesis_alternatives``: device tensors, nothing copied to the host.
+    Position ``p`` of hypothesis ``h`` (the one that predicts ``h[p+1]``) is live iff ``p < length``.  Where not live:
+    ``top_id`` = -1, ``rank`` = -1, the rest exactly 0."""
+    top_id: torch.Tensor             # int32 [..., T, k]: the k most probable ids, best first, equal logits by ascending id
+    top_logp: torch.Tensor           # fp32 [..., T, k]: their log-probabilities
+    chosen_logp: torch.Tensor        # fp32 [..., T]: log-probability of the emitted token (HypothesisScores.token_logp, bit for bit)
+    rank: torch.Tensor               # int32 [..., T]: tokens the model preferred to the emitted one (0: it was the first maximum)
+    entropy: torch.Tensor            # fp32 [..., T]: entropy of the distribution, nats
+    length: torch.Tensor             # int32 [...]: as HypothesisScores.length
+
+    @property
+    def margin(self) -> torch.Tensor:
+        """fp32 [..., T]: log-probability of the best id minus that of the runner-up (needs k >= 2); exactly 0 where not live."""
+        if self.top_logp.shape[-1] < 2:
+            raise ValueError("margin needs k >= 2")
+        return self.top_logp[..., 0] - self.top_logp[..., 1]
+
+
 class NativeTransformer:
     # score_hypotheses: decoder positions (rows x columns) of one call; the widest activation buffer takes ff_dim floats per
     # position (256 MiB at ff_dim 2048), and a bench batch of 32 rows x 199 columns still fits one call
@@ -631,6 +650,92 @@ class NativeTransformer:
             if part is not None and Wt != W:
                 tok[b0:b1, :, :Wt - 1] = part
         return HypothesisScores(score, length, fin, tok)
+
+    # -- per-position alternatives of hypotheses -------------------------------------------------
+    def _alt_buffers(self, lead: tuple, T: int, k: int, fill: bool) -> Alternatives:
+        """Output tensors of the alternatives stage; ``fill``: pre-set to the not-live values (columns a trimmed pass leaves)."""
+        dev = self.device
+
+        def make(shape, dtype, value):
+            return torch.full(shape, value, dtype=dtype, device=dev) if fill else torch.empty(shape, dtype=dtype, device=dev)
+
+        return Alternatives(make(lead + (T, k), torch.int32, -1), make(lead + (T, k), torch.float32, 0.0),
+                            make(lead + (T,), torch.float32, 0.0), make(lead + (T,), torch.int32, -1),
+                            make(lead + (T,), torch.float32, 0.0), torch.empty(lead, dtype=torch.int32, device=dev))
+
+    def hypothesis_alternatives(self, logits: torch.Tensor, hyp: torch.Tensor, pad: int, eos: int, k: int = 5) -> Alternatives:
+        """The alternatives stage alone (ttx_hypothesis_alternatives): ``logits`` fp32 [..., W-1, V] as
+        ``decode_tgt(hyp[..., :-1])`` gives them, ``hyp`` Long[..., W] with the same leading shape.  A ``logits`` tensor that is
+        already a contiguous fp32 device tensor is read in place.  Nothing is synchronised."""
+        x = logits.to(self.device, torch.float32)
+        if not x.is_contiguous():
+            x = x.contiguous()
+        hyp = self._tokens(hyp)
+        lead, W = tuple(hyp.shape[:-1]), int(hyp.shape[-1])
+        if hyp.dim() < 2 or W < 2 or tuple(x.shape[:-1]) != lead + (W - 1,):
+            raise ValueError(f"hypothesis_alternatives needs hyp [..., W >= 2] for logits [..., W-1, V]; got {tuple(hyp.shape)} "
+                             f"for {tuple(x.shape)}")
+        V, k = int(x.shape[-1]), int(k)
+        if not 1 <= k <= min(32, V):
+            raise ValueError(f"k must be in [1, min(32, V)], got {k} for V = {V}")
+        self.check_tokens(hyp, V)
+        out = self._alt_buffers(lead, W - 1, k, fill=False)
+        N.check(self._lib.ttx_hypothesis_alternatives(self._scoring_session(), x.data_ptr(), hyp.data_ptr(), hyp.numel() // W, W, V,
+                                                      int(pad), int(eos), k, *(t.data_ptr() for t in out), self._stream()))
+        return out
+
+    def alternatives(self, src: torch.Tensor, hyp: torch.Tensor, k: int = 5, eos_token_idx: int = 2, max_rows: int | None = None,
+                     trim: bool = True, with_scores: bool = False):
+        """What the model considered at every position of hypothesis ``hyp[b, n]`` (Long[B, N, W]) of source ``src[b]``: the
+        ``k`` most probable tokens with their log-probabilities, the log-probability and rank of the emitted token and the
+        entropy, from the teacher-forced pass ``score_hypotheses`` runs (ttx_score_alternatives).
+
+        ``trim`` and ``max_rows`` behave as in ``score_hypotheses``: one scalar device-to-host read or none, whole sources per
+        chunk.  Results keep the full ``W-1``; columns cut by ``trim`` hold the not-live values.
+
+        ``with_scores=True`` returns ``(Alternatives, HypothesisScores)`` (the scores with ``token_logp``), both from the same
+        decoder pass: the chunk's logits stay in a device buffer and the scoring stage runs on them."""
+        src, hyp = self._tokens(src), self._tokens(hyp)
+        if src.dim() != 2 or hyp.dim() != 3 or hyp.shape[0] != src.shape[0] or hyp.shape[1] < 1 or hyp.shape[2] < 2:
+            raise ValueError(f"alternatives needs hyp [B, N >= 1, W >= 2] for src [B, Ls]; got {tuple(hyp.shape)} for "
+                             f"{tuple(src.shape)}")
+        k, V = int(k), self.tgt_vocab_size
+        if not 1 <= k <= min(32, V):
+            raise ValueError(f"k must be in [1, min(32, V)], got {k} for V = {V}")
+        self.check_tokens(src)
+        self.check_tokens(hyp, V)
+        (B, Ls), (_, K, W) = src.shape, hyp.shape
+        eos = int(eos_token_idx)
+        Wt, chunk = self._trim_and_chunk(hyp, eos, trim, max_rows)
+        T, Tt = W - 1, Wt - 1
+        out = self._alt_buffers((B, K), T, k, fill=Wt != W)
+        sc = None
+        if with_scores:
+            sc = HypothesisScores(torch.empty((B, K), dtype=torch.float32, device=self.device), out.length,
+                                  torch.empty((B, K), dtype=torch.bool, device=self.device),
+                                  (torch.empty if Wt == W else torch.zeros)((B, K, T), dtype=torch.float32, device=self.device))
+            buf = torch.empty((min(B, chunk) * K, Tt, V), dtype=torch.float32, device=self.device)   # one chunk's logits, reused
+        sess, stream = self._scoring_session(), self._stream()
+        for b0 in range(0, B, chunk):
+            b1 = min(B, b0 + chunk)
+            nb = b1 - b0
+            part = Alternatives(*(t[b0:b1] for t in out)) if Wt == W else self._alt_buffers((nb, K), Tt, k, fill=False)
+            logits = buf[:nb * K] if with_scores else None
+            N.check(self._lib.ttx_score_alternatives(sess, src[b0:b1].data_ptr(), nb, Ls, hyp[b0:b1].data_ptr(), W, K, Wt, eos, k,
+                                                     self._ptr(logits), *(t.data_ptr() for t in part[:5]),
+                                                     out.length[b0:b1].data_ptr(), stream))
+            if Wt != W:
+                for full, cut in zip(out[:5], part[:5]):
+                    full[b0:b1, :, :Tt] = cut
+            if with_scores:
+                rows = hyp[b0:b1] if Wt == W else hyp[b0:b1, :, :Wt].contiguous()
+                tok = sc.token_logp[b0:b1] if Wt == W else torch.empty((nb, K, Tt), dtype=torch.float32, device=self.device)
+                N.check(self._lib.ttx_hypothesis_logprobs(sess, logits.data_ptr(), rows.data_ptr(), nb * K, Wt, V,
+                                                          self.tgt_pad_token_i, eos, tok.data_ptr(), sc.score[b0:b1].data_ptr(),
+                                                          out.length[b0:b1].data_ptr(), sc.finished[b0:b1].data_ptr(), stream))
+                if Wt != W:
+                    sc.token_logp[b0:b1, :, :Tt] = tok
+        return (out, sc) if with_scores else out
 
     # -- cross-attention maps of hypotheses -----------------------------------------------------
     def attention_maps(self, src: torch.Tensor, hyp: torch.Tensor, eos_token_idx: int = 2, layer: int = -1, heads: str = "mean",

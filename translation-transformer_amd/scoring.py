@@ -162,6 +162,38 @@ def read_alignments(filename: str) -> list:
         return [[[int(j) for j in field.split()] for field in line.rstrip("\n").split(",")] for line in f]
 
 
+def write_alternatives(filename: str, alts, append: bool = True) -> None:
+    """The alternatives side file of the prediction CSV: one line per source, the hypotheses separated by commas in the order of
+    the CSV's ``prediction_1..N`` columns, the live positions of a hypothesis separated by ``;``, each position as
+    ``id_1:logp_1 .. id_k:logp_k|rank|entropy`` (9 significant digits: fp32 round-trips; a hypothesis of length 0 gives an empty
+    field).  ``alts``: an Alternatives (or anything with its fields).  The prediction CSV itself is left as it is."""
+    ids, lps, rk, en, ln = (t.detach().cpu().tolist() for t in (alts.top_id, alts.top_logp, alts.rank, alts.entropy, alts.length))
+    with open(filename, "a" if append else "w") as f:
+        for i_row, p_row, r_row, e_row, l_row in zip(ids, lps, rk, en, ln):
+            print(",".join(";".join(" ".join(f"{int(v)}:{lp:.9g}" for v, lp in zip(i_row[h][p], p_row[h][p]))
+                                    + f"|{int(r_row[h][p])}|{e_row[h][p]:.9g}" for p in range(int(n)))
+                           for h, n in enumerate(l_row)), file=f)
+
+
+def read_alternatives(filename: str) -> list:
+    """What ``write_alternatives`` wrote: per source a list of hypotheses, each a list of positions
+    ``([(id, logp), ...], rank, entropy)``."""
+    def position(text):
+        pairs, rank, entropy = text.split("|")
+        return [(int(i), float(lp)) for i, lp in (pair.split(":") for pair in pairs.split())], int(rank), float(entropy)
+
+    with open(filename) as f:
+        return [[[position(t) for t in field.split(";")] if field else [] for field in line.rstrip("\n").split(",")] for line in f]
+
+
+def near_ties(alts, eps: float):
+    """bool [..., T]: the live positions of every hypothesis whose top-1 / top-2 ``margin`` is below ``eps`` — where an fp32
+    near-tie decided which token ranks first.  ``alts``: an Alternatives with k >= 2."""
+    import torch
+    margin = alts.margin
+    return (torch.arange(margin.shape[-1], device=margin.device) < alts.length.unsqueeze(-1)) & (margin < eps)
+
+
 def _fmt(d: dict) -> str:
     w = max(len(k) for k in d)
     return "\n".join(f"{k.ljust(w)}    {'n/a' if v is None else round(v, 6)}" for k, v in d.items())
