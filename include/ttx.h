@@ -553,7 +553,7 @@ typedef struct ttx_debug_accept_args {
   int32_t gen_ld, traj_ld, pool_rows, row_rule, pool;
   int32_t B, N, D, Ls, max_len, pad, bos, eos;
   int32_t greedy;          /* 1: k_greedy_accept (N = 1, D = 0, no row_rule; rows [0, n_active) all at the front of row 0) */
-  int32_t threads;         /* k_accept's block size: 0 the production choice (256 for B <= 256, 1024 above), or 256 / 1024 */
+  int32_t threads;         /* k_accept's block size: 0 the production choice (256 for B <= 256; above, k_accept_slots + k_accept_finish, or 1024 under TTX_ACCEPT_SPREAD=0), or 256 / 1024 */
 } ttx_debug_accept_args;
 
 /* ttx_debug_accept: ONE launch of k_accept (greedy: k_greedy_accept).  `state` is a HOST array of 17 int64: on entry [0..7] =
@@ -566,6 +566,11 @@ typedef struct ttx_debug_accept_args {
  * runs with 256 threads.  Also refused: null required pointers, n_active outside [0, B], act_idx that are not distinct rows of
  * [0, B), a gen_ld below max_len or too small for front + D + 2 of a running row, row_of outside [0, pool_rows). */
 int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, int64_t* state, void* stream);
+
+/* ttx_debug_accept_block: the first n_words int32 words of the session's AcceptBlk (csrc/ttx_loop_kernels.hip.h: the sums that
+ * k_accept_slots hands k_accept_finish; 264 words), copied to the HOST array `words` after `stream` has drained.  Every word is 0
+ * between accept steps.  Refused before the session has run the pair once. */
+int ttx_debug_accept_block(ttx_session* s, int32_t* words, int n_words, void* stream);
 
 /* ttx_debug_kvcopy: ONE launch of k_kvcopy on a grid of (B, Ld) workgroups: for slot < n_copy with record (b, best, n_acc,
  * front_old, .) of d_rec int32 [B, 5] and j = 0 .. n_acc, the K and V thirds of step row (j == 0 ? 0 : 1 + best*D + (j-1)) of the

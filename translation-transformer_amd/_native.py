@@ -103,6 +103,7 @@ class DebugAcceptArgs(C.Structure):
                                          "pad", "bos", "eos", "greedy", "threads")]
 
 
+DEBUG_ACCEPT_BLOCK_WORDS = 264    # int32 words of the AcceptBlk between k_accept_slots and k_accept_finish (ttx_debug_accept_block)
 DEBUG_ACCEPT_STATE_WORDS = 17     # int64 words of ttx_debug_accept's host `state` array (include/ttx.h)
 
 
@@ -175,6 +176,7 @@ SYMBOLS = {
     "ttx_debug_argmax": (C.c_int, [_VP, _VP, _I, _VP, _VP, _I, _VP]),
     "ttx_debug_embed": (C.c_int, [_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _I, _I, _I, _I, _I, _VP]),
     "ttx_debug_accept": (C.c_int, [_VP, C.POINTER(DebugAcceptArgs), C.POINTER(C.c_int64), _VP]),
+    "ttx_debug_accept_block": (C.c_int, [_VP, C.POINTER(C.c_int32), _I, _VP]),
     "ttx_debug_kvcopy": (C.c_int, [_VP, _VP, _I, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int64, _I, _I, _I, _I, _I, _VP]),
     "ttx_debug_kvcopy_split": (C.c_int, [_VP, _VP, _I, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int64, _I, _I, _I, _I, _I, _VP, _VP,
                                          C.c_int64, _VP]),

@@ -329,6 +329,7 @@ extern "C" int ttx_session_create(ttx_model* m, ttx_session** out) {
   if (const char* e = getenv("TTX_QKV_SMALL_ROWS")) s->qkv_small_rows = std::max(0, atoi(e));
   // test hook: every attention launch on the streaming fallback kernel
   if (const char* e = getenv("TTX_ATTN_FALLBACK")) s->attn_fallback = atoi(e) != 0;
+  if (const char* e = getenv("TTX_ACCEPT_SPREAD")) s->accept_spread = atoi(e) != 0;
   // A/B and test switch: 0 keeps one-row step launches off k_attn1, 1 puts every eligible one on it
   if (const char* e = getenv("TTX_ATTN_ROW")) s->attn_row = atoi(e) != 0 ? 1 : 0;
   s->host_timing = getenv("TTX_HOST_TIMING") != nullptr;
@@ -1070,10 +1071,38 @@ struct GenCtx {
   KvCopyArgs kc;
 };
 
-static int launch_accept_and_commit(ttx_session* s, hipStream_t st, const GenCtx& g, bool greedy) {
-  if (greedy) hipLaunchKernelGGL(k_greedy_accept, dim3(1), dim3(256), 0, st, g.la);
-  else hipLaunchKernelGGL(k_accept, dim3(1), dim3(g.k.B > 256 ? ACCEPT_THREADS : 256), 0, st, g.la);
+// The accept step of a speculative loop over B slots: k_accept alone, or with `la.blk` set (accept_blk_for) the pair.
+static int launch_accept(hipStream_t st, const LoopArgs& la, int threads) {
+  if (la.blk) {
+    hipLaunchKernelGGL(k_accept_slots, dim3(cdiv(la.B, ACCEPT_SLOT_WAVES)), dim3(ACCEPT_SLOT_WAVES * 64), 0, st, la);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_accept_finish, dim3(1), dim3(ACCEPT_THREADS), 0, st, la);
+  } else {
+    hipLaunchKernelGGL(k_accept, dim3(1), dim3(threads ? threads : (la.B > 256 ? ACCEPT_THREADS : 256)), 0, st, la);
+  }
   HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+// The session's AcceptBlk for loops of more than 256 slots (null otherwise, and with TTX_ACCEPT_SPREAD=0): zero when fresh, and
+// left zero by every k_accept_finish.  The choice follows the capacity alone, as k_accept's block size does.
+static int accept_blk_for(ttx_session* s, hipStream_t st, int B, AcceptBlk** out) {
+  *out = nullptr;
+  if (!s->accept_spread || B <= 256) return TTX_OK;
+  const void* before = s->accept_blk.p;
+  TTX_TRY(ensure(s->accept_blk, sizeof(AcceptBlk), st));
+  if (s->accept_blk.p != before) HIP_TRY(hipMemsetAsync(s->accept_blk.p, 0, sizeof(AcceptBlk), st));
+  *out = s->accept_blk.as<AcceptBlk>();
+  return TTX_OK;
+}
+
+static int launch_accept_and_commit(ttx_session* s, hipStream_t st, const GenCtx& g, bool greedy) {
+  if (greedy) {
+    hipLaunchKernelGGL(k_greedy_accept, dim3(1), dim3(256), 0, st, g.la);
+    HIP_TRY(hipGetLastError());
+  } else {
+    TTX_TRY(launch_accept(st, g.la, 0));
+  }
   hipLaunchKernelGGL(k_kvcopy, dim3(g.k.B, s->m->cfg.num_decoder_layers), dim3(256), 0, st, g.kc);
   HIP_TRY(hipGetLastError());
   return TTX_OK;
@@ -1230,6 +1259,8 @@ static int gen_start(GenJob& j, ttx_session* s, hipStream_t st, const int64_t* d
   TTX_TRY(ensure_acts(s, st, Macts, 1));
   TTX_TRY(ensure(s->qkv, std::max((size_t)Ld * Mmax, (size_t)B * Ls) * 3 * d * 4, st));
   TTX_TRY(ensure(s->slab, sizeof(float) * 16 * Macts * d, st));   // no allocation may happen inside a graph capture
+  AcceptBlk* blk = nullptr;
+  if (!greedy) TTX_TRY(accept_blk_for(s, st, B, &blk));
   s->graphs_current();                                            // captured pointers may be stale
 
   s->ev_used = 0;
@@ -1255,6 +1286,7 @@ static int gen_start(GenJob& j, ttx_session* s, hipStream_t st, const int64_t* d
   g.la.eos = p->eos_token;
   g.la.row_rule = row_rule ? 1 : 0; g.la.traj = row_rule ? s->traj.as<short>() : nullptr; g.la.traj_ld = max_len + 1;
   g.la.fin_step = row_rule ? s->fin_step.as<int>() : nullptr;
+  g.la.blk = blk;
   g.kc.st = s->state.as<DecState>(); g.kc.rec = s->rec.as<CopyRec>(); g.kc.qkv = s->qkv.as<float>();
   g.kc.qkv_layer_stride = (long long)Mmax * 3 * d;
   g.kc.kcache = s->kcache.as<float>(); g.kc.vcache = s->vcache.as<float>();
@@ -1446,6 +1478,36 @@ extern "C" int ttx_greedy_generate(ttx_session* s, const int64_t* d_src, int B, 
   return generate_common(s, d_src, B, Ls, p, d_out, stats, stream, true);
 }
 
+// Length buckets inside an admission.  An admission is encoded at the width of its longest row, so a chunk of 1 024 length-sorted
+// rows pads its short rows to the longest one: in the encoder, in the cross K/V, and, through src_len, in every cross-attention
+// launch of the rows' slots.  Its rows are therefore admitted in consecutive sub-chunks, each at its own width (its longest row,
+// at least 2).  A sub-chunk closes once rows x width reaches `budget` padded rows: the GEMM tiles run at their large-launch rates
+// from about 16 000 rows, so a shorter launch would give back what the padding saves.  A last sub-chunk of fewer
+// than budget / 2 padded rows joins the one before it; an admission below the budget stays one chunk.  budget 0: one chunk.
+// `ends` receives the end (exclusive, relative to `len`) of every sub-chunk.
+constexpr long long ADMIT_ROWS = 16384;
+static int chunk_width(const int32_t* len, int first, int end) {
+  int w = 2;
+  for (int r = first; r < end; ++r) w = std::max(w, (int)len[r]);
+  return w;
+}
+static void admit_chunks(const int32_t* len, int n, long long budget, std::vector<int>& ends) {
+  ends.clear();
+  if (budget > 0 && (long long)n * chunk_width(len, 0, n) >= budget) {
+    int first = 0, w = 2;
+    for (int r = 0; r < n; ++r) {
+      w = std::max(w, (int)len[r]);
+      if ((long long)(r + 1 - first) * w >= budget) { ends.push_back(r + 1); first = r + 1; w = 2; }
+    }
+    if (first < n) {
+      const bool merge = !ends.empty() && (long long)(n - first) * chunk_width(len, first, n) * 2 < budget;
+      if (merge) ends.back() = n; else ends.push_back(n);
+    }
+  } else {
+    ends.push_back(n);
+  }
+}
+
 // Several batches in flight on one GPU: batch i is decoded on session i % n_sessions, each
 // session on its own stream; one host thread round-robins over the sessions, enqueueing the next verify step of
 // whichever session has published its previous one.  Outputs per batch are identical to the one-at-a-time call.
@@ -1466,6 +1528,7 @@ struct PoolJob {
   PoolIo io{};
   Progress progress;
   long long admitted_rows = 0, src_tokens_padded = 0;
+  long long admit_rows = 0; // TTX_ADMIT_ROWS: padded encoder rows at which a sub-chunk of an admission closes; 0: one chunk per admission
   // two-phase verify step (DESIGN.md "Two-phase verify step"): a free choice per step, both forms give the same bits
   bool two_phase = true;    // TTX_TWO_PHASE=0: every step in one pass
   long long min_rows = 800; // TTX_TWO_PHASE_MIN_ROWS: steps with fewer live rows (slots * RPS) run in one pass; 0: always split
@@ -1521,6 +1584,8 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
   j.two_phase = true; j.min_rows = 800; j.probes = 0; j.probe_pending = false;
   j.slot_steps = j.matched_slot_steps = j.split_steps = j.skipped_draft_passes = 0;
   j.drafts_matched = j.rows_executed = j.unsplit_rows = 0;
+  j.admit_rows = ADMIT_ROWS;
+  if (const char* e = getenv("TTX_ADMIT_ROWS")) j.admit_rows = std::max(0, atoi(e));
   if (const char* e = getenv("TTX_TWO_PHASE")) j.two_phase = atoi(e) != 0;
   if (const char* e = getenv("TTX_TWO_PHASE_MIN_ROWS")) j.min_rows = std::max(0, atoi(e));
   // draft select needs the compacted-row mapping, which k_attn3 / k_attn3s have: head dimension 32, H % 4 == 0.  Models whose step
@@ -1537,6 +1602,8 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
     TTX_TRY(ensure(s->pred_draft, Mmax * 4, st));
     TTX_TRY(ensure(s->state2, 3 * sizeof(DecState), st));
   }
+  AcceptBlk* blk = nullptr;
+  TTX_TRY(accept_blk_for(s, st, C, &blk));
   s->graphs_current();
 
   s->ev_used = 0;
@@ -1558,6 +1625,7 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
   g.la.eos = p->eos_token;
   g.la.row_rule = 1; g.la.traj = nullptr; g.la.traj_ld = max_len + 1; g.la.fin_step = nullptr;
   g.la.pool = 1; g.la.rstep = s->rstep.as<int>(); g.la.row_of = s->row_of.as<int>(); g.la.io = s->pool_io.as<PoolIo>();
+  g.la.blk = blk;
   g.k.src_len = s->src_len.as<int>();
   g.kc.st = s->state.as<DecState>(); g.kc.rec = s->rec.as<CopyRec>(); g.kc.qkv = s->qkv.as<float>();
   g.kc.qkv_layer_stride = (long long)Mmax * 3 * d;
@@ -1730,6 +1798,7 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
   const int n_jobs = std::min(n_sessions, cdiv(R_total, std::max(1, std::min(capacity / 2, 32))));   // short lists: several small pools
   const int C = std::min(capacity, std::max(1, cdiv(R_total, n_jobs)));      // never more slots than a fair share of the rows
   std::vector<PoolJob> jobs(n_jobs);
+  std::vector<int> chunk_ends;
   int rc_final = TTX_OK;
   std::fill(std::begin(sessions[0]->pool_counters), std::end(sessions[0]->pool_counters), 0LL);
   for (int i = 0; i < n_jobs && rc_final == TTX_OK; ++i) {
@@ -1797,9 +1866,15 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
           // before this one have taken theirs), so that nothing is left waiting for a later admission
           if (!serial && j.launched == 0 && (long long)n_jobs * C >= R_total) share = std::max(1, cdiv(remaining, n_jobs - i));
           const int take = std::min({free_slots, remaining, share});
-          int Ls_new = 2;                                                      // longest row of the chunk
-          for (int r = cursor; r < cursor + take; ++r) Ls_new = std::max(Ls_new, (int)h_len[r]);
-          rc_final = pool_admit(j, d_src + (size_t)cursor * Ls_all, Ls_all, take, Ls_new, cursor, d_out, d_traj, d_fin_step);
+          // every sub-chunk at the width of its own longest row; the staging buffers are the stream's, one sub-chunk after another
+          admit_chunks(h_len + cursor, take, j.admit_rows, chunk_ends);
+          int r0 = cursor;
+          for (const int end : chunk_ends) {
+            const int r1 = cursor + end;
+            rc_final = pool_admit(j, d_src + (size_t)r0 * Ls_all, Ls_all, r1 - r0, chunk_width(h_len, r0, r1), r0, d_out, d_traj, d_fin_step);
+            if (rc_final != TTX_OK) break;
+            r0 = r1;
+          }
           if (rc_final != TTX_OK) break;
           cursor += take;
           n_act += take;
@@ -3314,9 +3389,12 @@ extern "C" int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, 
     la.row_rule = a->row_rule ? 1 : 0; la.traj = a->d_traj; la.traj_ld = a->traj_ld; la.fin_step = a->d_fin_step;
     la.pool = a->pool ? 1 : 0; la.rstep = a->d_rstep; la.row_of = a->d_row_of; la.io = dio;
     la.B = a->B; la.N = a->N; la.D = a->D; la.Ls = a->Ls; la.max_len = a->max_len; la.pad = a->pad; la.bos = a->bos; la.eos = a->eos;
-    if (greedy) hipLaunchKernelGGL(k_greedy_accept, dim3(1), dim3(256), 0, st, la);
-    else hipLaunchKernelGGL(k_accept, dim3(1), dim3(a->threads ? a->threads : (a->B > 256 ? ACCEPT_THREADS : 256)), 0, st, la);
-    err = hipGetLastError();
+    // threads = 0 is the production route: above 256 slots the pair, unless TTX_ACCEPT_SPREAD=0
+    int rc_blk = TTX_OK;
+    if (!greedy && a->threads == 0) rc_blk = accept_blk_for(s, st, a->B, &la.blk);
+    if (rc_blk != TTX_OK) err = hipErrorOutOfMemory;
+    else if (greedy) { hipLaunchKernelGGL(k_greedy_accept, dim3(1), dim3(256), 0, st, la); err = hipGetLastError(); }
+    else if (launch_accept(st, la, a->threads) != TTX_OK) err = hipErrorLaunchFailure;
   }
   if (err == hipSuccess) err = hipMemcpyAsync(hs, dst, sizeof(DecState), hipMemcpyDeviceToHost, st);
   const hipError_t esync = hipStreamSynchronize(st);
@@ -3332,6 +3410,17 @@ extern "C" int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, 
   if (hinfo) (void)hipHostFree(hinfo);
   HIP_TRY(err);
   HIP_TRY(esync);
+  return TTX_OK;
+}
+
+extern "C" int ttx_debug_accept_block(ttx_session* s, int32_t* words, int n_words, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !words || n_words < 0 || (size_t)n_words * 4 > sizeof(AcceptBlk))
+    return fail(TTX_ERR_INVALID, "ttx_debug_accept_block: words must hold at most the block's int32 words");
+  if (!s->accept_blk.p) return fail(TTX_ERR_INVALID, "ttx_debug_accept_block: this session has not run the accept pair yet");
+  HIP_TRY(hipSetDevice(s->m->device));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpy(words, s->accept_blk.p, (size_t)n_words * 4, hipMemcpyDeviceToHost));
   return TTX_OK;
 }
 

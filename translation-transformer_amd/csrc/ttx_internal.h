@@ -116,6 +116,8 @@ struct GraphCache {
   X(qkv_probe) X(pred_probe) X(pred_draft) X(act2) X(pos2) X(state2)                                                             \
   /* draft select: per matching slot its present drafts and the first of its compacted rows; compacted row -> layout row */       \
   X(draft_mask) X(row_base) X(row_map)                                                                                           \
+  /* accept in two launches: the block-wide sums between k_accept_slots and k_accept_finish (AcceptBlk) */                         \
+  X(accept_blk)                                                                                                                  \
   /* snapshot of one verify step for the logits parity test (ttx_gen_params.want_logits) */                                      \
   X(snap_logits) X(snap_act) X(snap_front) X(snap_gen) X(snap_state)                                                             \
   X(leaf_score) X(leaf_tok) X(leaf_cnt) X(beam_summary)                                                                          \
@@ -174,6 +176,7 @@ struct ttx_session {
   int last_gemm_kernel = 0, last_gemm_big_min_tiles = 0;
   int attn_split = -1;             // -1 by launch size, 0 never, 1 always (key tiles of a head over 4 waves)
   int attn_row = -1;               // TTX_ATTN_ROW: one-row step launches on k_attn1: -1 those k_attn3s would get, 0 never, 1 every eligible one
+  bool accept_spread = true;       // TTX_ACCEPT_SPREAD=0: k_accept alone at every capacity (above 256 slots: k_accept_slots + k_accept_finish)
   bool attn_fallback = false;      // TTX_ATTN_FALLBACK=1 (test hook): every attention launch on the streaming kernel k_attn
   int attn_force = 0;              // ttx_debug_attn (test hook): an AttnKernelId that replaces launch_attn's choice; 0 (always, outside that call): unset
   int attn_sel_N = 0, attn_sel_D = 0;   // > 0 around the launches of a probe (run_step, ttx_debug_attn_as): choose between k_attn2 and k_attn as a step launch in the layout (N, D) does

@@ -147,8 +147,20 @@ struct LoopArgs {
   int B, N, D, Ls, max_len, pad, bos, eos;
   // two-phase verify step: rows the step really sent through the decoder (live slots + matching slots * RPS); null: Bc * RPS
   const int* exec_rows;
+  // accept in two launches (k_accept_slots, k_accept_finish): the block-wide sums between them; null: k_accept alone
+  struct AcceptBlk* blk;
 };
 struct PoolIo { int64_t* out; short* traj; int* fin_step; int traj_ld; int pad_; };
+
+// Block-wide quantities of one accept step when its per-slot part runs on many workgroups (k_accept_slots): integer atomics, so
+// the sums do not depend on the order of the slots.  Zero between steps: k_accept_finish clears what it has read, the init
+// kernels clear it before a loop's first step.
+struct AcceptBlk { int maxfront, nfin, pad_[2]; unsigned long long acc, prefix; int finlist[256]; };
+
+__device__ __forceinline__ void accept_blk_clear(AcceptBlk* k, int t) {          // by the first 256 threads of one workgroup
+  if (t < 256) k->finlist[t] = 0;
+  if (t == 0) { k->maxfront = 0; k->nfin = 0; k->pad_[0] = k->pad_[1] = 0; k->acc = 0; k->prefix = 0; }
+}
 
 __global__ void k_loop_init(LoopArgs a) {
   const int tid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -161,6 +173,7 @@ __global__ void k_loop_init(LoopArgs a) {
   }
   if (a.row_rule)
     for (int i = tid; i < a.B * a.traj_ld; i += gridDim.x * blockDim.x) a.traj[i] = (i % a.traj_ld == 0) ? 0 : -1;
+  if (a.blk && blockIdx.x == 0) accept_blk_clear(a.blk, threadIdx.x);
   if (tid == 0) {
     DecState s;
     s.n_active = a.B; s.r_rows = a.B * a.N; s.m_rows = a.B * step_rps(a.N, a.D);
@@ -176,75 +189,75 @@ __global__ void k_loop_init(LoopArgs a) {
   }
 }
 
-// One block.  Verify each draft against the argmax tokens, keep the longest accepted prefix plus one
-// bonus token, retire rows that produced EOS, compact the active list, decide whether the loop goes on.
-constexpr int ACCEPT_THREADS = 1024;                // one slot per thread up to 1 024 slots per round; 16 waves copy finished rows
-__global__ __launch_bounds__(ACCEPT_THREADS) void k_accept(LoopArgs a) {
-  __shared__ int s_maxfront, s_anyfin, s_suspect, s_nn, s_maxf_new, s_nfin;
-  __shared__ int s_finlist[256];                    // finished rows of this step (their output copy is shared out below)
-  __shared__ long long s_acc, s_prefix;
-  __shared__ int s_scan[ACCEPT_THREADS];
-  DecState* st = a.st;
-  const int Bc = st->n_active;
-  if (Bc == 0) return;
-  const int D1 = a.D + 1, RPS = step_rps(a.N, a.D);
-  if (threadIdx.x == 0) { s_maxfront = 0; s_anyfin = 0; s_acc = 0; s_prefix = 0; s_suspect = 0; s_nn = 0; s_maxf_new = 0; s_nfin = 0; }
-  __syncthreads();
-  for (int slot = threadIdx.x; slot < Bc; slot += blockDim.x) {
-    const int b = a.act_idx[slot];
-    const int f = a.front[b];
-    const int* ps = a.pred + (size_t)slot * RPS;       // predictions of the slot's step rows
-    // prediction made at position f + j on draft n: row 0 for j = 0, else row 1 + n*D + (j-1)
-    int best = 0, bacc = -1;
-    for (int n = 0; n < a.N; ++n) {
-      const int* dr = a.drafts + ((size_t)b * a.N + n) * a.D;
-      const int* pr = ps + 1 + n * a.D - 1;            // pr[j] = prediction at position f + j for j >= 1
-      // first mismatch without an early exit: the D + D loads are independent and go out back to back (the
-      // early-exit loop was a chain of dependent global loads, ~30 round trips per row)
-      int acc = a.D;
-      for (int j = a.D - 1; j >= 0; --j)
-        if (dr[j] != (j == 0 ? ps[0] : pr[j])) acc = j;
-      if (acc > bacc) { bacc = acc; best = n; }
+struct SlotStep { int b, f, bacc; bool fin; };
+// Bookkeeping of a slot whose tokens are written: front, haspad, the trajectory under the row rule, the copy record.
+__device__ __forceinline__ void accept_slot_commit(const LoopArgs& a, const DecState* st, int slot, int b, int f, int best, int bacc,
+                                                   bool fin, bool sawpad) {
+  const int D1 = a.D + 1;
+  if (sawpad) a.haspad[b] = 1;
+  a.front[b] = f + bacc + 1;
+  int flags = fin ? 1 : 0;
+  if (a.row_rule) {
+    int it = st->steps + 1;                          // all rows of a device batch start together ...
+    short* trow = a.traj + (size_t)b * a.traj_ld;
+    int* finp = a.fin_step + b;
+    if (a.pool) {                                    // ... rows of a slot pool do not
+      it = a.rstep[b] + 1;
+      a.rstep[b] = it;
+      trow = a.io->traj + (size_t)a.row_of[b] * a.traj_ld;
+      finp = a.io->fin_step + a.row_of[b];
     }
-    const int* pr = ps + 1 + best * a.D - 1;
-    int* g = a.gen + (size_t)b * a.gen_ld;
-    bool fin = false, sawpad = false;
-    for (int j = 0; j <= bacc; ++j) {
-      const int t = (j == 0) ? ps[0] : pr[j];
-      g[f + 1 + j] = t;
-      fin |= (t == a.eos);
-      sawpad |= (t == a.pad);                          // a PAD inside the generated part (reference quirk 2)
-    }
-    if (sawpad) a.haspad[b] = 1;
-    a.front[b] = f + bacc + 1;
-    int flags = fin ? 1 : 0;
-    if (a.row_rule) {
-      int it = st->steps + 1;                          // all rows of a device batch start together ...
-      short* trow = a.traj + (size_t)b * a.traj_ld;
-      int* finp = a.fin_step + b;
-      if (a.pool) {                                    // ... rows of a slot pool do not
-        it = a.rstep[b] + 1;
-        a.rstep[b] = it;
-        trow = a.io->traj + (size_t)a.row_of[b] * a.traj_ld;
-        finp = a.io->fin_step + a.row_of[b];
-      }
-      if (it < a.traj_ld) trow[it] = (short)(f + bacc + 1);
-      if (fin) *finp = it;
-      // alone in a batch this row would see width f + D + 2 after this step and stop once that reaches max_len (:93)
-      else if (f + D1 + 1 >= a.max_len) flags = 2;
-    }
-    a.rec[slot] = CopyRec{b, best, bacc, f, flags};
-    atomicMax(&s_maxfront, f);
-    atomicAdd((unsigned long long*)&s_acc, (unsigned long long)bacc);
-    atomicAdd((unsigned long long*)&s_prefix, (unsigned long long)f);
-    if (fin) {
-      s_anyfin = 1;
-      const int k = atomicAdd(&s_nfin, 1);
-      if (k < 256) s_finlist[k] = b;
-    }
+    if (it < a.traj_ld) trow[it] = (short)(f + bacc + 1);
+    if (fin) *finp = it;
+    // alone in a batch this row would see width f + D + 2 after this step and stop once that reaches max_len (:93)
+    else if (f + D1 + 1 >= a.max_len) flags = 2;
   }
+  a.rec[slot] = CopyRec{b, best, bacc, f, flags};
+}
+
+// The per-slot part of an accept step: verify the slot's drafts against the argmax tokens, write the longest accepted prefix
+// plus one bonus token, advance the front, record the trajectory and the copy record.  Needs nothing of the other slots.
+__device__ __forceinline__ SlotStep accept_slot(const LoopArgs& a, const DecState* st, int slot) {
+  const int RPS = step_rps(a.N, a.D);
+  const int b = a.act_idx[slot];
+  const int f = a.front[b];
+  const int* ps = a.pred + (size_t)slot * RPS;       // predictions of the slot's step rows
+  // prediction made at position f + j on draft n: row 0 for j = 0, else row 1 + n*D + (j-1)
+  int best = 0, bacc = -1;
+  for (int n = 0; n < a.N; ++n) {
+    const int* dr = a.drafts + ((size_t)b * a.N + n) * a.D;
+    const int* pr = ps + 1 + n * a.D - 1;            // pr[j] = prediction at position f + j for j >= 1
+    // first mismatch without an early exit: the D + D loads are independent and go out back to back (the
+    // early-exit loop was a chain of dependent global loads, ~30 round trips per row)
+    int acc = a.D;
+    for (int j = a.D - 1; j >= 0; --j)
+      if (dr[j] != (j == 0 ? ps[0] : pr[j])) acc = j;
+    if (acc > bacc) { bacc = acc; best = n; }
+  }
+  const int* pr = ps + 1 + best * a.D - 1;
+  int* g = a.gen + (size_t)b * a.gen_ld;
+  bool fin = false, sawpad = false;
+  for (int j = 0; j <= bacc; ++j) {
+    const int t = (j == 0) ? ps[0] : pr[j];
+    g[f + 1 + j] = t;
+    fin |= (t == a.eos);
+    sawpad |= (t == a.pad);                          // a PAD inside the generated part (reference quirk 2)
+  }
+  accept_slot_commit(a, st, slot, b, f, best, bacc, fin, sawpad);
+  return SlotStep{b, f, bacc, fin};
+}
+
+// The part of an accept step that needs one workgroup: retire rows that produced EOS, compact the active list in order, copy the
+// finished rows out, decide whether the loop goes on and publish.  `finlist` holds the first 256 of the `nfin` finished rows.
+constexpr int ACCEPT_THREADS = 1024;                // one slot per thread up to 1 024 slots per round; 16 waves copy finished rows
+__device__ __forceinline__ void accept_finish(const LoopArgs& a, DecState* st, int Bc, int maxfront, int nfin, const int* finlist,
+                                              long long acc, long long prefix) {
+  __shared__ int s_suspect, s_maxf_new;
+  __shared__ int s_scan[ACCEPT_THREADS / 64];
+  const int D1 = a.D + 1, RPS = step_rps(a.N, a.D);
+  if (threadIdx.x == 0) { s_suspect = 0; s_maxf_new = 0; }
   __syncthreads();
-  const int width = s_maxfront + 1 + D1;          // columns of generated_tokens after this step (:97-102,:145)
+  const int width = maxfront + 1 + D1;            // columns of generated_tokens after this step (:97-102,:145)
   const int wcopy = width < a.max_len ? width : a.max_len;
   // finished rows -> output (:158); compaction of the running list by a block-wide ordered scan
   int nn_before = 0;
@@ -277,8 +290,8 @@ __global__ __launch_bounds__(ACCEPT_THREADS) void k_accept(LoopArgs a) {
     int64_t* orow = a.pool ? a.io->out + (size_t)a.row_of[b] * a.max_len : a.out + (size_t)b * a.max_len;
     for (int c = first; c < wout; c += stride) orow[c] = g[c];
   };
-  if (s_nfin <= 256) {                               // one wave per finished row
-    for (int k = threadIdx.x >> 6; k < s_nfin; k += (int)(blockDim.x >> 6)) copy_row(s_finlist[k], threadIdx.x & 63, 64);
+  if (nfin <= 256) {                                 // one wave per finished row
+    for (int k = threadIdx.x >> 6; k < nfin; k += (int)(blockDim.x >> 6)) copy_row(finlist[k], threadIdx.x & 63, 64);
   } else {                                           // more rows finished at once than the list holds: scan all slots
     for (int slot = 0; slot < Bc; ++slot)
       if (a.rec[slot].flags == 1) copy_row(a.rec[slot].b, threadIdx.x, blockDim.x);
@@ -288,13 +301,13 @@ __global__ __launch_bounds__(ACCEPT_THREADS) void k_accept(LoopArgs a) {
     const int nn = nn_before;
     st->n_copy = Bc;
     st->steps += 1;
-    st->accepted += s_acc;
-    st->produced += s_acc + Bc;
+    st->accepted += acc;
+    st->produced += acc + Bc;
     st->verified_positions += a.exec_rows ? (long long)*a.exec_rows : (long long)Bc * RPS;
-    st->kv_prefix_positions += s_prefix;
+    st->kv_prefix_positions += prefix;
     st->src_positions += (long long)Bc * a.Ls;
     st->width = width;
-    if (s_anyfin && width > a.max_len && !a.row_rule) st->error = 1;
+    if (nfin > 0 && width > a.max_len && !a.row_rule) st->error = 1;
     int stop = (nn == 0 || (!a.row_rule && width >= a.max_len)) ? 1 : 0;
     if (a.row_rule && s_suspect) st->error = 3;     // a PAD inside a sequence: per-batch quirks cannot be replayed from rows
     if (!stop && s_suspect && !a.row_rule) {
@@ -323,6 +336,111 @@ __global__ __launch_bounds__(ACCEPT_THREADS) void k_accept(LoopArgs a) {
   }                                                  // (the kernel's end releases it; the graph's next node is far away)
 }
 
+// One block.  Verify each draft against the argmax tokens, keep the longest accepted prefix plus one
+// bonus token, retire rows that produced EOS, compact the active list, decide whether the loop goes on.
+__global__ __launch_bounds__(ACCEPT_THREADS) void k_accept(LoopArgs a) {
+  __shared__ int s_maxfront, s_nfin;
+  __shared__ int s_finlist[256];                    // finished rows of this step (their output copy is shared out below)
+  __shared__ long long s_acc, s_prefix;
+  DecState* st = a.st;
+  const int Bc = st->n_active;
+  if (Bc == 0) return;
+  if (threadIdx.x == 0) { s_maxfront = 0; s_acc = 0; s_prefix = 0; s_nfin = 0; }
+  __syncthreads();
+  for (int slot = threadIdx.x; slot < Bc; slot += blockDim.x) {
+    const SlotStep r = accept_slot(a, st, slot);
+    atomicMax(&s_maxfront, r.f);
+    atomicAdd((unsigned long long*)&s_acc, (unsigned long long)r.bacc);
+    atomicAdd((unsigned long long*)&s_prefix, (unsigned long long)r.f);
+    if (r.fin) {
+      const int k = atomicAdd(&s_nfin, 1);
+      if (k < 256) s_finlist[k] = r.b;
+    }
+  }
+  __syncthreads();
+  accept_finish(a, st, Bc, s_maxfront, s_nfin, s_finlist, s_acc, s_prefix);
+}
+
+// accept_slot by one wave: lane e compares element e of the slot's N x D draft tokens with its prediction, so the reads of a slot
+// are one or two coalesced round trips instead of a chain of D dependent ones; the first mismatch of every draft comes out of the
+// wave's ballot, draft after draft in order (a draft may straddle two passes of 64 elements).  Every value below is wave-uniform.
+__device__ __forceinline__ SlotStep accept_slot_wave(const LoopArgs& a, const DecState* st, int slot, int lane) {
+  const int RPS = step_rps(a.N, a.D), ND = a.N * a.D;
+  const int b = a.act_idx[slot];
+  const int f = a.front[b];
+  const int* ps = a.pred + (size_t)slot * RPS;
+  const int* dr = a.drafts + (size_t)b * ND;
+  int best = 0, bacc = -1, open_acc = a.D;
+  for (int base = 0; base < ND; base += 64) {
+    const int e = base + lane;
+    bool miss = false;
+    if (e < ND) miss = dr[e] != ps[(e % a.D == 0) ? 0 : e];           // element (n, j): row 0 for j = 0, else row n*D + j = e
+    const unsigned long long m = __ballot(miss);
+    for (int n = base / a.D; n < a.N && n * a.D < base + 64; ++n) {
+      const int start = n * a.D, end = start + a.D;
+      const int lo = max(start, base) - base, hi = min(end, base + 64) - base;
+      const unsigned long long bits = (m >> lo) & (hi - lo == 64 ? ~0ull : (1ull << (hi - lo)) - 1ull);
+      if (start >= base) open_acc = a.D;                              // the draft begins in this pass
+      if (bits && open_acc == a.D) open_acc = base + lo - start + (int)__ffsll((long long)bits) - 1;
+      if (end <= base + 64 && open_acc > bacc) { bacc = open_acc; best = n; }     // complete: the first maximum wins
+    }
+  }
+  int* g = a.gen + (size_t)b * a.gen_ld;
+  bool fin = false, sawpad = false;
+  for (int j0 = 0; j0 <= bacc; j0 += 64) {
+    const int j = j0 + lane;
+    int t = -1;
+    if (j <= bacc) { t = ps[j == 0 ? 0 : best * a.D + j]; g[f + 1 + j] = t; }
+    fin |= __ballot(j <= bacc && t == a.eos) != 0;
+    sawpad |= __ballot(j <= bacc && t == a.pad) != 0;                  // a PAD inside the generated part (reference quirk 2)
+  }
+  if (lane == 0) accept_slot_commit(a, st, slot, b, f, best, bacc, fin, sawpad);
+  return SlotStep{b, f, bacc, fin};
+}
+
+// k_accept in two launches, for pools of more than 256 slots: one CU's vector L1 takes tens of microseconds for the strided reads
+// of 1 024 slots' drafts and predictions.  k_accept_slots runs the per-slot part, one wave per slot on a grid sized for the
+// capacity, and sums into `blk`; k_accept_finish (one workgroup of ACCEPT_THREADS) does the rest from `blk`.  Same state as
+// k_accept from the same operands.
+constexpr int ACCEPT_SLOT_WAVES = 4;
+__global__ __launch_bounds__(ACCEPT_SLOT_WAVES * 64) void k_accept_slots(LoopArgs a) {
+  __shared__ int s_maxfront;
+  __shared__ unsigned long long s_acc, s_prefix;
+  const DecState* st = a.st;
+  const int Bc = st->n_active;
+  if ((int)blockIdx.x * ACCEPT_SLOT_WAVES >= Bc) return;
+  if (threadIdx.x == 0) { s_maxfront = 0; s_acc = 0; s_prefix = 0; }
+  __syncthreads();
+  const int slot = blockIdx.x * ACCEPT_SLOT_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (slot < Bc) {
+    const SlotStep r = accept_slot_wave(a, st, slot, lane);
+    if (lane == 0) {
+      atomicMax(&s_maxfront, r.f);
+      atomicAdd(&s_acc, (unsigned long long)r.bacc);
+      atomicAdd(&s_prefix, (unsigned long long)r.f);
+      if (r.fin) {
+        const int k = atomicAdd(&a.blk->nfin, 1);
+        if (k < 256) a.blk->finlist[k] = r.b;
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {                            // three atomics per workgroup
+    atomicMax(&a.blk->maxfront, s_maxfront);
+    atomicAdd(&a.blk->acc, s_acc);
+    atomicAdd(&a.blk->prefix, s_prefix);
+  }
+}
+
+__global__ __launch_bounds__(ACCEPT_THREADS) void k_accept_finish(LoopArgs a) {
+  DecState* st = a.st;
+  const int Bc = st->n_active;
+  if (Bc == 0) return;                               // k_accept_slots did nothing: the block is still zero
+  AcceptBlk* k = a.blk;
+  accept_finish(a, st, Bc, k->maxfront, k->nfin, k->finlist, (long long)k->acc, (long long)k->prefix);
+  accept_blk_clear(k, threadIdx.x);                  // every read of the block lies before accept_finish's last barrier
+}
+
 // ------------------------------------------------------------------------------------------------
 // Slot pool (continuous batching under the per-row rule).  The pool has B slots; k_pool_init empties it, k_pool_admit
 // hands free slots to R new rows (encoder output, cross K/V and drafts of those rows were just computed into
@@ -331,6 +449,7 @@ __global__ __launch_bounds__(ACCEPT_THREADS) void k_accept(LoopArgs a) {
 __global__ void k_pool_init(LoopArgs a) {
   const int tid = blockIdx.x * blockDim.x + threadIdx.x;
   for (int i = tid; i < a.B; i += gridDim.x * blockDim.x) { a.act_idx[i] = 0; a.front[i] = 0; a.haspad[i] = 0; a.rstep[i] = 0; a.row_of[i] = 0; }
+  if (a.blk && blockIdx.x == 0) accept_blk_clear(a.blk, threadIdx.x);
   if (tid == 0) {
     DecState s;
     s.n_active = 0; s.r_rows = 0; s.m_rows = 0; s.width = 1; s.steps = 0; s.error = 0; s.n_copy = 0; s.stop = 0;

@@ -331,6 +331,12 @@ class NativeTransformer:
         N.check(self._lib.ttx_debug_accept(self._session, C.byref(a), words, self._stream()))
         return [int(v) for v in words]
 
+    def debug_accept_block(self) -> list:
+        """The int32 words of the session's AcceptBlk (ttx_debug_accept_block): all zero between accept steps."""
+        words = (C.c_int32 * N.DEBUG_ACCEPT_BLOCK_WORDS)()
+        N.check(self._lib.ttx_debug_accept_block(self._session, words, N.DEBUG_ACCEPT_BLOCK_WORDS, self._stream()))
+        return [int(v) for v in words]
+
     def debug_kvcopy(self, rec: torch.Tensor, n_copy: int, qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
                      n: int, d: int, width: int, B: int) -> None:
         """One k_kvcopy launch (ttx_debug_kvcopy): ``rec`` int32 [B, 5], ``qkv`` fp32 [Ld, B * (1 + n*d), 3 * width], the caches
