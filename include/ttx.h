@@ -255,6 +255,44 @@ int ttx_greedy_speculative_generate(ttx_session* s, const int64_t* d_src, int B,
 int ttx_greedy_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_gen_params* p,
                         int64_t* d_out, ttx_gen_stats* stats, void* stream);
 
+/* Seeded ancestral sampling: temperature, top-k and top-p (nucleus) on the device. */
+typedef struct ttx_sample_params {
+  int32_t max_len, num_samples;          /* n >= 1 samples per source */
+  float   temperature;                   /* >= 0; 0 = greedy */
+  int32_t top_k;                         /* 0 = off, else 1..32 */
+  float   top_p;                         /* (0, 1]; 1 = off.  top_p < 1 with top_k = 0 runs with top_k = 32 */
+  int32_t pad_token, bos_token, eos_token;
+  uint64_t seed;
+} ttx_sample_params;
+
+/* The plain greedy loop of ttx_greedy_generate (KV cache, one captured graph per step shape) over R = B * n decoder rows, with
+ * k_sample choosing each row's token where k_argmax would.  The encoder and the cross K/V projection run once per source; row
+ * r = b * n + j attends source b and is keyed (d_row_keys[b], j); d_row_keys NULL: keys 0..B-1.  d_out int64 [B, n, max_len]: BOS,
+ * the sampled tokens up to and including the row's first EOS or PAD, PAD after it.  The loop ends when every row has ended or the
+ * width is exhausted; stats->model_calls counts the steps.
+ *
+ * The rule, for a live row with logits x[0..V-1], at position pos (1 for the first token after BOS):
+ *   1  A row that has ended emits PAD; its logits are not read.
+ *   2  temperature == 0: the token is k_argmax's (first maximum, see ttx_debug_argmax), bit for bit.  Otherwise y_v = x_v * inv_T
+ *      with inv_T = 1.0f / temperature formed on the host, one rounded fp32 product per logit.  A -inf logit is never emitted.
+ *   3  Kept set.  top_k == 0 and top_p == 1: all V tokens, in ascending id.  Otherwise mask_with_num_logits_according_nucleus
+ *      (see ttx_nucleus_mask) on y with nucleus = top_p and max_num_of_unmasked_positions = top_k: tokens in rank order, best first,
+ *      equal values the lower id first; rank i is kept while i < top_k and the softmax mass ranked above it is < top_p; rank 0 always.
+ *   4  u = (x0 >> 8) * 2^-24, an fp32 in [0, 1), x0 = word 0 of Philox4x32-10 with key (seed_lo, seed_hi) and counter
+ *      (key_lo, key_hi, sample, pos); multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, round
+ *      c' = (hi(M1*c2) ^ c1 ^ k0, lo(M1*c2), hi(M0*c0) ^ c3 ^ k1, lo(M0*c0)).
+ *   5  e_v = expf(y_v - max y), S their sum over the kept set: the first kept token (ascending id without a filter, rank order with
+ *      one) whose inclusive prefix sum exceeds u * S; the last kept token with e_v > 0 if rounding leaves none.  The order of the
+ *      fp32 sums is fixed by V and the filter alone (csrc/ttx_sample.hip.h), so a row's token depends on its own logits, key,
+ *      sample id and position only: not on B, n, the row's place in the launch, or what shares its batch.
+ *   6  EOS and PAD both end a row.
+ * Limits: vocab_size <= 1024; at most 32 kept tokens when a filter is on.  TTX_ERR_INVALID with nothing launched: vocab_size >
+ * 1024, num_samples < 1, temperature < 0 or not finite, top_k outside {0, 1..32}, top_p outside (0, 1] or not finite, and
+ * everything ttx_greedy_generate refuses.  Per-token log-probabilities are not produced: ttx_score_hypotheses on the samples gives
+ * them on the scale of every other generator. */
+int ttx_sample_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sample_params* p,
+                        int64_t* d_out, ttx_gen_stats* stats, void* stream);
+
 /* Beam-speculative bookkeeping kernels.
  * ttx_nucleus_mask: mask_with_num_logits_according_nucleus (src/decoding/speculative_decoding.py:871-904): per row of
  *   d_logits [rows,V] keep the best logit and further ones, best first, while the softmax mass ranked above is
@@ -526,6 +564,15 @@ int ttx_debug_attn_as(ttx_session* s, const float* d_q, int ldq, const float* d_
  * contract and only give some id in [0, V).  d_m: live row count on the device
  * or NULL (all m_max rows); rows >= *d_m are not written.  Refused: null pointers, V < 1, m_max < 1, *d_m outside [0, m_max]. */
 int ttx_debug_argmax(ttx_session* s, const float* d_logits, int V, int32_t* d_pred, const int32_t* d_m, int m_max, void* stream);
+
+/* ttx_debug_sample (tests/test_gpu_sample_kernel.py): ONE launch of k_sample with production's grid on the caller's device operands,
+ * the rule of ttx_sample_generate.  d_logits fp32 [m_max, V], d_key uint64 [m_max], d_sample uint32 [m_max], d_done int32 [m_max]
+ * (read and written: rows with done != 0 give PAD and their logits are not read; a row that emits EOS or PAD is marked), d_front
+ * int32 [1] (the position filled is d_front[0] + 1), d_pred int32 [m_max] out, d_m the live row count on the device or NULL (all
+ * m_max rows); rows >= *d_m are not written.  Of `p` the temperature, top_k, top_p, pad_token, eos_token and seed are used.
+ * Refused: null pointers, V < 1, V > 1024, m_max < 1, *d_m outside [0, m_max], and the parameter errors of ttx_sample_generate. */
+int ttx_debug_sample(ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample, int32_t* d_done,
+                     const int32_t* d_front, int32_t* d_pred, const int32_t* d_m, int m_max, const ttx_sample_params* p, void* stream);
 
 /* ttx_debug_embed: k_embed on the caller's embedding table d_table [V, d] and positional table d_pe [pe_rows, d]:
  * X[row] = table[tok] + pe[pos + 1] in fp32, ids outside [0, V) looked up as id 0.  step == 0 (full mode): tok = d_tok[row],

@@ -17,8 +17,8 @@ LIB_PATH = PKG_DIR / "libttx_hip.so"
 # translation units (compiled in parallel, linked into one shared library) and the headers every one of them depends on
 UNITS = [CSRC / "ttx_api.hip", CSRC / "ttx_gemm.hip", CSRC / "ttx_attn.hip"]
 HEADERS = [CSRC / "ttx_internal.h", CSRC / "ttx_common.hip.h", CSRC / "ttx_loop_kernels.hip.h", CSRC / "ttx_metrics.hip.h",
-           CSRC / "ttx_score.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_select.h",
-           CSRC / "ttx_tokenizer.h", INCLUDE / "ttx.h"]
+           CSRC / "ttx_score.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_sample.hip.h",
+           CSRC / "ttx_select.h", CSRC / "ttx_tokenizer.h", INCLUDE / "ttx.h"]
 SOURCES = UNITS + HEADERS
 OBJ_DIR = CSRC / "build"
 
@@ -94,6 +94,13 @@ class GenStats(C.Structure):
                 ("status", C.c_int64)]
 
 
+class SampleParams(C.Structure):
+    """ttx_sample_params: temperature 0 is greedy, top_k 0 and top_p 1 are off."""
+    _fields_ = [("max_len", C.c_int32), ("num_samples", C.c_int32), ("temperature", C.c_float), ("top_k", C.c_int32),
+                ("top_p", C.c_float), ("pad_token", C.c_int32), ("bos_token", C.c_int32), ("eos_token", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
 class DebugAcceptArgs(C.Structure):
     """ttx_debug_accept_args: the device arrays and scalars of one k_accept / k_greedy_accept launch."""
     _fields_ = [(n, C.c_void_p) for n in ("d_act_idx", "d_front", "d_gen", "d_drafts", "d_pred", "d_rec", "d_out", "d_haspad",
@@ -136,6 +143,7 @@ SYMBOLS = {
     "ttx_make_drafts": (C.c_int, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP]),
     "ttx_greedy_speculative_generate": (C.c_int, [_VP, _VP, _I, _I, C.POINTER(GenParams), _VP, C.POINTER(GenStats), _VP]),
     "ttx_greedy_generate": (C.c_int, [_VP, _VP, _I, _I, C.POINTER(GenParams), _VP, C.POINTER(GenStats), _VP]),
+    "ttx_sample_generate": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SampleParams), _VP, C.POINTER(GenStats), _VP]),
     "ttx_greedy_speculative_generate_many": (C.c_int, [C.POINTER(_VP), _I, _I, C.POINTER(_VP), C.POINTER(C.c_int),
                                                       C.POINTER(C.c_int), C.POINTER(GenParams), C.POINTER(_VP),
                                                       C.POINTER(GenStats), _VP]),
@@ -174,6 +182,7 @@ SYMBOLS = {
     "ttx_debug_attn_as": (C.c_int, [_VP, _VP, _I, _VP, _VP, _I, _VP, _I, _I, C.c_float, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                     _VP, C.c_int64, _VP, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, _I, _VP]),
     "ttx_debug_argmax": (C.c_int, [_VP, _VP, _I, _VP, _VP, _I, _VP]),
+    "ttx_debug_sample": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I, C.POINTER(SampleParams), _VP]),
     "ttx_debug_embed": (C.c_int, [_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _I, _I, _I, _I, _I, _VP]),
     "ttx_debug_accept": (C.c_int, [_VP, C.POINTER(DebugAcceptArgs), C.POINTER(C.c_int64), _VP]),
     "ttx_debug_accept_block": (C.c_int, [_VP, C.POINTER(C.c_int32), _I, _VP]),

@@ -8,6 +8,7 @@
 #include "ttx_score.hip.h"
 #include "ttx_alternatives.hip.h"
 #include "ttx_attn_probs.hip.h"
+#include "ttx_sample.hip.h"
 #include "ttx_tokenizer.h"
 
 #include <algorithm>
@@ -997,6 +998,8 @@ struct StepCtx {
   const int* src_len = nullptr;    // slot pool: source keys per slot
   const int* cache_slot = nullptr; // batch pool: running row (candidate) -> slot of its KV cache
   bool want_argmax = true;
+  bool want_sample = false;        // sampling loop: k_sample on `sample` where k_argmax would run
+  SampleArgs sample{};
   int variant = GV_BIG;            // GemmVariant of this step's launches (bit-identical results; chosen from the live row count)
   // two-phase verify step of the slot pool; unset (null): the session's state, active list, step QKV buffer and argmax buffer
   DecState* st_ov = nullptr;       // live rows of this pass
@@ -1007,6 +1010,18 @@ struct StepCtx {
   // draft select (draft pass of a split step; all null otherwise): the pass's rows are stored compacted (k_probe_split)
   const int* row_base = nullptr; const int* draft_mask = nullptr; const int* row_map = nullptr;
 };
+
+// k_sample with k_argmax's launch shape; the values a lane holds follow the vocabulary (V <= SAMPLE_MAX_V, checked by the callers).
+static int launch_sample(hipStream_t st, const SampleArgs& a) {
+  const dim3 grid(cdiv(a.M, 4)), block(256);
+  if (a.V <= 64) hipLaunchKernelGGL((k_sample<1>), grid, block, 0, st, a);
+  else if (a.V <= 128) hipLaunchKernelGGL((k_sample<2>), grid, block, 0, st, a);
+  else if (a.V <= 256) hipLaunchKernelGGL((k_sample<4>), grid, block, 0, st, a);
+  else if (a.V <= 512) hipLaunchKernelGGL((k_sample<8>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((k_sample<16>), grid, block, 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
 
 static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) {
   const ttx_model* m = s->m;
@@ -1058,6 +1073,11 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
         return launch_attn(ATT_STEP_CROSS, s, st, ca, k.B, H, RPS, k.Ls, k.N, D1);
       },
       logits));
+  if (k.want_sample) {
+    SampleArgs a = k.sample;
+    a.logits = logits; a.V = V; a.pred = s->pred.as<int>(); a.m_ptr = m_ptr; a.M = Mmax;
+    return launch_sample(st, a);
+  }
   if (k.want_argmax) {
     hipLaunchKernelGGL(k_argmax, dim3(cdiv(Mmax, 4)), dim3(256), 0, st, logits, V, k.pred_ov ? k.pred_ov : s->pred.as<int>(), m_ptr, Mmax);
     HIP_TRY(hipGetLastError());
@@ -1216,8 +1236,11 @@ static int gen_validate(const ttx_session* s, const int64_t* d_src, int B, int L
   return TTX_OK;
 }
 
+// `per_src` > 1 (sampling loop): the B decoder rows are per_src consecutive rows per source, d_src holds B / per_src sources, and
+// the caller sets StepCtx::src_of before the first step.
 static int gen_start(GenJob& j, ttx_session* s, hipStream_t st, const int64_t* d_src, int B, int Ls, const ttx_gen_params* p,
-                     int64_t* d_out, ttx_gen_stats* stats, bool greedy, int16_t* d_traj = nullptr, int32_t* d_fin = nullptr) {
+                     int64_t* d_out, ttx_gen_stats* stats, bool greedy, int16_t* d_traj = nullptr, int32_t* d_fin = nullptr,
+                     int per_src = 1) {
   const ttx_model* m = s->m;
   const ttx_config& c = m->cfg;
   const int d = c.embedding_dim, Ld = c.num_decoder_layers, V = c.vocab_size;
@@ -1233,11 +1256,12 @@ static int gen_start(GenJob& j, ttx_session* s, hipStream_t st, const int64_t* d
   g.k.Lc = max_len + D1;           // cache positions per row (front + D < max_len + D)
   g.k.gen_ld = max_len + D + 2;
   const size_t Mmax = (size_t)B * step_rps(N, D);
+  const int Bs = B / per_src;      // sources
 
-  TTX_TRY(ensure(s->tok_src, (size_t)B * Ls * 4, st));
-  TTX_TRY(ensure(s->src_valid, (size_t)B * Ls, st));
-  TTX_TRY(ensure(s->memory, (size_t)B * Ls * d * 4, st));
-  TTX_TRY(ensure(s->memkv, (size_t)B * Ls * Ld * 2 * d * 4, st));
+  TTX_TRY(ensure(s->tok_src, (size_t)Bs * Ls * 4, st));
+  TTX_TRY(ensure(s->src_valid, (size_t)Bs * Ls, st));
+  TTX_TRY(ensure(s->memory, (size_t)Bs * Ls * d * 4, st));
+  TTX_TRY(ensure(s->memkv, (size_t)Bs * Ls * Ld * 2 * d * 4, st));
   TTX_TRY(ensure(s->drafts, (size_t)B * N * std::max(D, 1) * 4, st));
   TTX_TRY(ensure(s->gen, (size_t)B * g.k.gen_ld * 4, st));
   TTX_TRY(ensure(s->front, (size_t)B * 4, st));
@@ -1255,9 +1279,9 @@ static int gen_start(GenJob& j, ttx_session* s, hipStream_t st, const int64_t* d
   TTX_TRY(ensure(s->kcache, (size_t)Ld * B * g.k.Lc * d * 4, st));
   TTX_TRY(ensure(s->vcache, (size_t)Ld * B * g.k.Lc * d * 4, st));
   // the encoder and the step share the activation buffers; size them for the larger of the two
-  const size_t Macts = std::max(Mmax, (size_t)B * Ls);
+  const size_t Macts = std::max(Mmax, (size_t)Bs * Ls);
   TTX_TRY(ensure_acts(s, st, Macts, 1));
-  TTX_TRY(ensure(s->qkv, std::max((size_t)Ld * Mmax, (size_t)B * Ls) * 3 * d * 4, st));
+  TTX_TRY(ensure(s->qkv, std::max((size_t)Ld * Mmax, (size_t)Bs * Ls) * 3 * d * 4, st));
   TTX_TRY(ensure(s->slab, sizeof(float) * 16 * Macts * d, st));   // no allocation may happen inside a graph capture
   AcceptBlk* blk = nullptr;
   if (!greedy) TTX_TRY(accept_blk_for(s, st, B, &blk));
@@ -1266,11 +1290,11 @@ static int gen_start(GenJob& j, ttx_session* s, hipStream_t st, const int64_t* d
   s->ev_used = 0;
   HIP_TRY(hipEventRecord(s->ev_a, st));
   // encoder once per batch (:60-61) + cross-attention K/V of every decoder layer once per source
-  TTX_TRY(prepare_tokens(st, d_src, s->tok_src.as<int>(), s->src_valid.as<uint8_t>(), B * Ls, c.pad_token));
-  TTX_TRY(run_encoder(s, st, s->tok_src.as<int>(), s->src_valid.as<uint8_t>(), B, Ls, s->memory.as<float>()));
-  const int gv = variant_for_rows(s, (long long)B * Ls, false);
+  TTX_TRY(prepare_tokens(st, d_src, s->tok_src.as<int>(), s->src_valid.as<uint8_t>(), Bs * Ls, c.pad_token));
+  TTX_TRY(run_encoder(s, st, s->tok_src.as<int>(), s->src_valid.as<uint8_t>(), Bs, Ls, s->memory.as<float>()));
+  const int gv = variant_for_rows(s, (long long)Bs * Ls, false);
   TTX_TRY(launch_gemm(s, st, s->memory.as<float>(), d, m->p(m->cross_kv_w), d, m->p(m->cross_kv_b), s->memkv.as<float>(),
-                      Ld * 2 * d, nullptr, B * Ls, Ld * 2 * d, d, false, 0, 0, gv));
+                      Ld * 2 * d, nullptr, Bs * Ls, Ld * 2 * d, d, false, 0, 0, gv));
   // drafts from src[:, 1:] (:64-73): min_draft_len 1, max_draft_len max_len
   if (!greedy)
     TTX_TRY(launch_make_drafts<int>(st, s->tok_src.as<int>(), Ls, 1, B, Ls - 1, N, D, p->eos_token, p->pad_token,
@@ -1336,7 +1360,7 @@ static int gen_launch_step(GenJob& j, int width_bound) {
     s->snap_B = k.B; s->snap_rps = step_rps(k.N, k.D); s->snap_gen_ld = k.gen_ld; s->snap_step = j.launched + 1;
     TTX_TRY(launch_accept_and_commit(s, j.st, j.g, j.greedy));
   } else {
-    const int site = j.greedy ? GS_STEP_GREEDY : (j.g.la.row_rule ? GS_STEP_ROW_RULE : GS_STEP_SPECULATIVE);
+    const int site = k.want_sample ? GS_STEP_SAMPLE : j.greedy ? GS_STEP_GREEDY : (j.g.la.row_rule ? GS_STEP_ROW_RULE : GS_STEP_SPECULATIVE);
     TTX_TRY(graph_replay(s, j.st, s->step_graphs, GraphKey{site, k.B, k.Ls, k.N, k.D, k.max_len, kcap, k.variant, 0}, enqueue));
   }
   ++j.launched;
@@ -1432,8 +1456,42 @@ static int gen_finish_collect(GenJob& j) {
   return TTX_OK;
 }
 
+// The sampling loop's additions to a greedy generate call (ttx_sample_generate): B counts decoder rows, n of them per source.
+struct SampleSetup {
+  int n;
+  const int64_t* d_row_keys;       // [B / n] or null
+  SampleBlock blk;
+};
+
+// Session buffers of the sampling loop, sized before anything is captured.
+static int sample_ensure(ttx_session* s, hipStream_t st, size_t rows) {
+  TTX_TRY(ensure(s->smp_key, rows * 8, st));
+  TTX_TRY(ensure(s->smp_sample, rows * 4, st));
+  TTX_TRY(ensure(s->smp_done, rows * 4, st));
+  TTX_TRY(ensure(s->smp_src_of, rows * 4, st));
+  return ensure(s->smp_prm, sizeof(SampleBlock), st);
+}
+
+// After gen_start: the rows' keys, sample ids, done flags and sources and the call's parameter block on the device; every step
+// of the job then samples.
+static int sample_begin(GenJob& j, const SampleSetup& smp) {
+  ttx_session* s = j.s;
+  const int R = j.g.k.B;
+  hipLaunchKernelGGL(k_sample_params, dim3(1), dim3(64), 0, j.st, s->smp_prm.as<SampleBlock>(), smp.blk);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_sample_init, dim3(cdiv(R, 256)), dim3(256), 0, j.st, s->smp_key.as<unsigned long long>(),
+                     s->smp_sample.as<unsigned>(), s->smp_done.as<int>(), s->smp_src_of.as<int>(), smp.d_row_keys, R, smp.n);
+  HIP_TRY(hipGetLastError());
+  StepCtx& k = j.g.k;
+  k.src_of = s->smp_src_of.as<int>();
+  k.want_sample = true;
+  k.sample.key = s->smp_key.as<unsigned long long>(); k.sample.sample = s->smp_sample.as<unsigned>();
+  k.sample.done = s->smp_done.as<int>(); k.sample.front = s->front.as<int>(); k.sample.prm = s->smp_prm.as<SampleBlock>();
+  return TTX_OK;
+}
+
 static int generate_common(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_gen_params* p, int64_t* d_out,
-                           ttx_gen_stats* stats, void* stream, bool greedy) {
+                           ttx_gen_stats* stats, void* stream, bool greedy, const SampleSetup* smp = nullptr) {
   TTX_TRY(gen_validate(s, d_src, B, Ls, p, d_out, greedy));
   TTX_TRY(session_alive(s));
   HIP_TRY(hipSetDevice(s->m->device));
@@ -1446,7 +1504,13 @@ static int generate_common(ttx_session* s, const int64_t* d_src, int B, int Ls, 
   HIP_TRY(hipStreamWaitEvent(s->own_stream, s->ev_done, 0));
   hipStream_t st = s->own_stream;
   GenJob j;
-  TTX_TRY(gen_start(j, s, st, d_src, B, Ls, p, d_out, stats, greedy));
+  if (smp) {
+    TTX_TRY(sample_ensure(s, st, (size_t)B));
+    TTX_TRY(gen_start(j, s, st, d_src, B, Ls, p, d_out, stats, greedy, nullptr, nullptr, smp->n));
+    TTX_TRY(sample_begin(j, *smp));
+  } else {
+    TTX_TRY(gen_start(j, s, st, d_src, B, Ls, p, d_out, stats, greedy));
+  }
   const int D1 = j.g.k.D + 1;
   // One step in flight: the next step is enqueued as soon as the accept kernel has published the previous one's
   // result to the host-mapped words (no stream synchronisation inside the loop).
@@ -1476,6 +1540,45 @@ extern "C" int ttx_greedy_speculative_generate(ttx_session* s, const int64_t* d_
 extern "C" int ttx_greedy_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_gen_params* p,
                                    int64_t* d_out, ttx_gen_stats* stats, void* stream) {
   return generate_common(s, d_src, B, Ls, p, d_out, stats, stream, true);
+}
+
+// The SampleBlock of a call, or TTX_ERR_INVALID: temperature >= 0 and finite (0: greedy), top_k 0 or 1..32, top_p in (0, 1].  A call
+// that gives only top_p < 1 runs with top_k = 32.
+static int sample_block(const char* who, const ttx_sample_params* p, SampleBlock* out) {
+  if (!(p->temperature >= 0.0f) || !std::isfinite(p->temperature))
+    return fail(TTX_ERR_INVALID, std::string(who) + ": temperature must be finite and >= 0");
+  if (p->top_k < 0 || p->top_k > SAMPLE_MAX_KEEP) return fail(TTX_ERR_INVALID, std::string(who) + ": top_k must be 0 or in [1, 32]");
+  if (!(p->top_p > 0.0f) || !(p->top_p <= 1.0f)) return fail(TTX_ERR_INVALID, std::string(who) + ": top_p must be in (0, 1]");
+  SampleBlock b{};
+  b.seed = p->seed;
+  b.greedy = p->temperature == 0.0f ? 1 : 0;
+  b.inv_T = b.greedy ? 0.0f : 1.0f / p->temperature;
+  b.top_p = p->top_p;
+  b.top_k = (p->top_k == 0 && p->top_p < 1.0f) ? SAMPLE_MAX_KEEP : p->top_k;
+  b.pad = p->pad_token; b.eos = p->eos_token;
+  if (!b.greedy && !(b.inv_T > 0.0f && std::isfinite(b.inv_T)))
+    return fail(TTX_ERR_INVALID, std::string(who) + ": 1 / temperature is not a positive finite fp32");
+  *out = b;
+  return TTX_OK;
+}
+
+extern "C" int ttx_sample_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                   const ttx_sample_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
+  if (!s || !p) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
+  if (s->m->cfg.vocab_size > SAMPLE_MAX_V) return fail(TTX_ERR_INVALID, "ttx_sample_generate: vocabularies above 1024 are not supported");
+  if (p->num_samples < 1) return fail(TTX_ERR_INVALID, "ttx_sample_generate: num_samples must be at least 1");
+  SampleSetup smp{};
+  TTX_TRY(sample_block("ttx_sample_generate", p, &smp.blk));
+  if (B > 0 && (long long)B * p->num_samples * ((long long)std::max(p->max_len, 0) + 2) >= (1ll << 31))
+    return fail(TTX_ERR_INVALID, "ttx_sample_generate: B * num_samples * (max_len + 2) must stay below 2^31");
+  smp.n = p->num_samples; smp.d_row_keys = d_row_keys;
+  ttx_gen_params g{};
+  g.max_len = p->max_len; g.draft_len = 0; g.n_drafts = 1; g.pad_token = p->pad_token; g.bos_token = p->bos_token;
+  g.eos_token = p->eos_token; g.replace_token = p->pad_token; g.want_logits = 0;
+  if (B <= 0) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
+  const int rc = generate_common(s, d_src, B * p->num_samples, Ls, &g, d_out, stats, stream, true, &smp);
+  if (rc == TTX_OK && stats) stats->src_tokens_padded = (long long)B * Ls;    // the encoder ran once per source
+  return rc;
 }
 
 // Length buckets inside an admission.  An admission is encoded at the width of its longest row, so a chunk of 1 024 length-sorted
@@ -3241,6 +3344,32 @@ extern "C" int ttx_debug_argmax(ttx_session* s, const float* d_logits, int V, in
   hipLaunchKernelGGL(k_argmax, dim3(cdiv(m_max, 4)), dim3(256), 0, st, d_logits, V, d_pred, d_m, m_max);
   HIP_TRY(hipGetLastError());
   return TTX_OK;
+}
+
+extern "C" int ttx_debug_sample(ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample,
+                                int32_t* d_done, const int32_t* d_front, int32_t* d_pred, const int32_t* d_m, int m_max,
+                                const ttx_sample_params* p, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !d_logits || !d_key || !d_sample || !d_done || !d_front || !d_pred || !p)
+    return fail(TTX_ERR_INVALID, "null argument to ttx_debug_sample");
+  if (V < 1 || V > SAMPLE_MAX_V || m_max < 1) return fail(TTX_ERR_INVALID, "ttx_debug_sample: V must be in [1, 1024] and m_max positive");
+  SampleBlock blk{};
+  TTX_TRY(sample_block("ttx_debug_sample", p, &blk));
+  HIP_TRY(hipSetDevice(s->m->device));
+  if (d_m) {
+    int32_t m = -1;
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(&m, d_m, 4, hipMemcpyDeviceToHost));
+    if (m < 0 || m > m_max) return fail(TTX_ERR_INVALID, "ttx_debug_sample: the live row count on the device is outside [0, m_max]");
+  }
+  TTX_TRY(ensure(s->smp_prm, sizeof(SampleBlock), st));
+  hipLaunchKernelGGL(k_sample_params, dim3(1), dim3(64), 0, st, s->smp_prm.as<SampleBlock>(), blk);
+  HIP_TRY(hipGetLastError());
+  SampleArgs a{};
+  a.logits = d_logits; a.V = V; a.pred = d_pred; a.m_ptr = d_m; a.M = m_max;
+  a.key = reinterpret_cast<const unsigned long long*>(d_key); a.sample = d_sample; a.done = d_done; a.front = d_front;
+  a.prm = s->smp_prm.as<SampleBlock>();
+  return launch_sample(st, a);
 }
 
 // d_row_map (ttx_debug_embed_select; null: ttx_debug_embed): the launch writes m_rows rows, row i holding layout row d_row_map[i]

@@ -1,0 +1,222 @@
+// Seeded ancestral sampling on the greedy step (included by ttx_api.hip only): k_sample chooses a row's next token from its
+// logits where the greedy loop launches k_argmax.  Hand-written HIP for gfx950, wave64: ONE wave per logits row, 4 rows per
+// workgroup, the row in registers (V <= 64 * VPL <= 1024), no LDS, no atomics, nothing crosses a wave or a row.
+// The rule for a live row r (include/ttx.h states it as the contract; tests/util_sample_checks.py restates it in float64):
+//   1  done[r] != 0: pred[r] = pad, the logits are not read.
+//   2  greedy block (temperature 0): pred[r] is k_argmax's answer on the bits (first maximum, its NaN rule); no scaling.
+//   3  y_v = x_v * inv_T, one rounded fp32 product per logit (never contracted into the subtraction that follows).
+//   4  kept set.  Filter off: all V tokens, in ascending id.  Filter on: sample_topk_to_lanes below, i.e. topk_to_lanes
+//      (mask_with_num_logits_according_nucleus) on y: ranks best first, equal values the lower id first, rank i kept while the
+//      softmax mass ranked above it is < top_p and i < top_k, rank 0 always; lane i holds rank i.
+//   5  u = (x0 >> 8) * 2^-24 with x0 = word 0 of Philox4x32-10, key (seed_lo, seed_hi), counter (key_lo, key_hi, sample, pos),
+//      pos = front[0] + 1.
+//   6  e_v = expf(y_v - m) over the kept set (m the row's maximum of y), C its inclusive prefix sums in the order of 4, S the
+//      last of them, t = u * S: the first kept token with e_v > 0 and C_v > t; if rounding leaves none, the last kept token with
+//      e_v > 0.  A -inf logit has e_v = 0 and is never emitted.
+//      Order of the sums (fixed by V and the filter alone).  Filter off: lane l owns the VPL consecutive ids l * VPL .. and adds
+//      them in ascending order; the lanes' totals go through a Hillis-Steele inclusive scan (offsets 1, 2, .., 32); the prefix of
+//      an id is its lane's exclusive scan value plus the lane's running sum.  Filter on: the scan alone, over the ranks.
+//   7  the token is eos or pad: done[r] = 1.
+// Rows at or beyond *m_ptr are not written.  Rows outside the contract (NaN, +inf, all -inf) give some id in [0, V).
+#pragma once
+#include "ttx_loop_kernels.hip.h"
+
+namespace ttx {
+
+constexpr int SAMPLE_MAX_V = 64 * NUC_VPL;   // 1 024
+constexpr int SAMPLE_MAX_KEEP = NUC_MAX_KEEP;
+
+// The call's parameters, device-resident so that a captured step holds none of them (written by k_sample_params).
+struct SampleBlock {
+  unsigned long long seed;
+  float inv_T;                     // 1 / temperature, formed on the host; unused when greedy
+  float top_p;
+  int top_k;                       // 0: filter off (then top_p is 1); else 1..32
+  int greedy;                      // temperature == 0
+  int pad, eos;
+};
+
+struct SampleArgs {
+  const float* logits; int V;      // [M, V]
+  int* pred;                       // [M]
+  const int* m_ptr; int M;         // live rows on the device (null: M)
+  const unsigned long long* key;   // [M]
+  const unsigned* sample;          // [M]
+  int* done;                       // [M], read and written
+  const int* front;                // front[0] + 1 is the position being filled
+  const SampleBlock* prm;
+};
+
+__global__ void k_sample_params(SampleBlock* out, SampleBlock v) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *out = v;
+}
+
+// Row r = b * n + j of a sampling loop: source b, sample j, key (row_keys[b] or b, j), not done.
+__global__ void k_sample_init(unsigned long long* key, unsigned* sample, int* done, int* src_of, const int64_t* row_keys, int R, int n) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const int b = r / n;
+  key[r] = row_keys ? (unsigned long long)row_keys[b] : (unsigned long long)b;
+  sample[r] = (unsigned)(r - b * n);
+  done[r] = 0;
+  src_of[r] = b;
+}
+
+// Word 0 of Philox4x32-10 (Salmon et al., SC'11): integer arithmetic only.
+__device__ __forceinline__ unsigned philox4x32_10_word0(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+  for (int round = 0; round < 10; ++round) {
+    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
+    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return c0;
+}
+
+__device__ __forceinline__ float sample_uniform(unsigned long long seed, unsigned long long key, unsigned sample, unsigned pos) {
+  const unsigned x0 = philox4x32_10_word0((unsigned)key, (unsigned)(key >> 32), sample, pos, (unsigned)seed, (unsigned)(seed >> 32));
+  return (float)(x0 >> 8) * 5.9604644775390625e-08f;     // 24 bits * 2^-24: exact, in [0, 1)
+}
+
+// Hillis-Steele inclusive scan over the 64 lanes, offsets 1, 2, .., 32.
+__device__ __forceinline__ float wave_scan_incl(float v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float up = __shfl_up(v, o, 64);
+    if (lane >= o) v += up;
+  }
+  return v;
+}
+
+// topk_to_lanes on y = x * inv_T: the same selection and the same arithmetic on the scaled row (lane r holds rank r).
+template <int VPL>
+__device__ __forceinline__ void sample_topk_to_lanes(const float* __restrict__ p, int V, float inv_T, float nucleus, int n_best, int lane,
+                                                     int& my_idx, float& my_val, int& n_kept, float& m_out) {
+  float v[VPL];
+  float m = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    const int c = lane + 64 * i;
+    v[i] = c < V ? __fmul_rn(p[c], inv_T) : -INFINITY;
+    m = fmaxf(m, v[i]);
+  }
+  m = wave_max(m);
+  float z = 0.f;
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) z += (lane + 64 * i < V) ? expf(v[i] - m) : 0.f;
+  z = wave_sum(z);
+  m_out = m;
+  n_kept = 0;
+  my_idx = -1; my_val = -INFINITY;
+  float above = 0.f;                        // softmax mass of the ranks already taken
+  for (int rank = 0; rank < n_best && rank < V; ++rank) {
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i)
+      if (v[i] > best || (v[i] == best && lane + 64 * i < bi && v[i] != -INFINITY)) { best = v[i]; bi = lane + 64 * i; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(best, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    if (bi == 0x7fffffff) break;            // nothing finite left
+    if (rank != 0 && !(above < nucleus)) break;   // the mass above only grows: no later rank can be kept
+    if (lane == rank) { my_idx = bi; my_val = best; }
+    ++n_kept;
+    above += expf(best - m) / z;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i)
+      if (lane + 64 * i == bi) v[i] = -INFINITY;
+  }
+}
+
+template <int VPL>
+__global__ __launch_bounds__(256) void k_sample(const SampleArgs a) {
+  const int rows = a.m_ptr ? *a.m_ptr : a.M;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;                  // wave-uniform
+  const int lane = threadIdx.x & 63;
+  const SampleBlock prm = *a.prm;
+  if (a.done[row]) {                        // wave-uniform
+    if (lane == 0) a.pred[row] = prm.pad;
+    return;
+  }
+  const int V = a.V;
+  const float* p = a.logits + (size_t)row * V;
+  int tok;
+  if (prm.greedy) {
+    // k_argmax, statement for statement
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int c = lane; c < V; c += 64) {
+      const float v = p[c];
+      if (v > best) { best = v; bi = c; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(best, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    tok = (bi < V) ? bi : 0;
+  } else {
+    const float u = sample_uniform(prm.seed, a.key[row], a.sample[row], (unsigned)(a.front[0] + 1));
+    if (prm.top_k > 0) {
+      int my_idx, n_kept;
+      float my_val, m;
+      sample_topk_to_lanes<VPL>(p, V, prm.inv_T, prm.top_p, prm.top_k, lane, my_idx, my_val, n_kept, m);
+      const float e = (lane < n_kept) ? expf(my_val - m) : 0.0f;
+      const float C = wave_scan_incl(e, lane);
+      const float t = __fmul_rn(u, __shfl(C, 63, 64));
+      const unsigned long long live = __ballot(e > 0.0f);
+      const unsigned long long hit = __ballot(e > 0.0f && C > t);
+      const int src = hit ? __ffsll((long long)hit) - 1 : (live ? 63 - __clzll((long long)live) : 0);
+      tok = __shfl(my_idx, src, 64);
+    } else {
+      // lane l owns ids l * VPL .. l * VPL + VPL - 1
+      float e[VPL];
+      float m = -INFINITY;
+      const int c0 = lane * VPL;
+#pragma unroll
+      for (int j = 0; j < VPL; ++j) {
+        e[j] = (c0 + j < V) ? __fmul_rn(p[c0 + j], prm.inv_T) : -INFINITY;
+        m = fmaxf(m, e[j]);
+      }
+      m = wave_max(m);
+      float tot = 0.0f;
+      int last = -1;                        // the lane's last id with e > 0
+#pragma unroll
+      for (int j = 0; j < VPL; ++j) {
+        e[j] = (c0 + j < V) ? expf(e[j] - m) : 0.0f;
+        tot += e[j];
+        if (e[j] > 0.0f) last = c0 + j;
+      }
+      const float C = wave_scan_incl(tot, lane);
+      const float t = __fmul_rn(u, __shfl(C, 63, 64));
+      const unsigned long long live = __ballot(last >= 0);
+      const unsigned long long hit = __ballot(last >= 0 && C > t);
+      const int src = hit ? __ffsll((long long)hit) - 1 : (live ? 63 - __clzll((long long)live) : 0);
+      // inside the chosen lane: the first id whose prefix exceeds t, else the lane's last id with e > 0
+      const float before = __shfl_up(C, 1, 64);
+      float run = lane ? before : 0.0f;     // the scan value of the lanes before this one
+      int pick = -1;
+#pragma unroll
+      for (int j = 0; j < VPL; ++j) {
+        run += e[j];
+        if (pick < 0 && e[j] > 0.0f && run > t) pick = c0 + j;
+      }
+      if (pick < 0) pick = last;
+      tok = __shfl(pick, src, 64);
+    }
+    if ((unsigned)tok >= (unsigned)V) tok = 0;   // rows outside the contract only: never an id outside [0, V)
+  }
+  if (lane == 0) {
+    a.pred[row] = tok;
+    if (tok == prm.eos || tok == prm.pad) a.done[row] = 1;
+  }
+}
+
+}  // namespace ttx

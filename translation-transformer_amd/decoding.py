@@ -345,8 +345,57 @@ class TranslationInferenceGreedy(_ScoresHypotheses):
         return self._scored(src, out, return_scores)
 
 
+class TranslationInferenceSampling(_ScoresHypotheses):
+    """Seeded ancestral sampling: ``num_samples`` draws per source from the model's distribution under ``temperature``,
+    ``top_k`` and ``top_p``.  The whole loop runs in ttx_sample_generate: the greedy loop (KV cache, one graph per step) with
+    k_sample choosing each token, the encoder once per source.  The reference has the seam for it
+    (TranslationInferenceGreedy.sample, src/decoding/standard_decoding.py:27-28) and no sampler of its own.
+
+    ``temperature=0`` is greedy.  ``top_k`` is 0 (off) or 1..32; ``top_p`` is in (0, 1] (1: off); a ``top_p < 1`` with
+    ``top_k=0`` runs with ``top_k=32``, so a filtered kept set never holds more than 32 tokens.  Vocabularies up to 1 024.
+    Sample ``j`` of a source depends on (seed, the source's row key, j, position) and on the source alone: not on the batch
+    size, ``num_samples`` or the other rows of the batch.  A sampled PAD ends a row as EOS does."""
+
+    def __init__(self, model, max_len: int, pad_token: int, bos_token: int, eos_token: int, temperature: float = 1.0,
+                 top_k: int = 0, top_p: float = 1.0, num_samples: int = 1, seed: int = 0) -> None:
+        self.model = _need_native(model)
+        self.max_len = max_len
+        self.pad_token, self.bos_token, self.eos_token = pad_token, bos_token, eos_token
+        self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
+        self.num_samples, self.seed = int(num_samples), int(seed)
+        self.model_calls_num = 0
+        self.given_tokens = 0
+
+    def __str__(self):
+        return (f"Sampling (temperature={self.temperature}, top_k={self.top_k}, top_p={self.top_p}, "
+                f"num_samples={self.num_samples}, seed={self.seed}, max_len={self.max_len})")
+
+    def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False):
+        """Long[B, num_samples, max_len].  ``row_keys``: one integer per source (default 0..B-1), the source's identity for
+        the random stream: the same (source, key) gives the same samples in any batch.  ``return_scores=True``:
+        ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``)."""
+        m, n = self.model, self.num_samples
+        src = src.to(m.device, torch.int64).contiguous()
+        m.check_tokens(src)
+        B, Ls = src.shape
+        keys = None
+        if row_keys is not None:
+            keys = torch.as_tensor(row_keys, dtype=torch.int64).to(m.device).contiguous()
+            if keys.shape != (B,):
+                raise ValueError(f"row_keys must hold one key per source ({B}), got shape {tuple(keys.shape)}")
+        p = N.SampleParams(self.max_len, n, self.temperature, self.top_k, self.top_p, self.pad_token, self.bos_token,
+                           self.eos_token, self.seed & 0xFFFFFFFFFFFFFFFF)
+        out = torch.empty((B, max(n, 1), max(self.max_len, 1)), dtype=torch.int64, device=m.device)
+        st = N.GenStats()
+        N.check(m._lib.ttx_sample_generate(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
+                                           C.byref(p), out.data_ptr(), C.byref(st), m._stream()))
+        self.model_calls_num += int(st.model_calls)
+        self.given_tokens += int((src != m.src_pad_token_i).sum())
+        return self._scored(src, out, return_scores)
+
+
 class TranslationInferenceBeamSearch(_ScoresHypotheses):
-    """Drop-in for src/decoding/standard_decoding.py:58-174: the whole loop runs in ttx_beam_generate (per-hypothesis KV
+    """Drop-in for src/decoding/standard_decoding.py:58-174:the whole loop runs in ttx_beam_generate (per-hypothesis KV
     cache, encoder and cross K/V once per source, log-softmax + top-beam + row assembly in one kernel per step)."""
 
     def __init__(self, model, beam_size: int, max_len: int, pad_token: int, bos_token: int, eos_token: int):

@@ -168,6 +168,7 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
                  learning_rate: float = 3e-4, weight_decay: float = 0., scheduler: str = "const", warmup_steps: int = 0,
                  generation: str = "beam_search", beam_size: int = 0, max_len: int = 0, n_drafts: int = 0,
                  draft_len: int = 0, smart_drafts_mode: bool = True,
+                 sampling_temperature: float = 1.0, sampling_top_k: int = 0, sampling_top_p: float = 1.0, sampling_seed: int = 0,
                  report_prediction_time: bool = True, report_prediction_file: str | None = None):
         super().__init__()
         self.save_hyperparameters(ignore=["src_tokenizer", "tgt_tokenizer"])
@@ -183,8 +184,8 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         self.model = WeightContainer(self.src_vocab_size, self.tgt_vocab_size, num_encoder_layers, num_decoder_layers,
                                      embedding_dim, num_heads, feedforward_dim, share_embeddings,
                                      self.src_pad_token_i, self.tgt_pad_token_i, activation)
-        if generation not in ("greedy", "beam_search", "greedy_speculative", "beam_search_speculative"):
-            options = ", ".join(["beam_search", "greedy", "greedy_speculative", "beam_search_speculative"])
+        if generation not in ("greedy", "beam_search", "greedy_speculative", "beam_search_speculative", "sampling"):
+            options = ", ".join(["beam_search", "greedy", "greedy_speculative", "beam_search_speculative", "sampling"])
             raise ValueError(f'Unknown generation option {generation}. Options are {options}.')
         if generation == "greedy_speculative":
             assert draft_len > 0, "Number of speculative tokens must be a positive integer."
@@ -192,6 +193,9 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         self.generator = None
         self._ahead = None
         self._scores_on = False
+        # generation="sampling": reactions predicted so far in this predict run; a reaction's running index is its row key, so
+        # its samples do not depend on the batch size or on what shares its batch
+        self._predict_rows = 0
         # batches decoded ahead of predict_step (0: decode every batch inside its own predict_step like the reference);
         # not an init_arg, so the reference's YAML files load unchanged — set the attribute or TTX_PREDICT_WINDOW
         self.predict_window = 256
@@ -259,6 +263,10 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         if h.generation == "greedy_speculative":
             return D.TranslationInferenceGreedySpeculative(m, max_len=h.max_len, draft_len=h.draft_len, n_drafts=h.n_drafts,
                                                            replace_token=self.tgt_tokenizer.encoder_dict["c"], **common)
+        if h.generation == "sampling":               # beam_size samples per reaction, as the reference uses it for n_best
+            return D.TranslationInferenceSampling(m, max_len=h.max_len, temperature=h.sampling_temperature, top_k=h.sampling_top_k,
+                                                  top_p=h.sampling_top_p, num_samples=max(1, h.beam_size), seed=h.sampling_seed,
+                                                  **common)
         return D.TranslationInferenceBeamSearchSpeculative(
             m, vocab_size=self.tgt_vocab_size, max_len=h.max_len, n_best=h.beam_size, draft_len=h.draft_len,
             n_drafts=h.n_drafts, C_token=self.tgt_tokenizer.encoder_dict["c"], smart_drafts_mode=h.smart_drafts_mode, **common)
@@ -271,7 +279,11 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         pred = None
         if ahead is not None and dataloader_idx == 0:
             pred = ahead.take(batch["src_tokens"], batch_idx)
-        if pred is None:
+        if pred is None and self.hparams.generation == "sampling":
+            B = int(batch["src_tokens"].shape[0])
+            pred = self.generator.generate(batch["src_tokens"], row_keys=torch.arange(self._predict_rows, self._predict_rows + B))
+            self._predict_rows += B
+        elif pred is None:
             pred = self.generator.generate(batch["src_tokens"])
         if self._alternatives_k > 0:
             self._alternatives_batch(batch["src_tokens"], pred, batch_idx)
@@ -344,6 +356,7 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
     def on_predict_start(self) -> None:
         self.build_native()                      # weights are final here (Trainer.predict has loaded --ckpt_path)
         self._ahead = None
+        self._predict_rows = 0
         self._scores_on = bool(self.predict_with_scores) or os.environ.get("TTX_PREDICT_SCORES") == "1"
         self.predict_scores = {}
         self._attention_on = bool(self.predict_with_attention) or os.environ.get("TTX_PREDICT_ATTENTION") == "1"

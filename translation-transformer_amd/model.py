@@ -302,6 +302,17 @@ class NativeTransformer:
         N.check(self._lib.ttx_debug_argmax(self._session, logits.data_ptr(), int(logits.shape[1]), pred.data_ptr(),
                                            self._ptr(m_live), int(m_max), self._stream()))
 
+    def debug_sample(self, logits: torch.Tensor, key: torch.Tensor, sample: torch.Tensor, done: torch.Tensor, front: torch.Tensor,
+                     pred: torch.Tensor, m_max: int, m_live: torch.Tensor | None = None, *, temperature: float = 1.0, top_k: int = 0,
+                     top_p: float = 1.0, pad: int = 0, eos: int = 2, seed: int = 0) -> None:
+        """One k_sample launch (ttx_debug_sample): ``logits`` fp32 [m_max, V] contiguous, ``key`` int64 [m_max] (read as
+        uint64), ``sample`` int32 [m_max] (read as uint32), ``done`` int32 [m_max] (read and written), ``front`` int32 [1],
+        ``pred`` int32 [m_max], ``m_live`` an int32 device scalar or None."""
+        p = N.SampleParams(1, 1, float(temperature), int(top_k), float(top_p), int(pad), 0, int(eos), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        N.check(self._lib.ttx_debug_sample(self._session, logits.data_ptr(), int(logits.shape[1]), key.data_ptr(), sample.data_ptr(),
+                                           done.data_ptr(), front.data_ptr(), pred.data_ptr(), self._ptr(m_live), int(m_max),
+                                           C.byref(p), self._stream()))
+
     def debug_embed(self, table: torch.Tensor, pe: torch.Tensor, x: torch.Tensor, tok: torch.Tensor | None = None, rows: int = 0,
                     L: int = 0, act_idx: torch.Tensor | None = None, front: torch.Tensor | None = None,
                     gen: torch.Tensor | None = None, drafts: torch.Tensor | None = None, B: int = 0, n: int = 1, d: int = 0,

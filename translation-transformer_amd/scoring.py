@@ -125,6 +125,35 @@ def rank_by_score(pred, scores):
     return pred.gather(1, perm[:, :, None].expand(-1, -1, pred.shape[2])), out, perm
 
 
+def unique_samples(samples, scores, eos: int = 2):
+    """The distinct hypotheses among each source's samples.  ``samples`` Long[B, N, L] as
+    ``TranslationInferenceSampling.generate`` returns it; ``scores`` Float[B, N] (or anything with ``score`` [B, N], such as a
+    HypothesisScores).  Two samples are the same hypothesis when their tokens agree up to and including the first ``eos`` (whatever
+    follows it is ignored).  Returns one list per source of ``(tokens Long[L], count, score)``:
+    the first occurrence of each hypothesis, how many of the N samples equal it, and its score, ordered by descending score
+    (equal scores: first occurrence first).  Plain torch, on whatever device the tensors are on."""
+    import torch
+    sc = getattr(scores, "score", scores)
+    B, N, L = samples.shape
+    if tuple(sc.shape) != (B, N):
+        raise ValueError(f"scores must be [B, N] = [{B}, {N}], got {tuple(sc.shape)}")
+    after = ((samples == eos).cumsum(-1) - (samples == eos).long()) > 0          # strictly after the first EOS
+    canon = torch.where(after, torch.full_like(samples, -1), samples).cpu()
+    rows, vals = samples.cpu(), sc.detach().cpu().tolist()
+    out = []
+    for b in range(B):
+        first: dict = {}
+        for j in range(N):
+            key = tuple(canon[b, j].tolist())
+            if key in first:
+                first[key][1] += 1
+            else:
+                first[key] = [j, 1]
+        uniq = sorted(first.values(), key=lambda e: (-vals[b][e[0]], e[0]))
+        out.append([(rows[b, j], cnt, vals[b][j]) for j, cnt in uniq])
+    return out
+
+
 def write_scores(filename: str, scores, append: bool = True) -> None:
     """The side file of the prediction CSV: one line per source, ``score_1,length_1,finished_1,...,score_N,length_N,finished_N``
     in the order of the CSV's ``prediction_1..N`` columns (scores with 9 significant digits: fp32 round-trips).  The prediction
