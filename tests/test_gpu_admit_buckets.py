@@ -1,4 +1,4 @@
-"""Length buckets inside a pool admission (csrc/ttx_api.hip: admit_chunks): the rows of one admission are encoded in consecutive
+"""Length buckets inside a pool admission (csrc/ttx_admit.h: admit_chunks): the rows of one admission are encoded in consecutive
 sub-chunks, each at the width of its own longest row, instead of all at the width of the admission's longest row.  A row's encoder
 output, cross K/V and drafts do not depend on the padding of the launch that computed them, so TTX_ADMIT_ROWS (the padded rows at
 which a sub-chunk closes; 0: one chunk, as before) may change the counters of padded work and nothing else.  Every check is exact
@@ -13,6 +13,7 @@ import ctypes as C
 import pytest
 import torch
 
+from util_admit import padded_rows
 from util_draft_select import h4_gen, h4_state
 from util_models import BOS, EOS, PAD, fixture_tokens, load_npz, tiny_state, upto_eos
 
@@ -38,30 +39,6 @@ def model(request, tta):
     m = tta.NativeTransformer(st, cfg["num_heads"], 0, device=0)
     yield m, gold
     m.close()
-
-
-def chunk_ends(lens, budget):
-    n = len(lens)
-    if budget <= 0 or n * max(2, max(lens)) < budget:
-        return [n]
-    ends, first, w = [], 0, 2
-    for r in range(n):
-        w = max(w, lens[r])
-        if (r + 1 - first) * w >= budget:
-            ends.append(r + 1)
-            first, w = r + 1, 2
-    if first < n:
-        if ends and (n - first) * max(2, max(lens[first:])) * 2 < budget:
-            ends[-1] = n
-        else:
-            ends.append(n)
-    return ends
-
-
-def padded_rows(lens, budget):
-    """(rows x width summed over the sub-chunks of ONE admission, number of sub-chunks)."""
-    ends = chunk_ends(lens, budget)
-    return sum((e - f) * max(2, max(lens[f:e])) for f, e in zip([0] + ends[:-1], ends)), len(ends)
 
 
 def lengths_of(src):

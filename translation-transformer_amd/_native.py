@@ -18,7 +18,7 @@ LIB_PATH = PKG_DIR / "libttx_hip.so"
 UNITS = [CSRC / "ttx_api.hip", CSRC / "ttx_gemm.hip", CSRC / "ttx_attn.hip"]
 HEADERS = [CSRC / "ttx_internal.h", CSRC / "ttx_common.hip.h", CSRC / "ttx_loop_kernels.hip.h", CSRC / "ttx_metrics.hip.h",
            CSRC / "ttx_score.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_sample.hip.h",
-           CSRC / "ttx_select.h", CSRC / "ttx_tokenizer.h", INCLUDE / "ttx.h"]
+           CSRC / "ttx_select.h", CSRC / "ttx_tokenizer.h", CSRC / "ttx_drive.h", CSRC / "ttx_admit.h", INCLUDE / "ttx.h"]
 SOURCES = UNITS + HEADERS
 OBJ_DIR = CSRC / "build"
 

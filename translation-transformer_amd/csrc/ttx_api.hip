@@ -1,8 +1,10 @@
 // Host side of libttx_hip.so: the C ABI of include/ttx.h, the runtime around the kernels (sessions, workspaces, hipGraphs,
-// polling loops, slot pools) and the loop / bookkeeping kernels (ttx_loop_kernels.hip.h).  The GEMM and attention families
+// polling loops under drive_sessions, slot pools) and the loop / bookkeeping kernels (ttx_loop_kernels.hip.h).  The GEMM and attention families
 // live in ttx_gemm.hip / ttx_attn.hip and are reached through the launchers of ttx_internal.h.
 // No CPU fallback exists anywhere in this library: without a gfx950 device every entry point fails.
 #include "ttx_internal.h"
+#include "ttx_admit.h"
+#include "ttx_drive.h"
 #include "ttx_loop_kernels.hip.h"
 #include "ttx_metrics.hip.h"
 #include "ttx_score.hip.h"
@@ -462,6 +464,44 @@ static int prepare_tokens(hipStream_t st, const int64_t* d_in, int* out, uint8_t
   hipLaunchKernelGGL(k_prepare_tokens, dim3(cdiv(n, 256)), dim3(256), 0, st, d_in, out, valid, n, pad);
   HIP_TRY(hipGetLastError());
   return TTX_OK;
+}
+
+// The sources of a decoding loop: R rows of Ls int64 tokens at d_src (ld_src apart; 0: packed, B x Ls in one piece) -> s->tok_src
+// and `valid`, the encoder into s->memory, and the cross-attention K/V of every decoder layer, packed [R * Ls][Ld * 2d], into
+// `memkv`.  enc_qkv: run_encoder's qkv_buf.
+static int encode_sources(ttx_session* s, hipStream_t st, const int64_t* d_src, int ld_src, int R, int Ls, uint8_t* valid, float* memkv,
+                          float* enc_qkv = nullptr) {
+  const ttx_model* m = s->m;
+  const int d = m->cfg.embedding_dim, kv_row = m->cfg.num_decoder_layers * 2 * d;
+  if (ld_src == 0) {
+    TTX_TRY(prepare_tokens(st, d_src, s->tok_src.as<int>(), valid, R * Ls, m->cfg.pad_token));
+  } else {
+    hipLaunchKernelGGL(k_prepare_tokens_2d, dim3(cdiv(R * Ls, 256)), dim3(256), 0, st, d_src, ld_src, s->tok_src.as<int>(), valid, R, Ls,
+                       m->cfg.pad_token);
+    HIP_TRY(hipGetLastError());
+  }
+  TTX_TRY(run_encoder(s, st, s->tok_src.as<int>(), valid, R, Ls, s->memory.as<float>(), enc_qkv));
+  return launch_gemm(s, st, s->memory.as<float>(), d, m->p(m->cross_kv_w), d, m->p(m->cross_kv_b), memkv, kv_row, nullptr, R * Ls, kv_row,
+                     d, false, 0, 0, variant_for_rows(s, (long long)R * Ls, false));
+}
+
+// Sizes the workspaces of a call before anything is enqueued or captured: need(buffer, bytes) for each, then TTX_TRY(need.rc).
+// The first failure sticks and skips the rest.
+struct Needs {
+  hipStream_t st;
+  int rc = TTX_OK;
+  void operator()(Buf& b, size_t bytes) { if (rc == TTX_OK) rc = ensure(b, bytes, st); }
+};
+
+// What every decoding loop needs for its verify steps of up to Mmax rows, next to an encoder pass over src_rows rows: the argmax,
+// the loop state, the logits, and the activation, Q/K/V and slab buffers the encoder and the step share (sized for the larger).
+static void need_step_workspaces(ttx_session* s, Needs& need, size_t Mmax, size_t src_rows) {
+  const ttx_config& c = s->m->cfg;
+  const size_t d = c.embedding_dim, Macts = std::max(Mmax, src_rows);
+  need(s->pred, Mmax * 4); need(s->state, sizeof(DecState)); need(s->logits, Mmax * c.vocab_size * 4);
+  if (need.rc == TTX_OK) need.rc = ensure_acts(s, need.st, Macts, 1);
+  need(s->qkv, std::max((size_t)c.num_decoder_layers * Mmax, src_rows) * 3 * d * 4);
+  need(s->slab, sizeof(float) * 16 * Macts * d);            // no allocation may happen inside a graph capture
 }
 
 extern "C" int ttx_encode_src(ttx_session* s, const int64_t* d_src, int B, int Ls, float* d_memory, void* stream) {
@@ -1128,12 +1168,6 @@ static int launch_accept_and_commit(ttx_session* s, hipStream_t st, const GenCtx
   return TTX_OK;
 }
 
-// The polling loops give up after this long without a published step (a failed kernel never publishes).
-static bool watchdog_expired(std::chrono::steady_clock::time_point since) {
-  static const int limit_s = [] { const char* e = getenv("TTX_WATCHDOG_SECONDS"); return e && atoi(e) > 0 ? atoi(e) : 120; }();
-  return std::chrono::steady_clock::now() - since > std::chrono::seconds(limit_s);
-}
-
 // A verify step did not publish within the watchdog time.  The stream may be stuck for good, so NOTHING here (or in the
 // callers, on this path) synchronises it: the session is marked unusable, every later call on it fails at once, and
 // destroying it leaks its workspaces instead of waiting for the device.  The process should report the error and exit
@@ -1148,15 +1182,6 @@ static int session_alive(const ttx_session* s) {
   if (s && s->dead) return fail(TTX_ERR_HIP, "this session hung in an earlier call and is unusable");
   return TTX_OK;
 }
-
-// A polling loop's wait for the step in flight: stalled() counts one fruitless look and asks the watchdog on every 65 536th,
-// advanced() restarts both when the step has published.  No HIP call while polling: only the clock.
-struct Progress {
-  unsigned idle_spins = 0;
-  std::chrono::steady_clock::time_point last_progress = std::chrono::steady_clock::now();
-  bool stalled() { return (++idle_spins & 0xffff) == 0 && watchdog_expired(last_progress); }
-  void advanced() { idle_spins = 0; last_progress = std::chrono::steady_clock::now(); }
-};
 
 // Key capacity of a step whose rows see fewer than `width` prefix keys: the LDS images of the self-attention come in buckets of
 // 64 keys, so that a graph serves 64 widths.
@@ -1195,10 +1220,70 @@ static int graph_replay(ttx_session* s, hipStream_t st, GraphCache& cache, const
   return TTX_OK;
 }
 
+// LoopArgs and KvCopyArgs of a speculative loop over the g.k.B slots of the session's greedy-path buffers: everything but the output
+// buffer and the per-row trace (gen_start) and the pool's own fields (pool_start), which the caller sets after the call.
+static int fill_loop_args(ttx_session* s, GenCtx& g, AcceptBlk* blk) {
+  const StepCtx& k = g.k;
+  const int d = s->m->cfg.embedding_dim;
+  LoopArgs& la = g.la;
+  la.st = s->state.as<DecState>(); la.act_idx = s->act_idx.as<int>(); la.front = s->front.as<int>();
+  la.gen = s->gen.as<int>(); la.gen_ld = k.gen_ld; la.drafts = s->drafts.as<int>(); la.pred = s->pred.as<int>();
+  la.rec = s->rec.as<CopyRec>(); la.haspad = s->haspad.as<int>();
+  HIP_TRY(hipHostGetDevicePointer((void**)&la.host, (void*)s->host_info, 0));
+  la.B = k.B; la.N = k.N; la.D = k.D; la.Ls = k.Ls; la.max_len = k.max_len; la.pad = k.p.pad_token; la.bos = k.p.bos_token;
+  la.eos = k.p.eos_token; la.traj_ld = k.max_len + 1; la.blk = blk;
+  KvCopyArgs& kc = g.kc;
+  kc.st = la.st; kc.rec = la.rec; kc.qkv = s->qkv.as<float>();
+  kc.qkv_layer_stride = (long long)k.B * step_rps(k.N, k.D) * 3 * d;
+  kc.kcache = s->kcache.as<float>(); kc.vcache = s->vcache.as<float>();
+  kc.cache_seq_stride = (long long)k.Lc * d; kc.cache_layer_stride = (long long)k.B * k.Lc * d;
+  kc.N = k.N; kc.D = k.D; kc.d = d;
+  return TTX_OK;
+}
+
 struct EventGuard {              // destroys the event on every exit path
   hipEvent_t e = nullptr;
   ~EventGuard() { if (e) (void)hipEventDestroy(e); }
 };
+
+// One call decoding on sessions[0 .. n) from this host thread, each session on its own stream (the caller's may be the legacy null
+// stream, which cannot be captured into a graph).  Every session stream first waits for what the caller's stream holds; then
+// start(i) runs for each session in turn, and drive_jobs (ttx_drive.h) hands out turn(i) until every session has finished.
+// Whatever ends the call, a stream that was given work has drained when it returns, so the caller may free its buffers and
+// sees the outputs from whatever it enqueues next.  The one exception is a hang: nothing is synchronised then, every session
+// of the call is retired, and the call returns what session_hung set.
+template <class Start, class TurnFn>
+static int drive_sessions(ttx_session** sessions, int n, bool serial, void* stream, Start&& start, TurnFn&& turn) {
+  for (int i = 0; i < n; ++i) TTX_TRY(session_alive(sessions[i]));
+  HIP_TRY(hipSetDevice(sessions[0]->m->device));
+  release_retired();
+  EventGuard ready;
+  HIP_TRY(hipEventCreateWithFlags(&ready.e, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(ready.e, (hipStream_t)stream));
+  const auto after_caller = [&](ttx_session* s) -> int {
+    TTX_TRY(ensure_own_stream(s));
+    HIP_TRY(hipStreamWaitEvent(s->own_stream, ready.e, 0));
+    return TTX_OK;
+  };
+  DriveResult r{TTX_OK, false, -1};
+  int given = 0;                   // sessions whose stream may hold work of this call
+  while (given < n && r.rc == TTX_OK) {
+    r.rc = after_caller(sessions[given]);
+    if (r.rc == TTX_OK) r.rc = start(given);
+    ++given;
+  }
+  if (r.rc == TTX_OK) r = drive_jobs(n, serial, watchdog_seconds(), turn);
+  if (r.hung) {
+    // a stream that never published may never drain: do not wait on any of them, and retire every session of this call
+    // (their workspaces may still be written by whatever is stuck)
+    const int rc = session_hung(sessions[r.stalled_job]);
+    for (int i = 0; i < n; ++i) sessions[i]->dead = true;
+    return rc;
+  }
+  for (int i = 0; i < given; ++i)
+    if (sessions[i]->own_stream) (void)hipStreamSynchronize(sessions[i]->own_stream);
+  return r.rc;
+}
 
 // One generate call in flight on one session: start (encoder, drafts, loop init) -> steps -> finish.
 struct GenJob {
@@ -1213,7 +1298,6 @@ struct GenJob {
   int launched = 0;
   int phase = 0;          // 0 idle, 1 running, 2 finishing
   int batch = -1;
-  Progress progress;
 };
 
 static int gen_validate(const ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_gen_params* p, const int64_t* d_out,
@@ -1241,9 +1325,7 @@ static int gen_validate(const ttx_session* s, const int64_t* d_src, int B, int L
 static int gen_start(GenJob& j, ttx_session* s, hipStream_t st, const int64_t* d_src, int B, int Ls, const ttx_gen_params* p,
                      int64_t* d_out, ttx_gen_stats* stats, bool greedy, int16_t* d_traj = nullptr, int32_t* d_fin = nullptr,
                      int per_src = 1) {
-  const ttx_model* m = s->m;
-  const ttx_config& c = m->cfg;
-  const int d = c.embedding_dim, Ld = c.num_decoder_layers, V = c.vocab_size;
+  const int d = s->m->cfg.embedding_dim, Ld = s->m->cfg.num_decoder_layers;
   const int N = greedy ? 1 : p->n_drafts, D = greedy ? 0 : p->draft_len, D1 = D + 1;
   const int max_len = p->max_len;
   j.s = s; j.st = st; j.greedy = greedy; j.d_out = d_out; j.stats = stats; j.launched = 0;
@@ -1258,31 +1340,16 @@ static int gen_start(GenJob& j, ttx_session* s, hipStream_t st, const int64_t* d
   const size_t Mmax = (size_t)B * step_rps(N, D);
   const int Bs = B / per_src;      // sources
 
-  TTX_TRY(ensure(s->tok_src, (size_t)Bs * Ls * 4, st));
-  TTX_TRY(ensure(s->src_valid, (size_t)Bs * Ls, st));
-  TTX_TRY(ensure(s->memory, (size_t)Bs * Ls * d * 4, st));
-  TTX_TRY(ensure(s->memkv, (size_t)Bs * Ls * Ld * 2 * d * 4, st));
-  TTX_TRY(ensure(s->drafts, (size_t)B * N * std::max(D, 1) * 4, st));
-  TTX_TRY(ensure(s->gen, (size_t)B * g.k.gen_ld * 4, st));
-  TTX_TRY(ensure(s->front, (size_t)B * 4, st));
-  TTX_TRY(ensure(s->act_idx, (size_t)B * 4, st));
-  TTX_TRY(ensure(s->haspad, (size_t)B * 4, st));
-  if (row_rule) {
-    TTX_TRY(ensure(s->traj, (size_t)B * (max_len + 1) * 2, st));
-    TTX_TRY(ensure(s->fin_step, (size_t)B * 4, st));
-  }
-  TTX_TRY(ensure(s->rec, (size_t)B * sizeof(CopyRec), st));
-  TTX_TRY(ensure(s->pred, Mmax * 4, st));
-  TTX_TRY(ensure(s->state, sizeof(DecState), st));
-  TTX_TRY(ensure(s->logits, Mmax * V * 4, st));
-  TTX_TRY(ensure(s->outbuf, (size_t)B * max_len * 8, st));
-  TTX_TRY(ensure(s->kcache, (size_t)Ld * B * g.k.Lc * d * 4, st));
-  TTX_TRY(ensure(s->vcache, (size_t)Ld * B * g.k.Lc * d * 4, st));
-  // the encoder and the step share the activation buffers; size them for the larger of the two
-  const size_t Macts = std::max(Mmax, (size_t)Bs * Ls);
-  TTX_TRY(ensure_acts(s, st, Macts, 1));
-  TTX_TRY(ensure(s->qkv, std::max((size_t)Ld * Mmax, (size_t)Bs * Ls) * 3 * d * 4, st));
-  TTX_TRY(ensure(s->slab, sizeof(float) * 16 * Macts * d, st));   // no allocation may happen inside a graph capture
+  Needs need{st};
+  need(s->tok_src, (size_t)Bs * Ls * 4); need(s->src_valid, (size_t)Bs * Ls); need(s->memory, (size_t)Bs * Ls * d * 4);
+  need(s->memkv, (size_t)Bs * Ls * Ld * 2 * d * 4);
+  need(s->drafts, (size_t)B * N * std::max(D, 1) * 4);
+  need(s->gen, (size_t)B * g.k.gen_ld * 4); need(s->front, (size_t)B * 4); need(s->act_idx, (size_t)B * 4); need(s->haspad, (size_t)B * 4);
+  if (row_rule) { need(s->traj, (size_t)B * (max_len + 1) * 2); need(s->fin_step, (size_t)B * 4); }
+  need(s->rec, (size_t)B * sizeof(CopyRec)); need(s->outbuf, (size_t)B * max_len * 8);
+  need(s->kcache, (size_t)Ld * B * g.k.Lc * d * 4); need(s->vcache, (size_t)Ld * B * g.k.Lc * d * 4);
+  need_step_workspaces(s, need, Mmax, (size_t)Bs * Ls);
+  TTX_TRY(need.rc);
   AcceptBlk* blk = nullptr;
   if (!greedy) TTX_TRY(accept_blk_for(s, st, B, &blk));
   s->graphs_current();                                            // captured pointers may be stale
@@ -1290,32 +1357,16 @@ static int gen_start(GenJob& j, ttx_session* s, hipStream_t st, const int64_t* d
   s->ev_used = 0;
   HIP_TRY(hipEventRecord(s->ev_a, st));
   // encoder once per batch (:60-61) + cross-attention K/V of every decoder layer once per source
-  TTX_TRY(prepare_tokens(st, d_src, s->tok_src.as<int>(), s->src_valid.as<uint8_t>(), Bs * Ls, c.pad_token));
-  TTX_TRY(run_encoder(s, st, s->tok_src.as<int>(), s->src_valid.as<uint8_t>(), Bs, Ls, s->memory.as<float>()));
-  const int gv = variant_for_rows(s, (long long)Bs * Ls, false);
-  TTX_TRY(launch_gemm(s, st, s->memory.as<float>(), d, m->p(m->cross_kv_w), d, m->p(m->cross_kv_b), s->memkv.as<float>(),
-                      Ld * 2 * d, nullptr, Bs * Ls, Ld * 2 * d, d, false, 0, 0, gv));
+  TTX_TRY(encode_sources(s, st, d_src, 0, Bs, Ls, s->src_valid.as<uint8_t>(), s->memkv.as<float>()));
   // drafts from src[:, 1:] (:64-73): min_draft_len 1, max_draft_len max_len
   if (!greedy)
     TTX_TRY(launch_make_drafts<int>(st, s->tok_src.as<int>(), Ls, 1, B, Ls - 1, N, D, p->eos_token, p->pad_token,
                                     p->replace_token, s->drafts.as<int>()));
 
-  g.la.st = s->state.as<DecState>(); g.la.act_idx = s->act_idx.as<int>(); g.la.front = s->front.as<int>();
-  g.la.gen = s->gen.as<int>(); g.la.gen_ld = g.k.gen_ld; g.la.drafts = s->drafts.as<int>(); g.la.pred = s->pred.as<int>();
-  g.la.rec = s->rec.as<CopyRec>(); g.la.out = s->outbuf.as<int64_t>(); g.la.haspad = s->haspad.as<int>();
-  HostInfo* dev_info = nullptr;
-  HIP_TRY(hipHostGetDevicePointer((void**)&dev_info, (void*)s->host_info, 0));
-  g.la.host = dev_info;
-  g.la.B = B; g.la.N = N; g.la.D = D; g.la.Ls = Ls; g.la.max_len = max_len; g.la.pad = p->pad_token; g.la.bos = p->bos_token;
-  g.la.eos = p->eos_token;
-  g.la.row_rule = row_rule ? 1 : 0; g.la.traj = row_rule ? s->traj.as<short>() : nullptr; g.la.traj_ld = max_len + 1;
+  TTX_TRY(fill_loop_args(s, g, blk));
+  g.la.out = s->outbuf.as<int64_t>();
+  g.la.row_rule = row_rule ? 1 : 0; g.la.traj = row_rule ? s->traj.as<short>() : nullptr;
   g.la.fin_step = row_rule ? s->fin_step.as<int>() : nullptr;
-  g.la.blk = blk;
-  g.kc.st = s->state.as<DecState>(); g.kc.rec = s->rec.as<CopyRec>(); g.kc.qkv = s->qkv.as<float>();
-  g.kc.qkv_layer_stride = (long long)Mmax * 3 * d;
-  g.kc.kcache = s->kcache.as<float>(); g.kc.vcache = s->vcache.as<float>();
-  g.kc.cache_seq_stride = (long long)g.k.Lc * d; g.kc.cache_layer_stride = (long long)B * g.k.Lc * d;
-  g.kc.N = N; g.kc.D = D; g.kc.d = d;
 
   s->host_info->stop = 0;
   s->host_info->steps_done = 0;
@@ -1519,12 +1570,7 @@ static int generate_common(ttx_session* s, const int64_t* d_src, int B, int Ls, 
   while (!hi->stop) {
     if (j.launched > p->max_len + 2) return fail(TTX_ERR_HIP, "decode loop failed to terminate");
     TTX_TRY(gen_launch_step(j, hi->width + D1));
-    const int want = j.launched;
-    Progress wait;
-    while (hi->steps_done < want && !hi->stop) {
-      if (wait.stalled()) return session_hung(s);
-      __builtin_ia32_pause();
-    }
+    if (!wait_published(watchdog_seconds(), [&] { return hi->steps_done >= j.launched || hi->stop; })) return session_hung(s);
   }
   TTX_TRY(gen_finish_enqueue(j));
   HIP_TRY(hipStreamSynchronize(st));
@@ -1581,39 +1627,6 @@ extern "C" int ttx_sample_generate(ttx_session* s, const int64_t* d_src, int B, 
   return rc;
 }
 
-// Length buckets inside an admission.  An admission is encoded at the width of its longest row, so a chunk of 1 024 length-sorted
-// rows pads its short rows to the longest one: in the encoder, in the cross K/V, and, through src_len, in every cross-attention
-// launch of the rows' slots.  Its rows are therefore admitted in consecutive sub-chunks, each at its own width (its longest row,
-// at least 2).  A sub-chunk closes once rows x width reaches `budget` padded rows: the GEMM tiles run at their large-launch rates
-// from about 16 000 rows, so a shorter launch would give back what the padding saves.  A last sub-chunk of fewer
-// than budget / 2 padded rows joins the one before it; an admission below the budget stays one chunk.  budget 0: one chunk.
-// `ends` receives the end (exclusive, relative to `len`) of every sub-chunk.
-constexpr long long ADMIT_ROWS = 16384;
-static int chunk_width(const int32_t* len, int first, int end) {
-  int w = 2;
-  for (int r = first; r < end; ++r) w = std::max(w, (int)len[r]);
-  return w;
-}
-static void admit_chunks(const int32_t* len, int n, long long budget, std::vector<int>& ends) {
-  ends.clear();
-  if (budget > 0 && (long long)n * chunk_width(len, 0, n) >= budget) {
-    int first = 0, w = 2;
-    for (int r = 0; r < n; ++r) {
-      w = std::max(w, (int)len[r]);
-      if ((long long)(r + 1 - first) * w >= budget) { ends.push_back(r + 1); first = r + 1; w = 2; }
-    }
-    if (first < n) {
-      const bool merge = !ends.empty() && (long long)(n - first) * chunk_width(len, first, n) * 2 < budget;
-      if (merge) ends.back() = n; else ends.push_back(n);
-    }
-  } else {
-    ends.push_back(n);
-  }
-}
-
-// Several batches in flight on one GPU: batch i is decoded on session i % n_sessions, each
-// session on its own stream; one host thread round-robins over the sessions, enqueueing the next verify step of
-// whichever session has published its previous one.  Outputs per batch are identical to the one-at-a-time call.
 // ------------------------------------------------------------------------------------------------
 // Slot pool: continuous batching under the per-row rule.  A session owns `C` slots; whenever enough of them are free
 // the next rows of the (length-sorted) work list are encoded and admitted, so the verify step keeps close to
@@ -1629,7 +1642,6 @@ struct PoolJob {
   int admits = 0;
   int quota_end = -1;       // serial (profiling) pass: end of this pool's share of the work list
   PoolIo io{};
-  Progress progress;
   long long admitted_rows = 0, src_tokens_padded = 0;
   long long admit_rows = 0; // TTX_ADMIT_ROWS: padded encoder rows at which a sub-chunk of an admission closes; 0: one chunk per admission
   // two-phase verify step (DESIGN.md "Two-phase verify step"): a free choice per step, both forms give the same bits
@@ -1649,9 +1661,8 @@ struct PoolJob {
 
 static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_cap, const ttx_gen_params* p, int64_t* d_out,
                       int16_t* d_traj, int32_t* d_fin) {
-  const ttx_model* m = s->m;
-  const ttx_config& c = m->cfg;
-  const int d = c.embedding_dim, Ld = c.num_decoder_layers, V = c.vocab_size;
+  const ttx_config& c = s->m->cfg;
+  const int d = c.embedding_dim, Ld = c.num_decoder_layers;
   const int N = p->n_drafts, D = p->draft_len, D1 = D + 1, max_len = p->max_len;
   j.s = s; j.st = st; j.C = C; j.Ls_cap = Ls_cap; j.launched = 0; j.admits = 0; j.admitted_rows = 0; j.src_tokens_padded = 0;
   s->snap_step = 0;
@@ -1662,27 +1673,15 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
   g.k.gen_ld = max_len + D + 2;
   const size_t Mmax = (size_t)C * step_rps(N, D);
   const size_t kv_row = (size_t)Ld * 2 * d;
-  TTX_TRY(ensure(s->tok_src, (size_t)C * Ls_cap * 4, st));
-  TTX_TRY(ensure(s->valid_new, (size_t)C * Ls_cap, st));
-  TTX_TRY(ensure(s->src_valid, (size_t)C * Ls_cap, st));
-  TTX_TRY(ensure(s->memory, (size_t)C * Ls_cap * d * 4, st));
-  TTX_TRY(ensure(s->memkv_new, (size_t)C * Ls_cap * kv_row * 4, st));
-  TTX_TRY(ensure(s->memkv, (size_t)C * Ls_cap * kv_row * 4, st));
-  TTX_TRY(ensure(s->drafts, (size_t)C * N * D * 4, st));
-  TTX_TRY(ensure(s->drafts_new, (size_t)C * N * D * 4, st));
-  TTX_TRY(ensure(s->gen, (size_t)C * g.k.gen_ld * 4, st));
-  for (Buf* b : {&s->front, &s->act_idx, &s->haspad, &s->rstep, &s->row_of, &s->src_len, &s->new_slot}) TTX_TRY(ensure(*b, (size_t)C * 4, st));
-  TTX_TRY(ensure(s->rec, (size_t)C * sizeof(CopyRec), st));
-  TTX_TRY(ensure(s->pred, Mmax * 4, st));
-  TTX_TRY(ensure(s->state, sizeof(DecState), st));
-  TTX_TRY(ensure(s->pool_io, sizeof(PoolIo), st));
-  TTX_TRY(ensure(s->logits, Mmax * V * 4, st));
-  TTX_TRY(ensure(s->kcache, (size_t)Ld * C * g.k.Lc * d * 4, st));
-  TTX_TRY(ensure(s->vcache, (size_t)Ld * C * g.k.Lc * d * 4, st));
-  const size_t Macts = std::max(Mmax, (size_t)C * Ls_cap);
-  TTX_TRY(ensure_acts(s, st, Macts, 1));
-  TTX_TRY(ensure(s->qkv, std::max((size_t)Ld * Mmax, (size_t)C * Ls_cap) * 3 * d * 4, st));
-  TTX_TRY(ensure(s->slab, sizeof(float) * 16 * Macts * d, st));
+  Needs need{st};
+  need(s->tok_src, (size_t)C * Ls_cap * 4); need(s->valid_new, (size_t)C * Ls_cap); need(s->src_valid, (size_t)C * Ls_cap);
+  need(s->memory, (size_t)C * Ls_cap * d * 4); need(s->memkv_new, (size_t)C * Ls_cap * kv_row * 4); need(s->memkv, (size_t)C * Ls_cap * kv_row * 4);
+  need(s->drafts, (size_t)C * N * D * 4); need(s->drafts_new, (size_t)C * N * D * 4);
+  need(s->gen, (size_t)C * g.k.gen_ld * 4);
+  for (Buf* b : {&s->front, &s->act_idx, &s->haspad, &s->rstep, &s->row_of, &s->src_len, &s->new_slot}) need(*b, (size_t)C * 4);
+  need(s->rec, (size_t)C * sizeof(CopyRec)); need(s->pool_io, sizeof(PoolIo));
+  need(s->kcache, (size_t)Ld * C * g.k.Lc * d * 4); need(s->vcache, (size_t)Ld * C * g.k.Lc * d * 4);
+  need_step_workspaces(s, need, Mmax, (size_t)C * Ls_cap);
   // read at the start of every pool call
   j.two_phase = true; j.min_rows = 800; j.probes = 0; j.probe_pending = false;
   j.slot_steps = j.matched_slot_steps = j.split_steps = j.skipped_draft_passes = 0;
@@ -1696,15 +1695,15 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
   j.draft_select = j.two_phase && d == c.num_heads * ATT_DH && c.num_heads % 4 == 0 && !s->attn_fallback && N <= 32 && D >= 1;
   if (const char* e = getenv("TTX_DRAFT_SELECT")) j.draft_select = j.draft_select && atoi(e) != 0;
   if (j.draft_select) {
-    for (Buf* b : {&s->draft_mask, &s->row_base}) TTX_TRY(ensure(*b, (size_t)C * 4, st));
-    TTX_TRY(ensure(s->row_map, Mmax * 4, st));
+    for (Buf* b : {&s->draft_mask, &s->row_base}) need(*b, (size_t)C * 4);
+    need(s->row_map, Mmax * 4);
   }
   if (j.two_phase) {                                              // nothing may allocate inside a capture
-    TTX_TRY(ensure(s->qkv_probe, (size_t)Ld * C * 3 * d * 4, st));
-    for (Buf* b : {&s->pred_probe, &s->act2, &s->pos2}) TTX_TRY(ensure(*b, (size_t)C * 4, st));
-    TTX_TRY(ensure(s->pred_draft, Mmax * 4, st));
-    TTX_TRY(ensure(s->state2, 3 * sizeof(DecState), st));
+    need(s->qkv_probe, (size_t)Ld * C * 3 * d * 4);
+    for (Buf* b : {&s->pred_probe, &s->act2, &s->pos2}) need(*b, (size_t)C * 4);
+    need(s->pred_draft, Mmax * 4); need(s->state2, 3 * sizeof(DecState));
   }
+  TTX_TRY(need.rc);
   AcceptBlk* blk = nullptr;
   TTX_TRY(accept_blk_for(s, st, C, &blk));
   s->graphs_current();
@@ -1718,23 +1717,10 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
   }
   j.io = PoolIo{d_out, d_traj, d_fin, max_len + 1, 0};        // lives in the job until every stream has drained
   HIP_TRY(hipMemcpyAsync(s->pool_io.p, &j.io, sizeof(j.io), hipMemcpyHostToDevice, st));
-  g.la.st = s->state.as<DecState>(); g.la.act_idx = s->act_idx.as<int>(); g.la.front = s->front.as<int>();
-  g.la.gen = s->gen.as<int>(); g.la.gen_ld = g.k.gen_ld; g.la.drafts = s->drafts.as<int>(); g.la.pred = s->pred.as<int>();
-  g.la.rec = s->rec.as<CopyRec>(); g.la.out = nullptr; g.la.haspad = s->haspad.as<int>();
-  HostInfo* dev_info = nullptr;
-  HIP_TRY(hipHostGetDevicePointer((void**)&dev_info, (void*)s->host_info, 0));
-  g.la.host = dev_info;
-  g.la.B = C; g.la.N = N; g.la.D = D; g.la.Ls = Ls_cap; g.la.max_len = max_len; g.la.pad = p->pad_token; g.la.bos = p->bos_token;
-  g.la.eos = p->eos_token;
-  g.la.row_rule = 1; g.la.traj = nullptr; g.la.traj_ld = max_len + 1; g.la.fin_step = nullptr;
+  TTX_TRY(fill_loop_args(s, g, blk));
+  g.la.row_rule = 1;
   g.la.pool = 1; g.la.rstep = s->rstep.as<int>(); g.la.row_of = s->row_of.as<int>(); g.la.io = s->pool_io.as<PoolIo>();
-  g.la.blk = blk;
   g.k.src_len = s->src_len.as<int>();
-  g.kc.st = s->state.as<DecState>(); g.kc.rec = s->rec.as<CopyRec>(); g.kc.qkv = s->qkv.as<float>();
-  g.kc.qkv_layer_stride = (long long)Mmax * 3 * d;
-  g.kc.kcache = s->kcache.as<float>(); g.kc.vcache = s->vcache.as<float>();
-  g.kc.cache_seq_stride = (long long)g.k.Lc * d; g.kc.cache_layer_stride = (long long)C * g.k.Lc * d;
-  g.kc.N = N; g.kc.D = D; g.kc.d = d;
   j.g2 = g;
   if (j.two_phase) {
     j.g2.la.exec_rows = reinterpret_cast<const int*>(s->state2.as<DecState>() + 2);
@@ -1754,18 +1740,9 @@ static int pool_admit(PoolJob& j, const int64_t* d_src_rows, int ld_src, int R, 
                       int16_t* d_traj, int32_t* d_fin) {
   ttx_session* s = j.s;
   hipStream_t st = j.st;
-  const ttx_model* m = s->m;
-  const ttx_config& c = m->cfg;
   const StepCtx& k = j.g.k;
-  const int d = c.embedding_dim, Ld = c.num_decoder_layers;
-  const int kv_row = Ld * 2 * d;
-  hipLaunchKernelGGL(k_prepare_tokens_2d, dim3(cdiv(R * Ls_new, 256)), dim3(256), 0, st, d_src_rows, ld_src, s->tok_src.as<int>(),
-                     s->valid_new.as<uint8_t>(), R, Ls_new, c.pad_token);
-  HIP_TRY(hipGetLastError());
-  TTX_TRY(run_encoder(s, st, s->tok_src.as<int>(), s->valid_new.as<uint8_t>(), R, Ls_new, s->memory.as<float>()));
-  const int gv = variant_for_rows(s, (long long)R * Ls_new, false);
-  TTX_TRY(launch_gemm(s, st, s->memory.as<float>(), d, m->p(m->cross_kv_w), d, m->p(m->cross_kv_b), s->memkv_new.as<float>(),
-                      kv_row, nullptr, R * Ls_new, kv_row, d, false, 0, 0, gv));
+  const int kv_row = s->m->cfg.num_decoder_layers * 2 * s->m->cfg.embedding_dim;
+  TTX_TRY(encode_sources(s, st, d_src_rows, ld_src, R, Ls_new, s->valid_new.as<uint8_t>(), s->memkv_new.as<float>()));
   TTX_TRY(launch_make_drafts<int>(st, s->tok_src.as<int>(), Ls_new, 1, R, Ls_new - 1, k.N, k.D, k.p.eos_token, k.p.pad_token,
                                   k.p.replace_token, s->drafts_new.as<int>()));
   PoolAdmitArgs a{};
@@ -1884,166 +1861,100 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
   int len_max = 0;
   for (int i = 0; i < R_total; ++i) len_max = std::max(len_max, (int)h_len[i]);
   if (len_max > Ls_all) return fail(TTX_ERR_INVALID, "row length beyond the source matrix width");
-  // slot width: 192 positions, beyond that in steps of 64 — calls whose longest sources differ share workspaces and
-  // the captured step graph (a slot's keys are bounded by its own source length, so the padding costs memory only:
-  // 0.8 GB of cross K/V per 512-slot pool at 192)
-  int Ls_cap = std::min(std::max(192, ((len_max + 63) / 64) * 64), sessions[0]->m->cfg.max_positions);
-  Ls_cap = std::max(Ls_cap, std::max(2, len_max));
+  const int Ls_cap = pool_slot_width(len_max, sessions[0]->m->cfg.max_positions);
   TTX_TRY(gen_validate(sessions[0], d_src, capacity, Ls_cap, p, d_out, false));
-  HIP_TRY(hipSetDevice(sessions[0]->m->device));
-  release_retired();
-  for (int i = 0; i < n_sessions; ++i) TTX_TRY(session_alive(sessions[i]));
-  EventGuard ready_guard;
-  HIP_TRY(hipEventCreateWithFlags(&ready_guard.e, hipEventDisableTiming));
-  hipEvent_t ready = ready_guard.e;
-  HIP_TRY(hipEventRecord(ready, (hipStream_t)stream));
-  bool hung = false;
-  const int n_jobs = std::min(n_sessions, cdiv(R_total, std::max(1, std::min(capacity / 2, 32))));   // short lists: several small pools
-  const int C = std::min(capacity, std::max(1, cdiv(R_total, n_jobs)));      // never more slots than a fair share of the rows
+  const PoolShape shape = pool_shape(n_sessions, R_total, R_total, capacity, 32, 1);      // the work list: rows, i.e. unit batches
+  const int n_jobs = shape.n_jobs, C = shape.C;
+  std::vector<int> first(R_total + 1);
+  for (int r = 0; r <= R_total; ++r) first[r] = r;
   std::vector<PoolJob> jobs(n_jobs);
   std::vector<int> chunk_ends;
-  int rc_final = TTX_OK;
   std::fill(std::begin(sessions[0]->pool_counters), std::end(sessions[0]->pool_counters), 0LL);
-  for (int i = 0; i < n_jobs && rc_final == TTX_OK; ++i) {
-    ttx_session* s = sessions[i];
-    TTX_TRY(ensure_own_stream(s));
-    HIP_TRY(hipStreamWaitEvent(s->own_stream, ready, 0));
-    rc_final = pool_start(jobs[i], s, s->own_stream, C, Ls_cap, p, d_out, d_traj, d_fin_step);
-  }
-  // every pool of a call has the same model and reads the same environment: the mode is the call's
-  sessions[0]->pool_counters[6] = jobs[0].draft_select ? 1 : 0;
-  const int min_admit = std::max(1, C / 4);                    // admissions of at least a quarter pool (or into an empty one)
+  // profiling sessions (bench.py's roofline pass): the pools run ONE AFTER ANOTHER, so that the event pair around a GEMM launch
+  // measures that launch and not the kernels of three other pools sharing the device with it
   const bool serial = sessions[0]->profile;
-  int cursor = 0, done = 0;
-  while (done < n_jobs && rc_final == TTX_OK) {
-    bool progressed = false;
-    // profiling sessions (bench.py's roofline pass): the pools run ONE AFTER ANOTHER, so that the event pair around a GEMM launch
-    // measures that launch and not the kernels of three other pools sharing the device with it
-    int only = -1;
-    if (serial)
-      for (int i = n_jobs - 1; i >= 0; --i)
-        if (jobs[i].phase != 3) only = i;
-    for (int i = 0; i < n_jobs && rc_final == TTX_OK; ++i) {
-      if (serial && i != only) continue;
-      PoolJob& j = jobs[i];
-      ttx_session* s = j.s;
-      volatile HostInfo* hi = s->host_info;
-      if (j.phase == 1) {
-        if (j.probe_pending) {                                                // the same rules as for steps_done below
-          if (((volatile ProbeInfo*)s->probe_info)->probes_done < j.probes) {
-            if (j.progress.stalled()) {
-              rc_final = session_hung(s);
-              hung = true;
-              break;
-            }
-            continue;
-          }
-          j.progress.advanced();
-          rc_final = pool_launch_drafts(j);
-          progressed = true;
-          continue;
-        }
-        if (j.launched > 0 && hi->steps_done < j.launched) {                  // the step in flight has not published yet
-          if (j.progress.stalled()) {                                         // never spin forever
-            rc_final = session_hung(s);
-            hung = true;
-            break;
-          }
-          continue;
-        }
-        j.progress.advanced();
-        int n_act = (j.launched == 0) ? 0 : hi->n_active;
-        const int free_slots = C - n_act;
-        // serial pass: every pool decodes an equal contiguous share of the rest of the list (what it takes at once when the list
-        // fits the pools; otherwise its own continuous batching over that share, one tail per pool as in the concurrent run)
-        if (serial && j.quota_end < 0) j.quota_end = cursor + cdiv(R_total - cursor, n_jobs - i);
-        const int list_end = serial ? j.quota_end : R_total;
-        if (cursor < list_end && (n_act == 0 || free_slots >= min_admit)) {
-          // the last rows of the list are shared out over the pools still running, so that they drain together
-          // instead of one pool swallowing the rest and finishing alone
-          int n_running = 0;
-          for (const PoolJob& o : jobs) n_running += (o.phase == 1);
-          const int remaining = list_end - cursor;
-          int share = std::max(1, cdiv(remaining, std::max(1, serial ? 1 : n_running)));
-          // first fill of a list that fits the pools at once: an equal share for every pool not yet started (the pools
-          // before this one have taken theirs), so that nothing is left waiting for a later admission
-          if (!serial && j.launched == 0 && (long long)n_jobs * C >= R_total) share = std::max(1, cdiv(remaining, n_jobs - i));
-          const int take = std::min({free_slots, remaining, share});
-          // every sub-chunk at the width of its own longest row; the staging buffers are the stream's, one sub-chunk after another
-          admit_chunks(h_len + cursor, take, j.admit_rows, chunk_ends);
-          int r0 = cursor;
-          for (const int end : chunk_ends) {
-            const int r1 = cursor + end;
-            rc_final = pool_admit(j, d_src + (size_t)r0 * Ls_all, Ls_all, r1 - r0, chunk_width(h_len, r0, r1), r0, d_out, d_traj, d_fin_step);
-            if (rc_final != TTX_OK) break;
-            r0 = r1;
-          }
-          if (rc_final != TTX_OK) break;
-          cursor += take;
-          n_act += take;
-        }
-        if (n_act == 0) {
-          if (hipEventRecord(s->ev_c, j.st) != hipSuccess ||
-              hipMemcpyAsync(s->host_state, s->state.as<DecState>(), sizeof(DecState), hipMemcpyDeviceToHost, j.st) != hipSuccess ||
-              hipEventRecord(s->ev_done, j.st) != hipSuccess) {
-            rc_final = fail(TTX_ERR_HIP, "slot pool: enqueueing the final state read-back failed");
-            break;
-          }
-          j.phase = 2;
-        } else {
-          if (j.launched > (long long)(p->max_len + 2) * (R_total + 1)) { rc_final = fail(TTX_ERR_HIP, "decode loop failed to terminate"); break; }
-          rc_final = pool_launch_step(j, n_act);
-        }
-        progressed = true;
-      } else if (j.phase == 2) {
-        if (hipEventQuery(s->ev_done) == hipSuccess) {
-          const DecState& hs = *s->host_state;
-          if (stats) {
-            stats->model_calls += hs.steps;
-            stats->accepted_tokens += hs.accepted;
-            stats->produced_tokens += hs.produced;
-            stats->verified_positions += hs.verified_positions;
-            stats->kv_prefix_positions += hs.kv_prefix_positions;
-            stats->src_positions += hs.src_positions;
-            stats->src_tokens_padded += j.src_tokens_padded;
-            collect_gemm_profile(s, j.st);
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, s->ev_a, s->ev_c) == hipSuccess) stats->decode_ms += ms;
-          }
-          if (getenv("TTX_TWO_PHASE_STATS"))
-            fprintf(stderr, "[ttx two-phase] pool %d: %d steps, %lld split (%lld without a draft pass), %lld slot-steps probed, %lld matched, "
-                            "%lld draft rows executed, %lld drafts matched\n",      // draft select off: N drafts per matching slot
-                    i, j.launched, j.split_steps, j.skipped_draft_passes, j.slot_steps, j.matched_slot_steps,
-                    j.rows_executed - j.slot_steps - j.unsplit_rows, j.drafts_matched);
-          {
-            long long* pc = sessions[0]->pool_counters;
-            pc[0] += j.launched; pc[1] += j.split_steps; pc[2] += j.slot_steps; pc[3] += j.matched_slot_steps;
-            pc[4] += j.drafts_matched; pc[5] += j.rows_executed;
-          }
-          if (hs.error == 3 && rc_final == TTX_OK)
-            rc_final = fail(TTX_ERR_ROW_REPLAY, "a row emitted PAD inside its sequence: decode the batches as given");
-          else if (hs.error && rc_final == TTX_OK)
-            rc_final = fail(TTX_ERR_HIP, "slot pool bookkeeping failed (admitted more rows than free slots)");
-          j.phase = 3;
-          ++done;
-          progressed = true;
-        }
+  int cursor = 0;
+  const auto start = [&](int i) -> int {
+    TTX_TRY(pool_start(jobs[i], sessions[i], sessions[i]->own_stream, C, Ls_cap, p, d_out, d_traj, d_fin_step));
+    // every pool of a call has the same model and reads the same environment: the mode is the call's
+    if (i == 0) sessions[0]->pool_counters[6] = jobs[0].draft_select ? 1 : 0;
+    return TTX_OK;
+  };
+  const auto turn = [&](int i) -> int {
+    PoolJob& j = jobs[i];
+    ttx_session* s = j.s;
+    volatile HostInfo* hi = s->host_info;
+    if (j.phase == 1) {
+      if (j.probe_pending) {
+        if (((volatile ProbeInfo*)s->probe_info)->probes_done < j.probes) return TURN_WAITING;
+        TTX_TRY(pool_launch_drafts(j));
+        return TURN_PROGRESSED;
       }
+      if (j.launched > 0 && hi->steps_done < j.launched) return TURN_WAITING;       // the step in flight has not published yet
+      int n_act = (j.launched == 0) ? 0 : hi->n_active;
+      if (serial && j.quota_end < 0) j.quota_end = serial_quota(first.data(), R_total, cursor, i, n_jobs);
+      int n_running = 0;
+      for (const PoolJob& o : jobs) n_running += (o.phase == 1);
+      const int take = plan_admission(first.data(), R_total, C, {cursor, C - n_act, n_act, j.launched == 0, i, n_jobs, n_running, serial, j.quota_end});
+      if (take > 0) {
+        // every sub-chunk at the width of its own longest row; the staging buffers are the stream's, one sub-chunk after another
+        admit_chunks(h_len + cursor, take, j.admit_rows, chunk_ends);
+        int r0 = cursor;
+        for (const int end : chunk_ends) {
+          const int r1 = cursor + end;
+          TTX_TRY(pool_admit(j, d_src + (size_t)r0 * Ls_all, Ls_all, r1 - r0, chunk_width(h_len, r0, r1), r0, d_out, d_traj, d_fin_step));
+          r0 = r1;
+        }
+        cursor += take;
+        n_act += take;
+      }
+      if (n_act == 0) {
+        if (hipEventRecord(s->ev_c, j.st) != hipSuccess ||
+            hipMemcpyAsync(s->host_state, s->state.as<DecState>(), sizeof(DecState), hipMemcpyDeviceToHost, j.st) != hipSuccess ||
+            hipEventRecord(s->ev_done, j.st) != hipSuccess)
+          return fail(TTX_ERR_HIP, "slot pool: enqueueing the final state read-back failed");
+        j.phase = 2;
+      } else {
+        if (j.launched > (long long)(p->max_len + 2) * (R_total + 1)) return fail(TTX_ERR_HIP, "decode loop failed to terminate");
+        TTX_TRY(pool_launch_step(j, n_act));
+      }
+      return TURN_PROGRESSED;
     }
-    if (!progressed) __builtin_ia32_pause();
-  }
-  if (hung) {
-    // a stream that never published may never drain: do not wait on any of them, and retire every session of this call
-    // (their workspaces may still be written by whatever is stuck)
-    for (int i = 0; i < n_jobs; ++i) jobs[i].s->dead = true;
-  } else {
-    for (int i = 0; i < n_jobs; ++i)
-      if (jobs[i].s && jobs[i].s->own_stream) (void)hipStreamSynchronize(jobs[i].s->own_stream);
-  }
-  if (stats) stats->status = rc_final;
-  return rc_final;
+    if (hipEventQuery(s->ev_done) != hipSuccess) return TURN_IDLE;
+    const DecState& hs = *s->host_state;
+    if (stats) {
+      stats->model_calls += hs.steps;
+      stats->accepted_tokens += hs.accepted;
+      stats->produced_tokens += hs.produced;
+      stats->verified_positions += hs.verified_positions;
+      stats->kv_prefix_positions += hs.kv_prefix_positions;
+      stats->src_positions += hs.src_positions;
+      stats->src_tokens_padded += j.src_tokens_padded;
+      collect_gemm_profile(s, j.st);
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, s->ev_a, s->ev_c) == hipSuccess) stats->decode_ms += ms;
+    }
+    if (getenv("TTX_TWO_PHASE_STATS"))
+      fprintf(stderr, "[ttx two-phase] pool %d: %d steps, %lld split (%lld without a draft pass), %lld slot-steps probed, %lld matched, "
+                      "%lld draft rows executed, %lld drafts matched\n",      // draft select off: N drafts per matching slot
+              i, j.launched, j.split_steps, j.skipped_draft_passes, j.slot_steps, j.matched_slot_steps,
+              j.rows_executed - j.slot_steps - j.unsplit_rows, j.drafts_matched);
+    long long* pc = sessions[0]->pool_counters;
+    pc[0] += j.launched; pc[1] += j.split_steps; pc[2] += j.slot_steps; pc[3] += j.matched_slot_steps;
+    pc[4] += j.drafts_matched; pc[5] += j.rows_executed;
+    j.phase = 3;
+    if (hs.error == 3) return fail(TTX_ERR_ROW_REPLAY, "a row emitted PAD inside its sequence: decode the batches as given");
+    if (hs.error) return fail(TTX_ERR_HIP, "slot pool bookkeeping failed (admitted more rows than free slots)");
+    return TURN_FINISHED;
+  };
+  const int rc = drive_sessions(sessions, n_jobs, serial, stream, start, turn);
+  if (stats) stats->status = rc;
+  return rc;
 }
 
+// Several batches in flight on one GPU: each session, on its own stream, decodes the next batch of the list
+// whenever it has finished one; a turn enqueues the next verify step of a session that has published its previous one.
+// Outputs per batch are identical to the one-at-a-time call.
 static int generate_many_impl(ttx_session** sessions, int n_sessions, int n_batches, const int64_t* const* d_src, const int* B,
                               const int* Ls, const ttx_gen_params* p, int64_t* const* d_out, int16_t* const* d_traj,
                               int32_t* const* d_fin, ttx_gen_stats* stats, void* stream) {
@@ -2054,76 +1965,38 @@ static int generate_many_impl(ttx_session** sessions, int n_sessions, int n_batc
       if (!d_traj[i] || !d_fin || !d_fin[i]) return fail(TTX_ERR_INVALID, "missing trace buffer for a batch");
   for (int i = 0; i < n_batches; ++i) TTX_TRY(gen_validate(sessions[0], d_src[i], B[i], Ls[i], p, d_out[i], false));
   if (sessions[0]->profile) n_sessions = 1;      // profiling: one batch at a time, so that an event pair times its own launch
-  HIP_TRY(hipSetDevice(sessions[0]->m->device));
-  release_retired();
-  hipStream_t caller = (hipStream_t)stream;
-  // inputs were produced on the caller's stream: every session stream waits for it once
-  for (int i = 0; i < n_sessions; ++i) TTX_TRY(session_alive(sessions[i]));
-  EventGuard ready_guard;
-  HIP_TRY(hipEventCreateWithFlags(&ready_guard.e, hipEventDisableTiming));
-  hipEvent_t ready = ready_guard.e;
-  HIP_TRY(hipEventRecord(ready, caller));
-  bool hung = false;
   std::vector<GenJob> jobs(n_sessions);
-  for (int i = 0; i < n_sessions; ++i) {
-    TTX_TRY(ensure_own_stream(sessions[i]));
-    HIP_TRY(hipStreamWaitEvent(sessions[i]->own_stream, ready, 0));
-  }
   const int D1 = p->draft_len + 1;
-  int next = 0, done = 0, rc_final = TTX_OK;
-  while (done < n_batches) {
-    bool progressed = false;
-    for (int i = 0; i < n_sessions; ++i) {
-      GenJob& j = jobs[i];
-      ttx_session* s = sessions[i];
-      if (j.phase == 0) {
-        if (next < n_batches) {
-          j.batch = next++;
-          int rc = gen_start(j, s, s->own_stream, d_src[j.batch], B[j.batch], Ls[j.batch], p, d_out[j.batch],
-                             stats ? &stats[j.batch] : nullptr, false, d_traj ? d_traj[j.batch] : nullptr,
-                             d_traj ? d_fin[j.batch] : nullptr);
-          if (rc != TTX_OK) { rc_final = rc; done = n_batches; break; }
-          progressed = true;
-        }
-        continue;
-      }
-      volatile HostInfo* hi = s->host_info;
-      if (j.phase == 1) {
-        if (hi->stop) {
-          // stop is published by the accept kernel (or by loop init): nothing further to enqueue
-          if (j.launched == 0 && hipStreamQuery(s->own_stream) != hipSuccess) continue;   // init not yet run
-          int rc = gen_finish_enqueue(j);
-          if (rc != TTX_OK) { rc_final = rc; done = n_batches; break; }
-          progressed = true;
-        } else if (hi->steps_done >= j.launched && (j.launched > 0 || hipStreamQuery(s->own_stream) == hipSuccess)) {
-          if (j.launched > p->max_len + 2) { rc_final = fail(TTX_ERR_HIP, "decode loop failed to terminate"); done = n_batches; break; }
-          int rc = gen_launch_step(j, hi->width + D1);
-          if (rc != TTX_OK) { rc_final = rc; done = n_batches; break; }
-          progressed = true;
-          j.progress.advanced();
-        } else if (j.launched > 0 && j.progress.stalled()) {
-          rc_final = session_hung(s);
-          hung = true;
-          done = n_batches;
-          break;
-        }
-      } else if (j.phase == 2) {
-        if (hipEventQuery(s->ev_done) == hipSuccess) {
-          int rc = gen_finish_collect(j);
-          if (rc != TTX_OK && rc_final == TTX_OK) rc_final = rc;
-          ++done;
-          progressed = true;
-        }
-      }
+  int next = 0, rc_batch = TTX_OK;               // next batch of the list; the first error a batch's own result carried
+  const auto turn = [&](int i) -> int {
+    GenJob& j = jobs[i];
+    ttx_session* s = sessions[i];
+    volatile HostInfo* hi = s->host_info;
+    if (j.phase == 0) {
+      if (next >= n_batches) return TURN_FINISHED;
+      j.batch = next++;
+      TTX_TRY(gen_start(j, s, s->own_stream, d_src[j.batch], B[j.batch], Ls[j.batch], p, d_out[j.batch], stats ? &stats[j.batch] : nullptr,
+                        false, d_traj ? d_traj[j.batch] : nullptr, d_traj ? d_fin[j.batch] : nullptr));
+      return TURN_PROGRESSED;
     }
-    if (!progressed) __builtin_ia32_pause();
-  }
-  if (hung) {
-    for (int i = 0; i < n_sessions; ++i) sessions[i]->dead = true;      // never wait for a stream that may be stuck
-  } else {
-    for (int i = 0; i < n_sessions; ++i) (void)hipStreamSynchronize(sessions[i]->own_stream);
-  }
-  return rc_final;
+    if (j.phase == 1) {
+      // loop init publishes no step: the stream has run it once it is idle; from then on the accept kernel publishes
+      if (j.launched == 0 ? hipStreamQuery(s->own_stream) != hipSuccess : (!hi->stop && hi->steps_done < j.launched)) return TURN_WAITING;
+      if (hi->stop) {                            // set by the accept kernel (or by loop init): nothing further to enqueue
+        TTX_TRY(gen_finish_enqueue(j));
+        return TURN_PROGRESSED;
+      }
+      if (j.launched > p->max_len + 2) return fail(TTX_ERR_HIP, "decode loop failed to terminate");
+      TTX_TRY(gen_launch_step(j, hi->width + D1));
+      return TURN_PROGRESSED;
+    }
+    if (hipEventQuery(s->ev_done) != hipSuccess) return TURN_IDLE;
+    const int rc = gen_finish_collect(j);        // a batch the reference fails on does not end the other batches
+    if (rc_batch == TTX_OK) rc_batch = rc;
+    return TURN_PROGRESSED;
+  };
+  const int rc = drive_sessions(sessions, n_sessions, false, stream, [](int) { return TTX_OK; }, turn);
+  return rc != TTX_OK ? rc : rc_batch;      // what ended the call (a hang, a failed launch) before what a batch reported
 }
 
 extern "C" int ttx_greedy_speculative_generate_many(ttx_session** sessions, int n_sessions, int n_batches,
@@ -2211,7 +2084,6 @@ struct BeamJob {
   int64_t* d_out = nullptr;
   ttx_beam_stats* stats = nullptr;
   int rc = TTX_OK;
-  Progress progress;
 };
 
 static int beam_validate(const ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_beam_params* p, const int64_t* d_out) {
@@ -2236,7 +2108,7 @@ static int beam_start(BeamJob& j, ttx_session* s, hipStream_t st, const int64_t*
                       int64_t* d_out, ttx_beam_stats* stats) {
   const ttx_model* m = s->m;
   const ttx_config& c = m->cfg;
-  const int d = c.embedding_dim, Ld = c.num_decoder_layers, V = c.vocab_size;
+  const int d = c.embedding_dim, Ld = c.num_decoder_layers;
   j = BeamJob{};
   j.s = s; j.st = st; j.p = *p; j.B = B; j.Ls = Ls; j.K = p->n_best; j.N = p->n_drafts; j.smart = p->smart_drafts_mode != 0;
   j.d_out = d_out; j.stats = stats;
@@ -2251,13 +2123,11 @@ static int beam_start(BeamJob& j, ttx_session* s, hipStream_t st, const int64_t*
   j.Lc = p->max_len + j.D0 + 2;
   const size_t MC = (size_t)j.max_cand;
   const size_t Mmax = MC * step_rps(j.N, j.D0);
-  int rc = TTX_OK;
-  auto need = [&](Buf& b, size_t bytes) { if (rc == TTX_OK) rc = ensure(b, bytes, st); };
+  Needs need{st};
   need(s->tok_src, (size_t)B * Ls * 4); need(s->src_valid, (size_t)B * Ls); need(s->memory, (size_t)B * Ls * d * 4);
   need(s->memkv, (size_t)B * Ls * Ld * 2 * d * 4);
   need(s->drafts, MC * j.N * std::max(j.D0, 1) * 4);
   need(s->gen, MC * j.gen_ld * 4); need(s->front, MC * 4); need(s->act_idx, MC * 4);
-  need(s->pred, Mmax * 4); need(s->state, sizeof(DecState)); need(s->logits, Mmax * V * 4);
   for (int i = 0; i < 2; ++i) { need(s->tk[i], (size_t)Ld * MC * j.Lc * d * 4); need(s->tv[i], (size_t)Ld * MC * j.Lc * d * 4); }
   need(s->t_prev_len, MC * 4); need(s->t_slot_of, MC * 4); need(s->t_src_of, MC * 4);
   need(s->bs_cand_next, MC * j.gen_ld * 8); need(s->bs_len_next, MC * 4); need(s->bs_fin_next, MC); need(s->bs_logp_next, MC * 4);
@@ -2270,12 +2140,9 @@ static int beam_start(BeamJob& j, ttx_session* s, hipStream_t st, const int64_t*
   const size_t dl1 = (size_t)j.D0 + 1;
   need(s->leaf_score, MC * dl1 * j.K * 4); need(s->leaf_tok, MC * dl1 * j.K * 4); need(s->leaf_cnt, MC * dl1 * 4);
   need(s->beam_summary, 8 * 4);
-  const size_t Macts = std::max(Mmax, (size_t)B * Ls);
-  if (rc == TTX_OK) rc = ensure_acts(s, st, Macts, 1);
-  need(s->qkv, std::max((size_t)Ld * Mmax, (size_t)B * Ls) * 3 * d * 4);
-  need(s->slab, sizeof(float) * 16 * Macts * d);
+  need_step_workspaces(s, need, Mmax, (size_t)B * Ls);
   s->graphs_current();
-  TTX_TRY(rc);
+  TTX_TRY(need.rc);
   if ((size_t)j.K * dl1 > 1023 || 2 * (size_t)j.K * dl1 * j.K * 4 > 150 * 1024)
     return fail(TTX_ERR_INVALID, "too many leaves per source for the selection kernel's LDS image");
   if (!s->beam_host) {
@@ -2287,11 +2154,7 @@ static int beam_start(BeamJob& j, ttx_session* s, hipStream_t st, const int64_t*
   s->ev_used = 0;
   HIP_TRY(hipEventRecord(s->ev_a, st));
   // encoder + cross K/V once per source (:439 / :626); drafts (:430) or the draft library (:603-615)
-  TTX_TRY(prepare_tokens(st, d_src, s->tok_src.as<int>(), s->src_valid.as<uint8_t>(), B * Ls, c.pad_token));
-  TTX_TRY(run_encoder(s, st, s->tok_src.as<int>(), s->src_valid.as<uint8_t>(), B, Ls, s->memory.as<float>()));
-  const int gv = variant_for_rows(s, (long long)B * Ls, false);
-  TTX_TRY(launch_gemm(s, st, s->memory.as<float>(), d, m->p(m->cross_kv_w), d, m->p(m->cross_kv_b), s->memkv.as<float>(),
-                      Ld * 2 * d, nullptr, B * Ls, Ld * 2 * d, d, false, 0, 0, gv));
+  TTX_TRY(encode_sources(s, st, d_src, 0, B, Ls, s->src_valid.as<uint8_t>(), s->memkv.as<float>()));
   if (j.smart)
     TTX_TRY(launch_make_drafts<int>(st, s->tok_src.as<int>(), Ls, 0, B, Ls, j.n_lib, j.lib_ld, p->eos_token, p->pad_token,
                                     p->replace_token, s->bs_drafts_src.as<int>()));
@@ -2461,7 +2324,6 @@ static int beam_launch_iter(BeamJob& j) {
   j.cur = cur ^ 1;
   j.prev_dl = j.dl;
   j.any_iteration = true;
-  j.progress.advanced();
   return TTX_OK;
 }
 
@@ -2532,65 +2394,35 @@ extern "C" int ttx_beam_speculative_generate_many(ttx_session** sessions, int n_
                                                   ttx_beam_stats* stats, void* stream) {
   if (!sessions || n_sessions <= 0 || n_batches < 0 || !d_src || !B || !Ls || !p || !d_out || !stats)
     return fail(TTX_ERR_INVALID, "bad argument to ttx_beam_speculative_generate_many");
-  for (int i = 0; i < n_sessions; ++i) { if (!sessions[i]) return fail(TTX_ERR_INVALID, "null session"); TTX_TRY(session_alive(sessions[i])); }
+  for (int i = 0; i < n_sessions; ++i) if (!sessions[i]) return fail(TTX_ERR_INVALID, "null session");
   for (int i = 0; i < n_batches; ++i) TTX_TRY(beam_validate(sessions[0], d_src[i], B[i], Ls[i], p, d_out[i]));
   if (n_batches == 0) return TTX_OK;
-  HIP_TRY(hipSetDevice(sessions[0]->m->device));
-  release_retired();
-  EventGuard ready;
-  HIP_TRY(hipEventCreateWithFlags(&ready.e, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(ready.e, (hipStream_t)stream));
   if (sessions[0]->profile) n_sessions = 1;      // profiling: one batch at a time (see the greedy driver)
   const int n_jobs = std::min(n_sessions, n_batches);
-  for (int i = 0; i < n_jobs; ++i) {
-    TTX_TRY(ensure_own_stream(sessions[i]));
-    HIP_TRY(hipStreamWaitEvent(sessions[i]->own_stream, ready.e, 0));
-  }
   std::vector<BeamJob> jobs(n_jobs);
-  std::vector<int> batch_of(n_jobs, -1);
-  int next = 0, done = 0, rc_final = TTX_OK;
-  bool hung = false;
-  auto fail_all = [&](int rc) { if (rc_final == TTX_OK) rc_final = rc; done = n_batches; };
-  while (done < n_batches) {
-    bool progressed = false;
-    for (int i = 0; i < n_jobs && done < n_batches; ++i) {
-      BeamJob& j = jobs[i];
-      ttx_session* s = sessions[i];
-      if (j.phase == 0 || j.phase == 3) {
-        if (next >= n_batches) continue;
-        const int b = next++;
-        batch_of[i] = b;
-        int rc = beam_start(j, s, s->own_stream, d_src[b], B[b], Ls[b], p, d_out[b], &stats[b]);
-        if (rc == TTX_OK) rc = beam_launch_iter(j);                 // max_len >= 3: the first iteration always runs
-        if (rc != TTX_OK) { fail_all(rc); break; }
-        progressed = true;
-      } else if (j.phase == 1) {
-        if (s->beam_host->steps_done < j.launched) {               // the iteration in flight has not published yet
-          if (j.progress.stalled()) { hung = true; fail_all(session_hung(s)); break; }
-          continue;
-        }
-        int rc = TTX_OK;
-        if (beam_after_iter(j)) rc = beam_launch_iter(j);
-        else rc = beam_finish_enqueue(j);
-        if (rc != TTX_OK) { fail_all(rc); break; }
-        progressed = true;
-      } else if (j.phase == 2) {
-        if (hipEventQuery(s->ev_done) == hipSuccess) {
-          beam_collect(j);
-          if (j.rc != TTX_OK && rc_final == TTX_OK) rc_final = j.rc;
-          ++done;
-          progressed = true;
-        }
-      }
+  int next = 0, rc_batch = TTX_OK;               // as in generate_many_impl
+  const auto turn = [&](int i) -> int {
+    BeamJob& j = jobs[i];
+    ttx_session* s = sessions[i];
+    if (j.phase == 0 || j.phase == 3) {
+      if (next >= n_batches) return TURN_FINISHED;
+      const int b = next++;
+      TTX_TRY(beam_start(j, s, s->own_stream, d_src[b], B[b], Ls[b], p, d_out[b], &stats[b]));
+      TTX_TRY(beam_launch_iter(j));                                 // max_len >= 3: the first iteration always runs
+      return TURN_PROGRESSED;
     }
-    if (!progressed) __builtin_ia32_pause();
-  }
-  if (hung) {
-    for (int i = 0; i < n_jobs; ++i) sessions[i]->dead = true;
-  } else {
-    for (int i = 0; i < n_jobs; ++i) (void)hipStreamSynchronize(sessions[i]->own_stream);
-  }
-  return rc_final;
+    if (j.phase == 1) {
+      if (((volatile BeamHost*)s->beam_host)->steps_done < j.launched) return TURN_WAITING;   // the iteration in flight has not published yet
+      TTX_TRY(beam_after_iter(j) ? beam_launch_iter(j) : beam_finish_enqueue(j));
+      return TURN_PROGRESSED;
+    }
+    if (hipEventQuery(s->ev_done) != hipSuccess) return TURN_IDLE;
+    beam_collect(j);
+    if (rc_batch == TTX_OK) rc_batch = j.rc;
+    return TURN_PROGRESSED;
+  };
+  const int rc = drive_sessions(sessions, n_jobs, false, stream, [](int) { return TTX_OK; }, turn);
+  return rc != TTX_OK ? rc : rc_batch;      // what ended the call (a hang, a failed launch) before what a batch reported
 }
 
 extern "C" int ttx_beam_speculative_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_beam_params* p,
@@ -2622,14 +2454,12 @@ struct BeamPoolJob {
   int admitted_since = 0;           // sources admitted since the last published iteration
   int quota_b = -1;                 // serial (profiling) pass: end (batch index) of this pool's share of the work list
   long long src_tokens_padded = 0, admitted_rows = 0;
-  Progress progress;
 };
 
 static int bpool_start(BeamPoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_cap, const ttx_beam_params* p, const BeamPoolIo& io_host,
                        const int32_t* h_len, const int32_t* h_batch_of, const int32_t* h_given, int R_total, int n_batches) {
-  const ttx_model* m = s->m;
-  const ttx_config& c = m->cfg;
-  const int d = c.embedding_dim, Ld = c.num_decoder_layers, V = c.vocab_size;
+  const ttx_config& c = s->m->cfg;
+  const int d = c.embedding_dim, Ld = c.num_decoder_layers;
   j = BeamPoolJob{};
   j.s = s; j.st = st; j.p = *p; j.C = C; j.K = p->n_best; j.N = p->n_drafts; j.smart = p->smart_drafts_mode != 0; j.Ls_cap = Ls_cap;
   const int Dreq = clamp_draft_len(p->draft_len, 5, 200);
@@ -2641,8 +2471,7 @@ static int bpool_start(BeamPoolJob& j, ttx_session* s, hipStream_t st, int C, in
   const size_t MC = (size_t)j.MC;
   const size_t Mmax = MC * step_rps(j.N, j.D0);
   const size_t kv_row = (size_t)Ld * 2 * d;
-  int rc = TTX_OK;
-  auto need = [&](Buf& b, size_t bytes) { if (rc == TTX_OK) rc = ensure(b, bytes, st); };
+  Needs need{st};
   need(s->tok_src, (size_t)C * Ls_cap * 4); need(s->valid_new, (size_t)C * Ls_cap); need(s->src_valid, (size_t)C * Ls_cap);
   need(s->memory, (size_t)C * Ls_cap * d * 4); need(s->memkv_new, (size_t)C * Ls_cap * kv_row * 4); need(s->memkv, (size_t)C * Ls_cap * kv_row * 4);
   need(s->bp_tok, (size_t)C * Ls_cap * 4);
@@ -2650,7 +2479,6 @@ static int bpool_start(BeamPoolJob& j, ttx_session* s, hipStream_t st, int C, in
   need(s->drafts_new, (size_t)C * j.N * j.D0 * 4); need(s->bs_drafts_src, (size_t)C * j.N * j.D0 * 4);
   need(s->drafts, MC * j.N * j.D0 * 4);
   need(s->gen, MC * j.gen_ld * 4); need(s->front, MC * 4); need(s->act_idx, MC * 4);
-  need(s->pred, Mmax * 4); need(s->state, sizeof(DecState)); need(s->logits, Mmax * V * 4);
   need(s->tk[0], (size_t)Ld * MC * j.Lc * d * 4); need(s->tv[0], (size_t)Ld * MC * j.Lc * d * 4);      // one buffer: candidate -> slot map
   need(s->t_prev_len, MC * 4); need(s->t_slot_of, MC * 4); need(s->t_src_of, MC * 4); need(s->bp_cand_len, MC * 4);
   need(s->bs_cand_next, MC * j.gen_ld * 8); need(s->bs_len_next, MC * 4); need(s->bs_fin_next, MC); need(s->bs_logp_next, MC * 4);
@@ -2667,12 +2495,9 @@ static int bpool_start(BeamPoolJob& j, ttx_session* s, hipStream_t st, int C, in
   need(s->bp_src_acc, (size_t)C * 32);
   need(s->bp_new_slot, (size_t)C * 4);
   need(s->bp_io, sizeof(BeamPoolIo) + ((size_t)R_total * 2 + n_batches) * 4);
-  const size_t Macts = std::max(Mmax, (size_t)C * Ls_cap);
-  if (rc == TTX_OK) rc = ensure_acts(s, st, Macts, 1);
-  need(s->qkv, std::max((size_t)Ld * Mmax, (size_t)C * Ls_cap) * 3 * d * 4);
-  need(s->slab, sizeof(float) * 16 * Macts * d);
+  need_step_workspaces(s, need, Mmax, (size_t)C * Ls_cap);
   s->graphs_current();
-  TTX_TRY(rc);
+  TTX_TRY(need.rc);
   if ((size_t)j.K * dl1 > 1023 || 2 * (size_t)j.K * dl1 * j.K * 4 > 150 * 1024)
     return fail(TTX_ERR_INVALID, "too many leaves per source for the selection kernel's LDS image");
   if (!s->bp_host) {
@@ -2727,17 +2552,8 @@ static int bpool_start(BeamPoolJob& j, ttx_session* s, hipStream_t st, int C, in
 static int bpool_admit(BeamPoolJob& j, const int64_t* d_src_rows, int ld_src, int R, int Ls_new, int first_row) {
   ttx_session* s = j.s;
   hipStream_t st = j.st;
-  const ttx_model* m = s->m;
-  const ttx_config& c = m->cfg;
-  const int d = c.embedding_dim, Ld = c.num_decoder_layers;
-  const int kv_row = Ld * 2 * d;
-  hipLaunchKernelGGL(k_prepare_tokens_2d, dim3(cdiv(R * Ls_new, 256)), dim3(256), 0, st, d_src_rows, ld_src, s->tok_src.as<int>(),
-                     s->valid_new.as<uint8_t>(), R, Ls_new, c.pad_token);
-  HIP_TRY(hipGetLastError());
-  TTX_TRY(run_encoder(s, st, s->tok_src.as<int>(), s->valid_new.as<uint8_t>(), R, Ls_new, s->memory.as<float>(), s->bp_enc_qkv.as<float>()));
-  const int gv = variant_for_rows(s, (long long)R * Ls_new, false);
-  TTX_TRY(launch_gemm(s, st, s->memory.as<float>(), d, m->p(m->cross_kv_w), d, m->p(m->cross_kv_b), s->memkv_new.as<float>(),
-                      kv_row, nullptr, R * Ls_new, kv_row, d, false, 0, 0, gv));
+  const int kv_row = s->m->cfg.num_decoder_layers * 2 * s->m->cfg.embedding_dim;
+  TTX_TRY(encode_sources(s, st, d_src_rows, ld_src, R, Ls_new, s->valid_new.as<uint8_t>(), s->memkv_new.as<float>(), s->bp_enc_qkv.as<float>()));
   if (!j.smart)      // make_drafts(src[:, 1:], draft_len, N, 5, 200) (:430): independent of how far the row is padded
     TTX_TRY(launch_make_drafts<int>(st, s->tok_src.as<int>(), Ls_new, 1, R, Ls_new - 1, j.N, j.D0, j.p.eos_token, j.p.pad_token,
                                     j.p.replace_token, s->drafts_new.as<int>()));
@@ -2794,7 +2610,6 @@ static int bpool_launch_iter(BeamPoolJob& j, int n_running) {
   ++j.launched;
   j.cur ^= 1;
   j.admitted_since = 0;
-  j.progress.advanced();
   return TTX_OK;
 }
 
@@ -2807,7 +2622,7 @@ extern "C" int ttx_beam_speculative_generate_pool(ttx_session** sessions, int n_
       capacity > 1024 || !p || !d_out || !d_trace_len || !d_summary || trace_cap <= 0 || trace_cap > 32000 || !stats)
     return fail(TTX_ERR_INVALID, "bad argument to ttx_beam_speculative_generate_pool");
   if (R_total == 0) return TTX_OK;
-  for (int i = 0; i < n_sessions; ++i) { if (!sessions[i]) return fail(TTX_ERR_INVALID, "null session"); TTX_TRY(session_alive(sessions[i])); }
+  for (int i = 0; i < n_sessions; ++i) if (!sessions[i]) return fail(TTX_ERR_INVALID, "null session");
   // the work list: whole batches, in order; batch b owns the sources [first[b], first[b + 1])
   std::vector<int> first(n_batches + 1, 0);
   int len_max = 2, max_batch = 0;
@@ -2826,133 +2641,75 @@ extern "C" int ttx_beam_speculative_generate_pool(ttx_session** sessions, int n_
   if (R_total > 0 && h_batch_of[R_total - 1] != n_batches - 1) return fail(TTX_ERR_INVALID, "n_batches does not match h_batch_of");
   for (int b = 0; b < n_batches; ++b) max_batch = std::max(max_batch, first[b + 1] - first[b]);
   if (max_batch > capacity) return fail(TTX_ERR_INVALID, "a batch has more sources than the pool has slots");
-  const ttx_config& c = sessions[0]->m->cfg;
-  int Ls_cap = std::min(std::max(192, ((len_max + 63) / 64) * 64), c.max_positions);
-  Ls_cap = std::max(Ls_cap, len_max);
+  const int Ls_cap = pool_slot_width(len_max, sessions[0]->m->cfg.max_positions);
   TTX_TRY(beam_validate(sessions[0], d_src, 1, Ls_cap, p, d_out));
-  HIP_TRY(hipSetDevice(sessions[0]->m->device));
-  release_retired();
-  EventGuard ready;
-  HIP_TRY(hipEventCreateWithFlags(&ready.e, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(ready.e, (hipStream_t)stream));
-  const int n_jobs = std::max(1, std::min({n_sessions, n_batches, cdiv(R_total, std::max(1, std::min(capacity / 2, 8)))}));
-  const int C = std::min(capacity, std::max(max_batch, cdiv(R_total, n_jobs)));
+  const PoolShape shape = pool_shape(n_sessions, n_batches, R_total, capacity, 8, max_batch);
+  const int n_jobs = shape.n_jobs, C = shape.C;
   BeamPoolIo io{};
   io.out = d_out; io.trace_len = d_trace_len; io.summary = d_summary; io.T_cap = trace_cap;
   std::vector<BeamPoolJob> jobs(n_jobs);
-  int rc_final = TTX_OK;
-  for (int i = 0; i < n_jobs && rc_final == TTX_OK; ++i) {
-    ttx_session* s = sessions[i];
-    TTX_TRY(ensure_own_stream(s));
-    HIP_TRY(hipStreamWaitEvent(s->own_stream, ready.e, 0));
-    rc_final = bpool_start(jobs[i], s, s->own_stream, C, Ls_cap, p, io, h_len, h_batch_of, h_given_ls, R_total, n_batches);
-  }
-  const int min_admit = std::max(1, C / 4);                    // admissions of at least a quarter pool (or into an empty one)
-  const bool serial = sessions[0]->profile;
-  int cursor_b = 0, done = 0;                                  // next batch of the work list
+  const bool serial = sessions[0]->profile;                    // profiling sessions: one pool after another (see the greedy pool)
+  int cursor_b = 0;                                            // next batch of the work list
   const auto t_call = std::chrono::steady_clock::now();
-  bool hung = false;
   ttx_beam_stats acc{};
-  while (done < n_jobs && rc_final == TTX_OK) {
-    bool progressed = false;
-    int only = -1;                       // profiling sessions: one pool after another (see the greedy pool)
-    if (serial)
-      for (int i = n_jobs - 1; i >= 0; --i)
-        if (jobs[i].phase != 3) only = i;
-    for (int i = 0; i < n_jobs && rc_final == TTX_OK; ++i) {
-      if (serial && i != only) continue;
-      BeamPoolJob& j = jobs[i];
-      ttx_session* s = j.s;
-      volatile BeamPoolHost* bh = s->bp_host;
-      if (j.phase == 1) {
-        if (j.launched > 0 && bh->steps_done < j.launched) {                  // the iteration in flight has not published yet
-          if (j.progress.stalled()) { rc_final = session_hung(s); hung = true; break; }
-          continue;
-        }
-        if (bh->error) { rc_final = fail(TTX_ERR_HIP, "batch pool bookkeeping failed (admitted more sources than free slots)"); break; }
-        int n_live = (j.launched == 0 ? 0 : bh->n_live) + j.admitted_since;
-        int n_running = (j.launched == 0 ? 0 : bh->n_running) + j.admitted_since;
-        const int free_slots = C - n_live;
-        if (serial && j.quota_b < 0) {                  // serial pass: an equal contiguous share of the rest of the list (greedy pool)
-          const int target = first[cursor_b] + cdiv(R_total - first[cursor_b], n_jobs - i);
-          j.quota_b = cursor_b;
-          while (j.quota_b < n_batches && first[j.quota_b] < target) ++j.quota_b;
-        }
-        const int list_end_b = serial ? j.quota_b : n_batches;
-        if (cursor_b < list_end_b && (n_live == 0 || free_slots >= std::max(min_admit, first[cursor_b + 1] - first[cursor_b]))) {
-          // whole batches, as many as fit; the last batches of the list are shared out over the pools still running, so that
-          // they drain together, and a first fill that fits the pools at once is split evenly
-          int n_run_jobs = 0;
-          for (const BeamPoolJob& o : jobs) n_run_jobs += (o.phase == 1);
-          const int remaining = first[list_end_b] - first[cursor_b];
-          int share = std::max(1, cdiv(remaining, std::max(1, serial ? 1 : n_run_jobs)));
-          if (!serial && j.launched == 0 && (long long)n_jobs * C >= R_total) share = std::max(1, cdiv(remaining, n_jobs - i));
-          int take = 0, b_end = cursor_b;
-          while (b_end < list_end_b) {
-            const int sz = first[b_end + 1] - first[b_end];
-            if (take + sz > free_slots || (take > 0 && take + sz > share)) break;
-            take += sz;
-            ++b_end;
-          }
-          if (take > 0) {
-            const int r_first = first[cursor_b];
-            int Ls_new = 2;
-            for (int r = r_first; r < r_first + take; ++r) Ls_new = std::max(Ls_new, (int)h_len[r]);
-            rc_final = bpool_admit(j, d_src + (size_t)r_first * Ls_all, Ls_all, take, Ls_new, r_first);
-            if (rc_final != TTX_OK) break;
-            cursor_b = b_end;
-            n_live += take;
-            n_running += take;
-          }
-        }
-        if (n_live == 0) {
-          if (hipEventRecord(s->ev_c, j.st) != hipSuccess ||
-              hipMemcpyAsync(s->host_state, s->bs_cnt.p, sizeof(BeamCounters), hipMemcpyDeviceToHost, j.st) != hipSuccess ||
-              hipEventRecord(s->ev_done, j.st) != hipSuccess) {
-            rc_final = fail(TTX_ERR_HIP, "batch pool: enqueueing the final counter read-back failed");
-            break;
-          }
-          j.phase = 2;
-        } else {
-          if (j.launched > (long long)(trace_cap + 2) * (R_total + 1)) { rc_final = fail(TTX_ERR_HIP, "batch pool failed to terminate"); break; }
-          if (s->host_timing)
-            fprintf(stderr, "[ttx pool %d] t=%.3f ms iteration %d: %d live sources, %d running candidates, next batch %d of %d\n", i,
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(), j.launched + 1, n_live,
-                    n_running, cursor_b, n_batches);
-          rc_final = bpool_launch_iter(j, n_running);
-        }
-        progressed = true;
-      } else if (j.phase == 2) {
-        if (hipEventQuery(s->ev_done) == hipSuccess) {
-          const BeamCounters* cn = reinterpret_cast<const BeamCounters*>(s->host_state);
-          acc.model_calls += cn->model_calls;
-          acc.input_lines += cn->input_lines;
-          acc.running_rows += cn->running_rows;
-          acc.verified_positions += cn->verified_positions;
-          acc.executed_positions += cn->executed_positions;
-          acc.kv_prefix_positions += cn->kv_prefix_positions;
-          acc.running_candidates += cn->running_cands;
-          acc.src_tokens_padded += j.src_tokens_padded;
-          float ms = 0.f;
-          if (hipEventElapsedTime(&ms, s->ev_a, s->ev_c) == hipSuccess) acc.decode_ms += ms;
-          collect_gemm_profile(s, j.st);
-          j.phase = 3;
-          ++done;
-          progressed = true;
-        }
+  const auto start = [&](int i) -> int {
+    return bpool_start(jobs[i], sessions[i], sessions[i]->own_stream, C, Ls_cap, p, io, h_len, h_batch_of, h_given_ls, R_total, n_batches);
+  };
+  const auto turn = [&](int i) -> int {
+    BeamPoolJob& j = jobs[i];
+    ttx_session* s = j.s;
+    volatile BeamPoolHost* bh = s->bp_host;
+    if (j.phase == 1) {
+      if (j.launched > 0 && bh->steps_done < j.launched) return TURN_WAITING;       // the iteration in flight has not published yet
+      if (bh->error) return fail(TTX_ERR_HIP, "batch pool bookkeeping failed (admitted more sources than free slots)");
+      int n_live = (j.launched == 0 ? 0 : bh->n_live) + j.admitted_since;
+      int n_running = (j.launched == 0 ? 0 : bh->n_running) + j.admitted_since;
+      if (serial && j.quota_b < 0) j.quota_b = serial_quota(first.data(), n_batches, cursor_b, i, n_jobs);
+      int n_run_jobs = 0;
+      for (const BeamPoolJob& o : jobs) n_run_jobs += (o.phase == 1);
+      const int n_take = plan_admission(first.data(), n_batches, C, {cursor_b, C - n_live, n_live, j.launched == 0, i, n_jobs, n_run_jobs, serial, j.quota_b});
+      if (n_take > 0) {
+        const int r_first = first[cursor_b], take = first[cursor_b + n_take] - r_first;
+        TTX_TRY(bpool_admit(j, d_src + (size_t)r_first * Ls_all, Ls_all, take, chunk_width(h_len, r_first, r_first + take), r_first));
+        cursor_b += n_take;
+        n_live += take;
+        n_running += take;
       }
+      if (n_live == 0) {
+        if (hipEventRecord(s->ev_c, j.st) != hipSuccess ||
+            hipMemcpyAsync(s->host_state, s->bs_cnt.p, sizeof(BeamCounters), hipMemcpyDeviceToHost, j.st) != hipSuccess ||
+            hipEventRecord(s->ev_done, j.st) != hipSuccess)
+          return fail(TTX_ERR_HIP, "batch pool: enqueueing the final counter read-back failed");
+        j.phase = 2;
+      } else {
+        if (j.launched > (long long)(trace_cap + 2) * (R_total + 1)) return fail(TTX_ERR_HIP, "batch pool failed to terminate");
+        if (s->host_timing)
+          fprintf(stderr, "[ttx pool %d] t=%.3f ms iteration %d: %d live sources, %d running candidates, next batch %d of %d\n", i,
+                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(), j.launched + 1, n_live,
+                  n_running, cursor_b, n_batches);
+        TTX_TRY(bpool_launch_iter(j, n_running));
+      }
+      return TURN_PROGRESSED;
     }
-    if (!progressed) __builtin_ia32_pause();
-  }
-  if (hung) {
-    for (int i = 0; i < n_jobs; ++i) jobs[i].s->dead = true;
-  } else {
-    for (int i = 0; i < n_jobs; ++i)
-      if (jobs[i].s && jobs[i].s->own_stream) (void)hipStreamSynchronize(jobs[i].s->own_stream);
-  }
-  acc.status = rc_final;
+    if (hipEventQuery(s->ev_done) != hipSuccess) return TURN_IDLE;
+    const BeamCounters* cn = reinterpret_cast<const BeamCounters*>(s->host_state);
+    acc.model_calls += cn->model_calls;
+    acc.input_lines += cn->input_lines;
+    acc.running_rows += cn->running_rows;
+    acc.verified_positions += cn->verified_positions;
+    acc.executed_positions += cn->executed_positions;
+    acc.kv_prefix_positions += cn->kv_prefix_positions;
+    acc.running_candidates += cn->running_cands;
+    acc.src_tokens_padded += j.src_tokens_padded;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->ev_a, s->ev_c) == hipSuccess) acc.decode_ms += ms;
+    collect_gemm_profile(s, j.st);
+    j.phase = 3;
+    return TURN_FINISHED;
+  };
+  acc.status = drive_sessions(sessions, n_jobs, serial, stream, start, turn);
   *stats = acc;
-  return rc_final;
+  return acc.status;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2992,25 +2749,20 @@ static int beam_generate_impl(ttx_session* s, const int64_t* d_src, int B, int L
   const int d = c.embedding_dim, Ld = c.num_decoder_layers;
   const int MC = B * K, ld = max_len + 2, Lc = max_len + 2;
   const size_t Mmax = (size_t)MC;
-  int rc = TTX_OK;
-  auto need = [&](Buf& b, size_t bytes) { if (rc == TTX_OK) rc = ensure(b, bytes, st); };
+  Needs need{st};
   need(s->tok_src, (size_t)B * Ls * 4); need(s->src_valid, (size_t)B * Ls); need(s->memory, (size_t)B * Ls * d * 4);
   need(s->memkv, (size_t)B * Ls * Ld * 2 * d * 4);
   need(s->drafts, (size_t)MC * 4);
   need(s->gen, (size_t)MC * ld * 4); need(s->front, (size_t)MC * 4); need(s->act_idx, (size_t)MC * 4);
-  need(s->pred, Mmax * 4); need(s->state, sizeof(DecState)); need(s->logits, Mmax * V * 4);
   for (int i = 0; i < 2; ++i) { need(s->tk[i], (size_t)Ld * MC * Lc * d * 4); need(s->tv[i], (size_t)Ld * MC * Lc * d * 4); }
   need(s->t_prev_len, (size_t)MC * 4); need(s->t_slot_of, (size_t)MC * 4); need(s->t_src_of, (size_t)MC * 4);
   need(s->bs_cand_next, (size_t)MC * ld * 8); need(s->bs_len_next, (size_t)MC * 4); need(s->bs_fin_next, (size_t)MC);
   need(s->bs_logp_next, (size_t)MC * 4); need(s->bs_len, (size_t)MC * 4); need(s->bs_fin, (size_t)MC); need(s->bs_active, (size_t)MC);
   need(s->bs_logp, (size_t)MC * 4); need(s->bs_per_cand, (size_t)MC * 4); need(s->bs_parent, (size_t)MC * 4);
   need(s->bs_parent_draft, (size_t)MC * 4); need(s->bs_cnt, sizeof(BeamCounters)); need(s->beam_summary, 8 * 4);
-  const size_t Macts = std::max(Mmax, (size_t)B * Ls);
-  if (rc == TTX_OK) rc = ensure_acts(s, st, Macts, 1);
-  need(s->qkv, std::max((size_t)Ld * Mmax, (size_t)B * Ls) * 3 * d * 4);
-  need(s->slab, sizeof(float) * 16 * Macts * d);
+  need_step_workspaces(s, need, Mmax, (size_t)B * Ls);
   s->graphs_current();
-  TTX_TRY(rc);
+  TTX_TRY(need.rc);
   if (!s->beam_host && hipHostMalloc((void**)&s->beam_host, sizeof(BeamHost), hipHostMallocMapped) != hipSuccess)
     return fail(TTX_ERR_NOMEM, "hipHostMalloc failed");
   std::memset(s->beam_host, 0, sizeof(BeamHost));
@@ -3018,11 +2770,7 @@ static int beam_generate_impl(ttx_session* s, const int64_t* d_src, int B, int L
   HIP_TRY(hipHostGetDevicePointer((void**)&dev_host, (void*)s->beam_host, 0));
   // self.model(src, y) of the first step = encoder + the decoder on <BOS>; the reference then re-encodes the source once per
   // beam (:120-124): identical rows, so the beams of a source share its memory row here
-  TTX_TRY(prepare_tokens(st, d_src, s->tok_src.as<int>(), s->src_valid.as<uint8_t>(), B * Ls, c.pad_token));
-  TTX_TRY(run_encoder(s, st, s->tok_src.as<int>(), s->src_valid.as<uint8_t>(), B, Ls, s->memory.as<float>()));
-  const int gv = variant_for_rows(s, (long long)B * Ls, false);
-  TTX_TRY(launch_gemm(s, st, s->memory.as<float>(), d, m->p(m->cross_kv_w), d, m->p(m->cross_kv_b), s->memkv.as<float>(),
-                      Ld * 2 * d, nullptr, B * Ls, Ld * 2 * d, d, false, 0, 0, gv));
+  TTX_TRY(encode_sources(s, st, d_src, 0, B, Ls, s->src_valid.as<uint8_t>(), s->memkv.as<float>()));
   hipLaunchKernelGGL(k_bs_init, dim3(64), dim3(256), 0, st, s->bs_cand_next.as<int64_t>(), ld, s->bs_len_next.as<int>(),
                      s->bs_fin_next.as<uint8_t>(), s->bs_logp_next.as<float>(), s->bs_parent.as<int>(), s->bs_parent_draft.as<int>(),
                      MC, B, p->bos_token, p->pad_token, s->bs_cnt.as<BeamCounters>());
@@ -3061,11 +2809,7 @@ static int beam_generate_impl(ttx_session* s, const int64_t* d_src, int B, int L
     TTX_TRY(enqueue(first));
     ++launched;
     cur ^= 1;
-    Progress wait;
-    while (bh->steps_done < launched) {
-      if (wait.stalled()) return session_hung(s);
-      __builtin_ia32_pause();
-    }
+    if (!wait_published(watchdog_seconds(), [&] { return bh->steps_done >= launched; })) return session_hung(s);
     width += 1;
     n_cand = B * K; beam = K;
     n_eos = bh->summary[0];

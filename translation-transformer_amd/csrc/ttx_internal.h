@@ -2,7 +2,9 @@
 // ttx_gemm.hip: GEMM family; ttx_attn.hip: attention family): the model and its weight layout, the session with its
 // workspaces (declared once, in TTX_SESSION_BUFS) and its two caches of captured graphs (GraphCache, keyed by GraphKey).
 // Kernels are launched from the unit that defines them; the other units reach them through the launchers declared at the
-// bottom.
+// bottom.  Two host-only headers (no HIP, compiled by the host tests as well) belong to ttx_api.hip: ttx_drive.h, the core of the
+// polling loops (round-robin turns over the jobs of a call, watchdog, first error), and ttx_admit.h, the admission policy of the
+// two pools (pool count and size, which batches a pool takes, length buckets).
 #pragma once
 #include "ttx.h"
 #include "ttx_common.hip.h"
