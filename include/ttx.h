@@ -619,6 +619,93 @@ int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, int64_t* st
  * between accept steps.  Refused before the session has run the pair once. */
 int ttx_debug_accept_block(ttx_session* s, int32_t* words, int n_words, void* stream);
 
+/* ---- The beam family of csrc/ttx_loop_kernels.hip.h, ONE launch each on DEVICE arrays of the caller (tests/test_gpu_beam_loop_kernels.py;
+ * the rules are restated in tests/util_beam_checks.py).  Every struct below is the kernel's own argument block: pointers first,
+ * then int32 scalars, named as the kernel names them.  Grid, block, dynamic LDS, the logits-per-lane dispatch and the raise of the
+ * LDS limit are the production launch functions of csrc/ttx_api.hip.  Arrays are sized by max_cand (the grid) where the kernel
+ * indexes them by candidate.  Each entry waits for its launch.  Refused (TTX_ERR_INVALID, nothing launched): a null required
+ * pointer, a non-positive size, and whatever lies beyond the limits the generators enforce: n_best (K) <= 32, n_drafts (N) <= 64,
+ * V <= 1024, K * (dl + 1) <= 1023 segments, dynamic LDS <= 150 KiB. */
+typedef struct ttx_debug_bs_prep_args {
+  const int64_t* d_cand_next; const int32_t* d_len_next; const uint8_t* d_fin_next; const float* d_logp_next;   /* [max_cand, ld], [max_cand] x 3 */
+  const int32_t* d_drafts_all;          /* all drafts: [B, N, D0] */
+  const int32_t* d_lib;                 /* smart: [B, n_lib, lib_ld] */
+  int32_t* d_gen; int32_t* d_front; int32_t* d_len; uint8_t* d_active; uint8_t* d_finished; float* d_logp; int32_t* d_per_cand;
+  int32_t* d_drafts32;                  /* [max_cand, N, dl] */
+  int32_t ld, max_cand, n_cand, beam, dl, N, pad, smart, n_lib, lib_ld, D0;
+} ttx_debug_bs_prep_args;
+/* ttx_debug_bs_prep: k_bs_prep on max_cand workgroups.  Also refused: n_cand > max_cand, all drafts with dl > D0, smart with
+ * dl + 1 > lib_ld or n_lib < 1. */
+int ttx_debug_bs_prep(ttx_session* s, const ttx_debug_bs_prep_args* a, void* stream);
+
+typedef struct ttx_debug_bs_list_args {
+  const uint8_t* d_active; const int32_t* d_per_cand; const int32_t* d_len;     /* [n_cand] */
+  int32_t* d_act_idx; int32_t* d_slot_of; int32_t* d_prev_len;                  /* [n_cand] */
+  int32_t* d_summary;                                                           /* [5] */
+  int32_t n_cand, N, dl;
+} ttx_debug_bs_list_args;
+/* ttx_debug_bs_list: k_bs_list.  `words` is a HOST array of 21 int64: on entry [0..7] = the BeamCounters image (model_calls,
+ * input_lines, running_rows, verified_positions, executed_positions, kv_prefix_positions, running_cands, max_group), put on the
+ * device, ordered on `stream`; on return the same 8 words as the kernel left them and [8..20] = the DecState it wrote (the 13
+ * words of ttx_debug_accept). */
+int ttx_debug_bs_list(ttx_session* s, const ttx_debug_bs_list_args* a, int64_t* words, void* stream);
+
+typedef struct ttx_debug_bs_hits_args {
+  const float* d_logits;                /* [n_active * (1 + N*dl), V] */
+  const uint8_t* d_finished; const int32_t* d_slot_of; const int32_t* d_per_cand; const int32_t* d_drafts32;
+  uint8_t* d_hit;                       /* [max_cand, N * dl] */
+  const int32_t* d_dl_of;               /* pool: [max_cand]; NULL: the per-batch path */
+  int32_t V, max_cand, n_cand, N, dl, K;
+  int32_t vpl;                          /* logits per lane: 0 the production choice by V, or 4 / 8 / 16 (refused unless 64 * vpl >= V) */
+} ttx_debug_bs_hits_args;
+/* ttx_debug_bs_hits: k_bs_hits with the generators' nucleus 0.9975. */
+int ttx_debug_bs_hits(ttx_session* s, const ttx_debug_bs_hits_args* a, void* stream);
+
+typedef struct ttx_debug_bs_leaves_args {
+  const float* d_logits; const uint8_t* d_finished; const int32_t* d_slot_of; const int32_t* d_per_cand; const int32_t* d_drafts32;
+  const float* d_logp; const uint8_t* d_hit;
+  int32_t* d_best_n; int32_t* d_best_slot; int64_t* d_chosen;                   /* [max_cand], [max_cand], [max_cand, dl] */
+  float* d_leaf_score; int32_t* d_leaf_tok; int32_t* d_leaf_cnt;                /* [max_cand, dl+1, K] x 2, [max_cand, dl+1] */
+  const uint8_t* d_live; const int32_t* d_dl_of; const int32_t* d_grp_of; const int32_t* d_cand_batch;   /* pool; all NULL: per batch */
+  int32_t V, max_cand, n_cand, N, dl, K, bos, pad, smart;
+  int32_t max_group;                    /* per-batch smart mode: BeamCounters.max_group as k_bs_list left it */
+  int32_t vpl;
+} ttx_debug_bs_leaves_args;
+/* ttx_debug_bs_leaves: k_bs_leaves.  Also refused: grp_of without cand_batch or the reverse. */
+int ttx_debug_bs_leaves(ttx_session* s, const ttx_debug_bs_leaves_args* a, void* stream);
+
+typedef struct ttx_debug_beam_select_args {
+  const float* d_leaf_score; const int32_t* d_leaf_tok; const int32_t* d_leaf_cnt;
+  const int32_t* d_cand; const int32_t* d_len; const int64_t* d_chosen; const int32_t* d_chosen_slot; const uint8_t* d_finished;
+  int64_t* d_new_cand; float* d_new_logp; int32_t* d_parent; int32_t* d_parent_draft; int32_t* d_mark;   /* [B*K, ld_out], [B*K] .. */
+  int32_t* d_summary;                   /* [5], read and written */
+  int32_t* d_new_len; uint8_t* d_new_finished;                                  /* [B*K], both or neither */
+  int32_t width, ld_in, ld_out, B, beam, dl, K, pad, eos;
+} ttx_debug_beam_select_args;
+/* ttx_debug_beam_select: k_beam_select<int> on B workgroups.  Also refused: width above ld_in or ld_out. */
+int ttx_debug_beam_select(ttx_session* s, const ttx_debug_beam_select_args* a, void* stream);
+
+typedef struct ttx_debug_beam_step_args {
+  const float* d_logits; const int32_t* d_slot_of; const uint8_t* d_finished; const float* d_score; const int32_t* d_gen;
+  int64_t* d_new_cand; float* d_new_score; int32_t* d_parent; int32_t* d_new_len; uint8_t* d_new_finished; int32_t* d_parent_draft;
+  int32_t* d_summary;                   /* [0] += new candidates holding EOS */
+  int32_t V, ld, width, B, beam, K, pad, eos;
+} ttx_debug_beam_step_args;
+/* ttx_debug_beam_step: k_beam_step on B workgroups.  Also refused: K > beam * V, width >= ld. */
+int ttx_debug_beam_step(ttx_session* s, const ttx_debug_beam_step_args* a, void* stream);
+
+typedef struct ttx_debug_tree_cache_args {
+  const int32_t* d_len; const int32_t* d_parent; const int32_t* d_parent_draft; const int32_t* d_prev_len; const uint8_t* d_active;
+  const float* d_k_old; const float* d_v_old; float* d_k_new; float* d_v_new;
+  const float* d_qkv_prev; const int32_t* d_prev_slot_of;
+  const int32_t* d_slot_parent; const int32_t* d_slot_self;                     /* both NULL: two buffers, cache row = candidate */
+  int64_t cache_layer_stride, cache_seq_stride, qkv_layer_stride;               /* floats */
+  int32_t max_cand, layers, prev_N, prev_D, d;
+} ttx_debug_tree_cache_args;
+/* ttx_debug_tree_cache: k_tree_cache on (max_cand, layers) workgroups.  Also refused: d not a multiple of 4, strides that are not
+ * multiples of 4 floats, buffers that are not 16-byte aligned, one slot map without the other, slot maps with k_old != k_new. */
+int ttx_debug_tree_cache(ttx_session* s, const ttx_debug_tree_cache_args* a, void* stream);
+
 /* ttx_debug_kvcopy: ONE launch of k_kvcopy on a grid of (B, Ld) workgroups: for slot < n_copy with record (b, best, n_acc,
  * front_old, .) of d_rec int32 [B, 5] and j = 0 .. n_acc, the K and V thirds of step row (j == 0 ? 0 : 1 + best*D + (j-1)) of the
  * slot, in d_qkv [Ld][B * (1 + N*D)][3d] with qkv_layer_stride floats between layers, are copied bit for bit to position

@@ -36,6 +36,14 @@ def test_struct_sizes_match_header_layout():
     assert C.sizeof(N.GenStats) == 6 * 8 + 2 * 8 + 2 * 8
     assert C.sizeof(N.Tensor) == 24
     assert C.sizeof(N.DebugAcceptArgs) == 15 * 8 + 15 * 4 + 4            # ttx_debug_accept_args: 15 pointers, 15 int32, tail padding
+    # the beam family's ttx_debug_*_args: pointers, int64 strides, int32 scalars, tail padding to 8
+    assert C.sizeof(N.DebugBsPrepArgs) == 14 * 8 + 11 * 4 + 4
+    assert C.sizeof(N.DebugBsListArgs) == 7 * 8 + 3 * 4 + 4
+    assert C.sizeof(N.DebugBsHitsArgs) == 7 * 8 + 7 * 4 + 4
+    assert C.sizeof(N.DebugBsLeavesArgs) == 17 * 8 + 11 * 4 + 4
+    assert C.sizeof(N.DebugBeamSelectArgs) == 16 * 8 + 9 * 4 + 4
+    assert C.sizeof(N.DebugBeamStepArgs) == 12 * 8 + 8 * 4
+    assert C.sizeof(N.DebugTreeCacheArgs) == 13 * 8 + 3 * 8 + 5 * 4 + 4
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="only meaningful on a machine without a GPU")

@@ -22,9 +22,9 @@ import torch
 
 PAD, BOS, EOS = 0, 1, 2
 GUARD = 64                                   # elements in front of and behind every operand (16-byte alignment is kept)
-SENTINEL = {torch.int16: -21846, torch.int32: -1431655766, torch.int64: -6148914691236517206}      # 0xAA.. patterns
+SENTINEL = {torch.uint8: 0xAA, torch.int16: -21846, torch.int32: -1431655766, torch.int64: -6148914691236517206}      # 0xAA.. patterns
 FLOAT_FILL = 0x7FD5AAAA                      # quiet NaN with a payload: what a float output holds before its launch
-NP_OF = {torch.int16: np.int16, torch.int32: np.int32, torch.int64: np.int64, torch.float32: np.float32}
+NP_OF = {torch.uint8: np.uint8, torch.int16: np.int16, torch.int32: np.int32, torch.int64: np.int64, torch.float32: np.float32}
 
 WORDS = ["n_active", "r_rows", "m_rows", "stop", "width", "steps", "error", "n_copy", "accepted", "produced",
          "verified_positions", "kv_prefix_positions", "src_positions", "host_stop", "host_steps_done", "host_width", "host_n_active"]

@@ -110,7 +110,44 @@ class DebugAcceptArgs(C.Structure):
                                          "pad", "bos", "eos", "greedy", "threads")]
 
 
-DEBUG_ACCEPT_BLOCK_WORDS = 264    # int32 words of the AcceptBlk between k_accept_slots and k_accept_finish (ttx_debug_accept_block)
+def _debug_args(name: str, pointers, ints, int64s=()):
+    """A ttx_debug_*_args struct of include/ttx.h: device pointers, then int64 strides, then int32 scalars."""
+    fields = [(n, C.c_void_p) for n in pointers] + [(n, C.c_int64) for n in int64s] + [(n, C.c_int32) for n in ints]
+    return type(name, (C.Structure,), {"_fields_": fields, "POINTERS": tuple(pointers), "__doc__": f"ttx_{name}: one launch's operands."})
+
+
+# the beam family (csrc/ttx_loop_kernels.hip.h), one struct per kernel
+DebugBsPrepArgs = _debug_args("debug_bs_prep_args",
+                              ("d_cand_next", "d_len_next", "d_fin_next", "d_logp_next", "d_drafts_all", "d_lib", "d_gen", "d_front",
+                               "d_len", "d_active", "d_finished", "d_logp", "d_per_cand", "d_drafts32"),
+                              ("ld", "max_cand", "n_cand", "beam", "dl", "N", "pad", "smart", "n_lib", "lib_ld", "D0"))
+DebugBsListArgs = _debug_args("debug_bs_list_args",
+                              ("d_active", "d_per_cand", "d_len", "d_act_idx", "d_slot_of", "d_prev_len", "d_summary"), ("n_cand", "N", "dl"))
+DebugBsHitsArgs = _debug_args("debug_bs_hits_args",
+                              ("d_logits", "d_finished", "d_slot_of", "d_per_cand", "d_drafts32", "d_hit", "d_dl_of"),
+                              ("V", "max_cand", "n_cand", "N", "dl", "K", "vpl"))
+DebugBsLeavesArgs = _debug_args("debug_bs_leaves_args",
+                                ("d_logits", "d_finished", "d_slot_of", "d_per_cand", "d_drafts32", "d_logp", "d_hit", "d_best_n",
+                                 "d_best_slot", "d_chosen", "d_leaf_score", "d_leaf_tok", "d_leaf_cnt", "d_live", "d_dl_of", "d_grp_of",
+                                 "d_cand_batch"),
+                                ("V", "max_cand", "n_cand", "N", "dl", "K", "bos", "pad", "smart", "max_group", "vpl"))
+DebugBeamSelectArgs = _debug_args("debug_beam_select_args",
+                                  ("d_leaf_score", "d_leaf_tok", "d_leaf_cnt", "d_cand", "d_len", "d_chosen", "d_chosen_slot",
+                                   "d_finished", "d_new_cand", "d_new_logp", "d_parent", "d_parent_draft", "d_mark", "d_summary",
+                                   "d_new_len", "d_new_finished"),
+                                  ("width", "ld_in", "ld_out", "B", "beam", "dl", "K", "pad", "eos"))
+DebugBeamStepArgs = _debug_args("debug_beam_step_args",
+                                ("d_logits", "d_slot_of", "d_finished", "d_score", "d_gen", "d_new_cand", "d_new_score", "d_parent",
+                                 "d_new_len", "d_new_finished", "d_parent_draft", "d_summary"),
+                                ("V", "ld", "width", "B", "beam", "K", "pad", "eos"))
+DebugTreeCacheArgs = _debug_args("debug_tree_cache_args",
+                                 ("d_len", "d_parent", "d_parent_draft", "d_prev_len", "d_active", "d_k_old", "d_v_old", "d_k_new",
+                                  "d_v_new", "d_qkv_prev", "d_prev_slot_of", "d_slot_parent", "d_slot_self"),
+                                 ("max_cand", "layers", "prev_N", "prev_D", "d"),
+                                 ("cache_layer_stride", "cache_seq_stride", "qkv_layer_stride"))
+DEBUG_BS_LIST_WORDS = 21          # int64 words of ttx_debug_bs_list's host array: 8 of the BeamCounters, 13 of the DecState
+
+DEBUG_ACCEPT_BLOCK_WORDS = 264   # int32 words of the AcceptBlk between k_accept_slots and k_accept_finish (ttx_debug_accept_block)
 DEBUG_ACCEPT_STATE_WORDS = 17     # int64 words of ttx_debug_accept's host `state` array (include/ttx.h)
 
 
@@ -186,6 +223,13 @@ SYMBOLS = {
     "ttx_debug_embed": (C.c_int, [_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _I, _I, _I, _I, _I, _VP]),
     "ttx_debug_accept": (C.c_int, [_VP, C.POINTER(DebugAcceptArgs), C.POINTER(C.c_int64), _VP]),
     "ttx_debug_accept_block": (C.c_int, [_VP, C.POINTER(C.c_int32), _I, _VP]),
+    "ttx_debug_bs_prep": (C.c_int, [_VP, C.POINTER(DebugBsPrepArgs), _VP]),
+    "ttx_debug_bs_list": (C.c_int, [_VP, C.POINTER(DebugBsListArgs), C.POINTER(C.c_int64), _VP]),
+    "ttx_debug_bs_hits": (C.c_int, [_VP, C.POINTER(DebugBsHitsArgs), _VP]),
+    "ttx_debug_bs_leaves": (C.c_int, [_VP, C.POINTER(DebugBsLeavesArgs), _VP]),
+    "ttx_debug_beam_select": (C.c_int, [_VP, C.POINTER(DebugBeamSelectArgs), _VP]),
+    "ttx_debug_beam_step": (C.c_int, [_VP, C.POINTER(DebugBeamStepArgs), _VP]),
+    "ttx_debug_tree_cache": (C.c_int, [_VP, C.POINTER(DebugTreeCacheArgs), _VP]),
     "ttx_debug_kvcopy": (C.c_int, [_VP, _VP, _I, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int64, _I, _I, _I, _I, _I, _VP]),
     "ttx_debug_kvcopy_split": (C.c_int, [_VP, _VP, _I, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int64, _I, _I, _I, _I, _I, _VP, _VP,
                                          C.c_int64, _VP]),

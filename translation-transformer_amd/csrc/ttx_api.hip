@@ -2182,14 +2182,22 @@ __global__ void k_bs_src_of(int* src_of, int n, int beam) {
 // ---- the pieces of one beam iteration, shared by the beam-speculative loop, its batch pool and standard beam search ----------
 // k_bs_prep (the rows of the last selection -> this iteration's candidates and draft slots) and the candidate -> source map.
 // `pa` arrives with the shape (ld, n_cand, beam, dl, N, pad) and, for the speculative loop, the draft-source fields set.
+// Every enqueue_* helper below is two parts: it fills the kernel's argument struct from the session, and a launch_* function
+// launches that struct (grid, block, dynamic LDS, VPL dispatch, raise_lds_limit).  The ttx_debug_* entries of the beam kernels
+// call the launch_* part on the caller's operands, so a test launch is the production launch.
+static int launch_bs_prep(hipStream_t st, int MC, const BeamPrepArgs& pa) {
+  hipLaunchKernelGGL(k_bs_prep, dim3(MC), dim3(256), 0, st, pa);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
 static int enqueue_bs_prep(ttx_session* s, hipStream_t st, int MC, BeamPrepArgs pa) {
   pa.cand_next = s->bs_cand_next.as<int64_t>(); pa.len_next = s->bs_len_next.as<int>();
   pa.fin_next = s->bs_fin_next.as<uint8_t>(); pa.logp_next = s->bs_logp_next.as<float>();
   pa.gen = s->gen.as<int>(); pa.front = s->front.as<int>(); pa.len = s->bs_len.as<int>(); pa.active = s->bs_active.as<uint8_t>();
   pa.finished = s->bs_fin.as<uint8_t>(); pa.logp = s->bs_logp.as<float>(); pa.per_cand = s->bs_per_cand.as<int>();
   pa.drafts32 = s->drafts.as<int>();
-  hipLaunchKernelGGL(k_bs_prep, dim3(MC), dim3(256), 0, st, pa);
-  HIP_TRY(hipGetLastError());
+  TTX_TRY(launch_bs_prep(st, MC, pa));
   hipLaunchKernelGGL(k_bs_src_of, dim3(cdiv(MC, 256)), dim3(256), 0, st, s->t_src_of.as<int>(), MC, pa.beam);
   HIP_TRY(hipGetLastError());
   return TTX_OK;
@@ -2198,6 +2206,12 @@ static int enqueue_bs_prep(ttx_session* s, hipStream_t st, int MC, BeamPrepArgs 
 // k_tree_cache: every candidate's KV cache in buffer `to` from its parent's in buffer `from` plus the rows the parent's accepted
 // draft left in the previous step's Q/K/V buffer (layout (prev_N, prev_D)).  With slot maps (the batch pool: from == to) a
 // candidate's cache lives in the slot the map names.
+static int launch_tree_cache(hipStream_t st, int MC, int layers, const TreeCacheArgs& ca) {
+  hipLaunchKernelGGL(k_tree_cache, dim3(MC, layers), dim3(256), 0, st, ca);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
 static int enqueue_tree_cache(ttx_session* s, hipStream_t st, int MC, int Lc, int from, int to, const int* slot_parent,
                               const int* slot_self, int prev_N, int prev_D) {
   const int d = s->m->cfg.embedding_dim;
@@ -2211,21 +2225,23 @@ static int enqueue_tree_cache(ttx_session* s, hipStream_t st, int MC, int Lc, in
   ca.qkv_prev = s->qkv.as<float>();
   ca.qkv_layer_stride = (long long)MC * step_rps(prev_N, prev_D) * 3 * d;
   ca.prev_slot_of = s->t_slot_of.as<int>(); ca.prev_N = prev_N; ca.prev_D = prev_D; ca.d = d;
-  hipLaunchKernelGGL(k_tree_cache, dim3(MC, s->m->cfg.num_decoder_layers), dim3(256), 0, st, ca);
+  return launch_tree_cache(st, MC, s->m->cfg.num_decoder_layers, ca);
+}
+
+// k_bs_list: the running candidates -> the verify step's active list, slot map and DecState.
+static int launch_bs_list(hipStream_t st, const BeamListArgs& la) {
+  hipLaunchKernelGGL(k_bs_list, dim3(1), dim3(256), 0, st, la);
   HIP_TRY(hipGetLastError());
   return TTX_OK;
 }
 
-// k_bs_list: the running candidates -> the verify step's active list, slot map and DecState.
 static int enqueue_bs_list(ttx_session* s, hipStream_t st, int n_cand, int N, int dl) {
   BeamListArgs la{};
   la.active = s->bs_active.as<uint8_t>(); la.per_cand = s->bs_per_cand.as<int>(); la.len = s->bs_len.as<int>();
   la.n_cand = n_cand; la.N = N; la.dl = dl;
   la.act_idx = s->act_idx.as<int>(); la.slot_of = s->t_slot_of.as<int>(); la.prev_len = s->t_prev_len.as<int>();
   la.st = s->state.as<DecState>(); la.cnt = s->bs_cnt.as<BeamCounters>(); la.summary = s->beam_summary.as<int>();
-  hipLaunchKernelGGL(k_bs_list, dim3(1), dim3(256), 0, st, la);
-  HIP_TRY(hipGetLastError());
-  return TTX_OK;
+  return launch_bs_list(st, la);
 }
 
 // The verify step of tree decoding: D + 1 new positions per (running candidate, draft slot) on the candidate's KV cache in
@@ -2241,13 +2257,32 @@ static StepCtx tree_step_ctx(ttx_session* s, int MC, int Ls, int N, int D, int L
 // k_bs_hits (which draft tokens the step's logits accept) and k_bs_leaves (the best draft per candidate and its leaves).
 // `pool`: the batch pool's per-candidate draft lengths, live flags and batch maps (null: one batch, one draft length).
 // `skip_hits_without_drafts`: the single-batch loop launches no k_bs_hits at dl == 0; the pool always launches it.
+// `ha` / `le`: the launch of k_bs_hits / k_bs_leaves, null for none (both carry V, N and dl).  `vpl`: logits per lane the
+// selection keeps in registers, 0 = the smallest of 4 / 8 / 16 that covers the vocabulary (same results), else that one.
+static int launch_hits_leaves(hipStream_t st, int MC, const BeamHitsArgs* ha, const BeamLeaves2Args* le, int vpl) {
+  const int V = ha ? ha->V : le->V, N = ha ? ha->N : le->N, dl = ha ? ha->dl : le->dl;
+  const dim3 hits_grid(MC, cdiv(std::max(N * dl, 1), BS_HITS_WAVES));
+  const size_t leaves_lds = (size_t)2 * (dl + 1) * 4;
+  const auto launch = [&](auto v) {
+    constexpr int VPL = decltype(v)::value;
+    if (ha) hipLaunchKernelGGL(k_bs_hits<VPL>, hits_grid, dim3(BS_HITS_WAVES * 64), 0, st, *ha);
+    if (le) hipLaunchKernelGGL(k_bs_leaves<VPL>, dim3(MC), dim3(BS_LEAVES_THREADS), leaves_lds, st, *le);
+  };
+  if (vpl == 0) vpl = V <= 256 ? 4 : (V <= 512 ? 8 : NUC_VPL);
+  if (vpl == 4) launch(std::integral_constant<int, 4>{});
+  else if (vpl == 8) launch(std::integral_constant<int, 8>{});
+  else launch(std::integral_constant<int, NUC_VPL>{});
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
 static int enqueue_hits_leaves(ttx_session* s, hipStream_t st, int MC, int n_cand, int N, int dl, int K, const ttx_beam_params& p,
                                bool smart, const BeamPoolArgs* pool, bool skip_hits_without_drafts) {
   const int V = s->m->cfg.vocab_size;
   BeamHitsArgs ha{};
   ha.logits = s->logits.as<float>(); ha.V = V; ha.finished = s->bs_fin.as<uint8_t>(); ha.slot_of = s->t_slot_of.as<int>();
   ha.per_cand = s->bs_per_cand.as<int>(); ha.drafts32 = s->drafts.as<int>();
-  ha.n_cand = n_cand; ha.N = N; ha.dl = dl; ha.K = K; ha.nucleus = 0.9975f; ha.hit = s->bs_hit.as<uint8_t>();
+  ha.n_cand = n_cand; ha.N = N; ha.dl = dl; ha.K = K; ha.nucleus = BS_NUCLEUS; ha.hit = s->bs_hit.as<uint8_t>();
   BeamLeaves2Args le{};
   le.logits = s->logits.as<float>(); le.V = V; le.finished = s->bs_fin.as<uint8_t>(); le.slot_of = s->t_slot_of.as<int>();
   le.per_cand = s->bs_per_cand.as<int>(); le.drafts32 = s->drafts.as<int>(); le.logp = s->bs_logp.as<float>();
@@ -2259,25 +2294,29 @@ static int enqueue_hits_leaves(ttx_session* s, hipStream_t st, int MC, int n_can
     ha.dl_of = pool->cand_dl;
     le.live = pool->live; le.dl_of = pool->cand_dl; le.grp_of = pool->bat_grp; le.cand_batch = pool->cand_batch;
   }
-  const dim3 hits_grid(MC, cdiv(std::max(N * dl, 1), BS_HITS_WAVES));
-  const size_t leaves_lds = (size_t)2 * (dl + 1) * 4;
   const bool hits = dl > 0 || !skip_hits_without_drafts;
-  const auto launch = [&](auto vpl) {
-    constexpr int VPL = decltype(vpl)::value;
-    if (hits) hipLaunchKernelGGL(k_bs_hits<VPL>, hits_grid, dim3(BS_HITS_WAVES * 64), 0, st, ha);
-    hipLaunchKernelGGL(k_bs_leaves<VPL>, dim3(MC), dim3(BS_LEAVES_THREADS), leaves_lds, st, le);
-  };
-  // logits per lane the selection keeps in registers: the smallest of 4 / 8 / 16 that covers the vocabulary (same results)
-  if (V <= 256) launch(std::integral_constant<int, 4>{});
-  else if (V <= 512) launch(std::integral_constant<int, 8>{});
-  else launch(std::integral_constant<int, NUC_VPL>{});
-  HIP_TRY(hipGetLastError());
-  return TTX_OK;
+  return launch_hits_leaves(st, MC, hits ? &ha : nullptr, &le, 0);
 }
 
 // The kernels of one iteration, in order, as a function of the job's scalars alone (so that the sequence can be captured
 // once per shape and replayed).  `first`: no cache to derive (every candidate is a fresh <BOS> row); `cur`: which of the
 // two cache buffers holds the parents' caches.
+static int launch_beam_select(ttx_session* s, hipStream_t st, const BeamSelectArgs<int>& sa) {
+  const size_t lds = 2 * (size_t)sa.beam * (sa.dl + 1) * sa.K * 4;
+  TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_beam_select<int>), lds, s->attr_select));
+  hipLaunchKernelGGL(k_beam_select<int>, dim3(sa.B), dim3(256), lds, st, sa);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+static int launch_beam_step(ttx_session* s, hipStream_t st, const BeamStepArgs& sa) {
+  const size_t lds = (size_t)sa.beam * sa.V * 4;
+  TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_beam_step), lds, s->attr_step));
+  hipLaunchKernelGGL(k_beam_step, dim3(sa.B), dim3(256), lds, st, sa);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
 static int beam_enqueue_iter(const BeamJob& j, bool first, int cur) {
   ttx_session* s = j.s;
   hipStream_t st = j.st;
@@ -2297,10 +2336,7 @@ static int beam_enqueue_iter(const BeamJob& j, bool first, int cur) {
                          j.B, j.beam, dl, j.K, j.p.pad_token, j.p.eos_token, s->bs_cand_next.as<int64_t>(), s->bs_logp_next.as<float>(),
                          s->bs_parent.as<int>(), s->bs_parent_draft.as<int>(), s->bs_mark.as<int>(), s->beam_summary.as<int>(),
                          s->bs_len_next.as<int>(), s->bs_fin_next.as<uint8_t>()};
-  const size_t lds = 2 * (size_t)j.beam * (dl + 1) * j.K * 4;
-  TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_beam_select<int>), lds, s->attr_select));
-  hipLaunchKernelGGL(k_beam_select<int>, dim3(j.B), dim3(256), lds, st, sa);
-  HIP_TRY(hipGetLastError());
+  TTX_TRY(launch_beam_select(s, st, sa));
   BeamHost* dev_host = nullptr;
   HIP_TRY(hipHostGetDevicePointer((void**)&dev_host, (void*)s->beam_host, 0));
   hipLaunchKernelGGL(k_bs_publish, dim3(1), dim3(64), 0, st, s->beam_summary.as<int>(), dev_host, s->bs_cnt.as<BeamCounters>());
@@ -2793,10 +2829,7 @@ static int beam_generate_impl(ttx_session* s, const int64_t* d_src, int B, int L
     sa.new_cand = s->bs_cand_next.as<int64_t>(); sa.new_score = s->bs_logp_next.as<float>(); sa.parent = s->bs_parent.as<int>();
     sa.new_len = s->bs_len_next.as<int>(); sa.new_finished = s->bs_fin_next.as<uint8_t>(); sa.parent_draft = s->bs_parent_draft.as<int>();
     sa.summary = s->beam_summary.as<int>();
-    const size_t lds = (size_t)beam * V * 4;
-    TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_beam_step), lds, s->attr_step));
-    hipLaunchKernelGGL(k_beam_step, dim3(B), dim3(256), lds, st, sa);
-    HIP_TRY(hipGetLastError());
+    TTX_TRY(launch_beam_step(s, st, sa));
     hipLaunchKernelGGL(k_bs_publish, dim3(1), dim3(64), 0, st, s->beam_summary.as<int>(), dev_host, s->bs_cnt.as<BeamCounters>());
     HIP_TRY(hipGetLastError());
     return TTX_OK;
@@ -3295,6 +3328,208 @@ extern "C" int ttx_debug_accept_block(ttx_session* s, int32_t* words, int n_word
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipMemcpy(words, s->accept_blk.p, (size_t)n_words * 4, hipMemcpyDeviceToHost));
   return TTX_OK;
+}
+
+// ---- the beam family, one launch each: the caller's operands through the launch_* halves of the enqueue_* helpers -------------
+// Limits the generators enforce before they launch any of these (beam_check_params, beam_start, beam_generate_impl).
+static int dbg_beam_limits(const char* who, int K, int N, int V, int dl) {
+  const std::string w(who);
+  if (K < 1 || K > NUC_MAX_KEEP) return fail(TTX_ERR_INVALID, w + ": n_best must lie in [1, 32]");
+  if (N < 1 || N > BS_MAX_SLOTS) return fail(TTX_ERR_INVALID, w + ": n_drafts must lie in [1, 64]");
+  if (V < 1 || V > 64 * NUC_VPL) return fail(TTX_ERR_INVALID, w + ": V must lie in [1, 1024]");
+  if (dl < 0 || (size_t)K * (dl + 1) > 1023) return fail(TTX_ERR_INVALID, w + ": dl >= 0 and K * (dl + 1) <= 1023 segments");
+  return TTX_OK;
+}
+
+static int dbg_vpl(const char* who, int vpl, int V) {
+  if (vpl != 0 && vpl != 4 && vpl != 8 && vpl != NUC_VPL) return fail(TTX_ERR_INVALID, std::string(who) + ": vpl is 0, 4, 8 or 16");
+  if (vpl != 0 && 64 * vpl < V) return fail(TTX_ERR_INVALID, std::string(who) + ": vpl does not cover V");
+  return TTX_OK;
+}
+
+static int dbg_launched(int rc, hipStream_t st) {
+  const hipError_t e = hipStreamSynchronize(st);
+  TTX_TRY(rc);
+  HIP_TRY(e);
+  return TTX_OK;
+}
+
+extern "C" int ttx_debug_bs_prep(ttx_session* s, const ttx_debug_bs_prep_args* a, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !a) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_bs_prep");
+  if (!a->d_cand_next || !a->d_len_next || !a->d_fin_next || !a->d_logp_next || !a->d_gen || !a->d_front || !a->d_len || !a->d_active ||
+      !a->d_finished || !a->d_logp || !a->d_per_cand || !a->d_drafts32 || (a->smart ? !a->d_lib : !a->d_drafts_all))
+    return fail(TTX_ERR_INVALID, "ttx_debug_bs_prep: a required array is null");
+  if (a->max_cand < 1 || a->n_cand < 0 || a->n_cand > a->max_cand || a->beam < 1 || a->ld < 1)
+    return fail(TTX_ERR_INVALID, "ttx_debug_bs_prep: max_cand, beam and ld must be positive and n_cand in [0, max_cand]");
+  if (a->N < 1 || a->N > BS_MAX_SLOTS || a->dl < 0) return fail(TTX_ERR_INVALID, "ttx_debug_bs_prep: N must lie in [1, 64] and dl >= 0");
+  if (!a->smart && a->dl > a->D0) return fail(TTX_ERR_INVALID, "ttx_debug_bs_prep: dl exceeds the drafts' D0");
+  if (a->smart && (a->n_lib < 1 || a->dl + 1 > a->lib_ld)) return fail(TTX_ERR_INVALID, "ttx_debug_bs_prep: smart mode needs n_lib >= 1 and lib_ld >= dl + 1");
+  HIP_TRY(hipSetDevice(s->m->device));
+  BeamPrepArgs pa{};
+  pa.cand_next = a->d_cand_next; pa.ld = a->ld; pa.len_next = a->d_len_next; pa.fin_next = a->d_fin_next; pa.logp_next = a->d_logp_next;
+  pa.n_cand = a->n_cand; pa.beam = a->beam; pa.dl = a->dl; pa.N = a->N; pa.pad = a->pad;
+  pa.smart = a->smart ? 1 : 0; pa.n_lib = a->n_lib; pa.lib_ld = a->lib_ld; pa.drafts_all = a->d_drafts_all; pa.D0 = a->D0; pa.lib = a->d_lib;
+  pa.gen = a->d_gen; pa.front = a->d_front; pa.len = a->d_len; pa.active = a->d_active; pa.finished = a->d_finished; pa.logp = a->d_logp;
+  pa.per_cand = a->d_per_cand; pa.drafts32 = a->d_drafts32;
+  return dbg_launched(launch_bs_prep(st, a->max_cand, pa), st);
+}
+
+extern "C" int ttx_debug_bs_list(ttx_session* s, const ttx_debug_bs_list_args* a, int64_t* words, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !a || !words) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_bs_list");
+  if (!a->d_active || !a->d_per_cand || !a->d_len || !a->d_act_idx || !a->d_slot_of || !a->d_prev_len || !a->d_summary)
+    return fail(TTX_ERR_INVALID, "ttx_debug_bs_list: a required array is null");
+  if (a->n_cand < 0 || a->N < 1 || a->N > BS_MAX_SLOTS || a->dl < 0) return fail(TTX_ERR_INVALID, "ttx_debug_bs_list: n_cand, dl >= 0 and N in [1, 64]");
+  HIP_TRY(hipSetDevice(s->m->device));
+  struct Image { BeamCounters cnt; DecState st; };
+  Image* dev = nullptr;
+  HIP_TRY(hipMalloc((void**)&dev, sizeof(Image)));
+  Image h{};
+  h.cnt.model_calls = words[0]; h.cnt.input_lines = words[1]; h.cnt.running_rows = words[2]; h.cnt.verified_positions = words[3];
+  h.cnt.executed_positions = words[4]; h.cnt.kv_prefix_positions = words[5]; h.cnt.running_cands = words[6]; h.cnt.max_group = (int)words[7];
+  std::memset(&h.st, 0xAA, sizeof(DecState));          // the kernel writes every word of the DecState
+  hipError_t err = hipMemcpyAsync(dev, &h, sizeof(Image), hipMemcpyHostToDevice, st);
+  int rc = TTX_OK;
+  if (err == hipSuccess) {
+    BeamListArgs la{};
+    la.active = a->d_active; la.per_cand = a->d_per_cand; la.len = a->d_len; la.n_cand = a->n_cand; la.N = a->N; la.dl = a->dl;
+    la.act_idx = a->d_act_idx; la.slot_of = a->d_slot_of; la.prev_len = a->d_prev_len; la.st = &dev->st; la.cnt = &dev->cnt;
+    la.summary = a->d_summary;
+    rc = launch_bs_list(st, la);
+  }
+  if (err == hipSuccess && rc == TTX_OK) err = hipMemcpyAsync(&h, dev, sizeof(Image), hipMemcpyDeviceToHost, st);
+  const hipError_t esync = hipStreamSynchronize(st);
+  (void)hipFree(dev);
+  TTX_TRY(rc);
+  HIP_TRY(err);
+  HIP_TRY(esync);
+  words[0] = h.cnt.model_calls; words[1] = h.cnt.input_lines; words[2] = h.cnt.running_rows; words[3] = h.cnt.verified_positions;
+  words[4] = h.cnt.executed_positions; words[5] = h.cnt.kv_prefix_positions; words[6] = h.cnt.running_cands; words[7] = h.cnt.max_group;
+  const DecState& d = h.st;
+  words[8] = d.n_active; words[9] = d.r_rows; words[10] = d.m_rows; words[11] = d.stop; words[12] = d.width; words[13] = d.steps;
+  words[14] = d.error; words[15] = d.n_copy; words[16] = d.accepted; words[17] = d.produced; words[18] = d.verified_positions;
+  words[19] = d.kv_prefix_positions; words[20] = d.src_positions;
+  return TTX_OK;
+}
+
+extern "C" int ttx_debug_bs_hits(ttx_session* s, const ttx_debug_bs_hits_args* a, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !a) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_bs_hits");
+  if (!a->d_logits || !a->d_finished || !a->d_slot_of || !a->d_per_cand || !a->d_drafts32 || !a->d_hit)
+    return fail(TTX_ERR_INVALID, "ttx_debug_bs_hits: a required array is null");
+  TTX_TRY(dbg_beam_limits("ttx_debug_bs_hits", a->K, a->N, a->V, a->dl));
+  TTX_TRY(dbg_vpl("ttx_debug_bs_hits", a->vpl, a->V));
+  if (a->max_cand < 1 || a->n_cand < 0 || a->n_cand > a->max_cand) return fail(TTX_ERR_INVALID, "ttx_debug_bs_hits: n_cand must lie in [0, max_cand]");
+  HIP_TRY(hipSetDevice(s->m->device));
+  BeamHitsArgs ha{};
+  ha.logits = a->d_logits; ha.V = a->V; ha.finished = a->d_finished; ha.slot_of = a->d_slot_of; ha.per_cand = a->d_per_cand;
+  ha.drafts32 = a->d_drafts32; ha.n_cand = a->n_cand; ha.N = a->N; ha.dl = a->dl; ha.K = a->K; ha.nucleus = BS_NUCLEUS;
+  ha.hit = a->d_hit; ha.dl_of = a->d_dl_of;
+  return dbg_launched(launch_hits_leaves(st, a->max_cand, &ha, nullptr, a->vpl), st);
+}
+
+extern "C" int ttx_debug_bs_leaves(ttx_session* s, const ttx_debug_bs_leaves_args* a, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !a) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_bs_leaves");
+  if (!a->d_logits || !a->d_finished || !a->d_slot_of || !a->d_per_cand || !a->d_drafts32 || !a->d_logp || !a->d_hit || !a->d_best_n ||
+      !a->d_best_slot || !a->d_chosen || !a->d_leaf_score || !a->d_leaf_tok || !a->d_leaf_cnt)
+    return fail(TTX_ERR_INVALID, "ttx_debug_bs_leaves: a required array is null");
+  TTX_TRY(dbg_beam_limits("ttx_debug_bs_leaves", a->K, a->N, a->V, a->dl));
+  TTX_TRY(dbg_vpl("ttx_debug_bs_leaves", a->vpl, a->V));
+  if (a->max_cand < 1 || a->n_cand < 0 || a->n_cand > a->max_cand) return fail(TTX_ERR_INVALID, "ttx_debug_bs_leaves: n_cand must lie in [0, max_cand]");
+  if (!a->d_grp_of != !a->d_cand_batch) return fail(TTX_ERR_INVALID, "ttx_debug_bs_leaves: grp_of and cand_batch come together");
+  if (a->smart && !a->d_grp_of && (a->max_group < 1 || a->max_group > a->N))
+    return fail(TTX_ERR_INVALID, "ttx_debug_bs_leaves: max_group must lie in [1, N]");
+  HIP_TRY(hipSetDevice(s->m->device));
+  BeamCounters* cnt = nullptr;
+  HIP_TRY(hipMalloc((void**)&cnt, sizeof(BeamCounters)));
+  BeamCounters hc{};
+  hc.max_group = a->max_group;
+  const hipError_t err = hipMemcpyAsync(cnt, &hc, sizeof(BeamCounters), hipMemcpyHostToDevice, st);
+  int rc = TTX_OK;
+  if (err == hipSuccess) {
+    BeamLeaves2Args le{};
+    le.logits = a->d_logits; le.V = a->V; le.finished = a->d_finished; le.slot_of = a->d_slot_of; le.per_cand = a->d_per_cand;
+    le.drafts32 = a->d_drafts32; le.logp = a->d_logp; le.hit = a->d_hit; le.cnt = cnt;
+    le.n_cand = a->n_cand; le.N = a->N; le.dl = a->dl; le.K = a->K; le.bos = a->bos; le.pad = a->pad; le.smart = a->smart ? 1 : 0;
+    le.best_n = a->d_best_n; le.best_slot = a->d_best_slot; le.chosen = a->d_chosen;
+    le.leaf_score = a->d_leaf_score; le.leaf_tok = a->d_leaf_tok; le.leaf_cnt = a->d_leaf_cnt;
+    le.live = a->d_live; le.dl_of = a->d_dl_of; le.grp_of = a->d_grp_of; le.cand_batch = a->d_cand_batch;
+    rc = launch_hits_leaves(st, a->max_cand, nullptr, &le, a->vpl);
+  }
+  const hipError_t esync = hipStreamSynchronize(st);
+  (void)hipFree(cnt);
+  TTX_TRY(rc);
+  HIP_TRY(err);
+  HIP_TRY(esync);
+  return TTX_OK;
+}
+
+extern "C" int ttx_debug_beam_select(ttx_session* s, const ttx_debug_beam_select_args* a, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !a) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_beam_select");
+  if (!a->d_leaf_score || !a->d_leaf_tok || !a->d_leaf_cnt || !a->d_cand || !a->d_len || !a->d_chosen || !a->d_chosen_slot ||
+      !a->d_finished || !a->d_new_cand || !a->d_new_logp || !a->d_parent || !a->d_parent_draft || !a->d_mark || !a->d_summary)
+    return fail(TTX_ERR_INVALID, "ttx_debug_beam_select: a required array is null");
+  if (!a->d_new_len != !a->d_new_finished) return fail(TTX_ERR_INVALID, "ttx_debug_beam_select: new_len and new_finished come together");
+  if (a->B < 1 || a->beam < 1 || a->beam > NUC_MAX_KEEP || a->K < 1 || a->K > NUC_MAX_KEEP || a->dl < 0)
+    return fail(TTX_ERR_INVALID, "ttx_debug_beam_select: B >= 1, beam and K in [1, 32], dl >= 0");
+  const size_t nseg = (size_t)a->beam * (a->dl + 1);
+  if (nseg > 1023 || (size_t)a->K * (a->dl + 1) > 1023 || 2 * nseg * a->K * 4 > 150 * 1024)
+    return fail(TTX_ERR_INVALID, "ttx_debug_beam_select: too many leaves per source for the selection kernel's LDS image");
+  if (a->width < 1 || a->width > a->ld_in || a->width > a->ld_out) return fail(TTX_ERR_INVALID, "ttx_debug_beam_select: width must lie in [1, min(ld_in, ld_out)]");
+  HIP_TRY(hipSetDevice(s->m->device));
+  BeamSelectArgs<int> sa{a->d_leaf_score, a->d_leaf_tok, a->d_leaf_cnt, a->d_cand, a->width, a->ld_in, a->ld_out, a->d_len, a->d_chosen,
+                         a->d_chosen_slot, a->d_finished, a->B, a->beam, a->dl, a->K, a->pad, a->eos, a->d_new_cand, a->d_new_logp,
+                         a->d_parent, a->d_parent_draft, a->d_mark, a->d_summary, a->d_new_len, a->d_new_finished};
+  return dbg_launched(launch_beam_select(s, st, sa), st);
+}
+
+extern "C" int ttx_debug_beam_step(ttx_session* s, const ttx_debug_beam_step_args* a, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !a) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_beam_step");
+  if (!a->d_logits || !a->d_slot_of || !a->d_finished || !a->d_score || !a->d_gen || !a->d_new_cand || !a->d_new_score || !a->d_parent ||
+      !a->d_new_len || !a->d_new_finished || !a->d_parent_draft || !a->d_summary)
+    return fail(TTX_ERR_INVALID, "ttx_debug_beam_step: a required array is null");
+  if (a->B < 1 || a->beam < 1 || a->K < 1 || a->V < 1 || a->V > 64 * NUC_VPL) return fail(TTX_ERR_INVALID, "ttx_debug_beam_step: B, beam, K >= 1 and V in [1, 1024]");
+  if ((size_t)a->K > (size_t)a->beam * a->V) return fail(TTX_ERR_INVALID, "ttx_debug_beam_step: K exceeds the beam * V totals");
+  if ((size_t)a->beam * a->V * 4 > 150 * 1024) return fail(TTX_ERR_INVALID, "ttx_debug_beam_step: beam x vocabulary beyond the selection kernel's LDS image");
+  if (a->width < 1 || a->width >= a->ld) return fail(TTX_ERR_INVALID, "ttx_debug_beam_step: width must lie in [1, ld)");
+  HIP_TRY(hipSetDevice(s->m->device));
+  BeamStepArgs sa{};
+  sa.logits = a->d_logits; sa.V = a->V; sa.slot_of = a->d_slot_of; sa.finished = a->d_finished; sa.score = a->d_score;
+  sa.gen = a->d_gen; sa.ld = a->ld; sa.width = a->width; sa.B = a->B; sa.beam = a->beam; sa.K = a->K; sa.pad = a->pad; sa.eos = a->eos;
+  sa.new_cand = a->d_new_cand; sa.new_score = a->d_new_score; sa.parent = a->d_parent; sa.new_len = a->d_new_len;
+  sa.new_finished = a->d_new_finished; sa.parent_draft = a->d_parent_draft; sa.summary = a->d_summary;
+  return dbg_launched(launch_beam_step(s, st, sa), st);
+}
+
+extern "C" int ttx_debug_tree_cache(ttx_session* s, const ttx_debug_tree_cache_args* a, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !a) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_tree_cache");
+  if (!a->d_len || !a->d_parent || !a->d_parent_draft || !a->d_prev_len || !a->d_active || !a->d_k_old || !a->d_v_old || !a->d_k_new ||
+      !a->d_v_new || !a->d_qkv_prev || !a->d_prev_slot_of)
+    return fail(TTX_ERR_INVALID, "ttx_debug_tree_cache: a required array is null");
+  if (!a->d_slot_parent != !a->d_slot_self) return fail(TTX_ERR_INVALID, "ttx_debug_tree_cache: slot_parent and slot_self come together");
+  if (a->d_slot_self && (a->d_k_old != a->d_k_new || a->d_v_old != a->d_v_new))
+    return fail(TTX_ERR_INVALID, "ttx_debug_tree_cache: with slot maps there is one cache buffer");
+  if (a->max_cand < 1 || a->layers < 1 || a->prev_N < 1 || a->prev_N > BS_MAX_SLOTS || a->prev_D < 0 || a->d < 4 || (a->d & 3))
+    return fail(TTX_ERR_INVALID, "ttx_debug_tree_cache: max_cand, layers >= 1, prev_N in [1, 64], prev_D >= 0, d a positive multiple of 4");
+  if ((a->cache_layer_stride & 3) || (a->cache_seq_stride & 3) || (a->qkv_layer_stride & 3) || a->cache_seq_stride < a->d ||
+      a->cache_layer_stride < a->cache_seq_stride || a->qkv_layer_stride < 3 * a->d)
+    return fail(TTX_ERR_INVALID, "ttx_debug_tree_cache: strides must be multiples of 4 floats that cover their rows");
+  if (!dbg_aligned16(a->d_k_old) || !dbg_aligned16(a->d_v_old) || !dbg_aligned16(a->d_k_new) || !dbg_aligned16(a->d_v_new) ||
+      !dbg_aligned16(a->d_qkv_prev))
+    return fail(TTX_ERR_INVALID, "ttx_debug_tree_cache: float operands must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(s->m->device));
+  TreeCacheArgs ca{};
+  ca.len = a->d_len; ca.parent = a->d_parent; ca.parent_draft = a->d_parent_draft; ca.prev_len = a->d_prev_len; ca.active = a->d_active;
+  ca.k_old = a->d_k_old; ca.v_old = a->d_v_old; ca.k_new = a->d_k_new; ca.v_new = a->d_v_new;
+  ca.cache_layer_stride = a->cache_layer_stride; ca.cache_seq_stride = a->cache_seq_stride;
+  ca.qkv_prev = a->d_qkv_prev; ca.qkv_layer_stride = a->qkv_layer_stride; ca.prev_slot_of = a->d_prev_slot_of;
+  ca.prev_N = a->prev_N; ca.prev_D = a->prev_D; ca.d = a->d; ca.slot_parent = a->d_slot_parent; ca.slot_self = a->d_slot_self;
+  return dbg_launched(launch_tree_cache(st, a->max_cand, a->layers, ca), st);
 }
 
 static int kvcopy_debug(const char* who, ttx_session* s, const int32_t* d_rec, int n_copy, const float* d_qkv, int64_t qkv_layer_stride,

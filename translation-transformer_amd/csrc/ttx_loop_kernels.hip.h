@@ -1375,6 +1375,7 @@ struct BeamHitsArgs {
 // position (:539-548, :847-869)?  The positions are independent — only the count of LEADING hits matters, and k_bs_leaves
 // takes it from these flags.  (One workgroup per candidate doing all its pairs kept 20-80 CUs busy for 40-60 us.)
 constexpr int BS_HITS_WAVES = 4;
+constexpr float BS_NUCLEUS = 0.9975f;         // the acceptance nucleus (:539)
 template <int VPL>
 __global__ __launch_bounds__(BS_HITS_WAVES * 64) void k_bs_hits(BeamHitsArgs a) {
   const int c = blockIdx.x;

@@ -348,6 +348,63 @@ class NativeTransformer:
         N.check(self._lib.ttx_debug_accept_block(self._session, words, N.DEBUG_ACCEPT_BLOCK_WORDS, self._stream()))
         return [int(v) for v in words]
 
+    # the beam family, one launch each (include/ttx.h: ttx_debug_bs_prep .. ttx_debug_tree_cache)
+    def _debug_beam(self, struct, entry, scalars: dict, arrays: dict, *extra):
+        """Fill ``struct`` (a ttx_debug_*_args of _native.py) from int scalars and device tensors named as its fields without
+        the ``d_`` prefix (None or absent: a null pointer), and call ``entry``."""
+        a = struct()
+        for name in struct.POINTERS:
+            t = arrays.pop(name[2:], None)
+            setattr(a, name, None if t is None else t.data_ptr())
+        assert not arrays, f"unknown operands {sorted(arrays)}"
+        for name, v in scalars.items():
+            setattr(a, name, int(v))
+        N.check(entry(self._session, C.byref(a), *extra, self._stream()))
+
+    def debug_bs_prep(self, *, ld: int, max_cand: int, n_cand: int, beam: int, dl: int, n: int, pad: int, smart: bool = False,
+                      n_lib: int = 0, lib_ld: int = 0, D0: int = 0, **arrays) -> None:
+        """One k_bs_prep launch (ttx_debug_bs_prep)."""
+        self._debug_beam(N.DebugBsPrepArgs, self._lib.ttx_debug_bs_prep,
+                         dict(ld=ld, max_cand=max_cand, n_cand=n_cand, beam=beam, dl=dl, N=n, pad=pad, smart=smart, n_lib=n_lib,
+                              lib_ld=lib_ld, D0=D0), arrays)
+
+    def debug_bs_list(self, counters, *, n_cand: int, n: int, dl: int, **arrays) -> list:
+        """One k_bs_list launch (ttx_debug_bs_list) on the 8 entry words of the BeamCounters image.  Returns 21 words: the
+        counters as the kernel left them, then the DecState it wrote."""
+        words = (C.c_int64 * N.DEBUG_BS_LIST_WORDS)(*[int(v) for v in counters], *([0] * (N.DEBUG_BS_LIST_WORDS - len(counters))))
+        self._debug_beam(N.DebugBsListArgs, self._lib.ttx_debug_bs_list, dict(n_cand=n_cand, N=n, dl=dl), arrays, words)
+        return [int(v) for v in words]
+
+    def debug_bs_hits(self, *, V: int, max_cand: int, n_cand: int, n: int, dl: int, K: int, vpl: int = 0, **arrays) -> None:
+        """One k_bs_hits launch (ttx_debug_bs_hits); ``vpl`` 0 is the production choice by V."""
+        self._debug_beam(N.DebugBsHitsArgs, self._lib.ttx_debug_bs_hits,
+                         dict(V=V, max_cand=max_cand, n_cand=n_cand, N=n, dl=dl, K=K, vpl=vpl), arrays)
+
+    def debug_bs_leaves(self, *, V: int, max_cand: int, n_cand: int, n: int, dl: int, K: int, bos: int, pad: int, smart: bool = False,
+                        max_group: int = 0, vpl: int = 0, **arrays) -> None:
+        """One k_bs_leaves launch (ttx_debug_bs_leaves)."""
+        self._debug_beam(N.DebugBsLeavesArgs, self._lib.ttx_debug_bs_leaves,
+                         dict(V=V, max_cand=max_cand, n_cand=n_cand, N=n, dl=dl, K=K, bos=bos, pad=pad, smart=smart,
+                              max_group=max_group, vpl=vpl), arrays)
+
+    def debug_beam_select(self, *, width: int, ld_in: int, ld_out: int, B: int, beam: int, dl: int, K: int, pad: int, eos: int,
+                          **arrays) -> None:
+        """One k_beam_select<int> launch (ttx_debug_beam_select)."""
+        self._debug_beam(N.DebugBeamSelectArgs, self._lib.ttx_debug_beam_select,
+                         dict(width=width, ld_in=ld_in, ld_out=ld_out, B=B, beam=beam, dl=dl, K=K, pad=pad, eos=eos), arrays)
+
+    def debug_beam_step(self, *, V: int, ld: int, width: int, B: int, beam: int, K: int, pad: int, eos: int, **arrays) -> None:
+        """One k_beam_step launch (ttx_debug_beam_step)."""
+        self._debug_beam(N.DebugBeamStepArgs, self._lib.ttx_debug_beam_step,
+                         dict(V=V, ld=ld, width=width, B=B, beam=beam, K=K, pad=pad, eos=eos), arrays)
+
+    def debug_tree_cache(self, *, max_cand: int, layers: int, prev_n: int, prev_d: int, d: int, cache_layer_stride: int,
+                         cache_seq_stride: int, qkv_layer_stride: int, **arrays) -> None:
+        """One k_tree_cache launch (ttx_debug_tree_cache); ``slot_parent`` / ``slot_self`` absent: two buffers."""
+        self._debug_beam(N.DebugTreeCacheArgs, self._lib.ttx_debug_tree_cache,
+                         dict(max_cand=max_cand, layers=layers, prev_N=prev_n, prev_D=prev_d, d=d, cache_layer_stride=cache_layer_stride,
+                              cache_seq_stride=cache_seq_stride, qkv_layer_stride=qkv_layer_stride), arrays)
+
     def debug_kvcopy(self, rec: torch.Tensor, n_copy: int, qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
                      n: int, d: int, width: int, B: int) -> None:
         """One k_kvcopy launch (ttx_debug_kvcopy): ``rec`` int32 [B, 5], ``qkv`` fp32 [Ld, B * (1 + n*d), 3 * width], the caches
