@@ -293,6 +293,35 @@ typedef struct ttx_sample_params {
 int ttx_sample_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sample_params* p,
                         int64_t* d_out, ttx_gen_stats* stats, void* stream);
 
+/* Speculative seeded sampling: ttx_sample_generate's samples from the greedy-speculative loop. */
+typedef struct ttx_sample_spec_params {
+  ttx_sample_params sample;              /* as for ttx_sample_generate */
+  int32_t draft_len, n_drafts;           /* copy drafts per source: n_drafts >= 1 windows of 1 <= draft_len <= max_len source tokens */
+  int32_t replace_token;                 /* takes the place of EOS and PAD inside a draft; differs from both */
+  int32_t reserved;                      /* 0 */
+} ttx_sample_spec_params;
+
+/* The loop of ttx_greedy_speculative_generate (copy drafts of the source, 1 + n_drafts * draft_len positions per row and decoder
+ * pass, KV cache, one captured graph per step shape) over R = B * n decoder rows, with the keyed draw of ttx_sample_generate where
+ * the argmax stands.  Rows, keys and the encoder are ttx_sample_generate's; the n rows of a source share its drafts (made once per
+ * source and replicated to the rows).
+ *
+ * The rule.  The sampler is counter-based: the token at position pos of row (key, sample) is a function of that position's logits
+ * and of u(seed, key, sample, pos) alone (steps 2-5 above).  A verify step therefore knows, for every step row, the token the plain
+ * sampler would emit there: step row 0 of a decoder row at front f predicts position f + 1, the row of token j (0-based) of a draft
+ * predicts position f + 2 + j.  A draft token is accepted iff it equals that token; the longest accepted prefix over the drafts is
+ * taken (the first draft wins ties) and the draw after it is written as the bonus token.  Every committed token is thus the plain
+ * sampler's token for the prefix before it: the distribution is exact, and so is the seeding contract (same source, same key,
+ * same samples in any batch, at any n).  The logits of a position come out of a pass over more rows than in ttx_sample_generate, so
+ * their last bits may differ; a row can differ from ttx_sample_generate's only where u falls within that rounding of a CDF boundary.
+ * A row ends with a written EOS or PAD, or when its front reaches max_len - 1; tokens beyond column max_len - 1 are dropped.
+ * d_out int64 [B, n, max_len] as ttx_sample_generate writes it.  stats: model_calls = the steps of the longest row,
+ * accepted_tokens draft tokens accepted, produced_tokens = accepted + one per row and step, src_tokens_padded = B * Ls.
+ * TTX_ERR_INVALID with nothing launched: everything ttx_sample_generate refuses; n_drafts < 1, draft_len outside [1, max_len],
+ * pad, eos and replace tokens not pairwise different, max_len + draft_len + 2 beyond the positional table. */
+int ttx_sample_speculative_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                    const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream);
+
 /* Beam-speculative bookkeeping kernels.
  * ttx_nucleus_mask: mask_with_num_logits_according_nucleus (src/decoding/speculative_decoding.py:871-904): per row of
  *   d_logits [rows,V] keep the best logit and further ones, best first, while the softmax mass ranked above is
@@ -574,6 +603,18 @@ int ttx_debug_argmax(ttx_session* s, const float* d_logits, int V, int32_t* d_pr
 int ttx_debug_sample(ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample, int32_t* d_done,
                      const int32_t* d_front, int32_t* d_pred, const int32_t* d_m, int m_max, const ttx_sample_params* p, void* stream);
 
+/* ttx_debug_sample_step (tests/test_gpu_sample_step_kernel.py): ONE launch of k_sample_step with production's grid (B * (1 + N*D)
+ * rows, 4 per workgroup) on the caller's device operands.  d_logits fp32 [B * (1 + N*D), V] in the step-row layout of
+ * ttx_debug_embed; d_key uint64 [B] and d_sample uint32 [B] by decoder row; d_act_idx int32 [B]; d_front int32 [B].  Row
+ * slot * (1 + N*D) + rs belongs to decoder row b = d_act_idx[slot]; it gets ttx_debug_sample's token for (d_key[b], d_sample[b]) at
+ * position d_front[b] + 1 (rs == 0) or d_front[b] + 2 + (rs - 1) % D.  d_m: live row count on the device, or NULL (all rows; then
+ * n_active == B); rows >= *d_m are not written.  Refused: null pointers, V outside [1, 1024], B, N, D < 1, n_active outside
+ * [0, B], act_idx that are not distinct rows of [0, B), a negative front, *d_m outside [0, n_active * (1 + N*D)], and the parameter
+ * errors of ttx_sample_generate. */
+int ttx_debug_sample_step(ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample,
+                          const int32_t* d_act_idx, const int32_t* d_front, int B, int N, int D, int n_active, int32_t* d_pred,
+                          const int32_t* d_m, const ttx_sample_params* p, void* stream);
+
 /* ttx_debug_embed: k_embed on the caller's embedding table d_table [V, d] and positional table d_pe [pe_rows, d]:
  * X[row] = table[tok] + pe[pos + 1] in fp32, ids outside [0, V) looked up as id 0.  step == 0 (full mode): tok = d_tok[row],
  * pos = row % L, rows [0, rows).  step != 0 (one verify step): slot g < n_active is sequence b = d_act_idx[g] with front f =
@@ -613,6 +654,15 @@ typedef struct ttx_debug_accept_args {
  * runs with 256 threads.  Also refused: null required pointers, n_active outside [0, B], act_idx that are not distinct rows of
  * [0, B), a gen_ld below max_len or too small for front + D + 2 of a running row, row_of outside [0, pool_rows). */
 int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, int64_t* state, void* stream);
+
+/* ttx_debug_sample_accept (tests/test_gpu_sample_accept_kernel.py): ONE launch of k_sample_accept, the accept step of
+ * ttx_sample_speculative_generate, on ttx_debug_accept's argument block and `state`.  greedy, row_rule and pool are 0; d_pred
+ * holds the draws of the step rows; d_haspad int32 [B] holds zeros and is not written.  A running row's tokens j = 0 .. n_acc of
+ * the best draft's draws are written after its front; it ends (rec flags 1, copied to out[row, :max_len], dropped from act_idx)
+ * when a written token in a column below max_len is EOS or PAD or when its new front is >= max_len - 1; width = max(old fronts) +
+ * D + 2; the loop stops when no row runs; error stays as it was.  threads: 0 (256 for B <= 256, else 1024), 256 or 1024; the
+ * kernel takes any B by rounds.  Refusals as for ttx_debug_accept. */
+int ttx_debug_sample_accept(ttx_session* s, const ttx_debug_accept_args* a, int64_t* state, void* stream);
 
 /* ttx_debug_accept_block: the first n_words int32 words of the session's AcceptBlk (csrc/ttx_loop_kernels.hip.h: the sums that
  * k_accept_slots hands k_accept_finish; 264 words), copied to the HOST array `words` after `stream` has drained.  Every word is 0

@@ -101,6 +101,12 @@ class SampleParams(C.Structure):
                 ("seed", C.c_uint64)]
 
 
+class SampleSpecParams(C.Structure):
+    """ttx_sample_spec_params: the sampler's parameters and the copy drafts of the speculative form."""
+    _fields_ = [("sample", SampleParams), ("draft_len", C.c_int32), ("n_drafts", C.c_int32), ("replace_token", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class DebugAcceptArgs(C.Structure):
     """ttx_debug_accept_args: the device arrays and scalars of one k_accept / k_greedy_accept launch."""
     _fields_ = [(n, C.c_void_p) for n in ("d_act_idx", "d_front", "d_gen", "d_drafts", "d_pred", "d_rec", "d_out", "d_haspad",
@@ -181,6 +187,7 @@ SYMBOLS = {
     "ttx_greedy_speculative_generate": (C.c_int, [_VP, _VP, _I, _I, C.POINTER(GenParams), _VP, C.POINTER(GenStats), _VP]),
     "ttx_greedy_generate": (C.c_int, [_VP, _VP, _I, _I, C.POINTER(GenParams), _VP, C.POINTER(GenStats), _VP]),
     "ttx_sample_generate": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SampleParams), _VP, C.POINTER(GenStats), _VP]),
+    "ttx_sample_speculative_generate": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SampleSpecParams), _VP, C.POINTER(GenStats), _VP]),
     "ttx_greedy_speculative_generate_many": (C.c_int, [C.POINTER(_VP), _I, _I, C.POINTER(_VP), C.POINTER(C.c_int),
                                                       C.POINTER(C.c_int), C.POINTER(GenParams), C.POINTER(_VP),
                                                       C.POINTER(GenStats), _VP]),
@@ -220,6 +227,8 @@ SYMBOLS = {
                                     _VP, C.c_int64, _VP, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, _I, _VP]),
     "ttx_debug_argmax": (C.c_int, [_VP, _VP, _I, _VP, _VP, _I, _VP]),
     "ttx_debug_sample": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I, C.POINTER(SampleParams), _VP]),
+    "ttx_debug_sample_step": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, C.POINTER(SampleParams), _VP]),
+    "ttx_debug_sample_accept": (C.c_int, [_VP, C.POINTER(DebugAcceptArgs), C.POINTER(C.c_int64), _VP]),
     "ttx_debug_embed": (C.c_int, [_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _I, _I, _I, _I, _I, _VP]),
     "ttx_debug_accept": (C.c_int, [_VP, C.POINTER(DebugAcceptArgs), C.POINTER(C.c_int64), _VP]),
     "ttx_debug_accept_block": (C.c_int, [_VP, C.POINTER(C.c_int32), _I, _VP]),

@@ -1040,7 +1040,8 @@ struct StepCtx {
   bool want_argmax = true;
   bool want_sample = false;        // sampling loop: k_sample on `sample` where k_argmax would run
   SampleArgs sample{};
-  int variant = GV_BIG;            // GemmVariant of this step's launches (bit-identical results; chosen from the live row count)
+  bool want_sample_step = false;   // speculative sampling loop: k_sample_step on `sample`'s key, sample and prm
+  int variant = GV_BIG;           // GemmVariant of this step's launches (bit-identical results; chosen from the live row count)
   // two-phase verify step of the slot pool; unset (null): the session's state, active list, step QKV buffer and argmax buffer
   DecState* st_ov = nullptr;       // live rows of this pass
   const int* act_ov = nullptr;     // sequences of this pass
@@ -1059,6 +1060,18 @@ static int launch_sample(hipStream_t st, const SampleArgs& a) {
   else if (a.V <= 256) hipLaunchKernelGGL((k_sample<4>), grid, block, 0, st, a);
   else if (a.V <= 512) hipLaunchKernelGGL((k_sample<8>), grid, block, 0, st, a);
   else hipLaunchKernelGGL((k_sample<16>), grid, block, 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+// k_sample_step with the same launch shape and the same choice of VPL.
+static int launch_sample_step(hipStream_t st, const SampleStepArgs& a) {
+  const dim3 grid(cdiv(a.M, 4)), block(256);
+  if (a.V <= 64) hipLaunchKernelGGL((k_sample_step<1>), grid, block, 0, st, a);
+  else if (a.V <= 128) hipLaunchKernelGGL((k_sample_step<2>), grid, block, 0, st, a);
+  else if (a.V <= 256) hipLaunchKernelGGL((k_sample_step<4>), grid, block, 0, st, a);
+  else if (a.V <= 512) hipLaunchKernelGGL((k_sample_step<8>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((k_sample_step<16>), grid, block, 0, st, a);
   HIP_TRY(hipGetLastError());
   return TTX_OK;
 }
@@ -1118,6 +1131,13 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
     a.logits = logits; a.V = V; a.pred = s->pred.as<int>(); a.m_ptr = m_ptr; a.M = Mmax;
     return launch_sample(st, a);
   }
+  if (k.want_sample_step) {
+    SampleStepArgs a{};
+    a.logits = logits; a.V = V; a.pred = s->pred.as<int>(); a.m_ptr = m_ptr; a.M = Mmax;
+    a.key = k.sample.key; a.sample = k.sample.sample; a.prm = k.sample.prm;
+    a.act_idx = act; a.front = s->front.as<int>(); a.N = k.N; a.D = k.D;
+    return launch_sample_step(st, a);
+  }
   if (k.want_argmax) {
     hipLaunchKernelGGL(k_argmax, dim3(cdiv(Mmax, 4)), dim3(256), 0, st, logits, V, k.pred_ov ? k.pred_ov : s->pred.as<int>(), m_ptr, Mmax);
     HIP_TRY(hipGetLastError());
@@ -1144,6 +1164,13 @@ static int launch_accept(hipStream_t st, const LoopArgs& la, int threads) {
   return TTX_OK;
 }
 
+// The accept step of the speculative sampling loop: one workgroup, k_accept's block size.
+static int launch_sample_accept(hipStream_t st, const LoopArgs& la) {
+  hipLaunchKernelGGL(k_sample_accept, dim3(1), dim3(la.B > 256 ? ACCEPT_THREADS : 256), 0, st, la);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
 // The session's AcceptBlk for loops of more than 256 slots (null otherwise, and with TTX_ACCEPT_SPREAD=0): zero when fresh, and
 // left zero by every k_accept_finish.  The choice follows the capacity alone, as k_accept's block size does.
 static int accept_blk_for(ttx_session* s, hipStream_t st, int B, AcceptBlk** out) {
@@ -1160,6 +1187,8 @@ static int launch_accept_and_commit(ttx_session* s, hipStream_t st, const GenCtx
   if (greedy) {
     hipLaunchKernelGGL(k_greedy_accept, dim3(1), dim3(256), 0, st, g.la);
     HIP_TRY(hipGetLastError());
+  } else if (g.la.sample_rule) {
+    TTX_TRY(launch_sample_accept(st, g.la));
   } else {
     TTX_TRY(launch_accept(st, g.la, 0));
   }
@@ -1321,10 +1350,12 @@ static int gen_validate(const ttx_session* s, const int64_t* d_src, int B, int L
 }
 
 // `per_src` > 1 (sampling loop): the B decoder rows are per_src consecutive rows per source, d_src holds B / per_src sources, and
-// the caller sets StepCtx::src_of before the first step.
+// the caller sets StepCtx::src_of before the first step.  `sample_rule` (speculative sampling): the copy drafts of a source are made
+// once and replicated to its per_src decoder rows (k_embed and the accept step keep indexing drafts by decoder row), and the loop
+// runs under LoopArgs::sample_rule.
 static int gen_start(GenJob& j, ttx_session* s, hipStream_t st, const int64_t* d_src, int B, int Ls, const ttx_gen_params* p,
                      int64_t* d_out, ttx_gen_stats* stats, bool greedy, int16_t* d_traj = nullptr, int32_t* d_fin = nullptr,
-                     int per_src = 1) {
+                     int per_src = 1, bool sample_rule = false) {
   const int d = s->m->cfg.embedding_dim, Ld = s->m->cfg.num_decoder_layers;
   const int N = greedy ? 1 : p->n_drafts, D = greedy ? 0 : p->draft_len, D1 = D + 1;
   const int max_len = p->max_len;
@@ -1351,7 +1382,8 @@ static int gen_start(GenJob& j, ttx_session* s, hipStream_t st, const int64_t* d
   need_step_workspaces(s, need, Mmax, (size_t)Bs * Ls);
   TTX_TRY(need.rc);
   AcceptBlk* blk = nullptr;
-  if (!greedy) TTX_TRY(accept_blk_for(s, st, B, &blk));
+  if (!greedy && !sample_rule) TTX_TRY(accept_blk_for(s, st, B, &blk));
+  if (!greedy && per_src > 1) TTX_TRY(ensure(s->smp_drafts, (size_t)Bs * N * D * 4, st));
   s->graphs_current();                                            // captured pointers may be stale
 
   s->ev_used = 0;
@@ -1359,12 +1391,19 @@ static int gen_start(GenJob& j, ttx_session* s, hipStream_t st, const int64_t* d
   // encoder once per batch (:60-61) + cross-attention K/V of every decoder layer once per source
   TTX_TRY(encode_sources(s, st, d_src, 0, Bs, Ls, s->src_valid.as<uint8_t>(), s->memkv.as<float>()));
   // drafts from src[:, 1:] (:64-73): min_draft_len 1, max_draft_len max_len
-  if (!greedy)
-    TTX_TRY(launch_make_drafts<int>(st, s->tok_src.as<int>(), Ls, 1, B, Ls - 1, N, D, p->eos_token, p->pad_token,
-                                    p->replace_token, s->drafts.as<int>()));
+  if (!greedy) {
+    TTX_TRY(launch_make_drafts<int>(st, s->tok_src.as<int>(), Ls, 1, Bs, Ls - 1, N, D, p->eos_token, p->pad_token,
+                                    p->replace_token, per_src > 1 ? s->smp_drafts.as<int>() : s->drafts.as<int>()));
+    if (per_src > 1) {
+      hipLaunchKernelGGL(k_sample_rep_drafts, dim3(cdiv(B * N * D, 256)), dim3(256), 0, st, s->smp_drafts.as<int>(), s->drafts.as<int>(),
+                         B, per_src, N * D);
+      HIP_TRY(hipGetLastError());
+    }
+  }
 
   TTX_TRY(fill_loop_args(s, g, blk));
   g.la.out = s->outbuf.as<int64_t>();
+  g.la.sample_rule = sample_rule ? 1 : 0;
   g.la.row_rule = row_rule ? 1 : 0; g.la.traj = row_rule ? s->traj.as<short>() : nullptr;
   g.la.fin_step = row_rule ? s->fin_step.as<int>() : nullptr;
 
@@ -1411,7 +1450,7 @@ static int gen_launch_step(GenJob& j, int width_bound) {
     s->snap_B = k.B; s->snap_rps = step_rps(k.N, k.D); s->snap_gen_ld = k.gen_ld; s->snap_step = j.launched + 1;
     TTX_TRY(launch_accept_and_commit(s, j.st, j.g, j.greedy));
   } else {
-    const int site = k.want_sample ? GS_STEP_SAMPLE : j.greedy ? GS_STEP_GREEDY : (j.g.la.row_rule ? GS_STEP_ROW_RULE : GS_STEP_SPECULATIVE);
+    const int site = k.want_sample_step ? GS_STEP_SAMPLE_SPEC : k.want_sample ? GS_STEP_SAMPLE : j.greedy ? GS_STEP_GREEDY : (j.g.la.row_rule ? GS_STEP_ROW_RULE : GS_STEP_SPECULATIVE);
     TTX_TRY(graph_replay(s, j.st, s->step_graphs, GraphKey{site, k.B, k.Ls, k.N, k.D, k.max_len, kcap, k.variant, 0}, enqueue));
   }
   ++j.launched;
@@ -1512,6 +1551,7 @@ struct SampleSetup {
   int n;
   const int64_t* d_row_keys;       // [B / n] or null
   SampleBlock blk;
+  bool spec;                       // ttx_sample_speculative_generate: the speculative loop with k_sample_step and k_sample_accept
 };
 
 // Session buffers of the sampling loop, sized before anything is captured.
@@ -1535,7 +1575,8 @@ static int sample_begin(GenJob& j, const SampleSetup& smp) {
   HIP_TRY(hipGetLastError());
   StepCtx& k = j.g.k;
   k.src_of = s->smp_src_of.as<int>();
-  k.want_sample = true;
+  k.want_sample = !smp.spec;
+  k.want_sample_step = smp.spec;
   k.sample.key = s->smp_key.as<unsigned long long>(); k.sample.sample = s->smp_sample.as<unsigned>();
   k.sample.done = s->smp_done.as<int>(); k.sample.front = s->front.as<int>(); k.sample.prm = s->smp_prm.as<SampleBlock>();
   return TTX_OK;
@@ -1557,7 +1598,7 @@ static int generate_common(ttx_session* s, const int64_t* d_src, int B, int Ls, 
   GenJob j;
   if (smp) {
     TTX_TRY(sample_ensure(s, st, (size_t)B));
-    TTX_TRY(gen_start(j, s, st, d_src, B, Ls, p, d_out, stats, greedy, nullptr, nullptr, smp->n));
+    TTX_TRY(gen_start(j, s, st, d_src, B, Ls, p, d_out, stats, greedy, nullptr, nullptr, smp->n, smp->spec));
     TTX_TRY(sample_begin(j, *smp));
   } else {
     TTX_TRY(gen_start(j, s, st, d_src, B, Ls, p, d_out, stats, greedy));
@@ -1623,6 +1664,38 @@ extern "C" int ttx_sample_generate(ttx_session* s, const int64_t* d_src, int B, 
   g.eos_token = p->eos_token; g.replace_token = p->pad_token; g.want_logits = 0;
   if (B <= 0) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
   const int rc = generate_common(s, d_src, B * p->num_samples, Ls, &g, d_out, stats, stream, true, &smp);
+  if (rc == TTX_OK && stats) stats->src_tokens_padded = (long long)B * Ls;    // the encoder ran once per source
+  return rc;
+}
+
+// Speculative seeded sampling: the greedy-speculative loop over R = B * n decoder rows with the keyed draw where the argmax stands
+// (k_sample_step, k_sample_accept).  A draft token is accepted iff it is the token the plain sampler emits at its position, so the
+// committed rows are ttx_sample_generate's.
+extern "C" int ttx_sample_speculative_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                               const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
+  const char* who = "ttx_sample_speculative_generate";
+  if (!s || !p) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
+  const ttx_sample_params& sp = p->sample;
+  if (s->m->cfg.vocab_size > SAMPLE_MAX_V) return fail(TTX_ERR_INVALID, std::string(who) + ": vocabularies above 1024 are not supported");
+  if (sp.num_samples < 1) return fail(TTX_ERR_INVALID, std::string(who) + ": num_samples must be at least 1");
+  SampleSetup smp{};
+  TTX_TRY(sample_block(who, &sp, &smp.blk));
+  if (B <= 0) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
+  // refused with TTX_ERR_INVALID here, whatever code gen_validate would give: nothing of this call is the reference's
+  if (p->n_drafts < 1) return fail(TTX_ERR_INVALID, std::string(who) + ": n_drafts must be at least 1");
+  if (sp.max_len < 1) return fail(TTX_ERR_INVALID, std::string(who) + ": max_len must be positive");
+  if (p->draft_len < 1 || p->draft_len > sp.max_len) return fail(TTX_ERR_INVALID, std::string(who) + ": draft_len must lie in [1, max_len]");
+  if (sp.pad_token == p->replace_token || sp.eos_token == p->replace_token || sp.eos_token == sp.pad_token)
+    return fail(TTX_ERR_INVALID, std::string(who) + ": pad, eos and replace tokens must be pairwise different");
+  const long long R = (long long)B * sp.num_samples;
+  if (R * ((long long)sp.max_len + p->draft_len + 2) >= (1ll << 31) ||
+      R * step_rps(p->n_drafts, p->draft_len) * (long long)s->m->cfg.vocab_size >= (1ll << 31))
+    return fail(TTX_ERR_INVALID, std::string(who) + ": B * num_samples * (max_len + draft_len + 2) and the step's logits must stay below 2^31 elements");
+  smp.n = sp.num_samples; smp.d_row_keys = d_row_keys; smp.spec = true;
+  ttx_gen_params g{};
+  g.max_len = sp.max_len; g.draft_len = p->draft_len; g.n_drafts = p->n_drafts; g.pad_token = sp.pad_token; g.bos_token = sp.bos_token;
+  g.eos_token = sp.eos_token; g.replace_token = p->replace_token; g.want_logits = 0;
+  const int rc = generate_common(s, d_src, (int)R, Ls, &g, d_out, stats, stream, false, &smp);
   if (rc == TTX_OK && stats) stats->src_tokens_padded = (long long)B * Ls;    // the encoder ran once per source
   return rc;
 }
@@ -3149,6 +3222,39 @@ extern "C" int ttx_debug_sample(ttx_session* s, const float* d_logits, int V, co
   return launch_sample(st, a);
 }
 
+extern "C" int ttx_debug_sample_step(ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample,
+                                     const int32_t* d_act_idx, const int32_t* d_front, int B, int N, int D, int n_active,
+                                     int32_t* d_pred, const int32_t* d_m, const ttx_sample_params* p, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !d_logits || !d_key || !d_sample || !d_act_idx || !d_front || !d_pred || !p)
+    return fail(TTX_ERR_INVALID, "null argument to ttx_debug_sample_step");
+  if (V < 1 || V > SAMPLE_MAX_V) return fail(TTX_ERR_INVALID, "ttx_debug_sample_step: V must be in [1, 1024]");
+  if (B < 1 || N < 1 || D < 1 || (long long)B * step_rps(N, D) * V >= (1ll << 31))
+    return fail(TTX_ERR_INVALID, "ttx_debug_sample_step: B, N and D must be positive and the logits below 2^31 elements");
+  if (n_active < 0 || n_active > B) return fail(TTX_ERR_INVALID, "ttx_debug_sample_step: n_active must lie in [0, B]");
+  if (!d_m && n_active != B) return fail(TTX_ERR_INVALID, "ttx_debug_sample_step: without a live row count every slot must be active");
+  SampleBlock blk{};
+  TTX_TRY(sample_block("ttx_debug_sample_step", p, &blk));
+  HIP_TRY(hipSetDevice(s->m->device));
+  const int RPS = step_rps(N, D);
+  int max_front = 0;
+  TTX_TRY(dbg_check_slots("ttx_debug_sample_step", d_act_idx, d_front, B, n_active, 1 << 30, D, st, &max_front));
+  if (d_m) {
+    int32_t m = -1;
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(&m, d_m, 4, hipMemcpyDeviceToHost));
+    if (m < 0 || m > n_active * RPS) return fail(TTX_ERR_INVALID, "ttx_debug_sample_step: the live row count on the device is outside [0, n_active * (1 + N*D)]");
+  }
+  TTX_TRY(ensure(s->smp_prm, sizeof(SampleBlock), st));
+  hipLaunchKernelGGL(k_sample_params, dim3(1), dim3(64), 0, st, s->smp_prm.as<SampleBlock>(), blk);
+  HIP_TRY(hipGetLastError());
+  SampleStepArgs a{};
+  a.logits = d_logits; a.V = V; a.pred = d_pred; a.m_ptr = d_m; a.M = B * RPS;
+  a.key = reinterpret_cast<const unsigned long long*>(d_key); a.sample = d_sample; a.act_idx = d_act_idx; a.front = d_front;
+  a.N = N; a.D = D; a.prm = s->smp_prm.as<SampleBlock>();
+  return launch_sample_step(st, a);
+}
+
 // d_row_map (ttx_debug_embed_select; null: ttx_debug_embed): the launch writes m_rows rows, row i holding layout row d_row_map[i]
 static int embed_debug(ttx_session* s, const float* d_table, int V, const float* d_pe, int pe_rows, int d, float* d_x,
                        const int32_t* d_tok, int rows, int L, const int32_t* d_act_idx, const int32_t* d_front,
@@ -3222,9 +3328,12 @@ extern "C" int ttx_debug_embed_select(ttx_session* s, const float* d_table, int 
                      d_row_map, m_rows, stream);
 }
 
-extern "C" int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, int64_t* state, void* stream) {
+// ttx_debug_accept; `sample`: ttx_debug_sample_accept, k_sample_accept on the same argument block
+static int accept_debug(ttx_session* s, const ttx_debug_accept_args* a, int64_t* state, void* stream, bool sample) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (!s || !a || !state) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_accept");
+  if (sample && (a->greedy || a->row_rule || a->pool))
+    return fail(TTX_ERR_INVALID, "ttx_debug_sample_accept: greedy, row_rule and pool must be 0");
   if (!a->d_act_idx || !a->d_front || !a->d_gen || !a->d_pred || !a->d_rec)
     return fail(TTX_ERR_INVALID, "ttx_debug_accept: act_idx, front, gen, pred and rec are required");
   const bool greedy = a->greedy != 0;
@@ -3297,8 +3406,13 @@ extern "C" int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, 
     la.B = a->B; la.N = a->N; la.D = a->D; la.Ls = a->Ls; la.max_len = a->max_len; la.pad = a->pad; la.bos = a->bos; la.eos = a->eos;
     // threads = 0 is the production route: above 256 slots the pair, unless TTX_ACCEPT_SPREAD=0
     int rc_blk = TTX_OK;
-    if (!greedy && a->threads == 0) rc_blk = accept_blk_for(s, st, a->B, &la.blk);
+    la.sample_rule = sample ? 1 : 0;
+    if (!greedy && !sample && a->threads == 0) rc_blk = accept_blk_for(s, st, a->B, &la.blk);
     if (rc_blk != TTX_OK) err = hipErrorOutOfMemory;
+    else if (sample) {
+      if (a->threads == 0) { if (launch_sample_accept(st, la) != TTX_OK) err = hipErrorLaunchFailure; }
+      else { hipLaunchKernelGGL(k_sample_accept, dim3(1), dim3(a->threads), 0, st, la); err = hipGetLastError(); }
+    }
     else if (greedy) { hipLaunchKernelGGL(k_greedy_accept, dim3(1), dim3(256), 0, st, la); err = hipGetLastError(); }
     else if (launch_accept(st, la, a->threads) != TTX_OK) err = hipErrorLaunchFailure;
   }
@@ -3317,6 +3431,14 @@ extern "C" int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, 
   HIP_TRY(err);
   HIP_TRY(esync);
   return TTX_OK;
+}
+
+extern "C" int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, int64_t* state, void* stream) {
+  return accept_debug(s, a, state, stream, false);
+}
+
+extern "C" int ttx_debug_sample_accept(ttx_session* s, const ttx_debug_accept_args* a, int64_t* state, void* stream) {
+  return accept_debug(s, a, state, stream, true);
 }
 
 extern "C" int ttx_debug_accept_block(ttx_session* s, int32_t* words, int n_words, void* stream) {

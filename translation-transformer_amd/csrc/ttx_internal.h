@@ -77,8 +77,10 @@ enum AttnKernelId { AK_ATTN = 1, AK_ATTN2 = 2, AK_ATTN3 = 3, AK_ATTN3S = 4, AK_A
 //                                 1 probe, 2 draft pass + accept, 3 accept alone; 4, 5, 6: the same three under draft select; else 0)
 //   GS_BEAM_ITER, GS_BEAM_POOL_ITER   see beam_launch_iter / bpool_launch_iter
 //   GS_STEP_SAMPLE                the greedy step's key with k_sample in k_argmax's place (ttx_sample_generate); B counts decoder rows
+//   GS_STEP_SAMPLE_SPEC           the speculative step's key with k_sample_step and k_sample_accept in k_argmax's and k_accept's place
+//                                 (ttx_sample_speculative_generate); B counts decoder rows
 enum GraphSite { GS_STEP_SPECULATIVE = 0, GS_STEP_GREEDY = 1, GS_STEP_ROW_RULE = 2, GS_STEP_POOL = 3, GS_BEAM_ITER = 4, GS_BEAM_POOL_ITER = 5,
-                 GS_STEP_SAMPLE = 6 };
+                 GS_STEP_SAMPLE = 6, GS_STEP_SAMPLE_SPEC = 7 };
 typedef std::vector<int> GraphKey;
 
 // Captured graphs of one family of keys.  A key runs eagerly the first time it is seen (`warmed`: function attributes are set
@@ -133,7 +135,8 @@ struct GraphCache {
   /* beam-speculative source pool (continuous batching over sources of many batches) */                                          \
   X(bp_row_of) X(bp_batch) X(bp_cand) X(bp_cand_len) X(bp_tok) X(bp_new_slot) X(bp_io) X(bp_grp) X(bp_src_acc) X(bp_enc_qkv)            \
   /* sampling loop (ttx_sample_generate): per decoder row its key, sample id, done flag and source row; the call's SampleBlock */ \
-  X(smp_key) X(smp_sample) X(smp_done) X(smp_src_of) X(smp_prm)
+  /* speculative form: the copy drafts per source [B][N][D], before they are replicated to the decoder rows */                   \
+  X(smp_key) X(smp_sample) X(smp_done) X(smp_src_of) X(smp_prm) X(smp_drafts)
 #define TTX_DECLARE_BUF(name) Buf name;
 #define TTX_REGISTER_BUF(name) all.push_back(&name);
 

@@ -149,6 +149,9 @@ struct LoopArgs {
   const int* exec_rows;
   // accept in two launches (k_accept_slots, k_accept_finish): the block-wide sums between them; null: k_accept alone
   struct AcceptBlk* blk;
+  // speculative sampling (k_sample_accept; 0 everywhere else): `pred` holds the keyed draw of every step row, a row ends on EOS, on
+  // PAD or at max_len - 1, and the output starts as the plain sampler's (BOS in column 0)
+  int sample_rule;
 };
 struct PoolIo { int64_t* out; short* traj; int* fin_step; int traj_ld; int pad_; };
 
@@ -166,7 +169,7 @@ __global__ void k_loop_init(LoopArgs a) {
   const int tid = blockIdx.x * blockDim.x + threadIdx.x;
   const int total = a.B * a.gen_ld;
   for (int i = tid; i < total; i += gridDim.x * blockDim.x) a.gen[i] = (i % a.gen_ld == 0) ? a.bos : a.pad;
-  for (int i = tid; i < a.B * a.max_len; i += gridDim.x * blockDim.x) a.out[i] = a.pad;
+  for (int i = tid; i < a.B * a.max_len; i += gridDim.x * blockDim.x) a.out[i] = (a.sample_rule && i % a.max_len == 0) ? a.bos : a.pad;
   for (int i = tid; i < a.B; i += gridDim.x * blockDim.x) {
     a.act_idx[i] = i; a.front[i] = 0; a.haspad[i] = 0;
     if (a.row_rule) a.fin_step[i] = 0;
@@ -215,15 +218,11 @@ __device__ __forceinline__ void accept_slot_commit(const LoopArgs& a, const DecS
   a.rec[slot] = CopyRec{b, best, bacc, f, flags};
 }
 
-// The per-slot part of an accept step: verify the slot's drafts against the argmax tokens, write the longest accepted prefix
-// plus one bonus token, advance the front, record the trajectory and the copy record.  Needs nothing of the other slots.
-__device__ __forceinline__ SlotStep accept_slot(const LoopArgs& a, const DecState* st, int slot) {
-  const int RPS = step_rps(a.N, a.D);
-  const int b = a.act_idx[slot];
-  const int f = a.front[b];
-  const int* ps = a.pred + (size_t)slot * RPS;       // predictions of the slot's step rows
+// The draft of row b with the longest leading run of tokens equal to the predictions `ps` of its slot's step rows, and that run's
+// length; the first draft wins ties.  Shared by accept_slot and sample_accept_slot (there `ps` holds the keyed draws).
+__device__ __forceinline__ void accept_best_draft(const LoopArgs& a, int b, const int* ps, int& best, int& bacc) {
   // prediction made at position f + j on draft n: row 0 for j = 0, else row 1 + n*D + (j-1)
-  int best = 0, bacc = -1;
+  best = 0; bacc = -1;
   for (int n = 0; n < a.N; ++n) {
     const int* dr = a.drafts + ((size_t)b * a.N + n) * a.D;
     const int* pr = ps + 1 + n * a.D - 1;            // pr[j] = prediction at position f + j for j >= 1
@@ -234,6 +233,17 @@ __device__ __forceinline__ SlotStep accept_slot(const LoopArgs& a, const DecStat
       if (dr[j] != (j == 0 ? ps[0] : pr[j])) acc = j;
     if (acc > bacc) { bacc = acc; best = n; }
   }
+}
+
+// The per-slot part of an accept step: verify the slot's drafts against the argmax tokens, write the longest accepted prefix
+// plus one bonus token, advance the front, record the trajectory and the copy record.  Needs nothing of the other slots.
+__device__ __forceinline__ SlotStep accept_slot(const LoopArgs& a, const DecState* st, int slot) {
+  const int RPS = step_rps(a.N, a.D);
+  const int b = a.act_idx[slot];
+  const int f = a.front[b];
+  const int* ps = a.pred + (size_t)slot * RPS;       // predictions of the slot's step rows
+  int best, bacc;
+  accept_best_draft(a, b, ps, best, bacc);
   const int* pr = ps + 1 + best * a.D - 1;
   int* g = a.gen + (size_t)b * a.gen_ld;
   bool fin = false, sawpad = false;
@@ -439,6 +449,62 @@ __global__ __launch_bounds__(ACCEPT_THREADS) void k_accept_finish(LoopArgs a) {
   AcceptBlk* k = a.blk;
   accept_finish(a, st, Bc, k->maxfront, k->nfin, k->finlist, (long long)k->acc, (long long)k->prefix);
   accept_blk_clear(k, threadIdx.x);                  // every read of the block lies before accept_finish's last barrier
+}
+
+// ------------------------------------------------------------------------------------------------
+// Accept step of speculative sampling (ttx_sample_speculative_generate).  `pred` holds, for every step row, the token the plain
+// sampler emits at that row's position from that row's logits (k_sample_step), so a draft token is accepted iff it equals it and
+// the committed sequence is the plain sampler's.  Per slot: accept_best_draft, the accepted prefix plus the bonus token, the
+// front, the copy record.  A row ends (flags 1) when a written token in a column below max_len is EOS or PAD, or when its front
+// reaches max_len - 1; drafts hold neither EOS nor PAD, so an ending token is the last one written.  No haspad, no error, no
+// batch-coupled width.
+__device__ __forceinline__ SlotStep sample_accept_slot(const LoopArgs& a, int slot) {
+  const int RPS = step_rps(a.N, a.D);
+  const int b = a.act_idx[slot];
+  const int f = a.front[b];
+  const int* ps = a.pred + (size_t)slot * RPS;
+  int best, bacc;
+  accept_best_draft(a, b, ps, best, bacc);
+  const int* pr = ps + 1 + best * a.D - 1;
+  int* g = a.gen + (size_t)b * a.gen_ld;
+  bool fin = false;
+  for (int j = 0; j <= bacc; ++j) {
+    const int t = (j == 0) ? ps[0] : pr[j];
+    g[f + 1 + j] = t;                                // f + 1 + D < gen_ld; columns at or beyond max_len are dropped at copy-out
+    fin |= (t == a.eos || t == a.pad) && f + 1 + j < a.max_len;
+  }
+  const int nf = f + bacc + 1;
+  fin |= nf >= a.max_len - 1;
+  a.front[b] = nf;
+  a.rec[slot] = CopyRec{b, best, bacc, f, fin ? 1 : 0};
+  return SlotStep{b, f, bacc, fin};
+}
+
+// One block, any slot count by rounds of blockDim.x.  The rest of the step is accept_finish as it runs under the per-row rule: it
+// copies max_len columns of every ended row out, keeps the rows with flags 0 in order, sums the counters, stops when nobody runs
+// and publishes.  haspad stays zero on this path (k_loop_init), so accept_finish raises no error here.
+__global__ __launch_bounds__(ACCEPT_THREADS) void k_sample_accept(LoopArgs a) {
+  __shared__ int s_maxfront, s_nfin;
+  __shared__ int s_finlist[256];
+  __shared__ long long s_acc, s_prefix;
+  DecState* st = a.st;
+  const int Bc = st->n_active;
+  if (Bc == 0) return;
+  if (threadIdx.x == 0) { s_maxfront = 0; s_acc = 0; s_prefix = 0; s_nfin = 0; }
+  __syncthreads();
+  for (int slot = threadIdx.x; slot < Bc; slot += blockDim.x) {
+    const SlotStep r = sample_accept_slot(a, slot);
+    atomicMax(&s_maxfront, r.f);
+    atomicAdd((unsigned long long*)&s_acc, (unsigned long long)r.bacc);
+    atomicAdd((unsigned long long*)&s_prefix, (unsigned long long)r.f);
+    if (r.fin) {
+      const int k = atomicAdd(&s_nfin, 1);
+      if (k < 256) s_finlist[k] = r.b;
+    }
+  }
+  __syncthreads();
+  a.row_rule = 1; a.pool = 0; a.exec_rows = nullptr;
+  accept_finish(a, st, Bc, s_maxfront, s_nfin, s_finlist, s_acc, s_prefix);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@
 //      an id is its lane's exclusive scan value plus the lane's running sum.  Filter on: the scan alone, over the ranks.
 //   7  the token is eos or pad: done[r] = 1.
 // Rows at or beyond *m_ptr are not written.  Rows outside the contract (NaN, +inf, all -inf) give some id in [0, V).
+// k_sample_step is steps 2-6 (sample_row, shared with k_sample) on the rows of a speculative verify step: see its comment below.
 #pragma once
 #include "ttx_loop_kernels.hip.h"
 
@@ -133,19 +134,11 @@ __device__ __forceinline__ void sample_topk_to_lanes(const float* __restrict__ p
   }
 }
 
+// Steps 2-6 of the rule for one logits row `p` of V <= 64 * VPL values, by one wave: the token of row (key, sample) at position `pos`.
+// Shared by k_sample and k_sample_step, so that both emit the same token from the same bits.  Every lane returns the token.
 template <int VPL>
-__global__ __launch_bounds__(256) void k_sample(const SampleArgs a) {
-  const int rows = a.m_ptr ? *a.m_ptr : a.M;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;                  // wave-uniform
-  const int lane = threadIdx.x & 63;
-  const SampleBlock prm = *a.prm;
-  if (a.done[row]) {                        // wave-uniform
-    if (lane == 0) a.pred[row] = prm.pad;
-    return;
-  }
-  const int V = a.V;
-  const float* p = a.logits + (size_t)row * V;
+__device__ __forceinline__ int sample_row(const float* __restrict__ p, int V, const SampleBlock& prm, unsigned long long key,
+                                          unsigned sample, unsigned pos, int lane) {
   int tok;
   if (prm.greedy) {
     // k_argmax, statement for statement
@@ -163,7 +156,7 @@ __global__ __launch_bounds__(256) void k_sample(const SampleArgs a) {
     }
     tok = (bi < V) ? bi : 0;
   } else {
-    const float u = sample_uniform(prm.seed, a.key[row], a.sample[row], (unsigned)(a.front[0] + 1));
+    const float u = sample_uniform(prm.seed, key, sample, pos);
     if (prm.top_k > 0) {
       int my_idx, n_kept;
       float my_val, m;
@@ -213,10 +206,64 @@ __global__ __launch_bounds__(256) void k_sample(const SampleArgs a) {
     }
     if ((unsigned)tok >= (unsigned)V) tok = 0;   // rows outside the contract only: never an id outside [0, V)
   }
+  return tok;
+}
+
+template <int VPL>
+__global__ __launch_bounds__(256) void k_sample(const SampleArgs a) {
+  const int rows = a.m_ptr ? *a.m_ptr : a.M;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;                  // wave-uniform
+  const int lane = threadIdx.x & 63;
+  const SampleBlock prm = *a.prm;
+  if (a.done[row]) {                        // wave-uniform
+    if (lane == 0) a.pred[row] = prm.pad;
+    return;
+  }
+  const int tok = sample_row<VPL>(a.logits + (size_t)row * a.V, a.V, prm, a.key[row], a.sample[row], (unsigned)(a.front[0] + 1), lane);
   if (lane == 0) {
     a.pred[row] = tok;
     if (tok == prm.eos || tok == prm.pad) a.done[row] = 1;
   }
+}
+
+// The sampler on the rows of a speculative verify step (ttx_sample_speculative_generate), in the step-row layout of k_embed<true>:
+// row = slot * RPS + rs belongs to decoder row b = act_idx[slot] at front f = front[b]; rs == 0 predicts position f + 1, row
+// rs = 1 + n * D + j (token j of draft n, at position f + 1 + j) predicts position f + 2 + j.  The token is sample_row's for
+// (key[b], sample[b], that position): what k_sample emits there from the same logits.  key and sample are indexed by decoder row,
+// not by slot (the active list compacts).  k_argmax's launch shape and live-row rule; no done flags (rows retire through the
+// active list); rows at or beyond *m_ptr are not written.
+struct SampleStepArgs {
+  const float* logits; int V;      // [M, V]
+  int* pred;                       // [M]
+  const int* m_ptr; int M;         // live rows on the device (null: M)
+  const unsigned long long* key;   // [B]
+  const unsigned* sample;          // [B]
+  const int* act_idx;              // [n_active]
+  const int* front;                // [B]
+  int N, D;
+  const SampleBlock* prm;
+};
+
+template <int VPL>
+__global__ __launch_bounds__(256) void k_sample_step(const SampleStepArgs a) {
+  const int rows = a.m_ptr ? *a.m_ptr : a.M;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;                  // wave-uniform
+  const int lane = threadIdx.x & 63;
+  const SampleBlock prm = *a.prm;
+  const int RPS = step_rps(a.N, a.D);
+  const int rs = row % RPS;
+  const int b = a.act_idx[row / RPS];
+  const int pos = a.front[b] + (rs == 0 ? 1 : 2 + (rs - 1) % a.D);
+  const int tok = sample_row<VPL>(a.logits + (size_t)row * a.V, a.V, prm, a.key[b], a.sample[b], (unsigned)pos, lane);
+  if (lane == 0) a.pred[row] = tok;
+}
+
+// Copy drafts of the sampling loop: the n decoder rows of a source share its drafts.  in [B, nd] -> out [B * n, nd].
+__global__ void k_sample_rep_drafts(const int* in, int* out, int R, int n, int nd) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < R * nd) out[i] = in[(size_t)(i / nd / n) * nd + i % nd];
 }
 
 }  // namespace ttx

@@ -394,6 +394,60 @@ class TranslationInferenceSampling(_ScoresHypotheses):
         return self._scored(src, out, return_scores)
 
 
+class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
+    """``TranslationInferenceSampling``'s samples from the greedy-speculative loop: copy drafts of the source are verified
+    ``1 + n_drafts * draft_len`` positions per decoder pass, and a draft token is accepted iff it is the token the plain sampler
+    emits at its position (the sampler is counter-based, so that token is defined for every row of a verify step).  The
+    committed rows are therefore the plain sampler's, under the same seeding contract: sample ``j`` of a source depends on
+    (seed, the source's row key, j, position) and on the source alone.  The whole loop runs in
+    ttx_sample_speculative_generate.  A row can differ from the plain sampler's only where its uniform falls within fp32
+    rounding of a CDF boundary (the two loops form a position's logits in passes over different row counts)."""
+
+    def __init__(self, model, max_len: int, draft_len: int, n_drafts: int, pad_token: int, bos_token: int, eos_token: int,
+                 replace_token: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, num_samples: int = 1,
+                 seed: int = 0) -> None:
+        super().__init__(model, max_len, pad_token, bos_token, eos_token, temperature, top_k, top_p, num_samples, seed)
+        self.draft_len, self.n_drafts, self.replace_token = int(draft_len), int(n_drafts), int(replace_token)
+        self.accepted_tokens_num = 0
+        self.stats_total = {"accepted_tokens": 0, "produced_tokens": 0, "verified_positions": 0, "kv_prefix_positions": 0,
+                            "src_positions": 0, "encode_ms": 0.0, "decode_ms": 0.0, "src_tokens_padded": 0, "batches": 0}
+        self.last_stats: N.GenStats | None = None
+
+    def __str__(self):
+        return (f"Speculative sampling (draft_len={self.draft_len}, n_drafts={self.n_drafts}, temperature={self.temperature}, "
+                f"top_k={self.top_k}, top_p={self.top_p}, num_samples={self.num_samples}, seed={self.seed}, max_len={self.max_len})")
+
+    def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False):
+        """Long[B, num_samples, max_len]; ``row_keys`` and ``return_scores`` as for ``TranslationInferenceSampling.generate``."""
+        m, n = self.model, self.num_samples
+        src = src.to(m.device, torch.int64).contiguous()
+        m.check_tokens(src)
+        B, Ls = src.shape
+        keys = None
+        if row_keys is not None:
+            keys = torch.as_tensor(row_keys, dtype=torch.int64).to(m.device).contiguous()
+            if keys.shape != (B,):
+                raise ValueError(f"row_keys must hold one key per source ({B}), got shape {tuple(keys.shape)}")
+        p = N.SampleSpecParams(N.SampleParams(self.max_len, n, self.temperature, self.top_k, self.top_p, self.pad_token,
+                                              self.bos_token, self.eos_token, self.seed & 0xFFFFFFFFFFFFFFFF),
+                               self.draft_len, self.n_drafts, self.replace_token, 0)
+        out = torch.empty((B, max(n, 1), max(self.max_len, 1)), dtype=torch.int64, device=m.device)
+        st = N.GenStats()
+        N.check(m._lib.ttx_sample_speculative_generate(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
+                                                       C.byref(p), out.data_ptr(), C.byref(st), m._stream()))
+        self.model_calls_num += int(st.model_calls)
+        self.accepted_tokens_num += int(st.accepted_tokens)
+        self.given_tokens += int((src != m.src_pad_token_i).sum())
+        t = self.stats_total
+        for k in ("accepted_tokens", "produced_tokens", "verified_positions", "kv_prefix_positions", "src_positions", "encode_ms",
+                  "decode_ms"):
+            t[k] += getattr(st, k)
+        t["src_tokens_padded"] += B * Ls
+        t["batches"] += 1
+        self.last_stats = st
+        return self._scored(src, out, return_scores)
+
+
 class TranslationInferenceBeamSearch(_ScoresHypotheses):
     """Drop-in for src/decoding/standard_decoding.py:58-174:the whole loop runs in ttx_beam_generate (per-hypothesis KV
     cache, encoder and cross K/V once per source, log-softmax + top-beam + row assembly in one kernel per step)."""

@@ -184,16 +184,18 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         self.model = WeightContainer(self.src_vocab_size, self.tgt_vocab_size, num_encoder_layers, num_decoder_layers,
                                      embedding_dim, num_heads, feedforward_dim, share_embeddings,
                                      self.src_pad_token_i, self.tgt_pad_token_i, activation)
-        if generation not in ("greedy", "beam_search", "greedy_speculative", "beam_search_speculative", "sampling"):
-            options = ", ".join(["beam_search", "greedy", "greedy_speculative", "beam_search_speculative", "sampling"])
+        if generation not in ("greedy", "beam_search", "greedy_speculative", "beam_search_speculative", "sampling",
+                              "sampling_speculative"):
+            options = ", ".join(["beam_search", "greedy", "greedy_speculative", "beam_search_speculative", "sampling",
+                                 "sampling_speculative"])
             raise ValueError(f'Unknown generation option {generation}. Options are {options}.')
-        if generation == "greedy_speculative":
+        if generation in ("greedy_speculative", "sampling_speculative"):
             assert draft_len > 0, "Number of speculative tokens must be a positive integer."
         self.native: NativeTransformer | None = None
         self.generator = None
         self._ahead = None
         self._scores_on = False
-        # generation="sampling": reactions predicted so far in this predict run; a reaction's running index is its row key, so
+        # generation="sampling" and "sampling_speculative": reactions predicted so far in this predict run; a reaction's running index is its row key, so
         # its samples do not depend on the batch size or on what shares its batch
         self._predict_rows = 0
         # batches decoded ahead of predict_step (0: decode every batch inside its own predict_step like the reference);
@@ -267,6 +269,11 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             return D.TranslationInferenceSampling(m, max_len=h.max_len, temperature=h.sampling_temperature, top_k=h.sampling_top_k,
                                                   top_p=h.sampling_top_p, num_samples=max(1, h.beam_size), seed=h.sampling_seed,
                                                   **common)
+        if h.generation == "sampling_speculative":   # the same samples from the speculative loop
+            return D.TranslationInferenceSamplingSpeculative(
+                m, max_len=h.max_len, draft_len=h.draft_len, n_drafts=h.n_drafts, replace_token=self.tgt_tokenizer.encoder_dict["c"],
+                temperature=h.sampling_temperature, top_k=h.sampling_top_k, top_p=h.sampling_top_p, num_samples=max(1, h.beam_size),
+                seed=h.sampling_seed, **common)
         return D.TranslationInferenceBeamSearchSpeculative(
             m, vocab_size=self.tgt_vocab_size, max_len=h.max_len, n_best=h.beam_size, draft_len=h.draft_len,
             n_drafts=h.n_drafts, C_token=self.tgt_tokenizer.encoder_dict["c"], smart_drafts_mode=h.smart_drafts_mode, **common)
@@ -279,7 +286,7 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         pred = None
         if ahead is not None and dataloader_idx == 0:
             pred = ahead.take(batch["src_tokens"], batch_idx)
-        if pred is None and self.hparams.generation == "sampling":
+        if pred is None and self.hparams.generation in ("sampling", "sampling_speculative"):
             B = int(batch["src_tokens"].shape[0])
             pred = self.generator.generate(batch["src_tokens"], row_keys=torch.arange(self._predict_rows, self._predict_rows + B))
             self._predict_rows += B
@@ -402,6 +409,12 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
                 report["accepted_tokens"] = self.generator.accepted_tokens_num
                 report["acceptance_rate"] = round(self.generator.accepted_tokens_num /
                                                   max(1, self.generator.produced_non_pad_tokens), 4)
+        if h.generation == "sampling_speculative":
+            report["n_drafts"] = h.n_drafts
+            report["draft_len"] = h.draft_len
+            report["accepted_tokens"] = self.generator.accepted_tokens_num
+            report["acceptance_rate"] = round(self.generator.accepted_tokens_num /
+                                              max(1, self.generator.stats_total["produced_tokens"]), 4)
         if self._scores_on:
             report["scoring_seconds"] = round(self._scoring_seconds, 6)
             report["mean_top1_logprob"] = round(float(self._top1_sum) / max(1, self._top1_n), 6)

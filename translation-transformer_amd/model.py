@@ -313,6 +313,18 @@ class NativeTransformer:
                                            done.data_ptr(), front.data_ptr(), pred.data_ptr(), self._ptr(m_live), int(m_max),
                                            C.byref(p), self._stream()))
 
+    def debug_sample_step(self, logits: torch.Tensor, key: torch.Tensor, sample: torch.Tensor, act_idx: torch.Tensor,
+                          front: torch.Tensor, pred: torch.Tensor, *, B: int, n: int, d: int, n_active: int,
+                          m_live: torch.Tensor | None = None, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                          pad: int = 0, eos: int = 2, seed: int = 0) -> None:
+        """One k_sample_step launch (ttx_debug_sample_step): ``logits`` fp32 [B * (1 + n*d), V] contiguous in the step-row layout,
+        ``key`` int64 [B] (read as uint64) and ``sample`` int32 [B] (read as uint32) by decoder row, ``act_idx`` / ``front`` int32
+        [B], ``pred`` int32 [B * (1 + n*d)], ``m_live`` an int32 device scalar or None."""
+        p = N.SampleParams(1, 1, float(temperature), int(top_k), float(top_p), int(pad), 0, int(eos), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        N.check(self._lib.ttx_debug_sample_step(self._session, logits.data_ptr(), int(logits.shape[1]), key.data_ptr(),
+                                                sample.data_ptr(), act_idx.data_ptr(), front.data_ptr(), int(B), int(n), int(d),
+                                                int(n_active), pred.data_ptr(), self._ptr(m_live), C.byref(p), self._stream()))
+
     def debug_embed(self, table: torch.Tensor, pe: torch.Tensor, x: torch.Tensor, tok: torch.Tensor | None = None, rows: int = 0,
                     L: int = 0, act_idx: torch.Tensor | None = None, front: torch.Tensor | None = None,
                     gen: torch.Tensor | None = None, drafts: torch.Tensor | None = None, B: int = 0, n: int = 1, d: int = 0,
@@ -326,7 +338,7 @@ class NativeTransformer:
 
     def debug_accept(self, state, *, B: int, n: int, d: int, Ls: int, max_len: int, pad: int, bos: int, eos: int, gen_ld: int,
                      greedy: bool = False, threads: int = 0, row_rule: bool = False, pool: bool = False, traj_ld: int = 0,
-                     pool_rows: int = 0, **arrays) -> list:
+                     pool_rows: int = 0, _entry: str = "ttx_debug_accept", **arrays) -> list:
         """One k_accept (``greedy``: k_greedy_accept) launch (ttx_debug_accept).  ``state``: the 13 entry words of the DecState
         (include/ttx.h); ``arrays``: device tensors named as the fields of ttx_debug_accept_args without the ``d_`` prefix.
         Returns the 17 exit words: the DecState the kernel left and the four words it published for the host."""
@@ -339,8 +351,15 @@ class NativeTransformer:
         a.B, a.N, a.D, a.Ls, a.max_len, a.pad, a.bos, a.eos = int(B), int(n), int(d), int(Ls), int(max_len), int(pad), int(bos), int(eos)
         a.greedy, a.threads = int(greedy), int(threads)
         words = (C.c_int64 * N.DEBUG_ACCEPT_STATE_WORDS)(*[int(v) for v in state], *([0] * (N.DEBUG_ACCEPT_STATE_WORDS - len(state))))
-        N.check(self._lib.ttx_debug_accept(self._session, C.byref(a), words, self._stream()))
+        N.check(getattr(self._lib, _entry)(self._session, C.byref(a), words, self._stream()))
         return [int(v) for v in words]
+
+    def debug_sample_accept(self, state, *, B: int, n: int, d: int, Ls: int, max_len: int, pad: int, bos: int, eos: int, gen_ld: int,
+                            threads: int = 0, **arrays) -> list:
+        """One k_sample_accept launch (ttx_debug_sample_accept), the accept step of speculative sampling: ``debug_accept``'s
+        ``state``, exit words and ``arrays`` (act_idx, front, gen, drafts, pred, rec, out, and haspad holding zeros)."""
+        return self.debug_accept(state, B=B, n=n, d=d, Ls=Ls, max_len=max_len, pad=pad, bos=bos, eos=eos, gen_ld=gen_ld,
+                                 threads=threads, _entry="ttx_debug_sample_accept", **arrays)
 
     def debug_accept_block(self) -> list:
         """The int32 words of the session's AcceptBlk (ttx_debug_accept_block): all zero between accept steps."""
