@@ -33,12 +33,3 @@ extern "C" int ttx_host_drive(int n, int serial, int watchdog_s, const int* scri
   *stalled_job = r.stalled_job;
   return r.rc;
 }
-
-// wait_published: published() holds from the `after`-th look on (never: after < 0).  Returns 1 when it published in time.
-extern "C" int ttx_host_wait_published(int watchdog_s, long long after, double* seconds) {
-  const auto t0 = std::chrono::steady_clock::now();
-  long long looks = 0;
-  const bool ok = ttx::wait_published(watchdog_s, [&] { return after >= 0 && ++looks > after; });
-  *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return ok ? 1 : 0;
-}

@@ -22,9 +22,7 @@ def drv(tmp_path_factory):
     out = tmp_path_factory.mktemp("drive") / "libdrive.so"
     subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", f"-I{CSRC}", "-o", str(out), str(ROOT / "tests" / "host" / "drive_host.cpp")],
                    check=True)
-    lib = ctypes.CDLL(str(out))
-    lib.ttx_host_wait_published.argtypes = [ctypes.c_int, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double)]
-    return lib
+    return ctypes.CDLL(str(out))
 
 
 def drive(drv, scripts, serial=False, watchdog_s=WATCHDOG_S, cap=4096):
@@ -75,11 +73,3 @@ def test_progress_resets_the_wait(drv):
     # the same job beside one that waits 1.3 s in one piece: that one is hung, whatever the other does meanwhile
     r = drive(drv, [[wait_ms(600), PROGRESSED, wait_ms(600), FINISHED], [wait_ms(1300), FINISHED]])
     assert (r["rc"], r["hung"], r["stalled_job"]) == (0, True, 1)
-
-
-def test_wait_published(drv):
-    seconds = ctypes.c_double()
-    assert drv.ttx_host_wait_published(WATCHDOG_S, 0, ctypes.byref(seconds)) == 1
-    assert drv.ttx_host_wait_published(WATCHDOG_S, 200000, ctypes.byref(seconds)) == 1 and seconds.value < WATCHDOG_S
-    assert drv.ttx_host_wait_published(WATCHDOG_S, -1, ctypes.byref(seconds)) == 0
-    assert WATCHDOG_S <= seconds.value < WATCHDOG_S + 1.0

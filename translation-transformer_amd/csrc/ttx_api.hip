@@ -1354,8 +1354,8 @@ static int gen_validate(const ttx_session* s, const int64_t* d_src, int B, int L
 // once and replicated to its per_src decoder rows (k_embed and the accept step keep indexing drafts by decoder row), and the loop
 // runs under LoopArgs::sample_rule.
 static int gen_start(GenJob& j, ttx_session* s, hipStream_t st, const int64_t* d_src, int B, int Ls, const ttx_gen_params* p,
-                     int64_t* d_out, ttx_gen_stats* stats, bool greedy, int16_t* d_traj = nullptr, int32_t* d_fin = nullptr,
-                     int per_src = 1, bool sample_rule = false) {
+                     int64_t* d_out, ttx_gen_stats* stats, bool greedy, int16_t* d_traj, int32_t* d_fin, int per_src,
+                     bool sample_rule) {
   const int d = s->m->cfg.embedding_dim, Ld = s->m->cfg.num_decoder_layers;
   const int N = greedy ? 1 : p->n_drafts, D = greedy ? 0 : p->draft_len, D1 = D + 1;
   const int max_len = p->max_len;
@@ -1457,6 +1457,35 @@ static int gen_launch_step(GenJob& j, int width_bound) {
   return TTX_OK;
 }
 
+// The last thing a job enqueues: the end of the decode phase (ev_c), the `bytes` counters at `d_counters` into the pinned
+// host_state, and ev_done, which the job's turn polls before it reads them.
+static int enqueue_readback(ttx_session* s, hipStream_t st, const void* d_counters, size_t bytes) {
+  HIP_TRY(hipEventRecord(s->ev_c, st));
+  HIP_TRY(hipMemcpyAsync(s->host_state, d_counters, bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipEventRecord(s->ev_done, st));
+  return TTX_OK;
+}
+
+// The counters a finished job read back, added to `st` (a single batch starts from zeroes).
+static void add_counters(ttx_gen_stats& st, const DecState& hs) {
+  st.model_calls += hs.steps;
+  st.accepted_tokens += hs.accepted;
+  st.produced_tokens += hs.produced;
+  st.verified_positions += hs.verified_positions;
+  st.kv_prefix_positions += hs.kv_prefix_positions;
+  st.src_positions += hs.src_positions;
+}
+
+static void add_counters(ttx_beam_stats& st, const BeamCounters& cn) {
+  st.model_calls += cn.model_calls;
+  st.input_lines += cn.input_lines;
+  st.running_rows += cn.running_rows;
+  st.verified_positions += cn.verified_positions;
+  st.executed_positions += cn.executed_positions;
+  st.kv_prefix_positions += cn.kv_prefix_positions;
+  st.running_candidates += cn.running_cands;
+}
+
 static int gen_finish_enqueue(GenJob& j) {
   ttx_session* s = j.s;
   const StepCtx& k = j.g.k;
@@ -1471,9 +1500,7 @@ static int gen_finish_enqueue(GenJob& j) {
       HIP_TRY(hipMemcpyAsync(j.d_fin, s->fin_step.p, (size_t)k.B * 4, hipMemcpyDeviceToDevice, j.st));
     }
   }
-  HIP_TRY(hipEventRecord(s->ev_c, j.st));
-  HIP_TRY(hipMemcpyAsync(s->host_state, s->state.as<DecState>(), sizeof(DecState), hipMemcpyDeviceToHost, j.st));
-  HIP_TRY(hipEventRecord(s->ev_done, j.st));
+  TTX_TRY(enqueue_readback(s, j.st, s->state.p, sizeof(DecState)));
   j.phase = 2;
   return TTX_OK;
 }
@@ -1520,12 +1547,8 @@ static int gen_finish_collect(GenJob& j) {
   ttx_session* s = j.s;
   const DecState& hs = *s->host_state;
   if (j.stats) {
-    j.stats->model_calls = hs.steps;
-    j.stats->accepted_tokens = hs.accepted;
-    j.stats->produced_tokens = hs.produced;
-    j.stats->verified_positions = hs.verified_positions;
-    j.stats->kv_prefix_positions = hs.kv_prefix_positions;
-    j.stats->src_positions = hs.src_positions;
+    *j.stats = ttx_gen_stats{};
+    add_counters(*j.stats, hs);
     j.stats->src_tokens_padded = (long long)j.g.k.B * j.g.k.Ls;
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, s->ev_a, s->ev_b));
@@ -1582,51 +1605,64 @@ static int sample_begin(GenJob& j, const SampleSetup& smp) {
   return TTX_OK;
 }
 
-static int generate_common(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_gen_params* p, int64_t* d_out,
-                           ttx_gen_stats* stats, void* stream, bool greedy, const SampleSetup* smp = nullptr) {
+// The batches of one generate call (validated by the caller) under drive_sessions: each session decodes the next batch of the list
+// whenever it has finished one; a turn enqueues the next verify step of a session that has published its previous one (one step
+// in flight per session, no stream synchronisation inside the loop).  `greedy` and `smp` are the single-session calls'.
+static int generate_batches(ttx_session** sessions, int n_sessions, int n_batches, const int64_t* const* d_src, const int* B,
+                            const int* Ls, const ttx_gen_params* p, int64_t* const* d_out, int16_t* const* d_traj,
+                            int32_t* const* d_fin, ttx_gen_stats* stats, void* stream, bool greedy, const SampleSetup* smp) {
+  std::vector<GenJob> jobs(n_sessions);
+  const int D1 = greedy ? 1 : p->draft_len + 1;
+  int next = 0, rc_batch = TTX_OK;               // next batch of the list; the first error a batch's own result carried
+  const auto turn = [&](int i) -> int {
+    GenJob& j = jobs[i];
+    ttx_session* s = sessions[i];
+    volatile HostInfo* hi = s->host_info;
+    if (j.phase == 0) {
+      if (next >= n_batches) return TURN_FINISHED;
+      j.batch = next++;
+      if (smp) TTX_TRY(sample_ensure(s, s->own_stream, (size_t)B[j.batch]));
+      TTX_TRY(gen_start(j, s, s->own_stream, d_src[j.batch], B[j.batch], Ls[j.batch], p, d_out[j.batch], stats ? &stats[j.batch] : nullptr,
+                        greedy, d_traj ? d_traj[j.batch] : nullptr, d_traj ? d_fin[j.batch] : nullptr, smp ? smp->n : 1, smp && smp->spec));
+      if (smp) TTX_TRY(sample_begin(j, *smp));
+      return TURN_PROGRESSED;
+    }
+    if (j.phase == 1) {
+      // loop init publishes no step: the stream has run it once it is idle; from then on the accept kernel publishes
+      if (j.launched == 0 ? hipStreamQuery(s->own_stream) != hipSuccess : (!hi->stop && hi->steps_done < j.launched)) return TURN_WAITING;
+      if (hi->stop) {                            // set by the accept kernel (or by loop init): nothing further to enqueue
+        TTX_TRY(gen_finish_enqueue(j));
+        return TURN_PROGRESSED;
+      }
+      if (j.launched > p->max_len + 2) return fail(TTX_ERR_HIP, "decode loop failed to terminate");
+      TTX_TRY(gen_launch_step(j, hi->width + D1));
+      return TURN_PROGRESSED;
+    }
+    if (hipEventQuery(s->ev_done) != hipSuccess) return TURN_IDLE;
+    const int rc = gen_finish_collect(j);        // a batch the reference fails on does not end the other batches
+    if (rc_batch == TTX_OK) rc_batch = rc;
+    return TURN_PROGRESSED;
+  };
+  const int rc = drive_sessions(sessions, n_sessions, false, stream, [](int) { return TTX_OK; }, turn);
+  return rc != TTX_OK ? rc : rc_batch;      // what ended the call (a hang, a failed launch) before what a batch reported
+}
+
+// A single-session generate call: one session, one batch.
+static int generate_one(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_gen_params* p, int64_t* d_out,
+                        ttx_gen_stats* stats, void* stream, bool greedy, const SampleSetup* smp = nullptr) {
   TTX_TRY(gen_validate(s, d_src, B, Ls, p, d_out, greedy));
-  TTX_TRY(session_alive(s));
-  HIP_TRY(hipSetDevice(s->m->device));
-  release_retired();
-  // The loop runs on the session's own stream (the caller's may be the legacy null stream, which cannot be
-  // captured into a graph); it first waits for the caller's stream, and the call returns only after the
-  // session stream has drained, so the outputs are visible to whatever the caller enqueues next.
-  TTX_TRY(ensure_own_stream(s));
-  HIP_TRY(hipEventRecord(s->ev_done, (hipStream_t)stream));
-  HIP_TRY(hipStreamWaitEvent(s->own_stream, s->ev_done, 0));
-  hipStream_t st = s->own_stream;
-  GenJob j;
-  if (smp) {
-    TTX_TRY(sample_ensure(s, st, (size_t)B));
-    TTX_TRY(gen_start(j, s, st, d_src, B, Ls, p, d_out, stats, greedy, nullptr, nullptr, smp->n, smp->spec));
-    TTX_TRY(sample_begin(j, *smp));
-  } else {
-    TTX_TRY(gen_start(j, s, st, d_src, B, Ls, p, d_out, stats, greedy));
-  }
-  const int D1 = j.g.k.D + 1;
-  // One step in flight: the next step is enqueued as soon as the accept kernel has published the previous one's
-  // result to the host-mapped words (no stream synchronisation inside the loop).
-  volatile HostInfo* hi = s->host_info;
-  HIP_TRY(hipStreamSynchronize(st));            // loop init published (also covers max_len <= 1: stop already set)
-  while (!hi->stop) {
-    if (j.launched > p->max_len + 2) return fail(TTX_ERR_HIP, "decode loop failed to terminate");
-    TTX_TRY(gen_launch_step(j, hi->width + D1));
-    if (!wait_published(watchdog_seconds(), [&] { return hi->steps_done >= j.launched || hi->stop; })) return session_hung(s);
-  }
-  TTX_TRY(gen_finish_enqueue(j));
-  HIP_TRY(hipStreamSynchronize(st));
-  return gen_finish_collect(j);
+  return generate_batches(&s, 1, 1, &d_src, &B, &Ls, p, &d_out, nullptr, nullptr, stats, stream, greedy, smp);
 }
 
 extern "C" int ttx_greedy_speculative_generate(ttx_session* s, const int64_t* d_src, int B, int Ls,
                                                const ttx_gen_params* p, int64_t* d_out, ttx_gen_stats* stats,
                                                void* stream) {
-  return generate_common(s, d_src, B, Ls, p, d_out, stats, stream, false);
+  return generate_one(s, d_src, B, Ls, p, d_out, stats, stream, false);
 }
 
 extern "C" int ttx_greedy_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_gen_params* p,
                                    int64_t* d_out, ttx_gen_stats* stats, void* stream) {
-  return generate_common(s, d_src, B, Ls, p, d_out, stats, stream, true);
+  return generate_one(s, d_src, B, Ls, p, d_out, stats, stream, true);
 }
 
 // The SampleBlock of a call, or TTX_ERR_INVALID: temperature >= 0 and finite (0: greedy), top_k 0 or 1..32, top_p in (0, 1].  A call
@@ -1663,7 +1699,7 @@ extern "C" int ttx_sample_generate(ttx_session* s, const int64_t* d_src, int B, 
   g.max_len = p->max_len; g.draft_len = 0; g.n_drafts = 1; g.pad_token = p->pad_token; g.bos_token = p->bos_token;
   g.eos_token = p->eos_token; g.replace_token = p->pad_token; g.want_logits = 0;
   if (B <= 0) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
-  const int rc = generate_common(s, d_src, B * p->num_samples, Ls, &g, d_out, stats, stream, true, &smp);
+  const int rc = generate_one(s, d_src, B * p->num_samples, Ls, &g, d_out, stats, stream, true, &smp);
   if (rc == TTX_OK && stats) stats->src_tokens_padded = (long long)B * Ls;    // the encoder ran once per source
   return rc;
 }
@@ -1695,7 +1731,7 @@ extern "C" int ttx_sample_speculative_generate(ttx_session* s, const int64_t* d_
   ttx_gen_params g{};
   g.max_len = sp.max_len; g.draft_len = p->draft_len; g.n_drafts = p->n_drafts; g.pad_token = sp.pad_token; g.bos_token = sp.bos_token;
   g.eos_token = sp.eos_token; g.replace_token = p->replace_token; g.want_logits = 0;
-  const int rc = generate_common(s, d_src, (int)R, Ls, &g, d_out, stats, stream, false, &smp);
+  const int rc = generate_one(s, d_src, (int)R, Ls, &g, d_out, stats, stream, false, &smp);
   if (rc == TTX_OK && stats) stats->src_tokens_padded = (long long)B * Ls;    // the encoder ran once per source
   return rc;
 }
@@ -1982,10 +2018,7 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
         n_act += take;
       }
       if (n_act == 0) {
-        if (hipEventRecord(s->ev_c, j.st) != hipSuccess ||
-            hipMemcpyAsync(s->host_state, s->state.as<DecState>(), sizeof(DecState), hipMemcpyDeviceToHost, j.st) != hipSuccess ||
-            hipEventRecord(s->ev_done, j.st) != hipSuccess)
-          return fail(TTX_ERR_HIP, "slot pool: enqueueing the final state read-back failed");
+        TTX_TRY(enqueue_readback(s, j.st, s->state.p, sizeof(DecState)));
         j.phase = 2;
       } else {
         if (j.launched > (long long)(p->max_len + 2) * (R_total + 1)) return fail(TTX_ERR_HIP, "decode loop failed to terminate");
@@ -1996,12 +2029,7 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
     if (hipEventQuery(s->ev_done) != hipSuccess) return TURN_IDLE;
     const DecState& hs = *s->host_state;
     if (stats) {
-      stats->model_calls += hs.steps;
-      stats->accepted_tokens += hs.accepted;
-      stats->produced_tokens += hs.produced;
-      stats->verified_positions += hs.verified_positions;
-      stats->kv_prefix_positions += hs.kv_prefix_positions;
-      stats->src_positions += hs.src_positions;
+      add_counters(*stats, hs);
       stats->src_tokens_padded += j.src_tokens_padded;
       collect_gemm_profile(s, j.st);
       float ms = 0.f;
@@ -2025,9 +2053,7 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
   return rc;
 }
 
-// Several batches in flight on one GPU: each session, on its own stream, decodes the next batch of the list
-// whenever it has finished one; a turn enqueues the next verify step of a session that has published its previous one.
-// Outputs per batch are identical to the one-at-a-time call.
+// Several batches in flight on one GPU: outputs per batch are identical to the one-at-a-time call.
 static int generate_many_impl(ttx_session** sessions, int n_sessions, int n_batches, const int64_t* const* d_src, const int* B,
                               const int* Ls, const ttx_gen_params* p, int64_t* const* d_out, int16_t* const* d_traj,
                               int32_t* const* d_fin, ttx_gen_stats* stats, void* stream) {
@@ -2038,38 +2064,7 @@ static int generate_many_impl(ttx_session** sessions, int n_sessions, int n_batc
       if (!d_traj[i] || !d_fin || !d_fin[i]) return fail(TTX_ERR_INVALID, "missing trace buffer for a batch");
   for (int i = 0; i < n_batches; ++i) TTX_TRY(gen_validate(sessions[0], d_src[i], B[i], Ls[i], p, d_out[i], false));
   if (sessions[0]->profile) n_sessions = 1;      // profiling: one batch at a time, so that an event pair times its own launch
-  std::vector<GenJob> jobs(n_sessions);
-  const int D1 = p->draft_len + 1;
-  int next = 0, rc_batch = TTX_OK;               // next batch of the list; the first error a batch's own result carried
-  const auto turn = [&](int i) -> int {
-    GenJob& j = jobs[i];
-    ttx_session* s = sessions[i];
-    volatile HostInfo* hi = s->host_info;
-    if (j.phase == 0) {
-      if (next >= n_batches) return TURN_FINISHED;
-      j.batch = next++;
-      TTX_TRY(gen_start(j, s, s->own_stream, d_src[j.batch], B[j.batch], Ls[j.batch], p, d_out[j.batch], stats ? &stats[j.batch] : nullptr,
-                        false, d_traj ? d_traj[j.batch] : nullptr, d_traj ? d_fin[j.batch] : nullptr));
-      return TURN_PROGRESSED;
-    }
-    if (j.phase == 1) {
-      // loop init publishes no step: the stream has run it once it is idle; from then on the accept kernel publishes
-      if (j.launched == 0 ? hipStreamQuery(s->own_stream) != hipSuccess : (!hi->stop && hi->steps_done < j.launched)) return TURN_WAITING;
-      if (hi->stop) {                            // set by the accept kernel (or by loop init): nothing further to enqueue
-        TTX_TRY(gen_finish_enqueue(j));
-        return TURN_PROGRESSED;
-      }
-      if (j.launched > p->max_len + 2) return fail(TTX_ERR_HIP, "decode loop failed to terminate");
-      TTX_TRY(gen_launch_step(j, hi->width + D1));
-      return TURN_PROGRESSED;
-    }
-    if (hipEventQuery(s->ev_done) != hipSuccess) return TURN_IDLE;
-    const int rc = gen_finish_collect(j);        // a batch the reference fails on does not end the other batches
-    if (rc_batch == TTX_OK) rc_batch = rc;
-    return TURN_PROGRESSED;
-  };
-  const int rc = drive_sessions(sessions, n_sessions, false, stream, [](int) { return TTX_OK; }, turn);
-  return rc != TTX_OK ? rc : rc_batch;      // what ended the call (a hang, a failed launch) before what a batch reported
+  return generate_batches(sessions, n_sessions, n_batches, d_src, B, Ls, p, d_out, d_traj, d_fin, stats, stream, false, nullptr);
 }
 
 extern "C" int ttx_greedy_speculative_generate_many(ttx_session** sessions, int n_sessions, int n_batches,
@@ -2469,22 +2464,13 @@ static int beam_finish_enqueue(BeamJob& j) {
   if (j.width > j.p.max_len) return fail(TTX_ERR_HIP, "beam-speculative loop: result wider than max_len (internal error)");
   HIP_TRY(hipMemcpy2DAsync(j.d_out, (size_t)j.p.max_len * 8, s->bs_cand_next.p, (size_t)j.gen_ld * 8, (size_t)j.width * 8,
                            (size_t)j.B * j.K, hipMemcpyDeviceToDevice, j.st));
-  HIP_TRY(hipEventRecord(s->ev_c, j.st));
-  HIP_TRY(hipMemcpyAsync(s->host_state, s->bs_cnt.p, sizeof(BeamCounters), hipMemcpyDeviceToHost, j.st));
-  HIP_TRY(hipEventRecord(s->ev_done, j.st));
+  TTX_TRY(enqueue_readback(s, j.st, s->bs_cnt.p, sizeof(BeamCounters)));
   j.phase = 2;
   return TTX_OK;
 }
 
 static void beam_collect(BeamJob& j) {
-  const BeamCounters* cn = reinterpret_cast<const BeamCounters*>(j.s->host_state);
-  j.acc.model_calls = cn->model_calls;
-  j.acc.input_lines = cn->input_lines;
-  j.acc.running_rows = cn->running_rows;
-  j.acc.verified_positions = cn->verified_positions;
-  j.acc.executed_positions = cn->executed_positions;
-  j.acc.kv_prefix_positions = cn->kv_prefix_positions;
-  j.acc.running_candidates = cn->running_cands;
+  add_counters(j.acc, *reinterpret_cast<const BeamCounters*>(j.s->host_state));    // beam_start zeroed them
   j.acc.src_tokens_padded = (int64_t)j.B * j.Ls;
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, j.s->ev_a, j.s->ev_b) == hipSuccess) j.acc.encode_ms = ms;
@@ -2509,7 +2495,7 @@ extern "C" int ttx_beam_speculative_generate_many(ttx_session** sessions, int n_
   if (sessions[0]->profile) n_sessions = 1;      // profiling: one batch at a time (see the greedy driver)
   const int n_jobs = std::min(n_sessions, n_batches);
   std::vector<BeamJob> jobs(n_jobs);
-  int next = 0, rc_batch = TTX_OK;               // as in generate_many_impl
+  int next = 0, rc_batch = TTX_OK;               // as in generate_batches
   const auto turn = [&](int i) -> int {
     BeamJob& j = jobs[i];
     ttx_session* s = sessions[i];
@@ -2541,8 +2527,7 @@ extern "C" int ttx_beam_speculative_generate(ttx_session* s, const int64_t* d_sr
   int64_t* outs[1] = {d_out};
   ttx_session* ss[1] = {s};
   if (!s) return fail(TTX_ERR_INVALID, "null session");
-  const int rc = ttx_beam_speculative_generate_many(ss, 1, 1, srcs, &B, &Ls, p, outs, stats ? stats : &local, stream);
-  return rc;
+  return ttx_beam_speculative_generate_many(ss, 1, 1, srcs, &B, &Ls, p, outs, stats ? stats : &local, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2785,10 +2770,7 @@ extern "C" int ttx_beam_speculative_generate_pool(ttx_session** sessions, int n_
         n_running += take;
       }
       if (n_live == 0) {
-        if (hipEventRecord(s->ev_c, j.st) != hipSuccess ||
-            hipMemcpyAsync(s->host_state, s->bs_cnt.p, sizeof(BeamCounters), hipMemcpyDeviceToHost, j.st) != hipSuccess ||
-            hipEventRecord(s->ev_done, j.st) != hipSuccess)
-          return fail(TTX_ERR_HIP, "batch pool: enqueueing the final counter read-back failed");
+        TTX_TRY(enqueue_readback(s, j.st, s->bs_cnt.p, sizeof(BeamCounters)));
         j.phase = 2;
       } else {
         if (j.launched > (long long)(trace_cap + 2) * (R_total + 1)) return fail(TTX_ERR_HIP, "batch pool failed to terminate");
@@ -2801,14 +2783,7 @@ extern "C" int ttx_beam_speculative_generate_pool(ttx_session** sessions, int n_
       return TURN_PROGRESSED;
     }
     if (hipEventQuery(s->ev_done) != hipSuccess) return TURN_IDLE;
-    const BeamCounters* cn = reinterpret_cast<const BeamCounters*>(s->host_state);
-    acc.model_calls += cn->model_calls;
-    acc.input_lines += cn->input_lines;
-    acc.running_rows += cn->running_rows;
-    acc.verified_positions += cn->verified_positions;
-    acc.executed_positions += cn->executed_positions;
-    acc.kv_prefix_positions += cn->kv_prefix_positions;
-    acc.running_candidates += cn->running_cands;
+    add_counters(acc, *reinterpret_cast<const BeamCounters*>(s->host_state));
     acc.src_tokens_padded += j.src_tokens_padded;
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, s->ev_a, s->ev_c) == hipSuccess) acc.decode_ms += ms;
@@ -2824,23 +2799,23 @@ extern "C" int ttx_beam_speculative_generate_pool(ttx_session** sessions, int n_
 // ------------------------------------------------------------------------------------------------
 // Standard beam search, whole loop native (standard_decoding.py:89-174): per-hypothesis KV cache (the tree kernels),
 // the verify-step kernels with one row per running hypothesis, k_beam_step for log-softmax + top-beam + row assembly.
-static int beam_generate_impl(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_beam_search_params* p, int64_t* d_out,
-                              ttx_beam_search_stats* stats, void* stream);
+struct BeamSearchJob {
+  ttx_session* s = nullptr;
+  hipStream_t st = nullptr;
+  ttx_beam_search_params p{};
+  int B = 0, Ls = 0, K = 0, MC = 0, ld = 0, Lc = 0;
+  BeamHost* dev_host = nullptr;    // device address of the session's pinned summary words
+  int n_cand = 0, beam = 1, width = 1, cur = 0, launched = 0;   // loop scalars
+  int n_eos = 0;             // hypotheses holding EOS after the previous iteration
+  int phase = 0;             // 0 not started, 1 iteration in flight, 2 finishing
+  int64_t* d_out = nullptr;
+};
 
-extern "C" int ttx_beam_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_beam_search_params* p, int64_t* d_out,
-                                 ttx_beam_search_stats* stats, void* stream) {
-  const int rc = beam_generate_impl(s, d_src, B, Ls, p, d_out, stats, stream);
-  // an error return must not leave work of this call in flight on the session's stream (the caller may free d_src / d_out)
-  if (rc != TTX_OK && s && !s->dead && s->own_stream) (void)hipStreamSynchronize(s->own_stream);
-  return rc;
-}
-
-static int beam_generate_impl(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_beam_search_params* p, int64_t* d_out,
-                              ttx_beam_search_stats* stats, void* stream) {
-  if (!s || !d_src || !p || !d_out || !stats || B <= 0 || Ls <= 1) return fail(TTX_ERR_INVALID, "bad argument to ttx_beam_generate");
-  TTX_TRY(session_alive(s));
-  const ttx_model* m = s->m;
-  const ttx_config& c = m->cfg;
+// Everything of the call behind the argument check: the reference's asserts and this library's limits, the workspaces, the
+// encoder and the <BOS> hypotheses.
+static int bsearch_start(BeamSearchJob& j, ttx_session* s, hipStream_t st, const int64_t* d_src, int B, int Ls,
+                         const ttx_beam_search_params* p, int64_t* d_out) {
+  const ttx_config& c = s->m->cfg;
   const int K = p->beam_size, max_len = p->max_len, V = c.vocab_size;
   if (max_len <= 1) return fail(TTX_ERR_REFERENCE, "assert self.max_len > 1 (standard_decoding.py:79)");
   if (K <= 0) return fail(TTX_ERR_REFERENCE, "assert self.beam_size > 0 (standard_decoding.py:80)");
@@ -2848,13 +2823,9 @@ static int beam_generate_impl(ttx_session* s, const int64_t* d_src, int B, int L
   if ((size_t)K * V * 4 > 150 * 1024) return fail(TTX_ERR_INVALID, "beam_size x vocabulary beyond the selection kernel's LDS image");
   if (p->pad_token != c.pad_token) return fail(TTX_ERR_INVALID, "generator pad token differs from the model's");
   if (max_len + 2 > c.max_positions) return fail(TTX_ERR_INVALID, "max_len exceeds the positional table");
-  HIP_TRY(hipSetDevice(m->device));
-  release_retired();
-  TTX_TRY(ensure_own_stream(s));
+  j = BeamSearchJob{};
+  j.s = s; j.st = st; j.p = *p; j.B = B; j.Ls = Ls; j.K = K; j.d_out = d_out;
   s->ev_used = 0;                     // profiling sessions: the event pairs of this call start from the first one
-  HIP_TRY(hipEventRecord(s->ev_done, (hipStream_t)stream));
-  HIP_TRY(hipStreamWaitEvent(s->own_stream, s->ev_done, 0));
-  hipStream_t st = s->own_stream;
   const int d = c.embedding_dim, Ld = c.num_decoder_layers;
   const int MC = B * K, ld = max_len + 2, Lc = max_len + 2;
   const size_t Mmax = (size_t)MC;
@@ -2875,8 +2846,7 @@ static int beam_generate_impl(ttx_session* s, const int64_t* d_src, int B, int L
   if (!s->beam_host && hipHostMalloc((void**)&s->beam_host, sizeof(BeamHost), hipHostMallocMapped) != hipSuccess)
     return fail(TTX_ERR_NOMEM, "hipHostMalloc failed");
   std::memset(s->beam_host, 0, sizeof(BeamHost));
-  BeamHost* dev_host = nullptr;
-  HIP_TRY(hipHostGetDevicePointer((void**)&dev_host, (void*)s->beam_host, 0));
+  HIP_TRY(hipHostGetDevicePointer((void**)&j.dev_host, (void*)s->beam_host, 0));
   // self.model(src, y) of the first step = encoder + the decoder on <BOS>; the reference then re-encodes the source once per
   // beam (:120-124): identical rows, so the beams of a source share its memory row here
   TTX_TRY(encode_sources(s, st, d_src, 0, B, Ls, s->src_valid.as<uint8_t>(), s->memkv.as<float>()));
@@ -2884,52 +2854,78 @@ static int beam_generate_impl(ttx_session* s, const int64_t* d_src, int B, int L
                      s->bs_fin_next.as<uint8_t>(), s->bs_logp_next.as<float>(), s->bs_parent.as<int>(), s->bs_parent_draft.as<int>(),
                      MC, B, p->bos_token, p->pad_token, s->bs_cnt.as<BeamCounters>());
   HIP_TRY(hipGetLastError());
-
-  int n_cand = B, beam = 1, width = 1, cur = 0, launched = 0, n_eos = 0;
-  const int max_iters = max_len - 1;                 // the <BOS> step plus `predictions - 1` loop iterations (:127-131)
-  auto enqueue = [&](bool first) -> int {
-    BeamPrepArgs pa{};
-    pa.ld = ld; pa.n_cand = n_cand; pa.beam = beam; pa.dl = 0; pa.N = 1; pa.pad = p->pad_token; pa.smart = 0;
-    TTX_TRY(enqueue_bs_prep(s, st, MC, pa));
-    if (!first) TTX_TRY(enqueue_tree_cache(s, st, MC, Lc, cur, cur ^ 1, nullptr, nullptr, 1, 0));
-    TTX_TRY(enqueue_bs_list(s, st, n_cand, 1, 0));
-    const int variant = variant_for_rows(s, (long long)std::max(1, n_cand - n_eos), true);
-    TTX_TRY(run_step(s, st, tree_step_ctx(s, MC, Ls, 1, 0, Lc, ld, max_len, cur ^ 1, variant), key_capacity(width, max_len)));
-    BeamStepArgs sa{};
-    sa.logits = s->logits.as<float>(); sa.V = V; sa.slot_of = s->t_slot_of.as<int>(); sa.finished = s->bs_fin.as<uint8_t>();
-    sa.score = s->bs_logp.as<float>(); sa.gen = s->gen.as<int>(); sa.ld = ld; sa.width = width;
-    sa.B = B; sa.beam = beam; sa.K = K; sa.pad = p->pad_token; sa.eos = p->eos_token;
-    sa.new_cand = s->bs_cand_next.as<int64_t>(); sa.new_score = s->bs_logp_next.as<float>(); sa.parent = s->bs_parent.as<int>();
-    sa.new_len = s->bs_len_next.as<int>(); sa.new_finished = s->bs_fin_next.as<uint8_t>(); sa.parent_draft = s->bs_parent_draft.as<int>();
-    sa.summary = s->beam_summary.as<int>();
-    TTX_TRY(launch_beam_step(s, st, sa));
-    hipLaunchKernelGGL(k_bs_publish, dim3(1), dim3(64), 0, st, s->beam_summary.as<int>(), dev_host, s->bs_cnt.as<BeamCounters>());
-    HIP_TRY(hipGetLastError());
-    return TTX_OK;
-  };
-  volatile BeamHost* bh = s->beam_host;
-  while (launched < max_iters) {
-    const bool first = launched == 0;
-    // width changes every step, so a step's graph would be replayed once: the steps run eagerly (about 12 launches per
-    // decoder layer, enqueued well ahead of the device)
-    TTX_TRY(enqueue(first));
-    ++launched;
-    cur ^= 1;
-    if (!wait_published(watchdog_seconds(), [&] { return bh->steps_done >= launched; })) return session_hung(s);
-    width += 1;
-    n_cand = B * K; beam = K;
-    n_eos = bh->summary[0];
-    if (n_eos == B * K && !first) break;                   // :166 (the check sits inside the loop, after the first step)
-  }
-  HIP_TRY(hipMemcpy2DAsync(d_out, (size_t)max_len * 8, s->bs_cand_next.p, (size_t)ld * 8, (size_t)width * 8, (size_t)B * K,
-                           hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(s->host_state, s->bs_cnt.p, sizeof(BeamCounters), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const BeamCounters* cn = reinterpret_cast<const BeamCounters*>(s->host_state);
-  stats->model_calls = cn->model_calls;
-  stats->running_rows = cn->running_cands;
-  stats->out_width = width;
+  j.MC = MC; j.ld = ld; j.Lc = Lc; j.n_cand = B; j.phase = 1;
   return TTX_OK;
+}
+
+// Enqueue one iteration.  width changes every step, so a step's graph would be replayed once: the steps run eagerly (about 12
+// launches per decoder layer, enqueued well ahead of the device).
+static int bsearch_launch_iter(BeamSearchJob& j) {
+  ttx_session* s = j.s;
+  hipStream_t st = j.st;
+  const int max_len = j.p.max_len, cur = j.cur;
+  BeamPrepArgs pa{};
+  pa.ld = j.ld; pa.n_cand = j.n_cand; pa.beam = j.beam; pa.dl = 0; pa.N = 1; pa.pad = j.p.pad_token; pa.smart = 0;
+  TTX_TRY(enqueue_bs_prep(s, st, j.MC, pa));
+  if (j.launched > 0) TTX_TRY(enqueue_tree_cache(s, st, j.MC, j.Lc, cur, cur ^ 1, nullptr, nullptr, 1, 0));
+  TTX_TRY(enqueue_bs_list(s, st, j.n_cand, 1, 0));
+  const int variant = variant_for_rows(s, (long long)std::max(1, j.n_cand - j.n_eos), true);
+  TTX_TRY(run_step(s, st, tree_step_ctx(s, j.MC, j.Ls, 1, 0, j.Lc, j.ld, max_len, cur ^ 1, variant), key_capacity(j.width, max_len)));
+  BeamStepArgs sa{};
+  sa.logits = s->logits.as<float>(); sa.V = s->m->cfg.vocab_size; sa.slot_of = s->t_slot_of.as<int>(); sa.finished = s->bs_fin.as<uint8_t>();
+  sa.score = s->bs_logp.as<float>(); sa.gen = s->gen.as<int>(); sa.ld = j.ld; sa.width = j.width;
+  sa.B = j.B; sa.beam = j.beam; sa.K = j.K; sa.pad = j.p.pad_token; sa.eos = j.p.eos_token;
+  sa.new_cand = s->bs_cand_next.as<int64_t>(); sa.new_score = s->bs_logp_next.as<float>(); sa.parent = s->bs_parent.as<int>();
+  sa.new_len = s->bs_len_next.as<int>(); sa.new_finished = s->bs_fin_next.as<uint8_t>(); sa.parent_draft = s->bs_parent_draft.as<int>();
+  sa.summary = s->beam_summary.as<int>();
+  TTX_TRY(launch_beam_step(s, st, sa));
+  hipLaunchKernelGGL(k_bs_publish, dim3(1), dim3(64), 0, st, s->beam_summary.as<int>(), j.dev_host, s->bs_cnt.as<BeamCounters>());
+  HIP_TRY(hipGetLastError());
+  ++j.launched;
+  j.cur = cur ^ 1;
+  return TTX_OK;
+}
+
+// The published summary of the iteration just finished -> the loop scalars.  Returns true when the loop goes on: the <BOS> step
+// plus `predictions - 1` loop iterations (:127-131).
+static bool bsearch_after_iter(BeamSearchJob& j) {
+  const bool first = j.launched == 1;
+  j.width += 1;
+  j.n_cand = j.B * j.K; j.beam = j.K;
+  j.n_eos = ((volatile BeamHost*)j.s->beam_host)->summary[0];
+  if (j.n_eos == j.B * j.K && !first) return false;        // :166 (the check sits inside the loop, after the first step)
+  return j.launched < j.p.max_len - 1;
+}
+
+static int bsearch_finish_enqueue(BeamSearchJob& j) {
+  ttx_session* s = j.s;
+  HIP_TRY(hipMemcpy2DAsync(j.d_out, (size_t)j.p.max_len * 8, s->bs_cand_next.p, (size_t)j.ld * 8, (size_t)j.width * 8,
+                           (size_t)j.B * j.K, hipMemcpyDeviceToDevice, j.st));
+  TTX_TRY(enqueue_readback(s, j.st, s->bs_cnt.p, sizeof(BeamCounters)));
+  j.phase = 2;
+  return TTX_OK;
+}
+
+extern "C" int ttx_beam_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_beam_search_params* p, int64_t* d_out,
+                                 ttx_beam_search_stats* stats, void* stream) {
+  if (!s || !d_src || !p || !d_out || !stats || B <= 0 || Ls <= 1) return fail(TTX_ERR_INVALID, "bad argument to ttx_beam_generate");
+  BeamSearchJob j;
+  const auto start = [&](int) -> int {
+    TTX_TRY(bsearch_start(j, s, s->own_stream, d_src, B, Ls, p, d_out));
+    return bsearch_launch_iter(j);                                  // max_len > 1: the first iteration always runs
+  };
+  const auto turn = [&](int) -> int {
+    if (j.phase == 1) {
+      if (((volatile BeamHost*)s->beam_host)->steps_done < j.launched) return TURN_WAITING;   // the iteration in flight has not published yet
+      TTX_TRY(bsearch_after_iter(j) ? bsearch_launch_iter(j) : bsearch_finish_enqueue(j));
+      return TURN_PROGRESSED;
+    }
+    if (hipEventQuery(s->ev_done) != hipSuccess) return TURN_IDLE;
+    const BeamCounters* cn = reinterpret_cast<const BeamCounters*>(s->host_state);
+    stats->model_calls = cn->model_calls; stats->running_rows = cn->running_cands; stats->out_width = j.width;
+    return TURN_FINISHED;
+  };
+  return drive_sessions(&s, 1, false, stream, start, turn);
 }
 
 // Parity instrumentation: the verify step selected by ttx_gen_params.want_logits (1-based step number) of the most
@@ -3453,7 +3449,7 @@ extern "C" int ttx_debug_accept_block(ttx_session* s, int32_t* words, int n_word
 }
 
 // ---- the beam family, one launch each: the caller's operands through the launch_* halves of the enqueue_* helpers -------------
-// Limits the generators enforce before they launch any of these (beam_check_params, beam_start, beam_generate_impl).
+// Limits the generators enforce before they launch any of these (beam_check_params, beam_start, bsearch_start).
 static int dbg_beam_limits(const char* who, int K, int N, int V, int dl) {
   const std::string w(who);
   if (K < 1 || K > NUC_MAX_KEEP) return fail(TTX_ERR_INVALID, w + ": n_best must lie in [1, 32]");

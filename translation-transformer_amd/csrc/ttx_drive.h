@@ -1,5 +1,6 @@
-// Host-only core of the polling loops (no HIP in here: tests/host/drive_host.cpp compiles it with g++ and drives it with fake
-// jobs).  A call decodes on n jobs (sessions, each on its own stream) from one host thread: drive_jobs() visits them round-robin
+// Host-only core of the polling loop every decoding entry point runs under (no HIP in here: tests/host/drive_host.cpp compiles it
+// with g++ and drives it with fake jobs).  A call decodes on n jobs (sessions, each on its own stream; the single-session calls
+// have n = 1) from one host thread: drive_jobs() visits them round-robin
 // and gives each a turn; what a turn does (start a batch, enqueue the next step once the last one has published, admit rows,
 // collect the result) is the caller's.  The core owns the order of the visits, the serial mode, the pause, the watchdog and the
 // rule that the first error ends the call.
@@ -28,17 +29,6 @@ struct Progress {
   bool stalled(int limit_s) { return (++idle_spins & 0xffff) == 0 && watchdog_expired(last_progress, limit_s); }
   void advanced() { idle_spins = 0; last_progress = std::chrono::steady_clock::now(); }
 };
-
-// Single-stream loops: spin until published() holds; false when the watchdog time went by first.
-template <class Published>
-inline bool wait_published(int watchdog_s, Published&& published) {
-  Progress wait;
-  while (!published()) {
-    if (wait.stalled(watchdog_s)) return false;
-    __builtin_ia32_pause();
-  }
-  return true;
-}
 
 // What turn(i) reports; a negative value is an error code (TTX_ERR_*) and ends the call.
 enum Turn {
