@@ -322,6 +322,33 @@ typedef struct ttx_sample_spec_params {
 int ttx_sample_speculative_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
                                     const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream);
 
+/* ttx_sample_speculative_generate over a whole list of sources on the slot pool of ttx_greedy_speculative_generate_pool
+ * (continuous batching, length-bucketed admissions, the two-phase verify step, draft select, the accept step in two launches
+ * above 256 slots), with the keyed draw where the argmax stands.  d_src int64 [S_total][Ls_all] holds ALL sources right-padded in
+ * the order they are to be admitted, h_len (HOST, int32 [S_total]) their lengths, d_row_keys int64 [S_total] their keys in the
+ * order of d_src (NULL: keys 0 .. S_total - 1).  d_out int64 [S_total][num_samples][max_len] in the order of d_src: row (s, j)
+ * holds what ttx_sample_speculative_generate writes for source s with key d_row_keys[s] and sample j (BOS, the tokens up to and
+ * including the first EOS or PAD, then PAD); the acceptance rule, the ending rule (EOS, PAD, front at max_len - 1) and the
+ * dropped columns are that call's.  The token at a position is a function of that position's logits and of (seed, key, sample,
+ * pos) alone, so a row does not depend on its slot, on when it was admitted, on the capacity or on what shares the pool.
+ *
+ * Work-list units are sources: the n = num_samples decoder rows of a source are admitted together into n slots (capacity counts
+ * decoder rows).  The encoder, the cross K/V projection and the copy drafts run once per source of an admission sub-chunk; the
+ * fill replicates them into the source's n slots.  A slot carries its key, its sample id (i % n) and its row of d_out.  There are
+ * no per-row traces and no TTX_ERR_ROW_REPLAY (nothing is replayed), and no int16 limit on max_len.
+ *
+ * stats (zero it first) receives sums over the pools: model_calls = verify steps the device executed, accepted_tokens,
+ * produced_tokens, verified_positions (the rows of matching slots under a split step), kv_prefix_positions, src_positions,
+ * src_tokens_padded (sources x width per admission sub-chunk), decode_ms.  ttx_pool_last_counters reports this call's pool counters.
+ * The greedy pool's switches apply and are read at pool start: TTX_TWO_PHASE, TTX_TWO_PHASE_MIN_ROWS, TTX_DRAFT_SELECT,
+ * TTX_ADMIT_ROWS, TTX_ACCEPT_SPREAD, TTX_TWO_PHASE_STATS.  TTX_ACCEPT_SPREAD too is read at pool start by this call (unset: on;
+ * the value a session saw when it was created, which the greedy pool goes by, plays no part here).
+ * TTX_ERR_INVALID with nothing launched: everything ttx_sample_speculative_generate refuses; null pointers; capacity outside
+ * [num_samples, 4096]; an h_len entry above Ls_all; a slot width beyond the positional table.  S_total == 0 returns TTX_OK. */
+int ttx_sample_speculative_generate_pool(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total, int Ls_all,
+                                         const int32_t* h_len, const int64_t* d_row_keys, int capacity,
+                                         const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream);
+
 /* Beam-speculative bookkeeping kernels.
  * ttx_nucleus_mask: mask_with_num_logits_according_nucleus (src/decoding/speculative_decoding.py:871-904): per row of
  *   d_logits [rows,V] keep the best logit and further ones, best first, while the softmax mass ranked above is
@@ -663,6 +690,48 @@ int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, int64_t* st
  * D + 2; the loop stops when no row runs; error stays as it was.  threads: 0 (256 for B <= 256, else 1024), 256 or 1024; the
  * kernel takes any B by rounds.  Refusals as for ttx_debug_accept. */
 int ttx_debug_sample_accept(ttx_session* s, const ttx_debug_accept_args* a, int64_t* state, void* stream);
+
+/* ttx_debug_sample_step_select (tests/test_gpu_sample_step_select_kernel.py): ONE launch of k_sample_step as a pass of the slot
+ * pool runs it, on ttx_debug_sample_step's operands.  The launch covers n_rows rows stored compacted: d_logits fp32 [n_rows, V] and
+ * d_pred int32 [n_rows]; row i draws for layout row d_row_map[i] (int32 [n_rows], as ttx_debug_embed_select reads it; NULL: row i
+ * itself, and n_rows == n_active * (1 + N*D)): decoder row b = d_act_idx[d_row_map[i] / (1 + N*D)], position as in
+ * ttx_debug_sample_step from the row inside the slot.  The probe layout N = 1, D = 0 is accepted (every row predicts d_front[b] + 1).
+ * d_m: live row count on the device or NULL (n_rows).  Refused: what ttx_debug_sample_step refuses (D = 0 only with N = 1), n_rows
+ * outside [1, n_active * (1 + N*D)], a row map entry outside the active slots' rows, *d_m outside [0, n_rows]. */
+int ttx_debug_sample_step_select(ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample,
+                                 const int32_t* d_act_idx, const int32_t* d_front, int B, int N, int D, int n_active, int32_t* d_pred,
+                                 const int32_t* d_m, const ttx_sample_params* p, const int32_t* d_row_map, int n_rows, void* stream);
+
+/* ttx_debug_sample_accept_pool (tests/test_gpu_sample_accept_pool_kernel.py): the accept step of
+ * ttx_sample_speculative_generate_pool on ttx_debug_accept's argument block and `state`: greedy 0, row_rule and pool 1; d_row_of
+ * int32 [B] and d_pool_out int64 [pool_rows, max_len] are required, an ended row b is copied to d_pool_out[d_row_of[b]]; the traj /
+ * fin_step / rstep pointers are unused.  d_exec_rows (device int32, or NULL): what verified_positions adds instead of n_active *
+ * (1 + N*D).  spread 0: ONE launch of k_sample_accept (threads 0, 256 or 1024 as for ttx_debug_sample_accept); spread 1 (threads 0):
+ * the pair k_sample_accept_slots, k_accept_finish at any B (production takes it above 256 slots), which leaves the session's
+ * AcceptBlk zero (ttx_debug_accept_block).  Both forms leave the same state.  Refusals as for ttx_debug_accept. */
+int ttx_debug_sample_accept_pool(ttx_session* s, const ttx_debug_accept_args* a, int64_t* state, const int32_t* d_exec_rows, int spread,
+                                 void* stream);
+
+/* ttx_debug_pool_fill_sample (tests/test_gpu_pool_fill_sample.py): ONE admission of the sampling pool, k_pool_admit then k_pool_fill,
+ * on the caller's arrays: n_sources staged sources (first_src the first one's index in the call's list) x per_src samples into a
+ * pool of B slots of which the n_active slots d_act_idx[0 .. n_active) are occupied.  New decoder row i takes the lowest free slot
+ * b: front 0, haspad 0, rstep 0, row_of = first_src * per_src + i, src_len = Ls_new, key = d_row_keys[first_src + i / per_src]
+ * (NULL: that index), sample = i % per_src; gen row BOS then PAD; drafts [N * D], validity bytes (zero from Ls_new to Ls_cap) and
+ * cross K/V [Ls_new, kv_row] of staged source i / per_src; caller row d_out[row_of] = BOS then PAD.  Per-slot arrays int32 [B]
+ * (d_key uint64 [B], d_sample uint32 [B]), d_gen int32 [B, gen_ld], d_drafts int32 [B, N * D], d_src_valid uint8 [B, Ls_cap], d_memkv
+ * fp32 [B, Ls_cap, kv_row]; staged d_drafts_new int32 [n_sources, N * D], d_valid_new uint8 [n_sources, Ls_new], d_memkv_new fp32
+ * [n_sources, Ls_new, kv_row]; d_out int64 [out_rows, max_len].  result (HOST int32 [4]): n_active, m_rows and error of the state
+ * after the admission, and the n_active word published for the host.  More rows than free slots: error 4, and nothing is filled.
+ * Refused: null arrays (d_row_keys may be NULL), non-positive sizes, B or rows above 4096, Ls_new > Ls_cap, kv_row not a multiple
+ * of 4 or K/V arrays not 16-byte aligned, admitted rows beyond out_rows, act_idx that are not distinct slots of [0, B). */
+typedef struct ttx_debug_pool_fill_args {
+  int32_t* d_act_idx; int32_t* d_front; int32_t* d_haspad; int32_t* d_rstep; int32_t* d_row_of; int32_t* d_src_len;
+  uint64_t* d_key; uint32_t* d_sample; const int64_t* d_row_keys;
+  int32_t* d_gen; int32_t* d_drafts; const int32_t* d_drafts_new; uint8_t* d_src_valid; const uint8_t* d_valid_new;
+  float* d_memkv; const float* d_memkv_new; int64_t* d_out;
+  int32_t B, N, D, n_active, n_sources, per_src, first_src, Ls_new, Ls_cap, gen_ld, kv_row, max_len, out_rows, bos, pad;
+} ttx_debug_pool_fill_args;
+int ttx_debug_pool_fill_sample(ttx_session* s, const ttx_debug_pool_fill_args* a, int32_t* result, void* stream);
 
 /* ttx_debug_accept_block: the first n_words int32 words of the session's AcceptBlk (csrc/ttx_loop_kernels.hip.h: the sums that
  * k_accept_slots hands k_accept_finish; 264 words), copied to the HOST array `words` after `stream` has drained.  Every word is 0

@@ -116,6 +116,15 @@ class DebugAcceptArgs(C.Structure):
                                          "pad", "bos", "eos", "greedy", "threads")]
 
 
+class DebugPoolFillArgs(C.Structure):
+    """ttx_debug_pool_fill_args: the device arrays and scalars of one admission of the sampling pool."""
+    POINTERS = ("d_act_idx", "d_front", "d_haspad", "d_rstep", "d_row_of", "d_src_len", "d_key", "d_sample", "d_row_keys", "d_gen",
+                "d_drafts", "d_drafts_new", "d_src_valid", "d_valid_new", "d_memkv", "d_memkv_new", "d_out")
+    _fields_ = [(n, C.c_void_p) for n in POINTERS] + \
+               [(n, C.c_int32) for n in ("B", "N", "D", "n_active", "n_sources", "per_src", "first_src", "Ls_new", "Ls_cap", "gen_ld",
+                                         "kv_row", "max_len", "out_rows", "bos", "pad")]
+
+
 def _debug_args(name: str, pointers, ints, int64s=()):
     """A ttx_debug_*_args struct of include/ttx.h: device pointers, then int64 strides, then int32 scalars."""
     fields = [(n, C.c_void_p) for n in pointers] + [(n, C.c_int64) for n in int64s] + [(n, C.c_int32) for n in ints]
@@ -196,6 +205,8 @@ SYMBOLS = {
                                                       C.POINTER(_VP), C.POINTER(_VP), C.POINTER(GenStats), _VP]),
     "ttx_greedy_speculative_generate_pool": (C.c_int, [C.POINTER(_VP), _I, _VP, _I, _I, C.POINTER(C.c_int32), _I,
                                                       C.POINTER(GenParams), _VP, _VP, _VP, C.POINTER(GenStats), _VP]),
+    "ttx_sample_speculative_generate_pool": (C.c_int, [C.POINTER(_VP), _I, _VP, _I, _I, C.POINTER(C.c_int32), _VP, _I,
+                                                      C.POINTER(SampleSpecParams), _VP, C.POINTER(GenStats), _VP]),
     "ttx_beam_speculative_generate": (C.c_int, [_VP, _VP, _I, _I, C.POINTER(BeamParams), _VP, C.POINTER(BeamStats), _VP]),
     "ttx_beam_speculative_generate_many": (C.c_int, [C.POINTER(_VP), _I, _I, C.POINTER(_VP), C.POINTER(C.c_int),
                                                     C.POINTER(C.c_int), C.POINTER(BeamParams), C.POINTER(_VP),
@@ -229,6 +240,10 @@ SYMBOLS = {
     "ttx_debug_sample": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I, C.POINTER(SampleParams), _VP]),
     "ttx_debug_sample_step": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, C.POINTER(SampleParams), _VP]),
     "ttx_debug_sample_accept": (C.c_int, [_VP, C.POINTER(DebugAcceptArgs), C.POINTER(C.c_int64), _VP]),
+    "ttx_debug_sample_step_select": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, C.POINTER(SampleParams),
+                                              _VP, _I, _VP]),
+    "ttx_debug_sample_accept_pool": (C.c_int, [_VP, C.POINTER(DebugAcceptArgs), C.POINTER(C.c_int64), _VP, _I, _VP]),
+    "ttx_debug_pool_fill_sample": (C.c_int, [_VP, C.POINTER(DebugPoolFillArgs), C.POINTER(C.c_int32), _VP]),
     "ttx_debug_embed": (C.c_int, [_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _I, _I, _I, _I, _I, _VP]),
     "ttx_debug_accept": (C.c_int, [_VP, C.POINTER(DebugAcceptArgs), C.POINTER(C.c_int64), _VP]),
     "ttx_debug_accept_block": (C.c_int, [_VP, C.POINTER(C.c_int32), _I, _VP]),

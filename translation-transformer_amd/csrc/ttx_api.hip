@@ -1133,9 +1133,9 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
   }
   if (k.want_sample_step) {
     SampleStepArgs a{};
-    a.logits = logits; a.V = V; a.pred = s->pred.as<int>(); a.m_ptr = m_ptr; a.M = Mmax;
+    a.logits = logits; a.V = V; a.pred = k.pred_ov ? k.pred_ov : s->pred.as<int>(); a.m_ptr = m_ptr; a.M = Mmax;
     a.key = k.sample.key; a.sample = k.sample.sample; a.prm = k.sample.prm;
-    a.act_idx = act; a.front = s->front.as<int>(); a.N = k.N; a.D = k.D;
+    a.act_idx = act; a.front = s->front.as<int>(); a.N = k.N; a.D = k.D; a.row_map = k.row_map;
     return launch_sample_step(st, a);
   }
   if (k.want_argmax) {
@@ -1164,24 +1164,33 @@ static int launch_accept(hipStream_t st, const LoopArgs& la, int threads) {
   return TTX_OK;
 }
 
-// The accept step of the speculative sampling loop: one workgroup, k_accept's block size.
+// The accept step of the speculative sampling loop: one workgroup with k_accept's block size, or with `la.blk` set (the sampling
+// pool above 256 slots, accept_blk_for) the pair k_sample_accept_slots, k_accept_finish.
 static int launch_sample_accept(hipStream_t st, const LoopArgs& la) {
-  hipLaunchKernelGGL(k_sample_accept, dim3(1), dim3(la.B > 256 ? ACCEPT_THREADS : 256), 0, st, la);
+  if (la.blk) {
+    hipLaunchKernelGGL(k_sample_accept_slots, dim3(cdiv(la.B, ACCEPT_SLOT_WAVES)), dim3(ACCEPT_SLOT_WAVES * 64), 0, st, la);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_accept_finish, dim3(1), dim3(ACCEPT_THREADS), 0, st, la);
+  } else {
+    hipLaunchKernelGGL(k_sample_accept, dim3(1), dim3(la.B > 256 ? ACCEPT_THREADS : 256), 0, st, la);
+  }
   HIP_TRY(hipGetLastError());
   return TTX_OK;
 }
 
 // The session's AcceptBlk for loops of more than 256 slots (null otherwise, and with TTX_ACCEPT_SPREAD=0): zero when fresh, and
 // left zero by every k_accept_finish.  The choice follows the capacity alone, as k_accept's block size does.
-static int accept_blk_for(ttx_session* s, hipStream_t st, int B, AcceptBlk** out) {
+// `spread`: the switch as the caller reads it (the session's TTX_ACCEPT_SPREAD, or the sampling pool's reading at pool start).
+static int accept_blk_when(ttx_session* s, hipStream_t st, int B, bool spread, AcceptBlk** out) {
   *out = nullptr;
-  if (!s->accept_spread || B <= 256) return TTX_OK;
+  if (!spread || B <= 256) return TTX_OK;
   const void* before = s->accept_blk.p;
   TTX_TRY(ensure(s->accept_blk, sizeof(AcceptBlk), st));
   if (s->accept_blk.p != before) HIP_TRY(hipMemsetAsync(s->accept_blk.p, 0, sizeof(AcceptBlk), st));
   *out = s->accept_blk.as<AcceptBlk>();
   return TTX_OK;
 }
+static int accept_blk_for(ttx_session* s, hipStream_t st, int B, AcceptBlk** out) { return accept_blk_when(s, st, B, s->accept_spread, out); }
 
 static int launch_accept_and_commit(ttx_session* s, hipStream_t st, const GenCtx& g, bool greedy) {
   if (greedy) {
@@ -1704,6 +1713,28 @@ extern "C" int ttx_sample_generate(ttx_session* s, const int64_t* d_src, int B, 
   return rc;
 }
 
+// What the speculative sampling calls refuse with TTX_ERR_INVALID whatever code gen_validate would give (nothing of these calls is
+// the reference's), over `rows` decoder rows in one loop; then the call's SampleSetup and the loop's parameters.
+static int sample_spec_validate(const char* who, const ttx_session* s, const ttx_sample_spec_params* p, long long rows, SampleSetup* smp,
+                                ttx_gen_params* g) {
+  const ttx_sample_params& sp = p->sample;
+  if (s->m->cfg.vocab_size > SAMPLE_MAX_V) return fail(TTX_ERR_INVALID, std::string(who) + ": vocabularies above 1024 are not supported");
+  if (sp.num_samples < 1) return fail(TTX_ERR_INVALID, std::string(who) + ": num_samples must be at least 1");
+  TTX_TRY(sample_block(who, &sp, &smp->blk));
+  if (p->n_drafts < 1) return fail(TTX_ERR_INVALID, std::string(who) + ": n_drafts must be at least 1");
+  if (sp.max_len < 1) return fail(TTX_ERR_INVALID, std::string(who) + ": max_len must be positive");
+  if (p->draft_len < 1 || p->draft_len > sp.max_len) return fail(TTX_ERR_INVALID, std::string(who) + ": draft_len must lie in [1, max_len]");
+  if (sp.pad_token == p->replace_token || sp.eos_token == p->replace_token || sp.eos_token == sp.pad_token)
+    return fail(TTX_ERR_INVALID, std::string(who) + ": pad, eos and replace tokens must be pairwise different");
+  if (rows * ((long long)sp.max_len + p->draft_len + 2) >= (1ll << 31) ||
+      rows * step_rps(p->n_drafts, p->draft_len) * (long long)s->m->cfg.vocab_size >= (1ll << 31))
+    return fail(TTX_ERR_INVALID, std::string(who) + ": B * num_samples * (max_len + draft_len + 2) and the step's logits must stay below 2^31 elements");
+  smp->n = sp.num_samples; smp->spec = true;
+  g->max_len = sp.max_len; g->draft_len = p->draft_len; g->n_drafts = p->n_drafts; g->pad_token = sp.pad_token; g->bos_token = sp.bos_token;
+  g->eos_token = sp.eos_token; g->replace_token = p->replace_token; g->want_logits = 0;
+  return TTX_OK;
+}
+
 // Speculative seeded sampling: the greedy-speculative loop over R = B * n decoder rows with the keyed draw where the argmax stands
 // (k_sample_step, k_sample_accept).  A draft token is accepted iff it is the token the plain sampler emits at its position, so the
 // committed rows are ttx_sample_generate's.
@@ -1711,26 +1742,12 @@ extern "C" int ttx_sample_speculative_generate(ttx_session* s, const int64_t* d_
                                                const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
   const char* who = "ttx_sample_speculative_generate";
   if (!s || !p) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
-  const ttx_sample_params& sp = p->sample;
-  if (s->m->cfg.vocab_size > SAMPLE_MAX_V) return fail(TTX_ERR_INVALID, std::string(who) + ": vocabularies above 1024 are not supported");
-  if (sp.num_samples < 1) return fail(TTX_ERR_INVALID, std::string(who) + ": num_samples must be at least 1");
   SampleSetup smp{};
-  TTX_TRY(sample_block(who, &sp, &smp.blk));
-  if (B <= 0) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
-  // refused with TTX_ERR_INVALID here, whatever code gen_validate would give: nothing of this call is the reference's
-  if (p->n_drafts < 1) return fail(TTX_ERR_INVALID, std::string(who) + ": n_drafts must be at least 1");
-  if (sp.max_len < 1) return fail(TTX_ERR_INVALID, std::string(who) + ": max_len must be positive");
-  if (p->draft_len < 1 || p->draft_len > sp.max_len) return fail(TTX_ERR_INVALID, std::string(who) + ": draft_len must lie in [1, max_len]");
-  if (sp.pad_token == p->replace_token || sp.eos_token == p->replace_token || sp.eos_token == sp.pad_token)
-    return fail(TTX_ERR_INVALID, std::string(who) + ": pad, eos and replace tokens must be pairwise different");
-  const long long R = (long long)B * sp.num_samples;
-  if (R * ((long long)sp.max_len + p->draft_len + 2) >= (1ll << 31) ||
-      R * step_rps(p->n_drafts, p->draft_len) * (long long)s->m->cfg.vocab_size >= (1ll << 31))
-    return fail(TTX_ERR_INVALID, std::string(who) + ": B * num_samples * (max_len + draft_len + 2) and the step's logits must stay below 2^31 elements");
-  smp.n = sp.num_samples; smp.d_row_keys = d_row_keys; smp.spec = true;
   ttx_gen_params g{};
-  g.max_len = sp.max_len; g.draft_len = p->draft_len; g.n_drafts = p->n_drafts; g.pad_token = sp.pad_token; g.bos_token = sp.bos_token;
-  g.eos_token = sp.eos_token; g.replace_token = p->replace_token; g.want_logits = 0;
+  const long long R = (long long)std::max(B, 0) * std::max(p->sample.num_samples, 0);
+  TTX_TRY(sample_spec_validate(who, s, p, R, &smp, &g));
+  if (B <= 0) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
+  smp.d_row_keys = d_row_keys;
   const int rc = generate_one(s, d_src, (int)R, Ls, &g, d_out, stats, stream, false, &smp);
   if (rc == TTX_OK && stats) stats->src_tokens_padded = (long long)B * Ls;    // the encoder ran once per source
   return rc;
@@ -1766,10 +1783,17 @@ struct PoolJob {
   long long drafts_matched = 0;     // drafts run by the draft passes (draft select: the matching ones; else N per matching slot)
   long long rows_executed = 0;      // rows every step of this pool sent through the decoder, probes included
   long long unsplit_rows = 0;       // ... of which in steps that ran in one pass
+  // sampling pool (ttx_sample_speculative_generate_pool; 0 / null: the greedy pool): decoder rows per source, the sources' keys
+  int per_src = 0;
+  const int64_t* d_row_keys = nullptr;
 };
 
+static int pool_sample_begin(PoolJob& j, const SampleSetup& smp);
+
+// `smp` (null: the greedy pool): the sampling pool, whose slots carry a key and a sample id, whose steps draw with k_sample_step and
+// accept with k_sample_accept, and which keeps no per-row trace (d_traj and d_fin are null).
 static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_cap, const ttx_gen_params* p, int64_t* d_out,
-                      int16_t* d_traj, int32_t* d_fin) {
+                      int16_t* d_traj, int32_t* d_fin, const SampleSetup* smp = nullptr) {
   const ttx_config& c = s->m->cfg;
   const int d = c.embedding_dim, Ld = c.num_decoder_layers;
   const int N = p->n_drafts, D = p->draft_len, D1 = D + 1, max_len = p->max_len;
@@ -1812,9 +1836,14 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
     for (Buf* b : {&s->pred_probe, &s->act2, &s->pos2}) need(*b, (size_t)C * 4);
     need(s->pred_draft, Mmax * 4); need(s->state2, 3 * sizeof(DecState));
   }
+  if (smp) { need(s->smp_key, (size_t)C * 8); need(s->smp_sample, (size_t)C * 4); need(s->smp_prm, sizeof(SampleBlock)); }
   TTX_TRY(need.rc);
   AcceptBlk* blk = nullptr;
-  TTX_TRY(accept_blk_for(s, st, C, &blk));
+  // the greedy pool keeps the session's reading of TTX_ACCEPT_SPREAD; the sampling pool reads it here, with its other switches
+  // (unset: on), and that reading alone decides
+  bool spread = s->accept_spread;
+  if (smp) { const char* e = getenv("TTX_ACCEPT_SPREAD"); spread = e ? atoi(e) != 0 : true; }
+  TTX_TRY(accept_blk_when(s, st, C, spread, &blk));
   s->graphs_current();
 
   s->ev_used = 0;
@@ -1830,6 +1859,8 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
   g.la.row_rule = 1;
   g.la.pool = 1; g.la.rstep = s->rstep.as<int>(); g.la.row_of = s->row_of.as<int>(); g.la.io = s->pool_io.as<PoolIo>();
   g.k.src_len = s->src_len.as<int>();
+  j.per_src = 0; j.d_row_keys = nullptr;
+  if (smp) TTX_TRY(pool_sample_begin(j, *smp));
   j.g2 = g;
   if (j.two_phase) {
     j.g2.la.exec_rows = reinterpret_cast<const int*>(s->state2.as<DecState>() + 2);
@@ -1845,37 +1876,49 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
 
 // Encode R new rows (rows first_row .. first_row+R-1 of the caller's sorted matrix, Ls_new columns of it) and hand
 // them free slots.
+// Sampling pool: the R rows of d_src_rows are sources (first_row the first one's index); each is encoded once and fills
+// j.per_src slots, rows first_row * per_src .. of d_out.
 static int pool_admit(PoolJob& j, const int64_t* d_src_rows, int ld_src, int R, int Ls_new, int first_row, int64_t* d_out,
                       int16_t* d_traj, int32_t* d_fin) {
   ttx_session* s = j.s;
   hipStream_t st = j.st;
   const StepCtx& k = j.g.k;
   const int kv_row = s->m->cfg.num_decoder_layers * 2 * s->m->cfg.embedding_dim;
+  const int per = std::max(1, j.per_src), rows = R * per, row0 = first_row * per;      // decoder rows of this admission
   TTX_TRY(encode_sources(s, st, d_src_rows, ld_src, R, Ls_new, s->valid_new.as<uint8_t>(), s->memkv_new.as<float>()));
   TTX_TRY(launch_make_drafts<int>(st, s->tok_src.as<int>(), Ls_new, 1, R, Ls_new - 1, k.N, k.D, k.p.eos_token, k.p.pad_token,
                                   k.p.replace_token, s->drafts_new.as<int>()));
   PoolAdmitArgs a{};
   a.st = s->state.as<DecState>(); a.act_idx = s->act_idx.as<int>(); a.front = s->front.as<int>(); a.haspad = s->haspad.as<int>();
   a.rstep = s->rstep.as<int>(); a.row_of = s->row_of.as<int>(); a.src_len = s->src_len.as<int>(); a.new_slot = s->new_slot.as<int>();
-  a.host = j.g.la.host; a.B = j.C; a.N = k.N; a.D = k.D; a.R = R; a.first_row = first_row; a.Ls_new = Ls_new;
+  a.host = j.g.la.host; a.B = j.C; a.N = k.N; a.D = k.D; a.R = rows; a.first_row = row0; a.Ls_new = Ls_new;
+  if (j.per_src) {
+    a.key = s->smp_key.as<unsigned long long>(); a.sample = s->smp_sample.as<unsigned>(); a.row_keys = j.d_row_keys;
+    a.per_src = j.per_src; a.first_src = first_row;
+  }
   hipLaunchKernelGGL(k_pool_admit, dim3(1), dim3(256), (size_t)j.C * 4, st, a);
   HIP_TRY(hipGetLastError());
   PoolFillArgs f{};
-  f.new_slot = s->new_slot.as<int>(); f.R = R; f.gen = s->gen.as<int>(); f.gen_ld = k.gen_ld; f.bos = k.p.bos_token; f.pad = k.p.pad_token;
+  f.new_slot = s->new_slot.as<int>(); f.R = rows; f.gen = s->gen.as<int>(); f.gen_ld = k.gen_ld; f.bos = k.p.bos_token; f.pad = k.p.pad_token;
   f.drafts = s->drafts.as<int>(); f.drafts_new = s->drafts_new.as<int>(); f.nd = k.N * k.D;
   f.src_valid = s->src_valid.as<uint8_t>(); f.valid_new = s->valid_new.as<uint8_t>(); f.Ls_cap = j.Ls_cap; f.Ls_new = Ls_new;
   f.memkv = s->memkv.as<float>(); f.memkv_new = s->memkv_new.as<float>(); f.kv_row = kv_row;
-  f.out_rows = d_out; f.traj_rows = d_traj; f.fin_rows = d_fin; f.max_len = k.max_len; f.traj_ld = k.max_len + 1; f.first_row = first_row;
-  hipLaunchKernelGGL(k_pool_fill, dim3(R, 1 + Ls_new), dim3(256), 0, st, f);
+  f.out_rows = d_out; f.traj_rows = d_traj; f.fin_rows = d_fin; f.max_len = k.max_len; f.traj_ld = k.max_len + 1; f.first_row = row0;
+  f.per_src = j.per_src;
+  hipLaunchKernelGGL(k_pool_fill, dim3(rows, 1 + Ls_new), dim3(256), 0, st, f);
   HIP_TRY(hipGetLastError());
   ++j.admits;
-  j.admitted_rows += R;
+  j.admitted_rows += rows;
   j.src_tokens_padded += (long long)R * Ls_new;
   return TTX_OK;
 }
 
 // Key of one graph's worth of a pool step (`phase`: GraphKey in ttx_internal.h); the pool's steps see every key of a slot.
-static GraphKey pool_key(const StepCtx& k, int variant, int phase) {
+// The sampling pool has a site of its own, and its keys end with the form of the accept step (1: the pair), which it reads from
+// the environment per call.
+static GraphKey pool_key(const PoolJob& j, const StepCtx& k, int variant, int phase) {
+  if (k.want_sample_step)
+    return GraphKey{GS_STEP_POOL_SAMPLE, k.B, k.Ls, k.N, k.D, k.max_len, k.max_len, variant, phase, j.g.la.blk ? 1 : 0};
   return GraphKey{GS_STEP_POOL, k.B, k.Ls, k.N, k.D, k.max_len, k.max_len, variant, phase};
 }
 
@@ -1888,7 +1931,7 @@ static int pool_launch_step(PoolJob& j, int n_live) {
   const long long rows = (long long)n_live * step_rps(k.N, k.D);
   if (!j.two_phase || rows < j.min_rows) {
     k.variant = variant_for_rows(s, rows, true);     // free choice: identical bits
-    TTX_TRY(graph_replay(s, j.st, s->step_graphs, pool_key(k, k.variant, 0), [&]() -> int {
+    TTX_TRY(graph_replay(s, j.st, s->step_graphs, pool_key(j, k, k.variant, 0), [&]() -> int {
       TTX_TRY(run_step(s, j.st, k, kcap));
       return launch_accept_and_commit(s, j.st, j.g, false);
     }));
@@ -1901,7 +1944,7 @@ static int pool_launch_step(PoolJob& j, int n_live) {
   kp.N = 1; kp.D = 0; kp.sel_N = k.N; kp.sel_D = k.D;
   kp.st_ov = st2; kp.qkv_ov = s->qkv_probe.as<float>(); kp.pred_ov = s->pred_probe.as<int>();
   kp.variant = variant_for_rows(s, n_live, true);
-  TTX_TRY(graph_replay(s, j.st, s->step_graphs, pool_key(k, kp.variant, j.draft_select ? 4 : 1), [&]() -> int {
+  TTX_TRY(graph_replay(s, j.st, s->step_graphs, pool_key(j, k, kp.variant, j.draft_select ? 4 : 1), [&]() -> int {
     hipLaunchKernelGGL(k_probe_begin, dim3(1), dim3(64), 0, j.st, s->state.as<DecState>(), st2);
     HIP_TRY(hipGetLastError());
     TTX_TRY(run_step(s, j.st, kp, kcap));
@@ -1941,7 +1984,7 @@ static int pool_launch_drafts(PoolJob& j) {
   j.matched_slot_steps += matches; j.skipped_draft_passes += matches ? 0 : 1;
   j.rows_executed += rows; j.drafts_matched += (rows - matches) / k.D;
   const int phase = j.draft_select ? (matches ? 5 : 6) : (matches ? 2 : 3);
-  TTX_TRY(graph_replay(s, j.st, s->step_graphs, pool_key(k, k.variant, phase), [&]() -> int {
+  TTX_TRY(graph_replay(s, j.st, s->step_graphs, pool_key(j, k, k.variant, phase), [&]() -> int {
     if (matches) TTX_TRY(run_step(s, j.st, k, kcap));
     MergePredArgs mp{};
     mp.st = s->state.as<DecState>(); mp.pos2 = s->pos2.as<int>(); mp.pred_probe = s->pred_probe.as<int>();
@@ -1956,26 +1999,32 @@ static int pool_launch_drafts(PoolJob& j) {
   return TTX_OK;
 }
 
-extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int n_sessions, const int64_t* d_src, int R_total,
-                                                    int Ls_all, const int32_t* h_len, int capacity, const ttx_gen_params* p,
-                                                    int64_t* d_out, int16_t* d_traj, int32_t* d_fin_step, ttx_gen_stats* stats,
-                                                    void* stream) {
-  if (!sessions || n_sessions <= 0 || !d_src || R_total < 0 || !h_len || capacity <= 0 || capacity > 4096 || !p || !d_out || !d_traj ||
-      !d_fin_step)
-    return fail(TTX_ERR_INVALID, "bad argument to ttx_greedy_speculative_generate_pool");
-  if (R_total == 0) return TTX_OK;
-  if (p->max_len > 32000) return fail(TTX_ERR_INVALID, "max_len too large for the int16 trace");
-  // the longest row fixes the slot width; rows are admitted in the order given (length-sorted lists pad least: a chunk
-  // is encoded at the width of its longest row)
-  int len_max = 0;
-  for (int i = 0; i < R_total; ++i) len_max = std::max(len_max, (int)h_len[i]);
-  if (len_max > Ls_all) return fail(TTX_ERR_INVALID, "row length beyond the source matrix width");
-  const int Ls_cap = pool_slot_width(len_max, sessions[0]->m->cfg.max_positions);
-  TTX_TRY(gen_validate(sessions[0], d_src, capacity, Ls_cap, p, d_out, false));
-  const PoolShape shape = pool_shape(n_sessions, R_total, R_total, capacity, 32, 1);      // the work list: rows, i.e. unit batches
+// After pool_start's allocations: the call's parameter block on the device; every step of the pool then draws with k_sample_step on
+// the slots' keys and sample ids (written at admission) and accepts under the sampling rule.
+static int pool_sample_begin(PoolJob& j, const SampleSetup& smp) {
+  ttx_session* s = j.s;
+  hipLaunchKernelGGL(k_sample_params, dim3(1), dim3(64), 0, j.st, s->smp_prm.as<SampleBlock>(), smp.blk);
+  HIP_TRY(hipGetLastError());
+  StepCtx& k = j.g.k;
+  k.want_sample_step = true;
+  k.sample.key = s->smp_key.as<unsigned long long>(); k.sample.sample = s->smp_sample.as<unsigned>();
+  k.sample.front = s->front.as<int>(); k.sample.prm = s->smp_prm.as<SampleBlock>();
+  j.g.la.sample_rule = 1;
+  j.per_src = smp.n; j.d_row_keys = smp.d_row_keys;
+  return TTX_OK;
+}
+
+// The two slot pools (arguments validated by the callers).  The work list holds R_total units of `per` decoder rows each, admitted
+// together: the greedy pool's rows (per 1, smp null), the sampling pool's sources (per = num_samples).  d_src, h_len and the
+// admission's length buckets go by unit; slots, d_out and the counters by decoder row.
+static int pool_generate(ttx_session** sessions, int n_sessions, const int64_t* d_src, int R_total, int Ls_all, const int32_t* h_len,
+                         int Ls_cap, int capacity, const ttx_gen_params* p, int64_t* d_out, int16_t* d_traj, int32_t* d_fin_step,
+                         ttx_gen_stats* stats, void* stream, const SampleSetup* smp) {
+  const int per = smp ? smp->n : 1;
+  const PoolShape shape = pool_shape(n_sessions, R_total, R_total * per, capacity, 32, per);      // the work list: units
   const int n_jobs = shape.n_jobs, C = shape.C;
   std::vector<int> first(R_total + 1);
-  for (int r = 0; r <= R_total; ++r) first[r] = r;
+  for (int r = 0; r <= R_total; ++r) first[r] = r * per;
   std::vector<PoolJob> jobs(n_jobs);
   std::vector<int> chunk_ends;
   std::fill(std::begin(sessions[0]->pool_counters), std::end(sessions[0]->pool_counters), 0LL);
@@ -1984,7 +2033,7 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
   const bool serial = sessions[0]->profile;
   int cursor = 0;
   const auto start = [&](int i) -> int {
-    TTX_TRY(pool_start(jobs[i], sessions[i], sessions[i]->own_stream, C, Ls_cap, p, d_out, d_traj, d_fin_step));
+    TTX_TRY(pool_start(jobs[i], sessions[i], sessions[i]->own_stream, C, Ls_cap, p, d_out, d_traj, d_fin_step, smp));
     // every pool of a call has the same model and reads the same environment: the mode is the call's
     if (i == 0) sessions[0]->pool_counters[6] = jobs[0].draft_select ? 1 : 0;
     return TTX_OK;
@@ -2014,8 +2063,8 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
           TTX_TRY(pool_admit(j, d_src + (size_t)r0 * Ls_all, Ls_all, r1 - r0, chunk_width(h_len, r0, r1), r0, d_out, d_traj, d_fin_step));
           r0 = r1;
         }
+        n_act += first[cursor + take] - first[cursor];
         cursor += take;
-        n_act += take;
       }
       if (n_act == 0) {
         TTX_TRY(enqueue_readback(s, j.st, s->state.p, sizeof(DecState)));
@@ -2051,6 +2100,54 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
   const int rc = drive_sessions(sessions, n_jobs, serial, stream, start, turn);
   if (stats) stats->status = rc;
   return rc;
+}
+
+extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int n_sessions, const int64_t* d_src, int R_total,
+                                                    int Ls_all, const int32_t* h_len, int capacity, const ttx_gen_params* p,
+                                                    int64_t* d_out, int16_t* d_traj, int32_t* d_fin_step, ttx_gen_stats* stats,
+                                                    void* stream) {
+  if (!sessions || n_sessions <= 0 || !d_src || R_total < 0 || !h_len || capacity <= 0 || capacity > 4096 || !p || !d_out || !d_traj ||
+      !d_fin_step)
+    return fail(TTX_ERR_INVALID, "bad argument to ttx_greedy_speculative_generate_pool");
+  if (R_total == 0) return TTX_OK;
+  if (p->max_len > 32000) return fail(TTX_ERR_INVALID, "max_len too large for the int16 trace");
+  // the longest row fixes the slot width; rows are admitted in the order given (length-sorted lists pad least: a chunk
+  // is encoded at the width of its longest row)
+  int len_max = 0;
+  for (int i = 0; i < R_total; ++i) len_max = std::max(len_max, (int)h_len[i]);
+  if (len_max > Ls_all) return fail(TTX_ERR_INVALID, "row length beyond the source matrix width");
+  const int Ls_cap = pool_slot_width(len_max, sessions[0]->m->cfg.max_positions);
+  TTX_TRY(gen_validate(sessions[0], d_src, capacity, Ls_cap, p, d_out, false));
+  return pool_generate(sessions, n_sessions, d_src, R_total, Ls_all, h_len, Ls_cap, capacity, p, d_out, d_traj, d_fin_step, stats, stream,
+                       nullptr);
+}
+
+// ttx_sample_speculative_generate's rows over a whole list of sources on the slot pool: the n decoder rows of a source are admitted
+// together, the step kernels are the pool's with the keyed draw where the argmax stands.
+extern "C" int ttx_sample_speculative_generate_pool(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total, int Ls_all,
+                                                    const int32_t* h_len, const int64_t* d_row_keys, int capacity,
+                                                    const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
+  const char* who = "ttx_sample_speculative_generate_pool";
+  if (!sessions || n_sessions <= 0 || !d_src || S_total < 0 || !h_len || !p || !d_out)
+    return fail(TTX_ERR_INVALID, std::string("bad argument to ") + who);
+  for (int i = 0; i < n_sessions; ++i)
+    if (!sessions[i]) return fail(TTX_ERR_INVALID, std::string("bad argument to ") + who);
+  SampleSetup smp{};
+  ttx_gen_params g{};
+  TTX_TRY(sample_spec_validate(who, sessions[0], p, capacity, &smp, &g));
+  if (capacity < p->sample.num_samples || capacity > 4096)
+    return fail(TTX_ERR_INVALID, std::string(who) + ": capacity must lie in [num_samples, 4096]");
+  int len_max = 0;
+  for (int i = 0; i < S_total; ++i) len_max = std::max(len_max, (int)h_len[i]);
+  if (len_max > Ls_all) return fail(TTX_ERR_INVALID, std::string(who) + ": source length beyond the source matrix width");
+  const ttx_config& c = sessions[0]->m->cfg;
+  const int Ls_cap = pool_slot_width(len_max, c.max_positions);
+  if (Ls_cap > c.max_positions) return fail(TTX_ERR_INVALID, std::string(who) + ": slot width beyond the positional table");
+  if (g.pad_token != c.pad_token) return fail(TTX_ERR_INVALID, std::string(who) + ": generator pad token differs from the model's");
+  if (g.max_len + g.draft_len + 2 > c.max_positions) return fail(TTX_ERR_INVALID, std::string(who) + ": max_len + draft_len exceeds the positional table");
+  if (S_total == 0) return TTX_OK;
+  smp.d_row_keys = d_row_keys;
+  return pool_generate(sessions, n_sessions, d_src, S_total, Ls_all, h_len, Ls_cap, capacity, &g, d_out, nullptr, nullptr, stats, stream, &smp);
 }
 
 // Several batches in flight on one GPU: outputs per batch are identical to the one-at-a-time call.
@@ -3218,37 +3315,67 @@ extern "C" int ttx_debug_sample(ttx_session* s, const float* d_logits, int V, co
   return launch_sample(st, a);
 }
 
-extern "C" int ttx_debug_sample_step(ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample,
-                                     const int32_t* d_act_idx, const int32_t* d_front, int B, int N, int D, int n_active,
-                                     int32_t* d_pred, const int32_t* d_m, const ttx_sample_params* p, void* stream) {
+// `select` (ttx_debug_sample_step_select): the launch covers n_rows rows stored compacted, row i drawing for layout row d_row_map[i]
+// (null: row i itself), and the probe layout N = 1, D = 0 is accepted.
+static int sample_step_debug(const char* who_c, ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample,
+                             const int32_t* d_act_idx, const int32_t* d_front, int B, int N, int D, int n_active, int32_t* d_pred,
+                             const int32_t* d_m, const ttx_sample_params* p, void* stream, bool select, const int32_t* d_row_map,
+                             int n_rows) {
+  const std::string who(who_c);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (!s || !d_logits || !d_key || !d_sample || !d_act_idx || !d_front || !d_pred || !p)
-    return fail(TTX_ERR_INVALID, "null argument to ttx_debug_sample_step");
-  if (V < 1 || V > SAMPLE_MAX_V) return fail(TTX_ERR_INVALID, "ttx_debug_sample_step: V must be in [1, 1024]");
-  if (B < 1 || N < 1 || D < 1 || (long long)B * step_rps(N, D) * V >= (1ll << 31))
-    return fail(TTX_ERR_INVALID, "ttx_debug_sample_step: B, N and D must be positive and the logits below 2^31 elements");
-  if (n_active < 0 || n_active > B) return fail(TTX_ERR_INVALID, "ttx_debug_sample_step: n_active must lie in [0, B]");
-  if (!d_m && n_active != B) return fail(TTX_ERR_INVALID, "ttx_debug_sample_step: without a live row count every slot must be active");
-  SampleBlock blk{};
-  TTX_TRY(sample_block("ttx_debug_sample_step", p, &blk));
-  HIP_TRY(hipSetDevice(s->m->device));
+    return fail(TTX_ERR_INVALID, "null argument to " + who);
+  if (V < 1 || V > SAMPLE_MAX_V) return fail(TTX_ERR_INVALID, who + ": V must be in [1, 1024]");
+  const bool probe = select && N == 1 && D == 0;
+  if (B < 1 || N < 1 || (D < 1 && !probe) || (long long)B * step_rps(N, D) * V >= (1ll << 31))
+    return fail(TTX_ERR_INVALID, who + ": B, N and D must be positive and the logits below 2^31 elements");
+  if (n_active < 0 || n_active > B) return fail(TTX_ERR_INVALID, who + ": n_active must lie in [0, B]");
+  if (!select && !d_m && n_active != B) return fail(TTX_ERR_INVALID, who + ": without a live row count every slot must be active");
   const int RPS = step_rps(N, D);
+  if (select && (n_rows < 1 || n_rows > n_active * RPS)) return fail(TTX_ERR_INVALID, who + ": n_rows must lie in [1, n_active * (1 + N*D)]");
+  if (select && !d_row_map && n_rows != n_active * RPS) return fail(TTX_ERR_INVALID, who + ": without a row map the launch covers every row of the active slots");
+  SampleBlock blk{};
+  TTX_TRY(sample_block(who_c, p, &blk));
+  HIP_TRY(hipSetDevice(s->m->device));
   int max_front = 0;
-  TTX_TRY(dbg_check_slots("ttx_debug_sample_step", d_act_idx, d_front, B, n_active, 1 << 30, D, st, &max_front));
+  TTX_TRY(dbg_check_slots(who_c, d_act_idx, d_front, B, n_active, 1 << 30, D, st, &max_front));
+  const int M = select ? n_rows : B * RPS;
   if (d_m) {
     int32_t m = -1;
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipMemcpy(&m, d_m, 4, hipMemcpyDeviceToHost));
-    if (m < 0 || m > n_active * RPS) return fail(TTX_ERR_INVALID, "ttx_debug_sample_step: the live row count on the device is outside [0, n_active * (1 + N*D)]");
+    if (m < 0 || m > (select ? n_rows : n_active * RPS)) return fail(TTX_ERR_INVALID, who + ": the live row count on the device is outside the launch's rows");
+  }
+  if (d_row_map) {
+    std::vector<int32_t> map((size_t)n_rows);
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(map.data(), d_row_map, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
+    for (const int32_t r : map)
+      if (r < 0 || r >= n_active * RPS) return fail(TTX_ERR_INVALID, who + ": a row map entry lies outside the active slots' rows");
   }
   TTX_TRY(ensure(s->smp_prm, sizeof(SampleBlock), st));
   hipLaunchKernelGGL(k_sample_params, dim3(1), dim3(64), 0, st, s->smp_prm.as<SampleBlock>(), blk);
   HIP_TRY(hipGetLastError());
   SampleStepArgs a{};
-  a.logits = d_logits; a.V = V; a.pred = d_pred; a.m_ptr = d_m; a.M = B * RPS;
+  a.logits = d_logits; a.V = V; a.pred = d_pred; a.m_ptr = d_m; a.M = M;
   a.key = reinterpret_cast<const unsigned long long*>(d_key); a.sample = d_sample; a.act_idx = d_act_idx; a.front = d_front;
-  a.N = N; a.D = D; a.prm = s->smp_prm.as<SampleBlock>();
+  a.N = N; a.D = D; a.prm = s->smp_prm.as<SampleBlock>(); a.row_map = d_row_map;
   return launch_sample_step(st, a);
+}
+
+extern "C" int ttx_debug_sample_step(ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample,
+                                     const int32_t* d_act_idx, const int32_t* d_front, int B, int N, int D, int n_active,
+                                     int32_t* d_pred, const int32_t* d_m, const ttx_sample_params* p, void* stream) {
+  return sample_step_debug("ttx_debug_sample_step", s, d_logits, V, d_key, d_sample, d_act_idx, d_front, B, N, D, n_active, d_pred, d_m, p,
+                           stream, false, nullptr, 0);
+}
+
+extern "C" int ttx_debug_sample_step_select(ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample,
+                                            const int32_t* d_act_idx, const int32_t* d_front, int B, int N, int D, int n_active,
+                                            int32_t* d_pred, const int32_t* d_m, const ttx_sample_params* p, const int32_t* d_row_map,
+                                            int n_rows, void* stream) {
+  return sample_step_debug("ttx_debug_sample_step_select", s, d_logits, V, d_key, d_sample, d_act_idx, d_front, B, N, D, n_active, d_pred,
+                           d_m, p, stream, true, d_row_map, n_rows);
 }
 
 // d_row_map (ttx_debug_embed_select; null: ttx_debug_embed): the launch writes m_rows rows, row i holding layout row d_row_map[i]
@@ -3325,10 +3452,17 @@ extern "C" int ttx_debug_embed_select(ttx_session* s, const float* d_table, int 
 }
 
 // ttx_debug_accept; `sample`: ttx_debug_sample_accept, k_sample_accept on the same argument block
-static int accept_debug(ttx_session* s, const ttx_debug_accept_args* a, int64_t* state, void* stream, bool sample) {
+// `sample_pool` (ttx_debug_sample_accept_pool): the sampling rule in pool mode (pool = row_rule = 1; the traj / fin_step pointers are
+// unused), with the executed-row count at d_exec_rows (may be null) and, with `spread`, the pair k_sample_accept_slots +
+// k_accept_finish whatever B is.
+static int accept_debug(ttx_session* s, const ttx_debug_accept_args* a, int64_t* state, void* stream, bool sample, bool sample_pool = false,
+                        const int32_t* d_exec_rows = nullptr, bool spread = false) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (!s || !a || !state) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_accept");
-  if (sample && (a->greedy || a->row_rule || a->pool))
+  if (sample_pool && (a->greedy || !a->row_rule || !a->pool))
+    return fail(TTX_ERR_INVALID, "ttx_debug_sample_accept_pool: greedy must be 0, row_rule and pool 1");
+  if (sample_pool && spread && a->threads != 0) return fail(TTX_ERR_INVALID, "ttx_debug_sample_accept_pool: the pair runs with threads = 0");
+  if (sample && !sample_pool && (a->greedy || a->row_rule || a->pool))
     return fail(TTX_ERR_INVALID, "ttx_debug_sample_accept: greedy, row_rule and pool must be 0");
   if (!a->d_act_idx || !a->d_front || !a->d_gen || !a->d_pred || !a->d_rec)
     return fail(TTX_ERR_INVALID, "ttx_debug_accept: act_idx, front, gen, pred and rec are required");
@@ -3340,7 +3474,9 @@ static int accept_debug(ttx_session* s, const ttx_debug_accept_args* a, int64_t*
   if (a->pool && !a->row_rule) return fail(TTX_ERR_INVALID, "ttx_debug_accept: pool implies row_rule");
   if (!greedy && !a->pool && !a->d_out) return fail(TTX_ERR_INVALID, "ttx_debug_accept: out is required outside pool mode");
   if (a->row_rule && !a->pool && (!a->d_traj || !a->d_fin_step)) return fail(TTX_ERR_INVALID, "ttx_debug_accept: row_rule needs traj and fin_step");
-  if (a->pool && (!a->d_rstep || !a->d_row_of || !a->d_pool_out || !a->d_pool_traj || !a->d_pool_fin_step || a->pool_rows < 1))
+  if (sample_pool && (!a->d_row_of || !a->d_pool_out || a->pool_rows < 1))
+    return fail(TTX_ERR_INVALID, "ttx_debug_sample_accept_pool: pool mode needs row_of and the caller-side out rows");
+  if (a->pool && !sample_pool && (!a->d_rstep || !a->d_row_of || !a->d_pool_out || !a->d_pool_traj || !a->d_pool_fin_step || a->pool_rows < 1))
     return fail(TTX_ERR_INVALID, "ttx_debug_accept: pool mode needs rstep, row_of and the caller-side out, traj and fin_step rows");
   if (a->row_rule && a->traj_ld < 1) return fail(TTX_ERR_INVALID, "ttx_debug_accept: traj_ld must be positive");
   if (a->B < 1 || a->max_len < 1 || a->gen_ld < 1 || a->Ls < 0) return fail(TTX_ERR_INVALID, "ttx_debug_accept: B, max_len and gen_ld must be positive");
@@ -3403,7 +3539,14 @@ static int accept_debug(ttx_session* s, const ttx_debug_accept_args* a, int64_t*
     // threads = 0 is the production route: above 256 slots the pair, unless TTX_ACCEPT_SPREAD=0
     int rc_blk = TTX_OK;
     la.sample_rule = sample ? 1 : 0;
+    la.exec_rows = d_exec_rows;
     if (!greedy && !sample && a->threads == 0) rc_blk = accept_blk_for(s, st, a->B, &la.blk);
+    if (sample_pool && spread) {
+      const void* before = s->accept_blk.p;
+      rc_blk = ensure(s->accept_blk, sizeof(AcceptBlk), st);
+      if (rc_blk == TTX_OK && s->accept_blk.p != before && hipMemsetAsync(s->accept_blk.p, 0, sizeof(AcceptBlk), st) != hipSuccess) rc_blk = TTX_ERR_HIP;
+      la.blk = s->accept_blk.as<AcceptBlk>();
+    }
     if (rc_blk != TTX_OK) err = hipErrorOutOfMemory;
     else if (sample) {
       if (a->threads == 0) { if (launch_sample_accept(st, la) != TTX_OK) err = hipErrorLaunchFailure; }
@@ -3435,6 +3578,82 @@ extern "C" int ttx_debug_accept(ttx_session* s, const ttx_debug_accept_args* a, 
 
 extern "C" int ttx_debug_sample_accept(ttx_session* s, const ttx_debug_accept_args* a, int64_t* state, void* stream) {
   return accept_debug(s, a, state, stream, true);
+}
+
+extern "C" int ttx_debug_sample_accept_pool(ttx_session* s, const ttx_debug_accept_args* a, int64_t* state, const int32_t* d_exec_rows,
+                                            int spread, void* stream) {
+  return accept_debug(s, a, state, stream, true, true, d_exec_rows, spread != 0);
+}
+
+// One admission of the sampling pool (k_pool_admit, then k_pool_fill unless the admission failed) on the caller's arrays.
+extern "C" int ttx_debug_pool_fill_sample(ttx_session* s, const ttx_debug_pool_fill_args* a, int32_t* result, void* stream) {
+  const std::string who = "ttx_debug_pool_fill_sample";
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !a || !result) return fail(TTX_ERR_INVALID, "null argument to " + who);
+  if (!a->d_act_idx || !a->d_front || !a->d_haspad || !a->d_rstep || !a->d_row_of || !a->d_src_len || !a->d_key || !a->d_sample ||
+      !a->d_gen || !a->d_drafts || !a->d_drafts_new || !a->d_src_valid || !a->d_valid_new || !a->d_memkv || !a->d_memkv_new || !a->d_out)
+    return fail(TTX_ERR_INVALID, who + ": every array but row_keys is required");
+  if (a->B < 1 || a->B > 4096 || a->N < 1 || a->D < 1 || a->n_sources < 1 || a->per_src < 1 || a->first_src < 0 || a->max_len < 1 ||
+      a->gen_ld < 1 || a->Ls_new < 1 || a->Ls_cap < a->Ls_new || a->kv_row < 4 || a->kv_row % 4 != 0 || a->out_rows < 1)
+    return fail(TTX_ERR_INVALID, who + ": sizes must be positive, Ls_new <= Ls_cap, kv_row a multiple of 4, B at most 4096");
+  if (a->n_active < 0 || a->n_active > a->B) return fail(TTX_ERR_INVALID, who + ": n_active must lie in [0, B]");
+  const long long rows = (long long)a->n_sources * a->per_src;
+  if (rows > 4096) return fail(TTX_ERR_INVALID, who + ": at most 4096 rows per admission");
+  if (((long long)a->first_src + a->n_sources) * a->per_src > a->out_rows) return fail(TTX_ERR_INVALID, who + ": the admitted rows lie beyond the caller's out rows");
+  if (!dbg_aligned16(a->d_memkv) || !dbg_aligned16(a->d_memkv_new)) return fail(TTX_ERR_INVALID, who + ": the cross K/V arrays must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(s->m->device));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (a->n_active > 0) {
+    std::vector<int32_t> act((size_t)a->n_active);
+    HIP_TRY(hipMemcpy(act.data(), a->d_act_idx, (size_t)a->n_active * 4, hipMemcpyDeviceToHost));
+    std::vector<char> seen((size_t)a->B, 0);
+    for (const int32_t b : act) {
+      if (b < 0 || b >= a->B || seen[b]) return fail(TTX_ERR_INVALID, who + ": act_idx must hold distinct slots in [0, B)");
+      seen[b] = 1;
+    }
+  }
+  DecState* dst = nullptr;
+  int32_t* d_new_slot = nullptr;
+  HostInfo* hinfo = nullptr;
+  HostInfo* dev_info = nullptr;
+  hipError_t err = hipMalloc((void**)&dst, sizeof(DecState));
+  if (err == hipSuccess) err = hipMalloc((void**)&d_new_slot, (size_t)rows * 4);
+  if (err == hipSuccess) err = hipHostMalloc((void**)&hinfo, sizeof(HostInfo), hipHostMallocMapped);
+  if (err == hipSuccess) err = hipHostGetDevicePointer((void**)&dev_info, (void*)hinfo, 0);
+  DecState hs{};
+  hs.n_active = a->n_active; hs.r_rows = a->n_active * a->N; hs.m_rows = a->n_active * step_rps(a->N, a->D); hs.width = 1;
+  if (err == hipSuccess) err = hipMemcpy(dst, &hs, sizeof(DecState), hipMemcpyHostToDevice);
+  if (err == hipSuccess) {
+    *hinfo = HostInfo{-1, -1, -1, -1};
+    PoolAdmitArgs pa{};
+    pa.st = dst; pa.act_idx = a->d_act_idx; pa.front = a->d_front; pa.haspad = a->d_haspad; pa.rstep = a->d_rstep; pa.row_of = a->d_row_of;
+    pa.src_len = a->d_src_len; pa.new_slot = d_new_slot; pa.host = dev_info; pa.B = a->B; pa.N = a->N; pa.D = a->D; pa.R = (int)rows;
+    pa.first_row = a->first_src * a->per_src; pa.Ls_new = a->Ls_new;
+    pa.key = reinterpret_cast<unsigned long long*>(a->d_key); pa.sample = a->d_sample; pa.row_keys = a->d_row_keys;
+    pa.per_src = a->per_src; pa.first_src = a->first_src;
+    hipLaunchKernelGGL(k_pool_admit, dim3(1), dim3(256), (size_t)a->B * 4, st, pa);
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess) err = hipStreamSynchronize(st);
+  if (err == hipSuccess) err = hipMemcpy(&hs, dst, sizeof(DecState), hipMemcpyDeviceToHost);
+  if (err == hipSuccess && hs.error == 0) {          // a failed admission handed out fewer slots than rows: nothing to fill
+    PoolFillArgs f{};
+    f.new_slot = d_new_slot; f.R = (int)rows; f.gen = a->d_gen; f.gen_ld = a->gen_ld; f.bos = a->bos; f.pad = a->pad;
+    f.drafts = a->d_drafts; f.drafts_new = a->d_drafts_new; f.nd = a->N * a->D;
+    f.src_valid = a->d_src_valid; f.valid_new = a->d_valid_new; f.Ls_cap = a->Ls_cap; f.Ls_new = a->Ls_new;
+    f.memkv = a->d_memkv; f.memkv_new = a->d_memkv_new; f.kv_row = a->kv_row;
+    f.out_rows = a->d_out; f.max_len = a->max_len; f.traj_ld = a->max_len + 1; f.first_row = a->first_src * a->per_src;
+    f.per_src = a->per_src;
+    hipLaunchKernelGGL(k_pool_fill, dim3((int)rows, 1 + a->Ls_new), dim3(256), 0, st, f);
+    err = hipGetLastError();
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+  }
+  if (err == hipSuccess) { result[0] = hs.n_active; result[1] = hs.m_rows; result[2] = hs.error; result[3] = hinfo->n_active; }
+  if (d_new_slot) (void)hipFree(d_new_slot);
+  if (dst) (void)hipFree(dst);
+  if (hinfo) (void)hipHostFree(hinfo);
+  HIP_TRY(err);
+  return TTX_OK;
 }
 
 extern "C" int ttx_debug_accept_block(ttx_session* s, int32_t* words, int n_words, void* stream) {

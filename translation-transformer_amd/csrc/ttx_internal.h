@@ -79,8 +79,10 @@ enum AttnKernelId { AK_ATTN = 1, AK_ATTN2 = 2, AK_ATTN3 = 3, AK_ATTN3S = 4, AK_A
 //   GS_STEP_SAMPLE                the greedy step's key with k_sample in k_argmax's place (ttx_sample_generate); B counts decoder rows
 //   GS_STEP_SAMPLE_SPEC           the speculative step's key with k_sample_step and k_sample_accept in k_argmax's and k_accept's place
 //                                 (ttx_sample_speculative_generate); B counts decoder rows
+//   GS_STEP_POOL_SAMPLE           GS_STEP_POOL's key and phases with k_sample_step and the sampling accept in k_argmax's and k_accept's
+//                                 place (ttx_sample_speculative_generate_pool): never a graph of the greedy pool
 enum GraphSite { GS_STEP_SPECULATIVE = 0, GS_STEP_GREEDY = 1, GS_STEP_ROW_RULE = 2, GS_STEP_POOL = 3, GS_BEAM_ITER = 4, GS_BEAM_POOL_ITER = 5,
-                 GS_STEP_SAMPLE = 6, GS_STEP_SAMPLE_SPEC = 7 };
+                 GS_STEP_SAMPLE = 6, GS_STEP_SAMPLE_SPEC = 7, GS_STEP_POOL_SAMPLE = 8 };
 typedef std::vector<int> GraphKey;
 
 // Captured graphs of one family of keys.  A key runs eagerly the first time it is seen (`warmed`: function attributes are set
@@ -150,7 +152,7 @@ struct ttx_session {
   Buf tk[2], tv[2];                // tree (beam) decoding: the two cache buffers an iteration derives one from the other
   int snap_B = 0, snap_rps = 0, snap_gen_ld = 0, snap_step = 0;        // what snap_* hold
   ttx::ProbeInfo* probe_info = nullptr; // pinned + device-mapped, written by k_probe_split
-  // ttx_pool_last_counters: summed over the pools of the last ttx_greedy_speculative_generate_pool call whose first session this was
+  // ttx_pool_last_counters: summed over the pools of the last slot-pool call (greedy or sampling) whose first session this was
   long long pool_counters[7] = {};
   ttx::BeamHost* beam_host = nullptr;   // pinned + device-mapped, written by k_bs_publish
   ttx::BeamPoolHost* bp_host = nullptr; // pinned + device-mapped, written by k_bsp_publish

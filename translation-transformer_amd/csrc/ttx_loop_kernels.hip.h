@@ -374,13 +374,11 @@ __global__ __launch_bounds__(ACCEPT_THREADS) void k_accept(LoopArgs a) {
 // accept_slot by one wave: lane e compares element e of the slot's N x D draft tokens with its prediction, so the reads of a slot
 // are one or two coalesced round trips instead of a chain of D dependent ones; the first mismatch of every draft comes out of the
 // wave's ballot, draft after draft in order (a draft may straddle two passes of 64 elements).  Every value below is wave-uniform.
-__device__ __forceinline__ SlotStep accept_slot_wave(const LoopArgs& a, const DecState* st, int slot, int lane) {
-  const int RPS = step_rps(a.N, a.D), ND = a.N * a.D;
-  const int b = a.act_idx[slot];
-  const int f = a.front[b];
-  const int* ps = a.pred + (size_t)slot * RPS;
+__device__ __forceinline__ void accept_best_draft_wave(const LoopArgs& a, int b, const int* ps, int lane, int& best, int& bacc) {
+  const int ND = a.N * a.D;
   const int* dr = a.drafts + (size_t)b * ND;
-  int best = 0, bacc = -1, open_acc = a.D;
+  int open_acc = a.D;
+  best = 0; bacc = -1;
   for (int base = 0; base < ND; base += 64) {
     const int e = base + lane;
     bool miss = false;
@@ -395,6 +393,15 @@ __device__ __forceinline__ SlotStep accept_slot_wave(const LoopArgs& a, const De
       if (end <= base + 64 && open_acc > bacc) { bacc = open_acc; best = n; }     // complete: the first maximum wins
     }
   }
+}
+
+__device__ __forceinline__ SlotStep accept_slot_wave(const LoopArgs& a, const DecState* st, int slot, int lane) {
+  const int RPS = step_rps(a.N, a.D);
+  const int b = a.act_idx[slot];
+  const int f = a.front[b];
+  const int* ps = a.pred + (size_t)slot * RPS;
+  int best, bacc;
+  accept_best_draft_wave(a, b, ps, lane, best, bacc);
   int* g = a.gen + (size_t)b * a.gen_ld;
   bool fin = false, sawpad = false;
   for (int j0 = 0; j0 <= bacc; j0 += 64) {
@@ -413,7 +420,9 @@ __device__ __forceinline__ SlotStep accept_slot_wave(const LoopArgs& a, const De
 // capacity, and sums into `blk`; k_accept_finish (one workgroup of ACCEPT_THREADS) does the rest from `blk`.  Same state as
 // k_accept from the same operands.
 constexpr int ACCEPT_SLOT_WAVES = 4;
-__global__ __launch_bounds__(ACCEPT_SLOT_WAVES * 64) void k_accept_slots(LoopArgs a) {
+__device__ __forceinline__ SlotStep sample_accept_slot_wave(const LoopArgs& a, int slot, int lane);
+template <bool SAMPLE>
+__device__ __forceinline__ void accept_slots_body(const LoopArgs& a) {
   __shared__ int s_maxfront;
   __shared__ unsigned long long s_acc, s_prefix;
   const DecState* st = a.st;
@@ -423,7 +432,7 @@ __global__ __launch_bounds__(ACCEPT_SLOT_WAVES * 64) void k_accept_slots(LoopArg
   __syncthreads();
   const int slot = blockIdx.x * ACCEPT_SLOT_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (slot < Bc) {
-    const SlotStep r = accept_slot_wave(a, st, slot, lane);
+    const SlotStep r = SAMPLE ? sample_accept_slot_wave(a, slot, lane) : accept_slot_wave(a, st, slot, lane);
     if (lane == 0) {
       atomicMax(&s_maxfront, r.f);
       atomicAdd(&s_acc, (unsigned long long)r.bacc);
@@ -441,6 +450,8 @@ __global__ __launch_bounds__(ACCEPT_SLOT_WAVES * 64) void k_accept_slots(LoopArg
     atomicAdd(&a.blk->prefix, s_prefix);
   }
 }
+
+__global__ __launch_bounds__(ACCEPT_SLOT_WAVES * 64) void k_accept_slots(LoopArgs a) { accept_slots_body<false>(a); }
 
 __global__ __launch_bounds__(ACCEPT_THREADS) void k_accept_finish(LoopArgs a) {
   DecState* st = a.st;
@@ -480,6 +491,36 @@ __device__ __forceinline__ SlotStep sample_accept_slot(const LoopArgs& a, int sl
   return SlotStep{b, f, bacc, fin};
 }
 
+// sample_accept_slot by one wave, as accept_slot_wave is accept_slot by one wave: the same choice of draft, the same tokens, the
+// same ending rule.  Every value is wave-uniform.
+__device__ __forceinline__ SlotStep sample_accept_slot_wave(const LoopArgs& a, int slot, int lane) {
+  const int RPS = step_rps(a.N, a.D);
+  const int b = a.act_idx[slot];
+  const int f = a.front[b];
+  const int* ps = a.pred + (size_t)slot * RPS;
+  int best, bacc;
+  accept_best_draft_wave(a, b, ps, lane, best, bacc);
+  int* g = a.gen + (size_t)b * a.gen_ld;
+  bool fin = false;
+  for (int j0 = 0; j0 <= bacc; j0 += 64) {
+    const int j = j0 + lane;
+    int t = -1;
+    if (j <= bacc) { t = ps[j == 0 ? 0 : best * a.D + j]; g[f + 1 + j] = t; }
+    fin |= __ballot(j <= bacc && (t == a.eos || t == a.pad) && f + 1 + j < a.max_len) != 0;
+  }
+  const int nf = f + bacc + 1;
+  fin |= nf >= a.max_len - 1;
+  if (lane == 0) {
+    a.front[b] = nf;
+    a.rec[slot] = CopyRec{b, best, bacc, f, fin ? 1 : 0};
+  }
+  return SlotStep{b, f, bacc, fin};
+}
+
+// The per-slot part of k_sample_accept on a grid sized for the capacity (pools of more than 256 slots), summing into `blk`;
+// k_accept_finish follows it and leaves the block zero.
+__global__ __launch_bounds__(ACCEPT_SLOT_WAVES * 64) void k_sample_accept_slots(LoopArgs a) { accept_slots_body<true>(a); }
+
 // One block, any slot count by rounds of blockDim.x.  The rest of the step is accept_finish as it runs under the per-row rule: it
 // copies max_len columns of every ended row out, keeps the rows with flags 0 in order, sums the counters, stops when nobody runs
 // and publishes.  haspad stays zero on this path (k_loop_init), so accept_finish raises no error here.
@@ -503,7 +544,7 @@ __global__ __launch_bounds__(ACCEPT_THREADS) void k_sample_accept(LoopArgs a) {
     }
   }
   __syncthreads();
-  a.row_rule = 1; a.pool = 0; a.exec_rows = nullptr;
+  a.row_rule = 1;                                    // pool and exec_rows are the caller's: zero on the single-session path
   accept_finish(a, st, Bc, s_maxfront, s_nfin, s_finlist, s_acc, s_prefix);
 }
 
@@ -529,6 +570,9 @@ __global__ void k_pool_init(LoopArgs a) {
 struct PoolAdmitArgs {
   DecState* st; int* act_idx; int* front; int* haspad; int* rstep; int* row_of; int* src_len; int* new_slot; HostInfo* host;
   int B, N, D, R, first_row, Ls_new;
+  // sampling pool (key null: the greedy pool): the R rows are per_src consecutive samples of R / per_src sources, first_row =
+  // first_src * per_src; row i gets the key of source first_src + i / per_src (row_keys null: that index) and sample id i % per_src
+  unsigned long long* key; unsigned* sample; const int64_t* row_keys; int per_src, first_src;
 };
 
 // One block.  Free slots = those not in act_idx[0, n_active); the R new rows take the lowest free ones in order.
@@ -549,6 +593,11 @@ __global__ __launch_bounds__(256) void k_pool_admit(PoolAdmitArgs a) {
       a.front[b] = 0; a.haspad[b] = 0; a.rstep[b] = 0;
       a.row_of[b] = a.first_row + got;
       a.src_len[b] = a.Ls_new;
+      if (a.key) {
+        const int src = a.first_src + got / a.per_src;
+        a.key[b] = a.row_keys ? (unsigned long long)a.row_keys[src] : (unsigned long long)src;
+        a.sample[b] = (unsigned)(got % a.per_src);
+      }
       ++got;
     }
     // the host only admits as many rows as it knows to be free, so got == R
@@ -569,6 +618,9 @@ struct PoolFillArgs {
   uint8_t* src_valid; const uint8_t* valid_new; int Ls_cap; int Ls_new;
   float* memkv; const float* memkv_new; int kv_row;                   // floats per source position (Ld * 2 * d)
   int64_t* out_rows; short* traj_rows; int* fin_rows; int max_len; int traj_ld; int first_row;   // caller arrays of these rows
+  // sampling pool (0: the greedy pool): row i takes the staged drafts, validity bytes and cross K/V of source i / per_src, its
+  // caller row starts as the sampler's (BOS in column 0), and there are no traj / fin_step rows
+  int per_src;
 };
 
 // grid (R, 1 + Ls_new): block (i, 0) initialises row i's slot scalars and its caller-side rows, block (i, 1 + key)
@@ -577,18 +629,23 @@ __global__ __launch_bounds__(256) void k_pool_fill(PoolFillArgs a) {
   const int i = blockIdx.x;
   const int b = a.new_slot[i];
   const int t = threadIdx.x;
+  const int is = a.per_src ? i / a.per_src : i;     // staged source of row i
   if (blockIdx.y == 0) {
     for (int c = t; c < a.gen_ld; c += blockDim.x) a.gen[(size_t)b * a.gen_ld + c] = (c == 0) ? a.bos : a.pad;
-    for (int c = t; c < a.nd; c += blockDim.x) a.drafts[(size_t)b * a.nd + c] = a.drafts_new[(size_t)i * a.nd + c];
+    for (int c = t; c < a.nd; c += blockDim.x) a.drafts[(size_t)b * a.nd + c] = a.drafts_new[(size_t)is * a.nd + c];
     for (int c = t; c < a.Ls_cap; c += blockDim.x)
-      a.src_valid[(size_t)b * a.Ls_cap + c] = (c < a.Ls_new) ? a.valid_new[(size_t)i * a.Ls_new + c] : (uint8_t)0;
+      a.src_valid[(size_t)b * a.Ls_cap + c] = (c < a.Ls_new) ? a.valid_new[(size_t)is * a.Ls_new + c] : (uint8_t)0;
     const size_t row = (size_t)(a.first_row + i);
-    for (int c = t; c < a.max_len; c += blockDim.x) a.out_rows[row * a.max_len + c] = a.pad;
-    for (int c = t; c < a.traj_ld; c += blockDim.x) a.traj_rows[row * a.traj_ld + c] = (c == 0) ? 0 : -1;
-    if (t == 0) a.fin_rows[row] = 0;
+    if (a.per_src) {
+      for (int c = t; c < a.max_len; c += blockDim.x) a.out_rows[row * a.max_len + c] = (c == 0) ? a.bos : a.pad;
+    } else {
+      for (int c = t; c < a.max_len; c += blockDim.x) a.out_rows[row * a.max_len + c] = a.pad;
+      for (int c = t; c < a.traj_ld; c += blockDim.x) a.traj_rows[row * a.traj_ld + c] = (c == 0) ? 0 : -1;
+      if (t == 0) a.fin_rows[row] = 0;
+    }
   } else {
     const int key = blockIdx.y - 1;
-    const float4* src = reinterpret_cast<const float4*>(a.memkv_new + ((size_t)i * a.Ls_new + key) * a.kv_row);
+    const float4* src = reinterpret_cast<const float4*>(a.memkv_new + ((size_t)is * a.Ls_new + key) * a.kv_row);
     float4* dst = reinterpret_cast<float4*>(a.memkv + ((size_t)b * a.Ls_cap + key) * a.kv_row);
     for (int c = t; c < a.kv_row / 4; c += blockDim.x) dst[c] = src[c];
   }

@@ -233,6 +233,9 @@ __global__ __launch_bounds__(256) void k_sample(const SampleArgs a) {
 // (key[b], sample[b], that position): what k_sample emits there from the same logits.  key and sample are indexed by decoder row,
 // not by slot (the active list compacts).  k_argmax's launch shape and live-row rule; no done flags (rows retire through the
 // active list); rows at or beyond *m_ptr are not written.
+// Slot pool: `act_idx` is the list of the pass (the probe's: every live slot; the draft pass's: the matching slots), `pred` the
+// pass's own buffer, and under draft select `row_map` gives the layout row of every compacted row as k_embed<true> reads it: the
+// logits and pred are indexed by the compacted row, the position comes from the layout row.  The probe layout is N = 1, D = 0.
 struct SampleStepArgs {
   const float* logits; int V;      // [M, V]
   int* pred;                       // [M]
@@ -243,6 +246,7 @@ struct SampleStepArgs {
   const int* front;                // [B]
   int N, D;
   const SampleBlock* prm;
+  const int* row_map;              // [rows] or null: row = layout row
 };
 
 template <int VPL>
@@ -253,9 +257,11 @@ __global__ __launch_bounds__(256) void k_sample_step(const SampleStepArgs a) {
   const int lane = threadIdx.x & 63;
   const SampleBlock prm = *a.prm;
   const int RPS = step_rps(a.N, a.D);
-  const int rs = row % RPS;
-  const int b = a.act_idx[row / RPS];
-  const int pos = a.front[b] + (rs == 0 ? 1 : 2 + (rs - 1) % a.D);
+  const int lrow = a.row_map ? a.row_map[row] : row;
+  const int rs = lrow % RPS;
+  const int b = a.act_idx[lrow / RPS];
+  int pos = a.front[b] + 1;
+  if (rs != 0 && a.D > 0) pos += 1 + (rs - 1) % a.D;       // the probe (D == 0) has row 0 only
   const int tok = sample_row<VPL>(a.logits + (size_t)row * a.V, a.V, prm, a.key[b], a.sample[b], (unsigned)pos, lane);
   if (lane == 0) a.pred[row] = tok;
 }

@@ -59,6 +59,20 @@ class _ScoresHypotheses:
         return [(p, None if p is None else self.score(b, p)) for b, p in zip(batches, preds)]
 
 
+def _slot_pool_plan(rows: int, in_flight: int, capacity: int | None) -> tuple:
+    """(slots per pool, sessions) of a slot-pool call over ``rows`` decoder rows: 1 024 slots x 3 pools for lists that fill them, else
+    512 slots x 5 pools (measured; profiles/r08_sweep_c2_pools.txt, profiles/r03_sweep_c2_pools.txt); a given
+    ``capacity`` or TTX_POOL_CAPACITY sets the slots, TTX_POOL_SESSIONS the sessions (experiments).  One rule for the
+    greedy pool and the sampling pool."""
+    by_default = not (capacity or os.environ.get("TTX_POOL_CAPACITY"))
+    cap = int(capacity or os.environ.get("TTX_POOL_CAPACITY") or (1024 if rows >= 3 * 1024 else 512))
+    n_pools = 3 if (by_default and cap == 1024) else max(1, 2560 // cap)
+    n_sess = max(1, min(in_flight, n_pools, -(-rows // 32)))
+    if os.environ.get("TTX_POOL_SESSIONS"):
+        n_sess = max(1, int(os.environ["TTX_POOL_SESSIONS"]))
+    return cap, n_sess
+
+
 class TranslationInferenceGreedySpeculative(_ScoresHypotheses):
     """Drop-in for src/decoding/speculative_decoding.py:8-174: copy-drafts, one parallel verify pass per
     step, longest accepted prefix + 1 bonus token — the whole loop runs in ttx_greedy_speculative_generate."""
@@ -203,7 +217,7 @@ class TranslationInferenceGreedySpeculative(_ScoresHypotheses):
         # occupancy, but at least `in_flight` groups should exist so that tails overlap
         if pool:      # slot pool: 1 024 slots x 3 pools for lists that fill them, else 512 slots x 5 pools (measured, DESIGN.md
             # §6); lists that fit the pools at once are split evenly
-            gsz = int(group_size or os.environ.get("TTX_POOL_CAPACITY") or (1024 if R >= 3 * 1024 else 512))
+            gsz, pool_sessions = _slot_pool_plan(R, in_flight, group_size)
         else:
             gsz = int(group_size or min(256, max(max(sizes), -(-R // max(1, in_flight)))))
         self.last_group_size = gsz
@@ -231,12 +245,7 @@ class TranslationInferenceGreedySpeculative(_ScoresHypotheses):
             # the default of a list that fills them is three pools of 1 024 slots since the verify step runs in two phases
             # (profiles/r08_sweep_c2_pools.txt); every other case keeps the rule it had (five pools of 512:
             # profiles/r03_sweep_c2_pools.txt)
-            by_default = not (group_size or os.environ.get("TTX_POOL_CAPACITY"))
-            n_pools = 3 if (by_default and gsz == 1024) else max(1, 2560 // gsz)
-            n_sess = max(1, min(in_flight, n_pools, -(-R // 32)))
-            if os.environ.get("TTX_POOL_SESSIONS"):                               # experiments
-                n_sess = max(1, int(os.environ["TTX_POOL_SESSIONS"]))
-            sessions = m.session_pool(n_sess)
+            sessions = m.session_pool(pool_sessions)
             sess = (C.c_void_p * len(sessions))(*[q.value for q in sessions])
             width = max(2, int(sorted_len.max()))
             src_mat = sorted_src[:, :width].contiguous() if width <= sorted_src.shape[1] else torch.nn.functional.pad(
@@ -446,6 +455,92 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         t["batches"] += 1
         self.last_stats = st
         return self._scored(src, out, return_scores)
+
+    def generate_many(self, batches: list, row_keys=None, in_flight: int = 4, capacity: int | None = None,
+                      return_scores: bool = False) -> list:
+        """The samples of all batches from slot pools (ttx_sample_speculative_generate_pool: continuous batching over the sources
+        of the whole list, sorted by length; the ``num_samples`` rows of a source are admitted together).  Returns one
+        Long[B_i, num_samples, max_len] per batch.
+
+        ``row_keys``: one sequence of integers per batch; by default the running index over the concatenated batches, so that
+        ``generate_many(batches)[i]`` holds the rows of ``generate(batches[i], row_keys=arange(off_i, off_i + B_i))``.  A row does
+        not depend on its slot, on the capacity or on what shares the pool.  ``capacity`` (slots, i.e. decoder rows, per pool;
+        ``TTX_POOL_CAPACITY``) and the pool count follow the greedy generator's rule over the ``S * num_samples`` decoder rows and
+        are never below ``num_samples``.  ``model_calls_num`` counts the verify steps the device executed.
+        ``return_scores=True``: a list of ``(pred, HypothesisScores)`` pairs."""
+        if return_scores:
+            return self._scored_many(batches, self.generate_many(batches, row_keys, in_flight, capacity))
+        from .scheduling import plan_row_groups
+        if not batches:
+            return []
+        m, n, L = self.model, self.num_samples, self.max_len
+        srcs = [b.to(m.device, torch.int64) for b in batches]
+        sizes = [int(s.shape[0]) for s in srcs]
+        S = sum(sizes)
+        if row_keys is None:
+            keys = torch.arange(S, dtype=torch.int64)
+        else:
+            if len(row_keys) != len(srcs):
+                raise ValueError(f"row_keys must hold one sequence per batch ({len(srcs)}), got {len(row_keys)}")
+            per = [torch.as_tensor(k, dtype=torch.int64).reshape(-1).cpu() for k in row_keys]
+            for i, (k, B) in enumerate(zip(per, sizes)):
+                if k.shape != (B,):
+                    raise ValueError(f"row_keys[{i}] must hold one key per source ({B}), got shape {tuple(k.shape)}")
+            keys = torch.cat(per) if per else torch.zeros(0, dtype=torch.int64)
+        p = N.SampleSpecParams(N.SampleParams(L, n, self.temperature, self.top_k, self.top_p, self.pad_token, self.bos_token,
+                                              self.eos_token, self.seed & 0xFFFFFFFFFFFFFFFF),
+                               self.draft_len, self.n_drafts, self.replace_token, 0)
+        R = S * max(n, 1)
+        cap, n_sess = _slot_pool_plan(R, in_flight, capacity)
+        cap = max(cap, n)
+        self.last_group_size, self.last_pool_sessions = cap, n_sess
+        # all sources in one right-padded matrix, sorted by length (longest first) with their keys
+        Lmax = max([int(s.shape[1]) for s in srcs if s.shape[0]] or [2])
+        allsrc = torch.full((S, Lmax), self.pad_token, dtype=torch.int64, device=m.device)
+        r0 = 0
+        for s in srcs:
+            allsrc[r0:r0 + s.shape[0], :s.shape[1]] = s
+            r0 += s.shape[0]
+        m.check_tokens(allsrc)
+        out_sorted = torch.empty((S, max(n, 1), max(L, 1)), dtype=torch.int64, device=m.device)
+        st = N.GenStats()
+        if S:
+            pos = torch.arange(1, Lmax + 1, device=m.device)
+            lengths = ((allsrc != self.pad_token) * pos).amax(dim=1)
+            order, _ = plan_row_groups(lengths.cpu().numpy(), cap)
+            order_t = torch.from_numpy(order).to(m.device)
+            sorted_len = lengths[order_t].cpu().numpy()
+            width = max(2, int(sorted_len.max()))
+            sorted_src = allsrc[order_t]
+            src_mat = sorted_src[:, :width].contiguous() if width <= Lmax else torch.nn.functional.pad(
+                sorted_src, (0, width - Lmax), value=self.pad_token).contiguous()
+            keys_sorted = keys.to(m.device)[order_t].contiguous()
+            h_len = (C.c_int32 * S)(*[int(x) for x in sorted_len])
+            sessions = m.session_pool(n_sess)
+            sess = (C.c_void_p * len(sessions))(*[q.value for q in sessions])
+            N.check(m._lib.ttx_sample_speculative_generate_pool(sess, len(sessions), src_mat.data_ptr(), S, width, h_len,
+                                                                keys_sorted.data_ptr(), cap, C.byref(p), out_sorted.data_ptr(),
+                                                                C.byref(st), m._stream()))
+            inv = torch.empty_like(order_t)
+            inv[order_t] = torch.arange(S, device=m.device)
+            out_rows = out_sorted[inv]
+            self.given_tokens += int((allsrc != m.src_pad_token_i).sum())
+        else:
+            out_rows = out_sorted
+        self.model_calls_num += int(st.model_calls)
+        self.accepted_tokens_num += int(st.accepted_tokens)
+        t = self.stats_total
+        for k in ("accepted_tokens", "produced_tokens", "verified_positions", "kv_prefix_positions", "src_positions", "encode_ms",
+                  "decode_ms", "src_tokens_padded"):
+            t[k] += getattr(st, k)
+        t["batches"] += len(srcs)
+        t["pool_calls"] = t.get("pool_calls", 0) + 1
+        self.last_stats = st
+        outs, r0 = [], 0
+        for B in sizes:
+            outs.append(out_rows[r0:r0 + B].contiguous())
+            r0 += B
+        return outs
 
 
 class TranslationInferenceBeamSearch(_ScoresHypotheses):

@@ -107,6 +107,7 @@ class _PredictAhead:
         self.enabled = True
         self.served = self.fallbacks = self.windows = 0
         self.decode_seconds = 0.0
+        self.rows = 0                # sources decoded ahead so far: the running index the sampling generators key their rows by
 
     def _decode_window(self, device) -> None:
         pending = []
@@ -123,6 +124,13 @@ class _PredictAhead:
         t0 = timer()
         if isinstance(g, D.TranslationInferenceGreedySpeculative):      # slot pools over all rows of the window
             preds = g.generate_many(pending, in_flight=self.in_flight, reorder=True, on_error="skip")
+        elif isinstance(g, D.TranslationInferenceSamplingSpeculative):  # slot pools over all sources, keyed as predict_step keys them
+            keys, r0 = [], self.rows
+            for b in pending:
+                keys.append(torch.arange(r0, r0 + int(b.shape[0])))
+                r0 += int(b.shape[0])
+            preds = g.generate_many(pending, row_keys=keys, in_flight=self.in_flight)
+            self.rows = r0
         else:                                                           # source pools over all sources of the window
             preds = g.generate_many(pending, in_flight=self.in_flight, on_error="skip")
         shares = list(getattr(g, "last_batch_counters", [])) or [None] * len(pending)
@@ -201,6 +209,9 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         # batches decoded ahead of predict_step (0: decode every batch inside its own predict_step like the reference);
         # not an init_arg, so the reference's YAML files load unchanged — set the attribute or TTX_PREDICT_WINDOW
         self.predict_window = 256
+        # speculative sampling: decode the look-ahead windows through generate_many (slot pools over the sources of a window, the
+        # reactions' running indices as row keys); like predict_window no init_arg — set the attribute or TTX_PREDICT_SAMPLE_POOL=1
+        self.predict_sample_pool = False
         # predict_step also scores its hypotheses (NativeTransformer.score_hypotheses) into self.predict_scores[batch_idx];
         # like predict_window no init_arg — set the attribute or TTX_PREDICT_SCORES=1
         self.predict_with_scores = False
@@ -286,7 +297,9 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         pred = None
         if ahead is not None and dataloader_idx == 0:
             pred = ahead.take(batch["src_tokens"], batch_idx)
-        if pred is None and self.hparams.generation in ("sampling", "sampling_speculative"):
+        if pred is not None and self.hparams.generation in ("sampling", "sampling_speculative"):
+            self._predict_rows += int(batch["src_tokens"].shape[0])        # served ahead under these keys: a fallback goes on from here
+        elif pred is None and self.hparams.generation in ("sampling", "sampling_speculative"):
             B = int(batch["src_tokens"].shape[0])
             pred = self.generator.generate(batch["src_tokens"], row_keys=torch.arange(self._predict_rows, self._predict_rows + B))
             self._predict_rows += B
@@ -378,7 +391,10 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         self._attention_seconds = 0.0
         self._scoring_seconds, self._top1_n, self._top1_sum, self._unfinished = 0.0, 0, 0.0, 0
         window = int(os.environ.get("TTX_PREDICT_WINDOW", str(self.predict_window)))
-        if window > 0 and hasattr(self.generator, "generate_many"):
+        # speculative sampling decodes per batch unless asked to pool: predict_sample_pool / TTX_PREDICT_SAMPLE_POOL=1
+        pooled = not isinstance(self.generator, D.TranslationInferenceSamplingSpeculative) or bool(self.predict_sample_pool) \
+            or os.environ.get("TTX_PREDICT_SAMPLE_POOL") == "1"
+        if window > 0 and pooled and hasattr(self.generator, "generate_many"):
             loader = self._predict_loader()
             # a second pass over the loader must not consume it: one-shot iterators (iter(x) is x) are decoded per batch
             if loader is not None and iter(loader) is not loader:

@@ -361,6 +361,55 @@ class NativeTransformer:
         return self.debug_accept(state, B=B, n=n, d=d, Ls=Ls, max_len=max_len, pad=pad, bos=bos, eos=eos, gen_ld=gen_ld,
                                  threads=threads, _entry="ttx_debug_sample_accept", **arrays)
 
+    def debug_sample_step_select(self, logits: torch.Tensor, key: torch.Tensor, sample: torch.Tensor, act_idx: torch.Tensor,
+                                 front: torch.Tensor, pred: torch.Tensor, *, B: int, n: int, d: int, n_active: int, n_rows: int,
+                                 row_map: torch.Tensor | None = None, m_live: torch.Tensor | None = None, temperature: float = 1.0,
+                                 top_k: int = 0, top_p: float = 1.0, pad: int = 0, eos: int = 2, seed: int = 0) -> None:
+        """One k_sample_step launch as a pass of the slot pool runs it (ttx_debug_sample_step_select): ``debug_sample_step``'s
+        operands with ``logits`` [n_rows, V] and ``pred`` [n_rows] stored compacted and ``row_map`` int32 [n_rows] (None: the
+        identity); the probe layout n = 1, d = 0 is accepted."""
+        p = N.SampleParams(1, 1, float(temperature), int(top_k), float(top_p), int(pad), 0, int(eos), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        N.check(self._lib.ttx_debug_sample_step_select(self._session, logits.data_ptr(), int(logits.shape[1]), key.data_ptr(),
+                                                       sample.data_ptr(), act_idx.data_ptr(), front.data_ptr(), int(B), int(n), int(d),
+                                                       int(n_active), pred.data_ptr(), self._ptr(m_live), C.byref(p),
+                                                       self._ptr(row_map), int(n_rows), self._stream()))
+
+    def debug_sample_accept_pool(self, state, *, B: int, n: int, d: int, Ls: int, max_len: int, pad: int, bos: int, eos: int,
+                                 gen_ld: int, pool_rows: int, traj_ld: int = 1, threads: int = 0, spread: bool = False,
+                                 exec_rows: torch.Tensor | None = None, **arrays) -> list:
+        """The accept step of the sampling pool (ttx_debug_sample_accept_pool): ``debug_accept``'s ``state`` and exit words;
+        ``arrays``: act_idx, front, gen, drafts, pred, rec, haspad (zeros), row_of and pool_out.  ``spread``: the pair
+        k_sample_accept_slots + k_accept_finish instead of one k_sample_accept launch; ``exec_rows``: an int32 device scalar."""
+        a = N.DebugAcceptArgs()
+        for name, _ in N.DebugAcceptArgs._fields_[:15]:
+            t = arrays.pop(name[2:], None)
+            setattr(a, name, None if t is None else t.data_ptr())
+        assert not arrays, f"unknown operands {sorted(arrays)}"
+        a.gen_ld, a.traj_ld, a.pool_rows, a.row_rule, a.pool = int(gen_ld), int(traj_ld), int(pool_rows), 1, 1
+        a.B, a.N, a.D, a.Ls, a.max_len, a.pad, a.bos, a.eos = int(B), int(n), int(d), int(Ls), int(max_len), int(pad), int(bos), int(eos)
+        a.greedy, a.threads = 0, int(threads)
+        words = (C.c_int64 * N.DEBUG_ACCEPT_STATE_WORDS)(*[int(v) for v in state], *([0] * (N.DEBUG_ACCEPT_STATE_WORDS - len(state))))
+        N.check(self._lib.ttx_debug_sample_accept_pool(self._session, C.byref(a), words, self._ptr(exec_rows), int(bool(spread)),
+                                                       self._stream()))
+        return [int(v) for v in words]
+
+    def debug_pool_fill_sample(self, *, B: int, n: int, d: int, n_active: int, n_sources: int, per_src: int, first_src: int, Ls_new: int,
+                               Ls_cap: int, gen_ld: int, kv_row: int, max_len: int, out_rows: int, bos: int, pad: int, **arrays) -> dict:
+        """One admission of the sampling pool (ttx_debug_pool_fill_sample); ``arrays``: device tensors named as the pointer fields
+        of ttx_debug_pool_fill_args without the ``d_`` prefix (row_keys may be absent).  Returns n_active, m_rows, error and the
+        n_active word published for the host."""
+        a = N.DebugPoolFillArgs()
+        for name in N.DebugPoolFillArgs.POINTERS:
+            t = arrays.pop(name[2:], None)
+            setattr(a, name, None if t is None else t.data_ptr())
+        assert not arrays, f"unknown operands {sorted(arrays)}"
+        for name, v in dict(B=B, N=n, D=d, n_active=n_active, n_sources=n_sources, per_src=per_src, first_src=first_src, Ls_new=Ls_new,
+                            Ls_cap=Ls_cap, gen_ld=gen_ld, kv_row=kv_row, max_len=max_len, out_rows=out_rows, bos=bos, pad=pad).items():
+            setattr(a, name, int(v))
+        res = (C.c_int32 * 4)()
+        N.check(self._lib.ttx_debug_pool_fill_sample(self._session, C.byref(a), res, self._stream()))
+        return dict(zip(("n_active", "m_rows", "error", "host_n_active"), (int(v) for v in res)))
+
     def debug_accept_block(self) -> list:
         """The int32 words of the session's AcceptBlk (ttx_debug_accept_block): all zero between accept steps."""
         words = (C.c_int32 * N.DEBUG_ACCEPT_BLOCK_WORDS)()
