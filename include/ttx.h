@@ -349,6 +349,42 @@ int ttx_sample_speculative_generate_pool(ttx_session** sessions, int n_sessions,
                                          const int32_t* h_len, const int64_t* d_row_keys, int capacity,
                                          const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream);
 
+/* Forced target prefixes (prompted decoding) for the three sampling calls above.  Each *_prefix call takes the arguments of its
+ * unprompted call plus d_prefix (DEVICE, int64 [sources][ld_prefix], without BOS), ld_prefix and h_prefix_len (HOST, int32
+ * [sources], like h_len): source b carries a prefix of plen = h_prefix_len[b] tokens, 0 <= plen <= max_len - 1, shared by its
+ * num_samples rows.  `sources` is B (S_total for the pool).  The unprompted calls are the same code with a null prefix, and a call
+ * whose lengths are all 0 (or whose h_prefix_len is NULL) IS the unprompted call: the same launches, the same graphs, the same bits.
+ *
+ * The position rule, for a row of source b at position pos (1 = the first token after BOS), beside the sampling rule above:
+ *   pos <= plen: the token is prefix[b][pos - 1].  The logits are not read and no uniform is consumed.  An id outside [0, V) is
+ *                emitted as 0, like the sampler's own guard.
+ *   otherwise:   steps 2-5 of the sampling rule, unchanged: the counter of the draw is still (key, sample, pos).
+ * A forced EOS or PAD ends the row exactly as an emitted one does; tokens beyond column max_len - 1 are dropped; a row that has
+ * ended emits PAD.  A row therefore depends on its source, its prefix, its key and its sample id, and on nothing else: not on the
+ * batch, on ld_prefix, on num_samples, on the pool's capacity or on its switches.
+ *
+ * Speculative calls.  The acceptance rule is NOT changed: a draft token is accepted iff it equals the token of its position, which
+ * now comes from the position rule.  What changes is the drafts: before every verify step k_prefix_drafts rewrites draft 0 of every
+ * active row, for j = 0 .. draft_len - 1: column c = front + 1 + j receives prefix[c - 1] if c <= plen (EOS and PAD as
+ * replace_token, as in every draft), else token j of the row's own source-copy draft 0.  So a prefix of P tokens enters the KV cache
+ * in ceil(P / (draft_len + 1)) verify steps; once front >= plen draft 0 is the source draft again; drafts still hold neither EOS
+ * nor PAD, so a forced EOS arrives as the bonus token and is the last one written; drafts 1 .. n_drafts - 1 stay the source
+ * windows.  ttx_sample_generate_prefix pays one decoder step per forced token (no one-pass prefill).
+ *
+ * Limits: prefixes are per source, not per sample; the plain greedy, greedy-speculative and beam generators take none.
+ * TTX_ERR_INVALID with nothing launched: a length outside [0, max_len - 1] or above ld_prefix, a negative ld_prefix, a null
+ * d_prefix together with a non-zero length, and everything the unprompted call refuses. */
+int ttx_sample_generate_prefix(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sample_params* p,
+                               const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len, int64_t* d_out,
+                               ttx_gen_stats* stats, void* stream);
+int ttx_sample_speculative_generate_prefix(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                           const ttx_sample_spec_params* p, const int64_t* d_prefix, int ld_prefix,
+                                           const int32_t* h_prefix_len, int64_t* d_out, ttx_gen_stats* stats, void* stream);
+int ttx_sample_speculative_generate_pool_prefix(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total, int Ls_all,
+                                                const int32_t* h_len, const int64_t* d_row_keys, int capacity,
+                                                const ttx_sample_spec_params* p, const int64_t* d_prefix, int ld_prefix,
+                                                const int32_t* h_prefix_len, int64_t* d_out, ttx_gen_stats* stats, void* stream);
+
 /* Beam-speculative bookkeeping kernels.
  * ttx_nucleus_mask: mask_with_num_logits_according_nucleus (src/decoding/speculative_decoding.py:871-904): per row of
  *   d_logits [rows,V] keep the best logit and further ones, best first, while the softmax mass ranked above is
@@ -701,6 +737,33 @@ int ttx_debug_sample_accept(ttx_session* s, const ttx_debug_accept_args* a, int6
 int ttx_debug_sample_step_select(ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample,
                                  const int32_t* d_act_idx, const int32_t* d_front, int B, int N, int D, int n_active, int32_t* d_pred,
                                  const int32_t* d_m, const ttx_sample_params* p, const int32_t* d_row_map, int n_rows, void* stream);
+
+/* The forced prefixes of a debug launch (tests/test_gpu_prefix_kernels.py), as the kernels see them: d_tok int32 [n_sources][ld]
+ * the table, d_len int32 [rows] and d_src int32 [rows] by decoder row (slot of a pool): the length of the row's prefix and its row
+ * of the table.  Checked on the host: lengths in [0, ld], sources in [0, n_sources). */
+typedef struct ttx_debug_prefix {
+  const int32_t* d_tok; int32_t ld, n_sources;
+  const int32_t* d_len; const int32_t* d_src;
+} ttx_debug_prefix;
+
+/* ttx_debug_prefix_drafts: ONE launch of k_prefix_drafts with production's grid (one wave per slot of B) on the caller's arrays.
+ * For every active row b = d_act_idx[slot], slot < n_active, and j < D: d_drafts[b][0][j] = prefix token of column
+ * c = d_front[b] + 1 + j when c <= d_len[b] (eos_token and pad_token as replace_token), else d_draft0[b][j].  d_drafts int32
+ * [B, N, D]; d_draft0 int32 [B, D]; nothing else is written.  Synchronises the stream.  Refused: null pointers, B, N or D < 1,
+ * n_active outside [0, B], repeated or out-of-range d_act_idx entries, negative fronts, and a prefix table outside its bounds.
+ * ttx_debug_sample_prefix: ttx_debug_sample with the table (rows = m_max); a live row with d_front[0] + 1 <= d_len[row] emits its
+ * prefix token (an id outside [0, V) as 0), sets done on EOS / PAD, and does not read its logits.
+ * ttx_debug_sample_step_prefix: ttx_debug_sample_step_select (row map, probe layout, compacted rows) with the table (rows = B). */
+int ttx_debug_prefix_drafts(ttx_session* s, const int32_t* d_act_idx, const int32_t* d_front, int B, int N, int D, int n_active,
+                            int32_t* d_drafts, const int32_t* d_draft0, const ttx_debug_prefix* pfx, int eos_token, int pad_token,
+                            int replace_token, void* stream);
+int ttx_debug_sample_prefix(ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample, int32_t* d_done,
+                            const int32_t* d_front, int32_t* d_pred, const int32_t* d_m, int m_max, const ttx_sample_params* p,
+                            const ttx_debug_prefix* pfx, void* stream);
+int ttx_debug_sample_step_prefix(ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample,
+                                 const int32_t* d_act_idx, const int32_t* d_front, int B, int N, int D, int n_active, int32_t* d_pred,
+                                 const int32_t* d_m, const ttx_sample_params* p, const int32_t* d_row_map, int n_rows,
+                                 const ttx_debug_prefix* pfx, void* stream);
 
 /* ttx_debug_sample_accept_pool (tests/test_gpu_sample_accept_pool_kernel.py): the accept step of
  * ttx_sample_speculative_generate_pool on ttx_debug_accept's argument block and `state`: greedy 0, row_rule and pool 1; d_row_of

@@ -107,6 +107,11 @@ class SampleSpecParams(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class DebugPrefix(C.Structure):
+    """ttx_debug_prefix: the forced prefixes of a debug launch (table, row length, sources; per-row length and table row)."""
+    _fields_ = [("d_tok", C.c_void_p), ("ld", C.c_int32), ("n_sources", C.c_int32), ("d_len", C.c_void_p), ("d_src", C.c_void_p)]
+
+
 class DebugAcceptArgs(C.Structure):
     """ttx_debug_accept_args: the device arrays and scalars of one k_accept / k_greedy_accept launch."""
     _fields_ = [(n, C.c_void_p) for n in ("d_act_idx", "d_front", "d_gen", "d_drafts", "d_pred", "d_rec", "d_out", "d_haspad",
@@ -197,6 +202,13 @@ SYMBOLS = {
     "ttx_greedy_generate": (C.c_int, [_VP, _VP, _I, _I, C.POINTER(GenParams), _VP, C.POINTER(GenStats), _VP]),
     "ttx_sample_generate": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SampleParams), _VP, C.POINTER(GenStats), _VP]),
     "ttx_sample_speculative_generate": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SampleSpecParams), _VP, C.POINTER(GenStats), _VP]),
+    "ttx_sample_generate_prefix": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SampleParams), _VP, _I, C.POINTER(C.c_int32), _VP,
+                                            C.POINTER(GenStats), _VP]),
+    "ttx_sample_speculative_generate_prefix": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SampleSpecParams), _VP, _I,
+                                                        C.POINTER(C.c_int32), _VP, C.POINTER(GenStats), _VP]),
+    "ttx_sample_speculative_generate_pool_prefix": (C.c_int, [C.POINTER(_VP), _I, _VP, _I, _I, C.POINTER(C.c_int32), _VP, _I,
+                                                             C.POINTER(SampleSpecParams), _VP, _I, C.POINTER(C.c_int32), _VP,
+                                                             C.POINTER(GenStats), _VP]),
     "ttx_greedy_speculative_generate_many": (C.c_int, [C.POINTER(_VP), _I, _I, C.POINTER(_VP), C.POINTER(C.c_int),
                                                       C.POINTER(C.c_int), C.POINTER(GenParams), C.POINTER(_VP),
                                                       C.POINTER(GenStats), _VP]),
@@ -242,6 +254,11 @@ SYMBOLS = {
     "ttx_debug_sample_accept": (C.c_int, [_VP, C.POINTER(DebugAcceptArgs), C.POINTER(C.c_int64), _VP]),
     "ttx_debug_sample_step_select": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, C.POINTER(SampleParams),
                                               _VP, _I, _VP]),
+    "ttx_debug_prefix_drafts": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, C.POINTER(DebugPrefix), _I, _I, _I, _VP]),
+    "ttx_debug_sample_prefix": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I, C.POINTER(SampleParams),
+                                         C.POINTER(DebugPrefix), _VP]),
+    "ttx_debug_sample_step_prefix": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, C.POINTER(SampleParams),
+                                              _VP, _I, C.POINTER(DebugPrefix), _VP]),
     "ttx_debug_sample_accept_pool": (C.c_int, [_VP, C.POINTER(DebugAcceptArgs), C.POINTER(C.c_int64), _VP, _I, _VP]),
     "ttx_debug_pool_fill_sample": (C.c_int, [_VP, C.POINTER(DebugPoolFillArgs), C.POINTER(C.c_int32), _VP]),
     "ttx_debug_embed": (C.c_int, [_VP, _VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _I, _I, _I, _I, _I, _VP]),

@@ -1041,6 +1041,7 @@ struct StepCtx {
   bool want_sample = false;        // sampling loop: k_sample on `sample` where k_argmax would run
   SampleArgs sample{};
   bool want_sample_step = false;   // speculative sampling loop: k_sample_step on `sample`'s key, sample and prm
+  const int* pfx_draft0 = nullptr; // prompted speculative sampling (sample.pfx set): the rows' source draft 0, [B, D]
   int variant = GV_BIG;           // GemmVariant of this step's launches (bit-identical results; chosen from the live row count)
   // two-phase verify step of the slot pool; unset (null): the session's state, active list, step QKV buffer and argmax buffer
   DecState* st_ov = nullptr;       // live rows of this pass
@@ -1074,6 +1075,23 @@ static int launch_sample_step(hipStream_t st, const SampleStepArgs& a) {
   else hipLaunchKernelGGL((k_sample_step<16>), grid, block, 0, st, a);
   HIP_TRY(hipGetLastError());
   return TTX_OK;
+}
+
+// k_prefix_drafts on the session's loop state: draft 0 of every active row, one wave per slot, grid for the capacity.
+static int launch_prefix_drafts_args(hipStream_t st, const PrefixDraftsArgs& a, int B) {
+  hipLaunchKernelGGL(k_prefix_drafts, dim3(cdiv(B, 4)), dim3(256), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+// The head of every verify step of a prompted speculative sampling loop; nothing for any other loop.
+static int launch_prefix_drafts(ttx_session* s, hipStream_t st, const StepCtx& k) {
+  if (!k.sample.pfx.tok || !k.want_sample_step) return TTX_OK;
+  PrefixDraftsArgs a{};
+  a.st = s->state.as<DecState>(); a.act_idx = s->act_idx.as<int>(); a.front = s->front.as<int>();
+  a.drafts = s->drafts.as<int>(); a.N = k.N; a.D = k.D; a.draft0 = k.pfx_draft0; a.pfx = k.sample.pfx;
+  a.eos = k.p.eos_token; a.pad = k.p.pad_token; a.repl = k.p.replace_token;
+  return launch_prefix_drafts_args(st, a, k.B);
 }
 
 static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) {
@@ -1135,7 +1153,7 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
     SampleStepArgs a{};
     a.logits = logits; a.V = V; a.pred = k.pred_ov ? k.pred_ov : s->pred.as<int>(); a.m_ptr = m_ptr; a.M = Mmax;
     a.key = k.sample.key; a.sample = k.sample.sample; a.prm = k.sample.prm;
-    a.act_idx = act; a.front = s->front.as<int>(); a.N = k.N; a.D = k.D; a.row_map = k.row_map;
+    a.act_idx = act; a.front = s->front.as<int>(); a.N = k.N; a.D = k.D; a.row_map = k.row_map; a.pfx = k.sample.pfx;
     return launch_sample_step(st, a);
   }
   if (k.want_argmax) {
@@ -1438,11 +1456,13 @@ static int gen_launch_step(GenJob& j, int width_bound) {
   k.variant = variant_for_rows(s, (long long)live * step_rps(k.N, k.D), true);
   const int kcap = key_capacity(std::max(width_bound, 1), k.max_len);        // prefix keys this step can see: < width_bound
   const auto enqueue = [&]() -> int {
+    TTX_TRY(launch_prefix_drafts(s, j.st, k));
     TTX_TRY(run_step(s, j.st, k, kcap));
     return launch_accept_and_commit(s, j.st, j.g, j.greedy);
   };
   if (k.p.want_logits > 0 && k.p.want_logits == j.launched + 1) {
     // the snapshot step runs eagerly: keep its pre-argmax logits and the loop state they belong to (before accept changes it)
+    TTX_TRY(launch_prefix_drafts(s, j.st, k));       // the head of a prompted step, as in `enqueue` (the sampling calls ask for no snapshot today)
     TTX_TRY(run_step(s, j.st, k, kcap));
     const ttx_config& c = s->m->cfg;
     const size_t Mmax = (size_t)k.B * step_rps(k.N, k.D);
@@ -1459,7 +1479,10 @@ static int gen_launch_step(GenJob& j, int width_bound) {
     s->snap_B = k.B; s->snap_rps = step_rps(k.N, k.D); s->snap_gen_ld = k.gen_ld; s->snap_step = j.launched + 1;
     TTX_TRY(launch_accept_and_commit(s, j.st, j.g, j.greedy));
   } else {
-    const int site = k.want_sample_step ? GS_STEP_SAMPLE_SPEC : k.want_sample ? GS_STEP_SAMPLE : j.greedy ? GS_STEP_GREEDY : (j.g.la.row_rule ? GS_STEP_ROW_RULE : GS_STEP_SPECULATIVE);
+    const bool pfx = k.sample.pfx.tok != nullptr;  // a prompted call never shares a graph with an unprompted one
+    const int site = k.want_sample_step ? (pfx ? GS_STEP_SAMPLE_SPEC_PREFIX : GS_STEP_SAMPLE_SPEC)
+                     : k.want_sample    ? (pfx ? GS_STEP_SAMPLE_PREFIX : GS_STEP_SAMPLE)
+                     : j.greedy ? GS_STEP_GREEDY : (j.g.la.row_rule ? GS_STEP_ROW_RULE : GS_STEP_SPECULATIVE);
     TTX_TRY(graph_replay(s, j.st, s->step_graphs, GraphKey{site, k.B, k.Ls, k.N, k.D, k.max_len, kcap, k.variant, 0}, enqueue));
   }
   ++j.launched;
@@ -1584,10 +1607,47 @@ struct SampleSetup {
   const int64_t* d_row_keys;       // [B / n] or null
   SampleBlock blk;
   bool spec;                       // ttx_sample_speculative_generate: the speculative loop with k_sample_step and k_sample_accept
+  // forced prefixes (prefix_validate); prompted false: the call is the unprompted one, launch for launch
+  bool prompted;
+  const int64_t* d_prefix; int ld_prefix; const int32_t* h_prefix_len; int n_sources;
 };
 
+// The prefix arguments of a sampling call over S sources, or TTX_ERR_INVALID.  A call whose lengths are all zero (or absent) is
+// not prompted: it runs the unprompted call's launches and graphs.
+static int prefix_validate(const char* who, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len, int S, int max_len,
+                           SampleSetup* smp) {
+  smp->prompted = false; smp->d_prefix = d_prefix; smp->ld_prefix = ld_prefix; smp->h_prefix_len = h_prefix_len; smp->n_sources = S;
+  if (!h_prefix_len) return TTX_OK;
+  if (ld_prefix < 0) return fail(TTX_ERR_INVALID, std::string(who) + ": ld_prefix must not be negative");
+  for (int i = 0; i < S; ++i) {
+    const int n = h_prefix_len[i];
+    if (n < 0 || n > max_len - 1) return fail(TTX_ERR_INVALID, std::string(who) + ": a prefix length must lie in [0, max_len - 1]");
+    if (n > ld_prefix) return fail(TTX_ERR_INVALID, std::string(who) + ": a prefix length exceeds ld_prefix");
+    if (n > 0 && !d_prefix) return fail(TTX_ERR_INVALID, std::string(who) + ": a prefix length is non-zero but d_prefix is null");
+    smp->prompted |= n > 0;
+  }
+  return TTX_OK;
+}
+
+// The session's prefix table of a prompted call, int32 [S][max_len], and the sources' lengths on the device.  The row length is
+// max_len, which every step key holds, and the buffers are the session's, so a captured step holds nothing of the call.
+static int prefix_upload(ttx_session* s, hipStream_t st, const SampleSetup& smp, int max_len, int pad) {
+  const int S = smp.n_sources;
+  HIP_TRY(hipMemcpyAsync(s->pfx_len_src.p, smp.h_prefix_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_prefix_load, dim3(cdiv(S * max_len, 256)), dim3(256), 0, st, smp.d_prefix, smp.ld_prefix, s->pfx_len_src.as<int>(),
+                     s->pfx_tok.as<int>(), S, max_len, pad);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
 // Session buffers of the sampling loop, sized before anything is captured.
-static int sample_ensure(ttx_session* s, hipStream_t st, size_t rows) {
+static int sample_ensure(ttx_session* s, hipStream_t st, size_t rows, const SampleSetup& smp, const ttx_gen_params* p) {
+  if (smp.prompted) {
+    TTX_TRY(ensure(s->pfx_tok, (size_t)smp.n_sources * p->max_len * 4, st));
+    TTX_TRY(ensure(s->pfx_len_src, (size_t)smp.n_sources * 4, st));
+    TTX_TRY(ensure(s->pfx_len, rows * 4, st));
+    if (smp.spec) TTX_TRY(ensure(s->pfx_draft0, rows * p->draft_len * 4, st));
+  }
   TTX_TRY(ensure(s->smp_key, rows * 8, st));
   TTX_TRY(ensure(s->smp_sample, rows * 4, st));
   TTX_TRY(ensure(s->smp_done, rows * 4, st));
@@ -1611,6 +1671,18 @@ static int sample_begin(GenJob& j, const SampleSetup& smp) {
   k.want_sample_step = smp.spec;
   k.sample.key = s->smp_key.as<unsigned long long>(); k.sample.sample = s->smp_sample.as<unsigned>();
   k.sample.done = s->smp_done.as<int>(); k.sample.front = s->front.as<int>(); k.sample.prm = s->smp_prm.as<SampleBlock>();
+  if (smp.prompted) {
+    TTX_TRY(prefix_upload(s, j.st, smp, k.max_len, k.p.pad_token));
+    hipLaunchKernelGGL(k_prefix_rows, dim3(cdiv(R, 256)), dim3(256), 0, j.st, s->pfx_len_src.as<int>(), s->smp_src_of.as<int>(),
+                       s->pfx_len.as<int>(), R);
+    HIP_TRY(hipGetLastError());
+    k.sample.pfx = PrefixTab{s->pfx_tok.as<int>(), k.max_len, s->pfx_len.as<int>(), s->smp_src_of.as<int>()};
+    if (smp.spec) {                                  // draft 0 of every row as gen_start left it, before any step rewrites it
+      HIP_TRY(hipMemcpy2DAsync(s->pfx_draft0.p, (size_t)k.D * 4, s->drafts.p, (size_t)k.N * k.D * 4, (size_t)k.D * 4, (size_t)R,
+                               hipMemcpyDeviceToDevice, j.st));
+      k.pfx_draft0 = s->pfx_draft0.as<int>();
+    }
+  }
   return TTX_OK;
 }
 
@@ -1630,7 +1702,7 @@ static int generate_batches(ttx_session** sessions, int n_sessions, int n_batche
     if (j.phase == 0) {
       if (next >= n_batches) return TURN_FINISHED;
       j.batch = next++;
-      if (smp) TTX_TRY(sample_ensure(s, s->own_stream, (size_t)B[j.batch]));
+      if (smp) TTX_TRY(sample_ensure(s, s->own_stream, (size_t)B[j.batch], *smp, p));
       TTX_TRY(gen_start(j, s, s->own_stream, d_src[j.batch], B[j.batch], Ls[j.batch], p, d_out[j.batch], stats ? &stats[j.batch] : nullptr,
                         greedy, d_traj ? d_traj[j.batch] : nullptr, d_traj ? d_fin[j.batch] : nullptr, smp ? smp->n : 1, smp && smp->spec));
       if (smp) TTX_TRY(sample_begin(j, *smp));
@@ -1694,8 +1766,10 @@ static int sample_block(const char* who, const ttx_sample_params* p, SampleBlock
   return TTX_OK;
 }
 
-extern "C" int ttx_sample_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
-                                   const ttx_sample_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
+// ttx_sample_generate and ttx_sample_generate_prefix: one body, the unprompted call with a null prefix.
+static int sample_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sample_params* p,
+                           int64_t* d_out, ttx_gen_stats* stats, void* stream, const int64_t* d_prefix, int ld_prefix,
+                           const int32_t* h_prefix_len) {
   if (!s || !p) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
   if (s->m->cfg.vocab_size > SAMPLE_MAX_V) return fail(TTX_ERR_INVALID, "ttx_sample_generate: vocabularies above 1024 are not supported");
   if (p->num_samples < 1) return fail(TTX_ERR_INVALID, "ttx_sample_generate: num_samples must be at least 1");
@@ -1704,6 +1778,7 @@ extern "C" int ttx_sample_generate(ttx_session* s, const int64_t* d_src, int B, 
   if (B > 0 && (long long)B * p->num_samples * ((long long)std::max(p->max_len, 0) + 2) >= (1ll << 31))
     return fail(TTX_ERR_INVALID, "ttx_sample_generate: B * num_samples * (max_len + 2) must stay below 2^31");
   smp.n = p->num_samples; smp.d_row_keys = d_row_keys;
+  TTX_TRY(prefix_validate("ttx_sample_generate", d_prefix, ld_prefix, h_prefix_len, std::max(B, 0), p->max_len, &smp));
   ttx_gen_params g{};
   g.max_len = p->max_len; g.draft_len = 0; g.n_drafts = 1; g.pad_token = p->pad_token; g.bos_token = p->bos_token;
   g.eos_token = p->eos_token; g.replace_token = p->pad_token; g.want_logits = 0;
@@ -1711,6 +1786,17 @@ extern "C" int ttx_sample_generate(ttx_session* s, const int64_t* d_src, int B, 
   const int rc = generate_one(s, d_src, B * p->num_samples, Ls, &g, d_out, stats, stream, true, &smp);
   if (rc == TTX_OK && stats) stats->src_tokens_padded = (long long)B * Ls;    // the encoder ran once per source
   return rc;
+}
+
+extern "C" int ttx_sample_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                   const ttx_sample_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
+  return sample_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, nullptr, 0, nullptr);
+}
+
+extern "C" int ttx_sample_generate_prefix(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                          const ttx_sample_params* p, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
+                                          int64_t* d_out, ttx_gen_stats* stats, void* stream) {
+  return sample_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, d_prefix, ld_prefix, h_prefix_len);
 }
 
 // What the speculative sampling calls refuse with TTX_ERR_INVALID whatever code gen_validate would give (nothing of these calls is
@@ -1738,8 +1824,9 @@ static int sample_spec_validate(const char* who, const ttx_session* s, const ttx
 // Speculative seeded sampling: the greedy-speculative loop over R = B * n decoder rows with the keyed draw where the argmax stands
 // (k_sample_step, k_sample_accept).  A draft token is accepted iff it is the token the plain sampler emits at its position, so the
 // committed rows are ttx_sample_generate's.
-extern "C" int ttx_sample_speculative_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
-                                               const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
+static int sample_speculative_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                       const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream,
+                                       const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len) {
   const char* who = "ttx_sample_speculative_generate";
   if (!s || !p) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
   SampleSetup smp{};
@@ -1748,9 +1835,22 @@ extern "C" int ttx_sample_speculative_generate(ttx_session* s, const int64_t* d_
   TTX_TRY(sample_spec_validate(who, s, p, R, &smp, &g));
   if (B <= 0) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
   smp.d_row_keys = d_row_keys;
+  TTX_TRY(prefix_validate(who, d_prefix, ld_prefix, h_prefix_len, B, g.max_len, &smp));
   const int rc = generate_one(s, d_src, (int)R, Ls, &g, d_out, stats, stream, false, &smp);
   if (rc == TTX_OK && stats) stats->src_tokens_padded = (long long)B * Ls;    // the encoder ran once per source
   return rc;
+}
+
+extern "C" int ttx_sample_speculative_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                               const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
+  return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, nullptr, 0, nullptr);
+}
+
+// The prompted form: the prefix rides in as draft 0 (k_prefix_drafts), ceil(len / (draft_len + 1)) steps for len forced tokens.
+extern "C" int ttx_sample_speculative_generate_prefix(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                                      const ttx_sample_spec_params* p, const int64_t* d_prefix, int ld_prefix,
+                                                      const int32_t* h_prefix_len, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
+  return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, d_prefix, ld_prefix, h_prefix_len);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1837,6 +1937,10 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
     need(s->pred_draft, Mmax * 4); need(s->state2, 3 * sizeof(DecState));
   }
   if (smp) { need(s->smp_key, (size_t)C * 8); need(s->smp_sample, (size_t)C * 4); need(s->smp_prm, sizeof(SampleBlock)); }
+  if (smp && smp->prompted) {
+    need(s->pfx_tok, (size_t)smp->n_sources * max_len * 4); need(s->pfx_len_src, (size_t)smp->n_sources * 4);
+    need(s->pfx_len, (size_t)C * 4); need(s->pfx_src, (size_t)C * 4); need(s->pfx_draft0, (size_t)C * D * 4);
+  }
   TTX_TRY(need.rc);
   AcceptBlk* blk = nullptr;
   // the greedy pool keeps the session's reading of TTX_ACCEPT_SPREAD; the sampling pool reads it here, with its other switches
@@ -1895,6 +1999,7 @@ static int pool_admit(PoolJob& j, const int64_t* d_src_rows, int ld_src, int R, 
   if (j.per_src) {
     a.key = s->smp_key.as<unsigned long long>(); a.sample = s->smp_sample.as<unsigned>(); a.row_keys = j.d_row_keys;
     a.per_src = j.per_src; a.first_src = first_row;
+    if (k.sample.pfx.tok) { a.pfx_src = s->pfx_src.as<int>(); a.pfx_len = s->pfx_len.as<int>(); a.pfx_len_of_src = s->pfx_len_src.as<int>(); }
   }
   hipLaunchKernelGGL(k_pool_admit, dim3(1), dim3(256), (size_t)j.C * 4, st, a);
   HIP_TRY(hipGetLastError());
@@ -1905,6 +2010,7 @@ static int pool_admit(PoolJob& j, const int64_t* d_src_rows, int ld_src, int R, 
   f.memkv = s->memkv.as<float>(); f.memkv_new = s->memkv_new.as<float>(); f.kv_row = kv_row;
   f.out_rows = d_out; f.traj_rows = d_traj; f.fin_rows = d_fin; f.max_len = k.max_len; f.traj_ld = k.max_len + 1; f.first_row = row0;
   f.per_src = j.per_src;
+  if (k.sample.pfx.tok) { f.draft0 = s->pfx_draft0.as<int>(); f.D = k.D; }
   hipLaunchKernelGGL(k_pool_fill, dim3(rows, 1 + Ls_new), dim3(256), 0, st, f);
   HIP_TRY(hipGetLastError());
   ++j.admits;
@@ -1918,7 +2024,7 @@ static int pool_admit(PoolJob& j, const int64_t* d_src_rows, int ld_src, int R, 
 // the environment per call.
 static GraphKey pool_key(const PoolJob& j, const StepCtx& k, int variant, int phase) {
   if (k.want_sample_step)
-    return GraphKey{GS_STEP_POOL_SAMPLE, k.B, k.Ls, k.N, k.D, k.max_len, k.max_len, variant, phase, j.g.la.blk ? 1 : 0};
+    return GraphKey{k.sample.pfx.tok ? GS_STEP_POOL_SAMPLE_PREFIX : GS_STEP_POOL_SAMPLE, k.B, k.Ls, k.N, k.D, k.max_len, k.max_len, variant, phase, j.g.la.blk ? 1 : 0};
   return GraphKey{GS_STEP_POOL, k.B, k.Ls, k.N, k.D, k.max_len, k.max_len, variant, phase};
 }
 
@@ -1932,6 +2038,7 @@ static int pool_launch_step(PoolJob& j, int n_live) {
   if (!j.two_phase || rows < j.min_rows) {
     k.variant = variant_for_rows(s, rows, true);     // free choice: identical bits
     TTX_TRY(graph_replay(s, j.st, s->step_graphs, pool_key(j, k, k.variant, 0), [&]() -> int {
+      TTX_TRY(launch_prefix_drafts(s, j.st, k));
       TTX_TRY(run_step(s, j.st, k, kcap));
       return launch_accept_and_commit(s, j.st, j.g, false);
     }));
@@ -1945,6 +2052,7 @@ static int pool_launch_step(PoolJob& j, int n_live) {
   kp.st_ov = st2; kp.qkv_ov = s->qkv_probe.as<float>(); kp.pred_ov = s->pred_probe.as<int>();
   kp.variant = variant_for_rows(s, n_live, true);
   TTX_TRY(graph_replay(s, j.st, s->step_graphs, pool_key(j, k, kp.variant, j.draft_select ? 4 : 1), [&]() -> int {
+    TTX_TRY(launch_prefix_drafts(s, j.st, k));       // before the probe: k_probe_split compares against the drafts
     hipLaunchKernelGGL(k_probe_begin, dim3(1), dim3(64), 0, j.st, s->state.as<DecState>(), st2);
     HIP_TRY(hipGetLastError());
     TTX_TRY(run_step(s, j.st, kp, kcap));
@@ -2011,6 +2119,11 @@ static int pool_sample_begin(PoolJob& j, const SampleSetup& smp) {
   k.sample.front = s->front.as<int>(); k.sample.prm = s->smp_prm.as<SampleBlock>();
   j.g.la.sample_rule = 1;
   j.per_src = smp.n; j.d_row_keys = smp.d_row_keys;
+  if (smp.prompted) {                                // the slots' lengths, sources and draft 0 are written at admission
+    TTX_TRY(prefix_upload(s, j.st, smp, k.max_len, k.p.pad_token));
+    k.sample.pfx = PrefixTab{s->pfx_tok.as<int>(), k.max_len, s->pfx_len.as<int>(), s->pfx_src.as<int>()};
+    k.pfx_draft0 = s->pfx_draft0.as<int>();
+  }
   return TTX_OK;
 }
 
@@ -2124,9 +2237,10 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
 
 // ttx_sample_speculative_generate's rows over a whole list of sources on the slot pool: the n decoder rows of a source are admitted
 // together, the step kernels are the pool's with the keyed draw where the argmax stands.
-extern "C" int ttx_sample_speculative_generate_pool(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total, int Ls_all,
-                                                    const int32_t* h_len, const int64_t* d_row_keys, int capacity,
-                                                    const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
+static int sample_speculative_generate_pool(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total, int Ls_all,
+                                            const int32_t* h_len, const int64_t* d_row_keys, int capacity, const ttx_sample_spec_params* p,
+                                            int64_t* d_out, ttx_gen_stats* stats, void* stream, const int64_t* d_prefix, int ld_prefix,
+                                            const int32_t* h_prefix_len) {
   const char* who = "ttx_sample_speculative_generate_pool";
   if (!sessions || n_sessions <= 0 || !d_src || S_total < 0 || !h_len || !p || !d_out)
     return fail(TTX_ERR_INVALID, std::string("bad argument to ") + who);
@@ -2145,9 +2259,27 @@ extern "C" int ttx_sample_speculative_generate_pool(ttx_session** sessions, int 
   if (Ls_cap > c.max_positions) return fail(TTX_ERR_INVALID, std::string(who) + ": slot width beyond the positional table");
   if (g.pad_token != c.pad_token) return fail(TTX_ERR_INVALID, std::string(who) + ": generator pad token differs from the model's");
   if (g.max_len + g.draft_len + 2 > c.max_positions) return fail(TTX_ERR_INVALID, std::string(who) + ": max_len + draft_len exceeds the positional table");
+  TTX_TRY(prefix_validate(who, d_prefix, ld_prefix, h_prefix_len, S_total, g.max_len, &smp));
   if (S_total == 0) return TTX_OK;
   smp.d_row_keys = d_row_keys;
   return pool_generate(sessions, n_sessions, d_src, S_total, Ls_all, h_len, Ls_cap, capacity, &g, d_out, nullptr, nullptr, stats, stream, &smp);
+}
+
+extern "C" int ttx_sample_speculative_generate_pool(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total, int Ls_all,
+                                                    const int32_t* h_len, const int64_t* d_row_keys, int capacity,
+                                                    const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
+  return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p, d_out, stats, stream,
+                                          nullptr, 0, nullptr);
+}
+
+// The prompted pool: every pool of the call holds the whole prefix table; a slot gets its source's index and length at admission.
+extern "C" int ttx_sample_speculative_generate_pool_prefix(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total,
+                                                           int Ls_all, const int32_t* h_len, const int64_t* d_row_keys, int capacity,
+                                                           const ttx_sample_spec_params* p, const int64_t* d_prefix, int ld_prefix,
+                                                           const int32_t* h_prefix_len, int64_t* d_out, ttx_gen_stats* stats,
+                                                           void* stream) {
+  return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p, d_out, stats, stream,
+                                          d_prefix, ld_prefix, h_prefix_len);
 }
 
 // Several batches in flight on one GPU: outputs per batch are identical to the one-at-a-time call.
@@ -3289,9 +3421,25 @@ extern "C" int ttx_debug_argmax(ttx_session* s, const float* d_logits, int V, in
   return TTX_OK;
 }
 
-extern "C" int ttx_debug_sample(ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample,
-                                int32_t* d_done, const int32_t* d_front, int32_t* d_pred, const int32_t* d_m, int m_max,
-                                const ttx_sample_params* p, void* stream) {
+// The prefix table of a debug launch over `rows` decoder rows, checked on the host: every row's source inside the table, every
+// length in [0, ld].  The caller's writes are ordered on its stream.
+static int dbg_prefix_tab(const char* who, const ttx_debug_prefix* x, int rows, hipStream_t st, PrefixTab* out) {
+  if (!x || !x->d_tok || !x->d_len || !x->d_src || x->ld < 1 || x->n_sources < 1)
+    return fail(TTX_ERR_INVALID, std::string(who) + ": the prefix table needs d_tok, d_len, d_src, ld >= 1 and n_sources >= 1");
+  std::vector<int32_t> len((size_t)rows), src((size_t)rows);
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpy(len.data(), x->d_len, (size_t)rows * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(src.data(), x->d_src, (size_t)rows * 4, hipMemcpyDeviceToHost));
+  for (int r = 0; r < rows; ++r)
+    if (len[r] < 0 || len[r] > x->ld || src[r] < 0 || src[r] >= x->n_sources)
+      return fail(TTX_ERR_INVALID, std::string(who) + ": a prefix length lies outside [0, ld] or a source outside the table");
+  *out = PrefixTab{x->d_tok, x->ld, x->d_len, x->d_src};
+  return TTX_OK;
+}
+
+static int sample_debug(const char* who_c, ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample,
+                        int32_t* d_done, const int32_t* d_front, int32_t* d_pred, const int32_t* d_m, int m_max,
+                        const ttx_sample_params* p, const ttx_debug_prefix* pfx, bool prompted, void* stream) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (!s || !d_logits || !d_key || !d_sample || !d_done || !d_front || !d_pred || !p)
     return fail(TTX_ERR_INVALID, "null argument to ttx_debug_sample");
@@ -3312,7 +3460,26 @@ extern "C" int ttx_debug_sample(ttx_session* s, const float* d_logits, int V, co
   a.logits = d_logits; a.V = V; a.pred = d_pred; a.m_ptr = d_m; a.M = m_max;
   a.key = reinterpret_cast<const unsigned long long*>(d_key); a.sample = d_sample; a.done = d_done; a.front = d_front;
   a.prm = s->smp_prm.as<SampleBlock>();
+  if (prompted) {
+    int32_t f = -1;
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(&f, d_front, 4, hipMemcpyDeviceToHost));
+    if (f < 0) return fail(TTX_ERR_INVALID, std::string(who_c) + ": the front must not be negative");
+    TTX_TRY(dbg_prefix_tab(who_c, pfx, m_max, st, &a.pfx));
+  }
   return launch_sample(st, a);
+}
+
+extern "C" int ttx_debug_sample(ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample,
+                                int32_t* d_done, const int32_t* d_front, int32_t* d_pred, const int32_t* d_m, int m_max,
+                                const ttx_sample_params* p, void* stream) {
+  return sample_debug("ttx_debug_sample", s, d_logits, V, d_key, d_sample, d_done, d_front, d_pred, d_m, m_max, p, nullptr, false, stream);
+}
+
+extern "C" int ttx_debug_sample_prefix(ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample,
+                                       int32_t* d_done, const int32_t* d_front, int32_t* d_pred, const int32_t* d_m, int m_max,
+                                       const ttx_sample_params* p, const ttx_debug_prefix* pfx, void* stream) {
+  return sample_debug("ttx_debug_sample_prefix", s, d_logits, V, d_key, d_sample, d_done, d_front, d_pred, d_m, m_max, p, pfx, true, stream);
 }
 
 // `select` (ttx_debug_sample_step_select): the launch covers n_rows rows stored compacted, row i drawing for layout row d_row_map[i]
@@ -3320,7 +3487,7 @@ extern "C" int ttx_debug_sample(ttx_session* s, const float* d_logits, int V, co
 static int sample_step_debug(const char* who_c, ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample,
                              const int32_t* d_act_idx, const int32_t* d_front, int B, int N, int D, int n_active, int32_t* d_pred,
                              const int32_t* d_m, const ttx_sample_params* p, void* stream, bool select, const int32_t* d_row_map,
-                             int n_rows) {
+                             int n_rows, const ttx_debug_prefix* pfx = nullptr, bool prompted = false) {
   const std::string who(who_c);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (!s || !d_logits || !d_key || !d_sample || !d_act_idx || !d_front || !d_pred || !p)
@@ -3360,6 +3527,7 @@ static int sample_step_debug(const char* who_c, ttx_session* s, const float* d_l
   a.logits = d_logits; a.V = V; a.pred = d_pred; a.m_ptr = d_m; a.M = M;
   a.key = reinterpret_cast<const unsigned long long*>(d_key); a.sample = d_sample; a.act_idx = d_act_idx; a.front = d_front;
   a.N = N; a.D = D; a.prm = s->smp_prm.as<SampleBlock>(); a.row_map = d_row_map;
+  if (prompted) TTX_TRY(dbg_prefix_tab(who_c, pfx, B, st, &a.pfx));
   return launch_sample_step(st, a);
 }
 
@@ -3376,6 +3544,45 @@ extern "C" int ttx_debug_sample_step_select(ttx_session* s, const float* d_logit
                                             int n_rows, void* stream) {
   return sample_step_debug("ttx_debug_sample_step_select", s, d_logits, V, d_key, d_sample, d_act_idx, d_front, B, N, D, n_active, d_pred,
                            d_m, p, stream, true, d_row_map, n_rows);
+}
+
+extern "C" int ttx_debug_sample_step_prefix(ttx_session* s, const float* d_logits, int V, const uint64_t* d_key, const uint32_t* d_sample,
+                                            const int32_t* d_act_idx, const int32_t* d_front, int B, int N, int D, int n_active,
+                                            int32_t* d_pred, const int32_t* d_m, const ttx_sample_params* p, const int32_t* d_row_map,
+                                            int n_rows, const ttx_debug_prefix* pfx, void* stream) {
+  return sample_step_debug("ttx_debug_sample_step_prefix", s, d_logits, V, d_key, d_sample, d_act_idx, d_front, B, N, D, n_active, d_pred,
+                           d_m, p, stream, true, d_row_map, n_rows, pfx, true);
+}
+
+extern "C" int ttx_debug_prefix_drafts(ttx_session* s, const int32_t* d_act_idx, const int32_t* d_front, int B, int N, int D, int n_active,
+                                       int32_t* d_drafts, const int32_t* d_draft0, const ttx_debug_prefix* pfx, int eos_token,
+                                       int pad_token, int replace_token, void* stream) {
+  const char* who = "ttx_debug_prefix_drafts";
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !d_act_idx || !d_front || !d_drafts || !d_draft0) return fail(TTX_ERR_INVALID, std::string("null argument to ") + who);
+  if (B < 1 || N < 1 || D < 1 || (long long)B * N * D >= (1ll << 31)) return fail(TTX_ERR_INVALID, std::string(who) + ": B, N and D must be positive");
+  if (n_active < 0 || n_active > B) return fail(TTX_ERR_INVALID, std::string(who) + ": n_active must lie in [0, B]");
+  HIP_TRY(hipSetDevice(s->m->device));
+  int max_front = 0;
+  TTX_TRY(dbg_check_slots(who, d_act_idx, d_front, B, n_active, 1 << 30, D, st, &max_front));
+  PrefixDraftsArgs a{};
+  TTX_TRY(dbg_prefix_tab(who, pfx, B, st, &a.pfx));
+  DecState* dst = nullptr;
+  HIP_TRY(hipMalloc((void**)&dst, sizeof(DecState)));
+  DecState hs{};
+  hs.n_active = n_active; hs.r_rows = n_active * N; hs.m_rows = n_active * step_rps(N, D);
+  hipError_t err = hipMemcpy(dst, &hs, sizeof(DecState), hipMemcpyHostToDevice);
+  int rc = TTX_OK;
+  if (err == hipSuccess) {
+    a.st = dst; a.act_idx = d_act_idx; a.front = d_front; a.drafts = d_drafts; a.N = N; a.D = D; a.draft0 = d_draft0;
+    a.eos = eos_token; a.pad = pad_token; a.repl = replace_token;
+    rc = launch_prefix_drafts_args(st, a, B);         // production's grid: one wave per slot of the capacity
+  }
+  const hipError_t esync = hipStreamSynchronize(st);   // the launch reads the state: keep it until the launch is through
+  (void)hipFree(dst);
+  HIP_TRY(err);
+  HIP_TRY(esync);
+  return rc;
 }
 
 // d_row_map (ttx_debug_embed_select; null: ttx_debug_embed): the launch writes m_rows rows, row i holding layout row d_row_map[i]

@@ -81,8 +81,11 @@ enum AttnKernelId { AK_ATTN = 1, AK_ATTN2 = 2, AK_ATTN3 = 3, AK_ATTN3S = 4, AK_A
 //                                 (ttx_sample_speculative_generate); B counts decoder rows
 //   GS_STEP_POOL_SAMPLE           GS_STEP_POOL's key and phases with k_sample_step and the sampling accept in k_argmax's and k_accept's
 //                                 place (ttx_sample_speculative_generate_pool): never a graph of the greedy pool
+//   GS_STEP_*_PREFIX              the three sampling sites of a prompted call (forced prefixes): the same keys; k_prefix_drafts leads
+//                                 the speculative ones and the sampling kernels carry the session's prefix table (row length max_len)
 enum GraphSite { GS_STEP_SPECULATIVE = 0, GS_STEP_GREEDY = 1, GS_STEP_ROW_RULE = 2, GS_STEP_POOL = 3, GS_BEAM_ITER = 4, GS_BEAM_POOL_ITER = 5,
-                 GS_STEP_SAMPLE = 6, GS_STEP_SAMPLE_SPEC = 7, GS_STEP_POOL_SAMPLE = 8 };
+                 GS_STEP_SAMPLE = 6, GS_STEP_SAMPLE_SPEC = 7, GS_STEP_POOL_SAMPLE = 8,
+                 GS_STEP_SAMPLE_PREFIX = 9, GS_STEP_SAMPLE_SPEC_PREFIX = 10, GS_STEP_POOL_SAMPLE_PREFIX = 11 };
 typedef std::vector<int> GraphKey;
 
 // Captured graphs of one family of keys.  A key runs eagerly the first time it is seen (`warmed`: function attributes are set
@@ -138,7 +141,10 @@ struct GraphCache {
   X(bp_row_of) X(bp_batch) X(bp_cand) X(bp_cand_len) X(bp_tok) X(bp_new_slot) X(bp_io) X(bp_grp) X(bp_src_acc) X(bp_enc_qkv)            \
   /* sampling loop (ttx_sample_generate): per decoder row its key, sample id, done flag and source row; the call's SampleBlock */ \
   /* speculative form: the copy drafts per source [B][N][D], before they are replicated to the decoder rows */                   \
-  X(smp_key) X(smp_sample) X(smp_done) X(smp_src_of) X(smp_prm) X(smp_drafts)
+  X(smp_key) X(smp_sample) X(smp_done) X(smp_src_of) X(smp_prm) X(smp_drafts)                                                     \
+  /* forced prefixes of a prompted sampling call: the table int32 [sources][max_len] and the sources' lengths; per decoder row */ \
+  /* (slot) its prefix length, its row of the table (pool; single-session loops use smp_src_of) and its source draft 0 [D] */     \
+  X(pfx_tok) X(pfx_len_src) X(pfx_len) X(pfx_src) X(pfx_draft0)
 #define TTX_DECLARE_BUF(name) Buf name;
 #define TTX_REGISTER_BUF(name) all.push_back(&name);
 

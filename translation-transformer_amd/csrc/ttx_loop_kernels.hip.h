@@ -573,6 +573,8 @@ struct PoolAdmitArgs {
   // sampling pool (key null: the greedy pool): the R rows are per_src consecutive samples of R / per_src sources, first_row =
   // first_src * per_src; row i gets the key of source first_src + i / per_src (row_keys null: that index) and sample id i % per_src
   unsigned long long* key; unsigned* sample; const int64_t* row_keys; int per_src, first_src;
+  // prompted sampling pool (pfx_src null: no prefixes): the slot's source index in the call's list and that source's prefix length
+  int* pfx_src; int* pfx_len; const int* pfx_len_of_src;
 };
 
 // One block.  Free slots = those not in act_idx[0, n_active); the R new rows take the lowest free ones in order.
@@ -597,6 +599,7 @@ __global__ __launch_bounds__(256) void k_pool_admit(PoolAdmitArgs a) {
         const int src = a.first_src + got / a.per_src;
         a.key[b] = a.row_keys ? (unsigned long long)a.row_keys[src] : (unsigned long long)src;
         a.sample[b] = (unsigned)(got % a.per_src);
+        if (a.pfx_src) { a.pfx_src[b] = src; a.pfx_len[b] = a.pfx_len_of_src[src]; }
       }
       ++got;
     }
@@ -621,6 +624,8 @@ struct PoolFillArgs {
   // sampling pool (0: the greedy pool): row i takes the staged drafts, validity bytes and cross K/V of source i / per_src, its
   // caller row starts as the sampler's (BOS in column 0), and there are no traj / fin_step rows
   int per_src;
+  // prompted sampling pool (null: no prefixes): [B, D], the slot's copy of its source draft 0, which k_prefix_drafts reads
+  int* draft0; int D;
 };
 
 // grid (R, 1 + Ls_new): block (i, 0) initialises row i's slot scalars and its caller-side rows, block (i, 1 + key)
@@ -633,6 +638,8 @@ __global__ __launch_bounds__(256) void k_pool_fill(PoolFillArgs a) {
   if (blockIdx.y == 0) {
     for (int c = t; c < a.gen_ld; c += blockDim.x) a.gen[(size_t)b * a.gen_ld + c] = (c == 0) ? a.bos : a.pad;
     for (int c = t; c < a.nd; c += blockDim.x) a.drafts[(size_t)b * a.nd + c] = a.drafts_new[(size_t)is * a.nd + c];
+    if (a.draft0)
+      for (int c = t; c < a.D; c += blockDim.x) a.draft0[(size_t)b * a.D + c] = a.drafts_new[(size_t)is * a.nd + c];
     for (int c = t; c < a.Ls_cap; c += blockDim.x)
       a.src_valid[(size_t)b * a.Ls_cap + c] = (c < a.Ls_new) ? a.valid_new[(size_t)is * a.Ls_new + c] : (uint8_t)0;
     const size_t row = (size_t)(a.first_row + i);

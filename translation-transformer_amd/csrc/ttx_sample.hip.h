@@ -19,6 +19,9 @@
 //   7  the token is eos or pad: done[r] = 1.
 // Rows at or beyond *m_ptr are not written.  Rows outside the contract (NaN, +inf, all -inf) give some id in [0, V).
 // k_sample_step is steps 2-6 (sample_row, shared with k_sample) on the rows of a speculative verify step: see its comment below.
+// Forced prefixes (PrefixTab, include/ttx.h "Forced target prefixes"): a live row whose position is inside its source's prefix emits
+// the prefix token (an id outside [0, V) as 0) and skips steps 2-6; the logits are not read and no uniform is formed.  k_prefix_drafts
+// rewrites draft 0 of every active row of a prompted speculative loop before each step.
 #pragma once
 #include "ttx_loop_kernels.hip.h"
 
@@ -37,6 +40,20 @@ struct SampleBlock {
   int pad, eos;
 };
 
+// The forced prefixes of a prompted call as the kernels see them (tok null: an unprompted call, nothing below is read).  `len` and
+// `src` go by decoder row (slot of a pool): the length of the row's prefix and the row of `tok` that holds it.
+struct PrefixTab {
+  const int* tok; int ld;          // [sources][ld]
+  const int* len;                  // [B]
+  const int* src;                  // [B]
+};
+
+// The forced token of decoder row b at position pos (1 <= pos <= len[b] <= ld), as every lane of the row's wave reads it.
+__device__ __forceinline__ int prefix_token(const PrefixTab& t, int b, int pos, int V) {
+  const int tok = t.tok[(size_t)t.src[b] * t.ld + pos - 1];
+  return (unsigned)tok < (unsigned)V ? tok : 0;
+}
+
 struct SampleArgs {
   const float* logits; int V;      // [M, V]
   int* pred;                       // [M]
@@ -46,6 +63,7 @@ struct SampleArgs {
   int* done;                       // [M], read and written
   const int* front;                // front[0] + 1 is the position being filled
   const SampleBlock* prm;
+  PrefixTab pfx;                   // by row
 };
 
 __global__ void k_sample_params(SampleBlock* out, SampleBlock v) {
@@ -220,7 +238,10 @@ __global__ __launch_bounds__(256) void k_sample(const SampleArgs a) {
     if (lane == 0) a.pred[row] = prm.pad;
     return;
   }
-  const int tok = sample_row<VPL>(a.logits + (size_t)row * a.V, a.V, prm, a.key[row], a.sample[row], (unsigned)(a.front[0] + 1), lane);
+  const int pos = a.front[0] + 1;
+  int tok;
+  if (a.pfx.tok && pos <= a.pfx.len[row]) tok = prefix_token(a.pfx, row, pos, a.V);     // wave-uniform
+  else tok = sample_row<VPL>(a.logits + (size_t)row * a.V, a.V, prm, a.key[row], a.sample[row], (unsigned)pos, lane);
   if (lane == 0) {
     a.pred[row] = tok;
     if (tok == prm.eos || tok == prm.pad) a.done[row] = 1;
@@ -247,6 +268,7 @@ struct SampleStepArgs {
   int N, D;
   const SampleBlock* prm;
   const int* row_map;              // [rows] or null: row = layout row
+  PrefixTab pfx;                   // by decoder row, like key and sample
 };
 
 template <int VPL>
@@ -262,7 +284,9 @@ __global__ __launch_bounds__(256) void k_sample_step(const SampleStepArgs a) {
   const int b = a.act_idx[lrow / RPS];
   int pos = a.front[b] + 1;
   if (rs != 0 && a.D > 0) pos += 1 + (rs - 1) % a.D;       // the probe (D == 0) has row 0 only
-  const int tok = sample_row<VPL>(a.logits + (size_t)row * a.V, a.V, prm, a.key[b], a.sample[b], (unsigned)pos, lane);
+  int tok;
+  if (a.pfx.tok && pos <= a.pfx.len[b]) tok = prefix_token(a.pfx, b, pos, a.V);        // wave-uniform
+  else tok = sample_row<VPL>(a.logits + (size_t)row * a.V, a.V, prm, a.key[b], a.sample[b], (unsigned)pos, lane);
   if (lane == 0) a.pred[row] = tok;
 }
 
@@ -270,6 +294,67 @@ __global__ __launch_bounds__(256) void k_sample_step(const SampleStepArgs a) {
 __global__ void k_sample_rep_drafts(const int* in, int* out, int R, int n, int nd) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < R * nd) out[i] = in[(size_t)(i / nd / n) * nd + i % nd];
+}
+
+// ------------------------------------------------------------------------------------------------
+// Forced prefixes in the speculative sampling loops.  The acceptance rule is untouched: a draft token is accepted iff it is the token
+// of its position, and inside the prefix that token is the prefix's (k_sample_step above).  So the prefix is offered as draft 0:
+// before every verify step, column c = front + 1 + j of draft 0 of every active row receives prefix[c - 1] while c <= len (EOS and
+// PAD as `repl`, as k_make_drafts writes them, so that drafts still hold neither and a forced EOS arrives as the bonus token), and
+// token j of the row's own source draft 0 beyond it.  Stateless and idempotent: the D ints of every active row are rewritten from
+// `draft0`, which nothing writes after the row was set up, so once front >= len draft 0 is the source draft again.  Drafts 1 .. N-1
+// are not touched.  One wave per slot, grid for the capacity; per slot one round of independent loads (front, len, src by the
+// row) and then D independent ones.
+struct PrefixDraftsArgs {
+  const DecState* st;              // n_active live slots
+  const int* act_idx;              // [n_active]
+  const int* front;                // [B]
+  int* drafts; int N, D;           // [B, N, D], draft 0 of the active rows rewritten
+  const int* draft0;               // [B, D] the rows' source draft 0
+  PrefixTab pfx;
+  int eos, pad, repl;
+};
+
+__global__ __launch_bounds__(256) void k_prefix_drafts(const PrefixDraftsArgs a) {
+  const int slot = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (slot >= a.st->n_active) return;       // wave-uniform
+  const int lane = threadIdx.x & 63;
+  const int b = a.act_idx[slot];
+  const int f = a.front[b], len = a.pfx.len[b], src = a.pfx.src[b];
+  const int* pre = a.pfx.tok + (size_t)src * a.pfx.ld;
+  const int* own = a.draft0 + (size_t)b * a.D;
+  int* out = a.drafts + (size_t)b * a.N * a.D;
+  for (int j = lane; j < a.D; j += 64) {
+    const int c = f + 1 + j;
+    int t;
+    if (c <= len) {
+      t = pre[c - 1];
+      if (t == a.eos || t == a.pad) t = a.repl;
+    } else {
+      t = own[j];
+    }
+    out[j] = t;
+  }
+}
+
+// The session's prefix table of a prompted call: int64 [S][ld_in] -> int32 [S][ld], columns at or beyond a source's length (and
+// beyond ld_in) as `pad`.  Lengths are bounded by min(ld, ld_in) (checked on the host).
+__global__ void k_prefix_load(const int64_t* in, int ld_in, const int* len, int* out, int S, int ld, int pad) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= S * ld) return;
+  const int s = i / ld, c = i - s * ld;
+  int t = pad;
+  if (c < len[s] && c < ld_in) {
+    const int64_t v = in[(size_t)s * ld_in + c];
+    t = (v >= 0 && v <= 0x7fffffff) ? (int)v : -1;       // an id no int32 holds stays outside every vocabulary
+  }
+  out[i] = t;
+}
+
+// Prefix length of every decoder row of a single-session loop: its source's.
+__global__ void k_prefix_rows(const int* len_src, const int* src_of, int* len_row, int R) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < R) len_row[r] = len_src[src_of[r]];
 }
 
 }  // namespace ttx

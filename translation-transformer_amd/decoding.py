@@ -354,6 +354,30 @@ class TranslationInferenceGreedy(_ScoresHypotheses):
         return self._scored(src, out, return_scores)
 
 
+def check_prefix(prefix, B: int, max_len: int, pad_token: int, vocab_size: int):
+    """The forced target prefixes of a sampling call: ``prefix`` Long[B, Lp] without BOS, right-padded with PAD, a row's
+    length the number of tokens before its first PAD.  Returns ``(Long[B, Lp] on the CPU, [length per source])``, or
+    ``(None, None)`` for ``prefix=None``.  ValueError: a shape that is not [B, Lp], a non-PAD token after a PAD, an id
+    outside the vocabulary, a length above ``max_len - 1``.  Needs no device."""
+    if prefix is None:
+        return None, None
+    p = torch.as_tensor(prefix)
+    if p.dim() != 2 or p.dtype.is_floating_point or p.dtype == torch.bool:
+        raise ValueError(f"prefix must be an integer tensor [B, Lp], got {tuple(p.shape)} {p.dtype}")
+    if p.shape[0] != B:
+        raise ValueError(f"prefix must hold one row per source ({B}), got {p.shape[0]}")
+    p = p.detach().to("cpu", torch.int64).contiguous()
+    is_pad = p == pad_token
+    lengths = (~is_pad).to(torch.int64).cumprod(dim=1).sum(dim=1)            # tokens before the first PAD
+    if bool(((~is_pad).sum(dim=1) != lengths).any()):
+        raise ValueError("prefix holds a non-PAD token after a PAD: prefixes are right-padded")
+    if p.numel() and (int(p.min()) < 0 or int(p.max()) >= vocab_size):
+        raise ValueError(f"prefix holds an id outside the vocabulary [0, {vocab_size})")
+    if p.shape[0] and int(lengths.max()) > max_len - 1:
+        raise ValueError(f"a prefix of {int(lengths.max())} tokens does not fit max_len - 1 = {max_len - 1}")
+    return p, [int(x) for x in lengths]
+
+
 class TranslationInferenceSampling(_ScoresHypotheses):
     """Seeded ancestral sampling: ``num_samples`` draws per source from the model's distribution under ``temperature``,
     ``top_k`` and ``top_p``.  The whole loop runs in ttx_sample_generate: the greedy loop (KV cache, one graph per step) with
@@ -374,19 +398,36 @@ class TranslationInferenceSampling(_ScoresHypotheses):
         self.num_samples, self.seed = int(num_samples), int(seed)
         self.model_calls_num = 0
         self.given_tokens = 0
+        self.last_stats: N.GenStats | None = None
 
     def __str__(self):
         return (f"Sampling (temperature={self.temperature}, top_k={self.top_k}, top_p={self.top_p}, "
                 f"num_samples={self.num_samples}, seed={self.seed}, max_len={self.max_len})")
 
-    def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False):
+    def _prefix_args(self, prefix, B: int):
+        """``(device tensor or None, its pointer, its row length, host lengths)`` of a call's ``prefix`` (``check_prefix``)."""
+        m = self.model
+        p, lengths = check_prefix(prefix, B, self.max_len, self.pad_token, m.tgt_vocab_size)
+        if p is None:
+            return None, None, 0, None
+        d = p.to(m.device)
+        return d, (d.data_ptr() if d.numel() else None), int(d.shape[1]), (C.c_int32 * max(B, 1))(*lengths)
+
+    def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, prefix=None):
         """Long[B, num_samples, max_len].  ``row_keys``: one integer per source (default 0..B-1), the source's identity for
         the random stream: the same (source, key) gives the same samples in any batch.  ``return_scores=True``:
-        ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``)."""
+        ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``).
+
+        ``prefix``: Long[B, Lp] without BOS, right-padded with PAD: the forced beginning of every sample of a source.  A
+        row is BOS, its prefix, the sampled completion, PAD; a position inside the prefix holds the prefix token whatever the
+        logits say and consumes no random number, so the completion's draws are those of its positions.  A forced EOS ends
+        the row.  One decoder step per forced token.  An empty prefix (zero width, all PAD, ``None``) is the unprompted call."""
         m, n = self.model, self.num_samples
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
         B, Ls = src.shape
+        # d_prefix is bound only to keep the device tensor alive until the call returns: prefix_ptr points into it
+        d_prefix, prefix_ptr, ld_prefix, h_plen = self._prefix_args(prefix, B)
         keys = None
         if row_keys is not None:
             keys = torch.as_tensor(row_keys, dtype=torch.int64).to(m.device).contiguous()
@@ -396,10 +437,12 @@ class TranslationInferenceSampling(_ScoresHypotheses):
                            self.eos_token, self.seed & 0xFFFFFFFFFFFFFFFF)
         out = torch.empty((B, max(n, 1), max(self.max_len, 1)), dtype=torch.int64, device=m.device)
         st = N.GenStats()
-        N.check(m._lib.ttx_sample_generate(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
-                                           C.byref(p), out.data_ptr(), C.byref(st), m._stream()))
+        N.check(m._lib.ttx_sample_generate_prefix(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
+                                                  C.byref(p), prefix_ptr, ld_prefix, h_plen, out.data_ptr(), C.byref(st),
+                                                  m._stream()))
         self.model_calls_num += int(st.model_calls)
         self.given_tokens += int((src != m.src_pad_token_i).sum())
+        self.last_stats = st
         return self._scored(src, out, return_scores)
 
 
@@ -426,12 +469,16 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         return (f"Speculative sampling (draft_len={self.draft_len}, n_drafts={self.n_drafts}, temperature={self.temperature}, "
                 f"top_k={self.top_k}, top_p={self.top_p}, num_samples={self.num_samples}, seed={self.seed}, max_len={self.max_len})")
 
-    def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False):
-        """Long[B, num_samples, max_len]; ``row_keys`` and ``return_scores`` as for ``TranslationInferenceSampling.generate``."""
+    def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, prefix=None):
+        """Long[B, num_samples, max_len]; ``row_keys``, ``return_scores`` and ``prefix`` as for
+        ``TranslationInferenceSampling.generate``.  A prefix rides in as the first draft of its rows, which is certain to be
+        accepted: ``P`` forced tokens take ``ceil(P / (draft_len + 1))`` verify steps."""
         m, n = self.model, self.num_samples
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
         B, Ls = src.shape
+        # d_prefix is bound only to keep the device tensor alive until the call returns: prefix_ptr points into it
+        d_prefix, prefix_ptr, ld_prefix, h_plen = self._prefix_args(prefix, B)
         keys = None
         if row_keys is not None:
             keys = torch.as_tensor(row_keys, dtype=torch.int64).to(m.device).contiguous()
@@ -442,8 +489,9 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
                                self.draft_len, self.n_drafts, self.replace_token, 0)
         out = torch.empty((B, max(n, 1), max(self.max_len, 1)), dtype=torch.int64, device=m.device)
         st = N.GenStats()
-        N.check(m._lib.ttx_sample_speculative_generate(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
-                                                       C.byref(p), out.data_ptr(), C.byref(st), m._stream()))
+        N.check(m._lib.ttx_sample_speculative_generate_prefix(m.session, src.data_ptr(), B, Ls,
+                                                              None if keys is None else keys.data_ptr(), C.byref(p), prefix_ptr,
+                                                              ld_prefix, h_plen, out.data_ptr(), C.byref(st), m._stream()))
         self.model_calls_num += int(st.model_calls)
         self.accepted_tokens_num += int(st.accepted_tokens)
         self.given_tokens += int((src != m.src_pad_token_i).sum())
@@ -457,7 +505,7 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         return self._scored(src, out, return_scores)
 
     def generate_many(self, batches: list, row_keys=None, in_flight: int = 4, capacity: int | None = None,
-                      return_scores: bool = False) -> list:
+                      return_scores: bool = False, prefixes=None) -> list:
         """The samples of all batches from slot pools (ttx_sample_speculative_generate_pool: continuous batching over the sources
         of the whole list, sorted by length; the ``num_samples`` rows of a source are admitted together).  Returns one
         Long[B_i, num_samples, max_len] per batch.
@@ -467,16 +515,36 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         not depend on its slot, on the capacity or on what shares the pool.  ``capacity`` (slots, i.e. decoder rows, per pool;
         ``TTX_POOL_CAPACITY``) and the pool count follow the greedy generator's rule over the ``S * num_samples`` decoder rows and
         are never below ``num_samples``.  ``model_calls_num`` counts the verify steps the device executed.
-        ``return_scores=True``: a list of ``(pred, HypothesisScores)`` pairs."""
+        ``return_scores=True``: a list of ``(pred, HypothesisScores)`` pairs.
+        ``prefixes``: a list aligned with ``batches``, each entry a ``prefix`` tensor for that batch (see ``generate``) or
+        ``None``; ``generate_many(batches, prefixes=ps)[i]`` holds the rows of ``generate(batches[i], prefix=ps[i],
+        row_keys=arange(off_i, off_i + B_i))``."""
         if return_scores:
-            return self._scored_many(batches, self.generate_many(batches, row_keys, in_flight, capacity))
+            return self._scored_many(batches, self.generate_many(batches, row_keys, in_flight, capacity, prefixes=prefixes))
         from .scheduling import plan_row_groups
+        if prefixes is not None and len(prefixes) != len(batches):
+            raise ValueError(f"prefixes must hold one entry per batch ({len(batches)}), got {len(prefixes)}")
         if not batches:
             return []
         m, n, L = self.model, self.num_samples, self.max_len
-        srcs = [b.to(m.device, torch.int64) for b in batches]
-        sizes = [int(s.shape[0]) for s in srcs]
+        sizes = [int(b.shape[0]) for b in batches]
         S = sum(sizes)
+        # every source's prefix in one right-padded matrix beside the sources, or None when no batch carries one
+        allpre = plen = None
+        if prefixes is not None and any(q is not None for q in prefixes):
+            checked = [check_prefix(q, B, L, self.pad_token, m.tgt_vocab_size) for q, B in zip(prefixes, sizes)]
+            Lp = max([int(c[0].shape[1]) for c in checked if c[0] is not None] or [0])
+            allpre = torch.full((S, Lp), self.pad_token, dtype=torch.int64)
+            plen = torch.zeros(S, dtype=torch.int64)
+            r0 = 0
+            for (q, lens), B in zip(checked, sizes):
+                if q is not None:
+                    allpre[r0:r0 + B, :q.shape[1]] = q
+                    plen[r0:r0 + B] = torch.tensor(lens, dtype=torch.int64)
+                r0 += B
+            if not bool(plen.any()):                  # every prefix is empty: the unprompted call, with nothing to sort or upload
+                allpre = plen = None
+        srcs = [b.to(m.device, torch.int64) for b in batches]
         if row_keys is None:
             keys = torch.arange(S, dtype=torch.int64)
         else:
@@ -518,9 +586,15 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
             h_len = (C.c_int32 * S)(*[int(x) for x in sorted_len])
             sessions = m.session_pool(n_sess)
             sess = (C.c_void_p * len(sessions))(*[q.value for q in sessions])
-            N.check(m._lib.ttx_sample_speculative_generate_pool(sess, len(sessions), src_mat.data_ptr(), S, width, h_len,
-                                                                keys_sorted.data_ptr(), cap, C.byref(p), out_sorted.data_ptr(),
-                                                                C.byref(st), m._stream()))
+            pre_sorted, pre_ptr, ld_prefix, h_plen = None, None, 0, None
+            if allpre is not None:
+                order_cpu = torch.from_numpy(order).to(torch.int64)
+                pre_sorted = allpre[order_cpu].contiguous().to(m.device)
+                pre_ptr, ld_prefix = (pre_sorted.data_ptr() if pre_sorted.numel() else None), int(pre_sorted.shape[1])
+                h_plen = (C.c_int32 * S)(*[int(x) for x in plen[order_cpu]])
+            N.check(m._lib.ttx_sample_speculative_generate_pool_prefix(sess, len(sessions), src_mat.data_ptr(), S, width, h_len,
+                                                                       keys_sorted.data_ptr(), cap, C.byref(p), pre_ptr, ld_prefix,
+                                                                       h_plen, out_sorted.data_ptr(), C.byref(st), m._stream()))
             inv = torch.empty_like(order_t)
             inv[order_t] = torch.arange(S, device=m.device)
             out_rows = out_sorted[inv]

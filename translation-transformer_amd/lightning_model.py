@@ -108,19 +108,25 @@ class _PredictAhead:
         self.served = self.fallbacks = self.windows = 0
         self.decode_seconds = 0.0
         self.rows = 0                # sources decoded ahead so far: the running index the sampling generators key their rows by
+        self.prefixes = {}           # batch index -> the batch's "prefix_tokens" it was decoded with (sampling generators; None: none)
 
     def _decode_window(self, device) -> None:
-        pending = []
+        pending, prefixes = [], []
         for _ in range(self.window):
             try:
                 b = next(self.it)
             except StopIteration:
                 break
             pending.append(b["src_tokens"].to(device))
+            prefixes.append(b.get("prefix_tokens") if hasattr(b, "get") else None)
         if not pending:
             self.enabled = False
             return
         g = self.generator
+        prompted = any(q is not None for q in prefixes)
+        if prompted and not isinstance(g, D.TranslationInferenceSamplingSpeculative):
+            raise ValueError(f'"prefix_tokens" in a batch: only generation="sampling" and "sampling_speculative" take forced prefixes, '
+                             f"not {type(g).__name__}")
         t0 = timer()
         if isinstance(g, D.TranslationInferenceGreedySpeculative):      # slot pools over all rows of the window
             preds = g.generate_many(pending, in_flight=self.in_flight, reorder=True, on_error="skip")
@@ -129,7 +135,7 @@ class _PredictAhead:
             for b in pending:
                 keys.append(torch.arange(r0, r0 + int(b.shape[0])))
                 r0 += int(b.shape[0])
-            preds = g.generate_many(pending, row_keys=keys, in_flight=self.in_flight)
+            preds = g.generate_many(pending, row_keys=keys, in_flight=self.in_flight, prefixes=prefixes if prompted else None)
             self.rows = r0
         else:                                                           # source pools over all sources of the window
             preds = g.generate_many(pending, in_flight=self.in_flight, on_error="skip")
@@ -138,6 +144,7 @@ class _PredictAhead:
         self.windows += 1
         for k, (src, pred) in enumerate(zip(pending, preds)):
             self.ready[self.next_idx + k] = (src, pred, shares[k])
+            self.prefixes[self.next_idx + k] = prefixes[k]
         self.next_idx += len(pending)
 
     def _take_back(self, entries) -> None:
@@ -147,17 +154,26 @@ class _PredictAhead:
                 for name, v in share.items():
                     setattr(self.generator, name, getattr(self.generator, name) - v)
 
-    def take(self, src: torch.Tensor, batch_idx: int):
-        """The prediction prepared for batch `batch_idx`, or None (decode it now)."""
+    @staticmethod
+    def _same_prefix(a, b) -> bool:
+        if a is None or b is None:
+            return a is None and b is None
+        return a.shape == b.shape and torch.equal(a.cpu(), b.cpu())
+
+    def take(self, src: torch.Tensor, batch_idx: int, prefix=None):
+        """The prediction prepared for batch `batch_idx` (and its forced prefixes `prefix`), or None (decode it now)."""
         if not self.enabled:
             return None
         if batch_idx not in self.ready and batch_idx == self.next_idx:
             self._decode_window(src.device)
         hit = self.ready.pop(batch_idx, None)
-        if hit is None or hit[0].shape != src.shape or not torch.equal(hit[0], src.to(hit[0].device)):
+        had = self.prefixes.pop(batch_idx, None)
+        if hit is None or hit[0].shape != src.shape or not torch.equal(hit[0], src.to(hit[0].device)) \
+                or not self._same_prefix(had, prefix):
             self.enabled = False                       # not the batch that was decoded for this index: stop looking ahead
             self._take_back(([hit] if hit is not None else []) + list(self.ready.values()))
             self.ready.clear()
+            self.prefixes.clear()
             self.fallbacks += 1
             return None
         if hit[1] is None:                             # the reference raises on this batch: let generate() raise it here
@@ -295,13 +311,19 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             self.build_native()
         ahead = self._ahead
         pred = None
+        sampling = self.hparams.generation in ("sampling", "sampling_speculative")
+        prefix = batch["prefix_tokens"] if "prefix_tokens" in batch else None      # forced target prefixes: Long[B, Lp], no BOS
+        if prefix is not None and not sampling:
+            raise ValueError(f'"prefix_tokens" in a batch: only generation="sampling" and "sampling_speculative" take forced '
+                             f'prefixes, not "{self.hparams.generation}"')
         if ahead is not None and dataloader_idx == 0:
-            pred = ahead.take(batch["src_tokens"], batch_idx)
+            pred = ahead.take(batch["src_tokens"], batch_idx, prefix)
         if pred is not None and self.hparams.generation in ("sampling", "sampling_speculative"):
             self._predict_rows += int(batch["src_tokens"].shape[0])        # served ahead under these keys: a fallback goes on from here
         elif pred is None and self.hparams.generation in ("sampling", "sampling_speculative"):
             B = int(batch["src_tokens"].shape[0])
-            pred = self.generator.generate(batch["src_tokens"], row_keys=torch.arange(self._predict_rows, self._predict_rows + B))
+            pred = self.generator.generate(batch["src_tokens"], row_keys=torch.arange(self._predict_rows, self._predict_rows + B),
+                                           prefix=prefix)
             self._predict_rows += B
         elif pred is None:
             pred = self.generator.generate(batch["src_tokens"])

@@ -374,6 +374,48 @@ class NativeTransformer:
                                                        int(n_active), pred.data_ptr(), self._ptr(m_live), C.byref(p),
                                                        self._ptr(row_map), int(n_rows), self._stream()))
 
+    @staticmethod
+    def _debug_prefix(tok: torch.Tensor, length: torch.Tensor, src: torch.Tensor) -> N.DebugPrefix:
+        """ttx_debug_prefix of the forced prefixes ``tok`` int32 [sources, ld], ``length`` int32 [rows], ``src`` int32 [rows]."""
+        return N.DebugPrefix(tok.data_ptr(), int(tok.shape[1]), int(tok.shape[0]), length.data_ptr(), src.data_ptr())
+
+    def debug_prefix_drafts(self, act_idx: torch.Tensor, front: torch.Tensor, drafts: torch.Tensor, draft0: torch.Tensor, *,
+                            prefix_tok: torch.Tensor, prefix_len: torch.Tensor, prefix_src: torch.Tensor, n_active: int,
+                            eos: int = 2, pad: int = 0, replace: int = 3) -> None:
+        """One k_prefix_drafts launch (ttx_debug_prefix_drafts): ``act_idx`` / ``front`` int32 [B], ``drafts`` int32 [B, n, d]
+        (draft 0 of the active rows is rewritten), ``draft0`` int32 [B, d], the prefix table int32 [sources, ld] with the rows'
+        lengths and sources int32 [B]."""
+        B, n, d = drafts.shape
+        x = self._debug_prefix(prefix_tok, prefix_len, prefix_src)
+        N.check(self._lib.ttx_debug_prefix_drafts(self._session, act_idx.data_ptr(), front.data_ptr(), int(B), int(n), int(d),
+                                                  int(n_active), drafts.data_ptr(), draft0.data_ptr(), C.byref(x), int(eos), int(pad),
+                                                  int(replace), self._stream()))
+
+    def debug_sample_prefix(self, logits: torch.Tensor, key: torch.Tensor, sample: torch.Tensor, done: torch.Tensor,
+                            front: torch.Tensor, pred: torch.Tensor, m_max: int, m_live: torch.Tensor | None = None, *,
+                            prefix_tok: torch.Tensor, prefix_len: torch.Tensor, prefix_src: torch.Tensor, temperature: float = 1.0,
+                            top_k: int = 0, top_p: float = 1.0, pad: int = 0, eos: int = 2, seed: int = 0) -> None:
+        """``debug_sample`` with forced prefixes (ttx_debug_sample_prefix): the table and the rows' lengths and sources [m_max]."""
+        p = N.SampleParams(1, 1, float(temperature), int(top_k), float(top_p), int(pad), 0, int(eos), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        x = self._debug_prefix(prefix_tok, prefix_len, prefix_src)
+        N.check(self._lib.ttx_debug_sample_prefix(self._session, logits.data_ptr(), int(logits.shape[1]), key.data_ptr(),
+                                                  sample.data_ptr(), done.data_ptr(), front.data_ptr(), pred.data_ptr(),
+                                                  self._ptr(m_live), int(m_max), C.byref(p), C.byref(x), self._stream()))
+
+    def debug_sample_step_prefix(self, logits: torch.Tensor, key: torch.Tensor, sample: torch.Tensor, act_idx: torch.Tensor,
+                                 front: torch.Tensor, pred: torch.Tensor, *, B: int, n: int, d: int, n_active: int, n_rows: int,
+                                 prefix_tok: torch.Tensor, prefix_len: torch.Tensor, prefix_src: torch.Tensor,
+                                 row_map: torch.Tensor | None = None, m_live: torch.Tensor | None = None, temperature: float = 1.0,
+                                 top_k: int = 0, top_p: float = 1.0, pad: int = 0, eos: int = 2, seed: int = 0) -> None:
+        """``debug_sample_step_select`` with forced prefixes (ttx_debug_sample_step_prefix): the table and the decoder rows' lengths
+        and sources [B]."""
+        p = N.SampleParams(1, 1, float(temperature), int(top_k), float(top_p), int(pad), 0, int(eos), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        x = self._debug_prefix(prefix_tok, prefix_len, prefix_src)
+        N.check(self._lib.ttx_debug_sample_step_prefix(self._session, logits.data_ptr(), int(logits.shape[1]), key.data_ptr(),
+                                                       sample.data_ptr(), act_idx.data_ptr(), front.data_ptr(), int(B), int(n), int(d),
+                                                       int(n_active), pred.data_ptr(), self._ptr(m_live), C.byref(p),
+                                                       self._ptr(row_map), int(n_rows), C.byref(x), self._stream()))
+
     def debug_sample_accept_pool(self, state, *, B: int, n: int, d: int, Ls: int, max_len: int, pad: int, bos: int, eos: int,
                                  gen_ld: int, pool_rows: int, traj_ld: int = 1, threads: int = 0, spread: bool = False,
                                  exec_rows: torch.Tensor | None = None, **arrays) -> list:
