@@ -493,6 +493,56 @@ typedef struct ttx_beam_search_stats {
 int ttx_beam_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_beam_search_params* p, int64_t* d_out,
                       ttx_beam_search_stats* stats, void* stream);
 
+/* Stochastic beam search (Kool, van Hoof & Welling, "Stochastic Beams and Where to Find Them", ICML 2019): K hypotheses per source
+ * that are an exact sample WITHOUT replacement from the model's sequence distribution at the given temperature.  The loop is
+ * ttx_beam_generate's (per-hypothesis KV cache, one decoder pass per level over the unfinished candidates) with k_sbs_step
+ * (csrc/ttx_sbs.hip.h) where that loop launches k_beam_step.
+ *
+ * The rule.  Per candidate: phi (fp32 log-probability), G (fp32 perturbed log-probability) and `finished`.  Start: one <BOS>
+ * candidate per source with phi = 0, G = 0.  Step at position pos (1 = first token after BOS), source with key `key`, candidates
+ * k = 0 .. beam-1 in the order of the previous selection; beam is 1 at the first step and K afterwards:
+ *   1  y_v = x_v * inv_T with inv_T = 1.0f / temperature formed on the host, one rounded fp32 product per logit.
+ *   2  m = max_v y_v, z = sum_v expf(y_v - m) in an order fixed by V alone (csrc/ttx_sbs.hip.h), lp_v = (y_v - m) - logf(z),
+ *      phi'_{k,v} = phi_k + lp_v.
+ *   3  u_{k,v} = ((w >> 9) + 0.5f) * 2^-23, an fp32 strictly inside (0, 1), exact; w = word v & 3 of Philox4x32-10 with key
+ *      (seed_lo, seed_hi) and counter (key_lo, key_hi, 0x80000000 | (k << 8) | (v >> 2), pos); constants and round function as
+ *      for ttx_sample_generate.  Bit 31 of counter word 2 keeps these draws apart from the sampler's, whose word 2 is a sample id.
+ *   4  g_{k,v} = phi'_{k,v} - logf(-logf(u_{k,v})), Z_k = max_v g_{k,v}.
+ *   5  G'_{k,v} = G_k exactly where g_{k,v} == Z_k; elsewhere t = G_k - g + log1pf(-expf(g - Z_k)) and
+ *      G' = G_k - fmaxf(t, 0) - log1pf(expf(-fabsf(t))).  A -inf logit gives G' = -inf.
+ *   6  A finished candidate has one child, token PAD at flat index k * V + pad, with phi and G unchanged; its logits are not read.
+ *   7  The new candidates are the K largest G' over the beam * V children, largest first; equal values break towards the lower
+ *      flat index k * V + v.  New candidate r takes the parent's row plus the token, phi', G', and finished = parent finished or
+ *      token in {EOS, PAD}.  G' = -inf is selected only when fewer than K finite children exist; such a candidate is finished and
+ *      its logp and gumbel are -inf.
+ *   8  The loop ends when all B * K candidates are finished, or after max_len - 1 steps.
+ * Consequences: rank 0 of every source carries gumbel == 0.0f exactly; G' never exceeds its parent's G; the K hypotheses of a
+ * source are pairwise distinct; noise is keyed by parent rank and ranks nest, so the call with K returns the first K rows of the
+ * call with K' > K; the output depends on the source, its key, the seed, the temperature and K only (not on B or the padded width).
+ *
+ *   d_out int64 [B, K, max_len]: BOS, the tokens up to and including the row's first EOS or PAD, PAD after it; rows in sampling
+ *   order (gumbel descending).  d_logp, d_gumbel fp32 [B, K].  d_row_keys int64 [B] or NULL (keys 0 .. B-1).
+ *   trace (optional): device arrays [max_len - 1, B, K] of the parent rank, token, phi' and G' of every new candidate of every
+ *   level; stats->model_calls says how many levels are valid.  stats->out_width is the number of columns the loop filled.
+ * Cost, measured on one MI355X (4+4 model, 32 sources, max_len 200): 1.8 % (K = 5) and 2.2 % (K = 10) more per
+ * decoder step than ttx_beam_generate with the same K, and 8.8 % / 11.0 % more per call, since the sampled rows run longer.
+ * Limits: no top-k / top-p filter, no forced prefix, no pooled generate_many.  TTX_ERR_INVALID with nothing launched: max_len <= 1,
+ * beam_size outside [1, min(32, vocab_size)], vocab_size > 1024, beam_size * vocab_size * 4 > 150 KB, a temperature that is not
+ * finite or not > 0, a trace with a NULL array, and everything else ttx_beam_generate refuses. */
+typedef struct ttx_sbs_params {
+  int32_t max_len, beam_size;            /* beam_size = K */
+  float   temperature;                   /* finite, > 0 */
+  int32_t pad_token, bos_token, eos_token;
+  uint64_t seed;
+} ttx_sbs_params;
+typedef struct ttx_sbs_trace {
+  int32_t* d_parent; int32_t* d_token;   /* [max_len - 1, B, K] */
+  float* d_phi; float* d_g;
+} ttx_sbs_trace;
+int ttx_sbs_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sbs_params* p,
+                     int64_t* d_out, float* d_logp, float* d_gumbel, const ttx_sbs_trace* trace_or_null,
+                     ttx_beam_search_stats* stats, void* stream);
+
 /* Several batches in flight on one GPU (the scheduling SURVEY.md §8(f) #1 names; the reference's predict loop
  * is strictly one batch at a time, src/model/lightning_model.py:209-212).  Batch i is decoded on
  * sessions[i % n_sessions]; each session runs on its own internal stream that first waits for `stream`
@@ -875,6 +925,21 @@ typedef struct ttx_debug_beam_step_args {
 } ttx_debug_beam_step_args;
 /* ttx_debug_beam_step: k_beam_step on B workgroups.  Also refused: K > beam * V, width >= ld. */
 int ttx_debug_beam_step(ttx_session* s, const ttx_debug_beam_step_args* a, void* stream);
+
+typedef struct ttx_debug_sbs_step_args {
+  const float* d_logits; const int32_t* d_slot_of; const uint8_t* d_finished; const float* d_phi; const float* d_g; const int32_t* d_gen;
+  const int64_t* d_key;                 /* [B] or NULL: keys 0 .. B-1 */
+  int64_t* d_new_cand; float* d_new_phi; float* d_new_g; int32_t* d_parent; int32_t* d_new_len; uint8_t* d_new_finished;
+  int32_t* d_parent_draft;
+  int32_t* d_summary;                   /* [0] += new candidates that are finished */
+  int32_t* d_tr_parent; int32_t* d_tr_token; float* d_tr_phi; float* d_tr_g;    /* [B, K] trace records, all four or none */
+  uint64_t seed;
+  int32_t V, ld, width, B, beam, K, pad, eos, pos;
+  float inv_T;
+} ttx_debug_sbs_step_args;
+/* ttx_debug_sbs_step: k_sbs_step on B workgroups, operands as for ttx_debug_beam_step with phi, G, the keys, the position, the
+ * seed and inv_T added.  Also refused: beam or K above 32, K > beam * V, width >= ld, pos < 1, inv_T not finite or not > 0. */
+int ttx_debug_sbs_step(ttx_session* s, const ttx_debug_sbs_step_args* a, void* stream);
 
 typedef struct ttx_debug_tree_cache_args {
   const int32_t* d_len; const int32_t* d_parent; const int32_t* d_parent_draft; const int32_t* d_prev_len; const uint8_t* d_active;

@@ -5,7 +5,8 @@ from ._native import build, lib, TtxError, ReferenceError_  # noqa: F401
 from .model import NativeTransformer, HypothesisScores, AttentionMaps, Alternatives, reference_pe_table  # noqa: F401
 from .decoding import (TranslationInferenceGreedySpeculative, TranslationInferenceGreedy,  # noqa: F401
                        TranslationInferenceBeamSearch, TranslationInferenceBeamSearchSpeculative,
-                       TranslationInferenceSampling, TranslationInferenceSamplingSpeculative)
+                       TranslationInferenceSampling, TranslationInferenceSamplingSpeculative,
+                       TranslationInferenceStochasticBeamSearch, SbsDetails, SbsTrace)
 from .lightning_model import VanillaEncoderDecoderTransformerLightning, run_predict, run_evaluate  # noqa: F401,E402
 from . import dist  # noqa: F401,E402
 from .tokenizer import NativeSmilesTokenizer  # noqa: F401,E402

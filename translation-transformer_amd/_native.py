@@ -17,7 +17,7 @@ LIB_PATH = PKG_DIR / "libttx_hip.so"
 # translation units (compiled in parallel, linked into one shared library) and the headers every one of them depends on
 UNITS = [CSRC / "ttx_api.hip", CSRC / "ttx_gemm.hip", CSRC / "ttx_attn.hip"]
 HEADERS = [CSRC / "ttx_internal.h", CSRC / "ttx_common.hip.h", CSRC / "ttx_loop_kernels.hip.h", CSRC / "ttx_metrics.hip.h",
-           CSRC / "ttx_score.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_sample.hip.h",
+           CSRC / "ttx_score.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_sample.hip.h", CSRC / "ttx_sbs.hip.h",
            CSRC / "ttx_select.h", CSRC / "ttx_tokenizer.h", CSRC / "ttx_drive.h", CSRC / "ttx_admit.h", INCLUDE / "ttx.h"]
 SOURCES = UNITS + HEADERS
 OBJ_DIR = CSRC / "build"
@@ -85,6 +85,26 @@ class BeamSearchParams(C.Structure):
 
 class BeamSearchStats(C.Structure):
     _fields_ = [("model_calls", C.c_int64), ("running_rows", C.c_int64), ("out_width", C.c_int32), ("pad_", C.c_int32)]
+
+
+class SbsParams(C.Structure):
+    """ttx_sbs_params: stochastic beam search; beam_size is K, the temperature is finite and > 0."""
+    _fields_ = [("max_len", C.c_int32), ("beam_size", C.c_int32), ("temperature", C.c_float), ("pad_token", C.c_int32),
+                ("bos_token", C.c_int32), ("eos_token", C.c_int32), ("seed", C.c_uint64)]
+
+
+class SbsTrace(C.Structure):
+    """ttx_sbs_trace: device arrays [max_len - 1, B, K] of parent rank, token, phi' and G' per level."""
+    _fields_ = [(n, C.c_void_p) for n in ("d_parent", "d_token", "d_phi", "d_g")]
+
+
+class DebugSbsStepArgs(C.Structure):
+    """ttx_debug_sbs_step_args: one k_sbs_step launch's operands."""
+    POINTERS = ("d_logits", "d_slot_of", "d_finished", "d_phi", "d_g", "d_gen", "d_key", "d_new_cand", "d_new_phi", "d_new_g",
+                "d_parent", "d_new_len", "d_new_finished", "d_parent_draft", "d_summary", "d_tr_parent", "d_tr_token", "d_tr_phi",
+                "d_tr_g")
+    _fields_ = [(n, C.c_void_p) for n in POINTERS] + [("seed", C.c_uint64)] + \
+               [(n, C.c_int32) for n in ("V", "ld", "width", "B", "beam", "K", "pad", "eos", "pos")] + [("inv_T", C.c_float)]
 
 
 class GenStats(C.Structure):
@@ -227,6 +247,8 @@ SYMBOLS = {
                                                     C.POINTER(C.c_int32), _I, C.POINTER(BeamParams), _VP, _VP, _VP, _I,
                                                     C.POINTER(BeamStats), _VP]),
     "ttx_beam_generate": (C.c_int, [_VP, _VP, _I, _I, C.POINTER(BeamSearchParams), _VP, C.POINTER(BeamSearchStats), _VP]),
+    "ttx_sbs_generate": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SbsParams), _VP, _VP, _VP, C.POINTER(SbsTrace),
+                                  C.POINTER(BeamSearchStats), _VP]),
     "ttx_nucleus_mask": (C.c_int, [_VP, _VP, _I, _I, C.c_float, _I, C.c_float, _VP, _VP]),
     "ttx_accepted_lengths": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, C.c_float, _I, _VP, _VP]),
     "ttx_ragged_topk": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
@@ -270,6 +292,7 @@ SYMBOLS = {
     "ttx_debug_bs_leaves": (C.c_int, [_VP, C.POINTER(DebugBsLeavesArgs), _VP]),
     "ttx_debug_beam_select": (C.c_int, [_VP, C.POINTER(DebugBeamSelectArgs), _VP]),
     "ttx_debug_beam_step": (C.c_int, [_VP, C.POINTER(DebugBeamStepArgs), _VP]),
+    "ttx_debug_sbs_step": (C.c_int, [_VP, C.POINTER(DebugSbsStepArgs), _VP]),
     "ttx_debug_tree_cache": (C.c_int, [_VP, C.POINTER(DebugTreeCacheArgs), _VP]),
     "ttx_debug_kvcopy": (C.c_int, [_VP, _VP, _I, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int64, _I, _I, _I, _I, _I, _VP]),
     "ttx_debug_kvcopy_split": (C.c_int, [_VP, _VP, _I, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int64, _I, _I, _I, _I, _I, _VP, _VP,

@@ -11,6 +11,7 @@
 #include "ttx_alternatives.hip.h"
 #include "ttx_attn_probs.hip.h"
 #include "ttx_sample.hip.h"
+#include "ttx_sbs.hip.h"
 #include "ttx_tokenizer.h"
 
 #include <algorithm>
@@ -2614,6 +2615,14 @@ static int launch_beam_step(ttx_session* s, hipStream_t st, const BeamStepArgs& 
   return TTX_OK;
 }
 
+static int launch_sbs_step(ttx_session* s, hipStream_t st, const SbsStepArgs& sa) {
+  const size_t lds = (size_t)sa.beam * sa.V * 4;
+  TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_sbs_step), lds, s->attr_sbs_step));
+  hipLaunchKernelGGL(k_sbs_step, dim3(sa.B), dim3(256), lds, st, sa);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
 static int beam_enqueue_iter(const BeamJob& j, bool first, int cur) {
   ttx_session* s = j.s;
   hipStream_t st = j.st;
@@ -3038,12 +3047,20 @@ struct BeamSearchJob {
   int n_eos = 0;             // hypotheses holding EOS after the previous iteration
   int phase = 0;             // 0 not started, 1 iteration in flight, 2 finishing
   int64_t* d_out = nullptr;
+  // stochastic beam search (ttx_sbs_generate): the same loop with k_sbs_step as the step kernel.  phi rides bs_logp / bs_logp_next;
+  // G is read from sbs_g or sbs_g_next by the parity of the iteration and written to the other.
+  bool sbs = false;
+  float inv_T = 1.f;
+  unsigned long long seed = 0;
+  const int64_t* row_keys = nullptr;
+  float* d_logp = nullptr; float* d_gumbel = nullptr;
+  ttx_sbs_trace trace{};
 };
 
 // Everything of the call behind the argument check: the reference's asserts and this library's limits, the workspaces, the
 // encoder and the <BOS> hypotheses.
 static int bsearch_start(BeamSearchJob& j, ttx_session* s, hipStream_t st, const int64_t* d_src, int B, int Ls,
-                         const ttx_beam_search_params* p, int64_t* d_out) {
+                         const ttx_beam_search_params* p, int64_t* d_out, bool sbs = false) {
   const ttx_config& c = s->m->cfg;
   const int K = p->beam_size, max_len = p->max_len, V = c.vocab_size;
   if (max_len <= 1) return fail(TTX_ERR_REFERENCE, "assert self.max_len > 1 (standard_decoding.py:79)");
@@ -3053,7 +3070,7 @@ static int bsearch_start(BeamSearchJob& j, ttx_session* s, hipStream_t st, const
   if (p->pad_token != c.pad_token) return fail(TTX_ERR_INVALID, "generator pad token differs from the model's");
   if (max_len + 2 > c.max_positions) return fail(TTX_ERR_INVALID, "max_len exceeds the positional table");
   j = BeamSearchJob{};
-  j.s = s; j.st = st; j.p = *p; j.B = B; j.Ls = Ls; j.K = K; j.d_out = d_out;
+  j.s = s; j.st = st; j.p = *p; j.B = B; j.Ls = Ls; j.K = K; j.d_out = d_out; j.sbs = sbs;
   s->ev_used = 0;                     // profiling sessions: the event pairs of this call start from the first one
   const int d = c.embedding_dim, Ld = c.num_decoder_layers;
   const int MC = B * K, ld = max_len + 2, Lc = max_len + 2;
@@ -3069,6 +3086,7 @@ static int bsearch_start(BeamSearchJob& j, ttx_session* s, hipStream_t st, const
   need(s->bs_logp_next, (size_t)MC * 4); need(s->bs_len, (size_t)MC * 4); need(s->bs_fin, (size_t)MC); need(s->bs_active, (size_t)MC);
   need(s->bs_logp, (size_t)MC * 4); need(s->bs_per_cand, (size_t)MC * 4); need(s->bs_parent, (size_t)MC * 4);
   need(s->bs_parent_draft, (size_t)MC * 4); need(s->bs_cnt, sizeof(BeamCounters)); need(s->beam_summary, 8 * 4);
+  if (sbs) { need(s->sbs_g, (size_t)MC * 4); need(s->sbs_g_next, (size_t)MC * 4); }
   need_step_workspaces(s, need, Mmax, (size_t)B * Ls);
   s->graphs_current();
   TTX_TRY(need.rc);
@@ -3076,6 +3094,7 @@ static int bsearch_start(BeamSearchJob& j, ttx_session* s, hipStream_t st, const
     return fail(TTX_ERR_NOMEM, "hipHostMalloc failed");
   std::memset(s->beam_host, 0, sizeof(BeamHost));
   HIP_TRY(hipHostGetDevicePointer((void**)&j.dev_host, (void*)s->beam_host, 0));
+  if (sbs) HIP_TRY(hipMemsetAsync(s->sbs_g.p, 0, (size_t)MC * 4, st));       // G = 0 for the <BOS> candidates
   // self.model(src, y) of the first step = encoder + the decoder on <BOS>; the reference then re-encodes the source once per
   // beam (:120-124): identical rows, so the beams of a source share its memory row here
   TTX_TRY(encode_sources(s, st, d_src, 0, B, Ls, s->src_valid.as<uint8_t>(), s->memkv.as<float>()));
@@ -3100,6 +3119,27 @@ static int bsearch_launch_iter(BeamSearchJob& j) {
   TTX_TRY(enqueue_bs_list(s, st, j.n_cand, 1, 0));
   const int variant = variant_for_rows(s, (long long)std::max(1, j.n_cand - j.n_eos), true);
   TTX_TRY(run_step(s, st, tree_step_ctx(s, j.MC, j.Ls, 1, 0, j.Lc, j.ld, max_len, cur ^ 1, variant), key_capacity(j.width, max_len)));
+  if (j.sbs) {
+    SbsStepArgs sa{};
+    float* const gbuf[2] = {s->sbs_g.as<float>(), s->sbs_g_next.as<float>()};
+    sa.logits = s->logits.as<float>(); sa.V = s->m->cfg.vocab_size; sa.slot_of = s->t_slot_of.as<int>(); sa.finished = s->bs_fin.as<uint8_t>();
+    sa.phi = s->bs_logp.as<float>(); sa.g = gbuf[j.launched & 1]; sa.gen = s->gen.as<int>(); sa.ld = j.ld; sa.width = j.width;
+    sa.B = j.B; sa.beam = j.beam; sa.K = j.K; sa.pad = j.p.pad_token; sa.eos = j.p.eos_token;
+    sa.row_keys = j.row_keys; sa.seed = j.seed; sa.pos = j.width; sa.inv_T = j.inv_T;
+    sa.new_cand = s->bs_cand_next.as<int64_t>(); sa.new_phi = s->bs_logp_next.as<float>(); sa.new_g = gbuf[(j.launched & 1) ^ 1];
+    sa.parent = s->bs_parent.as<int>(); sa.new_len = s->bs_len_next.as<int>(); sa.new_finished = s->bs_fin_next.as<uint8_t>();
+    sa.parent_draft = s->bs_parent_draft.as<int>(); sa.summary = s->beam_summary.as<int>();
+    if (j.trace.d_parent) {
+      const size_t at = (size_t)j.launched * j.B * j.K;
+      sa.tr_parent = j.trace.d_parent + at; sa.tr_token = j.trace.d_token + at; sa.tr_phi = j.trace.d_phi + at; sa.tr_g = j.trace.d_g + at;
+    }
+    TTX_TRY(launch_sbs_step(s, st, sa));
+    hipLaunchKernelGGL(k_bs_publish, dim3(1), dim3(64), 0, st, s->beam_summary.as<int>(), j.dev_host, s->bs_cnt.as<BeamCounters>());
+    HIP_TRY(hipGetLastError());
+    ++j.launched;
+    j.cur = cur ^ 1;
+    return TTX_OK;
+  }
   BeamStepArgs sa{};
   sa.logits = s->logits.as<float>(); sa.V = s->m->cfg.vocab_size; sa.slot_of = s->t_slot_of.as<int>(); sa.finished = s->bs_fin.as<uint8_t>();
   sa.score = s->bs_logp.as<float>(); sa.gen = s->gen.as<int>(); sa.ld = j.ld; sa.width = j.width;
@@ -3122,14 +3162,21 @@ static bool bsearch_after_iter(BeamSearchJob& j) {
   j.width += 1;
   j.n_cand = j.B * j.K; j.beam = j.K;
   j.n_eos = ((volatile BeamHost*)j.s->beam_host)->summary[0];
-  if (j.n_eos == j.B * j.K && !first) return false;        // :166 (the check sits inside the loop, after the first step)
+  if (j.n_eos == j.B * j.K && (!first || j.sbs)) return false;   // :166 (the check sits inside the loop, after the first step; the
+                                                                 // stochastic rule stops as soon as every candidate is finished)
   return j.launched < j.p.max_len - 1;
 }
 
 static int bsearch_finish_enqueue(BeamSearchJob& j) {
   ttx_session* s = j.s;
-  HIP_TRY(hipMemcpy2DAsync(j.d_out, (size_t)j.p.max_len * 8, s->bs_cand_next.p, (size_t)j.ld * 8, (size_t)j.width * 8,
+  // the rows are PAD beyond `width` up to their stride ld = max_len + 2: the stochastic form hands out all max_len columns
+  HIP_TRY(hipMemcpy2DAsync(j.d_out, (size_t)j.p.max_len * 8, s->bs_cand_next.p, (size_t)j.ld * 8, (size_t)(j.sbs ? j.p.max_len : j.width) * 8,
                            (size_t)j.B * j.K, hipMemcpyDeviceToDevice, j.st));
+  if (j.sbs) {
+    const Buf& g = (j.launched & 1) ? s->sbs_g_next : s->sbs_g;
+    if (j.d_logp) HIP_TRY(hipMemcpyAsync(j.d_logp, s->bs_logp_next.p, (size_t)j.B * j.K * 4, hipMemcpyDeviceToDevice, j.st));
+    if (j.d_gumbel) HIP_TRY(hipMemcpyAsync(j.d_gumbel, g.p, (size_t)j.B * j.K * 4, hipMemcpyDeviceToDevice, j.st));
+  }
   TTX_TRY(enqueue_readback(s, j.st, s->bs_cnt.p, sizeof(BeamCounters)));
   j.phase = 2;
   return TTX_OK;
@@ -3146,6 +3193,45 @@ extern "C" int ttx_beam_generate(ttx_session* s, const int64_t* d_src, int B, in
   const auto turn = [&](int) -> int {
     if (j.phase == 1) {
       if (((volatile BeamHost*)s->beam_host)->steps_done < j.launched) return TURN_WAITING;   // the iteration in flight has not published yet
+      TTX_TRY(bsearch_after_iter(j) ? bsearch_launch_iter(j) : bsearch_finish_enqueue(j));
+      return TURN_PROGRESSED;
+    }
+    if (hipEventQuery(s->ev_done) != hipSuccess) return TURN_IDLE;
+    const BeamCounters* cn = reinterpret_cast<const BeamCounters*>(s->host_state);
+    stats->model_calls = cn->model_calls; stats->running_rows = cn->running_cands; stats->out_width = j.width;
+    return TURN_FINISHED;
+  };
+  return drive_sessions(&s, 1, false, stream, start, turn);
+}
+
+// Stochastic beam search: the standard beam loop above with k_sbs_step (csrc/ttx_sbs.hip.h) where it launches k_beam_step.
+extern "C" int ttx_sbs_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sbs_params* p,
+                                int64_t* d_out, float* d_logp, float* d_gumbel, const ttx_sbs_trace* trace, ttx_beam_search_stats* stats,
+                                void* stream) {
+  if (!s || !d_src || !p || !d_out || !d_logp || !d_gumbel || !stats || B <= 0 || Ls <= 1)
+    return fail(TTX_ERR_INVALID, "bad argument to ttx_sbs_generate");
+  const int V = s->m->cfg.vocab_size;
+  if (p->max_len <= 1) return fail(TTX_ERR_INVALID, "ttx_sbs_generate: max_len must exceed 1");
+  if (p->beam_size < 1 || p->beam_size > SBS_MAX_BEAM) return fail(TTX_ERR_INVALID, "ttx_sbs_generate: beam_size must lie in [1, 32]");
+  if (V > SBS_MAX_V) return fail(TTX_ERR_INVALID, "ttx_sbs_generate: vocab_size above 1024");
+  if (p->beam_size > V) return fail(TTX_ERR_INVALID, "ttx_sbs_generate: beam_size larger than the vocabulary");
+  if (!(p->temperature > 0.0f) || !std::isfinite(p->temperature)) return fail(TTX_ERR_INVALID, "ttx_sbs_generate: temperature must be finite and > 0");
+  const float inv_T = 1.0f / p->temperature;
+  if (!(inv_T > 0.0f) || !std::isfinite(inv_T)) return fail(TTX_ERR_INVALID, "ttx_sbs_generate: 1 / temperature is not a positive finite fp32");
+  if (trace && (!trace->d_parent || !trace->d_token || !trace->d_phi || !trace->d_g))
+    return fail(TTX_ERR_INVALID, "ttx_sbs_generate: a trace needs all four arrays");
+  ttx_beam_search_params bp{};
+  bp.max_len = p->max_len; bp.beam_size = p->beam_size; bp.pad_token = p->pad_token; bp.bos_token = p->bos_token; bp.eos_token = p->eos_token;
+  BeamSearchJob j;
+  const auto start = [&](int) -> int {
+    TTX_TRY(bsearch_start(j, s, s->own_stream, d_src, B, Ls, &bp, d_out, true));
+    j.inv_T = inv_T; j.seed = p->seed; j.row_keys = d_row_keys; j.d_logp = d_logp; j.d_gumbel = d_gumbel;
+    if (trace) j.trace = *trace;
+    return bsearch_launch_iter(j);
+  };
+  const auto turn = [&](int) -> int {
+    if (j.phase == 1) {
+      if (((volatile BeamHost*)s->beam_host)->steps_done < j.launched) return TURN_WAITING;
       TTX_TRY(bsearch_after_iter(j) ? bsearch_launch_iter(j) : bsearch_finish_enqueue(j));
       return TURN_PROGRESSED;
     }
@@ -4047,6 +4133,32 @@ extern "C" int ttx_debug_beam_step(ttx_session* s, const ttx_debug_beam_step_arg
   sa.new_cand = a->d_new_cand; sa.new_score = a->d_new_score; sa.parent = a->d_parent; sa.new_len = a->d_new_len;
   sa.new_finished = a->d_new_finished; sa.parent_draft = a->d_parent_draft; sa.summary = a->d_summary;
   return dbg_launched(launch_beam_step(s, st, sa), st);
+}
+
+extern "C" int ttx_debug_sbs_step(ttx_session* s, const ttx_debug_sbs_step_args* a, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !a) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_sbs_step");
+  if (!a->d_logits || !a->d_slot_of || !a->d_finished || !a->d_phi || !a->d_g || !a->d_gen || !a->d_new_cand || !a->d_new_phi || !a->d_new_g ||
+      !a->d_parent || !a->d_new_len || !a->d_new_finished || !a->d_parent_draft || !a->d_summary)
+    return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step: a required array is null");
+  if (!a->d_tr_parent != !a->d_tr_token || !a->d_tr_parent != !a->d_tr_phi || !a->d_tr_parent != !a->d_tr_g)
+    return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step: the four trace arrays come together");
+  if (a->B < 1 || a->beam < 1 || a->beam > SBS_MAX_BEAM || a->K < 1 || a->K > SBS_MAX_BEAM || a->V < 1 || a->V > SBS_MAX_V)
+    return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step: B >= 1, beam and K in [1, 32] and V in [1, 1024]");
+  if ((size_t)a->K > (size_t)a->beam * a->V) return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step: K exceeds the beam * V children");
+  if ((size_t)a->beam * a->V * 4 > 150 * 1024) return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step: beam x vocabulary beyond the kernel's LDS image");
+  if (a->width < 1 || a->width >= a->ld) return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step: width must lie in [1, ld)");
+  if (a->pos < 1) return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step: pos starts at 1");
+  if (!(a->inv_T > 0.0f) || !std::isfinite(a->inv_T)) return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step: inv_T must be finite and > 0");
+  HIP_TRY(hipSetDevice(s->m->device));
+  SbsStepArgs sa{};
+  sa.logits = a->d_logits; sa.V = a->V; sa.slot_of = a->d_slot_of; sa.finished = a->d_finished; sa.phi = a->d_phi; sa.g = a->d_g;
+  sa.gen = a->d_gen; sa.ld = a->ld; sa.width = a->width; sa.B = a->B; sa.beam = a->beam; sa.K = a->K; sa.pad = a->pad; sa.eos = a->eos;
+  sa.row_keys = a->d_key; sa.seed = a->seed; sa.pos = a->pos; sa.inv_T = a->inv_T;
+  sa.new_cand = a->d_new_cand; sa.new_phi = a->d_new_phi; sa.new_g = a->d_new_g; sa.parent = a->d_parent; sa.new_len = a->d_new_len;
+  sa.new_finished = a->d_new_finished; sa.parent_draft = a->d_parent_draft; sa.summary = a->d_summary;
+  sa.tr_parent = a->d_tr_parent; sa.tr_token = a->d_tr_token; sa.tr_phi = a->d_tr_phi; sa.tr_g = a->d_tr_g;
+  return dbg_launched(launch_sbs_step(s, st, sa), st);
 }
 
 extern "C" int ttx_debug_tree_cache(ttx_session* s, const ttx_debug_tree_cache_args* a, void* stream) {

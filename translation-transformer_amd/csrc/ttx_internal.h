@@ -144,7 +144,9 @@ struct GraphCache {
   X(smp_key) X(smp_sample) X(smp_done) X(smp_src_of) X(smp_prm) X(smp_drafts)                                                     \
   /* forced prefixes of a prompted sampling call: the table int32 [sources][max_len] and the sources' lengths; per decoder row */ \
   /* (slot) its prefix length, its row of the table (pool; single-session loops use smp_src_of) and its source draft 0 [D] */     \
-  X(pfx_tok) X(pfx_len_src) X(pfx_len) X(pfx_src) X(pfx_draft0)
+  X(pfx_tok) X(pfx_len_src) X(pfx_len) X(pfx_src) X(pfx_draft0)                                                                  \
+  /* stochastic beam search (ttx_sbs_generate): the perturbed log-probabilities G of the candidates, read and written in turn */  \
+  X(sbs_g) X(sbs_g_next)
 #define TTX_DECLARE_BUF(name) Buf name;
 #define TTX_REGISTER_BUF(name) all.push_back(&name);
 
@@ -179,7 +181,7 @@ struct ttx_session {
   ttx::DecState* host_state = nullptr;  // pinned copy target
   // function attributes (dynamic LDS limits) are per device: set once per session, outside graph capture
   bool attr_attn2[2][8] = {};      // [head dimension 32 / 64][mode]
-  bool attr_select = false, attr_step = false, attr_topk = false, attr_pool_select = false;
+  bool attr_select = false, attr_step = false, attr_topk = false, attr_pool_select = false, attr_sbs_step = false;
   bool attr_attn_probs[8] = {};    // k_attn_probs: [head dimension 32 / 64][16-byte output stores][16-byte key loads]
   // GEMM policy (all choices are between bit-identical evaluations, see GemmVariant)
   int qkv_small_rows = 800;        // a verify step with fewer live rows than this runs under GV_SMALL (TTX_QKV_SMALL_ROWS)

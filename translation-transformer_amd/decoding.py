@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -648,6 +649,100 @@ class TranslationInferenceBeamSearch(_ScoresHypotheses):
         self.b_sz += int(st.running_rows)
         self.given_tokens += int((src != m.src_pad_token_i).sum())
         return self._scored(src, out[:, :, :int(st.out_width)].contiguous(), return_scores)
+
+
+class SbsTrace(NamedTuple):
+    """Every level of a stochastic beam search, in selection order: tensors [levels, B, K] of the parent's rank in the previous
+    level, the token, the child's log-probability ``phi`` and its perturbed log-probability ``g``."""
+    parent: torch.Tensor
+    token: torch.Tensor
+    phi: torch.Tensor
+    g: torch.Tensor
+
+
+class SbsDetails(NamedTuple):
+    """What stochastic beam search knows about its rows: ``logp`` Float[B, K] the model's log-probability of each hypothesis at
+    the generator's temperature, ``gumbel`` Float[B, K] its perturbed log-probability (the sampling order: non-increasing, 0 for
+    the first row), ``finished`` Bool[B, K], and the ``trace`` when one was asked for (always in sampling order)."""
+    logp: torch.Tensor
+    gumbel: torch.Tensor
+    finished: torch.Tensor
+    trace: SbsTrace | None = None
+
+
+class TranslationInferenceStochasticBeamSearch(_ScoresHypotheses):
+    """Stochastic beam search (Kool, van Hoof & Welling, ICML 2019): ``beam_size`` = K pairwise distinct hypotheses per source
+    that are an exact sample without replacement from the model's sequence distribution under ``temperature``.  The whole loop
+    runs in ttx_sbs_generate: the standard beam loop with k_sbs_step, which perturbs the children's log-probabilities with
+    Gumbel noise keyed by (seed, the source's row key, the parent's rank, token, position) and keeps the K largest conditional
+    maxima (include/ttx.h states the rule).  The rows of a source depend on the source, its key, the seed, the temperature and
+    K only, and the call with K returns the first K rows of the call with a larger K.  A sampled PAD ends a row as EOS does.
+    No top-k / top-p filter, no forced prefix, no ``generate_many``.  ``scoring.sbs_weights`` turns ``logp`` and ``gumbel`` of a
+    K + 1 call into importance weights."""
+
+    def __init__(self, model, beam_size: int, max_len: int, pad_token: int, bos_token: int, eos_token: int,
+                 temperature: float = 1.0, seed: int = 0) -> None:
+        self.model = _need_native(model)
+        self.beam_size, self.max_len = int(beam_size), int(max_len)
+        self.pad_token, self.bos_token, self.eos_token = pad_token, bos_token, eos_token
+        self.temperature, self.seed = float(temperature), int(seed)
+        self.model_calls_num = 0
+        self.given_tokens = 0
+        self.b_sz = 0
+
+    def __str__(self):
+        return (f"Stochastic beam search (beam_size={self.beam_size}, temperature={self.temperature}, seed={self.seed}, "
+                f"max_len={self.max_len})")
+
+    def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, return_details: bool = False,
+                 order: str = "sample", trace: bool = False):
+        """Long[B, K, max_len]: BOS, the tokens up to and including the first EOS or PAD, PAD after.  ``row_keys``: one integer
+        per source (default 0..B-1), the source's identity for the random stream.  ``order="sample"``: rows in sampling order
+        (``gumbel`` descending); ``order="logp"``: re-sorted by ``logp``, best first (equal values keep their sampling order).
+        ``return_scores=True`` appends the ``HypothesisScores`` of the returned rows and ``return_details=True`` an
+        ``SbsDetails`` (with ``trace=True`` including the ``SbsTrace``), in that order, as a tuple."""
+        if order not in ("sample", "logp"):
+            raise ValueError(f"order must be 'sample' or 'logp', got {order!r}")
+        m, K = self.model, self.beam_size
+        src = src.to(m.device, torch.int64).contiguous()
+        m.check_tokens(src)
+        B, Ls = src.shape
+        keys = None
+        if row_keys is not None:
+            keys = torch.as_tensor(row_keys, dtype=torch.int64).to(m.device).contiguous()
+            if keys.shape != (B,):
+                raise ValueError(f"row_keys must hold one key per source ({B}), got shape {tuple(keys.shape)}")
+        p = N.SbsParams(self.max_len, K, self.temperature, self.pad_token, self.bos_token, self.eos_token,
+                        self.seed & 0xFFFFFFFFFFFFFFFF)
+        Kc, Lc = max(K, 1), max(self.max_len, 2)
+        out = torch.empty((B, Kc, Lc), dtype=torch.int64, device=m.device)
+        logp = torch.empty((B, Kc), dtype=torch.float32, device=m.device)
+        gumbel = torch.empty((B, Kc), dtype=torch.float32, device=m.device)
+        tr = tr_arg = None
+        if trace:
+            shape = (Lc - 1, B, Kc)
+            tr = SbsTrace(torch.zeros(shape, dtype=torch.int32, device=m.device), torch.zeros(shape, dtype=torch.int32, device=m.device),
+                          torch.zeros(shape, dtype=torch.float32, device=m.device), torch.zeros(shape, dtype=torch.float32, device=m.device))
+            tr_arg = C.byref(N.SbsTrace(*(t.data_ptr() for t in tr)))
+        st = N.BeamSearchStats()
+        N.check(m._lib.ttx_sbs_generate(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(), C.byref(p),
+                                        out.data_ptr(), logp.data_ptr(), gumbel.data_ptr(), tr_arg, C.byref(st), m._stream()))
+        self.model_calls_num += int(st.model_calls)
+        self.b_sz += int(st.running_rows)
+        self.given_tokens += int((src != m.src_pad_token_i).sum())
+        if order == "logp":
+            idx = torch.argsort(logp, dim=1, descending=True, stable=True)
+            out = torch.gather(out, 1, idx[:, :, None].expand_as(out))
+            logp, gumbel = torch.gather(logp, 1, idx), torch.gather(gumbel, 1, idx)
+        res = [out]
+        if return_scores:
+            res.append(self.score(src, out))
+        if return_details:
+            ended = ((out[:, :, 1:] == self.eos_token) | (out[:, :, 1:] == self.pad_token)).any(-1) | torch.isinf(gumbel)
+            if tr is not None:
+                tr = SbsTrace(*(t[:int(st.model_calls)] for t in tr))
+            res.append(SbsDetails(logp, gumbel, ended, tr))
+        return res[0] if len(res) == 1 else tuple(res)
 
 
 class TranslationInferenceBeamSearchSpeculative(_ScoresHypotheses):

@@ -209,9 +209,9 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
                                      embedding_dim, num_heads, feedforward_dim, share_embeddings,
                                      self.src_pad_token_i, self.tgt_pad_token_i, activation)
         if generation not in ("greedy", "beam_search", "greedy_speculative", "beam_search_speculative", "sampling",
-                              "sampling_speculative"):
+                              "sampling_speculative", "stochastic_beam_search"):
             options = ", ".join(["beam_search", "greedy", "greedy_speculative", "beam_search_speculative", "sampling",
-                                 "sampling_speculative"])
+                                 "sampling_speculative", "stochastic_beam_search"])
             raise ValueError(f'Unknown generation option {generation}. Options are {options}.')
         if generation in ("greedy_speculative", "sampling_speculative"):
             assert draft_len > 0, "Number of speculative tokens must be a positive integer."
@@ -292,6 +292,9 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         if h.generation == "greedy_speculative":
             return D.TranslationInferenceGreedySpeculative(m, max_len=h.max_len, draft_len=h.draft_len, n_drafts=h.n_drafts,
                                                            replace_token=self.tgt_tokenizer.encoder_dict["c"], **common)
+        if h.generation == "stochastic_beam_search":  # beam_size distinct draws per reaction (sampling without replacement)
+            return D.TranslationInferenceStochasticBeamSearch(m, beam_size=h.beam_size, max_len=h.max_len,
+                                                              temperature=h.sampling_temperature, seed=h.sampling_seed, **common)
         if h.generation == "sampling":               # beam_size samples per reaction, as the reference uses it for n_best
             return D.TranslationInferenceSampling(m, max_len=h.max_len, temperature=h.sampling_temperature, top_k=h.sampling_top_k,
                                                   top_p=h.sampling_top_p, num_samples=max(1, h.beam_size), seed=h.sampling_seed,
@@ -324,6 +327,10 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             B = int(batch["src_tokens"].shape[0])
             pred = self.generator.generate(batch["src_tokens"], row_keys=torch.arange(self._predict_rows, self._predict_rows + B),
                                            prefix=prefix)
+            self._predict_rows += B
+        elif pred is None and self.hparams.generation == "stochastic_beam_search":   # keyed like the samplers: the running index
+            B = int(batch["src_tokens"].shape[0])
+            pred = self.generator.generate(batch["src_tokens"], row_keys=torch.arange(self._predict_rows, self._predict_rows + B))
             self._predict_rows += B
         elif pred is None:
             pred = self.generator.generate(batch["src_tokens"])

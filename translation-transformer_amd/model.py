@@ -508,6 +508,20 @@ class NativeTransformer:
         self._debug_beam(N.DebugBeamStepArgs, self._lib.ttx_debug_beam_step,
                          dict(V=V, ld=ld, width=width, B=B, beam=beam, K=K, pad=pad, eos=eos), arrays)
 
+    def debug_sbs_step(self, *, V: int, ld: int, width: int, B: int, beam: int, K: int, pad: int, eos: int, pos: int, seed: int,
+                       inv_T: float, **arrays) -> None:
+        """One k_sbs_step launch (ttx_debug_sbs_step): the operands of debug_beam_step with ``phi``, ``g``, ``key`` (absent: keys
+        0..B-1), ``new_phi``, ``new_g`` and optionally the four ``tr_*`` trace arrays."""
+        a = N.DebugSbsStepArgs()
+        for name in a.POINTERS:
+            t = arrays.pop(name[2:], None)
+            setattr(a, name, None if t is None else t.data_ptr())
+        assert not arrays, f"unknown operands {sorted(arrays)}"
+        for name, v in dict(V=V, ld=ld, width=width, B=B, beam=beam, K=K, pad=pad, eos=eos, pos=pos).items():
+            setattr(a, name, int(v))
+        a.seed, a.inv_T = int(seed) & 0xFFFFFFFFFFFFFFFF, float(inv_T)
+        N.check(self._lib.ttx_debug_sbs_step(self._session, C.byref(a), self._stream()))
+
     def debug_tree_cache(self, *, max_cand: int, layers: int, prev_n: int, prev_d: int, d: int, cache_layer_stride: int,
                          cache_seq_stride: int, qkv_layer_stride: int, **arrays) -> None:
         """One k_tree_cache launch (ttx_debug_tree_cache); ``slot_parent`` / ``slot_self`` absent: two buffers."""
