@@ -385,6 +385,44 @@ int ttx_sample_speculative_generate_pool_prefix(ttx_session** sessions, int n_se
                                                 const ttx_sample_spec_params* p, const int64_t* d_prefix, int ld_prefix,
                                                 const int32_t* h_prefix_len, int64_t* d_out, ttx_gen_stats* stats, void* stream);
 
+/* Proposal drafts for the two speculative sampling calls: drafts the caller brings (a cheap model's output, an earlier prediction,
+ * the row's own greedy answer), OFFERED and never forced.  Each *_proposal call takes the arguments of its *_prefix call plus
+ * d_proposal (DEVICE, int64 [sources][ld_proposal], without BOS, may end in EOS), ld_proposal and h_proposal_len (HOST, int32
+ * [sources]): source b carries a proposal of len = h_proposal_len[b] tokens, 0 <= len <= max_len - 1, shared by its num_samples
+ * rows.  k_sample_step and k_sample_accept are the unproposed call's and see no table: a draft token is accepted iff it equals the
+ * token of its position, so a proposal forces no token, whatever it holds: the rows are the plain sampler's under the contract of
+ * ttx_sample_speculative_generate, and only step counts change.  (That contract's one caveat holds between a proposed and an
+ * unproposed call as it holds between either and the plain sampler: the drafts decide in which row of which pass a position's logits
+ * are formed, and a uniform within fp32 rounding of a CDF boundary can then fall on either side.)  A call whose
+ * proposal lengths are all 0 (or whose h_proposal_len is NULL) IS the *_prefix call with the same remaining arguments, launch for
+ * launch: no new graph site, no upload.  A call is either prompted or proposed: non-empty prefixes together with non-empty
+ * proposals are refused (TTX_ERR_INVALID, nothing launched), as is everything prefix lengths are refused for.
+ *
+ * The rule.  Before every verify step k_proposal_drafts rewrites draft 0 of every active row.  For a row with tokens g[0 .. f]
+ * (g[0] = BOS, f the slot's front) and proposal q[0 .. len - 1] (q[i] is proposed for column i + 1; q[-1] := BOS):
+ *   for each shift d in [-32, 31] (one lane of a wave per shift, d = lane - 32)
+ *     c(d) = the number of a in {0 .. CTX - 1} with  f - a >= 0,  -1 <= f-1-a+d < len  and  q[f-1-a+d] == g[f-a];
+ *     d is eligible iff c(d) >= 1 and 0 <= f + d < len;
+ *   the eligible d with the largest c is chosen; ties go to the smaller |d|, then to d >= 0.  (A proposal equal to the row so far
+ *   always selects d = 0.)
+ *   Draft 0 token j (column f + 1 + j), j = 0 .. draft_len - 1, is q[f + d + j] while that index is < len, and token j of the row's
+ *   own source draft 0 past the end of the proposal, as k_prefix_drafts does behind a prefix.  EOS and PAD are written as
+ *   replace_token, so drafts still hold neither and EOS arrives as the bonus token.
+ *   If no d is eligible, or len = 0, draft 0 is the source draft 0.  Drafts 1 .. n_drafts - 1 are never touched.
+ * The rule is stateless and idempotent: it reads the row, the proposal and the source draft kept at set-up, and nothing it wrote.
+ * CTX = 2; the window of 64 shifts is the wave width.  Neither forces a token.  (TTX_PROPOSAL_CTX = 2, 4 or 8, read per call,
+ * overrides CTX for measurements; any other value is refused.)  With a proposal equal to the row's final tokens, L emitted tokens
+ * (EOS included) take ceil(L / (draft_len + 1)) verify steps. */
+int ttx_sample_speculative_generate_proposal(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                             const ttx_sample_spec_params* p, const int64_t* d_prefix, int ld_prefix,
+                                             const int32_t* h_prefix_len, const int64_t* d_proposal, int ld_proposal,
+                                             const int32_t* h_proposal_len, int64_t* d_out, ttx_gen_stats* stats, void* stream);
+int ttx_sample_speculative_generate_pool_proposal(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total, int Ls_all,
+                                                  const int32_t* h_len, const int64_t* d_row_keys, int capacity,
+                                                  const ttx_sample_spec_params* p, const int64_t* d_prefix, int ld_prefix,
+                                                  const int32_t* h_prefix_len, const int64_t* d_proposal, int ld_proposal,
+                                                  const int32_t* h_proposal_len, int64_t* d_out, ttx_gen_stats* stats, void* stream);
+
 /* Beam-speculative bookkeeping kernels.
  * ttx_nucleus_mask: mask_with_num_logits_according_nucleus (src/decoding/speculative_decoding.py:871-904): per row of
  *   d_logits [rows,V] keep the best logit and further ones, best first, while the softmax mass ranked above is
@@ -814,6 +852,16 @@ int ttx_debug_sample_step_prefix(ttx_session* s, const float* d_logits, int V, c
                                  const int32_t* d_act_idx, const int32_t* d_front, int B, int N, int D, int n_active, int32_t* d_pred,
                                  const int32_t* d_m, const ttx_sample_params* p, const int32_t* d_row_map, int n_rows,
                                  const ttx_debug_prefix* pfx, void* stream);
+
+/* ttx_debug_proposal_drafts (tests/test_gpu_proposal_kernel.py): ONE launch of k_proposal_drafts with production's grid (one wave
+ * per slot of B) on the caller's arrays, under the rule of "Proposal drafts" above with CTX = ctx.  d_gen int32 [B, gen_ld] the
+ * rows' tokens (columns 0 .. d_front[b] are read); `proposal` the table as ttx_debug_prefix describes it (d_len, d_src by slot);
+ * d_drafts int32 [B, N, D]; d_draft0 int32 [B, D]; only draft 0 of the active rows is written.  Synchronises the stream.  Refused:
+ * null pointers, B, N, D or gen_ld < 1, n_active outside [0, B], repeated or out-of-range d_act_idx entries, an active front
+ * outside [0, gen_ld), ctx other than 2, 4, 8, and a table outside its bounds. */
+int ttx_debug_proposal_drafts(ttx_session* s, const int32_t* d_act_idx, const int32_t* d_front, const int32_t* d_gen, int gen_ld, int B,
+                              int N, int D, int n_active, int32_t* d_drafts, const int32_t* d_draft0, const ttx_debug_prefix* proposal,
+                              int ctx, int bos_token, int eos_token, int pad_token, int replace_token, void* stream);
 
 /* ttx_debug_sample_accept_pool (tests/test_gpu_sample_accept_pool_kernel.py): the accept step of
  * ttx_sample_speculative_generate_pool on ttx_debug_accept's argument block and `state`: greedy 0, row_rule and pool 1; d_row_of

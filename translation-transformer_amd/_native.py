@@ -18,6 +18,7 @@ LIB_PATH = PKG_DIR / "libttx_hip.so"
 UNITS = [CSRC / "ttx_api.hip", CSRC / "ttx_gemm.hip", CSRC / "ttx_attn.hip"]
 HEADERS = [CSRC / "ttx_internal.h", CSRC / "ttx_common.hip.h", CSRC / "ttx_loop_kernels.hip.h", CSRC / "ttx_metrics.hip.h",
            CSRC / "ttx_score.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_sample.hip.h", CSRC / "ttx_sbs.hip.h",
+           CSRC / "ttx_proposal.hip.h",
            CSRC / "ttx_select.h", CSRC / "ttx_tokenizer.h", CSRC / "ttx_drive.h", CSRC / "ttx_admit.h", INCLUDE / "ttx.h"]
 SOURCES = UNITS + HEADERS
 OBJ_DIR = CSRC / "build"
@@ -229,6 +230,12 @@ SYMBOLS = {
     "ttx_sample_speculative_generate_pool_prefix": (C.c_int, [C.POINTER(_VP), _I, _VP, _I, _I, C.POINTER(C.c_int32), _VP, _I,
                                                              C.POINTER(SampleSpecParams), _VP, _I, C.POINTER(C.c_int32), _VP,
                                                              C.POINTER(GenStats), _VP]),
+    "ttx_sample_speculative_generate_proposal": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SampleSpecParams), _VP, _I,
+                                                          C.POINTER(C.c_int32), _VP, _I, C.POINTER(C.c_int32), _VP,
+                                                          C.POINTER(GenStats), _VP]),
+    "ttx_sample_speculative_generate_pool_proposal": (C.c_int, [C.POINTER(_VP), _I, _VP, _I, _I, C.POINTER(C.c_int32), _VP, _I,
+                                                               C.POINTER(SampleSpecParams), _VP, _I, C.POINTER(C.c_int32), _VP, _I,
+                                                               C.POINTER(C.c_int32), _VP, C.POINTER(GenStats), _VP]),
     "ttx_greedy_speculative_generate_many": (C.c_int, [C.POINTER(_VP), _I, _I, C.POINTER(_VP), C.POINTER(C.c_int),
                                                       C.POINTER(C.c_int), C.POINTER(GenParams), C.POINTER(_VP),
                                                       C.POINTER(GenStats), _VP]),
@@ -277,6 +284,8 @@ SYMBOLS = {
     "ttx_debug_sample_step_select": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, C.POINTER(SampleParams),
                                               _VP, _I, _VP]),
     "ttx_debug_prefix_drafts": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, C.POINTER(DebugPrefix), _I, _I, _I, _VP]),
+    "ttx_debug_proposal_drafts": (C.c_int, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, C.POINTER(DebugPrefix), _I, _I, _I, _I,
+                                            _I, _VP]),
     "ttx_debug_sample_prefix": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I, C.POINTER(SampleParams),
                                          C.POINTER(DebugPrefix), _VP]),
     "ttx_debug_sample_step_prefix": (C.c_int, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, C.POINTER(SampleParams),

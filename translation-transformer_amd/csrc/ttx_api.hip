@@ -12,6 +12,7 @@
 #include "ttx_attn_probs.hip.h"
 #include "ttx_sample.hip.h"
 #include "ttx_sbs.hip.h"
+#include "ttx_proposal.hip.h"
 #include "ttx_tokenizer.h"
 
 #include <algorithm>
@@ -1042,7 +1043,9 @@ struct StepCtx {
   bool want_sample = false;        // sampling loop: k_sample on `sample` where k_argmax would run
   SampleArgs sample{};
   bool want_sample_step = false;   // speculative sampling loop: k_sample_step on `sample`'s key, sample and prm
-  const int* pfx_draft0 = nullptr; // prompted speculative sampling (sample.pfx set): the rows' source draft 0, [B, D]
+  const int* pfx_draft0 = nullptr; // prompted or proposed speculative sampling (sample.pfx or prop set): the rows' source draft 0, [B, D]
+  PrefixTab prop{};                // proposed speculative sampling: the proposals, offered as draft 0 and never forced (sample.pfx unset)
+  int prop_ctx = PROPOSAL_CTX;     // context tokens k_proposal_drafts compares per shift
   int variant = GV_BIG;           // GemmVariant of this step's launches (bit-identical results; chosen from the live row count)
   // two-phase verify step of the slot pool; unset (null): the session's state, active list, step QKV buffer and argmax buffer
   DecState* st_ov = nullptr;       // live rows of this pass
@@ -1085,8 +1088,26 @@ static int launch_prefix_drafts_args(hipStream_t st, const PrefixDraftsArgs& a, 
   return TTX_OK;
 }
 
-// The head of every verify step of a prompted speculative sampling loop; nothing for any other loop.
+// k_proposal_drafts with k_prefix_drafts' launch shape.
+static int launch_proposal_drafts_args(hipStream_t st, const ProposalDraftsArgs& a, int B) {
+  hipLaunchKernelGGL(k_proposal_drafts, dim3(cdiv(B, 4)), dim3(256), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+// The table a prompted or a proposed call carries through pool admission (a call is one or the other), tok null for neither.
+static const PrefixTab& step_tab(const StepCtx& k) { return k.sample.pfx.tok ? k.sample.pfx : k.prop; }
+
+// The head of every verify step of a prompted or a proposed speculative sampling loop; nothing for any other loop.
 static int launch_prefix_drafts(ttx_session* s, hipStream_t st, const StepCtx& k) {
+  if (k.prop.tok && k.want_sample_step) {
+    ProposalDraftsArgs a{};
+    a.st = s->state.as<DecState>(); a.act_idx = s->act_idx.as<int>(); a.front = s->front.as<int>();
+    a.gen = s->gen.as<int>(); a.gen_ld = k.gen_ld;
+    a.drafts = s->drafts.as<int>(); a.N = k.N; a.D = k.D; a.draft0 = k.pfx_draft0; a.tab = k.prop;
+    a.bos = k.p.bos_token; a.eos = k.p.eos_token; a.pad = k.p.pad_token; a.repl = k.p.replace_token; a.ctx = k.prop_ctx;
+    return launch_proposal_drafts_args(st, a, k.B);
+  }
   if (!k.sample.pfx.tok || !k.want_sample_step) return TTX_OK;
   PrefixDraftsArgs a{};
   a.st = s->state.as<DecState>(); a.act_idx = s->act_idx.as<int>(); a.front = s->front.as<int>();
@@ -1481,10 +1502,13 @@ static int gen_launch_step(GenJob& j, int width_bound) {
     TTX_TRY(launch_accept_and_commit(s, j.st, j.g, j.greedy));
   } else {
     const bool pfx = k.sample.pfx.tok != nullptr;  // a prompted call never shares a graph with an unprompted one
-    const int site = k.want_sample_step ? (pfx ? GS_STEP_SAMPLE_SPEC_PREFIX : GS_STEP_SAMPLE_SPEC)
+    const bool prop = k.prop.tok != nullptr;       // nor does a proposed one; its keys end with the context length of the launch
+    const int site = k.want_sample_step ? (prop ? GS_STEP_SAMPLE_SPEC_PROPOSAL : pfx ? GS_STEP_SAMPLE_SPEC_PREFIX : GS_STEP_SAMPLE_SPEC)
                      : k.want_sample    ? (pfx ? GS_STEP_SAMPLE_PREFIX : GS_STEP_SAMPLE)
                      : j.greedy ? GS_STEP_GREEDY : (j.g.la.row_rule ? GS_STEP_ROW_RULE : GS_STEP_SPECULATIVE);
-    TTX_TRY(graph_replay(s, j.st, s->step_graphs, GraphKey{site, k.B, k.Ls, k.N, k.D, k.max_len, kcap, k.variant, 0}, enqueue));
+    GraphKey key{site, k.B, k.Ls, k.N, k.D, k.max_len, kcap, k.variant, 0};
+    if (prop) key.push_back(k.prop_ctx);
+    TTX_TRY(graph_replay(s, j.st, s->step_graphs, key, enqueue));
   }
   ++j.launched;
   return TTX_OK;
@@ -1611,6 +1635,10 @@ struct SampleSetup {
   // forced prefixes (prefix_validate); prompted false: the call is the unprompted one, launch for launch
   bool prompted;
   const int64_t* d_prefix; int ld_prefix; const int32_t* h_prefix_len; int n_sources;
+  // proposal drafts (proposal_validate): the table rides in the prefix fields above and through the same workspaces, since a call is
+  // either prompted or proposed; proposed false: no proposal, launch for launch
+  bool proposed; int prop_ctx;
+  bool tabled() const { return prompted || proposed; }
 };
 
 // The prefix arguments of a sampling call over S sources, or TTX_ERR_INVALID.  A call whose lengths are all zero (or absent) is
@@ -1630,6 +1658,28 @@ static int prefix_validate(const char* who, const int64_t* d_prefix, int ld_pref
   return TTX_OK;
 }
 
+// The proposal arguments of a speculative sampling call, after prefix_validate: the same refusals, and a call that carries both a
+// non-empty prefix and a non-empty proposal is refused.  A proposed call keeps its table in the prefix fields of `smp`.  The context
+// length is PROPOSAL_CTX; TTX_PROPOSAL_CTX (2, 4 or 8, read per call) overrides it for measurements and changes no output.
+static int proposal_validate(const char* who, const int64_t* d_proposal, int ld_proposal, const int32_t* h_proposal_len, int S,
+                             int max_len, SampleSetup* smp) {
+  smp->proposed = false; smp->prop_ctx = PROPOSAL_CTX;
+  if (!h_proposal_len) return TTX_OK;
+  SampleSetup q{};
+  const std::string who_q = std::string(who) + " (the proposal, held to a prefix's limits)";
+  TTX_TRY(prefix_validate(who_q.c_str(), d_proposal, ld_proposal, h_proposal_len, S, max_len, &q));
+  if (!q.prompted) return TTX_OK;
+  if (smp->prompted) return fail(TTX_ERR_INVALID, std::string(who) + ": a call takes forced prefixes or proposals, not both");
+  smp->d_prefix = d_proposal; smp->ld_prefix = ld_proposal; smp->h_prefix_len = h_proposal_len; smp->n_sources = S;
+  smp->proposed = true;
+  if (const char* e = getenv("TTX_PROPOSAL_CTX")) {
+    const int c = atoi(e);
+    if (c != 2 && c != 4 && c != 8) return fail(TTX_ERR_INVALID, std::string(who) + ": TTX_PROPOSAL_CTX must be 2, 4 or 8");
+    smp->prop_ctx = c;
+  }
+  return TTX_OK;
+}
+
 // The session's prefix table of a prompted call, int32 [S][max_len], and the sources' lengths on the device.  The row length is
 // max_len, which every step key holds, and the buffers are the session's, so a captured step holds nothing of the call.
 static int prefix_upload(ttx_session* s, hipStream_t st, const SampleSetup& smp, int max_len, int pad) {
@@ -1643,7 +1693,7 @@ static int prefix_upload(ttx_session* s, hipStream_t st, const SampleSetup& smp,
 
 // Session buffers of the sampling loop, sized before anything is captured.
 static int sample_ensure(ttx_session* s, hipStream_t st, size_t rows, const SampleSetup& smp, const ttx_gen_params* p) {
-  if (smp.prompted) {
+  if (smp.tabled()) {
     TTX_TRY(ensure(s->pfx_tok, (size_t)smp.n_sources * p->max_len * 4, st));
     TTX_TRY(ensure(s->pfx_len_src, (size_t)smp.n_sources * 4, st));
     TTX_TRY(ensure(s->pfx_len, rows * 4, st));
@@ -1672,12 +1722,14 @@ static int sample_begin(GenJob& j, const SampleSetup& smp) {
   k.want_sample_step = smp.spec;
   k.sample.key = s->smp_key.as<unsigned long long>(); k.sample.sample = s->smp_sample.as<unsigned>();
   k.sample.done = s->smp_done.as<int>(); k.sample.front = s->front.as<int>(); k.sample.prm = s->smp_prm.as<SampleBlock>();
-  if (smp.prompted) {
+  if (smp.tabled()) {
     TTX_TRY(prefix_upload(s, j.st, smp, k.max_len, k.p.pad_token));
     hipLaunchKernelGGL(k_prefix_rows, dim3(cdiv(R, 256)), dim3(256), 0, j.st, s->pfx_len_src.as<int>(), s->smp_src_of.as<int>(),
                        s->pfx_len.as<int>(), R);
     HIP_TRY(hipGetLastError());
-    k.sample.pfx = PrefixTab{s->pfx_tok.as<int>(), k.max_len, s->pfx_len.as<int>(), s->smp_src_of.as<int>()};
+    const PrefixTab tab{s->pfx_tok.as<int>(), k.max_len, s->pfx_len.as<int>(), s->smp_src_of.as<int>()};
+    if (smp.proposed) { k.prop = tab; k.prop_ctx = smp.prop_ctx; }      // offered: the sampling kernels see no table
+    else k.sample.pfx = tab;
     if (smp.spec) {                                  // draft 0 of every row as gen_start left it, before any step rewrites it
       HIP_TRY(hipMemcpy2DAsync(s->pfx_draft0.p, (size_t)k.D * 4, s->drafts.p, (size_t)k.N * k.D * 4, (size_t)k.D * 4, (size_t)R,
                                hipMemcpyDeviceToDevice, j.st));
@@ -1827,7 +1879,8 @@ static int sample_spec_validate(const char* who, const ttx_session* s, const ttx
 // committed rows are ttx_sample_generate's.
 static int sample_speculative_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
                                        const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream,
-                                       const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len) {
+                                       const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
+                                       const int64_t* d_proposal = nullptr, int ld_proposal = 0, const int32_t* h_proposal_len = nullptr) {
   const char* who = "ttx_sample_speculative_generate";
   if (!s || !p) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
   SampleSetup smp{};
@@ -1837,6 +1890,7 @@ static int sample_speculative_generate(ttx_session* s, const int64_t* d_src, int
   if (B <= 0) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
   smp.d_row_keys = d_row_keys;
   TTX_TRY(prefix_validate(who, d_prefix, ld_prefix, h_prefix_len, B, g.max_len, &smp));
+  TTX_TRY(proposal_validate(who, d_proposal, ld_proposal, h_proposal_len, B, g.max_len, &smp));
   const int rc = generate_one(s, d_src, (int)R, Ls, &g, d_out, stats, stream, false, &smp);
   if (rc == TTX_OK && stats) stats->src_tokens_padded = (long long)B * Ls;    // the encoder ran once per source
   return rc;
@@ -1852,6 +1906,16 @@ extern "C" int ttx_sample_speculative_generate_prefix(ttx_session* s, const int6
                                                       const ttx_sample_spec_params* p, const int64_t* d_prefix, int ld_prefix,
                                                       const int32_t* h_prefix_len, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
   return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, d_prefix, ld_prefix, h_prefix_len);
+}
+
+// The proposed form: the proposal is offered as draft 0 wherever it can be aligned with the row (k_proposal_drafts); no token changes.
+extern "C" int ttx_sample_speculative_generate_proposal(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                                        const ttx_sample_spec_params* p, const int64_t* d_prefix, int ld_prefix,
+                                                        const int32_t* h_prefix_len, const int64_t* d_proposal, int ld_proposal,
+                                                        const int32_t* h_proposal_len, int64_t* d_out, ttx_gen_stats* stats,
+                                                        void* stream) {
+  return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, d_prefix, ld_prefix, h_prefix_len, d_proposal,
+                                     ld_proposal, h_proposal_len);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1938,7 +2002,7 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
     need(s->pred_draft, Mmax * 4); need(s->state2, 3 * sizeof(DecState));
   }
   if (smp) { need(s->smp_key, (size_t)C * 8); need(s->smp_sample, (size_t)C * 4); need(s->smp_prm, sizeof(SampleBlock)); }
-  if (smp && smp->prompted) {
+  if (smp && smp->tabled()) {
     need(s->pfx_tok, (size_t)smp->n_sources * max_len * 4); need(s->pfx_len_src, (size_t)smp->n_sources * 4);
     need(s->pfx_len, (size_t)C * 4); need(s->pfx_src, (size_t)C * 4); need(s->pfx_draft0, (size_t)C * D * 4);
   }
@@ -2000,7 +2064,7 @@ static int pool_admit(PoolJob& j, const int64_t* d_src_rows, int ld_src, int R, 
   if (j.per_src) {
     a.key = s->smp_key.as<unsigned long long>(); a.sample = s->smp_sample.as<unsigned>(); a.row_keys = j.d_row_keys;
     a.per_src = j.per_src; a.first_src = first_row;
-    if (k.sample.pfx.tok) { a.pfx_src = s->pfx_src.as<int>(); a.pfx_len = s->pfx_len.as<int>(); a.pfx_len_of_src = s->pfx_len_src.as<int>(); }
+    if (step_tab(k).tok) { a.pfx_src = s->pfx_src.as<int>(); a.pfx_len = s->pfx_len.as<int>(); a.pfx_len_of_src = s->pfx_len_src.as<int>(); }
   }
   hipLaunchKernelGGL(k_pool_admit, dim3(1), dim3(256), (size_t)j.C * 4, st, a);
   HIP_TRY(hipGetLastError());
@@ -2011,7 +2075,7 @@ static int pool_admit(PoolJob& j, const int64_t* d_src_rows, int ld_src, int R, 
   f.memkv = s->memkv.as<float>(); f.memkv_new = s->memkv_new.as<float>(); f.kv_row = kv_row;
   f.out_rows = d_out; f.traj_rows = d_traj; f.fin_rows = d_fin; f.max_len = k.max_len; f.traj_ld = k.max_len + 1; f.first_row = row0;
   f.per_src = j.per_src;
-  if (k.sample.pfx.tok) { f.draft0 = s->pfx_draft0.as<int>(); f.D = k.D; }
+  if (step_tab(k).tok) { f.draft0 = s->pfx_draft0.as<int>(); f.D = k.D; }
   hipLaunchKernelGGL(k_pool_fill, dim3(rows, 1 + Ls_new), dim3(256), 0, st, f);
   HIP_TRY(hipGetLastError());
   ++j.admits;
@@ -2024,6 +2088,8 @@ static int pool_admit(PoolJob& j, const int64_t* d_src_rows, int ld_src, int R, 
 // The sampling pool has a site of its own, and its keys end with the form of the accept step (1: the pair), which it reads from
 // the environment per call.
 static GraphKey pool_key(const PoolJob& j, const StepCtx& k, int variant, int phase) {
+  if (k.want_sample_step && k.prop.tok)              // a proposed pool: a site of its own, the key ends with the context length
+    return GraphKey{GS_STEP_POOL_SAMPLE_PROPOSAL, k.B, k.Ls, k.N, k.D, k.max_len, k.max_len, variant, phase, j.g.la.blk ? 1 : 0, k.prop_ctx};
   if (k.want_sample_step)
     return GraphKey{k.sample.pfx.tok ? GS_STEP_POOL_SAMPLE_PREFIX : GS_STEP_POOL_SAMPLE, k.B, k.Ls, k.N, k.D, k.max_len, k.max_len, variant, phase, j.g.la.blk ? 1 : 0};
   return GraphKey{GS_STEP_POOL, k.B, k.Ls, k.N, k.D, k.max_len, k.max_len, variant, phase};
@@ -2120,9 +2186,11 @@ static int pool_sample_begin(PoolJob& j, const SampleSetup& smp) {
   k.sample.front = s->front.as<int>(); k.sample.prm = s->smp_prm.as<SampleBlock>();
   j.g.la.sample_rule = 1;
   j.per_src = smp.n; j.d_row_keys = smp.d_row_keys;
-  if (smp.prompted) {                                // the slots' lengths, sources and draft 0 are written at admission
+  if (smp.tabled()) {                                // the slots' lengths, sources and draft 0 are written at admission
     TTX_TRY(prefix_upload(s, j.st, smp, k.max_len, k.p.pad_token));
-    k.sample.pfx = PrefixTab{s->pfx_tok.as<int>(), k.max_len, s->pfx_len.as<int>(), s->pfx_src.as<int>()};
+    const PrefixTab tab{s->pfx_tok.as<int>(), k.max_len, s->pfx_len.as<int>(), s->pfx_src.as<int>()};
+    if (smp.proposed) { k.prop = tab; k.prop_ctx = smp.prop_ctx; }
+    else k.sample.pfx = tab;
     k.pfx_draft0 = s->pfx_draft0.as<int>();
   }
   return TTX_OK;
@@ -2241,7 +2309,8 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
 static int sample_speculative_generate_pool(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total, int Ls_all,
                                             const int32_t* h_len, const int64_t* d_row_keys, int capacity, const ttx_sample_spec_params* p,
                                             int64_t* d_out, ttx_gen_stats* stats, void* stream, const int64_t* d_prefix, int ld_prefix,
-                                            const int32_t* h_prefix_len) {
+                                            const int32_t* h_prefix_len, const int64_t* d_proposal = nullptr, int ld_proposal = 0,
+                                            const int32_t* h_proposal_len = nullptr) {
   const char* who = "ttx_sample_speculative_generate_pool";
   if (!sessions || n_sessions <= 0 || !d_src || S_total < 0 || !h_len || !p || !d_out)
     return fail(TTX_ERR_INVALID, std::string("bad argument to ") + who);
@@ -2261,6 +2330,7 @@ static int sample_speculative_generate_pool(ttx_session** sessions, int n_sessio
   if (g.pad_token != c.pad_token) return fail(TTX_ERR_INVALID, std::string(who) + ": generator pad token differs from the model's");
   if (g.max_len + g.draft_len + 2 > c.max_positions) return fail(TTX_ERR_INVALID, std::string(who) + ": max_len + draft_len exceeds the positional table");
   TTX_TRY(prefix_validate(who, d_prefix, ld_prefix, h_prefix_len, S_total, g.max_len, &smp));
+  TTX_TRY(proposal_validate(who, d_proposal, ld_proposal, h_proposal_len, S_total, g.max_len, &smp));
   if (S_total == 0) return TTX_OK;
   smp.d_row_keys = d_row_keys;
   return pool_generate(sessions, n_sessions, d_src, S_total, Ls_all, h_len, Ls_cap, capacity, &g, d_out, nullptr, nullptr, stats, stream, &smp);
@@ -2281,6 +2351,17 @@ extern "C" int ttx_sample_speculative_generate_pool_prefix(ttx_session** session
                                                            void* stream) {
   return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p, d_out, stats, stream,
                                           d_prefix, ld_prefix, h_prefix_len);
+}
+
+// The proposed pool: the proposal table rides through admission as the prefix table does.
+extern "C" int ttx_sample_speculative_generate_pool_proposal(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total,
+                                                             int Ls_all, const int32_t* h_len, const int64_t* d_row_keys, int capacity,
+                                                             const ttx_sample_spec_params* p, const int64_t* d_prefix, int ld_prefix,
+                                                             const int32_t* h_prefix_len, const int64_t* d_proposal, int ld_proposal,
+                                                             const int32_t* h_proposal_len, int64_t* d_out, ttx_gen_stats* stats,
+                                                             void* stream) {
+  return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p, d_out, stats, stream,
+                                          d_prefix, ld_prefix, h_prefix_len, d_proposal, ld_proposal, h_proposal_len);
 }
 
 // Several batches in flight on one GPU: outputs per batch are identical to the one-at-a-time call.
@@ -3663,6 +3744,41 @@ extern "C" int ttx_debug_prefix_drafts(ttx_session* s, const int32_t* d_act_idx,
     a.st = dst; a.act_idx = d_act_idx; a.front = d_front; a.drafts = d_drafts; a.N = N; a.D = D; a.draft0 = d_draft0;
     a.eos = eos_token; a.pad = pad_token; a.repl = replace_token;
     rc = launch_prefix_drafts_args(st, a, B);         // production's grid: one wave per slot of the capacity
+  }
+  const hipError_t esync = hipStreamSynchronize(st);   // the launch reads the state: keep it until the launch is through
+  (void)hipFree(dst);
+  HIP_TRY(err);
+  HIP_TRY(esync);
+  return rc;
+}
+
+extern "C" int ttx_debug_proposal_drafts(ttx_session* s, const int32_t* d_act_idx, const int32_t* d_front, const int32_t* d_gen, int gen_ld,
+                                         int B, int N, int D, int n_active, int32_t* d_drafts, const int32_t* d_draft0,
+                                         const ttx_debug_prefix* proposal, int ctx, int bos_token, int eos_token, int pad_token,
+                                         int replace_token, void* stream) {
+  const char* who = "ttx_debug_proposal_drafts";
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!s || !d_act_idx || !d_front || !d_gen || !d_drafts || !d_draft0) return fail(TTX_ERR_INVALID, std::string("null argument to ") + who);
+  if (B < 1 || N < 1 || D < 1 || gen_ld < 1 || (long long)B * N * D >= (1ll << 31) || (long long)B * gen_ld >= (1ll << 31))
+    return fail(TTX_ERR_INVALID, std::string(who) + ": B, N, D and gen_ld must be positive");
+  if (n_active < 0 || n_active > B) return fail(TTX_ERR_INVALID, std::string(who) + ": n_active must lie in [0, B]");
+  if (ctx != 2 && ctx != 4 && ctx != 8) return fail(TTX_ERR_INVALID, std::string(who) + ": ctx must be 2, 4 or 8");
+  HIP_TRY(hipSetDevice(s->m->device));
+  int max_front = 0;
+  // the kernel reads gen[0 .. front] of the active rows: front + 1 <= gen_ld (dbg_check_slots asks for front + 0 + 2)
+  TTX_TRY(dbg_check_slots(who, d_act_idx, d_front, B, n_active, gen_ld + 1, 0, st, &max_front));
+  ProposalDraftsArgs a{};
+  TTX_TRY(dbg_prefix_tab(who, proposal, B, st, &a.tab));
+  DecState* dst = nullptr;
+  HIP_TRY(hipMalloc((void**)&dst, sizeof(DecState)));
+  DecState hs{};
+  hs.n_active = n_active; hs.r_rows = n_active * N; hs.m_rows = n_active * step_rps(N, D);
+  hipError_t err = hipMemcpy(dst, &hs, sizeof(DecState), hipMemcpyHostToDevice);
+  int rc = TTX_OK;
+  if (err == hipSuccess) {
+    a.st = dst; a.act_idx = d_act_idx; a.front = d_front; a.gen = d_gen; a.gen_ld = gen_ld; a.drafts = d_drafts; a.N = N; a.D = D;
+    a.draft0 = d_draft0; a.bos = bos_token; a.eos = eos_token; a.pad = pad_token; a.repl = replace_token; a.ctx = ctx;
+    rc = launch_proposal_drafts_args(st, a, B);       // production's grid: one wave per slot of the capacity
   }
   const hipError_t esync = hipStreamSynchronize(st);   // the launch reads the state: keep it until the launch is through
   (void)hipFree(dst);

@@ -83,9 +83,13 @@ enum AttnKernelId { AK_ATTN = 1, AK_ATTN2 = 2, AK_ATTN3 = 3, AK_ATTN3S = 4, AK_A
 //                                 place (ttx_sample_speculative_generate_pool): never a graph of the greedy pool
 //   GS_STEP_*_PREFIX              the three sampling sites of a prompted call (forced prefixes): the same keys; k_prefix_drafts leads
 //                                 the speculative ones and the sampling kernels carry the session's prefix table (row length max_len)
+//   GS_STEP_*_PROPOSAL            the two speculative sampling sites of a proposed call (proposal drafts): the same keys with the
+//                                 context length of k_proposal_drafts appended; that kernel leads the step, the sampling kernels
+//                                 carry no table
 enum GraphSite { GS_STEP_SPECULATIVE = 0, GS_STEP_GREEDY = 1, GS_STEP_ROW_RULE = 2, GS_STEP_POOL = 3, GS_BEAM_ITER = 4, GS_BEAM_POOL_ITER = 5,
                  GS_STEP_SAMPLE = 6, GS_STEP_SAMPLE_SPEC = 7, GS_STEP_POOL_SAMPLE = 8,
-                 GS_STEP_SAMPLE_PREFIX = 9, GS_STEP_SAMPLE_SPEC_PREFIX = 10, GS_STEP_POOL_SAMPLE_PREFIX = 11 };
+                 GS_STEP_SAMPLE_PREFIX = 9, GS_STEP_SAMPLE_SPEC_PREFIX = 10, GS_STEP_POOL_SAMPLE_PREFIX = 11,
+                 GS_STEP_SAMPLE_SPEC_PROPOSAL = 12, GS_STEP_POOL_SAMPLE_PROPOSAL = 13 };
 typedef std::vector<int> GraphKey;
 
 // Captured graphs of one family of keys.  A key runs eagerly the first time it is seen (`warmed`: function attributes are set

@@ -470,16 +470,31 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         return (f"Speculative sampling (draft_len={self.draft_len}, n_drafts={self.n_drafts}, temperature={self.temperature}, "
                 f"top_k={self.top_k}, top_p={self.top_p}, num_samples={self.num_samples}, seed={self.seed}, max_len={self.max_len})")
 
-    def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, prefix=None):
+    def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, prefix=None, proposal=None):
         """Long[B, num_samples, max_len]; ``row_keys``, ``return_scores`` and ``prefix`` as for
         ``TranslationInferenceSampling.generate``.  A prefix rides in as the first draft of its rows, which is certain to be
-        accepted: ``P`` forced tokens take ``ceil(P / (draft_len + 1))`` verify steps."""
+        accepted: ``P`` forced tokens take ``ceil(P / (draft_len + 1))`` verify steps.
+
+        ``proposal``: Long[B, Lq] without BOS, right-padded with PAD, may end in EOS: a draft the caller brings for every sample
+        of a source (a cheaper model's output, an earlier prediction, the source's own greedy answer).  It is offered, never
+        forced: a draft token is accepted iff it is the token of its position, so the returned rows are those of the call
+        without ``proposal`` whatever the proposal holds (under the class's one caveat: a uniform within fp32 rounding of a CDF
+        boundary); only the number of decoder passes changes.  Before every
+        verify step the proposal is aligned with the row so far (up to 32 tokens to the left, 31 to the right, by the last few
+        tokens) and replaces the first draft from there on, so a row finds its place again after a substitution, an insertion
+        or a deletion.  A proposal equal to the row takes ``ceil(L / (draft_len + 1))`` passes for ``L`` emitted tokens.
+        ``temperature=0`` is the greedy use: the tokens are the greedy-speculative generator's and the proposal is a draft for
+        them.  An empty proposal (zero width, all PAD, ``None``) is the call without one.  ``prefix`` together with
+        ``proposal`` raises ValueError."""
+        if prefix is not None and proposal is not None:
+            raise ValueError("a call takes a forced prefix or a proposal, not both")
         m, n = self.model, self.num_samples
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
         B, Ls = src.shape
         # d_prefix is bound only to keep the device tensor alive until the call returns: prefix_ptr points into it
         d_prefix, prefix_ptr, ld_prefix, h_plen = self._prefix_args(prefix, B)
+        d_prop, prop_ptr, ld_prop, h_qlen = self._prefix_args(proposal, B)          # the same checks and limits
         keys = None
         if row_keys is not None:
             keys = torch.as_tensor(row_keys, dtype=torch.int64).to(m.device).contiguous()
@@ -490,9 +505,10 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
                                self.draft_len, self.n_drafts, self.replace_token, 0)
         out = torch.empty((B, max(n, 1), max(self.max_len, 1)), dtype=torch.int64, device=m.device)
         st = N.GenStats()
-        N.check(m._lib.ttx_sample_speculative_generate_prefix(m.session, src.data_ptr(), B, Ls,
-                                                              None if keys is None else keys.data_ptr(), C.byref(p), prefix_ptr,
-                                                              ld_prefix, h_plen, out.data_ptr(), C.byref(st), m._stream()))
+        N.check(m._lib.ttx_sample_speculative_generate_proposal(m.session, src.data_ptr(), B, Ls,
+                                                                None if keys is None else keys.data_ptr(), C.byref(p), prefix_ptr,
+                                                                ld_prefix, h_plen, prop_ptr, ld_prop, h_qlen, out.data_ptr(),
+                                                                C.byref(st), m._stream()))
         self.model_calls_num += int(st.model_calls)
         self.accepted_tokens_num += int(st.accepted_tokens)
         self.given_tokens += int((src != m.src_pad_token_i).sum())
@@ -506,7 +522,7 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         return self._scored(src, out, return_scores)
 
     def generate_many(self, batches: list, row_keys=None, in_flight: int = 4, capacity: int | None = None,
-                      return_scores: bool = False, prefixes=None) -> list:
+                      return_scores: bool = False, prefixes=None, proposals=None) -> list:
         """The samples of all batches from slot pools (ttx_sample_speculative_generate_pool: continuous batching over the sources
         of the whole list, sorted by length; the ``num_samples`` rows of a source are admitted together).  Returns one
         Long[B_i, num_samples, max_len] per batch.
@@ -519,32 +535,43 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         ``return_scores=True``: a list of ``(pred, HypothesisScores)`` pairs.
         ``prefixes``: a list aligned with ``batches``, each entry a ``prefix`` tensor for that batch (see ``generate``) or
         ``None``; ``generate_many(batches, prefixes=ps)[i]`` holds the rows of ``generate(batches[i], prefix=ps[i],
-        row_keys=arange(off_i, off_i + B_i))``."""
+        row_keys=arange(off_i, off_i + B_i))``.
+        ``proposals``: the same for ``generate``'s ``proposal``: offered drafts, which change no row.  A call takes ``prefixes``
+        or ``proposals``, not both (ValueError)."""
         if return_scores:
-            return self._scored_many(batches, self.generate_many(batches, row_keys, in_flight, capacity, prefixes=prefixes))
+            return self._scored_many(batches, self.generate_many(batches, row_keys, in_flight, capacity, prefixes=prefixes,
+                                                                 proposals=proposals))
         from .scheduling import plan_row_groups
-        if prefixes is not None and len(prefixes) != len(batches):
-            raise ValueError(f"prefixes must hold one entry per batch ({len(batches)}), got {len(prefixes)}")
+        if prefixes is not None and proposals is not None:
+            raise ValueError("a call takes forced prefixes or proposals, not both")
+        for name, tabs in (("prefixes", prefixes), ("proposals", proposals)):
+            if tabs is not None and len(tabs) != len(batches):
+                raise ValueError(f"{name} must hold one entry per batch ({len(batches)}), got {len(tabs)}")
         if not batches:
             return []
         m, n, L = self.model, self.num_samples, self.max_len
         sizes = [int(b.shape[0]) for b in batches]
         S = sum(sizes)
-        # every source's prefix in one right-padded matrix beside the sources, or None when no batch carries one
-        allpre = plen = None
-        if prefixes is not None and any(q is not None for q in prefixes):
-            checked = [check_prefix(q, B, L, self.pad_token, m.tgt_vocab_size) for q, B in zip(prefixes, sizes)]
+
+        def stacked(tabs):
+            """Every source's prefix (proposal) in one right-padded matrix beside the sources and the lengths, or (None, None)
+            when no batch carries a non-empty one: the plain call, with nothing to sort or upload."""
+            if tabs is None or all(q is None for q in tabs):
+                return None, None
+            checked = [check_prefix(q, B, L, self.pad_token, m.tgt_vocab_size) for q, B in zip(tabs, sizes)]
             Lp = max([int(c[0].shape[1]) for c in checked if c[0] is not None] or [0])
-            allpre = torch.full((S, Lp), self.pad_token, dtype=torch.int64)
-            plen = torch.zeros(S, dtype=torch.int64)
+            mat = torch.full((S, Lp), self.pad_token, dtype=torch.int64)
+            lens_all = torch.zeros(S, dtype=torch.int64)
             r0 = 0
             for (q, lens), B in zip(checked, sizes):
                 if q is not None:
-                    allpre[r0:r0 + B, :q.shape[1]] = q
-                    plen[r0:r0 + B] = torch.tensor(lens, dtype=torch.int64)
+                    mat[r0:r0 + B, :q.shape[1]] = q
+                    lens_all[r0:r0 + B] = torch.tensor(lens, dtype=torch.int64)
                 r0 += B
-            if not bool(plen.any()):                  # every prefix is empty: the unprompted call, with nothing to sort or upload
-                allpre = plen = None
+            return (mat, lens_all) if bool(lens_all.any()) else (None, None)
+
+        allpre, plen = stacked(prefixes)
+        allprop, qlen = stacked(proposals)
         srcs = [b.to(m.device, torch.int64) for b in batches]
         if row_keys is None:
             keys = torch.arange(S, dtype=torch.int64)
@@ -587,15 +614,21 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
             h_len = (C.c_int32 * S)(*[int(x) for x in sorted_len])
             sessions = m.session_pool(n_sess)
             sess = (C.c_void_p * len(sessions))(*[q.value for q in sessions])
-            pre_sorted, pre_ptr, ld_prefix, h_plen = None, None, 0, None
-            if allpre is not None:
-                order_cpu = torch.from_numpy(order).to(torch.int64)
-                pre_sorted = allpre[order_cpu].contiguous().to(m.device)
-                pre_ptr, ld_prefix = (pre_sorted.data_ptr() if pre_sorted.numel() else None), int(pre_sorted.shape[1])
-                h_plen = (C.c_int32 * S)(*[int(x) for x in plen[order_cpu]])
-            N.check(m._lib.ttx_sample_speculative_generate_pool_prefix(sess, len(sessions), src_mat.data_ptr(), S, width, h_len,
-                                                                       keys_sorted.data_ptr(), cap, C.byref(p), pre_ptr, ld_prefix,
-                                                                       h_plen, out_sorted.data_ptr(), C.byref(st), m._stream()))
+            order_cpu = torch.from_numpy(order).to(torch.int64)
+
+            def table_args(mat, lens_all):
+                """``(sorted device matrix kept alive, its pointer, its row length, host lengths)`` in the pool's order."""
+                if mat is None:
+                    return None, None, 0, None
+                d = mat[order_cpu].contiguous().to(m.device)
+                return d, (d.data_ptr() if d.numel() else None), int(d.shape[1]), (C.c_int32 * S)(*[int(x) for x in lens_all[order_cpu]])
+
+            pre_sorted, pre_ptr, ld_prefix, h_plen = table_args(allpre, plen)
+            prop_sorted, prop_ptr, ld_prop, h_qlen = table_args(allprop, qlen)
+            N.check(m._lib.ttx_sample_speculative_generate_pool_proposal(sess, len(sessions), src_mat.data_ptr(), S, width, h_len,
+                                                                         keys_sorted.data_ptr(), cap, C.byref(p), pre_ptr, ld_prefix,
+                                                                         h_plen, prop_ptr, ld_prop, h_qlen, out_sorted.data_ptr(),
+                                                                         C.byref(st), m._stream()))
             inv = torch.empty_like(order_t)
             inv[order_t] = torch.arange(S, device=m.device)
             out_rows = out_sorted[inv]

@@ -111,7 +111,7 @@ class _PredictAhead:
         self.prefixes = {}           # batch index -> the batch's "prefix_tokens" it was decoded with (sampling generators; None: none)
 
     def _decode_window(self, device) -> None:
-        pending, prefixes = [], []
+        pending, prefixes, proposals = [], [], []
         for _ in range(self.window):
             try:
                 b = next(self.it)
@@ -119,6 +119,7 @@ class _PredictAhead:
                 break
             pending.append(b["src_tokens"].to(device))
             prefixes.append(b.get("prefix_tokens") if hasattr(b, "get") else None)
+            proposals.append(b.get("proposal_tokens") if hasattr(b, "get") else None)
         if not pending:
             self.enabled = False
             return
@@ -126,6 +127,10 @@ class _PredictAhead:
         prompted = any(q is not None for q in prefixes)
         if prompted and not isinstance(g, D.TranslationInferenceSamplingSpeculative):
             raise ValueError(f'"prefix_tokens" in a batch: only generation="sampling" and "sampling_speculative" take forced prefixes, '
+                             f"not {type(g).__name__}")
+        proposed = any(q is not None for q in proposals)     # offered drafts: they change no row, so take() does not compare them
+        if proposed and not isinstance(g, D.TranslationInferenceSamplingSpeculative):
+            raise ValueError(f'"proposal_tokens" in a batch: only generation="sampling_speculative" takes proposals, '
                              f"not {type(g).__name__}")
         t0 = timer()
         if isinstance(g, D.TranslationInferenceGreedySpeculative):      # slot pools over all rows of the window
@@ -135,7 +140,8 @@ class _PredictAhead:
             for b in pending:
                 keys.append(torch.arange(r0, r0 + int(b.shape[0])))
                 r0 += int(b.shape[0])
-            preds = g.generate_many(pending, row_keys=keys, in_flight=self.in_flight, prefixes=prefixes if prompted else None)
+            preds = g.generate_many(pending, row_keys=keys, in_flight=self.in_flight, prefixes=prefixes if prompted else None,
+                                    proposals=proposals if proposed else None)
             self.rows = r0
         else:                                                           # source pools over all sources of the window
             preds = g.generate_many(pending, in_flight=self.in_flight, on_error="skip")
@@ -319,14 +325,19 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         if prefix is not None and not sampling:
             raise ValueError(f'"prefix_tokens" in a batch: only generation="sampling" and "sampling_speculative" take forced '
                              f'prefixes, not "{self.hparams.generation}"')
+        proposal = batch["proposal_tokens"] if "proposal_tokens" in batch else None  # offered drafts: Long[B, Lq], no BOS
+        if proposal is not None and self.hparams.generation != "sampling_speculative":
+            raise ValueError(f'"proposal_tokens" in a batch: only generation="sampling_speculative" takes proposals, '
+                             f'not "{self.hparams.generation}"')
         if ahead is not None and dataloader_idx == 0:
             pred = ahead.take(batch["src_tokens"], batch_idx, prefix)
         if pred is not None and self.hparams.generation in ("sampling", "sampling_speculative"):
             self._predict_rows += int(batch["src_tokens"].shape[0])        # served ahead under these keys: a fallback goes on from here
         elif pred is None and self.hparams.generation in ("sampling", "sampling_speculative"):
             B = int(batch["src_tokens"].shape[0])
+            more = {} if proposal is None else {"proposal": proposal}
             pred = self.generator.generate(batch["src_tokens"], row_keys=torch.arange(self._predict_rows, self._predict_rows + B),
-                                           prefix=prefix)
+                                           prefix=prefix, **more)
             self._predict_rows += B
         elif pred is None and self.hparams.generation == "stochastic_beam_search":   # keyed like the samplers: the running index
             B = int(batch["src_tokens"].shape[0])

@@ -391,6 +391,20 @@ class NativeTransformer:
                                                   int(n_active), drafts.data_ptr(), draft0.data_ptr(), C.byref(x), int(eos), int(pad),
                                                   int(replace), self._stream()))
 
+    def debug_proposal_drafts(self, act_idx: torch.Tensor, front: torch.Tensor, gen: torch.Tensor, drafts: torch.Tensor,
+                              draft0: torch.Tensor, *, proposal_tok: torch.Tensor, proposal_len: torch.Tensor,
+                              proposal_src: torch.Tensor, n_active: int, ctx: int = 2, bos: int = 1, eos: int = 2, pad: int = 0,
+                              replace: int = 3) -> None:
+        """One k_proposal_drafts launch (ttx_debug_proposal_drafts): ``act_idx`` / ``front`` int32 [B], ``gen`` int32 [B, gen_ld]
+        the rows' tokens, ``drafts`` int32 [B, n, d] (draft 0 of the active rows is rewritten), ``draft0`` int32 [B, d], the
+        proposal table int32 [sources, ld] with the rows' lengths and sources int32 [B]."""
+        B, n, d = drafts.shape
+        x = self._debug_prefix(proposal_tok, proposal_len, proposal_src)
+        N.check(self._lib.ttx_debug_proposal_drafts(self._session, act_idx.data_ptr(), front.data_ptr(), gen.data_ptr(),
+                                                    int(gen.shape[1]), int(B), int(n), int(d), int(n_active), drafts.data_ptr(),
+                                                    draft0.data_ptr(), C.byref(x), int(ctx), int(bos), int(eos), int(pad),
+                                                    int(replace), self._stream()))
+
     def debug_sample_prefix(self, logits: torch.Tensor, key: torch.Tensor, sample: torch.Tensor, done: torch.Tensor,
                             front: torch.Tensor, pred: torch.Tensor, m_max: int, m_live: torch.Tensor | None = None, *,
                             prefix_tok: torch.Tensor, prefix_len: torch.Tensor, prefix_src: torch.Tensor, temperature: float = 1.0,
