@@ -1001,6 +1001,46 @@ typedef struct ttx_debug_tree_cache_args {
  * multiples of 4 floats, buffers that are not 16-byte aligned, one slot map without the other, slot maps with k_old != k_new. */
 int ttx_debug_tree_cache(ttx_session* s, const ttx_debug_tree_cache_args* a, void* stream);
 
+/* ---- The bookkeeping kernels of the beam-speculative batch pool (csrc/ttx_loop_kernels.hip.h: k_bsp_init .. k_bsp_publish), ONE
+ * launch per call on DEVICE arrays of the caller (tests/test_gpu_bsp_kernels.py; the rules are restated in tests/util_bsp_checks.py).
+ * The struct is the kernels' argument block: every array of BeamPoolArgs, the caller-side arrays of BeamPoolIo (d_out int64
+ * [rows, K, max_len], d_trace_len int16 [rows, T_cap], d_summary int32 [rows, 8], d_len_all / d_batch_all int32 [rows],
+ * d_given_all int32 [batches]), the extra operands of k_bsp_init / k_bsp_admit (d_src_of, d_cand_src_len int32 [C*K]; d_new_slot
+ * int32 [C]) and of k_bsp_fill (staged d_tok_new int32 [R, Ls_new], d_valid_new uint8 [R, Ls_new], d_drafts_new int32 [R, N*D0] or
+ * NULL as in smart mode, d_memkv_new fp32 [R, Ls_new, kv_row]; the pool's d_src_valid uint8 [C, Ls_cap], d_memkv fp32 [C, Ls_cap,
+ * kv_row]), then the int32 scalars, named as the kernels name them.  Source- and batch-slot arrays are int32 [C] (d_src_acc [C, 8]),
+ * candidate arrays [C*K] (d_cand_next int64 [C*K, ld], d_gen int32 [C*K, ld], d_drafts32 int32 [C*K, N, D0], d_chosen int64 [C*K, D0],
+ * d_leaf_score / d_leaf_tok [C*K, D0+1, K], d_leaf_cnt [C*K, D0+1]), d_tok int32 [C, Ls_cap], d_drafts_all int32 [C, N, D0],
+ * d_dev_summary int32 [4].  The entry builds the BeamPoolIo block and uses the session's pinned BeamPoolHost.
+ * op: 0 init, 1 admit, 2 fill, 3 prep, 4 select, 5 batches, 6 retire, 7 publish; grid, block, dynamic LDS and the raise of
+ * k_bsp_select's LDS limit are the pool's own launch functions (csrc/ttx_api.hip: launch_bsp_*).  Each call waits for its launch.
+ * `words` is a HOST array of 12 int64: on entry [0..7] = the BeamCounters image (as for ttx_debug_bs_list) and [8..11] = the
+ * BeamPoolHost image (steps_done, n_live, n_running, error), both put where the kernel reads them, ordered on `stream`; on return
+ * the same 12 words as the kernel left them.
+ * Refused (TTX_ERR_INVALID, nothing launched): a null required pointer (every array of BeamPoolArgs and BeamPoolIo for every op,
+ * d_drafts_all in all-drafts mode only; d_src_of and d_cand_src_len for init; d_new_slot and d_cand_src_len for admit; d_new_slot
+ * and the fill operands but d_drafts_new for fill), a non-positive size (D0, max_steps and first_row may be 0), an unknown op,
+ * C > 1024, K > 32, N > 64, K * (D0 + 1) > 1023 segments, k_bsp_select's LDS image 2 * K * (D0 + 1) * K * 4 above 150 KiB,
+ * ld < max_len + D0 + 2, and for admit / fill R > C; for fill Ls_new > Ls_cap, kv_row not a multiple of 4, d_memkv or d_memkv_new
+ * not 16-byte aligned. */
+typedef struct ttx_debug_bsp_args {
+  int32_t* d_row_of; int32_t* d_slot_batch; int32_t* d_src_acc; int32_t* d_src_state; int32_t* d_tok; int32_t* d_drafts_all;
+  int32_t* d_bat_id; int32_t* d_bat_iter; int32_t* d_bat_dl; int32_t* d_bat_grp; int32_t* d_bat_live; int32_t* d_bat_nfin;
+  int32_t* d_bat_longest_fin; int32_t* d_bat_longest_cur; int32_t* d_bat_state; int32_t* d_bat_given;
+  int64_t* d_cand_next; int32_t* d_len_next; uint8_t* d_fin_next; float* d_logp_next; int32_t* d_parent; int32_t* d_parent_draft;
+  int32_t* d_gen; int32_t* d_front; int32_t* d_len; uint8_t* d_active; uint8_t* d_finished; uint8_t* d_live; float* d_logp;
+  int32_t* d_per_cand; int32_t* d_drafts32; int32_t* d_cand_dl; int32_t* d_cand_batch; int32_t* d_cache_slot; int32_t* d_cache_slot_parent;
+  const int32_t* d_chosen_slot; const int64_t* d_chosen; const float* d_leaf_score; const int32_t* d_leaf_tok; const int32_t* d_leaf_cnt;
+  int32_t* d_dev_summary;
+  int64_t* d_out; int16_t* d_trace_len; int32_t* d_summary; const int32_t* d_len_all; const int32_t* d_batch_all; const int32_t* d_given_all;
+  int32_t* d_src_of; int32_t* d_cand_src_len; int32_t* d_new_slot;
+  const int32_t* d_tok_new; const uint8_t* d_valid_new; uint8_t* d_src_valid; const int32_t* d_drafts_new; float* d_memkv;
+  const float* d_memkv_new;
+  int32_t C, K, N, D0, Ls_cap, max_len, ld, smart, lib_ld, pad, bos, eos, repl, max_steps;
+  int32_t T_cap, R, first_row, kv_row, Ls_new;
+} ttx_debug_bsp_args;
+int ttx_debug_bsp(ttx_session* s, int op, const ttx_debug_bsp_args* a, int64_t* words, void* stream);
+
 /* ttx_debug_kvcopy: ONE launch of k_kvcopy on a grid of (B, Ld) workgroups: for slot < n_copy with record (b, best, n_acc,
  * front_old, .) of d_rec int32 [B, 5] and j = 0 .. n_acc, the K and V thirds of step row (j == 0 ? 0 : 1 + best*D + (j-1)) of the
  * slot, in d_qkv [Ld][B * (1 + N*D)][3d] with qkv_layer_stride floats between layers, are copied bit for bit to position

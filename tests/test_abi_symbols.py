@@ -44,6 +44,7 @@ def test_struct_sizes_match_header_layout():
     assert C.sizeof(N.DebugBeamSelectArgs) == 16 * 8 + 9 * 4 + 4
     assert C.sizeof(N.DebugBeamStepArgs) == 12 * 8 + 8 * 4
     assert C.sizeof(N.DebugTreeCacheArgs) == 13 * 8 + 3 * 8 + 5 * 4 + 4
+    assert C.sizeof(N.DebugBspArgs) == 56 * 8 + 19 * 4 + 4                # ttx_debug_bsp_args: 41 + 6 + 3 + 6 pointers, 14 + 5 int32
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="only meaningful on a machine without a GPU")

@@ -47,7 +47,8 @@ EPS32 = 2.0 ** -23
 NUCLEUS, HIT_MARGIN, HIT_CAP, PLANT_MARGIN = 0.9975, 1e-5, 0.01, 1e-3
 GAP = 1e-3                                   # separation of the planted k_beam_step totals
 I32, I64, F32, U8 = np.int32, np.int64, np.float32, np.uint8
-TORCH_OF = {np.dtype(U8): torch.uint8, np.dtype(I32): torch.int32, np.dtype(I64): torch.int64, np.dtype(F32): torch.float32}
+TORCH_OF = {np.dtype(U8): torch.uint8, np.dtype(np.int16): torch.int16, np.dtype(I32): torch.int32, np.dtype(I64): torch.int64,
+            np.dtype(F32): torch.float32}
 BIG = 0x7FFFFFFF
 
 

@@ -186,6 +186,20 @@ DebugTreeCacheArgs = _debug_args("debug_tree_cache_args",
                                   "d_v_new", "d_qkv_prev", "d_prev_slot_of", "d_slot_parent", "d_slot_self"),
                                  ("max_cand", "layers", "prev_N", "prev_D", "d"),
                                  ("cache_layer_stride", "cache_seq_stride", "qkv_layer_stride"))
+# the pool's bookkeeping kernels (k_bsp_init .. k_bsp_publish): one struct for the eight of them
+DebugBspArgs = _debug_args("debug_bsp_args",
+                           ("d_row_of", "d_slot_batch", "d_src_acc", "d_src_state", "d_tok", "d_drafts_all", "d_bat_id", "d_bat_iter",
+                            "d_bat_dl", "d_bat_grp", "d_bat_live", "d_bat_nfin", "d_bat_longest_fin", "d_bat_longest_cur", "d_bat_state",
+                            "d_bat_given", "d_cand_next", "d_len_next", "d_fin_next", "d_logp_next", "d_parent", "d_parent_draft",
+                            "d_gen", "d_front", "d_len", "d_active", "d_finished", "d_live", "d_logp", "d_per_cand", "d_drafts32",
+                            "d_cand_dl", "d_cand_batch", "d_cache_slot", "d_cache_slot_parent", "d_chosen_slot", "d_chosen",
+                            "d_leaf_score", "d_leaf_tok", "d_leaf_cnt", "d_dev_summary", "d_out", "d_trace_len", "d_summary",
+                            "d_len_all", "d_batch_all", "d_given_all", "d_src_of", "d_cand_src_len", "d_new_slot", "d_tok_new",
+                            "d_valid_new", "d_src_valid", "d_drafts_new", "d_memkv", "d_memkv_new"),
+                           ("C", "K", "N", "D0", "Ls_cap", "max_len", "ld", "smart", "lib_ld", "pad", "bos", "eos", "repl", "max_steps",
+                            "T_cap", "R", "first_row", "kv_row", "Ls_new"))
+DEBUG_BSP_OPS = ("init", "admit", "fill", "prep", "select", "batches", "retire", "publish")     # ttx_debug_bsp's op, in order
+DEBUG_BSP_WORDS = 12              # int64 words of ttx_debug_bsp's host array: 8 of the BeamCounters, 4 of the BeamPoolHost
 DEBUG_BS_LIST_WORDS = 21          # int64 words of ttx_debug_bs_list's host array: 8 of the BeamCounters, 13 of the DecState
 
 DEBUG_ACCEPT_BLOCK_WORDS = 264   # int32 words of the AcceptBlk between k_accept_slots and k_accept_finish (ttx_debug_accept_block)
@@ -303,6 +317,7 @@ SYMBOLS = {
     "ttx_debug_beam_step": (C.c_int, [_VP, C.POINTER(DebugBeamStepArgs), _VP]),
     "ttx_debug_sbs_step": (C.c_int, [_VP, C.POINTER(DebugSbsStepArgs), _VP]),
     "ttx_debug_tree_cache": (C.c_int, [_VP, C.POINTER(DebugTreeCacheArgs), _VP]),
+    "ttx_debug_bsp": (C.c_int, [_VP, _I, C.POINTER(DebugBspArgs), C.POINTER(C.c_int64), _VP]),
     "ttx_debug_kvcopy": (C.c_int, [_VP, _VP, _I, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int64, _I, _I, _I, _I, _I, _VP]),
     "ttx_debug_kvcopy_split": (C.c_int, [_VP, _VP, _I, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int64, _I, _I, _I, _I, _I, _VP, _VP,
                                          C.c_int64, _VP]),

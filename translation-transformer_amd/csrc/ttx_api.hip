@@ -2869,6 +2869,75 @@ struct BeamPoolJob {
   long long src_tokens_padded = 0, admitted_rows = 0;
 };
 
+// The pool's eight bookkeeping launches (bpool_start, bpool_admit, bpool_enqueue_iter; one at a time: ttx_debug_bsp).
+static int launch_bsp_init(hipStream_t st, const BeamPoolArgs& a, int* src_of, int* cand_src_len) {
+  hipLaunchKernelGGL(k_bsp_init, dim3(64), dim3(256), 0, st, a, src_of, cand_src_len);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+static int launch_bsp_admit(hipStream_t st, const BeamPoolArgs& a, int* new_slot, int* cand_src_len, int R, int first_row) {
+  hipLaunchKernelGGL(k_bsp_admit, dim3(1), dim3(1), 0, st, a, new_slot, cand_src_len, R, first_row);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+// k_bsp_fill's operands: the pool's own arrays from `a`, the staged sources of one admission from the caller.
+static BeamPoolFillArgs bsp_fill_args(const BeamPoolArgs& a, const int* new_slot, int R, int first_row, int Ls_new, const int* tok_new,
+                                      uint8_t* src_valid, const uint8_t* valid_new, const int* drafts_new, float* memkv,
+                                      const float* memkv_new, int kv_row) {
+  BeamPoolFillArgs f{};
+  f.new_slot = new_slot; f.R = R; f.first_row = first_row;
+  f.C = a.C; f.K = a.K; f.N = a.N; f.D0 = a.D0; f.ld = a.ld; f.Ls_cap = a.Ls_cap; f.Ls_new = Ls_new; f.max_len = a.max_len;
+  f.pad = a.pad; f.bos = a.bos;
+  f.cand_next = a.cand_next; f.len_next = a.len_next; f.fin_next = a.fin_next; f.logp_next = a.logp_next; f.parent = a.parent;
+  f.parent_draft = a.parent_draft;
+  f.tok = const_cast<int*>(a.tok); f.tok_new = tok_new; f.src_valid = src_valid; f.valid_new = valid_new;
+  f.drafts_all = const_cast<int*>(a.drafts_all); f.drafts_new = drafts_new;
+  f.memkv = memkv; f.memkv_new = memkv_new; f.kv_row = kv_row; f.io = a.io;
+  return f;
+}
+
+static int launch_bsp_fill(hipStream_t st, const BeamPoolFillArgs& f) {
+  hipLaunchKernelGGL(k_bsp_fill, dim3(f.R, 1 + f.Ls_new), dim3(256), 0, st, f);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+static int launch_bsp_prep(hipStream_t st, const BeamPoolArgs& a) {
+  hipLaunchKernelGGL(k_bsp_prep, dim3(a.C * a.K), dim3(256), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+static size_t bsp_select_lds(int K, int D0) { return 2 * (size_t)K * (D0 + 1) * K * 4; }
+
+static int launch_bsp_select(ttx_session* s, hipStream_t st, const BeamPoolArgs& a) {
+  const size_t lds = bsp_select_lds(a.K, a.D0);
+  TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_bsp_select), lds, s->attr_pool_select));
+  hipLaunchKernelGGL(k_bsp_select, dim3(a.C), dim3(256), lds, st, a);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+static int launch_bsp_batches(hipStream_t st, const BeamPoolArgs& a) {
+  hipLaunchKernelGGL(k_bsp_batches, dim3(cdiv(a.C, 256)), dim3(256), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+static int launch_bsp_retire(hipStream_t st, const BeamPoolArgs& a) {
+  hipLaunchKernelGGL(k_bsp_retire, dim3(a.C), dim3(256), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+static int launch_bsp_publish(hipStream_t st, const BeamPoolArgs& a) {
+  hipLaunchKernelGGL(k_bsp_publish, dim3(cdiv(a.C, 256)), dim3(256), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
 static int bpool_start(BeamPoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_cap, const ttx_beam_params* p, const BeamPoolIo& io_host,
                        const int32_t* h_len, const int32_t* h_batch_of, const int32_t* h_given, int R_total, int n_batches) {
   const ttx_config& c = s->m->cfg;
@@ -2954,8 +3023,7 @@ static int bpool_start(BeamPoolJob& j, ttx_session* s, hipStream_t st, int C, in
   a.chosen_slot = s->bs_best_slot.as<int>(); a.chosen = s->bs_chosen.as<int64_t>();
   a.leaf_score = s->leaf_score.as<float>(); a.leaf_tok = s->leaf_tok.as<int>(); a.leaf_cnt = s->leaf_cnt.as<int>();
   a.cnt = s->bs_cnt.as<BeamCounters>(); a.io = reinterpret_cast<const BeamPoolIo*>(io_dev); a.host = dev_host; a.dev_summary = s->bp_grp.as<int>();
-  hipLaunchKernelGGL(k_bsp_init, dim3(64), dim3(256), 0, st, a, s->t_src_of.as<int>(), s->bp_cand_len.as<int>());
-  HIP_TRY(hipGetLastError());
+  TTX_TRY(launch_bsp_init(st, a, s->t_src_of.as<int>(), s->bp_cand_len.as<int>()));
   HIP_TRY(hipEventRecord(s->ev_b, st));
   j.phase = 1;
   return TTX_OK;
@@ -2970,19 +3038,10 @@ static int bpool_admit(BeamPoolJob& j, const int64_t* d_src_rows, int ld_src, in
   if (!j.smart)      // make_drafts(src[:, 1:], draft_len, N, 5, 200) (:430): independent of how far the row is padded
     TTX_TRY(launch_make_drafts<int>(st, s->tok_src.as<int>(), Ls_new, 1, R, Ls_new - 1, j.N, j.D0, j.p.eos_token, j.p.pad_token,
                                     j.p.replace_token, s->drafts_new.as<int>()));
-  hipLaunchKernelGGL(k_bsp_admit, dim3(1), dim3(1), 0, st, j.a, s->bp_new_slot.as<int>(), s->bp_cand_len.as<int>(), R, first_row);
-  HIP_TRY(hipGetLastError());
-  BeamPoolFillArgs f{};
-  f.new_slot = s->bp_new_slot.as<int>(); f.R = R; f.first_row = first_row;
-  f.C = j.C; f.K = j.K; f.N = j.N; f.D0 = j.D0; f.ld = j.gen_ld; f.Ls_cap = j.Ls_cap; f.Ls_new = Ls_new; f.max_len = j.p.max_len;
-  f.pad = j.p.pad_token; f.bos = j.p.bos_token;
-  f.cand_next = j.a.cand_next; f.len_next = j.a.len_next; f.fin_next = j.a.fin_next; f.logp_next = j.a.logp_next; f.parent = j.a.parent;
-  f.parent_draft = j.a.parent_draft;
-  f.tok = s->bp_tok.as<int>(); f.tok_new = s->tok_src.as<int>(); f.src_valid = s->src_valid.as<uint8_t>(); f.valid_new = s->valid_new.as<uint8_t>();
-  f.drafts_all = s->bs_drafts_src.as<int>(); f.drafts_new = j.smart ? nullptr : s->drafts_new.as<int>();
-  f.memkv = s->memkv.as<float>(); f.memkv_new = s->memkv_new.as<float>(); f.kv_row = kv_row; f.io = j.a.io;
-  hipLaunchKernelGGL(k_bsp_fill, dim3(R, 1 + Ls_new), dim3(256), 0, st, f);
-  HIP_TRY(hipGetLastError());
+  TTX_TRY(launch_bsp_admit(st, j.a, s->bp_new_slot.as<int>(), s->bp_cand_len.as<int>(), R, first_row));
+  TTX_TRY(launch_bsp_fill(st, bsp_fill_args(j.a, s->bp_new_slot.as<int>(), R, first_row, Ls_new, s->tok_src.as<int>(), s->src_valid.as<uint8_t>(),
+                                            s->valid_new.as<uint8_t>(), j.smart ? nullptr : s->drafts_new.as<int>(), s->memkv.as<float>(),
+                                            s->memkv_new.as<float>(), kv_row)));
   j.admitted_rows += R;
   j.admitted_since += R;
   j.src_tokens_padded += (long long)R * Ls_new;
@@ -2993,8 +3052,7 @@ static int bpool_enqueue_iter(const BeamPoolJob& j, int variant) {
   ttx_session* s = j.s;
   hipStream_t st = j.st;
   const int dl = j.D0, MC = j.MC;
-  hipLaunchKernelGGL(k_bsp_prep, dim3(MC), dim3(256), 0, st, j.a);
-  HIP_TRY(hipGetLastError());
+  TTX_TRY(launch_bsp_prep(st, j.a));
   // ONE cache buffer and a candidate -> slot map (k_bsp_select): most children append in their parent's slot, few copy; fresh
   // candidates (parent -1) have nothing to inherit
   TTX_TRY(enqueue_tree_cache(s, st, MC, j.Lc, 0, 0, j.a.cache_slot_parent, j.a.cache_slot, j.N, dl));
@@ -3003,14 +3061,10 @@ static int bpool_enqueue_iter(const BeamPoolJob& j, int variant) {
   k.cache_slot = j.a.cache_slot; k.src_len = s->bp_cand_len.as<int>();
   TTX_TRY(run_step(s, st, k, key_capacity(j.p.max_len, j.p.max_len)));
   TTX_TRY(enqueue_hits_leaves(s, st, MC, MC, j.N, dl, j.K, j.p, j.smart, &j.a, false));
-  const size_t lds = 2 * (size_t)j.K * (dl + 1) * j.K * 4;
-  TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_bsp_select), lds, s->attr_pool_select));
-  hipLaunchKernelGGL(k_bsp_select, dim3(j.C), dim3(256), lds, st, j.a);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_bsp_batches, dim3(cdiv(j.C, 256)), dim3(256), 0, st, j.a);
-  hipLaunchKernelGGL(k_bsp_retire, dim3(j.C), dim3(256), 0, st, j.a);
-  hipLaunchKernelGGL(k_bsp_publish, dim3(cdiv(j.C, 256)), dim3(256), 0, st, j.a);
-  HIP_TRY(hipGetLastError());
+  TTX_TRY(launch_bsp_select(s, st, j.a));
+  TTX_TRY(launch_bsp_batches(st, j.a));
+  TTX_TRY(launch_bsp_retire(st, j.a));
+  TTX_TRY(launch_bsp_publish(st, j.a));
   return TTX_OK;
 }
 
@@ -4302,6 +4356,101 @@ extern "C" int ttx_debug_tree_cache(ttx_session* s, const ttx_debug_tree_cache_a
   ca.qkv_prev = a->d_qkv_prev; ca.qkv_layer_stride = a->qkv_layer_stride; ca.prev_slot_of = a->d_prev_slot_of;
   ca.prev_N = a->prev_N; ca.prev_D = a->prev_D; ca.d = a->d; ca.slot_parent = a->d_slot_parent; ca.slot_self = a->d_slot_self;
   return dbg_launched(launch_tree_cache(st, a->max_cand, a->layers, ca), st);
+}
+
+// ---- the pool's bookkeeping kernels, one launch per call through launch_bsp_* ---------------------------------------------------
+extern "C" int ttx_debug_bsp(ttx_session* s, int op, const ttx_debug_bsp_args* a, int64_t* words, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const std::string w = "ttx_debug_bsp";
+  enum { OP_INIT, OP_ADMIT, OP_FILL, OP_PREP, OP_SELECT, OP_BATCHES, OP_RETIRE, OP_PUBLISH, OP_COUNT };
+  if (!s || !a || !words) return fail(TTX_ERR_INVALID, "null argument to " + w);
+  if (op < 0 || op >= OP_COUNT) return fail(TTX_ERR_INVALID, w + ": op is 0 (init) .. 7 (publish)");
+  if (!a->d_row_of || !a->d_slot_batch || !a->d_src_acc || !a->d_src_state || !a->d_tok || (!a->smart && !a->d_drafts_all) || !a->d_bat_id ||
+      !a->d_bat_iter || !a->d_bat_dl || !a->d_bat_grp || !a->d_bat_live || !a->d_bat_nfin || !a->d_bat_longest_fin || !a->d_bat_longest_cur ||
+      !a->d_bat_state || !a->d_bat_given || !a->d_cand_next || !a->d_len_next || !a->d_fin_next || !a->d_logp_next || !a->d_parent ||
+      !a->d_parent_draft || !a->d_gen || !a->d_front || !a->d_len || !a->d_active || !a->d_finished || !a->d_live || !a->d_logp ||
+      !a->d_per_cand || !a->d_drafts32 || !a->d_cand_dl || !a->d_cand_batch || !a->d_cache_slot || !a->d_cache_slot_parent ||
+      !a->d_chosen_slot || !a->d_chosen || !a->d_leaf_score || !a->d_leaf_tok || !a->d_leaf_cnt || !a->d_dev_summary)
+    return fail(TTX_ERR_INVALID, w + ": an array of the pool's argument block is null");
+  if (!a->d_out || !a->d_trace_len || !a->d_summary || !a->d_len_all || !a->d_batch_all || !a->d_given_all)
+    return fail(TTX_ERR_INVALID, w + ": a caller-side array is null");
+  if (op == OP_INIT && (!a->d_src_of || !a->d_cand_src_len)) return fail(TTX_ERR_INVALID, w + ": init needs src_of and cand_src_len");
+  if (op == OP_ADMIT && (!a->d_new_slot || !a->d_cand_src_len)) return fail(TTX_ERR_INVALID, w + ": admit needs new_slot and cand_src_len");
+  if (op == OP_FILL && (!a->d_new_slot || !a->d_tok_new || !a->d_valid_new || !a->d_src_valid || !a->d_memkv || !a->d_memkv_new))
+    return fail(TTX_ERR_INVALID, w + ": fill needs new_slot, tok_new, valid_new, src_valid, memkv and memkv_new");
+  if (a->C < 1 || a->K < 1 || a->N < 1 || a->D0 < 0 || a->Ls_cap < 1 || a->max_len < 1 || a->ld < 1 || a->T_cap < 1 || a->max_steps < 0)
+    return fail(TTX_ERR_INVALID, w + ": C, K, N, Ls_cap, max_len, ld and T_cap must be positive, D0 and max_steps >= 0");
+  if (a->C > 1024 || a->K > NUC_MAX_KEEP || a->N > BS_MAX_SLOTS) return fail(TTX_ERR_INVALID, w + ": C <= 1024, K <= 32 and N <= 64");
+  if ((size_t)a->K * (a->D0 + 1) > 1023 || bsp_select_lds(a->K, a->D0) > 150 * 1024)
+    return fail(TTX_ERR_INVALID, w + ": too many leaves per source for the selection kernel's LDS image");
+  if (a->ld < a->max_len + a->D0 + 2) return fail(TTX_ERR_INVALID, w + ": ld must cover max_len + D0 + 2 columns");
+  if (op == OP_ADMIT || op == OP_FILL) {
+    if (a->R < 1 || a->first_row < 0) return fail(TTX_ERR_INVALID, w + ": R must be positive and first_row >= 0");
+    if (a->R > a->C) return fail(TTX_ERR_INVALID, w + ": more new sources than the pool has slots");
+  }
+  if (op == OP_FILL) {
+    if (a->Ls_new < 1 || a->Ls_new > a->Ls_cap) return fail(TTX_ERR_INVALID, w + ": Ls_new must lie in [1, Ls_cap]");
+    if (a->kv_row < 4 || (a->kv_row & 3)) return fail(TTX_ERR_INVALID, w + ": kv_row must be a positive multiple of 4");
+    if (!dbg_aligned16(a->d_memkv) || !dbg_aligned16(a->d_memkv_new)) return fail(TTX_ERR_INVALID, w + ": memkv operands must be 16-byte aligned");
+  }
+  HIP_TRY(hipSetDevice(s->m->device));
+  if (!s->bp_host && hipHostMalloc((void**)&s->bp_host, sizeof(BeamPoolHost), hipHostMallocMapped) != hipSuccess)
+    return fail(TTX_ERR_NOMEM, "hipHostMalloc failed");
+  BeamPoolHost* dev_host = nullptr;
+  HIP_TRY(hipHostGetDevicePointer((void**)&dev_host, (void*)s->bp_host, 0));
+  HIP_TRY(hipStreamSynchronize(st));                    // nothing in flight reads the pinned words while the image goes in
+  s->bp_host->steps_done = (int)words[8]; s->bp_host->n_live = (int)words[9]; s->bp_host->n_running = (int)words[10];
+  s->bp_host->error = (int)words[11];
+  struct Image { BeamCounters cnt; BeamPoolIo io; };
+  Image* dev = nullptr;
+  HIP_TRY(hipMalloc((void**)&dev, sizeof(Image)));
+  Image h{};
+  h.cnt.model_calls = words[0]; h.cnt.input_lines = words[1]; h.cnt.running_rows = words[2]; h.cnt.verified_positions = words[3];
+  h.cnt.executed_positions = words[4]; h.cnt.kv_prefix_positions = words[5]; h.cnt.running_cands = words[6]; h.cnt.max_group = (int)words[7];
+  h.io.out = a->d_out; h.io.trace_len = a->d_trace_len; h.io.summary = a->d_summary; h.io.len_all = a->d_len_all;
+  h.io.batch_all = a->d_batch_all; h.io.given_all = a->d_given_all; h.io.T_cap = a->T_cap;
+  hipError_t err = hipMemcpyAsync(dev, &h, sizeof(Image), hipMemcpyHostToDevice, st);
+  int rc = TTX_OK;
+  if (err == hipSuccess) {
+    BeamPoolArgs p{};
+    p.C = a->C; p.K = a->K; p.N = a->N; p.D0 = a->D0; p.Ls_cap = a->Ls_cap; p.max_len = a->max_len; p.ld = a->ld;
+    p.smart = a->smart ? 1 : 0; p.lib_ld = a->lib_ld; p.pad = a->pad; p.bos = a->bos; p.eos = a->eos; p.repl = a->repl; p.max_steps = a->max_steps;
+    p.row_of = a->d_row_of; p.slot_batch = a->d_slot_batch; p.src_acc = a->d_src_acc; p.src_state = a->d_src_state;
+    p.tok = a->d_tok; p.drafts_all = a->d_drafts_all;
+    p.bat_id = a->d_bat_id; p.bat_iter = a->d_bat_iter; p.bat_dl = a->d_bat_dl; p.bat_grp = a->d_bat_grp; p.bat_live = a->d_bat_live;
+    p.bat_nfin = a->d_bat_nfin; p.bat_longest_fin = a->d_bat_longest_fin; p.bat_longest_cur = a->d_bat_longest_cur;
+    p.bat_state = a->d_bat_state; p.bat_given = a->d_bat_given;
+    p.cand_next = a->d_cand_next; p.len_next = a->d_len_next; p.fin_next = a->d_fin_next; p.logp_next = a->d_logp_next;
+    p.parent = a->d_parent; p.parent_draft = a->d_parent_draft;
+    p.gen = a->d_gen; p.front = a->d_front; p.len = a->d_len; p.active = a->d_active; p.finished = a->d_finished; p.live = a->d_live;
+    p.logp = a->d_logp; p.per_cand = a->d_per_cand; p.drafts32 = a->d_drafts32; p.cand_dl = a->d_cand_dl; p.cand_batch = a->d_cand_batch;
+    p.cache_slot = a->d_cache_slot; p.cache_slot_parent = a->d_cache_slot_parent;
+    p.chosen_slot = a->d_chosen_slot; p.chosen = a->d_chosen; p.leaf_score = a->d_leaf_score; p.leaf_tok = a->d_leaf_tok; p.leaf_cnt = a->d_leaf_cnt;
+    p.cnt = &dev->cnt; p.io = &dev->io; p.host = dev_host; p.dev_summary = a->d_dev_summary;
+    switch (op) {
+      case OP_INIT: rc = launch_bsp_init(st, p, a->d_src_of, a->d_cand_src_len); break;
+      case OP_ADMIT: rc = launch_bsp_admit(st, p, a->d_new_slot, a->d_cand_src_len, a->R, a->first_row); break;
+      case OP_FILL:
+        rc = launch_bsp_fill(st, bsp_fill_args(p, a->d_new_slot, a->R, a->first_row, a->Ls_new, a->d_tok_new, a->d_src_valid, a->d_valid_new,
+                                               a->d_drafts_new, a->d_memkv, a->d_memkv_new, a->kv_row));
+        break;
+      case OP_PREP: rc = launch_bsp_prep(st, p); break;
+      case OP_SELECT: rc = launch_bsp_select(s, st, p); break;
+      case OP_BATCHES: rc = launch_bsp_batches(st, p); break;
+      case OP_RETIRE: rc = launch_bsp_retire(st, p); break;
+      default: rc = launch_bsp_publish(st, p); break;
+    }
+  }
+  if (err == hipSuccess && rc == TTX_OK) err = hipMemcpyAsync(&h, dev, sizeof(Image), hipMemcpyDeviceToHost, st);
+  const hipError_t esync = hipStreamSynchronize(st);
+  (void)hipFree(dev);
+  TTX_TRY(rc);
+  HIP_TRY(err);
+  HIP_TRY(esync);
+  words[0] = h.cnt.model_calls; words[1] = h.cnt.input_lines; words[2] = h.cnt.running_rows; words[3] = h.cnt.verified_positions;
+  words[4] = h.cnt.executed_positions; words[5] = h.cnt.kv_prefix_positions; words[6] = h.cnt.running_cands; words[7] = h.cnt.max_group;
+  words[8] = s->bp_host->steps_done; words[9] = s->bp_host->n_live; words[10] = s->bp_host->n_running; words[11] = s->bp_host->error;
+  return TTX_OK;
 }
 
 static int kvcopy_debug(const char* who, ttx_session* s, const int32_t* d_rec, int n_copy, const float* d_qkv, int64_t qkv_layer_stride,

@@ -543,6 +543,26 @@ class NativeTransformer:
                          dict(max_cand=max_cand, layers=layers, prev_N=prev_n, prev_D=prev_d, d=d, cache_layer_stride=cache_layer_stride,
                               cache_seq_stride=cache_seq_stride, qkv_layer_stride=qkv_layer_stride), arrays)
 
+    def debug_bsp(self, op: str, words, *, C_: int, K: int, n: int, D0: int, Ls_cap: int, max_len: int, ld: int, smart: bool, lib_ld: int,
+                  pad: int, bos: int, eos: int, repl: int, max_steps: int, T_cap: int, R: int = 0, first_row: int = 0, kv_row: int = 0,
+                  Ls_new: int = 0, **arrays) -> list:
+        """One launch of a bookkeeping kernel of the beam-speculative batch pool (ttx_debug_bsp); ``op`` one of
+        _native.DEBUG_BSP_OPS, ``C_`` the pool's source slots.  ``words``: the 8 BeamCounters words and the 4 BeamPoolHost words
+        on entry; returns the 12 as the kernel left them."""
+        w = (C.c_int64 * N.DEBUG_BSP_WORDS)(*[int(v) for v in words])
+        scalars = dict(C=C_, K=K, N=n, D0=D0, Ls_cap=Ls_cap, max_len=max_len, ld=ld, smart=smart, lib_ld=lib_ld, pad=pad, bos=bos, eos=eos,
+                       repl=repl, max_steps=max_steps, T_cap=T_cap, R=R, first_row=first_row, kv_row=kv_row, Ls_new=Ls_new)
+        a = N.DebugBspArgs()
+        for name in N.DebugBspArgs.POINTERS:
+            t = arrays.pop(name[2:], None)
+            setattr(a, name, None if t is None else t.data_ptr())
+        assert not arrays, f"unknown operands {sorted(arrays)}"
+        for name, v in scalars.items():
+            setattr(a, name, int(v))
+        code = op if isinstance(op, int) else N.DEBUG_BSP_OPS.index(op)
+        N.check(self._lib.ttx_debug_bsp(self._session, code, C.byref(a), w, self._stream()))
+        return [int(v) for v in w]
+
     def debug_kvcopy(self, rec: torch.Tensor, n_copy: int, qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
                      n: int, d: int, width: int, B: int) -> None:
         """One k_kvcopy launch (ttx_debug_kvcopy): ``rec`` int32 [B, 5], ``qkv`` fp32 [Ld, B * (1 + n*d), 3 * width], the caches
