@@ -564,7 +564,8 @@ int ttx_beam_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const
  *   level; stats->model_calls says how many levels are valid.  stats->out_width is the number of columns the loop filled.
  * Cost, measured on one MI355X (4+4 model, 32 sources, max_len 200): 1.8 % (K = 5) and 2.2 % (K = 10) more per
  * decoder step than ttx_beam_generate with the same K, and 8.8 % / 11.0 % more per call, since the sampled rows run longer.
- * Limits: no top-k / top-p filter, no forced prefix, no pooled generate_many.  TTX_ERR_INVALID with nothing launched: max_len <= 1,
+ * Limits: no pooled generate_many (the top-k / top-p filter and forced prefixes are ttx_sbs_generate_ex below).  TTX_ERR_INVALID with
+ * nothing launched: max_len <= 1,
  * beam_size outside [1, min(32, vocab_size)], vocab_size > 1024, beam_size * vocab_size * 4 > 150 KB, a temperature that is not
  * finite or not > 0, a trace with a NULL array, and everything else ttx_beam_generate refuses. */
 typedef struct ttx_sbs_params {
@@ -580,6 +581,43 @@ typedef struct ttx_sbs_trace {
 int ttx_sbs_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sbs_params* p,
                      int64_t* d_out, float* d_logp, float* d_gumbel, const ttx_sbs_trace* trace_or_null,
                      ttx_beam_search_stats* stats, void* stream);
+
+/* Stochastic beam search under a top-k / top-p filter and / or forced target prefixes: ttx_sbs_generate with a per-parent token
+ * mask in front of its rule (k_sbs_step_masked, csrc/ttx_sbs.hip.h).  A masked token behaves exactly like a -inf logit, which
+ * steps 5 and 7 above already define.  Per unfinished parent k of source b at position pos, before step 2:
+ *   Forced position (1 <= pos <= h_prefix_len[b]).  tok = d_prefix[b][pos - 1], an id outside [0, V) read as 0 (as the prompted
+ *     samplers read theirs).  The child tok has phi' = phi_k and G' = G_k exactly; every other child of the parent is -inf.  The
+ *     logits are not read and no Philox block is formed.  A forced token thus costs no log-probability: logp is the
+ *     log-probability of the completion given source and prefix, and the rows are a sample without replacement from that
+ *     conditional distribution.  A forced EOS or PAD finishes the row as any EOS or PAD does.
+ *   Free position, filter on (top_k != 0 or top_p < 1; top_p < 1 with top_k = 0 runs with top_k = 32).  The kept set is the
+ *     sampler's on the bits (ttx_sample_generate, step 4: ranks of y best first, equal values the lower id first, rank i kept while
+ *     the softmax mass ranked above it is < top_p and i < top_k, rank 0 always; at most 32 tokens).  A token outside it has
+ *     y_v = -inf.  Steps 2-5 run unchanged on that row, m, z and Z in the order fixed by V alone, masked ids contributing
+ *     expf(-inf) = 0: lp is renormalised over the kept set, so the search samples without replacement from the sequence
+ *     distribution the filtered ttx_sample_generate draws from.  Philox counters stay keyed by the token id v, not by the rank in
+ *     the kept set: a kept token's uniform is the one the unfiltered call forms for it.  A kept set of one token is a mask of one
+ *     token, as a forced position is: that child has phi' = phi_k and G' = G_k exactly.
+ *   Steps 6-8 are unchanged.  Masked children are -inf children: selected only when fewer than K finite ones exist, by ascending
+ *     flat index, finished, with logp = gumbel = -inf.
+ * Consequences (exact): a kept set of every token (V <= 32, top_k = 32, top_p = 1) gives ttx_sbs_generate's outputs bit for bit;
+ * top_k = 1 gives the greedy row at rank 0 with logp == gumbel == 0.0f and ranks >= 1 at -inf, finished; with f NULL (or top_k = 0,
+ * top_p = 1) and no non-empty prefix the call IS ttx_sbs_generate, launch for launch; every finite row of a prompted call is BOS,
+ * the prefix, a completion; gumbel of rank 0 is 0.0f; rows are pairwise distinct; K returns the first K rows of K' > K; the output
+ * depends on the source, its prefix, its key, the seed, the temperature, the filter and K only.
+ *   f_or_null: the filter; d_prefix int64 [B, ld_prefix] without BOS and h_prefix_len HOST int32 [B] (NULL: no prefixes), as for
+ *   ttx_sample_generate_prefix.  Everything else as for ttx_sbs_generate.
+ * TTX_ERR_INVALID with nothing launched: top_k outside [0, 32], top_p outside (0, 1], a prefix length outside [0, max_len - 1] or
+ * above ld_prefix, a non-zero length with d_prefix NULL, and everything ttx_sbs_generate refuses.
+ * Cost: DESIGN.md §23.  Limits: no pooled generate_many. */
+typedef struct ttx_sbs_filter {
+  int32_t top_k;                         /* 0: off, else 1..32 */
+  float   top_p;                         /* (0, 1]; 1: off */
+} ttx_sbs_filter;
+int ttx_sbs_generate_ex(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sbs_params* p,
+                        const ttx_sbs_filter* f_or_null, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
+                        int64_t* d_out, float* d_logp, float* d_gumbel, const ttx_sbs_trace* trace_or_null,
+                        ttx_beam_search_stats* stats, void* stream);
 
 /* Several batches in flight on one GPU (the scheduling SURVEY.md §8(f) #1 names; the reference's predict loop
  * is strictly one batch at a time, src/model/lightning_model.py:209-212).  Batch i is decoded on
@@ -988,6 +1026,13 @@ typedef struct ttx_debug_sbs_step_args {
 /* ttx_debug_sbs_step: k_sbs_step on B workgroups, operands as for ttx_debug_beam_step with phi, G, the keys, the position, the
  * seed and inv_T added.  Also refused: beam or K above 32, K > beam * V, width >= ld, pos < 1, inv_T not finite or not > 0. */
 int ttx_debug_sbs_step(ttx_session* s, const ttx_debug_sbs_step_args* a, void* stream);
+/* ttx_debug_sbs_step_ex: ONE launch of k_sbs_step_masked on the same operands (whatever top_k / top_p / pfx say: the production
+ * loop launches it only under a filter or a prefix).  top_k, top_p as ttx_sbs_filter (top_p < 1 with top_k = 0 runs with 32);
+ * pfx NULL or the table by source (d_len, d_src int32 [B]): source b is forced at a->pos when a->pos <= d_len[b].  waves: 0 the
+ * production choice (4 up to beam 4, 8 up to beam 8, else 16), or 4, 8, 16: the outputs do not depend on it.  Also refused: top_k
+ * outside [0, 32], top_p outside (0, 1], another wave count, a table outside its bounds, pos inside a prefix but beyond pfx->ld. */
+int ttx_debug_sbs_step_ex(ttx_session* s, const ttx_debug_sbs_step_args* a, int top_k, float top_p, const ttx_debug_prefix* pfx,
+                          int waves, void* stream);
 
 typedef struct ttx_debug_tree_cache_args {
   const int32_t* d_len; const int32_t* d_parent; const int32_t* d_parent_draft; const int32_t* d_prev_len; const uint8_t* d_active;

@@ -94,6 +94,11 @@ class SbsParams(C.Structure):
                 ("bos_token", C.c_int32), ("eos_token", C.c_int32), ("seed", C.c_uint64)]
 
 
+class SbsFilter(C.Structure):
+    """ttx_sbs_filter: top_k 0 and top_p 1 are off."""
+    _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float)]
+
+
 class SbsTrace(C.Structure):
     """ttx_sbs_trace: device arrays [max_len - 1, B, K] of parent rank, token, phi' and G' per level."""
     _fields_ = [(n, C.c_void_p) for n in ("d_parent", "d_token", "d_phi", "d_g")]
@@ -270,6 +275,8 @@ SYMBOLS = {
     "ttx_beam_generate": (C.c_int, [_VP, _VP, _I, _I, C.POINTER(BeamSearchParams), _VP, C.POINTER(BeamSearchStats), _VP]),
     "ttx_sbs_generate": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SbsParams), _VP, _VP, _VP, C.POINTER(SbsTrace),
                                   C.POINTER(BeamSearchStats), _VP]),
+    "ttx_sbs_generate_ex": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SbsParams), C.POINTER(SbsFilter), _VP, _I, _VP, _VP, _VP, _VP,
+                                     C.POINTER(SbsTrace), C.POINTER(BeamSearchStats), _VP]),
     "ttx_nucleus_mask": (C.c_int, [_VP, _VP, _I, _I, C.c_float, _I, C.c_float, _VP, _VP]),
     "ttx_accepted_lengths": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, C.c_float, _I, _VP, _VP]),
     "ttx_ragged_topk": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
@@ -316,6 +323,7 @@ SYMBOLS = {
     "ttx_debug_beam_select": (C.c_int, [_VP, C.POINTER(DebugBeamSelectArgs), _VP]),
     "ttx_debug_beam_step": (C.c_int, [_VP, C.POINTER(DebugBeamStepArgs), _VP]),
     "ttx_debug_sbs_step": (C.c_int, [_VP, C.POINTER(DebugSbsStepArgs), _VP]),
+    "ttx_debug_sbs_step_ex": (C.c_int, [_VP, C.POINTER(DebugSbsStepArgs), _I, C.c_float, C.POINTER(DebugPrefix), _I, _VP]),
     "ttx_debug_tree_cache": (C.c_int, [_VP, C.POINTER(DebugTreeCacheArgs), _VP]),
     "ttx_debug_bsp": (C.c_int, [_VP, _I, C.POINTER(DebugBspArgs), C.POINTER(C.c_int64), _VP]),
     "ttx_debug_kvcopy": (C.c_int, [_VP, _VP, _I, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int64, _I, _I, _I, _I, _I, _VP]),

@@ -2704,6 +2704,29 @@ static int launch_sbs_step(ttx_session* s, hipStream_t st, const SbsStepArgs& sa
   return TTX_OK;
 }
 
+// The waves per source k_sbs_step_masked runs with: a wave owns whole parent rows, and a filtered row costs up to 32 dependent
+// selection rounds, so wider beams get more waves (DESIGN.md §23 has the measurement).
+static int sbs_masked_waves(int beam) { return beam <= 4 ? 4 : (beam <= 8 ? 8 : SBS_MASKED_MAX_WAVES); }
+
+template <int VPL>
+static int launch_sbs_step_masked_vpl(ttx_session* s, hipStream_t st, const SbsStepArgs& sa, int waves, bool& attr) {
+  const size_t lds = (size_t)sa.beam * sa.V * 4;
+  TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_sbs_step_masked<VPL>), lds, attr));
+  hipLaunchKernelGGL((k_sbs_step_masked<VPL>), dim3(sa.B), dim3(64 * waves), lds, st, sa);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+// waves 0: production's choice.
+static int launch_sbs_step_masked(ttx_session* s, hipStream_t st, const SbsStepArgs& sa, int waves = 0) {
+  if (waves == 0) waves = sbs_masked_waves(sa.beam);
+  if (sa.V <= 64) return launch_sbs_step_masked_vpl<1>(s, st, sa, waves, s->attr_sbs_step_masked[0]);
+  if (sa.V <= 128) return launch_sbs_step_masked_vpl<2>(s, st, sa, waves, s->attr_sbs_step_masked[1]);
+  if (sa.V <= 256) return launch_sbs_step_masked_vpl<4>(s, st, sa, waves, s->attr_sbs_step_masked[2]);
+  if (sa.V <= 512) return launch_sbs_step_masked_vpl<8>(s, st, sa, waves, s->attr_sbs_step_masked[3]);
+  return launch_sbs_step_masked_vpl<16>(s, st, sa, waves, s->attr_sbs_step_masked[4]);
+}
+
 static int beam_enqueue_iter(const BeamJob& j, bool first, int cur) {
   ttx_session* s = j.s;
   hipStream_t st = j.st;
@@ -3190,6 +3213,10 @@ struct BeamSearchJob {
   const int64_t* row_keys = nullptr;
   float* d_logp = nullptr; float* d_gumbel = nullptr;
   ttx_sbs_trace trace{};
+  // ttx_sbs_generate_ex with a filter on or a non-empty prefix: k_sbs_step_masked instead (masked false: k_sbs_step, launch for launch)
+  bool masked = false;
+  int top_k = 0; float top_p = 1.f;
+  PrefixTab pfx{};
 };
 
 // Everything of the call behind the argument check: the reference's asserts and this library's limits, the workspaces, the
@@ -3268,7 +3295,12 @@ static int bsearch_launch_iter(BeamSearchJob& j) {
       const size_t at = (size_t)j.launched * j.B * j.K;
       sa.tr_parent = j.trace.d_parent + at; sa.tr_token = j.trace.d_token + at; sa.tr_phi = j.trace.d_phi + at; sa.tr_g = j.trace.d_g + at;
     }
-    TTX_TRY(launch_sbs_step(s, st, sa));
+    if (j.masked) {
+      sa.top_k = j.top_k; sa.top_p = j.top_p; sa.pfx = j.pfx;
+      TTX_TRY(launch_sbs_step_masked(s, st, sa));
+    } else {
+      TTX_TRY(launch_sbs_step(s, st, sa));
+    }
     hipLaunchKernelGGL(k_bs_publish, dim3(1), dim3(64), 0, st, s->beam_summary.as<int>(), j.dev_host, s->bs_cnt.as<BeamCounters>());
     HIP_TRY(hipGetLastError());
     ++j.launched;
@@ -3340,9 +3372,10 @@ extern "C" int ttx_beam_generate(ttx_session* s, const int64_t* d_src, int B, in
 }
 
 // Stochastic beam search: the standard beam loop above with k_sbs_step (csrc/ttx_sbs.hip.h) where it launches k_beam_step.
-extern "C" int ttx_sbs_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sbs_params* p,
-                                int64_t* d_out, float* d_logp, float* d_gumbel, const ttx_sbs_trace* trace, ttx_beam_search_stats* stats,
-                                void* stream) {
+// ttx_sbs_generate and ttx_sbs_generate_ex: one body; a call with no filter and no prefix is the plain one, launch for launch.
+static int sbs_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sbs_params* p,
+                        int64_t* d_out, float* d_logp, float* d_gumbel, const ttx_sbs_trace* trace, ttx_beam_search_stats* stats,
+                        void* stream, const ttx_sbs_filter* f, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len) {
   if (!s || !d_src || !p || !d_out || !d_logp || !d_gumbel || !stats || B <= 0 || Ls <= 1)
     return fail(TTX_ERR_INVALID, "bad argument to ttx_sbs_generate");
   const int V = s->m->cfg.vocab_size;
@@ -3355,13 +3388,37 @@ extern "C" int ttx_sbs_generate(ttx_session* s, const int64_t* d_src, int B, int
   if (!(inv_T > 0.0f) || !std::isfinite(inv_T)) return fail(TTX_ERR_INVALID, "ttx_sbs_generate: 1 / temperature is not a positive finite fp32");
   if (trace && (!trace->d_parent || !trace->d_token || !trace->d_phi || !trace->d_g))
     return fail(TTX_ERR_INVALID, "ttx_sbs_generate: a trace needs all four arrays");
+  int top_k = 0;
+  float top_p = 1.0f;
+  if (f) {
+    if (f->top_k < 0 || f->top_k > SAMPLE_MAX_KEEP) return fail(TTX_ERR_INVALID, "ttx_sbs_generate_ex: top_k must be 0 or in [1, 32]");
+    if (!(f->top_p > 0.0f) || !(f->top_p <= 1.0f)) return fail(TTX_ERR_INVALID, "ttx_sbs_generate_ex: top_p must be in (0, 1]");
+    top_p = f->top_p;
+    top_k = (f->top_k == 0 && f->top_p < 1.0f) ? SAMPLE_MAX_KEEP : f->top_k;      // as the sampler runs a top_p alone
+  }
+  SampleSetup pre{};
+  TTX_TRY(prefix_validate("ttx_sbs_generate_ex", d_prefix, ld_prefix, h_prefix_len, B, p->max_len, &pre));
+  const bool masked = top_k > 0 || pre.prompted;
   ttx_beam_search_params bp{};
   bp.max_len = p->max_len; bp.beam_size = p->beam_size; bp.pad_token = p->pad_token; bp.bos_token = p->bos_token; bp.eos_token = p->eos_token;
   BeamSearchJob j;
   const auto start = [&](int) -> int {
-    TTX_TRY(bsearch_start(j, s, s->own_stream, d_src, B, Ls, &bp, d_out, true));
+    hipStream_t st = s->own_stream;
+    if (pre.prompted) {                 // sized before bsearch_start settles which graphs are current
+      TTX_TRY(ensure(s->pfx_tok, (size_t)B * p->max_len * 4, st));
+      TTX_TRY(ensure(s->pfx_len_src, (size_t)B * 4, st));
+      TTX_TRY(ensure(s->smp_src_of, (size_t)B * 4, st));
+    }
+    TTX_TRY(bsearch_start(j, s, st, d_src, B, Ls, &bp, d_out, true));
     j.inv_T = inv_T; j.seed = p->seed; j.row_keys = d_row_keys; j.d_logp = d_logp; j.d_gumbel = d_gumbel;
     if (trace) j.trace = *trace;
+    j.masked = masked; j.top_k = top_k; j.top_p = top_p;
+    if (pre.prompted) {                 // the table by source: int32 [B][max_len], the lengths, and every source's own row of it
+      TTX_TRY(prefix_upload(s, st, pre, p->max_len, p->pad_token));
+      hipLaunchKernelGGL(k_sbs_prefix_src, dim3(cdiv(B, 256)), dim3(256), 0, st, s->smp_src_of.as<int>(), B);
+      HIP_TRY(hipGetLastError());
+      j.pfx = PrefixTab{s->pfx_tok.as<int>(), p->max_len, s->pfx_len_src.as<int>(), s->smp_src_of.as<int>()};
+    }
     return bsearch_launch_iter(j);
   };
   const auto turn = [&](int) -> int {
@@ -3376,6 +3433,20 @@ extern "C" int ttx_sbs_generate(ttx_session* s, const int64_t* d_src, int B, int
     return TURN_FINISHED;
   };
   return drive_sessions(&s, 1, false, stream, start, turn);
+}
+
+extern "C" int ttx_sbs_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sbs_params* p,
+                                int64_t* d_out, float* d_logp, float* d_gumbel, const ttx_sbs_trace* trace, ttx_beam_search_stats* stats,
+                                void* stream) {
+  return sbs_generate(s, d_src, B, Ls, d_row_keys, p, d_out, d_logp, d_gumbel, trace, stats, stream, nullptr, nullptr, 0, nullptr);
+}
+
+extern "C" int ttx_sbs_generate_ex(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sbs_params* p,
+                                   const ttx_sbs_filter* f_or_null, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
+                                   int64_t* d_out, float* d_logp, float* d_gumbel, const ttx_sbs_trace* trace,
+                                   ttx_beam_search_stats* stats, void* stream) {
+  return sbs_generate(s, d_src, B, Ls, d_row_keys, p, d_out, d_logp, d_gumbel, trace, stats, stream, f_or_null, d_prefix, ld_prefix,
+                      h_prefix_len);
 }
 
 // Parity instrumentation: the verify step selected by ttx_gen_params.want_logits (1-based step number) of the most
@@ -4305,22 +4376,22 @@ extern "C" int ttx_debug_beam_step(ttx_session* s, const ttx_debug_beam_step_arg
   return dbg_launched(launch_beam_step(s, st, sa), st);
 }
 
-extern "C" int ttx_debug_sbs_step(ttx_session* s, const ttx_debug_sbs_step_args* a, void* stream) {
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (!s || !a) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_sbs_step");
+// The operands of a k_sbs_step / k_sbs_step_masked debug launch, checked, as the kernels' argument block.
+static int sbs_debug_args(const char* who_c, ttx_session* s, const ttx_debug_sbs_step_args* a, SbsStepArgs* out) {
+  const std::string who(who_c);
+  if (!s || !a) return fail(TTX_ERR_INVALID, "null argument to " + who);
   if (!a->d_logits || !a->d_slot_of || !a->d_finished || !a->d_phi || !a->d_g || !a->d_gen || !a->d_new_cand || !a->d_new_phi || !a->d_new_g ||
       !a->d_parent || !a->d_new_len || !a->d_new_finished || !a->d_parent_draft || !a->d_summary)
-    return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step: a required array is null");
+    return fail(TTX_ERR_INVALID, who + ": a required array is null");
   if (!a->d_tr_parent != !a->d_tr_token || !a->d_tr_parent != !a->d_tr_phi || !a->d_tr_parent != !a->d_tr_g)
-    return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step: the four trace arrays come together");
+    return fail(TTX_ERR_INVALID, who + ": the four trace arrays come together");
   if (a->B < 1 || a->beam < 1 || a->beam > SBS_MAX_BEAM || a->K < 1 || a->K > SBS_MAX_BEAM || a->V < 1 || a->V > SBS_MAX_V)
-    return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step: B >= 1, beam and K in [1, 32] and V in [1, 1024]");
-  if ((size_t)a->K > (size_t)a->beam * a->V) return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step: K exceeds the beam * V children");
-  if ((size_t)a->beam * a->V * 4 > 150 * 1024) return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step: beam x vocabulary beyond the kernel's LDS image");
-  if (a->width < 1 || a->width >= a->ld) return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step: width must lie in [1, ld)");
-  if (a->pos < 1) return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step: pos starts at 1");
-  if (!(a->inv_T > 0.0f) || !std::isfinite(a->inv_T)) return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step: inv_T must be finite and > 0");
-  HIP_TRY(hipSetDevice(s->m->device));
+    return fail(TTX_ERR_INVALID, who + ": B >= 1, beam and K in [1, 32] and V in [1, 1024]");
+  if ((size_t)a->K > (size_t)a->beam * a->V) return fail(TTX_ERR_INVALID, who + ": K exceeds the beam * V children");
+  if ((size_t)a->beam * a->V * 4 > 150 * 1024) return fail(TTX_ERR_INVALID, who + ": beam x vocabulary beyond the kernel's LDS image");
+  if (a->width < 1 || a->width >= a->ld) return fail(TTX_ERR_INVALID, who + ": width must lie in [1, ld)");
+  if (a->pos < 1) return fail(TTX_ERR_INVALID, who + ": pos starts at 1");
+  if (!(a->inv_T > 0.0f) || !std::isfinite(a->inv_T)) return fail(TTX_ERR_INVALID, who + ": inv_T must be finite and > 0");
   SbsStepArgs sa{};
   sa.logits = a->d_logits; sa.V = a->V; sa.slot_of = a->d_slot_of; sa.finished = a->d_finished; sa.phi = a->d_phi; sa.g = a->d_g;
   sa.gen = a->d_gen; sa.ld = a->ld; sa.width = a->width; sa.B = a->B; sa.beam = a->beam; sa.K = a->K; sa.pad = a->pad; sa.eos = a->eos;
@@ -4328,7 +4399,41 @@ extern "C" int ttx_debug_sbs_step(ttx_session* s, const ttx_debug_sbs_step_args*
   sa.new_cand = a->d_new_cand; sa.new_phi = a->d_new_phi; sa.new_g = a->d_new_g; sa.parent = a->d_parent; sa.new_len = a->d_new_len;
   sa.new_finished = a->d_new_finished; sa.parent_draft = a->d_parent_draft; sa.summary = a->d_summary;
   sa.tr_parent = a->d_tr_parent; sa.tr_token = a->d_tr_token; sa.tr_phi = a->d_tr_phi; sa.tr_g = a->d_tr_g;
+  *out = sa;
+  return TTX_OK;
+}
+
+extern "C" int ttx_debug_sbs_step(ttx_session* s, const ttx_debug_sbs_step_args* a, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  SbsStepArgs sa{};
+  TTX_TRY(sbs_debug_args("ttx_debug_sbs_step", s, a, &sa));
+  HIP_TRY(hipSetDevice(s->m->device));
   return dbg_launched(launch_sbs_step(s, st, sa), st);
+}
+
+extern "C" int ttx_debug_sbs_step_ex(ttx_session* s, const ttx_debug_sbs_step_args* a, int top_k, float top_p, const ttx_debug_prefix* pfx,
+                                     int waves, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const char* who = "ttx_debug_sbs_step_ex";
+  SbsStepArgs sa{};
+  TTX_TRY(sbs_debug_args(who, s, a, &sa));
+  if (top_k < 0 || top_k > SAMPLE_MAX_KEEP) return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step_ex: top_k must be 0 or in [1, 32]");
+  if (!(top_p > 0.0f) || !(top_p <= 1.0f)) return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step_ex: top_p must be in (0, 1]");
+  if (waves != 0 && waves != 4 && waves != 8 && waves != SBS_MASKED_MAX_WAVES)
+    return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step_ex: waves must be 0 (the production choice), 4, 8 or 16");
+  HIP_TRY(hipSetDevice(s->m->device));
+  sa.top_p = top_p;
+  sa.top_k = (top_k == 0 && top_p < 1.0f) ? SAMPLE_MAX_KEEP : top_k;
+  if (pfx) {
+    TTX_TRY(dbg_prefix_tab(who, pfx, a->B, st, &sa.pfx));
+    if (a->pos > pfx->ld) {             // a position beyond the table is forced for no source
+      std::vector<int32_t> len((size_t)a->B);
+      HIP_TRY(hipMemcpy(len.data(), pfx->d_len, (size_t)a->B * 4, hipMemcpyDeviceToHost));
+      for (int b = 0; b < a->B; ++b)
+        if (len[b] >= a->pos) return fail(TTX_ERR_INVALID, "ttx_debug_sbs_step_ex: pos inside a prefix but beyond the table's ld");
+    }
+  }
+  return dbg_launched(launch_sbs_step_masked(s, st, sa, waves), st);
 }
 
 extern "C" int ttx_debug_tree_cache(ttx_session* s, const ttx_debug_tree_cache_args* a, void* stream) {

@@ -186,6 +186,7 @@ struct ttx_session {
   // function attributes (dynamic LDS limits) are per device: set once per session, outside graph capture
   bool attr_attn2[2][8] = {};      // [head dimension 32 / 64][mode]
   bool attr_select = false, attr_step = false, attr_topk = false, attr_pool_select = false, attr_sbs_step = false;
+  bool attr_sbs_step_masked[5] = {};   // k_sbs_step_masked<VPL>, VPL = 1, 2, 4, 8, 16
   bool attr_attn_probs[8] = {};    // k_attn_probs: [head dimension 32 / 64][16-byte output stores][16-byte key loads]
   // GEMM policy (all choices are between bit-identical evaluations, see GemmVariant)
   int qkv_small_rows = 800;        // a verify step with fewer live rows than this runs under GV_SMALL (TTX_QKV_SMALL_ROWS)

@@ -695,7 +695,8 @@ class SbsTrace(NamedTuple):
 
 class SbsDetails(NamedTuple):
     """What stochastic beam search knows about its rows: ``logp`` Float[B, K] the model's log-probability of each hypothesis at
-    the generator's temperature, ``gumbel`` Float[B, K] its perturbed log-probability (the sampling order: non-increasing, 0 for
+    the generator's temperature (under ``top_k`` / ``top_p`` the log-probability under the filtered, renormalised distribution;
+    under a ``prefix`` that of the completion given source and prefix: forced tokens cost nothing), ``gumbel`` Float[B, K] its perturbed log-probability (the sampling order: non-increasing, 0 for
     the first row), ``finished`` Bool[B, K], and the ``trace`` when one was asked for (always in sampling order)."""
     logp: torch.Tensor
     gumbel: torch.Tensor
@@ -710,36 +711,58 @@ class TranslationInferenceStochasticBeamSearch(_ScoresHypotheses):
     Gumbel noise keyed by (seed, the source's row key, the parent's rank, token, position) and keeps the K largest conditional
     maxima (include/ttx.h states the rule).  The rows of a source depend on the source, its key, the seed, the temperature and
     K only, and the call with K returns the first K rows of the call with a larger K.  A sampled PAD ends a row as EOS does.
-    No top-k / top-p filter, no forced prefix, no ``generate_many``.  ``scoring.sbs_weights`` turns ``logp`` and ``gumbel`` of a
-    K + 1 call into importance weights."""
+
+    ``top_k`` (0: off, or 1..32) and ``top_p`` (in (0, 1]; 1: off; a ``top_p < 1`` alone runs with ``top_k=32``) are
+    ``TranslationInferenceSampling``'s filter: at every free position the kept set is the sampler's, on the bits, every other token
+    counts as a -inf logit, and the log-probabilities are renormalised over the kept set.  The K rows are then a sample without
+    replacement from the sequence distribution the filtered sampler draws from; fewer than K rows may exist (``top_k=1`` has one:
+    the greedy row), and the missing ranks come back finished with ``logp = gumbel = -inf``.  A filter or a ``prefix`` runs
+    ttx_sbs_generate_ex (k_sbs_step_masked); a call with neither is ttx_sbs_generate, launch for launch.
+    No ``generate_many``.  ``scoring.sbs_weights`` turns ``logp`` and ``gumbel`` of a K + 1 call into importance weights, of the
+    filtered / conditional distribution when a filter / prefix is on."""
 
     def __init__(self, model, beam_size: int, max_len: int, pad_token: int, bos_token: int, eos_token: int,
-                 temperature: float = 1.0, seed: int = 0) -> None:
+                 temperature: float = 1.0, seed: int = 0, top_k: int = 0, top_p: float = 1.0) -> None:
         self.model = _need_native(model)
         self.beam_size, self.max_len = int(beam_size), int(max_len)
         self.pad_token, self.bos_token, self.eos_token = pad_token, bos_token, eos_token
         self.temperature, self.seed = float(temperature), int(seed)
+        self.top_k, self.top_p = int(top_k), float(top_p)
         self.model_calls_num = 0
         self.given_tokens = 0
         self.b_sz = 0
 
     def __str__(self):
-        return (f"Stochastic beam search (beam_size={self.beam_size}, temperature={self.temperature}, seed={self.seed}, "
-                f"max_len={self.max_len})")
+        return (f"Stochastic beam search (beam_size={self.beam_size}, temperature={self.temperature}, top_k={self.top_k}, "
+                f"top_p={self.top_p}, seed={self.seed}, max_len={self.max_len})")
 
     def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, return_details: bool = False,
-                 order: str = "sample", trace: bool = False):
+                 order: str = "sample", trace: bool = False, prefix=None):
         """Long[B, K, max_len]: BOS, the tokens up to and including the first EOS or PAD, PAD after.  ``row_keys``: one integer
         per source (default 0..B-1), the source's identity for the random stream.  ``order="sample"``: rows in sampling order
         (``gumbel`` descending); ``order="logp"``: re-sorted by ``logp``, best first (equal values keep their sampling order).
         ``return_scores=True`` appends the ``HypothesisScores`` of the returned rows and ``return_details=True`` an
-        ``SbsDetails`` (with ``trace=True`` including the ``SbsTrace``), in that order, as a tuple."""
+        ``SbsDetails`` (with ``trace=True`` including the ``SbsTrace``), in that order, as a tuple.
+
+        ``prefix``: Long[B, Lp] without BOS, right-padded with PAD, validated as the samplers validate theirs
+        (``check_prefix``): the forced beginning of every row of a source.  A finite row is BOS, the prefix, a completion, PAD;
+        the rows are K distinct completions, a sample without replacement from the model's distribution given source and prefix,
+        and ``logp`` is the completion's conditional log-probability.  A forced position reads no logits and spends no noise; a
+        forced EOS ends the row (one finite row).  One decoder step per forced token.  An empty prefix (zero width, all PAD,
+        ``None``) is the unprompted call."""
         if order not in ("sample", "logp"):
             raise ValueError(f"order must be 'sample' or 'logp', got {order!r}")
         m, K = self.model, self.beam_size
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
         B, Ls = src.shape
+        pre, plen = check_prefix(prefix, B, self.max_len, self.pad_token, m.tgt_vocab_size)
+        d_prefix = prefix_ptr = h_plen = None            # d_prefix keeps the device tensor alive until the call returns
+        ld_prefix = 0
+        if pre is not None:
+            d_prefix = pre.to(m.device)
+            prefix_ptr, ld_prefix = (d_prefix.data_ptr() if d_prefix.numel() else None), int(d_prefix.shape[1])
+            h_plen = (C.c_int32 * max(B, 1))(*plen)
         keys = None
         if row_keys is not None:
             keys = torch.as_tensor(row_keys, dtype=torch.int64).to(m.device).contiguous()
@@ -758,8 +781,10 @@ class TranslationInferenceStochasticBeamSearch(_ScoresHypotheses):
                           torch.zeros(shape, dtype=torch.float32, device=m.device), torch.zeros(shape, dtype=torch.float32, device=m.device))
             tr_arg = C.byref(N.SbsTrace(*(t.data_ptr() for t in tr)))
         st = N.BeamSearchStats()
-        N.check(m._lib.ttx_sbs_generate(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(), C.byref(p),
-                                        out.data_ptr(), logp.data_ptr(), gumbel.data_ptr(), tr_arg, C.byref(st), m._stream()))
+        filt = N.SbsFilter(self.top_k, self.top_p)
+        N.check(m._lib.ttx_sbs_generate_ex(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(), C.byref(p),
+                                           C.byref(filt), prefix_ptr, ld_prefix, h_plen, out.data_ptr(), logp.data_ptr(),
+                                           gumbel.data_ptr(), tr_arg, C.byref(st), m._stream()))
         self.model_calls_num += int(st.model_calls)
         self.b_sz += int(st.running_rows)
         self.given_tokens += int((src != m.src_pad_token_i).sum())

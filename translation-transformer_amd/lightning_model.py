@@ -300,7 +300,8 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
                                                            replace_token=self.tgt_tokenizer.encoder_dict["c"], **common)
         if h.generation == "stochastic_beam_search":  # beam_size distinct draws per reaction (sampling without replacement)
             return D.TranslationInferenceStochasticBeamSearch(m, beam_size=h.beam_size, max_len=h.max_len,
-                                                              temperature=h.sampling_temperature, seed=h.sampling_seed, **common)
+                                                              temperature=h.sampling_temperature, seed=h.sampling_seed,
+                                                              top_k=h.sampling_top_k, top_p=h.sampling_top_p, **common)
         if h.generation == "sampling":               # beam_size samples per reaction, as the reference uses it for n_best
             return D.TranslationInferenceSampling(m, max_len=h.max_len, temperature=h.sampling_temperature, top_k=h.sampling_top_k,
                                                   top_p=h.sampling_top_p, num_samples=max(1, h.beam_size), seed=h.sampling_seed,
@@ -322,9 +323,9 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         pred = None
         sampling = self.hparams.generation in ("sampling", "sampling_speculative")
         prefix = batch["prefix_tokens"] if "prefix_tokens" in batch else None      # forced target prefixes: Long[B, Lp], no BOS
-        if prefix is not None and not sampling:
-            raise ValueError(f'"prefix_tokens" in a batch: only generation="sampling" and "sampling_speculative" take forced '
-                             f'prefixes, not "{self.hparams.generation}"')
+        if prefix is not None and not sampling and self.hparams.generation != "stochastic_beam_search":
+            raise ValueError(f'"prefix_tokens" in a batch: only generation="sampling", "sampling_speculative" and '
+                             f'"stochastic_beam_search" take forced prefixes, not "{self.hparams.generation}"')
         proposal = batch["proposal_tokens"] if "proposal_tokens" in batch else None  # offered drafts: Long[B, Lq], no BOS
         if proposal is not None and self.hparams.generation != "sampling_speculative":
             raise ValueError(f'"proposal_tokens" in a batch: only generation="sampling_speculative" takes proposals, '
@@ -341,7 +342,8 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             self._predict_rows += B
         elif pred is None and self.hparams.generation == "stochastic_beam_search":   # keyed like the samplers: the running index
             B = int(batch["src_tokens"].shape[0])
-            pred = self.generator.generate(batch["src_tokens"], row_keys=torch.arange(self._predict_rows, self._predict_rows + B))
+            pred = self.generator.generate(batch["src_tokens"], row_keys=torch.arange(self._predict_rows, self._predict_rows + B),
+                                           prefix=prefix)
             self._predict_rows += B
         elif pred is None:
             pred = self.generator.generate(batch["src_tokens"])

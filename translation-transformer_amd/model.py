@@ -526,15 +526,31 @@ class NativeTransformer:
                        inv_T: float, **arrays) -> None:
         """One k_sbs_step launch (ttx_debug_sbs_step): the operands of debug_beam_step with ``phi``, ``g``, ``key`` (absent: keys
         0..B-1), ``new_phi``, ``new_g`` and optionally the four ``tr_*`` trace arrays."""
+        a = self._sbs_step_args(arrays, dict(V=V, ld=ld, width=width, B=B, beam=beam, K=K, pad=pad, eos=eos, pos=pos), seed, inv_T)
+        N.check(self._lib.ttx_debug_sbs_step(self._session, C.byref(a), self._stream()))
+
+    @staticmethod
+    def _sbs_step_args(arrays: dict, scalars: dict, seed: int, inv_T: float):
         a = N.DebugSbsStepArgs()
         for name in a.POINTERS:
             t = arrays.pop(name[2:], None)
             setattr(a, name, None if t is None else t.data_ptr())
         assert not arrays, f"unknown operands {sorted(arrays)}"
-        for name, v in dict(V=V, ld=ld, width=width, B=B, beam=beam, K=K, pad=pad, eos=eos, pos=pos).items():
+        for name, v in scalars.items():
             setattr(a, name, int(v))
         a.seed, a.inv_T = int(seed) & 0xFFFFFFFFFFFFFFFF, float(inv_T)
-        N.check(self._lib.ttx_debug_sbs_step(self._session, C.byref(a), self._stream()))
+        return a
+
+    def debug_sbs_step_ex(self, *, V: int, ld: int, width: int, B: int, beam: int, K: int, pad: int, eos: int, pos: int, seed: int,
+                          inv_T: float, top_k: int = 0, top_p: float = 1.0, waves: int = 0, pfx_tok=None, pfx_len=None, pfx_src=None,
+                          pfx_ld: int = 0, pfx_sources: int = 0, **arrays) -> None:
+        """One k_sbs_step_masked launch (ttx_debug_sbs_step_ex): debug_sbs_step's operands, the filter, ``waves`` (0: the production
+        choice) and optionally the prefix table by source (``pfx_tok`` int32 [pfx_sources, pfx_ld], ``pfx_len`` / ``pfx_src`` int32 [B])."""
+        a = self._sbs_step_args(arrays, dict(V=V, ld=ld, width=width, B=B, beam=beam, K=K, pad=pad, eos=eos, pos=pos), seed, inv_T)
+        pfx = None
+        if pfx_tok is not None or pfx_len is not None or pfx_src is not None:
+            pfx = C.byref(N.DebugPrefix(self._ptr(pfx_tok), int(pfx_ld), int(pfx_sources), self._ptr(pfx_len), self._ptr(pfx_src)))
+        N.check(self._lib.ttx_debug_sbs_step_ex(self._session, C.byref(a), int(top_k), float(top_p), pfx, int(waves), self._stream()))
 
     def debug_tree_cache(self, *, max_cand: int, layers: int, prev_n: int, prev_d: int, d: int, cache_layer_stride: int,
                          cache_seq_stride: int, qkv_layer_stride: int, **arrays) -> None:

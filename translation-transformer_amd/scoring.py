@@ -171,7 +171,11 @@ def sbs_weights(logp, gumbel):
 
     With the K hypotheses y_i, ``sum_i w_i f(y_i)`` is an unbiased estimate of ``E_{y ~ p} f(y)``: ``sum_i w_i 1[y_i == y*]``
     estimates the mass the model gives an answer y*, ``sum_i w_i`` estimates 1, and ``sum_i w_i 1[..]`` over any set of answers
-    its total mass.  A kappa of -inf (fewer than K + 1 hypotheses exist) gives ``w_i = p_i``: the sample is the support."""
+    its total mass.  A kappa of -inf (fewer than K + 1 hypotheses exist) gives ``w_i = p_i``: the sample is the support.
+
+    Under the generator's ``top_k`` / ``top_p`` filter ``logp`` is the log-probability under the filtered, renormalised model and
+    the weights estimate masses of that distribution; under a ``prefix`` they estimate masses of the conditional distribution
+    given source and prefix.  Rows with ``logp = -inf`` (ranks that do not exist) get weight 0."""
     import numpy as np
 
     def host(x):
