@@ -564,8 +564,8 @@ int ttx_beam_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const
  *   level; stats->model_calls says how many levels are valid.  stats->out_width is the number of columns the loop filled.
  * Cost, measured on one MI355X (4+4 model, 32 sources, max_len 200): 1.8 % (K = 5) and 2.2 % (K = 10) more per
  * decoder step than ttx_beam_generate with the same K, and 8.8 % / 11.0 % more per call, since the sampled rows run longer.
- * Limits: no pooled generate_many (the top-k / top-p filter and forced prefixes are ttx_sbs_generate_ex below).  TTX_ERR_INVALID with
- * nothing launched: max_len <= 1,
+ * The top-k / top-p filter and forced prefixes are ttx_sbs_generate_ex below; many batches on a pool of source slots are
+ * ttx_sbs_generate_pool.  TTX_ERR_INVALID with nothing launched: max_len <= 1,
  * beam_size outside [1, min(32, vocab_size)], vocab_size > 1024, beam_size * vocab_size * 4 > 150 KB, a temperature that is not
  * finite or not > 0, a trace with a NULL array, and everything else ttx_beam_generate refuses. */
 typedef struct ttx_sbs_params {
@@ -609,7 +609,7 @@ int ttx_sbs_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const 
  *   ttx_sample_generate_prefix.  Everything else as for ttx_sbs_generate.
  * TTX_ERR_INVALID with nothing launched: top_k outside [0, 32], top_p outside (0, 1], a prefix length outside [0, max_len - 1] or
  * above ld_prefix, a non-zero length with d_prefix NULL, and everything ttx_sbs_generate refuses.
- * Cost: DESIGN.md §23.  Limits: no pooled generate_many. */
+ * Cost: DESIGN.md §23. */
 typedef struct ttx_sbs_filter {
   int32_t top_k;                         /* 0: off, else 1..32 */
   float   top_p;                         /* (0, 1]; 1: off */
@@ -618,6 +618,48 @@ int ttx_sbs_generate_ex(ttx_session* s, const int64_t* d_src, int B, int Ls, con
                         const ttx_sbs_filter* f_or_null, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
                         int64_t* d_out, float* d_logp, float* d_gumbel, const ttx_sbs_trace* trace_or_null,
                         ttx_beam_search_stats* stats, void* stream);
+
+/* Stochastic beam search over a whole list of sources on a pool of source slots (continuous batching; kernels and slot state:
+ * csrc/ttx_sbs_pool.hip.h).  Each of up to n_sessions pools owns C <= capacity source slots of K candidates; a
+ * source is admitted into a free slot (one <BOS> candidate with phi = G = 0), steps at its OWN level with its own key and prefix,
+ * and retires - its K rows, logp and gumbel written to its row of the outputs, the slot free in the same iteration - as soon as
+ * all K candidates are finished or its level has reached max_len - 1.  One decoder pass per iteration serves every unfinished
+ * candidate of every source in the pool.
+ *
+ * Exactness contract.  Row s of d_out, d_logp and d_gumbel holds, bit for bit, what ttx_sbs_generate_ex writes for that source
+ * with that key and prefix under the same p and f: tokens, logp and gumbel.  It does not depend on capacity, on the number of
+ * pools in flight, on the order of the list or on what shares the pool.  The contract rests on the rule being per source (a source
+ * whose K candidates are finished is a fixed point of the step), on the GEMM family's single summation order and on the
+ * attention kernels' padding invariance.  Range: the pool fixes the key capacity of its self-attention at max_len while the
+ * per-batch loop grows it with the width in buckets of 64, so beyond the staged key limit (ttx_attn_staged_key_limit: 384
+ * positions, 320 at head dimension 64) the two may run different attention kernels, which agree to rounding only.  The contract
+ * holds while max_len + 1 (the prefix keys and the step's own row) does not exceed that limit.
+ *
+ *   d_src int64 [S_total, Ls_all], sources in admission order (sort them longest first: an admission is encoded at the width of
+ *   its longest source); h_len HOST int32 [S_total], the position after each source's last non-PAD token; d_row_keys int64
+ *   [S_total] or NULL (keys 0 .. S_total - 1); capacity: sources per pool; f_or_null, d_prefix [S_total, ld_prefix],
+ *   h_prefix_len as for ttx_sbs_generate_ex; d_out int64 [S_total, K, max_len], d_logp, d_gumbel fp32 [S_total, K].  There is no
+ *   trace.  stats: sums over the pools.  S_total == 0 returns TTX_OK with nothing launched.
+ * TTX_ERR_INVALID with nothing launched: a NULL pointer (d_row_keys, f, d_prefix and h_prefix_len may be NULL), capacity outside
+ * [1, 1024], an h_len entry above Ls_all or below 2, and everything ttx_sbs_generate_ex refuses.  TTX_ERR_HIP "failed to
+ * terminate" once a pool's iterations exceed max_len * (S_total + 1). */
+typedef struct ttx_sbs_pool_stats {
+  int64_t model_calls;             /* iterations executed (decoder passes), summed over the pools             */
+  int64_t running_rows;            /* unfinished candidates summed over the iterations                        */
+  int64_t src_tokens_padded;       /* encoder positions computed                                              */
+  int64_t live_slots;              /* occupied source slots summed over the iterations                        */
+  double  decode_ms;               /* device time (HIP events) from a pool's start to its last retirement, summed */
+  int32_t status;
+  int32_t pad_;
+  int32_t* d_src_running_rows;     /* IN, the block's one input: NULL, or a device int32 [S_total] that receives, per source, the
+                                      candidates decoded for it summed over its levels (the entries sum to running_rows)   */
+} ttx_sbs_pool_stats;
+int ttx_sbs_generate_pool(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total, int Ls_all,
+                          const int32_t* h_len, const int64_t* d_row_keys, int capacity /* sources per pool */,
+                          const ttx_sbs_params* p, const ttx_sbs_filter* f_or_null,
+                          const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
+                          int64_t* d_out /* [S_total][K][max_len] */, float* d_logp, float* d_gumbel /* [S_total][K] */,
+                          ttx_sbs_pool_stats* stats, void* stream);
 
 /* Several batches in flight on one GPU (the scheduling SURVEY.md §8(f) #1 names; the reference's predict loop
  * is strictly one batch at a time, src/model/lightning_model.py:209-212).  Batch i is decoded on
@@ -1045,6 +1087,46 @@ typedef struct ttx_debug_tree_cache_args {
 /* ttx_debug_tree_cache: k_tree_cache on (max_cand, layers) workgroups.  Also refused: d not a multiple of 4, strides that are not
  * multiples of 4 floats, buffers that are not 16-byte aligned, one slot map without the other, slot maps with k_old != k_new. */
 int ttx_debug_tree_cache(ttx_session* s, const ttx_debug_tree_cache_args* a, void* stream);
+
+/* ---- The kernels of the stochastic beam pool (csrc/ttx_sbs_pool.hip.h), ONE launch per call on DEVICE arrays of the caller
+ * (tests/test_gpu_sbs_pool_kernel.py; the rules are restated in tests/util_sbs_pool_checks.py).
+ * ttx_debug_sbs_step_pool: k_sbs_step_pool (masked == 0) or k_sbs_step_pool_masked on C workgroups.  Candidate arrays are [C*K]
+ * (candidate c = slot * K + k; d_gen int32 [C*K, ld], d_new_cand int64 [C*K, ld]), slot arrays int32 [C] (d_key int64 [C]):
+ * d_row_of (-1: a free slot, whose workgroup writes nothing), d_level (pos = width), d_nlive (parents: 1 or K), d_nfin (output:
+ * finished ones among the slot's K new candidates).  top_k, top_p, pfx as for ttx_debug_sbs_step_ex with the table by SLOT.
+ * Refused: a null array, C outside [1, 1024], K outside [1, min(32, V)], V above 1024, K * V * 4 above 150 KB, a live slot's
+ * level outside [1, ld) or parent count outside [1, K], a filter or table with masked == 0, top_k / top_p outside their ranges. */
+typedef struct ttx_debug_sbs_step_pool_args {
+  const float* d_logits; const int32_t* d_slot_of; const uint8_t* d_finished; const float* d_phi; const float* d_g; const int32_t* d_gen;
+  const int32_t* d_row_of; const int32_t* d_level; const int32_t* d_nlive; const int64_t* d_key;
+  int64_t* d_new_cand; float* d_new_phi; float* d_new_g; int32_t* d_parent; int32_t* d_new_len; uint8_t* d_new_finished;
+  int32_t* d_parent_draft; int32_t* d_nfin;
+  uint64_t seed;
+  int32_t V, ld, C, K, pad, eos;
+  float inv_T;
+} ttx_debug_sbs_step_pool_args;
+int ttx_debug_sbs_step_pool(ttx_session* s, const ttx_debug_sbs_step_pool_args* a, int masked, int top_k, float top_p,
+                            const ttx_debug_prefix* pfx, void* stream);
+/* ttx_debug_sbs_pool: the bookkeeping kernels.  op: 0 init (also needs d_src_of int32 [C*K]; zeroes d_g_in and d_g_out), 1 admit
+ * (d_new_slot int32 [C]), 2 fill (d_new_slot, staged d_valid_new uint8 [R, Ls_new] and d_memkv_new fp32 [R, Ls_new, kv_row]; the
+ * pool's d_src_valid uint8 [C, Ls_cap] and d_memkv fp32 [C, Ls_cap, kv_row]), 3 retire, 4 publish.  d_g_in: G as the next step
+ * reads it (fill writes it); d_g_out: G as the last step wrote it (retire reads it).  d_len_all int32 [S], d_row_keys int64 [S] or
+ * NULL, d_pfx_len_src int32 [S] or NULL; d_out int64 [S, K, max_len], d_out_logp / d_out_gumbel fp32 [S, K]; d_run_acc int32 [C]
+ * and d_src_running int32 [S] or NULL (the per-source count of decoded candidates, written at retirement); d_dev_summary int32
+ * [4].  `words`: as for ttx_debug_bsp.  Refused: a null required pointer, C outside [1, 1024], K outside [1, 32], max_len < 2,
+ * ld < max_len, R outside [1, C], Ls_new outside [1, Ls_cap], kv_row not a positive multiple of 4, unaligned memkv operands. */
+typedef struct ttx_debug_sbs_pool_args {
+  int32_t* d_row_of; int32_t* d_level; int32_t* d_nlive; int32_t* d_nfin; int64_t* d_key; int32_t* d_pfx_len; int32_t* d_pfx_src;
+  int32_t* d_run_acc;
+  int64_t* d_cand_next; int32_t* d_len_next; uint8_t* d_fin_next; float* d_phi_next; int32_t* d_parent; int32_t* d_parent_draft;
+  int32_t* d_cand_src_len; float* d_g_in; float* d_g_out;
+  const int32_t* d_len_all; const int64_t* d_row_keys; const int32_t* d_pfx_len_src;
+  int64_t* d_out; float* d_out_logp; float* d_out_gumbel; int32_t* d_src_running; int32_t* d_dev_summary;
+  int32_t* d_src_of; int32_t* d_new_slot; const uint8_t* d_valid_new; uint8_t* d_src_valid; float* d_memkv; const float* d_memkv_new;
+  int32_t C, K, max_len, ld, Ls_cap, pad, bos;
+  int32_t R, first_row, kv_row, Ls_new;
+} ttx_debug_sbs_pool_args;
+int ttx_debug_sbs_pool(ttx_session* s, int op, const ttx_debug_sbs_pool_args* a, int64_t* words, void* stream);
 
 /* ---- The bookkeeping kernels of the beam-speculative batch pool (csrc/ttx_loop_kernels.hip.h: k_bsp_init .. k_bsp_publish), ONE
  * launch per call on DEVICE arrays of the caller (tests/test_gpu_bsp_kernels.py; the rules are restated in tests/util_bsp_checks.py).

@@ -17,7 +17,7 @@ LIB_PATH = PKG_DIR / "libttx_hip.so"
 # translation units (compiled in parallel, linked into one shared library) and the headers every one of them depends on
 UNITS = [CSRC / "ttx_api.hip", CSRC / "ttx_gemm.hip", CSRC / "ttx_attn.hip"]
 HEADERS = [CSRC / "ttx_internal.h", CSRC / "ttx_common.hip.h", CSRC / "ttx_loop_kernels.hip.h", CSRC / "ttx_metrics.hip.h",
-           CSRC / "ttx_score.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_sample.hip.h", CSRC / "ttx_sbs.hip.h",
+           CSRC / "ttx_score.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_sample.hip.h", CSRC / "ttx_sbs.hip.h", CSRC / "ttx_sbs_pool.hip.h",
            CSRC / "ttx_proposal.hip.h",
            CSRC / "ttx_select.h", CSRC / "ttx_tokenizer.h", CSRC / "ttx_drive.h", CSRC / "ttx_admit.h", INCLUDE / "ttx.h"]
 SOURCES = UNITS + HEADERS
@@ -113,6 +113,30 @@ class DebugSbsStepArgs(C.Structure):
                [(n, C.c_int32) for n in ("V", "ld", "width", "B", "beam", "K", "pad", "eos", "pos")] + [("inv_T", C.c_float)]
 
 
+class SbsPoolStats(C.Structure):
+    """ttx_sbs_pool_stats: sums over the pools of one ttx_sbs_generate_pool call."""
+    _fields_ = [("model_calls", C.c_int64), ("running_rows", C.c_int64), ("src_tokens_padded", C.c_int64), ("live_slots", C.c_int64),
+                ("decode_ms", C.c_double), ("status", C.c_int32), ("pad_", C.c_int32), ("d_src_running_rows", C.c_void_p)]
+
+
+class DebugSbsStepPoolArgs(C.Structure):
+    """ttx_debug_sbs_step_pool_args: one k_sbs_step_pool / k_sbs_step_pool_masked launch's operands."""
+    POINTERS = ("d_logits", "d_slot_of", "d_finished", "d_phi", "d_g", "d_gen", "d_row_of", "d_level", "d_nlive", "d_key", "d_new_cand",
+                "d_new_phi", "d_new_g", "d_parent", "d_new_len", "d_new_finished", "d_parent_draft", "d_nfin")
+    _fields_ = [(n, C.c_void_p) for n in POINTERS] + [("seed", C.c_uint64)] + \
+               [(n, C.c_int32) for n in ("V", "ld", "C", "K", "pad", "eos")] + [("inv_T", C.c_float)]
+
+
+class DebugSbsPoolArgs(C.Structure):
+    """ttx_debug_sbs_pool_args: the operands of one bookkeeping launch of the stochastic beam pool."""
+    POINTERS = ("d_row_of", "d_level", "d_nlive", "d_nfin", "d_key", "d_pfx_len", "d_pfx_src", "d_run_acc", "d_cand_next", "d_len_next", "d_fin_next",
+                "d_phi_next", "d_parent", "d_parent_draft", "d_cand_src_len", "d_g_in", "d_g_out", "d_len_all", "d_row_keys",
+                "d_pfx_len_src", "d_out", "d_out_logp", "d_out_gumbel", "d_src_running", "d_dev_summary", "d_src_of", "d_new_slot", "d_valid_new",
+                "d_src_valid", "d_memkv", "d_memkv_new")
+    _fields_ = [(n, C.c_void_p) for n in POINTERS] + \
+               [(n, C.c_int32) for n in ("C", "K", "max_len", "ld", "Ls_cap", "pad", "bos", "R", "first_row", "kv_row", "Ls_new")]
+
+
 class GenStats(C.Structure):
     _fields_ = [("model_calls", C.c_int64), ("accepted_tokens", C.c_int64), ("produced_tokens", C.c_int64),
                 ("verified_positions", C.c_int64), ("kv_prefix_positions", C.c_int64), ("src_positions", C.c_int64),
@@ -204,6 +228,7 @@ DebugBspArgs = _debug_args("debug_bsp_args",
                            ("C", "K", "N", "D0", "Ls_cap", "max_len", "ld", "smart", "lib_ld", "pad", "bos", "eos", "repl", "max_steps",
                             "T_cap", "R", "first_row", "kv_row", "Ls_new"))
 DEBUG_BSP_OPS = ("init", "admit", "fill", "prep", "select", "batches", "retire", "publish")     # ttx_debug_bsp's op, in order
+DEBUG_SBS_POOL_OPS = ("init", "admit", "fill", "retire", "publish")     # ttx_debug_sbs_pool's op, in order (words: DEBUG_BSP_WORDS)
 DEBUG_BSP_WORDS = 12              # int64 words of ttx_debug_bsp's host array: 8 of the BeamCounters, 4 of the BeamPoolHost
 DEBUG_BS_LIST_WORDS = 21          # int64 words of ttx_debug_bs_list's host array: 8 of the BeamCounters, 13 of the DecState
 
@@ -277,6 +302,8 @@ SYMBOLS = {
                                   C.POINTER(BeamSearchStats), _VP]),
     "ttx_sbs_generate_ex": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SbsParams), C.POINTER(SbsFilter), _VP, _I, _VP, _VP, _VP, _VP,
                                      C.POINTER(SbsTrace), C.POINTER(BeamSearchStats), _VP]),
+    "ttx_sbs_generate_pool": (C.c_int, [_VP, _I, _VP, _I, _I, C.POINTER(C.c_int32), _VP, _I, C.POINTER(SbsParams), C.POINTER(SbsFilter),
+                                       _VP, _I, _VP, _VP, _VP, _VP, C.POINTER(SbsPoolStats), _VP]),
     "ttx_nucleus_mask": (C.c_int, [_VP, _VP, _I, _I, C.c_float, _I, C.c_float, _VP, _VP]),
     "ttx_accepted_lengths": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, C.c_float, _I, _VP, _VP]),
     "ttx_ragged_topk": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
@@ -324,6 +351,8 @@ SYMBOLS = {
     "ttx_debug_beam_step": (C.c_int, [_VP, C.POINTER(DebugBeamStepArgs), _VP]),
     "ttx_debug_sbs_step": (C.c_int, [_VP, C.POINTER(DebugSbsStepArgs), _VP]),
     "ttx_debug_sbs_step_ex": (C.c_int, [_VP, C.POINTER(DebugSbsStepArgs), _I, C.c_float, C.POINTER(DebugPrefix), _I, _VP]),
+    "ttx_debug_sbs_step_pool": (C.c_int, [_VP, C.POINTER(DebugSbsStepPoolArgs), _I, _I, C.c_float, C.POINTER(DebugPrefix), _VP]),
+    "ttx_debug_sbs_pool": (C.c_int, [_VP, _I, C.POINTER(DebugSbsPoolArgs), C.POINTER(C.c_int64), _VP]),
     "ttx_debug_tree_cache": (C.c_int, [_VP, C.POINTER(DebugTreeCacheArgs), _VP]),
     "ttx_debug_bsp": (C.c_int, [_VP, _I, C.POINTER(DebugBspArgs), C.POINTER(C.c_int64), _VP]),
     "ttx_debug_kvcopy": (C.c_int, [_VP, _VP, _I, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int64, _I, _I, _I, _I, _I, _VP]),

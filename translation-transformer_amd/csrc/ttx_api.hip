@@ -12,6 +12,7 @@
 #include "ttx_attn_probs.hip.h"
 #include "ttx_sample.hip.h"
 #include "ttx_sbs.hip.h"
+#include "ttx_sbs_pool.hip.h"
 #include "ttx_proposal.hip.h"
 #include "ttx_tokenizer.h"
 
@@ -3449,6 +3450,314 @@ extern "C" int ttx_sbs_generate_ex(ttx_session* s, const int64_t* d_src, int B, 
                       h_prefix_len);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Stochastic beam search on a pool of source slots (kernels, slot state and the argument for exactness: csrc/ttx_sbs_pool.hip.h).
+// Host side: one job per session, each a pool of C source slots fed from the caller's list of sources; an iteration is one fixed
+// linear launch sequence (captured once per cache parity and GEMM variant) over every unfinished candidate in the pool.
+struct SbsPoolJob {
+  ttx_session* s = nullptr;
+  hipStream_t st = nullptr;
+  ttx_sbs_params p{};
+  int C = 0, K = 0, MC = 0, ld = 0, Lc = 0, Ls_cap = 0;
+  float inv_T = 1.f;
+  bool masked = false, prompted = false;
+  int top_k = 0; float top_p = 1.f;
+  SbsPoolArgs a{};                  // g_in / g_out unset: sbsp_args(j, parity) fills them
+  SbsPoolStepArgs sa{};             // g / new_g likewise
+  int launched = 0, cur = 0;        // cur: the parity of the iteration to come (cache buffer read, G buffer read)
+  int phase = 0;                    // 0 not started, 1 running, 2 finishing, 3 done
+  int admitted_since = 0;           // sources admitted since the last published iteration
+  int quota_end = -1;               // serial (profiling) pass: end of this pool's share of the list
+  long long src_tokens_padded = 0, live_slots = 0;
+  SbsPoolIo io{};                   // host image of the session's device block
+};
+
+static SbsPoolArgs sbsp_args(const SbsPoolJob& j, int parity) {
+  float* const gbuf[2] = {j.s->sbs_g.as<float>(), j.s->sbs_g_next.as<float>()};
+  SbsPoolArgs a = j.a;
+  a.g_in = gbuf[parity]; a.g_out = gbuf[parity ^ 1];
+  return a;
+}
+
+static int launch_sbsp_init(hipStream_t st, const SbsPoolArgs& a, float* g_a, float* g_b, int* src_of) {
+  hipLaunchKernelGGL(k_sbsp_init, dim3(64), dim3(256), 0, st, a, g_a, g_b, src_of);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+static int launch_sbsp_admit(hipStream_t st, const SbsPoolArgs& a, int* new_slot, int R, int first_row) {
+  hipLaunchKernelGGL(k_sbsp_admit, dim3(1), dim3(1), 0, st, a, new_slot, R, first_row);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+static int launch_sbsp_fill(hipStream_t st, const SbsPoolFillArgs& f) {
+  hipLaunchKernelGGL(k_sbsp_fill, dim3(f.R, 1 + f.Ls_new), dim3(256), 0, st, f);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+static int launch_sbsp_retire(hipStream_t st, const SbsPoolArgs& a) {
+  hipLaunchKernelGGL(k_sbsp_retire, dim3(a.C), dim3(256), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+static int launch_sbsp_publish(hipStream_t st, const SbsPoolArgs& a) {
+  hipLaunchKernelGGL(k_sbsp_publish, dim3(1), dim3(256), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+static int launch_sbs_step_pool(ttx_session* s, hipStream_t st, const SbsPoolStepArgs& sa) {
+  const size_t lds = (size_t)sa.K * sa.V * 4;
+  TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_sbs_step_pool), lds, s->attr_sbs_step_pool));
+  hipLaunchKernelGGL(k_sbs_step_pool, dim3(sa.C), dim3(256), lds, st, sa);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+template <int VPL>
+static int launch_sbs_step_pool_masked_vpl(hipStream_t st, const SbsPoolStepArgs& sa, int waves, bool& attr) {
+  const size_t lds = (size_t)sa.K * sa.V * 4;
+  TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_sbs_step_pool_masked<VPL>), lds, attr));
+  hipLaunchKernelGGL((k_sbs_step_pool_masked<VPL>), dim3(sa.C), dim3(64 * waves), lds, st, sa);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+// The wave count follows K (a slot's parent count is 1 or K; no sum or maximum changes its order with the wave count).
+static int launch_sbs_step_pool_masked(ttx_session* s, hipStream_t st, const SbsPoolStepArgs& sa) {
+  const int waves = sbs_masked_waves(sa.K);
+  if (sa.V <= 64) return launch_sbs_step_pool_masked_vpl<1>(st, sa, waves, s->attr_sbs_step_pool_masked[0]);
+  if (sa.V <= 128) return launch_sbs_step_pool_masked_vpl<2>(st, sa, waves, s->attr_sbs_step_pool_masked[1]);
+  if (sa.V <= 256) return launch_sbs_step_pool_masked_vpl<4>(st, sa, waves, s->attr_sbs_step_pool_masked[2]);
+  if (sa.V <= 512) return launch_sbs_step_pool_masked_vpl<8>(st, sa, waves, s->attr_sbs_step_pool_masked[3]);
+  return launch_sbs_step_pool_masked_vpl<16>(st, sa, waves, s->attr_sbs_step_pool_masked[4]);
+}
+
+// The call's prefix arguments as sbsp_start uploads them (prompted false: nothing is uploaded)
+struct SbsPoolCall {
+  const int32_t* h_len; const int64_t* d_row_keys; int S_total;
+  SampleSetup pre;
+  int64_t* d_out; float* d_logp; float* d_gumbel; int32_t* d_src_running;
+};
+
+static int sbsp_start(SbsPoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_cap, const ttx_sbs_params* p, float inv_T, int top_k,
+                      float top_p, const SbsPoolCall& call) {
+  const ttx_config& c = s->m->cfg;
+  const int d = c.embedding_dim, Ld = c.num_decoder_layers, K = p->beam_size, S = call.S_total;
+  j = SbsPoolJob{};
+  j.s = s; j.st = st; j.p = *p; j.C = C; j.K = K; j.MC = C * K; j.ld = p->max_len + 2; j.Lc = p->max_len + 2; j.Ls_cap = Ls_cap;
+  j.inv_T = inv_T; j.top_k = top_k; j.top_p = top_p; j.prompted = call.pre.prompted; j.masked = top_k > 0 || call.pre.prompted;
+  const size_t MC = (size_t)j.MC, kv_row = (size_t)Ld * 2 * d;
+  Needs need{st};
+  need(s->tok_src, (size_t)C * Ls_cap * 4); need(s->valid_new, (size_t)C * Ls_cap); need(s->src_valid, (size_t)C * Ls_cap);
+  need(s->memory, (size_t)C * Ls_cap * d * 4); need(s->memkv_new, (size_t)C * Ls_cap * kv_row * 4); need(s->memkv, (size_t)C * Ls_cap * kv_row * 4);
+  need(s->bp_enc_qkv, (size_t)C * Ls_cap * 3 * d * 4);      // admissions must not touch the step's Q/K/V rows (k_tree_cache reads them)
+  need(s->drafts, MC * 4);
+  need(s->gen, MC * j.ld * 4); need(s->front, MC * 4); need(s->act_idx, MC * 4);
+  for (int i = 0; i < 2; ++i) { need(s->tk[i], (size_t)Ld * MC * j.Lc * d * 4); need(s->tv[i], (size_t)Ld * MC * j.Lc * d * 4); }
+  need(s->t_prev_len, MC * 4); need(s->t_slot_of, MC * 4); need(s->t_src_of, MC * 4); need(s->bp_cand_len, MC * 4);
+  need(s->bs_cand_next, MC * j.ld * 8); need(s->bs_len_next, MC * 4); need(s->bs_fin_next, MC); need(s->bs_logp_next, MC * 4);
+  need(s->bs_len, MC * 4); need(s->bs_fin, MC); need(s->bs_active, MC); need(s->bs_logp, MC * 4); need(s->bs_per_cand, MC * 4);
+  need(s->bs_parent, MC * 4); need(s->bs_parent_draft, MC * 4); need(s->bs_cnt, sizeof(BeamCounters)); need(s->beam_summary, 8 * 4);
+  need(s->sbs_g, MC * 4); need(s->sbs_g_next, MC * 4);
+  need(s->sbp_slot, (size_t)C * (8 + 7 * 4)); need(s->sbp_len, (size_t)S * 4); need(s->bp_new_slot, (size_t)C * 4); need(s->bp_grp, 4 * 4);
+  need(s->sbp_io, sizeof(SbsPoolIo));
+  if (j.prompted) { need(s->pfx_tok, (size_t)S * p->max_len * 4); need(s->pfx_len_src, (size_t)S * 4); }
+  need_step_workspaces(s, need, MC, (size_t)C * Ls_cap);
+  s->graphs_current();
+  TTX_TRY(need.rc);
+  if (!s->bp_host) {
+    if (hipHostMalloc((void**)&s->bp_host, sizeof(BeamPoolHost), hipHostMallocMapped) != hipSuccess)
+      return fail(TTX_ERR_NOMEM, "hipHostMalloc failed");
+  }
+  std::memset(s->bp_host, 0, sizeof(BeamPoolHost));
+  BeamPoolHost* dev_host = nullptr;
+  HIP_TRY(hipHostGetDevicePointer((void**)&dev_host, (void*)s->bp_host, 0));
+  s->ev_used = 0;
+  HIP_TRY(hipEventRecord(s->ev_a, st));
+  HIP_TRY(hipMemcpyAsync(s->sbp_len.p, call.h_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
+  if (j.prompted) TTX_TRY(prefix_upload(s, st, call.pre, p->max_len, p->pad_token));
+  SbsPoolArgs& a = j.a;
+  a.C = C; a.K = K; a.max_len = p->max_len; a.ld = j.ld; a.Ls_cap = Ls_cap; a.pad = p->pad_token; a.bos = p->bos_token;
+  a.key = s->sbp_slot.as<int64_t>();
+  a.row_of = reinterpret_cast<int*>(a.key + C); a.level = a.row_of + C; a.nlive = a.row_of + 2 * C; a.nfin = a.row_of + 3 * C;
+  a.pfx_len = a.row_of + 4 * C; a.pfx_src = a.row_of + 5 * C; a.run_acc = a.row_of + 6 * C;
+  a.cand_next = s->bs_cand_next.as<int64_t>(); a.len_next = s->bs_len_next.as<int>(); a.fin_next = s->bs_fin_next.as<uint8_t>();
+  a.phi_next = s->bs_logp_next.as<float>(); a.parent = s->bs_parent.as<int>(); a.parent_draft = s->bs_parent_draft.as<int>();
+  a.cand_src_len = s->bp_cand_len.as<int>();
+  a.len_all = s->sbp_len.as<int>(); a.row_keys = call.d_row_keys; a.pfx_len_src = j.prompted ? s->pfx_len_src.as<int>() : nullptr;
+  j.io = SbsPoolIo{call.d_out, call.d_logp, call.d_gumbel, call.d_src_running};
+  HIP_TRY(hipMemcpyAsync(s->sbp_io.p, &j.io, sizeof(SbsPoolIo), hipMemcpyHostToDevice, st));
+  a.io = s->sbp_io.as<SbsPoolIo>();
+  a.cnt = s->bs_cnt.as<BeamCounters>(); a.host = dev_host; a.dev_summary = s->bp_grp.as<int>();
+  SbsPoolStepArgs& sa = j.sa;
+  sa.logits = s->logits.as<float>(); sa.V = c.vocab_size; sa.slot_of = s->t_slot_of.as<int>(); sa.finished = s->bs_fin.as<uint8_t>();
+  sa.phi = s->bs_logp.as<float>(); sa.gen = s->gen.as<int>(); sa.ld = j.ld; sa.C = C; sa.K = K; sa.pad = p->pad_token; sa.eos = p->eos_token;
+  sa.row_of = a.row_of; sa.level = a.level; sa.nlive = a.nlive; sa.key = a.key; sa.seed = p->seed; sa.inv_T = inv_T;
+  sa.new_cand = a.cand_next; sa.new_phi = a.phi_next; sa.parent = a.parent; sa.new_len = a.len_next; sa.new_finished = a.fin_next;
+  sa.parent_draft = a.parent_draft; sa.nfin = a.nfin;
+  sa.top_k = top_k; sa.top_p = top_p;
+  if (j.prompted) sa.pfx = PrefixTab{s->pfx_tok.as<int>(), p->max_len, a.pfx_len, a.pfx_src};
+  TTX_TRY(launch_sbsp_init(st, a, s->sbs_g.as<float>(), s->sbs_g_next.as<float>(), s->t_src_of.as<int>()));
+  HIP_TRY(hipEventRecord(s->ev_b, st));
+  j.phase = 1;
+  return TTX_OK;
+}
+
+// Encode R new sources (rows first_row .. of the caller's matrix, Ls_new columns of it) and hand them free slots.
+static int sbsp_admit(SbsPoolJob& j, const int64_t* d_src_rows, int ld_src, int R, int Ls_new, int first_row) {
+  ttx_session* s = j.s;
+  hipStream_t st = j.st;
+  TTX_TRY(encode_sources(s, st, d_src_rows, ld_src, R, Ls_new, s->valid_new.as<uint8_t>(), s->memkv_new.as<float>(), s->bp_enc_qkv.as<float>()));
+  SbsPoolFillArgs f{};
+  f.a = sbsp_args(j, j.cur);                  // G = 0 goes where the next iteration reads it
+  f.new_slot = s->bp_new_slot.as<int>(); f.R = R; f.first_row = first_row; f.Ls_new = Ls_new;
+  f.src_valid = s->src_valid.as<uint8_t>(); f.valid_new = s->valid_new.as<uint8_t>();
+  f.memkv = s->memkv.as<float>(); f.memkv_new = s->memkv_new.as<float>(); f.kv_row = s->m->cfg.num_decoder_layers * 2 * s->m->cfg.embedding_dim;
+  TTX_TRY(launch_sbsp_admit(st, f.a, s->bp_new_slot.as<int>(), R, first_row));
+  TTX_TRY(launch_sbsp_fill(st, f));
+  j.admitted_since += R;
+  j.src_tokens_padded += (long long)R * Ls_new;
+  return TTX_OK;
+}
+
+static int sbsp_enqueue_iter(const SbsPoolJob& j, int variant) {
+  ttx_session* s = j.s;
+  hipStream_t st = j.st;
+  const int cur = j.cur, max_len = j.p.max_len;
+  BeamPrepArgs pa{};
+  pa.ld = j.ld; pa.n_cand = j.MC; pa.beam = j.K; pa.dl = 0; pa.N = 1; pa.pad = j.p.pad_token; pa.smart = 0;
+  TTX_TRY(enqueue_bs_prep(s, st, j.MC, pa));
+  TTX_TRY(enqueue_tree_cache(s, st, j.MC, j.Lc, cur, cur ^ 1, nullptr, nullptr, 1, 0));      // fresh candidates (parent -1) inherit nothing
+  TTX_TRY(enqueue_bs_list(s, st, j.MC, 1, 0));
+  StepCtx k = tree_step_ctx(s, j.MC, j.Ls_cap, 1, 0, j.Lc, j.ld, max_len, cur ^ 1, variant);
+  k.src_len = s->bp_cand_len.as<int>();
+  TTX_TRY(run_step(s, st, k, key_capacity(max_len, max_len)));
+  const SbsPoolArgs a = sbsp_args(j, cur);
+  SbsPoolStepArgs sa = j.sa;
+  sa.g = a.g_in; sa.new_g = const_cast<float*>(a.g_out);
+  if (j.masked) TTX_TRY(launch_sbs_step_pool_masked(s, st, sa));
+  else TTX_TRY(launch_sbs_step_pool(s, st, sa));
+  TTX_TRY(launch_sbsp_retire(st, a));
+  return launch_sbsp_publish(st, a);
+}
+
+static int sbsp_launch_iter(SbsPoolJob& j, int n_running) {
+  ttx_session* s = j.s;
+  const int variant = variant_for_rows(s, (long long)std::max(1, n_running), true);
+  int inv_T_bits = 0, top_p_bits = 0;
+  std::memcpy(&inv_T_bits, &j.inv_T, 4); std::memcpy(&top_p_bits, &j.top_p, 4);
+  const GraphKey key{GS_SBS_POOL_ITER, j.C, j.Ls_cap, j.K, j.p.max_len, j.cur, variant, j.p.pad_token, j.p.bos_token, j.p.eos_token,
+                     j.masked ? 1 : 0, j.prompted ? 1 : 0, j.top_k, top_p_bits, inv_T_bits, (int)(unsigned)j.p.seed, (int)(unsigned)(j.p.seed >> 32)};
+  TTX_TRY(graph_replay(s, j.st, s->iter_graphs, key, [&]() -> int { return sbsp_enqueue_iter(j, variant); }));
+  ++j.launched;
+  j.cur ^= 1;
+  j.admitted_since = 0;
+  return TTX_OK;
+}
+
+extern "C" int ttx_sbs_generate_pool(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total, int Ls_all,
+                                     const int32_t* h_len, const int64_t* d_row_keys, int capacity, const ttx_sbs_params* p,
+                                     const ttx_sbs_filter* f, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
+                                     int64_t* d_out, float* d_logp, float* d_gumbel, ttx_sbs_pool_stats* stats, void* stream) {
+  const std::string who = "ttx_sbs_generate_pool";
+  if (!sessions || n_sessions <= 0 || !d_src || S_total < 0 || Ls_all <= 1 || !h_len || !p || !d_out || !d_logp || !d_gumbel || !stats)
+    return fail(TTX_ERR_INVALID, "bad argument to " + who);
+  for (int i = 0; i < n_sessions; ++i) if (!sessions[i]) return fail(TTX_ERR_INVALID, who + ": null session");
+  if (capacity < 1 || capacity > 1024) return fail(TTX_ERR_INVALID, who + ": capacity must lie in [1, 1024]");
+  const ttx_config& c = sessions[0]->m->cfg;
+  const int V = c.vocab_size, K = p->beam_size;
+  if (p->max_len <= 1) return fail(TTX_ERR_INVALID, who + ": max_len must exceed 1");
+  if (K < 1 || K > SBS_MAX_BEAM) return fail(TTX_ERR_INVALID, who + ": beam_size must lie in [1, 32]");
+  if (V > SBS_MAX_V) return fail(TTX_ERR_INVALID, who + ": vocab_size above 1024");
+  if (K > V) return fail(TTX_ERR_INVALID, who + ": beam_size larger than the vocabulary");
+  if ((size_t)K * V * 4 > 150 * 1024) return fail(TTX_ERR_INVALID, who + ": beam_size x vocabulary beyond the selection kernel's LDS image");
+  if (!(p->temperature > 0.0f) || !std::isfinite(p->temperature)) return fail(TTX_ERR_INVALID, who + ": temperature must be finite and > 0");
+  const float inv_T = 1.0f / p->temperature;
+  if (!(inv_T > 0.0f) || !std::isfinite(inv_T)) return fail(TTX_ERR_INVALID, who + ": 1 / temperature is not a positive finite fp32");
+  if (p->pad_token != c.pad_token) return fail(TTX_ERR_INVALID, who + ": generator pad token differs from the model's");
+  if (p->max_len + 2 > c.max_positions) return fail(TTX_ERR_INVALID, who + ": max_len exceeds the positional table");
+  int top_k = 0;
+  float top_p = 1.0f;
+  if (f) {
+    if (f->top_k < 0 || f->top_k > SAMPLE_MAX_KEEP) return fail(TTX_ERR_INVALID, who + ": top_k must be 0 or in [1, 32]");
+    if (!(f->top_p > 0.0f) || !(f->top_p <= 1.0f)) return fail(TTX_ERR_INVALID, who + ": top_p must be in (0, 1]");
+    top_p = f->top_p;
+    top_k = (f->top_k == 0 && f->top_p < 1.0f) ? SAMPLE_MAX_KEEP : f->top_k;
+  }
+  int len_max = 2;
+  for (int i = 0; i < S_total; ++i) {
+    if (h_len[i] < 2 || h_len[i] > Ls_all) return fail(TTX_ERR_INVALID, who + ": source length outside [2, width of the source matrix]");
+    len_max = std::max(len_max, (int)h_len[i]);
+  }
+  const int Ls_cap = pool_slot_width(len_max, c.max_positions);
+  if (Ls_cap > c.max_positions) return fail(TTX_ERR_INVALID, who + ": source longer than the positional table");
+  SbsPoolCall call{};
+  call.h_len = h_len; call.d_row_keys = d_row_keys; call.S_total = S_total; call.d_out = d_out; call.d_logp = d_logp; call.d_gumbel = d_gumbel;
+  TTX_TRY(prefix_validate(who.c_str(), d_prefix, ld_prefix, h_prefix_len, S_total, p->max_len, &call.pre));
+  call.d_src_running = stats->d_src_running_rows;           // the one input of the block
+  *stats = ttx_sbs_pool_stats{};
+  stats->d_src_running_rows = call.d_src_running;
+  if (S_total == 0) return TTX_OK;
+  const PoolShape shape = pool_shape(n_sessions, S_total, S_total, capacity, 8, 1);      // the work list: sources
+  const int n_jobs = shape.n_jobs, C = shape.C;
+  std::vector<int> first(S_total + 1);
+  for (int r = 0; r <= S_total; ++r) first[r] = r;
+  std::vector<SbsPoolJob> jobs(n_jobs);
+  const bool serial = sessions[0]->profile;                    // profiling sessions: one pool after another (see the greedy pool)
+  int cursor = 0;
+  ttx_sbs_pool_stats acc{};
+  acc.d_src_running_rows = call.d_src_running;
+  const auto start = [&](int i) -> int {
+    return sbsp_start(jobs[i], sessions[i], sessions[i]->own_stream, C, Ls_cap, p, inv_T, top_k, top_p, call);
+  };
+  const auto turn = [&](int i) -> int {
+    SbsPoolJob& j = jobs[i];
+    ttx_session* s = j.s;
+    volatile BeamPoolHost* bh = s->bp_host;
+    if (j.phase == 1) {
+      if (j.launched > 0 && bh->steps_done < j.launched) return TURN_WAITING;       // the iteration in flight has not published yet
+      if (bh->error) return fail(TTX_ERR_HIP, "stochastic beam pool bookkeeping failed (admitted more sources than free slots)");
+      int n_live = (j.launched == 0 ? 0 : bh->n_live) + j.admitted_since;
+      int n_running = (j.launched == 0 ? 0 : bh->n_running) + j.admitted_since;
+      if (serial && j.quota_end < 0) j.quota_end = serial_quota(first.data(), S_total, cursor, i, n_jobs);
+      int n_run_jobs = 0;
+      for (const SbsPoolJob& o : jobs) n_run_jobs += (o.phase == 1);
+      const int take = plan_admission(first.data(), S_total, C, {cursor, C - n_live, n_live, j.launched == 0, i, n_jobs, n_run_jobs, serial, j.quota_end});
+      if (take > 0) {
+        TTX_TRY(sbsp_admit(j, d_src + (size_t)cursor * Ls_all, Ls_all, take, chunk_width(h_len, cursor, cursor + take), cursor));
+        cursor += take;
+        n_live += take;
+        n_running += take;
+      }
+      if (n_live == 0) {
+        TTX_TRY(enqueue_readback(s, j.st, s->bs_cnt.p, sizeof(BeamCounters)));
+        j.phase = 2;
+      } else {
+        if (j.launched > (long long)p->max_len * (S_total + 1)) return fail(TTX_ERR_HIP, "stochastic beam pool failed to terminate");
+        j.live_slots += n_live;
+        TTX_TRY(sbsp_launch_iter(j, n_running));
+      }
+      return TURN_PROGRESSED;
+    }
+    if (hipEventQuery(s->ev_done) != hipSuccess) return TURN_IDLE;
+    const BeamCounters* cn = reinterpret_cast<const BeamCounters*>(s->host_state);
+    acc.model_calls += cn->model_calls; acc.running_rows += cn->running_cands; acc.src_tokens_padded += j.src_tokens_padded;
+    acc.live_slots += j.live_slots;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->ev_a, s->ev_c) == hipSuccess) acc.decode_ms += ms;
+    collect_gemm_profile(s, j.st);
+    j.phase = 3;
+    return TURN_FINISHED;
+  };
+  acc.status = drive_sessions(sessions, n_jobs, serial, stream, start, turn);
+  *stats = acc;
+  return acc.status;
+}
+
 // Parity instrumentation: the verify step selected by ttx_gen_params.want_logits (1-based step number) of the most
 // recent generate call on this session: its pre-argmax logits and the loop state they were computed from.
 // All destinations are HOST pointers; sizes: logits [n_active*rps, V], act [n_active], front [B], gen [B, gen_ld].
@@ -4544,6 +4853,124 @@ extern "C" int ttx_debug_bsp(ttx_session* s, int op, const ttx_debug_bsp_args* a
       case OP_BATCHES: rc = launch_bsp_batches(st, p); break;
       case OP_RETIRE: rc = launch_bsp_retire(st, p); break;
       default: rc = launch_bsp_publish(st, p); break;
+    }
+  }
+  if (err == hipSuccess && rc == TTX_OK) err = hipMemcpyAsync(&h, dev, sizeof(Image), hipMemcpyDeviceToHost, st);
+  const hipError_t esync = hipStreamSynchronize(st);
+  (void)hipFree(dev);
+  TTX_TRY(rc);
+  HIP_TRY(err);
+  HIP_TRY(esync);
+  words[0] = h.cnt.model_calls; words[1] = h.cnt.input_lines; words[2] = h.cnt.running_rows; words[3] = h.cnt.verified_positions;
+  words[4] = h.cnt.executed_positions; words[5] = h.cnt.kv_prefix_positions; words[6] = h.cnt.running_cands; words[7] = h.cnt.max_group;
+  words[8] = s->bp_host->steps_done; words[9] = s->bp_host->n_live; words[10] = s->bp_host->n_running; words[11] = s->bp_host->error;
+  return TTX_OK;
+}
+
+// The stochastic beam pool's step kernels, one launch (tests/test_gpu_sbs_pool_kernel.py).
+extern "C" int ttx_debug_sbs_step_pool(ttx_session* s, const ttx_debug_sbs_step_pool_args* a, int masked, int top_k, float top_p,
+                                       const ttx_debug_prefix* pfx, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const std::string w = "ttx_debug_sbs_step_pool";
+  if (!s || !a) return fail(TTX_ERR_INVALID, "null argument to " + w);
+  if (!a->d_logits || !a->d_slot_of || !a->d_finished || !a->d_phi || !a->d_g || !a->d_gen || !a->d_row_of || !a->d_level || !a->d_nlive ||
+      !a->d_key || !a->d_new_cand || !a->d_new_phi || !a->d_new_g || !a->d_parent || !a->d_new_len || !a->d_new_finished || !a->d_parent_draft ||
+      !a->d_nfin)
+    return fail(TTX_ERR_INVALID, w + ": a required array is null");
+  if (a->C < 1 || a->C > 1024 || a->K < 1 || a->K > SBS_MAX_BEAM || a->V < 1 || a->V > SBS_MAX_V)
+    return fail(TTX_ERR_INVALID, w + ": C in [1, 1024], K in [1, 32] and V in [1, 1024]");
+  if (a->K > a->V) return fail(TTX_ERR_INVALID, w + ": K exceeds the V children of a fresh slot");
+  if ((size_t)a->K * a->V * 4 > 150 * 1024) return fail(TTX_ERR_INVALID, w + ": K x vocabulary beyond the kernel's LDS image");
+  if (a->ld < 2) return fail(TTX_ERR_INVALID, w + ": ld must be at least 2");
+  if (!(a->inv_T > 0.0f) || !std::isfinite(a->inv_T)) return fail(TTX_ERR_INVALID, w + ": inv_T must be finite and > 0");
+  if (!masked && (top_k != 0 || top_p != 1.0f || pfx)) return fail(TTX_ERR_INVALID, w + ": a filter or a prefix table needs the masked kernel");
+  if (top_k < 0 || top_k > SAMPLE_MAX_KEEP) return fail(TTX_ERR_INVALID, w + ": top_k must be 0 or in [1, 32]");
+  if (!(top_p > 0.0f) || !(top_p <= 1.0f)) return fail(TTX_ERR_INVALID, w + ": top_p must be in (0, 1]");
+  HIP_TRY(hipSetDevice(s->m->device));
+  HIP_TRY(hipStreamSynchronize(st));
+  std::vector<int32_t> slot((size_t)a->C * 3);
+  HIP_TRY(hipMemcpy(slot.data(), a->d_row_of, (size_t)a->C * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(slot.data() + a->C, a->d_level, (size_t)a->C * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(slot.data() + 2 * a->C, a->d_nlive, (size_t)a->C * 4, hipMemcpyDeviceToHost));
+  for (int b = 0; b < a->C; ++b) {
+    if (slot[b] < 0) continue;
+    if (slot[a->C + b] < 1 || slot[a->C + b] >= a->ld) return fail(TTX_ERR_INVALID, w + ": a live slot's level must lie in [1, ld)");
+    if (slot[2 * a->C + b] < 1 || slot[2 * a->C + b] > a->K) return fail(TTX_ERR_INVALID, w + ": a live slot's parent count must lie in [1, K]");
+  }
+  SbsPoolStepArgs sa{};
+  sa.logits = a->d_logits; sa.V = a->V; sa.slot_of = a->d_slot_of; sa.finished = a->d_finished; sa.phi = a->d_phi; sa.g = a->d_g;
+  sa.gen = a->d_gen; sa.ld = a->ld; sa.C = a->C; sa.K = a->K; sa.pad = a->pad; sa.eos = a->eos;
+  sa.row_of = a->d_row_of; sa.level = a->d_level; sa.nlive = a->d_nlive; sa.key = a->d_key; sa.seed = a->seed; sa.inv_T = a->inv_T;
+  sa.new_cand = a->d_new_cand; sa.new_phi = a->d_new_phi; sa.new_g = a->d_new_g; sa.parent = a->d_parent; sa.new_len = a->d_new_len;
+  sa.new_finished = a->d_new_finished; sa.parent_draft = a->d_parent_draft; sa.nfin = a->d_nfin;
+  if (!masked) return dbg_launched(launch_sbs_step_pool(s, st, sa), st);
+  sa.top_p = top_p;
+  sa.top_k = (top_k == 0 && top_p < 1.0f) ? SAMPLE_MAX_KEEP : top_k;
+  if (pfx) TTX_TRY(dbg_prefix_tab(w.c_str(), pfx, a->C, st, &sa.pfx));
+  return dbg_launched(launch_sbs_step_pool_masked(s, st, sa), st);
+}
+
+// The stochastic beam pool's bookkeeping kernels, one launch per call (ttx_debug_bsp's conventions).
+extern "C" int ttx_debug_sbs_pool(ttx_session* s, int op, const ttx_debug_sbs_pool_args* a, int64_t* words, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const std::string w = "ttx_debug_sbs_pool";
+  enum { OP_INIT, OP_ADMIT, OP_FILL, OP_RETIRE, OP_PUBLISH, OP_COUNT };
+  if (!s || !a || !words) return fail(TTX_ERR_INVALID, "null argument to " + w);
+  if (op < 0 || op >= OP_COUNT) return fail(TTX_ERR_INVALID, w + ": op is 0 (init) .. 4 (publish)");
+  if (!a->d_row_of || !a->d_level || !a->d_nlive || !a->d_nfin || !a->d_key || !a->d_pfx_len || !a->d_pfx_src || !a->d_run_acc || !a->d_cand_next ||
+      !a->d_len_next || !a->d_fin_next || !a->d_phi_next || !a->d_parent || !a->d_parent_draft || !a->d_cand_src_len || !a->d_g_in ||
+      !a->d_g_out || !a->d_len_all || !a->d_out || !a->d_out_logp || !a->d_out_gumbel || !a->d_dev_summary)
+    return fail(TTX_ERR_INVALID, w + ": an array of the pool's argument block is null");
+  if (op == OP_INIT && !a->d_src_of) return fail(TTX_ERR_INVALID, w + ": init needs src_of");
+  if ((op == OP_ADMIT || op == OP_FILL) && !a->d_new_slot) return fail(TTX_ERR_INVALID, w + ": admit and fill need new_slot");
+  if (op == OP_FILL && (!a->d_valid_new || !a->d_src_valid || !a->d_memkv || !a->d_memkv_new))
+    return fail(TTX_ERR_INVALID, w + ": fill needs valid_new, src_valid, memkv and memkv_new");
+  if (a->C < 1 || a->C > 1024 || a->K < 1 || a->K > SBS_MAX_BEAM || a->Ls_cap < 1 || a->max_len < 2 || a->ld < a->max_len)
+    return fail(TTX_ERR_INVALID, w + ": C in [1, 1024], K in [1, 32], Ls_cap >= 1, max_len >= 2 and ld >= max_len");
+  if (op == OP_ADMIT || op == OP_FILL) {
+    if (a->R < 1 || a->first_row < 0 || a->R > a->C) return fail(TTX_ERR_INVALID, w + ": R must lie in [1, C] and first_row >= 0");
+  }
+  if (op == OP_FILL) {
+    if (a->Ls_new < 1 || a->Ls_new > a->Ls_cap) return fail(TTX_ERR_INVALID, w + ": Ls_new must lie in [1, Ls_cap]");
+    if (a->kv_row < 4 || (a->kv_row & 3)) return fail(TTX_ERR_INVALID, w + ": kv_row must be a positive multiple of 4");
+    if (!dbg_aligned16(a->d_memkv) || !dbg_aligned16(a->d_memkv_new)) return fail(TTX_ERR_INVALID, w + ": memkv operands must be 16-byte aligned");
+  }
+  HIP_TRY(hipSetDevice(s->m->device));
+  if (!s->bp_host && hipHostMalloc((void**)&s->bp_host, sizeof(BeamPoolHost), hipHostMallocMapped) != hipSuccess)
+    return fail(TTX_ERR_NOMEM, "hipHostMalloc failed");
+  BeamPoolHost* dev_host = nullptr;
+  HIP_TRY(hipHostGetDevicePointer((void**)&dev_host, (void*)s->bp_host, 0));
+  HIP_TRY(hipStreamSynchronize(st));                    // nothing in flight reads the pinned words while the image goes in
+  s->bp_host->steps_done = (int)words[8]; s->bp_host->n_live = (int)words[9]; s->bp_host->n_running = (int)words[10];
+  s->bp_host->error = (int)words[11];
+  struct Image { BeamCounters cnt; SbsPoolIo io; };
+  Image* dev = nullptr;
+  HIP_TRY(hipMalloc((void**)&dev, sizeof(Image)));
+  Image h{};
+  h.cnt.model_calls = words[0]; h.cnt.input_lines = words[1]; h.cnt.running_rows = words[2]; h.cnt.verified_positions = words[3];
+  h.cnt.executed_positions = words[4]; h.cnt.kv_prefix_positions = words[5]; h.cnt.running_cands = words[6]; h.cnt.max_group = (int)words[7];
+  h.io = SbsPoolIo{a->d_out, a->d_out_logp, a->d_out_gumbel, a->d_src_running};
+  hipError_t err = hipMemcpyAsync(dev, &h, sizeof(Image), hipMemcpyHostToDevice, st);
+  int rc = TTX_OK;
+  if (err == hipSuccess) {
+    SbsPoolFillArgs f{};
+    SbsPoolArgs& p = f.a;
+    p.C = a->C; p.K = a->K; p.max_len = a->max_len; p.ld = a->ld; p.Ls_cap = a->Ls_cap; p.pad = a->pad; p.bos = a->bos;
+    p.row_of = a->d_row_of; p.level = a->d_level; p.nlive = a->d_nlive; p.nfin = a->d_nfin; p.key = a->d_key; p.pfx_len = a->d_pfx_len;
+    p.pfx_src = a->d_pfx_src; p.run_acc = a->d_run_acc;
+    p.cand_next = a->d_cand_next; p.len_next = a->d_len_next; p.fin_next = a->d_fin_next; p.phi_next = a->d_phi_next; p.parent = a->d_parent;
+    p.parent_draft = a->d_parent_draft; p.cand_src_len = a->d_cand_src_len; p.g_in = a->d_g_in; p.g_out = a->d_g_out;
+    p.len_all = a->d_len_all; p.row_keys = a->d_row_keys; p.pfx_len_src = a->d_pfx_len_src;
+    p.io = &dev->io;
+    p.cnt = &dev->cnt; p.host = dev_host; p.dev_summary = a->d_dev_summary;
+    f.new_slot = a->d_new_slot; f.R = a->R; f.first_row = a->first_row; f.Ls_new = a->Ls_new;
+    f.src_valid = a->d_src_valid; f.valid_new = a->d_valid_new; f.memkv = a->d_memkv; f.memkv_new = a->d_memkv_new; f.kv_row = a->kv_row;
+    switch (op) {
+      case OP_INIT: rc = launch_sbsp_init(st, p, a->d_g_in, a->d_g_out, a->d_src_of); break;
+      case OP_ADMIT: rc = launch_sbsp_admit(st, p, a->d_new_slot, a->R, a->first_row); break;
+      case OP_FILL: rc = launch_sbsp_fill(st, f); break;
+      case OP_RETIRE: rc = launch_sbsp_retire(st, p); break;
+      default: rc = launch_sbsp_publish(st, p); break;
     }
   }
   if (err == hipSuccess && rc == TTX_OK) err = hipMemcpyAsync(&h, dev, sizeof(Image), hipMemcpyDeviceToHost, st);

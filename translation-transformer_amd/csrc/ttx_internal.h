@@ -76,6 +76,7 @@ enum AttnKernelId { AK_ATTN = 1, AK_ATTN2 = 2, AK_ATTN3 = 3, AK_ATTN3S = 4, AK_A
 //   verify step (GS_STEP_*)       B, Ls, N, D, max_len, key capacity, GemmVariant, phase (slot pool: 0 the whole step in one pass,
 //                                 1 probe, 2 draft pass + accept, 3 accept alone; 4, 5, 6: the same three under draft select; else 0)
 //   GS_BEAM_ITER, GS_BEAM_POOL_ITER   see beam_launch_iter / bpool_launch_iter
+//   GS_SBS_POOL_ITER              see sbsp_launch_iter: a site of its own, never a graph of the beam-speculative pool
 //   GS_STEP_SAMPLE                the greedy step's key with k_sample in k_argmax's place (ttx_sample_generate); B counts decoder rows
 //   GS_STEP_SAMPLE_SPEC           the speculative step's key with k_sample_step and k_sample_accept in k_argmax's and k_accept's place
 //                                 (ttx_sample_speculative_generate); B counts decoder rows
@@ -89,7 +90,7 @@ enum AttnKernelId { AK_ATTN = 1, AK_ATTN2 = 2, AK_ATTN3 = 3, AK_ATTN3S = 4, AK_A
 enum GraphSite { GS_STEP_SPECULATIVE = 0, GS_STEP_GREEDY = 1, GS_STEP_ROW_RULE = 2, GS_STEP_POOL = 3, GS_BEAM_ITER = 4, GS_BEAM_POOL_ITER = 5,
                  GS_STEP_SAMPLE = 6, GS_STEP_SAMPLE_SPEC = 7, GS_STEP_POOL_SAMPLE = 8,
                  GS_STEP_SAMPLE_PREFIX = 9, GS_STEP_SAMPLE_SPEC_PREFIX = 10, GS_STEP_POOL_SAMPLE_PREFIX = 11,
-                 GS_STEP_SAMPLE_SPEC_PROPOSAL = 12, GS_STEP_POOL_SAMPLE_PROPOSAL = 13 };
+                 GS_STEP_SAMPLE_SPEC_PROPOSAL = 12, GS_STEP_POOL_SAMPLE_PROPOSAL = 13, GS_SBS_POOL_ITER = 14 };
 typedef std::vector<int> GraphKey;
 
 // Captured graphs of one family of keys.  A key runs eagerly the first time it is seen (`warmed`: function attributes are set
@@ -150,7 +151,10 @@ struct GraphCache {
   /* (slot) its prefix length, its row of the table (pool; single-session loops use smp_src_of) and its source draft 0 [D] */     \
   X(pfx_tok) X(pfx_len_src) X(pfx_len) X(pfx_src) X(pfx_draft0)                                                                  \
   /* stochastic beam search (ttx_sbs_generate): the perturbed log-probabilities G of the candidates, read and written in turn */  \
-  X(sbs_g) X(sbs_g_next)
+  X(sbs_g) X(sbs_g_next)                                                                                                         \
+  /* stochastic beam pool (ttx_sbs_generate_pool): the per-slot words (keys, then six int arrays), the sources' lengths and the */ \
+  /* call's output pointers (SbsPoolIo) */                                                                                        \
+  X(sbp_slot) X(sbp_len) X(sbp_io)
 #define TTX_DECLARE_BUF(name) Buf name;
 #define TTX_REGISTER_BUF(name) all.push_back(&name);
 
@@ -187,6 +191,7 @@ struct ttx_session {
   bool attr_attn2[2][8] = {};      // [head dimension 32 / 64][mode]
   bool attr_select = false, attr_step = false, attr_topk = false, attr_pool_select = false, attr_sbs_step = false;
   bool attr_sbs_step_masked[5] = {};   // k_sbs_step_masked<VPL>, VPL = 1, 2, 4, 8, 16
+  bool attr_sbs_step_pool = false, attr_sbs_step_pool_masked[5] = {};   // the pool forms of the two
   bool attr_attn_probs[8] = {};    // k_attn_probs: [head dimension 32 / 64][16-byte output stores][16-byte key loads]
   // GEMM policy (all choices are between bit-identical evaluations, see GemmVariant)
   int qkv_small_rows = 800;        // a verify step with fewer live rows than this runs under GV_SMALL (TTX_QKV_SMALL_ROWS)

@@ -32,6 +32,10 @@
 // up to 32 dependent selection rounds per parent row are the cost, so the kernel runs 4, 8 or 16 waves per source (by the beam):
 // a wave still owns whole parent rows, and the K selection rounds take their partial winners from as many waves; no sum or maximum
 // changes its order with the wave count.
+//
+// Both kernels have a pool form in csrc/ttx_sbs_pool.hip.h (k_sbs_step_pool, k_sbs_step_pool_masked): the same statements with pos,
+// width, the parent count and the key read per slot.  A change to the rule here is made there as well;
+// tests/test_gpu_sbs_pool_kernel.py holds the two to the same bits.
 #pragma once
 #include "ttx_sample.hip.h"
 

@@ -718,7 +718,8 @@ class TranslationInferenceStochasticBeamSearch(_ScoresHypotheses):
     replacement from the sequence distribution the filtered sampler draws from; fewer than K rows may exist (``top_k=1`` has one:
     the greedy row), and the missing ranks come back finished with ``logp = gumbel = -inf``.  A filter or a ``prefix`` runs
     ttx_sbs_generate_ex (k_sbs_step_masked); a call with neither is ttx_sbs_generate, launch for launch.
-    No ``generate_many``.  ``scoring.sbs_weights`` turns ``logp`` and ``gumbel`` of a K + 1 call into importance weights, of the
+    ``generate_many`` decodes a whole list of batches on a pool of source slots (ttx_sbs_generate_pool) and returns, bit for bit,
+    the rows of the per-batch calls.  ``scoring.sbs_weights`` turns ``logp`` and ``gumbel`` of a K + 1 call into importance weights, of the
     filtered / conditional distribution when a filter / prefix is on."""
 
     def __init__(self, model, beam_size: int, max_len: int, pad_token: int, bos_token: int, eos_token: int,
@@ -731,6 +732,8 @@ class TranslationInferenceStochasticBeamSearch(_ScoresHypotheses):
         self.model_calls_num = 0
         self.given_tokens = 0
         self.b_sz = 0
+        self.last_stats: N.SbsPoolStats | None = None       # of the most recent generate_many
+        self.last_batch_counters: list = []                 # generate_many: what each batch added to the counter attributes
 
     def __str__(self):
         return (f"Stochastic beam search (beam_size={self.beam_size}, temperature={self.temperature}, top_k={self.top_k}, "
@@ -801,6 +804,148 @@ class TranslationInferenceStochasticBeamSearch(_ScoresHypotheses):
                 tr = SbsTrace(*(t[:int(st.model_calls)] for t in tr))
             res.append(SbsDetails(logp, gumbel, ended, tr))
         return res[0] if len(res) == 1 else tuple(res)
+
+    def _pool_plan(self, S: int, in_flight: int, capacity: int | None) -> tuple:
+        """(source slots per pool, sessions): a given ``capacity`` or TTX_POOL_CAPACITY counts sources; the default is the greedy
+        pool's row plan for the ``S * K`` decoder rows, divided by K (DESIGN.md §24 has the sweep behind it)."""
+        K = max(self.beam_size, 1)
+        given = capacity if capacity is not None else (os.environ.get("TTX_POOL_CAPACITY") or None)
+        if given is not None and not 1 <= int(given) <= 1024:
+            raise ValueError(f"capacity (source slots per pool) must lie in [1, 1024], got {given}")
+        # the pool count follows the decoder rows a pool holds, whichever way the capacity was given
+        rows_cap, n_sess = _slot_pool_plan(S * K, in_flight, None if given is None else int(given) * K)
+        return (int(given) if given is not None else min(1024, max(1, rows_cap // K))), n_sess
+
+    def generate_many(self, batches: list, row_keys=None, in_flight: int = 4, capacity: int | None = None,
+                      return_scores: bool = False, return_details: bool = False, order: str = "sample", prefixes=None) -> list:
+        """``generate`` over a whole list of batches on pools of source slots (ttx_sbs_generate_pool: continuous batching over the
+        sources of the list, sorted by length).  A source leaves the pool as soon as its K rows are finished and the next one
+        takes its slot, so a decoder pass serves unfinished candidates only.  Returns one entry per batch, shaped as ``generate``
+        returns it (a tensor, or a tuple with ``HypothesisScores`` and / or ``SbsDetails``, whose ``trace`` is ``None``: the pool
+        keeps none).
+
+        ``generate_many(batches, row_keys=ks, prefixes=ps)[i]`` equals ``generate(batches[i], row_keys=ks[i], prefix=ps[i])`` bit
+        for bit: tokens, ``logp`` and ``gumbel``, whatever the capacity, ``in_flight``, the order of the list or the batching
+        (include/ttx.h states the contract and its range).  ``row_keys``: one sequence of integers per batch; by default the
+        running index over the concatenated batches.  ``prefixes``: a list aligned with ``batches``, each entry a ``prefix`` for
+        that batch or ``None``.  ``capacity``: source slots per pool (``TTX_POOL_CAPACITY``), at most 1 024; ``in_flight``: pools
+        at once.  ``model_calls_num`` counts the decoder passes the device executed, ``b_sz`` the unfinished candidates they
+        served; ``last_batch_counters`` holds each batch's share of the counters (``b_sz`` and ``given_tokens`` as ``generate`` counts
+        them for that batch, the decoder passes apportioned by candidates)."""
+        from .scheduling import plan_row_groups
+        if order not in ("sample", "logp"):
+            raise ValueError(f"order must be 'sample' or 'logp', got {order!r}")
+        self._pool_plan(1, in_flight, capacity)               # refuses a capacity outside [1, 1024] before anything else
+        if prefixes is not None and len(prefixes) != len(batches):
+            raise ValueError(f"prefixes must hold one entry per batch ({len(batches)}), got {len(prefixes)}")
+        if row_keys is not None and len(row_keys) != len(batches):
+            raise ValueError(f"row_keys must hold one sequence per batch ({len(batches)}), got {len(row_keys)}")
+        if not batches:
+            return []
+        m, K, L = self.model, self.beam_size, self.max_len
+        sizes = [int(b.shape[0]) for b in batches]
+        S = sum(sizes)
+        if row_keys is None:
+            keys = torch.arange(S, dtype=torch.int64)
+        else:
+            per = [torch.as_tensor(k, dtype=torch.int64).reshape(-1).cpu() for k in row_keys]
+            for i, (k, B) in enumerate(zip(per, sizes)):
+                if k.shape != (B,):
+                    raise ValueError(f"row_keys[{i}] must hold one key per source ({B}), got shape {tuple(k.shape)}")
+            keys = torch.cat(per) if per else torch.zeros(0, dtype=torch.int64)
+        allpre = plen = None
+        if prefixes is not None and any(q is not None for q in prefixes):
+            checked = [check_prefix(q, B, L, self.pad_token, m.tgt_vocab_size) for q, B in zip(prefixes, sizes)]
+            Lp = max([int(c[0].shape[1]) for c in checked if c[0] is not None] or [0])
+            allpre = torch.full((S, Lp), self.pad_token, dtype=torch.int64)
+            plen = torch.zeros(S, dtype=torch.int64)
+            r0 = 0
+            for (q, lens), B in zip(checked, sizes):
+                if q is not None:
+                    allpre[r0:r0 + B, :q.shape[1]] = q
+                    plen[r0:r0 + B] = torch.tensor(lens, dtype=torch.int64)
+                r0 += B
+            if not bool(plen.any()):
+                allpre = plen = None
+        srcs = [b.to(m.device, torch.int64) for b in batches]
+        Lmax = max([int(s.shape[1]) for s in srcs if s.shape[0]] or [2])
+        allsrc = torch.full((S, Lmax), self.pad_token, dtype=torch.int64, device=m.device)
+        r0 = 0
+        for s in srcs:
+            allsrc[r0:r0 + s.shape[0], :s.shape[1]] = s
+            r0 += s.shape[0]
+        m.check_tokens(allsrc)
+        cap, n_sess = self._pool_plan(S, in_flight, capacity)
+        self.last_group_size, self.last_pool_sessions = cap, n_sess
+        p = N.SbsParams(L, K, self.temperature, self.pad_token, self.bos_token, self.eos_token, self.seed & 0xFFFFFFFFFFFFFFFF)
+        filt = N.SbsFilter(self.top_k, self.top_p)
+        Kc, Lc = max(K, 1), max(L, 2)
+        out_sorted = torch.empty((S, Kc, Lc), dtype=torch.int64, device=m.device)
+        logp_sorted = torch.empty((S, Kc), dtype=torch.float32, device=m.device)
+        gumbel_sorted = torch.empty((S, Kc), dtype=torch.float32, device=m.device)
+        st = N.SbsPoolStats()
+        per_src = torch.zeros(max(S, 1), dtype=torch.int32, device=m.device)     # candidates decoded per source, in the pool's order
+        st.d_src_running_rows = per_src.data_ptr()
+        if S:
+            pos = torch.arange(1, Lmax + 1, device=m.device)
+            lengths = ((allsrc != self.pad_token) * pos).amax(dim=1)
+            order_np, _ = plan_row_groups(lengths.cpu().numpy(), cap * Kc)
+            order_t = torch.from_numpy(order_np).to(m.device)
+            sorted_len = lengths[order_t].cpu().numpy()
+            width = max(2, int(sorted_len.max()))
+            sorted_src = allsrc[order_t]
+            src_mat = sorted_src[:, :width].contiguous() if width <= Lmax else torch.nn.functional.pad(
+                sorted_src, (0, width - Lmax), value=self.pad_token).contiguous()
+            keys_sorted = keys.to(m.device)[order_t].contiguous()
+            h_len = (C.c_int32 * S)(*[max(2, int(x)) for x in sorted_len])
+            sessions = m.session_pool(n_sess)
+            sess = (C.c_void_p * len(sessions))(*[q.value for q in sessions])
+            d_prefix = prefix_ptr = h_plen = None            # d_prefix keeps the device tensor alive until the call returns
+            ld_prefix = 0
+            if allpre is not None:
+                order_cpu = torch.from_numpy(order_np).to(torch.int64)
+                d_prefix = allpre[order_cpu].contiguous().to(m.device)
+                prefix_ptr, ld_prefix = (d_prefix.data_ptr() if d_prefix.numel() else None), int(d_prefix.shape[1])
+                h_plen = (C.c_int32 * S)(*[int(x) for x in plen[order_cpu]])
+            N.check(m._lib.ttx_sbs_generate_pool(sess, len(sessions), src_mat.data_ptr(), S, width, h_len, keys_sorted.data_ptr(), cap,
+                                                 C.byref(p), C.byref(filt), prefix_ptr, ld_prefix, h_plen, out_sorted.data_ptr(),
+                                                 logp_sorted.data_ptr(), gumbel_sorted.data_ptr(), C.byref(st), m._stream()))
+            inv = torch.empty_like(order_t)
+            inv[order_t] = torch.arange(S, device=m.device)
+            out_rows, logp_rows, gumbel_rows = out_sorted[inv], logp_sorted[inv], gumbel_sorted[inv]
+            per_src = per_src[inv]
+            self.given_tokens += int((allsrc != m.src_pad_token_i).sum())
+        else:
+            out_rows, logp_rows, gumbel_rows = out_sorted, logp_sorted, gumbel_sorted
+        self.model_calls_num += int(st.model_calls)
+        self.b_sz += int(st.running_rows)
+        self.last_stats = st
+        # what each batch added to the counters (a look-ahead that falls back takes them back): its sources' tokens, the candidates
+        # decoded for its sources (exactly what generate(batch) counts), and the call's decoder passes apportioned by those
+        # candidates (largest remainder: the shares sum to the call's count, which serves every batch at once)
+        rows_of = [int(x) for x in torch.stack([c.sum() for c in torch.split(per_src[:S].long(), sizes)]).cpu()] if S else [0] * len(sizes)
+        total_rows, calls = max(1, sum(rows_of)), int(st.model_calls)
+        quota = [calls * r // total_rows for r in rows_of]
+        for i in sorted(range(len(sizes)), key=lambda i: -(calls * rows_of[i] % total_rows))[:calls - sum(quota)]:
+            quota[i] += 1
+        self.last_batch_counters = [{"model_calls_num": q, "b_sz": r, "given_tokens": int((b != m.src_pad_token_i).sum())}
+                                    for q, r, b in zip(quota, rows_of, srcs)]
+        res, r0 = [], 0
+        for src, B in zip(srcs, sizes):
+            out, logp, gumbel = out_rows[r0:r0 + B].contiguous(), logp_rows[r0:r0 + B].contiguous(), gumbel_rows[r0:r0 + B].contiguous()
+            r0 += B
+            if order == "logp":
+                idx = torch.argsort(logp, dim=1, descending=True, stable=True)
+                out = torch.gather(out, 1, idx[:, :, None].expand_as(out))
+                logp, gumbel = torch.gather(logp, 1, idx), torch.gather(gumbel, 1, idx)
+            entry = [out]
+            if return_scores:
+                entry.append(self.score(src, out) if B else None)
+            if return_details:
+                ended = ((out[:, :, 1:] == self.eos_token) | (out[:, :, 1:] == self.pad_token)).any(-1) | torch.isinf(gumbel)
+                entry.append(SbsDetails(logp, gumbel, ended, None))
+            res.append(entry[0] if len(entry) == 1 else tuple(entry))
+        return res
 
 
 class TranslationInferenceBeamSearchSpeculative(_ScoresHypotheses):

@@ -125,9 +125,10 @@ class _PredictAhead:
             return
         g = self.generator
         prompted = any(q is not None for q in prefixes)
-        if prompted and not isinstance(g, D.TranslationInferenceSamplingSpeculative):
-            raise ValueError(f'"prefix_tokens" in a batch: only generation="sampling" and "sampling_speculative" take forced prefixes, '
-                             f"not {type(g).__name__}")
+        keyed = isinstance(g, (D.TranslationInferenceSamplingSpeculative, D.TranslationInferenceStochasticBeamSearch))
+        if prompted and not keyed:
+            raise ValueError(f'"prefix_tokens" in a batch: only generation="sampling", "sampling_speculative" and '
+                             f'"stochastic_beam_search" take forced prefixes, not {type(g).__name__}')
         proposed = any(q is not None for q in proposals)     # offered drafts: they change no row, so take() does not compare them
         if proposed and not isinstance(g, D.TranslationInferenceSamplingSpeculative):
             raise ValueError(f'"proposal_tokens" in a batch: only generation="sampling_speculative" takes proposals, '
@@ -135,13 +136,13 @@ class _PredictAhead:
         t0 = timer()
         if isinstance(g, D.TranslationInferenceGreedySpeculative):      # slot pools over all rows of the window
             preds = g.generate_many(pending, in_flight=self.in_flight, reorder=True, on_error="skip")
-        elif isinstance(g, D.TranslationInferenceSamplingSpeculative):  # slot pools over all sources, keyed as predict_step keys them
+        elif keyed:                 # pools over all sources of the window, keyed as predict_step keys them: the running source index
             keys, r0 = [], self.rows
             for b in pending:
                 keys.append(torch.arange(r0, r0 + int(b.shape[0])))
                 r0 += int(b.shape[0])
-            preds = g.generate_many(pending, row_keys=keys, in_flight=self.in_flight, prefixes=prefixes if prompted else None,
-                                    proposals=proposals if proposed else None)
+            more = {"proposals": proposals} if proposed else {}
+            preds = g.generate_many(pending, row_keys=keys, in_flight=self.in_flight, prefixes=prefixes if prompted else None, **more)
             self.rows = r0
         else:                                                           # source pools over all sources of the window
             preds = g.generate_many(pending, in_flight=self.in_flight, on_error="skip")
@@ -332,7 +333,7 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
                              f'not "{self.hparams.generation}"')
         if ahead is not None and dataloader_idx == 0:
             pred = ahead.take(batch["src_tokens"], batch_idx, prefix)
-        if pred is not None and self.hparams.generation in ("sampling", "sampling_speculative"):
+        if pred is not None and self.hparams.generation in ("sampling", "sampling_speculative", "stochastic_beam_search"):
             self._predict_rows += int(batch["src_tokens"].shape[0])        # served ahead under these keys: a fallback goes on from here
         elif pred is None and self.hparams.generation in ("sampling", "sampling_speculative"):
             B = int(batch["src_tokens"].shape[0])
@@ -433,8 +434,10 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         self._attention_seconds = 0.0
         self._scoring_seconds, self._top1_n, self._top1_sum, self._unfinished = 0.0, 0, 0.0, 0
         window = int(os.environ.get("TTX_PREDICT_WINDOW", str(self.predict_window)))
-        # speculative sampling decodes per batch unless asked to pool: predict_sample_pool / TTX_PREDICT_SAMPLE_POOL=1
-        pooled = not isinstance(self.generator, D.TranslationInferenceSamplingSpeculative) or bool(self.predict_sample_pool) \
+        # speculative sampling and stochastic beam search decode per batch unless asked to pool: predict_sample_pool /
+        # TTX_PREDICT_SAMPLE_POOL=1
+        per_batch = (D.TranslationInferenceSamplingSpeculative, D.TranslationInferenceStochasticBeamSearch)
+        pooled = not isinstance(self.generator, per_batch) or bool(self.predict_sample_pool) \
             or os.environ.get("TTX_PREDICT_SAMPLE_POOL") == "1"
         if window > 0 and pooled and hasattr(self.generator, "generate_many"):
             loader = self._predict_loader()

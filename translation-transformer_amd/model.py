@@ -579,6 +579,42 @@ class NativeTransformer:
         N.check(self._lib.ttx_debug_bsp(self._session, code, C.byref(a), w, self._stream()))
         return [int(v) for v in w]
 
+    def debug_sbs_step_pool(self, *, V: int, ld: int, C_: int, K: int, pad: int, eos: int, seed: int, inv_T: float, masked: bool = False,
+                            top_k: int = 0, top_p: float = 1.0, pfx_tok=None, pfx_len=None, pfx_src=None, pfx_ld: int = 0,
+                            pfx_sources: int = 0, **arrays) -> None:
+        """One k_sbs_step_pool (``masked`` false) or k_sbs_step_pool_masked launch (ttx_debug_sbs_step_pool) over ``C_`` slots:
+        candidate arrays [C_ * K], slot arrays ``row_of``, ``level``, ``nlive``, ``key``, ``nfin`` [C_]; the prefix table by slot."""
+        a = N.DebugSbsStepPoolArgs()
+        for name in a.POINTERS:
+            t = arrays.pop(name[2:], None)
+            setattr(a, name, None if t is None else t.data_ptr())
+        assert not arrays, f"unknown operands {sorted(arrays)}"
+        for name, v in dict(V=V, ld=ld, C=C_, K=K, pad=pad, eos=eos).items():
+            setattr(a, name, int(v))
+        a.seed, a.inv_T = int(seed) & 0xFFFFFFFFFFFFFFFF, float(inv_T)
+        pfx = None
+        if pfx_tok is not None or pfx_len is not None or pfx_src is not None:
+            pfx = C.byref(N.DebugPrefix(self._ptr(pfx_tok), int(pfx_ld), int(pfx_sources), self._ptr(pfx_len), self._ptr(pfx_src)))
+        N.check(self._lib.ttx_debug_sbs_step_pool(self._session, C.byref(a), int(bool(masked)), int(top_k), float(top_p), pfx,
+                                                  self._stream()))
+
+    def debug_sbs_pool(self, op: str, words, *, C_: int, K: int, max_len: int, ld: int, Ls_cap: int, pad: int, bos: int, R: int = 0,
+                       first_row: int = 0, kv_row: int = 0, Ls_new: int = 0, **arrays) -> list:
+        """One launch of a bookkeeping kernel of the stochastic beam pool (ttx_debug_sbs_pool); ``op`` one of
+        _native.DEBUG_SBS_POOL_OPS.  ``words`` as for ``debug_bsp``; returns the 12 as the kernel left them."""
+        w = (C.c_int64 * N.DEBUG_BSP_WORDS)(*[int(v) for v in words])
+        a = N.DebugSbsPoolArgs()
+        for name in a.POINTERS:
+            t = arrays.pop(name[2:], None)
+            setattr(a, name, None if t is None else t.data_ptr())
+        assert not arrays, f"unknown operands {sorted(arrays)}"
+        for name, v in dict(C=C_, K=K, max_len=max_len, ld=ld, Ls_cap=Ls_cap, pad=pad, bos=bos, R=R, first_row=first_row, kv_row=kv_row,
+                            Ls_new=Ls_new).items():
+            setattr(a, name, int(v))
+        code = op if isinstance(op, int) else N.DEBUG_SBS_POOL_OPS.index(op)
+        N.check(self._lib.ttx_debug_sbs_pool(self._session, code, C.byref(a), w, self._stream()))
+        return [int(v) for v in w]
+
     def debug_kvcopy(self, rec: torch.Tensor, n_copy: int, qkv: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor,
                      n: int, d: int, width: int, B: int) -> None:
         """One k_kvcopy launch (ttx_debug_kvcopy): ``rec`` int32 [B, 5], ``qkv`` fp32 [Ld, B * (1 + n*d), 3 * width], the caches
