@@ -289,9 +289,69 @@ typedef struct ttx_sample_params {
  * Limits: vocab_size <= 1024; at most 32 kept tokens when a filter is on.  TTX_ERR_INVALID with nothing launched: vocab_size >
  * 1024, num_samples < 1, temperature < 0 or not finite, top_k outside {0, 1..32}, top_p outside (0, 1] or not finite, and
  * everything ttx_greedy_generate refuses.  Per-token log-probabilities are not produced: ttx_score_hypotheses on the samples gives
- * them on the scale of every other generator. */
+ * them on the scale of every other generator (log p under the model), ttx_score_proposal under the distribution sampled from
+ * (log q, below). */
 int ttx_sample_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sample_params* p,
                         int64_t* d_out, ttx_gen_stats* stats, void* stream);
+
+/* Log-probability of hypotheses under the SAMPLING distribution q (temperature, top-k, top-p), where ttx_score_hypotheses gives it
+ * under the model p.  A distribution is (temperature, top_k, top_p) with ttx_sample_params' limits and defaults: temperature >= 0
+ * and finite (0 = greedy), top_k 0 or 1..32, top_p in (0, 1]; top_p < 1 with top_k = 0 runs with top_k = 32. */
+typedef struct ttx_dist { float temperature; int32_t top_k; float top_p; } ttx_dist;
+
+/* The quantity.  Hypothesis rows, logits, n (= length) and finished are those of ttx_score_hypotheses; T = W - 1; for a row h and a
+ * position p = t - 1 < n, x is the fp32 logits row of position p and tok_logq[p] is the log of the probability that steps 2-5 of
+ * ttx_sample_generate's rule emit h[t] from x, ignoring the rounding of the inverse CDF (step 5 compares fp32 prefix sums with
+ * u * S; this is the ratio e_t / S those sums approximate):
+ *   temperature == 0   0.0f if h[t] is k_argmax's token (the first maximum of x), else -inf.
+ *   otherwise          y_v = __fmul_rn(x_v, inv_T): the sampler's product, inv_T = 1.0f / temperature formed on the host.
+ *   no filter          tok_logq = -(log1pf(rs) + (m - y_t)), where m is the row maximum of y and rs the sum of expf(y_v - m) over
+ *                      every v but the first maximum: the arithmetic and summation order of the scoring stage (tok_logp) on y.
+ *   filter on          the kept set is the sampler's on the bits (the same device function selects it): ranks best first, equal
+ *                      values the lower id first, rank i kept while i < top_k and the softmax mass ranked above it is < top_p,
+ *                      rank 0 always.  e_r = expf(y_r - m) for the kept ranks r = 0..n_kept-1, S the last element of their
+ *                      inclusive prefix sums in rank order (Hillis-Steele over the 64 lanes, offsets 1, 2, .., 32: the very S the
+ *                      sampler multiplies u by).  For a kept h[t]: tok_logq = (y_t - m) - logf(S); for any other: -inf.
+ *   forced positions   p < forced_len[r] (d_forced_len int32 [R], NULL = all 0; clamped to [0, n] by the kernel): exactly 0.0f and
+ *                      inside the support, the logits are not read.  This is what the prompted samplers and the prompted
+ *                      stochastic beam search do at a prefix position: the prefix token, no draw, no cost.
+ *   p >= n             exactly 0.0f.
+ * Per row:  logq = the sum of tok_logq[0..n-1] in position order, accumulated in double, rounded once; -inf as soon as one term is.
+ *           first_outside (int32) = the first p < n with tok_logq[p] == -inf (the token cannot be emitted there), else -1.
+ * Per position, optional (NULL: not computed), int32 [R,T]:
+ *   rank    the number of v with y_v > y_t, or y_v == y_t and v < t: the rule of ttx_score_alternatives on y (on x at temperature 0).
+ *   n_kept  the size of the kept set: V without a filter, 1 at temperature 0.  Under a filter a token is kept iff rank < n_kept,
+ *           and a token with rank == n_kept sits just outside the nucleus.
+ *   Forced positions and positions p >= n hold rank = -1 and n_kept = 0.
+ * With temperature 1, no filter and no forced_len, tok_logq / logq are tok_logp / score of the scoring pair (ttx_score_proposal
+ * runs that very kernel; ttx_hypothesis_logq gives its bits for V % 4 == 0 on a 16-byte aligned d_logits wherever the scoring
+ * stage gives a number).  A -inf logit is an ordinary value with probability 0.  A finite logit so far below the maximum that
+ * expf(y_t - m) underflows to 0 (about 103 or more below it in y) is never emitted by the sampler, which requires e_t > 0; the
+ * formulas above still give it its finite, very negative value rather than -inf.
+ * CAVEAT.  These are the TEACHER-FORCED logits.  A row that a sampler drew from its decode-time logits can get -inf here when one
+ * of its tokens sat on the boundary of the nucleus: the decode loop and the teacher-forced pass run different attention kernels
+ * and agree to rounding only, so the last kept rank can differ between them.  rank and n_kept show that case:
+ * first_outside = p with rank[p] == n_kept[p] is a boundary token, not a row the sampler could not have drawn.
+ * A row that ended on a SAMPLED PAD is not finished under the length rule above: that last draw lies at position n, is not scored,
+ * and is not part of logq (a search that accumulated its own log q, such as ttx_sbs_generate's logp, includes it).
+ * Nothing is synchronised, nothing is atomic, two calls give the same bits, and a position's outputs depend on its own logits row
+ * and the hypothesis alone (not on R, the batch or a d_logits base that is or is not 16-byte aligned).  d_logq and d_length are
+ * required, every other output is optional.  TTX_ERR_INVALID with nothing launched: the limits of the scoring pair, a NULL or
+ * out-of-range distribution (temperature < 0 or not finite, 1 / temperature not a positive finite fp32, top_k outside {0, 1..32},
+ * top_p outside (0, 1]).  Negative forced_len entries live on the device and cannot be refused without a synchronisation: they are
+ * clamped to 0.
+ * ttx_hypothesis_logq: the stage alone over caller-provided logits fp32 [R,W-1,V]; d_hyp int64 [R,W].
+ * ttx_score_proposal: exactly the pass of ttx_score_hypotheses (d_hyp rows of stride ld_hyp >= W, d_logits [B*N,W-1,V] or NULL for
+ * session scratch), then the stage; d_score (and with it d_tok_logp) optionally receive ttx_score_hypotheses' outputs from the same
+ * decoder pass, so that p and q of a row come from one pass. */
+int ttx_hypothesis_logq(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad, int eos,
+                        const ttx_dist* dist, const int32_t* d_forced_len, float* d_tok_logq, float* d_logq,
+                        int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept, int32_t* d_length, uint8_t* d_finished,
+                        void* stream);
+int ttx_score_proposal(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N, int W, int eos,
+                       const ttx_dist* dist, const int32_t* d_forced_len, float* d_logits, float* d_tok_logp, float* d_score,
+                       float* d_tok_logq, float* d_logq, int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept,
+                       int32_t* d_length, uint8_t* d_finished, void* stream);
 
 /* Speculative seeded sampling: ttx_sample_generate's samples from the greedy-speculative loop. */
 typedef struct ttx_sample_spec_params {

@@ -17,7 +17,7 @@ LIB_PATH = PKG_DIR / "libttx_hip.so"
 # translation units (compiled in parallel, linked into one shared library) and the headers every one of them depends on
 UNITS = [CSRC / "ttx_api.hip", CSRC / "ttx_gemm.hip", CSRC / "ttx_attn.hip"]
 HEADERS = [CSRC / "ttx_internal.h", CSRC / "ttx_common.hip.h", CSRC / "ttx_loop_kernels.hip.h", CSRC / "ttx_metrics.hip.h",
-           CSRC / "ttx_score.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_sample.hip.h", CSRC / "ttx_sbs.hip.h", CSRC / "ttx_sbs_pool.hip.h",
+           CSRC / "ttx_score.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_sample.hip.h", CSRC / "ttx_logq.hip.h", CSRC / "ttx_sbs.hip.h", CSRC / "ttx_sbs_pool.hip.h",
            CSRC / "ttx_proposal.hip.h",
            CSRC / "ttx_select.h", CSRC / "ttx_tokenizer.h", CSRC / "ttx_drive.h", CSRC / "ttx_admit.h", INCLUDE / "ttx.h"]
 SOURCES = UNITS + HEADERS
@@ -151,6 +151,11 @@ class SampleParams(C.Structure):
                 ("seed", C.c_uint64)]
 
 
+class Dist(C.Structure):
+    """ttx_dist: a sampling distribution; temperature 0 is greedy, top_k 0 and top_p 1 are off."""
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float)]
+
+
 class SampleSpecParams(C.Structure):
     """ttx_sample_spec_params: the sampler's parameters and the copy drafts of the speculative form."""
     _fields_ = [("sample", SampleParams), ("draft_len", C.c_int32), ("n_drafts", C.c_int32), ("replace_token", C.c_int32),
@@ -259,6 +264,9 @@ SYMBOLS = {
     "ttx_score_hypotheses": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ttx_hypothesis_alternatives": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ttx_score_alternatives": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ttx_hypothesis_logq": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, _I, C.POINTER(Dist), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ttx_score_proposal": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, C.POINTER(Dist), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                    _VP, _VP, _VP, _VP]),
     "ttx_attention_maps": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "ttx_attn_probs_key_limit": (C.c_int, [_I]),
     "ttx_debug_attn_probs": (C.c_int, [_VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, C.c_float, _VP, _VP, _VP, _VP]),

@@ -11,6 +11,7 @@
 #include "ttx_alternatives.hip.h"
 #include "ttx_attn_probs.hip.h"
 #include "ttx_sample.hip.h"
+#include "ttx_logq.hip.h"
 #include "ttx_sbs.hip.h"
 #include "ttx_sbs_pool.hip.h"
 #include "ttx_proposal.hip.h"
@@ -1818,6 +1819,110 @@ static int sample_block(const char* who, const ttx_sample_params* p, SampleBlock
     return fail(TTX_ERR_INVALID, std::string(who) + ": 1 / temperature is not a positive finite fp32");
   *out = b;
   return TTX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Log-probability of hypotheses under the sampling distribution: csrc/ttx_logq.hip.h.
+struct LogqOut {
+  float* tok_logq; float* logq; int32_t* first_outside; int32_t* rank; int32_t* n_kept; int32_t* length; uint8_t* finished;
+};
+
+// The distribution of a call as the sampler would run it (sample_block: its limits, its inv_T, top_p < 1 alone runs with top_k 32).
+static int logq_block(const char* who, const ttx_dist* d, SampleBlock* out) {
+  if (!d) return fail(TTX_ERR_INVALID, std::string(who) + ": null distribution");
+  ttx_sample_params p{};
+  p.temperature = d->temperature; p.top_k = d->top_k; p.top_p = d->top_p;
+  return sample_block(who, &p, out);
+}
+
+static bool logq_is_model(const SampleBlock& b, const int32_t* forced_len) {
+  return !b.greedy && b.inv_T == 1.0f && b.top_k == 0 && !forced_len;
+}
+
+// ONE launch of k_hyp_logq, the VPL chosen as the sampler's kernels choose it.
+static int launch_logq(ttx_session* s, hipStream_t st, const float* logits, const int64_t* hyp, int ld_hyp, int R, int W, int V, int pad,
+                       int eos, const SampleBlock& b, const int32_t* forced_len, const LogqOut& o) {
+  LogqArgs a{};
+  a.logits = logits; a.hyp = hyp; a.forced_len = forced_len; a.tok_logq = o.tok_logq; a.logq = o.logq;
+  a.first_outside = o.first_outside; a.rank = o.rank; a.n_kept = o.n_kept; a.length = o.length; a.finished = o.finished;
+  a.ld_hyp = ld_hyp; a.W = W; a.V = V; a.pad = pad; a.eos = eos;
+  a.inv_T = b.greedy ? 1.0f : b.inv_T; a.top_p = b.top_p; a.top_k = b.top_k; a.greedy = b.greedy;
+  if (!a.tok_logq) {                      // the sum reads the per-token values back: session scratch when the caller wants none
+    TTX_TRY(ensure(s->lq_tok, (size_t)R * (W - 1) * sizeof(float), st));
+    a.tok_logq = s->lq_tok.as<float>();
+  }
+  const dim3 grid(R), block(LOGQ_THREADS);
+  if (V <= 64) hipLaunchKernelGGL((k_hyp_logq<1>), grid, block, 0, st, a);
+  else if (V <= 128) hipLaunchKernelGGL((k_hyp_logq<2>), grid, block, 0, st, a);
+  else if (V <= 256) hipLaunchKernelGGL((k_hyp_logq<4>), grid, block, 0, st, a);
+  else if (V <= 512) hipLaunchKernelGGL((k_hyp_logq<8>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((k_hyp_logq<16>), grid, block, 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+extern "C" int ttx_hypothesis_logq(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad, int eos,
+                                   const ttx_dist* dist, const int32_t* d_forced_len, float* d_tok_logq, float* d_logq,
+                                   int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept, int32_t* d_length,
+                                   uint8_t* d_finished, void* stream) {
+  if (!s) return session_required("ttx_hypothesis_logq");
+  if (!d_logits || !d_hyp || !d_logq || !d_length) return fail(TTX_ERR_INVALID, "bad argument to ttx_hypothesis_logq");
+  TTX_TRY(check_score_shapes(s, R, W, V, "ttx_hypothesis_logq"));
+  SampleBlock b{};
+  TTX_TRY(logq_block("ttx_hypothesis_logq", dist, &b));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->m->device));
+  return launch_logq(s, st, d_logits, d_hyp, W, R, W, V, pad, eos, b, d_forced_len,
+                     LogqOut{d_tok_logq, d_logq, d_first_outside, d_rank, d_n_kept, d_length, d_finished});
+}
+
+extern "C" int ttx_score_proposal(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N, int W,
+                                  int eos, const ttx_dist* dist, const int32_t* d_forced_len, float* d_logits, float* d_tok_logp,
+                                  float* d_score, float* d_tok_logq, float* d_logq, int32_t* d_first_outside, int32_t* d_rank,
+                                  int32_t* d_n_kept, int32_t* d_length, uint8_t* d_finished, void* stream) {
+  if (!s) return session_required("ttx_score_proposal");
+  if (!d_src || !d_hyp || !d_logq || !d_length || B <= 0 || N <= 0 || Ls <= 0)
+    return fail(TTX_ERR_INVALID, "bad argument to ttx_score_proposal");
+  if (d_tok_logp && !d_score) return fail(TTX_ERR_INVALID, "ttx_score_proposal: d_tok_logp needs d_score");
+  if (ld_hyp < W) return fail(TTX_ERR_INVALID, "ttx_score_proposal: row stride ld_hyp smaller than W");
+  const ttx_config& c = s->m->cfg;
+  TTX_TRY(check_score_shapes(s, (long long)B * N, W, c.vocab_size, "ttx_score_proposal"));
+  if (Ls > c.max_positions) return fail(TTX_ERR_INVALID, "source longer than the positional table");
+  SampleBlock b{};
+  TTX_TRY(logq_block("ttx_score_proposal", dist, &b));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->m->device));
+  const int R = B * N, T = W - 1, V = c.vocab_size, pad = c.pad_token;
+  if (!d_logits) {
+    TTX_TRY(ensure(s->ev_logits, (size_t)R * T * V * sizeof(float), st));
+    d_logits = s->ev_logits.as<float>();
+  }
+  TTX_TRY(score_forward(s, st, d_src, B, Ls, d_hyp, ld_hyp, N, W, d_logits));
+  if (logq_is_model(b, d_forced_len)) {
+    // q is the model's own distribution: ONE launch of k_hyp_score gives the values, so that they are ttx_score_hypotheses' bit
+    // for bit; with d_score set they are copied, not computed twice.  first_outside follows from them (k_logq_first_outside);
+    // k_hyp_logq runs for rank / n_kept alone.
+    const float* tok = nullptr;
+    if (d_score) {
+      TTX_TRY(launch_score(s, st, d_logits, d_hyp, ld_hyp, R, W, V, pad, eos, d_tok_logp, d_score, d_length, d_finished));
+      tok = d_tok_logp ? d_tok_logp : s->ev_nll.as<float>();
+      if (d_tok_logq) HIP_TRY(hipMemcpyAsync(d_tok_logq, tok, (size_t)R * T * sizeof(float), hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemcpyAsync(d_logq, d_score, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, st));
+    } else {
+      TTX_TRY(launch_score(s, st, d_logits, d_hyp, ld_hyp, R, W, V, pad, eos, d_tok_logq, d_logq, d_length, d_finished));
+      tok = d_tok_logq ? d_tok_logq : s->ev_nll.as<float>();
+    }
+    if (d_first_outside) {
+      hipLaunchKernelGGL(k_logq_first_outside, dim3(cdiv(R, 4)), dim3(256), 0, st, tok, d_length, d_first_outside, R, T);
+      HIP_TRY(hipGetLastError());
+    }
+    if (!d_rank && !d_n_kept) return TTX_OK;
+    return launch_logq(s, st, d_logits, d_hyp, ld_hyp, R, W, V, pad, eos, b, nullptr,
+                       LogqOut{nullptr, nullptr, nullptr, d_rank, d_n_kept, nullptr, nullptr});
+  }
+  if (d_score) TTX_TRY(launch_score(s, st, d_logits, d_hyp, ld_hyp, R, W, V, pad, eos, d_tok_logp, d_score, d_length, d_finished));
+  return launch_logq(s, st, d_logits, d_hyp, ld_hyp, R, W, V, pad, eos, b, d_forced_len,
+                     LogqOut{d_tok_logq, d_logq, d_first_outside, d_rank, d_n_kept, d_length, d_finished});
 }
 
 // ttx_sample_generate and ttx_sample_generate_prefix: one body, the unprompted call with a null prefix.

@@ -122,6 +122,8 @@ struct GraphCache {
   /* hypothesis scoring (ttx_score_hypotheses): decoder row -> memory row; logits / per-token values it does not hand out live */ \
   /* in ev_logits / ev_nll */                                                                                                    \
   X(sc_src_of) X(am_length)                                                                                                                   \
+  /* ttx_hypothesis_logq / ttx_score_proposal: the per-token values the caller did not ask for */                                  \
+  X(lq_tok)                                                                                                                      \
   /* loop */                                                                                                                     \
   X(drafts) X(gen) X(front) X(act_idx) X(rec) X(pred) X(state) X(kcache) X(vcache) X(src32) X(outbuf) X(haspad) X(traj)           \
   X(fin_step)                                                                                                                    \

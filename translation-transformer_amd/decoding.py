@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .model import AttentionMaps, HypothesisScores, NativeTransformer
+from .model import AttentionMaps, HypothesisScores, NativeTransformer, ProposalScores
 
 
 def _need_native(model) -> NativeTransformer:
@@ -53,11 +53,37 @@ class _ScoresHypotheses:
             raise ValueError("the generator's pad token differs from the model's")
         return self.model.alternatives(src, pred, k=k, eos_token_idx=eos, **kw)
 
-    def _scored(self, src: torch.Tensor, pred: torch.Tensor, return_scores: bool):
-        return (pred, self.score(src, pred)) if return_scores else pred
+    def logq(self, src: torch.Tensor, pred: torch.Tensor, prefix=None, **kw) -> ProposalScores:
+        """The log-probability of the hypotheses ``pred`` (Long[B, N, L] as ``generate(src)`` returned it) under a SAMPLING
+        distribution, beside ``score`` (which gives it under the model): by default the generator's own ``temperature``,
+        ``top_k`` and ``top_p`` where it has them (the two samplers, stochastic beam search), temperature 1 without a filter on
+        the deterministic generators.  ``prefix``: the forced prefix the rows were generated with (``check_prefix``'s form);
+        its positions cost nothing (``forced_len`` = the prefix lengths).  Other keywords go to
+        ``NativeTransformer.proposal_scores``."""
+        pad, eos = self._pad_eos()
+        if pad != self.model.tgt_pad_token_i:
+            raise ValueError("the generator's pad token differs from the model's")
+        for name, default in (("temperature", 1.0), ("top_k", 0), ("top_p", 1.0)):
+            kw.setdefault(name, getattr(self, name, default))
+        if prefix is not None:
+            if kw.get("forced_len") is not None:
+                raise ValueError("a call takes a prefix or forced_len, not both")
+            _, lengths = check_prefix(prefix, int(pred.shape[0]), int(pred.shape[-1]), pad, self.model.tgt_vocab_size)
+            kw["forced_len"] = torch.tensor(lengths, dtype=torch.int32)
+        return self.model.proposal_scores(src, pred, eos_token_idx=eos, **kw)
 
-    def _scored_many(self, batches: list, preds: list) -> list:
-        return [(p, None if p is None else self.score(b, p)) for b, p in zip(batches, preds)]
+    def _scored(self, src: torch.Tensor, pred: torch.Tensor, return_scores: bool, return_logq: bool = False, prefix=None):
+        """``pred``; with ``return_scores`` and / or ``return_logq`` the tuple ``(pred[, HypothesisScores][, ProposalScores])``.
+        Both flags: ONE decoder pass (``with_scores=True``), the ProposalScores' ``scores`` being the HypothesisScores."""
+        if not return_logq:
+            return (pred, self.score(src, pred)) if return_scores else pred
+        q = self.logq(src, pred, prefix=prefix, with_scores=return_scores)
+        return (pred, q.scores, q) if return_scores else (pred, q)
+
+    def _scored_many(self, batches: list, preds: list, return_scores: bool = True, return_logq: bool = False, prefixes=None) -> list:
+        pres = prefixes if prefixes is not None else [None] * len(batches)
+        return [(p,) + (None,) * (int(return_scores) + int(return_logq)) if p is None
+                else self._scored(b, p, return_scores, return_logq, q) for b, p, q in zip(batches, preds, pres)]
 
 
 def _slot_pool_plan(rows: int, in_flight: int, capacity: int | None) -> tuple:
@@ -414,10 +440,12 @@ class TranslationInferenceSampling(_ScoresHypotheses):
         d = p.to(m.device)
         return d, (d.data_ptr() if d.numel() else None), int(d.shape[1]), (C.c_int32 * max(B, 1))(*lengths)
 
-    def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, prefix=None):
+    def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, prefix=None, return_logq: bool = False):
         """Long[B, num_samples, max_len].  ``row_keys``: one integer per source (default 0..B-1), the source's identity for
         the random stream: the same (source, key) gives the same samples in any batch.  ``return_scores=True``:
-        ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``).
+        ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``).  ``return_logq=True``: ``(pred, ProposalScores)``, the
+        rows' log-probability under the distribution they were drawn from (see ``logq``; what ``logq(src, pred, prefix=prefix)``
+        returns); both flags: ``(pred, HypothesisScores, ProposalScores)`` from one decoder pass.
 
         ``prefix``: Long[B, Lp] without BOS, right-padded with PAD: the forced beginning of every sample of a source.  A
         row is BOS, its prefix, the sampled completion, PAD; a position inside the prefix holds the prefix token whatever the
@@ -444,7 +472,7 @@ class TranslationInferenceSampling(_ScoresHypotheses):
         self.model_calls_num += int(st.model_calls)
         self.given_tokens += int((src != m.src_pad_token_i).sum())
         self.last_stats = st
-        return self._scored(src, out, return_scores)
+        return self._scored(src, out, return_scores, return_logq, prefix)
 
 
 class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
@@ -470,8 +498,9 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         return (f"Speculative sampling (draft_len={self.draft_len}, n_drafts={self.n_drafts}, temperature={self.temperature}, "
                 f"top_k={self.top_k}, top_p={self.top_p}, num_samples={self.num_samples}, seed={self.seed}, max_len={self.max_len})")
 
-    def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, prefix=None, proposal=None):
-        """Long[B, num_samples, max_len]; ``row_keys``, ``return_scores`` and ``prefix`` as for
+    def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, prefix=None, proposal=None,
+                 return_logq: bool = False):
+        """Long[B, num_samples, max_len]; ``row_keys``, ``return_scores``, ``return_logq`` and ``prefix`` as for
         ``TranslationInferenceSampling.generate``.  A prefix rides in as the first draft of its rows, which is certain to be
         accepted: ``P`` forced tokens take ``ceil(P / (draft_len + 1))`` verify steps.
 
@@ -519,10 +548,10 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         t["src_tokens_padded"] += B * Ls
         t["batches"] += 1
         self.last_stats = st
-        return self._scored(src, out, return_scores)
+        return self._scored(src, out, return_scores, return_logq, prefix)
 
     def generate_many(self, batches: list, row_keys=None, in_flight: int = 4, capacity: int | None = None,
-                      return_scores: bool = False, prefixes=None, proposals=None) -> list:
+                      return_scores: bool = False, prefixes=None, proposals=None, return_logq: bool = False) -> list:
         """The samples of all batches from slot pools (ttx_sample_speculative_generate_pool: continuous batching over the sources
         of the whole list, sorted by length; the ``num_samples`` rows of a source are admitted together).  Returns one
         Long[B_i, num_samples, max_len] per batch.
@@ -532,15 +561,16 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         not depend on its slot, on the capacity or on what shares the pool.  ``capacity`` (slots, i.e. decoder rows, per pool;
         ``TTX_POOL_CAPACITY``) and the pool count follow the greedy generator's rule over the ``S * num_samples`` decoder rows and
         are never below ``num_samples``.  ``model_calls_num`` counts the verify steps the device executed.
-        ``return_scores=True``: a list of ``(pred, HypothesisScores)`` pairs.
+        ``return_scores=True``: a list of ``(pred, HypothesisScores)`` pairs; ``return_logq=True``: of ``(pred, ProposalScores)``
+        pairs (what ``logq(batches[i], pred_i, prefix=prefixes[i])`` returns); both: of triples, one decoder pass per batch.
         ``prefixes``: a list aligned with ``batches``, each entry a ``prefix`` tensor for that batch (see ``generate``) or
         ``None``; ``generate_many(batches, prefixes=ps)[i]`` holds the rows of ``generate(batches[i], prefix=ps[i],
         row_keys=arange(off_i, off_i + B_i))``.
         ``proposals``: the same for ``generate``'s ``proposal``: offered drafts, which change no row.  A call takes ``prefixes``
         or ``proposals``, not both (ValueError)."""
-        if return_scores:
+        if return_scores or return_logq:
             return self._scored_many(batches, self.generate_many(batches, row_keys, in_flight, capacity, prefixes=prefixes,
-                                                                 proposals=proposals))
+                                                                 proposals=proposals), return_scores, return_logq, prefixes)
         from .scheduling import plan_row_groups
         if prefixes is not None and proposals is not None:
             raise ValueError("a call takes forced prefixes or proposals, not both")

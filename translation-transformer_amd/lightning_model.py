@@ -251,6 +251,14 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         # TTX_PREDICT_ALTERNATIVES=k
         self.predict_with_alternatives = 0
         self.predict_alternatives: dict = {}
+        # predict_step also evaluates the hypotheses under the distribution they were drawn from (generator.logq: the
+        # generator's temperature and filter, the batch's prefix as forced positions) into self.predict_logq[batch_idx], a
+        # ProposalScores; generation "sampling", "sampling_speculative" and "stochastic_beam_search" only.  No init_arg either —
+        # set the attribute or TTX_PREDICT_LOGQ=1
+        self.predict_with_logq = False
+        self.predict_logq: dict = {}
+        self._logq_on = False
+        self._logq_seconds, self._outside = 0.0, 0
         self._alternatives_k = 0
         self.report_prediction_time = report_prediction_time
         self.prediction_start_time = None
@@ -348,13 +356,35 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             self._predict_rows += B
         elif pred is None:
             pred = self.generator.generate(batch["src_tokens"])
+        both = self._logq_on and self._scores_on and self._alternatives_k <= 0     # scores and log q from ONE decoder pass
         if self._alternatives_k > 0:
             self._alternatives_batch(batch["src_tokens"], pred, batch_idx)
-        elif self._scores_on:
+        elif self._scores_on and not both:
             self._score_batch(batch["src_tokens"], pred, batch_idx)
         if self._attention_on:
             self._align_batch(batch["src_tokens"], pred, batch_idx)
+        if self._logq_on:
+            self._logq_batch(batch["src_tokens"], pred, batch_idx, prefix, with_scores=both)
         return pred
+
+    def _logq_batch(self, src: torch.Tensor, pred: torch.Tensor, batch_idx: int, prefix, with_scores: bool = False) -> None:
+        """The batch's ProposalScores under the generator's own distribution, whether it was decoded ahead or on the spot; the
+        token tensor predict_step returns stays what it was.  ``with_scores``: the batch's HypothesisScores come from the same
+        decoder pass (its time then counts as scoring_seconds too, as _alternatives_batch counts its own).  Timed like
+        _score_batch."""
+        torch.cuda.synchronize()
+        t0 = timer()
+        q = self.generator.logq(src, pred, prefix=prefix, with_scores=with_scores)
+        torch.cuda.synchronize()
+        dt = timer() - t0
+        self._logq_seconds += dt
+        if with_scores:
+            sc = q.scores
+            self._scoring_seconds += dt
+            self._keep_scores(type(sc)(sc.score, sc.length, sc.finished, None), batch_idx)
+            q = q._replace(scores=None)
+        self.predict_logq[batch_idx] = q
+        self._outside = self._outside + (q.first_outside >= 0).sum()      # kept on the device until the report
 
     def _score_batch(self, src: torch.Tensor, pred: torch.Tensor, batch_idx: int) -> None:
         """The batch's HypothesisScores, whether it was decoded ahead or on the spot; the token tensor predict_step returns
@@ -430,6 +460,12 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             raise ValueError("predict_with_alternatives / TTX_PREDICT_ALTERNATIVES must be an integer k (0: off), got "
                              f"{self.predict_with_alternatives!r} / {os.environ.get('TTX_PREDICT_ALTERNATIVES')!r}") from None
         self.predict_alternatives = {}
+        self._logq_on = bool(self.predict_with_logq) or os.environ.get("TTX_PREDICT_LOGQ") == "1"
+        if self._logq_on and self.hparams.generation not in ("sampling", "sampling_speculative", "stochastic_beam_search"):
+            raise ValueError('predict_with_logq / TTX_PREDICT_LOGQ: only generation="sampling", "sampling_speculative" and '
+                             f'"stochastic_beam_search" draw from a sampling distribution, not "{self.hparams.generation}"')
+        self.predict_logq = {}
+        self._logq_seconds, self._outside = 0.0, 0
         self._alternatives_seconds = 0.0
         self._attention_seconds = 0.0
         self._scoring_seconds, self._top1_n, self._top1_sum, self._unfinished = 0.0, 0, 0.0, 0
@@ -484,6 +520,9 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             report["alternatives_seconds"] = round(self._alternatives_seconds, 6)
         if self._attention_on:
             report["attention_seconds"] = round(self._attention_seconds, 6)
+        if self._logq_on:
+            report["logq_seconds"] = round(self._logq_seconds, 6)
+            report["hypotheses_outside_support"] = int(self._outside)
         text = json.dumps(report)
         print(text)
         if h.report_prediction_file is not None:

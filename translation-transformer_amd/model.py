@@ -105,6 +105,22 @@ class Alternatives(NamedTuple):
         return self.top_logp[..., 0] - self.top_logp[..., 1]
 
 
+class ProposalScores(NamedTuple):
+    """Result of ``NativeTransformer.proposal_scores`` / ``hypothesis_logq``: device tensors, nothing copied to the host.  The
+    log-probability of hypothesis ``hyp[b, k]`` under the SAMPLING distribution q (temperature, top-k, top-p) where
+    ``HypothesisScores.score`` is its log-probability under the model p.  Position ``p`` (the one that predicts ``h[p+1]``) is
+    live iff ``p < length``; forced positions and positions that are not live hold ``token_logq`` = 0, ``rank`` = -1 and
+    ``n_kept`` = 0."""
+    logq: torch.Tensor                # fp32 [B, N]: log q of the hypothesis; -inf when the sampler cannot emit it
+    length: torch.Tensor              # int32 [B, N]: as HypothesisScores.length
+    finished: torch.Tensor            # bool [B, N]: as HypothesisScores.finished
+    first_outside: torch.Tensor       # int32 [B, N]: the first live position whose token is outside q's support, else -1
+    token_logq: torch.Tensor | None   # fp32 [B, N, W-1] when asked for
+    rank: torch.Tensor | None         # int32 [B, N, W-1] when asked for: tokens ranked above the emitted one under q's scaling
+    n_kept: torch.Tensor | None       # int32 [B, N, W-1] when asked for: size of the kept set (rank == n_kept: just outside it)
+    scores: HypothesisScores | None   # with_scores=True: score_hypotheses' result (with token_logp), from the same decoder pass
+
+
 class NativeTransformer:
     # score_hypotheses: decoder positions (rows x columns) of one call; the widest activation buffer takes ff_dim floats per
     # position (256 MiB at ff_dim 2048), and a bench batch of 32 rows x 199 columns still fits one call
@@ -1020,6 +1036,129 @@ class NativeTransformer:
                 if Wt != W:
                     sc.token_logp[b0:b1, :, :Tt] = tok
         return (out, sc) if with_scores else out
+
+    # -- log-probability of hypotheses under the sampling distribution ---------------------------
+    @staticmethod
+    def _dist(temperature: float, top_k: int, top_p: float) -> N.Dist:
+        """The ``ttx_dist`` of a call; ValueError for what the sampler refuses (the library checks again before any launch)."""
+        t, k, p = float(temperature), int(top_k), float(top_p)
+        if not (t >= 0.0 and t != float("inf")):
+            raise ValueError(f"temperature must be finite and >= 0, got {temperature!r}")
+        if not 0 <= k <= 32:
+            raise ValueError(f"top_k must be 0 or in [1, 32], got {top_k!r}")
+        if not 0.0 < p <= 1.0:
+            raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
+        return N.Dist(t, k, p)
+
+    def _forced_rows(self, forced_len, lead: tuple) -> torch.Tensor | None:
+        """``forced_len`` as the int32 device tensor of shape ``lead`` the kernel reads: given per hypothesis (``lead``) or, for
+        ``lead = (B, N)``, per source ([B]).  ValueError: another shape, a non-integer dtype, or (for a host tensor, where it
+        costs no synchronisation) a negative entry; the kernel clamps to [0, length]."""
+        if forced_len is None:
+            return None
+        f = torch.as_tensor(forced_len)
+        if f.dtype.is_floating_point or f.dtype == torch.bool:
+            raise ValueError(f"forced_len must be an integer tensor, got {f.dtype}")
+        if tuple(f.shape) == lead[:1] and len(lead) == 2:
+            f = f[:, None].expand(lead)
+        elif tuple(f.shape) != lead:
+            raise ValueError(f"forced_len must have shape {lead[:1] if len(lead) == 2 else lead} or {lead}, got {tuple(f.shape)}")
+        if f.device.type == "cpu" and f.numel() and int(f.min()) < 0:
+            raise ValueError("forced_len holds a negative entry")
+        return f.to(self.device, torch.int32).contiguous()
+
+    def hypothesis_logq(self, logits: torch.Tensor, hyp: torch.Tensor, pad: int, eos: int, temperature: float = 1.0, top_k: int = 0,
+                        top_p: float = 1.0, forced_len=None, check_ids: bool = True) -> ProposalScores:
+        """The stage alone (ttx_hypothesis_logq): ``logits`` fp32 [..., W-1, V] as ``decode_tgt(hyp[..., :-1])`` gives them,
+        ``hyp`` Long[..., W] with the same leading shape, ``forced_len`` integers of that leading shape.  A ``logits`` tensor
+        that is already a contiguous fp32 device tensor is read in place.  Every output is returned.  Nothing is synchronised
+        (``check_ids=False`` skips the IndexError check of the token ids, which reads their range back)."""
+        x = logits.to(self.device, torch.float32)
+        if not x.is_contiguous():
+            x = x.contiguous()
+        hyp = self._tokens(hyp)
+        lead, W = tuple(hyp.shape[:-1]), int(hyp.shape[-1])
+        if hyp.dim() < 2 or W < 2 or tuple(x.shape[:-1]) != lead + (W - 1,):
+            raise ValueError(f"hypothesis_logq needs hyp [..., W >= 2] for logits [..., W-1, V]; got {tuple(hyp.shape)} for "
+                             f"{tuple(x.shape)}")
+        V = int(x.shape[-1])
+        dist = self._dist(temperature, top_k, top_p)
+        forced = self._forced_rows(forced_len, lead)
+        if check_ids:
+            self.check_tokens(hyp, V)
+        dev = self.device
+        out = ProposalScores(torch.empty(lead, dtype=torch.float32, device=dev), torch.empty(lead, dtype=torch.int32, device=dev),
+                             torch.empty(lead, dtype=torch.bool, device=dev), torch.empty(lead, dtype=torch.int32, device=dev),
+                             torch.empty(lead + (W - 1,), dtype=torch.float32, device=dev),
+                             torch.empty(lead + (W - 1,), dtype=torch.int32, device=dev),
+                             torch.empty(lead + (W - 1,), dtype=torch.int32, device=dev), None)
+        N.check(self._lib.ttx_hypothesis_logq(self._scoring_session(), x.data_ptr(), hyp.data_ptr(), hyp.numel() // W, W, V, int(pad),
+                                              int(eos), C.byref(dist), self._ptr(forced), out.token_logq.data_ptr(),
+                                              out.logq.data_ptr(), out.first_outside.data_ptr(), out.rank.data_ptr(),
+                                              out.n_kept.data_ptr(), out.length.data_ptr(), out.finished.data_ptr(), self._stream()))
+        return out
+
+    def proposal_scores(self, src: torch.Tensor, hyp: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
+                        forced_len=None, with_scores: bool = False, return_token_logq: bool = False, return_rank: bool = False,
+                        trim: bool = True, max_rows: int | None = None, eos_token_idx: int = 2) -> ProposalScores:
+        """Log-probability of every hypothesis ``hyp[b, k]`` (Long[B, N, W]) of source ``src[b]`` under the distribution a sampler
+        with (``temperature``, ``top_k``, ``top_p``) draws from: the teacher-forced pass of ``score_hypotheses`` and the stage
+        that evaluates the sampler's own rule at every emitted token (ttx_score_proposal; include/ttx.h defines the quantity).
+        ``logq = -inf`` means the sampler cannot emit the row (``first_outside`` names the position).  A row that was SAMPLED at
+        these settings can still get ``-inf`` when one of its tokens sat on the nucleus boundary: decode-time and teacher-forced
+        logits agree to rounding only.  ``return_rank=True`` returns ``rank`` and ``n_kept``, which show that case
+        (``rank == n_kept`` at ``first_outside``).
+
+        ``forced_len``: integers [B] (per source) or [B, N]: the first ``forced_len`` positions of a row were forced (a prefix),
+        cost nothing and are inside the support.  ``with_scores=True`` fills ``scores`` with ``score_hypotheses``' result (with
+        ``token_logp``) from the same decoder pass.  With temperature 1, no filter and no ``forced_len``, ``logq`` is
+        ``score_hypotheses``' ``score`` bit for bit.  ``trim`` and ``max_rows`` behave as in ``score_hypotheses``; results keep the
+        full ``W-1``, columns cut by ``trim`` hold the not-live values."""
+        src, hyp = self._tokens(src), self._tokens(hyp)
+        if src.dim() != 2 or hyp.dim() != 3 or hyp.shape[0] != src.shape[0] or hyp.shape[1] < 1 or hyp.shape[2] < 2:
+            raise ValueError(f"proposal_scores needs hyp [B, N >= 1, W >= 2] for src [B, Ls]; got {tuple(hyp.shape)} for "
+                             f"{tuple(src.shape)}")
+        V = self.tgt_vocab_size                   # above 1024: refused by the library from the model's config, before any launch
+        dist = self._dist(temperature, top_k, top_p)
+        (B, Ls), (_, K, W) = src.shape, hyp.shape
+        forced = self._forced_rows(forced_len, (B, K))
+        self.check_tokens(src)
+        self.check_tokens(hyp, V)
+        eos, dev = int(eos_token_idx), self.device
+        Wt, chunk = self._trim_and_chunk(hyp, eos, trim, max_rows)
+        T, Tt = W - 1, Wt - 1
+        cut = Wt != W
+
+        def per_pos(dtype, value, wanted=True):
+            if not wanted:
+                return None
+            return torch.full((B, K, T), value, dtype=dtype, device=dev) if cut else torch.empty((B, K, T), dtype=dtype, device=dev)
+
+        sc = None
+        if with_scores:
+            sc = HypothesisScores(torch.empty((B, K), dtype=torch.float32, device=dev), torch.empty((B, K), dtype=torch.int32, device=dev),
+                                  torch.empty((B, K), dtype=torch.bool, device=dev), per_pos(torch.float32, 0.0))
+        out = ProposalScores(torch.empty((B, K), dtype=torch.float32, device=dev), sc.length if sc else torch.empty((B, K), dtype=torch.int32, device=dev),
+                             sc.finished if sc else torch.empty((B, K), dtype=torch.bool, device=dev),
+                             torch.empty((B, K), dtype=torch.int32, device=dev), per_pos(torch.float32, 0.0, return_token_logq),
+                             per_pos(torch.int32, -1, return_rank), per_pos(torch.int32, 0, return_rank), sc)
+        full = [out.token_logq, out.rank, out.n_kept, sc.token_logp if sc else None]
+        sess, stream = self._scoring_session(), self._stream()
+        for b0 in range(0, B, chunk):
+            b1 = min(B, b0 + chunk)
+            nb = b1 - b0
+            part = [None if t is None else (t[b0:b1] if not cut else torch.empty((nb, K, Tt), dtype=t.dtype, device=dev)) for t in full]
+            N.check(self._lib.ttx_score_proposal(sess, src[b0:b1].data_ptr(), nb, Ls, hyp[b0:b1].data_ptr(), W, K, Wt, eos,
+                                                 C.byref(dist), None if forced is None else forced[b0:b1].data_ptr(), None,
+                                                 self._ptr(part[3]), sc.score[b0:b1].data_ptr() if sc else None,
+                                                 self._ptr(part[0]), out.logq[b0:b1].data_ptr(), out.first_outside[b0:b1].data_ptr(),
+                                                 self._ptr(part[1]), self._ptr(part[2]), out.length[b0:b1].data_ptr(),
+                                                 out.finished[b0:b1].data_ptr(), stream))
+            if cut:
+                for t, c in zip(full, part):
+                    if t is not None:
+                        t[b0:b1, :, :Tt] = c
+        return out
 
     # -- cross-attention maps of hypotheses -----------------------------------------------------
     def attention_maps(self, src: torch.Tensor, hyp: torch.Tensor, eos_token_idx: int = 2, layer: int = -1, heads: str = "mean",

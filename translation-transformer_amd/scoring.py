@@ -223,6 +223,68 @@ def _exp_e1(a):
     return np.where(np.isinf(a), 0.0, out)
 
 
+def importance_weights(scores, logq, normalize: bool = True):
+    """Importance weights ``p(y) / q(y)`` of hypotheses drawn from a sampling distribution q (temperature, top-k, top-p), float64
+    [B, N] on the host.  ``scores``: a HypothesisScores (or log p as an array [B, N]); ``logq``: a ProposalScores (or log q as an
+    array [B, N]) of the same rows.  The weight is ``exp(logp - logq)``; a row with ``logq = -inf`` (the sampler cannot emit it:
+    its ratio is undefined and it is no draw from q) and a row that is not finished (where ``finished`` is known: an object was
+    passed) get weight 0.  ``normalize=True`` divides every source's weights by their sum (self-normalised importance sampling);
+    a source without a finite row gets zeros.
+
+    What they estimate.  For N independent draws y_i ~ q of one source, ``(1 / N) sum_i w_i f(y_i)`` with ``normalize=False`` is
+    an unbiased estimate of ``sum_{y in supp q} p(y) f(y)``: expectations under the model p RESTRICTED to q's support.  Without a
+    filter (temperature only) the supports agree and this is ``E_p f``.  Under ``top_k`` / ``top_p`` the support of p exceeds
+    that of q, the mass of p outside it is never seen, and the estimate is biased low by exactly that mass; ``(1 / N) sum_i w_i``
+    estimates the mass p gives q's support, not 1.  ``normalize=True`` gives ``sum_i w_i f(y_i)``, the self-normalised
+    estimate of ``E_p[f | supp q]``: consistent, biased at finite N (order 1 / N), and usable when p or q is known up to a
+    constant only.  Rows must be independent draws; the K distinct rows of stochastic beam search are a sample without
+    replacement, for which ``sbs_weights`` is the estimator."""
+    import numpy as np
+
+    def host(x):
+        x = x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+        return x.astype(np.float64)
+    fin = None
+    for obj in (scores, logq):
+        f = getattr(obj, "finished", None)
+        if f is not None:
+            f = host(f) != 0
+            fin = f if fin is None else (fin & f)
+    lp = host(scores.score if hasattr(scores, "score") else scores)
+    lq = host(logq.logq if hasattr(logq, "logq") else logq)
+    if lp.ndim != 2 or lp.shape != lq.shape or (fin is not None and fin.shape != lp.shape):
+        raise ValueError(f"scores and logq must share a shape [B, N], got {lp.shape} and {lq.shape}")
+    ok = np.isfinite(lq) & np.isfinite(lp)
+    if fin is not None:
+        ok &= fin
+    with np.errstate(over="ignore", invalid="ignore"):
+        w = np.where(ok, np.exp(np.where(ok, lp - lq, 0.0)), 0.0)
+    if normalize:
+        tot = w.sum(axis=1, keepdims=True)
+        w = np.divide(w, tot, out=np.zeros_like(w), where=tot > 0)
+    return w
+
+
+def write_logq(filename: str, logq, append: bool = True) -> None:
+    """The log q side file of the prediction CSV: one line per source, ``logq_1,length_1,finished_1,first_outside_1,...`` in the
+    order of the CSV's ``prediction_1..N`` columns (log q with 9 significant digits: fp32 round-trips; ``-inf`` for a row outside
+    the support).  ``logq``: a ProposalScores.  The prediction CSV itself is left as it is."""
+    lq, ln, fin, fo = (t.detach().cpu().tolist() for t in (logq.logq, logq.length, logq.finished, logq.first_outside))
+    with open(filename, "a" if append else "w") as f:
+        for q_row, l_row, f_row, o_row in zip(lq, ln, fin, fo):
+            print(",".join(f"{q:.9g},{int(n)},{int(bool(d))},{int(o)}" for q, n, d, o in zip(q_row, l_row, f_row, o_row)), file=f)
+
+
+def read_logq(filename: str) -> list:
+    """What ``write_logq`` wrote: per source a list of ``(logq, length, finished, first_outside)``."""
+    rows = []
+    with open(filename) as f:
+        for line in f:
+            v = line.strip().split(",")
+            rows.append([(float(v[i]), int(v[i + 1]), bool(int(v[i + 2])), int(v[i + 3])) for i in range(0, len(v) - 3, 4)])
+    return rows
+
+
 def write_scores(filename: str, scores, append: bool = True) -> None:
     """The side file of the prediction CSV: one line per source, ``score_1,length_1,finished_1,...,score_N,length_N,finished_N``
     in the order of the CSV's ``prediction_1..N`` columns (scores with 9 significant digits: fp32 round-trips).  The prediction
