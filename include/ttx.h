@@ -483,6 +483,72 @@ int ttx_sample_speculative_generate_pool_proposal(ttx_session** sessions, int n_
                                                   const int32_t* h_prefix_len, const int64_t* d_proposal, int ld_proposal,
                                                   const int32_t* h_proposal_len, int64_t* d_out, ttx_gen_stats* stats, void* stream);
 
+/* Per-source logit bias and token allow-lists for the sampling calls and stochastic beam search: WHICH tokens a source may produce.
+ * d_bias is DEVICE, fp32 [sources][ld_bias], ld_bias >= V, one row per source (`sources` is B; S_total for the pool, in the order of
+ * d_src).  NULL is the unbiased call, launch for launch: no new kernel, no new buffer, the same graph keys.
+ *
+ * The rule.  For every decoder row of source b and every position whose logits a rule reads,
+ *     x'_v = x_v + bias[b][v]        ONE rounded fp32 add (never contracted),
+ * and the rule (ttx_sample_generate's steps 2-6, the stochastic beam step, log q) then runs on x'.  An entry that is exactly zero
+ * (+0.0 or -0.0) skips the add: the logit keeps its bits, so a -0.0 logit keeps its sign and an all-zero bias returns the unbiased
+ * call's tokens on the bits.  -inf forbids a token: every consumer defines a -inf logit as "never emitted".  An allow-list is a bias
+ * of 0 / -inf.  The bias comes before temperature and filter: the kept set and its renormalisation are the sampler's, on the biased
+ * row.  A forced prefix position emits its prefix token whatever the bias says (it reads no logits).  Drafts (copies, prefixes,
+ * proposals) need no rule: a draft token is accepted iff it equals the keyed draw, so a token the biased sampler cannot emit is never
+ * accepted.
+ * Values must be finite or -inf.  NaN and +inf are outside the contract; they live on the device and this library does not read them
+ * back (the Python layer's check_logit_bias refuses them).  A row whose bias leaves no finite logit is outside the contract exactly as
+ * an all -inf row is: the result is some id in [0, V), never an out-of-range write.
+ * Seeding contract, one item longer: a row depends on its source, key, sample id, prefix and ITS SOURCE'S BIAS ROW alone; it is
+ * bit-identical in any batch, at any batch size, ld_bias or padded width, per batch or pooled (under the speculative calls' one
+ * caveat), and from run to run.
+ * Mechanism.  ONE launch of k_logit_bias (csrc/ttx_logit_bias.hip.h) per decoder pass, in place on the pass's logits, between the
+ * classifier and the consumer.  The values are copied into a session buffer at call start, so a captured step never holds the
+ * caller's pointer; a biased step has graph keys of its own.  A pool slot gets its source's row index at admission.
+ * The *_ex calls take every option of their family in one struct (a NULL struct, or zeroed fields, is the plain call); the prefix and
+ * proposal fields are the arguments of the *_prefix / *_proposal calls, under their rules.  ttx_sample_generate_ex refuses a proposal.
+ * ttx_sbs_generate_bias is ttx_sbs_generate_ex plus the bias.  The greedy, greedy-speculative, beam and beam-speculative calls and
+ * ttx_sbs_generate_pool take no bias (temperature 0 on the sampling calls, the pooled one included, is constrained greedy decoding).
+ * TTX_ERR_INVALID with nothing launched: ld_bias < V with a non-null d_bias, and everything the call refuses without a bias. */
+typedef struct ttx_sample_opts {
+  const int64_t* d_prefix; int32_t ld_prefix; const int32_t* h_prefix_len;          /* forced prefixes, or NULL / 0 / NULL */
+  const int64_t* d_proposal; int32_t ld_proposal; const int32_t* h_proposal_len;    /* proposal drafts, or NULL / 0 / NULL */
+  const float* d_bias; int32_t ld_bias;                                             /* logit bias, or NULL / 0 */
+} ttx_sample_opts;
+int ttx_sample_generate_ex(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sample_params* p,
+                           const ttx_sample_opts* opts, int64_t* d_out, ttx_gen_stats* stats, void* stream);
+int ttx_sample_speculative_generate_ex(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                       const ttx_sample_spec_params* p, const ttx_sample_opts* opts, int64_t* d_out,
+                                       ttx_gen_stats* stats, void* stream);
+int ttx_sample_speculative_generate_pool_ex(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total, int Ls_all,
+                                            const int32_t* h_len, const int64_t* d_row_keys, int capacity,
+                                            const ttx_sample_spec_params* p, const ttx_sample_opts* opts, int64_t* d_out,
+                                            ttx_gen_stats* stats, void* stream);
+/* log q under the bias: ttx_hypothesis_logq / ttx_score_proposal with k_logit_bias applied to the teacher-forced logits before the
+ * log q stage (hypothesis row r belongs to source r / N), so that logq is the log-probability under the distribution the biased sampler
+ * draws from: first_outside names the first forbidden token and logq = -inf means "cannot be emitted".  ttx_score_proposal_bias runs
+ * the scoring stage (d_score, d_tok_logp) on the RAW logits first, in the same pass, so p stays the model's; a caller's d_logits then
+ * receives the biased logits.  ttx_hypothesis_logq_bias leaves the caller's logits alone (it biases a copy).  A NULL d_bias is the
+ * call without one. */
+int ttx_hypothesis_logq_bias(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad, int eos,
+                             const ttx_dist* dist, const int32_t* d_forced_len, const float* d_bias, int ld_bias, int N,
+                             float* d_tok_logq, float* d_logq, int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept,
+                             int32_t* d_length, uint8_t* d_finished, void* stream);
+int ttx_score_proposal_bias(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N, int W, int eos,
+                            const ttx_dist* dist, const int32_t* d_forced_len, const float* d_bias, int ld_bias, float* d_logits,
+                            float* d_tok_logp, float* d_score, float* d_tok_logq, float* d_logq, int32_t* d_first_outside,
+                            int32_t* d_rank, int32_t* d_n_kept, int32_t* d_length, uint8_t* d_finished, void* stream);
+/* ONE launch of k_logit_bias on DEVICE arrays of the caller (tests/test_gpu_logit_bias_kernel.py), in place on d_logits fp32 [M][V];
+ * rows at or beyond *d_m (int32 on the device, NULL: M) keep their bits.  Plain mapping (d_act_idx NULL): the bias row of logits row r
+ * is d_src[r], or r / rows_per_src with a NULL d_src.  Step layout (d_act_idx set, k_sample_step's): lrow = d_row_map ? d_row_map[row]
+ * : row, b = d_act_idx[lrow / (1 + N * D)], bias row d_src[b].  Every index is the caller's to keep in range. */
+int ttx_debug_logit_bias(ttx_session* s, float* d_logits, int V, int M, const int32_t* d_m, const float* d_bias, int ld_bias,
+                         const int32_t* d_src, int rows_per_src, const int32_t* d_act_idx, const int32_t* d_row_map, int N, int D,
+                         void* stream);
+/* The number of k_logit_bias launches the session has enqueued since it was created, eagerly or into a captured step (a replayed
+ * graph adds none; ttx_debug_logit_bias is not counted).  A session that only ever served unbiased calls reports 0. */
+int ttx_debug_logit_bias_launches(ttx_session* s);
+
 /* Beam-speculative bookkeeping kernels.
  * ttx_nucleus_mask: mask_with_num_logits_according_nucleus (src/decoding/speculative_decoding.py:871-904): per row of
  *   d_logits [rows,V] keep the best logit and further ones, best first, while the softmax mass ranked above is
@@ -678,6 +744,15 @@ int ttx_sbs_generate_ex(ttx_session* s, const int64_t* d_src, int B, int Ls, con
                         const ttx_sbs_filter* f_or_null, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
                         int64_t* d_out, float* d_logp, float* d_gumbel, const ttx_sbs_trace* trace_or_null,
                         ttx_beam_search_stats* stats, void* stream);
+/* ttx_sbs_generate_ex under a per-source logit bias ("Per-source logit bias" above; d_bias fp32 [B][ld_bias] on the device, NULL: the
+ * call without one).  k_logit_bias rewrites every level's logits before the step kernel reads them (the row of a running candidate
+ * takes the bias row of the candidate's source), so phi, logp and the K rows are those of the biased, then filtered, distribution: a
+ * sample without replacement from what the biased sampler draws from.  Fewer than K rows may exist under a narrow allow-list; the
+ * missing ranks come back as under a filter. */
+int ttx_sbs_generate_bias(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sbs_params* p,
+                          const ttx_sbs_filter* f_or_null, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
+                          const float* d_bias, int ld_bias, int64_t* d_out, float* d_logp, float* d_gumbel,
+                          const ttx_sbs_trace* trace_or_null, ttx_beam_search_stats* stats, void* stream);
 
 /* Stochastic beam search over a whole list of sources on a pool of source slots (continuous batching; kernels and slot state:
  * csrc/ttx_sbs_pool.hip.h).  Each of up to n_sessions pools owns C <= capacity source slots of K candidates; a

@@ -18,7 +18,7 @@ LIB_PATH = PKG_DIR / "libttx_hip.so"
 UNITS = [CSRC / "ttx_api.hip", CSRC / "ttx_gemm.hip", CSRC / "ttx_attn.hip"]
 HEADERS = [CSRC / "ttx_internal.h", CSRC / "ttx_common.hip.h", CSRC / "ttx_loop_kernels.hip.h", CSRC / "ttx_metrics.hip.h",
            CSRC / "ttx_score.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_sample.hip.h", CSRC / "ttx_logq.hip.h", CSRC / "ttx_sbs.hip.h", CSRC / "ttx_sbs_pool.hip.h",
-           CSRC / "ttx_proposal.hip.h",
+           CSRC / "ttx_proposal.hip.h", CSRC / "ttx_logit_bias.hip.h",
            CSRC / "ttx_select.h", CSRC / "ttx_tokenizer.h", CSRC / "ttx_drive.h", CSRC / "ttx_admit.h", INCLUDE / "ttx.h"]
 SOURCES = UNITS + HEADERS
 OBJ_DIR = CSRC / "build"
@@ -162,6 +162,21 @@ class SampleSpecParams(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class SampleOpts(C.Structure):
+    """ttx_sample_opts: every option of a sampling call (prefix, proposal, logit bias); a zeroed struct is the plain call."""
+    _fields_ = [("d_prefix", C.c_void_p), ("ld_prefix", C.c_int32), ("h_prefix_len", C.c_void_p),
+                ("d_proposal", C.c_void_p), ("ld_proposal", C.c_int32), ("h_proposal_len", C.c_void_p),
+                ("d_bias", C.c_void_p), ("ld_bias", C.c_int32)]
+
+    @classmethod
+    def of(cls, prefix_ptr=None, ld_prefix=0, h_prefix_len=None, proposal_ptr=None, ld_proposal=0, h_proposal_len=None, bias=None):
+        """From the device pointers, the HOST length arrays (ctypes int32 arrays, which the caller keeps alive) and a contiguous
+        float32 device tensor ``bias`` [sources, V] (or None)."""
+        host = lambda a: None if a is None else C.cast(a, C.c_void_p)
+        return cls(prefix_ptr, ld_prefix, host(h_prefix_len), proposal_ptr, ld_proposal, host(h_proposal_len),
+                   None if bias is None else bias.data_ptr(), 0 if bias is None else int(bias.stride(0)))
+
+
 class DebugPrefix(C.Structure):
     """ttx_debug_prefix: the forced prefixes of a debug launch (table, row length, sources; per-row length and table row)."""
     _fields_ = [("d_tok", C.c_void_p), ("ld", C.c_int32), ("n_sources", C.c_int32), ("d_len", C.c_void_p), ("d_src", C.c_void_p)]
@@ -288,6 +303,19 @@ SYMBOLS = {
     "ttx_sample_speculative_generate_pool_proposal": (C.c_int, [C.POINTER(_VP), _I, _VP, _I, _I, C.POINTER(C.c_int32), _VP, _I,
                                                                C.POINTER(SampleSpecParams), _VP, _I, C.POINTER(C.c_int32), _VP, _I,
                                                                C.POINTER(C.c_int32), _VP, C.POINTER(GenStats), _VP]),
+    "ttx_sample_generate_ex": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SampleParams), C.POINTER(SampleOpts), _VP, C.POINTER(GenStats), _VP]),
+    "ttx_sample_speculative_generate_ex": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SampleSpecParams), C.POINTER(SampleOpts), _VP,
+                                                    C.POINTER(GenStats), _VP]),
+    "ttx_sample_speculative_generate_pool_ex": (C.c_int, [C.POINTER(_VP), _I, _VP, _I, _I, C.POINTER(C.c_int32), _VP, _I,
+                                                         C.POINTER(SampleSpecParams), C.POINTER(SampleOpts), _VP, C.POINTER(GenStats), _VP]),
+    "ttx_hypothesis_logq_bias": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, _I, C.POINTER(Dist), _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP,
+                                          _VP, _VP, _VP]),
+    "ttx_score_proposal_bias": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, C.POINTER(Dist), _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP,
+                                         _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ttx_sbs_generate_bias": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SbsParams), C.POINTER(SbsFilter), _VP, _I, _VP, _VP, _I, _VP, _VP,
+                                       _VP, C.POINTER(SbsTrace), C.POINTER(BeamSearchStats), _VP]),
+    "ttx_debug_logit_bias_launches": (C.c_int, [_VP]),
+    "ttx_debug_logit_bias": (C.c_int, [_VP, _VP, _I, _I, _VP, _VP, _I, _VP, _I, _VP, _VP, _I, _I, _VP]),
     "ttx_greedy_speculative_generate_many": (C.c_int, [C.POINTER(_VP), _I, _I, C.POINTER(_VP), C.POINTER(C.c_int),
                                                       C.POINTER(C.c_int), C.POINTER(GenParams), C.POINTER(_VP),
                                                       C.POINTER(GenStats), _VP]),

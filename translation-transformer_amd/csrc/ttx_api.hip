@@ -11,6 +11,7 @@
 #include "ttx_alternatives.hip.h"
 #include "ttx_attn_probs.hip.h"
 #include "ttx_sample.hip.h"
+#include "ttx_logit_bias.hip.h"
 #include "ttx_logq.hip.h"
 #include "ttx_sbs.hip.h"
 #include "ttx_sbs_pool.hip.h"
@@ -1057,7 +1058,33 @@ struct StepCtx {
   int sel_N = 0, sel_D = 0;        // probe: the layout of the draft pass, whose choice between k_attn2 and k_attn it takes
   // draft select (draft pass of a split step; all null otherwise): the pass's rows are stored compacted (k_probe_split)
   const int* row_base = nullptr; const int* draft_mask = nullptr; const int* row_map = nullptr;
+  // per-source logit bias (val null: none, no launch): k_logit_bias between the classifier and the consumer of the logits.  `src` goes
+  // by decoder row (slot of a pool; candidate of a beam loop); the values live in a session buffer, never in the caller's tensor
+  LogitBiasTab bias{};
 };
+
+// k_logit_bias with k_sample's launch shape, in place on `a.logits`; `step`: the step-row layout (act_idx, row_map, N, D set).
+static int launch_logit_bias(hipStream_t st, const LogitBiasArgs& a, bool step) {
+  const dim3 grid(cdiv(a.M, 4)), block(256);
+  if (step) hipLaunchKernelGGL((k_logit_bias<true>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((k_logit_bias<false>), grid, block, 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+// The bias of a call over S sources into the session's table, float [S][V] (the row length is the vocabulary, which no key needs to
+// hold): a captured step reads the session's buffer and nothing of the caller's.  Enqueued outside capture, before the first step.
+static int bias_upload(ttx_session* s, hipStream_t st, const float* d_bias, int ld_bias, int S) {
+  const size_t row = (size_t)s->m->cfg.vocab_size * sizeof(float);
+  HIP_TRY(hipMemcpy2DAsync(s->lb_val.p, row, d_bias, (size_t)ld_bias * sizeof(float), row, (size_t)S, hipMemcpyDeviceToDevice, st));
+  return TTX_OK;
+}
+
+// The bias arguments of a generate call, or TTX_ERR_INVALID (the values are the caller's to keep finite or -inf: they live on the device).
+static int bias_validate(const char* who, const ttx_session* s, const float* d_bias, int ld_bias) {
+  if (d_bias && ld_bias < s->m->cfg.vocab_size) return fail(TTX_ERR_INVALID, std::string(who) + ": ld_bias must be at least the vocabulary");
+  return TTX_OK;
+}
 
 // k_sample with k_argmax's launch shape; the values a lane holds follow the vocabulary (V <= SAMPLE_MAX_V, checked by the callers).
 static int launch_sample(hipStream_t st, const SampleArgs& a) {
@@ -1168,6 +1195,13 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
         return launch_attn(ATT_STEP_CROSS, s, st, ca, k.B, H, RPS, k.Ls, k.N, D1);
       },
       logits));
+  if (k.bias.val) {                  // one launch, and none in an unbiased step
+    LogitBiasArgs b{};
+    b.logits = logits; b.V = V; b.m_ptr = m_ptr; b.M = Mmax; b.tab = k.bias; b.rows_per_src = 1;
+    if (!k.want_sample) { b.act_idx = act; b.row_map = k.row_map; b.N = k.N; b.D = k.D; }
+    TTX_TRY(launch_logit_bias(st, b, !k.want_sample));
+    s->logit_bias_launches += 1;
+  }
   if (k.want_sample) {
     SampleArgs a = k.sample;
     a.logits = logits; a.V = V; a.pred = s->pred.as<int>(); a.m_ptr = m_ptr; a.M = Mmax;
@@ -1508,7 +1542,7 @@ static int gen_launch_step(GenJob& j, int width_bound) {
     const int site = k.want_sample_step ? (prop ? GS_STEP_SAMPLE_SPEC_PROPOSAL : pfx ? GS_STEP_SAMPLE_SPEC_PREFIX : GS_STEP_SAMPLE_SPEC)
                      : k.want_sample    ? (pfx ? GS_STEP_SAMPLE_PREFIX : GS_STEP_SAMPLE)
                      : j.greedy ? GS_STEP_GREEDY : (j.g.la.row_rule ? GS_STEP_ROW_RULE : GS_STEP_SPECULATIVE);
-    GraphKey key{site, k.B, k.Ls, k.N, k.D, k.max_len, kcap, k.variant, 0};
+    GraphKey key{site | (k.bias.val ? GS_LOGIT_BIAS : 0), k.B, k.Ls, k.N, k.D, k.max_len, kcap, k.variant, 0};
     if (prop) key.push_back(k.prop_ctx);
     TTX_TRY(graph_replay(s, j.st, s->step_graphs, key, enqueue));
   }
@@ -1641,6 +1675,8 @@ struct SampleSetup {
   // either prompted or proposed; proposed false: no proposal, launch for launch
   bool proposed; int prop_ctx;
   bool tabled() const { return prompted || proposed; }
+  // per-source logit bias (bias_validate): d_bias null is the unbiased call, launch for launch; [n_sources][ld_bias]
+  const float* d_bias; int ld_bias;
 };
 
 // The prefix arguments of a sampling call over S sources, or TTX_ERR_INVALID.  A call whose lengths are all zero (or absent) is
@@ -1701,6 +1737,7 @@ static int sample_ensure(ttx_session* s, hipStream_t st, size_t rows, const Samp
     TTX_TRY(ensure(s->pfx_len, rows * 4, st));
     if (smp.spec) TTX_TRY(ensure(s->pfx_draft0, rows * p->draft_len * 4, st));
   }
+  if (smp.d_bias) TTX_TRY(ensure(s->lb_val, (size_t)smp.n_sources * s->m->cfg.vocab_size * sizeof(float), st));
   TTX_TRY(ensure(s->smp_key, rows * 8, st));
   TTX_TRY(ensure(s->smp_sample, rows * 4, st));
   TTX_TRY(ensure(s->smp_done, rows * 4, st));
@@ -1737,6 +1774,10 @@ static int sample_begin(GenJob& j, const SampleSetup& smp) {
                                hipMemcpyDeviceToDevice, j.st));
       k.pfx_draft0 = s->pfx_draft0.as<int>();
     }
+  }
+  if (smp.d_bias) {                                  // decoder row -> source: the map k_sample_init wrote
+    TTX_TRY(bias_upload(s, j.st, smp.d_bias, smp.ld_bias, smp.n_sources));
+    k.bias = LogitBiasTab{s->lb_val.as<float>(), s->m->cfg.vocab_size, s->smp_src_of.as<int>()};
   }
   return TTX_OK;
 }
@@ -1861,26 +1902,60 @@ static int launch_logq(ttx_session* s, hipStream_t st, const float* logits, cons
   return TTX_OK;
 }
 
-extern "C" int ttx_hypothesis_logq(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad, int eos,
-                                   const ttx_dist* dist, const int32_t* d_forced_len, float* d_tok_logq, float* d_logq,
-                                   int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept, int32_t* d_length,
-                                   uint8_t* d_finished, void* stream) {
+// k_logit_bias on teacher-forced logits [R, T, V] of R hypothesis rows, N per source: logits row r * T + t belongs to source r / N.
+static int bias_scored_logits(hipStream_t st, float* logits, int R, int T, int V, int N, const float* d_bias, int ld_bias) {
+  LogitBiasArgs a{};
+  a.logits = logits; a.V = V; a.M = R * T; a.tab = LogitBiasTab{d_bias, ld_bias, nullptr}; a.rows_per_src = N * T;
+  return launch_logit_bias(st, a, false);
+}
+
+static int hypothesis_logq(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad, int eos,
+                           const ttx_dist* dist, const int32_t* d_forced_len, float* d_tok_logq, float* d_logq,
+                           int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept, int32_t* d_length,
+                           uint8_t* d_finished, void* stream, const float* d_bias, int ld_bias, int N) {
   if (!s) return session_required("ttx_hypothesis_logq");
   if (!d_logits || !d_hyp || !d_logq || !d_length) return fail(TTX_ERR_INVALID, "bad argument to ttx_hypothesis_logq");
   TTX_TRY(check_score_shapes(s, R, W, V, "ttx_hypothesis_logq"));
+  if (d_bias && (ld_bias < V || N < 1 || R % N != 0))
+    return fail(TTX_ERR_INVALID, "ttx_hypothesis_logq_bias: ld_bias must be at least V and R a multiple of the rows per source");
   SampleBlock b{};
   TTX_TRY(logq_block("ttx_hypothesis_logq", dist, &b));
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(s->m->device));
+  if (d_bias) {                           // the caller's logits stay as they are: the biased copy lives in session scratch
+    const size_t bytes = (size_t)R * (W - 1) * V * sizeof(float);
+    TTX_TRY(ensure(s->ev_logits, bytes, st));
+    HIP_TRY(hipMemcpyAsync(s->ev_logits.p, d_logits, bytes, hipMemcpyDeviceToDevice, st));
+    TTX_TRY(bias_scored_logits(st, s->ev_logits.as<float>(), R, W - 1, V, N, d_bias, ld_bias));
+    s->logit_bias_launches += 1;
+    d_logits = s->ev_logits.as<float>();
+  }
   return launch_logq(s, st, d_logits, d_hyp, W, R, W, V, pad, eos, b, d_forced_len,
                      LogqOut{d_tok_logq, d_logq, d_first_outside, d_rank, d_n_kept, d_length, d_finished});
 }
 
-extern "C" int ttx_score_proposal(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N, int W,
-                                  int eos, const ttx_dist* dist, const int32_t* d_forced_len, float* d_logits, float* d_tok_logp,
-                                  float* d_score, float* d_tok_logq, float* d_logq, int32_t* d_first_outside, int32_t* d_rank,
-                                  int32_t* d_n_kept, int32_t* d_length, uint8_t* d_finished, void* stream) {
+extern "C" int ttx_hypothesis_logq(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad, int eos,
+                                   const ttx_dist* dist, const int32_t* d_forced_len, float* d_tok_logq, float* d_logq,
+                                   int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept, int32_t* d_length,
+                                   uint8_t* d_finished, void* stream) {
+  return hypothesis_logq(s, d_logits, d_hyp, R, W, V, pad, eos, dist, d_forced_len, d_tok_logq, d_logq, d_first_outside, d_rank, d_n_kept,
+                         d_length, d_finished, stream, nullptr, 0, 1);
+}
+
+extern "C" int ttx_hypothesis_logq_bias(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad, int eos,
+                                        const ttx_dist* dist, const int32_t* d_forced_len, const float* d_bias, int ld_bias, int N,
+                                        float* d_tok_logq, float* d_logq, int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept,
+                                        int32_t* d_length, uint8_t* d_finished, void* stream) {
+  return hypothesis_logq(s, d_logits, d_hyp, R, W, V, pad, eos, dist, d_forced_len, d_tok_logq, d_logq, d_first_outside, d_rank, d_n_kept,
+                         d_length, d_finished, stream, d_bias, ld_bias, N);
+}
+
+static int score_proposal(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N, int W,
+                          int eos, const ttx_dist* dist, const int32_t* d_forced_len, float* d_logits, float* d_tok_logp,
+                          float* d_score, float* d_tok_logq, float* d_logq, int32_t* d_first_outside, int32_t* d_rank,
+                          int32_t* d_n_kept, int32_t* d_length, uint8_t* d_finished, void* stream, const float* d_bias, int ld_bias) {
   if (!s) return session_required("ttx_score_proposal");
+  if (d_bias && ld_bias < s->m->cfg.vocab_size) return fail(TTX_ERR_INVALID, "ttx_score_proposal_bias: ld_bias must be at least the vocabulary");
   if (!d_src || !d_hyp || !d_logq || !d_length || B <= 0 || N <= 0 || Ls <= 0)
     return fail(TTX_ERR_INVALID, "bad argument to ttx_score_proposal");
   if (d_tok_logp && !d_score) return fail(TTX_ERR_INVALID, "ttx_score_proposal: d_tok_logp needs d_score");
@@ -1898,6 +1973,15 @@ extern "C" int ttx_score_proposal(ttx_session* s, const int64_t* d_src, int B, i
     d_logits = s->ev_logits.as<float>();
   }
   TTX_TRY(score_forward(s, st, d_src, B, Ls, d_hyp, ld_hyp, N, W, d_logits));
+  if (d_bias) {
+    // p before q, from one pass: k_hyp_score reads the raw logits, k_logit_bias then rewrites them in place (a caller's d_logits
+    // receives the biased values), and k_hyp_logq reads what the biased sampler's consumer reads
+    if (d_score) TTX_TRY(launch_score(s, st, d_logits, d_hyp, ld_hyp, R, W, V, pad, eos, d_tok_logp, d_score, d_length, d_finished));
+    TTX_TRY(bias_scored_logits(st, d_logits, R, T, V, N, d_bias, ld_bias));
+    s->logit_bias_launches += 1;
+    return launch_logq(s, st, d_logits, d_hyp, ld_hyp, R, W, V, pad, eos, b, d_forced_len,
+                       LogqOut{d_tok_logq, d_logq, d_first_outside, d_rank, d_n_kept, d_length, d_finished});
+  }
   if (logq_is_model(b, d_forced_len)) {
     // q is the model's own distribution: ONE launch of k_hyp_score gives the values, so that they are ttx_score_hypotheses' bit
     // for bit; with d_score set they are copied, not computed twice.  first_outside follows from them (k_logq_first_outside);
@@ -1925,11 +2009,29 @@ extern "C" int ttx_score_proposal(ttx_session* s, const int64_t* d_src, int B, i
                      LogqOut{d_tok_logq, d_logq, d_first_outside, d_rank, d_n_kept, d_length, d_finished});
 }
 
+extern "C" int ttx_score_proposal(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N, int W,
+                                  int eos, const ttx_dist* dist, const int32_t* d_forced_len, float* d_logits, float* d_tok_logp,
+                                  float* d_score, float* d_tok_logq, float* d_logq, int32_t* d_first_outside, int32_t* d_rank,
+                                  int32_t* d_n_kept, int32_t* d_length, uint8_t* d_finished, void* stream) {
+  return score_proposal(s, d_src, B, Ls, d_hyp, ld_hyp, N, W, eos, dist, d_forced_len, d_logits, d_tok_logp, d_score, d_tok_logq, d_logq,
+                        d_first_outside, d_rank, d_n_kept, d_length, d_finished, stream, nullptr, 0);
+}
+
+extern "C" int ttx_score_proposal_bias(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N, int W,
+                                       int eos, const ttx_dist* dist, const int32_t* d_forced_len, const float* d_bias, int ld_bias,
+                                       float* d_logits, float* d_tok_logp, float* d_score, float* d_tok_logq, float* d_logq,
+                                       int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept, int32_t* d_length,
+                                       uint8_t* d_finished, void* stream) {
+  return score_proposal(s, d_src, B, Ls, d_hyp, ld_hyp, N, W, eos, dist, d_forced_len, d_logits, d_tok_logp, d_score, d_tok_logq, d_logq,
+                        d_first_outside, d_rank, d_n_kept, d_length, d_finished, stream, d_bias, ld_bias);
+}
+
 // ttx_sample_generate and ttx_sample_generate_prefix: one body, the unprompted call with a null prefix.
 static int sample_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sample_params* p,
                            int64_t* d_out, ttx_gen_stats* stats, void* stream, const int64_t* d_prefix, int ld_prefix,
-                           const int32_t* h_prefix_len) {
+                           const int32_t* h_prefix_len, const float* d_bias = nullptr, int ld_bias = 0) {
   if (!s || !p) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
+  TTX_TRY(bias_validate("ttx_sample_generate", s, d_bias, ld_bias));
   if (s->m->cfg.vocab_size > SAMPLE_MAX_V) return fail(TTX_ERR_INVALID, "ttx_sample_generate: vocabularies above 1024 are not supported");
   if (p->num_samples < 1) return fail(TTX_ERR_INVALID, "ttx_sample_generate: num_samples must be at least 1");
   SampleSetup smp{};
@@ -1938,6 +2040,7 @@ static int sample_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, 
     return fail(TTX_ERR_INVALID, "ttx_sample_generate: B * num_samples * (max_len + 2) must stay below 2^31");
   smp.n = p->num_samples; smp.d_row_keys = d_row_keys;
   TTX_TRY(prefix_validate("ttx_sample_generate", d_prefix, ld_prefix, h_prefix_len, std::max(B, 0), p->max_len, &smp));
+  smp.d_bias = d_bias; smp.ld_bias = ld_bias;
   ttx_gen_params g{};
   g.max_len = p->max_len; g.draft_len = 0; g.n_drafts = 1; g.pad_token = p->pad_token; g.bos_token = p->bos_token;
   g.eos_token = p->eos_token; g.replace_token = p->pad_token; g.want_logits = 0;
@@ -1956,6 +2059,16 @@ extern "C" int ttx_sample_generate_prefix(ttx_session* s, const int64_t* d_src, 
                                           const ttx_sample_params* p, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
                                           int64_t* d_out, ttx_gen_stats* stats, void* stream) {
   return sample_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, d_prefix, ld_prefix, h_prefix_len);
+}
+
+// The form that takes every option of the plain sampler: the prefix of ttx_sample_generate_prefix and the per-source logit bias.
+extern "C" int ttx_sample_generate_ex(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                      const ttx_sample_params* p, const ttx_sample_opts* o, int64_t* d_out, ttx_gen_stats* stats,
+                                      void* stream) {
+  if (!o) return sample_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, nullptr, 0, nullptr);
+  if (o->h_proposal_len) return fail(TTX_ERR_INVALID, "ttx_sample_generate_ex: the plain sampler verifies no drafts and takes no proposal");
+  return sample_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, o->d_prefix, o->ld_prefix, o->h_prefix_len, o->d_bias,
+                         o->ld_bias);
 }
 
 // What the speculative sampling calls refuse with TTX_ERR_INVALID whatever code gen_validate would give (nothing of these calls is
@@ -1986,9 +2099,11 @@ static int sample_spec_validate(const char* who, const ttx_session* s, const ttx
 static int sample_speculative_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
                                        const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream,
                                        const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
-                                       const int64_t* d_proposal = nullptr, int ld_proposal = 0, const int32_t* h_proposal_len = nullptr) {
+                                       const int64_t* d_proposal = nullptr, int ld_proposal = 0, const int32_t* h_proposal_len = nullptr,
+                                       const float* d_bias = nullptr, int ld_bias = 0) {
   const char* who = "ttx_sample_speculative_generate";
   if (!s || !p) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
+  TTX_TRY(bias_validate(who, s, d_bias, ld_bias));
   SampleSetup smp{};
   ttx_gen_params g{};
   const long long R = (long long)std::max(B, 0) * std::max(p->sample.num_samples, 0);
@@ -1997,6 +2112,7 @@ static int sample_speculative_generate(ttx_session* s, const int64_t* d_src, int
   smp.d_row_keys = d_row_keys;
   TTX_TRY(prefix_validate(who, d_prefix, ld_prefix, h_prefix_len, B, g.max_len, &smp));
   TTX_TRY(proposal_validate(who, d_proposal, ld_proposal, h_proposal_len, B, g.max_len, &smp));
+  smp.d_bias = d_bias; smp.ld_bias = ld_bias;
   const int rc = generate_one(s, d_src, (int)R, Ls, &g, d_out, stats, stream, false, &smp);
   if (rc == TTX_OK && stats) stats->src_tokens_padded = (long long)B * Ls;    // the encoder ran once per source
   return rc;
@@ -2022,6 +2138,16 @@ extern "C" int ttx_sample_speculative_generate_proposal(ttx_session* s, const in
                                                         void* stream) {
   return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, d_prefix, ld_prefix, h_prefix_len, d_proposal,
                                      ld_proposal, h_proposal_len);
+}
+
+// The form that takes every option: prefix, proposal and the per-source logit bias (a null `o` is the plain call).
+extern "C" int ttx_sample_speculative_generate_ex(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                                  const ttx_sample_spec_params* p, const ttx_sample_opts* o, int64_t* d_out,
+                                                  ttx_gen_stats* stats, void* stream) {
+  const ttx_sample_opts none{};
+  if (!o) o = &none;
+  return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, o->d_prefix, o->ld_prefix, o->h_prefix_len,
+                                     o->d_proposal, o->ld_proposal, o->h_proposal_len, o->d_bias, o->ld_bias);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2112,6 +2238,7 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
     need(s->pfx_tok, (size_t)smp->n_sources * max_len * 4); need(s->pfx_len_src, (size_t)smp->n_sources * 4);
     need(s->pfx_len, (size_t)C * 4); need(s->pfx_src, (size_t)C * 4); need(s->pfx_draft0, (size_t)C * D * 4);
   }
+  if (smp && smp->d_bias) { need(s->lb_val, (size_t)smp->n_sources * c.vocab_size * sizeof(float)); need(s->lb_src, (size_t)C * 4); }
   TTX_TRY(need.rc);
   AcceptBlk* blk = nullptr;
   // the greedy pool keeps the session's reading of TTX_ACCEPT_SPREAD; the sampling pool reads it here, with its other switches
@@ -2171,6 +2298,7 @@ static int pool_admit(PoolJob& j, const int64_t* d_src_rows, int ld_src, int R, 
     a.key = s->smp_key.as<unsigned long long>(); a.sample = s->smp_sample.as<unsigned>(); a.row_keys = j.d_row_keys;
     a.per_src = j.per_src; a.first_src = first_row;
     if (step_tab(k).tok) { a.pfx_src = s->pfx_src.as<int>(); a.pfx_len = s->pfx_len.as<int>(); a.pfx_len_of_src = s->pfx_len_src.as<int>(); }
+    if (k.bias.val) a.bias_src = s->lb_src.as<int>();
   }
   hipLaunchKernelGGL(k_pool_admit, dim3(1), dim3(256), (size_t)j.C * 4, st, a);
   HIP_TRY(hipGetLastError());
@@ -2194,10 +2322,11 @@ static int pool_admit(PoolJob& j, const int64_t* d_src_rows, int ld_src, int R, 
 // The sampling pool has a site of its own, and its keys end with the form of the accept step (1: the pair), which it reads from
 // the environment per call.
 static GraphKey pool_key(const PoolJob& j, const StepCtx& k, int variant, int phase) {
+  const int biased = k.bias.val ? GS_LOGIT_BIAS : 0; // a biased step is never replayed for an unbiased call
   if (k.want_sample_step && k.prop.tok)              // a proposed pool: a site of its own, the key ends with the context length
-    return GraphKey{GS_STEP_POOL_SAMPLE_PROPOSAL, k.B, k.Ls, k.N, k.D, k.max_len, k.max_len, variant, phase, j.g.la.blk ? 1 : 0, k.prop_ctx};
+    return GraphKey{GS_STEP_POOL_SAMPLE_PROPOSAL | biased, k.B, k.Ls, k.N, k.D, k.max_len, k.max_len, variant, phase, j.g.la.blk ? 1 : 0, k.prop_ctx};
   if (k.want_sample_step)
-    return GraphKey{k.sample.pfx.tok ? GS_STEP_POOL_SAMPLE_PREFIX : GS_STEP_POOL_SAMPLE, k.B, k.Ls, k.N, k.D, k.max_len, k.max_len, variant, phase, j.g.la.blk ? 1 : 0};
+    return GraphKey{(k.sample.pfx.tok ? GS_STEP_POOL_SAMPLE_PREFIX : GS_STEP_POOL_SAMPLE) | biased, k.B, k.Ls, k.N, k.D, k.max_len, k.max_len, variant, phase, j.g.la.blk ? 1 : 0};
   return GraphKey{GS_STEP_POOL, k.B, k.Ls, k.N, k.D, k.max_len, k.max_len, variant, phase};
 }
 
@@ -2298,6 +2427,10 @@ static int pool_sample_begin(PoolJob& j, const SampleSetup& smp) {
     if (smp.proposed) { k.prop = tab; k.prop_ctx = smp.prop_ctx; }
     else k.sample.pfx = tab;
     k.pfx_draft0 = s->pfx_draft0.as<int>();
+  }
+  if (smp.d_bias) {                                  // every pool of the call holds the whole table; a slot's row is written at admission
+    TTX_TRY(bias_upload(s, j.st, smp.d_bias, smp.ld_bias, smp.n_sources));
+    k.bias = LogitBiasTab{s->lb_val.as<float>(), s->m->cfg.vocab_size, s->lb_src.as<int>()};
   }
   return TTX_OK;
 }
@@ -2416,12 +2549,13 @@ static int sample_speculative_generate_pool(ttx_session** sessions, int n_sessio
                                             const int32_t* h_len, const int64_t* d_row_keys, int capacity, const ttx_sample_spec_params* p,
                                             int64_t* d_out, ttx_gen_stats* stats, void* stream, const int64_t* d_prefix, int ld_prefix,
                                             const int32_t* h_prefix_len, const int64_t* d_proposal = nullptr, int ld_proposal = 0,
-                                            const int32_t* h_proposal_len = nullptr) {
+                                            const int32_t* h_proposal_len = nullptr, const float* d_bias = nullptr, int ld_bias = 0) {
   const char* who = "ttx_sample_speculative_generate_pool";
   if (!sessions || n_sessions <= 0 || !d_src || S_total < 0 || !h_len || !p || !d_out)
     return fail(TTX_ERR_INVALID, std::string("bad argument to ") + who);
   for (int i = 0; i < n_sessions; ++i)
     if (!sessions[i]) return fail(TTX_ERR_INVALID, std::string("bad argument to ") + who);
+  TTX_TRY(bias_validate(who, sessions[0], d_bias, ld_bias));
   SampleSetup smp{};
   ttx_gen_params g{};
   TTX_TRY(sample_spec_validate(who, sessions[0], p, capacity, &smp, &g));
@@ -2439,6 +2573,7 @@ static int sample_speculative_generate_pool(ttx_session** sessions, int n_sessio
   TTX_TRY(proposal_validate(who, d_proposal, ld_proposal, h_proposal_len, S_total, g.max_len, &smp));
   if (S_total == 0) return TTX_OK;
   smp.d_row_keys = d_row_keys;
+  smp.d_bias = d_bias; smp.ld_bias = ld_bias;
   return pool_generate(sessions, n_sessions, d_src, S_total, Ls_all, h_len, Ls_cap, capacity, &g, d_out, nullptr, nullptr, stats, stream, &smp);
 }
 
@@ -2468,6 +2603,18 @@ extern "C" int ttx_sample_speculative_generate_pool_proposal(ttx_session** sessi
                                                              void* stream) {
   return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p, d_out, stats, stream,
                                           d_prefix, ld_prefix, h_prefix_len, d_proposal, ld_proposal, h_proposal_len);
+}
+
+// The form that takes every option; the bias table is [S_total][ld_bias] in the order of d_src, and a slot gets its row at admission.
+extern "C" int ttx_sample_speculative_generate_pool_ex(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total,
+                                                       int Ls_all, const int32_t* h_len, const int64_t* d_row_keys, int capacity,
+                                                       const ttx_sample_spec_params* p, const ttx_sample_opts* o, int64_t* d_out,
+                                                       ttx_gen_stats* stats, void* stream) {
+  const ttx_sample_opts none{};
+  if (!o) o = &none;
+  return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p, d_out, stats, stream,
+                                          o->d_prefix, o->ld_prefix, o->h_prefix_len, o->d_proposal, o->ld_proposal, o->h_proposal_len,
+                                          o->d_bias, o->ld_bias);
 }
 
 // Several batches in flight on one GPU: outputs per batch are identical to the one-at-a-time call.
@@ -3323,6 +3470,7 @@ struct BeamSearchJob {
   bool masked = false;
   int top_k = 0; float top_p = 1.f;
   PrefixTab pfx{};
+  LogitBiasTab bias{};       // ttx_sbs_generate_bias: the session's table, by candidate (t_src_of); val null: no bias, no launch
 };
 
 // Everything of the call behind the argument check: the reference's asserts and this library's limits, the workspaces, the
@@ -3386,7 +3534,9 @@ static int bsearch_launch_iter(BeamSearchJob& j) {
   if (j.launched > 0) TTX_TRY(enqueue_tree_cache(s, st, j.MC, j.Lc, cur, cur ^ 1, nullptr, nullptr, 1, 0));
   TTX_TRY(enqueue_bs_list(s, st, j.n_cand, 1, 0));
   const int variant = variant_for_rows(s, (long long)std::max(1, j.n_cand - j.n_eos), true);
-  TTX_TRY(run_step(s, st, tree_step_ctx(s, j.MC, j.Ls, 1, 0, j.Lc, j.ld, max_len, cur ^ 1, variant), key_capacity(j.width, max_len)));
+  StepCtx k = tree_step_ctx(s, j.MC, j.Ls, 1, 0, j.Lc, j.ld, max_len, cur ^ 1, variant);
+  k.bias = j.bias;                 // the step kernels below then read biased logits
+  TTX_TRY(run_step(s, st, k, key_capacity(j.width, max_len)));
   if (j.sbs) {
     SbsStepArgs sa{};
     float* const gbuf[2] = {s->sbs_g.as<float>(), s->sbs_g_next.as<float>()};
@@ -3481,9 +3631,11 @@ extern "C" int ttx_beam_generate(ttx_session* s, const int64_t* d_src, int B, in
 // ttx_sbs_generate and ttx_sbs_generate_ex: one body; a call with no filter and no prefix is the plain one, launch for launch.
 static int sbs_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sbs_params* p,
                         int64_t* d_out, float* d_logp, float* d_gumbel, const ttx_sbs_trace* trace, ttx_beam_search_stats* stats,
-                        void* stream, const ttx_sbs_filter* f, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len) {
+                        void* stream, const ttx_sbs_filter* f, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
+                        const float* d_bias = nullptr, int ld_bias = 0) {
   if (!s || !d_src || !p || !d_out || !d_logp || !d_gumbel || !stats || B <= 0 || Ls <= 1)
     return fail(TTX_ERR_INVALID, "bad argument to ttx_sbs_generate");
+  TTX_TRY(bias_validate("ttx_sbs_generate_bias", s, d_bias, ld_bias));
   const int V = s->m->cfg.vocab_size;
   if (p->max_len <= 1) return fail(TTX_ERR_INVALID, "ttx_sbs_generate: max_len must exceed 1");
   if (p->beam_size < 1 || p->beam_size > SBS_MAX_BEAM) return fail(TTX_ERR_INVALID, "ttx_sbs_generate: beam_size must lie in [1, 32]");
@@ -3515,7 +3667,12 @@ static int sbs_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, con
       TTX_TRY(ensure(s->pfx_len_src, (size_t)B * 4, st));
       TTX_TRY(ensure(s->smp_src_of, (size_t)B * 4, st));
     }
+    if (d_bias) TTX_TRY(ensure(s->lb_val, (size_t)B * V * sizeof(float), st));
     TTX_TRY(bsearch_start(j, s, st, d_src, B, Ls, &bp, d_out, true));
+    if (d_bias) {                       // the steps run eagerly, yet read the session's copy as every biased loop does
+      TTX_TRY(bias_upload(s, st, d_bias, ld_bias, B));
+      j.bias = LogitBiasTab{s->lb_val.as<float>(), V, s->t_src_of.as<int>()};
+    }
     j.inv_T = inv_T; j.seed = p->seed; j.row_keys = d_row_keys; j.d_logp = d_logp; j.d_gumbel = d_gumbel;
     if (trace) j.trace = *trace;
     j.masked = masked; j.top_k = top_k; j.top_p = top_p;
@@ -3553,6 +3710,15 @@ extern "C" int ttx_sbs_generate_ex(ttx_session* s, const int64_t* d_src, int B, 
                                    ttx_beam_search_stats* stats, void* stream) {
   return sbs_generate(s, d_src, B, Ls, d_row_keys, p, d_out, d_logp, d_gumbel, trace, stats, stream, f_or_null, d_prefix, ld_prefix,
                       h_prefix_len);
+}
+
+// ttx_sbs_generate_ex under a per-source logit bias: k_logit_bias runs on every level's logits before the step kernel reads them.
+extern "C" int ttx_sbs_generate_bias(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sbs_params* p,
+                                     const ttx_sbs_filter* f_or_null, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
+                                     const float* d_bias, int ld_bias, int64_t* d_out, float* d_logp, float* d_gumbel,
+                                     const ttx_sbs_trace* trace, ttx_beam_search_stats* stats, void* stream) {
+  return sbs_generate(s, d_src, B, Ls, d_row_keys, p, d_out, d_logp, d_gumbel, trace, stats, stream, f_or_null, d_prefix, ld_prefix,
+                      h_prefix_len, d_bias, ld_bias);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4108,6 +4274,28 @@ static int dbg_check_slots(const char* who, const int32_t* d_act_idx, const int3
     *max_front = std::max(*max_front, (int)front[b]);
   }
   return TTX_OK;
+}
+
+// ONE launch of k_logit_bias on the caller's device arrays (tests/test_gpu_logit_bias_kernel.py): the plain mapping (d_act_idx null:
+// d_src by row, or null for row / rows_per_src) or the step layout (d_act_idx set: d_row_map or null, N, D).
+extern "C" int ttx_debug_logit_bias(ttx_session* s, float* d_logits, int V, int M, const int32_t* d_m, const float* d_bias, int ld_bias,
+                                    const int32_t* d_src, int rows_per_src, const int32_t* d_act_idx, const int32_t* d_row_map, int N, int D,
+                                    void* stream) {
+  if (!s) return session_required("ttx_debug_logit_bias");
+  if (!d_logits || !d_bias || V <= 0 || M <= 0 || ld_bias < V) return fail(TTX_ERR_INVALID, "bad argument to ttx_debug_logit_bias");
+  if (d_act_idx ? (!d_src || N < 1 || D < 0) : (!d_src && rows_per_src < 1))
+    return fail(TTX_ERR_INVALID, "ttx_debug_logit_bias: the step layout needs d_src, N >= 1 and D >= 0; the plain mapping d_src or rows_per_src >= 1");
+  HIP_TRY(hipSetDevice(s->m->device));
+  LogitBiasArgs a{};
+  a.logits = d_logits; a.V = V; a.m_ptr = d_m; a.M = M; a.tab = LogitBiasTab{d_bias, ld_bias, d_src}; a.rows_per_src = std::max(rows_per_src, 1);
+  a.act_idx = d_act_idx; a.row_map = d_row_map; a.N = N; a.D = D;
+  return launch_logit_bias((hipStream_t)stream, a, d_act_idx != nullptr);
+}
+
+// k_logit_bias launches the session has enqueued (eagerly or into a captured step; a replayed graph adds none) since it was created,
+// ttx_debug_logit_bias's not counted: 0 for a session that never served a biased call.
+extern "C" int ttx_debug_logit_bias_launches(ttx_session* s) {
+  return s ? (int)std::min<long long>(s->logit_bias_launches, 0x7fffffff) : 0;
 }
 
 extern "C" int ttx_debug_argmax(ttx_session* s, const float* d_logits, int V, int32_t* d_pred, const int32_t* d_m, int m_max,

@@ -90,7 +90,11 @@ enum AttnKernelId { AK_ATTN = 1, AK_ATTN2 = 2, AK_ATTN3 = 3, AK_ATTN3S = 4, AK_A
 enum GraphSite { GS_STEP_SPECULATIVE = 0, GS_STEP_GREEDY = 1, GS_STEP_ROW_RULE = 2, GS_STEP_POOL = 3, GS_BEAM_ITER = 4, GS_BEAM_POOL_ITER = 5,
                  GS_STEP_SAMPLE = 6, GS_STEP_SAMPLE_SPEC = 7, GS_STEP_POOL_SAMPLE = 8,
                  GS_STEP_SAMPLE_PREFIX = 9, GS_STEP_SAMPLE_SPEC_PREFIX = 10, GS_STEP_POOL_SAMPLE_PREFIX = 11,
-                 GS_STEP_SAMPLE_SPEC_PROPOSAL = 12, GS_STEP_POOL_SAMPLE_PROPOSAL = 13, GS_SBS_POOL_ITER = 14 };
+                 GS_STEP_SAMPLE_SPEC_PROPOSAL = 12, GS_STEP_POOL_SAMPLE_PROPOSAL = 13, GS_SBS_POOL_ITER = 14,
+                 // or-ed into the site of a sampling step that carries a per-source logit bias (k_logit_bias between the classifier
+                 // and the sampling kernel, reading the session's table): the key of the unbiased step is untouched, and a biased
+                 // step is never replayed for an unbiased call
+                 GS_LOGIT_BIAS = 256 };
 typedef std::vector<int> GraphKey;
 
 // Captured graphs of one family of keys.  A key runs eagerly the first time it is seen (`warmed`: function attributes are set
@@ -152,6 +156,9 @@ struct GraphCache {
   /* forced prefixes of a prompted sampling call: the table int32 [sources][max_len] and the sources' lengths; per decoder row */ \
   /* (slot) its prefix length, its row of the table (pool; single-session loops use smp_src_of) and its source draft 0 [D] */     \
   X(pfx_tok) X(pfx_len_src) X(pfx_len) X(pfx_src) X(pfx_draft0)                                                                  \
+  /* per-source logit bias of a biased call: the session's copy of the table, float [sources][V], and per pool slot its row of it */ \
+  /* (single-session loops use smp_src_of, the beam loops t_src_of) */                                                            \
+  X(lb_val) X(lb_src)                                                                                                            \
   /* stochastic beam search (ttx_sbs_generate): the perturbed log-probabilities G of the candidates, read and written in turn */  \
   X(sbs_g) X(sbs_g_next)                                                                                                         \
   /* stochastic beam pool (ttx_sbs_generate_pool): the per-slot words (keys, then six int arrays), the sources' lengths and the */ \
@@ -172,6 +179,7 @@ struct ttx_session {
   ttx::ProbeInfo* probe_info = nullptr; // pinned + device-mapped, written by k_probe_split
   // ttx_pool_last_counters: summed over the pools of the last slot-pool call (greedy or sampling) whose first session this was
   long long pool_counters[7] = {};
+  long long logit_bias_launches = 0;    // k_logit_bias launches this session enqueued or captured (ttx_debug_logit_bias_launches)
   ttx::BeamHost* beam_host = nullptr;   // pinned + device-mapped, written by k_bs_publish
   ttx::BeamPoolHost* bp_host = nullptr; // pinned + device-mapped, written by k_bsp_publish
   ttx::HostInfo* host_info = nullptr;   // pinned + device-mapped, written by the accept kernels

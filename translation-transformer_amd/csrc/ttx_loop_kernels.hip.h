@@ -575,6 +575,8 @@ struct PoolAdmitArgs {
   unsigned long long* key; unsigned* sample; const int64_t* row_keys; int per_src, first_src;
   // prompted sampling pool (pfx_src null: no prefixes): the slot's source index in the call's list and that source's prefix length
   int* pfx_src; int* pfx_len; const int* pfx_len_of_src;
+  // biased sampling pool (null: no logit bias): the slot's row of the call's bias table, i.e. its source index in the call's list
+  int* bias_src;
 };
 
 // One block.  Free slots = those not in act_idx[0, n_active); the R new rows take the lowest free ones in order.
@@ -600,6 +602,7 @@ __global__ __launch_bounds__(256) void k_pool_admit(PoolAdmitArgs a) {
         a.key[b] = a.row_keys ? (unsigned long long)a.row_keys[src] : (unsigned long long)src;
         a.sample[b] = (unsigned)(got % a.per_src);
         if (a.pfx_src) { a.pfx_src[b] = src; a.pfx_len[b] = a.pfx_len_of_src[src]; }
+        if (a.bias_src) a.bias_src[b] = src;
       }
       ++got;
     }

@@ -13,6 +13,15 @@ import torch
 
 from . import _native as N
 from .model import AttentionMaps, HypothesisScores, NativeTransformer, ProposalScores
+from .scoring import combine_bias
+
+
+def _refuse_bias(who: str, logit_bias, allowed) -> None:
+    """The generators that take no logit bias say so, rather than decode unconstrained."""
+    if logit_bias is not None or allowed is not None:
+        raise ValueError(f"{who} takes no logit_bias / allowed: the per-source logit bias is implemented for TranslationInferenceSampling, "
+                         "TranslationInferenceSamplingSpeculative (generate and generate_many) and "
+                         "TranslationInferenceStochasticBeamSearch.generate; temperature=0 on the samplers is constrained greedy decoding")
 
 
 def _need_native(model) -> NativeTransformer:
@@ -53,12 +62,15 @@ class _ScoresHypotheses:
             raise ValueError("the generator's pad token differs from the model's")
         return self.model.alternatives(src, pred, k=k, eos_token_idx=eos, **kw)
 
-    def logq(self, src: torch.Tensor, pred: torch.Tensor, prefix=None, **kw) -> ProposalScores:
+    def logq(self, src: torch.Tensor, pred: torch.Tensor, prefix=None, logit_bias=None, allowed=None, **kw) -> ProposalScores:
         """The log-probability of the hypotheses ``pred`` (Long[B, N, L] as ``generate(src)`` returned it) under a SAMPLING
         distribution, beside ``score`` (which gives it under the model): by default the generator's own ``temperature``,
         ``top_k`` and ``top_p`` where it has them (the two samplers, stochastic beam search), temperature 1 without a filter on
         the deterministic generators.  ``prefix``: the forced prefix the rows were generated with (``check_prefix``'s form);
-        its positions cost nothing (``forced_len`` = the prefix lengths).  Other keywords go to
+        its positions cost nothing (``forced_len`` = the prefix lengths).  ``logit_bias`` (Float[B, V]) and / or ``allowed``
+        (Bool[B, V]): the per-source bias the rows were generated under (``generate``'s keywords): ``logq`` is then the
+        log-probability under the biased distribution, ``-inf`` with ``first_outside`` at the first forbidden token for a row the
+        biased sampler cannot emit, while ``with_scores=True`` keeps ``scores`` the raw model's.  Other keywords go to
         ``NativeTransformer.proposal_scores``."""
         pad, eos = self._pad_eos()
         if pad != self.model.tgt_pad_token_i:
@@ -70,20 +82,26 @@ class _ScoresHypotheses:
                 raise ValueError("a call takes a prefix or forced_len, not both")
             _, lengths = check_prefix(prefix, int(pred.shape[0]), int(pred.shape[-1]), pad, self.model.tgt_vocab_size)
             kw["forced_len"] = torch.tensor(lengths, dtype=torch.int32)
+        bias = combine_bias(logit_bias, allowed, int(pred.shape[0]), self.model.tgt_vocab_size)
+        if bias is not None:
+            kw["logit_bias"] = bias
         return self.model.proposal_scores(src, pred, eos_token_idx=eos, **kw)
 
-    def _scored(self, src: torch.Tensor, pred: torch.Tensor, return_scores: bool, return_logq: bool = False, prefix=None):
+    def _scored(self, src: torch.Tensor, pred: torch.Tensor, return_scores: bool, return_logq: bool = False, prefix=None,
+                logit_bias=None):
         """``pred``; with ``return_scores`` and / or ``return_logq`` the tuple ``(pred[, HypothesisScores][, ProposalScores])``.
         Both flags: ONE decoder pass (``with_scores=True``), the ProposalScores' ``scores`` being the HypothesisScores."""
         if not return_logq:
             return (pred, self.score(src, pred)) if return_scores else pred
-        q = self.logq(src, pred, prefix=prefix, with_scores=return_scores)
+        q = self.logq(src, pred, prefix=prefix, logit_bias=logit_bias, with_scores=return_scores)
         return (pred, q.scores, q) if return_scores else (pred, q)
 
-    def _scored_many(self, batches: list, preds: list, return_scores: bool = True, return_logq: bool = False, prefixes=None) -> list:
+    def _scored_many(self, batches: list, preds: list, return_scores: bool = True, return_logq: bool = False, prefixes=None,
+                     biases=None) -> list:
         pres = prefixes if prefixes is not None else [None] * len(batches)
+        bs = biases if biases is not None else [None] * len(batches)
         return [(p,) + (None,) * (int(return_scores) + int(return_logq)) if p is None
-                else self._scored(b, p, return_scores, return_logq, q) for b, p, q in zip(batches, preds, pres)]
+                else self._scored(b, p, return_scores, return_logq, q, lb) for b, p, q, lb in zip(batches, preds, pres, bs)]
 
 
 def _slot_pool_plan(rows: int, in_flight: int, capacity: int | None) -> tuple:
@@ -142,8 +160,10 @@ class TranslationInferenceGreedySpeculative(_ScoresHypotheses):
         return (f"Greedy speculative decoding (draft_len={self.draft_len}, n_drafts={self.n_drafts}, "
                 f"max_len={self.max_len})")
 
-    def generate(self, src: torch.Tensor, return_scores: bool = False):
-        """``return_scores=True``: ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``)."""
+    def generate(self, src: torch.Tensor, return_scores: bool = False, logit_bias=None, allowed=None):
+        """``return_scores=True``: ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``).  ``logit_bias`` / ``allowed``
+        are refused (ValueError): the samplers at ``temperature=0`` decode greedily under a bias."""
+        _refuse_bias("TranslationInferenceGreedySpeculative", logit_bias, allowed)
         m = self.model
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
@@ -165,7 +185,8 @@ class TranslationInferenceGreedySpeculative(_ScoresHypotheses):
         return self._scored(src, out, return_scores)
 
     def generate_many(self, batches: list, in_flight: int = 4, reorder: bool = False, group_size: int | None = None,
-                      on_error: str = "raise", pool: bool | None = None, return_scores: bool = False) -> list:
+                      on_error: str = "raise", pool: bool | None = None, return_scores: bool = False, logit_biases=None,
+                      allowed=None) -> list:
         """Decode several batches with up to `in_flight` of them on the GPU at once (one session + stream each;
         ttx_greedy_speculative_generate_many).  Returns one [B,1,max_len] tensor per batch, each identical to what
         ``generate`` returns for that batch; counters accumulate as if ``generate`` had been called per batch.
@@ -180,7 +201,8 @@ class TranslationInferenceGreedySpeculative(_ScoresHypotheses):
         kept in ``self.last_failed_batches``.
 
         ``return_scores=True``: a list of ``(pred, HypothesisScores)`` pairs; a batch that came back ``None`` has ``None``
-        scores."""
+        scores.  ``logit_biases`` / ``allowed`` are refused (ValueError), as in ``generate``."""
+        _refuse_bias("TranslationInferenceGreedySpeculative.generate_many", logit_biases, allowed)
         if return_scores:
             return self._scored_many(batches, self.generate_many(batches, in_flight, reorder, group_size, on_error, pool))
         m = self.model
@@ -365,8 +387,10 @@ class TranslationInferenceGreedy(_ScoresHypotheses):
     def __str__(self):
         return f"Greedy decoding (max_len={self.max_len})"
 
-    def generate(self, src: torch.Tensor, return_scores: bool = False):
-        """``return_scores=True``: ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``)."""
+    def generate(self, src: torch.Tensor, return_scores: bool = False, logit_bias=None, allowed=None):
+        """``return_scores=True``: ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``).  ``logit_bias`` / ``allowed``
+        are refused (ValueError): ``TranslationInferenceSampling`` at ``temperature=0`` is this loop under a bias."""
+        _refuse_bias("TranslationInferenceGreedy", logit_bias, allowed)
         m = self.model
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
@@ -440,7 +464,14 @@ class TranslationInferenceSampling(_ScoresHypotheses):
         d = p.to(m.device)
         return d, (d.data_ptr() if d.numel() else None), int(d.shape[1]), (C.c_int32 * max(B, 1))(*lengths)
 
-    def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, prefix=None, return_logq: bool = False):
+    def _bias_arg(self, logit_bias, allowed, B: int):
+        """The call's ``logit_bias`` / ``allowed`` as one contiguous float32 device tensor [B, V], or None for neither."""
+        m = self.model
+        bias = combine_bias(logit_bias, allowed, B, m.tgt_vocab_size)
+        return None if bias is None else bias.to(m.device).contiguous()
+
+    def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, prefix=None, return_logq: bool = False,
+                 logit_bias=None, allowed=None):
         """Long[B, num_samples, max_len].  ``row_keys``: one integer per source (default 0..B-1), the source's identity for
         the random stream: the same (source, key) gives the same samples in any batch.  ``return_scores=True``:
         ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``).  ``return_logq=True``: ``(pred, ProposalScores)``, the
@@ -450,13 +481,22 @@ class TranslationInferenceSampling(_ScoresHypotheses):
         ``prefix``: Long[B, Lp] without BOS, right-padded with PAD: the forced beginning of every sample of a source.  A
         row is BOS, its prefix, the sampled completion, PAD; a position inside the prefix holds the prefix token whatever the
         logits say and consumes no random number, so the completion's draws are those of its positions.  A forced EOS ends
-        the row.  One decoder step per forced token.  An empty prefix (zero width, all PAD, ``None``) is the unprompted call."""
+        the row.  One decoder step per forced token.  An empty prefix (zero width, all PAD, ``None``) is the unprompted call.
+
+        ``logit_bias``: Float[B, V], one row per source, added to the logits of every row of that source at every position before
+        temperature and filter (one rounded fp32 add; an entry that is exactly zero leaves the logit's bits alone; ``-inf`` forbids
+        the token; ``NaN`` and ``+inf`` are refused: ``scoring.check_logit_bias``).  ``allowed``: Bool[B, V], sugar for a bias of
+        0 / ``-inf`` (``scoring.allowlist_from_source`` builds the "tokens of the source" list); both together: the allow-list is
+        added onto the bias.  A forced prefix position ignores the bias.  A row depends on its source, key, sample id, prefix and
+        its source's bias row alone.  ``temperature=0`` is constrained greedy decoding.  ``return_logq=True`` scores under the
+        call's bias.  ``None`` for both is the call without the keywords, launch for launch."""
         m, n = self.model, self.num_samples
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
         B, Ls = src.shape
         # d_prefix is bound only to keep the device tensor alive until the call returns: prefix_ptr points into it
         d_prefix, prefix_ptr, ld_prefix, h_plen = self._prefix_args(prefix, B)
+        bias = self._bias_arg(logit_bias, allowed, B)
         keys = None
         if row_keys is not None:
             keys = torch.as_tensor(row_keys, dtype=torch.int64).to(m.device).contiguous()
@@ -466,13 +506,18 @@ class TranslationInferenceSampling(_ScoresHypotheses):
                            self.eos_token, self.seed & 0xFFFFFFFFFFFFFFFF)
         out = torch.empty((B, max(n, 1), max(self.max_len, 1)), dtype=torch.int64, device=m.device)
         st = N.GenStats()
-        N.check(m._lib.ttx_sample_generate_prefix(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
-                                                  C.byref(p), prefix_ptr, ld_prefix, h_plen, out.data_ptr(), C.byref(st),
-                                                  m._stream()))
+        if bias is None:
+            N.check(m._lib.ttx_sample_generate_prefix(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
+                                                      C.byref(p), prefix_ptr, ld_prefix, h_plen, out.data_ptr(), C.byref(st),
+                                                      m._stream()))
+        else:
+            opts = N.SampleOpts.of(prefix_ptr, ld_prefix, h_plen, bias=bias)
+            N.check(m._lib.ttx_sample_generate_ex(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
+                                                  C.byref(p), C.byref(opts), out.data_ptr(), C.byref(st), m._stream()))
         self.model_calls_num += int(st.model_calls)
         self.given_tokens += int((src != m.src_pad_token_i).sum())
         self.last_stats = st
-        return self._scored(src, out, return_scores, return_logq, prefix)
+        return self._scored(src, out, return_scores, return_logq, prefix, bias)
 
 
 class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
@@ -499,9 +544,10 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
                 f"top_k={self.top_k}, top_p={self.top_p}, num_samples={self.num_samples}, seed={self.seed}, max_len={self.max_len})")
 
     def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, prefix=None, proposal=None,
-                 return_logq: bool = False):
-        """Long[B, num_samples, max_len]; ``row_keys``, ``return_scores``, ``return_logq`` and ``prefix`` as for
-        ``TranslationInferenceSampling.generate``.  A prefix rides in as the first draft of its rows, which is certain to be
+                 return_logq: bool = False, logit_bias=None, allowed=None):
+        """Long[B, num_samples, max_len]; ``row_keys``, ``return_scores``, ``return_logq``, ``prefix``, ``logit_bias`` and
+        ``allowed`` as for ``TranslationInferenceSampling.generate`` (the rows under a bias are the plain sampler's under the same
+        bias; a draft, prefix-as-draft or proposal token the biased sampler cannot emit is never accepted).  A prefix rides in as the first draft of its rows, which is certain to be
         accepted: ``P`` forced tokens take ``ceil(P / (draft_len + 1))`` verify steps.
 
         ``proposal``: Long[B, Lq] without BOS, right-padded with PAD, may end in EOS: a draft the caller brings for every sample
@@ -524,6 +570,7 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         # d_prefix is bound only to keep the device tensor alive until the call returns: prefix_ptr points into it
         d_prefix, prefix_ptr, ld_prefix, h_plen = self._prefix_args(prefix, B)
         d_prop, prop_ptr, ld_prop, h_qlen = self._prefix_args(proposal, B)          # the same checks and limits
+        bias = self._bias_arg(logit_bias, allowed, B)
         keys = None
         if row_keys is not None:
             keys = torch.as_tensor(row_keys, dtype=torch.int64).to(m.device).contiguous()
@@ -534,10 +581,16 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
                                self.draft_len, self.n_drafts, self.replace_token, 0)
         out = torch.empty((B, max(n, 1), max(self.max_len, 1)), dtype=torch.int64, device=m.device)
         st = N.GenStats()
-        N.check(m._lib.ttx_sample_speculative_generate_proposal(m.session, src.data_ptr(), B, Ls,
-                                                                None if keys is None else keys.data_ptr(), C.byref(p), prefix_ptr,
-                                                                ld_prefix, h_plen, prop_ptr, ld_prop, h_qlen, out.data_ptr(),
-                                                                C.byref(st), m._stream()))
+        if bias is None:
+            N.check(m._lib.ttx_sample_speculative_generate_proposal(m.session, src.data_ptr(), B, Ls,
+                                                                    None if keys is None else keys.data_ptr(), C.byref(p), prefix_ptr,
+                                                                    ld_prefix, h_plen, prop_ptr, ld_prop, h_qlen, out.data_ptr(),
+                                                                    C.byref(st), m._stream()))
+        else:
+            opts = N.SampleOpts.of(prefix_ptr, ld_prefix, h_plen, prop_ptr, ld_prop, h_qlen, bias)
+            N.check(m._lib.ttx_sample_speculative_generate_ex(m.session, src.data_ptr(), B, Ls,
+                                                              None if keys is None else keys.data_ptr(), C.byref(p), C.byref(opts),
+                                                              out.data_ptr(), C.byref(st), m._stream()))
         self.model_calls_num += int(st.model_calls)
         self.accepted_tokens_num += int(st.accepted_tokens)
         self.given_tokens += int((src != m.src_pad_token_i).sum())
@@ -548,10 +601,11 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         t["src_tokens_padded"] += B * Ls
         t["batches"] += 1
         self.last_stats = st
-        return self._scored(src, out, return_scores, return_logq, prefix)
+        return self._scored(src, out, return_scores, return_logq, prefix, bias)
 
     def generate_many(self, batches: list, row_keys=None, in_flight: int = 4, capacity: int | None = None,
-                      return_scores: bool = False, prefixes=None, proposals=None, return_logq: bool = False) -> list:
+                      return_scores: bool = False, prefixes=None, proposals=None, return_logq: bool = False,
+                      logit_biases=None, allowed=None) -> list:
         """The samples of all batches from slot pools (ttx_sample_speculative_generate_pool: continuous batching over the sources
         of the whole list, sorted by length; the ``num_samples`` rows of a source are admitted together).  Returns one
         Long[B_i, num_samples, max_len] per batch.
@@ -567,10 +621,27 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         ``None``; ``generate_many(batches, prefixes=ps)[i]`` holds the rows of ``generate(batches[i], prefix=ps[i],
         row_keys=arange(off_i, off_i + B_i))``.
         ``proposals``: the same for ``generate``'s ``proposal``: offered drafts, which change no row.  A call takes ``prefixes``
-        or ``proposals``, not both (ValueError)."""
+        or ``proposals``, not both (ValueError).
+        ``logit_biases`` and ``allowed``: lists aligned with ``batches``, each entry a ``logit_bias`` / ``allowed`` tensor for that
+        batch (see ``generate``) or ``None``: ``generate_many(batches, logit_biases=bs)[i]`` holds the rows of
+        ``generate(batches[i], logit_bias=bs[i], row_keys=arange(off_i, off_i + B_i))``.  Every pool holds the call's table
+        [S, V]; a slot gets its source's row at admission and a reused slot carries nothing over.  ``return_logq=True`` scores
+        each batch under its own bias."""
+        for name, tabs in (("logit_biases", logit_biases), ("allowed", allowed)):
+            if tabs is not None and len(tabs) != len(batches):
+                raise ValueError(f"{name} must hold one entry per batch ({len(batches)}), got {len(tabs)}")
+        biases = None
+        if logit_biases is not None or allowed is not None:
+            V = self.model.tgt_vocab_size
+            lbs = logit_biases if logit_biases is not None else [None] * len(batches)
+            als = allowed if allowed is not None else [None] * len(batches)
+            biases = [combine_bias(lb, al, int(b.shape[0]), V) for lb, al, b in zip(lbs, als, batches)]
+            if all(b is None for b in biases):
+                biases = None
         if return_scores or return_logq:
             return self._scored_many(batches, self.generate_many(batches, row_keys, in_flight, capacity, prefixes=prefixes,
-                                                                 proposals=proposals), return_scores, return_logq, prefixes)
+                                                                 proposals=proposals, logit_biases=biases),
+                                     return_scores, return_logq, prefixes, biases)
         from .scheduling import plan_row_groups
         if prefixes is not None and proposals is not None:
             raise ValueError("a call takes forced prefixes or proposals, not both")
@@ -602,6 +673,10 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
 
         allpre, plen = stacked(prefixes)
         allprop, qlen = stacked(proposals)
+        allbias = None                  # every source's bias row, zeros (no bias) for the batches that carry none
+        if biases is not None:
+            allbias = torch.cat([torch.zeros((B, V), dtype=torch.float32, device=m.device) if b is None else b.to(m.device)
+                                 for b, B in zip(biases, sizes)])
         srcs = [b.to(m.device, torch.int64) for b in batches]
         if row_keys is None:
             keys = torch.arange(S, dtype=torch.int64)
@@ -655,10 +730,17 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
 
             pre_sorted, pre_ptr, ld_prefix, h_plen = table_args(allpre, plen)
             prop_sorted, prop_ptr, ld_prop, h_qlen = table_args(allprop, qlen)
-            N.check(m._lib.ttx_sample_speculative_generate_pool_proposal(sess, len(sessions), src_mat.data_ptr(), S, width, h_len,
-                                                                         keys_sorted.data_ptr(), cap, C.byref(p), pre_ptr, ld_prefix,
-                                                                         h_plen, prop_ptr, ld_prop, h_qlen, out_sorted.data_ptr(),
-                                                                         C.byref(st), m._stream()))
+            if allbias is None:
+                N.check(m._lib.ttx_sample_speculative_generate_pool_proposal(sess, len(sessions), src_mat.data_ptr(), S, width, h_len,
+                                                                             keys_sorted.data_ptr(), cap, C.byref(p), pre_ptr, ld_prefix,
+                                                                             h_plen, prop_ptr, ld_prop, h_qlen, out_sorted.data_ptr(),
+                                                                             C.byref(st), m._stream()))
+            else:
+                bias_sorted = allbias[order_t].contiguous()
+                opts = N.SampleOpts.of(pre_ptr, ld_prefix, h_plen, prop_ptr, ld_prop, h_qlen, bias_sorted)
+                N.check(m._lib.ttx_sample_speculative_generate_pool_ex(sess, len(sessions), src_mat.data_ptr(), S, width, h_len,
+                                                                       keys_sorted.data_ptr(), cap, C.byref(p), C.byref(opts),
+                                                                       out_sorted.data_ptr(), C.byref(st), m._stream()))
             inv = torch.empty_like(order_t)
             inv[order_t] = torch.arange(S, device=m.device)
             out_rows = out_sorted[inv]
@@ -698,8 +780,10 @@ class TranslationInferenceBeamSearch(_ScoresHypotheses):
     def __str__(self):
         return f"Beam search decoding (beam_size={self.beam_size}, max_len={self.max_len})"
 
-    def generate(self, src: torch.Tensor, return_scores: bool = False):
-        """``return_scores=True``: ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``)."""
+    def generate(self, src: torch.Tensor, return_scores: bool = False, logit_bias=None, allowed=None):
+        """``return_scores=True``: ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``).  ``logit_bias`` / ``allowed``
+        are refused (ValueError)."""
+        _refuse_bias("TranslationInferenceBeamSearch", logit_bias, allowed)
         m, K = self.model, self.beam_size
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
@@ -770,7 +854,7 @@ class TranslationInferenceStochasticBeamSearch(_ScoresHypotheses):
                 f"top_p={self.top_p}, seed={self.seed}, max_len={self.max_len})")
 
     def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, return_details: bool = False,
-                 order: str = "sample", trace: bool = False, prefix=None):
+                 order: str = "sample", trace: bool = False, prefix=None, logit_bias=None, allowed=None):
         """Long[B, K, max_len]: BOS, the tokens up to and including the first EOS or PAD, PAD after.  ``row_keys``: one integer
         per source (default 0..B-1), the source's identity for the random stream.  ``order="sample"``: rows in sampling order
         (``gumbel`` descending); ``order="logp"``: re-sorted by ``logp``, best first (equal values keep their sampling order).
@@ -782,7 +866,13 @@ class TranslationInferenceStochasticBeamSearch(_ScoresHypotheses):
         the rows are K distinct completions, a sample without replacement from the model's distribution given source and prefix,
         and ``logp`` is the completion's conditional log-probability.  A forced position reads no logits and spends no noise; a
         forced EOS ends the row (one finite row).  One decoder step per forced token.  An empty prefix (zero width, all PAD,
-        ``None``) is the unprompted call."""
+        ``None``) is the unprompted call.
+
+        ``logit_bias`` (Float[B, V]) and ``allowed`` (Bool[B, V]) as for ``TranslationInferenceSampling.generate``: the bias is
+        added to every level's logits before temperature and filter (ttx_sbs_generate_bias), so the K rows are a sample without
+        replacement from what the biased sampler draws from and ``logp`` is the log-probability under it; under a narrow
+        allow-list fewer than K rows may exist (the missing ranks come back as under a filter).  ``None`` for both is the call
+        without the keywords."""
         if order not in ("sample", "logp"):
             raise ValueError(f"order must be 'sample' or 'logp', got {order!r}")
         m, K = self.model, self.beam_size
@@ -815,9 +905,17 @@ class TranslationInferenceStochasticBeamSearch(_ScoresHypotheses):
             tr_arg = C.byref(N.SbsTrace(*(t.data_ptr() for t in tr)))
         st = N.BeamSearchStats()
         filt = N.SbsFilter(self.top_k, self.top_p)
-        N.check(m._lib.ttx_sbs_generate_ex(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(), C.byref(p),
-                                           C.byref(filt), prefix_ptr, ld_prefix, h_plen, out.data_ptr(), logp.data_ptr(),
-                                           gumbel.data_ptr(), tr_arg, C.byref(st), m._stream()))
+        bias = combine_bias(logit_bias, allowed, B, m.tgt_vocab_size)
+        if bias is None:
+            N.check(m._lib.ttx_sbs_generate_ex(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(), C.byref(p),
+                                               C.byref(filt), prefix_ptr, ld_prefix, h_plen, out.data_ptr(), logp.data_ptr(),
+                                               gumbel.data_ptr(), tr_arg, C.byref(st), m._stream()))
+        else:
+            bias = bias.to(m.device).contiguous()
+            N.check(m._lib.ttx_sbs_generate_bias(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
+                                                 C.byref(p), C.byref(filt), prefix_ptr, ld_prefix, h_plen, bias.data_ptr(),
+                                                 int(bias.stride(0)), out.data_ptr(), logp.data_ptr(), gumbel.data_ptr(), tr_arg,
+                                                 C.byref(st), m._stream()))
         self.model_calls_num += int(st.model_calls)
         self.b_sz += int(st.running_rows)
         self.given_tokens += int((src != m.src_pad_token_i).sum())
@@ -847,7 +945,8 @@ class TranslationInferenceStochasticBeamSearch(_ScoresHypotheses):
         return (int(given) if given is not None else min(1024, max(1, rows_cap // K))), n_sess
 
     def generate_many(self, batches: list, row_keys=None, in_flight: int = 4, capacity: int | None = None,
-                      return_scores: bool = False, return_details: bool = False, order: str = "sample", prefixes=None) -> list:
+                      return_scores: bool = False, return_details: bool = False, order: str = "sample", prefixes=None,
+                      logit_biases=None, allowed=None) -> list:
         """``generate`` over a whole list of batches on pools of source slots (ttx_sbs_generate_pool: continuous batching over the
         sources of the list, sorted by length).  A source leaves the pool as soon as its K rows are finished and the next one
         takes its slot, so a decoder pass serves unfinished candidates only.  Returns one entry per batch, shaped as ``generate``
@@ -863,6 +962,7 @@ class TranslationInferenceStochasticBeamSearch(_ScoresHypotheses):
         served; ``last_batch_counters`` holds each batch's share of the counters (``b_sz`` and ``given_tokens`` as ``generate`` counts
         them for that batch, the decoder passes apportioned by candidates)."""
         from .scheduling import plan_row_groups
+        _refuse_bias("TranslationInferenceStochasticBeamSearch.generate_many (the source-slot pool)", logit_biases, allowed)
         if order not in ("sample", "logp"):
             raise ValueError(f"order must be 'sample' or 'logp', got {order!r}")
         self._pool_plan(1, in_flight, capacity)               # refuses a capacity outside [1, 1024] before anything else
@@ -1047,8 +1147,10 @@ class TranslationInferenceBeamSearchSpeculative(_ScoresHypotheses):
         if not self.smart_drafts_mode:
             self.n_drafts += B * self.requested_drafts_num                       # :434
 
-    def generate(self, src: torch.Tensor, return_scores: bool = False):
-        """``return_scores=True``: ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``)."""
+    def generate(self, src: torch.Tensor, return_scores: bool = False, logit_bias=None, allowed=None):
+        """``return_scores=True``: ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``).  ``logit_bias`` / ``allowed``
+        are refused (ValueError)."""
+        _refuse_bias("TranslationInferenceBeamSearchSpeculative", logit_bias, allowed)
         m = self.model
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
@@ -1061,7 +1163,7 @@ class TranslationInferenceBeamSearchSpeculative(_ScoresHypotheses):
         return self._scored(src, out[:, :, :int(st.out_width)].contiguous(), return_scores)
 
     def generate_many(self, batches: list, in_flight: int = 4, pool: bool | None = None, on_error: str = "raise",
-                      capacity: int | None = None, return_scores: bool = False) -> list:
+                      capacity: int | None = None, return_scores: bool = False, logit_biases=None, allowed=None) -> list:
         """Several batches on the GPU at once; every returned tensor and the counters are those of per-batch ``generate`` calls.
 
         ``pool`` (default: on for two or more batches, ``TTX_BEAM_POOL=0`` turns it off): the given batches are decoded in slot
@@ -1075,7 +1177,8 @@ class TranslationInferenceBeamSearchSpeculative(_ScoresHypotheses):
         ending the call; the indices are kept in ``self.last_failed_batches`` — ``generate`` on that batch raises the error.
 
         ``return_scores=True``: a list of ``(pred, HypothesisScores)`` pairs; a batch that came back ``None`` has ``None``
-        scores."""
+        scores.  ``logit_biases`` / ``allowed`` are refused (ValueError), as in ``generate``."""
+        _refuse_bias("TranslationInferenceBeamSearchSpeculative.generate_many", logit_biases, allowed)
         if return_scores:
             return self._scored_many(batches, self.generate_many(batches, in_flight, pool, on_error, capacity))
         m = self.model

@@ -109,9 +109,10 @@ class _PredictAhead:
         self.decode_seconds = 0.0
         self.rows = 0                # sources decoded ahead so far: the running index the sampling generators key their rows by
         self.prefixes = {}           # batch index -> the batch's "prefix_tokens" it was decoded with (sampling generators; None: none)
+        self.biases = {}             # batch index -> the batch's ("logit_bias", "allowed_tokens") it was decoded with (None: none)
 
     def _decode_window(self, device) -> None:
-        pending, prefixes, proposals = [], [], []
+        pending, prefixes, proposals, biases, allowed = [], [], [], [], []
         for _ in range(self.window):
             try:
                 b = next(self.it)
@@ -120,6 +121,8 @@ class _PredictAhead:
             pending.append(b["src_tokens"].to(device))
             prefixes.append(b.get("prefix_tokens") if hasattr(b, "get") else None)
             proposals.append(b.get("proposal_tokens") if hasattr(b, "get") else None)
+            biases.append(b.get("logit_bias") if hasattr(b, "get") else None)
+            allowed.append(b.get("allowed_tokens") if hasattr(b, "get") else None)
         if not pending:
             self.enabled = False
             return
@@ -133,6 +136,13 @@ class _PredictAhead:
         if proposed and not isinstance(g, D.TranslationInferenceSamplingSpeculative):
             raise ValueError(f'"proposal_tokens" in a batch: only generation="sampling_speculative" takes proposals, '
                              f"not {type(g).__name__}")
+        biased = any(q is not None for q in biases) or any(q is not None for q in allowed)
+        if biased and not keyed:
+            raise ValueError(f'"logit_bias" / "allowed_tokens" in a batch: only generation="sampling", "sampling_speculative" and '
+                             f'"stochastic_beam_search" take a logit bias, not {type(g).__name__}')
+        if biased and not isinstance(g, D.TranslationInferenceSamplingSpeculative):
+            self.enabled = False     # the stochastic beam pool takes no bias: these batches are decoded one by one (take() falls back)
+            return
         t0 = timer()
         if isinstance(g, D.TranslationInferenceGreedySpeculative):      # slot pools over all rows of the window
             preds = g.generate_many(pending, in_flight=self.in_flight, reorder=True, on_error="skip")
@@ -142,6 +152,8 @@ class _PredictAhead:
                 keys.append(torch.arange(r0, r0 + int(b.shape[0])))
                 r0 += int(b.shape[0])
             more = {"proposals": proposals} if proposed else {}
+            if biased:
+                more.update(logit_biases=biases, allowed=allowed)
             preds = g.generate_many(pending, row_keys=keys, in_flight=self.in_flight, prefixes=prefixes if prompted else None, **more)
             self.rows = r0
         else:                                                           # source pools over all sources of the window
@@ -152,6 +164,7 @@ class _PredictAhead:
         for k, (src, pred) in enumerate(zip(pending, preds)):
             self.ready[self.next_idx + k] = (src, pred, shares[k])
             self.prefixes[self.next_idx + k] = prefixes[k]
+            self.biases[self.next_idx + k] = (biases[k], allowed[k])
         self.next_idx += len(pending)
 
     def _take_back(self, entries) -> None:
@@ -167,20 +180,24 @@ class _PredictAhead:
             return a is None and b is None
         return a.shape == b.shape and torch.equal(a.cpu(), b.cpu())
 
-    def take(self, src: torch.Tensor, batch_idx: int, prefix=None):
-        """The prediction prepared for batch `batch_idx` (and its forced prefixes `prefix`), or None (decode it now)."""
+    def take(self, src: torch.Tensor, batch_idx: int, prefix=None, logit_bias=None, allowed=None):
+        """The prediction prepared for batch `batch_idx` (and its forced prefixes `prefix`, its `logit_bias` and `allowed`
+        list), or None (decode it now)."""
         if not self.enabled:
             return None
         if batch_idx not in self.ready and batch_idx == self.next_idx:
             self._decode_window(src.device)
         hit = self.ready.pop(batch_idx, None)
         had = self.prefixes.pop(batch_idx, None)
+        had_bias = self.biases.pop(batch_idx, (None, None))
         if hit is None or hit[0].shape != src.shape or not torch.equal(hit[0], src.to(hit[0].device)) \
-                or not self._same_prefix(had, prefix):
+                or not self._same_prefix(had, prefix) or not self._same_prefix(had_bias[0], logit_bias) \
+                or not self._same_prefix(had_bias[1], allowed):
             self.enabled = False                       # not the batch that was decoded for this index: stop looking ahead
             self._take_back(([hit] if hit is not None else []) + list(self.ready.values()))
             self.ready.clear()
             self.prefixes.clear()
+            self.biases.clear()
             self.fallbacks += 1
             return None
         if hit[1] is None:                             # the reference raises on this batch: let generate() raise it here
@@ -339,20 +356,25 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         if proposal is not None and self.hparams.generation != "sampling_speculative":
             raise ValueError(f'"proposal_tokens" in a batch: only generation="sampling_speculative" takes proposals, '
                              f'not "{self.hparams.generation}"')
+        # per-source logit bias Float[B, V] and / or allow-list Bool[B, V]: which tokens a source may produce
+        bias = {k: batch[name] for k, name in (("logit_bias", "logit_bias"), ("allowed", "allowed_tokens")) if name in batch}
+        if bias and not sampling and self.hparams.generation != "stochastic_beam_search":
+            raise ValueError(f'"logit_bias" / "allowed_tokens" in a batch: only generation="sampling", "sampling_speculative" and '
+                             f'"stochastic_beam_search" take a logit bias, not "{self.hparams.generation}"')
         if ahead is not None and dataloader_idx == 0:
-            pred = ahead.take(batch["src_tokens"], batch_idx, prefix)
+            pred = ahead.take(batch["src_tokens"], batch_idx, prefix, bias.get("logit_bias"), bias.get("allowed"))
         if pred is not None and self.hparams.generation in ("sampling", "sampling_speculative", "stochastic_beam_search"):
             self._predict_rows += int(batch["src_tokens"].shape[0])        # served ahead under these keys: a fallback goes on from here
         elif pred is None and self.hparams.generation in ("sampling", "sampling_speculative"):
             B = int(batch["src_tokens"].shape[0])
-            more = {} if proposal is None else {"proposal": proposal}
+            more = dict(bias) if proposal is None else dict(bias, proposal=proposal)
             pred = self.generator.generate(batch["src_tokens"], row_keys=torch.arange(self._predict_rows, self._predict_rows + B),
                                            prefix=prefix, **more)
             self._predict_rows += B
         elif pred is None and self.hparams.generation == "stochastic_beam_search":   # keyed like the samplers: the running index
             B = int(batch["src_tokens"].shape[0])
             pred = self.generator.generate(batch["src_tokens"], row_keys=torch.arange(self._predict_rows, self._predict_rows + B),
-                                           prefix=prefix)
+                                           prefix=prefix, **bias)
             self._predict_rows += B
         elif pred is None:
             pred = self.generator.generate(batch["src_tokens"])
@@ -364,17 +386,18 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         if self._attention_on:
             self._align_batch(batch["src_tokens"], pred, batch_idx)
         if self._logq_on:
-            self._logq_batch(batch["src_tokens"], pred, batch_idx, prefix, with_scores=both)
+            self._logq_batch(batch["src_tokens"], pred, batch_idx, prefix, with_scores=both, bias=bias)
         return pred
 
-    def _logq_batch(self, src: torch.Tensor, pred: torch.Tensor, batch_idx: int, prefix, with_scores: bool = False) -> None:
+    def _logq_batch(self, src: torch.Tensor, pred: torch.Tensor, batch_idx: int, prefix, with_scores: bool = False,
+                    bias: dict | None = None) -> None:
         """The batch's ProposalScores under the generator's own distribution, whether it was decoded ahead or on the spot; the
         token tensor predict_step returns stays what it was.  ``with_scores``: the batch's HypothesisScores come from the same
         decoder pass (its time then counts as scoring_seconds too, as _alternatives_batch counts its own).  Timed like
         _score_batch."""
         torch.cuda.synchronize()
         t0 = timer()
-        q = self.generator.logq(src, pred, prefix=prefix, with_scores=with_scores)
+        q = self.generator.logq(src, pred, prefix=prefix, with_scores=with_scores, **(bias or {}))
         torch.cuda.synchronize()
         dt = timer() - t0
         self._logq_seconds += dt

@@ -216,16 +216,19 @@ class NativeTransformer:
 
     def kernel_profile(self) -> dict:
         """GEMM event-pair sums of every session of this model since the last read (ttx_last_kernel_profile; sessions created
-        under TTX_PROFILE_GEMM=1): {"gemm_ms", "launches", "pair_overhead_ms"}."""
+        under TTX_PROFILE_GEMM=1): {"gemm_ms", "launches", "pair_overhead_ms"}, and "logit_bias_launches": the k_logit_bias
+        launches the sessions have enqueued since they were created (not reset by a read; 0 unless a biased call ran)."""
         ms, n, e = C.c_double(), C.c_int64(), C.c_double()
-        tot_ms, tot_n, over = 0.0, 0, []
+        tot_ms, tot_n, over, lb = 0.0, 0, [], 0
         for sess in (getattr(self, "_pool", None) or [self._session]):
+            lb += int(self._lib.ttx_debug_logit_bias_launches(sess))
             N.check(self._lib.ttx_last_kernel_profile(sess, C.byref(ms), C.byref(n), C.byref(e)))
             tot_ms += ms.value
             tot_n += n.value
             if n.value and e.value > 0:
                 over.append(e.value)
-        return {"gemm_ms": tot_ms, "launches": tot_n, "pair_overhead_ms": float(np.median(over)) if over else 0.0}
+        return {"gemm_ms": tot_ms, "launches": tot_n, "pair_overhead_ms": float(np.median(over)) if over else 0.0,
+                "logit_bias_launches": lb}
 
     # -- kernel-level test entry points --------------------------------------------------------
     @staticmethod
@@ -317,6 +320,19 @@ class NativeTransformer:
         int32 device scalar or None."""
         N.check(self._lib.ttx_debug_argmax(self._session, logits.data_ptr(), int(logits.shape[1]), pred.data_ptr(),
                                            self._ptr(m_live), int(m_max), self._stream()))
+
+    def debug_logit_bias(self, logits: torch.Tensor, bias: torch.Tensor, src: torch.Tensor | None = None, m_live: torch.Tensor | None = None,
+                         rows_per_src: int = 1, act_idx: torch.Tensor | None = None, row_map: torch.Tensor | None = None, n: int = 1,
+                         d: int = 0) -> None:
+        """ONE launch of k_logit_bias, in place on ``logits`` (a float32 device tensor [M, V] whose rows are contiguous; a view
+        with a 4-byte aligned base is fine) with ``bias`` float32 [sources, ld >= V] (row stride ``bias.stride(0)``).  Plain mapping
+        (``act_idx`` None): ``src`` int32 [M] or ``rows_per_src``; step layout: ``act_idx``, ``src`` by decoder row, ``row_map`` or
+        None, ``n`` drafts of ``d`` tokens.  ``m_live``: int32 [1] on the device, the live rows."""
+        M, V = logits.shape
+        assert logits.stride(1) == 1 and logits.stride(0) == V and bias.stride(1) == 1
+        N.check(self._lib.ttx_debug_logit_bias(self.session, logits.data_ptr(), V, M, self._ptr(m_live), bias.data_ptr(),
+                                               int(bias.stride(0)), self._ptr(src), rows_per_src, self._ptr(act_idx), self._ptr(row_map),
+                                               n, d, self._stream()))
 
     def debug_sample(self, logits: torch.Tensor, key: torch.Tensor, sample: torch.Tensor, done: torch.Tensor, front: torch.Tensor,
                      pred: torch.Tensor, m_max: int, m_live: torch.Tensor | None = None, *, temperature: float = 1.0, top_k: int = 0,
@@ -1068,11 +1084,13 @@ class NativeTransformer:
         return f.to(self.device, torch.int32).contiguous()
 
     def hypothesis_logq(self, logits: torch.Tensor, hyp: torch.Tensor, pad: int, eos: int, temperature: float = 1.0, top_k: int = 0,
-                        top_p: float = 1.0, forced_len=None, check_ids: bool = True) -> ProposalScores:
+                        top_p: float = 1.0, forced_len=None, check_ids: bool = True, logit_bias=None) -> ProposalScores:
         """The stage alone (ttx_hypothesis_logq): ``logits`` fp32 [..., W-1, V] as ``decode_tgt(hyp[..., :-1])`` gives them,
         ``hyp`` Long[..., W] with the same leading shape, ``forced_len`` integers of that leading shape.  A ``logits`` tensor
         that is already a contiguous fp32 device tensor is read in place.  Every output is returned.  Nothing is synchronised
-        (``check_ids=False`` skips the IndexError check of the token ids, which reads their range back)."""
+        (``check_ids=False`` skips the IndexError check of the token ids, which reads their range back).
+        ``logit_bias``: Float[S, V] with ``S`` the first leading dimension (the sources; ``scoring.check_logit_bias``'s form): the
+        stage runs on a biased copy of the logits (ttx_hypothesis_logq_bias), ``logits`` itself is not written."""
         x = logits.to(self.device, torch.float32)
         if not x.is_contiguous():
             x = x.contiguous()
@@ -1092,6 +1110,16 @@ class NativeTransformer:
                              torch.empty(lead + (W - 1,), dtype=torch.float32, device=dev),
                              torch.empty(lead + (W - 1,), dtype=torch.int32, device=dev),
                              torch.empty(lead + (W - 1,), dtype=torch.int32, device=dev), None)
+        if logit_bias is not None:
+            from .scoring import check_logit_bias
+            bias = check_logit_bias(logit_bias, int(lead[0]), V).to(dev).contiguous()
+            R = hyp.numel() // W
+            N.check(self._lib.ttx_hypothesis_logq_bias(self._scoring_session(), x.data_ptr(), hyp.data_ptr(), R, W, V, int(pad),
+                                                       int(eos), C.byref(dist), self._ptr(forced), bias.data_ptr(), V,
+                                                       R // max(int(lead[0]), 1), out.token_logq.data_ptr(), out.logq.data_ptr(),
+                                                       out.first_outside.data_ptr(), out.rank.data_ptr(), out.n_kept.data_ptr(),
+                                                       out.length.data_ptr(), out.finished.data_ptr(), self._stream()))
+            return out
         N.check(self._lib.ttx_hypothesis_logq(self._scoring_session(), x.data_ptr(), hyp.data_ptr(), hyp.numel() // W, W, V, int(pad),
                                               int(eos), C.byref(dist), self._ptr(forced), out.token_logq.data_ptr(),
                                               out.logq.data_ptr(), out.first_outside.data_ptr(), out.rank.data_ptr(),
@@ -1100,7 +1128,7 @@ class NativeTransformer:
 
     def proposal_scores(self, src: torch.Tensor, hyp: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                         forced_len=None, with_scores: bool = False, return_token_logq: bool = False, return_rank: bool = False,
-                        trim: bool = True, max_rows: int | None = None, eos_token_idx: int = 2) -> ProposalScores:
+                        trim: bool = True, max_rows: int | None = None, eos_token_idx: int = 2, logit_bias=None) -> ProposalScores:
         """Log-probability of every hypothesis ``hyp[b, k]`` (Long[B, N, W]) of source ``src[b]`` under the distribution a sampler
         with (``temperature``, ``top_k``, ``top_p``) draws from: the teacher-forced pass of ``score_hypotheses`` and the stage
         that evaluates the sampler's own rule at every emitted token (ttx_score_proposal; include/ttx.h defines the quantity).
@@ -1113,7 +1141,13 @@ class NativeTransformer:
         cost nothing and are inside the support.  ``with_scores=True`` fills ``scores`` with ``score_hypotheses``' result (with
         ``token_logp``) from the same decoder pass.  With temperature 1, no filter and no ``forced_len``, ``logq`` is
         ``score_hypotheses``' ``score`` bit for bit.  ``trim`` and ``max_rows`` behave as in ``score_hypotheses``; results keep the
-        full ``W-1``, columns cut by ``trim`` hold the not-live values."""
+        full ``W-1``, columns cut by ``trim`` hold the not-live values.
+
+        ``logit_bias``: Float[B, V], the per-source bias the rows were (or would be) sampled under (``scoring.check_logit_bias``'s
+        form; ``-inf`` forbids a token).  The log q stage then reads the biased logits (k_logit_bias on the teacher-forced logits,
+        ttx_score_proposal_bias), so ``logq`` is the log-probability under the biased sampler's distribution, ``first_outside`` names
+        the first forbidden token and ``logq = -inf`` means "cannot be emitted".  ``scores`` (``with_scores=True``) stay the RAW
+        model's log p, from the logits before the bias, in the same pass: ``scoring.importance_weights`` stays ``p / q``."""
         src, hyp = self._tokens(src), self._tokens(hyp)
         if src.dim() != 2 or hyp.dim() != 3 or hyp.shape[0] != src.shape[0] or hyp.shape[1] < 1 or hyp.shape[2] < 2:
             raise ValueError(f"proposal_scores needs hyp [B, N >= 1, W >= 2] for src [B, Ls]; got {tuple(hyp.shape)} for "
@@ -1125,6 +1159,10 @@ class NativeTransformer:
         self.check_tokens(src)
         self.check_tokens(hyp, V)
         eos, dev = int(eos_token_idx), self.device
+        bias = None
+        if logit_bias is not None:
+            from .scoring import check_logit_bias
+            bias = check_logit_bias(logit_bias, B, V).to(dev).contiguous()
         Wt, chunk = self._trim_and_chunk(hyp, eos, trim, max_rows)
         T, Tt = W - 1, Wt - 1
         cut = Wt != W
@@ -1148,12 +1186,15 @@ class NativeTransformer:
             b1 = min(B, b0 + chunk)
             nb = b1 - b0
             part = [None if t is None else (t[b0:b1] if not cut else torch.empty((nb, K, Tt), dtype=t.dtype, device=dev)) for t in full]
-            N.check(self._lib.ttx_score_proposal(sess, src[b0:b1].data_ptr(), nb, Ls, hyp[b0:b1].data_ptr(), W, K, Wt, eos,
-                                                 C.byref(dist), None if forced is None else forced[b0:b1].data_ptr(), None,
-                                                 self._ptr(part[3]), sc.score[b0:b1].data_ptr() if sc else None,
-                                                 self._ptr(part[0]), out.logq[b0:b1].data_ptr(), out.first_outside[b0:b1].data_ptr(),
-                                                 self._ptr(part[1]), self._ptr(part[2]), out.length[b0:b1].data_ptr(),
-                                                 out.finished[b0:b1].data_ptr(), stream))
+            tail = (None, self._ptr(part[3]), sc.score[b0:b1].data_ptr() if sc else None,
+                    self._ptr(part[0]), out.logq[b0:b1].data_ptr(), out.first_outside[b0:b1].data_ptr(),
+                    self._ptr(part[1]), self._ptr(part[2]), out.length[b0:b1].data_ptr(), out.finished[b0:b1].data_ptr(), stream)
+            head = (sess, src[b0:b1].data_ptr(), nb, Ls, hyp[b0:b1].data_ptr(), W, K, Wt, eos, C.byref(dist),
+                    None if forced is None else forced[b0:b1].data_ptr())
+            if bias is None:
+                N.check(self._lib.ttx_score_proposal(*head, *tail))
+            else:
+                N.check(self._lib.ttx_score_proposal_bias(*head, bias[b0:b1].data_ptr(), V, *tail))
             if cut:
                 for t, c in zip(full, part):
                     if t is not None:

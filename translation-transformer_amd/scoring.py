@@ -265,6 +265,75 @@ def importance_weights(scores, logq, normalize: bool = True):
     return w
 
 
+def check_logit_bias(logit_bias, B: int, vocab_size: int):
+    """The per-source logit bias of a sampling call as the library takes it: a floating-point tensor [B, V], ``V`` the model's
+    vocabulary, one row per source, every value finite or ``-inf`` (``-inf`` forbids the token).  Returns it as float32, on the
+    device it came on; ``None`` for ``None``.  ValueError, naming the first offending source: a shape that is not [B, V], a
+    dtype that is not floating point, a ``NaN`` or a ``+inf``.  Pure: CPU tensors are checked as they are (a device tensor's
+    verdict is read back)."""
+    import torch
+    if logit_bias is None:
+        return None
+    b = torch.as_tensor(logit_bias)
+    if not b.dtype.is_floating_point:
+        raise ValueError(f"logit_bias must be a floating-point tensor [B, V], got {b.dtype}")
+    if b.dim() != 2 or tuple(b.shape) != (B, vocab_size):
+        raise ValueError(f"logit_bias must have shape [{B}, {vocab_size}] (one row per source, one value per token of the model's "
+                         f"vocabulary), got {tuple(b.shape)}")
+    b = b.detach().to(torch.float32)
+    bad = (torch.isnan(b) | (b == float("inf"))).any(dim=1)
+    if bool(bad.any()):
+        i = int(torch.nonzero(bad)[0])
+        v = int(torch.nonzero(torch.isnan(b[i]) | (b[i] == float("inf")))[0])
+        raise ValueError(f"logit_bias of source {i} holds {float(b[i, v])!r} at token {v}: values must be finite or -inf")
+    return b
+
+
+def bias_from_allowed(allowed):
+    """The logit bias of an allow-list: ``allowed`` Bool[B, V] -> Float32[B, V], ``0`` where a token is allowed and ``-inf`` where
+    it is not, on the device of ``allowed``.  ValueError for anything but a two-dimensional bool tensor."""
+    import torch
+    a = torch.as_tensor(allowed)
+    if a.dtype != torch.bool or a.dim() != 2:
+        raise ValueError(f"allowed must be a bool tensor [B, V], got {tuple(a.shape)} {a.dtype}")
+    out = torch.zeros(a.shape, dtype=torch.float32, device=a.device)
+    return out.masked_fill_(~a, float("-inf"))
+
+
+def combine_bias(logit_bias, allowed, B: int, vocab_size: int):
+    """``logit_bias`` and / or ``allowed`` of a call as ONE checked bias (``check_logit_bias``), or ``None`` for neither: the
+    allow-list is added as ``-inf`` onto the bias."""
+    import torch
+    if allowed is None:
+        return check_logit_bias(logit_bias, B, vocab_size)
+    mask = check_logit_bias(bias_from_allowed(allowed), B, vocab_size)
+    if logit_bias is None:
+        return mask
+    b = check_logit_bias(logit_bias, B, vocab_size)
+    return torch.where(torch.isinf(mask).to(b.device), mask.to(b.device), b)
+
+
+def allowlist_from_source(src, always, vocab_size: int, pad: int):
+    """The "product tokens come from the reactants" constraint: Bool[B, V], true for every token id that occurs in the source row
+    ``src[b]`` (Long[B, Ls], right-padded with ``pad``, which itself is not allowed on that ground) and for every id in ``always``
+    (the structure tokens, EOS).  One scatter on the device of ``src``.  Source ids outside [0, V) are ignored."""
+    import torch
+    src = torch.as_tensor(src)
+    if src.dim() != 2 or src.dtype.is_floating_point or src.dtype == torch.bool:
+        raise ValueError(f"src must be an integer tensor [B, Ls], got {tuple(src.shape)} {src.dtype}")
+    src = src.to(torch.int64)
+    ok = (src != pad) & (src >= 0) & (src < vocab_size)
+    out = torch.zeros((src.shape[0], vocab_size + 1), dtype=torch.bool, device=src.device)
+    out.scatter_(1, torch.where(ok, src, torch.full_like(src, vocab_size)), True)          # the spare column takes what is ignored
+    out = out[:, :vocab_size].contiguous()
+    ids = torch.as_tensor(list(always) if not hasattr(always, "shape") else always, dtype=torch.int64).reshape(-1)
+    if ids.numel():
+        if int(ids.min()) < 0 or int(ids.max()) >= vocab_size:
+            raise ValueError(f"always holds an id outside the vocabulary [0, {vocab_size})")
+        out[:, ids.to(src.device)] = True
+    return out
+
+
 def write_logq(filename: str, logq, append: bool = True) -> None:
     """The log q side file of the prediction CSV: one line per source, ``logq_1,length_1,finished_1,first_outside_1,...`` in the
     order of the CSV's ``prediction_1..N`` columns (log q with 9 significant digits: fp32 round-trips; ``-inf`` for a row outside
