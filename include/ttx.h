@@ -549,6 +549,91 @@ int ttx_debug_logit_bias(ttx_session* s, float* d_logits, int V, int M, const in
  * graph adds none; ttx_debug_logit_bias is not counted).  A session that only ever served unbiased calls reports 0. */
 int ttx_debug_logit_bias_launches(ttx_session* s);
 
+/* Syntax-constrained sampling: balanced branches and ring closures.  The sampling calls can be held to rows that can still end
+ * balanced: every OPEN token closed, every ring label used an even number of times, EOS inside max_len.  d_cls is DEVICE, int8 [V],
+ * the SYNTAX TABLE, one class per vocabulary id:
+ *     -1      FORBID   never emitted under the constraint (PAD, BOS, "?")
+ *      0      neutral  (and every value not listed here)
+ *      1      OPEN     "("
+ *      2      CLOSE    ")"
+ *      3 + l  ring label l, 0 <= l < 64   ("1", "2", "%10")
+ * EOS is the call's eos token whatever its class.  A NULL struct or a NULL d_cls is the call without the constraint, launch for
+ * launch: no new kernel, no new buffer, the same graph keys.
+ *
+ * The rule.  For a row prefix P (the tokens after BOS, as stored; an id outside [0, V) and a FORBID token count as neutral)
+ *     depth(P) = #OPEN - #CLOSE,   R(P) = the 64-bit XOR of 1 << l over its ring tokens,   need = max(depth, 0) + popcount(R),
+ * and for the position pos being predicted (column of the output row, BOS at 0) left = (max_len - 1) - pos columns follow it.
+ * Token v keeps its logit bit for bit if it is allowed; otherwise the logit becomes -inf:
+ *     EOS                                    depth == 0 and R == 0
+ *     FORBID                                 never
+ *     neutral                                need + 1 <= left
+ *     OPEN                                   need + 2 <= left
+ *     CLOSE                                  depth > 0
+ *     ring l, bit l set in R   (closes)      always
+ *     ring l, bit l clear in R (opens)       need + 2 <= left
+ * Consequences.  The allowed set is never empty (need == 0 allows EOS; need > 0 allows a closer).  From a prefix with need <= left
+ * every row ends in EOS at or before the last column with depth == 0, R == 0 and no FORBID token: every allowed token keeps
+ * need <= left at the next position (a neutral costs one column of a budget that had one to spare, an opener two of two, a closer
+ * pays for itself), and at need == left only closers and, at need == 0, EOS remain, so need falls to 0 no later than left does.  An
+ * unprompted call starts there (need 0) whenever max_len >= 2.
+ * This is a NECESSARY condition for a parseable SMILES string, not validity: valence, aromaticity, "()", "C11" and ring bonds across
+ * "." are outside it.
+ * A forced prefix position ignores the mask, as it ignores the bias, yet its tokens count in the state.  A prefix that already has
+ * need > left is accepted: the rule then allows closers only and the row may end unfinished.  A logit bias is applied first, the mask
+ * second; -inf stays -inf, so the allowed set is the intersection (which, unlike the mask's own, may be empty: outside the contract as
+ * an all -inf row is).  Drafts need no rule: a draft token is accepted iff it equals the keyed draw, and the draw of a draft position
+ * comes from the row masked for the prefix that includes the earlier draft tokens.  Temperature 0 is greedy decoding over the allowed
+ * set.  Seeding contract, one item longer: a row depends on its source, key, sample id, prefix, bias row, the table and max_len alone.
+ * Mechanism.  ONE launch of k_syntax_mask (csrc/ttx_syntax.hip.h) per decoder pass, in place on the pass's logits, after k_logit_bias
+ * and before the consumer.  The kernel never reads the logits; the state is a pure function of the row, recomputed from the committed
+ * tokens and the drafts, so accept, retire, admission, probe, draft select and graph replay carry nothing for it.  The table is copied
+ * into a session buffer at call start; a constrained step has graph keys of its own.
+ * max_len: 0 or the call's max_len for the generate calls (anything else: TTX_ERR_INVALID, nothing launched); for the scoring calls
+ * the max_len the rows were generated under (0: W; else at least 2). */
+typedef struct ttx_syntax {
+  const int8_t* d_cls;
+  int32_t max_len;
+} ttx_syntax;
+/* The *_ex calls plus the constraint. */
+int ttx_sample_generate_syntax(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sample_params* p,
+                               const ttx_sample_opts* opts, const ttx_syntax* syntax, int64_t* d_out, ttx_gen_stats* stats, void* stream);
+int ttx_sample_speculative_generate_syntax(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                           const ttx_sample_spec_params* p, const ttx_sample_opts* opts, const ttx_syntax* syntax,
+                                           int64_t* d_out, ttx_gen_stats* stats, void* stream);
+int ttx_sample_speculative_generate_pool_syntax(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total, int Ls_all,
+                                                const int32_t* h_len, const int64_t* d_row_keys, int capacity,
+                                                const ttx_sample_spec_params* p, const ttx_sample_opts* opts, const ttx_syntax* syntax,
+                                                int64_t* d_out, ttx_gen_stats* stats, void* stream);
+/* log q under the constraint: ttx_hypothesis_logq_bias / ttx_score_proposal_bias with k_syntax_mask applied to the teacher-forced
+ * logits after the bias and before the log q stage (logits row r * (W - 1) + t takes the prefix hyp[r][1 .. t]): first_outside names the
+ * first token the constrained sampler could not have emitted.  A hypothesis with an unmatched CLOSE is outside the support at that
+ * token; its depth is negative from there on, a state no constrained row reaches, in which the rule can leave a later position
+ * (left <= 0) no token at all: d_tok_logq is NaN there and d_logq of such a row is not a number to rely on beyond "not finite"
+ * (d_first_outside names the CLOSE; the Python layer reports -inf for every row that has a first_outside).  As with the bias, ttx_score_proposal_syntax scores p on the RAW logits
+ * first and a caller's d_logits then receives the masked logits; ttx_hypothesis_logq_syntax masks a copy.  d_bias may be NULL. */
+int ttx_hypothesis_logq_syntax(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad, int eos,
+                               const ttx_dist* dist, const int32_t* d_forced_len, const float* d_bias, int ld_bias, int N,
+                               const ttx_syntax* syntax, float* d_tok_logq, float* d_logq, int32_t* d_first_outside, int32_t* d_rank,
+                               int32_t* d_n_kept, int32_t* d_length, uint8_t* d_finished, void* stream);
+int ttx_score_proposal_syntax(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N, int W, int eos,
+                              const ttx_dist* dist, const int32_t* d_forced_len, const float* d_bias, int ld_bias, const ttx_syntax* syntax,
+                              float* d_logits, float* d_tok_logp, float* d_score, float* d_tok_logq, float* d_logq,
+                              int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept, int32_t* d_length, uint8_t* d_finished,
+                              void* stream);
+/* ONE launch of k_syntax_mask on DEVICE arrays of the caller (tests/test_gpu_syntax_kernel.py), in place on d_logits fp32 [M][V]; rows
+ * at or beyond *d_m (int32 on the device, NULL: M) keep their bits.  mode 0, k_sample's rows: d_tok int32 [M][ld_tok], the prefix of
+ * row r is d_tok[r][1 .. d_front[0]], pos = d_front[0] + 1.  mode 1, k_sample_step's layout: d_tok int32 [B][ld_tok], d_front [B],
+ * lrow = d_row_map ? d_row_map[row] : row, b = d_act_idx[lrow / (1 + N * D)], rs = lrow % (1 + N * D); rs == 0: the prefix
+ * d_tok[b][1 .. f], pos = f + 1; rs = 1 + n * D + j: tokens 0 .. j of draft n of d_drafts int32 [B][N][D] appended, pos = f + 2 + j.
+ * mode 2, teacher-forced: d_tok int64 [M / T][ld_tok], row r * T + t takes d_tok[r][1 .. t], pos = t + 1.  Every index is the
+ * caller's to keep in range. */
+int ttx_debug_syntax_mask(ttx_session* s, int mode, float* d_logits, int V, int M, const int32_t* d_m, const int8_t* d_cls, int max_len,
+                          int eos, const void* d_tok, int ld_tok, const int32_t* d_front, const int32_t* d_act_idx,
+                          const int32_t* d_row_map, const int32_t* d_drafts, int N, int D, int T, void* stream);
+/* The number of k_syntax_mask launches the session has enqueued since it was created, eagerly or into a captured step (a replayed
+ * graph adds none; ttx_debug_syntax_mask is not counted).  A session that only ever served unconstrained calls reports 0. */
+int ttx_debug_syntax_launches(ttx_session* s);
+
 /* Beam-speculative bookkeeping kernels.
  * ttx_nucleus_mask: mask_with_num_logits_according_nucleus (src/decoding/speculative_decoding.py:871-904): per row of
  *   d_logits [rows,V] keep the best logit and further ones, best first, while the softmax mass ranked above is

@@ -10,4 +10,5 @@ from .decoding import (TranslationInferenceGreedySpeculative, TranslationInferen
 from .lightning_model import VanillaEncoderDecoderTransformerLightning, run_predict, run_evaluate  # noqa: F401,E402
 from . import dist  # noqa: F401,E402
 from .tokenizer import NativeSmilesTokenizer  # noqa: F401,E402
-from . import scheduling, scoring  # noqa: F401,E402
+from . import scheduling, scoring, syntax  # noqa: F401,E402
+from .syntax import SmilesSyntax, SyntaxCheck  # noqa: F401,E402

@@ -18,7 +18,7 @@ LIB_PATH = PKG_DIR / "libttx_hip.so"
 UNITS = [CSRC / "ttx_api.hip", CSRC / "ttx_gemm.hip", CSRC / "ttx_attn.hip"]
 HEADERS = [CSRC / "ttx_internal.h", CSRC / "ttx_common.hip.h", CSRC / "ttx_loop_kernels.hip.h", CSRC / "ttx_metrics.hip.h",
            CSRC / "ttx_score.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_sample.hip.h", CSRC / "ttx_logq.hip.h", CSRC / "ttx_sbs.hip.h", CSRC / "ttx_sbs_pool.hip.h",
-           CSRC / "ttx_proposal.hip.h", CSRC / "ttx_logit_bias.hip.h",
+           CSRC / "ttx_proposal.hip.h", CSRC / "ttx_logit_bias.hip.h", CSRC / "ttx_syntax.hip.h",
            CSRC / "ttx_select.h", CSRC / "ttx_tokenizer.h", CSRC / "ttx_drive.h", CSRC / "ttx_admit.h", INCLUDE / "ttx.h"]
 SOURCES = UNITS + HEADERS
 OBJ_DIR = CSRC / "build"
@@ -177,6 +177,11 @@ class SampleOpts(C.Structure):
                    None if bias is None else bias.data_ptr(), 0 if bias is None else int(bias.stride(0)))
 
 
+class Syntax(C.Structure):
+    """ttx_syntax: the class table (int8 [V] on the device) and the maximal length of the rule."""
+    _fields_ = [("d_cls", C.c_void_p), ("max_len", C.c_int32)]
+
+
 class DebugPrefix(C.Structure):
     """ttx_debug_prefix: the forced prefixes of a debug launch (table, row length, sources; per-row length and table row)."""
     _fields_ = [("d_tok", C.c_void_p), ("ld", C.c_int32), ("n_sources", C.c_int32), ("d_len", C.c_void_p), ("d_src", C.c_void_p)]
@@ -315,6 +320,19 @@ SYMBOLS = {
     "ttx_sbs_generate_bias": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SbsParams), C.POINTER(SbsFilter), _VP, _I, _VP, _VP, _I, _VP, _VP,
                                        _VP, C.POINTER(SbsTrace), C.POINTER(BeamSearchStats), _VP]),
     "ttx_debug_logit_bias_launches": (C.c_int, [_VP]),
+    "ttx_sample_generate_syntax": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SampleParams), C.POINTER(SampleOpts), C.POINTER(Syntax), _VP,
+                                            C.POINTER(GenStats), _VP]),
+    "ttx_sample_speculative_generate_syntax": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SampleSpecParams), C.POINTER(SampleOpts),
+                                                        C.POINTER(Syntax), _VP, C.POINTER(GenStats), _VP]),
+    "ttx_sample_speculative_generate_pool_syntax": (C.c_int, [C.POINTER(_VP), _I, _VP, _I, _I, C.POINTER(C.c_int32), _VP, _I,
+                                                             C.POINTER(SampleSpecParams), C.POINTER(SampleOpts), C.POINTER(Syntax), _VP,
+                                                             C.POINTER(GenStats), _VP]),
+    "ttx_hypothesis_logq_syntax": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, _I, C.POINTER(Dist), _VP, _VP, _I, _I, C.POINTER(Syntax), _VP, _VP,
+                                            _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ttx_score_proposal_syntax": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, C.POINTER(Dist), _VP, _VP, _I, C.POINTER(Syntax), _VP, _VP,
+                                           _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ttx_debug_syntax_mask": (C.c_int, [_VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
+    "ttx_debug_syntax_launches": (C.c_int, [_VP]),
     "ttx_debug_logit_bias": (C.c_int, [_VP, _VP, _I, _I, _VP, _VP, _I, _VP, _I, _VP, _VP, _I, _I, _VP]),
     "ttx_greedy_speculative_generate_many": (C.c_int, [C.POINTER(_VP), _I, _I, C.POINTER(_VP), C.POINTER(C.c_int),
                                                       C.POINTER(C.c_int), C.POINTER(GenParams), C.POINTER(_VP),

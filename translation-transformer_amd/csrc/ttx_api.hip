@@ -12,6 +12,7 @@
 #include "ttx_attn_probs.hip.h"
 #include "ttx_sample.hip.h"
 #include "ttx_logit_bias.hip.h"
+#include "ttx_syntax.hip.h"
 #include "ttx_logq.hip.h"
 #include "ttx_sbs.hip.h"
 #include "ttx_sbs_pool.hip.h"
@@ -1061,7 +1062,37 @@ struct StepCtx {
   // per-source logit bias (val null: none, no launch): k_logit_bias between the classifier and the consumer of the logits.  `src` goes
   // by decoder row (slot of a pool; candidate of a beam loop); the values live in a session buffer, never in the caller's tensor
   LogitBiasTab bias{};
+  // syntax constraint (null: none, no launch): k_syntax_mask after the bias and before the consumer.  The class table lives in a session
+  // buffer; the rule's max_len and EOS are the step's (max_len, p.eos_token), the state comes from gen / drafts
+  const signed char* syntax = nullptr;
 };
+
+// k_syntax_mask with k_logit_bias's launch shape, in place on `a.logits`; `step`: the step-row layout.
+static int launch_syntax_mask(hipStream_t st, const SyntaxArgs& a, bool step) {
+  const dim3 grid(cdiv(a.M, 4)), block(256);
+  if (step) hipLaunchKernelGGL((k_syntax_mask<true>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((k_syntax_mask<false>), grid, block, 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+// The syntax argument of a call whose rows have `max_len` columns and whose vocabulary is the session's, or TTX_ERR_INVALID: a null
+// struct or a null table is the unconstrained call; max_len is 0 (the call's) or the call's.
+static int syntax_validate(const char* who, const ttx_syntax* syn, int max_len, const signed char** cls) {
+  *cls = nullptr;
+  if (!syn || !syn->d_cls) return TTX_OK;
+  if (syn->max_len != 0 && syn->max_len != max_len)
+    return fail(TTX_ERR_INVALID, std::string(who) + ": ttx_syntax.max_len must be 0 or the call's max_len");
+  *cls = reinterpret_cast<const signed char*>(syn->d_cls);
+  return TTX_OK;
+}
+
+// The class table of a constrained call into the session's copy, int8 [V]: a captured step reads the session's buffer and nothing of
+// the caller's.  Enqueued outside capture, before the first step.
+static int syntax_upload(ttx_session* s, hipStream_t st, const signed char* d_cls) {
+  HIP_TRY(hipMemcpyAsync(s->syn_cls.p, d_cls, (size_t)s->m->cfg.vocab_size, hipMemcpyDeviceToDevice, st));
+  return TTX_OK;
+}
 
 // k_logit_bias with k_sample's launch shape, in place on `a.logits`; `step`: the step-row layout (act_idx, row_map, N, D set).
 static int launch_logit_bias(hipStream_t st, const LogitBiasArgs& a, bool step) {
@@ -1201,6 +1232,14 @@ static int run_step(ttx_session* s, hipStream_t st, const StepCtx& k, int kcap) 
     if (!k.want_sample) { b.act_idx = act; b.row_map = k.row_map; b.N = k.N; b.D = k.D; }
     TTX_TRY(launch_logit_bias(st, b, !k.want_sample));
     s->logit_bias_launches += 1;
+  }
+  if (k.syntax) {                    // after the bias (-inf stays -inf), before the consumer; none in an unconstrained step
+    SyntaxArgs y{};
+    y.logits = logits; y.V = V; y.m_ptr = m_ptr; y.M = Mmax; y.cls = k.syntax; y.max_len = k.max_len; y.eos = k.p.eos_token;
+    y.gen = s->gen.as<int>(); y.gen_ld = k.gen_ld; y.front = s->front.as<int>();
+    if (!k.want_sample) { y.act_idx = act; y.row_map = k.row_map; y.drafts = s->drafts.as<int>(); y.N = k.N; y.D = k.D; }
+    TTX_TRY(launch_syntax_mask(st, y, !k.want_sample));
+    s->syntax_launches += 1;
   }
   if (k.want_sample) {
     SampleArgs a = k.sample;
@@ -1542,7 +1581,7 @@ static int gen_launch_step(GenJob& j, int width_bound) {
     const int site = k.want_sample_step ? (prop ? GS_STEP_SAMPLE_SPEC_PROPOSAL : pfx ? GS_STEP_SAMPLE_SPEC_PREFIX : GS_STEP_SAMPLE_SPEC)
                      : k.want_sample    ? (pfx ? GS_STEP_SAMPLE_PREFIX : GS_STEP_SAMPLE)
                      : j.greedy ? GS_STEP_GREEDY : (j.g.la.row_rule ? GS_STEP_ROW_RULE : GS_STEP_SPECULATIVE);
-    GraphKey key{site | (k.bias.val ? GS_LOGIT_BIAS : 0), k.B, k.Ls, k.N, k.D, k.max_len, kcap, k.variant, 0};
+    GraphKey key{site | (k.bias.val ? GS_LOGIT_BIAS : 0) | (k.syntax ? GS_SYNTAX : 0), k.B, k.Ls, k.N, k.D, k.max_len, kcap, k.variant, 0};
     if (prop) key.push_back(k.prop_ctx);
     TTX_TRY(graph_replay(s, j.st, s->step_graphs, key, enqueue));
   }
@@ -1677,6 +1716,8 @@ struct SampleSetup {
   bool tabled() const { return prompted || proposed; }
   // per-source logit bias (bias_validate): d_bias null is the unbiased call, launch for launch; [n_sources][ld_bias]
   const float* d_bias; int ld_bias;
+  // syntax constraint (syntax_validate): the caller's class table int8 [V] on the device, null for the unconstrained call
+  const signed char* d_syntax;
 };
 
 // The prefix arguments of a sampling call over S sources, or TTX_ERR_INVALID.  A call whose lengths are all zero (or absent) is
@@ -1738,6 +1779,7 @@ static int sample_ensure(ttx_session* s, hipStream_t st, size_t rows, const Samp
     if (smp.spec) TTX_TRY(ensure(s->pfx_draft0, rows * p->draft_len * 4, st));
   }
   if (smp.d_bias) TTX_TRY(ensure(s->lb_val, (size_t)smp.n_sources * s->m->cfg.vocab_size * sizeof(float), st));
+  if (smp.d_syntax) TTX_TRY(ensure(s->syn_cls, (size_t)s->m->cfg.vocab_size, st));
   TTX_TRY(ensure(s->smp_key, rows * 8, st));
   TTX_TRY(ensure(s->smp_sample, rows * 4, st));
   TTX_TRY(ensure(s->smp_done, rows * 4, st));
@@ -1778,6 +1820,10 @@ static int sample_begin(GenJob& j, const SampleSetup& smp) {
   if (smp.d_bias) {                                  // decoder row -> source: the map k_sample_init wrote
     TTX_TRY(bias_upload(s, j.st, smp.d_bias, smp.ld_bias, smp.n_sources));
     k.bias = LogitBiasTab{s->lb_val.as<float>(), s->m->cfg.vocab_size, s->smp_src_of.as<int>()};
+  }
+  if (smp.d_syntax) {
+    TTX_TRY(syntax_upload(s, j.st, smp.d_syntax));
+    k.syntax = s->syn_cls.as<signed char>();
   }
   return TTX_OK;
 }
@@ -1909,11 +1955,33 @@ static int bias_scored_logits(hipStream_t st, float* logits, int R, int T, int V
   return launch_logit_bias(st, a, false);
 }
 
+// k_syntax_mask on teacher-forced logits [R, T, V]: row r * T + t takes the prefix hyp[r][1 .. t] (k_hyp_logq's positions).
+static int syntax_scored_logits(ttx_session* s, hipStream_t st, float* logits, int R, int T, int V, const int64_t* d_hyp, int ld_hyp,
+                                const signed char* cls, int max_len, int eos) {
+  SyntaxArgs a{};
+  a.logits = logits; a.V = V; a.M = R * T; a.cls = cls; a.max_len = max_len; a.eos = eos; a.hyp = d_hyp; a.ld_hyp = ld_hyp; a.T = T;
+  TTX_TRY(launch_syntax_mask(st, a, false));
+  s->syntax_launches += 1;
+  return TTX_OK;
+}
+
+// The syntax argument of a scoring call over rows of W columns: max_len 0 is W; otherwise at least 2.
+static int syntax_validate_scored(const char* who, const ttx_syntax* syn, int W, const signed char** cls, int* max_len) {
+  *cls = nullptr; *max_len = W;
+  if (!syn || !syn->d_cls) return TTX_OK;
+  if (syn->max_len != 0 && syn->max_len < 2) return fail(TTX_ERR_INVALID, std::string(who) + ": ttx_syntax.max_len must be 0 or at least 2");
+  if (syn->max_len) *max_len = syn->max_len;
+  *cls = reinterpret_cast<const signed char*>(syn->d_cls);
+  return TTX_OK;
+}
+
 static int hypothesis_logq(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad, int eos,
                            const ttx_dist* dist, const int32_t* d_forced_len, float* d_tok_logq, float* d_logq,
                            int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept, int32_t* d_length,
-                           uint8_t* d_finished, void* stream, const float* d_bias, int ld_bias, int N) {
+                           uint8_t* d_finished, void* stream, const float* d_bias, int ld_bias, int N, const ttx_syntax* syn = nullptr) {
   if (!s) return session_required("ttx_hypothesis_logq");
+  const signed char* cls; int syn_len;
+  TTX_TRY(syntax_validate_scored("ttx_hypothesis_logq_syntax", syn, W, &cls, &syn_len));
   if (!d_logits || !d_hyp || !d_logq || !d_length) return fail(TTX_ERR_INVALID, "bad argument to ttx_hypothesis_logq");
   TTX_TRY(check_score_shapes(s, R, W, V, "ttx_hypothesis_logq"));
   if (d_bias && (ld_bias < V || N < 1 || R % N != 0))
@@ -1922,12 +1990,15 @@ static int hypothesis_logq(ttx_session* s, const float* d_logits, const int64_t*
   TTX_TRY(logq_block("ttx_hypothesis_logq", dist, &b));
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(s->m->device));
-  if (d_bias) {                           // the caller's logits stay as they are: the biased copy lives in session scratch
+  if (d_bias || cls) {                    // the caller's logits stay as they are: the biased / masked copy lives in session scratch
     const size_t bytes = (size_t)R * (W - 1) * V * sizeof(float);
     TTX_TRY(ensure(s->ev_logits, bytes, st));
     HIP_TRY(hipMemcpyAsync(s->ev_logits.p, d_logits, bytes, hipMemcpyDeviceToDevice, st));
-    TTX_TRY(bias_scored_logits(st, s->ev_logits.as<float>(), R, W - 1, V, N, d_bias, ld_bias));
-    s->logit_bias_launches += 1;
+    if (d_bias) {
+      TTX_TRY(bias_scored_logits(st, s->ev_logits.as<float>(), R, W - 1, V, N, d_bias, ld_bias));
+      s->logit_bias_launches += 1;
+    }
+    if (cls) TTX_TRY(syntax_scored_logits(s, st, s->ev_logits.as<float>(), R, W - 1, V, d_hyp, W, cls, syn_len, eos));
     d_logits = s->ev_logits.as<float>();
   }
   return launch_logq(s, st, d_logits, d_hyp, W, R, W, V, pad, eos, b, d_forced_len,
@@ -1950,11 +2021,23 @@ extern "C" int ttx_hypothesis_logq_bias(ttx_session* s, const float* d_logits, c
                          d_length, d_finished, stream, d_bias, ld_bias, N);
 }
 
+// ttx_hypothesis_logq_bias under a syntax constraint: k_syntax_mask on the (biased) copy of the logits before the log q stage.
+extern "C" int ttx_hypothesis_logq_syntax(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad, int eos,
+                                          const ttx_dist* dist, const int32_t* d_forced_len, const float* d_bias, int ld_bias, int N,
+                                          const ttx_syntax* syntax, float* d_tok_logq, float* d_logq, int32_t* d_first_outside,
+                                          int32_t* d_rank, int32_t* d_n_kept, int32_t* d_length, uint8_t* d_finished, void* stream) {
+  return hypothesis_logq(s, d_logits, d_hyp, R, W, V, pad, eos, dist, d_forced_len, d_tok_logq, d_logq, d_first_outside, d_rank, d_n_kept,
+                         d_length, d_finished, stream, d_bias, ld_bias, N, syntax);
+}
+
 static int score_proposal(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N, int W,
                           int eos, const ttx_dist* dist, const int32_t* d_forced_len, float* d_logits, float* d_tok_logp,
                           float* d_score, float* d_tok_logq, float* d_logq, int32_t* d_first_outside, int32_t* d_rank,
-                          int32_t* d_n_kept, int32_t* d_length, uint8_t* d_finished, void* stream, const float* d_bias, int ld_bias) {
+                          int32_t* d_n_kept, int32_t* d_length, uint8_t* d_finished, void* stream, const float* d_bias, int ld_bias,
+                          const ttx_syntax* syn = nullptr) {
   if (!s) return session_required("ttx_score_proposal");
+  const signed char* cls; int syn_len;
+  TTX_TRY(syntax_validate_scored("ttx_score_proposal_syntax", syn, W, &cls, &syn_len));
   if (d_bias && ld_bias < s->m->cfg.vocab_size) return fail(TTX_ERR_INVALID, "ttx_score_proposal_bias: ld_bias must be at least the vocabulary");
   if (!d_src || !d_hyp || !d_logq || !d_length || B <= 0 || N <= 0 || Ls <= 0)
     return fail(TTX_ERR_INVALID, "bad argument to ttx_score_proposal");
@@ -1973,12 +2056,15 @@ static int score_proposal(ttx_session* s, const int64_t* d_src, int B, int Ls, c
     d_logits = s->ev_logits.as<float>();
   }
   TTX_TRY(score_forward(s, st, d_src, B, Ls, d_hyp, ld_hyp, N, W, d_logits));
-  if (d_bias) {
-    // p before q, from one pass: k_hyp_score reads the raw logits, k_logit_bias then rewrites them in place (a caller's d_logits
-    // receives the biased values), and k_hyp_logq reads what the biased sampler's consumer reads
+  if (d_bias || cls) {
+    // p before q, from one pass: k_hyp_score reads the raw logits, k_logit_bias and k_syntax_mask then rewrite them in place (a
+    // caller's d_logits receives the biased, masked values), and k_hyp_logq reads what the constrained sampler's consumer reads
     if (d_score) TTX_TRY(launch_score(s, st, d_logits, d_hyp, ld_hyp, R, W, V, pad, eos, d_tok_logp, d_score, d_length, d_finished));
-    TTX_TRY(bias_scored_logits(st, d_logits, R, T, V, N, d_bias, ld_bias));
-    s->logit_bias_launches += 1;
+    if (d_bias) {
+      TTX_TRY(bias_scored_logits(st, d_logits, R, T, V, N, d_bias, ld_bias));
+      s->logit_bias_launches += 1;
+    }
+    if (cls) TTX_TRY(syntax_scored_logits(s, st, d_logits, R, T, V, d_hyp, ld_hyp, cls, syn_len, eos));
     return launch_logq(s, st, d_logits, d_hyp, ld_hyp, R, W, V, pad, eos, b, d_forced_len,
                        LogqOut{d_tok_logq, d_logq, d_first_outside, d_rank, d_n_kept, d_length, d_finished});
   }
@@ -2026,12 +2112,24 @@ extern "C" int ttx_score_proposal_bias(ttx_session* s, const int64_t* d_src, int
                         d_first_outside, d_rank, d_n_kept, d_length, d_finished, stream, d_bias, ld_bias);
 }
 
+// ttx_score_proposal_bias under a syntax constraint (a null `syntax` is that call).
+extern "C" int ttx_score_proposal_syntax(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N, int W,
+                                         int eos, const ttx_dist* dist, const int32_t* d_forced_len, const float* d_bias, int ld_bias,
+                                         const ttx_syntax* syntax, float* d_logits, float* d_tok_logp, float* d_score, float* d_tok_logq,
+                                         float* d_logq, int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept, int32_t* d_length,
+                                         uint8_t* d_finished, void* stream) {
+  return score_proposal(s, d_src, B, Ls, d_hyp, ld_hyp, N, W, eos, dist, d_forced_len, d_logits, d_tok_logp, d_score, d_tok_logq, d_logq,
+                        d_first_outside, d_rank, d_n_kept, d_length, d_finished, stream, d_bias, ld_bias, syntax);
+}
+
 // ttx_sample_generate and ttx_sample_generate_prefix: one body, the unprompted call with a null prefix.
 static int sample_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sample_params* p,
                            int64_t* d_out, ttx_gen_stats* stats, void* stream, const int64_t* d_prefix, int ld_prefix,
-                           const int32_t* h_prefix_len, const float* d_bias = nullptr, int ld_bias = 0) {
+                           const int32_t* h_prefix_len, const float* d_bias = nullptr, int ld_bias = 0, const ttx_syntax* syn = nullptr) {
   if (!s || !p) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
   TTX_TRY(bias_validate("ttx_sample_generate", s, d_bias, ld_bias));
+  const signed char* cls;
+  TTX_TRY(syntax_validate("ttx_sample_generate_syntax", syn, p->max_len, &cls));
   if (s->m->cfg.vocab_size > SAMPLE_MAX_V) return fail(TTX_ERR_INVALID, "ttx_sample_generate: vocabularies above 1024 are not supported");
   if (p->num_samples < 1) return fail(TTX_ERR_INVALID, "ttx_sample_generate: num_samples must be at least 1");
   SampleSetup smp{};
@@ -2040,7 +2138,7 @@ static int sample_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, 
     return fail(TTX_ERR_INVALID, "ttx_sample_generate: B * num_samples * (max_len + 2) must stay below 2^31");
   smp.n = p->num_samples; smp.d_row_keys = d_row_keys;
   TTX_TRY(prefix_validate("ttx_sample_generate", d_prefix, ld_prefix, h_prefix_len, std::max(B, 0), p->max_len, &smp));
-  smp.d_bias = d_bias; smp.ld_bias = ld_bias;
+  smp.d_bias = d_bias; smp.ld_bias = ld_bias; smp.d_syntax = cls;
   ttx_gen_params g{};
   g.max_len = p->max_len; g.draft_len = 0; g.n_drafts = 1; g.pad_token = p->pad_token; g.bos_token = p->bos_token;
   g.eos_token = p->eos_token; g.replace_token = p->pad_token; g.want_logits = 0;
@@ -2069,6 +2167,17 @@ extern "C" int ttx_sample_generate_ex(ttx_session* s, const int64_t* d_src, int 
   if (o->h_proposal_len) return fail(TTX_ERR_INVALID, "ttx_sample_generate_ex: the plain sampler verifies no drafts and takes no proposal");
   return sample_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, o->d_prefix, o->ld_prefix, o->h_prefix_len, o->d_bias,
                          o->ld_bias);
+}
+
+// ttx_sample_generate_ex under a syntax constraint (a null `syntax`, or a null table, is that call, launch for launch).
+extern "C" int ttx_sample_generate_syntax(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                          const ttx_sample_params* p, const ttx_sample_opts* o, const ttx_syntax* syntax, int64_t* d_out,
+                                          ttx_gen_stats* stats, void* stream) {
+  const ttx_sample_opts none{};
+  if (!o) o = &none;
+  if (o->h_proposal_len) return fail(TTX_ERR_INVALID, "ttx_sample_generate_syntax: the plain sampler verifies no drafts and takes no proposal");
+  return sample_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, o->d_prefix, o->ld_prefix, o->h_prefix_len, o->d_bias,
+                         o->ld_bias, syntax);
 }
 
 // What the speculative sampling calls refuse with TTX_ERR_INVALID whatever code gen_validate would give (nothing of these calls is
@@ -2100,10 +2209,12 @@ static int sample_speculative_generate(ttx_session* s, const int64_t* d_src, int
                                        const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream,
                                        const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
                                        const int64_t* d_proposal = nullptr, int ld_proposal = 0, const int32_t* h_proposal_len = nullptr,
-                                       const float* d_bias = nullptr, int ld_bias = 0) {
+                                       const float* d_bias = nullptr, int ld_bias = 0, const ttx_syntax* syn = nullptr) {
   const char* who = "ttx_sample_speculative_generate";
   if (!s || !p) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
   TTX_TRY(bias_validate(who, s, d_bias, ld_bias));
+  const signed char* cls;
+  TTX_TRY(syntax_validate(who, syn, p->sample.max_len, &cls));
   SampleSetup smp{};
   ttx_gen_params g{};
   const long long R = (long long)std::max(B, 0) * std::max(p->sample.num_samples, 0);
@@ -2112,7 +2223,7 @@ static int sample_speculative_generate(ttx_session* s, const int64_t* d_src, int
   smp.d_row_keys = d_row_keys;
   TTX_TRY(prefix_validate(who, d_prefix, ld_prefix, h_prefix_len, B, g.max_len, &smp));
   TTX_TRY(proposal_validate(who, d_proposal, ld_proposal, h_proposal_len, B, g.max_len, &smp));
-  smp.d_bias = d_bias; smp.ld_bias = ld_bias;
+  smp.d_bias = d_bias; smp.ld_bias = ld_bias; smp.d_syntax = cls;
   const int rc = generate_one(s, d_src, (int)R, Ls, &g, d_out, stats, stream, false, &smp);
   if (rc == TTX_OK && stats) stats->src_tokens_padded = (long long)B * Ls;    // the encoder ran once per source
   return rc;
@@ -2148,6 +2259,17 @@ extern "C" int ttx_sample_speculative_generate_ex(ttx_session* s, const int64_t*
   if (!o) o = &none;
   return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, o->d_prefix, o->ld_prefix, o->h_prefix_len,
                                      o->d_proposal, o->ld_proposal, o->h_proposal_len, o->d_bias, o->ld_bias);
+}
+
+// ttx_sample_speculative_generate_ex under a syntax constraint: the keyed draw of a draft position comes from the row masked for the
+// prefix that includes the earlier draft tokens, so the committed rows are ttx_sample_generate_syntax's.
+extern "C" int ttx_sample_speculative_generate_syntax(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                                                      const ttx_sample_spec_params* p, const ttx_sample_opts* o, const ttx_syntax* syntax,
+                                                      int64_t* d_out, ttx_gen_stats* stats, void* stream) {
+  const ttx_sample_opts none{};
+  if (!o) o = &none;
+  return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, o->d_prefix, o->ld_prefix, o->h_prefix_len,
+                                     o->d_proposal, o->ld_proposal, o->h_proposal_len, o->d_bias, o->ld_bias, syntax);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2239,6 +2361,7 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
     need(s->pfx_len, (size_t)C * 4); need(s->pfx_src, (size_t)C * 4); need(s->pfx_draft0, (size_t)C * D * 4);
   }
   if (smp && smp->d_bias) { need(s->lb_val, (size_t)smp->n_sources * c.vocab_size * sizeof(float)); need(s->lb_src, (size_t)C * 4); }
+  if (smp && smp->d_syntax) need(s->syn_cls, (size_t)c.vocab_size);
   TTX_TRY(need.rc);
   AcceptBlk* blk = nullptr;
   // the greedy pool keeps the session's reading of TTX_ACCEPT_SPREAD; the sampling pool reads it here, with its other switches
@@ -2322,7 +2445,8 @@ static int pool_admit(PoolJob& j, const int64_t* d_src_rows, int ld_src, int R, 
 // The sampling pool has a site of its own, and its keys end with the form of the accept step (1: the pair), which it reads from
 // the environment per call.
 static GraphKey pool_key(const PoolJob& j, const StepCtx& k, int variant, int phase) {
-  const int biased = k.bias.val ? GS_LOGIT_BIAS : 0; // a biased step is never replayed for an unbiased call
+  // a biased or a constrained step is never replayed for a call without the bias or the constraint
+  const int biased = (k.bias.val ? GS_LOGIT_BIAS : 0) | (k.syntax ? GS_SYNTAX : 0);
   if (k.want_sample_step && k.prop.tok)              // a proposed pool: a site of its own, the key ends with the context length
     return GraphKey{GS_STEP_POOL_SAMPLE_PROPOSAL | biased, k.B, k.Ls, k.N, k.D, k.max_len, k.max_len, variant, phase, j.g.la.blk ? 1 : 0, k.prop_ctx};
   if (k.want_sample_step)
@@ -2431,6 +2555,10 @@ static int pool_sample_begin(PoolJob& j, const SampleSetup& smp) {
   if (smp.d_bias) {                                  // every pool of the call holds the whole table; a slot's row is written at admission
     TTX_TRY(bias_upload(s, j.st, smp.d_bias, smp.ld_bias, smp.n_sources));
     k.bias = LogitBiasTab{s->lb_val.as<float>(), s->m->cfg.vocab_size, s->lb_src.as<int>()};
+  }
+  if (smp.d_syntax) {                                // one table for the call: nothing per slot, the state comes from the slot's row
+    TTX_TRY(syntax_upload(s, j.st, smp.d_syntax));
+    k.syntax = s->syn_cls.as<signed char>();
   }
   return TTX_OK;
 }
@@ -2549,13 +2677,16 @@ static int sample_speculative_generate_pool(ttx_session** sessions, int n_sessio
                                             const int32_t* h_len, const int64_t* d_row_keys, int capacity, const ttx_sample_spec_params* p,
                                             int64_t* d_out, ttx_gen_stats* stats, void* stream, const int64_t* d_prefix, int ld_prefix,
                                             const int32_t* h_prefix_len, const int64_t* d_proposal = nullptr, int ld_proposal = 0,
-                                            const int32_t* h_proposal_len = nullptr, const float* d_bias = nullptr, int ld_bias = 0) {
+                                            const int32_t* h_proposal_len = nullptr, const float* d_bias = nullptr, int ld_bias = 0,
+                                            const ttx_syntax* syn = nullptr) {
   const char* who = "ttx_sample_speculative_generate_pool";
   if (!sessions || n_sessions <= 0 || !d_src || S_total < 0 || !h_len || !p || !d_out)
     return fail(TTX_ERR_INVALID, std::string("bad argument to ") + who);
   for (int i = 0; i < n_sessions; ++i)
     if (!sessions[i]) return fail(TTX_ERR_INVALID, std::string("bad argument to ") + who);
   TTX_TRY(bias_validate(who, sessions[0], d_bias, ld_bias));
+  const signed char* cls;
+  TTX_TRY(syntax_validate(who, syn, p->sample.max_len, &cls));
   SampleSetup smp{};
   ttx_gen_params g{};
   TTX_TRY(sample_spec_validate(who, sessions[0], p, capacity, &smp, &g));
@@ -2573,7 +2704,7 @@ static int sample_speculative_generate_pool(ttx_session** sessions, int n_sessio
   TTX_TRY(proposal_validate(who, d_proposal, ld_proposal, h_proposal_len, S_total, g.max_len, &smp));
   if (S_total == 0) return TTX_OK;
   smp.d_row_keys = d_row_keys;
-  smp.d_bias = d_bias; smp.ld_bias = ld_bias;
+  smp.d_bias = d_bias; smp.ld_bias = ld_bias; smp.d_syntax = cls;
   return pool_generate(sessions, n_sessions, d_src, S_total, Ls_all, h_len, Ls_cap, capacity, &g, d_out, nullptr, nullptr, stats, stream, &smp);
 }
 
@@ -2615,6 +2746,18 @@ extern "C" int ttx_sample_speculative_generate_pool_ex(ttx_session** sessions, i
   return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p, d_out, stats, stream,
                                           o->d_prefix, o->ld_prefix, o->h_prefix_len, o->d_proposal, o->ld_proposal, o->h_proposal_len,
                                           o->d_bias, o->ld_bias);
+}
+
+// ttx_sample_speculative_generate_pool_ex under a syntax constraint: one table for the call, nothing per slot.
+extern "C" int ttx_sample_speculative_generate_pool_syntax(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total,
+                                                           int Ls_all, const int32_t* h_len, const int64_t* d_row_keys, int capacity,
+                                                           const ttx_sample_spec_params* p, const ttx_sample_opts* o,
+                                                           const ttx_syntax* syntax, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
+  const ttx_sample_opts none{};
+  if (!o) o = &none;
+  return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p, d_out, stats, stream,
+                                          o->d_prefix, o->ld_prefix, o->h_prefix_len, o->d_proposal, o->ld_proposal, o->h_proposal_len,
+                                          o->d_bias, o->ld_bias, syntax);
 }
 
 // Several batches in flight on one GPU: outputs per batch are identical to the one-at-a-time call.
@@ -4296,6 +4439,34 @@ extern "C" int ttx_debug_logit_bias(ttx_session* s, float* d_logits, int V, int 
 // ttx_debug_logit_bias's not counted: 0 for a session that never served a biased call.
 extern "C" int ttx_debug_logit_bias_launches(ttx_session* s) {
   return s ? (int)std::min<long long>(s->logit_bias_launches, 0x7fffffff) : 0;
+}
+
+// ONE launch of k_syntax_mask on the caller's device arrays (tests/test_gpu_syntax_kernel.py).  mode 0: the plain mapping (d_tok int32
+// [M][ld_tok], d_front one int); 1: the step layout (d_tok int32 [B][ld_tok], d_front [B], d_act_idx, d_row_map or null, d_drafts
+// [B][N][D]); 2: teacher-forced (d_tok int64 [M / T][ld_tok], rows of T positions).  Every index is the caller's to keep in range.
+extern "C" int ttx_debug_syntax_mask(ttx_session* s, int mode, float* d_logits, int V, int M, const int32_t* d_m, const int8_t* d_cls,
+                                     int max_len, int eos, const void* d_tok, int ld_tok, const int32_t* d_front,
+                                     const int32_t* d_act_idx, const int32_t* d_row_map, const int32_t* d_drafts, int N, int D, int T,
+                                     void* stream) {
+  if (!s) return session_required("ttx_debug_syntax_mask");
+  if (!d_logits || !d_cls || !d_tok || V <= 0 || M <= 0 || ld_tok < 1 || mode < 0 || mode > 2)
+    return fail(TTX_ERR_INVALID, "bad argument to ttx_debug_syntax_mask");
+  if (mode == 1 ? (!d_front || !d_act_idx || N < 1 || D < 0 || (D > 0 && !d_drafts)) : mode == 0 ? !d_front : (T < 1 || M % T != 0 || ld_tok <= T - 1))
+    return fail(TTX_ERR_INVALID, "ttx_debug_syntax_mask: the step layout needs d_front, d_act_idx, N >= 1, D >= 0 and drafts; the plain "
+                                 "mapping d_front; the teacher-forced one T >= 1, M a multiple of T and ld_tok >= T");
+  HIP_TRY(hipSetDevice(s->m->device));
+  SyntaxArgs a{};
+  a.logits = d_logits; a.V = V; a.m_ptr = d_m; a.M = M; a.cls = reinterpret_cast<const signed char*>(d_cls); a.max_len = max_len; a.eos = eos;
+  if (mode == 2) { a.hyp = static_cast<const int64_t*>(d_tok); a.ld_hyp = ld_tok; a.T = T; }
+  else { a.gen = static_cast<const int*>(d_tok); a.gen_ld = ld_tok; a.front = d_front; }
+  if (mode == 1) { a.act_idx = d_act_idx; a.row_map = d_row_map; a.drafts = d_drafts; a.N = N; a.D = D; }
+  return launch_syntax_mask((hipStream_t)stream, a, mode == 1);
+}
+
+// k_syntax_mask launches the session has enqueued (eagerly or into a captured step; a replayed graph adds none) since it was created,
+// ttx_debug_syntax_mask's not counted: 0 for a session that never served a constrained call.
+extern "C" int ttx_debug_syntax_launches(ttx_session* s) {
+  return s ? (int)std::min<long long>(s->syntax_launches, 0x7fffffff) : 0;
 }
 
 extern "C" int ttx_debug_argmax(ttx_session* s, const float* d_logits, int V, int32_t* d_pred, const int32_t* d_m, int m_max,

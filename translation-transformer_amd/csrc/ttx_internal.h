@@ -94,7 +94,10 @@ enum GraphSite { GS_STEP_SPECULATIVE = 0, GS_STEP_GREEDY = 1, GS_STEP_ROW_RULE =
                  // or-ed into the site of a sampling step that carries a per-source logit bias (k_logit_bias between the classifier
                  // and the sampling kernel, reading the session's table): the key of the unbiased step is untouched, and a biased
                  // step is never replayed for an unbiased call
-                 GS_LOGIT_BIAS = 256 };
+                 GS_LOGIT_BIAS = 256,
+                 // or-ed into the site of a sampling step under a syntax constraint (k_syntax_mask after k_logit_bias, reading the
+                 // session's class table): a constrained step has keys of its own; the rule's max_len is the step's, which every key holds
+                 GS_SYNTAX = 512 };
 typedef std::vector<int> GraphKey;
 
 // Captured graphs of one family of keys.  A key runs eagerly the first time it is seen (`warmed`: function attributes are set
@@ -159,6 +162,8 @@ struct GraphCache {
   /* per-source logit bias of a biased call: the session's copy of the table, float [sources][V], and per pool slot its row of it */ \
   /* (single-session loops use smp_src_of, the beam loops t_src_of) */                                                            \
   X(lb_val) X(lb_src)                                                                                                            \
+  /* syntax-constrained sampling: the session's copy of the call's class table, int8 [V] */                                       \
+  X(syn_cls)                                                                                                                     \
   /* stochastic beam search (ttx_sbs_generate): the perturbed log-probabilities G of the candidates, read and written in turn */  \
   X(sbs_g) X(sbs_g_next)                                                                                                         \
   /* stochastic beam pool (ttx_sbs_generate_pool): the per-slot words (keys, then six int arrays), the sources' lengths and the */ \
@@ -180,6 +185,7 @@ struct ttx_session {
   // ttx_pool_last_counters: summed over the pools of the last slot-pool call (greedy or sampling) whose first session this was
   long long pool_counters[7] = {};
   long long logit_bias_launches = 0;    // k_logit_bias launches this session enqueued or captured (ttx_debug_logit_bias_launches)
+  long long syntax_launches = 0;        // k_syntax_mask launches this session enqueued or captured (ttx_debug_syntax_launches)
   ttx::BeamHost* beam_host = nullptr;   // pinned + device-mapped, written by k_bs_publish
   ttx::BeamPoolHost* bp_host = nullptr; // pinned + device-mapped, written by k_bsp_publish
   ttx::HostInfo* host_info = nullptr;   // pinned + device-mapped, written by the accept kernels

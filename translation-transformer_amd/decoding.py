@@ -14,6 +14,7 @@ import torch
 from . import _native as N
 from .model import AttentionMaps, HypothesisScores, NativeTransformer, ProposalScores
 from .scoring import combine_bias
+from .syntax import as_syntax
 
 
 def _refuse_bias(who: str, logit_bias, allowed) -> None:
@@ -22,6 +23,14 @@ def _refuse_bias(who: str, logit_bias, allowed) -> None:
         raise ValueError(f"{who} takes no logit_bias / allowed: the per-source logit bias is implemented for TranslationInferenceSampling, "
                          "TranslationInferenceSamplingSpeculative (generate and generate_many) and "
                          "TranslationInferenceStochasticBeamSearch.generate; temperature=0 on the samplers is constrained greedy decoding")
+
+
+def _refuse_syntax(who: str, syntax) -> None:
+    """The generators that take no syntax constraint say so, rather than decode unconstrained."""
+    if syntax is not None:
+        raise ValueError(f"{who} takes no syntax: the syntax constraint is implemented for TranslationInferenceSampling and "
+                         "TranslationInferenceSamplingSpeculative (generate and generate_many); temperature=0 on the samplers is "
+                         "greedy decoding that cannot emit an unbalanced row")
 
 
 def _need_native(model) -> NativeTransformer:
@@ -62,7 +71,8 @@ class _ScoresHypotheses:
             raise ValueError("the generator's pad token differs from the model's")
         return self.model.alternatives(src, pred, k=k, eos_token_idx=eos, **kw)
 
-    def logq(self, src: torch.Tensor, pred: torch.Tensor, prefix=None, logit_bias=None, allowed=None, **kw) -> ProposalScores:
+    def logq(self, src: torch.Tensor, pred: torch.Tensor, prefix=None, logit_bias=None, allowed=None, syntax=None,
+             **kw) -> ProposalScores:
         """The log-probability of the hypotheses ``pred`` (Long[B, N, L] as ``generate(src)`` returned it) under a SAMPLING
         distribution, beside ``score`` (which gives it under the model): by default the generator's own ``temperature``,
         ``top_k`` and ``top_p`` where it has them (the two samplers, stochastic beam search), temperature 1 without a filter on
@@ -70,8 +80,11 @@ class _ScoresHypotheses:
         its positions cost nothing (``forced_len`` = the prefix lengths).  ``logit_bias`` (Float[B, V]) and / or ``allowed``
         (Bool[B, V]): the per-source bias the rows were generated under (``generate``'s keywords): ``logq`` is then the
         log-probability under the biased distribution, ``-inf`` with ``first_outside`` at the first forbidden token for a row the
-        biased sampler cannot emit, while ``with_scores=True`` keeps ``scores`` the raw model's.  Other keywords go to
-        ``NativeTransformer.proposal_scores``."""
+        biased sampler cannot emit, while ``with_scores=True`` keeps ``scores`` the raw model's.  ``syntax``: the ``SmilesSyntax``
+        the rows were generated under (``generate``'s keyword): ``logq`` is the log-probability under the constrained sampler, with
+        the generator's ``max_len`` as the rule's, and ``first_outside`` names the first position the constrained sampler could not
+        have emitted (an unmatched ``)``, an EOS with a branch or ring open, a token the column budget excludes).  Other keywords go
+        to ``NativeTransformer.proposal_scores``."""
         pad, eos = self._pad_eos()
         if pad != self.model.tgt_pad_token_i:
             raise ValueError("the generator's pad token differs from the model's")
@@ -85,23 +98,27 @@ class _ScoresHypotheses:
         bias = combine_bias(logit_bias, allowed, int(pred.shape[0]), self.model.tgt_vocab_size)
         if bias is not None:
             kw["logit_bias"] = bias
+        if syntax is not None:
+            kw["syntax"] = as_syntax(syntax)
+            kw["syntax"].check_prefix(prefix, pad)
+            kw.setdefault("syntax_max_len", int(getattr(self, "max_len", 0)) or int(pred.shape[-1]))
         return self.model.proposal_scores(src, pred, eos_token_idx=eos, **kw)
 
     def _scored(self, src: torch.Tensor, pred: torch.Tensor, return_scores: bool, return_logq: bool = False, prefix=None,
-                logit_bias=None):
+                logit_bias=None, syntax=None):
         """``pred``; with ``return_scores`` and / or ``return_logq`` the tuple ``(pred[, HypothesisScores][, ProposalScores])``.
         Both flags: ONE decoder pass (``with_scores=True``), the ProposalScores' ``scores`` being the HypothesisScores."""
         if not return_logq:
             return (pred, self.score(src, pred)) if return_scores else pred
-        q = self.logq(src, pred, prefix=prefix, logit_bias=logit_bias, with_scores=return_scores)
+        q = self.logq(src, pred, prefix=prefix, logit_bias=logit_bias, syntax=syntax, with_scores=return_scores)
         return (pred, q.scores, q) if return_scores else (pred, q)
 
     def _scored_many(self, batches: list, preds: list, return_scores: bool = True, return_logq: bool = False, prefixes=None,
-                     biases=None) -> list:
+                     biases=None, syntax=None) -> list:
         pres = prefixes if prefixes is not None else [None] * len(batches)
         bs = biases if biases is not None else [None] * len(batches)
         return [(p,) + (None,) * (int(return_scores) + int(return_logq)) if p is None
-                else self._scored(b, p, return_scores, return_logq, q, lb) for b, p, q, lb in zip(batches, preds, pres, bs)]
+                else self._scored(b, p, return_scores, return_logq, q, lb, syntax) for b, p, q, lb in zip(batches, preds, pres, bs)]
 
 
 def _slot_pool_plan(rows: int, in_flight: int, capacity: int | None) -> tuple:
@@ -160,10 +177,11 @@ class TranslationInferenceGreedySpeculative(_ScoresHypotheses):
         return (f"Greedy speculative decoding (draft_len={self.draft_len}, n_drafts={self.n_drafts}, "
                 f"max_len={self.max_len})")
 
-    def generate(self, src: torch.Tensor, return_scores: bool = False, logit_bias=None, allowed=None):
+    def generate(self, src: torch.Tensor, return_scores: bool = False, logit_bias=None, allowed=None, syntax=None):
         """``return_scores=True``: ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``).  ``logit_bias`` / ``allowed``
         are refused (ValueError): the samplers at ``temperature=0`` decode greedily under a bias."""
         _refuse_bias("TranslationInferenceGreedySpeculative", logit_bias, allowed)
+        _refuse_syntax("TranslationInferenceGreedySpeculative", syntax)
         m = self.model
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
@@ -186,7 +204,7 @@ class TranslationInferenceGreedySpeculative(_ScoresHypotheses):
 
     def generate_many(self, batches: list, in_flight: int = 4, reorder: bool = False, group_size: int | None = None,
                       on_error: str = "raise", pool: bool | None = None, return_scores: bool = False, logit_biases=None,
-                      allowed=None) -> list:
+                      allowed=None, syntax=None) -> list:
         """Decode several batches with up to `in_flight` of them on the GPU at once (one session + stream each;
         ttx_greedy_speculative_generate_many).  Returns one [B,1,max_len] tensor per batch, each identical to what
         ``generate`` returns for that batch; counters accumulate as if ``generate`` had been called per batch.
@@ -203,6 +221,7 @@ class TranslationInferenceGreedySpeculative(_ScoresHypotheses):
         ``return_scores=True``: a list of ``(pred, HypothesisScores)`` pairs; a batch that came back ``None`` has ``None``
         scores.  ``logit_biases`` / ``allowed`` are refused (ValueError), as in ``generate``."""
         _refuse_bias("TranslationInferenceGreedySpeculative.generate_many", logit_biases, allowed)
+        _refuse_syntax("TranslationInferenceGreedySpeculative.generate_many", syntax)
         if return_scores:
             return self._scored_many(batches, self.generate_many(batches, in_flight, reorder, group_size, on_error, pool))
         m = self.model
@@ -387,10 +406,11 @@ class TranslationInferenceGreedy(_ScoresHypotheses):
     def __str__(self):
         return f"Greedy decoding (max_len={self.max_len})"
 
-    def generate(self, src: torch.Tensor, return_scores: bool = False, logit_bias=None, allowed=None):
+    def generate(self, src: torch.Tensor, return_scores: bool = False, logit_bias=None, allowed=None, syntax=None):
         """``return_scores=True``: ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``).  ``logit_bias`` / ``allowed``
         are refused (ValueError): ``TranslationInferenceSampling`` at ``temperature=0`` is this loop under a bias."""
         _refuse_bias("TranslationInferenceGreedy", logit_bias, allowed)
+        _refuse_syntax("TranslationInferenceGreedy", syntax)
         m = self.model
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
@@ -470,8 +490,19 @@ class TranslationInferenceSampling(_ScoresHypotheses):
         bias = combine_bias(logit_bias, allowed, B, m.tgt_vocab_size)
         return None if bias is None else bias.to(m.device).contiguous()
 
+    def _syntax_arg(self, syntax, prefix=None):
+        """``(SmilesSyntax, device table, byref(ttx_syntax))`` of a call's ``syntax`` after its checks, or three ``None``."""
+        syn = as_syntax(syntax)
+        if syn is None:
+            return None, None, None
+        m = self.model
+        d_cls = syn.table(m.tgt_vocab_size, m.device)
+        for q in (prefix if isinstance(prefix, (list, tuple)) else [prefix]):
+            syn.check_prefix(q, self.pad_token)
+        return syn, d_cls, C.byref(N.Syntax(d_cls.data_ptr(), int(self.max_len)))
+
     def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, prefix=None, return_logq: bool = False,
-                 logit_bias=None, allowed=None):
+                 logit_bias=None, allowed=None, syntax=None):
         """Long[B, num_samples, max_len].  ``row_keys``: one integer per source (default 0..B-1), the source's identity for
         the random stream: the same (source, key) gives the same samples in any batch.  ``return_scores=True``:
         ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``).  ``return_logq=True``: ``(pred, ProposalScores)``, the
@@ -489,7 +520,17 @@ class TranslationInferenceSampling(_ScoresHypotheses):
         0 / ``-inf`` (``scoring.allowlist_from_source`` builds the "tokens of the source" list); both together: the allow-list is
         added onto the bias.  A forced prefix position ignores the bias.  A row depends on its source, key, sample id, prefix and
         its source's bias row alone.  ``temperature=0`` is constrained greedy decoding.  ``return_logq=True`` scores under the
-        call's bias.  ``None`` for both is the call without the keywords, launch for launch."""
+        call's bias.  ``None`` for both is the call without the keywords, launch for launch.
+
+        ``syntax``: a ``SmilesSyntax`` (or its raw int8 table [V]): the row can only hold tokens after which it can still end
+        balanced inside ``max_len``: every OPEN closed, every ring label used an even number of times, EOS at the end (the rule:
+        include/ttx.h; k_syntax_mask writes ``-inf`` over the other tokens after the bias and before temperature and filter, an
+        allowed logit keeps its bits).  Unprompted, every row ends in EOS at or before the last column, balanced and without a
+        FORBID token.  A necessary condition for a parseable SMILES string, not validity.  A forced prefix position ignores the
+        mask, yet its tokens count in the state; a prefix whose running depth goes negative is refused (ValueError), one that
+        already needs more columns than remain is accepted: closers only, and the row may end unfinished.  With a bias the allowed
+        set is the intersection.  ``temperature=0`` is greedy decoding over the allowed set.  ``return_logq=True`` scores under
+        the call's table.  ``None`` is the call without the keyword, launch for launch."""
         m, n = self.model, self.num_samples
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
@@ -497,6 +538,7 @@ class TranslationInferenceSampling(_ScoresHypotheses):
         # d_prefix is bound only to keep the device tensor alive until the call returns: prefix_ptr points into it
         d_prefix, prefix_ptr, ld_prefix, h_plen = self._prefix_args(prefix, B)
         bias = self._bias_arg(logit_bias, allowed, B)
+        syn, d_cls, syn_arg = self._syntax_arg(syntax, prefix)      # d_cls keeps the device table alive until the call returns
         keys = None
         if row_keys is not None:
             keys = torch.as_tensor(row_keys, dtype=torch.int64).to(m.device).contiguous()
@@ -506,7 +548,11 @@ class TranslationInferenceSampling(_ScoresHypotheses):
                            self.eos_token, self.seed & 0xFFFFFFFFFFFFFFFF)
         out = torch.empty((B, max(n, 1), max(self.max_len, 1)), dtype=torch.int64, device=m.device)
         st = N.GenStats()
-        if bias is None:
+        if syn is not None:
+            opts = N.SampleOpts.of(prefix_ptr, ld_prefix, h_plen, bias=bias)
+            N.check(m._lib.ttx_sample_generate_syntax(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
+                                                      C.byref(p), C.byref(opts), syn_arg, out.data_ptr(), C.byref(st), m._stream()))
+        elif bias is None:
             N.check(m._lib.ttx_sample_generate_prefix(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
                                                       C.byref(p), prefix_ptr, ld_prefix, h_plen, out.data_ptr(), C.byref(st),
                                                       m._stream()))
@@ -517,7 +563,7 @@ class TranslationInferenceSampling(_ScoresHypotheses):
         self.model_calls_num += int(st.model_calls)
         self.given_tokens += int((src != m.src_pad_token_i).sum())
         self.last_stats = st
-        return self._scored(src, out, return_scores, return_logq, prefix, bias)
+        return self._scored(src, out, return_scores, return_logq, prefix, bias, syn)
 
 
 class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
@@ -544,10 +590,12 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
                 f"top_k={self.top_k}, top_p={self.top_p}, num_samples={self.num_samples}, seed={self.seed}, max_len={self.max_len})")
 
     def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, prefix=None, proposal=None,
-                 return_logq: bool = False, logit_bias=None, allowed=None):
-        """Long[B, num_samples, max_len]; ``row_keys``, ``return_scores``, ``return_logq``, ``prefix``, ``logit_bias`` and
-        ``allowed`` as for ``TranslationInferenceSampling.generate`` (the rows under a bias are the plain sampler's under the same
-        bias; a draft, prefix-as-draft or proposal token the biased sampler cannot emit is never accepted).  A prefix rides in as the first draft of its rows, which is certain to be
+                 return_logq: bool = False, logit_bias=None, allowed=None, syntax=None):
+        """Long[B, num_samples, max_len]; ``row_keys``, ``return_scores``, ``return_logq``, ``prefix``, ``logit_bias``,
+        ``allowed`` and ``syntax`` as for ``TranslationInferenceSampling.generate`` (the rows under a bias or a syntax constraint
+        are the plain sampler's under the same; a draft, prefix-as-draft or proposal token the constrained sampler cannot emit is
+        never accepted: the draw of a draft position comes from the row masked for the prefix that includes the earlier draft
+        tokens).  A prefix rides in as the first draft of its rows, which is certain to be
         accepted: ``P`` forced tokens take ``ceil(P / (draft_len + 1))`` verify steps.
 
         ``proposal``: Long[B, Lq] without BOS, right-padded with PAD, may end in EOS: a draft the caller brings for every sample
@@ -571,6 +619,7 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         d_prefix, prefix_ptr, ld_prefix, h_plen = self._prefix_args(prefix, B)
         d_prop, prop_ptr, ld_prop, h_qlen = self._prefix_args(proposal, B)          # the same checks and limits
         bias = self._bias_arg(logit_bias, allowed, B)
+        syn, d_cls, syn_arg = self._syntax_arg(syntax, prefix)      # d_cls keeps the device table alive until the call returns
         keys = None
         if row_keys is not None:
             keys = torch.as_tensor(row_keys, dtype=torch.int64).to(m.device).contiguous()
@@ -581,7 +630,12 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
                                self.draft_len, self.n_drafts, self.replace_token, 0)
         out = torch.empty((B, max(n, 1), max(self.max_len, 1)), dtype=torch.int64, device=m.device)
         st = N.GenStats()
-        if bias is None:
+        if syn is not None:
+            opts = N.SampleOpts.of(prefix_ptr, ld_prefix, h_plen, prop_ptr, ld_prop, h_qlen, bias)
+            N.check(m._lib.ttx_sample_speculative_generate_syntax(m.session, src.data_ptr(), B, Ls,
+                                                                  None if keys is None else keys.data_ptr(), C.byref(p), C.byref(opts),
+                                                                  syn_arg, out.data_ptr(), C.byref(st), m._stream()))
+        elif bias is None:
             N.check(m._lib.ttx_sample_speculative_generate_proposal(m.session, src.data_ptr(), B, Ls,
                                                                     None if keys is None else keys.data_ptr(), C.byref(p), prefix_ptr,
                                                                     ld_prefix, h_plen, prop_ptr, ld_prop, h_qlen, out.data_ptr(),
@@ -601,11 +655,11 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         t["src_tokens_padded"] += B * Ls
         t["batches"] += 1
         self.last_stats = st
-        return self._scored(src, out, return_scores, return_logq, prefix, bias)
+        return self._scored(src, out, return_scores, return_logq, prefix, bias, syn)
 
     def generate_many(self, batches: list, row_keys=None, in_flight: int = 4, capacity: int | None = None,
                       return_scores: bool = False, prefixes=None, proposals=None, return_logq: bool = False,
-                      logit_biases=None, allowed=None) -> list:
+                      logit_biases=None, allowed=None, syntax=None) -> list:
         """The samples of all batches from slot pools (ttx_sample_speculative_generate_pool: continuous batching over the sources
         of the whole list, sorted by length; the ``num_samples`` rows of a source are admitted together).  Returns one
         Long[B_i, num_samples, max_len] per batch.
@@ -626,7 +680,10 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         batch (see ``generate``) or ``None``: ``generate_many(batches, logit_biases=bs)[i]`` holds the rows of
         ``generate(batches[i], logit_bias=bs[i], row_keys=arange(off_i, off_i + B_i))``.  Every pool holds the call's table
         [S, V]; a slot gets its source's row at admission and a reused slot carries nothing over.  ``return_logq=True`` scores
-        each batch under its own bias."""
+        each batch under its own bias.
+        ``syntax``: ONE ``SmilesSyntax`` for the whole call (see ``generate``): every row of every batch is generated under it,
+        and ``generate_many(batches, syntax=t)[i]`` holds the rows of ``generate(batches[i], syntax=t, row_keys=...)``.  The
+        state is recomputed from the slot's row, so a reused slot carries nothing over."""
         for name, tabs in (("logit_biases", logit_biases), ("allowed", allowed)):
             if tabs is not None and len(tabs) != len(batches):
                 raise ValueError(f"{name} must hold one entry per batch ({len(batches)}), got {len(tabs)}")
@@ -640,8 +697,8 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
                 biases = None
         if return_scores or return_logq:
             return self._scored_many(batches, self.generate_many(batches, row_keys, in_flight, capacity, prefixes=prefixes,
-                                                                 proposals=proposals, logit_biases=biases),
-                                     return_scores, return_logq, prefixes, biases)
+                                                                 proposals=proposals, logit_biases=biases, syntax=syntax),
+                                     return_scores, return_logq, prefixes, biases, as_syntax(syntax))
         from .scheduling import plan_row_groups
         if prefixes is not None and proposals is not None:
             raise ValueError("a call takes forced prefixes or proposals, not both")
@@ -651,6 +708,7 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
         if not batches:
             return []
         m, n, L = self.model, self.num_samples, self.max_len
+        syn, d_cls, syn_arg = self._syntax_arg(syntax, prefixes)    # d_cls keeps the device table alive until the call returns
         sizes = [int(b.shape[0]) for b in batches]
         S = sum(sizes)
 
@@ -730,7 +788,13 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
 
             pre_sorted, pre_ptr, ld_prefix, h_plen = table_args(allpre, plen)
             prop_sorted, prop_ptr, ld_prop, h_qlen = table_args(allprop, qlen)
-            if allbias is None:
+            if syn is not None:
+                bias_sorted = None if allbias is None else allbias[order_t].contiguous()
+                opts = N.SampleOpts.of(pre_ptr, ld_prefix, h_plen, prop_ptr, ld_prop, h_qlen, bias_sorted)
+                N.check(m._lib.ttx_sample_speculative_generate_pool_syntax(sess, len(sessions), src_mat.data_ptr(), S, width, h_len,
+                                                                           keys_sorted.data_ptr(), cap, C.byref(p), C.byref(opts),
+                                                                           syn_arg, out_sorted.data_ptr(), C.byref(st), m._stream()))
+            elif allbias is None:
                 N.check(m._lib.ttx_sample_speculative_generate_pool_proposal(sess, len(sessions), src_mat.data_ptr(), S, width, h_len,
                                                                              keys_sorted.data_ptr(), cap, C.byref(p), pre_ptr, ld_prefix,
                                                                              h_plen, prop_ptr, ld_prop, h_qlen, out_sorted.data_ptr(),
@@ -780,10 +844,11 @@ class TranslationInferenceBeamSearch(_ScoresHypotheses):
     def __str__(self):
         return f"Beam search decoding (beam_size={self.beam_size}, max_len={self.max_len})"
 
-    def generate(self, src: torch.Tensor, return_scores: bool = False, logit_bias=None, allowed=None):
+    def generate(self, src: torch.Tensor, return_scores: bool = False, logit_bias=None, allowed=None, syntax=None):
         """``return_scores=True``: ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``).  ``logit_bias`` / ``allowed``
         are refused (ValueError)."""
         _refuse_bias("TranslationInferenceBeamSearch", logit_bias, allowed)
+        _refuse_syntax("TranslationInferenceBeamSearch", syntax)
         m, K = self.model, self.beam_size
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
@@ -854,7 +919,7 @@ class TranslationInferenceStochasticBeamSearch(_ScoresHypotheses):
                 f"top_p={self.top_p}, seed={self.seed}, max_len={self.max_len})")
 
     def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, return_details: bool = False,
-                 order: str = "sample", trace: bool = False, prefix=None, logit_bias=None, allowed=None):
+                 order: str = "sample", trace: bool = False, prefix=None, logit_bias=None, allowed=None, syntax=None):
         """Long[B, K, max_len]: BOS, the tokens up to and including the first EOS or PAD, PAD after.  ``row_keys``: one integer
         per source (default 0..B-1), the source's identity for the random stream.  ``order="sample"``: rows in sampling order
         (``gumbel`` descending); ``order="logp"``: re-sorted by ``logp``, best first (equal values keep their sampling order).
@@ -872,7 +937,8 @@ class TranslationInferenceStochasticBeamSearch(_ScoresHypotheses):
         added to every level's logits before temperature and filter (ttx_sbs_generate_bias), so the K rows are a sample without
         replacement from what the biased sampler draws from and ``logp`` is the log-probability under it; under a narrow
         allow-list fewer than K rows may exist (the missing ranks come back as under a filter).  ``None`` for both is the call
-        without the keywords."""
+        without the keywords.  ``syntax`` is refused (ValueError): the beam layouts take no syntax constraint yet."""
+        _refuse_syntax("TranslationInferenceStochasticBeamSearch", syntax)
         if order not in ("sample", "logp"):
             raise ValueError(f"order must be 'sample' or 'logp', got {order!r}")
         m, K = self.model, self.beam_size
@@ -946,7 +1012,7 @@ class TranslationInferenceStochasticBeamSearch(_ScoresHypotheses):
 
     def generate_many(self, batches: list, row_keys=None, in_flight: int = 4, capacity: int | None = None,
                       return_scores: bool = False, return_details: bool = False, order: str = "sample", prefixes=None,
-                      logit_biases=None, allowed=None) -> list:
+                      logit_biases=None, allowed=None, syntax=None) -> list:
         """``generate`` over a whole list of batches on pools of source slots (ttx_sbs_generate_pool: continuous batching over the
         sources of the list, sorted by length).  A source leaves the pool as soon as its K rows are finished and the next one
         takes its slot, so a decoder pass serves unfinished candidates only.  Returns one entry per batch, shaped as ``generate``
@@ -963,6 +1029,7 @@ class TranslationInferenceStochasticBeamSearch(_ScoresHypotheses):
         them for that batch, the decoder passes apportioned by candidates)."""
         from .scheduling import plan_row_groups
         _refuse_bias("TranslationInferenceStochasticBeamSearch.generate_many (the source-slot pool)", logit_biases, allowed)
+        _refuse_syntax("TranslationInferenceStochasticBeamSearch.generate_many (the source-slot pool)", syntax)
         if order not in ("sample", "logp"):
             raise ValueError(f"order must be 'sample' or 'logp', got {order!r}")
         self._pool_plan(1, in_flight, capacity)               # refuses a capacity outside [1, 1024] before anything else
@@ -1147,10 +1214,11 @@ class TranslationInferenceBeamSearchSpeculative(_ScoresHypotheses):
         if not self.smart_drafts_mode:
             self.n_drafts += B * self.requested_drafts_num                       # :434
 
-    def generate(self, src: torch.Tensor, return_scores: bool = False, logit_bias=None, allowed=None):
+    def generate(self, src: torch.Tensor, return_scores: bool = False, logit_bias=None, allowed=None, syntax=None):
         """``return_scores=True``: ``(pred, HypothesisScores)`` instead of ``pred`` (see ``score``).  ``logit_bias`` / ``allowed``
         are refused (ValueError)."""
         _refuse_bias("TranslationInferenceBeamSearchSpeculative", logit_bias, allowed)
+        _refuse_syntax("TranslationInferenceBeamSearchSpeculative", syntax)
         m = self.model
         src = src.to(m.device, torch.int64).contiguous()
         m.check_tokens(src)
@@ -1163,7 +1231,7 @@ class TranslationInferenceBeamSearchSpeculative(_ScoresHypotheses):
         return self._scored(src, out[:, :, :int(st.out_width)].contiguous(), return_scores)
 
     def generate_many(self, batches: list, in_flight: int = 4, pool: bool | None = None, on_error: str = "raise",
-                      capacity: int | None = None, return_scores: bool = False, logit_biases=None, allowed=None) -> list:
+                      capacity: int | None = None, return_scores: bool = False, logit_biases=None, allowed=None, syntax=None) -> list:
         """Several batches on the GPU at once; every returned tensor and the counters are those of per-batch ``generate`` calls.
 
         ``pool`` (default: on for two or more batches, ``TTX_BEAM_POOL=0`` turns it off): the given batches are decoded in slot
@@ -1179,6 +1247,7 @@ class TranslationInferenceBeamSearchSpeculative(_ScoresHypotheses):
         ``return_scores=True``: a list of ``(pred, HypothesisScores)`` pairs; a batch that came back ``None`` has ``None``
         scores.  ``logit_biases`` / ``allowed`` are refused (ValueError), as in ``generate``."""
         _refuse_bias("TranslationInferenceBeamSearchSpeculative.generate_many", logit_biases, allowed)
+        _refuse_syntax("TranslationInferenceBeamSearchSpeculative.generate_many", syntax)
         if return_scores:
             return self._scored_many(batches, self.generate_many(batches, in_flight, pool, on_error, capacity))
         m = self.model

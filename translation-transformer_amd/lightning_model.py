@@ -109,6 +109,7 @@ class _PredictAhead:
         self.decode_seconds = 0.0
         self.rows = 0                # sources decoded ahead so far: the running index the sampling generators key their rows by
         self.prefixes = {}           # batch index -> the batch's "prefix_tokens" it was decoded with (sampling generators; None: none)
+        self.syntax = None           # the module's syntax table (sampling generators under predict_syntax_constraint)
         self.biases = {}             # batch index -> the batch's ("logit_bias", "allowed_tokens") it was decoded with (None: none)
 
     def _decode_window(self, device) -> None:
@@ -154,6 +155,8 @@ class _PredictAhead:
             more = {"proposals": proposals} if proposed else {}
             if biased:
                 more.update(logit_biases=biases, allowed=allowed)
+            if self.syntax is not None and isinstance(g, D.TranslationInferenceSamplingSpeculative):
+                more.update(syntax=self.syntax)
             preds = g.generate_many(pending, row_keys=keys, in_flight=self.in_flight, prefixes=prefixes if prompted else None, **more)
             self.rows = r0
         else:                                                           # source pools over all sources of the window
@@ -273,6 +276,10 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         # ProposalScores; generation "sampling", "sampling_speculative" and "stochastic_beam_search" only.  No init_arg either —
         # set the attribute or TTX_PREDICT_LOGQ=1
         self.predict_with_logq = False
+        # hold the samplers to rows that can still end balanced (branches closed, ring labels paired, EOS inside max_len): the
+        # syntax table is built from the target tokenizer (syntax.SmilesSyntax.from_vocab); generation "sampling" and
+        # "sampling_speculative" only.  No init_arg either — set the attribute or TTX_PREDICT_SYNTAX=1
+        self.predict_syntax_constraint = False
         self.predict_logq: dict = {}
         self._logq_on = False
         self._logq_seconds, self._outside = 0.0, 0
@@ -368,6 +375,8 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         elif pred is None and self.hparams.generation in ("sampling", "sampling_speculative"):
             B = int(batch["src_tokens"].shape[0])
             more = dict(bias) if proposal is None else dict(bias, proposal=proposal)
+            if getattr(self, "_syntax", None) is not None:
+                more["syntax"] = self._syntax
             pred = self.generator.generate(batch["src_tokens"], row_keys=torch.arange(self._predict_rows, self._predict_rows + B),
                                            prefix=prefix, **more)
             self._predict_rows += B
@@ -397,7 +406,10 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         _score_batch."""
         torch.cuda.synchronize()
         t0 = timer()
-        q = self.generator.logq(src, pred, prefix=prefix, with_scores=with_scores, **(bias or {}))
+        more = dict(bias or {})
+        if getattr(self, "_syntax", None) is not None:
+            more["syntax"] = self._syntax
+        q = self.generator.logq(src, pred, prefix=prefix, with_scores=with_scores, **more)
         torch.cuda.synchronize()
         dt = timer() - t0
         self._logq_seconds += dt
@@ -488,6 +500,13 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             raise ValueError('predict_with_logq / TTX_PREDICT_LOGQ: only generation="sampling", "sampling_speculative" and '
                              f'"stochastic_beam_search" draw from a sampling distribution, not "{self.hparams.generation}"')
         self.predict_logq = {}
+        self._syntax = None
+        if bool(self.predict_syntax_constraint) or os.environ.get("TTX_PREDICT_SYNTAX") == "1":
+            if self.hparams.generation not in ("sampling", "sampling_speculative"):
+                raise ValueError('predict_syntax_constraint / TTX_PREDICT_SYNTAX: only generation="sampling" and '
+                                 f'"sampling_speculative" take the syntax constraint, not "{self.hparams.generation}"')
+            from .syntax import SmilesSyntax
+            self._syntax = SmilesSyntax.from_vocab(self.tgt_tokenizer)
         self._logq_seconds, self._outside = 0.0, 0
         self._alternatives_seconds = 0.0
         self._attention_seconds = 0.0
@@ -503,6 +522,7 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             # a second pass over the loader must not consume it: one-shot iterators (iter(x) is x) are decoded per batch
             if loader is not None and iter(loader) is not loader:
                 self._ahead = _PredictAhead(self.generator, loader, window, int(os.environ.get("TTX_INFLIGHT", "8")))
+                self._ahead.syntax = self._syntax
         if self.report_prediction_time:
             self.prediction_start_time = timer()
 

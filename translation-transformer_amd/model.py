@@ -217,18 +217,20 @@ class NativeTransformer:
     def kernel_profile(self) -> dict:
         """GEMM event-pair sums of every session of this model since the last read (ttx_last_kernel_profile; sessions created
         under TTX_PROFILE_GEMM=1): {"gemm_ms", "launches", "pair_overhead_ms"}, and "logit_bias_launches": the k_logit_bias
-        launches the sessions have enqueued since they were created (not reset by a read; 0 unless a biased call ran)."""
+        launches the sessions have enqueued since they were created (not reset by a read; 0 unless a biased call ran), and
+        "syntax_launches": the same count of k_syntax_mask launches (0 unless a syntax-constrained call ran)."""
         ms, n, e = C.c_double(), C.c_int64(), C.c_double()
-        tot_ms, tot_n, over, lb = 0.0, 0, [], 0
+        tot_ms, tot_n, over, lb, sy = 0.0, 0, [], 0, 0
         for sess in (getattr(self, "_pool", None) or [self._session]):
             lb += int(self._lib.ttx_debug_logit_bias_launches(sess))
+            sy += int(self._lib.ttx_debug_syntax_launches(sess))
             N.check(self._lib.ttx_last_kernel_profile(sess, C.byref(ms), C.byref(n), C.byref(e)))
             tot_ms += ms.value
             tot_n += n.value
             if n.value and e.value > 0:
                 over.append(e.value)
         return {"gemm_ms": tot_ms, "launches": tot_n, "pair_overhead_ms": float(np.median(over)) if over else 0.0,
-                "logit_bias_launches": lb}
+                "logit_bias_launches": lb, "syntax_launches": sy}
 
     # -- kernel-level test entry points --------------------------------------------------------
     @staticmethod
@@ -333,6 +335,23 @@ class NativeTransformer:
         N.check(self._lib.ttx_debug_logit_bias(self.session, logits.data_ptr(), V, M, self._ptr(m_live), bias.data_ptr(),
                                                int(bias.stride(0)), self._ptr(src), rows_per_src, self._ptr(act_idx), self._ptr(row_map),
                                                n, d, self._stream()))
+
+    def debug_syntax_mask(self, logits: torch.Tensor, cls: torch.Tensor, max_len: int, eos: int, tok: torch.Tensor,
+                          front: torch.Tensor | None = None, m_live: torch.Tensor | None = None, act_idx: torch.Tensor | None = None,
+                          row_map: torch.Tensor | None = None, drafts: torch.Tensor | None = None, n: int = 1, d: int = 0,
+                          t: int = 0) -> None:
+        """ONE launch of k_syntax_mask, in place on ``logits`` (a float32 device tensor [M, V] whose rows are contiguous) with the
+        int8 class table ``cls`` [V].  Plain mapping (``act_idx`` None, ``t`` 0): ``tok`` int32 [M, ld], ``front`` int32 [1].  Step
+        layout (``act_idx`` set): ``tok`` int32 [B, ld], ``front`` int32 [B], ``row_map`` or None, ``drafts`` int32 [B, n, d].
+        Teacher-forced (``t`` > 0): ``tok`` int64 [M / t, ld].  ``m_live``: int32 [1] on the device, the live rows."""
+        M, V = logits.shape
+        assert logits.stride(1) == 1 and logits.stride(0) == V and tok.stride(1) == 1 and cls.dtype == torch.int8 and cls.numel() >= V
+        mode = 2 if t > 0 else 1 if act_idx is not None else 0
+        assert tok.dtype == (torch.int64 if mode == 2 else torch.int32)
+        N.check(self._lib.ttx_debug_syntax_mask(self.session, mode, logits.data_ptr(), V, M, self._ptr(m_live), cls.data_ptr(),
+                                                int(max_len), int(eos), tok.data_ptr(), int(tok.stride(0)), self._ptr(front),
+                                                self._ptr(act_idx), self._ptr(row_map), self._ptr(drafts), int(n), int(d), int(t),
+                                                self._stream()))
 
     def debug_sample(self, logits: torch.Tensor, key: torch.Tensor, sample: torch.Tensor, done: torch.Tensor, front: torch.Tensor,
                      pred: torch.Tensor, m_max: int, m_live: torch.Tensor | None = None, *, temperature: float = 1.0, top_k: int = 0,
@@ -1084,13 +1103,16 @@ class NativeTransformer:
         return f.to(self.device, torch.int32).contiguous()
 
     def hypothesis_logq(self, logits: torch.Tensor, hyp: torch.Tensor, pad: int, eos: int, temperature: float = 1.0, top_k: int = 0,
-                        top_p: float = 1.0, forced_len=None, check_ids: bool = True, logit_bias=None) -> ProposalScores:
+                        top_p: float = 1.0, forced_len=None, check_ids: bool = True, logit_bias=None, syntax=None,
+                        syntax_max_len: int = 0) -> ProposalScores:
         """The stage alone (ttx_hypothesis_logq): ``logits`` fp32 [..., W-1, V] as ``decode_tgt(hyp[..., :-1])`` gives them,
         ``hyp`` Long[..., W] with the same leading shape, ``forced_len`` integers of that leading shape.  A ``logits`` tensor
         that is already a contiguous fp32 device tensor is read in place.  Every output is returned.  Nothing is synchronised
         (``check_ids=False`` skips the IndexError check of the token ids, which reads their range back).
         ``logit_bias``: Float[S, V] with ``S`` the first leading dimension (the sources; ``scoring.check_logit_bias``'s form): the
-        stage runs on a biased copy of the logits (ttx_hypothesis_logq_bias), ``logits`` itself is not written."""
+        stage runs on a biased copy of the logits (ttx_hypothesis_logq_bias), ``logits`` itself is not written.
+        ``syntax``: a ``syntax.SmilesSyntax``: the copy is also masked by k_syntax_mask under the rule's ``syntax_max_len``
+        (0: W), after the bias (ttx_hypothesis_logq_syntax)."""
         x = logits.to(self.device, torch.float32)
         if not x.is_contiguous():
             x = x.contiguous()
@@ -1110,6 +1132,20 @@ class NativeTransformer:
                              torch.empty(lead + (W - 1,), dtype=torch.float32, device=dev),
                              torch.empty(lead + (W - 1,), dtype=torch.int32, device=dev),
                              torch.empty(lead + (W - 1,), dtype=torch.int32, device=dev), None)
+        if syntax is not None:
+            from .scoring import check_logit_bias
+            from .syntax import as_syntax
+            bias = None if logit_bias is None else check_logit_bias(logit_bias, int(lead[0]), V).to(dev).contiguous()
+            d_cls = as_syntax(syntax).table(V, dev)
+            R = hyp.numel() // W
+            N.check(self._lib.ttx_hypothesis_logq_syntax(self._scoring_session(), x.data_ptr(), hyp.data_ptr(), R, W, V, int(pad),
+                                                         int(eos), C.byref(dist), self._ptr(forced), self._ptr(bias), V,
+                                                         R // max(int(lead[0]), 1), C.byref(N.Syntax(d_cls.data_ptr(), int(syntax_max_len))),
+                                                         out.token_logq.data_ptr(), out.logq.data_ptr(),
+                                                         out.first_outside.data_ptr(), out.rank.data_ptr(), out.n_kept.data_ptr(),
+                                                         out.length.data_ptr(), out.finished.data_ptr(), self._stream()))
+            out.logq.masked_fill_(out.first_outside >= 0, float("-inf"))     # see proposal_scores
+            return out
         if logit_bias is not None:
             from .scoring import check_logit_bias
             bias = check_logit_bias(logit_bias, int(lead[0]), V).to(dev).contiguous()
@@ -1128,7 +1164,8 @@ class NativeTransformer:
 
     def proposal_scores(self, src: torch.Tensor, hyp: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                         forced_len=None, with_scores: bool = False, return_token_logq: bool = False, return_rank: bool = False,
-                        trim: bool = True, max_rows: int | None = None, eos_token_idx: int = 2, logit_bias=None) -> ProposalScores:
+                        trim: bool = True, max_rows: int | None = None, eos_token_idx: int = 2, logit_bias=None, syntax=None,
+                        syntax_max_len: int = 0) -> ProposalScores:
         """Log-probability of every hypothesis ``hyp[b, k]`` (Long[B, N, W]) of source ``src[b]`` under the distribution a sampler
         with (``temperature``, ``top_k``, ``top_p``) draws from: the teacher-forced pass of ``score_hypotheses`` and the stage
         that evaluates the sampler's own rule at every emitted token (ttx_score_proposal; include/ttx.h defines the quantity).
@@ -1147,7 +1184,13 @@ class NativeTransformer:
         form; ``-inf`` forbids a token).  The log q stage then reads the biased logits (k_logit_bias on the teacher-forced logits,
         ttx_score_proposal_bias), so ``logq`` is the log-probability under the biased sampler's distribution, ``first_outside`` names
         the first forbidden token and ``logq = -inf`` means "cannot be emitted".  ``scores`` (``with_scores=True``) stay the RAW
-        model's log p, from the logits before the bias, in the same pass: ``scoring.importance_weights`` stays ``p / q``."""
+        model's log p, from the logits before the bias, in the same pass: ``scoring.importance_weights`` stays ``p / q``.
+
+        ``syntax``: the ``syntax.SmilesSyntax`` the rows were (or would be) sampled under, with ``syntax_max_len`` the sampler's
+        ``max_len`` (0: W).  k_syntax_mask then masks the teacher-forced logits after the bias (ttx_score_proposal_syntax):
+        ``first_outside`` names the first position the constrained sampler could not have emitted; ``scores`` stay the raw log p.
+        After an unmatched CLOSE (depth below zero, which no constrained row reaches) the rule can leave a later position no token
+        at all: ``token_logq`` is NaN there, ``logq`` is ``-inf`` as for every row with a ``first_outside``."""
         src, hyp = self._tokens(src), self._tokens(hyp)
         if src.dim() != 2 or hyp.dim() != 3 or hyp.shape[0] != src.shape[0] or hyp.shape[1] < 1 or hyp.shape[2] < 2:
             raise ValueError(f"proposal_scores needs hyp [B, N >= 1, W >= 2] for src [B, Ls]; got {tuple(hyp.shape)} for "
@@ -1163,6 +1206,11 @@ class NativeTransformer:
         if logit_bias is not None:
             from .scoring import check_logit_bias
             bias = check_logit_bias(logit_bias, B, V).to(dev).contiguous()
+        d_cls = syn_arg = None
+        if syntax is not None:
+            from .syntax import as_syntax
+            d_cls = as_syntax(syntax).table(V, dev)
+            syn_arg = C.byref(N.Syntax(d_cls.data_ptr(), int(syntax_max_len) or W))
         Wt, chunk = self._trim_and_chunk(hyp, eos, trim, max_rows)
         T, Tt = W - 1, Wt - 1
         cut = Wt != W
@@ -1191,7 +1239,9 @@ class NativeTransformer:
                     self._ptr(part[1]), self._ptr(part[2]), out.length[b0:b1].data_ptr(), out.finished[b0:b1].data_ptr(), stream)
             head = (sess, src[b0:b1].data_ptr(), nb, Ls, hyp[b0:b1].data_ptr(), W, K, Wt, eos, C.byref(dist),
                     None if forced is None else forced[b0:b1].data_ptr())
-            if bias is None:
+            if syn_arg is not None:
+                N.check(self._lib.ttx_score_proposal_syntax(*head, None if bias is None else bias[b0:b1].data_ptr(), V, syn_arg, *tail))
+            elif bias is None:
                 N.check(self._lib.ttx_score_proposal(*head, *tail))
             else:
                 N.check(self._lib.ttx_score_proposal_bias(*head, bias[b0:b1].data_ptr(), V, *tail))
@@ -1199,6 +1249,10 @@ class NativeTransformer:
                 for t, c in zip(full, part):
                     if t is not None:
                         t[b0:b1, :, :Tt] = c
+        if syn_arg is not None:
+            # a hypothesis whose depth has gone negative (an unmatched CLOSE: outside the support from there on) can later meet a
+            # position at which the rule leaves no token at all; its token_logq is NaN there, and the row is -inf all the same
+            out.logq.masked_fill_(out.first_outside >= 0, float("-inf"))
         return out
 
     # -- cross-attention maps of hypotheses -----------------------------------------------------
