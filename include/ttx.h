@@ -154,6 +154,53 @@ int ttx_score_hypotheses(ttx_session* s, const int64_t* d_src, int B, int Ls, co
                          int eos, float* d_logits, float* d_tok_logp, float* d_score, int32_t* d_length, uint8_t* d_finished,
                          void* stream);
 
+/* Folding hypotheses: the N rows of every source reduced to their distinct hypotheses, counted and ranked, on the device.
+ * Input.  d_hyp: B*N int64 rows with row stride ld_hyp >= W; source b owns rows b*N .. b*N + N - 1.  d_score: optional fp32
+ *   [B,N]; a NaN score is read as -inf, so the outputs are always a permutation (rejecting NaN is the caller's job: the library
+ *   reads no device value back).
+ * Identity (scoring.unique_samples' rule, column 0 included).  e_j is the column of the first `eos` of row j in [0, W);
+ *   c_j = e_j + 1, or W when the row holds no `eos` (such a row is UNFINISHED).  Rows i and j of one source are the same
+ *   hypothesis iff c_i == c_j and their tokens agree on [0, c).  Tokens are compared as full 64-bit values.  What follows the
+ *   first `eos` is never read.
+ * Representative.  first[j] is the smallest i <= j equal to j; row j is a representative iff first[j] == j; its count is the
+ *   number of j' with first[j'] == j; its score is ITS OWN score, whatever scores its repeats carry.
+ * Order of the representatives: a precedes b
+ *   TTX_FOLD_FIRST   iff a < b;
+ *   TTX_FOLD_SCORE   (needs scores) iff s_a > s_b, or s_a == s_b under IEEE equality (-0.0 equals 0.0) and a < b: the order of
+ *                    scoring.unique_samples;
+ *   TTX_FOLD_COUNT   the larger count first, then the SCORE rule when scores are given, then a < b;
+ *   flag TTX_FOLD_UNFINISHED_LAST: every finished representative precedes every unfinished one, and the order above holds
+ *                    inside each class.
+ * Outputs, each optional (NULL: not handed out), each written in full for every source, on the device; nothing is synchronised.
+ * U is the number of representatives of the source.
+ *   d_first     int32 [B,N]  by sample: first[j]
+ *   d_rank_of   int32 [B,N]  by sample: the rank of the hypothesis that sample j belongs to
+ *   d_n_unique  int32 [B]    U
+ *   d_perm      int32 [B,N]  rank r -> sample index of the representative for r < U, -1 beyond
+ *   d_count     int32 [B,N]  by rank, 0 beyond U
+ *   d_out_score fp32  [B,N]  by rank: the representative's score bits (a NaN input reads -inf), -inf beyond U; all -inf when no
+ *                            scores were given
+ *   d_out       int64 [B,N,W] packed, by rank: the representative's row as it stands, all W columns; rows beyond U all `pad`
+ *   d_logmass   fp32  [B]    (needs scores) m = the largest representative score, acc = sum_r exp((double)s_r - m) in rank order
+ *                            in double, logmass = (float)(m + log(acc)); -inf when m is -inf.  With score = log p this is the
+ *                            log of the probability mass the distinct hypotheses cover.
+ * TTX_ERR_INVALID with nothing launched: B < 1, N < 1, N > 1024, W < 1, ld_hyp < W, a null d_hyp, an unknown order or flag bit,
+ * the SCORE order or d_logmass without scores, no output requested.
+ * Determinism.  A source's outputs depend on its own N rows and scores alone: bit-identical from call to call, at any B, any
+ * ld_hyp and any padded W at or beyond the longest compared column (widening W changes an unfinished row's c: the invariance
+ * holds for rows that hold an EOS, and for unfinished rows padded with `pad` on both sides of the comparison, which is what the
+ * generators emit).  No float is added by an atomic and nothing crosses a source.
+ * TTX_FOLD_DEBUG_NO_FILTER: the kernel's 64-bit filter word (which only spares token comparisons that cannot succeed) is taken as
+ * 0, so every pair of rows of equal c is confirmed on its tokens; the outputs are the same.  For tests.
+ * The session is optional (the kernel needs no workspace): with one the call runs on the session's device, without one on the
+ * current device; `stream` is used as given (NULL: the null stream), as the scoring pair does. */
+typedef enum ttx_fold_order { TTX_FOLD_FIRST = 0, TTX_FOLD_SCORE = 1, TTX_FOLD_COUNT = 2 } ttx_fold_order;
+enum { TTX_FOLD_UNFINISHED_LAST = 1, TTX_FOLD_DEBUG_NO_FILTER = 2 };
+int ttx_fold_hypotheses(ttx_session* s_or_null, const int64_t* d_hyp, int B, int N, int W, int ld_hyp, int pad, int eos,
+                        const float* d_score_or_null, int order, int flags, int32_t* d_first, int32_t* d_rank_of,
+                        int32_t* d_n_unique, int32_t* d_perm, int32_t* d_count, float* d_out_score, int64_t* d_out,
+                        float* d_logmass, void* stream);
+
 /* Per-position alternatives of hypotheses: what else the model considered where it emitted a token.  Hypothesis rows, logits, n
  * and the limits as for the scoring pair above; T = W - 1; x = logits[r,p,:]; position p of row r is live iff p < n, and for a live
  * position, t = h[p+1] and 1 <= k <= min(32, V):

@@ -2,7 +2,7 @@
 Academich/translation-transformer.  Import as ``translation_transformer_amd`` through the
 shim at the repository root (the directory name carries a hyphen)."""
 from ._native import build, lib, TtxError, ReferenceError_  # noqa: F401
-from .model import NativeTransformer, HypothesisScores, AttentionMaps, Alternatives, ProposalScores, reference_pe_table  # noqa: F401
+from .model import NativeTransformer, HypothesisScores, AttentionMaps, Alternatives, ProposalScores, FoldedHypotheses, reference_pe_table  # noqa: F401
 from .decoding import (TranslationInferenceGreedySpeculative, TranslationInferenceGreedy,  # noqa: F401
                        TranslationInferenceBeamSearch, TranslationInferenceBeamSearchSpeculative,
                        TranslationInferenceSampling, TranslationInferenceSamplingSpeculative,

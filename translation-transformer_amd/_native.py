@@ -17,7 +17,7 @@ LIB_PATH = PKG_DIR / "libttx_hip.so"
 # translation units (compiled in parallel, linked into one shared library) and the headers every one of them depends on
 UNITS = [CSRC / "ttx_api.hip", CSRC / "ttx_gemm.hip", CSRC / "ttx_attn.hip"]
 HEADERS = [CSRC / "ttx_internal.h", CSRC / "ttx_common.hip.h", CSRC / "ttx_loop_kernels.hip.h", CSRC / "ttx_metrics.hip.h",
-           CSRC / "ttx_score.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_sample.hip.h", CSRC / "ttx_logq.hip.h", CSRC / "ttx_sbs.hip.h", CSRC / "ttx_sbs_pool.hip.h",
+           CSRC / "ttx_score.hip.h", CSRC / "ttx_fold.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_sample.hip.h", CSRC / "ttx_logq.hip.h", CSRC / "ttx_sbs.hip.h", CSRC / "ttx_sbs_pool.hip.h",
            CSRC / "ttx_proposal.hip.h", CSRC / "ttx_logit_bias.hip.h", CSRC / "ttx_syntax.hip.h",
            CSRC / "ttx_select.h", CSRC / "ttx_tokenizer.h", CSRC / "ttx_drive.h", CSRC / "ttx_admit.h", INCLUDE / "ttx.h"]
 SOURCES = UNITS + HEADERS
@@ -26,6 +26,10 @@ OBJ_DIR = CSRC / "build"
 TTX_OK, TTX_ERR_INVALID, TTX_ERR_HIP, TTX_ERR_NO_DEVICE, TTX_ERR_REFERENCE, TTX_ERR_NOMEM = 0, -1, -2, -3, -4, -5
 TTX_ERR_ROW_REPLAY = -6
 TTX_ERR_MAX_STEPS = -7
+# enum ttx_fold_order and the flag bits of ttx_fold_hypotheses
+TTX_FOLD_FIRST, TTX_FOLD_SCORE, TTX_FOLD_COUNT = 0, 1, 2
+TTX_FOLD_UNFINISHED_LAST, TTX_FOLD_DEBUG_NO_FILTER = 1, 2
+FOLD_ORDERS = {"first": TTX_FOLD_FIRST, "score": TTX_FOLD_SCORE, "count": TTX_FOLD_COUNT}
 # enum ttx_activation; the strings are the reference's `activation` init_arg
 TTX_ACT_NONE, TTX_ACT_RELU, TTX_ACT_GELU = 0, 1, 2
 ACTIVATIONS = {"relu": TTX_ACT_RELU, "gelu": TTX_ACT_GELU}
@@ -282,6 +286,7 @@ SYMBOLS = {
     "ttx_teacher_forced_eval": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "ttx_hypothesis_logprobs": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "ttx_score_hypotheses": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ttx_fold_hypotheses": (C.c_int, [_VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ttx_hypothesis_alternatives": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ttx_score_alternatives": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ttx_hypothesis_logq": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, _I, C.POINTER(Dist), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),

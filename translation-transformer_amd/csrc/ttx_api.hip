@@ -8,6 +8,7 @@
 #include "ttx_loop_kernels.hip.h"
 #include "ttx_metrics.hip.h"
 #include "ttx_score.hip.h"
+#include "ttx_fold.hip.h"
 #include "ttx_alternatives.hip.h"
 #include "ttx_attn_probs.hip.h"
 #include "ttx_sample.hip.h"
@@ -819,6 +820,45 @@ extern "C" int ttx_score_hypotheses(ttx_session* s, const int64_t* d_src, int B,
   }
   TTX_TRY(score_forward(s, st, d_src, B, Ls, d_hyp, ld_hyp, N, W, d_logits));
   return launch_score(s, st, d_logits, d_hyp, ld_hyp, R, W, V, c.pad_token, eos, d_tok_logp, d_score, d_length, d_finished);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Folding hypotheses into their distinct ones: csrc/ttx_fold.hip.h.  One launch, no workspace: the session only names the device.
+extern "C" int ttx_fold_hypotheses(ttx_session* s, const int64_t* d_hyp, int B, int N, int W, int ld_hyp, int pad, int eos,
+                                   const float* d_score, int order, int flags, int32_t* d_first, int32_t* d_rank_of,
+                                   int32_t* d_n_unique, int32_t* d_perm, int32_t* d_count, float* d_out_score, int64_t* d_out,
+                                   float* d_logmass, void* stream) {
+  if (!d_hyp || B < 1 || N < 1 || W < 1) return fail(TTX_ERR_INVALID, "bad argument to ttx_fold_hypotheses: d_hyp, B >= 1, N >= 1, W >= 1");
+  if (N > FOLD_MAX_N) return fail(TTX_ERR_INVALID, "ttx_fold_hypotheses: more than 1024 rows per source");
+  if (ld_hyp < W) return fail(TTX_ERR_INVALID, "ttx_fold_hypotheses: row stride ld_hyp smaller than W");
+  if (order != TTX_FOLD_FIRST && order != TTX_FOLD_SCORE && order != TTX_FOLD_COUNT)
+    return fail(TTX_ERR_INVALID, "ttx_fold_hypotheses: unknown order");
+  if (flags & ~(TTX_FOLD_UNFINISHED_LAST | TTX_FOLD_DEBUG_NO_FILTER)) return fail(TTX_ERR_INVALID, "ttx_fold_hypotheses: unknown flag bit");
+  if (!d_score && order == TTX_FOLD_SCORE) return fail(TTX_ERR_INVALID, "ttx_fold_hypotheses: the SCORE order needs scores");
+  if (!d_score && d_logmass) return fail(TTX_ERR_INVALID, "ttx_fold_hypotheses: logmass needs scores");
+  if (!d_first && !d_rank_of && !d_n_unique && !d_perm && !d_count && !d_out_score && !d_out && !d_logmass)
+    return fail(TTX_ERR_INVALID, "ttx_fold_hypotheses: no output requested");
+  if (s) {
+    HIP_TRY(hipSetDevice(s->m->device));
+  } else {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
+      return fail(TTX_ERR_NO_DEVICE, "no HIP device visible; libttx_hip has no CPU fallback");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  FoldArgs a{};
+  a.hyp = d_hyp; a.score_in = d_score; a.first = d_first; a.rank_of = d_rank_of; a.n_unique = d_n_unique; a.perm = d_perm;
+  a.count = d_count; a.score = d_out_score; a.out = d_out; a.logmass = d_logmass;
+  a.N = N; a.W = W; a.ld_hyp = ld_hyp; a.pad = pad; a.eos = eos; a.order = order; a.flags = flags;
+  // 16-byte row copies: every source and destination row starts on 16 bytes (W and ld_hyp even, both bases aligned)
+  const bool vec2 = d_out && W % 2 == 0 && ld_hyp % 2 == 0 && reinterpret_cast<uintptr_t>(d_hyp) % 16 == 0 &&
+                    reinterpret_cast<uintptr_t>(d_out) % 16 == 0;
+  if (vec2)
+    hipLaunchKernelGGL(k_fold_hyps<true>, dim3(B), dim3(FOLD_THREADS), 0, st, a);
+  else
+    hipLaunchKernelGGL(k_fold_hyps<false>, dim3(B), dim3(FOLD_THREADS), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

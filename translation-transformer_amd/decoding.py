@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .model import AttentionMaps, HypothesisScores, NativeTransformer, ProposalScores
+from .model import AttentionMaps, FoldedHypotheses, HypothesisScores, NativeTransformer, ProposalScores
 from .scoring import combine_bias
 from .syntax import as_syntax
 
@@ -103,6 +103,23 @@ class _ScoresHypotheses:
             kw["syntax"].check_prefix(prefix, pad)
             kw.setdefault("syntax_max_len", int(getattr(self, "max_len", 0)) or int(pred.shape[-1]))
         return self.model.proposal_scores(src, pred, eos_token_idx=eos, **kw)
+
+    def fold(self, src: torch.Tensor, pred: torch.Tensor, scores=None, order: str = "score", unfinished: str = "last",
+             **kw) -> FoldedHypotheses:
+        """The distinct hypotheses among ``pred`` (Long[B, N, L] as ``generate(src)`` returned it), counted and ranked on the
+        device: a ``FoldedHypotheses`` whose ``pred`` holds each source's distinct rows best first and all-PAD rows after,
+        ``count`` how often each was drawn and ``logmass`` the log of the probability mass they cover (finished hypotheses exclude
+        each other; an unfinished row's score is that of its prefix, which overlaps with its continuations).  ``scores`` (Float[B, N] or
+        a HypothesisScores of the same rows) default to ``self.score(src, pred)``.  Candidates of several calls or of several
+        generators are merged before the call, by ``torch.cat([pred_a, pred_b], dim=1)`` (and the same on their scores): rows
+        that two of them share fold into one with the summed count.  Other keywords go to
+        ``NativeTransformer.fold_hypotheses``."""
+        pad, eos = self._pad_eos()
+        if pad != self.model.tgt_pad_token_i:
+            raise ValueError("the generator's pad token differs from the model's")
+        if scores is None:
+            scores = self.score(src, pred)
+        return self.model.fold_hypotheses(pred, scores, order=order, unfinished=unfinished, pad=pad, eos=eos, **kw)
 
     def _scored(self, src: torch.Tensor, pred: torch.Tensor, return_scores: bool, return_logq: bool = False, prefix=None,
                 logit_bias=None, syntax=None):

@@ -282,6 +282,16 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         self.predict_syntax_constraint = False
         self.predict_logq: dict = {}
         self._logq_on = False
+        # predict_step scores its samples, folds them on the device (generator.fold: order="score", unfinished="last") and
+        # RETURNS the folded rows: each reaction's distinct hypotheses best first, all-PAD rows after, so that the writer's
+        # prediction_1..N columns hold no duplicate and top-N accuracy means something for a sampling run.
+        # self.predict_folds[batch_idx] = (count, n_unique, logmass).  With predict_with_scores on, the kept scores are those of
+        # the folded rows.  generation "sampling" and "sampling_speculative" only; refused together with the per-sample records
+        # (attention, alternatives, log q).  No init_arg either — set the attribute or TTX_PREDICT_FOLD=1
+        self.predict_fold_samples = False
+        self.predict_folds: dict = {}
+        self._fold_on = False
+        self._fold_seconds, self._distinct = 0.0, 0
         self._logq_seconds, self._outside = 0.0, 0
         self._alternatives_k = 0
         self.report_prediction_time = report_prediction_time
@@ -387,6 +397,8 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             self._predict_rows += B
         elif pred is None:
             pred = self.generator.generate(batch["src_tokens"])
+        if self._fold_on:
+            return self._fold_batch(batch["src_tokens"], pred, batch_idx)
         both = self._logq_on and self._scores_on and self._alternatives_k <= 0     # scores and log q from ONE decoder pass
         if self._alternatives_k > 0:
             self._alternatives_batch(batch["src_tokens"], pred, batch_idx)
@@ -420,6 +432,31 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             q = q._replace(scores=None)
         self.predict_logq[batch_idx] = q
         self._outside = self._outside + (q.first_outside >= 0).sum()      # kept on the device until the report
+
+    def _fold_batch(self, src: torch.Tensor, pred: torch.Tensor, batch_idx: int) -> torch.Tensor:
+        """The batch's samples scored and folded, whether they were decoded ahead or on the spot: returns the folded rows
+        (distinct, best first, all-PAD rows after) and keeps (count, n_unique, logmass); with scores on, the kept
+        HypothesisScores are those of the folded rows, gathered by ``perm``, and hold what the scoring rule gives an all-PAD row
+        (score 0, length 0, unfinished) beyond ``n_unique``.  Timed like _score_batch."""
+        torch.cuda.synchronize()
+        t0 = timer()
+        sc = self.generator.score(src, pred)
+        torch.cuda.synchronize()
+        t1 = timer()
+        f = self.generator.fold(src, pred, scores=sc, order="score", unfinished="last")
+        torch.cuda.synchronize()
+        self._fold_seconds += timer() - t1
+        self.predict_folds[batch_idx] = (f.count, f.n_unique, f.logmass)
+        self._distinct = self._distinct + f.n_unique.sum()                 # kept on the device until the report
+        if self._scores_on:
+            self._scoring_seconds += t1 - t0
+            live = f.perm >= 0
+            idx = f.perm.clamp(min=0).long()
+            zero = torch.zeros((), dtype=sc.score.dtype, device=sc.score.device)
+            self._keep_scores(type(sc)(torch.where(live, sc.score.gather(1, idx), zero),
+                                       torch.where(live, sc.length.gather(1, idx), torch.zeros_like(sc.length)),
+                                       live & sc.finished.gather(1, idx), None), batch_idx)
+        return f.pred
 
     def _score_batch(self, src: torch.Tensor, pred: torch.Tensor, batch_idx: int) -> None:
         """The batch's HypothesisScores, whether it was decoded ahead or on the spot; the token tensor predict_step returns
@@ -500,6 +537,16 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             raise ValueError('predict_with_logq / TTX_PREDICT_LOGQ: only generation="sampling", "sampling_speculative" and '
                              f'"stochastic_beam_search" draw from a sampling distribution, not "{self.hparams.generation}"')
         self.predict_logq = {}
+        self._fold_on = bool(self.predict_fold_samples) or os.environ.get("TTX_PREDICT_FOLD") == "1"
+        if self._fold_on and self.hparams.generation not in ("sampling", "sampling_speculative"):
+            raise ValueError('predict_fold_samples / TTX_PREDICT_FOLD: only generation="sampling" and "sampling_speculative" '
+                             f'return repeated rows to fold, not "{self.hparams.generation}"')
+        if self._fold_on and (self._attention_on or self._alternatives_k > 0 or self._logq_on):
+            raise ValueError("predict_fold_samples / TTX_PREDICT_FOLD returns the folded rows; predict_with_attention, "
+                             "predict_with_alternatives and predict_with_logq keep one record per sample and cannot be combined "
+                             "with it (predict_with_scores can)")
+        self.predict_folds = {}
+        self._fold_seconds, self._distinct = 0.0, 0
         self._syntax = None
         if bool(self.predict_syntax_constraint) or os.environ.get("TTX_PREDICT_SYNTAX") == "1":
             if self.hparams.generation not in ("sampling", "sampling_speculative"):
@@ -563,6 +610,9 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             report["alternatives_seconds"] = round(self._alternatives_seconds, 6)
         if self._attention_on:
             report["attention_seconds"] = round(self._attention_seconds, 6)
+        if self._fold_on:
+            report["fold_seconds"] = round(self._fold_seconds, 6)
+            report["distinct_hypotheses"] = int(self._distinct)
         if self._logq_on:
             report["logq_seconds"] = round(self._logq_seconds, 6)
             report["hypotheses_outside_support"] = int(self._outside)

@@ -121,6 +121,78 @@ class ProposalScores(NamedTuple):
     scores: HypothesisScores | None   # with_scores=True: score_hypotheses' result (with token_logp), from the same decoder pass
 
 
+class FoldedHypotheses(NamedTuple):
+    """Result of ``fold_hypotheses`` / ``fold`` / ``scoring.fold_samples``: the distinct hypotheses of every source, counted and
+    ranked (ttx_fold_hypotheses); device tensors, nothing copied to the host.  ``U = n_unique[b]`` ranks of source ``b`` are
+    live."""
+    pred: torch.Tensor | None      # int64 [B, N, L] by rank: the representatives' rows as they stood, all-PAD rows beyond U (gather=True)
+    perm: torch.Tensor             # int32 [B, N]: rank -> sample index of the representative, -1 beyond U
+    count: torch.Tensor            # int32 [B, N] by rank: how many of the N rows are this hypothesis, 0 beyond U
+    n_unique: torch.Tensor         # int32 [B]: U
+    first: torch.Tensor            # int32 [B, N] by sample: the first row equal to this one
+    rank_of: torch.Tensor          # int32 [B, N] by sample: the rank of the hypothesis the row belongs to
+    score: torch.Tensor            # fp32 [B, N] by rank: the representative's own score (NaN read as -inf), -inf beyond U or unscored
+    logmass: torch.Tensor | None   # fp32 [B]: log sum exp of the representatives' scores (with scores = log p: the mass covered)
+
+
+def fold_on_device(lib, session, hyp, scores=None, order: str = "score", unfinished: str = "keep", gather: bool = True,
+                   with_logmass=None, pad: int = 0, eos: int = 2, debug_no_filter: bool = False) -> FoldedHypotheses:
+    """One ttx_fold_hypotheses call on ``hyp`` Long[B, N, L] (a device tensor, or a view of one whose last-dimension stride is 1:
+    it is folded in place through its row stride) and ``scores`` Float[B, N] (or anything with ``.score``, or None).
+    ``session``: a ttx_session or None (the kernel needs no workspace).  ``lib``: the loaded library, or None to load it after
+    the arguments have been checked.  Every argument is checked before the library or the device is touched."""
+    if not isinstance(hyp, torch.Tensor) or hyp.dim() != 3 or hyp.dtype.is_floating_point or hyp.dtype == torch.bool:
+        raise ValueError(f"fold needs hyp as an integer tensor [B, N, L], got {getattr(hyp, 'dtype', type(hyp))} "
+                         f"{tuple(getattr(hyp, 'shape', ()))}")
+    B, K, L = (int(v) for v in hyp.shape)
+    if B < 1 or K < 1 or L < 1:
+        raise ValueError(f"fold needs hyp [B >= 1, N >= 1, L >= 1], got {tuple(hyp.shape)}")
+    if K > 1024:
+        raise ValueError(f"fold takes at most 1024 rows per source, got N = {K}")
+    if order not in N.FOLD_ORDERS:
+        raise ValueError(f"order must be 'score', 'count' or 'first', got {order!r}")
+    if unfinished not in ("keep", "last"):
+        raise ValueError(f"unfinished must be 'keep' or 'last', got {unfinished!r}")
+    sc = getattr(scores, "score", scores)
+    if sc is not None:
+        if not isinstance(sc, torch.Tensor) or not sc.dtype.is_floating_point or tuple(sc.shape) != (B, K):
+            raise ValueError(f"scores must be a floating-point tensor [B, N] = [{B}, {K}], got "
+                             f"{getattr(sc, 'dtype', type(sc))} {tuple(getattr(sc, 'shape', ()))}")
+    elif order == "score":
+        raise ValueError("order='score' needs scores (pass scores, or order='count' / 'first')")
+    if with_logmass is None:
+        with_logmass = sc is not None
+    if with_logmass and sc is None:
+        raise ValueError("with_logmass needs scores")
+    if not hyp.is_cuda:
+        raise ValueError("fold runs on the GPU and has no CPU fallback: pass device tensors (scoring.unique_samples folds host "
+                         "tensors)")
+    if sc is not None and sc.device != hyp.device:
+        raise ValueError(f"scores are on {sc.device}, hyp on {hyp.device}")
+    dev = hyp.device
+    if hyp.dtype != torch.int64:
+        hyp = hyp.to(torch.int64)
+    ld = int(hyp.stride(1)) if K > 1 else (int(hyp.stride(0)) if B > 1 else L)
+    if not ((L == 1 or hyp.stride(2) == 1) and ld >= L and (B == 1 or hyp.stride(0) == K * ld) and (K == 1 or hyp.stride(1) == ld)):
+        hyp, ld = hyp.contiguous(), L
+    if sc is not None:
+        sc = sc.detach().to(torch.float32).contiguous()
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    first, rank_of, perm, count, n_unique = i32(B, K), i32(B, K), i32(B, K), i32(B, K), i32(B)
+    out_score = torch.empty((B, K), dtype=torch.float32, device=dev)
+    pred = torch.empty((B, K, L), dtype=torch.int64, device=dev) if gather else None
+    logmass = torch.empty((B,), dtype=torch.float32, device=dev) if with_logmass else None
+    flags = (N.TTX_FOLD_UNFINISHED_LAST if unfinished == "last" else 0) | (N.TTX_FOLD_DEBUG_NO_FILTER if debug_no_filter else 0)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    lib = lib or N.lib()
+    with torch.cuda.device(dev):
+        N.check(lib.ttx_fold_hypotheses(session, hyp.data_ptr(), B, K, L, ld, int(pad), int(eos), ptr(sc), N.FOLD_ORDERS[order], flags,
+                                        first.data_ptr(), rank_of.data_ptr(), n_unique.data_ptr(), perm.data_ptr(), count.data_ptr(),
+                                        out_score.data_ptr(), ptr(pred), ptr(logmass),
+                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return FoldedHypotheses(pred, perm, count, n_unique, first, rank_of, out_score, logmass)
+
+
 class NativeTransformer:
     # score_hypotheses: decoder positions (rows x columns) of one call; the widest activation buffer takes ff_dim floats per
     # position (256 MiB at ff_dim 2048), and a bench batch of 32 rows x 199 columns still fits one call
@@ -985,6 +1057,23 @@ class NativeTransformer:
             if part is not None and Wt != W:
                 tok[b0:b1, :, :Wt - 1] = part
         return HypothesisScores(score, length, fin, tok)
+
+    # -- folding hypotheses into their distinct ones ---------------------------------------------
+    def fold_hypotheses(self, hyp: torch.Tensor, scores=None, order: str = "score", unfinished: str = "keep", gather: bool = True,
+                        with_logmass: bool | None = None, pad: int | None = None, eos: int = 2,
+                        debug_no_filter: bool = False) -> FoldedHypotheses:
+        """The distinct hypotheses among each source's rows, counted and ranked on the device (ttx_fold_hypotheses; the rule
+        is ``scoring.unique_samples``', stated in include/ttx.h).  ``hyp`` Long[B, N, L] with N <= 1024, or a view whose
+        last-dimension stride is 1 (folded in place through its row stride); ``scores`` Float[B, N] or anything with ``.score``.
+        ``order``: "score" (descending score, equal scores by first occurrence; needs scores), "count" (the most frequent first,
+        then by score when given), "first" (by first occurrence).  ``unfinished="last"`` puts the hypotheses without an EOS behind
+        the finished ones.  ``gather=False`` skips the gathered rows (``pred`` is None); ``with_logmass`` defaults to whether
+        scores were given.  ``pad`` (default: the model's) fills the rows beyond ``n_unique``.  Nothing is synchronised."""
+        hyp = hyp.to(self.device) if isinstance(hyp, torch.Tensor) else hyp
+        sc = getattr(scores, "score", scores)
+        sc = sc.to(self.device) if isinstance(sc, torch.Tensor) else sc
+        return fold_on_device(self._lib, self._session, hyp, sc, order, unfinished, gather, with_logmass,
+                              self.tgt_pad_token_i if pad is None else pad, eos, debug_no_filter)
 
     # -- per-position alternatives of hypotheses -------------------------------------------------
     def _alt_buffers(self, lead: tuple, T: int, k: int, fill: bool) -> Alternatives:

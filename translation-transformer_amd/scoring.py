@@ -154,6 +154,45 @@ def unique_samples(samples, scores, eos: int = 2):
     return out
 
 
+def fold_samples(samples, scores=None, order: str = "score", unfinished: str = "keep", gather: bool = True, with_logmass=None,
+                 pad: int = 0, eos: int = 2):
+    """``unique_samples`` on the device, with no model at hand: the distinct hypotheses of every source, counted and ranked by
+    one kernel launch (ttx_fold_hypotheses without a session).  ``samples`` Long[B, N, L] on the GPU, ``scores`` Float[B, N] (or
+    anything with ``.score``) or None; the keywords and the ``FoldedHypotheses`` returned are those of
+    ``NativeTransformer.fold_hypotheses``.  With ``order="score"`` and ``unfinished="keep"`` the live ranks are
+    ``unique_samples``' list, in its order.  A CPU tensor raises ValueError: there is no CPU fallback, ``unique_samples`` folds on
+    the host."""
+    from .model import fold_on_device
+    if hasattr(samples, "is_cuda") and not samples.is_cuda:
+        raise ValueError("fold_samples runs on the GPU and has no CPU fallback: pass device tensors, or fold host tensors with "
+                         "scoring.unique_samples")
+    return fold_on_device(None, None, samples, scores, order, unfinished, gather, with_logmass, pad, eos)
+
+
+def write_folds(filename: str, folds, append: bool = True) -> None:
+    """The fold side file of the prediction CSV: one line per source, ``n_unique,logmass,count_1,...,count_U`` with the counts in
+    the order of the CSV's ``prediction_1..N`` columns (logmass with 9 significant digits: fp32 round-trips; ``nan`` when the fold
+    carried none).  ``folds``: a FoldedHypotheses, or ``(count, n_unique, logmass)`` as ``predict_folds`` keeps it."""
+    if hasattr(folds, "n_unique"):
+        folds = (folds.count, folds.n_unique, folds.logmass)
+    count, n_unique, logmass = folds
+    cnt, nu = count.detach().cpu().tolist(), n_unique.detach().cpu().tolist()
+    lm = [float("nan")] * len(nu) if logmass is None else logmass.detach().cpu().tolist()
+    with open(filename, "a" if append else "w") as f:
+        for c_row, u, m in zip(cnt, nu, lm):
+            print(",".join([str(int(u)), f"{m:.9g}"] + [str(int(c)) for c in c_row[:int(u)]]), file=f)
+
+
+def read_folds(filename: str) -> list:
+    """What ``write_folds`` wrote: per source ``(n_unique, logmass, [count_1, ..., count_U])``."""
+    rows = []
+    with open(filename) as f:
+        for line in f:
+            v = line.strip().split(",")
+            rows.append((int(v[0]), float(v[1]), [int(c) for c in v[2:]]))
+    return rows
+
+
 def sbs_weights(logp, gumbel):
     """Importance weights of a stochastic-beam-search sample (Kool, van Hoof & Welling, ICML 2019, §4.2).  ``logp`` and ``gumbel``
     are [..., K + 1] as ``TranslationInferenceStochasticBeamSearch(beam_size=K + 1).generate(.., return_details=True)`` returns
