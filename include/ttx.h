@@ -789,6 +789,53 @@ typedef struct ttx_beam_search_stats {
 int ttx_beam_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_beam_search_params* p, int64_t* d_out,
                       ttx_beam_search_stats* stats, void* stream);
 
+/* Constrained beam search: ttx_beam_generate under a per-source logit bias ("Per-source logit bias" above), a syntax constraint
+ * ("Syntax-constrained sampling" above) and forced target prefixes, each optional.  The loop is ttx_beam_generate's: per level one
+ * decoder pass over the unfinished candidates, then k_logit_bias and k_syntax_mask in place on the pass's logits (the row of a
+ * candidate takes its source's bias row; the mask's prefix is the candidate's row, its position the row's width, its max_len and EOS
+ * the call's), then k_beam_step_masked (csrc/ttx_beam_mask.hip.h) where ttx_beam_generate launches k_beam_step.
+ *
+ * The rule of a step.  Per candidate: score (fp32, cumulative log-probability) and `finished`.  Source b has candidates
+ * k = 0 .. beam-1 in the order of the previous selection (beam is 1 at the first step, K afterwards), rows of `width` tokens.
+ *   Live, unforced parent.  total[k][v] = score[k] + logf(expf(x_v - m) / z) with m = max_v x_v and z = sum_v expf(x_v - m), in
+ *     k_beam_step's expressions and order: on rows of finite logits every output equals ttx_beam_generate's bit for bit (as long
+ *     as that call selects no continuation of a finished hypothesis, see the next item).  A -inf
+ *     logit (a forbidden or masked token) contributes expf(-inf) = 0 to z and gives a -inf child, so the scores are
+ *     log-probabilities under the constrained, renormalised distribution.  A row with no finite logit gives -inf for every child,
+ *     never NaN.
+ *   Finished parent.  One child, PAD, with the total ttx_beam_generate gives it: score + logf(expf(35 - 35) / z) over the
+ *     reference's artificial row, 35 on PAD and 0 elsewhere (standard_decoding.py:133-135), on the bits.  The other V - 1
+ *     children, which that row puts 35 below the PAD child, are -inf here: ttx_beam_generate can only select one of them when a
+ *     source has fewer than K children within 35 of its best finished hypothesis, which a constraint makes the ordinary case (an
+ *     allow-list of two tokens), and they would fill the free ranks with rows that go on after their EOS instead of dead rows.
+ *     A finished parent with score -inf is a DEAD parent: all its children are -inf.
+ *   Forced position (width <= h_prefix_len[b]: the token at column `width` lies inside the source's prefix).  A live parent has one
+ *     child, tok = d_prefix[b][width - 1] (an id outside [0, V) read as 0), with total = score[k] exactly; every other child is
+ *     -inf.  The logits are not read, so bias and mask do not apply, and a forced token costs no log-probability.  Finished and
+ *     dead parents behave as above.
+ *   Selection.  The K largest totals over the beam * V children, largest first; equal values break towards the lower flat index
+ *     k * V + v.  -inf children are taken only when fewer than K finite ones exist, then by ascending flat index, none twice.
+ *   A selected -inf child is a DEAD ROW: the parent's tokens followed by PAD (the forbidden token is never written), score -inf,
+ *     finished; it counts with the hypotheses holding EOS in the stop rule and costs no decoder row.  Its parent index is the
+ *     real parent's.  A dead row only ever has -inf children, so it gives way to any finite child of a later level.
+ *   Everything else (a new row is finished when its parent was or its token is EOS; the stop rule; out_width; the counters) is
+ *     ttx_beam_generate's.
+ * Consequences.  With d_bias, syntax and the prefixes all absent the call IS ttx_beam_generate, launch for launch (k_beam_step, no
+ * k_logit_bias, no k_syntax_mask), plus the copy of the scores.  A bias of zeros, a table of neutral classes whose max_len no row
+ * reaches, and an allow-list of every token each return ttx_beam_generate's rows on the bits.  The K rows of a source are pairwise
+ * distinct; fewer than K may exist under a narrow allow-list or a short max_len, and the missing ranks are dead rows, last.  Every
+ * finite row of a prompted call is BOS, the prefix, a completion.  Under a syntax table every finite row that ends, ends balanced.
+ *   d_bias fp32 [B][ld_bias] or NULL; syntax as for ttx_sample_generate_syntax (NULL or d_cls NULL: none; max_len 0 or the call's);
+ *   d_prefix int64 [B, ld_prefix] without BOS and h_prefix_len HOST int32 [B] (NULL: no prefixes), as for ttx_sbs_generate_ex;
+ *   d_out as for ttx_beam_generate; d_score fp32 [B, K] or NULL: the rows' scores, -inf for a dead row.
+ * TTX_ERR_INVALID with nothing launched: ld_bias below the vocabulary, a syntax max_len that is neither 0 nor the call's, a prefix
+ * length outside [0, max_len - 1] or above ld_prefix, a non-zero length with d_prefix NULL; and everything ttx_beam_generate
+ * refuses.  Cost: DESIGN.md §29. */
+int ttx_beam_generate_constrained(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_beam_search_params* p,
+                                  const float* d_bias, int ld_bias, const ttx_syntax* syntax, const int64_t* d_prefix, int ld_prefix,
+                                  const int32_t* h_prefix_len, int64_t* d_out, float* d_score, ttx_beam_search_stats* stats,
+                                  void* stream);
+
 /* Stochastic beam search (Kool, van Hoof & Welling, "Stochastic Beams and Where to Find Them", ICML 2019): K hypotheses per source
  * that are an exact sample WITHOUT replacement from the model's sequence distribution at the given temperature.  The loop is
  * ttx_beam_generate's (per-hypothesis KV cache, one decoder pass per level over the unfinished candidates) with k_sbs_step
@@ -1320,6 +1367,13 @@ typedef struct ttx_debug_beam_step_args {
 } ttx_debug_beam_step_args;
 /* ttx_debug_beam_step: k_beam_step on B workgroups.  Also refused: K > beam * V, width >= ld. */
 int ttx_debug_beam_step(ttx_session* s, const ttx_debug_beam_step_args* a, void* stream);
+/* ttx_debug_beam_step_masked: ONE launch of k_beam_step_masked on the same operands (tests/test_gpu_beam_mask_kernel.py).  pfx NULL
+ * or the table by source (d_len, d_src int32 [B]): source b is forced at column a->width when a->width <= d_len[b].  Refused: what
+ * ttx_debug_beam_step refuses, a table outside its bounds, a width inside a prefix but beyond pfx->ld. */
+int ttx_debug_beam_step_masked(ttx_session* s, const ttx_debug_beam_step_args* a, const ttx_debug_prefix* pfx, void* stream);
+/* The number of k_beam_step_masked launches the session's beam loop has enqueued since it was created (ttx_debug_beam_step_masked
+ * is not counted).  A session that only ever served unconstrained calls reports 0. */
+int ttx_debug_beam_step_masked_launches(ttx_session* s);
 
 typedef struct ttx_debug_sbs_step_args {
   const float* d_logits; const int32_t* d_slot_of; const uint8_t* d_finished; const float* d_phi; const float* d_g; const int32_t* d_gen;

@@ -6,7 +6,8 @@ from .model import NativeTransformer, HypothesisScores, AttentionMaps, Alternati
 from .decoding import (TranslationInferenceGreedySpeculative, TranslationInferenceGreedy,  # noqa: F401
                        TranslationInferenceBeamSearch, TranslationInferenceBeamSearchSpeculative,
                        TranslationInferenceSampling, TranslationInferenceSamplingSpeculative,
-                       TranslationInferenceStochasticBeamSearch, SbsDetails, SbsTrace)
+                       TranslationInferenceStochasticBeamSearch, SbsDetails, SbsTrace,
+                       TranslationInferenceBeamSearchConstrained, ConstrainedBeamDetails)
 from .lightning_model import VanillaEncoderDecoderTransformerLightning, run_predict, run_evaluate  # noqa: F401,E402
 from . import dist  # noqa: F401,E402
 from .tokenizer import NativeSmilesTokenizer  # noqa: F401,E402

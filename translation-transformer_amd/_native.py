@@ -18,7 +18,7 @@ LIB_PATH = PKG_DIR / "libttx_hip.so"
 UNITS = [CSRC / "ttx_api.hip", CSRC / "ttx_gemm.hip", CSRC / "ttx_attn.hip"]
 HEADERS = [CSRC / "ttx_internal.h", CSRC / "ttx_common.hip.h", CSRC / "ttx_loop_kernels.hip.h", CSRC / "ttx_metrics.hip.h",
            CSRC / "ttx_score.hip.h", CSRC / "ttx_fold.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_sample.hip.h", CSRC / "ttx_logq.hip.h", CSRC / "ttx_sbs.hip.h", CSRC / "ttx_sbs_pool.hip.h",
-           CSRC / "ttx_proposal.hip.h", CSRC / "ttx_logit_bias.hip.h", CSRC / "ttx_syntax.hip.h",
+           CSRC / "ttx_proposal.hip.h", CSRC / "ttx_logit_bias.hip.h", CSRC / "ttx_syntax.hip.h", CSRC / "ttx_beam_mask.hip.h",
            CSRC / "ttx_select.h", CSRC / "ttx_tokenizer.h", CSRC / "ttx_drive.h", CSRC / "ttx_admit.h", INCLUDE / "ttx.h"]
 SOURCES = UNITS + HEADERS
 OBJ_DIR = CSRC / "build"
@@ -357,6 +357,8 @@ SYMBOLS = {
                                                     C.POINTER(C.c_int32), _I, C.POINTER(BeamParams), _VP, _VP, _VP, _I,
                                                     C.POINTER(BeamStats), _VP]),
     "ttx_beam_generate": (C.c_int, [_VP, _VP, _I, _I, C.POINTER(BeamSearchParams), _VP, C.POINTER(BeamSearchStats), _VP]),
+    "ttx_beam_generate_constrained": (C.c_int, [_VP, _VP, _I, _I, C.POINTER(BeamSearchParams), _VP, _I, C.POINTER(Syntax), _VP, _I, _VP,
+                                                _VP, _VP, C.POINTER(BeamSearchStats), _VP]),
     "ttx_sbs_generate": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SbsParams), _VP, _VP, _VP, C.POINTER(SbsTrace),
                                   C.POINTER(BeamSearchStats), _VP]),
     "ttx_sbs_generate_ex": (C.c_int, [_VP, _VP, _I, _I, _VP, C.POINTER(SbsParams), C.POINTER(SbsFilter), _VP, _I, _VP, _VP, _VP, _VP,
@@ -408,6 +410,8 @@ SYMBOLS = {
     "ttx_debug_bs_leaves": (C.c_int, [_VP, C.POINTER(DebugBsLeavesArgs), _VP]),
     "ttx_debug_beam_select": (C.c_int, [_VP, C.POINTER(DebugBeamSelectArgs), _VP]),
     "ttx_debug_beam_step": (C.c_int, [_VP, C.POINTER(DebugBeamStepArgs), _VP]),
+    "ttx_debug_beam_step_masked": (C.c_int, [_VP, C.POINTER(DebugBeamStepArgs), C.POINTER(DebugPrefix), _VP]),
+    "ttx_debug_beam_step_masked_launches": (C.c_int, [_VP]),
     "ttx_debug_sbs_step": (C.c_int, [_VP, C.POINTER(DebugSbsStepArgs), _VP]),
     "ttx_debug_sbs_step_ex": (C.c_int, [_VP, C.POINTER(DebugSbsStepArgs), _I, C.c_float, C.POINTER(DebugPrefix), _I, _VP]),
     "ttx_debug_sbs_step_pool": (C.c_int, [_VP, C.POINTER(DebugSbsStepPoolArgs), _I, _I, C.c_float, C.POINTER(DebugPrefix), _VP]),

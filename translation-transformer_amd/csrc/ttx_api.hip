@@ -17,6 +17,7 @@
 #include "ttx_logq.hip.h"
 #include "ttx_sbs.hip.h"
 #include "ttx_sbs_pool.hip.h"
+#include "ttx_beam_mask.hip.h"
 #include "ttx_proposal.hip.h"
 #include "ttx_tokenizer.h"
 
@@ -3132,6 +3133,15 @@ static int launch_beam_step(ttx_session* s, hipStream_t st, const BeamStepArgs& 
   return TTX_OK;
 }
 
+// k_beam_step_masked with k_beam_step's launch shape (`pfx.tok` null: no forced prefixes).
+static int launch_beam_step_masked(ttx_session* s, hipStream_t st, const BeamStepArgs& sa, const PrefixTab& pfx) {
+  const size_t lds = (size_t)sa.beam * sa.V * 4;
+  TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_beam_step_masked), lds, s->attr_step_masked));
+  hipLaunchKernelGGL(k_beam_step_masked, dim3(sa.B), dim3(256), lds, st, sa, pfx);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
 static int launch_sbs_step(ttx_session* s, hipStream_t st, const SbsStepArgs& sa) {
   const size_t lds = (size_t)sa.beam * sa.V * 4;
   TTX_TRY(raise_lds_limit(reinterpret_cast<const void*>(&k_sbs_step), lds, s->attr_sbs_step));
@@ -3654,6 +3664,11 @@ struct BeamSearchJob {
   int top_k = 0; float top_p = 1.f;
   PrefixTab pfx{};
   LogitBiasTab bias{};       // ttx_sbs_generate_bias: the session's table, by candidate (t_src_of); val null: no bias, no launch
+  // ttx_beam_generate_constrained under a bias, a syntax table or a non-empty prefix: k_beam_step_masked instead of k_beam_step
+  // (constrained false: k_beam_step, launch for launch).  `bias` and `pfx` above are shared with the stochastic form.
+  bool constrained = false;
+  const signed char* syntax = nullptr;   // the session's class table (syn_cls); null: no mask, no launch
+  float* d_score = nullptr;              // [B, K] or null: the rows' cumulative scores
 };
 
 // Everything of the call behind the argument check: the reference's asserts and this library's limits, the workspaces, the
@@ -3719,6 +3734,8 @@ static int bsearch_launch_iter(BeamSearchJob& j) {
   const int variant = variant_for_rows(s, (long long)std::max(1, j.n_cand - j.n_eos), true);
   StepCtx k = tree_step_ctx(s, j.MC, j.Ls, 1, 0, j.Lc, j.ld, max_len, cur ^ 1, variant);
   k.bias = j.bias;                 // the step kernels below then read biased logits
+  k.syntax = j.syntax;             // and masked ones: gen, front = len - 1 (k_bs_prep) and act_idx (k_bs_list) are what the mask's
+  k.p.eos_token = j.p.eos_token;   // step mapping reads at (N, D) = (1, 0); the rule's EOS and max_len are the call's
   TTX_TRY(run_step(s, st, k, key_capacity(j.width, max_len)));
   if (j.sbs) {
     SbsStepArgs sa{};
@@ -3753,7 +3770,12 @@ static int bsearch_launch_iter(BeamSearchJob& j) {
   sa.new_cand = s->bs_cand_next.as<int64_t>(); sa.new_score = s->bs_logp_next.as<float>(); sa.parent = s->bs_parent.as<int>();
   sa.new_len = s->bs_len_next.as<int>(); sa.new_finished = s->bs_fin_next.as<uint8_t>(); sa.parent_draft = s->bs_parent_draft.as<int>();
   sa.summary = s->beam_summary.as<int>();
-  TTX_TRY(launch_beam_step(s, st, sa));
+  if (j.constrained) {
+    TTX_TRY(launch_beam_step_masked(s, st, sa, j.pfx));
+    s->beam_step_masked_launches += 1;
+  } else {
+    TTX_TRY(launch_beam_step(s, st, sa));
+  }
   hipLaunchKernelGGL(k_bs_publish, dim3(1), dim3(64), 0, st, s->beam_summary.as<int>(), j.dev_host, s->bs_cnt.as<BeamCounters>());
   HIP_TRY(hipGetLastError());
   ++j.launched;
@@ -3783,6 +3805,7 @@ static int bsearch_finish_enqueue(BeamSearchJob& j) {
     if (j.d_logp) HIP_TRY(hipMemcpyAsync(j.d_logp, s->bs_logp_next.p, (size_t)j.B * j.K * 4, hipMemcpyDeviceToDevice, j.st));
     if (j.d_gumbel) HIP_TRY(hipMemcpyAsync(j.d_gumbel, g.p, (size_t)j.B * j.K * 4, hipMemcpyDeviceToDevice, j.st));
   }
+  if (j.d_score) HIP_TRY(hipMemcpyAsync(j.d_score, s->bs_logp_next.p, (size_t)j.B * j.K * 4, hipMemcpyDeviceToDevice, j.st));
   TTX_TRY(enqueue_readback(s, j.st, s->bs_cnt.p, sizeof(BeamCounters)));
   j.phase = 2;
   return TTX_OK;
@@ -3799,6 +3822,64 @@ extern "C" int ttx_beam_generate(ttx_session* s, const int64_t* d_src, int B, in
   const auto turn = [&](int) -> int {
     if (j.phase == 1) {
       if (((volatile BeamHost*)s->beam_host)->steps_done < j.launched) return TURN_WAITING;   // the iteration in flight has not published yet
+      TTX_TRY(bsearch_after_iter(j) ? bsearch_launch_iter(j) : bsearch_finish_enqueue(j));
+      return TURN_PROGRESSED;
+    }
+    if (hipEventQuery(s->ev_done) != hipSuccess) return TURN_IDLE;
+    const BeamCounters* cn = reinterpret_cast<const BeamCounters*>(s->host_state);
+    stats->model_calls = cn->model_calls; stats->running_rows = cn->running_cands; stats->out_width = j.width;
+    return TURN_FINISHED;
+  };
+  return drive_sessions(&s, 1, false, stream, start, turn);
+}
+
+// Constrained beam search: the standard beam loop above under a per-source logit bias (k_logit_bias), a syntax constraint
+// (k_syntax_mask) and forced prefixes, with k_beam_step_masked (csrc/ttx_beam_mask.hip.h) where it launches k_beam_step.  A call with
+// none of the three is ttx_beam_generate, launch for launch, plus the copy of the scores.
+extern "C" int ttx_beam_generate_constrained(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_beam_search_params* p,
+                                             const float* d_bias, int ld_bias, const ttx_syntax* syntax, const int64_t* d_prefix,
+                                             int ld_prefix, const int32_t* h_prefix_len, int64_t* d_out, float* d_score,
+                                             ttx_beam_search_stats* stats, void* stream) {
+  const char* who = "ttx_beam_generate_constrained";
+  if (!s || !d_src || !p || !d_out || !stats || B <= 0 || Ls <= 1) return fail(TTX_ERR_INVALID, "bad argument to ttx_beam_generate_constrained");
+  TTX_TRY(bias_validate(who, s, d_bias, ld_bias));
+  const signed char* cls = nullptr;
+  TTX_TRY(syntax_validate(who, syntax, p->max_len, &cls));
+  SampleSetup pre{};
+  TTX_TRY(prefix_validate(who, d_prefix, ld_prefix, h_prefix_len, B, p->max_len, &pre));
+  const int V = s->m->cfg.vocab_size;
+  BeamSearchJob j;
+  const auto start = [&](int) -> int {
+    hipStream_t st = s->own_stream;
+    if (pre.prompted) {                 // sized before bsearch_start settles which graphs are current
+      TTX_TRY(ensure(s->pfx_tok, (size_t)B * p->max_len * 4, st));
+      TTX_TRY(ensure(s->pfx_len_src, (size_t)B * 4, st));
+      TTX_TRY(ensure(s->smp_src_of, (size_t)B * 4, st));
+    }
+    if (d_bias) TTX_TRY(ensure(s->lb_val, (size_t)B * V * sizeof(float), st));
+    if (cls) TTX_TRY(ensure(s->syn_cls, (size_t)V, st));
+    TTX_TRY(bsearch_start(j, s, st, d_src, B, Ls, p, d_out));
+    j.d_score = d_score;
+    j.constrained = d_bias || cls || pre.prompted;
+    if (d_bias) {
+      TTX_TRY(bias_upload(s, st, d_bias, ld_bias, B));
+      j.bias = LogitBiasTab{s->lb_val.as<float>(), V, s->t_src_of.as<int>()};
+    }
+    if (cls) {
+      TTX_TRY(syntax_upload(s, st, cls));
+      j.syntax = s->syn_cls.as<signed char>();
+    }
+    if (pre.prompted) {                 // the table by source, as the stochastic form keeps it
+      TTX_TRY(prefix_upload(s, st, pre, p->max_len, p->pad_token));
+      hipLaunchKernelGGL(k_sbs_prefix_src, dim3(cdiv(B, 256)), dim3(256), 0, st, s->smp_src_of.as<int>(), B);
+      HIP_TRY(hipGetLastError());
+      j.pfx = PrefixTab{s->pfx_tok.as<int>(), p->max_len, s->pfx_len_src.as<int>(), s->smp_src_of.as<int>()};
+    }
+    return bsearch_launch_iter(j);
+  };
+  const auto turn = [&](int) -> int {
+    if (j.phase == 1) {
+      if (((volatile BeamHost*)s->beam_host)->steps_done < j.launched) return TURN_WAITING;
       TTX_TRY(bsearch_after_iter(j) ? bsearch_launch_iter(j) : bsearch_finish_enqueue(j));
       return TURN_PROGRESSED;
     }
@@ -5170,23 +5251,55 @@ extern "C" int ttx_debug_beam_select(ttx_session* s, const ttx_debug_beam_select
   return dbg_launched(launch_beam_select(s, st, sa), st);
 }
 
-extern "C" int ttx_debug_beam_step(ttx_session* s, const ttx_debug_beam_step_args* a, void* stream) {
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (!s || !a) return fail(TTX_ERR_INVALID, "null argument to ttx_debug_beam_step");
+// The operands of a k_beam_step / k_beam_step_masked debug launch, checked, as the kernels' argument block.
+static int beam_step_debug_args(const char* who_c, ttx_session* s, const ttx_debug_beam_step_args* a, BeamStepArgs* out) {
+  const std::string who(who_c);
+  if (!s || !a) return fail(TTX_ERR_INVALID, "null argument to " + who);
   if (!a->d_logits || !a->d_slot_of || !a->d_finished || !a->d_score || !a->d_gen || !a->d_new_cand || !a->d_new_score || !a->d_parent ||
       !a->d_new_len || !a->d_new_finished || !a->d_parent_draft || !a->d_summary)
-    return fail(TTX_ERR_INVALID, "ttx_debug_beam_step: a required array is null");
-  if (a->B < 1 || a->beam < 1 || a->K < 1 || a->V < 1 || a->V > 64 * NUC_VPL) return fail(TTX_ERR_INVALID, "ttx_debug_beam_step: B, beam, K >= 1 and V in [1, 1024]");
-  if ((size_t)a->K > (size_t)a->beam * a->V) return fail(TTX_ERR_INVALID, "ttx_debug_beam_step: K exceeds the beam * V totals");
-  if ((size_t)a->beam * a->V * 4 > 150 * 1024) return fail(TTX_ERR_INVALID, "ttx_debug_beam_step: beam x vocabulary beyond the selection kernel's LDS image");
-  if (a->width < 1 || a->width >= a->ld) return fail(TTX_ERR_INVALID, "ttx_debug_beam_step: width must lie in [1, ld)");
-  HIP_TRY(hipSetDevice(s->m->device));
+    return fail(TTX_ERR_INVALID, who + ": a required array is null");
+  if (a->B < 1 || a->beam < 1 || a->K < 1 || a->V < 1 || a->V > 64 * NUC_VPL) return fail(TTX_ERR_INVALID, who + ": B, beam, K >= 1 and V in [1, 1024]");
+  if ((size_t)a->K > (size_t)a->beam * a->V) return fail(TTX_ERR_INVALID, who + ": K exceeds the beam * V totals");
+  if ((size_t)a->beam * a->V * 4 > 150 * 1024) return fail(TTX_ERR_INVALID, who + ": beam x vocabulary beyond the selection kernel's LDS image");
+  if (a->width < 1 || a->width >= a->ld) return fail(TTX_ERR_INVALID, who + ": width must lie in [1, ld)");
   BeamStepArgs sa{};
   sa.logits = a->d_logits; sa.V = a->V; sa.slot_of = a->d_slot_of; sa.finished = a->d_finished; sa.score = a->d_score;
   sa.gen = a->d_gen; sa.ld = a->ld; sa.width = a->width; sa.B = a->B; sa.beam = a->beam; sa.K = a->K; sa.pad = a->pad; sa.eos = a->eos;
   sa.new_cand = a->d_new_cand; sa.new_score = a->d_new_score; sa.parent = a->d_parent; sa.new_len = a->d_new_len;
   sa.new_finished = a->d_new_finished; sa.parent_draft = a->d_parent_draft; sa.summary = a->d_summary;
+  *out = sa;
+  return TTX_OK;
+}
+
+extern "C" int ttx_debug_beam_step(ttx_session* s, const ttx_debug_beam_step_args* a, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  BeamStepArgs sa{};
+  TTX_TRY(beam_step_debug_args("ttx_debug_beam_step", s, a, &sa));
+  HIP_TRY(hipSetDevice(s->m->device));
   return dbg_launched(launch_beam_step(s, st, sa), st);
+}
+
+extern "C" int ttx_debug_beam_step_masked(ttx_session* s, const ttx_debug_beam_step_args* a, const ttx_debug_prefix* pfx, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const char* who = "ttx_debug_beam_step_masked";
+  BeamStepArgs sa{};
+  TTX_TRY(beam_step_debug_args(who, s, a, &sa));
+  HIP_TRY(hipSetDevice(s->m->device));
+  PrefixTab tab{};
+  if (pfx) {
+    TTX_TRY(dbg_prefix_tab(who, pfx, a->B, st, &tab));
+    if (a->width > pfx->ld) {           // a position beyond the table is forced for no source
+      std::vector<int32_t> len((size_t)a->B);
+      HIP_TRY(hipMemcpy(len.data(), pfx->d_len, (size_t)a->B * 4, hipMemcpyDeviceToHost));
+      for (int b = 0; b < a->B; ++b)
+        if (len[b] >= a->width) return fail(TTX_ERR_INVALID, "ttx_debug_beam_step_masked: width inside a prefix but beyond the table's ld");
+    }
+  }
+  return dbg_launched(launch_beam_step_masked(s, st, sa, tab), st);
+}
+
+extern "C" int ttx_debug_beam_step_masked_launches(ttx_session* s) {
+  return s ? (int)std::min<long long>(s->beam_step_masked_launches, 0x7fffffff) : 0;
 }
 
 // The operands of a k_sbs_step / k_sbs_step_masked debug launch, checked, as the kernels' argument block.

@@ -186,6 +186,7 @@ struct ttx_session {
   long long pool_counters[7] = {};
   long long logit_bias_launches = 0;    // k_logit_bias launches this session enqueued or captured (ttx_debug_logit_bias_launches)
   long long syntax_launches = 0;        // k_syntax_mask launches this session enqueued or captured (ttx_debug_syntax_launches)
+  long long beam_step_masked_launches = 0;   // k_beam_step_masked launches of the beam loop (ttx_debug_beam_step_masked_launches)
   ttx::BeamHost* beam_host = nullptr;   // pinned + device-mapped, written by k_bs_publish
   ttx::BeamPoolHost* bp_host = nullptr; // pinned + device-mapped, written by k_bsp_publish
   ttx::HostInfo* host_info = nullptr;   // pinned + device-mapped, written by the accept kernels
@@ -207,6 +208,7 @@ struct ttx_session {
   bool attr_attn2[2][8] = {};      // [head dimension 32 / 64][mode]
   bool attr_select = false, attr_step = false, attr_topk = false, attr_pool_select = false, attr_sbs_step = false;
   bool attr_sbs_step_masked[5] = {};   // k_sbs_step_masked<VPL>, VPL = 1, 2, 4, 8, 16
+  bool attr_step_masked = false;       // k_beam_step_masked
   bool attr_sbs_step_pool = false, attr_sbs_step_pool_masked[5] = {};   // the pool forms of the two
   bool attr_attn_probs[8] = {};    // k_attn_probs: [head dimension 32 / 64][16-byte output stores][16-byte key loads]
   // GEMM policy (all choices are between bit-identical evaluations, see GemmVariant)

@@ -22,7 +22,8 @@ def _refuse_bias(who: str, logit_bias, allowed) -> None:
     if logit_bias is not None or allowed is not None:
         raise ValueError(f"{who} takes no logit_bias / allowed: the per-source logit bias is implemented for TranslationInferenceSampling, "
                          "TranslationInferenceSamplingSpeculative (generate and generate_many) and "
-                         "TranslationInferenceStochasticBeamSearch.generate; temperature=0 on the samplers is constrained greedy decoding")
+                         "TranslationInferenceStochasticBeamSearch.generate; temperature=0 on the samplers is constrained greedy decoding, "
+                         "and TranslationInferenceBeamSearchConstrained is beam search under a bias")
 
 
 def _refuse_syntax(who: str, syntax) -> None:
@@ -30,7 +31,8 @@ def _refuse_syntax(who: str, syntax) -> None:
     if syntax is not None:
         raise ValueError(f"{who} takes no syntax: the syntax constraint is implemented for TranslationInferenceSampling and "
                          "TranslationInferenceSamplingSpeculative (generate and generate_many); temperature=0 on the samplers is "
-                         "greedy decoding that cannot emit an unbalanced row")
+                         "greedy decoding that cannot emit an unbalanced row, and TranslationInferenceBeamSearchConstrained is beam search "
+                         "under the constraint")
 
 
 def _need_native(model) -> NativeTransformer:
@@ -878,6 +880,91 @@ class TranslationInferenceBeamSearch(_ScoresHypotheses):
         self.b_sz += int(st.running_rows)
         self.given_tokens += int((src != m.src_pad_token_i).sum())
         return self._scored(src, out[:, :, :int(st.out_width)].contiguous(), return_scores)
+
+
+class ConstrainedBeamDetails(NamedTuple):
+    """What constrained beam search knows about its rows: ``logp`` Float[B, K] the cumulative log-probability of each hypothesis
+    under the constrained, renormalised distribution (a forced prefix position costs nothing; ``-inf`` for a dead row),
+    ``finished`` Bool[B, K] the loop's flag (the row holds EOS, or it is dead) and ``alive`` Bool[B, K] (``logp`` is finite)."""
+    logp: torch.Tensor
+    finished: torch.Tensor
+    alive: torch.Tensor
+
+
+class TranslationInferenceBeamSearchConstrained(_ScoresHypotheses):
+    """``TranslationInferenceBeamSearch`` under a per-source logit bias or allow-list, a syntax constraint and forced target
+    prefixes: "the K best answers that use only the reactants' tokens", "the K best balanced strings", "the K best completions
+    of this scaffold" as one call.  The whole loop runs in ttx_beam_generate_constrained: the standard beam loop with
+    k_logit_bias and k_syntax_mask on every level's logits and k_beam_step_masked where that loop launches k_beam_step
+    (include/ttx.h states the rule).  A forbidden or masked token is a -inf logit, the scores are log-probabilities under the
+    constrained, renormalised distribution, and a source with fewer than K possible rows returns the missing ranks as DEAD rows
+    (BOS then PAD, ``logp = -inf``), last.  Without a keyword ``generate`` is ``TranslationInferenceBeamSearch.generate``, launch
+    for launch."""
+
+    def __init__(self, model, beam_size: int, max_len: int, pad_token: int, bos_token: int, eos_token: int):
+        assert max_len > 1
+        assert beam_size > 0
+        self.model = _need_native(model)
+        self.beam_size, self.max_len = beam_size, max_len
+        self.pad_token, self.bos_token, self.eos_token = pad_token, bos_token, eos_token
+        self.model_calls_num = 0
+        self.given_tokens = 0
+        self.b_sz = 0
+
+    def __str__(self):
+        return f"Constrained beam search decoding (beam_size={self.beam_size}, max_len={self.max_len})"
+
+    _prefix_args = TranslationInferenceSampling._prefix_args
+    _bias_arg = TranslationInferenceSampling._bias_arg
+    _syntax_arg = TranslationInferenceSampling._syntax_arg
+
+    def generate(self, src: torch.Tensor, logit_bias=None, allowed=None, syntax=None, prefix=None, return_scores: bool = False,
+                 return_details: bool = False):
+        """Long[B, K, width], hypotheses best first; ``return_scores=True`` appends the ``HypothesisScores`` of the returned
+        rows (the raw model's, see ``score``) and ``return_details=True`` a ``ConstrainedBeamDetails``, in that order, as a tuple.
+
+        ``logit_bias`` (Float[B, V]) and ``allowed`` (Bool[B, V], sugar for 0 / ``-inf``) as for
+        ``TranslationInferenceSampling.generate`` (``scoring.check_logit_bias``; ``scoring.allowlist_from_source`` builds the
+        "tokens of the source" list): the bias is added to every level's logits before the log-softmax.  ``syntax``: a
+        ``SmilesSyntax`` (or its raw int8 table [V]) with the generator's ``max_len`` as the rule's: a row can only hold tokens
+        after which it can still end balanced inside ``max_len``, so every live row ends in EOS by the last column.  ``prefix``:
+        Long[B, Lp] without BOS, right-padded with PAD (``check_prefix``): the forced beginning of every row of a source; a forced
+        position ignores bias and mask, reads no logits and costs nothing in ``logp``; a forced EOS ends the row (one live row).
+        One decoder step per forced token.  A prefix whose running depth goes negative under ``syntax`` is refused (ValueError).
+
+        ``logp`` agrees with ``logq(src, pred, logit_bias=.., allowed=.., syntax=.., prefix=..).logq`` at temperature 1.  Dead
+        rows come back as BOS followed by PAD only, ``logp = -inf``, ``alive = False``."""
+        m, K = self.model, self.beam_size
+        src = src.to(m.device, torch.int64).contiguous()
+        m.check_tokens(src)
+        B, Ls = src.shape
+        # d_prefix and d_cls are bound only to keep the device tensors alive until the call returns
+        d_prefix, prefix_ptr, ld_prefix, h_plen = self._prefix_args(prefix, B)
+        bias = self._bias_arg(logit_bias, allowed, B)
+        syn, d_cls, syn_arg = self._syntax_arg(syntax, prefix)
+        out = torch.empty((B, K, self.max_len), dtype=torch.int64, device=m.device)
+        logp = torch.empty((B, K), dtype=torch.float32, device=m.device)
+        p = N.BeamSearchParams(self.max_len, K, self.pad_token, self.bos_token, self.eos_token)
+        st = N.BeamSearchStats()
+        N.check(m._lib.ttx_beam_generate_constrained(m.session, src.data_ptr(), B, Ls, C.byref(p),
+                                                     None if bias is None else bias.data_ptr(),
+                                                     0 if bias is None else int(bias.stride(0)), syn_arg, prefix_ptr, ld_prefix,
+                                                     h_plen, out.data_ptr(), logp.data_ptr(), C.byref(st), m._stream()))
+        self.model_calls_num += int(st.model_calls)
+        self.b_sz += int(st.running_rows)
+        self.given_tokens += int((src != m.src_pad_token_i).sum())
+        out = out[:, :, :int(st.out_width)].contiguous()
+        alive = torch.isfinite(logp)
+        blank = torch.full_like(out, self.pad_token)
+        blank[:, :, 0] = self.bos_token
+        out = torch.where(alive[:, :, None], out, blank)
+        res = [out]
+        if return_scores:
+            res.append(self.score(src, out))
+        if return_details:
+            finished = (out[:, :, 1:] == self.eos_token).any(-1) | ~alive
+            res.append(ConstrainedBeamDetails(logp, finished, alive))
+        return res[0] if len(res) == 1 else tuple(res)
 
 
 class SbsTrace(NamedTuple):

@@ -236,9 +236,9 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
                                      embedding_dim, num_heads, feedforward_dim, share_embeddings,
                                      self.src_pad_token_i, self.tgt_pad_token_i, activation)
         if generation not in ("greedy", "beam_search", "greedy_speculative", "beam_search_speculative", "sampling",
-                              "sampling_speculative", "stochastic_beam_search"):
+                              "sampling_speculative", "stochastic_beam_search", "beam_search_constrained"):
             options = ", ".join(["beam_search", "greedy", "greedy_speculative", "beam_search_speculative", "sampling",
-                                 "sampling_speculative", "stochastic_beam_search"])
+                                 "sampling_speculative", "stochastic_beam_search", "beam_search_constrained"])
             raise ValueError(f'Unknown generation option {generation}. Options are {options}.')
         if generation in ("greedy_speculative", "sampling_speculative"):
             assert draft_len > 0, "Number of speculative tokens must be a positive integer."
@@ -277,8 +277,8 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         # set the attribute or TTX_PREDICT_LOGQ=1
         self.predict_with_logq = False
         # hold the samplers to rows that can still end balanced (branches closed, ring labels paired, EOS inside max_len): the
-        # syntax table is built from the target tokenizer (syntax.SmilesSyntax.from_vocab); generation "sampling" and
-        # "sampling_speculative" only.  No init_arg either — set the attribute or TTX_PREDICT_SYNTAX=1
+        # syntax table is built from the target tokenizer (syntax.SmilesSyntax.from_vocab); generation "sampling",
+        # "sampling_speculative" and "beam_search_constrained" only.  No init_arg either — set the attribute or TTX_PREDICT_SYNTAX=1
         self.predict_syntax_constraint = False
         self.predict_logq: dict = {}
         self._logq_on = False
@@ -338,6 +338,8 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             return D.TranslationInferenceGreedy(m, max_len=h.max_len, **common)
         if h.generation == "beam_search":
             return D.TranslationInferenceBeamSearch(m, beam_size=h.beam_size, max_len=h.max_len, **common)
+        if h.generation == "beam_search_constrained":   # beam search under the batch's bias / allow-list / prefixes and the syntax table
+            return D.TranslationInferenceBeamSearchConstrained(m, beam_size=h.beam_size, max_len=h.max_len, **common)
         if h.generation == "greedy_speculative":
             return D.TranslationInferenceGreedySpeculative(m, max_len=h.max_len, draft_len=h.draft_len, n_drafts=h.n_drafts,
                                                            replace_token=self.tgt_tokenizer.encoder_dict["c"], **common)
@@ -365,19 +367,22 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         ahead = self._ahead
         pred = None
         sampling = self.hparams.generation in ("sampling", "sampling_speculative")
+        beams = ("stochastic_beam_search", "beam_search_constrained")              # the beam loops that take prefixes and a bias
         prefix = batch["prefix_tokens"] if "prefix_tokens" in batch else None      # forced target prefixes: Long[B, Lp], no BOS
-        if prefix is not None and not sampling and self.hparams.generation != "stochastic_beam_search":
-            raise ValueError(f'"prefix_tokens" in a batch: only generation="sampling", "sampling_speculative" and '
-                             f'"stochastic_beam_search" take forced prefixes, not "{self.hparams.generation}"')
+        if prefix is not None and not sampling and self.hparams.generation not in beams:
+            raise ValueError(f'"prefix_tokens" in a batch: only generation="sampling", "sampling_speculative", '
+                             f'"stochastic_beam_search" and "beam_search_constrained" take forced prefixes, not '
+                             f'"{self.hparams.generation}"')
         proposal = batch["proposal_tokens"] if "proposal_tokens" in batch else None  # offered drafts: Long[B, Lq], no BOS
         if proposal is not None and self.hparams.generation != "sampling_speculative":
             raise ValueError(f'"proposal_tokens" in a batch: only generation="sampling_speculative" takes proposals, '
                              f'not "{self.hparams.generation}"')
         # per-source logit bias Float[B, V] and / or allow-list Bool[B, V]: which tokens a source may produce
         bias = {k: batch[name] for k, name in (("logit_bias", "logit_bias"), ("allowed", "allowed_tokens")) if name in batch}
-        if bias and not sampling and self.hparams.generation != "stochastic_beam_search":
-            raise ValueError(f'"logit_bias" / "allowed_tokens" in a batch: only generation="sampling", "sampling_speculative" and '
-                             f'"stochastic_beam_search" take a logit bias, not "{self.hparams.generation}"')
+        if bias and not sampling and self.hparams.generation not in beams:
+            raise ValueError(f'"logit_bias" / "allowed_tokens" in a batch: only generation="sampling", "sampling_speculative", '
+                             f'"stochastic_beam_search" and "beam_search_constrained" take a logit bias, not '
+                             f'"{self.hparams.generation}"')
         if ahead is not None and dataloader_idx == 0:
             pred = ahead.take(batch["src_tokens"], batch_idx, prefix, bias.get("logit_bias"), bias.get("allowed"))
         if pred is not None and self.hparams.generation in ("sampling", "sampling_speculative", "stochastic_beam_search"):
@@ -395,6 +400,11 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             pred = self.generator.generate(batch["src_tokens"], row_keys=torch.arange(self._predict_rows, self._predict_rows + B),
                                            prefix=prefix, **bias)
             self._predict_rows += B
+        elif pred is None and self.hparams.generation == "beam_search_constrained":
+            more = dict(bias)
+            if getattr(self, "_syntax", None) is not None:
+                more["syntax"] = self._syntax
+            pred = self.generator.generate(batch["src_tokens"], prefix=prefix, **more)
         elif pred is None:
             pred = self.generator.generate(batch["src_tokens"])
         if self._fold_on:
@@ -549,9 +559,10 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         self._fold_seconds, self._distinct = 0.0, 0
         self._syntax = None
         if bool(self.predict_syntax_constraint) or os.environ.get("TTX_PREDICT_SYNTAX") == "1":
-            if self.hparams.generation not in ("sampling", "sampling_speculative"):
-                raise ValueError('predict_syntax_constraint / TTX_PREDICT_SYNTAX: only generation="sampling" and '
-                                 f'"sampling_speculative" take the syntax constraint, not "{self.hparams.generation}"')
+            if self.hparams.generation not in ("sampling", "sampling_speculative", "beam_search_constrained"):
+                raise ValueError('predict_syntax_constraint / TTX_PREDICT_SYNTAX: only generation="sampling", '
+                                 '"sampling_speculative" and "beam_search_constrained" take the syntax constraint, not '
+                                 f'"{self.hparams.generation}"')
             from .syntax import SmilesSyntax
             self._syntax = SmilesSyntax.from_vocab(self.tgt_tokenizer)
         self._logq_seconds, self._outside = 0.0, 0

@@ -645,6 +645,20 @@ class NativeTransformer:
         self._debug_beam(N.DebugBeamStepArgs, self._lib.ttx_debug_beam_step,
                          dict(V=V, ld=ld, width=width, B=B, beam=beam, K=K, pad=pad, eos=eos), arrays)
 
+    def debug_beam_step_masked(self, *, V: int, ld: int, width: int, B: int, beam: int, K: int, pad: int, eos: int, pfx_tok=None,
+                               pfx_len=None, pfx_src=None, pfx_ld: int = 0, pfx_sources: int = 0, **arrays) -> None:
+        """One k_beam_step_masked launch (ttx_debug_beam_step_masked): debug_beam_step's operands and optionally the prefix table by
+        source (``pfx_tok`` int32 [pfx_sources, pfx_ld], ``pfx_len`` / ``pfx_src`` int32 [B])."""
+        pfx = None
+        if pfx_tok is not None or pfx_len is not None or pfx_src is not None:
+            pfx = C.byref(N.DebugPrefix(self._ptr(pfx_tok), int(pfx_ld), int(pfx_sources), self._ptr(pfx_len), self._ptr(pfx_src)))
+        self._debug_beam(N.DebugBeamStepArgs, self._lib.ttx_debug_beam_step_masked,
+                         dict(V=V, ld=ld, width=width, B=B, beam=beam, K=K, pad=pad, eos=eos), arrays, pfx)
+
+    def debug_beam_step_masked_launches(self) -> int:
+        """k_beam_step_masked launches this model's session has enqueued from the beam loop (ttx_debug_beam_step_masked_launches)."""
+        return int(self._lib.ttx_debug_beam_step_masked_launches(self._session))
+
     def debug_sbs_step(self, *, V: int, ld: int, width: int, B: int, beam: int, K: int, pad: int, eos: int, pos: int, seed: int,
                        inv_T: float, **arrays) -> None:
         """One k_sbs_step launch (ttx_debug_sbs_step): the operands of debug_beam_step with ``phi``, ``g``, ``key`` (absent: keys
