@@ -1596,6 +1596,53 @@ int ttx_debug_attn_probs(ttx_session* s, const float* d_q, int ldq, const float*
                          const int32_t* d_mem_row, const int32_t* d_length, int R, int Rm, int H, int head_dim, int T, int Ls,
                          float scale, float* d_heads, float* d_mean, int32_t* d_align, void* stream);
 
+/* Length-bucketed scoring of a LIST of (src, hyp) batches (csrc/ttx_score_list.hip.h): what ttx_score_hypotheses gives for every
+ * batch of the list, bit for bit while sources and hypothesis windows stay within the staged key range of the attention kernels
+ * (ttx_attn_staged_key_limit), computed in chunks of sources of similar length.  Batch i is described by one ttx_score_batch (HOST
+ * array h_batches): d_src int64 [B,Ls], d_hyp int64 [B*N] rows of stride ld_hyp >= W (W >= 2 columns read), as ttx_score_hypotheses
+ * takes them; B, Ls, N, W and ld_hyp may differ from batch to batch.  The S sources and the R hypothesis rows of the list are
+ * numbered in list order (batch 0's first).  Each call uploads the table with one stream-ordered copy; the kernels read the batches
+ * through it.  Neither call synchronises: the caller reads d_e / d_ls back between the two, and that is the only read-back.
+ *
+ * ttx_score_list_extents: d_e int32 [S], e[s] = max(2, 1 + max n over the N rows of source s) with n as under
+ *   ttx_hypothesis_logprobs; d_ls int32 [S], ls[s] = max(1, 1 + the last non-PAD column of source s).  Optional: d_n int32 [R], n of
+ *   every row; d_bad int32 [1], bit 0 set when a source token id lies outside [0, src_vocab_size), bit 1 when a hypothesis id lies
+ *   outside [0, vocab_size), over the whole given widths.
+ * ttx_score_list_run: h_order int32 [S] names every source exactly once; chunk c (ttx_score_chunk, HOST array, run in the order
+ *   given) scores the sources h_order[first .. first + count), all of batches with N rows per source, in ONE teacher-forced pass over
+ *   their first W hypothesis columns and first Ls source columns (shorter rows are PAD-filled): W >= e[s] and Ls >= ls[s] for every
+ *   member keep every scored token and every non-PAD source token.  Outputs in list order: d_score fp32 [R], d_length int32 [R],
+ *   d_finished u8 [R] or NULL, d_tok_logp fp32 or NULL: batch i at h_tok_off[i] (int64 HOST array, in floats) as [B*N, W_i - 1], a
+ *   row's first min(W, W_i) - 1 values and exact zeros after them.
+ * TTX_ERR_INVALID with nothing launched: a null required pointer, an empty list, ld_hyp < W, W < 2, B, N or Ls < 1 in a batch; an
+ *   order or chunk table that names a source twice or leaves one out; a chunk with mixed N, W < 2, Ls < 1, 2^24 or more positions
+ *   (count * N * (W - 1)) or a width beyond the positional table; a vocabulary above 1024.
+ * ttx_debug_score_list (test entry): ONE launch of k_sl_extents (op 0), k_sl_pack (op 1) or k_sl_unpack (op 2) on the test's
+ *   operands: h_sel int32 [n_sel] are the chunk's sources (ops 1, 2); the chunk's N, W and Ls, and the arrays, come in `a`. */
+typedef struct ttx_score_batch {
+  const int64_t* d_src;
+  const int64_t* d_hyp;
+  int32_t B, Ls, N, W, ld_hyp;
+} ttx_score_batch;
+typedef struct ttx_score_chunk {
+  int32_t first, count;     /* the chunk's sources: h_order[first .. first + count) */
+  int32_t N, W, Ls;         /* rows per source; hypothesis and source columns of the pass */
+} ttx_score_chunk;
+typedef struct ttx_debug_score_list_args {
+  int32_t* d_e; int32_t* d_ls; int32_t* d_n; int32_t* d_bad;                                          /* op 0 */
+  int64_t* d_src_c; int64_t* d_hyp_c;                                                                 /* op 1: [n_sel,Ls], [n_sel*N,W] */
+  const float* d_score_c; const int32_t* d_length_c; const uint8_t* d_fin_c; const float* d_tok_c;    /* op 2, in: [n_sel*N], tok [.,W-1] */
+  float* d_score; int32_t* d_length; uint8_t* d_finished; float* d_tok_logp;                          /* op 2, out: list order */
+  int32_t N, W, Ls, eos;
+} ttx_debug_score_list_args;
+int ttx_score_list_extents(ttx_session* s, const ttx_score_batch* h_batches, int n_batches, int eos, int32_t* d_e, int32_t* d_ls,
+                           int32_t* d_n, int32_t* d_bad, void* stream);
+int ttx_score_list_run(ttx_session* s, const ttx_score_batch* h_batches, int n_batches, const int32_t* h_order, int n_order,
+                       const ttx_score_chunk* h_chunks, int n_chunks, int eos, float* d_score, int32_t* d_length,
+                       uint8_t* d_finished, float* d_tok_logp, const int64_t* h_tok_off, void* stream);
+int ttx_debug_score_list(ttx_session* s, int op, const ttx_score_batch* h_batches, int n_batches, const int32_t* h_sel, int n_sel,
+                         const int64_t* h_tok_off, const ttx_debug_score_list_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,7 @@ LIB_PATH = PKG_DIR / "libttx_hip.so"
 # translation units (compiled in parallel, linked into one shared library) and the headers every one of them depends on
 UNITS = [CSRC / "ttx_api.hip", CSRC / "ttx_gemm.hip", CSRC / "ttx_attn.hip"]
 HEADERS = [CSRC / "ttx_internal.h", CSRC / "ttx_common.hip.h", CSRC / "ttx_loop_kernels.hip.h", CSRC / "ttx_metrics.hip.h",
-           CSRC / "ttx_score.hip.h", CSRC / "ttx_fold.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_sample.hip.h", CSRC / "ttx_logq.hip.h", CSRC / "ttx_sbs.hip.h", CSRC / "ttx_sbs_pool.hip.h",
+           CSRC / "ttx_score.hip.h", CSRC / "ttx_score_list.hip.h", CSRC / "ttx_fold.hip.h", CSRC / "ttx_alternatives.hip.h", CSRC / "ttx_attn_probs.hip.h", CSRC / "ttx_sample.hip.h", CSRC / "ttx_logq.hip.h", CSRC / "ttx_sbs.hip.h", CSRC / "ttx_sbs_pool.hip.h",
            CSRC / "ttx_proposal.hip.h", CSRC / "ttx_logit_bias.hip.h", CSRC / "ttx_syntax.hip.h", CSRC / "ttx_beam_mask.hip.h",
            CSRC / "ttx_select.h", CSRC / "ttx_tokenizer.h", CSRC / "ttx_drive.h", CSRC / "ttx_admit.h", INCLUDE / "ttx.h"]
 SOURCES = UNITS + HEADERS
@@ -186,6 +186,26 @@ class Syntax(C.Structure):
     _fields_ = [("d_cls", C.c_void_p), ("max_len", C.c_int32)]
 
 
+class ScoreBatch(C.Structure):
+    """ttx_score_batch: one (src, hyp) batch of a list scored by ttx_score_list_*; device pointers, then the shape."""
+    _fields_ = [("d_src", C.c_void_p), ("d_hyp", C.c_void_p)] + [(n, C.c_int32) for n in ("B", "Ls", "N", "W", "ld_hyp")]
+
+
+class ScoreChunk(C.Structure):
+    """ttx_score_chunk: the sources order[first : first + count] in one pass of W hypothesis and Ls source columns."""
+    _fields_ = [(n, C.c_int32) for n in ("first", "count", "N", "W", "Ls")]
+
+
+class DebugScoreListArgs(C.Structure):
+    """ttx_debug_score_list_args: the operands of one k_sl_extents / k_sl_pack / k_sl_unpack launch."""
+    POINTERS = ("d_e", "d_ls", "d_n", "d_bad", "d_src_c", "d_hyp_c", "d_score_c", "d_length_c", "d_fin_c", "d_tok_c", "d_score",
+                "d_length", "d_finished", "d_tok_logp")
+    _fields_ = [(n, C.c_void_p) for n in POINTERS] + [(n, C.c_int32) for n in ("N", "W", "Ls", "eos")]
+
+
+DEBUG_SCORE_LIST_OPS = ("extents", "pack", "unpack")     # ttx_debug_score_list's op, in order
+
+
 class DebugPrefix(C.Structure):
     """ttx_debug_prefix: the forced prefixes of a debug launch (table, row length, sources; per-row length and table row)."""
     _fields_ = [("d_tok", C.c_void_p), ("ld", C.c_int32), ("n_sources", C.c_int32), ("d_len", C.c_void_p), ("d_src", C.c_void_p)]
@@ -286,6 +306,11 @@ SYMBOLS = {
     "ttx_teacher_forced_eval": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "ttx_hypothesis_logprobs": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "ttx_score_hypotheses": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "ttx_score_list_extents": (C.c_int, [_VP, C.POINTER(ScoreBatch), _I, _I, _VP, _VP, _VP, _VP, _VP]),
+    "ttx_score_list_run": (C.c_int, [_VP, C.POINTER(ScoreBatch), _I, C.POINTER(C.c_int32), _I, C.POINTER(ScoreChunk), _I, _I, _VP, _VP,
+                                     _VP, _VP, C.POINTER(C.c_int64), _VP]),
+    "ttx_debug_score_list": (C.c_int, [_VP, _I, C.POINTER(ScoreBatch), _I, C.POINTER(C.c_int32), _I, C.POINTER(C.c_int64),
+                                       C.POINTER(DebugScoreListArgs), _VP]),
     "ttx_fold_hypotheses": (C.c_int, [_VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ttx_hypothesis_alternatives": (C.c_int, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ttx_score_alternatives": (C.c_int, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),

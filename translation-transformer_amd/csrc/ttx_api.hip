@@ -8,6 +8,7 @@
 #include "ttx_loop_kernels.hip.h"
 #include "ttx_metrics.hip.h"
 #include "ttx_score.hip.h"
+#include "ttx_score_list.hip.h"
 #include "ttx_fold.hip.h"
 #include "ttx_alternatives.hip.h"
 #include "ttx_attn_probs.hip.h"
@@ -821,6 +822,195 @@ extern "C" int ttx_score_hypotheses(ttx_session* s, const int64_t* d_src, int B,
   }
   TTX_TRY(score_forward(s, st, d_src, B, Ls, d_hyp, ld_hyp, N, W, d_logits));
   return launch_score(s, st, d_logits, d_hyp, ld_hyp, R, W, V, c.pad_token, eos, d_tok_logp, d_score, d_length, d_finished);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Length-bucketed scoring of a list of batches: csrc/ttx_score_list.hip.h around score_forward + launch_score.
+// The caller's batches, checked, as the device table: sources and rows numbered in list order.  src_batch (optional): source -> batch.
+static int sl_table(const ttx_session* s, const ttx_score_batch* h, int nb, const int64_t* h_tok_off, const char* fn,
+                    std::vector<SlBatch>& tab, int* S_out, int* R_out, std::vector<int>* src_batch) {
+  if (!h || nb < 1) return fail(TTX_ERR_INVALID, std::string(fn) + ": an empty list of batches");
+  if (s->m->cfg.vocab_size > MET_MAX_V) return fail(TTX_ERR_INVALID, std::string(fn) + ": vocabulary larger than 1024");
+  long long S = 0, R = 0;
+  tab.resize(nb);
+  for (int i = 0; i < nb; ++i) {
+    const ttx_score_batch& b = h[i];
+    if (!b.d_src || !b.d_hyp || b.B < 1 || b.N < 1 || b.Ls < 1)
+      return fail(TTX_ERR_INVALID, std::string(fn) + ": batch " + std::to_string(i) + " needs d_src, d_hyp, B >= 1, N >= 1, Ls >= 1");
+    if (b.W < 2) return fail(TTX_ERR_INVALID, std::string(fn) + ": batch " + std::to_string(i) + " has W < 2");
+    if (b.ld_hyp < b.W) return fail(TTX_ERR_INVALID, std::string(fn) + ": batch " + std::to_string(i) + " has row stride ld_hyp smaller than W");
+    SlBatch& t = tab[i];
+    t.src = b.d_src; t.hyp = b.d_hyp; t.B = b.B; t.Ls = b.Ls; t.N = b.N; t.W = b.W; t.ld_hyp = b.ld_hyp;
+    t.src0 = (int)S; t.row0 = (int)R; t.pad_ = 0; t.tok0 = h_tok_off ? (long long)h_tok_off[i] : 0;
+    if (h_tok_off && h_tok_off[i] < 0) return fail(TTX_ERR_INVALID, std::string(fn) + ": negative tok_logp offset");
+    S += b.B;
+    R += (long long)b.B * b.N;
+    if (R >= (1LL << 31) - 64) return fail(TTX_ERR_INVALID, std::string(fn) + ": more than 2^31 hypothesis rows in one list");
+    if (src_batch) src_batch->insert(src_batch->end(), (size_t)b.B, i);
+  }
+  *S_out = (int)S;
+  *R_out = (int)R;
+  return TTX_OK;
+}
+
+// the table, and `n_extra` int32 words behind it (the run order / a chunk's sources), into sl_tab by ONE stream-ordered copy
+static int sl_upload(ttx_session* s, hipStream_t st, const std::vector<SlBatch>& tab, const int32_t* extra, int n_extra,
+                     const SlBatch** d_tab, const int** d_extra) {
+  const size_t tb = tab.size() * sizeof(SlBatch), bytes = tb + (size_t)n_extra * 4;
+  std::vector<char> blob(bytes);
+  std::memcpy(blob.data(), tab.data(), tb);
+  if (n_extra) std::memcpy(blob.data() + tb, extra, (size_t)n_extra * 4);
+  TTX_TRY(ensure(s->sl_tab, bytes, st));
+  HIP_TRY(hipMemcpyAsync(s->sl_tab.p, blob.data(), bytes, hipMemcpyHostToDevice, st));   // pageable source: staged before the call returns
+  *d_tab = s->sl_tab.as<SlBatch>();
+  *d_extra = reinterpret_cast<const int*>(s->sl_tab.as<char>() + tb);
+  return TTX_OK;
+}
+
+static int sl_launch_extents(ttx_session* s, hipStream_t st, const SlBatch* d_tab, int nb, int S, int R, int eos, int32_t* d_e,
+                             int32_t* d_ls, int32_t* d_n, int32_t* d_bad) {
+  const ttx_config& c = s->m->cfg;
+  HIP_TRY(hipMemsetAsync(d_e, 0, (size_t)S * 4, st));
+  if (d_bad) HIP_TRY(hipMemsetAsync(d_bad, 0, 4, st));
+  hipLaunchKernelGGL(k_sl_extents, dim3(cdiv(R + S, 4)), dim3(256), 0, st, d_tab, nb, S, R, c.src_vocab_size, c.vocab_size, c.pad_token,
+                     eos, d_e, d_ls, d_n, d_bad);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
+}
+
+extern "C" int ttx_score_list_extents(ttx_session* s, const ttx_score_batch* h_batches, int n_batches, int eos, int32_t* d_e,
+                                      int32_t* d_ls, int32_t* d_n, int32_t* d_bad, void* stream) {
+  if (!s) return session_required("ttx_score_list_extents");
+  if (!d_e || !d_ls) return fail(TTX_ERR_INVALID, "bad argument to ttx_score_list_extents: d_e and d_ls are required");
+  std::vector<SlBatch> tab;
+  int S = 0, R = 0;
+  TTX_TRY(sl_table(s, h_batches, n_batches, nullptr, "ttx_score_list_extents", tab, &S, &R, nullptr));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->m->device));
+  const SlBatch* d_tab;
+  const int* d_none;
+  TTX_TRY(sl_upload(s, st, tab, nullptr, 0, &d_tab, &d_none));
+  return sl_launch_extents(s, st, d_tab, n_batches, S, R, eos, d_e, d_ls, d_n, d_bad);
+}
+
+static int sl_check_chunk(const ttx_session* s, const ttx_score_chunk& ch, const char* fn) {
+  const ttx_config& c = s->m->cfg;
+  if (ch.count < 1 || ch.N < 1) return fail(TTX_ERR_INVALID, std::string(fn) + ": a chunk needs count >= 1 and N >= 1");
+  if (ch.W < 2 || ch.Ls < 1) return fail(TTX_ERR_INVALID, std::string(fn) + ": a chunk needs W >= 2 and Ls >= 1");
+  if ((long long)ch.count * ch.N * (ch.W - 1) >= (1LL << 24)) return fail(TTX_ERR_INVALID, std::string(fn) + ": more than 2^24 positions in one chunk");
+  if (ch.W - 1 > c.max_positions || ch.Ls > c.max_positions) return fail(TTX_ERR_INVALID, std::string(fn) + ": a chunk wider than the positional table");
+  return TTX_OK;
+}
+
+static void sl_launch_pack(hipStream_t st, const SlBatch* d_tab, int nb, const int* d_sel, int Bc, int N, int Wc, int Lsc, int pad,
+                           int64_t* src_c, int64_t* hyp_c) {
+  hipLaunchKernelGGL(k_sl_pack, dim3(cdiv(Bc + Bc * N, 4)), dim3(256), 0, st, d_tab, nb, d_sel, Bc, N, Wc, Lsc, pad, src_c, hyp_c);
+}
+
+static void sl_launch_unpack(hipStream_t st, const SlBatch* d_tab, int nb, const int* d_sel, int Bc, int N, int Wc, const float* score_c,
+                             const int32_t* length_c, const uint8_t* fin_c, const float* tok_c, float* score, int32_t* length,
+                             uint8_t* finished, float* tok) {
+  hipLaunchKernelGGL(k_sl_unpack, dim3(cdiv(Bc * N, 4)), dim3(256), 0, st, d_tab, nb, d_sel, Bc, N, Wc, score_c, length_c, fin_c, tok_c,
+                     score, length, finished, tok);
+}
+
+extern "C" int ttx_score_list_run(ttx_session* s, const ttx_score_batch* h_batches, int n_batches, const int32_t* h_order, int n_order,
+                                  const ttx_score_chunk* h_chunks, int n_chunks, int eos, float* d_score, int32_t* d_length,
+                                  uint8_t* d_finished, float* d_tok_logp, const int64_t* h_tok_off, void* stream) {
+  const char* fn = "ttx_score_list_run";
+  if (!s) return session_required(fn);
+  if (!h_order || !h_chunks || !d_score || !d_length || n_chunks < 1)
+    return fail(TTX_ERR_INVALID, "bad argument to ttx_score_list_run: h_order, h_chunks, d_score and d_length are required");
+  if (d_tok_logp && !h_tok_off) return fail(TTX_ERR_INVALID, "ttx_score_list_run: d_tok_logp needs h_tok_off");
+  std::vector<SlBatch> tab;
+  std::vector<int> src_batch;
+  int S = 0, Rtot = 0;
+  TTX_TRY(sl_table(s, h_batches, n_batches, d_tok_logp ? h_tok_off : nullptr, fn, tab, &S, &Rtot, &src_batch));
+  if (n_order != S) return fail(TTX_ERR_INVALID, "ttx_score_list_run: the order must name every source of the list exactly once");
+  std::vector<char> seen((size_t)S, 0);
+  long long covered = 0;
+  for (int ci = 0; ci < n_chunks; ++ci) {
+    const ttx_score_chunk& ch = h_chunks[ci];
+    TTX_TRY(sl_check_chunk(s, ch, fn));
+    if (ch.first < 0 || (long long)ch.first + ch.count > n_order) return fail(TTX_ERR_INVALID, "ttx_score_list_run: a chunk reaches outside the order");
+    for (int j = ch.first; j < ch.first + ch.count; ++j) {
+      const int src = h_order[j];
+      if (src < 0 || src >= S) return fail(TTX_ERR_INVALID, "ttx_score_list_run: a source index outside the list");
+      if (seen[src]) return fail(TTX_ERR_INVALID, "ttx_score_list_run: a source is covered twice");
+      seen[src] = 1;
+      if (tab[src_batch[src]].N != ch.N) return fail(TTX_ERR_INVALID, "ttx_score_list_run: a chunk holds a source whose batch has another N");
+    }
+    covered += ch.count;
+  }
+  if (covered != S) return fail(TTX_ERR_INVALID, "ttx_score_list_run: a source is left out of every chunk");
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->m->device));
+  const ttx_config& c = s->m->cfg;
+  const int V = c.vocab_size;
+  const SlBatch* d_tab;
+  const int* d_order;
+  TTX_TRY(sl_upload(s, st, tab, h_order, n_order, &d_tab, &d_order));
+  for (int ci = 0; ci < n_chunks; ++ci) {
+    const ttx_score_chunk& ch = h_chunks[ci];
+    const int Bc = ch.count, N = ch.N, Wc = ch.W, Lsc = ch.Ls, R = Bc * N, T = Wc - 1;
+    const size_t r4 = ((size_t)R * 4 + 15) & ~(size_t)15;
+    TTX_TRY(ensure(s->sl_src, (size_t)Bc * Lsc * 8, st));
+    TTX_TRY(ensure(s->sl_hyp, (size_t)R * Wc * 8, st));
+    TTX_TRY(ensure(s->sl_res, 2 * r4 + (size_t)R, st));
+    TTX_TRY(ensure(s->ev_logits, (size_t)R * T * V * sizeof(float), st));
+    TTX_TRY(ensure(s->ev_nll, (size_t)R * T * sizeof(float), st));
+    float* score_c = s->sl_res.as<float>();
+    int32_t* length_c = reinterpret_cast<int32_t*>(s->sl_res.as<char>() + r4);
+    uint8_t* fin_c = reinterpret_cast<uint8_t*>(s->sl_res.as<char>() + 2 * r4);
+    const int* d_sel = d_order + ch.first;
+    sl_launch_pack(st, d_tab, n_batches, d_sel, Bc, N, Wc, Lsc, c.pad_token, s->sl_src.as<int64_t>(), s->sl_hyp.as<int64_t>());
+    HIP_TRY(hipGetLastError());
+    // what ttx_score_hypotheses runs, on the packed rows
+    TTX_TRY(score_forward(s, st, s->sl_src.as<int64_t>(), Bc, Lsc, s->sl_hyp.as<int64_t>(), Wc, N, Wc, s->ev_logits.as<float>()));
+    TTX_TRY(launch_score(s, st, s->ev_logits.as<float>(), s->sl_hyp.as<int64_t>(), Wc, R, Wc, V, c.pad_token, eos, s->ev_nll.as<float>(),
+                         score_c, length_c, fin_c));
+    sl_launch_unpack(st, d_tab, n_batches, d_sel, Bc, N, Wc, score_c, length_c, fin_c, s->ev_nll.as<float>(), d_score, d_length,
+                     d_finished, d_tok_logp);
+    HIP_TRY(hipGetLastError());
+  }
+  return TTX_OK;
+}
+
+extern "C" int ttx_debug_score_list(ttx_session* s, int op, const ttx_score_batch* h_batches, int n_batches, const int32_t* h_sel,
+                                    int n_sel, const int64_t* h_tok_off, const ttx_debug_score_list_args* a, void* stream) {
+  const char* fn = "ttx_debug_score_list";
+  if (!s) return session_required(fn);
+  if (!a || op < 0 || op > 2) return fail(TTX_ERR_INVALID, "bad argument to ttx_debug_score_list: op 0, 1 or 2 and its operands");
+  std::vector<SlBatch> tab;
+  std::vector<int> src_batch;
+  int S = 0, R = 0;
+  TTX_TRY(sl_table(s, h_batches, n_batches, (op == 2 && a->d_tok_logp) ? h_tok_off : nullptr, fn, tab, &S, &R, &src_batch));
+  if (op == 0) {
+    if (!a->d_e || !a->d_ls) return fail(TTX_ERR_INVALID, "ttx_debug_score_list: op 0 needs d_e and d_ls");
+  } else {
+    if (!h_sel || n_sel < 1) return fail(TTX_ERR_INVALID, "ttx_debug_score_list: ops 1 and 2 need the chunk's sources");
+    TTX_TRY(sl_check_chunk(s, ttx_score_chunk{0, n_sel, a->N, a->W, a->Ls < 1 && op == 2 ? 1 : a->Ls}, fn));
+    for (int j = 0; j < n_sel; ++j)
+      if (h_sel[j] < 0 || h_sel[j] >= S || tab[src_batch[h_sel[j]]].N != a->N)
+        return fail(TTX_ERR_INVALID, "ttx_debug_score_list: a source outside the list or of a batch with another N");
+    if (op == 1 && (!a->d_src_c || !a->d_hyp_c)) return fail(TTX_ERR_INVALID, "ttx_debug_score_list: op 1 needs d_src_c and d_hyp_c");
+    if (op == 2 && (!a->d_score_c || !a->d_length_c || !a->d_fin_c || !a->d_score || !a->d_length))
+      return fail(TTX_ERR_INVALID, "ttx_debug_score_list: op 2 needs the chunk's score, length and finished and d_score, d_length");
+    if (op == 2 && a->d_tok_logp && (!a->d_tok_c || !h_tok_off)) return fail(TTX_ERR_INVALID, "ttx_debug_score_list: d_tok_logp needs d_tok_c and h_tok_off");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(s->m->device));
+  const SlBatch* d_tab;
+  const int* d_sel;
+  TTX_TRY(sl_upload(s, st, tab, h_sel, op == 0 ? 0 : n_sel, &d_tab, &d_sel));
+  if (op == 0) return sl_launch_extents(s, st, d_tab, n_batches, S, R, a->eos, a->d_e, a->d_ls, a->d_n, a->d_bad);
+  if (op == 1)
+    sl_launch_pack(st, d_tab, n_batches, d_sel, n_sel, a->N, a->W, a->Ls, s->m->cfg.pad_token, a->d_src_c, a->d_hyp_c);
+  else
+    sl_launch_unpack(st, d_tab, n_batches, d_sel, n_sel, a->N, a->W, a->d_score_c, a->d_length_c, a->d_fin_c, a->d_tok_c, a->d_score,
+                     a->d_length, a->d_finished, a->d_tok_logp);
+  HIP_TRY(hipGetLastError());
+  return TTX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -129,6 +129,9 @@ struct GraphCache {
   /* hypothesis scoring (ttx_score_hypotheses): decoder row -> memory row; logits / per-token values it does not hand out live */ \
   /* in ev_logits / ev_nll */                                                                                                    \
   X(sc_src_of) X(am_length)                                                                                                                   \
+  /* scoring a list of batches (ttx_score_list_*): the descriptor table with the run order behind it, a chunk's packed sources and */ \
+  /* hypotheses, and its score / length / finished before they are scattered to list order */                                     \
+  X(sl_tab) X(sl_src) X(sl_hyp) X(sl_res)                                                                                         \
   /* ttx_hypothesis_logq / ttx_score_proposal: the per-token values the caller did not ask for */                                  \
   X(lq_tok)                                                                                                                      \
   /* loop */                                                                                                                     \

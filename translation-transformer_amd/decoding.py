@@ -56,6 +56,15 @@ class _ScoresHypotheses:
             raise ValueError("the generator's pad token differs from the model's")
         return self.model.score_hypotheses(src, pred, eos_token_idx=eos, **kw)
 
+    def score_many(self, batches: list, preds: list, **kw) -> list:
+        """``score`` for a list: ``preds[i]`` as ``generate_many(batches)`` returned it (None for a batch that came back None), one
+        ``HypothesisScores`` or None per batch, in list order.  The whole list is scored in length buckets with one
+        synchronisation (NativeTransformer.score_hypotheses_many, which takes the keywords)."""
+        pad, eos = self._pad_eos()
+        if pad != self.model.tgt_pad_token_i:
+            raise ValueError("the generator's pad token differs from the model's")
+        return self.model.score_hypotheses_many(batches, preds, eos_token_idx=eos, **kw)
+
     def attention(self, src: torch.Tensor, pred: torch.Tensor, **kw) -> AttentionMaps:
         """Cross-attention maps and source alignments of the hypotheses ``pred`` (Long[B, N, L] as ``generate(src)`` returned
         it), from the same teacher-forced pass as ``score``.  Keywords go to ``attention_maps``."""
@@ -134,6 +143,9 @@ class _ScoresHypotheses:
 
     def _scored_many(self, batches: list, preds: list, return_scores: bool = True, return_logq: bool = False, prefixes=None,
                      biases=None, syntax=None) -> list:
+        if return_scores and not return_logq and os.environ.get("TTX_SCORE_LIST", "1") != "0":
+            # scores alone: the whole list in length buckets, the per-batch values on the bits (TTX_SCORE_LIST=0: batch by batch)
+            return [(p, s) for p, s in zip(preds, self.score_many(batches, preds))]
         pres = prefixes if prefixes is not None else [None] * len(batches)
         bs = biases if biases is not None else [None] * len(batches)
         return [(p,) + (None,) * (int(return_scores) + int(return_logq)) if p is None

@@ -111,6 +111,10 @@ class _PredictAhead:
         self.prefixes = {}           # batch index -> the batch's "prefix_tokens" it was decoded with (sampling generators; None: none)
         self.syntax = None           # the module's syntax table (sampling generators under predict_syntax_constraint)
         self.biases = {}             # batch index -> the batch's ("logit_bias", "allowed_tokens") it was decoded with (None: none)
+        self.score_ahead = False     # also score every decoded window in one bucketed pass (generator.score_many)
+        self.scores = {}             # batch index -> the HypothesisScores of the prediction kept in `ready`
+        self.score_seconds = 0.0     # time of the windows' scoring passes that the module has not yet added to its report
+        self.kept_scores = None      # set by take(): the scores of the prediction it returned
 
     def _decode_window(self, device) -> None:
         pending, prefixes, proposals, biases, allowed = [], [], [], [], []
@@ -164,6 +168,14 @@ class _PredictAhead:
         shares = list(getattr(g, "last_batch_counters", [])) or [None] * len(pending)
         self.decode_seconds += timer() - t0
         self.windows += 1
+        if self.score_ahead:        # the whole window in length buckets; timed like the module's per-batch pass, idle on both sides
+            torch.cuda.synchronize()
+            t0 = timer()
+            scored = g.score_many(pending, preds)
+            torch.cuda.synchronize()
+            self.score_seconds += timer() - t0
+            for k, sc in enumerate(scored):
+                self.scores[self.next_idx + k] = sc
         for k, (src, pred) in enumerate(zip(pending, preds)):
             self.ready[self.next_idx + k] = (src, pred, shares[k])
             self.prefixes[self.next_idx + k] = prefixes[k]
@@ -186,6 +198,7 @@ class _PredictAhead:
     def take(self, src: torch.Tensor, batch_idx: int, prefix=None, logit_bias=None, allowed=None):
         """The prediction prepared for batch `batch_idx` (and its forced prefixes `prefix`, its `logit_bias` and `allowed`
         list), or None (decode it now)."""
+        self.kept_scores = None
         if not self.enabled:
             return None
         if batch_idx not in self.ready and batch_idx == self.next_idx:
@@ -193,6 +206,7 @@ class _PredictAhead:
         hit = self.ready.pop(batch_idx, None)
         had = self.prefixes.pop(batch_idx, None)
         had_bias = self.biases.pop(batch_idx, (None, None))
+        self.kept_scores = self.scores.pop(batch_idx, None)       # of the prediction returned below; None when it is not served
         if hit is None or hit[0].shape != src.shape or not torch.equal(hit[0], src.to(hit[0].device)) \
                 or not self._same_prefix(had, prefix) or not self._same_prefix(had_bias[0], logit_bias) \
                 or not self._same_prefix(had_bias[1], allowed):
@@ -201,6 +215,8 @@ class _PredictAhead:
             self.ready.clear()
             self.prefixes.clear()
             self.biases.clear()
+            self.scores.clear()
+            self.kept_scores = None
             self.fallbacks += 1
             return None
         if hit[1] is None:                             # the reference raises on this batch: let generate() raise it here
@@ -383,8 +399,13 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             raise ValueError(f'"logit_bias" / "allowed_tokens" in a batch: only generation="sampling", "sampling_speculative", '
                              f'"stochastic_beam_search" and "beam_search_constrained" take a logit bias, not '
                              f'"{self.hparams.generation}"')
+        kept = None                  # the batch's HypothesisScores when its window was scored ahead
         if ahead is not None and dataloader_idx == 0:
             pred = ahead.take(batch["src_tokens"], batch_idx, prefix, bias.get("logit_bias"), bias.get("allowed"))
+            kept = ahead.kept_scores if pred is not None else None
+            if self._scores_on:      # the windows' scoring passes count where the per-batch passes count
+                self._scoring_seconds += ahead.score_seconds
+            ahead.score_seconds = 0.0
         if pred is not None and self.hparams.generation in ("sampling", "sampling_speculative", "stochastic_beam_search"):
             self._predict_rows += int(batch["src_tokens"].shape[0])        # served ahead under these keys: a fallback goes on from here
         elif pred is None and self.hparams.generation in ("sampling", "sampling_speculative"):
@@ -408,12 +429,12 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         elif pred is None:
             pred = self.generator.generate(batch["src_tokens"])
         if self._fold_on:
-            return self._fold_batch(batch["src_tokens"], pred, batch_idx)
+            return self._fold_batch(batch["src_tokens"], pred, batch_idx, kept)
         both = self._logq_on and self._scores_on and self._alternatives_k <= 0     # scores and log q from ONE decoder pass
         if self._alternatives_k > 0:
             self._alternatives_batch(batch["src_tokens"], pred, batch_idx)
         elif self._scores_on and not both:
-            self._score_batch(batch["src_tokens"], pred, batch_idx)
+            self._score_batch(batch["src_tokens"], pred, batch_idx, kept)
         if self._attention_on:
             self._align_batch(batch["src_tokens"], pred, batch_idx)
         if self._logq_on:
@@ -443,14 +464,15 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
         self.predict_logq[batch_idx] = q
         self._outside = self._outside + (q.first_outside >= 0).sum()      # kept on the device until the report
 
-    def _fold_batch(self, src: torch.Tensor, pred: torch.Tensor, batch_idx: int) -> torch.Tensor:
+    def _fold_batch(self, src: torch.Tensor, pred: torch.Tensor, batch_idx: int, kept=None) -> torch.Tensor:
         """The batch's samples scored and folded, whether they were decoded ahead or on the spot: returns the folded rows
         (distinct, best first, all-PAD rows after) and keeps (count, n_unique, logmass); with scores on, the kept
         HypothesisScores are those of the folded rows, gathered by ``perm``, and hold what the scoring rule gives an all-PAD row
-        (score 0, length 0, unfinished) beyond ``n_unique``.  Timed like _score_batch."""
+        (score 0, length 0, unfinished) beyond ``n_unique``.  Timed like _score_batch.  ``kept``: the samples' scores when the
+        look-ahead scored their window (the same values; their time is counted already)."""
         torch.cuda.synchronize()
         t0 = timer()
-        sc = self.generator.score(src, pred)
+        sc = kept if kept is not None else self.generator.score(src, pred)
         torch.cuda.synchronize()
         t1 = timer()
         f = self.generator.fold(src, pred, scores=sc, order="score", unfinished="last")
@@ -468,9 +490,14 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
                                        live & sc.finished.gather(1, idx), None), batch_idx)
         return f.pred
 
-    def _score_batch(self, src: torch.Tensor, pred: torch.Tensor, batch_idx: int) -> None:
+    def _score_batch(self, src: torch.Tensor, pred: torch.Tensor, batch_idx: int, kept=None) -> None:
         """The batch's HypothesisScores, whether it was decoded ahead or on the spot; the token tensor predict_step returns
-        stays what it was.  Timed with a synchronisation on both sides, so scoring_seconds is the pass's own time."""
+        stays what it was.  Timed with a synchronisation on both sides, so scoring_seconds is the pass's own time.  ``kept``: the
+        scores the look-ahead computed with the batch's window (generator.score_many: the same values bit for bit), served as
+        they are; their time was counted when the window was scored."""
+        if kept is not None:
+            self._keep_scores(kept, batch_idx)
+            return
         torch.cuda.synchronize()
         t0 = timer()
         sc = self.generator.score(src, pred)
@@ -581,6 +608,10 @@ class VanillaEncoderDecoderTransformerLightning(LightningModule):
             if loader is not None and iter(loader) is not loader:
                 self._ahead = _PredictAhead(self.generator, loader, window, int(os.environ.get("TTX_INFLIGHT", "8")))
                 self._ahead.syntax = self._syntax
+                # scores alone (for themselves or for the fold): score every window ahead too, in one bucketed pass; log q,
+                # alternatives and attention keep their per-batch passes (TTX_SCORE_LIST=0: so do the scores)
+                self._ahead.score_ahead = (self._scores_on or self._fold_on) and not self._logq_on and self._alternatives_k <= 0 \
+                    and not self._attention_on and os.environ.get("TTX_SCORE_LIST", "1") != "0"
         if self.report_prediction_time:
             self.prediction_start_time = timer()
 

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .scheduling import score_plan
 
 
 def reference_pe_table(emb: int, max_len: int = 5000) -> torch.Tensor:
@@ -383,6 +384,28 @@ class NativeTransformer:
                                                self._ptr(mem_row), length.data_ptr(), R, Rm, int(heads), int(head_dim), int(T), int(Ls),
                                                float(scale), self._ptr(out_heads), self._ptr(out_mean), self._ptr(out_align),
                                                self._stream()))
+
+    @staticmethod
+    def score_batch_table(batches: list):
+        """The ttx_score_batch array of ``batches``: (src, hyp, N, W) per batch with ``src`` int64 [B, Ls] contiguous and ``hyp``
+        int64 [B*N, >= W] whose row stride is ld_hyp (a view is fine); device tensors, borrowed."""
+        table = (N.ScoreBatch * len(batches))()
+        for i, (src, hyp, K, W) in enumerate(batches):
+            assert src.is_contiguous() and hyp.stride(1) == 1 and hyp.shape[0] == src.shape[0] * K
+            table[i] = N.ScoreBatch(src.data_ptr(), hyp.data_ptr(), int(src.shape[0]), int(src.shape[1]), int(K), int(W), int(hyp.stride(0)))
+        return table
+
+    def debug_score_list(self, op: str, batches: list, sel=None, tok_off=None, n: int = 0, w: int = 0, ls: int = 0, eos: int = 2,
+                         **arrays) -> None:
+        """ONE launch of k_sl_extents / k_sl_pack / k_sl_unpack (``op``: "extents", "pack", "unpack") on the caller's device
+        tensors (ttx_debug_score_list).  ``batches`` as ``score_batch_table`` takes them; ``sel``: the chunk's sources (indices in
+        list order), ``n`` / ``w`` / ``ls`` the chunk's rows per source and widths; ``tok_off``: per batch its offset into
+        ``d_tok_logp``, in floats; ``arrays``: the fields of ttx_debug_score_list_args by name (``d_e=...``), tensors or None."""
+        a = N.DebugScoreListArgs(N=int(n), W=int(w), Ls=int(ls), eos=int(eos), **{k: self._ptr(v) for k, v in arrays.items()})
+        h_sel = None if sel is None else (C.c_int32 * len(sel))(*[int(x) for x in sel])
+        h_off = None if tok_off is None else (C.c_int64 * len(tok_off))(*[int(x) for x in tok_off])
+        N.check(self._lib.ttx_debug_score_list(self._scoring_session(), N.DEBUG_SCORE_LIST_OPS.index(op), self.score_batch_table(batches),
+                                               len(batches), h_sel, 0 if sel is None else len(sel), h_off, C.byref(a), self._stream()))
 
     @staticmethod
     def attn_probs_key_limit(head_dim: int) -> int:
@@ -1071,6 +1094,71 @@ class NativeTransformer:
             if part is not None and Wt != W:
                 tok[b0:b1, :, :Wt - 1] = part
         return HypothesisScores(score, length, fin, tok)
+
+    def score_hypotheses_many(self, srcs: list, hyps: list, eos_token_idx: int = 2, return_token_logp: bool = False,
+                              max_rows: int | None = None) -> list:
+        """``score_hypotheses(srcs[i], hyps[i], eos_token_idx, return_token_logp)`` for every batch of a list, in list order, in
+        length buckets (ttx_score_list_extents / ttx_score_list_run): the sources of the whole list are sorted by their
+        hypotheses' and their own non-PAD extent (``scheduling.score_plan``) and scored in chunks of at most ``max_rows``
+        decoder positions (default ``SCORE_MAX_ROWS``; swept in DESIGN.md §30), each chunk at the widths of its own longest member, so that neither
+        hypothesis nor source columns that are PAD in almost every row are run.  Shapes may differ from batch to batch; an entry
+        whose ``hyp`` is None gives None.  The values are those of the per-batch calls bit for bit while sources and hypotheses
+        stay within the attention kernels' staged key range (384 positions, 320 at head dimension 64).  ONE device-to-host read
+        (the extents, with the token-id check riding on it) is the call's only synchronisation; the results of a call share one
+        allocation per field."""
+        if len(srcs) != len(hyps):
+            raise ValueError(f"score_hypotheses_many needs one hyp (or None) per src, got {len(hyps)} for {len(srcs)}")
+        out = [None] * len(hyps)
+        live = [i for i, h in enumerate(hyps) if h is not None]
+        if not live:
+            return out
+        eos = int(eos_token_idx)
+        keep, shapes = [], []                                  # the converted tensors stay alive until the call has been enqueued
+        table = (N.ScoreBatch * len(live))()
+        for j, i in enumerate(live):
+            src, hyp = self._tokens(srcs[i]), self._tokens(hyps[i])
+            if src.dim() != 2 or hyp.dim() != 3 or hyp.shape[0] != src.shape[0] or hyp.shape[1] < 1 or hyp.shape[2] < 2 \
+                    or src.shape[0] < 1 or src.shape[1] < 1:
+                raise ValueError(f"score_hypotheses_many needs hyp [B, N >= 1, W >= 2] for src [B >= 1, Ls >= 1]; batch {i} has "
+                                 f"{tuple(hyp.shape)} for {tuple(src.shape)}")
+            (B, Ls), (_, K, W) = src.shape, hyp.shape
+            keep.append((src, hyp))
+            shapes.append((B, K, W))
+            table[j] = N.ScoreBatch(src.data_ptr(), hyp.data_ptr(), B, Ls, K, W, W)
+        S = sum(B for B, _, _ in shapes)
+        rows = np.cumsum([0] + [B * K for B, K, _ in shapes])
+        toks = np.cumsum([0] + [B * K * (W - 1) for B, K, W in shapes])
+        R = int(rows[-1])
+        sess, stream = self._scoring_session(), self._stream()
+        ext = torch.empty(2 * S + 1, dtype=torch.int32, device=self.device)          # e, ls, the token-id flags
+        N.check(self._lib.ttx_score_list_extents(sess, table, len(live), eos, ext.data_ptr(), ext[S:].data_ptr(), None,
+                                                 ext[2 * S:].data_ptr(), stream))
+        host = ext.cpu().numpy()                                                     # the call's one synchronisation
+        if host[2 * S]:
+            raise IndexError("index out of range in self")
+        limit = min(int(max_rows or self.SCORE_MAX_ROWS), (1 << 24) - 1)
+        if limit < 1:
+            raise ValueError(f"max_rows must be at least 1, got {max_rows}")
+        plan = score_plan(np.repeat([K for _, K, _ in shapes], [B for B, _, _ in shapes]), host[:S], host[S:2 * S], limit)
+        order = np.ascontiguousarray(np.concatenate([c.sources for c in plan]), dtype=np.int32)
+        chunks, first = (N.ScoreChunk * len(plan))(), 0
+        for c, ch in enumerate(plan):
+            chunks[c] = N.ScoreChunk(first, len(ch.sources), ch.N, ch.W, ch.Ls)
+            first += len(ch.sources)
+        score = torch.empty(R, dtype=torch.float32, device=self.device)
+        length = torch.empty(R, dtype=torch.int32, device=self.device)
+        fin = torch.empty(R, dtype=torch.bool, device=self.device)
+        tok = torch.empty(int(toks[-1]), dtype=torch.float32, device=self.device) if return_token_logp else None
+        tok_off = (C.c_int64 * len(live))(*[int(t) for t in toks[:-1]])
+        N.check(self._lib.ttx_score_list_run(sess, table, len(live), order.ctypes.data_as(C.POINTER(C.c_int32)), S, chunks, len(plan),
+                                             eos, score.data_ptr(), length.data_ptr(), fin.data_ptr(), self._ptr(tok),
+                                             tok_off if tok is not None else None, stream))
+        self.last_score_plan = plan                            # for tools and tests: the chunks the last call ran
+        for j, i in enumerate(live):
+            (B, K, W), r0, r1 = shapes[j], int(rows[j]), int(rows[j + 1])
+            out[i] = HypothesisScores(score[r0:r1].view(B, K), length[r0:r1].view(B, K), fin[r0:r1].view(B, K),
+                                      None if tok is None else tok[int(toks[j]):int(toks[j + 1])].view(B, K, W - 1))
+        return out
 
     # -- folding hypotheses into their distinct ones ---------------------------------------------
     def fold_hypotheses(self, hyp: torch.Tensor, scores=None, order: str = "score", unfinished: str = "keep", gather: bool = True,

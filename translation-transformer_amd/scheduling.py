@@ -133,3 +133,51 @@ def replay_beam_batch(trace_len: np.ndarray, summary: np.ndarray, max_len: int, 
     acc = int(summary[:, 4].sum())
     return BeamBatchReplay(None, T, width, acc, acc + int(summary[:, 5].sum()),
                            int(summary[:, 2].sum() + ((T - T_s) * n_best).sum()), int(summary[:, 3].sum()))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Part 3 — scoring a list of batches in length buckets (ttx_score_list_run).
+#
+# A teacher-forced pass costs (sources x rows per source x hypothesis columns) decoder positions and (sources x source columns)
+# encoder positions, both at the widths of the LONGEST member.  Sources of one N sorted by their hypothesis extent, then by their
+# source extent, and cut into chunks of at most `max_rows` decoder positions, run each chunk at widths close to every member's own.
+# The plan reads lengths alone: the same lengths give the same plan, whatever the tokens are.
+
+@dataclass
+class ScoreChunk:
+    sources: np.ndarray       # int32 [count]: the chunk's sources, indices in list order, ascending by (e, ls, index)
+    N: int                    # hypothesis rows per source (one N per chunk)
+    W: int                    # hypothesis columns of the pass: the largest e of the chunk
+    Ls: int                   # source columns of the pass: the largest ls of the chunk
+
+    @property
+    def positions(self) -> int:
+        return len(self.sources) * self.N * (self.W - 1)
+
+
+def score_plan(N_of, e, ls, max_rows: int) -> list:
+    """The chunks of one bucketed scoring call, in the order they run.  ``N_of``, ``e``, ``ls``: int [S] per source of the list —
+    its batch's rows per source, its hypothesis extent ``max(2, 1 + longest scored length)`` and its source extent
+    ``max(1, 1 + last non-PAD column)``.  Sources are sorted by (N, e, ls, index) and cut greedily so that a chunk holds one N and
+    ``count * N * (W - 1) <= max_rows`` with W the chunk's largest e (a single source is never split, so a chunk of one source may
+    exceed the bound).  The chunks are returned largest first (decoder positions, then the sort order), so that workspaces sized by
+    a chunk are sized once."""
+    N_of, e, ls = (np.asarray(a).astype(np.int64).reshape(-1) for a in (N_of, e, ls))
+    S = N_of.shape[0]
+    if S < 1 or e.shape[0] != S or ls.shape[0] != S:
+        raise ValueError(f"score_plan needs N_of, e and ls of one length >= 1, got {N_of.shape[0]}, {e.shape[0]}, {ls.shape[0]}")
+    if (N_of < 1).any() or (e < 2).any() or (ls < 1).any():
+        raise ValueError("score_plan needs N >= 1, e >= 2 and ls >= 1 for every source")
+    max_rows = int(max_rows)
+    if max_rows < 1:
+        raise ValueError(f"max_rows must be at least 1, got {max_rows}")
+    order = np.lexsort((np.arange(S), ls, e, N_of))                # last key first: (N, e, ls, index)
+    chunks, start = [], 0
+    for j in range(1, S + 1):
+        # e ascends inside one N, so the chunk's W is its last member's e: close the chunk before the member that breaks the bound
+        if j == S or N_of[order[j]] != N_of[order[start]] or (j + 1 - start) * N_of[order[j]] * (e[order[j]] - 1) > max_rows:
+            sel = order[start:j]
+            chunks.append(ScoreChunk(sel.astype(np.int32), int(N_of[sel[0]]), int(e[sel].max()), int(ls[sel].max())))
+            start = j
+    rank = sorted(range(len(chunks)), key=lambda c: (-chunks[c].positions, c))
+    return [chunks[c] for c in rank]
