@@ -302,6 +302,14 @@ int ttx_greedy_speculative_generate(ttx_session* s, const int64_t* d_src, int B,
 int ttx_greedy_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_gen_params* p,
                         int64_t* d_out, ttx_gen_stats* stats, void* stream);
 
+/* The forms of a sampling call.  Every option of the sampling, stochastic beam search and log q calls (forced prefix, proposal, logit
+ * bias, syntax table, filter) arrived with an entry point of its own, and entry points are added, never changed.  Per family the
+ * last one is the GENERAL form and takes everything the others take: ttx_sample_generate_syntax,
+ * ttx_sample_speculative_generate_syntax, ttx_sample_speculative_generate_pool_syntax (one ttx_sample_opts, one ttx_syntax),
+ * ttx_sbs_generate_bias, ttx_beam_generate_constrained, ttx_hypothesis_logq_syntax, ttx_score_proposal_syntax.  Every other form of
+ * a family IS its general form with the fields it does not name zeroed (a null opts, a null d_bias, a null syntax or d_cls, a null
+ * filter, null lengths): the same checks, the same launches, the same bits.  A new binding needs the general forms alone. */
+
 /* Seeded ancestral sampling: temperature, top-k and top-p (nucleus) on the device. */
 typedef struct ttx_sample_params {
   int32_t max_len, num_samples;          /* n >= 1 samples per source */

@@ -185,6 +185,12 @@ class Syntax(C.Structure):
     """ttx_syntax: the class table (int8 [V] on the device) and the maximal length of the rule."""
     _fields_ = [("d_cls", C.c_void_p), ("max_len", C.c_int32)]
 
+    @classmethod
+    def arg(cls, d_cls=None, max_len: int = 0):
+        """The ``syntax`` argument of a call: a reference to the struct for the int8 device tensor ``d_cls`` [V] (which the caller
+        keeps alive until the call returns), or ``None`` (a NULL pointer: the unconstrained call) without a table."""
+        return None if d_cls is None else C.byref(cls(d_cls.data_ptr(), int(max_len)))
+
 
 class ScoreBatch(C.Structure):
     """ttx_score_batch: one (src, hyp) batch of a list scored by ttx_score_list_*; device pointers, then the shape."""

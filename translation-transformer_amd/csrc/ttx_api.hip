@@ -1307,44 +1307,12 @@ static int launch_syntax_mask(hipStream_t st, const SyntaxArgs& a, bool step) {
   return TTX_OK;
 }
 
-// The syntax argument of a call whose rows have `max_len` columns and whose vocabulary is the session's, or TTX_ERR_INVALID: a null
-// struct or a null table is the unconstrained call; max_len is 0 (the call's) or the call's.
-static int syntax_validate(const char* who, const ttx_syntax* syn, int max_len, const signed char** cls) {
-  *cls = nullptr;
-  if (!syn || !syn->d_cls) return TTX_OK;
-  if (syn->max_len != 0 && syn->max_len != max_len)
-    return fail(TTX_ERR_INVALID, std::string(who) + ": ttx_syntax.max_len must be 0 or the call's max_len");
-  *cls = reinterpret_cast<const signed char*>(syn->d_cls);
-  return TTX_OK;
-}
-
-// The class table of a constrained call into the session's copy, int8 [V]: a captured step reads the session's buffer and nothing of
-// the caller's.  Enqueued outside capture, before the first step.
-static int syntax_upload(ttx_session* s, hipStream_t st, const signed char* d_cls) {
-  HIP_TRY(hipMemcpyAsync(s->syn_cls.p, d_cls, (size_t)s->m->cfg.vocab_size, hipMemcpyDeviceToDevice, st));
-  return TTX_OK;
-}
-
 // k_logit_bias with k_sample's launch shape, in place on `a.logits`; `step`: the step-row layout (act_idx, row_map, N, D set).
 static int launch_logit_bias(hipStream_t st, const LogitBiasArgs& a, bool step) {
   const dim3 grid(cdiv(a.M, 4)), block(256);
   if (step) hipLaunchKernelGGL((k_logit_bias<true>), grid, block, 0, st, a);
   else hipLaunchKernelGGL((k_logit_bias<false>), grid, block, 0, st, a);
   HIP_TRY(hipGetLastError());
-  return TTX_OK;
-}
-
-// The bias of a call over S sources into the session's table, float [S][V] (the row length is the vocabulary, which no key needs to
-// hold): a captured step reads the session's buffer and nothing of the caller's.  Enqueued outside capture, before the first step.
-static int bias_upload(ttx_session* s, hipStream_t st, const float* d_bias, int ld_bias, int S) {
-  const size_t row = (size_t)s->m->cfg.vocab_size * sizeof(float);
-  HIP_TRY(hipMemcpy2DAsync(s->lb_val.p, row, d_bias, (size_t)ld_bias * sizeof(float), row, (size_t)S, hipMemcpyDeviceToDevice, st));
-  return TTX_OK;
-}
-
-// The bias arguments of a generate call, or TTX_ERR_INVALID (the values are the caller's to keep finite or -inf: they live on the device).
-static int bias_validate(const char* who, const ttx_session* s, const float* d_bias, int ld_bias) {
-  if (d_bias && ld_bias < s->m->cfg.vocab_size) return fail(TTX_ERR_INVALID, std::string(who) + ": ld_bias must be at least the vocabulary");
   return TTX_OK;
 }
 
@@ -1932,23 +1900,33 @@ static int gen_finish_collect(GenJob& j) {
   return TTX_OK;
 }
 
-// The sampling loop's additions to a greedy generate call (ttx_sample_generate): B counts decoder rows, n of them per source.
+// The sampling loop's additions to a greedy generate call (ttx_sample_generate): B counts decoder rows, n of them per source; and
+// the one host-side record of a call's constraints (constraints_validate fills them; the beam loops read nothing else of it).
 struct SampleSetup {
   int n;
   const int64_t* d_row_keys;       // [B / n] or null
   SampleBlock blk;
   bool spec;                       // ttx_sample_speculative_generate: the speculative loop with k_sample_step and k_sample_accept
-  // forced prefixes (prefix_validate); prompted false: the call is the unprompted one, launch for launch
+  // forced prefixes; prompted false: the call is the unprompted one, launch for launch
   bool prompted;
   const int64_t* d_prefix; int ld_prefix; const int32_t* h_prefix_len; int n_sources;
-  // proposal drafts (proposal_validate): the table rides in the prefix fields above and through the same workspaces, since a call is
-  // either prompted or proposed; proposed false: no proposal, launch for launch
+  // proposal drafts: the table rides in the prefix fields above and through the same workspaces, since a call is either prompted
+  // or proposed; proposed false: no proposal, launch for launch
   bool proposed; int prop_ctx;
   bool tabled() const { return prompted || proposed; }
-  // per-source logit bias (bias_validate): d_bias null is the unbiased call, launch for launch; [n_sources][ld_bias]
+  // per-source logit bias: d_bias null is the unbiased call, launch for launch; [n_sources][ld_bias]
   const float* d_bias; int ld_bias;
-  // syntax constraint (syntax_validate): the caller's class table int8 [V] on the device, null for the unconstrained call
+  // syntax constraint: the caller's class table int8 [V] on the device, null for the unconstrained call
   const signed char* d_syntax;
+  bool any() const { return tabled() || d_bias || d_syntax; }
+};
+
+// The names a call's refusals carry.  The feature that introduced an argument named its refusals after its own entry point, so a body
+// behind several forms keeps up to four: `call` for the loop's parameters, `ex` for prefix, proposal and filter, `bias`, `syntax`.
+struct Who {
+  const char* call; const char* ex; const char* bias; const char* syntax;
+  Who(const char* w) : call(w), ex(w), bias(w), syntax(w) {}
+  Who(const char* c, const char* e, const char* b, const char* y) : call(c), ex(e), bias(b), syntax(y) {}
 };
 
 // The prefix arguments of a sampling call over S sources, or TTX_ERR_INVALID.  A call whose lengths are all zero (or absent) is
@@ -1968,53 +1946,93 @@ static int prefix_validate(const char* who, const int64_t* d_prefix, int ld_pref
   return TTX_OK;
 }
 
-// The proposal arguments of a speculative sampling call, after prefix_validate: the same refusals, and a call that carries both a
-// non-empty prefix and a non-empty proposal is refused.  A proposed call keeps its table in the prefix fields of `smp`.  The context
-// length is PROPOSAL_CTX; TTX_PROPOSAL_CTX (2, 4 or 8, read per call) overrides it for measurements and changes no output.
-static int proposal_validate(const char* who, const int64_t* d_proposal, int ld_proposal, const int32_t* h_proposal_len, int S,
-                             int max_len, SampleSetup* smp) {
+// The constraints of a call over `n_sources` sources whose rows have `max_len` columns into `smp`, or TTX_ERR_INVALID; nothing of
+// `smp` but its constraint fields is touched.  In order: the bias (ld_bias at least the vocabulary; the values are the caller's to
+// keep finite or -inf, they live on the device), the syntax table (a null struct or a null table is the unconstrained call; its
+// max_len is 0 or the call's), the prefix, and the proposal, which is held to a prefix's limits and refused beside a non-empty prefix.
+// A proposed call keeps its table in the prefix fields.  The proposal's context length is PROPOSAL_CTX; TTX_PROPOSAL_CTX (2, 4 or 8,
+// read per call) overrides it for measurements and changes no output.  A zeroed `o` and a null `syn` leave `smp` unconstrained.
+static int constraints_validate(const Who& who, const ttx_session* s, const ttx_sample_opts& o, const ttx_syntax* syn, int n_sources,
+                                int max_len, SampleSetup* smp) {
+  if (o.d_bias && o.ld_bias < s->m->cfg.vocab_size) return fail(TTX_ERR_INVALID, std::string(who.bias) + ": ld_bias must be at least the vocabulary");
+  smp->d_bias = o.d_bias; smp->ld_bias = o.ld_bias; smp->d_syntax = nullptr;
+  if (syn && syn->d_cls) {
+    if (syn->max_len != 0 && syn->max_len != max_len)
+      return fail(TTX_ERR_INVALID, std::string(who.syntax) + ": ttx_syntax.max_len must be 0 or the call's max_len");
+    smp->d_syntax = reinterpret_cast<const signed char*>(syn->d_cls);
+  }
+  TTX_TRY(prefix_validate(who.ex, o.d_prefix, o.ld_prefix, o.h_prefix_len, n_sources, max_len, smp));
   smp->proposed = false; smp->prop_ctx = PROPOSAL_CTX;
-  if (!h_proposal_len) return TTX_OK;
+  if (!o.h_proposal_len) return TTX_OK;
   SampleSetup q{};
-  const std::string who_q = std::string(who) + " (the proposal, held to a prefix's limits)";
-  TTX_TRY(prefix_validate(who_q.c_str(), d_proposal, ld_proposal, h_proposal_len, S, max_len, &q));
+  const std::string who_q = std::string(who.ex) + " (the proposal, held to a prefix's limits)";
+  TTX_TRY(prefix_validate(who_q.c_str(), o.d_proposal, o.ld_proposal, o.h_proposal_len, n_sources, max_len, &q));
   if (!q.prompted) return TTX_OK;
-  if (smp->prompted) return fail(TTX_ERR_INVALID, std::string(who) + ": a call takes forced prefixes or proposals, not both");
-  smp->d_prefix = d_proposal; smp->ld_prefix = ld_proposal; smp->h_prefix_len = h_proposal_len; smp->n_sources = S;
+  if (smp->prompted) return fail(TTX_ERR_INVALID, std::string(who.ex) + ": a call takes forced prefixes or proposals, not both");
+  smp->d_prefix = o.d_proposal; smp->ld_prefix = o.ld_proposal; smp->h_prefix_len = o.h_proposal_len;
   smp->proposed = true;
   if (const char* e = getenv("TTX_PROPOSAL_CTX")) {
     const int c = atoi(e);
-    if (c != 2 && c != 4 && c != 8) return fail(TTX_ERR_INVALID, std::string(who) + ": TTX_PROPOSAL_CTX must be 2, 4 or 8");
+    if (c != 2 && c != 4 && c != 8) return fail(TTX_ERR_INVALID, std::string(who.ex) + ": TTX_PROPOSAL_CTX must be 2, 4 or 8");
     smp->prop_ctx = c;
   }
   return TTX_OK;
 }
 
-// The session's prefix table of a prompted call, int32 [S][max_len], and the sources' lengths on the device.  The row length is
-// max_len, which every step key holds, and the buffers are the session's, so a captured step holds nothing of the call.
-static int prefix_upload(ttx_session* s, hipStream_t st, const SampleSetup& smp, int max_len, int pad) {
-  const int S = smp.n_sources;
-  HIP_TRY(hipMemcpyAsync(s->pfx_len_src.p, smp.h_prefix_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_prefix_load, dim3(cdiv(S * max_len, 256)), dim3(256), 0, st, smp.d_prefix, smp.ld_prefix, s->pfx_len_src.as<int>(),
-                     s->pfx_tok.as<int>(), S, max_len, pad);
-  HIP_TRY(hipGetLastError());
+// The session buffers of a call's constraints, sized before anything is captured and before the loop's start settles which graphs
+// are current: the table of prefixes (or proposals) int32 [sources][max_len] with the sources' lengths, `rows` per-row lengths and
+// `draft0` saved first-draft tokens (the samplers' rows or slots; 0 where the table goes by source), the bias float [sources][V],
+// the class table int8 [V], and `src_of` entries of the row-to-source map smp_src_of (the samplers' rows; the sources of a prompted
+// beam loop; 0 for the pools, whose slots keep maps of their own).
+static int constraints_ensure(ttx_session* s, hipStream_t st, const SampleSetup& c, int max_len, size_t rows, size_t draft0, size_t src_of) {
+  const size_t S = c.n_sources, V = s->m->cfg.vocab_size;
+  if (c.tabled()) {
+    TTX_TRY(ensure(s->pfx_tok, S * max_len * 4, st));
+    TTX_TRY(ensure(s->pfx_len_src, S * 4, st));
+    TTX_TRY(ensure(s->pfx_len, rows * 4, st));
+    TTX_TRY(ensure(s->pfx_draft0, draft0 * 4, st));
+  }
+  if (c.d_bias) TTX_TRY(ensure(s->lb_val, S * V * sizeof(float), st));
+  if (c.d_syntax) TTX_TRY(ensure(s->syn_cls, V, st));
+  return ensure(s->smp_src_of, src_of * 4, st);
+}
+
+// What the steps of a constrained loop read, in the session's copies; pfx.tok, bias.val, syntax: null for a call without that one.
+struct ConstraintTabs { PrefixTab pfx{}; LogitBiasTab bias{}; const signed char* syntax = nullptr; };
+
+// The caller's bias, class table and prefix (or proposal) table into the session's copies, so that a captured step reads the session's
+// buffers and nothing of the call; enqueued outside capture, before the first step.  The row length of the bias is the vocabulary and
+// that of the prefix table max_len, which every step key holds.  How a decoder row finds its source differs per loop and is the
+// caller's: `pfx_len` and `pfx_src` (the rows' prefix lengths and table rows) and `bias_src`, device arrays the loop fills.
+static int constraints_upload(ttx_session* s, hipStream_t st, const SampleSetup& c, int max_len, int pad, const int* pfx_len,
+                              const int* pfx_src, const int* bias_src, ConstraintTabs* t) {
+  const int S = c.n_sources, V = s->m->cfg.vocab_size;
+  *t = ConstraintTabs{};
+  if (c.d_bias) {
+    HIP_TRY(hipMemcpy2DAsync(s->lb_val.p, (size_t)V * sizeof(float), c.d_bias, (size_t)c.ld_bias * sizeof(float), (size_t)V * sizeof(float),
+                             (size_t)S, hipMemcpyDeviceToDevice, st));
+    t->bias = LogitBiasTab{s->lb_val.as<float>(), V, bias_src};
+  }
+  if (c.d_syntax) {
+    HIP_TRY(hipMemcpyAsync(s->syn_cls.p, c.d_syntax, (size_t)V, hipMemcpyDeviceToDevice, st));
+    t->syntax = s->syn_cls.as<signed char>();
+  }
+  if (c.tabled()) {
+    HIP_TRY(hipMemcpyAsync(s->pfx_len_src.p, c.h_prefix_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_prefix_load, dim3(cdiv(S * max_len, 256)), dim3(256), 0, st, c.d_prefix, c.ld_prefix, s->pfx_len_src.as<int>(),
+                       s->pfx_tok.as<int>(), S, max_len, pad);
+    HIP_TRY(hipGetLastError());
+    t->pfx = PrefixTab{s->pfx_tok.as<int>(), max_len, pfx_len, pfx_src};
+  }
   return TTX_OK;
 }
 
 // Session buffers of the sampling loop, sized before anything is captured.
 static int sample_ensure(ttx_session* s, hipStream_t st, size_t rows, const SampleSetup& smp, const ttx_gen_params* p) {
-  if (smp.tabled()) {
-    TTX_TRY(ensure(s->pfx_tok, (size_t)smp.n_sources * p->max_len * 4, st));
-    TTX_TRY(ensure(s->pfx_len_src, (size_t)smp.n_sources * 4, st));
-    TTX_TRY(ensure(s->pfx_len, rows * 4, st));
-    if (smp.spec) TTX_TRY(ensure(s->pfx_draft0, rows * p->draft_len * 4, st));
-  }
-  if (smp.d_bias) TTX_TRY(ensure(s->lb_val, (size_t)smp.n_sources * s->m->cfg.vocab_size * sizeof(float), st));
-  if (smp.d_syntax) TTX_TRY(ensure(s->syn_cls, (size_t)s->m->cfg.vocab_size, st));
+  TTX_TRY(constraints_ensure(s, st, smp, p->max_len, rows, smp.spec ? rows * p->draft_len : 0, rows));
   TTX_TRY(ensure(s->smp_key, rows * 8, st));
   TTX_TRY(ensure(s->smp_sample, rows * 4, st));
   TTX_TRY(ensure(s->smp_done, rows * 4, st));
-  TTX_TRY(ensure(s->smp_src_of, rows * 4, st));
   return ensure(s->smp_prm, sizeof(SampleBlock), st);
 }
 
@@ -2034,27 +2052,20 @@ static int sample_begin(GenJob& j, const SampleSetup& smp) {
   k.want_sample_step = smp.spec;
   k.sample.key = s->smp_key.as<unsigned long long>(); k.sample.sample = s->smp_sample.as<unsigned>();
   k.sample.done = s->smp_done.as<int>(); k.sample.front = s->front.as<int>(); k.sample.prm = s->smp_prm.as<SampleBlock>();
+  ConstraintTabs t;                                  // decoder row -> source: the map k_sample_init wrote
+  TTX_TRY(constraints_upload(s, j.st, smp, k.max_len, k.p.pad_token, s->pfx_len.as<int>(), k.src_of, k.src_of, &t));
+  k.bias = t.bias; k.syntax = t.syntax;
   if (smp.tabled()) {
-    TTX_TRY(prefix_upload(s, j.st, smp, k.max_len, k.p.pad_token));
     hipLaunchKernelGGL(k_prefix_rows, dim3(cdiv(R, 256)), dim3(256), 0, j.st, s->pfx_len_src.as<int>(), s->smp_src_of.as<int>(),
                        s->pfx_len.as<int>(), R);
     HIP_TRY(hipGetLastError());
-    const PrefixTab tab{s->pfx_tok.as<int>(), k.max_len, s->pfx_len.as<int>(), s->smp_src_of.as<int>()};
-    if (smp.proposed) { k.prop = tab; k.prop_ctx = smp.prop_ctx; }      // offered: the sampling kernels see no table
-    else k.sample.pfx = tab;
+    if (smp.proposed) { k.prop = t.pfx; k.prop_ctx = smp.prop_ctx; }      // offered: the sampling kernels see no table
+    else k.sample.pfx = t.pfx;
     if (smp.spec) {                                  // draft 0 of every row as gen_start left it, before any step rewrites it
       HIP_TRY(hipMemcpy2DAsync(s->pfx_draft0.p, (size_t)k.D * 4, s->drafts.p, (size_t)k.N * k.D * 4, (size_t)k.D * 4, (size_t)R,
                                hipMemcpyDeviceToDevice, j.st));
       k.pfx_draft0 = s->pfx_draft0.as<int>();
     }
-  }
-  if (smp.d_bias) {                                  // decoder row -> source: the map k_sample_init wrote
-    TTX_TRY(bias_upload(s, j.st, smp.d_bias, smp.ld_bias, smp.n_sources));
-    k.bias = LogitBiasTab{s->lb_val.as<float>(), s->m->cfg.vocab_size, s->smp_src_of.as<int>()};
-  }
-  if (smp.d_syntax) {
-    TTX_TRY(syntax_upload(s, j.st, smp.d_syntax));
-    k.syntax = s->syn_cls.as<signed char>();
   }
   return TTX_OK;
 }
@@ -2103,7 +2114,7 @@ static int generate_batches(ttx_session** sessions, int n_sessions, int n_batche
 
 // A single-session generate call: one session, one batch.
 static int generate_one(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_gen_params* p, int64_t* d_out,
-                        ttx_gen_stats* stats, void* stream, bool greedy, const SampleSetup* smp = nullptr) {
+                        ttx_gen_stats* stats, void* stream, bool greedy, const SampleSetup* smp) {
   TTX_TRY(gen_validate(s, d_src, B, Ls, p, d_out, greedy));
   return generate_batches(&s, 1, 1, &d_src, &B, &Ls, p, &d_out, nullptr, nullptr, stats, stream, greedy, smp);
 }
@@ -2111,12 +2122,12 @@ static int generate_one(ttx_session* s, const int64_t* d_src, int B, int Ls, con
 extern "C" int ttx_greedy_speculative_generate(ttx_session* s, const int64_t* d_src, int B, int Ls,
                                                const ttx_gen_params* p, int64_t* d_out, ttx_gen_stats* stats,
                                                void* stream) {
-  return generate_one(s, d_src, B, Ls, p, d_out, stats, stream, false);
+  return generate_one(s, d_src, B, Ls, p, d_out, stats, stream, false, nullptr);
 }
 
 extern "C" int ttx_greedy_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_gen_params* p,
                                    int64_t* d_out, ttx_gen_stats* stats, void* stream) {
-  return generate_one(s, d_src, B, Ls, p, d_out, stats, stream, true);
+  return generate_one(s, d_src, B, Ls, p, d_out, stats, stream, true, nullptr);
 }
 
 // The SampleBlock of a call, or TTX_ERR_INVALID: temperature >= 0 and finite (0: greedy), top_k 0 or 1..32, top_p in (0, 1].  A call
@@ -2206,14 +2217,17 @@ static int syntax_validate_scored(const char* who, const ttx_syntax* syn, int W,
   return TTX_OK;
 }
 
+// The constraints of a scoring call: the bias [R / N][ld_bias] of N hypothesis rows per source and the syntax argument, null for none.
+struct ScoreConstraints { const float* d_bias; int ld_bias; int N; const ttx_syntax* syntax; };
+
 static int hypothesis_logq(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad, int eos,
-                           const ttx_dist* dist, const int32_t* d_forced_len, float* d_tok_logq, float* d_logq,
-                           int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept, int32_t* d_length,
-                           uint8_t* d_finished, void* stream, const float* d_bias, int ld_bias, int N, const ttx_syntax* syn = nullptr) {
+                           const ttx_dist* dist, const int32_t* d_forced_len, const ScoreConstraints& c, const LogqOut& o, void* stream) {
   if (!s) return session_required("ttx_hypothesis_logq");
+  const float* d_bias = c.d_bias;
+  const int ld_bias = c.ld_bias, N = c.N;
   const signed char* cls; int syn_len;
-  TTX_TRY(syntax_validate_scored("ttx_hypothesis_logq_syntax", syn, W, &cls, &syn_len));
-  if (!d_logits || !d_hyp || !d_logq || !d_length) return fail(TTX_ERR_INVALID, "bad argument to ttx_hypothesis_logq");
+  TTX_TRY(syntax_validate_scored("ttx_hypothesis_logq_syntax", c.syntax, W, &cls, &syn_len));
+  if (!d_logits || !d_hyp || !o.logq || !o.length) return fail(TTX_ERR_INVALID, "bad argument to ttx_hypothesis_logq");
   TTX_TRY(check_score_shapes(s, R, W, V, "ttx_hypothesis_logq"));
   if (d_bias && (ld_bias < V || N < 1 || R % N != 0))
     return fail(TTX_ERR_INVALID, "ttx_hypothesis_logq_bias: ld_bias must be at least V and R a multiple of the rows per source");
@@ -2232,24 +2246,23 @@ static int hypothesis_logq(ttx_session* s, const float* d_logits, const int64_t*
     if (cls) TTX_TRY(syntax_scored_logits(s, st, s->ev_logits.as<float>(), R, W - 1, V, d_hyp, W, cls, syn_len, eos));
     d_logits = s->ev_logits.as<float>();
   }
-  return launch_logq(s, st, d_logits, d_hyp, W, R, W, V, pad, eos, b, d_forced_len,
-                     LogqOut{d_tok_logq, d_logq, d_first_outside, d_rank, d_n_kept, d_length, d_finished});
+  return launch_logq(s, st, d_logits, d_hyp, W, R, W, V, pad, eos, b, d_forced_len, o);
 }
 
 extern "C" int ttx_hypothesis_logq(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad, int eos,
                                    const ttx_dist* dist, const int32_t* d_forced_len, float* d_tok_logq, float* d_logq,
                                    int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept, int32_t* d_length,
                                    uint8_t* d_finished, void* stream) {
-  return hypothesis_logq(s, d_logits, d_hyp, R, W, V, pad, eos, dist, d_forced_len, d_tok_logq, d_logq, d_first_outside, d_rank, d_n_kept,
-                         d_length, d_finished, stream, nullptr, 0, 1);
+  return hypothesis_logq(s, d_logits, d_hyp, R, W, V, pad, eos, dist, d_forced_len, ScoreConstraints{nullptr, 0, 1, nullptr},
+                         LogqOut{d_tok_logq, d_logq, d_first_outside, d_rank, d_n_kept, d_length, d_finished}, stream);
 }
 
 extern "C" int ttx_hypothesis_logq_bias(ttx_session* s, const float* d_logits, const int64_t* d_hyp, int R, int W, int V, int pad, int eos,
                                         const ttx_dist* dist, const int32_t* d_forced_len, const float* d_bias, int ld_bias, int N,
                                         float* d_tok_logq, float* d_logq, int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept,
                                         int32_t* d_length, uint8_t* d_finished, void* stream) {
-  return hypothesis_logq(s, d_logits, d_hyp, R, W, V, pad, eos, dist, d_forced_len, d_tok_logq, d_logq, d_first_outside, d_rank, d_n_kept,
-                         d_length, d_finished, stream, d_bias, ld_bias, N);
+  return hypothesis_logq(s, d_logits, d_hyp, R, W, V, pad, eos, dist, d_forced_len, ScoreConstraints{d_bias, ld_bias, N, nullptr},
+                         LogqOut{d_tok_logq, d_logq, d_first_outside, d_rank, d_n_kept, d_length, d_finished}, stream);
 }
 
 // ttx_hypothesis_logq_bias under a syntax constraint: k_syntax_mask on the (biased) copy of the logits before the log q stage.
@@ -2257,18 +2270,19 @@ extern "C" int ttx_hypothesis_logq_syntax(ttx_session* s, const float* d_logits,
                                           const ttx_dist* dist, const int32_t* d_forced_len, const float* d_bias, int ld_bias, int N,
                                           const ttx_syntax* syntax, float* d_tok_logq, float* d_logq, int32_t* d_first_outside,
                                           int32_t* d_rank, int32_t* d_n_kept, int32_t* d_length, uint8_t* d_finished, void* stream) {
-  return hypothesis_logq(s, d_logits, d_hyp, R, W, V, pad, eos, dist, d_forced_len, d_tok_logq, d_logq, d_first_outside, d_rank, d_n_kept,
-                         d_length, d_finished, stream, d_bias, ld_bias, N, syntax);
+  return hypothesis_logq(s, d_logits, d_hyp, R, W, V, pad, eos, dist, d_forced_len, ScoreConstraints{d_bias, ld_bias, N, syntax},
+                         LogqOut{d_tok_logq, d_logq, d_first_outside, d_rank, d_n_kept, d_length, d_finished}, stream);
 }
 
 static int score_proposal(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N, int W,
                           int eos, const ttx_dist* dist, const int32_t* d_forced_len, float* d_logits, float* d_tok_logp,
                           float* d_score, float* d_tok_logq, float* d_logq, int32_t* d_first_outside, int32_t* d_rank,
-                          int32_t* d_n_kept, int32_t* d_length, uint8_t* d_finished, void* stream, const float* d_bias, int ld_bias,
-                          const ttx_syntax* syn = nullptr) {
+                          int32_t* d_n_kept, int32_t* d_length, uint8_t* d_finished, void* stream, const ScoreConstraints& sc) {
   if (!s) return session_required("ttx_score_proposal");
+  const float* d_bias = sc.d_bias;
+  const int ld_bias = sc.ld_bias;
   const signed char* cls; int syn_len;
-  TTX_TRY(syntax_validate_scored("ttx_score_proposal_syntax", syn, W, &cls, &syn_len));
+  TTX_TRY(syntax_validate_scored("ttx_score_proposal_syntax", sc.syntax, W, &cls, &syn_len));
   if (d_bias && ld_bias < s->m->cfg.vocab_size) return fail(TTX_ERR_INVALID, "ttx_score_proposal_bias: ld_bias must be at least the vocabulary");
   if (!d_src || !d_hyp || !d_logq || !d_length || B <= 0 || N <= 0 || Ls <= 0)
     return fail(TTX_ERR_INVALID, "bad argument to ttx_score_proposal");
@@ -2331,7 +2345,7 @@ extern "C" int ttx_score_proposal(ttx_session* s, const int64_t* d_src, int B, i
                                   float* d_score, float* d_tok_logq, float* d_logq, int32_t* d_first_outside, int32_t* d_rank,
                                   int32_t* d_n_kept, int32_t* d_length, uint8_t* d_finished, void* stream) {
   return score_proposal(s, d_src, B, Ls, d_hyp, ld_hyp, N, W, eos, dist, d_forced_len, d_logits, d_tok_logp, d_score, d_tok_logq, d_logq,
-                        d_first_outside, d_rank, d_n_kept, d_length, d_finished, stream, nullptr, 0);
+                        d_first_outside, d_rank, d_n_kept, d_length, d_finished, stream, ScoreConstraints{nullptr, 0, N, nullptr});
 }
 
 extern "C" int ttx_score_proposal_bias(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_hyp, int ld_hyp, int N, int W,
@@ -2340,7 +2354,7 @@ extern "C" int ttx_score_proposal_bias(ttx_session* s, const int64_t* d_src, int
                                        int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept, int32_t* d_length,
                                        uint8_t* d_finished, void* stream) {
   return score_proposal(s, d_src, B, Ls, d_hyp, ld_hyp, N, W, eos, dist, d_forced_len, d_logits, d_tok_logp, d_score, d_tok_logq, d_logq,
-                        d_first_outside, d_rank, d_n_kept, d_length, d_finished, stream, d_bias, ld_bias);
+                        d_first_outside, d_rank, d_n_kept, d_length, d_finished, stream, ScoreConstraints{d_bias, ld_bias, N, nullptr});
 }
 
 // ttx_score_proposal_bias under a syntax constraint (a null `syntax` is that call).
@@ -2350,17 +2364,25 @@ extern "C" int ttx_score_proposal_syntax(ttx_session* s, const int64_t* d_src, i
                                          float* d_logq, int32_t* d_first_outside, int32_t* d_rank, int32_t* d_n_kept, int32_t* d_length,
                                          uint8_t* d_finished, void* stream) {
   return score_proposal(s, d_src, B, Ls, d_hyp, ld_hyp, N, W, eos, dist, d_forced_len, d_logits, d_tok_logp, d_score, d_tok_logq, d_logq,
-                        d_first_outside, d_rank, d_n_kept, d_length, d_finished, stream, d_bias, ld_bias, syntax);
+                        d_first_outside, d_rank, d_n_kept, d_length, d_finished, stream, ScoreConstraints{d_bias, ld_bias, N, syntax});
 }
 
-// ttx_sample_generate and ttx_sample_generate_prefix: one body, the unprompted call with a null prefix.
-static int sample_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sample_params* p,
-                           int64_t* d_out, ttx_gen_stats* stats, void* stream, const int64_t* d_prefix, int ld_prefix,
-                           const int32_t* h_prefix_len, const float* d_bias = nullptr, int ld_bias = 0, const ttx_syntax* syn = nullptr) {
+// The options of a form that spells them out as arguments; a form that takes none passes NO_OPTS, as a null `o` does.
+static const ttx_sample_opts NO_OPTS{};
+static ttx_sample_opts opts_of(const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len, const int64_t* d_proposal,
+                               int ld_proposal, const int32_t* h_proposal_len) {
+  ttx_sample_opts o{};
+  o.d_prefix = d_prefix; o.ld_prefix = ld_prefix; o.h_prefix_len = h_prefix_len;
+  o.d_proposal = d_proposal; o.ld_proposal = ld_proposal; o.h_proposal_len = h_proposal_len;
+  return o;
+}
+
+// The body of every form of ttx_sample_generate; `form` names the one that was called where a refusal says so.
+static int sample_generate(const char* form, ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
+                           const ttx_sample_params* p, const ttx_sample_opts& o, const ttx_syntax* syn, int64_t* d_out,
+                           ttx_gen_stats* stats, void* stream) {
+  if (o.h_proposal_len) return fail(TTX_ERR_INVALID, std::string(form) + ": the plain sampler verifies no drafts and takes no proposal");
   if (!s || !p) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
-  TTX_TRY(bias_validate("ttx_sample_generate", s, d_bias, ld_bias));
-  const signed char* cls;
-  TTX_TRY(syntax_validate("ttx_sample_generate_syntax", syn, p->max_len, &cls));
   if (s->m->cfg.vocab_size > SAMPLE_MAX_V) return fail(TTX_ERR_INVALID, "ttx_sample_generate: vocabularies above 1024 are not supported");
   if (p->num_samples < 1) return fail(TTX_ERR_INVALID, "ttx_sample_generate: num_samples must be at least 1");
   SampleSetup smp{};
@@ -2368,8 +2390,8 @@ static int sample_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, 
   if (B > 0 && (long long)B * p->num_samples * ((long long)std::max(p->max_len, 0) + 2) >= (1ll << 31))
     return fail(TTX_ERR_INVALID, "ttx_sample_generate: B * num_samples * (max_len + 2) must stay below 2^31");
   smp.n = p->num_samples; smp.d_row_keys = d_row_keys;
-  TTX_TRY(prefix_validate("ttx_sample_generate", d_prefix, ld_prefix, h_prefix_len, std::max(B, 0), p->max_len, &smp));
-  smp.d_bias = d_bias; smp.ld_bias = ld_bias; smp.d_syntax = cls;
+  TTX_TRY(constraints_validate(Who("ttx_sample_generate", "ttx_sample_generate", "ttx_sample_generate", "ttx_sample_generate_syntax"), s, o,
+                               syn, std::max(B, 0), p->max_len, &smp));
   ttx_gen_params g{};
   g.max_len = p->max_len; g.draft_len = 0; g.n_drafts = 1; g.pad_token = p->pad_token; g.bos_token = p->bos_token;
   g.eos_token = p->eos_token; g.replace_token = p->pad_token; g.want_logits = 0;
@@ -2381,34 +2403,28 @@ static int sample_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, 
 
 extern "C" int ttx_sample_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
                                    const ttx_sample_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
-  return sample_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, nullptr, 0, nullptr);
+  return sample_generate("ttx_sample_generate", s, d_src, B, Ls, d_row_keys, p, NO_OPTS, nullptr, d_out, stats, stream);
 }
 
 extern "C" int ttx_sample_generate_prefix(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
                                           const ttx_sample_params* p, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
                                           int64_t* d_out, ttx_gen_stats* stats, void* stream) {
-  return sample_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, d_prefix, ld_prefix, h_prefix_len);
+  return sample_generate("ttx_sample_generate_prefix", s, d_src, B, Ls, d_row_keys, p, opts_of(d_prefix, ld_prefix, h_prefix_len, nullptr, 0, nullptr),
+                         nullptr, d_out, stats, stream);
 }
 
 // The form that takes every option of the plain sampler: the prefix of ttx_sample_generate_prefix and the per-source logit bias.
 extern "C" int ttx_sample_generate_ex(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
                                       const ttx_sample_params* p, const ttx_sample_opts* o, int64_t* d_out, ttx_gen_stats* stats,
                                       void* stream) {
-  if (!o) return sample_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, nullptr, 0, nullptr);
-  if (o->h_proposal_len) return fail(TTX_ERR_INVALID, "ttx_sample_generate_ex: the plain sampler verifies no drafts and takes no proposal");
-  return sample_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, o->d_prefix, o->ld_prefix, o->h_prefix_len, o->d_bias,
-                         o->ld_bias);
+  return sample_generate("ttx_sample_generate_ex", s, d_src, B, Ls, d_row_keys, p, o ? *o : NO_OPTS, nullptr, d_out, stats, stream);
 }
 
-// ttx_sample_generate_ex under a syntax constraint (a null `syntax`, or a null table, is that call, launch for launch).
+// The general form: ttx_sample_generate_ex under a syntax constraint (a null `syntax`, or a null table, is that call, launch for launch).
 extern "C" int ttx_sample_generate_syntax(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
                                           const ttx_sample_params* p, const ttx_sample_opts* o, const ttx_syntax* syntax, int64_t* d_out,
                                           ttx_gen_stats* stats, void* stream) {
-  const ttx_sample_opts none{};
-  if (!o) o = &none;
-  if (o->h_proposal_len) return fail(TTX_ERR_INVALID, "ttx_sample_generate_syntax: the plain sampler verifies no drafts and takes no proposal");
-  return sample_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, o->d_prefix, o->ld_prefix, o->h_prefix_len, o->d_bias,
-                         o->ld_bias, syntax);
+  return sample_generate("ttx_sample_generate_syntax", s, d_src, B, Ls, d_row_keys, p, o ? *o : NO_OPTS, syntax, d_out, stats, stream);
 }
 
 // What the speculative sampling calls refuse with TTX_ERR_INVALID whatever code gen_validate would give (nothing of these calls is
@@ -2437,24 +2453,17 @@ static int sample_spec_validate(const char* who, const ttx_session* s, const ttx
 // (k_sample_step, k_sample_accept).  A draft token is accepted iff it is the token the plain sampler emits at its position, so the
 // committed rows are ttx_sample_generate's.
 static int sample_speculative_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
-                                       const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream,
-                                       const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
-                                       const int64_t* d_proposal = nullptr, int ld_proposal = 0, const int32_t* h_proposal_len = nullptr,
-                                       const float* d_bias = nullptr, int ld_bias = 0, const ttx_syntax* syn = nullptr) {
+                                       const ttx_sample_spec_params* p, const ttx_sample_opts& o, const ttx_syntax* syn, int64_t* d_out,
+                                       ttx_gen_stats* stats, void* stream) {
   const char* who = "ttx_sample_speculative_generate";
   if (!s || !p) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
-  TTX_TRY(bias_validate(who, s, d_bias, ld_bias));
-  const signed char* cls;
-  TTX_TRY(syntax_validate(who, syn, p->sample.max_len, &cls));
   SampleSetup smp{};
   ttx_gen_params g{};
   const long long R = (long long)std::max(B, 0) * std::max(p->sample.num_samples, 0);
   TTX_TRY(sample_spec_validate(who, s, p, R, &smp, &g));
   if (B <= 0) return fail(TTX_ERR_INVALID, "bad argument to a generate call");
   smp.d_row_keys = d_row_keys;
-  TTX_TRY(prefix_validate(who, d_prefix, ld_prefix, h_prefix_len, B, g.max_len, &smp));
-  TTX_TRY(proposal_validate(who, d_proposal, ld_proposal, h_proposal_len, B, g.max_len, &smp));
-  smp.d_bias = d_bias; smp.ld_bias = ld_bias; smp.d_syntax = cls;
+  TTX_TRY(constraints_validate(who, s, o, syn, B, g.max_len, &smp));
   const int rc = generate_one(s, d_src, (int)R, Ls, &g, d_out, stats, stream, false, &smp);
   if (rc == TTX_OK && stats) stats->src_tokens_padded = (long long)B * Ls;    // the encoder ran once per source
   return rc;
@@ -2462,14 +2471,15 @@ static int sample_speculative_generate(ttx_session* s, const int64_t* d_src, int
 
 extern "C" int ttx_sample_speculative_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
                                                const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
-  return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, nullptr, 0, nullptr);
+  return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, NO_OPTS, nullptr, d_out, stats, stream);
 }
 
 // The prompted form: the prefix rides in as draft 0 (k_prefix_drafts), ceil(len / (draft_len + 1)) steps for len forced tokens.
 extern "C" int ttx_sample_speculative_generate_prefix(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
                                                       const ttx_sample_spec_params* p, const int64_t* d_prefix, int ld_prefix,
                                                       const int32_t* h_prefix_len, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
-  return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, d_prefix, ld_prefix, h_prefix_len);
+  return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, opts_of(d_prefix, ld_prefix, h_prefix_len, nullptr, 0, nullptr), nullptr,
+                                     d_out, stats, stream);
 }
 
 // The proposed form: the proposal is offered as draft 0 wherever it can be aligned with the row (k_proposal_drafts); no token changes.
@@ -2478,29 +2488,24 @@ extern "C" int ttx_sample_speculative_generate_proposal(ttx_session* s, const in
                                                         const int32_t* h_prefix_len, const int64_t* d_proposal, int ld_proposal,
                                                         const int32_t* h_proposal_len, int64_t* d_out, ttx_gen_stats* stats,
                                                         void* stream) {
-  return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, d_prefix, ld_prefix, h_prefix_len, d_proposal,
-                                     ld_proposal, h_proposal_len);
+  return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p,
+                                     opts_of(d_prefix, ld_prefix, h_prefix_len, d_proposal, ld_proposal, h_proposal_len), nullptr, d_out, stats,
+                                     stream);
 }
 
 // The form that takes every option: prefix, proposal and the per-source logit bias (a null `o` is the plain call).
 extern "C" int ttx_sample_speculative_generate_ex(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
                                                   const ttx_sample_spec_params* p, const ttx_sample_opts* o, int64_t* d_out,
                                                   ttx_gen_stats* stats, void* stream) {
-  const ttx_sample_opts none{};
-  if (!o) o = &none;
-  return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, o->d_prefix, o->ld_prefix, o->h_prefix_len,
-                                     o->d_proposal, o->ld_proposal, o->h_proposal_len, o->d_bias, o->ld_bias);
+  return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, o ? *o : NO_OPTS, nullptr, d_out, stats, stream);
 }
 
-// ttx_sample_speculative_generate_ex under a syntax constraint: the keyed draw of a draft position comes from the row masked for the
-// prefix that includes the earlier draft tokens, so the committed rows are ttx_sample_generate_syntax's.
+// The general form: ttx_sample_speculative_generate_ex under a syntax constraint.  The keyed draw of a draft position comes from the
+// row masked for the prefix that includes the earlier draft tokens, so the committed rows are ttx_sample_generate_syntax's.
 extern "C" int ttx_sample_speculative_generate_syntax(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys,
                                                       const ttx_sample_spec_params* p, const ttx_sample_opts* o, const ttx_syntax* syntax,
                                                       int64_t* d_out, ttx_gen_stats* stats, void* stream) {
-  const ttx_sample_opts none{};
-  if (!o) o = &none;
-  return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, d_out, stats, stream, o->d_prefix, o->ld_prefix, o->h_prefix_len,
-                                     o->d_proposal, o->ld_proposal, o->h_proposal_len, o->d_bias, o->ld_bias, syntax);
+  return sample_speculative_generate(s, d_src, B, Ls, d_row_keys, p, o ? *o : NO_OPTS, syntax, d_out, stats, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2543,7 +2548,7 @@ static int pool_sample_begin(PoolJob& j, const SampleSetup& smp);
 // `smp` (null: the greedy pool): the sampling pool, whose slots carry a key and a sample id, whose steps draw with k_sample_step and
 // accept with k_sample_accept, and which keeps no per-row trace (d_traj and d_fin are null).
 static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_cap, const ttx_gen_params* p, int64_t* d_out,
-                      int16_t* d_traj, int32_t* d_fin, const SampleSetup* smp = nullptr) {
+                      int16_t* d_traj, int32_t* d_fin, const SampleSetup* smp) {
   const ttx_config& c = s->m->cfg;
   const int d = c.embedding_dim, Ld = c.num_decoder_layers;
   const int N = p->n_drafts, D = p->draft_len, D1 = D + 1, max_len = p->max_len;
@@ -2587,12 +2592,9 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
     need(s->pred_draft, Mmax * 4); need(s->state2, 3 * sizeof(DecState));
   }
   if (smp) { need(s->smp_key, (size_t)C * 8); need(s->smp_sample, (size_t)C * 4); need(s->smp_prm, sizeof(SampleBlock)); }
-  if (smp && smp->tabled()) {
-    need(s->pfx_tok, (size_t)smp->n_sources * max_len * 4); need(s->pfx_len_src, (size_t)smp->n_sources * 4);
-    need(s->pfx_len, (size_t)C * 4); need(s->pfx_src, (size_t)C * 4); need(s->pfx_draft0, (size_t)C * D * 4);
-  }
-  if (smp && smp->d_bias) { need(s->lb_val, (size_t)smp->n_sources * c.vocab_size * sizeof(float)); need(s->lb_src, (size_t)C * 4); }
-  if (smp && smp->d_syntax) need(s->syn_cls, (size_t)c.vocab_size);
+  if (smp && smp->tabled()) need(s->pfx_src, (size_t)C * 4);          // the slots' own row-to-source maps, written at admission
+  if (smp && smp->d_bias) need(s->lb_src, (size_t)C * 4);
+  if (smp && need.rc == TTX_OK) need.rc = constraints_ensure(s, st, *smp, max_len, (size_t)C, (size_t)C * D, 0);
   TTX_TRY(need.rc);
   AcceptBlk* blk = nullptr;
   // the greedy pool keeps the session's reading of TTX_ACCEPT_SPREAD; the sampling pool reads it here, with its other switches
@@ -2776,20 +2778,15 @@ static int pool_sample_begin(PoolJob& j, const SampleSetup& smp) {
   k.sample.front = s->front.as<int>(); k.sample.prm = s->smp_prm.as<SampleBlock>();
   j.g.la.sample_rule = 1;
   j.per_src = smp.n; j.d_row_keys = smp.d_row_keys;
-  if (smp.tabled()) {                                // the slots' lengths, sources and draft 0 are written at admission
-    TTX_TRY(prefix_upload(s, j.st, smp, k.max_len, k.p.pad_token));
-    const PrefixTab tab{s->pfx_tok.as<int>(), k.max_len, s->pfx_len.as<int>(), s->pfx_src.as<int>()};
-    if (smp.proposed) { k.prop = tab; k.prop_ctx = smp.prop_ctx; }
-    else k.sample.pfx = tab;
+  // every pool of the call holds the whole tables; a slot's prefix length, its rows of the tables and its draft 0 are written at
+  // admission.  The class table is one for the call: nothing per slot, the state comes from the slot's row
+  ConstraintTabs t;
+  TTX_TRY(constraints_upload(s, j.st, smp, k.max_len, k.p.pad_token, s->pfx_len.as<int>(), s->pfx_src.as<int>(), s->lb_src.as<int>(), &t));
+  k.bias = t.bias; k.syntax = t.syntax;
+  if (smp.tabled()) {
+    if (smp.proposed) { k.prop = t.pfx; k.prop_ctx = smp.prop_ctx; }
+    else k.sample.pfx = t.pfx;
     k.pfx_draft0 = s->pfx_draft0.as<int>();
-  }
-  if (smp.d_bias) {                                  // every pool of the call holds the whole table; a slot's row is written at admission
-    TTX_TRY(bias_upload(s, j.st, smp.d_bias, smp.ld_bias, smp.n_sources));
-    k.bias = LogitBiasTab{s->lb_val.as<float>(), s->m->cfg.vocab_size, s->lb_src.as<int>()};
-  }
-  if (smp.d_syntax) {                                // one table for the call: nothing per slot, the state comes from the slot's row
-    TTX_TRY(syntax_upload(s, j.st, smp.d_syntax));
-    k.syntax = s->syn_cls.as<signed char>();
   }
   return TTX_OK;
 }
@@ -2906,18 +2903,13 @@ extern "C" int ttx_greedy_speculative_generate_pool(ttx_session** sessions, int 
 // together, the step kernels are the pool's with the keyed draw where the argmax stands.
 static int sample_speculative_generate_pool(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total, int Ls_all,
                                             const int32_t* h_len, const int64_t* d_row_keys, int capacity, const ttx_sample_spec_params* p,
-                                            int64_t* d_out, ttx_gen_stats* stats, void* stream, const int64_t* d_prefix, int ld_prefix,
-                                            const int32_t* h_prefix_len, const int64_t* d_proposal = nullptr, int ld_proposal = 0,
-                                            const int32_t* h_proposal_len = nullptr, const float* d_bias = nullptr, int ld_bias = 0,
-                                            const ttx_syntax* syn = nullptr) {
+                                            const ttx_sample_opts& o, const ttx_syntax* syn, int64_t* d_out, ttx_gen_stats* stats,
+                                            void* stream) {
   const char* who = "ttx_sample_speculative_generate_pool";
   if (!sessions || n_sessions <= 0 || !d_src || S_total < 0 || !h_len || !p || !d_out)
     return fail(TTX_ERR_INVALID, std::string("bad argument to ") + who);
   for (int i = 0; i < n_sessions; ++i)
     if (!sessions[i]) return fail(TTX_ERR_INVALID, std::string("bad argument to ") + who);
-  TTX_TRY(bias_validate(who, sessions[0], d_bias, ld_bias));
-  const signed char* cls;
-  TTX_TRY(syntax_validate(who, syn, p->sample.max_len, &cls));
   SampleSetup smp{};
   ttx_gen_params g{};
   TTX_TRY(sample_spec_validate(who, sessions[0], p, capacity, &smp, &g));
@@ -2931,19 +2923,17 @@ static int sample_speculative_generate_pool(ttx_session** sessions, int n_sessio
   if (Ls_cap > c.max_positions) return fail(TTX_ERR_INVALID, std::string(who) + ": slot width beyond the positional table");
   if (g.pad_token != c.pad_token) return fail(TTX_ERR_INVALID, std::string(who) + ": generator pad token differs from the model's");
   if (g.max_len + g.draft_len + 2 > c.max_positions) return fail(TTX_ERR_INVALID, std::string(who) + ": max_len + draft_len exceeds the positional table");
-  TTX_TRY(prefix_validate(who, d_prefix, ld_prefix, h_prefix_len, S_total, g.max_len, &smp));
-  TTX_TRY(proposal_validate(who, d_proposal, ld_proposal, h_proposal_len, S_total, g.max_len, &smp));
+  TTX_TRY(constraints_validate(who, sessions[0], o, syn, S_total, g.max_len, &smp));
   if (S_total == 0) return TTX_OK;
   smp.d_row_keys = d_row_keys;
-  smp.d_bias = d_bias; smp.ld_bias = ld_bias; smp.d_syntax = cls;
   return pool_generate(sessions, n_sessions, d_src, S_total, Ls_all, h_len, Ls_cap, capacity, &g, d_out, nullptr, nullptr, stats, stream, &smp);
 }
 
 extern "C" int ttx_sample_speculative_generate_pool(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total, int Ls_all,
                                                     const int32_t* h_len, const int64_t* d_row_keys, int capacity,
                                                     const ttx_sample_spec_params* p, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
-  return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p, d_out, stats, stream,
-                                          nullptr, 0, nullptr);
+  return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p, NO_OPTS, nullptr, d_out,
+                                          stats, stream);
 }
 
 // The prompted pool: every pool of the call holds the whole prefix table; a slot gets its source's index and length at admission.
@@ -2952,8 +2942,8 @@ extern "C" int ttx_sample_speculative_generate_pool_prefix(ttx_session** session
                                                            const ttx_sample_spec_params* p, const int64_t* d_prefix, int ld_prefix,
                                                            const int32_t* h_prefix_len, int64_t* d_out, ttx_gen_stats* stats,
                                                            void* stream) {
-  return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p, d_out, stats, stream,
-                                          d_prefix, ld_prefix, h_prefix_len);
+  return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p,
+                                          opts_of(d_prefix, ld_prefix, h_prefix_len, nullptr, 0, nullptr), nullptr, d_out, stats, stream);
 }
 
 // The proposed pool: the proposal table rides through admission as the prefix table does.
@@ -2963,8 +2953,9 @@ extern "C" int ttx_sample_speculative_generate_pool_proposal(ttx_session** sessi
                                                              const int32_t* h_prefix_len, const int64_t* d_proposal, int ld_proposal,
                                                              const int32_t* h_proposal_len, int64_t* d_out, ttx_gen_stats* stats,
                                                              void* stream) {
-  return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p, d_out, stats, stream,
-                                          d_prefix, ld_prefix, h_prefix_len, d_proposal, ld_proposal, h_proposal_len);
+  return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p,
+                                          opts_of(d_prefix, ld_prefix, h_prefix_len, d_proposal, ld_proposal, h_proposal_len), nullptr, d_out,
+                                          stats, stream);
 }
 
 // The form that takes every option; the bias table is [S_total][ld_bias] in the order of d_src, and a slot gets its row at admission.
@@ -2972,23 +2963,17 @@ extern "C" int ttx_sample_speculative_generate_pool_ex(ttx_session** sessions, i
                                                        int Ls_all, const int32_t* h_len, const int64_t* d_row_keys, int capacity,
                                                        const ttx_sample_spec_params* p, const ttx_sample_opts* o, int64_t* d_out,
                                                        ttx_gen_stats* stats, void* stream) {
-  const ttx_sample_opts none{};
-  if (!o) o = &none;
-  return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p, d_out, stats, stream,
-                                          o->d_prefix, o->ld_prefix, o->h_prefix_len, o->d_proposal, o->ld_proposal, o->h_proposal_len,
-                                          o->d_bias, o->ld_bias);
+  return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p, o ? *o : NO_OPTS,
+                                          nullptr, d_out, stats, stream);
 }
 
-// ttx_sample_speculative_generate_pool_ex under a syntax constraint: one table for the call, nothing per slot.
+// The general form: ttx_sample_speculative_generate_pool_ex under a syntax constraint, one table for the call, nothing per slot.
 extern "C" int ttx_sample_speculative_generate_pool_syntax(ttx_session** sessions, int n_sessions, const int64_t* d_src, int S_total,
                                                            int Ls_all, const int32_t* h_len, const int64_t* d_row_keys, int capacity,
                                                            const ttx_sample_spec_params* p, const ttx_sample_opts* o,
                                                            const ttx_syntax* syntax, int64_t* d_out, ttx_gen_stats* stats, void* stream) {
-  const ttx_sample_opts none{};
-  if (!o) o = &none;
-  return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p, d_out, stats, stream,
-                                          o->d_prefix, o->ld_prefix, o->h_prefix_len, o->d_proposal, o->ld_proposal, o->h_proposal_len,
-                                          o->d_bias, o->ld_bias, syntax);
+  return sample_speculative_generate_pool(sessions, n_sessions, d_src, S_total, Ls_all, h_len, d_row_keys, capacity, p, o ? *o : NO_OPTS,
+                                          syntax, d_out, stats, stream);
 }
 
 // Several batches in flight on one GPU: outputs per batch are identical to the one-at-a-time call.
@@ -3864,7 +3849,7 @@ struct BeamSearchJob {
 // Everything of the call behind the argument check: the reference's asserts and this library's limits, the workspaces, the
 // encoder and the <BOS> hypotheses.
 static int bsearch_start(BeamSearchJob& j, ttx_session* s, hipStream_t st, const int64_t* d_src, int B, int Ls,
-                         const ttx_beam_search_params* p, int64_t* d_out, bool sbs = false) {
+                         const ttx_beam_search_params* p, int64_t* d_out, bool sbs) {
   const ttx_config& c = s->m->cfg;
   const int K = p->beam_size, max_len = p->max_len, V = c.vocab_size;
   if (max_len <= 1) return fail(TTX_ERR_REFERENCE, "assert self.max_len > 1 (standard_decoding.py:79)");
@@ -4001,14 +3986,11 @@ static int bsearch_finish_enqueue(BeamSearchJob& j) {
   return TTX_OK;
 }
 
-extern "C" int ttx_beam_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_beam_search_params* p, int64_t* d_out,
-                                 ttx_beam_search_stats* stats, void* stream) {
-  if (!s || !d_src || !p || !d_out || !stats || B <= 0 || Ls <= 1) return fail(TTX_ERR_INVALID, "bad argument to ttx_beam_generate");
-  BeamSearchJob j;
-  const auto start = [&](int) -> int {
-    TTX_TRY(bsearch_start(j, s, s->own_stream, d_src, B, Ls, p, d_out));
-    return bsearch_launch_iter(j);                                  // max_len > 1: the first iteration always runs
-  };
+// The three single-session beam loops (standard, constrained, stochastic) under drive_sessions.  `start` sizes the call's buffers,
+// runs bsearch_start, sets the job's options and enqueues the first iteration (max_len > 1: it always runs); a turn enqueues the
+// next iteration, or the copies of the results, once the one in flight has published.
+template <class Start>
+static int bsearch_drive(BeamSearchJob& j, ttx_session* s, ttx_beam_search_stats* stats, void* stream, Start start) {
   const auto turn = [&](int) -> int {
     if (j.phase == 1) {
       if (((volatile BeamHost*)s->beam_host)->steps_done < j.launched) return TURN_WAITING;   // the iteration in flight has not published yet
@@ -4023,156 +4005,135 @@ extern "C" int ttx_beam_generate(ttx_session* s, const int64_t* d_src, int B, in
   return drive_sessions(&s, 1, false, stream, start, turn);
 }
 
-// Constrained beam search: the standard beam loop above under a per-source logit bias (k_logit_bias), a syntax constraint
-// (k_syntax_mask) and forced prefixes, with k_beam_step_masked (csrc/ttx_beam_mask.hip.h) where it launches k_beam_step.  A call with
-// none of the three is ttx_beam_generate, launch for launch, plus the copy of the scores.
+// Before bsearch_start settles which graphs are current: the buffers of a beam call's constraints.  Its tables go by source; the
+// prefix table's row-to-source map is the identity over the B sources (k_sbs_prefix_src).
+static int bsearch_constraints_ensure(ttx_session* s, hipStream_t st, const SampleSetup& c, int B, int max_len) {
+  return constraints_ensure(s, st, c, max_len, 0, 0, c.prompted ? (size_t)B : 0);
+}
+
+// After bsearch_start: the call's tables into the job.  The bias goes by candidate (t_src_of); the steps run eagerly, yet read
+// the session's copies as every constrained loop does.
+static int bsearch_constraints_upload(BeamSearchJob& j, const SampleSetup& c) {
+  ttx_session* s = j.s;
+  ConstraintTabs t;
+  TTX_TRY(constraints_upload(s, j.st, c, j.p.max_len, j.p.pad_token, s->pfx_len_src.as<int>(), s->smp_src_of.as<int>(), s->t_src_of.as<int>(), &t));
+  j.bias = t.bias; j.syntax = t.syntax; j.pfx = t.pfx;
+  if (c.prompted) {
+    hipLaunchKernelGGL(k_sbs_prefix_src, dim3(cdiv(j.B, 256)), dim3(256), 0, j.st, s->smp_src_of.as<int>(), j.B);
+    HIP_TRY(hipGetLastError());
+  }
+  return TTX_OK;
+}
+
+// Standard beam search and its constrained form: the beam loop above under a per-source logit bias (k_logit_bias), a syntax
+// constraint (k_syntax_mask) and forced prefixes, with k_beam_step_masked (csrc/ttx_beam_mask.hip.h) where it launches k_beam_step.
+// A call with none of the three is ttx_beam_generate, launch for launch; the copy of the scores hangs on d_score alone.
+static int beam_generate(const char* who, ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_beam_search_params* p,
+                         const ttx_sample_opts& o, const ttx_syntax* syntax, int64_t* d_out, float* d_score, ttx_beam_search_stats* stats,
+                         void* stream) {
+  if (!s || !d_src || !p || !d_out || !stats || B <= 0 || Ls <= 1) return fail(TTX_ERR_INVALID, std::string("bad argument to ") + who);
+  SampleSetup c{};
+  TTX_TRY(constraints_validate(who, s, o, syntax, B, p->max_len, &c));
+  BeamSearchJob j;
+  return bsearch_drive(j, s, stats, stream, [&](int) -> int {
+    TTX_TRY(bsearch_constraints_ensure(s, s->own_stream, c, B, p->max_len));
+    TTX_TRY(bsearch_start(j, s, s->own_stream, d_src, B, Ls, p, d_out, false));
+    j.d_score = d_score;
+    j.constrained = c.any();
+    TTX_TRY(bsearch_constraints_upload(j, c));
+    return bsearch_launch_iter(j);
+  });
+}
+
+extern "C" int ttx_beam_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_beam_search_params* p, int64_t* d_out,
+                                 ttx_beam_search_stats* stats, void* stream) {
+  return beam_generate("ttx_beam_generate", s, d_src, B, Ls, p, NO_OPTS, nullptr, d_out, nullptr, stats, stream);
+}
+
 extern "C" int ttx_beam_generate_constrained(ttx_session* s, const int64_t* d_src, int B, int Ls, const ttx_beam_search_params* p,
                                              const float* d_bias, int ld_bias, const ttx_syntax* syntax, const int64_t* d_prefix,
                                              int ld_prefix, const int32_t* h_prefix_len, int64_t* d_out, float* d_score,
                                              ttx_beam_search_stats* stats, void* stream) {
-  const char* who = "ttx_beam_generate_constrained";
-  if (!s || !d_src || !p || !d_out || !stats || B <= 0 || Ls <= 1) return fail(TTX_ERR_INVALID, "bad argument to ttx_beam_generate_constrained");
-  TTX_TRY(bias_validate(who, s, d_bias, ld_bias));
-  const signed char* cls = nullptr;
-  TTX_TRY(syntax_validate(who, syntax, p->max_len, &cls));
-  SampleSetup pre{};
-  TTX_TRY(prefix_validate(who, d_prefix, ld_prefix, h_prefix_len, B, p->max_len, &pre));
-  const int V = s->m->cfg.vocab_size;
-  BeamSearchJob j;
-  const auto start = [&](int) -> int {
-    hipStream_t st = s->own_stream;
-    if (pre.prompted) {                 // sized before bsearch_start settles which graphs are current
-      TTX_TRY(ensure(s->pfx_tok, (size_t)B * p->max_len * 4, st));
-      TTX_TRY(ensure(s->pfx_len_src, (size_t)B * 4, st));
-      TTX_TRY(ensure(s->smp_src_of, (size_t)B * 4, st));
-    }
-    if (d_bias) TTX_TRY(ensure(s->lb_val, (size_t)B * V * sizeof(float), st));
-    if (cls) TTX_TRY(ensure(s->syn_cls, (size_t)V, st));
-    TTX_TRY(bsearch_start(j, s, st, d_src, B, Ls, p, d_out));
-    j.d_score = d_score;
-    j.constrained = d_bias || cls || pre.prompted;
-    if (d_bias) {
-      TTX_TRY(bias_upload(s, st, d_bias, ld_bias, B));
-      j.bias = LogitBiasTab{s->lb_val.as<float>(), V, s->t_src_of.as<int>()};
-    }
-    if (cls) {
-      TTX_TRY(syntax_upload(s, st, cls));
-      j.syntax = s->syn_cls.as<signed char>();
-    }
-    if (pre.prompted) {                 // the table by source, as the stochastic form keeps it
-      TTX_TRY(prefix_upload(s, st, pre, p->max_len, p->pad_token));
-      hipLaunchKernelGGL(k_sbs_prefix_src, dim3(cdiv(B, 256)), dim3(256), 0, st, s->smp_src_of.as<int>(), B);
-      HIP_TRY(hipGetLastError());
-      j.pfx = PrefixTab{s->pfx_tok.as<int>(), p->max_len, s->pfx_len_src.as<int>(), s->smp_src_of.as<int>()};
-    }
-    return bsearch_launch_iter(j);
-  };
-  const auto turn = [&](int) -> int {
-    if (j.phase == 1) {
-      if (((volatile BeamHost*)s->beam_host)->steps_done < j.launched) return TURN_WAITING;
-      TTX_TRY(bsearch_after_iter(j) ? bsearch_launch_iter(j) : bsearch_finish_enqueue(j));
-      return TURN_PROGRESSED;
-    }
-    if (hipEventQuery(s->ev_done) != hipSuccess) return TURN_IDLE;
-    const BeamCounters* cn = reinterpret_cast<const BeamCounters*>(s->host_state);
-    stats->model_calls = cn->model_calls; stats->running_rows = cn->running_cands; stats->out_width = j.width;
-    return TURN_FINISHED;
-  };
-  return drive_sessions(&s, 1, false, stream, start, turn);
+  ttx_sample_opts o = opts_of(d_prefix, ld_prefix, h_prefix_len, nullptr, 0, nullptr);
+  o.d_bias = d_bias; o.ld_bias = ld_bias;
+  return beam_generate("ttx_beam_generate_constrained", s, d_src, B, Ls, p, o, syntax, d_out, d_score, stats, stream);
 }
 
-// Stochastic beam search: the standard beam loop above with k_sbs_step (csrc/ttx_sbs.hip.h) where it launches k_beam_step.
-// ttx_sbs_generate and ttx_sbs_generate_ex: one body; a call with no filter and no prefix is the plain one, launch for launch.
+// The parameters and the filter of a stochastic beam search call over a model `cfg`, or TTX_ERR_INVALID: inv_T, and the filter as the
+// step kernel takes it (a null `f` is none; a top_p alone runs as top_k = 32, as the sampler runs it).  `who.call` names the refusals
+// of the parameters, `who.ex` those of the filter.
+static int sbs_validate(const Who& who, const ttx_config& cfg, const ttx_sbs_params* p, const ttx_sbs_filter* f, float* inv_T, int* top_k,
+                        float* top_p) {
+  const std::string w = who.call, x = who.ex;
+  const int V = cfg.vocab_size;
+  if (p->max_len <= 1) return fail(TTX_ERR_INVALID, w + ": max_len must exceed 1");
+  if (p->beam_size < 1 || p->beam_size > SBS_MAX_BEAM) return fail(TTX_ERR_INVALID, w + ": beam_size must lie in [1, 32]");
+  if (V > SBS_MAX_V) return fail(TTX_ERR_INVALID, w + ": vocab_size above 1024");
+  if (p->beam_size > V) return fail(TTX_ERR_INVALID, w + ": beam_size larger than the vocabulary");
+  if (!(p->temperature > 0.0f) || !std::isfinite(p->temperature)) return fail(TTX_ERR_INVALID, w + ": temperature must be finite and > 0");
+  *inv_T = 1.0f / p->temperature;
+  if (!(*inv_T > 0.0f) || !std::isfinite(*inv_T)) return fail(TTX_ERR_INVALID, w + ": 1 / temperature is not a positive finite fp32");
+  *top_k = 0; *top_p = 1.0f;
+  if (!f) return TTX_OK;
+  if (f->top_k < 0 || f->top_k > SAMPLE_MAX_KEEP) return fail(TTX_ERR_INVALID, x + ": top_k must be 0 or in [1, 32]");
+  if (!(f->top_p > 0.0f) || !(f->top_p <= 1.0f)) return fail(TTX_ERR_INVALID, x + ": top_p must be in (0, 1]");
+  *top_p = f->top_p;
+  *top_k = (f->top_k == 0 && f->top_p < 1.0f) ? SAMPLE_MAX_KEEP : f->top_k;
+  return TTX_OK;
+}
+
+// Stochastic beam search: the standard beam loop above with k_sbs_step (csrc/ttx_sbs.hip.h) where it launches k_beam_step; with a
+// filter on or a non-empty prefix k_sbs_step_masked.  A call with no filter, no prefix and no bias is the plain one, launch for launch.
 static int sbs_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sbs_params* p,
-                        int64_t* d_out, float* d_logp, float* d_gumbel, const ttx_sbs_trace* trace, ttx_beam_search_stats* stats,
-                        void* stream, const ttx_sbs_filter* f, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
-                        const float* d_bias = nullptr, int ld_bias = 0) {
+                        const ttx_sbs_filter* f, const ttx_sample_opts& o, int64_t* d_out, float* d_logp, float* d_gumbel,
+                        const ttx_sbs_trace* trace, ttx_beam_search_stats* stats, void* stream) {
+  const Who who("ttx_sbs_generate", "ttx_sbs_generate_ex", "ttx_sbs_generate_bias", "ttx_sbs_generate");
   if (!s || !d_src || !p || !d_out || !d_logp || !d_gumbel || !stats || B <= 0 || Ls <= 1)
     return fail(TTX_ERR_INVALID, "bad argument to ttx_sbs_generate");
-  TTX_TRY(bias_validate("ttx_sbs_generate_bias", s, d_bias, ld_bias));
-  const int V = s->m->cfg.vocab_size;
-  if (p->max_len <= 1) return fail(TTX_ERR_INVALID, "ttx_sbs_generate: max_len must exceed 1");
-  if (p->beam_size < 1 || p->beam_size > SBS_MAX_BEAM) return fail(TTX_ERR_INVALID, "ttx_sbs_generate: beam_size must lie in [1, 32]");
-  if (V > SBS_MAX_V) return fail(TTX_ERR_INVALID, "ttx_sbs_generate: vocab_size above 1024");
-  if (p->beam_size > V) return fail(TTX_ERR_INVALID, "ttx_sbs_generate: beam_size larger than the vocabulary");
-  if (!(p->temperature > 0.0f) || !std::isfinite(p->temperature)) return fail(TTX_ERR_INVALID, "ttx_sbs_generate: temperature must be finite and > 0");
-  const float inv_T = 1.0f / p->temperature;
-  if (!(inv_T > 0.0f) || !std::isfinite(inv_T)) return fail(TTX_ERR_INVALID, "ttx_sbs_generate: 1 / temperature is not a positive finite fp32");
+  float inv_T, top_p;
+  int top_k;
+  TTX_TRY(sbs_validate(who, s->m->cfg, p, f, &inv_T, &top_k, &top_p));
   if (trace && (!trace->d_parent || !trace->d_token || !trace->d_phi || !trace->d_g))
     return fail(TTX_ERR_INVALID, "ttx_sbs_generate: a trace needs all four arrays");
-  int top_k = 0;
-  float top_p = 1.0f;
-  if (f) {
-    if (f->top_k < 0 || f->top_k > SAMPLE_MAX_KEEP) return fail(TTX_ERR_INVALID, "ttx_sbs_generate_ex: top_k must be 0 or in [1, 32]");
-    if (!(f->top_p > 0.0f) || !(f->top_p <= 1.0f)) return fail(TTX_ERR_INVALID, "ttx_sbs_generate_ex: top_p must be in (0, 1]");
-    top_p = f->top_p;
-    top_k = (f->top_k == 0 && f->top_p < 1.0f) ? SAMPLE_MAX_KEEP : f->top_k;      // as the sampler runs a top_p alone
-  }
-  SampleSetup pre{};
-  TTX_TRY(prefix_validate("ttx_sbs_generate_ex", d_prefix, ld_prefix, h_prefix_len, B, p->max_len, &pre));
-  const bool masked = top_k > 0 || pre.prompted;
+  SampleSetup c{};
+  TTX_TRY(constraints_validate(who, s, o, nullptr, B, p->max_len, &c));
   ttx_beam_search_params bp{};
   bp.max_len = p->max_len; bp.beam_size = p->beam_size; bp.pad_token = p->pad_token; bp.bos_token = p->bos_token; bp.eos_token = p->eos_token;
   BeamSearchJob j;
-  const auto start = [&](int) -> int {
-    hipStream_t st = s->own_stream;
-    if (pre.prompted) {                 // sized before bsearch_start settles which graphs are current
-      TTX_TRY(ensure(s->pfx_tok, (size_t)B * p->max_len * 4, st));
-      TTX_TRY(ensure(s->pfx_len_src, (size_t)B * 4, st));
-      TTX_TRY(ensure(s->smp_src_of, (size_t)B * 4, st));
-    }
-    if (d_bias) TTX_TRY(ensure(s->lb_val, (size_t)B * V * sizeof(float), st));
-    TTX_TRY(bsearch_start(j, s, st, d_src, B, Ls, &bp, d_out, true));
-    if (d_bias) {                       // the steps run eagerly, yet read the session's copy as every biased loop does
-      TTX_TRY(bias_upload(s, st, d_bias, ld_bias, B));
-      j.bias = LogitBiasTab{s->lb_val.as<float>(), V, s->t_src_of.as<int>()};
-    }
+  return bsearch_drive(j, s, stats, stream, [&](int) -> int {
+    TTX_TRY(bsearch_constraints_ensure(s, s->own_stream, c, B, p->max_len));
+    TTX_TRY(bsearch_start(j, s, s->own_stream, d_src, B, Ls, &bp, d_out, true));
     j.inv_T = inv_T; j.seed = p->seed; j.row_keys = d_row_keys; j.d_logp = d_logp; j.d_gumbel = d_gumbel;
     if (trace) j.trace = *trace;
-    j.masked = masked; j.top_k = top_k; j.top_p = top_p;
-    if (pre.prompted) {                 // the table by source: int32 [B][max_len], the lengths, and every source's own row of it
-      TTX_TRY(prefix_upload(s, st, pre, p->max_len, p->pad_token));
-      hipLaunchKernelGGL(k_sbs_prefix_src, dim3(cdiv(B, 256)), dim3(256), 0, st, s->smp_src_of.as<int>(), B);
-      HIP_TRY(hipGetLastError());
-      j.pfx = PrefixTab{s->pfx_tok.as<int>(), p->max_len, s->pfx_len_src.as<int>(), s->smp_src_of.as<int>()};
-    }
+    j.masked = top_k > 0 || c.prompted; j.top_k = top_k; j.top_p = top_p;
+    TTX_TRY(bsearch_constraints_upload(j, c));
     return bsearch_launch_iter(j);
-  };
-  const auto turn = [&](int) -> int {
-    if (j.phase == 1) {
-      if (((volatile BeamHost*)s->beam_host)->steps_done < j.launched) return TURN_WAITING;
-      TTX_TRY(bsearch_after_iter(j) ? bsearch_launch_iter(j) : bsearch_finish_enqueue(j));
-      return TURN_PROGRESSED;
-    }
-    if (hipEventQuery(s->ev_done) != hipSuccess) return TURN_IDLE;
-    const BeamCounters* cn = reinterpret_cast<const BeamCounters*>(s->host_state);
-    stats->model_calls = cn->model_calls; stats->running_rows = cn->running_cands; stats->out_width = j.width;
-    return TURN_FINISHED;
-  };
-  return drive_sessions(&s, 1, false, stream, start, turn);
+  });
 }
 
 extern "C" int ttx_sbs_generate(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sbs_params* p,
                                 int64_t* d_out, float* d_logp, float* d_gumbel, const ttx_sbs_trace* trace, ttx_beam_search_stats* stats,
                                 void* stream) {
-  return sbs_generate(s, d_src, B, Ls, d_row_keys, p, d_out, d_logp, d_gumbel, trace, stats, stream, nullptr, nullptr, 0, nullptr);
+  return sbs_generate(s, d_src, B, Ls, d_row_keys, p, nullptr, NO_OPTS, d_out, d_logp, d_gumbel, trace, stats, stream);
 }
 
 extern "C" int ttx_sbs_generate_ex(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sbs_params* p,
                                    const ttx_sbs_filter* f_or_null, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
                                    int64_t* d_out, float* d_logp, float* d_gumbel, const ttx_sbs_trace* trace,
                                    ttx_beam_search_stats* stats, void* stream) {
-  return sbs_generate(s, d_src, B, Ls, d_row_keys, p, d_out, d_logp, d_gumbel, trace, stats, stream, f_or_null, d_prefix, ld_prefix,
-                      h_prefix_len);
+  return sbs_generate(s, d_src, B, Ls, d_row_keys, p, f_or_null, opts_of(d_prefix, ld_prefix, h_prefix_len, nullptr, 0, nullptr), d_out, d_logp,
+                      d_gumbel, trace, stats, stream);
 }
 
-// ttx_sbs_generate_ex under a per-source logit bias: k_logit_bias runs on every level's logits before the step kernel reads them.
+// The general form: ttx_sbs_generate_ex under a per-source logit bias, k_logit_bias on every level's logits before the step kernel
+// reads them.
 extern "C" int ttx_sbs_generate_bias(ttx_session* s, const int64_t* d_src, int B, int Ls, const int64_t* d_row_keys, const ttx_sbs_params* p,
                                      const ttx_sbs_filter* f_or_null, const int64_t* d_prefix, int ld_prefix, const int32_t* h_prefix_len,
                                      const float* d_bias, int ld_bias, int64_t* d_out, float* d_logp, float* d_gumbel,
                                      const ttx_sbs_trace* trace, ttx_beam_search_stats* stats, void* stream) {
-  return sbs_generate(s, d_src, B, Ls, d_row_keys, p, d_out, d_logp, d_gumbel, trace, stats, stream, f_or_null, d_prefix, ld_prefix,
-                      h_prefix_len, d_bias, ld_bias);
+  ttx_sample_opts o = opts_of(d_prefix, ld_prefix, h_prefix_len, nullptr, 0, nullptr);
+  o.d_bias = d_bias; o.ld_bias = ld_bias;
+  return sbs_generate(s, d_src, B, Ls, d_row_keys, p, f_or_null, o, d_out, d_logp, d_gumbel, trace, stats, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4261,10 +4222,10 @@ static int launch_sbs_step_pool_masked(ttx_session* s, hipStream_t st, const Sbs
   return launch_sbs_step_pool_masked_vpl<16>(st, sa, waves, s->attr_sbs_step_pool_masked[4]);
 }
 
-// The call's prefix arguments as sbsp_start uploads them (prompted false: nothing is uploaded)
+// What every pool of a call is started with; `c`: the call's constraints, of which the pool takes the prefix alone
 struct SbsPoolCall {
   const int32_t* h_len; const int64_t* d_row_keys; int S_total;
-  SampleSetup pre;
+  SampleSetup c;
   int64_t* d_out; float* d_logp; float* d_gumbel; int32_t* d_src_running;
 };
 
@@ -4274,7 +4235,7 @@ static int sbsp_start(SbsPoolJob& j, ttx_session* s, hipStream_t st, int C, int 
   const int d = c.embedding_dim, Ld = c.num_decoder_layers, K = p->beam_size, S = call.S_total;
   j = SbsPoolJob{};
   j.s = s; j.st = st; j.p = *p; j.C = C; j.K = K; j.MC = C * K; j.ld = p->max_len + 2; j.Lc = p->max_len + 2; j.Ls_cap = Ls_cap;
-  j.inv_T = inv_T; j.top_k = top_k; j.top_p = top_p; j.prompted = call.pre.prompted; j.masked = top_k > 0 || call.pre.prompted;
+  j.inv_T = inv_T; j.top_k = top_k; j.top_p = top_p; j.prompted = call.c.prompted; j.masked = top_k > 0 || call.c.prompted;
   const size_t MC = (size_t)j.MC, kv_row = (size_t)Ld * 2 * d;
   Needs need{st};
   need(s->tok_src, (size_t)C * Ls_cap * 4); need(s->valid_new, (size_t)C * Ls_cap); need(s->src_valid, (size_t)C * Ls_cap);
@@ -4290,7 +4251,7 @@ static int sbsp_start(SbsPoolJob& j, ttx_session* s, hipStream_t st, int C, int 
   need(s->sbs_g, MC * 4); need(s->sbs_g_next, MC * 4);
   need(s->sbp_slot, (size_t)C * (8 + 7 * 4)); need(s->sbp_len, (size_t)S * 4); need(s->bp_new_slot, (size_t)C * 4); need(s->bp_grp, 4 * 4);
   need(s->sbp_io, sizeof(SbsPoolIo));
-  if (j.prompted) { need(s->pfx_tok, (size_t)S * p->max_len * 4); need(s->pfx_len_src, (size_t)S * 4); }
+  if (need.rc == TTX_OK) need.rc = constraints_ensure(s, st, call.c, p->max_len, 0, 0, 0);
   need_step_workspaces(s, need, MC, (size_t)C * Ls_cap);
   s->graphs_current();
   TTX_TRY(need.rc);
@@ -4304,12 +4265,13 @@ static int sbsp_start(SbsPoolJob& j, ttx_session* s, hipStream_t st, int C, int 
   s->ev_used = 0;
   HIP_TRY(hipEventRecord(s->ev_a, st));
   HIP_TRY(hipMemcpyAsync(s->sbp_len.p, call.h_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
-  if (j.prompted) TTX_TRY(prefix_upload(s, st, call.pre, p->max_len, p->pad_token));
   SbsPoolArgs& a = j.a;
   a.C = C; a.K = K; a.max_len = p->max_len; a.ld = j.ld; a.Ls_cap = Ls_cap; a.pad = p->pad_token; a.bos = p->bos_token;
   a.key = s->sbp_slot.as<int64_t>();
   a.row_of = reinterpret_cast<int*>(a.key + C); a.level = a.row_of + C; a.nlive = a.row_of + 2 * C; a.nfin = a.row_of + 3 * C;
   a.pfx_len = a.row_of + 4 * C; a.pfx_src = a.row_of + 5 * C; a.run_acc = a.row_of + 6 * C;
+  ConstraintTabs t;                         // a slot's prefix length and its row of the table are written at admission
+  TTX_TRY(constraints_upload(s, st, call.c, p->max_len, p->pad_token, a.pfx_len, a.pfx_src, nullptr, &t));
   a.cand_next = s->bs_cand_next.as<int64_t>(); a.len_next = s->bs_len_next.as<int>(); a.fin_next = s->bs_fin_next.as<uint8_t>();
   a.phi_next = s->bs_logp_next.as<float>(); a.parent = s->bs_parent.as<int>(); a.parent_draft = s->bs_parent_draft.as<int>();
   a.cand_src_len = s->bp_cand_len.as<int>();
@@ -4325,7 +4287,7 @@ static int sbsp_start(SbsPoolJob& j, ttx_session* s, hipStream_t st, int C, int 
   sa.new_cand = a.cand_next; sa.new_phi = a.phi_next; sa.parent = a.parent; sa.new_len = a.len_next; sa.new_finished = a.fin_next;
   sa.parent_draft = a.parent_draft; sa.nfin = a.nfin;
   sa.top_k = top_k; sa.top_p = top_p;
-  if (j.prompted) sa.pfx = PrefixTab{s->pfx_tok.as<int>(), p->max_len, a.pfx_len, a.pfx_src};
+  sa.pfx = t.pfx;
   TTX_TRY(launch_sbsp_init(st, a, s->sbs_g.as<float>(), s->sbs_g_next.as<float>(), s->t_src_of.as<int>()));
   HIP_TRY(hipEventRecord(s->ev_b, st));
   j.phase = 1;
@@ -4394,25 +4356,13 @@ extern "C" int ttx_sbs_generate_pool(ttx_session** sessions, int n_sessions, con
   for (int i = 0; i < n_sessions; ++i) if (!sessions[i]) return fail(TTX_ERR_INVALID, who + ": null session");
   if (capacity < 1 || capacity > 1024) return fail(TTX_ERR_INVALID, who + ": capacity must lie in [1, 1024]");
   const ttx_config& c = sessions[0]->m->cfg;
-  const int V = c.vocab_size, K = p->beam_size;
-  if (p->max_len <= 1) return fail(TTX_ERR_INVALID, who + ": max_len must exceed 1");
-  if (K < 1 || K > SBS_MAX_BEAM) return fail(TTX_ERR_INVALID, who + ": beam_size must lie in [1, 32]");
-  if (V > SBS_MAX_V) return fail(TTX_ERR_INVALID, who + ": vocab_size above 1024");
-  if (K > V) return fail(TTX_ERR_INVALID, who + ": beam_size larger than the vocabulary");
-  if ((size_t)K * V * 4 > 150 * 1024) return fail(TTX_ERR_INVALID, who + ": beam_size x vocabulary beyond the selection kernel's LDS image");
-  if (!(p->temperature > 0.0f) || !std::isfinite(p->temperature)) return fail(TTX_ERR_INVALID, who + ": temperature must be finite and > 0");
-  const float inv_T = 1.0f / p->temperature;
-  if (!(inv_T > 0.0f) || !std::isfinite(inv_T)) return fail(TTX_ERR_INVALID, who + ": 1 / temperature is not a positive finite fp32");
+  float inv_T, top_p;
+  int top_k;
+  TTX_TRY(sbs_validate(who.c_str(), c, p, f, &inv_T, &top_k, &top_p));
+  if ((size_t)p->beam_size * c.vocab_size * 4 > 150 * 1024)
+    return fail(TTX_ERR_INVALID, who + ": beam_size x vocabulary beyond the selection kernel's LDS image");
   if (p->pad_token != c.pad_token) return fail(TTX_ERR_INVALID, who + ": generator pad token differs from the model's");
   if (p->max_len + 2 > c.max_positions) return fail(TTX_ERR_INVALID, who + ": max_len exceeds the positional table");
-  int top_k = 0;
-  float top_p = 1.0f;
-  if (f) {
-    if (f->top_k < 0 || f->top_k > SAMPLE_MAX_KEEP) return fail(TTX_ERR_INVALID, who + ": top_k must be 0 or in [1, 32]");
-    if (!(f->top_p > 0.0f) || !(f->top_p <= 1.0f)) return fail(TTX_ERR_INVALID, who + ": top_p must be in (0, 1]");
-    top_p = f->top_p;
-    top_k = (f->top_k == 0 && f->top_p < 1.0f) ? SAMPLE_MAX_KEEP : f->top_k;
-  }
   int len_max = 2;
   for (int i = 0; i < S_total; ++i) {
     if (h_len[i] < 2 || h_len[i] > Ls_all) return fail(TTX_ERR_INVALID, who + ": source length outside [2, width of the source matrix]");
@@ -4422,7 +4372,8 @@ extern "C" int ttx_sbs_generate_pool(ttx_session** sessions, int n_sessions, con
   if (Ls_cap > c.max_positions) return fail(TTX_ERR_INVALID, who + ": source longer than the positional table");
   SbsPoolCall call{};
   call.h_len = h_len; call.d_row_keys = d_row_keys; call.S_total = S_total; call.d_out = d_out; call.d_logp = d_logp; call.d_gumbel = d_gumbel;
-  TTX_TRY(prefix_validate(who.c_str(), d_prefix, ld_prefix, h_prefix_len, S_total, p->max_len, &call.pre));
+  TTX_TRY(constraints_validate(who.c_str(), sessions[0], opts_of(d_prefix, ld_prefix, h_prefix_len, nullptr, 0, nullptr), nullptr, S_total,
+                               p->max_len, &call.c));
   call.d_src_running = stats->d_src_running_rows;           // the one input of the block
   *stats = ttx_sbs_pool_stats{};
   stats->d_src_running_rows = call.d_src_running;

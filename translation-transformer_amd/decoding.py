@@ -530,7 +530,7 @@ class TranslationInferenceSampling(_ScoresHypotheses):
         d_cls = syn.table(m.tgt_vocab_size, m.device)
         for q in (prefix if isinstance(prefix, (list, tuple)) else [prefix]):
             syn.check_prefix(q, self.pad_token)
-        return syn, d_cls, C.byref(N.Syntax(d_cls.data_ptr(), int(self.max_len)))
+        return syn, d_cls, N.Syntax.arg(d_cls, self.max_len)
 
     def generate(self, src: torch.Tensor, row_keys=None, return_scores: bool = False, prefix=None, return_logq: bool = False,
                  logit_bias=None, allowed=None, syntax=None):
@@ -579,18 +579,9 @@ class TranslationInferenceSampling(_ScoresHypotheses):
                            self.eos_token, self.seed & 0xFFFFFFFFFFFFFFFF)
         out = torch.empty((B, max(n, 1), max(self.max_len, 1)), dtype=torch.int64, device=m.device)
         st = N.GenStats()
-        if syn is not None:
-            opts = N.SampleOpts.of(prefix_ptr, ld_prefix, h_plen, bias=bias)
-            N.check(m._lib.ttx_sample_generate_syntax(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
-                                                      C.byref(p), C.byref(opts), syn_arg, out.data_ptr(), C.byref(st), m._stream()))
-        elif bias is None:
-            N.check(m._lib.ttx_sample_generate_prefix(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
-                                                      C.byref(p), prefix_ptr, ld_prefix, h_plen, out.data_ptr(), C.byref(st),
-                                                      m._stream()))
-        else:
-            opts = N.SampleOpts.of(prefix_ptr, ld_prefix, h_plen, bias=bias)
-            N.check(m._lib.ttx_sample_generate_ex(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
-                                                  C.byref(p), C.byref(opts), out.data_ptr(), C.byref(st), m._stream()))
+        opts = N.SampleOpts.of(prefix_ptr, ld_prefix, h_plen, bias=bias)        # the general form: zeroed fields and a NULL syntax
+        N.check(m._lib.ttx_sample_generate_syntax(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
+                                                  C.byref(p), C.byref(opts), syn_arg, out.data_ptr(), C.byref(st), m._stream()))
         self.model_calls_num += int(st.model_calls)
         self.given_tokens += int((src != m.src_pad_token_i).sum())
         self.last_stats = st
@@ -661,21 +652,9 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
                                self.draft_len, self.n_drafts, self.replace_token, 0)
         out = torch.empty((B, max(n, 1), max(self.max_len, 1)), dtype=torch.int64, device=m.device)
         st = N.GenStats()
-        if syn is not None:
-            opts = N.SampleOpts.of(prefix_ptr, ld_prefix, h_plen, prop_ptr, ld_prop, h_qlen, bias)
-            N.check(m._lib.ttx_sample_speculative_generate_syntax(m.session, src.data_ptr(), B, Ls,
-                                                                  None if keys is None else keys.data_ptr(), C.byref(p), C.byref(opts),
-                                                                  syn_arg, out.data_ptr(), C.byref(st), m._stream()))
-        elif bias is None:
-            N.check(m._lib.ttx_sample_speculative_generate_proposal(m.session, src.data_ptr(), B, Ls,
-                                                                    None if keys is None else keys.data_ptr(), C.byref(p), prefix_ptr,
-                                                                    ld_prefix, h_plen, prop_ptr, ld_prop, h_qlen, out.data_ptr(),
-                                                                    C.byref(st), m._stream()))
-        else:
-            opts = N.SampleOpts.of(prefix_ptr, ld_prefix, h_plen, prop_ptr, ld_prop, h_qlen, bias)
-            N.check(m._lib.ttx_sample_speculative_generate_ex(m.session, src.data_ptr(), B, Ls,
-                                                              None if keys is None else keys.data_ptr(), C.byref(p), C.byref(opts),
-                                                              out.data_ptr(), C.byref(st), m._stream()))
+        opts = N.SampleOpts.of(prefix_ptr, ld_prefix, h_plen, prop_ptr, ld_prop, h_qlen, bias)
+        N.check(m._lib.ttx_sample_speculative_generate_syntax(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
+                                                              C.byref(p), C.byref(opts), syn_arg, out.data_ptr(), C.byref(st), m._stream()))
         self.model_calls_num += int(st.model_calls)
         self.accepted_tokens_num += int(st.accepted_tokens)
         self.given_tokens += int((src != m.src_pad_token_i).sum())
@@ -819,22 +798,10 @@ class TranslationInferenceSamplingSpeculative(TranslationInferenceSampling):
 
             pre_sorted, pre_ptr, ld_prefix, h_plen = table_args(allpre, plen)
             prop_sorted, prop_ptr, ld_prop, h_qlen = table_args(allprop, qlen)
-            if syn is not None:
-                bias_sorted = None if allbias is None else allbias[order_t].contiguous()
-                opts = N.SampleOpts.of(pre_ptr, ld_prefix, h_plen, prop_ptr, ld_prop, h_qlen, bias_sorted)
-                N.check(m._lib.ttx_sample_speculative_generate_pool_syntax(sess, len(sessions), src_mat.data_ptr(), S, width, h_len,
-                                                                           keys_sorted.data_ptr(), cap, C.byref(p), C.byref(opts),
-                                                                           syn_arg, out_sorted.data_ptr(), C.byref(st), m._stream()))
-            elif allbias is None:
-                N.check(m._lib.ttx_sample_speculative_generate_pool_proposal(sess, len(sessions), src_mat.data_ptr(), S, width, h_len,
-                                                                             keys_sorted.data_ptr(), cap, C.byref(p), pre_ptr, ld_prefix,
-                                                                             h_plen, prop_ptr, ld_prop, h_qlen, out_sorted.data_ptr(),
-                                                                             C.byref(st), m._stream()))
-            else:
-                bias_sorted = allbias[order_t].contiguous()
-                opts = N.SampleOpts.of(pre_ptr, ld_prefix, h_plen, prop_ptr, ld_prop, h_qlen, bias_sorted)
-                N.check(m._lib.ttx_sample_speculative_generate_pool_ex(sess, len(sessions), src_mat.data_ptr(), S, width, h_len,
-                                                                       keys_sorted.data_ptr(), cap, C.byref(p), C.byref(opts),
+            bias_sorted = None if allbias is None else allbias[order_t].contiguous()      # kept alive until the call returns
+            opts = N.SampleOpts.of(pre_ptr, ld_prefix, h_plen, prop_ptr, ld_prop, h_qlen, bias_sorted)
+            N.check(m._lib.ttx_sample_speculative_generate_pool_syntax(sess, len(sessions), src_mat.data_ptr(), S, width, h_len,
+                                                                       keys_sorted.data_ptr(), cap, C.byref(p), C.byref(opts), syn_arg,
                                                                        out_sorted.data_ptr(), C.byref(st), m._stream()))
             inv = torch.empty_like(order_t)
             inv[order_t] = torch.arange(S, device=m.device)
@@ -1088,16 +1055,12 @@ class TranslationInferenceStochasticBeamSearch(_ScoresHypotheses):
         st = N.BeamSearchStats()
         filt = N.SbsFilter(self.top_k, self.top_p)
         bias = combine_bias(logit_bias, allowed, B, m.tgt_vocab_size)
-        if bias is None:
-            N.check(m._lib.ttx_sbs_generate_ex(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(), C.byref(p),
-                                               C.byref(filt), prefix_ptr, ld_prefix, h_plen, out.data_ptr(), logp.data_ptr(),
-                                               gumbel.data_ptr(), tr_arg, C.byref(st), m._stream()))
-        else:
-            bias = bias.to(m.device).contiguous()
-            N.check(m._lib.ttx_sbs_generate_bias(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(),
-                                                 C.byref(p), C.byref(filt), prefix_ptr, ld_prefix, h_plen, bias.data_ptr(),
-                                                 int(bias.stride(0)), out.data_ptr(), logp.data_ptr(), gumbel.data_ptr(), tr_arg,
-                                                 C.byref(st), m._stream()))
+        if bias is not None:
+            bias = bias.to(m.device).contiguous()        # bound until the call returns; a NULL d_bias is the unbiased call
+        N.check(m._lib.ttx_sbs_generate_bias(m.session, src.data_ptr(), B, Ls, None if keys is None else keys.data_ptr(), C.byref(p),
+                                             C.byref(filt), prefix_ptr, ld_prefix, h_plen, None if bias is None else bias.data_ptr(),
+                                             0 if bias is None else int(bias.stride(0)), out.data_ptr(), logp.data_ptr(),
+                                             gumbel.data_ptr(), tr_arg, C.byref(st), m._stream()))
         self.model_calls_num += int(st.model_calls)
         self.b_sz += int(st.running_rows)
         self.given_tokens += int((src != m.src_pad_token_i).sum())

@@ -1323,34 +1323,22 @@ class NativeTransformer:
                              torch.empty(lead + (W - 1,), dtype=torch.float32, device=dev),
                              torch.empty(lead + (W - 1,), dtype=torch.int32, device=dev),
                              torch.empty(lead + (W - 1,), dtype=torch.int32, device=dev), None)
-        if syntax is not None:
-            from .scoring import check_logit_bias
-            from .syntax import as_syntax
-            bias = None if logit_bias is None else check_logit_bias(logit_bias, int(lead[0]), V).to(dev).contiguous()
-            d_cls = as_syntax(syntax).table(V, dev)
-            R = hyp.numel() // W
-            N.check(self._lib.ttx_hypothesis_logq_syntax(self._scoring_session(), x.data_ptr(), hyp.data_ptr(), R, W, V, int(pad),
-                                                         int(eos), C.byref(dist), self._ptr(forced), self._ptr(bias), V,
-                                                         R // max(int(lead[0]), 1), C.byref(N.Syntax(d_cls.data_ptr(), int(syntax_max_len))),
-                                                         out.token_logq.data_ptr(), out.logq.data_ptr(),
-                                                         out.first_outside.data_ptr(), out.rank.data_ptr(), out.n_kept.data_ptr(),
-                                                         out.length.data_ptr(), out.finished.data_ptr(), self._stream()))
-            out.logq.masked_fill_(out.first_outside >= 0, float("-inf"))     # see proposal_scores
-            return out
+        bias = d_cls = None                      # both bound until the call returns
         if logit_bias is not None:
             from .scoring import check_logit_bias
             bias = check_logit_bias(logit_bias, int(lead[0]), V).to(dev).contiguous()
-            R = hyp.numel() // W
-            N.check(self._lib.ttx_hypothesis_logq_bias(self._scoring_session(), x.data_ptr(), hyp.data_ptr(), R, W, V, int(pad),
-                                                       int(eos), C.byref(dist), self._ptr(forced), bias.data_ptr(), V,
-                                                       R // max(int(lead[0]), 1), out.token_logq.data_ptr(), out.logq.data_ptr(),
-                                                       out.first_outside.data_ptr(), out.rank.data_ptr(), out.n_kept.data_ptr(),
-                                                       out.length.data_ptr(), out.finished.data_ptr(), self._stream()))
-            return out
-        N.check(self._lib.ttx_hypothesis_logq(self._scoring_session(), x.data_ptr(), hyp.data_ptr(), hyp.numel() // W, W, V, int(pad),
-                                              int(eos), C.byref(dist), self._ptr(forced), out.token_logq.data_ptr(),
-                                              out.logq.data_ptr(), out.first_outside.data_ptr(), out.rank.data_ptr(),
-                                              out.n_kept.data_ptr(), out.length.data_ptr(), out.finished.data_ptr(), self._stream()))
+        if syntax is not None:
+            from .syntax import as_syntax
+            d_cls = as_syntax(syntax).table(V, dev)
+        R = hyp.numel() // W
+        # the general form: a NULL d_bias and a NULL syntax are the plain call
+        N.check(self._lib.ttx_hypothesis_logq_syntax(self._scoring_session(), x.data_ptr(), hyp.data_ptr(), R, W, V, int(pad), int(eos),
+                                                     C.byref(dist), self._ptr(forced), self._ptr(bias), V, R // max(int(lead[0]), 1),
+                                                     N.Syntax.arg(d_cls, syntax_max_len), out.token_logq.data_ptr(), out.logq.data_ptr(),
+                                                     out.first_outside.data_ptr(), out.rank.data_ptr(), out.n_kept.data_ptr(),
+                                                     out.length.data_ptr(), out.finished.data_ptr(), self._stream()))
+        if syntax is not None:
+            out.logq.masked_fill_(out.first_outside >= 0, float("-inf"))     # see proposal_scores
         return out
 
     def proposal_scores(self, src: torch.Tensor, hyp: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
@@ -1401,7 +1389,7 @@ class NativeTransformer:
         if syntax is not None:
             from .syntax import as_syntax
             d_cls = as_syntax(syntax).table(V, dev)
-            syn_arg = C.byref(N.Syntax(d_cls.data_ptr(), int(syntax_max_len) or W))
+            syn_arg = N.Syntax.arg(d_cls, int(syntax_max_len) or W)
         Wt, chunk = self._trim_and_chunk(hyp, eos, trim, max_rows)
         T, Tt = W - 1, Wt - 1
         cut = Wt != W
@@ -1430,12 +1418,7 @@ class NativeTransformer:
                     self._ptr(part[1]), self._ptr(part[2]), out.length[b0:b1].data_ptr(), out.finished[b0:b1].data_ptr(), stream)
             head = (sess, src[b0:b1].data_ptr(), nb, Ls, hyp[b0:b1].data_ptr(), W, K, Wt, eos, C.byref(dist),
                     None if forced is None else forced[b0:b1].data_ptr())
-            if syn_arg is not None:
-                N.check(self._lib.ttx_score_proposal_syntax(*head, None if bias is None else bias[b0:b1].data_ptr(), V, syn_arg, *tail))
-            elif bias is None:
-                N.check(self._lib.ttx_score_proposal(*head, *tail))
-            else:
-                N.check(self._lib.ttx_score_proposal_bias(*head, bias[b0:b1].data_ptr(), V, *tail))
+            N.check(self._lib.ttx_score_proposal_syntax(*head, None if bias is None else bias[b0:b1].data_ptr(), V, syn_arg, *tail))
             if cut:
                 for t, c in zip(full, part):
                     if t is not None:
