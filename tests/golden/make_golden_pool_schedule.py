@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Generate tests/golden/pool_schedule.npz: the schedule of the greedy slot pool and of the beam-speculative batch pool on ONE
 session of the tiny fixture model, recorded through the public C ABI alone (tests/util_pool_schedule.py holds the cases and says
-what is recorded).  Needs an MI355X.  Run it at the commit whose schedule is to be pinned: tests/test_gpu_pool_schedule.py then
-asserts exact equality with the file, so a change to the admission rule or to the polling order of the pools shows up there.
+what is recorded).  With `more` first, tests/golden/pool_schedule_more.npz instead: the stochastic-beam source pool and the sampling
+slot pool, recorded the same way (a file of its own, so that pool_schedule.npz stays as it was recorded).  Needs an MI355X.  Run it
+at the commit whose schedule is to be pinned: tests/test_gpu_pool_schedule.py then asserts exact equality with the file, so a change
+to the admission rule or to the polling order of the pools shows up there.
 
-Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_pool_schedule.py [OUT.npz]
+Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_pool_schedule.py [more] [OUT.npz]
 """
 import sys
 from pathlib import Path
@@ -21,11 +23,14 @@ import util_pool_schedule as U  # noqa: E402
 
 
 def main():
-    out = Path(sys.argv[1]) if len(sys.argv) > 1 else HERE / "pool_schedule.npz"
+    args = sys.argv[1:]
+    more = bool(args) and args[0] == "more"
+    record = U.record_more if more else U.record_all
+    out = Path(args[more]) if len(args) > more else HERE / ("pool_schedule_more.npz" if more else "pool_schedule.npz")
     assert tta.lib().ttx_device_count() >= 1, "needs a gfx950 device"
     model = U.make_model(tta)
-    rec = U.record_all(model)
-    again = U.record_all(model)                # the premise of the fixture: the schedule on one session is deterministic
+    rec = record(model)
+    again = record(model)                      # the premise of the fixture: the schedule on one session is deterministic
     for k, v in rec.items():
         assert np.array_equal(v, again[k]), f"{k} differs between two runs: not a deterministic schedule"
     model.close()

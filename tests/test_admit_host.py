@@ -1,6 +1,7 @@
-"""csrc/ttx_admit.h (the admission policy of the two pools) compiled for the host: admit_chunks against the rule of util_admit.py,
+"""csrc/ttx_admit.h (the admission policy of the pools) compiled for the host: admit_chunks against the rule of util_admit.py,
 plan_admission inside a simulated pool loop against the properties the pools rely on and against both rules it replaced,
-restated here from the two entry points it was factored out of."""
+restated here from the two entry points it was factored out of, and pool_step, the rule of a pool's turn, over whole calls on a
+fake device (tests/host/admit_host.cpp: ttx_host_pool_call) under the real polling core."""
 import ctypes
 import random
 import subprocess
@@ -27,6 +28,8 @@ def adm(tmp_path_factory):
     lib.ttx_host_pool_shape.restype = None
     lib.ttx_host_serial_quota.argtypes = [I32P] + [ctypes.c_int] * 4
     lib.ttx_host_plan_admission.argtypes = [I32P] + [ctypes.c_int] * 11
+    lib.ttx_host_pool_call.argtypes = [I32P] + [ctypes.c_int] * 4 + [ctypes.c_longlong, I32P, ctypes.c_int, I32P, ctypes.c_int, ctypes.c_int,
+                                       I32P, ctypes.c_int, I32P]
     return lib
 
 
@@ -108,9 +111,10 @@ def beam_take(first, n_batches, C, cursor_b, n_live, first_fill, i, n_jobs, n_ru
     return b_end - cursor_b
 
 
-def simulate(adm, rng, R_total, max_batch, n_jobs, C, serial):
+def simulate(adm, rng, R_total, max_batch, n_jobs, C, serial, script=None):
     """The pools' loop around plan_admission with a device that retires a random number of slots per step.  Returns the admissions
-    [(pool, first batch, batches)] after asserting the properties of every one."""
+    [(pool, first batch, batches)] after asserting the properties of every one.  `script` (a dict) receives the work list and what
+    the device retired, step by step."""
     sizes = []
     while sum(sizes) < R_total:
         sizes.append(min(rng.randint(1, max_batch), R_total - sum(sizes)))
@@ -155,7 +159,12 @@ def simulate(adm, rng, R_total, max_batch, n_jobs, C, serial):
                 assert cursor == (quota[i] if serial else n_batches), "a pool finished with its list not empty"
             else:
                 launched[i] = True
-                live[i] -= rng.randint(0, live[i])                       # one step: some slots retire
+                retired = rng.randint(0, live[i])                        # one step: some slots retire
+                live[i] -= retired
+                if script is not None:
+                    script.setdefault("retire", []).append(retired)
+    if script is not None:
+        script["first"] = first
     # every batch (so every row) exactly once and in list order
     assert [a[1] for a in admissions] == sorted(a[1] for a in admissions)
     assert sum(a[2] for a in admissions) == n_batches and cursor == n_batches
@@ -202,3 +211,112 @@ def test_first_fill_of_a_list_that_fits_is_split_evenly(adm):
     assert adm.ttx_host_plan_admission(first, 100, 16, 0, 16, 0, 1, 0, 4, 4, 0, -1) == 16
     assert adm.ttx_host_plan_admission(first, 100, 16, 90, 8, 8, 0, 1, 4, 4, 0, -1) == 3      # ceil(10 / 4)
     assert adm.ttx_host_plan_admission(first, 100, 16, 90, 3, 13, 0, 1, 4, 4, 0, -1) == 0      # below a quarter pool
+
+
+# ---- pool_step: whole calls on a fake device ------------------------------------------------------------------------------------
+WAIT, FAILED, STUCK, DRAIN, LAUNCH = range(5)
+FIELDS = ("job", "act", "first_batch", "n_take", "first_row", "rows", "n_live", "n_running", "cursor", "running_pools", "quota_end", "launched")
+
+
+def pool_call(adm, sizes, n_jobs, C, serial=False, max_launches=10 ** 6, looks=(), retire=(), error_at=0, first=None):
+    """-> (rc, [answer of every pool_step call, as a dict of FIELDS])"""
+    if first is None:
+        first = [0]
+        for sz in sizes:
+            first.append(first[-1] + sz)
+    cap = 1 << 16
+    log = (ctypes.c_int32 * (cap * len(FIELDS)))()
+    rc = ctypes.c_int32(99)
+    n = adm.ttx_host_pool_call(i32(first), len(first) - 1, n_jobs, C, int(serial), max_launches, i32(list(looks) or [0]), len(looks),
+                               i32(list(retire) or [0]), len(retire), error_at, log, cap, ctypes.byref(rc))
+    assert 0 < n <= cap
+    return rc.value, [dict(zip(FIELDS, log[k * len(FIELDS):(k + 1) * len(FIELDS)])) for k in range(n)]
+
+
+POOL_CASES = [([1] * 5, 1, 2), ([1] * 5, 2, 2), ([2, 1, 2], 1, 2), ([2, 1, 2], 2, 2)]      # batch sizes, pools, slots per pool
+
+
+@pytest.mark.parametrize("serial", [False, True])
+@pytest.mark.parametrize("sizes,n_jobs,C", POOL_CASES)
+def test_pool_step_runs_a_whole_call(adm, sizes, n_jobs, C, serial):
+    looks, retire = [0, 3, 1, 0, 2, 5, 0, 1], [1, 0, 2, 1, 1, 0, 2, 1, 1, 2, 1, 1]
+    rc, log = pool_call(adm, sizes, n_jobs, C, serial=serial, looks=looks, retire=retire + [C] * 8)
+    assert rc == 0 and not [a for a in log if a["act"] in (FAILED, STUCK)]
+    first = [sum(sizes[:b]) for b in range(len(sizes) + 1)]
+    # nothing is admitted or launched while unpublished: WAIT only, with the cursor and the counts untouched
+    cursor, launched, waits = 0, [0] * n_jobs, 0
+    for a in log:
+        if a["act"] == WAIT:
+            waits += 1
+            assert launched[a["job"]] > 0, "a WAIT with nothing in flight"
+            assert (a["cursor"], a["n_take"], a["rows"], a["n_live"], a["n_running"]) == (cursor, 0, 0, 0, 0), a
+        else:
+            assert a["first_batch"] == cursor and a["cursor"] == cursor + a["n_take"]
+        assert a["launched"] == launched[a["job"]]
+        cursor = a["cursor"]
+        launched[a["job"]] += a["act"] == LAUNCH
+    assert waits == sum(looks[:sum(launched)]), "the device publishes after its scripted number of looks"
+    # every batch exactly once, in order and whole
+    taken = [(a["first_batch"], a["n_take"], a["first_row"], a["rows"]) for a in log if a["n_take"]]
+    assert all(a["act"] == LAUNCH for a in log if a["n_take"]), "an admission is followed by a launch in the same turn"
+    pos = 0
+    for b0, n, r0, rows in taken:
+        assert b0 == pos and r0 == first[b0] and rows == first[b0 + n] - r0 and rows <= C
+        pos += n
+    assert pos == len(sizes) == cursor
+    # DRAIN exactly once per pool, at zero live, as the pool's last answer; the running pools count down with it
+    for i in range(n_jobs):
+        mine = [a for a in log if a["job"] == i]
+        assert [a["act"] for a in mine].count(DRAIN) == 1 and mine[-1]["act"] == DRAIN
+        assert (mine[-1]["n_live"], mine[-1]["n_take"]) == (0, 0)
+    assert all(a["n_live"] > 0 for a in log if a["act"] == LAUNCH)
+    drains = [a["running_pools"] for a in log if a["act"] == DRAIN]
+    assert drains == list(range(n_jobs - 1, -1, -1))
+    # serial: one pool after another, and their quotas partition the list
+    if serial:
+        assert [a["job"] for a in log] == sorted(a["job"] for a in log)
+        quotas = [[a for a in log if a["job"] == i][-1]["quota_end"] for i in range(n_jobs)]
+        assert quotas == sorted(quotas) and quotas[-1] == len(sizes)
+        for a in log:
+            if a["n_take"]:
+                lo = quotas[a["job"] - 1] if a["job"] else 0
+                assert lo <= a["first_batch"] and a["first_batch"] + a["n_take"] <= quotas[a["job"]]
+    else:
+        assert all(a["quota_end"] == -1 for a in log)
+
+
+def test_pool_step_error_word_fails_before_any_admission(adm):
+    # two slots, one row retires per iteration: the second look would admit row 2, but iteration 1 published the error word
+    rc, log = pool_call(adm, [1] * 5, 1, 2, retire=[1] * 9, looks=[2], error_at=1)
+    assert rc == -1 and [a["act"] for a in log] == [LAUNCH, WAIT, WAIT, FAILED]
+    assert (log[0]["n_take"], log[0]["cursor"]) == (2, 2)
+    assert (log[-1]["n_take"], log[-1]["rows"], log[-1]["cursor"]) == (0, 0, 2)
+    rc, log = pool_call(adm, [1] * 5, 1, 2, retire=[1] * 9)                    # the same call without it goes on admitting
+    assert rc == 0 and log[1]["act"] == LAUNCH and log[1]["n_take"] == 1
+
+
+@pytest.mark.parametrize("bound", [0, 1, 4])
+def test_pool_step_stuck_exactly_beyond_the_bound(adm, bound):
+    rc, log = pool_call(adm, [2, 1, 2], 1, 2, max_launches=bound)            # nothing ever retires
+    assert rc == -2
+    assert [a["act"] for a in log] == [LAUNCH] * (bound + 1) + [STUCK]         # launched 0 .. bound pass, bound + 1 is stuck
+    assert [a["launched"] for a in log] == list(range(bound + 2))
+    rc, log = pool_call(adm, [2, 1, 2], 1, 2, max_launches=3, retire=[2, 1, 2])     # three iterations: the bound is never met
+    assert rc == 0 and [a["act"] for a in log] == [LAUNCH] * 3 + [DRAIN]
+
+
+@pytest.mark.parametrize("serial", [False, True])
+def test_pool_step_admits_what_the_simulated_loop_admits(adm, serial):
+    """The inputs of test_plan_admission_in_a_simulated_pool_loop: pool_step under drive_jobs takes the batches that test's Python
+    loop takes with plan_admission alone, pool by pool."""
+    rng = random.Random(31 if serial else 17)
+    for case in range(600):
+        C = rng.choice([1, 2, 3, 4, 5, 7, 8, 16, 33, 64]) if case % 3 else rng.randint(1, 64)
+        R_total = rng.randint(1, 300)
+        max_batch = 1 if case % 2 == 0 else rng.randint(1, C)
+        n_jobs = rng.randint(1, 4)
+        script = {}
+        admissions = simulate(adm, rng, R_total, max_batch, n_jobs, C, serial, script)
+        rc, log = pool_call(adm, None, n_jobs, C, serial=serial, retire=script["retire"], first=script["first"])
+        assert rc == 0
+        assert [(a["job"], a["first_batch"], a["n_take"]) for a in log if a["n_take"]] == admissions, (case, C, R_total, n_jobs)

@@ -1,7 +1,7 @@
 """The cases of tests/test_gpu_pool_schedule.py and tests/golden/make_golden_pool_schedule.py: pool calls on ONE session of the tiny
-fixture model through the public C ABI.  On one session a pool's schedule is deterministic (one step in flight, the host decides
+fixture model through the public C ABI (greedy, beam, stochastic-beam and sampling pool).  On one session a pool's schedule is deterministic (one step in flight, the host decides
 after each publish), so everything recorded here is a pure function of the admission rule and the step policy: integer counters,
-the seven words of ttx_pool_last_counters, the per-row traces.  Times are not recorded."""
+the seven words of ttx_pool_last_counters, the per-row traces, the output tokens.  Times are not recorded."""
 import ctypes as C
 import os
 
@@ -22,6 +22,12 @@ GREEDY_CASES = {                      # name -> environment of the call
 # beam pool: six batches of 1 to 4 sources through 4 source slots
 BEAM_BATCHES, BEAM_CAPACITY = [[5, 0], [1], [3, 7, 2, 8], [4, 9, 6], [2], [6, 1]], 4
 BEAM_CASES = {"all_drafts": 0, "smart_drafts": 1}             # name -> smart_drafts_mode
+# the stochastic-beam source pool and the sampling slot pool (tests/golden/pool_schedule_more.npz): the ten fixture sources, longest
+# first, through 4 slots, so both pools are filled, refilled as rows retire and drained
+MORE_CAPACITY = 4
+SBS_MAX_LEN, SBS_BEAM, SBS_SEED = 30, 3, 0x5EED0B5C0FFEE
+SAMPLE_PER_SRC, SAMPLE_SEED = 2, 0x5A3B1E5EED          # 2 decoder rows per source: 4 slots hold two sources
+MORE_KEYS = [7, 1 << 40, 3, 99, 12345678901, 0, 5, (1 << 62) + 1, 42, 8]
 ENV_KEYS = ("TTX_ADMIT_ROWS", "TTX_TWO_PHASE", "TTX_TWO_PHASE_MIN_ROWS", "TTX_DRAFT_SELECT")
 
 
@@ -109,6 +115,65 @@ def beam_pool(model, case):
                                                                T_cap, C.byref(st), model._stream()))
     torch.cuda.synchronize()
     return {"stats": int_fields(st), "trace_len": tlen.cpu().numpy(), "summary": summ.cpu().numpy()}
+
+
+def sorted_sources(model):
+    """The ten fixture sources, longest first: (device matrix, host lengths, device keys)."""
+    fsrc, _, c_token, _ = fixture_tokens()
+    all_len = lengths_of(fsrc)
+    idx = sorted(range(fsrc.shape[0]), key=lambda r: -int(all_len[r]))
+    h_len = np.ascontiguousarray(all_len[idx])
+    src = fsrc[idx][:, :int(h_len.max())].contiguous().to(model.device)
+    keys = torch.tensor(MORE_KEYS[:len(idx)], dtype=torch.int64, device=model.device)
+    return src, h_len, keys, c_token
+
+
+def sbs_pool(model):
+    """-> {stats, src_running_rows, out} of ttx_sbs_generate_pool over the ten sources; stats holds model_calls, running_rows,
+    src_tokens_padded, live_slots and status."""
+    from translation_transformer_amd import _native as NA
+    src, h_len, keys, _ = sorted_sources(model)
+    S, width = src.shape
+    out = torch.zeros((S, SBS_BEAM, SBS_MAX_LEN), dtype=torch.int64, device=model.device)
+    logp = torch.zeros((S, SBS_BEAM), dtype=torch.float32, device=model.device)
+    gum = torch.zeros((S, SBS_BEAM), dtype=torch.float32, device=model.device)
+    per_src = torch.zeros((S,), dtype=torch.int32, device=model.device)
+    sess = (C.c_void_p * 1)(model.session_pool(1)[0].value)
+    p, st = NA.SbsParams(SBS_MAX_LEN, SBS_BEAM, 1.0, PAD, BOS, EOS, SBS_SEED), NA.SbsPoolStats()
+    st.d_src_running_rows = per_src.data_ptr()
+    with pool_env({}):
+        NA.check(model._lib.ttx_sbs_generate_pool(sess, 1, src.data_ptr(), S, width, h_len.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  keys.data_ptr(), MORE_CAPACITY, C.byref(p), None, None, 0, None, out.data_ptr(),
+                                                  logp.data_ptr(), gum.data_ptr(), C.byref(st), model._stream()))
+    torch.cuda.synchronize()
+    stats = np.array([st.model_calls, st.running_rows, st.src_tokens_padded, st.live_slots, st.status], dtype=np.int64)
+    return {"stats": stats, "src_running_rows": per_src.cpu().numpy(), "out": out.cpu().numpy()}
+
+
+def sampling_pool(model):
+    """-> {stats, counters, out} of ttx_sample_speculative_generate_pool over the ten sources, two keyed samples each."""
+    from translation_transformer_amd import _native as NA
+    src, h_len, keys, c_token = sorted_sources(model)
+    S, width = src.shape
+    out = torch.zeros((S, SAMPLE_PER_SRC, MAX_LEN), dtype=torch.int64, device=model.device)
+    sess = (C.c_void_p * 1)(model.session_pool(1)[0].value)
+    p = NA.SampleSpecParams(NA.SampleParams(MAX_LEN, SAMPLE_PER_SRC, 1.0, 0, 1.0, PAD, BOS, EOS, SAMPLE_SEED), 10, 3, c_token, 0)
+    st = NA.GenStats()
+    words = (C.c_int64 * 7)()
+    with pool_env({}):
+        NA.check(model._lib.ttx_sample_speculative_generate_pool(sess, 1, src.data_ptr(), S, width, h_len.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                                 keys.data_ptr(), MORE_CAPACITY, C.byref(p), out.data_ptr(), C.byref(st),
+                                                                 model._stream()))
+    torch.cuda.synchronize()
+    NA.check(model._lib.ttx_pool_last_counters(sess[0], words))
+    return {"stats": int_fields(st), "counters": np.array(list(words), dtype=np.int64), "out": out.cpu().numpy()}
+
+
+def record_more(model):
+    """The SBS-pool and the sampling-pool case, as the flat name -> array mapping of tests/golden/pool_schedule_more.npz."""
+    rec = {f"sbs__{k}": v for k, v in sbs_pool(model).items()}
+    rec.update({f"sampling__{k}": v for k, v in sampling_pool(model).items()})
+    return rec
 
 
 def record_all(model):

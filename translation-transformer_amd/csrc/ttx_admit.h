@@ -1,6 +1,7 @@
-// Host-only admission policy of the two pools (the greedy slot pool and the beam-speculative batch pool): how many pools a call
-// runs and how wide and deep they are, which batches of the work list a pool takes when it has free slots, and the length
-// buckets an admission is encoded in.  No HIP in here: tests/host/admit_host.cpp compiles it with g++.
+// Host-only admission policy of the slot pools (the greedy / sampling slot pool, the beam-speculative batch pool and the
+// stochastic-beam source pool): how many pools a call runs and how wide and deep they are, which batches of the work list a pool
+// takes when it has free slots, the length buckets an admission is encoded in, and pool_step, the one rule every pool's turn goes
+// by between two iterations.  No HIP in here: tests/host/admit_host.cpp compiles it with g++.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -76,6 +77,57 @@ inline int plan_admission(const int* first, int n_batches, int C, const AdmitSta
     ++end;
   }
   return end - a.cursor;
+}
+
+// One turn of a running pool, decided in one place.  The pool's turn (the lambda drive_jobs calls) reads its pinned words into a
+// PoolLook, asks pool_step, and acts on the answer with its own admit, launch and read-back calls: decide here, act at the call site.
+//   WAIT    the iteration in flight has not published: nothing was touched and nothing but `published` was read (the spin path: the
+//           caller's volatile read and one compare; of the answer only act and first_batch are set)
+//   FAILED  the device set its error word: nothing was admitted
+//   DRAIN   nothing is live and nothing was admitted: enqueue the read-back and go to the finishing phase
+//   LAUNCH  admit batches [first_batch, first_batch + n_take) = rows [first_row, first_row + rows) if n_take > 0, then launch the
+//           next iteration over n_live slots (n_running: the device's running count plus the admitted rows)
+//   STUCK   as LAUNCH, but the pool has launched more than max_launches iterations: fail ("failed to terminate"), admit nothing
+// pool_step settles the serial quota on the pool's first published turn, advances the list's cursor and counts the pool out of
+// list.n_running when it drains.  `launched` and `phase` are the caller's to advance, after it has acted: launched when an iteration
+// is enqueued, phase (1 running) when the read-back is.
+struct PoolList {      // one per call, shared by its pools
+  const int* first;
+  int n_batches;
+  int cursor;          // next batch of the work list
+  int n_jobs;          // pools of the call, all started before the first turn ...
+  int n_running;       // ... and those that have not drained yet (n_jobs at first)
+};
+inline PoolList pool_list(const int* first, int n_batches, int n_jobs) { return {first, n_batches, 0, n_jobs, n_jobs}; }
+struct PoolState { int launched = 0, phase = 0, quota_end = -1; };      // one per pool; phase: 0 not started, 1 running, 2 finishing, 3 done
+struct PoolLook {      // what the host just read from the pool's pinned words
+  bool published;      // steps_done has reached `launched`
+  bool error;          // looked at on every published turn, the first one included (the words are zeroed at the pool's start)
+  int n_live, n_running;      // read only when published; before the first launch `published` and both counts are ignored (nothing
+                              // in flight, counts 0)
+};
+struct PoolPlan {
+  enum Act { WAIT, FAILED, STUCK, DRAIN, LAUNCH } act;
+  int first_batch, n_take, first_row, rows, n_live, n_running;
+};
+// Inlined into every turn on purpose: out of line, each fruitless look of the spin loop paid for the call and for the PoolLook and
+// PoolPlan going through memory.
+__attribute__((always_inline)) inline PoolPlan pool_step(PoolState& p, PoolList& l, const PoolLook& look, int job, int C, bool serial, long long max_launches) {
+  const bool fresh = p.launched == 0;
+  PoolPlan plan{PoolPlan::WAIT, l.cursor, 0, 0, 0, 0, 0};
+  if (!fresh && !look.published) return plan;
+  plan.first_row = l.first[l.cursor];
+  if (look.error) { plan.act = PoolPlan::FAILED; return plan; }
+  const int n_live = fresh ? 0 : look.n_live;
+  if (serial && p.quota_end < 0) p.quota_end = serial_quota(l.first, l.n_batches, l.cursor, job, l.n_jobs);
+  plan.n_take = plan_admission(l.first, l.n_batches, C, {l.cursor, C - n_live, n_live, fresh, job, l.n_jobs, l.n_running, serial, p.quota_end});
+  l.cursor += plan.n_take;
+  plan.rows = l.first[l.cursor] - plan.first_row;
+  plan.n_live = n_live + plan.rows;
+  plan.n_running = (fresh ? 0 : look.n_running) + plan.rows;
+  if (plan.n_live == 0) { plan.act = PoolPlan::DRAIN; --l.n_running; }
+  else plan.act = p.launched > max_launches ? PoolPlan::STUCK : PoolPlan::LAUNCH;
+  return plan;
 }
 
 // Length buckets inside an admission.  An admission is encoded at the width of its longest row, so a chunk of 1 024 length-sorted

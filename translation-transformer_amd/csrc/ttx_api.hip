@@ -513,6 +513,14 @@ static void need_step_workspaces(ttx_session* s, Needs& need, size_t Mmax, size_
   need(s->slab, sizeof(float) * 16 * Macts * d);            // no allocation may happen inside a graph capture
 }
 
+// The source side of a pool of C slots of Ls_cap positions: the staging buffers of an admission and the slots' own copies.
+static void need_source_slots(ttx_session* s, Needs& need, int C, int Ls_cap) {
+  const ttx_config& c = s->m->cfg;
+  const size_t rows = (size_t)C * Ls_cap, kv_row = (size_t)c.num_decoder_layers * 2 * c.embedding_dim;
+  need(s->tok_src, rows * 4); need(s->valid_new, rows); need(s->src_valid, rows);
+  need(s->memory, rows * c.embedding_dim * 4); need(s->memkv_new, rows * kv_row * 4); need(s->memkv, rows * kv_row * 4);
+}
+
 extern "C" int ttx_encode_src(ttx_session* s, const int64_t* d_src, int B, int Ls, float* d_memory, void* stream) {
   if (!s || !d_src || !d_memory || B <= 0 || Ls <= 0) return fail(TTX_ERR_INVALID, "bad argument to ttx_encode_src");
   if (Ls > s->m->cfg.max_positions) return fail(TTX_ERR_INVALID, "source longer than the positional table");
@@ -1874,6 +1882,14 @@ static void collect_gemm_profile(ttx_session* s, hipStream_t st) {
   }
 }
 
+// What the finishing turns of the three pools share: the pool's device time (ev_a to ev_c) added to *decode_ms, and the GEMM event
+// pairs.  collect_gemm_profile reads and re-records the ev_pool pairs alone, never ev_a or ev_c, so the order of the two is free.
+static void pool_finish(ttx_session* s, hipStream_t st, double* decode_ms) {
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, s->ev_a, s->ev_c) == hipSuccess) *decode_ms += ms;
+  collect_gemm_profile(s, st);
+}
+
 static int gen_finish_collect(GenJob& j) {
   ttx_session* s = j.s;
   const DecState& hs = *s->host_state;
@@ -2518,12 +2534,9 @@ struct PoolJob {
   hipStream_t st = nullptr;
   GenCtx g{};
   int C = 0, Ls_cap = 0;
-  int launched = 0;
-  int phase = 0;            // 0 not started, 1 running, 2 finishing, 3 done
-  int admits = 0;
-  int quota_end = -1;       // serial (profiling) pass: end of this pool's share of the work list
+  PoolState pool;           // launched: steps whose accept and commit are enqueued (pool_step, ttx_admit.h)
   PoolIo io{};
-  long long admitted_rows = 0, src_tokens_padded = 0;
+  long long src_tokens_padded = 0;
   long long admit_rows = 0; // TTX_ADMIT_ROWS: padded encoder rows at which a sub-chunk of an admission closes; 0: one chunk per admission
   // two-phase verify step (DESIGN.md "Two-phase verify step"): a free choice per step, both forms give the same bits
   bool two_phase = true;    // TTX_TWO_PHASE=0: every step in one pass
@@ -2552,7 +2565,7 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
   const ttx_config& c = s->m->cfg;
   const int d = c.embedding_dim, Ld = c.num_decoder_layers;
   const int N = p->n_drafts, D = p->draft_len, D1 = D + 1, max_len = p->max_len;
-  j.s = s; j.st = st; j.C = C; j.Ls_cap = Ls_cap; j.launched = 0; j.admits = 0; j.admitted_rows = 0; j.src_tokens_padded = 0;
+  j.s = s; j.st = st; j.C = C; j.Ls_cap = Ls_cap; j.pool = PoolState{}; j.src_tokens_padded = 0;
   s->snap_step = 0;
   GenCtx& g = j.g;
   g = GenCtx{};
@@ -2560,10 +2573,8 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
   g.k.Lc = max_len + D1;
   g.k.gen_ld = max_len + D + 2;
   const size_t Mmax = (size_t)C * step_rps(N, D);
-  const size_t kv_row = (size_t)Ld * 2 * d;
   Needs need{st};
-  need(s->tok_src, (size_t)C * Ls_cap * 4); need(s->valid_new, (size_t)C * Ls_cap); need(s->src_valid, (size_t)C * Ls_cap);
-  need(s->memory, (size_t)C * Ls_cap * d * 4); need(s->memkv_new, (size_t)C * Ls_cap * kv_row * 4); need(s->memkv, (size_t)C * Ls_cap * kv_row * 4);
+  need_source_slots(s, need, C, Ls_cap);
   need(s->drafts, (size_t)C * N * D * 4); need(s->drafts_new, (size_t)C * N * D * 4);
   need(s->gen, (size_t)C * g.k.gen_ld * 4);
   for (Buf* b : {&s->front, &s->act_idx, &s->haspad, &s->rstep, &s->row_of, &s->src_len, &s->new_slot}) need(*b, (size_t)C * 4);
@@ -2628,7 +2639,7 @@ static int pool_start(PoolJob& j, ttx_session* s, hipStream_t st, int C, int Ls_
   s->host_info->stop = 0; s->host_info->steps_done = 0; s->host_info->width = 1; s->host_info->n_active = 0;
   hipLaunchKernelGGL(k_pool_init, dim3(4), dim3(256), 0, st, g.la);
   HIP_TRY(hipGetLastError());
-  j.phase = 1;
+  j.pool.phase = 1;
   return TTX_OK;
 }
 
@@ -2668,8 +2679,6 @@ static int pool_admit(PoolJob& j, const int64_t* d_src_rows, int ld_src, int R, 
   if (step_tab(k).tok) { f.draft0 = s->pfx_draft0.as<int>(); f.D = k.D; }
   hipLaunchKernelGGL(k_pool_fill, dim3(rows, 1 + Ls_new), dim3(256), 0, st, f);
   HIP_TRY(hipGetLastError());
-  ++j.admits;
-  j.admitted_rows += rows;
   j.src_tokens_padded += (long long)R * Ls_new;
   return TTX_OK;
 }
@@ -2701,7 +2710,7 @@ static int pool_launch_step(PoolJob& j, int n_live) {
       TTX_TRY(run_step(s, j.st, k, kcap));
       return launch_accept_and_commit(s, j.st, j.g, false);
     }));
-    ++j.launched;
+    ++j.pool.launched;
     j.rows_executed += rows; j.unsplit_rows += rows;
     return TTX_OK;
   }
@@ -2762,7 +2771,7 @@ static int pool_launch_drafts(PoolJob& j) {
     return launch_accept_and_commit(s, j.st, j.g2, false);
   }));
   j.probe_pending = false;
-  ++j.launched;
+  ++j.pool.launched;
   return TTX_OK;
 }
 
@@ -2802,13 +2811,14 @@ static int pool_generate(ttx_session** sessions, int n_sessions, const int64_t* 
   const int n_jobs = shape.n_jobs, C = shape.C;
   std::vector<int> first(R_total + 1);
   for (int r = 0; r <= R_total; ++r) first[r] = r * per;
+  PoolList list = pool_list(first.data(), R_total, n_jobs);
   std::vector<PoolJob> jobs(n_jobs);
   std::vector<int> chunk_ends;
   std::fill(std::begin(sessions[0]->pool_counters), std::end(sessions[0]->pool_counters), 0LL);
   // profiling sessions (bench.py's roofline pass): the pools run ONE AFTER ANOTHER, so that the event pair around a GEMM launch
   // measures that launch and not the kernels of three other pools sharing the device with it
   const bool serial = sessions[0]->profile;
-  int cursor = 0;
+  const long long max_launches = (long long)(p->max_len + 2) * (R_total + 1);
   const auto start = [&](int i) -> int {
     TTX_TRY(pool_start(jobs[i], sessions[i], sessions[i]->own_stream, C, Ls_cap, p, d_out, d_traj, d_fin_step, smp));
     // every pool of a call has the same model and reads the same environment: the mode is the call's
@@ -2819,36 +2829,37 @@ static int pool_generate(ttx_session** sessions, int n_sessions, const int64_t* 
     PoolJob& j = jobs[i];
     ttx_session* s = j.s;
     volatile HostInfo* hi = s->host_info;
-    if (j.phase == 1) {
+    if (j.pool.phase == 1) {
       if (j.probe_pending) {
         if (((volatile ProbeInfo*)s->probe_info)->probes_done < j.probes) return TURN_WAITING;
         TTX_TRY(pool_launch_drafts(j));
         return TURN_PROGRESSED;
       }
-      if (j.launched > 0 && hi->steps_done < j.launched) return TURN_WAITING;       // the step in flight has not published yet
-      int n_act = (j.launched == 0) ? 0 : hi->n_active;
-      if (serial && j.quota_end < 0) j.quota_end = serial_quota(first.data(), R_total, cursor, i, n_jobs);
-      int n_running = 0;
-      for (const PoolJob& o : jobs) n_running += (o.phase == 1);
-      const int take = plan_admission(first.data(), R_total, C, {cursor, C - n_act, n_act, j.launched == 0, i, n_jobs, n_running, serial, j.quota_end});
-      if (take > 0) {
-        // every sub-chunk at the width of its own longest row; the staging buffers are the stream's, one sub-chunk after another
-        admit_chunks(h_len + cursor, take, j.admit_rows, chunk_ends);
-        int r0 = cursor;
-        for (const int end : chunk_ends) {
-          const int r1 = cursor + end;
-          TTX_TRY(pool_admit(j, d_src + (size_t)r0 * Ls_all, Ls_all, r1 - r0, chunk_width(h_len, r0, r1), r0, d_out, d_traj, d_fin_step));
-          r0 = r1;
-        }
-        n_act += first[cursor + take] - first[cursor];
-        cursor += take;
-      }
-      if (n_act == 0) {
-        TTX_TRY(enqueue_readback(s, j.st, s->state.p, sizeof(DecState)));
-        j.phase = 2;
-      } else {
-        if (j.launched > (long long)(p->max_len + 2) * (R_total + 1)) return fail(TTX_ERR_HIP, "decode loop failed to terminate");
-        TTX_TRY(pool_launch_step(j, n_act));
+      PoolLook look{hi->steps_done >= j.pool.launched, false, 0, 0};      // the error word is read with the counters, at collect time
+      if (look.published) look.n_live = look.n_running = hi->n_active;
+      const PoolPlan plan = pool_step(j.pool, list, look, i, C, serial, max_launches);
+      switch (plan.act) {
+        case PoolPlan::WAIT: return TURN_WAITING;
+        case PoolPlan::FAILED:                        // not reached while look.error is false
+          return fail(TTX_ERR_HIP, "slot pool bookkeeping failed (admitted more rows than free slots)");
+        case PoolPlan::STUCK: return fail(TTX_ERR_HIP, "decode loop failed to terminate");
+        case PoolPlan::DRAIN:
+          TTX_TRY(enqueue_readback(s, j.st, s->state.p, sizeof(DecState)));
+          j.pool.phase = 2;
+          break;
+        case PoolPlan::LAUNCH:
+          if (plan.n_take > 0) {
+            // every sub-chunk at the width of its own longest row; the staging buffers are the stream's, one sub-chunk after another
+            admit_chunks(h_len + plan.first_batch, plan.n_take, j.admit_rows, chunk_ends);
+            int r0 = plan.first_batch;
+            for (const int end : chunk_ends) {
+              const int r1 = plan.first_batch + end;
+              TTX_TRY(pool_admit(j, d_src + (size_t)r0 * Ls_all, Ls_all, r1 - r0, chunk_width(h_len, r0, r1), r0, d_out, d_traj, d_fin_step));
+              r0 = r1;
+            }
+          }
+          TTX_TRY(pool_launch_step(j, plan.n_live));
+          break;
       }
       return TURN_PROGRESSED;
     }
@@ -2857,19 +2868,17 @@ static int pool_generate(ttx_session** sessions, int n_sessions, const int64_t* 
     if (stats) {
       add_counters(*stats, hs);
       stats->src_tokens_padded += j.src_tokens_padded;
-      collect_gemm_profile(s, j.st);
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, s->ev_a, s->ev_c) == hipSuccess) stats->decode_ms += ms;
+      pool_finish(s, j.st, &stats->decode_ms);
     }
     if (getenv("TTX_TWO_PHASE_STATS"))
       fprintf(stderr, "[ttx two-phase] pool %d: %d steps, %lld split (%lld without a draft pass), %lld slot-steps probed, %lld matched, "
                       "%lld draft rows executed, %lld drafts matched\n",      // draft select off: N drafts per matching slot
-              i, j.launched, j.split_steps, j.skipped_draft_passes, j.slot_steps, j.matched_slot_steps,
+              i, j.pool.launched, j.split_steps, j.skipped_draft_passes, j.slot_steps, j.matched_slot_steps,
               j.rows_executed - j.slot_steps - j.unsplit_rows, j.drafts_matched);
     long long* pc = sessions[0]->pool_counters;
-    pc[0] += j.launched; pc[1] += j.split_steps; pc[2] += j.slot_steps; pc[3] += j.matched_slot_steps;
+    pc[0] += j.pool.launched; pc[1] += j.split_steps; pc[2] += j.slot_steps; pc[3] += j.matched_slot_steps;
     pc[4] += j.drafts_matched; pc[5] += j.rows_executed;
-    j.phase = 3;
+    j.pool.phase = 3;
     if (hs.error == 3) return fail(TTX_ERR_ROW_REPLAY, "a row emitted PAD inside its sequence: decode the batches as given");
     if (hs.error) return fail(TTX_ERR_HIP, "slot pool bookkeeping failed (admitted more rows than free slots)");
     return TURN_FINISHED;
@@ -3506,12 +3515,28 @@ struct BeamPoolJob {
   bool smart = false;
   BeamPoolArgs a{};
   BeamPoolIo io{};
-  int launched = 0, cur = 0;
-  int phase = 0;                    // 0 not started, 1 running, 2 finishing, 3 done
-  int admitted_since = 0;           // sources admitted since the last published iteration
-  int quota_b = -1;                 // serial (profiling) pass: end (batch index) of this pool's share of the work list
-  long long src_tokens_padded = 0, admitted_rows = 0;
+  PoolState pool;                   // launched: iterations enqueued (pool_step, ttx_admit.h)
+  int cur = 0;
+  long long src_tokens_padded = 0;
 };
+
+// What the beam pool and the stochastic beam pool start with: the session's pinned BeamPoolHost words (allocated once) zeroed and
+// their device address in *dev_host, the GEMM event pairs rewound, the start of the pool's device time recorded.
+static int pool_host_begin(ttx_session* s, hipStream_t st, BeamPoolHost** dev_host) {
+  if (!s->bp_host && hipHostMalloc((void**)&s->bp_host, sizeof(BeamPoolHost), hipHostMallocMapped) != hipSuccess)
+    return fail(TTX_ERR_NOMEM, "hipHostMalloc failed");
+  std::memset(s->bp_host, 0, sizeof(BeamPoolHost));
+  HIP_TRY(hipHostGetDevicePointer((void**)dev_host, (void*)s->bp_host, 0));
+  s->ev_used = 0;
+  HIP_TRY(hipEventRecord(s->ev_a, st));
+  return TTX_OK;
+}
+
+// A look at those words for pool_step: the counts only once the iteration in flight has published.
+static PoolLook pool_look(const volatile BeamPoolHost* bh, int launched) {
+  if (bh->steps_done < launched) return {false, false, 0, 0};
+  return {true, bh->error != 0, bh->n_live, bh->n_running};
+}
 
 // The pool's eight bookkeeping launches (bpool_start, bpool_admit, bpool_enqueue_iter; one at a time: ttx_debug_bsp).
 static int launch_bsp_init(hipStream_t st, const BeamPoolArgs& a, int* src_of, int* cand_src_len) {
@@ -3596,10 +3621,8 @@ static int bpool_start(BeamPoolJob& j, ttx_session* s, hipStream_t st, int C, in
   j.MC = C * j.K;
   const size_t MC = (size_t)j.MC;
   const size_t Mmax = MC * step_rps(j.N, j.D0);
-  const size_t kv_row = (size_t)Ld * 2 * d;
   Needs need{st};
-  need(s->tok_src, (size_t)C * Ls_cap * 4); need(s->valid_new, (size_t)C * Ls_cap); need(s->src_valid, (size_t)C * Ls_cap);
-  need(s->memory, (size_t)C * Ls_cap * d * 4); need(s->memkv_new, (size_t)C * Ls_cap * kv_row * 4); need(s->memkv, (size_t)C * Ls_cap * kv_row * 4);
+  need_source_slots(s, need, C, Ls_cap);
   need(s->bp_tok, (size_t)C * Ls_cap * 4);
   need(s->bp_enc_qkv, (size_t)C * Ls_cap * 3 * d * 4);      // admissions must not touch the step's Q/K/V rows (see run_encoder)
   need(s->drafts_new, (size_t)C * j.N * j.D0 * 4); need(s->bs_drafts_src, (size_t)C * j.N * j.D0 * 4);
@@ -3626,15 +3649,8 @@ static int bpool_start(BeamPoolJob& j, ttx_session* s, hipStream_t st, int C, in
   TTX_TRY(need.rc);
   if ((size_t)j.K * dl1 > 1023 || 2 * (size_t)j.K * dl1 * j.K * 4 > 150 * 1024)
     return fail(TTX_ERR_INVALID, "too many leaves per source for the selection kernel's LDS image");
-  if (!s->bp_host) {
-    if (hipHostMalloc((void**)&s->bp_host, sizeof(BeamPoolHost), hipHostMallocMapped) != hipSuccess)
-      return fail(TTX_ERR_NOMEM, "hipHostMalloc failed");
-  }
-  std::memset(s->bp_host, 0, sizeof(BeamPoolHost));
   BeamPoolHost* dev_host = nullptr;
-  HIP_TRY(hipHostGetDevicePointer((void**)&dev_host, (void*)s->bp_host, 0));
-  s->ev_used = 0;
-  HIP_TRY(hipEventRecord(s->ev_a, st));
+  TTX_TRY(pool_host_begin(s, st, &dev_host));
   // the caller-side pointer block and the work list's lengths live in one device allocation:
   // [BeamPoolIo][len_all: R_total][batch_all: R_total][given_all: n_batches]
   char* io_dev = s->bp_io.as<char>();
@@ -3669,7 +3685,7 @@ static int bpool_start(BeamPoolJob& j, ttx_session* s, hipStream_t st, int C, in
   a.cnt = s->bs_cnt.as<BeamCounters>(); a.io = reinterpret_cast<const BeamPoolIo*>(io_dev); a.host = dev_host; a.dev_summary = s->bp_grp.as<int>();
   TTX_TRY(launch_bsp_init(st, a, s->t_src_of.as<int>(), s->bp_cand_len.as<int>()));
   HIP_TRY(hipEventRecord(s->ev_b, st));
-  j.phase = 1;
+  j.pool.phase = 1;
   return TTX_OK;
 }
 
@@ -3686,8 +3702,6 @@ static int bpool_admit(BeamPoolJob& j, const int64_t* d_src_rows, int ld_src, in
   TTX_TRY(launch_bsp_fill(st, bsp_fill_args(j.a, s->bp_new_slot.as<int>(), R, first_row, Ls_new, s->tok_src.as<int>(), s->src_valid.as<uint8_t>(),
                                             s->valid_new.as<uint8_t>(), j.smart ? nullptr : s->drafts_new.as<int>(), s->memkv.as<float>(),
                                             s->memkv_new.as<float>(), kv_row)));
-  j.admitted_rows += R;
-  j.admitted_since += R;
   j.src_tokens_padded += (long long)R * Ls_new;
   return TTX_OK;
 }
@@ -3718,9 +3732,8 @@ static int bpool_launch_iter(BeamPoolJob& j, int n_running) {
   const GraphKey key{GS_BEAM_POOL_ITER, j.C, j.Ls_cap, j.K, j.N, j.D0, j.smart ? 1 : 0, j.p.max_len, j.cur, variant, j.p.pad_token,
                      j.p.bos_token, j.p.eos_token, j.p.replace_token, j.p.max_steps};
   TTX_TRY(graph_replay(s, j.st, s->iter_graphs, key, [&]() -> int { return bpool_enqueue_iter(j, variant); }));
-  ++j.launched;
+  ++j.pool.launched;
   j.cur ^= 1;
-  j.admitted_since = 0;
   return TTX_OK;
 }
 
@@ -3758,9 +3771,10 @@ extern "C" int ttx_beam_speculative_generate_pool(ttx_session** sessions, int n_
   const int n_jobs = shape.n_jobs, C = shape.C;
   BeamPoolIo io{};
   io.out = d_out; io.trace_len = d_trace_len; io.summary = d_summary; io.T_cap = trace_cap;
+  PoolList list = pool_list(first.data(), n_batches, n_jobs);
   std::vector<BeamPoolJob> jobs(n_jobs);
   const bool serial = sessions[0]->profile;                    // profiling sessions: one pool after another (see the greedy pool)
-  int cursor_b = 0;                                            // next batch of the work list
+  const long long max_launches = (long long)(trace_cap + 2) * (R_total + 1);
   const auto t_call = std::chrono::steady_clock::now();
   ttx_beam_stats acc{};
   const auto start = [&](int i) -> int {
@@ -3769,43 +3783,34 @@ extern "C" int ttx_beam_speculative_generate_pool(ttx_session** sessions, int n_
   const auto turn = [&](int i) -> int {
     BeamPoolJob& j = jobs[i];
     ttx_session* s = j.s;
-    volatile BeamPoolHost* bh = s->bp_host;
-    if (j.phase == 1) {
-      if (j.launched > 0 && bh->steps_done < j.launched) return TURN_WAITING;       // the iteration in flight has not published yet
-      if (bh->error) return fail(TTX_ERR_HIP, "batch pool bookkeeping failed (admitted more sources than free slots)");
-      int n_live = (j.launched == 0 ? 0 : bh->n_live) + j.admitted_since;
-      int n_running = (j.launched == 0 ? 0 : bh->n_running) + j.admitted_since;
-      if (serial && j.quota_b < 0) j.quota_b = serial_quota(first.data(), n_batches, cursor_b, i, n_jobs);
-      int n_run_jobs = 0;
-      for (const BeamPoolJob& o : jobs) n_run_jobs += (o.phase == 1);
-      const int n_take = plan_admission(first.data(), n_batches, C, {cursor_b, C - n_live, n_live, j.launched == 0, i, n_jobs, n_run_jobs, serial, j.quota_b});
-      if (n_take > 0) {
-        const int r_first = first[cursor_b], take = first[cursor_b + n_take] - r_first;
-        TTX_TRY(bpool_admit(j, d_src + (size_t)r_first * Ls_all, Ls_all, take, chunk_width(h_len, r_first, r_first + take), r_first));
-        cursor_b += n_take;
-        n_live += take;
-        n_running += take;
-      }
-      if (n_live == 0) {
-        TTX_TRY(enqueue_readback(s, j.st, s->bs_cnt.p, sizeof(BeamCounters)));
-        j.phase = 2;
-      } else {
-        if (j.launched > (long long)(trace_cap + 2) * (R_total + 1)) return fail(TTX_ERR_HIP, "batch pool failed to terminate");
-        if (s->host_timing)
-          fprintf(stderr, "[ttx pool %d] t=%.3f ms iteration %d: %d live sources, %d running candidates, next batch %d of %d\n", i,
-                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(), j.launched + 1, n_live,
-                  n_running, cursor_b, n_batches);
-        TTX_TRY(bpool_launch_iter(j, n_running));
+    if (j.pool.phase == 1) {
+      const PoolPlan plan = pool_step(j.pool, list, pool_look(s->bp_host, j.pool.launched), i, C, serial, max_launches);
+      switch (plan.act) {
+        case PoolPlan::WAIT: return TURN_WAITING;
+        case PoolPlan::FAILED: return fail(TTX_ERR_HIP, "batch pool bookkeeping failed (admitted more sources than free slots)");
+        case PoolPlan::STUCK: return fail(TTX_ERR_HIP, "batch pool failed to terminate");
+        case PoolPlan::DRAIN:
+          TTX_TRY(enqueue_readback(s, j.st, s->bs_cnt.p, sizeof(BeamCounters)));
+          j.pool.phase = 2;
+          break;
+        case PoolPlan::LAUNCH:
+          if (plan.n_take > 0)
+            TTX_TRY(bpool_admit(j, d_src + (size_t)plan.first_row * Ls_all, Ls_all, plan.rows,
+                                chunk_width(h_len, plan.first_row, plan.first_row + plan.rows), plan.first_row));
+          if (s->host_timing)
+            fprintf(stderr, "[ttx pool %d] t=%.3f ms iteration %d: %d live sources, %d running candidates, next batch %d of %d\n", i,
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(), j.pool.launched + 1,
+                    plan.n_live, plan.n_running, list.cursor, n_batches);
+          TTX_TRY(bpool_launch_iter(j, plan.n_running));
+          break;
       }
       return TURN_PROGRESSED;
     }
     if (hipEventQuery(s->ev_done) != hipSuccess) return TURN_IDLE;
     add_counters(acc, *reinterpret_cast<const BeamCounters*>(s->host_state));
     acc.src_tokens_padded += j.src_tokens_padded;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev_a, s->ev_c) == hipSuccess) acc.decode_ms += ms;
-    collect_gemm_profile(s, j.st);
-    j.phase = 3;
+    pool_finish(s, j.st, &acc.decode_ms);
+    j.pool.phase = 3;
     return TURN_FINISHED;
   };
   acc.status = drive_sessions(sessions, n_jobs, serial, stream, start, turn);
@@ -4150,10 +4155,8 @@ struct SbsPoolJob {
   int top_k = 0; float top_p = 1.f;
   SbsPoolArgs a{};                  // g_in / g_out unset: sbsp_args(j, parity) fills them
   SbsPoolStepArgs sa{};             // g / new_g likewise
-  int launched = 0, cur = 0;        // cur: the parity of the iteration to come (cache buffer read, G buffer read)
-  int phase = 0;                    // 0 not started, 1 running, 2 finishing, 3 done
-  int admitted_since = 0;           // sources admitted since the last published iteration
-  int quota_end = -1;               // serial (profiling) pass: end of this pool's share of the list
+  PoolState pool;                   // launched: iterations enqueued (pool_step, ttx_admit.h)
+  int cur = 0;                      // the parity of the iteration to come (cache buffer read, G buffer read)
   long long src_tokens_padded = 0, live_slots = 0;
   SbsPoolIo io{};                   // host image of the session's device block
 };
@@ -4236,10 +4239,9 @@ static int sbsp_start(SbsPoolJob& j, ttx_session* s, hipStream_t st, int C, int 
   j = SbsPoolJob{};
   j.s = s; j.st = st; j.p = *p; j.C = C; j.K = K; j.MC = C * K; j.ld = p->max_len + 2; j.Lc = p->max_len + 2; j.Ls_cap = Ls_cap;
   j.inv_T = inv_T; j.top_k = top_k; j.top_p = top_p; j.prompted = call.c.prompted; j.masked = top_k > 0 || call.c.prompted;
-  const size_t MC = (size_t)j.MC, kv_row = (size_t)Ld * 2 * d;
+  const size_t MC = (size_t)j.MC;
   Needs need{st};
-  need(s->tok_src, (size_t)C * Ls_cap * 4); need(s->valid_new, (size_t)C * Ls_cap); need(s->src_valid, (size_t)C * Ls_cap);
-  need(s->memory, (size_t)C * Ls_cap * d * 4); need(s->memkv_new, (size_t)C * Ls_cap * kv_row * 4); need(s->memkv, (size_t)C * Ls_cap * kv_row * 4);
+  need_source_slots(s, need, C, Ls_cap);
   need(s->bp_enc_qkv, (size_t)C * Ls_cap * 3 * d * 4);      // admissions must not touch the step's Q/K/V rows (k_tree_cache reads them)
   need(s->drafts, MC * 4);
   need(s->gen, MC * j.ld * 4); need(s->front, MC * 4); need(s->act_idx, MC * 4);
@@ -4255,15 +4257,8 @@ static int sbsp_start(SbsPoolJob& j, ttx_session* s, hipStream_t st, int C, int 
   need_step_workspaces(s, need, MC, (size_t)C * Ls_cap);
   s->graphs_current();
   TTX_TRY(need.rc);
-  if (!s->bp_host) {
-    if (hipHostMalloc((void**)&s->bp_host, sizeof(BeamPoolHost), hipHostMallocMapped) != hipSuccess)
-      return fail(TTX_ERR_NOMEM, "hipHostMalloc failed");
-  }
-  std::memset(s->bp_host, 0, sizeof(BeamPoolHost));
   BeamPoolHost* dev_host = nullptr;
-  HIP_TRY(hipHostGetDevicePointer((void**)&dev_host, (void*)s->bp_host, 0));
-  s->ev_used = 0;
-  HIP_TRY(hipEventRecord(s->ev_a, st));
+  TTX_TRY(pool_host_begin(s, st, &dev_host));
   HIP_TRY(hipMemcpyAsync(s->sbp_len.p, call.h_len, (size_t)S * 4, hipMemcpyHostToDevice, st));
   SbsPoolArgs& a = j.a;
   a.C = C; a.K = K; a.max_len = p->max_len; a.ld = j.ld; a.Ls_cap = Ls_cap; a.pad = p->pad_token; a.bos = p->bos_token;
@@ -4290,7 +4285,7 @@ static int sbsp_start(SbsPoolJob& j, ttx_session* s, hipStream_t st, int C, int 
   sa.pfx = t.pfx;
   TTX_TRY(launch_sbsp_init(st, a, s->sbs_g.as<float>(), s->sbs_g_next.as<float>(), s->t_src_of.as<int>()));
   HIP_TRY(hipEventRecord(s->ev_b, st));
-  j.phase = 1;
+  j.pool.phase = 1;
   return TTX_OK;
 }
 
@@ -4306,7 +4301,6 @@ static int sbsp_admit(SbsPoolJob& j, const int64_t* d_src_rows, int ld_src, int 
   f.memkv = s->memkv.as<float>(); f.memkv_new = s->memkv_new.as<float>(); f.kv_row = s->m->cfg.num_decoder_layers * 2 * s->m->cfg.embedding_dim;
   TTX_TRY(launch_sbsp_admit(st, f.a, s->bp_new_slot.as<int>(), R, first_row));
   TTX_TRY(launch_sbsp_fill(st, f));
-  j.admitted_since += R;
   j.src_tokens_padded += (long long)R * Ls_new;
   return TTX_OK;
 }
@@ -4340,9 +4334,8 @@ static int sbsp_launch_iter(SbsPoolJob& j, int n_running) {
   const GraphKey key{GS_SBS_POOL_ITER, j.C, j.Ls_cap, j.K, j.p.max_len, j.cur, variant, j.p.pad_token, j.p.bos_token, j.p.eos_token,
                      j.masked ? 1 : 0, j.prompted ? 1 : 0, j.top_k, top_p_bits, inv_T_bits, (int)(unsigned)j.p.seed, (int)(unsigned)(j.p.seed >> 32)};
   TTX_TRY(graph_replay(s, j.st, s->iter_graphs, key, [&]() -> int { return sbsp_enqueue_iter(j, variant); }));
-  ++j.launched;
+  ++j.pool.launched;
   j.cur ^= 1;
-  j.admitted_since = 0;
   return TTX_OK;
 }
 
@@ -4382,9 +4375,10 @@ extern "C" int ttx_sbs_generate_pool(ttx_session** sessions, int n_sessions, con
   const int n_jobs = shape.n_jobs, C = shape.C;
   std::vector<int> first(S_total + 1);
   for (int r = 0; r <= S_total; ++r) first[r] = r;
+  PoolList list = pool_list(first.data(), S_total, n_jobs);
   std::vector<SbsPoolJob> jobs(n_jobs);
   const bool serial = sessions[0]->profile;                    // profiling sessions: one pool after another (see the greedy pool)
-  int cursor = 0;
+  const long long max_launches = (long long)p->max_len * (S_total + 1);
   ttx_sbs_pool_stats acc{};
   acc.d_src_running_rows = call.d_src_running;
   const auto start = [&](int i) -> int {
@@ -4393,29 +4387,23 @@ extern "C" int ttx_sbs_generate_pool(ttx_session** sessions, int n_sessions, con
   const auto turn = [&](int i) -> int {
     SbsPoolJob& j = jobs[i];
     ttx_session* s = j.s;
-    volatile BeamPoolHost* bh = s->bp_host;
-    if (j.phase == 1) {
-      if (j.launched > 0 && bh->steps_done < j.launched) return TURN_WAITING;       // the iteration in flight has not published yet
-      if (bh->error) return fail(TTX_ERR_HIP, "stochastic beam pool bookkeeping failed (admitted more sources than free slots)");
-      int n_live = (j.launched == 0 ? 0 : bh->n_live) + j.admitted_since;
-      int n_running = (j.launched == 0 ? 0 : bh->n_running) + j.admitted_since;
-      if (serial && j.quota_end < 0) j.quota_end = serial_quota(first.data(), S_total, cursor, i, n_jobs);
-      int n_run_jobs = 0;
-      for (const SbsPoolJob& o : jobs) n_run_jobs += (o.phase == 1);
-      const int take = plan_admission(first.data(), S_total, C, {cursor, C - n_live, n_live, j.launched == 0, i, n_jobs, n_run_jobs, serial, j.quota_end});
-      if (take > 0) {
-        TTX_TRY(sbsp_admit(j, d_src + (size_t)cursor * Ls_all, Ls_all, take, chunk_width(h_len, cursor, cursor + take), cursor));
-        cursor += take;
-        n_live += take;
-        n_running += take;
-      }
-      if (n_live == 0) {
-        TTX_TRY(enqueue_readback(s, j.st, s->bs_cnt.p, sizeof(BeamCounters)));
-        j.phase = 2;
-      } else {
-        if (j.launched > (long long)p->max_len * (S_total + 1)) return fail(TTX_ERR_HIP, "stochastic beam pool failed to terminate");
-        j.live_slots += n_live;
-        TTX_TRY(sbsp_launch_iter(j, n_running));
+    if (j.pool.phase == 1) {
+      const PoolPlan plan = pool_step(j.pool, list, pool_look(s->bp_host, j.pool.launched), i, C, serial, max_launches);
+      switch (plan.act) {
+        case PoolPlan::WAIT: return TURN_WAITING;
+        case PoolPlan::FAILED: return fail(TTX_ERR_HIP, "stochastic beam pool bookkeeping failed (admitted more sources than free slots)");
+        case PoolPlan::STUCK: return fail(TTX_ERR_HIP, "stochastic beam pool failed to terminate");
+        case PoolPlan::DRAIN:
+          TTX_TRY(enqueue_readback(s, j.st, s->bs_cnt.p, sizeof(BeamCounters)));
+          j.pool.phase = 2;
+          break;
+        case PoolPlan::LAUNCH:
+          if (plan.n_take > 0)
+            TTX_TRY(sbsp_admit(j, d_src + (size_t)plan.first_row * Ls_all, Ls_all, plan.rows,
+                               chunk_width(h_len, plan.first_row, plan.first_row + plan.rows), plan.first_row));
+          j.live_slots += plan.n_live;
+          TTX_TRY(sbsp_launch_iter(j, plan.n_running));
+          break;
       }
       return TURN_PROGRESSED;
     }
@@ -4423,10 +4411,8 @@ extern "C" int ttx_sbs_generate_pool(ttx_session** sessions, int n_sessions, con
     const BeamCounters* cn = reinterpret_cast<const BeamCounters*>(s->host_state);
     acc.model_calls += cn->model_calls; acc.running_rows += cn->running_cands; acc.src_tokens_padded += j.src_tokens_padded;
     acc.live_slots += j.live_slots;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev_a, s->ev_c) == hipSuccess) acc.decode_ms += ms;
-    collect_gemm_profile(s, j.st);
-    j.phase = 3;
+    pool_finish(s, j.st, &acc.decode_ms);
+    j.pool.phase = 3;
     return TURN_FINISHED;
   };
   acc.status = drive_sessions(sessions, n_jobs, serial, stream, start, turn);
